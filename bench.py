@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- encode throughput of the FELICS GPU path on synthetic 4K 8-bit grayscale frames.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 A "step" is one pass of the whole encode path (felics_compress_batch_device) over one batch of
@@ -10,10 +10,22 @@ streams end up in HBM too.  Frames are independent streams, so ranks shard them 
 collective (weak scaling: every rank encodes its own FRAMES frames); torch.distributed is used for
 the barrier and the max-over-ranks time only.
 
-Rank 0 prints one JSON line: MPix/s over all ranks, the HBM-read roofline of the dominant kernel
-(HIP events on the library's own stream, averaged over the timed steps) and the CPU baseline (the
-oracle -- a C port of the reference algorithm, the Rust reference cannot be built here -- timed on a
-bounded sample of the same frames on this box's host cores).
+Rank 0 prints one JSON line: MPix/s over all ranks and the HBM-read roofline of the dominant kernel
+(HIP events on the library's own stream, averaged over the timed steps).  A plain run does only
+that: set up, warm up, time the K steps, write the outputs (--dump-outputs) and print the line.
+--full adds everything else the line can hold: the oracle comparison before the timed steps and the
+digest check after them, the blocking-call steps, configs 2 / 4 / 5's share, the host-buffer and
+16-bit legs, the decode legs and the CPU baseline (the oracle -- a C port of the reference
+algorithm, the Rust reference cannot be built here -- timed on a bounded sample of the same frames
+on the host cores).
+
+--dump-outputs DIR writes what the last timed step handed its caller, as float arrays (rank 0's):
+DIR/offsets.npy and DIR/lens.npy (float64, one per stream), DIR/stream0_head.npy (the first stream's
+leading bytes, at most 4 MiB of them, float32), DIR/stream_sample.npy (float32, [streams, n]: the
+bytes at a fixed, seeded set of relative positions of every stream) and DIR/stream_digest_words.npy
+(float64, [streams, 4]: every stream's 16-byte blake2b digest as four 32-bit words, which covers the
+bytes the sample leaves out).  The frames are synthetic and seeded: the same arguments give the same
+inputs from run to run, so two builds can be compared output for output.
 """
 import argparse
 import hashlib
@@ -48,17 +60,23 @@ def parse():
     ap.add_argument("--depth16", action="store_true", help="16-bit grayscale frames (side measurement, not the headline)")
     ap.add_argument("--width", type=int, default=W4K)
     ap.add_argument("--height", type=int, default=H4K)
-    ap.add_argument("--cpu-seconds", type=float, default=12.0, help="budget of the CPU baseline leg (0 = skip)")
-    ap.add_argument("--check-frames", type=int, default=2, help="frames byte-compared with the oracle before timing")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: oracle and digest checks, blocking-call steps, side configs, decode legs, CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed to DIR/<name>.npy (float32 / float64, a seeded sample of the streams)")
+    ap.add_argument("--cpu-seconds", type=float, default=12.0, help="budget of the CPU baseline leg of a --full run (0 = skip)")
+    ap.add_argument("--check-frames", type=int, default=2, help="frames byte-compared with the oracle before timing (--full)")
     ap.add_argument("--synchronous", action="store_true", help="time the blocking entry point (one batch at a time)")
     ap.add_argument("--no-blocking-extra", action="store_true",
-                    help="skip the three extra blocking-call steps after the timed region (rocprofv3 runs: keeps the kernel averages those of the timed steps)")
-    ap.add_argument("--no-side-configs", action="store_true", help="skip the short config 2 / config 4 legs of the default run")
+                    help="skip the three extra blocking-call steps after the timed region of a --full run (rocprofv3 runs: keeps the kernel averages those of the timed steps)")
+    ap.add_argument("--no-side-configs", action="store_true", help="skip the short config 2 / config 4 legs of a --full run")
     ap.add_argument("--no-stage-timing", action="store_true", help="leave the library's per-launch event timing off during the timed steps (roofline is then null)")
-    ap.add_argument("--no-decode-leg", action="store_true", help="skip the decode measurement (GPU decoder next to the host decoder) of the default run")
+    ap.add_argument("--no-decode-leg", action="store_true", help="skip the decode measurement (GPU decoder next to the host decoder) of a --full run")
     ap.add_argument("--lanes", type=int, default=None, help="submissions in flight (sets FELICS_LANES; default: the library's 2, and 4 with --depth16, "
                     "whose kernels wait for memory more than for the ALUs: 3.95 against 4.36 ms per 16 frames)")
     args = ap.parse_args()
+    if args.dump_outputs is not None and args.steps < 1:
+        ap.error("--dump-outputs needs at least one timed step")
     if args.lanes is None and args.depth16 and "FELICS_LANES" not in os.environ:
         args.lanes = 4
     if args.lanes is not None:
@@ -118,6 +136,32 @@ def cpu_baseline(frames_np, budget_s):
     return single, multi
 
 
+DUMP_HEAD_BYTES = 1 << 22    # leading bytes of the first stream written in full
+DUMP_SAMPLE_BYTES = 1 << 22  # sampled bytes over all streams
+DUMP_SEED = 20261016
+
+
+def dump_outputs(out_dir, buf, offs, lens):
+    """What the last timed step handed its caller (offsets, lengths, the streams in `buf`) as DIR/<name>.npy, float32 /
+    float64 only, about 32 MB at most: offsets, lengths, the first stream's head, the bytes at fixed seeded relative
+    positions of every stream, and every stream's blake2b digest as four 32-bit words."""
+    import numpy as np
+
+    n = len(lens)
+    host = buf[: int(offs[-1] + lens[-1])].cpu().numpy()
+    streams = [host[int(offs[i]): int(offs[i] + lens[i])] for i in range(n)]
+    per = max(1, min(65536, DUMP_SAMPLE_BYTES // n))
+    rel = np.sort(np.random.default_rng(DUMP_SEED).random(per))  # the same relative positions in every stream, every run
+    sample = np.stack([s[np.minimum((rel * len(s)).astype(np.int64), len(s) - 1)] for s in streams])
+    digests = np.stack([np.frombuffer(hashlib.blake2b(s.tobytes(), digest_size=16).digest(), dtype="<u4") for s in streams])
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {"offsets": offs.astype(np.float64), "lens": lens.astype(np.float64),
+              "stream0_head": streams[0][:DUMP_HEAD_BYTES].astype(np.float32),
+              "stream_sample": sample.astype(np.float32), "stream_digest_words": digests.astype(np.float64)}
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 def main():
     args = parse()
     if args.gpus < 1:
@@ -175,25 +219,27 @@ def main():
         o = d_outs[i % depth_q]
         return enc.submit_batch_device(frames.data_ptr(), F, W, H, color, depth, o.data_ptr(), o.numel())
 
-    # ---- parity first: byte-compare a few streams with the oracle, checksum the rest ----
+    # ---- first call (sizes the workspace; untimed); with --full, parity: byte-compare a few streams with the oracle,
+    # checksum the rest ----
     offs, lens = step()
-    host = d_out[: int(offs[-1] + lens[-1])].cpu().numpy()
-    from tests import oracle_lib
-
-    oracle = oracle_lib.load()
     checked = 0
-    for i in range(min(args.check_frames, F)):
-        want = oracle.compress(frames[i].cpu().numpy().view(np.uint16) if args.depth16 else frames[i].cpu().numpy())
-        got = host[int(offs[i]): int(offs[i] + lens[i])].tobytes()
-        if got != want:
-            raise SystemExit("rank %d frame %d: GPU stream differs from the oracle" % (rank, i))
-        checked += 1
+    if args.full:
+        host = d_out[: int(offs[-1] + lens[-1])].cpu().numpy()
+        from tests import oracle_lib
+
+        oracle = oracle_lib.load()
+        for i in range(min(args.check_frames, F)):
+            want = oracle.compress(frames[i].cpu().numpy().view(np.uint16) if args.depth16 else frames[i].cpu().numpy())
+            got = host[int(offs[i]): int(offs[i] + lens[i])].tobytes()
+            if got != want:
+                raise SystemExit("rank %d frame %d: GPU stream differs from the oracle" % (rank, i))
+            checked += 1
 
     def stream_digests(buf):  # one digest per stream, in order: a reordered or shifted stream cannot pass
         h = buf[: int(offs[-1] + lens[-1])].cpu().numpy()
         return [hashlib.blake2b(h[int(offs[i]): int(offs[i] + lens[i])].tobytes(), digest_size=16).hexdigest() for i in range(F)]
 
-    ref_digests = stream_digests(d_out)
+    ref_digests = stream_digests(d_out) if args.full else None
     total_bytes = int(lens.sum())
 
     for _ in range(args.warmup):
@@ -207,10 +253,11 @@ def main():
     spans = []  # per timed step: HIP-event span from the step's first kernel to its last byte
 
     def finish(sub):  # felics_wait_batch: the batch is complete in HBM when this returns
-        enc.wait_batch(sub)
+        res = enc.wait_batch(sub)
         for k, v in enc.stage_ms().items():
             stage_acc[k] = stage_acc.get(k, 0.0) + v
         spans.append(enc.span_ms())
+        return res
 
     # The K timed steps go through the two-deep submission queue a streaming caller would use: step i + 1 is
     # queued before step i is waited for, so the GPU classifies / scatters the next batch while it packs the
@@ -219,10 +266,11 @@ def main():
     stats_before = enc.stats()
     group.barrier()
     torch.cuda.synchronize()
+    last = None  # (offsets, lens) of the last timed step
     t0 = time.perf_counter()
     if args.synchronous:
         for _ in range(args.steps):
-            step()
+            last = step()
             for k, v in enc.stage_ms().items():
                 stage_acc[k] = stage_acc.get(k, 0.0) + v
             spans.append(enc.span_ms())
@@ -230,12 +278,12 @@ def main():
         inflight = []
         for i in range(args.steps):
             if len(inflight) == depth_q:
-                finish(inflight.pop(0))
+                last = finish(inflight.pop(0))
             ts = time.perf_counter()
             inflight.append(submit(i))
             host_submit_s += time.perf_counter() - ts
         while inflight:
-            finish(inflight.pop(0))
+            last = finish(inflight.pop(0))
     torch.cuda.synchronize()
     group.barrier()
     elapsed = time.perf_counter() - t0
@@ -249,13 +297,18 @@ def main():
                                      "frames": F, "first_frame": first_frame})
     elapsed = group.max_over_ranks(elapsed)
 
+    # what the last timed step computed, before anything below writes to the output buffers again
+    if args.dump_outputs is not None and rank == 0:
+        dump_outputs(args.dump_outputs, d_out if args.synchronous else d_outs[(args.steps - 1) % depth_q], *last)
+
     # the timed steps must have produced the same bytes as the checked one (both output buffers)
-    for o in (d_outs[: max(1, min(depth_q, args.steps))] if not args.synchronous else d_outs[:1]):
-        if stream_digests(o) != ref_digests:
-            raise SystemExit("rank %d: output changed between steps" % rank)
+    if args.full:
+        for o in (d_outs[: max(1, min(depth_q, args.steps))] if not args.synchronous else d_outs[:1]):
+            if stream_digests(o) != ref_digests:
+                raise SystemExit("rank %d: output changed between steps" % rank)
     # for the record: a few steps through the blocking entry point (one batch at a time)
     sync_ms = None
-    if not args.synchronous and not args.no_blocking_extra and rank == 0:
+    if args.full and not args.synchronous and not args.no_blocking_extra and rank == 0:
         torch.cuda.synchronize()
         t1 = time.perf_counter()
         for _ in range(3):
@@ -265,7 +318,7 @@ def main():
     # Configs 2 and 4 (one 4K gray8 / RGB8 frame per call) ride along with the default run so that they are
     # driver-timed too: a short stream of single-frame submissions through the queue, and blocking calls.
     side = None
-    if rank == 0 and args.config == 3 and not args.no_side_configs and not args.depth16 and not args.rgb and (W, H) == (W4K, H4K):
+    if args.full and rank == 0 and args.config == 3 and not args.no_side_configs and not args.depth16 and not args.rgb and (W, H) == (W4K, H4K):
         side = {}
         for name, rgbf in (("config2_one_4k_gray8_frame", False), ("config4_one_4k_rgb8_frame", True)):
             fr = (synth_torch.rgb8(W, H, 0, device=dev) if rgbf else frames[0]).contiguous()
@@ -402,7 +455,7 @@ def main():
     # Decode, for the record: the batch's streams through the GPU decoder (one wave per stream: the
     # format is bit-serial per stream) and a sample of them through the host decoder on this box's cores.
     decode = None
-    if rank == 0 and args.config == 3 and not args.no_decode_leg and not args.depth16 and not args.rgb:
+    if args.full and rank == 0 and args.config == 3 and not args.no_decode_leg and not args.depth16 and not args.rgb:
         from concurrent.futures import ThreadPoolExecutor
 
         from felics_amd import api as fapi2
@@ -594,7 +647,7 @@ def main():
                                        "achieved_GBs": None if k in ("zero", "offsets") else round(alg_bytes / n / (v / n * 1e-3) / 1e9, 2)}
         pipeline_gbs = alg_bytes / (ms_per_step * 1e-3) / 1e9
         cpu1 = cpum = None
-        if args.cpu_seconds > 0:
+        if args.full and args.cpu_seconds > 0:
             sample = [frames[i].cpu().numpy().view(np.uint16) if args.depth16 else frames[i].cpu().numpy()
                       for i in range(min(F, 16))]
             cpu1, cpum = cpu_baseline(sample, args.cpu_seconds)
@@ -633,7 +686,8 @@ def main():
                          "batches_redone_in_timed_steps": redone,
                          "note": "the stages follow each other slice by slice on HIP streams of their own; launches overlap, so the sums exceed ms_per_step"},
             "per_rank": per_rank,
-            "parity": {"frames_byte_compared_with_oracle": checked, "streams_digest_checked_after_timed_steps": F,
+            "full": args.full,
+            "parity": {"frames_byte_compared_with_oracle": checked, "streams_digest_checked_after_timed_steps": F if args.full else 0,
                        "compressed_bytes_per_step_rank0": total_bytes,
                        "bits_per_pixel": round(total_bytes * 8 / (F * npix), 4)},
         }

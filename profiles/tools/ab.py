@@ -25,7 +25,7 @@ def run(name, env_extra, bench_args, serial):
     if serial:
         env.update({"FELICS_SERIAL": "1", "FELICS_SLICES": "1"})
         args += ["--synchronous"]
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--cpu-seconds", "0", "--no-side-configs", "--no-decode-leg"] + args,
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--cpu-seconds", "0", "--no-side-configs", "--no-decode-leg"] + args,
                        env=env, capture_output=True, text=True)
     if p.returncode != 0:
         return {"error": (p.stderr or p.stdout).strip().splitlines()[-1:]}

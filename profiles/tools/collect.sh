@@ -1,6 +1,6 @@
 #!/bin/bash
 # Runs ON THE GPU BOX from the repository root:  bash profiles/tools/collect.sh <tag>
-# 1. the default bench line (cpu_baseline, side configs, decode leg)      -> gpurun_out/<tag>/bench.json
+# 1. the --full bench line (cpu_baseline, side configs, decode leg)       -> <tag>/bench.json
 # 2. rocprofv3 --kernel-trace --stats of `bench.py --steps 10 --warmup 0 --no-blocking-extra` (timed steps through the
 #    submission queue, as in 1.)                                           -> gpurun_out/<tag>/kernel_stats.csv
 # 3. rocprofv3 --pmc FETCH_SIZE, --pmc WRITE_SIZE, --pmc SQ_INSTS_VALU SQ_INSTS_SALU SQ_WAVE_CYCLES SQ_WAIT_ANY ..., --pmc SQ_INSTS_LDS
@@ -15,7 +15,7 @@ O=$R/gpurun_out/$tag
 mkdir -p "$O"
 export TMPDIR=/tmp
 echo "[collect] bench line"
-timeout -k 10 400 python3 bench.py > "$O/bench.json" 2> "$O/bench.err" || { tail -5 "$O/bench.err"; exit 1; }
+timeout -k 10 400 python3 bench.py --full > "$O/bench.json" 2> "$O/bench.err" || { tail -5 "$O/bench.err"; exit 1; }
 cd /tmp
 # (The counter passes run blocking steps, the headline goes through the submission queue: the same kernels on the same data.)
 PMC_ARGS="--steps 1 --warmup 0 --synchronous --no-blocking-extra --no-side-configs --no-decode-leg --cpu-seconds 0"
