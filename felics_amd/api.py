@@ -65,6 +65,10 @@ class _CStats(C.Structure):
                 ("tile_overflows", C.c_uint64)]
 
 
+class _CImage(C.Structure):  # felics_image
+    _fields_ = [("pixels", C.c_void_p), ("width", C.c_uint32), ("height", C.c_uint32), ("color", C.c_int), ("depth", C.c_int)]
+
+
 class Header:  # format.rs:44-49
     def __init__(self, color_type, pixel_depth, width, height):
         self.color_type = ColorType(color_type)
@@ -87,6 +91,7 @@ EXPORTS = [
     "felics_decompress", "felics_strerror", "felics_last_error", "felics_set_profiling",
     "felics_stage_count", "felics_stage_name", "felics_get_stage_ms", "felics_get_stage_launches",
     "felics_lane_count", "felics_ctx_lane_count", "felics_get_span_ms", "felics_decompress_with_header", "felics_get_stats", "felics_decompress_batch_device",
+    "felics_compress_images", "felics_compress_images_device",
 ]
 
 _lib = None
@@ -139,6 +144,8 @@ def lib():
     L.felics_decompress.argtypes = [vp, sz, vp, sz, C.POINTER(_CHeader)]
     L.felics_decompress_with_header.argtypes = [vp, sz, C.POINTER(_CHeader), vp, sz]
     L.felics_get_stats.argtypes = [vp, C.POINTER(_CStats)]
+    L.felics_compress_images.argtypes = [vp, sz, C.POINTER(_CImage), C.POINTER(vp), C.POINTER(sz), C.POINTER(sz)]
+    L.felics_compress_images_device.argtypes = [vp, sz, C.POINTER(_CImage), vp, sz, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
     L.felics_decompress_batch_device.argtypes = [vp, sz, vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), vp, sz,
                                                  C.POINTER(_CHeader), C.POINTER(C.c_int)]
     L.felics_strerror.argtypes = [C.c_int]
@@ -236,6 +243,45 @@ class Encoder:
             if rc != 0:
                 self._raise(rc)
             return [outs[i][: lens[i]].tobytes() for i in range(n)]
+
+    def compress_images(self, images):
+        """Files of a list of images of any shapes and types, in one call (felics_compress_images)."""
+        if not images:
+            return []
+        descr = [_describe(im) for im in images]
+        n = len(descr)
+        imgs = (_CImage * n)(*[_CImage(d[0].ctypes.data if d[0].size else None, d[1], d[2], int(d[3]), int(d[4])) for d in descr])
+        caps = [14 + 8 * 3 + d[0].nbytes + d[0].nbytes // 2 + 64 for d in descr]
+        while True:
+            outs = [np.empty(c, dtype=np.uint8) for c in caps]
+            op = (C.c_void_p * n)(*[o.ctypes.data for o in outs])
+            cp = (C.c_size_t * n)(*caps)
+            lens = (C.c_size_t * n)()
+            rc = lib().felics_compress_images(self._h, n, imgs, op, cp, lens)
+            if rc == -8:  # grow to the sizes the library reported and submit again
+                grown = [max(c, int(l)) for c, l in zip(caps, lens)]
+                if grown == caps:
+                    self._raise(rc)
+                caps = grown
+                continue
+            if rc != 0:
+                self._raise(rc)
+            return [outs[i][: lens[i]].tobytes() for i in range(n)]
+
+    def compress_images_device(self, descs, d_out, d_out_cap):
+        """felics_compress_images_device: descs = [(device pointer, w, h, color, depth), ...], streams into d_out (device).
+        Returns (offsets, lens) numpy arrays."""
+        n = len(descs)
+        imgs = (_CImage * max(n, 1))(*[_CImage(int(p) if p else None, int(w), int(h), int(c), int(d)) for p, w, h, c, d in descs])
+        offs = np.zeros(max(n, 1), dtype=np.uint64)
+        lens = np.zeros(max(n, 1), dtype=np.uint64)
+        rc = lib().felics_compress_images_device(self._h, n, imgs, d_out, d_out_cap, offs.ctypes.data_as(C.POINTER(C.c_uint64)),
+                                                 lens.ctypes.data_as(C.POINTER(C.c_uint64)))
+        if rc == -8:
+            raise FelicsError(rc, "need %d bytes" % int(lens[0]))
+        if rc != 0:
+            self._raise(rc)
+        return offs[:n], lens[:n]
 
     def compress_batch_host(self, pixel_ptrs, n, w, h, color, depth, out_ptrs, caps):
         """felics_compress_batch on raw HOST pointers (lists of n addresses: frames in, buffers of caps[i] bytes out): the

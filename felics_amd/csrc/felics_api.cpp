@@ -11,6 +11,7 @@
 #include <thread>
 #include <type_traits>
 #include <string>
+#include <algorithm>
 #include <new>
 #include <vector>
 
@@ -86,6 +87,10 @@ struct Lane {
     Geometry g;
     size_t first_image = 0;
     const void *d_planes = nullptr;
+    // a mixed sub-batch (felics_compress_images*): its plane table, written on the host (pinned) and copied to the device
+    DevBuf mtable;
+    PlaneGeom *h_table = nullptr;
+    size_t h_table_cap = 0;
 };
 
 }  // namespace
@@ -139,6 +144,8 @@ struct felics_ctx {
     hipStream_t copy_in = nullptr, copy_out = nullptr;  // felics_compress_batch: frames to the device / streams back, beside the kernels
     std::vector<hipEvent_t> h2d_done;                   // a chunk's frames have arrived (one per chunk of a host-buffer batch; grown on demand)
     hipEvent_t wait_before_submit = nullptr;            // the next sub-batch's first kernel waits for this event (set around one submit)
+    DevBuf mix_in, mix_stage, mix_out, mix_redo;  // felics_compress_images*: 16-bit frames gathered per shape and their streams, the first
+                                                  // run of a call whose buffer cannot hold the slots, frames gathered for a remedy
     DevBuf own;      // encode_device's own output when the caller gives none (the host entry point's fall-back for a chunk whose streams outgrew their slots)
     DevBuf dec_meta, dec_planes;  // GPU decoder: offsets | lens | status of a batch; Y / Co / Cg planes of RGB streams
     DevBuf dec_lane_table;        // gray streams decoded 64 to a wave: the estimator rows that do not fit in LDS (3 KB per stream, zeroed per call)
@@ -299,7 +306,7 @@ int run_lane(felics_ctx *ctx, Lane &l, uint8_t *d_out, uint64_t slot_stride) {
     // tiles are handed out by ticket: the tiles of two of them waiting for each other's queued predecessors could hold all
     // workgroup slots, so the lanes share the tail stream).  Otherwise (exact placement, FELICS_TWO_PASS, after a look-back gave
     // up twice): k to a byte per pixel once every chain is replayed, then the lengths / bit scan / pack kernels over all tiles.
-    const bool fused = slot_stride != 0 && !ctx->two_pass;
+    const bool fused = (slot_stride != 0 || g.mixed != nullptr) && !ctx->two_pass;  // (a mixed sub-batch: slots from its table, never two-pass)
     const uint32_t cap = ctx->cap_max ? tile_cap_max(g.nctx, g.npix) : ctx->test_tile_cap ? std::min(4u * REC, tile_cap_max(g.nctx, g.npix)) : tile_cap_default(g.nctx, g.npix);
     const size_t ptiles = (size_t)g.nplanes * g.sort_tiles;
     const size_t slots = ptiles * cap, recs = slots / REC;
@@ -623,6 +630,7 @@ int launch_sub_batch(felics_ctx *ctx, Lane &l, size_t first, size_t cnt, const v
     const size_t frame_bytes = (size_t)npix * planes * (wide ? 2 : 1);
     int rc;
     Geometry &g = l.g;
+    g.mixed = nullptr;
     g.W = w;
     g.H = h;
     g.npix = (uint32_t)npix;
@@ -868,6 +876,389 @@ bool any_pending(const felics_ctx *ctx) {
     return false;
 }
 
+// ---- mixed shapes (felics_compress_images*) ------------------------------------------------------------------------------
+// 8-bit images go in BUCKETS of similar size: sorted by sort tiles T = ceil(w h / SORT_TILE), a bucket holds T_min .. ceil(1.25 T_min)
+// (at most 25 % of a bucket's tiles are padding), and a bucket is one sub-batch whose tile count is uniform at its T_max; what
+// differs per plane (samples, W, H, npix, the image's slot) comes from a table (Geometry::mixed).  16-bit images go through the
+// uniform path, one group per shape.  The sub-batches are queued over the lanes like felics_compress_batch's chunks.
+
+constexpr size_t MIX_MAX_IMAGES = 8192;  // images of one mixed sub-batch (k_concat_planes / k_rgb8_to_planes_mixed: one grid row per image)
+
+struct MixImage {
+    const uint8_t *px;  // device
+    uint32_t w, h;
+    int color, depth;
+    uint64_t npix;
+    uint32_t planes;
+    size_t frame_bytes;
+};
+
+MixImage mix_image(const felics_image &im) {
+    MixImage m;
+    m.px = (const uint8_t *)im.pixels;
+    m.w = im.width;
+    m.h = im.height;
+    m.color = im.color;
+    m.depth = im.depth;
+    m.npix = (uint64_t)im.width * im.height;
+    m.planes = im.color == FELICS_COLOR_RGB ? 3 : 1;
+    m.frame_bytes = (size_t)(m.npix * m.planes * (im.depth == FELICS_DEPTH_16 ? 2 : 1));
+    return m;
+}
+
+// every image checked before anything is launched: the first error in image order
+int check_images(size_t n, const felics_image *images) {
+    for (size_t i = 0; i < n; i++) {
+        const felics_image &im = images[i];
+        int rc = check_args(im.width, im.height, im.color, im.depth);
+        if (rc) return rc;
+        const MixImage m = mix_image(im);
+        if (!im.pixels && m.npix) return FELICS_E_INVALID_ARGUMENT;
+        if (m.npix * m.planes >= 0xE0000000ull) return FELICS_E_UNSUPPORTED;
+        if (m.depth == FELICS_DEPTH_16 && m.npix > WIDE_MAX_PLANE_PIXELS) return FELICS_E_UNSUPPORTED;
+    }
+    return FELICS_OK;
+}
+
+// a stream's slot, as encode_device sizes one
+uint64_t mix_slot(size_t frame_bytes) { return ((uint64_t)frame_bytes + frame_bytes / 4 + 64 + 15) & ~15ull; }
+uint32_t sort_tiles_of(uint64_t npix) { return (uint32_t)((npix + SORT_TILE - 1) / SORT_TILE); }
+
+struct MixJob {
+    bool wide = false;          // a 16-bit group of one shape (uniform path), else a mixed 8-bit sub-batch
+    std::vector<size_t> idx;    // its images
+    int lane = -1;
+    size_t in_off = 0, stage_off = 0;  // 16-bit: where its frames are gathered (mix_in) and its streams land (mix_stage)
+    uint64_t slot = 0;                 // 16-bit: the group's slot in mix_stage
+};
+
+// Where a call's streams go: image i at base + off[i], at most slot[i] bytes.  lens[i] = the size of stream i whether it fit or
+// not; overflow = one did not (the caller places the streams exactly and runs again).
+struct MixOut {
+    uint8_t *base;
+    const uint64_t *off, *slot;
+    uint64_t *lens;
+    bool overflow;
+};
+
+// Queues a mixed 8-bit sub-batch on lane l (see launch_sub_batch).
+int launch_mixed(felics_ctx *ctx, Lane &l, const std::vector<MixImage> &im, const std::vector<size_t> &idx, const MixOut &o, int nslices) {
+    const MixImage &f = im[idx[0]];
+    const uint32_t planes = f.planes;
+    const size_t cnt = idx.size();
+    uint32_t tmax = 0;
+    uint64_t max_npix = 0;
+    for (size_t i : idx) {
+        tmax = std::max(tmax, sort_tiles_of(im[i].npix));
+        max_npix = std::max(max_npix, im[i].npix);
+    }
+    l.nslices = std::max(1, std::min(nslices, SLICES));
+    l.queued = true;
+    ctx->stats.submissions++;
+    for (int i = 0; i < ST_COUNT; i++) l.ev_used[i] = 0;
+    Geometry &g = l.g;
+    g.W = SORT_TILE;  // (the uniform fields describe the padded planes: T_max tiles of SORT_TILE pixels)
+    g.H = tmax;
+    g.npix = tmax * SORT_TILE;
+    g.nimages = (uint32_t)cnt;
+    g.planes_per_image = planes;
+    g.nplanes = (uint32_t)(cnt * planes);
+    g.sort_tiles = tmax;
+    g.pack_tiles = tmax;
+    g.color = (uint32_t)f.color;
+    g.depth = FELICS_DEPTH_8;
+    g.nctx = planes == 3 ? nctx_of<int16_t>() : nctx_of<uint8_t>();
+    l.first_image = 0;
+    int rc;
+    const uint64_t pstride = g.npix;  // samples between two planes of the planes buffer (RGB)
+    if (planes == 3 && (rc = reserve(ctx, l.planes, (size_t)g.nplanes * pstride * 2 + STAGE_PAD)) != 0) return rc;
+    if (g.nplanes > l.h_table_cap) {
+        if (l.h_table) HIP_TRY(ctx, hipHostFree(l.h_table));
+        l.h_table = nullptr;
+        HIP_TRY(ctx, hipHostMalloc((void **)&l.h_table, (size_t)g.nplanes * sizeof(PlaneGeom), hipHostMallocDefault));
+        l.h_table_cap = g.nplanes;
+    }
+    for (size_t j = 0; j < cnt; j++) {
+        const MixImage &m = im[idx[j]];
+        for (uint32_t c = 0; c < planes; c++) {
+            PlaneGeom &pg = l.h_table[j * planes + c];
+            pg.samples = planes == 3 ? (const void *)((int16_t *)l.planes.p + (j * planes + c) * pstride) : (const void *)m.px;
+            pg.image = m.px;
+            pg.W = m.w;
+            pg.H = m.h;
+            pg.npix = (uint32_t)m.npix;
+            pg.ntiles = (uint32_t)((m.npix + PACK_TILE - 1) / PACK_TILE);
+            pg.out_off = o.off[idx[j]];
+            pg.out_slot = o.slot[idx[j]];
+        }
+    }
+    const size_t tbytes = (size_t)g.nplanes * sizeof(PlaneGeom);
+    if ((rc = reserve(ctx, l.mtable, tbytes)) != 0) return rc;
+    hipStream_t fs = ctx->serial ? l.stream : l.front;
+    if (ctx->profiling) HIP_TRY(ctx, hipEventRecord(l.span_begin, fs));
+    HIP_TRY(ctx, hipMemcpyAsync(l.mtable.p, l.h_table, tbytes, hipMemcpyHostToDevice, fs));
+    g.mixed = (const PlaneGeom *)l.mtable.p;
+    l.d_planes = planes == 3 ? l.planes.p : nullptr;  // (gray: every plane's samples come from the table)
+    if (planes == 3) {
+        StageTimer t(ctx, l, ST_PLANES, fs, true);
+        launch_rgb8_to_planes_mixed(fs, g.mixed, pstride, (uint32_t)max_npix, (uint32_t)cnt);
+    }
+    return planes == 3 ? run_lane<int16_t, uint16_t>(ctx, l, o.base, 0) : run_lane<uint8_t, uint8_t>(ctx, l, o.base, 0);
+}
+
+// The remedy: the images of `idx` once more through encode_device (its whole ladder), one group per shape, frames gathered
+// into one buffer, streams copied into their slots.
+int redo_by_shape(felics_ctx *ctx, Lane &l, const std::vector<MixImage> &im, const std::vector<size_t> &idx, MixOut &o) {
+    std::vector<size_t> rest = idx;
+    int rc;
+    while (!rest.empty()) {
+        const MixImage &f = im[rest[0]];
+        std::vector<size_t> grp, other;
+        for (size_t i : rest) {
+            const MixImage &m = im[i];
+            (m.w == f.w && m.h == f.h && m.color == f.color && m.depth == f.depth ? grp : other).push_back(i);
+        }
+        rest.swap(other);
+        const size_t cnt = grp.size();
+        if ((rc = reserve(ctx, ctx->mix_redo, f.frame_bytes * cnt + 64)) != 0) return rc;
+        for (size_t j = 0; j < cnt && f.frame_bytes; j++)
+            HIP_TRY(ctx, hipMemcpyAsync((uint8_t *)ctx->mix_redo.p + j * f.frame_bytes, im[grp[j]].px, f.frame_bytes, hipMemcpyDeviceToDevice, l.stream));
+        HIP_TRY(ctx, hipStreamSynchronize(l.stream));
+        std::vector<uint64_t> offs(cnt), lens(cnt);
+        uint8_t *used = nullptr;
+        if ((rc = encode_device(ctx, l, cnt, ctx->mix_redo.p, f.w, f.h, f.color, f.depth, nullptr, 0, offs.data(), lens.data(), &used)) != 0)
+            return rc;
+        for (size_t j = 0; j < cnt; j++) {
+            const size_t i = grp[j];
+            o.lens[i] = lens[j];
+            if (lens[j] > o.slot[i]) {
+                o.overflow = true;
+                continue;
+            }
+            HIP_TRY(ctx, hipMemcpyAsync(o.base + o.off[i], used + offs[j], (size_t)lens[j], hipMemcpyDeviceToDevice, l.stream));
+        }
+        HIP_TRY(ctx, hipStreamSynchronize(l.stream));  // (ctx->own is reused by the next group)
+    }
+    return FELICS_OK;
+}
+
+// A job's sub-batch is complete: sizes, its own checks, and the remedy where one is needed.
+int land_job(felics_ctx *ctx, MixJob &j, const std::vector<MixImage> &im, MixOut &o) {
+    Lane &l = ctx->lanes[j.lane];
+    int rc = wait_event(ctx, l.sized, "stream sizes");
+    if (rc) return rc;
+    const size_t cnt = j.idx.size();
+    if (j.wide) {
+        std::vector<uint64_t> offs(cnt), lens(cnt);
+        const SlotOutcome so = read_sizes(ctx, l, true, j.slot, offs.data(), lens.data());
+        uint8_t *from = (uint8_t *)ctx->mix_stage.p + j.stage_off;
+        if ((rc = sync_lane(ctx, l)) != 0) return rc;
+        if (so.overflow) {  // a stream outgrew its slot: the group again with exact placement (encode_device)
+            ctx->stats.slot_overflows++;
+            const MixImage &f = im[j.idx[0]];
+            if ((rc = encode_device(ctx, l, cnt, (uint8_t *)ctx->mix_in.p + j.in_off, f.w, f.h, f.color, f.depth, nullptr, 0, offs.data(),
+                                    lens.data(), &from, true)) != 0)
+                return rc;
+        }
+        for (size_t k = 0; k < cnt; k++) {
+            const size_t i = j.idx[k];
+            o.lens[i] = lens[k];
+            if (lens[k] > o.slot[i]) {
+                o.overflow = true;
+                continue;
+            }
+            HIP_TRY(ctx, hipMemcpyAsync(o.base + o.off[i], from + offs[k], (size_t)lens[k], hipMemcpyDeviceToDevice, l.stream));
+        }
+        HIP_TRY(ctx, hipStreamSynchronize(l.stream));
+        collect_timing(ctx, l);
+        return FELICS_OK;
+    }
+    const uint32_t err = (uint32_t)l.h_sizes[cnt], flags = (uint32_t)(l.h_sizes[cnt] >> 32);
+    SlotOutcome so;
+    so.lookback_failed = (err & 1u) != 0 || (ctx->test_lookback && l.m_fused);
+    so.overflow = (err & 2u) != 0;
+    so.order_violation = (flags & TL_FLAG_ORDER) != 0;
+    so.tile_overflow = (flags & TL_FLAG_OVERFLOW) != 0;
+    so.spine_error = (flags & TL_FLAG_SPINE) != 0;
+    for (size_t k = 0; k < cnt; k++) {  // (the table lists the sub-batch's images in the order of j.idx)
+        const size_t i = j.idx[k];
+        o.lens[i] = l.h_sizes[k];
+        if (l.h_sizes[k] > o.slot[i]) so.overflow = true;
+    }
+    if (!so.redo() && !so.overflow && !so.spine_error) {
+        collect_timing(ctx, l);
+        return FELICS_OK;
+    }
+    if ((rc = sync_lane(ctx, l)) != 0) return rc;
+    if (so.spine_error) return spine_failure(ctx);
+    if (so.order_violation)
+        note_scatter_order_violation(ctx);
+    else if (so.tile_overflow)
+        note_tile_overflow(ctx);
+    else if (so.lookback_failed)
+        note_lookback_failure(ctx, l);
+    else
+        ctx->stats.slot_overflows++;
+    return redo_by_shape(ctx, l, im, j.idx, o);
+}
+
+// Every image of the call into the slots of `o`: zero-sized images on the host path, the jobs queued over the lanes.
+int run_images(felics_ctx *ctx, const std::vector<MixImage> &im, MixOut &o) {
+    const size_t n = im.size();
+    int rc;
+    o.overflow = false;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    std::vector<MixJob> jobs;
+    for (int color : {FELICS_COLOR_GRAY, FELICS_COLOR_RGB}) {  // 8-bit: buckets of similar tile counts
+        std::vector<size_t> v;
+        for (size_t i = 0; i < n; i++)
+            if (im[i].npix && im[i].depth == FELICS_DEPTH_8 && im[i].color == color) v.push_back(i);
+        std::stable_sort(v.begin(), v.end(), [&](size_t a, size_t b) { return sort_tiles_of(im[a].npix) < sort_tiles_of(im[b].npix); });
+        for (size_t a = 0; a < v.size();) {
+            const uint64_t tmin = sort_tiles_of(im[v[a]].npix), lim = (5 * tmin + 3) / 4;  // ceil(1.25 T_min)
+            size_t b = a;
+            while (b < v.size() && sort_tiles_of(im[v[b]].npix) <= lim) b++;
+            const uint32_t planes = color == FELICS_COLOR_RGB ? 3 : 1;
+            const size_t per = std::min(MIX_MAX_IMAGES, max_images_per_pass((uint64_t)sort_tiles_of(im[v[b - 1]].npix) * SORT_TILE, planes, FELICS_DEPTH_8));
+            for (size_t c = a; c < b; c += per) {
+                MixJob j;
+                j.idx.assign(v.begin() + c, v.begin() + std::min(b, c + per));
+                jobs.push_back(std::move(j));
+            }
+            a = b;
+        }
+    }
+    size_t in_total = 0, stage_total = 0;
+    {  // 16-bit: one group per shape, frames gathered back to back
+        std::vector<bool> taken(n, false);
+        for (size_t i = 0; i < n; i++) {
+            if (taken[i] || !im[i].npix || im[i].depth != FELICS_DEPTH_16) continue;
+            std::vector<size_t> grp;
+            for (size_t k = i; k < n; k++)
+                if (!taken[k] && im[k].npix && im[k].depth == FELICS_DEPTH_16 && im[k].w == im[i].w && im[k].h == im[i].h && im[k].color == im[i].color) {
+                    taken[k] = true;
+                    grp.push_back(k);
+                }
+            const size_t per = max_images_per_pass(im[i].npix, im[i].planes, FELICS_DEPTH_16);
+            for (size_t c = 0; c < grp.size(); c += per) {
+                MixJob j;
+                j.wide = true;
+                j.idx.assign(grp.begin() + c, grp.begin() + std::min(grp.size(), c + per));
+                j.slot = mix_slot(im[i].frame_bytes);
+                j.in_off = in_total;
+                j.stage_off = stage_total;
+                in_total += ((im[i].frame_bytes * j.idx.size()) + 255) & ~(size_t)255;
+                stage_total += (size_t)(j.slot * j.idx.size());
+                jobs.push_back(std::move(j));
+            }
+        }
+    }
+    if (in_total && (rc = reserve(ctx, ctx->mix_in, in_total + 64)) != 0) return rc;
+    if (stage_total && (rc = reserve(ctx, ctx->mix_stage, stage_total + 64)) != 0) return rc;
+    for (size_t i = 0; i < n; i++) {  // zero-sized images: header + two zero words per plane, encode_device's host path
+        if (im[i].npix) continue;
+        uint64_t off = 0, len = 0;
+        if ((rc = encode_device(ctx, ctx->lanes[0], 1, nullptr, im[i].w, im[i].h, im[i].color, im[i].depth, o.base + o.off[i], (size_t)o.slot[i], &off,
+                                &len, nullptr)) != 0)
+            return rc;
+        o.lens[i] = len;
+    }
+    const int nslices = jobs.size() > 1 ? ctx->slices_queued : ctx->slices_blocking;
+    std::vector<size_t> flying;  // jobs in flight, oldest first (lanes handed out in turn: the oldest holds the next lane)
+    auto drain = [&](int r) {
+        for (size_t f : flying) {
+            (void)wait_event(ctx, ctx->lanes[jobs[f].lane].sized, "stream sizes");
+            (void)sync_lane(ctx, ctx->lanes[jobs[f].lane]);
+        }
+        return r;
+    };
+    for (size_t q = 0; q < jobs.size(); q++) {
+        if ((int)flying.size() == ctx->nlanes) {
+            rc = land_job(ctx, jobs[flying.front()], im, o);
+            flying.erase(flying.begin());
+            if (rc) return drain(rc);
+        }
+        MixJob &j = jobs[q];
+        if (!j.wide && ctx->two_pass) {  // (the mixed kernels are single-pass: a context on the two-pass kernels takes the uniform path,
+                                         // blocking, once every lane is idle)
+            while (!flying.empty()) {
+                rc = land_job(ctx, jobs[flying.front()], im, o);
+                flying.erase(flying.begin());
+                if (rc) return drain(rc);
+            }
+            if ((rc = redo_by_shape(ctx, ctx->lanes[ctx->next_lane], im, j.idx, o)) != 0) return rc;
+            continue;
+        }
+        j.lane = ctx->next_lane;
+        Lane &l = ctx->lanes[j.lane];
+        ctx->next_lane = (ctx->next_lane + 1) % ctx->nlanes;
+        if (j.wide) {
+            const MixImage &f = im[j.idx[0]];
+            uint8_t *in = (uint8_t *)ctx->mix_in.p + j.in_off;
+            for (size_t k = 0; k < j.idx.size(); k++)
+                if (hipMemcpyAsync(in + k * f.frame_bytes, im[j.idx[k]].px, f.frame_bytes, hipMemcpyDeviceToDevice, l.stream) != hipSuccess)
+                    return drain(hip_fail(ctx, hipGetLastError(), "gathering 16-bit frames"));
+            for (int i = 0; i < ST_COUNT; i++) l.ev_used[i] = 0;
+            rc = launch_sub_batch(ctx, l, 0, j.idx.size(), in, f.w, f.h, f.color, f.depth, (uint8_t *)ctx->mix_stage.p + j.stage_off, j.slot, nslices, true);
+        } else {
+            rc = launch_mixed(ctx, l, im, j.idx, o, nslices);
+        }
+        if (rc) {
+            (void)sync_lane(ctx, l);
+            return drain(rc);
+        }
+        flying.push_back(q);
+    }
+    while (!flying.empty()) {
+        rc = land_job(ctx, jobs[flying.front()], im, o);
+        flying.erase(flying.begin());
+        if (rc) return drain(rc);
+    }
+    return FELICS_OK;
+}
+
+// felics_compress_images_device without the argument checks: slots as encode_device sizes them if d_out holds them, else (or if
+// a stream outgrew its slot) a second run with every stream placed exactly, back to back.
+int images_device(felics_ctx *ctx, const std::vector<MixImage> &im, uint8_t *d_out, size_t d_out_cap, uint64_t *offsets, uint64_t *lens) {
+    const size_t n = im.size();
+    std::vector<uint64_t> off(n), slot(n);
+    uint64_t total = 0;
+    for (size_t i = 0; i < n; i++) {
+        slot[i] = mix_slot(im[i].frame_bytes);
+        off[i] = total;
+        total += slot[i];
+    }
+    MixOut o{d_out, off.data(), slot.data(), lens, false};
+    int rc;
+    if (total > d_out_cap) {  // the sizes first, into a buffer of the library's own
+        if ((rc = reserve(ctx, ctx->mix_out, (size_t)total + 64)) != 0) return rc;
+        o.base = (uint8_t *)ctx->mix_out.p;
+    }
+    if ((rc = run_images(ctx, im, o)) != 0) return rc;
+    if (o.base == d_out && !o.overflow) {
+        for (size_t i = 0; i < n; i++) offsets[i] = off[i];
+        return FELICS_OK;
+    }
+    uint64_t need = 0;
+    for (size_t i = 0; i < n; i++) {
+        off[i] = need;
+        slot[i] = (lens[i] + 15) & ~15ull;
+        need += slot[i];
+    }
+    if (need > d_out_cap) {
+        if (n) lens[0] = need;
+        return FELICS_E_BUFFER_TOO_SMALL;
+    }
+    o = MixOut{d_out, off.data(), slot.data(), lens, false};
+    if ((rc = run_images(ctx, im, o)) != 0) return rc;
+    if (o.overflow) {
+        ctx->err = "internal error: a stream outgrew the exact size it had before";
+        return FELICS_E_HIP;
+    }
+    for (size_t i = 0; i < n; i++) offsets[i] = off[i];
+    return FELICS_OK;
+}
+
 }  // namespace
 
 // --------------------------------------------------------------------------------------------
@@ -964,6 +1355,8 @@ void felics_ctx_destroy(felics_ctx *ctx) {
                           &l.partial, &l.status, &l.edge_first, &l.edge_last, &l.pscratch, &l.wrecs[0], &l.wrecs[1], &l.wtile_cnt, &l.wmeta, &l.whist, &l.wdigtot, &l.heads, &l.wlong};
         for (DevBuf *b : bufs) release(*b);
         if (l.h_sizes) (void)hipHostFree(l.h_sizes);
+        release(l.mtable);
+        if (l.h_table) (void)hipHostFree(l.h_table);
         for (int i = 0; i < ST_COUNT; i++)
             for (int k = 0; k < EV_PAIRS; k++)
                 for (int j = 0; j < 2; j++)
@@ -988,6 +1381,10 @@ void felics_ctx_destroy(felics_ctx *ctx) {
         if (ev) (void)hipEventDestroy(ev);
     release(ctx->out);
     release(ctx->own);
+    release(ctx->mix_in);
+    release(ctx->mix_stage);
+    release(ctx->mix_out);
+    release(ctx->mix_redo);
     release(ctx->dec_meta);
     release(ctx->dec_planes);
     release(ctx->dec_table);
@@ -1220,6 +1617,71 @@ int felics_compress_batch(felics_ctx *ctx, size_t n, const void *const *pixels, 
         if (rc) return drain(rc);
     }
     HIP_TRY(ctx, hipStreamSynchronize(ctx->copy_out));  // the streams have landed
+    return result;
+}
+
+int felics_compress_images_device(felics_ctx *ctx, size_t n, const felics_image *images, void *d_out, size_t d_out_cap, uint64_t *offsets,
+                                  uint64_t *lens) {
+    if (!ctx || (n && (!images || !d_out || !offsets || !lens))) return FELICS_E_INVALID_ARGUMENT;
+    if (ctx->failed) return FELICS_E_HIP;
+    int rc = check_images(n, images);
+    if (rc) return rc;
+    if (n == 0) return FELICS_OK;
+    if (any_pending(ctx)) return FELICS_E_INVALID_ARGUMENT;  // felics_wait_batch first
+    std::vector<MixImage> im(n);
+    for (size_t i = 0; i < n; i++) im[i] = mix_image(images[i]);
+    return images_device(ctx, im, (uint8_t *)d_out, d_out_cap, offsets, lens);
+}
+
+// Host frames in, host streams out: the frames are copied to the device (16-byte aligned, back to back), encoded as above into the
+// context's own buffer, and every stream that fits its caller's buffer is copied back.
+int felics_compress_images(felics_ctx *ctx, size_t n, const felics_image *images, uint8_t *const *outs, const size_t *caps, size_t *lens) {
+    if (!ctx || (n && (!images || !outs || !caps || !lens))) return FELICS_E_INVALID_ARGUMENT;
+    if (ctx->failed) return FELICS_E_HIP;
+    int rc = check_images(n, images);
+    if (rc) return rc;
+    if (n == 0) return FELICS_OK;
+    if (any_pending(ctx)) return FELICS_E_INVALID_ARGUMENT;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    if (!ctx->copy_in) {
+        HIP_TRY(ctx, hipStreamCreateWithFlags(&ctx->copy_in, hipStreamNonBlocking));
+        HIP_TRY(ctx, hipStreamCreateWithFlags(&ctx->copy_out, hipStreamNonBlocking));
+    }
+    std::vector<MixImage> im(n);
+    std::vector<size_t> at(n);
+    size_t in_total = 0;
+    uint64_t out_total = 64;
+    for (size_t i = 0; i < n; i++) {
+        im[i] = mix_image(images[i]);
+        at[i] = in_total;
+        in_total += (im[i].frame_bytes + 15) & ~(size_t)15;
+        out_total += mix_slot(im[i].frame_bytes);
+    }
+    if ((rc = reserve(ctx, ctx->in, in_total + 64)) != 0) return rc;
+    if ((rc = reserve(ctx, ctx->out, (size_t)out_total)) != 0) return rc;
+    for (size_t i = 0; i < n; i++) {
+        uint8_t *dst = (uint8_t *)ctx->in.p + at[i];
+        if (im[i].frame_bytes) HIP_TRY(ctx, hipMemcpyAsync(dst, images[i].pixels, im[i].frame_bytes, hipMemcpyHostToDevice, ctx->copy_in));
+        im[i].px = dst;
+    }
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->copy_in));
+    std::vector<uint64_t> offs(n), sizes(n);
+    rc = images_device(ctx, im, (uint8_t *)ctx->out.p, ctx->out.cap, offs.data(), sizes.data());
+    if (rc == FELICS_E_BUFFER_TOO_SMALL) {  // a stream outgrew its slot and the slots' room: exact placement in a larger buffer
+        if ((rc = reserve(ctx, ctx->out, (size_t)sizes[0] + 64)) != 0) return rc;
+        rc = images_device(ctx, im, (uint8_t *)ctx->out.p, ctx->out.cap, offs.data(), sizes.data());
+    }
+    if (rc) return rc;
+    int result = FELICS_OK;
+    for (size_t i = 0; i < n; i++) {
+        lens[i] = (size_t)sizes[i];
+        if (sizes[i] > caps[i] || !outs[i]) {
+            result = FELICS_E_BUFFER_TOO_SMALL;  // lens[] reports every size needed; nothing is written to this buffer
+            continue;
+        }
+        HIP_TRY(ctx, hipMemcpyAsync(outs[i], (const uint8_t *)ctx->out.p + offs[i], (size_t)sizes[i], hipMemcpyDeviceToHost, ctx->copy_out));
+    }
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->copy_out));
     return result;
 }
 

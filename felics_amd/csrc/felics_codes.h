@@ -192,6 +192,29 @@ __device__ __forceinline__ uint32_t *plane_words(const PlaneOut &po, uint32_t pl
     limit_words = po.plane_slot >> 2;
     return reinterpret_cast<uint32_t *>(po.scratch + ((uint64_t)img * (po.planes_per_image - 1) + c - 1) * po.plane_slot);
 }
+// The stream of image img (k_concat_planes) and the pack tiles of a plane (k_join_edges: its last tile ends the plane).
+__device__ __forceinline__ uint32_t *image_words(const PlaneOut &po, uint32_t img, uint64_t &limit_words) {
+    limit_words = po.slot_stride >> 2;
+    return reinterpret_cast<uint32_t *>(po.out + (uint64_t)img * po.slot_stride);
+}
+__device__ __forceinline__ uint32_t plane_tiles(const PlaneOut &, uint32_t, uint32_t ntiles) { return ntiles; }
+
+// The output of a mixed sub-batch (Geometry::mixed): image i's stream at out + table[i * planes_per_image].out_off, at most
+// out_slot bytes of it; planes 1, 2 of an RGB image in scratch slots as above.
+struct MixedOut {
+    PlaneOut po;
+    const PlaneGeom *table;
+};
+__device__ __forceinline__ uint32_t *image_words(const MixedOut &mo, uint32_t img, uint64_t &limit_words) {
+    const PlaneGeom *pg = mo.table + (uint64_t)img * mo.po.planes_per_image;
+    limit_words = pg->out_slot >> 2;
+    return reinterpret_cast<uint32_t *>(mo.po.out + pg->out_off);
+}
+__device__ __forceinline__ uint32_t *plane_words(const MixedOut &mo, uint32_t plane, uint64_t &limit_words) {
+    if (plane % mo.po.planes_per_image == 0) return image_words(mo, plane / mo.po.planes_per_image, limit_words);
+    return plane_words(mo.po, plane, limit_words);
+}
+__device__ __forceinline__ uint32_t plane_tiles(const MixedOut &mo, uint32_t plane, uint32_t) { return mo.table[plane].ntiles; }
 
 
 constexpr uint32_t ST_AGGREGATE = 1, ST_PREFIX = 2;

@@ -65,9 +65,26 @@ struct Geometry {
     uint32_t pack_tiles;        // ceil(npix / PACK_TILE)
     uint32_t color, depth;      // header fields
     uint32_t nctx;              // contexts per plane: nctx_of<sample type>()
+    // A MIXED sub-batch (8-bit images of different sizes, felics_compress_images*): the tile count stays uniform (sort_tiles =
+    // pack_tiles = the largest image's, npix = sort_tiles * SORT_TILE), what differs per plane is read from this device table
+    // (nullptr: the uniform geometry above).
+    const struct PlaneGeom *mixed = nullptr;
+};
+
+// One plane of a mixed sub-batch.  The kernels index it by plane (wave-uniform: scalar loads).  Tiles past the plane's own end
+// produce no events and no bits; the plane's size is still published by the last of the sub-batch's tiles.
+struct PlaneGeom {
+    const void *samples;   // the plane's first sample: the caller's frame (gray8), or its Y / Co / Cg plane in the lane's planes buffer
+    const void *image;     // the image's interleaved pixels as the caller gave them (RGB8: what k_rgb8_to_planes reads)
+    uint32_t W, H, npix;   // the image's size
+    uint32_t ntiles;       // the plane's own pack tiles, ceil(npix / PACK_TILE) (<= Geometry::pack_tiles)
+    uint64_t out_off;      // the image's slot in the output: byte offset from PackTarget::out, and size (writes beyond it are dropped)
+    uint64_t out_slot;
 };
 
 void launch_rgb8_to_planes(hipStream_t s, const uint8_t *rgb, int16_t *planes, uint32_t npix, uint32_t nimg);
+// mixed sub-batch: image i's pixels from table[3 i].image, its planes to table[3 i + c].samples (planes `plane_stride` samples apart)
+void launch_rgb8_to_planes_mixed(hipStream_t s, const PlaneGeom *table, uint64_t plane_stride, uint32_t max_npix, uint32_t nimg);
 
 // ------------------------------------------------------------------------------------------
 // The 8-bit pipeline in TILE-LOCAL layout (round 5).  A pixel is classified once: the front kernel sorts the events of

@@ -46,6 +46,34 @@ __device__ __forceinline__ void ycocg(int r, int gr, int b, int &yv, int &co, in
 // Four pixels per thread: 12 bytes in (three dwords), four samples out per plane (one 8-byte store each).
 // A group never straddles two images (it starts at a multiple of four inside its image; the last pixels
 // of an image whose size is not a multiple of four take the single-pixel path).
+// src = pixel i of the image, o = the image's Y plane, its Co / Cg planes `stride` samples behind it.
+__device__ __forceinline__ void rgb8_group(const uint8_t *__restrict__ src, int16_t *__restrict__ o, uint32_t i, uint32_t npix, uint64_t stride) {
+    if (i + 4 <= npix) {
+        uint32_t w[3];
+        __builtin_memcpy(w, src, 12);
+        int yv[4], co[4], cg[4];
+        ycocg((int)(w[0] & 0xFFu), (int)((w[0] >> 8) & 0xFFu), (int)((w[0] >> 16) & 0xFFu), yv[0], co[0], cg[0]);
+        ycocg((int)(w[0] >> 24), (int)(w[1] & 0xFFu), (int)((w[1] >> 8) & 0xFFu), yv[1], co[1], cg[1]);
+        ycocg((int)((w[1] >> 16) & 0xFFu), (int)(w[1] >> 24), (int)(w[2] & 0xFFu), yv[2], co[2], cg[2]);
+        ycocg((int)((w[2] >> 8) & 0xFFu), (int)((w[2] >> 16) & 0xFFu), (int)(w[2] >> 24), yv[3], co[3], cg[3]);
+        auto put4 = [&](int16_t *dst, const int (&v)[4]) {
+            const uint32_t p[2] = {(uint32_t)(v[0] & 0xFFFF) | ((uint32_t)v[1] << 16),
+                                   (uint32_t)(v[2] & 0xFFFF) | ((uint32_t)v[3] << 16)};
+            __builtin_memcpy(dst, p, 8);
+        };
+        put4(o + i, yv);
+        put4(o + stride + i, co);
+        put4(o + 2ull * stride + i, cg);
+    } else {
+        for (uint32_t j = i; j < npix; j++) {
+            int yv, co, cg;
+            ycocg(src[(j - i) * 3], src[(j - i) * 3 + 1], src[(j - i) * 3 + 2], yv, co, cg);
+            o[j] = (int16_t)yv;
+            o[stride + j] = (int16_t)co;
+            o[2ull * stride + j] = (int16_t)cg;
+        }
+    }
+}
 __global__ __launch_bounds__(256) void k_rgb8_to_planes(const uint8_t *__restrict__ rgb, int16_t *__restrict__ planes,
                                                         uint32_t npix, uint32_t nimg) {
     const uint32_t groups = (npix + 3) / 4;  // per image
@@ -54,34 +82,17 @@ __global__ __launch_bounds__(256) void k_rgb8_to_planes(const uint8_t *__restric
          g += (uint64_t)gridDim.x * blockDim.x) {
         const uint32_t img = (uint32_t)(g / groups);
         const uint32_t i = (uint32_t)(g - (uint64_t)img * groups) * 4;
-        const uint8_t *src = rgb + ((uint64_t)img * npix + i) * 3;
-        int16_t *o = planes + (uint64_t)img * 3 * npix;
-        if (i + 4 <= npix) {
-            uint32_t w[3];
-            __builtin_memcpy(w, src, 12);
-            int yv[4], co[4], cg[4];
-            ycocg((int)(w[0] & 0xFFu), (int)((w[0] >> 8) & 0xFFu), (int)((w[0] >> 16) & 0xFFu), yv[0], co[0], cg[0]);
-            ycocg((int)(w[0] >> 24), (int)(w[1] & 0xFFu), (int)((w[1] >> 8) & 0xFFu), yv[1], co[1], cg[1]);
-            ycocg((int)((w[1] >> 16) & 0xFFu), (int)(w[1] >> 24), (int)(w[2] & 0xFFu), yv[2], co[2], cg[2]);
-            ycocg((int)((w[2] >> 8) & 0xFFu), (int)((w[2] >> 16) & 0xFFu), (int)(w[2] >> 24), yv[3], co[3], cg[3]);
-            auto put4 = [&](int16_t *dst, const int (&v)[4]) {
-                const uint32_t p[2] = {(uint32_t)(v[0] & 0xFFFF) | ((uint32_t)v[1] << 16),
-                                       (uint32_t)(v[2] & 0xFFFF) | ((uint32_t)v[3] << 16)};
-                __builtin_memcpy(dst, p, 8);
-            };
-            put4(o + i, yv);
-            put4(o + (uint64_t)npix + i, co);
-            put4(o + 2ull * npix + i, cg);
-        } else {
-            for (uint32_t j = i; j < npix; j++) {
-                int yv, co, cg;
-                ycocg(src[(j - i) * 3], src[(j - i) * 3 + 1], src[(j - i) * 3 + 2], yv, co, cg);
-                o[j] = (int16_t)yv;
-                o[(uint64_t)npix + j] = (int16_t)co;
-                o[2ull * npix + j] = (int16_t)cg;
-            }
-        }
+        rgb8_group(rgb + ((uint64_t)img * npix + i) * 3, planes + (uint64_t)img * 3 * npix, i, npix, (uint64_t)npix);
     }
+}
+// A mixed sub-batch: image blockIdx.y from its own pointer and size (PlaneGeom), planes plane_stride samples apart.
+__global__ __launch_bounds__(256) void k_rgb8_to_planes_mixed(const PlaneGeom *__restrict__ table, uint64_t plane_stride) {
+    const PlaneGeom *pg = table + 3ull * blockIdx.y;
+    const uint32_t npix = pg->npix, groups = (npix + 3) / 4;
+    const uint8_t *rgb = (const uint8_t *)pg->image;
+    int16_t *o = (int16_t *)pg->samples;
+    for (uint32_t g = blockIdx.x * blockDim.x + threadIdx.x; g < groups; g += gridDim.x * blockDim.x)
+        rgb8_group(rgb + (uint64_t)g * 12u, o, g * 4, npix, plane_stride);
 }
 
 // ---- Instruction forms.  profiles/r04/valu_rate.txt: a gfx950 SIMD issues 32-bit add / sub / and / or / xor / lshr / ashr,
@@ -171,10 +182,33 @@ __device__ __forceinline__ uint32_t field_of(int v, int16_t) { return ((uint32_t
 #ifndef FELICS_FRONT_WAVES
 #define FELICS_FRONT_WAVES 6  // (gray planes; what the LDS allows.  A/B builds: profiles/tools/variant.sh)
 #endif
-template <typename T, typename ET>
+// Where a plane's samples are and how large it is: the geometry k_front and k_pack_t are instantiated with.  Uniform: every
+// plane W x (npix / W), back to back from `planes`; mixed (Geometry::mixed): the plane's PlaneGeom (plane is wave-uniform:
+// scalar loads).
+template <typename T>
+struct PlaneView {
+    const T *pl;
+    uint32_t W, H, npix;
+};
+template <typename T>
+__device__ __forceinline__ PlaneView<T> plane_view(const T *planes, uint32_t plane, uint32_t W, uint32_t npix) {
+    return PlaneView<T>{planes + (uint64_t)plane * npix, W, 0u, npix};
+}
+template <typename T>
+__device__ __forceinline__ PlaneView<T> plane_view(const PlaneGeom *table, uint32_t plane, uint32_t, uint32_t) {
+    return plane_view<T>((const T *)nullptr, plane, table);
+}
+template <typename T>
+__device__ __forceinline__ PlaneView<T> plane_view(const T *, uint32_t plane, const PlaneGeom *table) {
+    const PlaneGeom *pg = table + (uint32_t)__builtin_amdgcn_readfirstlane((int)plane);
+    return PlaneView<T>{(const T *)pg->samples, pg->W, pg->H, pg->npix};
+}
+
+// (S: const T * -- the uniform planes -- or const PlaneGeom * -- a mixed sub-batch's table; W and npix are then unused)
+template <typename T, typename ET, typename S>
 __attribute__((amdgpu_waves_per_eu(sizeof(T) == 1 ? FELICS_FRONT_WAVES : 5))) __global__ __launch_bounds__(256) void k_front(
-    const T *__restrict__ planes, ET *__restrict__ ev, uint16_t *__restrict__ pix, uint32_t *__restrict__ runtab,
-    uint32_t *__restrict__ tile_slots, uint32_t W, uint32_t npix, uint32_t ntiles, uint32_t tile_begin, uint32_t tile_end,
+    S __restrict__ planes, ET *__restrict__ ev, uint16_t *__restrict__ pix, uint32_t *__restrict__ runtab,
+    uint32_t *__restrict__ tile_slots, uint32_t W_, uint32_t npix_, uint32_t ntiles, uint32_t tile_begin, uint32_t tile_end,
     uint32_t nplanes, uint32_t cap, uint32_t *__restrict__ flags, uint32_t mode) {
     constexpr uint32_t NC = nctx_of<T>();
     constexpr uint32_t QUARTER = SORT_TILE / 4, TRIPS = QUARTER / 256;
@@ -202,7 +236,10 @@ __attribute__((amdgpu_waves_per_eu(sizeof(T) == 1 ? FELICS_FRONT_WAVES : 5))) __
     const uint32_t tile = tile_begin + item % wg_tiles;
     uint32_t *my_cnt = cnt[wave];
     for (uint32_t c = lane; c < NC; c += 64) my_cnt[c] = 0;
-    const T *pl = planes + (uint64_t)plane * npix;
+    // (mixed: a tile past the plane's end has no pixels -- no events, no slots in use, an empty run table)
+    const PlaneView<T> view = plane_view<T>(planes, plane, W_, npix_);
+    const uint32_t W = view.W, npix = view.npix;
+    const T *pl = view.pl;
     const uint32_t begin = tile * SORT_TILE;
     const uint32_t qbegin = min(begin + wave * QUARTER, npix);
     const uint32_t end = min(qbegin + QUARTER, npix);  // of this wave's quarter
@@ -863,13 +900,16 @@ __global__ __launch_bounds__(PACK_THREADS) void k_pack(const T *__restrict__ pla
 
 constexpr uint32_t FUSED_WIN_WORDS = PACK_TILE * 16 / 32;  // LDS bit window: 16 bits per pixel of a tile in one pass (more bits: more passes)
 
-struct FusedArgs {
+// PO: where the streams go -- PlaneOut (fixed slots i * slot_stride, every plane W x H) or MixedOut (a mixed sub-batch: slots and
+// plane sizes from the PlaneGeom table; W, H, npix below are then unused)
+template <typename PO>
+struct FusedArgsT {
     uint64_t *status;
     uint64_t *tile_bitoff;
     uint32_t *tile_bits;
     uint64_t *plane_carry;
     uint32_t *edge_first, *edge_last, *error;
-    PlaneOut po;
+    PO po;
     uint32_t W, H, npix, ntiles, color, depth, epoch;
     // Tiles are handed out by a ticket counter (zeroed before the launch) in (tile, plane) order, or -- null -- by
     // blockIdx: with tickets a tile only ever waits for tiles held by workgroups that are already running, whatever else
@@ -878,6 +918,16 @@ struct FusedArgs {
     uint32_t *ticket;
     uint32_t nplanes;
 };
+using FusedArgs = FusedArgsT<PlaneOut>;
+template <typename FA> struct OutOf;
+template <typename PO> struct OutOf<FusedArgsT<PO>> { using type = PO; };
+#define PO_OF(FA) typename OutOf<FA>::type
+__device__ __forceinline__ const PlaneOut &planes_out(const PlaneOut &po) { return po; }
+__device__ __forceinline__ const PlaneOut &planes_out(const MixedOut &mo) { return mo.po; }
+template <typename T>
+__device__ __forceinline__ PlaneView<T> plane_view(const T *planes, uint32_t plane, const FusedArgsT<MixedOut> &fa) {
+    return plane_view(planes, plane, fa.po.table);
+}
 #ifdef FELICS_PACK_STAMPS
 __device__ unsigned long long g_pack_stamps[256][16];
 #define PSTAMP(i)                                                                              \
@@ -1170,7 +1220,9 @@ __device__ __forceinline__ void walk_group_global(const T *__restrict__ pl, cons
         xy.advance(1, g.W);
     }
 }
-template <typename T>
+// (Own: one copy per k_pack_t instantiation -- a call's register conventions follow from all of a callee's callers, so the mixed
+// kernel's copy is kept apart from the uniform kernel's)
+template <typename T, typename Own>
 __device__ __noinline__ uint32_t general_group_bits(const uint32_t *words, const T *pl, const GeneralGroup g) {
     uint32_t bits = 0;
     if (g.first < g.end) {
@@ -1182,7 +1234,7 @@ __device__ __noinline__ uint32_t general_group_bits(const uint32_t *words, const
     return bits;
 }
 // (the window's word 0 is stream word win_word0; bit 0 of this group is stream bit my_lo)
-template <typename T>
+template <typename T, typename Own>
 __device__ __noinline__ void general_group_place(const uint32_t *words, const T *pl, const GeneralGroup g, uint32_t *win,
                                                  uint32_t win_words, uint64_t win_word0, uint64_t my_lo) {
     LaneBits bw;
@@ -1207,7 +1259,8 @@ __device__ __noinline__ void general_group_place(const uint32_t *words, const T 
 }
 
 // this workgroup's (tile offset in the launch, plane)
-__device__ __forceinline__ void take_ticket(const FusedArgs &fa, FusedLDS &fl, uint32_t &x, uint32_t &plane) {
+template <typename FA>
+__device__ __forceinline__ void take_ticket(const FA &fa, FusedLDS &fl, uint32_t &x, uint32_t &plane) {
     uint32_t t;
     if (fa.ticket) {
         if (threadIdx.x == 0) fl.ticket_sh = atomicAdd(fa.ticket, 1u);
@@ -1227,7 +1280,8 @@ __device__ __forceinline__ void take_ticket(const FusedArgs &fa, FusedLDS &fl, u
 // The tile's offset in its plane: decoupled look-back by wave 0 (see the comment above).  Publishes the tile's inclusive
 // prefix, leaves the exclusive one in fl.tile_lo_sh (far beyond any slot if the wait was given up: every store of the tile is
 // then dropped) and, for the last tile of a plane, the plane's size.  The tile's AGGREGATE has been published before.
-__device__ __forceinline__ void look_back(const FusedArgs &fa, FusedLDS &fl, uint32_t tile, uint32_t plane, uint32_t tile_total) {
+template <typename FA>
+__device__ __forceinline__ void look_back(const FA &fa, FusedLDS &fl, uint32_t tile, uint32_t plane, uint32_t tile_total) {
     const uint32_t lane = lane_id(), epoch = fa.epoch, ntiles = fa.ntiles;
     uint64_t *status = fa.status;
     uint64_t excl = 0;
@@ -1277,7 +1331,7 @@ __device__ __forceinline__ void look_back(const FusedArgs &fa, FusedLDS &fl, uin
             fa.tile_bits[(uint64_t)plane * ntiles + tile] = tile_total;
             if (tile + 1 == ntiles) {
                 fa.plane_carry[plane] = incl;
-                if (plane % fa.po.planes_per_image != 0 && incl > fa.po.plane_slot * 8u) atomicOr(fa.error, 2u);  // the plane outgrew its scratch slot
+                if (plane % planes_out(fa.po).planes_per_image != 0 && incl > planes_out(fa.po).plane_slot * 8u) atomicOr(fa.error, 2u);  // the plane outgrew its scratch slot
             }
         }
     }
@@ -1286,16 +1340,18 @@ __device__ __forceinline__ void look_back(const FusedArgs &fa, FusedLDS &fl, uin
 // The single-pass pack of ONE tile by a workgroup (the body of k_pack_t): see the comment above.
 // gsm = this thread's samples (valid where gg.fast); words = the tile's event words in LDS (BY_WORD: 0 where a pixel is no event; else
 // the array holds k of pixel j in byte j) and fl.win all zero, with a barrier behind both.
-template <typename T, bool BY_WORD>
+template <typename T, bool BY_WORD, typename FA>
 __device__ __forceinline__ void pack_tile_fused(const GroupSamples<T> &gsm, const uint32_t *words, FusedLDS &fl, const T *__restrict__ planes,
-                                                const FusedArgs &fa, uint32_t tile, uint32_t plane, const GroupGeom &gg) {
+                                                const FA &fa, uint32_t tile, uint32_t plane, const GroupGeom &gg) {
     uint32_t (&win)[FUSED_WIN_WORDS + 2] = fl.win;
     uint32_t (&wsum)[PACK_THREADS / 64] = fl.wsum;
-    const PlaneOut &po = fa.po;
-    const uint32_t W = fa.W, H = fa.H, npix = fa.npix, ntiles = fa.ntiles;
-    const bool first_plane = plane % po.planes_per_image == 0;
+    const auto &po = fa.po;
+    PlaneView<T> view{planes + (uint64_t)plane * fa.npix, fa.W, fa.H, fa.npix};
+    if constexpr (!std::is_same<PO_OF(FA), PlaneOut>::value) view = plane_view(planes, plane, fa);
+    const uint32_t W = view.W, H = view.H, npix = view.npix, ntiles = fa.ntiles;
+    const bool first_plane = plane % planes_out(po).planes_per_image == 0;
     const uint32_t lane = lane_id(), wave = threadIdx.x >> 6;
-    const T *pl = planes + (uint64_t)plane * npix;
+    const T *pl = view.pl;
     const uint32_t tile_first = tile * PACK_TILE;
     const uint32_t first = tile_first + threadIdx.x * PACK_PER_THREAD;
     const uint32_t end = min(tile_first + PACK_TILE, npix);
@@ -1309,7 +1365,7 @@ __device__ __forceinline__ void pack_tile_fused(const GroupSamples<T> &gsm, cons
     // front of group_codes, the placement behind the common path's.)
     const GeneralGroup general{tile_first, first, end, W, H, npix, fa.color, fa.depth, has_header ? 1u : 0u, BY_WORD ? 1u : 0u};
     uint32_t bits = 0;
-    if (!gg.fast) bits = general_group_bits<T>(words, pl, general);  // count now, build the codes straight into the window later
+    if (!gg.fast) bits = general_group_bits<T, PO_OF(FA)>(words, pl, general);  // count now, build the codes straight into the window later
     uint32_t c32[PACK_PER_THREAD], len[PACK_PER_THREAD];
     bool in_registers = false;
     if (gg.fast) {
@@ -1381,7 +1437,7 @@ __device__ __forceinline__ void pack_tile_fused(const GroupSamples<T> &gsm, cons
                 at += len[j];
             }
         }
-        if (!in_registers && bits != 0) general_group_place<T>(words, pl, general, win, FUSED_WIN_WORDS, 0, my_rel);
+        if (!in_registers && bits != 0) general_group_place<T, PO_OF(FA)>(words, pl, general, win, FUSED_WIN_WORDS, 0, my_rel);
         PSTAMP(8);
         if (wave == 0) look_back(fa, fl, tile, plane, tile_total);
         __syncthreads();
@@ -1407,7 +1463,7 @@ __device__ __forceinline__ void pack_tile_fused(const GroupSamples<T> &gsm, cons
                 __syncthreads();
             }
             if (bits != 0 && my_last >= wb && my_first < wb + FUSED_WIN_WORDS)
-                general_group_place<T>(words, pl, general, win, FUSED_WIN_WORDS, first_word + wb, my_lo);
+                general_group_place<T, PO_OF(FA)>(words, pl, general, win, FUSED_WIN_WORDS, first_word + wb, my_lo);
             __syncthreads();
             flush_window(wb, 0u, tile_lo);
         }
@@ -1451,8 +1507,8 @@ struct TSources {
 #ifndef FELICS_PACK_WAVES
 #define FELICS_PACK_WAVES 6  // (what the LDS allows: 24.6 KB per workgroup of four waves; A/B builds: profiles/tools/variant.sh)
 #endif
-template <typename T>
-__attribute__((amdgpu_waves_per_eu(FELICS_PACK_WAVES))) __global__ __launch_bounds__(PACK_THREADS) void k_pack_t(const T *__restrict__ planes, TSources ts, FusedArgs fa,
+template <typename T, typename PO>
+__attribute__((amdgpu_waves_per_eu(FELICS_PACK_WAVES))) __global__ __launch_bounds__(PACK_THREADS) void k_pack_t(const T *__restrict__ planes, TSources ts, FusedArgsT<PO> fa,
                                                                                                uint32_t sort_tile_begin, uint32_t pack_tile_end) {
     using ET = typename std::conditional<sizeof(T) == 1, uint8_t, uint16_t>::type;
     __shared__ alignas(16) uint32_t words[PACK_TILE + 4];  // the word of the event at pixel tile_first + j, 0 where there is none; [PACK_TILE]: dump
@@ -1469,13 +1525,17 @@ __attribute__((amdgpu_waves_per_eu(FELICS_PACK_WAVES))) __global__ __launch_boun
     take_ticket(fa, fl, x, plane);
     PSTAMP(0);
     const uint32_t st = sort_tile_begin + x;
-    const T *pl = planes + (uint64_t)plane * fa.npix;
+    // (mixed: a tile past the plane's end has no slots in use and no pixels -- zero bits, nothing written; it still takes part in the
+    // look-back, so that the sub-batch's last tile publishes the plane's size)
+    PlaneView<T> view{planes + (uint64_t)plane * fa.npix, fa.W, fa.H, fa.npix};
+    if constexpr (!std::is_same<PO, PlaneOut>::value) view = plane_view(planes, plane, fa);
+    const T *pl = view.pl;
     // ---- round trip 1: the tile's slots in use and the thread's pixels
     const uint64_t pt = (uint64_t)plane * ts.sort_ntiles + st;
     const uint32_t ns = (uint32_t)__builtin_amdgcn_readfirstlane((int)ts.tile_slots[pt]);  // a multiple of REC
-    const GroupGeom gg = group_geometry<T>(pl, st, fa.W, fa.npix);
+    const GroupGeom gg = group_geometry<T>(pl, st, view.W, view.npix);
     GroupSamples<T> gsm;
-    if (gg.fast) load_group(pl, st * PACK_TILE + threadIdx.x * PACK_PER_THREAD, fa.W, gsm);
+    if (gg.fast) load_group(pl, st * PACK_TILE + threadIdx.x * PACK_PER_THREAD, view.W, gsm);
     for (uint32_t j = threadIdx.x; j < FUSED_WIN_WORDS + 2; j += PACK_THREADS) fl.win[j] = 0;  // the bit window (barrier: behind the gather)
     const uint8_t *ksrc = ts.kq + pt * ts.cap;
     const uint16_t *psrc = ts.pix + pt * ts.cap;
@@ -1551,8 +1611,9 @@ __attribute__((amdgpu_waves_per_eu(FELICS_PACK_WAVES))) __global__ __launch_boun
 }
 
 // Words shared by two tiles (and the last, partly filled word of a plane): OR of the two halves.
+template <typename PO>
 __global__ void k_join_edges(const uint64_t *__restrict__ tile_bitoff, const uint32_t *__restrict__ tile_bits,
-                             const uint32_t *__restrict__ edge_first, const uint32_t *__restrict__ edge_last, PlaneOut po,
+                             const uint32_t *__restrict__ edge_first, const uint32_t *__restrict__ edge_last, PO po,
                              uint32_t ntiles) {
     const uint32_t tile = blockIdx.x * blockDim.x + threadIdx.x, plane = blockIdx.y;
     if (tile >= ntiles) return;
@@ -1568,7 +1629,7 @@ __global__ void k_join_edges(const uint64_t *__restrict__ tile_bitoff, const uin
         // altogether (then it is the plane's tiny last tile and has no successor, i.e. cannot be `tile - 1`)
         out_words[first_word] = __builtin_bswap32(edge_first[at] | edge_last[at - 1]);
     }
-    if (last_shared && tile + 1 == ntiles && !(first_shared && first_word == last_word) && last_word < limit_words)
+    if (last_shared && tile + 1 == plane_tiles(po, plane, ntiles) && !(first_shared && first_word == last_word) && last_word < limit_words)
         out_words[last_word] = __builtin_bswap32(edge_last[at]);
 }
 
@@ -1588,14 +1649,16 @@ __device__ __forceinline__ uint32_t plane_bits_at(const uint32_t *__restrict__ s
 // plane_base[p] = bit offset of plane p in its image's stream, plane_carry[p] = its bits (k_finish_sizes).
 // One thread per output word: it ORs what every plane contributes to that word (the first word also
 // keeps plane 0's last bits, already in place).
+template <typename PO>
 __global__ __launch_bounds__(256) void k_concat_planes(const uint64_t *__restrict__ plane_base,
-                                                       const uint64_t *__restrict__ plane_carry, PlaneOut po) {
-    const uint32_t img = blockIdx.y, ppi = po.planes_per_image;
+                                                       const uint64_t *__restrict__ plane_carry, PO po) {
+    const uint32_t img = blockIdx.y, ppi = planes_out(po).planes_per_image;
     const uint64_t *base = plane_base + (uint64_t)img * ppi, *bits = plane_carry + (uint64_t)img * ppi;
     const uint64_t begin_bit = base[1], end_bit = base[ppi - 1] + bits[ppi - 1];
     if (end_bit == begin_bit) return;
-    uint32_t *dst = reinterpret_cast<uint32_t *>(po.out + (uint64_t)img * po.slot_stride);
-    const uint64_t first_word = begin_bit >> 5, last_word = (end_bit - 1) >> 5, limit_words = po.slot_stride >> 2;
+    uint64_t limit_words;
+    uint32_t *dst = image_words(po, img, limit_words);
+    const uint64_t first_word = begin_bit >> 5, last_word = (end_bit - 1) >> 5;
     for (uint64_t w = first_word + (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; w <= last_word && w < limit_words;
          w += (uint64_t)gridDim.x * blockDim.x) {
         uint32_t v = (w == first_word && (begin_bit & 31u) != 0) ? __builtin_bswap32(dst[w]) : 0u;
@@ -1619,6 +1682,12 @@ void launch_rgb8_to_planes(hipStream_t s, const uint8_t *rgb, int16_t *planes, u
     uint32_t blocks = (uint32_t)std::min<uint64_t>((total + 255) / 256, 256u * 32u);
     if (blocks == 0) return;
     FELICS_LAUNCH(k_rgb8_to_planes, dim3(blocks), dim3(256), s, rgb, planes, npix, nimg);
+}
+
+void launch_rgb8_to_planes_mixed(hipStream_t s, const PlaneGeom *table, uint64_t plane_stride, uint32_t max_npix, uint32_t nimg) {
+    const uint32_t bx = std::min<uint32_t>(cdiv(((uint64_t)max_npix + 3) / 4, 256), 1024u);
+    if (bx == 0 || nimg == 0) return;
+    FELICS_LAUNCH(k_rgb8_to_planes_mixed, dim3(bx, nimg), dim3(256), s, table, plane_stride);
 }
 
 template <typename T>
@@ -1697,12 +1766,18 @@ void launch_pack_t(hipStream_t s, const T *planes, const uint8_t *kq, const uint
                    uint32_t *edge_last, uint32_t *error, const PackTarget &to, const Geometry &g, uint32_t st0, uint32_t st1, uint32_t epoch,
                    uint32_t *ticket) {
     if (st1 <= st0) return;
-    const FusedArgs fa{status, tile_bitoff, tile_bits, plane_carry, edge_first, edge_last, error,
-                       PlaneOut{to.out, to.slot_stride, to.scratch, to.plane_slot, g.planes_per_image},
-                       g.W, g.H, g.npix, g.pack_tiles, g.color, g.depth, epoch, ticket, g.nplanes};
+    const PlaneOut po{to.out, to.slot_stride, to.scratch, to.plane_slot, g.planes_per_image};
     const TSources ts{kq, pix, ev, tile_slots, cap, g.sort_tiles};
     // (the kernel takes its tile from the ticket, or from blockIdx.x of this one-dimensional grid: never from blockIdx.y)
-    FELICS_LAUNCH((k_pack_t<T>), dim3((st1 - st0) * g.nplanes), dim3(PACK_THREADS), s, planes, ts, fa, st0, g.pack_tiles);
+    if (g.mixed) {
+        const FusedArgsT<MixedOut> fa{status, tile_bitoff, tile_bits, plane_carry, edge_first, edge_last, error, MixedOut{po, g.mixed},
+                                      g.W, g.H, g.npix, g.pack_tiles, g.color, g.depth, epoch, ticket, g.nplanes};
+        FELICS_LAUNCH((k_pack_t<T, MixedOut>), dim3((st1 - st0) * g.nplanes), dim3(PACK_THREADS), s, planes, ts, fa, st0, g.pack_tiles);
+        return;
+    }
+    const FusedArgs fa{status, tile_bitoff, tile_bits, plane_carry, edge_first, edge_last, error, po,
+                       g.W, g.H, g.npix, g.pack_tiles, g.color, g.depth, epoch, ticket, g.nplanes};
+    FELICS_LAUNCH((k_pack_t<T, PlaneOut>), dim3((st1 - st0) * g.nplanes), dim3(PACK_THREADS), s, planes, ts, fa, st0, g.pack_tiles);
 }
 template void launch_pack_t<uint8_t>(hipStream_t, const uint8_t *, const uint8_t *, const uint16_t *, const void *, const uint32_t *, uint32_t, uint64_t *,
                                      uint64_t *, uint32_t *, uint64_t *, uint32_t *, uint32_t *, uint32_t *, const PackTarget &,
@@ -1716,8 +1791,12 @@ void launch_front(hipStream_t s, const T *planes, const TileLocal<ET> &tl, const
                   uint32_t *flags, uint32_t mode) {
     if (tile_end <= tile_begin) return;
     const dim3 grid(8u * cdiv(g.nplanes, 8) * (tile_end - tile_begin));  // one workgroup per tile, the planes dealt to the XCDs by the kernel
-    FELICS_LAUNCH((k_front<T, ET>), grid, dim3(256), s, planes, tl.ev, tl.pix, tl.runtab, tl.tile_slots, g.W, g.npix, g.sort_tiles, tile_begin,
-                  tile_end, g.nplanes, tl.cap, flags, mode);
+    if (g.mixed)
+        FELICS_LAUNCH((k_front<T, ET, const PlaneGeom *>), grid, dim3(256), s, g.mixed, tl.ev, tl.pix, tl.runtab, tl.tile_slots, 0u, 0u, g.sort_tiles,
+                      tile_begin, tile_end, g.nplanes, tl.cap, flags, mode);
+    else
+        FELICS_LAUNCH((k_front<T, ET, const T *>), grid, dim3(256), s, planes, tl.ev, tl.pix, tl.runtab, tl.tile_slots, g.W, g.npix, g.sort_tiles,
+                      tile_begin, tile_end, g.nplanes, tl.cap, flags, mode);
 }
 template void launch_front<uint8_t, uint8_t>(hipStream_t, const uint8_t *, const TileLocal<uint8_t> &, const Geometry &, uint32_t, uint32_t,
                                              uint32_t *, uint32_t);
@@ -1727,8 +1806,12 @@ template void launch_front<int16_t, uint16_t>(hipStream_t, const int16_t *, cons
 void launch_join_edges_tiles(hipStream_t s, const uint64_t *tile_bitoff, const uint32_t *tile_bits, const uint32_t *edge_first,
                              const uint32_t *edge_last, const PackTarget &to, const Geometry &g, uint32_t ntiles) {
     const PlaneOut po{to.out, to.slot_stride, to.scratch, to.plane_slot, g.planes_per_image};
-    FELICS_LAUNCH(k_join_edges, dim3(cdiv(ntiles, 256), g.nplanes), dim3(256), s, tile_bitoff, tile_bits,
-                       edge_first, edge_last, po, ntiles);
+    if (g.mixed)
+        FELICS_LAUNCH(k_join_edges<MixedOut>, dim3(cdiv(ntiles, 256), g.nplanes), dim3(256), s, tile_bitoff, tile_bits,
+                      edge_first, edge_last, MixedOut{po, g.mixed}, ntiles);
+    else
+        FELICS_LAUNCH(k_join_edges<PlaneOut>, dim3(cdiv(ntiles, 256), g.nplanes), dim3(256), s, tile_bitoff, tile_bits,
+                      edge_first, edge_last, po, ntiles);
 }
 
 void launch_join_edges(hipStream_t s, const uint64_t *tile_bitoff, const uint32_t *tile_bits, const uint32_t *edge_first,
@@ -1743,7 +1826,10 @@ void launch_concat_planes(hipStream_t s, const uint64_t *plane_base, const uint6
     // the planes behind plane 0 hold at most plane_slot bytes each: enough threads for that many words
     const uint64_t words = (to.plane_slot >> 2) * (g.planes_per_image - 1);
     const uint32_t bx = (uint32_t)std::min<uint64_t>(cdiv(words, 256 * 4), 2048u);
-    FELICS_LAUNCH(k_concat_planes, dim3(std::max(bx, 1u), g.nimages), dim3(256), s, plane_base, plane_carry, po);
+    if (g.mixed)
+        FELICS_LAUNCH(k_concat_planes<MixedOut>, dim3(std::max(bx, 1u), g.nimages), dim3(256), s, plane_base, plane_carry, MixedOut{po, g.mixed});
+    else
+        FELICS_LAUNCH(k_concat_planes<PlaneOut>, dim3(std::max(bx, 1u), g.nimages), dim3(256), s, plane_base, plane_carry, po);
 }
 
 }  // namespace felics

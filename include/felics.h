@@ -117,6 +117,31 @@ int felics_submit_batch_device(felics_ctx *ctx, size_t n, const void *d_pixels, 
                                int *ticket);
 int felics_wait_batch(felics_ctx *ctx, int ticket, uint64_t *offsets, uint64_t *lens);
 
+/* One image of a mixed-shape batch: its own size, colour and depth. */
+typedef struct felics_image {
+    const void *pixels;      /* host pointer (felics_compress_images) or device pointer (felics_compress_images_device) */
+    uint32_t width, height;
+    int color, depth;        /* FELICS_COLOR_*, FELICS_DEPTH_* -- per image */
+} felics_image;
+
+/* n images of ANY shapes and types in one call: what felics_compress_batch is for one shape.  Every stream is byte-identical to
+ * what felics_compress writes for that image alone.  Every image is checked before anything is launched (the first error in
+ * image order is returned; NULL pixels only for a zero-sized image).  8-bit images of similar size share a submission (their
+ * tile counts padded to the largest of the group, at most 25 %); 16-bit images go through the same-shape path, one group per
+ * shape.  outs[i], caps[i], lens[i] per image; on FELICS_E_BUFFER_TOO_SMALL every lens[i] holds the size stream i needs and
+ * nothing is written to a buffer that is too small.  The reference has no counterpart (it is one call per image). */
+int felics_compress_images(felics_ctx *ctx, size_t n, const felics_image *images, uint8_t *const *outs, const size_t *caps,
+                           size_t *lens);
+
+/* Same, with the frames (images[i].pixels) and the output in DEVICE memory.  Stream i is written at offsets[i] of d_out
+ * (16-byte aligned, ascending in image order, non-overlapping) with lens[i] bytes; offsets / lens are HOST arrays of n entries.
+ * If d_out_cap holds a slot of felics_compress_batch_device's size for every stream, the streams are encoded into those slots;
+ * otherwise they are placed exactly, back to back.  On FELICS_E_BUFFER_TOO_SMALL lens[0] holds the capacity needed.  The stream
+ * contract of felics_compress_batch_device holds: the frames must be complete in memory when the call is made.  Like the other
+ * synchronous entry points it refuses to run (FELICS_E_INVALID_ARGUMENT) while a felics_submit_batch_device ticket is outstanding. */
+int felics_compress_images_device(felics_ctx *ctx, size_t n, const felics_image *images, void *d_out, size_t d_out_cap,
+                                  uint64_t *offsets, uint64_t *lens);
+
 /* Replaces `read_header` (format.rs:63-84). */
 int felics_read_header(const uint8_t *in, size_t len, felics_header *hdr);
 /* Replaces `write_header` (format.rs:51-61): writes FELICS_HEADER_BYTES bytes. */
