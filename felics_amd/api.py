@@ -91,7 +91,8 @@ EXPORTS = [
     "felics_decompress", "felics_strerror", "felics_last_error", "felics_set_profiling",
     "felics_stage_count", "felics_stage_name", "felics_get_stage_ms", "felics_get_stage_launches",
     "felics_lane_count", "felics_ctx_lane_count", "felics_get_span_ms", "felics_decompress_with_header", "felics_get_stats", "felics_decompress_batch_device",
-    "felics_compress_images", "felics_compress_images_device",
+    "felics_compress_images", "felics_compress_images_device", "felics_read_headers_device",
+    "felics_decompress_images_device",
 ]
 
 _lib = None
@@ -148,6 +149,10 @@ def lib():
     L.felics_compress_images_device.argtypes = [vp, sz, C.POINTER(_CImage), vp, sz, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
     L.felics_decompress_batch_device.argtypes = [vp, sz, vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), vp, sz,
                                                  C.POINTER(_CHeader), C.POINTER(C.c_int)]
+    L.felics_read_headers_device.argtypes = [vp, sz, vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(_CHeader),
+                                             C.POINTER(C.c_int)]
+    L.felics_decompress_images_device.argtypes = [vp, sz, vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), vp, sz, C.POINTER(C.c_uint64),
+                                                  C.POINTER(_CHeader), C.POINTER(C.c_int)]
     L.felics_strerror.argtypes = [C.c_int]
     L.felics_strerror.restype = C.c_char_p
     L.felics_last_error.argtypes = [vp]
@@ -351,6 +356,47 @@ class Encoder:
         if rc != 0:
             self._raise(rc)
         return Header(ch.color_type, ch.pixel_depth, ch.width, ch.height), status
+
+    def read_headers_device(self, d_streams, offsets, lens):
+        """felics_read_headers_device: the headers of streams in device memory (raw pointer), read on the GPU.
+        Returns (list of Header, or None where the header is invalid; status array of felics_read_header codes)."""
+        offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+        lens = np.ascontiguousarray(lens, dtype=np.uint64)
+        n = len(offsets)
+        status = np.zeros(max(n, 1), dtype=np.int32)
+        hdrs = (_CHeader * max(n, 1))()
+        rc = lib().felics_read_headers_device(self._h, n, d_streams, offsets.ctypes.data_as(C.POINTER(C.c_uint64)),
+                                              lens.ctypes.data_as(C.POINTER(C.c_uint64)), hdrs, status.ctypes.data_as(C.POINTER(C.c_int)))
+        if rc != 0 and rc not in DecompressionError.KINDS:
+            self._raise(rc)
+        out = [Header(h.color_type, h.pixel_depth, h.width, h.height) if s == 0 else None for h, s in zip(hdrs[:n], status[:n])]
+        return out, status[:n]
+
+    def decompress_images_device(self, d_streams, offsets, lens, d_pixels, d_pixels_cap):
+        """felics_decompress_images_device: streams of any shapes in device memory -> frames in device memory (raw pointers).
+        Returns (pix_offsets, list of Header -- zeros where a header is invalid --, status array); a too-small buffer raises FelicsError(-8, "need N bytes"), a
+        failing stream DecompressionError with .status (and .pix_offsets, .headers)."""
+        offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+        lens = np.ascontiguousarray(lens, dtype=np.uint64)
+        n = len(offsets)
+        status = np.zeros(max(n, 1), dtype=np.int32)
+        pix = np.zeros(max(n, 1), dtype=np.uint64)
+        hdrs = (_CHeader * max(n, 1))()
+        rc = lib().felics_decompress_images_device(
+            self._h, n, d_streams, offsets.ctypes.data_as(C.POINTER(C.c_uint64)), lens.ctypes.data_as(C.POINTER(C.c_uint64)), d_pixels,
+            d_pixels_cap, pix.ctypes.data_as(C.POINTER(C.c_uint64)), hdrs, status.ctypes.data_as(C.POINTER(C.c_int)))
+        if rc == -8:
+            err = FelicsError(rc, "need %d bytes" % int(pix[0]))
+            err.status = status[:n]
+            raise err
+        headers = [Header(h.color_type, h.pixel_depth, h.width, h.height) for h in hdrs[:n]]  # (zeros where the header is invalid)
+        if rc in DecompressionError.KINDS:
+            err = DecompressionError(rc)
+            err.status, err.pix_offsets, err.headers = status[:n], pix[:n], headers
+            raise err
+        if rc != 0:
+            self._raise(rc)
+        return pix[:n], headers, status[:n]
 
     def lane_count(self):
         """felics_ctx_lane_count: submissions this context can have in flight (fixed when it was created)."""

@@ -13,6 +13,7 @@
 #include <string>
 #include <algorithm>
 #include <new>
+#include <tuple>
 #include <vector>
 
 #include "../../include/felics.h"
@@ -148,6 +149,7 @@ struct felics_ctx {
                                                   // run of a call whose buffer cannot hold the slots, frames gathered for a remedy
     DevBuf own;      // encode_device's own output when the caller gives none (the host entry point's fall-back for a chunk whose streams outgrew their slots)
     DevBuf dec_meta, dec_planes;  // GPU decoder: offsets | lens | status of a batch; Y / Co / Cg planes of RGB streams
+    DevBuf dec_planes16;          // mixed decode call: the int32 planes of its RGB16 streams (beside dec_planes, used at the same time)
     DevBuf dec_lane_table;        // gray streams decoded 64 to a wave: the estimator rows that do not fit in LDS (3 KB per stream, zeroed per call)
     DevBuf dec_table;             // 16-bit streams: estimator tables in HBM (8.4 MB per stream of a pass), zeroed once, rows tagged with an epoch
     uint32_t dec_epoch = 0;       // last epoch handed out (three per call: one per plane)
@@ -1259,6 +1261,345 @@ int images_device(felics_ctx *ctx, const std::vector<MixImage> &im, uint8_t *d_o
     return FELICS_OK;
 }
 
+// ---- GPU decoder helpers shared by felics_decompress_batch_device and felics_decompress_images_device -----------------------
+
+// 16-bit streams: estimator tables for passes of `per` <= n streams (at most DEC16_PASS, a stream's table is 8.4 MB of HBM, and at
+// most a quarter of the free HBM; an allocation that fails all the same halves the pass)
+int dec16_tables(felics_ctx *ctx, size_t n, size_t &per) {
+    constexpr size_t DEC16_PASS = 1024;
+    per = std::min(n, DEC16_PASS);
+    size_t free_b = 0, total_b = 0;
+    if (hipMemGetInfo(&free_b, &total_b) == hipSuccess && ctx->dec_table.cap < decode16_table_bytes((uint32_t)per))
+        per = std::max<size_t>(1, std::min(per, (free_b / 4 + ctx->dec_table.cap) / decode16_table_bytes(1)));
+    for (;;) {
+        const size_t table_bytes = decode16_table_bytes((uint32_t)per);
+        if (table_bytes > ctx->dec_table.cap) ctx->dec_epoch = 0;  // a fresh (zeroed) buffer: epochs start over
+        const int rc = reserve_zeroed(ctx, ctx->dec_table, table_bytes);
+        if (rc == 0) return FELICS_OK;
+        (void)hipGetLastError();
+        if (per == 1) return rc;
+        per = (per + 1) / 2;
+    }
+}
+
+// the first of the three epochs (one per plane) of the next pass on stream s
+int dec16_epoch(felics_ctx *ctx, hipStream_t s, uint32_t &epoch0) {
+    if (ctx->dec_epoch > 0xFFFFFFF0u) {  // epochs used up: clear the tables, start over
+        HIP_TRY(ctx, hipMemsetAsync(ctx->dec_table.p, 0, ctx->dec_table.cap, s));
+        ctx->dec_epoch = 0;
+    }
+    epoch0 = ctx->dec_epoch + 1;
+    ctx->dec_epoch += 3;
+    return FELICS_OK;
+}
+
+constexpr int HOST_DECODE_NO_MEMORY = 1;  // (not a status: the host could not hold the stream)
+
+// One stream through the host decoder (rows too wide for the LDS): copied to the host, decoded, the frame copied to d_dst.  A stream
+// longer than max_len is FELICS_E_INVALID_VALUE before anything is sized by it; a header other than `want`,
+// FELICS_E_INVALID_DIMENSIONS.  Returns the stream's status, FELICS_E_HIP (HIP error, ctx->err set) or HOST_DECODE_NO_MEMORY.
+int host_decode(felics_ctx *ctx, const uint8_t *d_src, uint64_t len, uint64_t max_len, const felics_header &want, uint8_t *d_dst,
+                std::vector<uint8_t> &sbuf, std::vector<uint8_t> &pbuf) {
+    if (len > max_len) return FELICS_E_INVALID_VALUE;
+    const uint64_t frame_bytes = (uint64_t)want.width * want.height * (want.color_type ? 3 : 1) * (want.pixel_depth ? 2 : 1);
+    try {
+        sbuf.resize((size_t)len);
+        pbuf.resize((size_t)frame_bytes);
+    } catch (const std::bad_alloc &) {
+        return HOST_DECODE_NO_MEMORY;
+    }
+    if (len && hipMemcpy(sbuf.data(), d_src, (size_t)len, hipMemcpyDeviceToHost) != hipSuccess)
+        return hip_fail(ctx, hipGetLastError(), "copying a stream to the host decoder");
+    felics_header hi;
+    int r = felics_read_header(sbuf.data(), sbuf.size(), &hi);
+    if (!r && (hi.width != want.width || hi.height != want.height || hi.color_type != want.color_type || hi.pixel_depth != want.pixel_depth))
+        r = FELICS_E_INVALID_DIMENSIONS;
+    if (!r) r = felics_decompress(sbuf.data(), sbuf.size(), pbuf.data(), pbuf.size(), nullptr);
+    if (!r && frame_bytes && hipMemcpy(d_dst, pbuf.data(), (size_t)frame_bytes, hipMemcpyHostToDevice) != hipSuccess)
+        return hip_fail(ctx, hipGetLastError(), "copying decoded pixels to the device");
+    return r;
+}
+
+// k_read_headers over n streams: offsets | lens | records in ctx->dec_meta (`extra` more bytes reserved behind them), the records
+// copied back to `rec`; d_off / d_len stay on the device
+int read_headers(felics_ctx *ctx, size_t n, const void *d_streams, const uint64_t *offsets, const uint64_t *lens, std::vector<DecodeHeader> &rec,
+                 hipStream_t s) {
+    int rc = reserve(ctx, ctx->dec_meta, n * 16 + n * sizeof(DecodeHeader));
+    if (rc) return rc;
+    try {
+        rec.resize(n);
+    } catch (const std::bad_alloc &) {
+        return FELICS_E_IO;
+    }
+    uint64_t *d_off = (uint64_t *)ctx->dec_meta.p, *d_len = d_off + n;
+    DecodeHeader *d_rec = (DecodeHeader *)(d_len + n);
+    HIP_TRY(ctx, hipMemcpyAsync(d_off, offsets, n * 8, hipMemcpyHostToDevice, s));
+    HIP_TRY(ctx, hipMemcpyAsync(d_len, lens, n * 8, hipMemcpyHostToDevice, s));
+    HIP_TRY(ctx, launch_read_headers(s, (const uint8_t *)d_streams, d_off, d_len, (uint32_t)n, d_rec));
+    HIP_TRY(ctx, hipMemcpyAsync(rec.data(), d_rec, n * sizeof(DecodeHeader), hipMemcpyDeviceToHost, s));
+    HIP_TRY(ctx, hipStreamSynchronize(s));
+    return FELICS_OK;
+}
+
+// felics_decompress_images_device after the argument checks.  Every stream's header is read on the device (k_read_headers); the
+// frames are laid out in stream order; each stream then takes one of four forms:
+//   - 8-bit, 64 streams of one shape per wave (k_decode8_lanes) -- groups of >= 64 streams of one shape, W >= 8, in a call with
+//     as many 8-bit streams as the same-shape entry point wants for that form;
+//   - 8-bit, a wave per stream (k_decode8), rows in LDS classes, longest streams first, a class per launch and stream;
+//   - 16-bit, a wave per stream (k_decode16), passes bounded by the estimator tables' memory;
+//   - the host decoder, stream by stream (rows wider than the LDS holds).
+// The GPU forms run on distinct streams of the context, joined with events before the statuses come back.
+int decompress_images(felics_ctx *ctx, size_t n, const void *d_streams, const uint64_t *offsets, const uint64_t *lens, uint8_t *d_pixels,
+                      size_t cap, uint64_t *pix_offsets, felics_header *hdrs, int *status) {
+    Lane &l0 = ctx->lanes[0];
+    hipStream_t s = l0.stream;
+    auto fail_all = [&](int code) {
+        for (size_t i = 0; i < n; i++) status[i] = code;
+        return code;
+    };
+    std::vector<DecodeHeader> rec;
+    int rc = read_headers(ctx, n, d_streams, offsets, lens, rec, s);
+    if (rc) return fail_all(rc);
+    // layout in stream order; a stream that will not be decoded gets no bytes
+    uint64_t at = 0;
+    std::vector<uint64_t> npix(n, 0);
+    for (size_t i = 0; i < n; i++) {
+        const DecodeHeader &h = rec[i];
+        if (hdrs) hdrs[i] = h.status == FELICS_OK ? felics_header{h.color, h.depth, h.W, h.H} : felics_header{};
+        status[i] = h.dstatus;
+        pix_offsets[i] = at;
+        if (h.dstatus != FELICS_OK) continue;
+        npix[i] = (uint64_t)h.W * h.H;
+        at = (at + npix[i] * (h.color ? 3 : 1) * (h.depth ? 2 : 1) + 15) & ~15ull;
+    }
+    const uint64_t needed = at;
+    if (needed > cap) {
+        for (size_t i = 0; i < n; i++)
+            if (status[i] == FELICS_OK) status[i] = FELICS_E_BUFFER_TOO_SMALL;
+        pix_offsets[0] = needed;
+        return FELICS_E_BUFFER_TOO_SMALL;
+    }
+    if (needed && !d_pixels) return fail_all(FELICS_E_INVALID_ARGUMENT);
+    // forms
+    int forced = -1;  // FELICS_TEST_DECODE_LANES=1 / =0: every same-shape group with W >= 8 / none in the lane form (tests)
+    if (const char *e = getenv("FELICS_TEST_DECODE_LANES")) forced = atoi(e) != 0;
+    std::vector<size_t> wave8, rows16, host;
+    size_t n8 = 0;
+    for (size_t i = 0; i < n; i++) {
+        const DecodeHeader &h = rec[i];
+        if (status[i] != FELICS_OK) continue;
+        if (!h.depth && decode8_lds_bytes(h.W, h.color) <= DECODE_LDS_LIMIT) n8++;
+        else if (h.depth && decode16_lds_bytes(h.W) <= DECODE_LDS_LIMIT) rows16.push_back(i);
+        else host.push_back(i);
+    }
+    // lane groups: 8-bit GPU streams of one shape, in stream order within a group
+    std::vector<std::vector<size_t>> lane_groups[2];  // [colour]
+    {
+        std::vector<size_t> idx8;
+        for (size_t i = 0; i < n; i++)
+            if (status[i] == FELICS_OK && !rec[i].depth && decode8_lds_bytes(rec[i].W, rec[i].color) <= DECODE_LDS_LIMIT) idx8.push_back(i);
+        std::stable_sort(idx8.begin(), idx8.end(), [&](size_t a, size_t b) {
+            return std::make_tuple(rec[a].color, rec[a].W, rec[a].H) < std::make_tuple(rec[b].color, rec[b].W, rec[b].H);
+        });
+        for (size_t k = 0; k < idx8.size();) {
+            size_t e = k;
+            while (e < idx8.size() && rec[idx8[e]].color == rec[idx8[k]].color && rec[idx8[e]].W == rec[idx8[k]].W && rec[idx8[e]].H == rec[idx8[k]].H) e++;
+            const DecodeHeader &h = rec[idx8[k]];
+            const size_t cnt = e - k;
+            size_t take = 0;
+            if (h.W >= 8) {
+                if (forced >= 0) take = forced ? cnt : 0;
+                else if (n8 >= (h.color ? DECODE8_LANES_MIN_STREAMS_RGB : DECODE8_LANES_MIN_STREAMS)) take = cnt / 64 * 64;
+            }
+            if (take) lane_groups[h.color].emplace_back(idx8.begin() + k, idx8.begin() + k + take);
+            wave8.insert(wave8.end(), idx8.begin() + k + take, idx8.begin() + e);
+            k = e;
+        }
+    }
+    auto longest_first = [&](std::vector<size_t> &v) {
+        std::stable_sort(v.begin(), v.end(), [&](size_t a, size_t b) { return npix[a] > npix[b]; });
+    };
+    longest_first(wave8);
+    longest_first(rows16);
+    // RGB8 planes (int16) of the wave rows and the lane slots
+    uint64_t planes8 = 0;
+    auto plane8_of = [&](size_t i) {
+        const uint64_t o = planes8;
+        planes8 += 3 * npix[i];
+        return o;
+    };
+    // wave-form rows in LDS classes: a class's launch asks for its widest row's LDS, so a thin image does not share a
+    // launch (and its residency) with a very wide one
+    constexpr uint32_t LDS_CLASS[] = {16u << 10, 32u << 10, 64u << 10, DECODE_LDS_LIMIT};
+    constexpr int NCLASS = 4;
+    std::vector<DecodeRow> rows;
+    struct Launch {
+        size_t first, cnt;
+        uint32_t lds;
+        uint64_t max_npix;
+        bool rgb;
+    };
+    std::vector<Launch> classes;
+    for (int c = 0; c < NCLASS; c++) {
+        Launch L{rows.size(), 0, 0, 0, false};
+        for (size_t i : wave8) {
+            const uint32_t lds = decode8_lds_bytes(rec[i].W, rec[i].color);
+            if (lds > LDS_CLASS[c] || (c > 0 && lds <= LDS_CLASS[c - 1])) continue;
+            const uint64_t poff = rec[i].color ? plane8_of(i) : 0;
+            rows.push_back(DecodeRow{(uint32_t)i, rec[i].W, rec[i].H, rec[i].color, pix_offsets[i], poff});
+            L.cnt++;
+            L.lds = std::max(L.lds, lds);
+            L.max_npix = std::max(L.max_npix, npix[i]);
+            L.rgb = L.rgb || rec[i].color;
+        }
+        if (L.cnt) classes.push_back(L);
+    }
+    // lane form: waves of up to 64 slots of one shape; gray slots first, then RGB (each colour one launch, its tables behind the other's)
+    std::vector<LaneWave> waves;
+    std::vector<LaneSlot> slots;
+    Launch lanes[2] = {};  // first / cnt index waves; max_npix; conversion rows of the RGB slots: `conv`
+    size_t slot0[2] = {0, 0};
+    Launch conv{0, 0, 0, 0, true};
+    for (int col = 0; col < 2; col++) {
+        lanes[col].first = waves.size();
+        slot0[col] = slots.size();
+        for (const auto &g : lane_groups[col]) {
+            for (size_t k = 0; k < g.size(); k += 64) {
+                const uint32_t cnt = (uint32_t)std::min<size_t>(64, g.size() - k);
+                waves.push_back(LaneWave{rec[g[k]].W, rec[g[k]].H, (uint32_t)(slots.size() - slot0[col]), cnt});
+                for (uint32_t j = 0; j < cnt; j++) {
+                    const size_t i = g[k + j];
+                    const uint64_t poff = col ? plane8_of(i) : 0;
+                    slots.push_back(LaneSlot{(uint32_t)i, 0, col ? poff : pix_offsets[i]});
+                    if (col) {
+                        if (!conv.cnt) conv.first = rows.size();
+                        rows.push_back(DecodeRow{(uint32_t)i, rec[i].W, rec[i].H, 1, pix_offsets[i], poff});
+                        conv.cnt++;
+                    }
+                    lanes[col].max_npix = std::max(lanes[col].max_npix, npix[i]);
+                }
+            }
+        }
+        lanes[col].cnt = waves.size() - lanes[col].first;
+    }
+    // 16-bit rows (passes below) behind the others
+    const size_t rows16_first = rows.size();
+    size_t per16 = 0;
+    uint64_t planes16 = 0;  // int32 samples of the largest pass's RGB planes
+    if (!rows16.empty()) {
+        if ((rc = dec16_tables(ctx, rows16.size(), per16)) != 0) return fail_all(rc);
+        for (size_t p = 0; p < rows16.size(); p += per16) {
+            uint64_t poff = 0;
+            for (size_t k = p; k < std::min(rows16.size(), p + per16); k++) {
+                const size_t i = rows16[k];
+                rows.push_back(DecodeRow{(uint32_t)i, rec[i].W, rec[i].H, rec[i].color, pix_offsets[i], poff});
+                if (rec[i].color) poff += 3 * npix[i];
+            }
+            planes16 = std::max(planes16, poff);
+        }
+    }
+    // device side: offsets | lens | status | rows | waves | slots (offsets and lens again: the buffer may have moved)
+    auto al = [](size_t b) { return (b + 15) & ~(size_t)15; };
+    const size_t o_status = n * 16, o_rows = o_status + al(n * 4), o_waves = o_rows + al(rows.size() * sizeof(DecodeRow)),
+                 o_slots = o_waves + al(waves.size() * sizeof(LaneWave)), o_end = o_slots + slots.size() * sizeof(LaneSlot);
+    if ((rc = reserve(ctx, ctx->dec_meta, o_end)) != 0) return fail_all(rc);
+    uint8_t *meta = (uint8_t *)ctx->dec_meta.p;
+    uint64_t *d_off = (uint64_t *)meta, *d_len = d_off + n;
+    int *d_status = (int *)(meta + o_status);
+    DecodeRow *d_rows = (DecodeRow *)(meta + o_rows);
+    LaneWave *d_waves = (LaneWave *)(meta + o_waves);
+    LaneSlot *d_slots = (LaneSlot *)(meta + o_slots);
+    if (planes8 && (rc = reserve(ctx, ctx->dec_planes, planes8 * 2 + 64)) != 0) return fail_all(rc);
+    if (planes16 && (rc = reserve(ctx, ctx->dec_planes16, planes16 * 4 + 64)) != 0) return fail_all(rc);
+    const size_t lt_gray = decode8_lanes_table_bytes((uint32_t)(slot0[1] - slot0[0]), 0);
+    const size_t lt_bytes = lt_gray + decode8_lanes_table_bytes((uint32_t)(slots.size() - slot0[1]), 1);
+    if (!slots.empty() && (rc = reserve(ctx, ctx->dec_lane_table, lt_bytes)) != 0) return fail_all(rc);
+    std::vector<int> dev_status(status, status + n);
+    for (size_t i = 0; i < n; i++)
+        if (dev_status[i] == FELICS_OK) dev_status[i] = FELICS_E_HIP;  // until the kernel's own word arrives
+    for (size_t i : host) dev_status[i] = FELICS_OK;
+    auto queue = [&]() -> int {
+        HIP_TRY(ctx, hipMemcpyAsync(d_off, offsets, n * 8, hipMemcpyHostToDevice, s));
+        HIP_TRY(ctx, hipMemcpyAsync(d_len, lens, n * 8, hipMemcpyHostToDevice, s));
+        HIP_TRY(ctx, hipMemcpyAsync(d_status, dev_status.data(), n * 4, hipMemcpyHostToDevice, s));
+        if (!rows.empty()) HIP_TRY(ctx, hipMemcpyAsync(d_rows, rows.data(), rows.size() * sizeof(DecodeRow), hipMemcpyHostToDevice, s));
+        if (!waves.empty()) HIP_TRY(ctx, hipMemcpyAsync(d_waves, waves.data(), waves.size() * sizeof(LaneWave), hipMemcpyHostToDevice, s));
+        if (!slots.empty()) HIP_TRY(ctx, hipMemcpyAsync(d_slots, slots.data(), slots.size() * sizeof(LaneSlot), hipMemcpyHostToDevice, s));
+        // the launches that do not depend on each other go to distinct streams of the context, behind the uploads
+        std::vector<hipStream_t> work;
+        for (int li = 0; li < ctx->nlanes; li++) {
+            Lane &l = ctx->lanes[li];
+            for (hipStream_t w : {l.front, l.kstream, li ? l.stream : l.tail})
+                if (w && std::find(work.begin(), work.end(), w) == work.end()) work.push_back(w);
+        }
+        HIP_TRY(ctx, hipEventRecord(l0.slice_done[0], s));
+        for (hipStream_t w : work) HIP_TRY(ctx, hipStreamWaitEvent(w, l0.slice_done[0], 0));
+        size_t next = 0;
+        auto stream_for = [&]() { return work[next++ % work.size()]; };
+        const uint8_t *st = (const uint8_t *)d_streams;
+        if (!rows16.empty()) {
+            hipStream_t w = stream_for();
+            for (size_t p = 0; p < rows16.size(); p += per16) {
+                const size_t cnt = std::min(per16, rows16.size() - p);
+                uint32_t lds = 0, epoch0 = 0;
+                uint64_t mx = 0;
+                bool rgb = false;
+                for (size_t k = p; k < p + cnt; k++) {
+                    const size_t i = rows16[k];
+                    lds = std::max(lds, decode16_lds_bytes(rec[i].W));
+                    mx = std::max(mx, npix[i]);
+                    rgb = rgb || rec[i].color;
+                }
+                int r = dec16_epoch(ctx, w, epoch0);
+                if (r) return r;
+                HIP_TRY(ctx, launch_decode16_rows(w, st, d_off, d_len, d_rows + rows16_first + p, (uint32_t)cnt, lds, mx, rgb, (uint16_t *)d_pixels,
+                                                  (int32_t *)ctx->dec_planes16.p, (uint32_t *)ctx->dec_table.p, epoch0, d_status));
+            }
+        }
+        if (!slots.empty()) {
+            hipStream_t w = stream_for();
+            HIP_TRY(ctx, hipMemsetAsync(ctx->dec_lane_table.p, 0, lt_bytes, w));
+            for (int col = 0; col < 2; col++)
+                HIP_TRY(ctx, launch_decode8_lanes_waves(w, st, d_off, d_len, d_waves + lanes[col].first, (uint32_t)lanes[col].cnt, d_slots + slot0[col],
+                                                        col, d_rows + conv.first, (uint32_t)conv.cnt, lanes[1].max_npix, d_pixels,
+                                                        (int16_t *)ctx->dec_planes.p, (uint32_t *)((uint8_t *)ctx->dec_lane_table.p + (col ? lt_gray : 0)),
+                                                        d_status));
+        }
+        for (const Launch &L : classes)
+            HIP_TRY(ctx, launch_decode8_rows(stream_for(), st, d_off, d_len, d_rows + L.first, (uint32_t)L.cnt, L.lds, L.max_npix, L.rgb, d_pixels,
+                                             (int16_t *)ctx->dec_planes.p, d_status));
+        // the host decoder meanwhile (into frames no kernel writes)
+        std::vector<uint8_t> sbuf, pbuf;
+        for (size_t i : host) {
+            const felics_header want{rec[i].color, rec[i].depth, rec[i].W, rec[i].H};
+            const int r = host_decode(ctx, st + offsets[i], lens[i], felics_max_compressed_size(rec[i].W, rec[i].H, rec[i].color, rec[i].depth), want,
+                                      d_pixels + pix_offsets[i], sbuf, pbuf);
+            if (r == FELICS_E_HIP) return r;
+            status[i] = r == HOST_DECODE_NO_MEMORY ? FELICS_E_IO : r;
+        }
+        const size_t used = std::min(next, work.size());
+        for (size_t k = 0; k < used; k++) {
+            HIP_TRY(ctx, hipEventRecord(l0.spine_done[k], work[k]));
+            HIP_TRY(ctx, hipStreamWaitEvent(s, l0.spine_done[k], 0));
+        }
+        HIP_TRY(ctx, hipMemcpyAsync(dev_status.data(), d_status, n * 4, hipMemcpyDeviceToHost, s));
+        HIP_TRY(ctx, hipStreamSynchronize(s));
+        return FELICS_OK;
+    };
+    if ((rc = queue()) != 0) {
+        for (size_t i = 0; i < n; i++) status[i] = FELICS_E_HIP;
+        return rc;
+    }
+    std::vector<char> on_host(n, 0);
+    for (size_t i : host) on_host[i] = 1;
+    int first = FELICS_OK;
+    for (size_t i = 0; i < n; i++) {
+        if (!on_host[i]) status[i] = dev_status[i];
+        if (status[i] && !first) first = status[i];
+    }
+    return first;
+}
+
 }  // namespace
 
 // --------------------------------------------------------------------------------------------
@@ -1387,6 +1728,7 @@ void felics_ctx_destroy(felics_ctx *ctx) {
     release(ctx->mix_redo);
     release(ctx->dec_meta);
     release(ctx->dec_planes);
+    release(ctx->dec_planes16);
     release(ctx->dec_table);
     release(ctx->dec_lane_table);
     delete ctx;
@@ -1735,19 +2077,8 @@ int felics_decompress_batch_device(felics_ctx *ctx, size_t n, const void *d_stre
     if (bps == 2 && decode16_lds_bytes(hdr.width) <= DECODE_LDS_LIMIT) {
         // 16-bit streams on the device: passes of at most DEC16_PASS streams (a stream's estimator table is 8.4 MB of HBM)
         // (and of at most a quarter of the free HBM; an allocation that fails all the same halves the pass)
-        constexpr size_t DEC16_PASS = 1024;
-        size_t per = std::min(n, DEC16_PASS);
-        size_t free_b = 0, total_b = 0;
-        if (hipMemGetInfo(&free_b, &total_b) == hipSuccess && ctx->dec_table.cap < decode16_table_bytes((uint32_t)per))
-            per = std::max<size_t>(1, std::min(per, (free_b / 4 + ctx->dec_table.cap) / decode16_table_bytes(1)));
-        for (;;) {
-            const size_t table_bytes = decode16_table_bytes((uint32_t)per);
-            if (table_bytes > ctx->dec_table.cap) ctx->dec_epoch = 0;  // a fresh (zeroed) buffer: epochs start over
-            if ((rc = reserve_zeroed(ctx, ctx->dec_table, table_bytes)) == 0) break;
-            (void)hipGetLastError();
-            if (per == 1) return fail_all(rc);
-            per = (per + 1) / 2;
-        }
+        size_t per = 0;
+        if ((rc = dec16_tables(ctx, n, per)) != 0) return fail_all(rc);
         if ((rc = reserve(ctx, ctx->dec_meta, per * 8 * 2 + per * 4)) != 0) return fail_all(rc);
         int32_t *d_planes32 = nullptr;
         if (planes == 3) {
@@ -1759,12 +2090,8 @@ int felics_decompress_batch_device(felics_ctx *ctx, size_t n, const void *d_stre
         int first_rc = FELICS_OK;
         for (size_t first = 0; first < n; first += per) {
             const size_t cnt = std::min(per, n - first);
-            if (ctx->dec_epoch > 0xFFFFFFF0u) {  // epochs used up: clear the tables, start over
-                HIP_TRY(ctx, hipMemsetAsync(ctx->dec_table.p, 0, ctx->dec_table.cap, s));
-                ctx->dec_epoch = 0;
-            }
-            const uint32_t epoch0 = ctx->dec_epoch + 1;
-            ctx->dec_epoch += 3;
+            uint32_t epoch0 = 0;
+            if ((rc = dec16_epoch(ctx, s, epoch0)) != 0) return rc;
             uint64_t *d_off = (uint64_t *)ctx->dec_meta.p, *d_len = d_off + cnt;
             int *d_status = (int *)(d_len + cnt);
             HIP_TRY(ctx, hipMemcpyAsync(d_off, offsets + first, cnt * 8, hipMemcpyHostToDevice, s));
@@ -1791,29 +2118,15 @@ int felics_decompress_batch_device(felics_ctx *ctx, size_t n, const void *d_stre
         }
         int first_rc = FELICS_OK;
         for (size_t i = 0; i < n; i++) {
-            if (lens[i] > max_len) {  // (checked before anything is sized by it)
-                status[i] = FELICS_E_INVALID_VALUE;
-                if (!first_rc) first_rc = FELICS_E_INVALID_VALUE;
-                continue;
+            const int r = host_decode(ctx, (const uint8_t *)d_streams + offsets[i], lens[i], max_len, hdr, (uint8_t *)d_pixels + i * frame_bytes,
+                                      sbuf, pbuf);
+            if (r == FELICS_E_HIP) {
+                for (size_t k = i; k < n; k++) status[k] = FELICS_E_HIP;
+                return r;
             }
-            try {
-                sbuf.resize((size_t)lens[i]);
-            } catch (const std::bad_alloc &) {
+            if (r == HOST_DECODE_NO_MEMORY) {
                 for (size_t k = i; k < n; k++) status[k] = FELICS_E_IO;
                 return first_rc ? first_rc : FELICS_E_IO;
-            }
-            if (lens[i] && hipMemcpy(sbuf.data(), (const uint8_t *)d_streams + offsets[i], (size_t)lens[i], hipMemcpyDeviceToHost) != hipSuccess) {
-                for (size_t k = i; k < n; k++) status[k] = FELICS_E_HIP;
-                return hip_fail(ctx, hipGetLastError(), "copying a stream to the host decoder");
-            }
-            felics_header hi;
-            int r = felics_read_header(sbuf.data(), sbuf.size(), &hi);
-            if (!r && (hi.width != hdr.width || hi.height != hdr.height || hi.color_type != hdr.color_type || hi.pixel_depth != hdr.pixel_depth))
-                r = FELICS_E_INVALID_DIMENSIONS;
-            if (!r) r = felics_decompress(sbuf.data(), sbuf.size(), pbuf.data(), pbuf.size(), nullptr);
-            if (!r && frame_bytes && hipMemcpy((uint8_t *)d_pixels + i * frame_bytes, pbuf.data(), (size_t)frame_bytes, hipMemcpyHostToDevice) != hipSuccess) {
-                for (size_t k = i; k < n; k++) status[k] = FELICS_E_HIP;
-                return hip_fail(ctx, hipGetLastError(), "copying decoded pixels to the device");
             }
             status[i] = r;
             if (r && !first_rc) first_rc = r;
@@ -1854,6 +2167,53 @@ int felics_decompress_batch_device(felics_ctx *ctx, size_t n, const void *d_stre
     for (size_t i = 0; i < n; i++)
         if (status[i]) return status[i];
     return FELICS_OK;
+}
+
+int felics_read_headers_device(felics_ctx *ctx, size_t n, const void *d_streams, const uint64_t *offsets, const uint64_t *lens,
+                               felics_header *hdrs, int *status) {
+    if (!ctx || (n && (!d_streams || !offsets || !lens || !hdrs || !status))) return FELICS_E_INVALID_ARGUMENT;
+    auto fail_all = [&](int code) {
+        for (size_t i = 0; i < n; i++) {
+            status[i] = code;
+            hdrs[i] = felics_header{};
+        }
+        return code;
+    };
+    if (ctx->failed) return fail_all(FELICS_E_HIP);
+    if (n == 0) return FELICS_OK;
+    if (any_pending(ctx)) return fail_all(FELICS_E_INVALID_ARGUMENT);  // felics_wait_batch first
+    if (n > 0xFFFFFFFFull) return fail_all(FELICS_E_INVALID_ARGUMENT);
+    if (hipSetDevice(ctx->device) != hipSuccess) return fail_all(hip_fail(ctx, hipGetLastError(), "hipSetDevice"));
+    // one launch, one copy back
+    std::vector<DecodeHeader> rec;
+    const int rc = read_headers(ctx, n, d_streams, offsets, lens, rec, ctx->lanes[0].stream);
+    if (rc) return fail_all(rc);
+    int first = FELICS_OK;
+    for (size_t i = 0; i < n; i++) {
+        status[i] = rec[i].status;
+        hdrs[i] = rec[i].status == FELICS_OK ? felics_header{rec[i].color, rec[i].depth, rec[i].W, rec[i].H} : felics_header{};
+        if (rec[i].status && !first) first = rec[i].status;
+    }
+    return first;
+}
+
+int felics_decompress_images_device(felics_ctx *ctx, size_t n, const void *d_streams, const uint64_t *offsets, const uint64_t *lens,
+                                    void *d_pixels, size_t d_pixels_cap, uint64_t *pix_offsets, felics_header *hdrs, int *status) {
+    if (!ctx || (n && (!d_streams || !offsets || !lens || !pix_offsets || !status))) return FELICS_E_INVALID_ARGUMENT;
+    auto fail_all = [&](int code) {
+        for (size_t i = 0; i < n; i++) {
+            status[i] = code;
+            pix_offsets[i] = 0;
+            if (hdrs) hdrs[i] = felics_header{};
+        }
+        return code;
+    };
+    if (ctx->failed) return fail_all(FELICS_E_HIP);
+    if (n == 0) return FELICS_OK;
+    if (any_pending(ctx)) return fail_all(FELICS_E_INVALID_ARGUMENT);  // felics_wait_batch first
+    if (n > 0xFFFFFFFFull) return fail_all(FELICS_E_INVALID_ARGUMENT);
+    if (hipSetDevice(ctx->device) != hipSuccess) return fail_all(hip_fail(ctx, hipGetLastError(), "hipSetDevice"));
+    return decompress_images(ctx, n, d_streams, offsets, lens, (uint8_t *)d_pixels, d_pixels_cap, pix_offsets, hdrs, status);
 }
 
 int felics_write_header(const felics_header *hdr, uint8_t *out, size_t cap) {

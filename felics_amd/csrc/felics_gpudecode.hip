@@ -121,10 +121,50 @@ struct ScalarBits {
     }
 };
 
+// Where a wave-per-stream kernel (k_decode8, k_decode16, the RGB conversions) finds its stream's shape and output: a geometry
+// policy.  DecUniform: the same-shape call's arguments -- stream = row, W x H of `color`, frames and planes back to back, RGB iff
+// there are planes.  DecMixed: row `row` of a DecodeRow table (the row index is wave-uniform: scalar loads).
+struct DecUniform {
+    uint32_t W, H, color;
+};
+struct DecMixed {
+    const DecodeRow *rows;
+};
+struct DecView {
+    uint32_t img, W, H, color;  // img: the stream's index into offsets / lens / status
+    uint64_t out_off, plane_off;
+};
+__device__ __forceinline__ DecView dec_view(const DecUniform &g, uint32_t row) { return DecView{row, g.W, g.H, g.color, 0, 0}; }
+__device__ __forceinline__ DecView dec_view(const DecMixed &g, uint32_t row) {
+    const DecodeRow r = g.rows[row];
+    return DecView{r.stream, r.W, r.H, r.color, r.out_off, r.plane_off};
+}
+template <typename P>
+__device__ __forceinline__ bool dec_rgb(const DecUniform &, const DecView &, const P *planes) { return planes != nullptr; }
+template <typename P>
+__device__ __forceinline__ bool dec_rgb(const DecMixed &, const DecView &v, const P *) { return v.color != 0; }
+// the stream's frame (uniform: `per` samples of T per stream) and plane c of its planes
+template <typename T>
+__device__ __forceinline__ T *dec_frame(const DecUniform &, T *pixels, const DecView &v, uint64_t per) { return pixels + (uint64_t)v.img * per; }
+template <typename T>
+__device__ __forceinline__ T *dec_frame(const DecMixed &, T *pixels, const DecView &v, uint64_t) {
+    return reinterpret_cast<T *>(reinterpret_cast<uint8_t *>(pixels) + v.out_off);
+}
+template <typename T>
+__device__ __forceinline__ T *dec_plane(const DecUniform &, T *planes, const DecView &v, uint32_t nplanes, uint32_t c, uint64_t npix) {
+    return planes + ((uint64_t)v.img * nplanes + c) * npix;
+}
+template <typename T>
+__device__ __forceinline__ T *dec_plane(const DecMixed &, T *planes, const DecView &v, uint32_t, uint32_t c, uint64_t npix) {
+    return planes + v.plane_off + (uint64_t)c * npix;
+}
+
 }  // namespace
 
 // One wave per stream.  status[i] = FELICS_OK or an error code.  Gray: u8 pixels straight to `pixels`;
 // RGB: the three planes as int16 to `planes` (image i at i * 3 * npix), converted by k_ycocg8_to_rgb.
+// G: DecUniform (the stream's header must be the one announced) or DecMixed (the row's shape: read from this stream's header by
+// k_read_headers, so the comparison below holds).
 // LDS (dynamic): table (256 or 512) x 6 u32 | rows 2 x rstride i16.
 //
 // The decode loop is one pixel after the other, and a lone wave retires a dependent vector instruction every ~10
@@ -133,16 +173,18 @@ struct ScalarBits {
 // the lane id).  The vector side only moves data in bulk: the stream 256 bytes at a time, the row above 64 samples at
 // a time (one register, read with v_readlane), the decoded row 64 samples at a time (collected with v_writelane,
 // stored to LDS for the next row and to global memory coalesced).
+template <typename G>
 __global__ __launch_bounds__(64) void k_decode8(const uint8_t *__restrict__ streams, const uint64_t *__restrict__ offsets,
-                                                const uint64_t *__restrict__ lens, uint32_t W, uint32_t H, uint32_t color,
-                                                uint8_t *__restrict__ pixels, int16_t *__restrict__ planes,
-                                                int *__restrict__ status) {
+                                                const uint64_t *__restrict__ lens, G geo, uint8_t *__restrict__ pixels,
+                                                int16_t *__restrict__ planes, int *__restrict__ status) {
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
+    const DecView v = dec_view(geo, blockIdx.x);
+    const uint32_t W = v.W, H = v.H, color = v.color;
     uint32_t *table = reinterpret_cast<uint32_t *>(smem);
     const uint32_t nctx = color ? nctx_of<int16_t>() : nctx_of<uint8_t>();  // gray: contexts 0..255, half the table
     int16_t *rows = reinterpret_cast<int16_t *>(smem + nctx * 6 * 4);
     const uint32_t rstride = decode8_row_stride(W);
-    const uint32_t img = blockIdx.x, lane = lane_id();
+    const uint32_t img = v.img, lane = lane_id();
     const uint8_t *s = streams + offsets[img];
     const uint64_t slen = lens[img];
     const uint64_t npix = (uint64_t)W * H;
@@ -175,8 +217,9 @@ __global__ __launch_bounds__(64) void k_decode8(const uint8_t *__restrict__ stre
         if (npix == 0) continue;
         for (uint32_t i = lane; i < nctx * 6; i += 64) table[i] = 0;  // KEstimator::new
         __builtin_amdgcn_wave_barrier();
-        int16_t *outp = planes ? planes + ((uint64_t)img * nplanes + c) * npix : nullptr;
-        uint8_t *outg = planes ? nullptr : pixels + (uint64_t)img * npix;
+        const bool rgb = dec_rgb(geo, v, planes);
+        int16_t *outp = rgb ? dec_plane(geo, planes, v, nplanes, c, npix) : nullptr;
+        uint8_t *outg = rgb ? nullptr : dec_frame(geo, pixels, v, npix);
         const int lo_ok = color ? -255 : 0, hi_ok = 255;  // what a sample of this plane can be (Y 0..255, Co / Cg -255..255)
         // rows: cur = the row being decoded, prev = the one above; both in LDS, written 64 samples at a time
         uint32_t x = 0, y = 0;
@@ -412,6 +455,44 @@ struct Four<int16_t> {
     }
 };
 
+// The lane form's geometry policy.  LaneUniform: the same-shape call's arguments -- lane j of wave b is stream 64 b + j, outputs
+// back to back.  LaneMixed: the wave's row (W, H, its slots: scalar loads) and the lane's slot (stream, output).
+struct LaneUniform {
+    uint32_t n, W, H;
+};
+struct LaneMixed {
+    const LaneWave *waves;
+    const LaneSlot *slots;
+};
+struct LaneView {
+    uint32_t W, H, img, slot;  // img: index into offsets / lens / status; slot: the estimator table
+    uint64_t out_off;
+};
+// false: this lane has no stream
+__device__ __forceinline__ bool lane_view(const LaneUniform &g, uint32_t lane, LaneView &v) {
+    v = LaneView{g.W, g.H, blockIdx.x * 64 + lane, blockIdx.x * 64 + lane, 0};
+    return v.img < g.n;
+}
+__device__ __forceinline__ bool lane_view(const LaneMixed &g, uint32_t lane, LaneView &v) {
+    const LaneWave w = g.waves[blockIdx.x];
+    v.W = w.W;
+    v.H = w.H;
+    if (lane >= w.n) return false;
+    v.slot = w.first + lane;
+    const LaneSlot s = g.slots[v.slot];
+    v.img = s.stream;
+    v.out_off = s.out_off;
+    return true;
+}
+template <typename ST>
+__device__ __forceinline__ ST *lane_plane(const LaneUniform &, void *out_base, const LaneView &v, uint32_t np, uint32_t plane, uint64_t npix) {
+    return reinterpret_cast<ST *>(out_base) + ((uint64_t)v.img * np + plane) * npix;
+}
+template <typename ST>
+__device__ __forceinline__ ST *lane_plane(const LaneMixed &, void *out_base, const LaneView &v, uint32_t, uint32_t plane, uint64_t npix) {
+    return reinterpret_cast<ST *>(out_base) + v.out_off + (uint64_t)plane * npix;
+}
+
 }  // namespace
 
 // RGB = false: gray8 streams, u8 frames straight to `out_base`.  RGB = true: the three planes of an RGB8 stream, one after the other from
@@ -419,18 +500,20 @@ struct Four<int16_t> {
 // -255 .. 255, contexts 0 .. 510, a zeroed table of its own per plane.  A counter still fits 16 bits: the Rice operand is at most 1024
 // (larger is the corrupt-stream exit), so counter 0 gains at most 1025 per event while counter 5 gains at least 38, i.e. at most 27.7 K
 // before the smallest counter passes 1024 and the row is halved -- below 56 K with the halved rest on top.
-template <bool RGB>
+// G: LaneUniform or LaneMixed (the streams of a wave have one shape either way).
+template <bool RGB, typename G>
 __global__ __launch_bounds__(64) void k_decode8_lanes(const uint8_t *__restrict__ streams, const uint64_t *__restrict__ offsets,
-                                                      const uint64_t *__restrict__ lens, uint32_t n, uint32_t W, uint32_t H,
-                                                      void *out_base, uint32_t *table, int *__restrict__ status) {
+                                                      const uint64_t *__restrict__ lens, G geo, void *out_base, uint32_t *table,
+                                                      int *__restrict__ status) {
     using ST = typename std::conditional<RGB, int16_t, uint8_t>::type;
     constexpr uint32_t NP = RGB ? 3u : 1u;
     constexpr uint32_t TABLE_DW = RGB ? DEC8L_TABLE_DW_RGB : DEC8L_TABLE_DW;  // per plane
     constexpr int LO_OK = RGB ? -255 : 0, HI_OK = 255;
     __shared__ uint32_t hot[DEC8L_HOT * 3 * 64];  // [context][pair of counters][lane]
     const uint32_t lane = lane_id();
-    const uint32_t img = blockIdx.x * 64 + lane;
-    if (img >= n) return;
+    LaneView v;
+    if (!lane_view(geo, lane, v)) return;
+    const uint32_t img = v.img, W = v.W, H = v.H;
     const uint8_t *s = streams + offsets[img];
     const uint64_t slen = lens[img];
     const uint64_t npix = (uint64_t)W * H;
@@ -458,8 +541,8 @@ __global__ __launch_bounds__(64) void k_decode8_lanes(const uint8_t *__restrict_
     const int32_t p0 = (int32_t)br.get(32), p1 = (int32_t)br.get(32);  // compression.rs:166-167
     if (br.failed() && rc == FELICS_OK) rc = FELICS_E_IO;
     if (npix == 0) continue;
-    uint32_t *tab = table + ((uint64_t)img * NP + plane) * TABLE_DW;
-    ST *out = reinterpret_cast<ST *>(out_base) + ((uint64_t)img * NP + plane) * npix;
+    uint32_t *tab = table + ((uint64_t)v.slot * NP + plane) * TABLE_DW;
+    ST *out = lane_plane<ST>(geo, out_base, v, NP, plane, npix);
     // (x, y) and everything derived from them alone is wave-uniform: every stream has the same shape
     int left = 0, left2 = 0;
     Four<ST> up4, up4_next, out4;
@@ -596,13 +679,45 @@ __global__ __launch_bounds__(64) void k_decode8_lanes(const uint8_t *__restrict_
     status[img] = rc;
 }
 
+// The conversions' geometry: ConvUniform -- npix of every stream, stream = blockIdx.y, planes and frames back to back; DecMixed --
+// row blockIdx.y (a gray row has nothing to convert).  False: nothing to do for this row.
+struct ConvUniform {
+    uint32_t npix;
+};
+template <typename P, typename T>
+struct ConvView {
+    uint32_t img, npix;
+    const P *pl;
+    T *dst;
+};
+template <typename P, typename T>
+__device__ __forceinline__ bool conv_view(const ConvUniform &g, const P *planes, T *pixels, ConvView<P, T> &c) {
+    c.img = blockIdx.y;
+    c.npix = g.npix;
+    c.pl = planes + (uint64_t)c.img * 3 * c.npix;
+    c.dst = pixels + (uint64_t)c.img * 3 * c.npix;
+    return true;
+}
+template <typename P, typename T>
+__device__ __forceinline__ bool conv_view(const DecMixed &g, const P *planes, T *pixels, ConvView<P, T> &c) {
+    const DecodeRow r = g.rows[blockIdx.y];
+    c.img = r.stream;
+    c.npix = r.W * r.H;
+    c.pl = planes + r.plane_off;
+    c.dst = reinterpret_cast<T *>(reinterpret_cast<uint8_t *>(pixels) + r.out_off);
+    return r.color != 0;
+}
+
 // ycocg_to_rgb (color_transform.rs:20-26) on the decoded planes, range-checked like try_into::<u8>()
+template <typename G>
 __global__ __launch_bounds__(256) void k_ycocg8_to_rgb(const int16_t *__restrict__ planes, uint8_t *__restrict__ pixels,
-                                                       uint32_t npix, int *__restrict__ status) {
-    const uint32_t img = blockIdx.y;
+                                                       G geo, int *__restrict__ status) {
+    ConvView<int16_t, uint8_t> cv;
+    if (!conv_view(geo, planes, pixels, cv)) return;
+    const uint32_t img = cv.img, npix = cv.npix;
     if (status[img] != FELICS_OK) return;
-    const int16_t *pl = planes + (uint64_t)img * 3 * npix;
-    uint8_t *dst = pixels + (uint64_t)img * 3 * npix;
+    const int16_t *pl = cv.pl;
+    uint8_t *dst = cv.dst;
     bool bad = false;
     for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < npix; i += gridDim.x * blockDim.x) {
         const int yv = pl[i], co = pl[(uint64_t)npix + i], cg = pl[2ull * npix + i];
@@ -640,21 +755,25 @@ __device__ __forceinline__ uint32_t row16_min(uint32_t v) {
     return (uint32_t)__builtin_amdgcn_readlane((int)v, 15);
 }
 
+// G: DecUniform or DecMixed as for k_decode8; the estimator table is the row's (blockIdx.x) either way.
+template <typename G>
 __global__ __launch_bounds__(64) void k_decode16(const uint8_t *__restrict__ streams, const uint64_t *__restrict__ offsets,
-                                                 const uint64_t *__restrict__ lens, uint32_t W, uint32_t H, uint32_t color,
-                                                 uint16_t *__restrict__ pixels, int32_t *__restrict__ planes,
-                                                 uint32_t *__restrict__ gtable, uint32_t epoch0, int *__restrict__ status) {
+                                                 const uint64_t *__restrict__ lens, G geo, uint16_t *__restrict__ pixels,
+                                                 int32_t *__restrict__ planes, uint32_t *__restrict__ gtable, uint32_t epoch0,
+                                                 int *__restrict__ status) {
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
+    const DecView v = dec_view(geo, blockIdx.x);
+    const uint32_t W = v.W, H = v.H, color = v.color;
     uint32_t *crow = reinterpret_cast<uint32_t *>(smem);                       // [DEC16_SLOTS][DEC16_ROW] cached rows
     uint32_t *ctag = crow + DEC16_SLOTS * DEC16_ROW;                            // [DEC16_SLOTS] context held (or ~0)
     int32_t *rows = reinterpret_cast<int32_t *>(ctag + DEC16_SLOTS);
     const uint32_t rstride = decode8_row_stride(W);
-    const uint32_t img = blockIdx.x, lane = lane_id();
+    const uint32_t img = v.img, lane = lane_id();
     const uint8_t *s = streams + offsets[img];
     const uint64_t slen = lens[img];
     const uint64_t npix = (uint64_t)W * H;
     const uint32_t nplanes = color ? 3u : 1u;
-    uint32_t *table = gtable + (uint64_t)img * DEC16_CONTEXTS * DEC16_ROW;
+    uint32_t *table = gtable + (uint64_t)blockIdx.x * DEC16_CONTEXTS * DEC16_ROW;
     int rc = FELICS_OK;
     if (slen < FELICS_HEADER_BYTES) {
         rc = FELICS_E_IO;
@@ -683,8 +802,9 @@ __global__ __launch_bounds__(64) void k_decode16(const uint8_t *__restrict__ str
         const uint32_t epoch = epoch0 + c;  // KEstimator::new: rows of other epochs read as zeros
         for (uint32_t i = lane; i < DEC16_SLOTS; i += 64) ctag[i] = 0xFFFFFFFFu;  // (nothing to write back: the last plane's rows are dead)
         __builtin_amdgcn_wave_barrier();
-        int32_t *outp = planes ? planes + ((uint64_t)img * nplanes + c) * npix : nullptr;
-        uint16_t *outg = planes ? nullptr : pixels + (uint64_t)img * npix;
+        const bool rgb = dec_rgb(geo, v, planes);
+        int32_t *outp = rgb ? dec_plane(geo, planes, v, nplanes, c, npix) : nullptr;
+        uint16_t *outg = rgb ? nullptr : dec_frame(geo, pixels, v, npix);
         const int lo_ok = (color && c > 0) ? -65535 : 0, hi_ok = 65535;  // Y 0..65535, Co / Cg -65535..65535
         uint32_t x = 0, y = 0;
         int32_t *cur = rows, *prev = rows + rstride;
@@ -796,12 +916,15 @@ __global__ __launch_bounds__(64) void k_decode16(const uint8_t *__restrict__ str
 }
 
 // ycocg_to_rgb (color_transform.rs:20-26) on the decoded 16-bit planes, range-checked like try_into::<u16>()
+template <typename G>
 __global__ __launch_bounds__(256) void k_ycocg16_to_rgb(const int32_t *__restrict__ planes, uint16_t *__restrict__ pixels,
-                                                        uint32_t npix, int *__restrict__ status) {
-    const uint32_t img = blockIdx.y;
+                                                        G geo, int *__restrict__ status) {
+    ConvView<int32_t, uint16_t> cv;
+    if (!conv_view(geo, planes, pixels, cv)) return;
+    const uint32_t img = cv.img, npix = cv.npix;
     if (status[img] != FELICS_OK) return;
-    const int32_t *pl = planes + (uint64_t)img * 3 * npix;
-    uint16_t *dst = pixels + (uint64_t)img * 3 * npix;
+    const int32_t *pl = cv.pl;
+    uint16_t *dst = cv.dst;
     bool bad = false;
     for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < npix; i += gridDim.x * blockDim.x) {
         const int yv = pl[i], co = pl[(uint64_t)npix + i], cg = pl[2ull * npix + i];
@@ -826,16 +949,16 @@ hipError_t launch_decode16(hipStream_t s, const uint8_t *streams, const uint64_t
     if (n == 0) return hipSuccess;
     const uint32_t lds = decode16_lds_bytes(W);
     if (lds > 64u * 1024u) {
-        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&k_decode16),
+        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&k_decode16<DecUniform>),
                                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)DECODE_LDS_LIMIT);
         if (e != hipSuccess) return e;
     }
-    hipLaunchKernelGGL(k_decode16, dim3(n), dim3(64), lds, s, streams, offsets, lens, W, H, color, pixels, planes, table, epoch0,
-                       status);
+    hipLaunchKernelGGL(k_decode16<DecUniform>, dim3(n), dim3(64), lds, s, streams, offsets, lens, DecUniform{W, H, color}, pixels, planes,
+                       table, epoch0, status);
     if (color) {
         const uint64_t npix = (uint64_t)W * H;
         const uint32_t bx = (uint32_t)std::min<uint64_t>((npix + 255) / 256, 1024u);
-        if (bx) hipLaunchKernelGGL(k_ycocg16_to_rgb, dim3(bx, n), dim3(256), 0, s, planes, pixels, (uint32_t)npix, status);
+        if (bx) hipLaunchKernelGGL(k_ycocg16_to_rgb<ConvUniform>, dim3(bx, n), dim3(256), 0, s, planes, pixels, ConvUniform{(uint32_t)npix}, status);
     }
     return hipGetLastError();
 }
@@ -848,13 +971,74 @@ hipError_t launch_decode8_lanes(hipStream_t s, const uint8_t *streams, const uin
                                 uint32_t W, uint32_t H, uint32_t color, uint8_t *pixels, int16_t *planes, uint32_t *table, int *status) {
     if (n == 0) return hipSuccess;
     if (!color) {
-        hipLaunchKernelGGL(k_decode8_lanes<false>, dim3((n + 63) / 64), dim3(64), 0, s, streams, offsets, lens, n, W, H, (void *)pixels, table, status);
+        hipLaunchKernelGGL((k_decode8_lanes<false, LaneUniform>), dim3((n + 63) / 64), dim3(64), 0, s, streams, offsets, lens,
+                           LaneUniform{n, W, H}, (void *)pixels, table, status);
         return hipGetLastError();
     }
-    hipLaunchKernelGGL(k_decode8_lanes<true>, dim3((n + 63) / 64), dim3(64), 0, s, streams, offsets, lens, n, W, H, (void *)planes, table, status);
+    hipLaunchKernelGGL((k_decode8_lanes<true, LaneUniform>), dim3((n + 63) / 64), dim3(64), 0, s, streams, offsets, lens,
+                       LaneUniform{n, W, H}, (void *)planes, table, status);
     const uint64_t npix = (uint64_t)W * H;
     const uint32_t bx = (uint32_t)std::min<uint64_t>((npix + 255) / 256, 1024u);
-    if (bx) hipLaunchKernelGGL(k_ycocg8_to_rgb, dim3(bx, n), dim3(256), 0, s, planes, pixels, (uint32_t)npix, status);
+    if (bx) hipLaunchKernelGGL(k_ycocg8_to_rgb<ConvUniform>, dim3(bx, n), dim3(256), 0, s, planes, pixels, ConvUniform{(uint32_t)npix}, status);
+    return hipGetLastError();
+}
+
+namespace {
+
+// read_header (format.rs:63-84) as felics_read_header does it: each field read only if the stream holds it; then, for a valid
+// header, the decode call's own rules: w * h < 2^32 (compression.rs:86), and at least C * (64 + max(0, w * h - 2)) bits behind the
+// header (two raw 32-bit samples per plane, then at least one flag bit per pixel, padded to a byte)
+__global__ __launch_bounds__(256) void k_read_headers(const uint8_t *__restrict__ streams, const uint64_t *__restrict__ offsets,
+                                                      const uint64_t *__restrict__ lens, uint32_t n, DecodeHeader *__restrict__ out) {
+    const uint32_t i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const uint8_t *s = streams + offsets[i];
+    const uint64_t len = lens[i];
+    DecodeHeader h = {0, 0, 0, 0, FELICS_OK, FELICS_OK};
+    if (len < 4) h.status = FELICS_E_IO;
+    else if (s[0] != 'F' || s[1] != 'L' || s[2] != 'C' || s[3] != 'S') h.status = FELICS_E_INVALID_SIGNATURE;
+    else if (len < 5) h.status = FELICS_E_IO;
+    else if (s[4] > 1) h.status = FELICS_E_INVALID_COLOR_TYPE;
+    else if (len < 6) h.status = FELICS_E_IO;
+    else if (s[5] > 1) h.status = FELICS_E_INVALID_PIXEL_DEPTH;
+    else if (len < FELICS_HEADER_BYTES) h.status = FELICS_E_IO;
+    h.dstatus = h.status;
+    if (h.status == FELICS_OK) {
+        h.color = s[4];
+        h.depth = s[5];
+        h.W = ((uint32_t)s[6] << 24) | ((uint32_t)s[7] << 16) | ((uint32_t)s[8] << 8) | s[9];
+        h.H = ((uint32_t)s[10] << 24) | ((uint32_t)s[11] << 16) | ((uint32_t)s[12] << 8) | s[13];
+        const uint64_t npix = (uint64_t)h.W * h.H;
+        if (npix > 0xFFFFFFFFull) {
+            h.dstatus = FELICS_E_INVALID_DIMENSIONS;
+        } else {
+            const uint64_t bits = (h.color ? 3u : 1u) * (64u + (npix > 2 ? npix - 2 : 0));
+            if (len - FELICS_HEADER_BYTES < (bits + 7) / 8) h.dstatus = FELICS_E_IO;
+        }
+    }
+    out[i] = h;
+}
+
+// the RGB conversion of `n` mixed rows (grid rows of at most 65 535)
+template <typename P, typename T>
+void launch_conv_rows(hipStream_t s, const DecodeRow *rows, uint32_t n, uint64_t max_npix, P *planes, T *pixels, int *status) {
+    const uint32_t bx = (uint32_t)std::min<uint64_t>((max_npix + 255) / 256, 1024u);
+    if (!bx) return;
+    for (uint32_t r0 = 0; r0 < n; r0 += 65535u) {
+        const uint32_t cnt = std::min(n - r0, 65535u);
+        if constexpr (sizeof(T) == 1)
+            hipLaunchKernelGGL(k_ycocg8_to_rgb<DecMixed>, dim3(bx, cnt), dim3(256), 0, s, planes, pixels, DecMixed{rows + r0}, status);
+        else
+            hipLaunchKernelGGL(k_ycocg16_to_rgb<DecMixed>, dim3(bx, cnt), dim3(256), 0, s, planes, pixels, DecMixed{rows + r0}, status);
+    }
+}
+
+}  // namespace
+
+hipError_t launch_read_headers(hipStream_t s, const uint8_t *streams, const uint64_t *offsets, const uint64_t *lens, uint32_t n,
+                               DecodeHeader *out) {
+    if (n == 0) return hipSuccess;
+    hipLaunchKernelGGL(k_read_headers, dim3((uint32_t)(((uint64_t)n + 255) / 256)), dim3(256), 0, s, streams, offsets, lens, n, out);
     return hipGetLastError();
 }
 
@@ -867,16 +1051,60 @@ hipError_t launch_decode8(hipStream_t s, const uint8_t *streams, const uint64_t 
     if (n == 0) return hipSuccess;
     const uint32_t lds = decode8_lds_bytes(W, color);
     if (lds > 64u * 1024u) {
-        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&k_decode8),
+        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&k_decode8<DecUniform>),
                                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)DECODE_LDS_LIMIT);
         if (e != hipSuccess) return e;
     }
-    hipLaunchKernelGGL(k_decode8, dim3(n), dim3(64), lds, s, streams, offsets, lens, W, H, color, pixels, planes, status);
+    hipLaunchKernelGGL(k_decode8<DecUniform>, dim3(n), dim3(64), lds, s, streams, offsets, lens, DecUniform{W, H, color}, pixels, planes,
+                       status);
     if (color) {
         const uint64_t npix = (uint64_t)W * H;
         const uint32_t bx = (uint32_t)std::min<uint64_t>((npix + 255) / 256, 1024u);
-        if (bx) hipLaunchKernelGGL(k_ycocg8_to_rgb, dim3(bx, n), dim3(256), 0, s, planes, pixels, (uint32_t)npix, status);
+        if (bx) hipLaunchKernelGGL(k_ycocg8_to_rgb<ConvUniform>, dim3(bx, n), dim3(256), 0, s, planes, pixels, ConvUniform{(uint32_t)npix}, status);
     }
+    return hipGetLastError();
+}
+
+hipError_t launch_decode8_rows(hipStream_t s, const uint8_t *streams, const uint64_t *offsets, const uint64_t *lens, const DecodeRow *rows,
+                               uint32_t n, uint32_t lds, uint64_t max_npix, bool any_rgb, uint8_t *pixels, int16_t *planes, int *status) {
+    if (n == 0) return hipSuccess;
+    if (lds > 64u * 1024u) {
+        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&k_decode8<DecMixed>),
+                                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)DECODE_LDS_LIMIT);
+        if (e != hipSuccess) return e;
+    }
+    hipLaunchKernelGGL(k_decode8<DecMixed>, dim3(n), dim3(64), lds, s, streams, offsets, lens, DecMixed{rows}, pixels, planes, status);
+    if (any_rgb) launch_conv_rows(s, rows, n, max_npix, planes, pixels, status);
+    return hipGetLastError();
+}
+
+hipError_t launch_decode8_lanes_waves(hipStream_t s, const uint8_t *streams, const uint64_t *offsets, const uint64_t *lens, const LaneWave *waves,
+                                      uint32_t nwaves, const LaneSlot *slots, uint32_t color, const DecodeRow *conv, uint32_t nconv,
+                                      uint64_t max_npix, uint8_t *pixels, int16_t *planes, uint32_t *table, int *status) {
+    if (nwaves == 0) return hipSuccess;
+    if (!color) {
+        hipLaunchKernelGGL((k_decode8_lanes<false, LaneMixed>), dim3(nwaves), dim3(64), 0, s, streams, offsets, lens, LaneMixed{waves, slots},
+                           (void *)pixels, table, status);
+        return hipGetLastError();
+    }
+    hipLaunchKernelGGL((k_decode8_lanes<true, LaneMixed>), dim3(nwaves), dim3(64), 0, s, streams, offsets, lens, LaneMixed{waves, slots},
+                       (void *)planes, table, status);
+    launch_conv_rows(s, conv, nconv, max_npix, planes, pixels, status);
+    return hipGetLastError();
+}
+
+hipError_t launch_decode16_rows(hipStream_t s, const uint8_t *streams, const uint64_t *offsets, const uint64_t *lens, const DecodeRow *rows,
+                                uint32_t n, uint32_t lds, uint64_t max_npix, bool any_rgb, uint16_t *pixels, int32_t *planes, uint32_t *table,
+                                uint32_t epoch0, int *status) {
+    if (n == 0) return hipSuccess;
+    if (lds > 64u * 1024u) {
+        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&k_decode16<DecMixed>),
+                                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)DECODE_LDS_LIMIT);
+        if (e != hipSuccess) return e;
+    }
+    hipLaunchKernelGGL(k_decode16<DecMixed>, dim3(n), dim3(64), lds, s, streams, offsets, lens, DecMixed{rows}, pixels, planes, table, epoch0,
+                       status);
+    if (any_rgb) launch_conv_rows(s, rows, n, max_npix, planes, pixels, status);
     return hipGetLastError();
 }
 

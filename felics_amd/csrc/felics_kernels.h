@@ -239,6 +239,46 @@ hipError_t launch_decode8_lanes(hipStream_t s, const uint8_t *streams, const uin
                                 uint32_t W, uint32_t H, uint32_t color, uint8_t *pixels, int16_t *planes, uint32_t *table, int *status);
 hipError_t launch_decode8(hipStream_t s, const uint8_t *streams, const uint64_t *offsets, const uint64_t *lens, uint32_t n,
                           uint32_t W, uint32_t H, uint32_t color, uint8_t *pixels, int16_t *planes, int *status);
+// The headers of n streams in device memory (felics_read_headers_device, felics_decompress_images_device): a lane per stream,
+// felics_read_header's checks in its order, every read inside [offsets[i], offsets[i] + lens[i]).  Fields are zero where
+// status != FELICS_OK.  dstatus: status, or for a valid header the decode call's own rules -- w * h < 2^32
+// (FELICS_E_INVALID_DIMENSIONS) and at least C * (64 + max(0, w * h - 2)) bits behind the header (FELICS_E_IO).
+struct DecodeHeader {
+    uint32_t W, H;
+    uint8_t color, depth;
+    int8_t status, dstatus;
+};
+hipError_t launch_read_headers(hipStream_t s, const uint8_t *streams, const uint64_t *offsets, const uint64_t *lens, uint32_t n,
+                               DecodeHeader *out);
+// ---- Mixed shapes in one decode call (felics_decompress_images_device).
+// A stream decoded by a wave of its own: k_decode8 / k_decode16 take blockIdx.x, the RGB conversions blockIdx.y as the row (scalar loads).
+struct DecodeRow {
+    uint32_t stream;     // index into offsets / lens / status
+    uint32_t W, H, color;
+    uint64_t out_off;    // byte offset of the frame in the caller's pixels
+    uint64_t plane_off;  // RGB: element offset of its Y / Co / Cg planes in the planes buffer
+};
+// k_decode8_lanes: a row per wave (every stream of a wave has one shape), a slot per lane
+struct LaneWave {
+    uint32_t W, H;
+    uint32_t first, n;   // slots first .. first + n - 1 (n <= 64; the lanes past n stay idle)
+};
+struct LaneSlot {
+    uint32_t stream;     // index into offsets / lens / status; the slot's index names its estimator table
+    uint32_t pad;
+    uint64_t out_off;    // element offset: gray, of the frame in the caller's pixels; RGB, of its planes in `planes`
+};
+// one launch per LDS class: lds = decode8_lds_bytes of the class's widest row; RGB rows through the int16 `planes`
+hipError_t launch_decode8_rows(hipStream_t s, const uint8_t *streams, const uint64_t *offsets, const uint64_t *lens, const DecodeRow *rows,
+                               uint32_t n, uint32_t lds, uint64_t max_npix, bool any_rgb, uint8_t *pixels, int16_t *planes, int *status);
+// waves of one colour; RGB: conv = a DecodeRow per slot for the conversion; `table` zeroed, decode8_lanes_table_bytes(slots, color) bytes
+hipError_t launch_decode8_lanes_waves(hipStream_t s, const uint8_t *streams, const uint64_t *offsets, const uint64_t *lens, const LaneWave *waves,
+                                      uint32_t nwaves, const LaneSlot *slots, uint32_t color, const DecodeRow *conv, uint32_t nconv,
+                                      uint64_t max_npix, uint8_t *pixels, int16_t *planes, uint32_t *table, int *status);
+// a pass of 16-bit rows: row j uses estimator table j
+hipError_t launch_decode16_rows(hipStream_t s, const uint8_t *streams, const uint64_t *offsets, const uint64_t *lens, const DecodeRow *rows,
+                                uint32_t n, uint32_t lds, uint64_t max_npix, bool any_rgb, uint16_t *pixels, int32_t *planes, uint32_t *table,
+                                uint32_t epoch0, int *status);
 
 // ---- 16-bit samples (felics_wide.hip): contexts 0..131070 and 15 Rice parameters (traits.rs:35-43).
 // The events of a batch are compacted into 64-bit records {context, Rice operand, sample index in its plane},

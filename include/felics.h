@@ -176,6 +176,41 @@ int felics_decompress_batch_device(felics_ctx *ctx, size_t n, const void *d_stre
                                    const uint64_t *lens, void *d_pixels, size_t d_pixels_cap, felics_header *hdr,
                                    int *status);
 
+/* The headers of n streams resident in device memory (stream i at d_streams + offsets[i], lens[i] bytes), read on the device in
+ * one launch and copied back once.  offsets / lens / hdrs / status are HOST arrays of n entries.  status[i] is exactly what
+ * felics_read_header returns for stream i's first min(lens[i], FELICS_HEADER_BYTES) bytes; hdrs[i] is that header, zeroed where
+ * status[i] != FELICS_OK.  Returns the first non-zero status; a HIP error or a refusal puts its own code in every status[i]
+ * (NULL pointers: FELICS_E_INVALID_ARGUMENT, nothing written).  No byte outside [offsets[i], offsets[i] + lens[i]) is read.
+ * Like the other synchronous entry points it refuses to run (FELICS_E_INVALID_ARGUMENT) while a felics_submit_batch_device
+ * ticket is outstanding; n = 0 returns FELICS_OK. */
+int felics_read_headers_device(felics_ctx *ctx, size_t n, const void *d_streams, const uint64_t *offsets, const uint64_t *lens,
+                               felics_header *hdrs, int *status);
+
+/* n streams of ANY shapes, colours and depths, resident in device memory (stream i at d_streams + offsets[i], lens[i] bytes),
+ * decoded in one call: what felics_decompress_batch_device is for one shape.  offsets / lens / pix_offsets / hdrs / status are
+ * HOST arrays of n entries; hdrs is optional.
+ *   - Output placement: frame i is written at d_pixels + pix_offsets[i], w * h * channels * bytes_per_sample bytes in the layout
+ *     the encoder takes.  Offsets are 16-byte aligned, ascending in stream order, and frames do not overlap.  A stream whose
+ *     header is invalid, or whose frame is empty, gets 0 bytes.  Bytes of d_pixels outside the frames are never written.
+ *   - Per-stream status: every stream has its own header and its own status; one bad stream does not fail the others (unlike
+ *     the same-shape call, where stream 0 names the shape).  Codes: the header codes of felics_read_header, then
+ *     FELICS_E_IO / _INVALID_VALUE / _INVALID_DIMENSIONS as for the same-shape call.  status[] is filled on every return.
+ *     hdrs[i] receives the header where felics_read_header would accept it, zeros otherwise.
+ *   - A header that claims more than the stream can hold is rejected before anything is sized: a valid stream of C planes has
+ *     at least C * (64 + max(0, w * h - 2)) bits behind its header.  A shorter stream gets FELICS_E_IO and no output space; a
+ *     header with w * h >= 2^32 gets FELICS_E_INVALID_DIMENSIONS.
+ *   - Buffer too small: if d_pixels_cap cannot hold the layout the call returns FELICS_E_BUFFER_TOO_SMALL, pix_offsets[0] holds
+ *     the capacity needed, hdrs is filled, nothing is written to d_pixels, the streams that would have been decoded get
+ *     FELICS_E_BUFFER_TOO_SMALL and the others keep their header status.
+ *   - Refusals as for the other synchronous entry points: FELICS_E_INVALID_ARGUMENT for NULL pointers or while a
+ *     felics_submit_batch_device ticket is outstanding, FELICS_E_HIP on a failed context; n = 0 returns FELICS_OK.
+ *   - The stream contract of felics_decompress_batch_device holds (complete in memory when the call is made; the kernels load
+ *     whole aligned words).  The same stream may be referenced several times.
+ * Returns the first non-zero status.  8-bit streams decode one wave per stream, or 64 streams of one shape per wave in calls of
+ * many 8-bit streams; 16-bit streams one wave per stream; streams whose rows do not fit the LDS on the host. */
+int felics_decompress_images_device(felics_ctx *ctx, size_t n, const void *d_streams, const uint64_t *offsets, const uint64_t *lens,
+                                    void *d_pixels, size_t d_pixels_cap, uint64_t *pix_offsets, felics_header *hdrs, int *status);
+
 /* Text for a code above; for FELICS_E_HIP felics_last_error(ctx) has the HIP message. */
 const char *felics_strerror(int code);
 const char *felics_last_error(const felics_ctx *ctx);
