@@ -30,7 +30,8 @@ const char *kStageNames[ST_COUNT] = {"planes", "hist", "offsets", "scatter", "sp
 static_assert(ST_COUNT <= FELICS_MAX_STAGES, "felics.h promises at most FELICS_MAX_STAGES stages");
 
 constexpr int SLICES = 12;              // at most; a submission uses lane.nslices of them
-constexpr int EV_PAIRS = SLICES + 2;     // launches of one stage per sub-batch that can be timed
+constexpr uint64_t PASS_MAX_CHAINS = 1u << 23;  // chains (plane x context) of one 8-bit pass at most: max_images_per_pass
+constexpr int EV_PAIRS = SLICES + 2;    // launches of one stage per sub-batch that can be timed
 constexpr int MAX_LANES = 4;            // upper bound of the submissions in flight (felics_submit_batch_device), each with streams and workspace of its own
 constexpr int DEFAULT_LANES = 2;        // what a context uses unless FELICS_LANES says otherwise (measured round 3: 2 lanes x 4 slices 3.03-3.06 ms per step,
                                         // 3 lanes x 3 slices 2.97-3.16, 4 lanes 3.18-3.47: the kernels are issue-bound, so more of them side by side gain nothing)
@@ -616,7 +617,15 @@ size_t max_images_per_pass(uint64_t npix, uint32_t planes, int depth) {
     // the records of a pass are numbered with 32 bits: tiles x records per tile (worst case)
     const uint64_t tiles = (npix + SORT_TILE - 1) / SORT_TILE;
     const uint64_t rec_per_image = tiles * planes * (tile_cap_max(NCTX, (uint32_t)std::min<uint64_t>(npix, SORT_TILE)) / REC);
-    return (size_t)std::max<uint64_t>(1, std::min(0xE0000000ull / per_image, 0xE0000000ull / rec_per_image));
+    // ... and a pass carries at most PASS_MAX_CHAINS = 2^23 chains (plane x context: 2^15 gray planes, 5 461 RGB images -- a batch
+    // of many tiny frames).  partial / chain_prog hold SLICES * 8 + 32 bytes per chain, so the per-chain workspace of a pass stops
+    // at 2^23 * 128 B = 1 GiB per lane (200 000 gray 8 x 8 frames as one pass held 9 GB), and felics_chain.hip numbers chains
+    // (plane * nctx + ctx) and sizes k_enum's and k_spine3's grids by them in 32 bits.  Not 2^24: k_enum runs one 256-thread
+    // workgroup per chain (planes rounded up to eight), and a grid of exactly 2^24 of them -- 2^32 work-items, a full pass of
+    // 2^16 gray planes -- is refused by the runtime ("invalid configuration argument")
+    const uint64_t chains_per_image = (uint64_t)planes * (planes == 3 ? nctx_of<int16_t>() : nctx_of<uint8_t>());
+    return (size_t)std::max<uint64_t>(
+        1, std::min<uint64_t>({0xE0000000ull / per_image, 0xE0000000ull / rec_per_image, PASS_MAX_CHAINS / chains_per_image}));
 }
 
 // Queues one sub-batch (cnt frames starting at frame `first` of d_pixels) on a lane: geometry, colour
