@@ -35,6 +35,7 @@ constexpr int EV_PAIRS = SLICES + 2;    // launches of one stage per sub-batch t
 constexpr int MAX_LANES = 4;            // upper bound of the submissions in flight (felics_submit_batch_device), each with streams and workspace of its own
 constexpr int DEFAULT_LANES = 2;        // what a context uses unless FELICS_LANES says otherwise (measured round 3: 2 lanes x 4 slices 3.03-3.06 ms per step,
                                         // 3 lanes x 3 slices 2.97-3.16, 4 lanes 3.18-3.47: the kernels are issue-bound, so more of them side by side gain nothing)
+enum AssignOn { ASSIGN_OWN, ASSIGN_FRONT, ASSIGN_TAIL };  // the stream k_assign3 is queued on (felics_ctx_create)
 int lanes_from_env() {
     if (const char *e = getenv("FELICS_LANES")) return std::max(1, std::min(atoi(e), MAX_LANES));
     return DEFAULT_LANES;
@@ -51,7 +52,7 @@ struct DevBuf {
 struct Lane {
     hipStream_t stream = nullptr;      // spine slices
     hipStream_t front = nullptr;       // planes, hist, offsets, scatter slices
-    hipStream_t kstream = nullptr;     // assign slices (k of the events)
+    hipStream_t kstream = nullptr;     // assign slices (k of the events); with four lanes there is none and they go to the front stream (felics_ctx_create)
     hipStream_t tail = nullptr;        // lengths, bit scan, pack slices
     hipEvent_t slice_done[SLICES] = {};
     hipEvent_t spine_done[SLICES] = {};
@@ -64,9 +65,11 @@ struct Lane {
     size_t h_sizes_cap = 0;
     // 8-bit samples, tile-local layout (felics_kernels.h): ev / pix_of / k_sorted = the tiles' slots (event value, pixel, k), counts = the
     // run table, tile_slots, desc / block_state = the records of the chains in chain order (place + events, start state), partial =
-    // the chains' record ranges per slice, chain_prog = the chains' running state
-    DevBuf planes, counts, chain_prog, scalars, evs, pix_of, k_map, k_sorted, block_state, group_bits, tile_slots, desc,
+    // the chains' record ranges per slice
+    // (8-bit: image_bytes is the head of the lane's CLEARED BLOCK -- sizes, error word, counters, plane sums, chain_state: run_lane)
+    DevBuf planes, counts, scalars, evs, pix_of, k_map, k_sorted, block_state, group_bits, tile_slots, desc,
         tile_bits, tile_bitoff, plane_sums, image_bytes, image_off, partial, status, edge_first, edge_last, pscratch;
+    uint64_t *plane_base = nullptr;   // the sub-batch's plane bases (behind its plane carries; pack_exact reads them)
     DevBuf wrecs[2], wtile_cnt, wmeta, whist, wdigtot, heads, wlong;  // 16-bit samples: event records (sort double buffer), tile counts, plane ranges, digit histograms, chain heads
     uint32_t epoch = 0;               // sub-batches this lane has run: block tags are (epoch, slice)
     // the submission in flight on this lane (felics_submit_batch_device .. felics_wait_batch)
@@ -116,6 +119,7 @@ struct felics_ctx {
     bool pack_tickets = false;
     bool two_pass = false;      // FELICS_TWO_PASS=1, or a look-back gave up with ticketed tiles as well: lengths + pack kernels
     bool own_tails = false;     // FELICS_OWN_TAILS=1: a tail stream per lane (pack kernels of two submissions side by side, tiles by ticket)
+    int assign_on = ASSIGN_OWN; // up to three lanes; ASSIGN_FRONT with four (felics_ctx_create); FELICS_ASSIGN_STREAM=own|front|tail (tuning sweeps: profiles/hw_queues.txt)
     bool serial = false;        // FELICS_SERIAL=1 (profiling tools: every kernel alone): all stages of a lane on one stream
     bool test_timeout = false;  // FELICS_TEST_TIMEOUT=1: every wait for the GPU reports a time-out (tests of the failed state)
     bool test_lookback = false; // FELICS_TEST_LOOKBACK_FAIL=1: pretend the first single-pass submission gave up (tests)
@@ -290,9 +294,11 @@ void header_bytes(uint8_t *o, uint32_t w, uint32_t h, int color, int depth) {
 }
 
 // Everything one sub-batch of 8-bit frames needs, queued without waiting for the host (tile-local layout, felics_kernels.h):
-//   front stream : the front kernel (classify + sort a tile's events, once) slice by slice
-//   spine stream : behind every front slice the records of its chains (k_enum) and the spine launch that walks them
-//   k stream     : behind every spine launch the k of the slice's events (k_assign3)
+//   front stream : one fill that clears the sub-batch's counters, sums and chain states; then slice by slice the front kernel
+//                  (classify + sort a tile's events, once) and the records of the slice's chains (k_enum)
+//   spine stream : behind every k_enum the spine launch that walks the slice's chains
+//   k stream     : behind every spine launch the k of the slice's events (k_assign3); a context of four lanes has no k stream
+//                  and queues them on the front stream, behind the NEXT slice's two launches
 //   tail stream  : behind every k launch -- when every stream has a fixed slot in the output -- the packed bits of that
 //                  slice's tiles (k_pack_t: code lengths, tile offsets by look-back, packing in one kernel); RGB planes 1, 2
 //                  go to scratch slots and are moved behind plane 0 at the end (the offset of planes 1 and 2 needs the size
@@ -322,14 +328,19 @@ int run_lane(felics_ctx *ctx, Lane &l, uint8_t *d_out, uint64_t slot_stride) {
     if ((rc = reserve(ctx, l.desc, recs * 8 + 64)) != 0) return rc;
     if ((rc = reserve(ctx, l.block_state, recs * 16 + 64)) != 0) return rc;         // state16
     if ((rc = reserve(ctx, l.partial, (size_t)SLICES * nchains * 8)) != 0) return rc;  // chain_seg per slice
-    if ((rc = reserve(ctx, l.chain_prog, nchains * 32)) != 0) return rc;            // chain_state
-    if ((rc = reserve(ctx, l.scalars, 64 + 4 * (SLICES + 2) + 4 * SLICES)) != 0) return rc;
     if (!fused && (rc = reserve(ctx, l.k_map, nsamples + STAGE_PAD)) != 0) return rc;
     if (!fused && (rc = reserve(ctx, l.group_bits, (size_t)g.nplanes * g.pack_tiles * PACK_THREADS * 2)) != 0) return rc;
     if ((rc = reserve(ctx, l.tile_bits, (size_t)g.nplanes * g.pack_tiles * 4)) != 0) return rc;
     if ((rc = reserve(ctx, l.tile_bitoff, (size_t)g.nplanes * g.pack_tiles * 8)) != 0) return rc;
-    if ((rc = reserve(ctx, l.plane_sums, (size_t)g.nplanes * 16)) != 0) return rc;  // carry[nplanes], base[nplanes]
-    if ((rc = reserve(ctx, l.image_bytes, (size_t)g.nimages * 8)) != 0) return rc;
+    // The cleared block: everything a sub-batch wants zero when it starts, in one allocation, so that ONE fill at the head of the
+    // front stream clears it (the lane is idle then: its last sub-batch's sizes have been waited for) and ONE copy brings the
+    // sizes, the error word and the flags back:
+    //   image_bytes[nimages] | d_error, d_flags | d_tickets[SLICES + 2], d_nrec[SLICES] | carry[nplanes], base[nplanes] | chain_state
+    const size_t o_words = (size_t)g.nimages * 8, o_counters = o_words + 8;
+    const size_t o_sums = (o_counters + 4 * (2 * SLICES + 2) + 15) & ~(size_t)15;
+    const size_t o_chain = (o_sums + (size_t)g.nplanes * 16 + 255) & ~(size_t)255;
+    const size_t cleared = o_chain + nchains * 32;
+    if ((rc = reserve(ctx, l.image_bytes, cleared)) != 0) return rc;
     if ((rc = reserve(ctx, l.image_off, (size_t)(g.nimages + 1) * 8)) != 0) return rc;
     if ((rc = reserve_zeroed(ctx, l.status, (size_t)g.nplanes * g.pack_tiles * 8)) != 0) return rc;
     if ((rc = reserve(ctx, l.edge_first, (size_t)g.nplanes * g.pack_tiles * 4)) != 0) return rc;
@@ -341,12 +352,17 @@ int run_lane(felics_ctx *ctx, Lane &l, uint8_t *d_out, uint64_t slot_stride) {
         HIP_TRY(ctx, hipHostMalloc((void **)&l.h_sizes, hs * 8 + 64, hipHostMallocDefault));
         l.h_sizes_cap = hs;
     }
-    hipStream_t s = l.stream, f = l.front, ks = l.kstream, tl = l.tail;
+    hipStream_t s = l.stream, f = l.front, tl = l.tail;
+    // k_assign3 of slice q follows spine[q] and goes in front of pack[q]: on the lane's k stream, or -- four lanes: the low pool is
+    // full of front streams -- on the front stream behind enum[q + 1], which does not wait for the spine
+    hipStream_t ks = ctx->assign_on == ASSIGN_TAIL ? tl : l.kstream ? l.kstream : f;
     if (ctx->serial) f = ks = tl = s;  // FELICS_SERIAL (profiling: every kernel alone): one stream, same order of launches
     const T *d_planes = (const T *)l.d_planes;
-    auto *chain_state = (uint32_t *)l.chain_prog.p;
-    auto *plane_carry = (uint64_t *)l.plane_sums.p;
+    uint8_t *block = (uint8_t *)l.image_bytes.p;
+    auto *chain_state = (uint32_t *)(block + o_chain);
+    auto *plane_carry = (uint64_t *)(block + o_sums);
     auto *plane_base = plane_carry + g.nplanes;
+    l.plane_base = plane_base;
     if (++l.epoch >= 0x03FFFFFFu) l.epoch = 1;
     if ((l.epoch & 0x3FFFFu) == 0) HIP_TRY(ctx, hipMemsetAsync(l.status.p, 0, l.status.cap, f));  // look-back tags: 18 epoch bits
     const uint32_t epoch = l.epoch;
@@ -356,10 +372,10 @@ int run_lane(felics_ctx *ctx, Lane &l, uint8_t *d_out, uint64_t slot_stride) {
         if ((rc = reserve(ctx, l.pscratch, (size_t)(target.plane_slot * g.nimages * (g.planes_per_image - 1)))) != 0) return rc;
         target.scratch = (uint8_t *)l.pscratch.p;
     }
-    uint32_t *d_error = (uint32_t *)l.scalars.p + 8;  // look-back watchdog of the single-pass pack
-    uint32_t *d_flags = (uint32_t *)l.scalars.p + 9;  // TL_FLAG_*: the front kernel's order check and tile overflow, the spine's self-check (read back together with d_error)
-    uint32_t *d_tickets = (uint32_t *)l.scalars.p + 16;  // one per pack launch of this sub-batch: tiles are handed out in order
-    uint32_t *d_nrec = (uint32_t *)l.scalars.p + 16 + SLICES + 2;  // records per slice
+    uint32_t *d_error = (uint32_t *)(block + o_words);  // look-back watchdog of the single-pass pack
+    uint32_t *d_flags = d_error + 1;  // TL_FLAG_*: the front kernel's order check and tile overflow, the spine's self-check (read back together with d_error)
+    uint32_t *d_tickets = (uint32_t *)(block + o_counters);  // one per pack launch of this sub-batch: tiles are handed out in order
+    uint32_t *d_nrec = d_tickets + SLICES + 2;  // records per slice
     const TileLocal<ET> tloc{(ET *)l.evs.p, (uint16_t *)l.pix_of.p, (uint8_t *)l.k_sorted.p, (uint32_t *)l.counts.p, (uint32_t *)l.tile_slots.p, cap};
     l.m_tickets = ctx->pack_tickets;
     l.m_fused = fused;
@@ -378,13 +394,30 @@ int run_lane(felics_ctx *ctx, Lane &l, uint8_t *d_out, uint64_t slot_stride) {
         for (DevBuf *b : bufs)
             if (b->p) HIP_TRY(ctx, hipMemsetAsync(b->p, 0xA5, b->cap, f));
     }
-    HIP_TRY(ctx, hipMemsetAsync(chain_state, 0, nchains * 32, f));
-    HIP_TRY(ctx, hipMemsetAsync(d_flags, 0, 4, f));
-    HIP_TRY(ctx, hipMemsetAsync(d_nrec, 0, 4 * SLICES, f));
+    HIP_TRY(ctx, hipMemsetAsync(block, 0, cleared, f));  // (the tail's words too: every tail launch follows an assign launch, and that this fill)
     // (FELICS_TEST_SCATTER_ORDER: the atomically ranked kernel reports a violation whatever it produced; the ballot-ranked form is
     // the remedy and is checked for real)
     const uint32_t front_mode = ctx->scatter_ballot ? FRONT_SAFE_RANK : ctx->test_scatter_order ? FRONT_TEST_VIOLATION : 0u;
     if (!ctx->scatter_ballot) ctx->stats.sorted_event_sorts++;
+    // behind every spine launch, k of the slice's events and -- when every stream has a fixed slot -- the packed bits of the slice's
+    // tiles on the tail stream.  Queued one slice late, so that on the front stream the k launch stands behind the NEXT slice's
+    // front and enum launches (which do not wait for the spine) and not in front of them.
+    auto behind_spine = [&](int q) -> int {
+        HIP_TRY(ctx, hipStreamWaitEvent(ks, l.spine_done[q], 0));
+        if (bounds[q + 1] != bounds[q]) {
+            StageTimer t(ctx, l, ST_ASSIGN, ks, true);
+            launch_assign3<ET>(ks, tloc, (const uint4 *)l.block_state.p, g, bounds[q], bounds[q + 1]);
+        }
+        HIP_TRY(ctx, hipEventRecord(l.assign_done[q], ks));
+        if (!fused) return FELICS_OK;
+        HIP_TRY(ctx, hipStreamWaitEvent(tl, l.assign_done[q], 0));
+        if (bounds[q + 1] == bounds[q]) return FELICS_OK;
+        StageTimer t(ctx, l, ST_PACK, tl, true);
+        launch_pack_t<T>(tl, d_planes, tloc.kq, tloc.pix, tloc.ev, tloc.tile_slots, cap, (uint64_t *)l.status.p, (uint64_t *)l.tile_bitoff.p,
+                         (uint32_t *)l.tile_bits.p, plane_carry, (uint32_t *)l.edge_first.p, (uint32_t *)l.edge_last.p, d_error, target, g,
+                         bounds[q], bounds[q + 1], epoch, ctx->pack_tickets ? d_tickets + q : nullptr);
+        return FELICS_OK;
+    };
     for (int q = 0; q < ns; q++) {
         if (bounds[q + 1] != bounds[q]) {
             {
@@ -396,39 +429,18 @@ int run_lane(felics_ctx *ctx, Lane &l, uint8_t *d_out, uint64_t slot_stride) {
             launch_enum(f, tloc.runtab, slice_of(q), g, bounds[q], bounds[q + 1], cap);
         }
         HIP_TRY(ctx, hipEventRecord(l.slice_done[q], f));
-    }
-    // ---- spine stream: the walk along every chain
-    for (int q = 0; q < ns; q++) {
+        // ---- spine stream: the walk along every chain
         HIP_TRY(ctx, hipStreamWaitEvent(s, l.slice_done[q], 0));
         if (bounds[q + 1] != bounds[q]) {
             StageTimer t(ctx, l, ST_SPINE, s, true);
             launch_spine3<ET>(s, tloc.ev, slice_of(q), chain_state, d_flags, g);
         }
         HIP_TRY(ctx, hipEventRecord(l.spine_done[q], s));
+        if (q > 0 && (rc = behind_spine(q - 1)) != 0) return rc;
     }
-    // ---- k stream: behind every spine launch, k of the slice's events
-    for (int q = 0; q < ns; q++) {
-        HIP_TRY(ctx, hipStreamWaitEvent(ks, l.spine_done[q], 0));
-        if (bounds[q + 1] != bounds[q]) {
-            StageTimer t(ctx, l, ST_ASSIGN, ks, true);
-            launch_assign3<ET>(ks, tloc, (const uint4 *)l.block_state.p, g, bounds[q], bounds[q + 1]);
-        }
-        HIP_TRY(ctx, hipEventRecord(l.assign_done[q], ks));
-    }
-    // ---- tail stream
-    HIP_TRY(ctx, hipMemsetAsync(plane_carry, 0, (size_t)g.nplanes * 16, tl));
-    HIP_TRY(ctx, hipMemsetAsync(d_error, 0, 4, tl));
-    HIP_TRY(ctx, hipMemsetAsync(d_tickets, 0, 4 * (SLICES + 2), tl));
+    if ((rc = behind_spine(ns - 1)) != 0) return rc;
+    // ---- tail stream: the sizes, and the streams' last touches
     if (fused) {
-        // behind every k launch: the packed bits of that slice's tiles
-        for (int q = 0; q < ns; q++) {
-            HIP_TRY(ctx, hipStreamWaitEvent(tl, l.assign_done[q], 0));
-            if (bounds[q + 1] == bounds[q]) continue;
-            StageTimer t(ctx, l, ST_PACK, tl, true);
-            launch_pack_t<T>(tl, d_planes, tloc.kq, tloc.pix, tloc.ev, tloc.tile_slots, cap, (uint64_t *)l.status.p, (uint64_t *)l.tile_bitoff.p,
-                             (uint32_t *)l.tile_bits.p, plane_carry, (uint32_t *)l.edge_first.p, (uint32_t *)l.edge_last.p, d_error, target, g,
-                             bounds[q], bounds[q + 1], epoch, ctx->pack_tickets ? d_tickets + q : nullptr);
-        }
         StageTimer t(ctx, l, ST_ZERO, tl);
         launch_finish_sizes(tl, plane_carry, plane_base, (uint64_t *)l.image_bytes.p, g);
         launch_join_edges(tl, (const uint64_t *)l.tile_bitoff.p, (const uint32_t *)l.tile_bits.p,
@@ -463,9 +475,8 @@ int run_lane(felics_ctx *ctx, Lane &l, uint8_t *d_out, uint64_t slot_stride) {
         }
     }
     HIP_TRY(ctx, hipGetLastError());
-    HIP_TRY(ctx, hipMemcpyAsync(l.h_sizes, l.image_bytes.p, (size_t)g.nimages * 8, hipMemcpyDeviceToHost, tl));
     l.h_sizes[g.nimages] = 0;
-    HIP_TRY(ctx, hipMemcpyAsync(&l.h_sizes[g.nimages], d_error, 8, hipMemcpyDeviceToHost, tl));  // d_error | d_flags << 32
+    HIP_TRY(ctx, hipMemcpyAsync(l.h_sizes, block, o_counters, hipMemcpyDeviceToHost, tl));  // the sizes, then d_error | d_flags << 32
     HIP_TRY(ctx, hipEventRecord(l.sized, tl));
     if (ctx->profiling) HIP_TRY(ctx, hipEventRecord(l.span_end, tl));
     return FELICS_OK;
@@ -510,6 +521,7 @@ int run_wide(felics_ctx *ctx, Lane &l, uint8_t *d_out, uint64_t slot_stride) {
     const T *d_planes = (const T *)l.d_planes;
     auto *plane_carry = (uint64_t *)l.plane_sums.p;
     auto *plane_base = plane_carry + g.nplanes;
+    l.plane_base = plane_base;
     auto *nheads = (uint32_t *)l.scalars.p;
     if (ctx->poison) {
         DevBuf *bufs[] = {&l.wrecs[0], &l.wrecs[1], &l.wtile_cnt, &l.wmeta, &l.whist, &l.heads, &l.k_map,
@@ -570,7 +582,7 @@ template <typename T>
 int pack_exact(felics_ctx *ctx, Lane &l, uint8_t *d_out) {
     const Geometry &g = l.g;
     hipStream_t s = l.tail;
-    auto *plane_base = (uint64_t *)l.plane_sums.p + g.nplanes;
+    const uint64_t *plane_base = l.plane_base;
     {
         StageTimer t(ctx, l, ST_ZERO, s);
         launch_zero_streams(s, (uint32_t *)d_out, (const uint64_t *)l.image_off.p, g);
@@ -1626,10 +1638,18 @@ int felics_ctx_create(int device, felics_ctx **out) {
     felics_ctx *ctx = new (std::nothrow) felics_ctx();
     if (!ctx) return FELICS_E_IO;
     ctx->device = device;
-    // The lanes' streams want hardware queues of their own; ROCm's default is 4 per process and the caller's stream
-    // takes one.
-    // (A library does not touch the process environment: felics_amd/api.py, bench.py and the command lines ask for the
-    // hardware queues -- GPU_MAX_HW_QUEUES -- before the runtime starts.)
+    // Hardware queues: the HIP runtime keeps one pool of them PER STREAM PRIORITY (low, normal, high), each capped by
+    // GPU_MAX_HW_QUEUES -- 4 unless the process was started with another value -- and a stream created beyond the cap shares the
+    // in-order queue of an earlier one of its priority: its kernels then wait behind kernels they do not depend on (up to round 5
+    // five high-priority streams: at the default cap one lane's assign launches stood behind its own next spine launch, +5 % per
+    // step).  So the stage graph is cut to fit the default, and no environment variable is needed (profiles/hw_queues.txt):
+    //   per lane  : `stream` (spine, high), `front` (front + enum, low), `kstream` (assign, low)
+    //   all lanes : one `tail` (pack, high)
+    //   two lanes 3 high + 4 low: a queue each.  Three lanes 4 high + 6 low: two pairs of low streams share, and which is the
+    //   runtime's choice -- measured no slower than round 5's graph and faster than the sharing the library could choose (the first
+    //   lane alone with a k stream, or none).  Four lanes: no `kstream` (the assign launches on the front stream, whose launches they
+    //   follow anyway) and the tail at normal priority, since the spines fill the high pool: 4 high + 4 low + 1 normal.
+    // The normal pool is otherwise the caller's (torch's streams), plus the host-buffer path's two copy streams.
     ctx->nlanes = lanes_from_env();
     ctx->poison = getenv("FELICS_POISON") != nullptr;
     ctx->two_pass = getenv("FELICS_TWO_PASS") != nullptr;
@@ -1639,6 +1659,8 @@ int felics_ctx_create(int device, felics_ctx **out) {
     ctx->test_scatter_order = getenv("FELICS_TEST_SCATTER_ORDER") != nullptr;
     ctx->pack_tickets = ctx->own_tails = getenv("FELICS_OWN_TAILS") != nullptr;
     ctx->serial = getenv("FELICS_SERIAL") != nullptr;
+    ctx->assign_on = ctx->nlanes > 3 ? ASSIGN_FRONT : ASSIGN_OWN;
+    if (const char *e = getenv("FELICS_ASSIGN_STREAM")) ctx->assign_on = !strcmp(e, "tail") ? ASSIGN_TAIL : !strcmp(e, "front") ? ASSIGN_FRONT : ASSIGN_OWN;
     ctx->test_timeout = getenv("FELICS_TEST_TIMEOUT") != nullptr;
     if (const char *e = getenv("FELICS_SLICES")) ctx->slices_blocking = std::max(1, std::min(atoi(e), SLICES));
     if (const char *e = getenv("FELICS_SLICES_QUEUED")) ctx->slices_queued = std::max(1, std::min(atoi(e), SLICES));  // (tuning sweeps: profiles/tools/sweep_queue.sh)
@@ -1652,12 +1674,13 @@ int felics_ctx_create(int device, felics_ctx **out) {
     // 2.53-2.65 ms, the differences inside the run-to-run spread (profiles/r05/experiments.txt); blocking calls do not care.
     int prio_low = 0, prio_high = 0;
     (void)hipDeviceGetStreamPriorityRange(&prio_low, &prio_high);  // numerically: low >= high
-    int prio_spine = prio_high, prio_front = prio_low, prio_tail = prio_high;
+    int prio_spine = prio_high, prio_front = prio_low, prio_tail = ctx->nlanes > 3 && !ctx->own_tails ? (prio_low + prio_high) / 2 : prio_high;
+    const int prio_assign = prio_low;  // (high up to round 5: the fifth stream of the high pool)
     for (int li = 0; li < ctx->nlanes; li++) {
         Lane &l = ctx->lanes[li];
         ok = ok && hipStreamCreateWithPriority(&l.stream, hipStreamNonBlocking, prio_spine) == hipSuccess;
         ok = ok && hipStreamCreateWithPriority(&l.front, hipStreamNonBlocking, prio_front) == hipSuccess;
-        ok = ok && hipStreamCreateWithPriority(&l.kstream, hipStreamNonBlocking, prio_tail) == hipSuccess;
+        if (ctx->assign_on == ASSIGN_OWN) ok = ok && hipStreamCreateWithPriority(&l.kstream, hipStreamNonBlocking, prio_assign) == hipSuccess;
         // One tail stream for all lanes: the pack kernels of two submissions run one after the other (measured faster:
         // 4.6 vs 4.8 ms per step).  FELICS_OWN_TAILS=1 gives every lane its own; that is safe since the pack kernels hand
         // out their tiles by ticket (FusedArgs::ticket), it just is not faster.
@@ -1700,7 +1723,7 @@ void felics_ctx_destroy(felics_ctx *ctx) {
     for (Lane &l : ctx->lanes)
         if (l.tail) (void)hipStreamSynchronize(l.tail);
     for (Lane &l : ctx->lanes) {
-        DevBuf *bufs[] = {&l.planes, &l.counts, &l.chain_prog, &l.scalars, &l.evs, &l.pix_of, &l.k_map, &l.k_sorted, &l.tile_slots, &l.desc,
+        DevBuf *bufs[] = {&l.planes, &l.counts, &l.scalars, &l.evs, &l.pix_of, &l.k_map, &l.k_sorted, &l.tile_slots, &l.desc,
                           &l.block_state, &l.group_bits, &l.tile_bits, &l.tile_bitoff, &l.plane_sums, &l.image_bytes, &l.image_off,
                           &l.partial, &l.status, &l.edge_first, &l.edge_last, &l.pscratch, &l.wrecs[0], &l.wrecs[1], &l.wtile_cnt, &l.wmeta, &l.whist, &l.wdigtot, &l.heads, &l.wlong};
         for (DevBuf *b : bufs) release(*b);
