@@ -69,6 +69,16 @@ class _CImage(C.Structure):  # felics_image
     _fields_ = [("pixels", C.c_void_p), ("width", C.c_uint32), ("height", C.c_uint32), ("color", C.c_int), ("depth", C.c_int)]
 
 
+class _CView(C.Structure):  # felics_view
+    _fields_ = [("data", C.c_void_p), ("width", C.c_uint32), ("height", C.c_uint32), ("color", C.c_int), ("depth", C.c_int),
+                ("row_stride", C.c_int64), ("pixel_stride", C.c_int64), ("channel_stride", C.c_int64)]
+
+
+class _CViewStats(C.Structure):  # felics_view_stats
+    _fields_ = [("views", C.c_uint64), ("dense", C.c_uint64), ("in_place", C.c_uint64), ("gathered", C.c_uint64),
+                ("bytes_staged", C.c_uint64)]
+
+
 class Header:  # format.rs:44-49
     def __init__(self, color_type, pixel_depth, width, height):
         self.color_type = ColorType(color_type)
@@ -93,6 +103,7 @@ EXPORTS = [
     "felics_lane_count", "felics_ctx_lane_count", "felics_get_span_ms", "felics_decompress_with_header", "felics_get_stats", "felics_decompress_batch_device",
     "felics_compress_images", "felics_compress_images_device", "felics_read_headers_device",
     "felics_decompress_images_device",
+    "felics_compress_views_device", "felics_view_extent", "felics_get_view_stats",
 ]
 
 _lib = None
@@ -153,6 +164,9 @@ def lib():
                                              C.POINTER(C.c_int)]
     L.felics_decompress_images_device.argtypes = [vp, sz, vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), vp, sz, C.POINTER(C.c_uint64),
                                                   C.POINTER(_CHeader), C.POINTER(C.c_int)]
+    L.felics_compress_views_device.argtypes = [vp, sz, C.POINTER(_CView), vp, vp, sz, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+    L.felics_view_extent.argtypes = [C.POINTER(_CView), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
+    L.felics_get_view_stats.argtypes = [vp, C.POINTER(_CViewStats), sz]
     L.felics_strerror.argtypes = [C.c_int]
     L.felics_strerror.restype = C.c_char_p
     L.felics_last_error.argtypes = [vp]
@@ -183,6 +197,53 @@ def _describe(image):
     else:
         raise TypeError("Unsupported image format: shape %s" % (image.shape,))
     return image, image.shape[1], image.shape[0], color, depth
+
+
+def _cview(view):
+    """A view tuple (ptr, w, h, color, depth, row_stride, pixel_stride, channel_stride) as a felics_view."""
+    p, w, h, c, d, rs, ps, cs = view
+    return _CView(int(p) if p else None, int(w), int(h), int(c), int(d), int(rs), int(ps), int(cs))
+
+
+def view_extent(view):
+    """felics_view_extent: the half-open byte range (lo, hi) relative to the view's pointer that an encode of it may read; the
+    view is checked exactly as Encoder.compress_views_device checks it (FelicsError otherwise).  Host only, needs no GPU."""
+    lo, hi = C.c_int64(0), C.c_int64(0)
+    v = _cview(view)
+    rc = lib().felics_view_extent(C.byref(v), C.byref(lo), C.byref(hi))
+    if rc != 0:
+        raise FelicsError(rc)
+    return int(lo.value), int(hi.value)
+
+
+def view_of_array(array):
+    """The view tuple of an object with __cuda_array_interface__ (a torch tensor on ROCm, a cupy array): shape (H, W) is gray,
+    (H, W, 3) RGB; typestr |u1 / <u2 gives the depth; strides (bytes, None for dense) are taken as given -- so a slice
+    t[y0:y1, x0:x1], rgba[..., :3] and chw.permute(1, 2, 0) are views of the memory they came from, no copy made."""
+    cai = array.__cuda_array_interface__
+    shape = tuple(int(v) for v in cai["shape"])
+    typestr = cai["typestr"]
+    if typestr in ("|u1", "<u1", "u1"):
+        depth, size = PixelDepth.Eight, 1
+    elif typestr == "<u2":
+        depth, size = PixelDepth.Sixteen, 2
+    else:
+        raise TypeError("Unsupported image format: %s" % typestr)
+    if len(shape) == 2:
+        color = ColorType.Gray
+    elif len(shape) == 3 and shape[2] == 3:
+        color = ColorType.Rgb
+    else:
+        raise TypeError("Unsupported image format: shape %s" % (shape,))
+    strides = cai.get("strides")
+    if strides is None:  # C-contiguous
+        strides, step = [], size
+        for extent in reversed(shape):
+            strides.insert(0, step)
+            step *= extent
+    strides = [int(v) for v in strides]
+    ptr = int(cai["data"][0]) if shape[0] * shape[1] else 0
+    return (ptr, shape[1], shape[0], color, depth, strides[0], strides[1], strides[2] if len(shape) == 3 else 0)
 
 
 class Encoder:
@@ -287,6 +348,35 @@ class Encoder:
         if rc != 0:
             self._raise(rc)
         return offs[:n], lens[:n]
+
+    def compress_views_device(self, views, d_out, d_out_cap, ready_event=None):
+        """felics_compress_views_device: views = [(device pointer, w, h, color, depth, row_stride, pixel_stride, channel_stride), ...]
+        (strides in bytes, signed), streams into d_out (device).  ready_event: a hipEvent_t handle (torch: Event.cuda_event) recorded
+        behind the producer of the views; the library's streams wait for it, the host does not.  Returns (offsets, lens)."""
+        n = len(views)
+        cv = (_CView * max(n, 1))(*[_cview(v) for v in views])
+        offs = np.zeros(max(n, 1), dtype=np.uint64)
+        lens = np.zeros(max(n, 1), dtype=np.uint64)
+        rc = lib().felics_compress_views_device(self._h, n, cv, int(ready_event) if ready_event else None, d_out, d_out_cap,
+                                                offs.ctypes.data_as(C.POINTER(C.c_uint64)), lens.ctypes.data_as(C.POINTER(C.c_uint64)))
+        if rc == -8:
+            raise FelicsError(rc, "need %d bytes" % int(lens[0]))
+        if rc != 0:
+            self._raise(rc)
+        return offs[:n], lens[:n]
+
+    def compress_arrays_device(self, arrays, d_out, d_out_cap, ready_event=None):
+        """compress_views_device on objects with __cuda_array_interface__ (view_of_array): slices, channel selections and permuted
+        tensors are encoded from the memory they lie in."""
+        return self.compress_views_device([view_of_array(a) for a in arrays], d_out, d_out_cap, ready_event)
+
+    def view_stats(self):
+        """felics_get_view_stats: views seen, and how they were read (dense / in_place / gathered, bytes_staged); cumulative."""
+        st = _CViewStats()
+        rc = lib().felics_get_view_stats(self._h, C.byref(st), C.sizeof(st))
+        if rc != 0:
+            self._raise(rc)
+        return {k: int(getattr(st, k)) for k, _ in _CViewStats._fields_}
 
     def compress_batch_host(self, pixel_ptrs, n, w, h, color, depth, out_ptrs, caps):
         """felics_compress_batch on raw HOST pointers (lists of n addresses: frames in, buffers of caps[i] bytes out): the

@@ -152,6 +152,11 @@ struct felics_ctx {
     hipEvent_t wait_before_submit = nullptr;            // the next sub-batch's first kernel waits for this event (set around one submit)
     DevBuf mix_in, mix_stage, mix_out, mix_redo;  // felics_compress_images*: 16-bit frames gathered per shape and their streams, the first
                                                   // run of a call whose buffer cannot hold the slots, frames gathered for a remedy
+    // felics_compress_views_device: the caller's ready event (every stream waits for it before it first reads a view or writes the
+    // output: wait_ready), the dense copies of gray8 views that cannot be read in place, the counts of felics_get_view_stats
+    hipEvent_t view_ready = nullptr;
+    DevBuf view_stage;
+    felics_view_stats vstats = {};
     DevBuf own;      // encode_device's own output when the caller gives none (the host entry point's fall-back for a chunk whose streams outgrew their slots)
     DevBuf dec_meta, dec_planes;  // GPU decoder: offsets | lens | status of a batch; Y / Co / Cg planes of RGB streams
     DevBuf dec_planes16;          // mixed decode call: the int32 planes of its RGB16 streams (beside dec_planes, used at the same time)
@@ -654,6 +659,7 @@ int launch_sub_batch(felics_ctx *ctx, Lane &l, size_t first, size_t cnt, const v
     int rc;
     Geometry &g = l.g;
     g.mixed = nullptr;
+    g.pitched = nullptr;
     g.W = w;
     g.H = h;
     g.npix = (uint32_t)npix;
@@ -914,7 +920,35 @@ struct MixImage {
     uint64_t npix;
     uint32_t planes;
     size_t frame_bytes;
+    // felics_compress_views_device: the frame is not dense at px but the view vr -- read where it lies by the mixed path (gray8
+    // rows `pitch` bytes apart; RGB8 of any strides through the plane transform), gathered into a dense frame where a path wants
+    // one (16-bit groups, remedies: stage_frame)
+    bool view = false;
+    uint64_t pitch = 0;
+    ViewRow vr = {};
 };
+
+// The caller's ready event in front of a stream's first access to a view or to the output (felics_compress_views_device).
+int wait_ready(felics_ctx *ctx, hipStream_t s) {
+    if (ctx->view_ready) HIP_TRY(ctx, hipStreamWaitEvent(s, ctx->view_ready, 0));
+    return FELICS_OK;
+}
+
+// Image m as a dense frame at dst: a copy, or the gather of its view (counted: felics_view_stats::bytes_staged).
+int stage_frame(felics_ctx *ctx, hipStream_t s, void *dst, const MixImage &m) {
+    if (!m.frame_bytes) return FELICS_OK;
+    if (!m.view) {
+        HIP_TRY(ctx, hipMemcpyAsync(dst, m.px, m.frame_bytes, hipMemcpyDeviceToDevice, s));
+        return FELICS_OK;
+    }
+    if (m.depth == FELICS_DEPTH_16)
+        launch_gather_view<uint16_t>(s, m.vr, m.w, m.h, m.planes, (uint16_t *)dst);
+    else
+        launch_gather_view<uint8_t>(s, m.vr, m.w, m.h, m.planes, (uint8_t *)dst);
+    HIP_TRY(ctx, hipGetLastError());
+    ctx->vstats.bytes_staged += m.frame_bytes;
+    return FELICS_OK;
+}
 
 MixImage mix_image(const felics_image &im) {
     MixImage m;
@@ -995,12 +1029,19 @@ int launch_mixed(felics_ctx *ctx, Lane &l, const std::vector<MixImage> &im, cons
     int rc;
     const uint64_t pstride = g.npix;  // samples between two planes of the planes buffer (RGB)
     if (planes == 3 && (rc = reserve(ctx, l.planes, (size_t)g.nplanes * pstride * 2 + STAGE_PAD)) != 0) return rc;
+    // (behind the table, room for what views add to it: the pitched policy's rows of a gray sub-batch, the views of an RGB one)
+    static_assert(sizeof(PitchedGeom) >= sizeof(ViewRow) && sizeof(PlaneGeom) % 8 == 0, "one extra row per plane holds either");
     if (g.nplanes > l.h_table_cap) {
         if (l.h_table) HIP_TRY(ctx, hipHostFree(l.h_table));
         l.h_table = nullptr;
-        HIP_TRY(ctx, hipHostMalloc((void **)&l.h_table, (size_t)g.nplanes * sizeof(PlaneGeom), hipHostMallocDefault));
+        HIP_TRY(ctx, hipHostMalloc((void **)&l.h_table, (size_t)g.nplanes * (sizeof(PlaneGeom) + sizeof(PitchedGeom)), hipHostMallocDefault));
         l.h_table_cap = g.nplanes;
     }
+    bool any_view = false;
+    for (size_t i : idx) any_view = any_view || im[i].view;
+    const size_t extra_off = (size_t)g.nplanes * sizeof(PlaneGeom);
+    PitchedGeom *h_pitched = (PitchedGeom *)((uint8_t *)l.h_table + extra_off);  // gray
+    ViewRow *h_views = (ViewRow *)((uint8_t *)l.h_table + extra_off);            // RGB
     for (size_t j = 0; j < cnt; j++) {
         const MixImage &m = im[idx[j]];
         for (uint32_t c = 0; c < planes; c++) {
@@ -1013,18 +1054,25 @@ int launch_mixed(felics_ctx *ctx, Lane &l, const std::vector<MixImage> &im, cons
             pg.ntiles = (uint32_t)((m.npix + PACK_TILE - 1) / PACK_TILE);
             pg.out_off = o.off[idx[j]];
             pg.out_slot = o.slot[idx[j]];
+            if (any_view && planes == 1) h_pitched[j] = PitchedGeom{pg, m.pitch ? m.pitch : (uint64_t)m.w};  // (a dense plane: pitch = W)
         }
+        if (any_view && planes == 3) h_views[j] = m.view ? m.vr : ViewRow{m.px, 3ll * m.w, 3, 1};
     }
-    const size_t tbytes = (size_t)g.nplanes * sizeof(PlaneGeom);
+    const size_t tbytes = (size_t)g.nplanes * sizeof(PlaneGeom) + (any_view ? (planes == 1 ? cnt * sizeof(PitchedGeom) : cnt * sizeof(ViewRow)) : 0);
     if ((rc = reserve(ctx, l.mtable, tbytes)) != 0) return rc;
     hipStream_t fs = ctx->serial ? l.stream : l.front;
+    if ((rc = wait_ready(ctx, fs)) != 0) return rc;
     if (ctx->profiling) HIP_TRY(ctx, hipEventRecord(l.span_begin, fs));
     HIP_TRY(ctx, hipMemcpyAsync(l.mtable.p, l.h_table, tbytes, hipMemcpyHostToDevice, fs));
     g.mixed = (const PlaneGeom *)l.mtable.p;
+    g.pitched = any_view && planes == 1 ? (const PitchedGeom *)((const uint8_t *)l.mtable.p + extra_off) : nullptr;
     l.d_planes = planes == 3 ? l.planes.p : nullptr;  // (gray: every plane's samples come from the table)
     if (planes == 3) {
         StageTimer t(ctx, l, ST_PLANES, fs, true);
-        launch_rgb8_to_planes_mixed(fs, g.mixed, pstride, (uint32_t)max_npix, (uint32_t)cnt);
+        if (any_view)  // (views read where they lie, whatever their strides; the dense images of the sub-batch as views of their own)
+            launch_rgb8_view_to_planes(fs, g.mixed, (const ViewRow *)((const uint8_t *)l.mtable.p + extra_off), pstride, (uint32_t)max_npix, (uint32_t)cnt);
+        else
+            launch_rgb8_to_planes_mixed(fs, g.mixed, pstride, (uint32_t)max_npix, (uint32_t)cnt);
     }
     return planes == 3 ? run_lane<int16_t, uint16_t>(ctx, l, o.base, 0) : run_lane<uint8_t, uint8_t>(ctx, l, o.base, 0);
 }
@@ -1044,8 +1092,9 @@ int redo_by_shape(felics_ctx *ctx, Lane &l, const std::vector<MixImage> &im, con
         rest.swap(other);
         const size_t cnt = grp.size();
         if ((rc = reserve(ctx, ctx->mix_redo, f.frame_bytes * cnt + 64)) != 0) return rc;
-        for (size_t j = 0; j < cnt && f.frame_bytes; j++)
-            HIP_TRY(ctx, hipMemcpyAsync((uint8_t *)ctx->mix_redo.p + j * f.frame_bytes, im[grp[j]].px, f.frame_bytes, hipMemcpyDeviceToDevice, l.stream));
+        if ((rc = wait_ready(ctx, l.stream)) != 0) return rc;
+        for (size_t j = 0; j < cnt && f.frame_bytes; j++)  // (a view: gathered, the path wants dense frames)
+            if ((rc = stage_frame(ctx, l.stream, (uint8_t *)ctx->mix_redo.p + j * f.frame_bytes, im[grp[j]])) != 0) return rc;
         HIP_TRY(ctx, hipStreamSynchronize(l.stream));
         std::vector<uint64_t> offs(cnt), lens(cnt);
         uint8_t *used = nullptr;
@@ -1180,6 +1229,7 @@ int run_images(felics_ctx *ctx, const std::vector<MixImage> &im, MixOut &o) {
     if (stage_total && (rc = reserve(ctx, ctx->mix_stage, stage_total + 64)) != 0) return rc;
     for (size_t i = 0; i < n; i++) {  // zero-sized images: header + two zero words per plane, encode_device's host path
         if (im[i].npix) continue;
+        if (ctx->view_ready) HIP_TRY(ctx, hipStreamWaitEvent(nullptr, ctx->view_ready, 0));  // (the copy below runs on the null stream)
         uint64_t off = 0, len = 0;
         if ((rc = encode_device(ctx, ctx->lanes[0], 1, nullptr, im[i].w, im[i].h, im[i].color, im[i].depth, o.base + o.off[i], (size_t)o.slot[i], &off,
                                 &len, nullptr)) != 0)
@@ -1218,9 +1268,9 @@ int run_images(felics_ctx *ctx, const std::vector<MixImage> &im, MixOut &o) {
         if (j.wide) {
             const MixImage &f = im[j.idx[0]];
             uint8_t *in = (uint8_t *)ctx->mix_in.p + j.in_off;
-            for (size_t k = 0; k < j.idx.size(); k++)
-                if (hipMemcpyAsync(in + k * f.frame_bytes, im[j.idx[k]].px, f.frame_bytes, hipMemcpyDeviceToDevice, l.stream) != hipSuccess)
-                    return drain(hip_fail(ctx, hipGetLastError(), "gathering 16-bit frames"));
+            if ((rc = wait_ready(ctx, l.stream)) != 0) return drain(rc);
+            for (size_t k = 0; k < j.idx.size(); k++)  // (a view is gathered by a kernel instead of copied)
+                if ((rc = stage_frame(ctx, l.stream, in + k * f.frame_bytes, im[j.idx[k]])) != 0) return drain(rc);
             for (int i = 0; i < ST_COUNT; i++) l.ev_used[i] = 0;
             rc = launch_sub_batch(ctx, l, 0, j.idx.size(), in, f.w, f.h, f.color, f.depth, (uint8_t *)ctx->mix_stage.p + j.stage_off, j.slot, nslices, true);
         } else {
@@ -1758,6 +1808,7 @@ void felics_ctx_destroy(felics_ctx *ctx) {
     release(ctx->mix_stage);
     release(ctx->mix_out);
     release(ctx->mix_redo);
+    release(ctx->view_stage);
     release(ctx->dec_meta);
     release(ctx->dec_planes);
     release(ctx->dec_planes16);
@@ -2005,6 +2056,122 @@ int felics_compress_images_device(felics_ctx *ctx, size_t n, const felics_image 
     std::vector<MixImage> im(n);
     for (size_t i = 0; i < n; i++) im[i] = mix_image(images[i]);
     return images_device(ctx, im, (uint8_t *)d_out, d_out_cap, offsets, lens);
+}
+
+namespace {
+
+// A view's checks (felics_view_extent and felics_compress_views_device alike) and the hull of its samples' bytes relative to data.
+int check_view(const felics_view &v, int64_t &lo, int64_t &hi) {
+    lo = hi = 0;
+    int rc = check_args(v.width, v.height, v.color, v.depth);
+    if (rc) return rc;
+    const uint64_t npix = (uint64_t)v.width * v.height;
+    const uint32_t planes = v.color == FELICS_COLOR_RGB ? 3 : 1;
+    const int bytes = v.depth == FELICS_DEPTH_16 ? 2 : 1;
+    if (!v.data && npix) return FELICS_E_INVALID_ARGUMENT;
+    if (bytes == 2 && (((uintptr_t)v.data | (uint64_t)v.row_stride | (uint64_t)v.pixel_stride | (planes == 3 ? (uint64_t)v.channel_stride : 0u)) & 1u))
+        return FELICS_E_INVALID_ARGUMENT;
+    if (npix * planes >= 0xE0000000ull) return FELICS_E_UNSUPPORTED;
+    if (v.depth == FELICS_DEPTH_16 && npix > WIDE_MAX_PLANE_PIXELS) return FELICS_E_UNSUPPORTED;
+    if (!npix) return FELICS_OK;
+    __int128 l = 0, h = bytes;
+    const int64_t steps[3] = {(int64_t)v.height - 1, (int64_t)v.width - 1, (int64_t)planes - 1};
+    const int64_t strides[3] = {v.row_stride, v.pixel_stride, planes == 3 ? v.channel_stride : 0};
+    for (int d = 0; d < 3; d++) {
+        const __int128 span = (__int128)steps[d] * strides[d];
+        (span < 0 ? l : h) += span;
+    }
+    if (l < INT64_MIN || h > INT64_MAX) return FELICS_E_INVALID_ARGUMENT;  // (addresses are computed in 64 bits)
+    lo = (int64_t)l;
+    hi = (int64_t)h;
+    return FELICS_OK;
+}
+
+}  // namespace
+
+int felics_view_extent(const felics_view *v, int64_t *lo, int64_t *hi) {
+    if (!v || !lo || !hi) return FELICS_E_INVALID_ARGUMENT;
+    return check_view(*v, *lo, *hi);
+}
+
+int felics_get_view_stats(const felics_ctx *ctx, felics_view_stats *out, size_t out_size) {
+    if (!ctx || !out) return FELICS_E_INVALID_ARGUMENT;
+    memcpy(out, &ctx->vstats, std::min(out_size, sizeof(felics_view_stats)));
+    return FELICS_OK;
+}
+
+int felics_compress_views_device(felics_ctx *ctx, size_t n, const felics_view *views, void *ready_event, void *d_out, size_t d_out_cap,
+                                 uint64_t *offsets, uint64_t *lens) {
+    if (!ctx || (n && (!views || !d_out || !offsets || !lens))) return FELICS_E_INVALID_ARGUMENT;
+    if (ctx->failed) return FELICS_E_HIP;
+    for (size_t i = 0; i < n; i++) {  // every view checked before anything is launched: the first error in view order
+        int64_t lo, hi;
+        int rc = check_view(views[i], lo, hi);
+        if (rc) return rc;
+    }
+    if (n == 0) return FELICS_OK;
+    if (any_pending(ctx)) return FELICS_E_INVALID_ARGUMENT;  // felics_wait_batch first
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    // the class of every view: dense, read in place, or gathered (gray8 now, into view_stage; 16-bit where its group is queued)
+    std::vector<MixImage> im(n);
+    std::vector<size_t> stage_at(n, 0);
+    size_t stage_total = 0;
+    felics_view_stats add = {};
+    for (size_t i = 0; i < n; i++) {
+        const felics_view &v = views[i];
+        MixImage &m = im[i];
+        m = mix_image(felics_image{v.data, v.width, v.height, v.color, v.depth});
+        const int64_t bytes = v.depth == FELICS_DEPTH_16 ? 2 : 1;
+        const bool rgb = v.color == FELICS_COLOR_RGB;
+        add.views++;
+        const bool dense = !m.npix || (v.pixel_stride == bytes * (rgb ? 3 : 1) && v.row_stride == (int64_t)v.width * v.pixel_stride &&
+                                       (!rgb || v.channel_stride == bytes));
+        if (dense) {
+            add.dense++;
+            continue;
+        }
+        m.view = true;
+        m.vr = ViewRow{v.data, v.row_stride, v.pixel_stride, rgb ? v.channel_stride : 0};
+        if (v.depth == FELICS_DEPTH_8 && rgb) {
+            add.in_place++;
+        } else if (v.depth == FELICS_DEPTH_8 && v.pixel_stride == 1 && v.row_stride >= (int64_t)v.width) {
+            add.in_place++;
+            m.pitch = (uint64_t)v.row_stride;
+        } else {
+            add.gathered++;
+            if (v.depth == FELICS_DEPTH_8) {
+                stage_at[i] = stage_total;
+                stage_total += (m.frame_bytes + 255) & ~(size_t)255;
+            }
+        }
+    }
+    int rc;
+    ctx->view_ready = (hipEvent_t)ready_event;
+    ctx->wait_before_submit = (hipEvent_t)ready_event;  // (the uniform path's sub-batches: launch_sub_batch)
+    auto leave = [&](int r) {
+        ctx->view_ready = nullptr;
+        ctx->wait_before_submit = nullptr;
+        return r;
+    };
+    if (stage_total) {
+        Lane &l = ctx->lanes[0];
+        if ((rc = reserve(ctx, ctx->view_stage, stage_total + 64)) != 0) return leave(rc);
+        if ((rc = wait_ready(ctx, l.stream)) != 0) return leave(rc);
+        for (size_t i = 0; i < n; i++) {
+            MixImage &m = im[i];
+            if (!m.view || m.depth != FELICS_DEPTH_8 || m.planes == 3 || m.pitch) continue;
+            uint8_t *dst = (uint8_t *)ctx->view_stage.p + stage_at[i];
+            if ((rc = stage_frame(ctx, l.stream, dst, m)) != 0) return leave(rc);
+            m.px = dst;
+            m.view = false;
+        }
+        if (hipStreamSynchronize(l.stream) != hipSuccess) return leave(hip_fail(ctx, hipGetLastError(), "gathering views"));
+    }
+    ctx->vstats.views += add.views;
+    ctx->vstats.dense += add.dense;
+    ctx->vstats.in_place += add.in_place;
+    ctx->vstats.gathered += add.gathered;
+    return leave(images_device(ctx, im, (uint8_t *)d_out, d_out_cap, offsets, lens));
 }
 
 // Host frames in, host streams out: the frames are copied to the device (16-byte aligned, back to back), encoded as above into the

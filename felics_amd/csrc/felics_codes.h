@@ -216,6 +216,16 @@ __device__ __forceinline__ uint32_t *plane_words(const MixedOut &mo, uint32_t pl
 }
 __device__ __forceinline__ uint32_t plane_tiles(const MixedOut &mo, uint32_t plane, uint32_t) { return mo.table[plane].ntiles; }
 
+// A mixed sub-batch with PITCHED planes (felics_compress_views_device: gray8 views read where they lie): the output of a mixed
+// sub-batch, and the pitched policy's own table (PitchedGeom: the plane and the bytes between two of its rows).
+struct PitchedOut {
+    MixedOut mo;
+    const PitchedGeom *rows;
+};
+__device__ __forceinline__ uint32_t *plane_words(const PitchedOut &po, uint32_t plane, uint64_t &limit_words) {
+    return plane_words(po.mo, plane, limit_words);
+}
+
 
 constexpr uint32_t ST_AGGREGATE = 1, ST_PREFIX = 2;
 constexpr uint32_t ST_VALUE_BITS = 44;        // bits of a plane fit: < 2^32 pixels x < 2^10 bits

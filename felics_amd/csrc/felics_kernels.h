@@ -69,6 +69,10 @@ struct Geometry {
     // pack_tiles = the largest image's, npix = sort_tiles * SORT_TILE), what differs per plane is read from this device table
     // (nullptr: the uniform geometry above).
     const struct PlaneGeom *mixed = nullptr;
+    // A mixed sub-batch of gray8 planes some of which are PITCHED (views read where they lie): beside `mixed`, which the kernels
+    // that see bits and not pixels go on reading, a table of the pitched policy's own row type for k_front and k_pack_t
+    // (nullptr: every plane is dense).
+    const struct PitchedGeom *pitched = nullptr;
 };
 
 // One plane of a mixed sub-batch.  The kernels index it by plane (wave-uniform: scalar loads).  Tiles past the plane's own end
@@ -80,6 +84,24 @@ struct PlaneGeom {
     uint32_t ntiles;       // the plane's own pack tiles, ceil(npix / PACK_TILE) (<= Geometry::pack_tiles)
     uint64_t out_off;      // the image's slot in the output: byte offset from PackTarget::out, and size (writes beyond it are dropped)
     uint64_t out_slot;
+};
+
+// A view (felics_view): sample (x, y, c) at data + y * row_stride + x * pixel_stride + c * channel_stride, strides in bytes, signed
+struct ViewRow {
+    const void *data;
+    int64_t row_stride, pixel_stride, channel_stride;
+};
+// mixed sub-batch of RGB8 views: image i read through rows[i] (a dense image: strides 3 W, 3, 1), its planes as launch_rgb8_to_planes_mixed
+void launch_rgb8_view_to_planes(hipStream_t s, const PlaneGeom *table, const ViewRow *rows, uint64_t plane_stride, uint32_t max_npix, uint32_t nimg);
+// a view copied to a dense frame (W * H * channels samples of T = u8 / u16): felics_wide.hip
+template <typename T>
+void launch_gather_view(hipStream_t s, const ViewRow &v, uint32_t W, uint32_t H, uint32_t channels, T *dst);
+
+// One plane of a sub-batch with pitched planes: the plane as in the mixed table, and the bytes between two of its rows (>= W; W: a
+// dense plane).  A row type of its own: PlaneGeom, which the mixed kernels load, stays as it is.
+struct PitchedGeom {
+    PlaneGeom g;
+    uint64_t pitch;
 };
 
 void launch_rgb8_to_planes(hipStream_t s, const uint8_t *rgb, int16_t *planes, uint32_t npix, uint32_t nimg);

@@ -95,6 +95,87 @@ __global__ __launch_bounds__(256) void k_rgb8_to_planes_mixed(const PlaneGeom *_
         rgb8_group(rgb + (uint64_t)g * 12u, o, g * 4, npix, plane_stride);
 }
 
+// A mixed sub-batch of RGB8 VIEWS (felics_compress_views_device): image blockIdx.y read where it lies -- sample (x, y, c) at
+// data + y * row_stride + x * pixel_stride + c * channel_stride, signed 64-bit strides -- into the same planes.  Four pixels per
+// thread as above where they lie in one row and the layout allows wide loads: three-byte pixels in either channel order (12 bytes),
+// four-byte pixels in either order (16 bytes; not a row's last group, whose fourth pad byte may lie behind the view), planar rows
+// (4 bytes per plane).  Everything else sample by sample.  The layout is the image's: the choice is wave-uniform.
+__global__ __launch_bounds__(256) void k_rgb8_view_to_planes(const PlaneGeom *__restrict__ table, const ViewRow *__restrict__ rows, uint64_t plane_stride) {
+    const PlaneGeom *pg = table + 3ull * blockIdx.y;
+    const ViewRow vr = rows[blockIdx.y];
+    const uint32_t npix = pg->npix, W = pg->W, groups = (npix + 3) / 4;
+    const uint8_t *data = (const uint8_t *)vr.data;
+    const int64_t rs = vr.row_stride, ps = vr.pixel_stride, cs = vr.channel_stride;
+    int16_t *o = (int16_t *)pg->samples;
+    const bool unit = cs == 1 || cs == -1;
+    const uint32_t mode = unit && ps == 3 ? 1u : unit && ps == 4 ? 2u : ps == 1 ? 3u : 0u;
+    const uint8_t *low = data + (cs < 0 ? 2 * cs : 0);  // the lowest of a pixel's three samples
+    for (uint32_t g = blockIdx.x * blockDim.x + threadIdx.x; g < groups; g += gridDim.x * blockDim.x) {
+        const uint32_t i = g * 4;
+        uint32_t y = i / W, x = i - y * W;
+        int r[4] = {0, 0, 0, 0}, gr[4] = {0, 0, 0, 0}, b[4] = {0, 0, 0, 0};
+        const bool whole = i + 4 <= npix;
+        const bool in_row = whole && x + 4 <= W && !(mode == 2u && x + 4 == W);
+        if (in_row && mode == 1u) {
+            uint32_t w[3];
+            __builtin_memcpy(w, low + (int64_t)y * rs + (int64_t)x * 3, 12);
+            const int q[12] = {(int)(w[0] & 0xFFu), (int)((w[0] >> 8) & 0xFFu), (int)((w[0] >> 16) & 0xFFu), (int)(w[0] >> 24),
+                               (int)(w[1] & 0xFFu), (int)((w[1] >> 8) & 0xFFu), (int)((w[1] >> 16) & 0xFFu), (int)(w[1] >> 24),
+                               (int)(w[2] & 0xFFu), (int)((w[2] >> 8) & 0xFFu), (int)((w[2] >> 16) & 0xFFu), (int)(w[2] >> 24)};
+#pragma unroll
+            for (uint32_t k = 0; k < 4; k++) {
+                r[k] = cs > 0 ? q[3 * k] : q[3 * k + 2];
+                gr[k] = q[3 * k + 1];
+                b[k] = cs > 0 ? q[3 * k + 2] : q[3 * k];
+            }
+        } else if (in_row && mode == 2u) {
+            uint32_t w[4];
+            __builtin_memcpy(w, low + (int64_t)y * rs + (int64_t)x * 4, 16);
+#pragma unroll
+            for (uint32_t k = 0; k < 4; k++) {
+                const int c0 = (int)(w[k] & 0xFFu), c2 = (int)((w[k] >> 16) & 0xFFu);
+                r[k] = cs > 0 ? c0 : c2;
+                gr[k] = (int)((w[k] >> 8) & 0xFFu);
+                b[k] = cs > 0 ? c2 : c0;
+            }
+        } else if (in_row && mode == 3u) {
+            const uint8_t *p = data + (int64_t)y * rs + (int64_t)x;
+            load4(p, r);
+            load4(p + cs, gr);
+            load4(p + 2 * cs, b);
+        } else {
+            for (uint32_t k = 0; k < 4 && i + k < npix; k++) {
+                const uint8_t *p = data + (int64_t)y * rs + (int64_t)x * ps;
+                r[k] = p[0];
+                gr[k] = p[cs];
+                b[k] = p[2 * cs];
+                if (++x == W) {
+                    x = 0;
+                    y++;
+                }
+            }
+        }
+        int yv[4], co[4], cg[4];
+#pragma unroll
+        for (uint32_t k = 0; k < 4; k++) ycocg(r[k], gr[k], b[k], yv[k], co[k], cg[k]);
+        if (whole) {
+            auto put4 = [&](int16_t *dst, const int (&v)[4]) {
+                const uint32_t pk[2] = {(uint32_t)(v[0] & 0xFFFF) | ((uint32_t)v[1] << 16), (uint32_t)(v[2] & 0xFFFF) | ((uint32_t)v[3] << 16)};
+                __builtin_memcpy(dst, pk, 8);
+            };
+            put4(o + i, yv);
+            put4(o + plane_stride + i, co);
+            put4(o + 2ull * plane_stride + i, cg);
+        } else {
+            for (uint32_t k = 0; i + k < npix; k++) {
+                o[i + k] = (int16_t)yv[k];
+                o[plane_stride + i + k] = (int16_t)co[k];
+                o[2ull * plane_stride + i + k] = (int16_t)cg[k];
+            }
+        }
+    }
+}
+
 // ---- Instruction forms.  profiles/r04/valu_rate.txt: a gfx950 SIMD issues 32-bit add / sub / and / or / xor / lshr / ashr,
 // v_bitop3_b32 and every 16-bit VOP2 instruction (min, max, add, shifts) in 1.0 ns, everything else -- v_min_u32,
 // v_lshlrev_b32, v_cndmask, compares, v_bfe, SDWA / DPP / VOP3 forms, 64-bit shifts -- in 1.7 ns.  The compiler prices them
@@ -204,7 +285,42 @@ __device__ __forceinline__ PlaneView<T> plane_view(const T *, uint32_t plane, co
     return PlaneView<T>{(const T *)pg->samples, pg->W, pg->H, pg->npix};
 }
 
-// (S: const T * -- the uniform planes -- or const PlaneGeom * -- a mixed sub-batch's table; W and npix are then unused)
+// The PITCHED policy (felics_compress_views_device: gray8 views read where they lie): a mixed sub-batch whose planes' rows are
+// pitch[plane] bytes apart.  The linear index i = y W + x of a pixel still names its tile, its slot and its place in the stream;
+// only the ADDRESS of a sample changes, y * pitch + x, in 64 bits (a view may lie anywhere in a surface of more than 4 GB).
+template <typename T>
+__device__ __forceinline__ PlaneView<T> plane_view(const PitchedGeom *rows, uint32_t plane, uint32_t, uint32_t) {
+    const PitchedGeom *pg = rows + (uint32_t)__builtin_amdgcn_readfirstlane((int)plane);
+    return PlaneView<T>{(const T *)pg->g.samples, pg->g.W, pg->g.H, pg->g.npix};
+}
+template <typename S>
+__device__ __forceinline__ uint64_t plane_pitch(S, uint32_t) { return 0; }
+__device__ __forceinline__ uint64_t plane_pitch(const PitchedGeom *rows, uint32_t plane) {
+    return rows[(uint32_t)__builtin_amdgcn_readfirstlane((int)plane)].pitch;
+}
+// classify() on a pitched plane: the same neighbour rule (misc.rs:6-24), addresses from (x, y)
+template <typename T>
+__device__ __forceinline__ PixelClass classify_pitched(const T *__restrict__ pl, uint32_t x, uint32_t y, uint64_t pitch) {
+    const uint64_t i = (uint64_t)y * pitch + x;
+    uint64_t a, b;
+    if (x > 0 && y > 0) {
+        a = i - 1;
+        b = i - pitch;
+    } else if (y == 0) {  // first row, x >= 2
+        a = i - 1;
+        b = i - 2;
+    } else if (y >= 2) {  // first column
+        a = i - pitch;
+        b = i - 2 * pitch;
+    } else {  // pixel (0,1); W >= 2
+        a = i - pitch;
+        b = i - pitch + 1;
+    }
+    return classify_values((int)pl[i], (int)pl[a], (int)pl[b]);
+}
+
+// (S: const T * -- the uniform planes --, const PlaneGeom * -- a mixed sub-batch's table; W and npix are then unused -- or
+// const PitchedGeom *: the table of a sub-batch with pitched planes)
 template <typename T, typename ET, typename S>
 __attribute__((amdgpu_waves_per_eu(sizeof(T) == 1 ? FELICS_FRONT_WAVES : 5))) __global__ __launch_bounds__(256) void k_front(
     S __restrict__ planes, ET *__restrict__ ev, uint16_t *__restrict__ pix, uint32_t *__restrict__ runtab,
@@ -240,6 +356,9 @@ __attribute__((amdgpu_waves_per_eu(sizeof(T) == 1 ? FELICS_FRONT_WAVES : 5))) __
     const PlaneView<T> view = plane_view<T>(planes, plane, W_, npix_);
     const uint32_t W = view.W, npix = view.npix;
     const T *pl = view.pl;
+    constexpr bool PITCHED = std::is_same<S, const PitchedGeom *>::value;
+    using Index = typename std::conditional<PITCHED, uint64_t, uint32_t>::type;  // of a sample from pl
+    const uint64_t pitch = plane_pitch(planes, plane);
     const uint32_t begin = tile * SORT_TILE;
     const uint32_t qbegin = min(begin + wave * QUARTER, npix);
     const uint32_t end = min(qbegin + QUARTER, npix);  // of this wave's quarter
@@ -256,22 +375,31 @@ __attribute__((amdgpu_waves_per_eu(sizeof(T) == 1 ? FELICS_FRONT_WAVES : 5))) __
     struct Trip {  // the samples of an interior trip as loaded: four of the row, four of the row above, the one in front of the span
         uint32_t cur[4], up[4], left0;
     };
-    auto load_trip = [&](uint32_t r, uint32_t left_index, Trip &t) {
+    auto load_trip = [&](Index r, Index left_index, Trip &t) {
 #pragma unroll
         for (uint32_t j = 0; j < 4; j++) {
             t.cur[j] = field_of((int)pl[r + 64 * j + lane], T());
-            t.up[j] = field_of((int)pl[r + 64 * j + lane - W], T());
+            if constexpr (PITCHED)
+                t.up[j] = field_of((int)pl[r + 64 * j + lane - pitch], T());
+            else
+                t.up[j] = field_of((int)pl[r + 64 * j + lane - W], T());
         }
         t.left0 = field_of((int)pl[left_index], T());  // (the same address in every lane)
     };
     bool have[TRIPS];
-    uint32_t leftidx[TRIPS];
+    Index leftidx[TRIPS];
+    Index tripat[TRIPS];  // pitched: where the trip's first sample lies (an interior trip is a piece of one row)
     {
         uint32_t ri = qbegin, yi = qbegin / W, xi = qbegin - yi * W;
 #pragma unroll
         for (uint32_t d = 0; d < TRIPS; d++) {
             have[d] = ri < end && is_interior(ri, xi, yi);
-            leftidx[d] = have[d] ? span_left_index(ri, xi, yi, W) : 0u;
+            if constexpr (PITCHED) {
+                tripat[d] = (uint64_t)yi * pitch + xi;
+                leftidx[d] = !have[d] ? 0u : xi > 0 ? tripat[d] - 1 : (yi >= 2 ? tripat[d] - 2 * pitch : tripat[d] - pitch + 1);
+            } else {
+                leftidx[d] = have[d] ? span_left_index(ri, xi, yi, W) : 0u;
+            }
             ri += 256;
             xi += 256;
             if (xi >= W) {  // (once per image row: scalar division)
@@ -284,11 +412,19 @@ __attribute__((amdgpu_waves_per_eu(sizeof(T) == 1 ? FELICS_FRONT_WAVES : 5))) __
     const uint32_t cnt_at = (uint32_t)(uintptr_t)(const __attribute__((address_space(3))) uint32_t *)my_cnt;  // LDS address of the wave's counters
     const uint32_t dummy_at = (NC + lane) * 4u;
     Trip pre[2];  // two trips in flight
-    if (have[0]) load_trip(qbegin, leftidx[0], pre[0]);
+    if constexpr (PITCHED) {
+        if (have[0]) load_trip(tripat[0], leftidx[0], pre[0]);
+    } else {
+        if (have[0]) load_trip(qbegin, leftidx[0], pre[0]);
+    }
 #pragma unroll
     for (uint32_t d = 0; d < TRIPS; d++) {
         const uint32_t row0 = qbegin + d * 256;
-        if (d + 1 < TRIPS && have[d + 1]) load_trip(row0 + 256, leftidx[d + 1], pre[(d + 1) & 1u]);
+        if constexpr (PITCHED) {
+            if (d + 1 < TRIPS && have[d + 1]) load_trip(tripat[d + 1], leftidx[d + 1], pre[(d + 1) & 1u]);
+        } else {
+            if (d + 1 < TRIPS && have[d + 1]) load_trip(row0 + 256, leftidx[d + 1], pre[(d + 1) & 1u]);
+        }
         if (have[d]) {
             const Trip &t = pre[d & 1u];
 #pragma unroll
@@ -323,7 +459,11 @@ __attribute__((amdgpu_waves_per_eu(sizeof(T) == 1 ? FELICS_FRONT_WAVES : 5))) __
                 const uint32_t i = row0 + j * 64 + lane;
                 uint32_t r = 0xFFFFFFFFu;
                 if (i < end && i >= 2) {
-                    const PixelClass pc = classify(pl, i, xy.x, xy.y, W);
+                    PixelClass pc;
+                    if constexpr (PITCHED)
+                        pc = classify_pitched(pl, xy.x, xy.y, pitch);
+                    else
+                        pc = classify(pl, i, xy.x, xy.y, W);
                     if (pc.cls != CLS_IN) r = (pc.ctx << 22) | (pc.val << 13) | (pc.cls == CLS_ABOVE ? 0x1000u : 0u) | (i - begin);
                 }
                 xy.advance(64, W);
@@ -924,10 +1064,18 @@ template <typename PO> struct OutOf<FusedArgsT<PO>> { using type = PO; };
 #define PO_OF(FA) typename OutOf<FA>::type
 __device__ __forceinline__ const PlaneOut &planes_out(const PlaneOut &po) { return po; }
 __device__ __forceinline__ const PlaneOut &planes_out(const MixedOut &mo) { return mo.po; }
+__device__ __forceinline__ const PlaneOut &planes_out(const PitchedOut &po) { return po.mo.po; }
 template <typename T>
 __device__ __forceinline__ PlaneView<T> plane_view(const T *planes, uint32_t plane, const FusedArgsT<MixedOut> &fa) {
     return plane_view(planes, plane, fa.po.table);
 }
+template <typename T>
+__device__ __forceinline__ PlaneView<T> plane_view(const T *planes, uint32_t plane, const FusedArgsT<PitchedOut> &fa) {
+    return plane_view<T>(fa.po.rows, plane, 0u, 0u);
+}
+template <typename PO>
+__device__ __forceinline__ uint64_t plane_pitch(const FusedArgsT<PO> &, uint32_t) { return 0; }
+__device__ __forceinline__ uint64_t plane_pitch(const FusedArgsT<PitchedOut> &fa, uint32_t plane) { return plane_pitch(fa.po.rows, plane); }
 #ifdef FELICS_PACK_STAMPS
 __device__ unsigned long long g_pack_stamps[256][16];
 #define PSTAMP(i)                                                                              \
@@ -975,6 +1123,32 @@ __device__ __forceinline__ GroupGeom group_geometry(const T *__restrict__ pl, ui
         if (gg.j0 < PACK_PER_THREAD) {
             const uint32_t i0 = first + gg.j0;
             gg.special = (int)pl[i0 >= 2 * W ? i0 - 2 * W : i0 - W + 1];
+        }
+    }
+    return gg;
+}
+
+// The same on a pitched plane: `at` = where the group's first sample lies.  A group that straddles a row end (one per row unless W
+// is a multiple of sixteen) is no longer sixteen consecutive bytes, nor is the span above it: load_group_pitched puts each together
+// from two loads, and the group then takes the same branch-free path, its first-column pixel being pixel j0 = W - x as before.
+template <typename T>
+__device__ __forceinline__ GroupGeom group_geometry_pitched(const T *__restrict__ pl, uint32_t tile, uint32_t W, uint32_t npix, uint64_t pitch,
+                                                            uint64_t &at) {
+    GroupGeom gg{false, PACK_PER_THREAD, 0};
+    const uint32_t first = tile * PACK_TILE + threadIdx.x * PACK_PER_THREAD;
+    const uint32_t end = min((tile + 1) * PACK_TILE, npix);
+    at = 0;
+    if (W >= PACK_PER_THREAD && first + PACK_PER_THREAD <= end && first >= W) {
+        gg.fast = true;
+        Coord xy;
+        xy.set(first, W);
+        at = (uint64_t)xy.y * pitch + xy.x;
+        if (xy.x == 0) {
+            gg.j0 = 0;
+            gg.special = (int)pl[xy.y >= 2 ? at - 2 * pitch : at - pitch + 1];
+        } else if (xy.x + PACK_PER_THREAD > W) {  // pixel j0 is (0, y + 1), y >= 1: its second neighbour is (0, y - 1)
+            gg.j0 = W - xy.x;
+            gg.special = (int)pl[(uint64_t)(xy.y - 1) * pitch];
         }
     }
     return gg;
@@ -1086,6 +1260,31 @@ __device__ __forceinline__ void load_group(const T *__restrict__ pl, uint32_t fi
     g.before = (int)pl[first - 1];
 }
 
+// Pitched: the group at `at`, a piece of one row -- or, 0 < j0 < 16, the last j0 samples of a row and the first 16 - j0 of the
+// next: two 16-byte loads each for the group and for the span above it, merged sample by sample.  The second piece is loaded so
+// that sample j of the group is byte j of the load (it starts j0 bytes in front of the next row: at + pitch - W), and every byte
+// read lies between the view's first and last sample (W >= 16, so 15 bytes behind a row's end or in front of its start do).
+// (a group in the first column has no sample in front of it and never uses one)
+template <typename T>
+__device__ __forceinline__ void load_group_pitched(const T *__restrict__ pl, uint64_t at, uint64_t pitch, uint32_t W, uint32_t j0, GroupSamples<T> &g) {
+    static_assert(sizeof(T) == 1, "the merge below is by bytes");
+    __builtin_memcpy(g.cw, pl + at, PACK_PER_THREAD);
+    __builtin_memcpy(g.uw, pl + at - pitch, PACK_PER_THREAD);
+    g.before = (int)pl[j0 == 0 ? at : at - 1];
+    if (j0 - 1u < PACK_PER_THREAD - 1u) {  // 0 < j0 < 16: straddling
+        uint32_t c2[4], u2[4];
+        __builtin_memcpy(c2, pl + at + pitch - W, PACK_PER_THREAD);  // the next row's start at byte j0
+        __builtin_memcpy(u2, pl + at - W, PACK_PER_THREAD);          // this row's start at byte j0: above the next row's pixels
+#pragma unroll
+        for (uint32_t w = 0; w < 4; w++) {
+            const uint32_t k = min(max((int)j0 - 4 * (int)w, 0), 4);              // bytes of dword w that belong to the first piece
+            const uint32_t m = k >= 4 ? 0xFFFFFFFFu : (1u << (8u * k)) - 1u;
+            g.cw[w] = (g.cw[w] & m) | (c2[w] & ~m);
+            g.uw[w] = (g.uw[w] & m) | (u2[w] & ~m);
+        }
+    }
+}
+
 // The codes of a thread's 16 pixels WITHOUT a branch (the common case): every pixel below the first image row, the group
 // inside the plane.  Same codes as classify + put_pixel, which stay as the general path (first row, the plane's first
 // two samples and its ragged end, Rice codes too long for a word, images narrower than 16 pixels).
@@ -1097,9 +1296,10 @@ __device__ __forceinline__ void load_group(const T *__restrict__ pl, uint32_t fi
 //     thread in 240 has such a pixel: its code is built a second time where a wave holds such a thread.
 // Returns the total length in bits (exact also when a Rice code did not fit its word: the word then carries the length);
 // longest = the longest code's length field (RICE_WORD_LONG: one did not fit).
-template <typename T>
-__device__ __forceinline__ uint32_t group_codes_w(const GroupSamples<T> &g, const uint32_t *words, const T *__restrict__ pl, uint32_t first,
-                                                uint32_t W, uint32_t j0, int special, uint32_t (&c32)[PACK_PER_THREAD],
+// (IX: the type of a sample's index from pl -- first and W -- uint32_t, or uint64_t with W = the pitch on a pitched plane)
+template <typename T, typename IX = uint32_t>
+__device__ __forceinline__ uint32_t group_codes_w(const GroupSamples<T> &g, const uint32_t *words, const T *__restrict__ pl, IX first,
+                                                IX W, uint32_t j0, int special, uint32_t (&c32)[PACK_PER_THREAD],
                                                 uint32_t (&len)[PACK_PER_THREAD], uint32_t &longest) {
     const uint32_t off = threadIdx.x * PACK_PER_THREAD;
     const uint32_t K31 = vgpr_const(0x80000000u);
@@ -1124,7 +1324,7 @@ __device__ __forceinline__ uint32_t group_codes_w(const GroupSamples<T> &g, cons
     }
     if (__ballot(j0 < PACK_PER_THREAD) != 0) {  // (wave-uniform: a quarter of the waves of a 4K plane)
         if (j0 < PACK_PER_THREAD && (words[word_index(off + j0)] & 63u) == 0u) {  // (an event's word does not depend on who its neighbours are here)
-            const uint32_t i0 = first + j0;
+            const IX i0 = first + j0;
             const PixelCode pc = code_in_range(field_of((int)pl[i0], T()), field_of(special, T()), field_of((int)pl[i0 - W], T()), K31);
 #pragma unroll
             for (uint32_t j = 0; j < PACK_PER_THREAD; j++) {
@@ -1156,9 +1356,9 @@ __device__ __forceinline__ uint32_t group_codes_w(const GroupSamples<T> &g, cons
 //     thread in 240 has such a pixel: its code is built a second time where a wave holds such a thread.
 // kq = the tile's k bytes in LDS.  Returns the total length in bits (exact also when a code is longer than 32 bits: only
 // that code's c32 is garbage then); longest = the longest code's length.
-template <typename T>
-__device__ __forceinline__ uint32_t group_codes_k(const GroupSamples<T> &g, const uint8_t *kq, const T *__restrict__ pl, uint32_t first,
-                                                uint32_t W, uint32_t j0, int special, uint32_t (&c32)[PACK_PER_THREAD],
+template <typename T, typename IX = uint32_t>
+__device__ __forceinline__ uint32_t group_codes_k(const GroupSamples<T> &g, const uint8_t *kq, const T *__restrict__ pl, IX first,
+                                                IX W, uint32_t j0, int special, uint32_t (&c32)[PACK_PER_THREAD],
                                                 uint32_t (&len)[PACK_PER_THREAD], uint32_t &longest) {
     const uint32_t off = threadIdx.x * PACK_PER_THREAD;
     uint32_t kw[4];
@@ -1180,7 +1380,7 @@ __device__ __forceinline__ uint32_t group_codes_k(const GroupSamples<T> &g, cons
     }
     if (__ballot(j0 < PACK_PER_THREAD) != 0) {  // (wave-uniform: a quarter of the waves of a 4K plane)
         if (j0 < PACK_PER_THREAD) {
-            const uint32_t i0 = first + j0;
+            const IX i0 = first + j0;
             const PixelCode pc = code_pixel(field_of((int)pl[i0], T()), field_of(special, T()), field_of((int)pl[i0 - W], T()),
                                             (uint32_t)kq[off + j0], K31, K7F);
 #pragma unroll
@@ -1207,23 +1407,35 @@ struct GeneralGroup {
     uint32_t tile_first, first, end, W, H, npix, color, depth, has_header;
     uint32_t by_word;  // k of pixel i: word_k(words[i]) (k_pack_t's word path), or byte i of the same LDS array (its k path)
 };
-template <typename T, typename FR, typename F>
-__device__ __forceinline__ void walk_group_global(const T *__restrict__ pl, const uint32_t *words, const GeneralGroup &g, FR &&raw, F &&f) {
+struct GeneralGroupPitched : GeneralGroup {  // (a type of its own: the uniform and mixed kernels' callees take GeneralGroup as it is)
+    uint64_t pitch;
+};
+template <typename T, typename G, typename FR, typename F>
+__device__ __forceinline__ void walk_group_global(const T *__restrict__ pl, const uint32_t *words, const G &g, FR &&raw, F &&f) {
+    constexpr bool PITCHED = std::is_same<G, GeneralGroupPitched>::value;
     Coord xy;
     xy.set(g.first, g.W);
     for (uint32_t i = g.first; i < min(g.end, g.first + PACK_PER_THREAD); i++) {
-        if (i < 2)
-            raw(i, (uint32_t)(int)pl[i]);  // stored as 32-bit values (compression.rs:105-106)
-        else
-            f(classify(pl, i, xy.x, xy.y, g.W),
-              g.by_word ? word_k(words[word_index(i - g.tile_first)]) : (uint32_t)reinterpret_cast<const uint8_t *>(words)[i - g.tile_first]);
+        if constexpr (PITCHED) {
+            if (i < 2)
+                raw(i, (uint32_t)(int)pl[(uint64_t)xy.y * g.pitch + xy.x]);
+            else
+                f(classify_pitched(pl, xy.x, xy.y, g.pitch),
+                  g.by_word ? word_k(words[word_index(i - g.tile_first)]) : (uint32_t)reinterpret_cast<const uint8_t *>(words)[i - g.tile_first]);
+        } else {
+            if (i < 2)
+                raw(i, (uint32_t)(int)pl[i]);  // stored as 32-bit values (compression.rs:105-106)
+            else
+                f(classify(pl, i, xy.x, xy.y, g.W),
+                  g.by_word ? word_k(words[word_index(i - g.tile_first)]) : (uint32_t)reinterpret_cast<const uint8_t *>(words)[i - g.tile_first]);
+        }
         xy.advance(1, g.W);
     }
 }
 // (Own: one copy per k_pack_t instantiation -- a call's register conventions follow from all of a callee's callers, so the mixed
 // kernel's copy is kept apart from the uniform kernel's)
-template <typename T, typename Own>
-__device__ __noinline__ uint32_t general_group_bits(const uint32_t *words, const T *pl, const GeneralGroup g) {
+template <typename T, typename Own, typename G>
+__device__ __noinline__ uint32_t general_group_bits(const uint32_t *words, const T *pl, const G g) {
     uint32_t bits = 0;
     if (g.first < g.end) {
         const uint32_t npix = g.npix;
@@ -1234,8 +1446,8 @@ __device__ __noinline__ uint32_t general_group_bits(const uint32_t *words, const
     return bits;
 }
 // (the window's word 0 is stream word win_word0; bit 0 of this group is stream bit my_lo)
-template <typename T, typename Own>
-__device__ __noinline__ void general_group_place(const uint32_t *words, const T *pl, const GeneralGroup g, uint32_t *win,
+template <typename T, typename Own, typename G>
+__device__ __noinline__ void general_group_place(const uint32_t *words, const T *pl, const G g, uint32_t *win,
                                                  uint32_t win_words, uint64_t win_word0, uint64_t my_lo) {
     LaneBits bw;
     bw.win = win;
@@ -1342,7 +1554,7 @@ __device__ __forceinline__ void look_back(const FA &fa, FusedLDS &fl, uint32_t t
 // the array holds k of pixel j in byte j) and fl.win all zero, with a barrier behind both.
 template <typename T, bool BY_WORD, typename FA>
 __device__ __forceinline__ void pack_tile_fused(const GroupSamples<T> &gsm, const uint32_t *words, FusedLDS &fl, const T *__restrict__ planes,
-                                                const FA &fa, uint32_t tile, uint32_t plane, const GroupGeom &gg) {
+                                                const FA &fa, uint32_t tile, uint32_t plane, const GroupGeom &gg, uint64_t group_at = 0) {
     uint32_t (&win)[FUSED_WIN_WORDS + 2] = fl.win;
     uint32_t (&wsum)[PACK_THREADS / 64] = fl.wsum;
     const auto &po = fa.po;
@@ -1363,14 +1575,25 @@ __device__ __forceinline__ void pack_tile_fused(const GroupSamples<T> &gsm, cons
     // first-column pixel in it (whose second neighbour -- two rows up, or above-right in row 1 -- comes from global memory).
     // (The general path is two function calls, placed where none of the common path's codes is in a register: the count in
     // front of group_codes, the placement behind the common path's.)
-    const GeneralGroup general{tile_first, first, end, W, H, npix, fa.color, fa.depth, has_header ? 1u : 0u, BY_WORD ? 1u : 0u};
+    constexpr bool PITCHED = std::is_same<PO_OF(FA), PitchedOut>::value;  // (group_at: where a fast group's row piece lies)
+    using General = typename std::conditional<PITCHED, GeneralGroupPitched, GeneralGroup>::type;
+    General general_at;
+    static_cast<GeneralGroup &>(general_at) = GeneralGroup{tile_first, first, end, W, H, npix, fa.color, fa.depth, has_header ? 1u : 0u, BY_WORD ? 1u : 0u};
+    if constexpr (PITCHED) general_at.pitch = plane_pitch(fa, plane);
+    const General general = general_at;
     uint32_t bits = 0;
     if (!gg.fast) bits = general_group_bits<T, PO_OF(FA)>(words, pl, general);  // count now, build the codes straight into the window later
     uint32_t c32[PACK_PER_THREAD], len[PACK_PER_THREAD];
     bool in_registers = false;
     if (gg.fast) {
         uint32_t longest;
-        if (BY_WORD) {
+        if constexpr (PITCHED) {
+            if (BY_WORD)
+                bits = group_codes_w<T, uint64_t>(gsm, words, pl, group_at, general.pitch, gg.j0, gg.special, c32, len, longest);
+            else
+                bits = group_codes_k<T, uint64_t>(gsm, reinterpret_cast<const uint8_t *>(words), pl, group_at, general.pitch, gg.j0, gg.special, c32, len, longest);
+            in_registers = BY_WORD ? longest != RICE_WORD_LONG : longest <= 32u;
+        } else if (BY_WORD) {
             bits = group_codes_w<T>(gsm, words, pl, first, W, gg.j0, gg.special, c32, len, longest);
             in_registers = longest != RICE_WORD_LONG;  // (a Rice code too long for its word: the lengths stand, the codes are built again the general way)
         } else {
@@ -1533,9 +1756,20 @@ __attribute__((amdgpu_waves_per_eu(FELICS_PACK_WAVES))) __global__ __launch_boun
     // ---- round trip 1: the tile's slots in use and the thread's pixels
     const uint64_t pt = (uint64_t)plane * ts.sort_ntiles + st;
     const uint32_t ns = (uint32_t)__builtin_amdgcn_readfirstlane((int)ts.tile_slots[pt]);  // a multiple of REC
-    const GroupGeom gg = group_geometry<T>(pl, st, view.W, view.npix);
+    constexpr bool PITCHED = std::is_same<PO, PitchedOut>::value;
+    uint64_t group_at = 0;
+    GroupGeom gg;
     GroupSamples<T> gsm;
-    if (gg.fast) load_group(pl, st * PACK_TILE + threadIdx.x * PACK_PER_THREAD, view.W, gsm);
+    if constexpr (PITCHED) {
+        const uint64_t pitch = plane_pitch(fa, plane);
+        gg = group_geometry_pitched<T>(pl, st, view.W, view.npix, pitch, group_at);
+        if (gg.fast) load_group_pitched(pl, group_at, pitch, view.W, gg.j0, gsm);
+        // (what the code phase indexes pixel j0 from: where the group lies, or -- straddling -- j0 in front of the next row's start)
+        if (gg.j0 - 1u < PACK_PER_THREAD - 1u) group_at += pitch - view.W;
+    } else {
+        gg = group_geometry<T>(pl, st, view.W, view.npix);
+        if (gg.fast) load_group(pl, st * PACK_TILE + threadIdx.x * PACK_PER_THREAD, view.W, gsm);
+    }
     for (uint32_t j = threadIdx.x; j < FUSED_WIN_WORDS + 2; j += PACK_THREADS) fl.win[j] = 0;  // the bit window (barrier: behind the gather)
     const uint8_t *ksrc = ts.kq + pt * ts.cap;
     const uint16_t *psrc = ts.pix + pt * ts.cap;
@@ -1579,7 +1813,7 @@ __attribute__((amdgpu_waves_per_eu(FELICS_PACK_WAVES))) __global__ __launch_boun
         PSTAMP(2);
         __syncthreads();
         PSTAMP(3);
-        if (st < pack_tile_end) pack_tile_fused<T, true>(gsm, words, fl, planes, fa, st, plane, gg);
+        if (st < pack_tile_end) pack_tile_fused<T, true>(gsm, words, fl, planes, fa, st, plane, gg, group_at);
     } else {
         // ---- round trip 2, many events (noise, texture): k of every event into byte `pixel` of the array; both codes of every pixel
         // are then built in the code phase (there are more slots than pixels to build a code for).  (A thread past the end takes
@@ -1606,7 +1840,7 @@ __attribute__((amdgpu_waves_per_eu(FELICS_PACK_WAVES))) __global__ __launch_boun
         PSTAMP(2);
         __syncthreads();
         PSTAMP(3);
-        if (st < pack_tile_end) pack_tile_fused<T, false>(gsm, words, fl, planes, fa, st, plane, gg);
+        if (st < pack_tile_end) pack_tile_fused<T, false>(gsm, words, fl, planes, fa, st, plane, gg, group_at);
     }
 }
 
@@ -1690,6 +1924,12 @@ void launch_rgb8_to_planes_mixed(hipStream_t s, const PlaneGeom *table, uint64_t
     FELICS_LAUNCH(k_rgb8_to_planes_mixed, dim3(bx, nimg), dim3(256), s, table, plane_stride);
 }
 
+void launch_rgb8_view_to_planes(hipStream_t s, const PlaneGeom *table, const ViewRow *rows, uint64_t plane_stride, uint32_t max_npix, uint32_t nimg) {
+    if (!nimg || !max_npix) return;
+    const uint32_t bx = std::max(1u, std::min(cdiv(cdiv(max_npix, 4), 256), 4096u));
+    FELICS_LAUNCH(k_rgb8_view_to_planes, dim3(bx, nimg), dim3(256), s, table, rows, plane_stride);
+}
+
 template <typename T>
 void launch_lengths(hipStream_t s, const T *planes, const uint8_t *k_map, group_bits_t<T> *group_bits,
                     uint32_t *tile_bits, const Geometry &g, uint32_t t0, uint32_t t1) {
@@ -1769,6 +2009,14 @@ void launch_pack_t(hipStream_t s, const T *planes, const uint8_t *kq, const uint
     const PlaneOut po{to.out, to.slot_stride, to.scratch, to.plane_slot, g.planes_per_image};
     const TSources ts{kq, pix, ev, tile_slots, cap, g.sort_tiles};
     // (the kernel takes its tile from the ticket, or from blockIdx.x of this one-dimensional grid: never from blockIdx.y)
+    if constexpr (sizeof(T) == 1) {
+        if (g.mixed && g.pitched) {
+            const FusedArgsT<PitchedOut> fa{status, tile_bitoff, tile_bits, plane_carry, edge_first, edge_last, error, PitchedOut{MixedOut{po, g.mixed}, g.pitched},
+                                            g.W, g.H, g.npix, g.pack_tiles, g.color, g.depth, epoch, ticket, g.nplanes};
+            FELICS_LAUNCH((k_pack_t<T, PitchedOut>), dim3((st1 - st0) * g.nplanes), dim3(PACK_THREADS), s, planes, ts, fa, st0, g.pack_tiles);
+            return;
+        }
+    }
     if (g.mixed) {
         const FusedArgsT<MixedOut> fa{status, tile_bitoff, tile_bits, plane_carry, edge_first, edge_last, error, MixedOut{po, g.mixed},
                                       g.W, g.H, g.npix, g.pack_tiles, g.color, g.depth, epoch, ticket, g.nplanes};
@@ -1791,6 +2039,13 @@ void launch_front(hipStream_t s, const T *planes, const TileLocal<ET> &tl, const
                   uint32_t *flags, uint32_t mode) {
     if (tile_end <= tile_begin) return;
     const dim3 grid(8u * cdiv(g.nplanes, 8) * (tile_end - tile_begin));  // one workgroup per tile, the planes dealt to the XCDs by the kernel
+    if constexpr (sizeof(T) == 1) {
+        if (g.mixed && g.pitched) {
+            FELICS_LAUNCH((k_front<T, ET, const PitchedGeom *>), grid, dim3(256), s, g.pitched, tl.ev, tl.pix, tl.runtab, tl.tile_slots, 0u, 0u,
+                          g.sort_tiles, tile_begin, tile_end, g.nplanes, tl.cap, flags, mode);
+            return;
+        }
+    }
     if (g.mixed)
         FELICS_LAUNCH((k_front<T, ET, const PlaneGeom *>), grid, dim3(256), s, g.mixed, tl.ev, tl.pix, tl.runtab, tl.tile_slots, 0u, 0u, g.sort_tiles,
                       tile_begin, tile_end, g.nplanes, tl.cap, flags, mode);

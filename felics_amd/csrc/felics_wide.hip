@@ -885,4 +885,33 @@ size_t wide_long_capacity(const Geometry &g, uint32_t lane_limit) {
     return lane_limit ? (size_t)((uint64_t)g.nplanes * g.npix / lane_limit + g.nplanes + 1) : 0;
 }
 
+// ------------------------------------------------------------------------------------------
+// k_gather_view: a view (felics_compress_views_device) copied to the dense frame the encoder takes -- what a 16-bit view, a gray8
+// view whose pixels are not consecutive bytes, and any view whose sub-batch needs a remedy go through.  A workgroup row per
+// image row (blockIdx.y, strided), consecutive threads take consecutive samples of the row: where pixel_stride is the dense one
+// the reads are as coalesced as the writes.  All addresses in 64 bits.
+// ------------------------------------------------------------------------------------------
+template <typename T>
+__global__ __launch_bounds__(256) void k_gather_view(ViewRow v, uint32_t W, uint32_t H, uint32_t C, T *__restrict__ dst) {
+    const uint8_t *data = (const uint8_t *)v.data;
+    const uint64_t row = (uint64_t)W * C;  // samples
+    for (uint32_t y = blockIdx.y; y < H; y += gridDim.y) {
+        const uint8_t *src = data + (int64_t)y * v.row_stride;
+        T *out = dst + (uint64_t)y * row;
+        for (uint64_t j = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; j < row; j += (uint64_t)gridDim.x * blockDim.x) {
+            const uint64_t x = C == 1 ? j : j / 3u;
+            const int64_t c = (int64_t)(j - x * C);
+            out[j] = *reinterpret_cast<const T *>(src + (int64_t)x * v.pixel_stride + c * v.channel_stride);
+        }
+    }
+}
+template <typename T>
+void launch_gather_view(hipStream_t s, const ViewRow &v, uint32_t W, uint32_t H, uint32_t channels, T *dst) {
+    if (!W || !H) return;
+    const uint32_t bx = std::max(1u, std::min(cdiv((uint64_t)W * channels, 256), 64u));
+    FELICS_LAUNCH((k_gather_view<T>), dim3(bx, std::min(H, 65535u)), dim3(256), s, v, W, H, channels, dst);
+}
+template void launch_gather_view<uint8_t>(hipStream_t, const ViewRow &, uint32_t, uint32_t, uint32_t, uint8_t *);
+template void launch_gather_view<uint16_t>(hipStream_t, const ViewRow &, uint32_t, uint32_t, uint32_t, uint16_t *);
+
 }  // namespace felics

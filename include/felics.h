@@ -142,6 +142,59 @@ int felics_compress_images(felics_ctx *ctx, size_t n, const felics_image *images
 int felics_compress_images_device(felics_ctx *ctx, size_t n, const felics_image *images, void *d_out, size_t d_out_cap,
                                   uint64_t *offsets, uint64_t *lens);
 
+/* A frame where it lies in DEVICE memory, in any layout strides can describe: the address of sample (x, y, c) is
+ *     data + y * row_stride + x * pixel_stride + c * channel_stride        (bytes; c = 0, 1, 2 = R, G, B)
+ * All strides are signed, and since a view is only read, zero and negative strides are legal: BGR is data + 2 with
+ * channel_stride = -1, a bottom-up image has a negative row_stride, row_stride = 0 repeats one row.  A pitched surface
+ * (hipMallocPitch), a sub-rectangle of one, RGBA / BGRA pixels and planar C x H x W tensors are all views.  For depth 16, data and
+ * every stride must be multiples of 2.  The reference has no counterpart for strides: its images are `ImageBuffer::as_raw()`. */
+typedef struct felics_view {
+    const void *data;          /* DEVICE address of sample (x=0, y=0, channel 0) */
+    uint32_t width, height;
+    int color, depth;          /* FELICS_COLOR_*, FELICS_DEPTH_* */
+    int64_t row_stride;        /* bytes from (x, y, c) to (x, y+1, c) */
+    int64_t pixel_stride;      /* bytes from (x, y, c) to (x+1, y, c) */
+    int64_t channel_stride;    /* bytes from (x, y, c) to (x, y, c+1); ignored for gray */
+} felics_view;
+
+/* felics_compress_images_device for views: stream i is byte-identical to what felics_compress writes for the dense copy of view i
+ * (still n x `compress`, compression.rs:255-282 / :322-371), and no dense copy is made where the kernels can read the view itself.
+ * Everything felics_compress_images_device says holds unless named here: placement and alignment of the streams, slots if
+ * d_out_cap holds them and exact placement otherwise, FELICS_E_BUFFER_TOO_SMALL with lens[0], every view checked before anything
+ * is launched (the first error in view order; NULL data only for a zero-sized view; FELICS_E_INVALID_ARGUMENT for an odd address
+ * or stride at depth 16 and for strides whose extent does not fit 64 bits; the size limits of felics_compress_images), refused
+ * while a ticket is outstanding, FELICS_E_HIP on a failed context, n = 0 returns FELICS_OK.
+ *   ready_event : a hipEvent_t the caller has recorded behind whatever produces the views and last used d_out, or NULL.  If given,
+ *                 every stream of the library waits for it (hipStreamWaitEvent) before it first reads a view or writes d_out in
+ *                 this call, and the caller need not synchronise the host.  NULL keeps the contract of
+ *                 felics_compress_batch_device: the frames are complete in memory when the call is made.
+ * How a view is read (felics_get_view_stats counts them):
+ *   dense     : the view is the layout felics_image describes; it takes felics_compress_images_device's path as it is;
+ *   in place  : gray8 with pixel_stride = 1 and row_stride >= width (the kernels take the row pitch), and RGB8 of ANY strides
+ *               (the plane transform reads the view; the Y / Co / Cg planes it writes exist for dense frames as well);
+ *   gathered  : everything else -- gray8 with another pixel stride or a row stride below the width, every 16-bit view -- is copied
+ *               to a dense frame in a staging buffer of the context first (one kernel).  So is a view of a sub-batch that has to
+ *               be redone (a remedy of felics_stats).
+ * The call is blocking: the streams are complete when it returns. */
+int felics_compress_views_device(felics_ctx *ctx, size_t n, const felics_view *views, void *ready_event, void *d_out,
+                                 size_t d_out_cap, uint64_t *offsets, uint64_t *lens);
+
+/* Host only, no context: checks a view exactly as felics_compress_views_device does and returns the half-open byte range
+ * [*lo, *hi) relative to `data` that an encode of the view may read -- the hull of its samples; both 0 for a zero-sized view.
+ * The caller's bounds check: the view is safe to encode if data + lo .. data + hi lies inside its allocation. */
+int felics_view_extent(const felics_view *v, int64_t *lo, int64_t *hi);
+
+/* How the views of a context's calls were read so far (cumulative). */
+typedef struct felics_view_stats {
+    uint64_t views;         /* views handed to felics_compress_views_device (calls that passed the checks) */
+    uint64_t dense;         /* ... that were the dense layout */
+    uint64_t in_place;      /* ... read where they lay */
+    uint64_t gathered;      /* ... copied to a dense frame first */
+    uint64_t bytes_staged;  /* bytes written by such copies, those of redone sub-batches included */
+} felics_view_stats;
+/* Writes min(out_size, sizeof(felics_view_stats)) bytes, never more: a caller built against a shorter struct stays valid. */
+int felics_get_view_stats(const felics_ctx *ctx, felics_view_stats *out, size_t out_size);
+
 /* Replaces `read_header` (format.rs:63-84). */
 int felics_read_header(const uint8_t *in, size_t len, felics_header *hdr);
 /* Replaces `write_header` (format.rs:51-61): writes FELICS_HEADER_BYTES bytes. */
