@@ -79,6 +79,11 @@ class _CViewStats(C.Structure):  # felics_view_stats
                 ("bytes_staged", C.c_uint64)]
 
 
+class _CDecodeStats(C.Structure):  # felics_decode_stats
+    _fields_ = [("streams", C.c_uint64), ("wave8", C.c_uint64), ("lanes8", C.c_uint64), ("wave16", C.c_uint64), ("lanes16", C.c_uint64),
+                ("host", C.c_uint64), ("undecoded", C.c_uint64), ("lanes16_table_bytes", C.c_uint64)]
+
+
 class Header:  # format.rs:44-49
     def __init__(self, color_type, pixel_depth, width, height):
         self.color_type = ColorType(color_type)
@@ -104,6 +109,7 @@ EXPORTS = [
     "felics_compress_images", "felics_compress_images_device", "felics_read_headers_device",
     "felics_decompress_images_device",
     "felics_compress_views_device", "felics_view_extent", "felics_get_view_stats",
+    "felics_get_decode_stats", "felics_decode_lanes_min_streams",
 ]
 
 _lib = None
@@ -167,6 +173,9 @@ def lib():
     L.felics_compress_views_device.argtypes = [vp, sz, C.POINTER(_CView), vp, vp, sz, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
     L.felics_view_extent.argtypes = [C.POINTER(_CView), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
     L.felics_get_view_stats.argtypes = [vp, C.POINTER(_CViewStats), sz]
+    L.felics_get_decode_stats.argtypes = [vp, C.POINTER(_CDecodeStats), sz]
+    L.felics_decode_lanes_min_streams.argtypes = [C.c_int, C.c_int]
+    L.felics_decode_lanes_min_streams.restype = C.c_uint32
     L.felics_strerror.argtypes = [C.c_int]
     L.felics_strerror.restype = C.c_char_p
     L.felics_last_error.argtypes = [vp]
@@ -488,6 +497,15 @@ class Encoder:
             self._raise(rc)
         return pix[:n], headers, status[:n]
 
+    def decode_stats(self):
+        """felics_get_decode_stats: how many streams the two device decode calls were handed and which form they took (wave8 / lanes8 /
+        wave16 / lanes16 / host / undecoded; cumulative), and lanes16_table_bytes of the last call."""
+        st = _CDecodeStats()
+        rc = lib().felics_get_decode_stats(self._h, C.byref(st), C.sizeof(st))
+        if rc != 0:
+            self._raise(rc)
+        return {k: int(getattr(st, k)) for k, _ in _CDecodeStats._fields_}
+
     def lane_count(self):
         """felics_ctx_lane_count: submissions this context can have in flight (fixed when it was created)."""
         return int(lib().felics_ctx_lane_count(self._h))
@@ -522,6 +540,12 @@ class Encoder:
 
 
 _default = {}
+
+
+def decode16_lanes_min_streams(color=0):
+    """felics_decode_lanes_min_streams(1, color): streams a device decode call must hold for its 16-bit streams (color: 0 gray, 1 RGB) to be
+    decoded 64 to a wave; 0xFFFFFFFF: never (the form is then reached with FELICS_TEST_DECODE16_LANES=1 only)."""
+    return int(lib().felics_decode_lanes_min_streams(1, int(color)))
 
 
 def default_encoder(device=0):

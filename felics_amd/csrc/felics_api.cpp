@@ -163,6 +163,9 @@ struct felics_ctx {
     DevBuf dec_lane_table;        // gray streams decoded 64 to a wave: the estimator rows that do not fit in LDS (3 KB per stream, zeroed per call)
     DevBuf dec_table;             // 16-bit streams: estimator tables in HBM (8.4 MB per stream of a pass), zeroed once, rows tagged with an epoch
     uint32_t dec_epoch = 0;       // last epoch handed out (three per call: one per plane)
+    DevBuf dec_lane16_table;      // 16-bit streams decoded 64 to a wave: their hashed estimator tables (felics_lanetable.h), zeroed once, rows tagged with an epoch
+    uint32_t dec_lane16_epoch = 0;  // last epoch handed out on dec_lane16_table (three per launch, 1 .. DEC16L_EPOCH_MAX)
+    felics_decode_stats dstats = {};  // felics_get_decode_stats
 };
 
 namespace {
@@ -236,6 +239,10 @@ int reserve_zeroed(felics_ctx *ctx, DevBuf &b, size_t bytes) {
     int rc = reserve(ctx, b, bytes);
     if (rc) return rc;
     HIP_TRY(ctx, hipMemset(b.p, 0, b.cap));
+    // (the memset of device memory may return before it has run, and the context's streams are non-blocking: without this wait a
+    // kernel could read rows of a grown epoch table -- often the memory of the one just freed, small epochs and all -- before the
+    // zeros arrive; seen as FELICS_E_INVALID_VALUE on the last good streams of a 64-stream k_decode16 call)
+    HIP_TRY(ctx, hipStreamSynchronize(nullptr));
     return FELICS_OK;
 }
 
@@ -1364,6 +1371,51 @@ int dec16_epoch(felics_ctx *ctx, hipStream_t s, uint32_t &epoch0) {
     return FELICS_OK;
 }
 
+// FELICS_TEST_DECODE16_LANES, read per call: 1 = 16-bit streams take the lane form wherever the shape allows it (W >= 8; in a mixed
+// call: whole waves of 64 streams of one shape), 0 = never, unset (-1) = from the measured thresholds on
+int dec16_lanes_forced() {
+    const char *e = getenv("FELICS_TEST_DECODE16_LANES");
+    return e ? (atoi(e) != 0 ? 1 : 0) : -1;
+}
+
+// FELICS_TEST_DECODE16_LANES_PASS=k: at most k streams (rounded down to whole waves, at least one) in a pass of the 16-bit lane form (tests)
+size_t dec16_lanes_pass_cap() {
+    const char *e = getenv("FELICS_TEST_DECODE16_LANES_PASS");
+    if (!e || atoll(e) <= 0) return SIZE_MAX / 2;
+    return std::max<size_t>(64, (size_t)atoll(e) / 64 * 64);
+}
+
+// 16-bit lane form: the table buffer for passes of `bytes` <= want bytes (what the whole call would like), at least `least` (one
+// wave's tables).  Bounded as dec16_tables bounds the wave form's: at most a quarter of the free HBM, and an allocation that fails
+// all the same halves the pass.  "Free" counts the buffer the context already holds, so the bound is the same call after call: with
+// free / 4 + cap a buffer of tens of GB grew a little with every call, and every growth is a free, an allocation and a memset
+// (seconds: profiles/decode16_lanes.txt, first run).
+int dec16_lanes_tables(felics_ctx *ctx, size_t want, size_t least, size_t &bytes) {
+    bytes = want;
+    size_t free_b = 0, total_b = 0;
+    if (hipMemGetInfo(&free_b, &total_b) == hipSuccess && ctx->dec_lane16_table.cap < bytes)
+        bytes = std::max(least, std::min(bytes, std::max(ctx->dec_lane16_table.cap, (free_b + ctx->dec_lane16_table.cap) / 4)));
+    for (;;) {
+        if (bytes > ctx->dec_lane16_table.cap) ctx->dec_lane16_epoch = 0;  // a fresh (zeroed) buffer: epochs start over
+        const int rc = reserve_zeroed(ctx, ctx->dec_lane16_table, bytes);
+        if (rc == 0) return FELICS_OK;
+        (void)hipGetLastError();
+        if (bytes <= least) return rc;
+        bytes = std::max(least, bytes / 2);
+    }
+}
+
+// the first of the three epochs (one per plane) of the next lane-form launch on stream s
+int dec16_lanes_epoch(felics_ctx *ctx, hipStream_t s, uint32_t &epoch0) {
+    if (ctx->dec_lane16_epoch + 3 > DEC16L_EPOCH_MAX) {  // epochs used up: clear the tables, start over
+        HIP_TRY(ctx, hipMemsetAsync(ctx->dec_lane16_table.p, 0, ctx->dec_lane16_table.cap, s));
+        ctx->dec_lane16_epoch = 0;
+    }
+    epoch0 = ctx->dec_lane16_epoch + 1;
+    ctx->dec_lane16_epoch += 3;
+    return FELICS_OK;
+}
+
 constexpr int HOST_DECODE_NO_MEMORY = 1;  // (not a status: the host could not hold the stream)
 
 // One stream through the host decoder (rows too wide for the LDS): copied to the host, decoded, the frame copied to d_dst.  A stream
@@ -1413,10 +1465,13 @@ int read_headers(felics_ctx *ctx, size_t n, const void *d_streams, const uint64_
 }
 
 // felics_decompress_images_device after the argument checks.  Every stream's header is read on the device (k_read_headers); the
-// frames are laid out in stream order; each stream then takes one of four forms:
+// frames are laid out in stream order; each stream then takes one of five forms:
 //   - 8-bit, 64 streams of one shape per wave (k_decode8_lanes) -- groups of >= 64 streams of one shape, W >= 8, in a call with
 //     as many 8-bit streams as the same-shape entry point wants for that form;
 //   - 8-bit, a wave per stream (k_decode8), rows in LDS classes, longest streams first, a class per launch and stream;
+//   - 16-bit, 64 streams of one shape per wave (k_decode16_lanes) -- whole waves out of groups of >= 64 streams of one shape and colour,
+//     W >= 8, in a call with as many 16-bit streams as the same-shape entry point wants for that form; passes bounded by the
+//     hashed tables' memory;
 //   - 16-bit, a wave per stream (k_decode16), passes bounded by the estimator tables' memory;
 //   - the host decoder, stream by stream (rows wider than the LDS holds).
 // The GPU forms run on distinct streams of the context, joined with events before the statuses come back.
@@ -1424,8 +1479,12 @@ int decompress_images(felics_ctx *ctx, size_t n, const void *d_streams, const ui
                       size_t cap, uint64_t *pix_offsets, felics_header *hdrs, int *status) {
     Lane &l0 = ctx->lanes[0];
     hipStream_t s = l0.stream;
+    felics_decode_stats &ds = ctx->dstats;
+    ds.streams += n;
+    ds.lanes16_table_bytes = 0;
     auto fail_all = [&](int code) {
         for (size_t i = 0; i < n; i++) status[i] = code;
+        ds.undecoded += n;
         return code;
     };
     std::vector<DecodeHeader> rec;
@@ -1448,6 +1507,7 @@ int decompress_images(felics_ctx *ctx, size_t n, const void *d_streams, const ui
         for (size_t i = 0; i < n; i++)
             if (status[i] == FELICS_OK) status[i] = FELICS_E_BUFFER_TOO_SMALL;
         pix_offsets[0] = needed;
+        ds.undecoded += n;
         return FELICS_E_BUFFER_TOO_SMALL;
     }
     if (needed && !d_pixels) return fail_all(FELICS_E_INVALID_ARGUMENT);
@@ -1486,6 +1546,30 @@ int decompress_images(felics_ctx *ctx, size_t n, const void *d_streams, const ui
             wave8.insert(wave8.end(), idx8.begin() + k + take, idx8.begin() + e);
             k = e;
         }
+    }
+    // 16-bit lane groups: whole waves of 64 streams of one shape and colour, W >= 8, in a call with as many 16-bit GPU streams as the
+    // same-shape entry point wants for that form (FELICS_TEST_DECODE16_LANES=1: in any call; =0: none); the rest of a group and
+    // every other 16-bit stream keep the wave form
+    std::vector<std::vector<size_t>> lane16_groups[2];  // [colour]
+    const int forced16 = dec16_lanes_forced();
+    if (forced16 != 0 && rows16.size() >= 64) {
+        std::vector<size_t> idx16 = rows16, rest;
+        std::stable_sort(idx16.begin(), idx16.end(), [&](size_t a, size_t b) {
+            return std::make_tuple(rec[a].color, rec[a].W, rec[a].H) < std::make_tuple(rec[b].color, rec[b].W, rec[b].H);
+        });
+        for (size_t k = 0; k < idx16.size();) {
+            size_t e = k;
+            while (e < idx16.size() && rec[idx16[e]].color == rec[idx16[k]].color && rec[idx16[e]].W == rec[idx16[k]].W && rec[idx16[e]].H == rec[idx16[k]].H) e++;
+            const DecodeHeader &h = rec[idx16[k]];
+            size_t take = 0;
+            if (h.W >= 8 && (forced16 == 1 || rows16.size() >= (h.color ? DECODE16_LANES_MIN_STREAMS_RGB : DECODE16_LANES_MIN_STREAMS)))
+                take = (e - k) / 64 * 64;
+            if (take) lane16_groups[h.color].emplace_back(idx16.begin() + k, idx16.begin() + k + take);
+            rest.insert(rest.end(), idx16.begin() + k + take, idx16.begin() + e);
+            k = e;
+        }
+        std::sort(rest.begin(), rest.end());  // (stream order again, as without this form)
+        rows16.swap(rest);
     }
     auto longest_first = [&](std::vector<size_t> &v) {
         std::stable_sort(v.begin(), v.end(), [&](size_t a, size_t b) { return npix[a] > npix[b]; });
@@ -1553,14 +1637,70 @@ int decompress_images(felics_ctx *ctx, size_t n, const void *d_streams, const ui
         }
         lanes[col].cnt = waves.size() - lanes[col].first;
     }
+    const size_t nslots8 = slots.size();  // (the 16-bit lane form's slots and waves follow)
+    // 16-bit lane form: passes of whole waves of one colour, each within the table memory dec16_lanes_tables grants; a pass's slots
+    // name their tables by row (LaneSlot::table_row) and its RGB planes start over at the front of dec_planes16
+    struct LanePass16 {
+        int col;
+        size_t wave_first, wave_cnt, slot_first, conv_first, conv_cnt;
+        uint64_t max_npix;
+    };
+    std::vector<LanePass16> passes16;
+    uint64_t lane_planes16 = 0;  // int32 samples of the largest lane pass's RGB planes
+    size_t nlanes16 = 0;
+    {
+        uint64_t want_rows = 0, least_rows = 0;
+        auto slot_rows = [&](size_t i) { return (uint64_t)(rec[i].color ? 3 : 1) * dec16l_rows(npix[i], rec[i].color ? 3 : 1); };
+        for (int col = 0; col < 2; col++)
+            for (const auto &g : lane16_groups[col]) {
+                want_rows += slot_rows(g[0]) * g.size();
+                least_rows = std::max(least_rows, slot_rows(g[0]) * 64);
+                nlanes16 += g.size();
+            }
+        size_t tbytes = 0;
+        if (nlanes16 && (rc = dec16_lanes_tables(ctx, (size_t)want_rows * DEC16L_ROW_BYTES, (size_t)least_rows * DEC16L_ROW_BYTES, tbytes)) != 0)
+            return fail_all(rc);
+        const uint64_t pass_rows = tbytes / DEC16L_ROW_BYTES;
+        const size_t pass_streams = dec16_lanes_pass_cap();
+        uint64_t used_rows = 0, poff = 0, most_rows = 0;
+        size_t in_pass = 0;
+        for (int col = 0; col < 2; col++)
+            for (const auto &g : lane16_groups[col])
+                for (size_t k = 0; k < g.size(); k += 64) {
+                    const uint64_t wave_rows = slot_rows(g[k]) * 64;
+                    if (passes16.empty() || passes16.back().col != col || used_rows + wave_rows > pass_rows || in_pass + 64 > pass_streams) {
+                        passes16.push_back(LanePass16{col, waves.size(), 0, slots.size(), rows.size(), 0, 0});
+                        used_rows = poff = 0;
+                        in_pass = 0;
+                    }
+                    LanePass16 &P = passes16.back();
+                    waves.push_back(LaneWave{rec[g[k]].W, rec[g[k]].H, (uint32_t)(slots.size() - P.slot_first), 64});
+                    P.wave_cnt++;
+                    for (uint32_t j = 0; j < 64; j++) {
+                        const size_t i = g[k + j];
+                        slots.push_back(LaneSlot{(uint32_t)i, (uint32_t)used_rows, col ? poff : pix_offsets[i] / 2});
+                        if (col) {
+                            rows.push_back(DecodeRow{(uint32_t)i, rec[i].W, rec[i].H, 1, pix_offsets[i], poff});
+                            P.conv_cnt++;
+                            poff += 3 * npix[i];
+                        }
+                        used_rows += slot_rows(i);
+                        P.max_npix = std::max(P.max_npix, npix[i]);
+                    }
+                    in_pass += 64;
+                    lane_planes16 = std::max(lane_planes16, poff);
+                    most_rows = std::max(most_rows, used_rows);
+                }
+        ds.lanes16_table_bytes = most_rows * DEC16L_ROW_BYTES;
+    }
     // 16-bit rows (passes below) behind the others
     const size_t rows16_first = rows.size();
     size_t per16 = 0;
-    uint64_t planes16 = 0;  // int32 samples of the largest pass's RGB planes
+    uint64_t planes16 = lane_planes16;  // int32 samples: the lane passes' RGB planes, the largest wave pass's behind them
     if (!rows16.empty()) {
         if ((rc = dec16_tables(ctx, rows16.size(), per16)) != 0) return fail_all(rc);
         for (size_t p = 0; p < rows16.size(); p += per16) {
-            uint64_t poff = 0;
+            uint64_t poff = lane_planes16;
             for (size_t k = p; k < std::min(rows16.size(), p + per16); k++) {
                 const size_t i = rows16[k];
                 rows.push_back(DecodeRow{(uint32_t)i, rec[i].W, rec[i].H, rec[i].color, pix_offsets[i], poff});
@@ -1583,12 +1723,18 @@ int decompress_images(felics_ctx *ctx, size_t n, const void *d_streams, const ui
     if (planes8 && (rc = reserve(ctx, ctx->dec_planes, planes8 * 2 + 64)) != 0) return fail_all(rc);
     if (planes16 && (rc = reserve(ctx, ctx->dec_planes16, planes16 * 4 + 64)) != 0) return fail_all(rc);
     const size_t lt_gray = decode8_lanes_table_bytes((uint32_t)(slot0[1] - slot0[0]), 0);
-    const size_t lt_bytes = lt_gray + decode8_lanes_table_bytes((uint32_t)(slots.size() - slot0[1]), 1);
-    if (!slots.empty() && (rc = reserve(ctx, ctx->dec_lane_table, lt_bytes)) != 0) return fail_all(rc);
+    const size_t lt_bytes = lt_gray + decode8_lanes_table_bytes((uint32_t)(nslots8 - slot0[1]), 1);
+    if (nslots8 && (rc = reserve(ctx, ctx->dec_lane_table, lt_bytes)) != 0) return fail_all(rc);
     std::vector<int> dev_status(status, status + n);
     for (size_t i = 0; i < n; i++)
         if (dev_status[i] == FELICS_OK) dev_status[i] = FELICS_E_HIP;  // until the kernel's own word arrives
     for (size_t i : host) dev_status[i] = FELICS_OK;
+    for (size_t i = 0; i < n; i++) ds.undecoded += status[i] != FELICS_OK;
+    ds.wave8 += wave8.size();
+    ds.lanes8 += n8 - wave8.size();
+    ds.wave16 += rows16.size();
+    ds.lanes16 += nlanes16;
+    ds.host += host.size();
     auto queue = [&]() -> int {
         HIP_TRY(ctx, hipMemcpyAsync(d_off, offsets, n * 8, hipMemcpyHostToDevice, s));
         HIP_TRY(ctx, hipMemcpyAsync(d_len, lens, n * 8, hipMemcpyHostToDevice, s));
@@ -1627,7 +1773,7 @@ int decompress_images(felics_ctx *ctx, size_t n, const void *d_streams, const ui
                                                   (int32_t *)ctx->dec_planes16.p, (uint32_t *)ctx->dec_table.p, epoch0, d_status));
             }
         }
-        if (!slots.empty()) {
+        if (nslots8) {
             hipStream_t w = stream_for();
             HIP_TRY(ctx, hipMemsetAsync(ctx->dec_lane_table.p, 0, lt_bytes, w));
             for (int col = 0; col < 2; col++)
@@ -1635,6 +1781,17 @@ int decompress_images(felics_ctx *ctx, size_t n, const void *d_streams, const ui
                                                         col, d_rows + conv.first, (uint32_t)conv.cnt, lanes[1].max_npix, d_pixels,
                                                         (int16_t *)ctx->dec_planes.p, (uint32_t *)((uint8_t *)ctx->dec_lane_table.p + (col ? lt_gray : 0)),
                                                         d_status));
+        }
+        if (!passes16.empty()) {
+            hipStream_t w = stream_for();
+            for (const LanePass16 &P : passes16) {
+                uint32_t epoch0 = 0;
+                int r = dec16_lanes_epoch(ctx, w, epoch0);
+                if (r) return r;
+                HIP_TRY(ctx, launch_decode16_lanes_waves(w, st, d_off, d_len, d_waves + P.wave_first, (uint32_t)P.wave_cnt, d_slots + P.slot_first, P.col,
+                                                         d_rows + P.conv_first, (uint32_t)P.conv_cnt, P.max_npix, (uint16_t *)d_pixels,
+                                                         (int32_t *)ctx->dec_planes16.p, (uint32_t *)ctx->dec_lane16_table.p, epoch0, d_status));
+            }
         }
         for (const Launch &L : classes)
             HIP_TRY(ctx, launch_decode8_rows(stream_for(), st, d_off, d_len, d_rows + L.first, (uint32_t)L.cnt, L.lds, L.max_npix, L.rgb, d_pixels,
@@ -1814,6 +1971,7 @@ void felics_ctx_destroy(felics_ctx *ctx) {
     release(ctx->dec_planes16);
     release(ctx->dec_table);
     release(ctx->dec_lane_table);
+    release(ctx->dec_lane16_table);
     delete ctx;
 }
 
@@ -2094,6 +2252,17 @@ int felics_view_extent(const felics_view *v, int64_t *lo, int64_t *hi) {
     return check_view(*v, *lo, *hi);
 }
 
+int felics_get_decode_stats(const felics_ctx *ctx, felics_decode_stats *out, size_t out_size) {
+    if (!ctx || !out) return FELICS_E_INVALID_ARGUMENT;
+    memcpy(out, &ctx->dstats, std::min(out_size, sizeof(felics_decode_stats)));
+    return FELICS_OK;
+}
+
+uint32_t felics_decode_lanes_min_streams(int depth, int color) {
+    if (depth) return color ? DECODE16_LANES_MIN_STREAMS_RGB : DECODE16_LANES_MIN_STREAMS;
+    return color ? DECODE8_LANES_MIN_STREAMS_RGB : DECODE8_LANES_MIN_STREAMS;
+}
+
 int felics_get_view_stats(const felics_ctx *ctx, felics_view_stats *out, size_t out_size) {
     if (!ctx || !out) return FELICS_E_INVALID_ARGUMENT;
     memcpy(out, &ctx->vstats, std::min(out_size, sizeof(felics_view_stats)));
@@ -2256,8 +2425,12 @@ int felics_decompress_batch_device(felics_ctx *ctx, size_t n, const void *d_stre
     if (hl) HIP_TRY(ctx, hipMemcpy(h0, (const uint8_t *)d_streams + offsets[0], hl, hipMemcpyDeviceToHost));
     // every stream gets a status on every path out of here (felics.h): a call that ends before the streams are decoded
     // reports its own error for all of them
+    felics_decode_stats &ds = ctx->dstats;
+    ds.streams += n;
+    ds.lanes16_table_bytes = 0;
     auto fail_all = [&](int code) {
         for (size_t i = 0; i < n; i++) status[i] = code;
+        ds.undecoded += n;
         return code;
     };
     felics_header hdr;
@@ -2273,6 +2446,46 @@ int felics_decompress_batch_device(felics_ctx *ctx, size_t n, const void *d_stre
     if (frame_bytes && !d_pixels) return fail_all(FELICS_E_INVALID_ARGUMENT);
     // a stream of this shape is never longer than this: a caller's length beyond it is not a stream (and not a size to allocate)
     const uint64_t max_len = felics_max_compressed_size(hdr.width, hdr.height, hdr.color_type, hdr.pixel_depth);
+    const int forced16 = dec16_lanes_forced();
+    if (bps == 2 && hdr.width >= 8 && decode16_lds_bytes(hdr.width) <= DECODE_LDS_LIMIT &&
+        (forced16 == 1 || (forced16 < 0 && n >= (planes == 3 ? DECODE16_LANES_MIN_STREAMS_RGB : DECODE16_LANES_MIN_STREAMS)))) {
+        // 16-bit streams 64 to a wave (k_decode16_lanes): passes of whole waves, bounded by the hashed tables' memory
+        const size_t tb1 = decode16_lanes_table_bytes(1, hdr.width, hdr.height, hdr.color_type);
+        const size_t n64 = (n + 63) / 64 * 64;
+        size_t tbytes = 0;
+        if ((rc = dec16_lanes_tables(ctx, std::min(n64, dec16_lanes_pass_cap()) * tb1, 64 * tb1, tbytes)) != 0) return fail_all(rc);
+        const size_t per = std::min(n64, tbytes / tb1 / 64 * 64);
+        const size_t most = std::min(per, n);
+        if ((rc = reserve(ctx, ctx->dec_meta, most * 8 * 2 + most * 4)) != 0) return fail_all(rc);
+        int32_t *d_planes32 = nullptr;
+        if (planes == 3) {
+            if ((rc = reserve(ctx, ctx->dec_planes, (size_t)(npix * 3 * 4 * most) + 64)) != 0) return fail_all(rc);
+            d_planes32 = (int32_t *)ctx->dec_planes.p;
+        }
+        ds.lanes16 += n;
+        ds.lanes16_table_bytes = most * tb1;
+        hipStream_t s = l.stream;
+        for (size_t i = 0; i < n; i++) status[i] = FELICS_E_HIP;  // until the kernel's own word arrives
+        int first_rc = FELICS_OK;
+        for (size_t first = 0; first < n; first += per) {
+            const size_t cnt = std::min(per, n - first);
+            uint32_t epoch0 = 0;
+            if ((rc = dec16_lanes_epoch(ctx, s, epoch0)) != 0) return rc;
+            uint64_t *d_off = (uint64_t *)ctx->dec_meta.p, *d_len = d_off + cnt;
+            int *d_status = (int *)(d_len + cnt);
+            HIP_TRY(ctx, hipMemcpyAsync(d_off, offsets + first, cnt * 8, hipMemcpyHostToDevice, s));
+            HIP_TRY(ctx, hipMemcpyAsync(d_len, lens + first, cnt * 8, hipMemcpyHostToDevice, s));
+            HIP_TRY(ctx, hipMemsetAsync(d_status, 0xFF, cnt * 4, s));
+            HIP_TRY(ctx, launch_decode16_lanes(s, (const uint8_t *)d_streams, d_off, d_len, (uint32_t)cnt, hdr.width, hdr.height, hdr.color_type,
+                                               (uint16_t *)d_pixels + first * (frame_bytes / 2), d_planes32,
+                                               (uint32_t *)ctx->dec_lane16_table.p, epoch0, d_status));
+            HIP_TRY(ctx, hipMemcpyAsync(status + first, d_status, cnt * 4, hipMemcpyDeviceToHost, s));
+            HIP_TRY(ctx, hipStreamSynchronize(s));
+            for (size_t i = first; i < first + cnt && !first_rc; i++)
+                if (status[i]) first_rc = status[i];
+        }
+        return first_rc;
+    }
     if (bps == 2 && decode16_lds_bytes(hdr.width) <= DECODE_LDS_LIMIT) {
         // 16-bit streams on the device: passes of at most DEC16_PASS streams (a stream's estimator table is 8.4 MB of HBM)
         // (and of at most a quarter of the free HBM; an allocation that fails all the same halves the pass)
@@ -2284,6 +2497,7 @@ int felics_decompress_batch_device(felics_ctx *ctx, size_t n, const void *d_stre
             if ((rc = reserve(ctx, ctx->dec_planes, (size_t)(npix * 3 * 4 * per) + 64)) != 0) return fail_all(rc);
             d_planes32 = (int32_t *)ctx->dec_planes.p;
         }
+        ds.wave16 += n;
         hipStream_t s = l.stream;
         for (size_t i = 0; i < n; i++) status[i] = FELICS_E_HIP;  // until the kernel's own word arrives
         int first_rc = FELICS_OK;
@@ -2315,6 +2529,7 @@ int felics_decompress_batch_device(felics_ctx *ctx, size_t n, const void *d_stre
         } catch (const std::bad_alloc &) {
             return fail_all(FELICS_E_IO);
         }
+        ds.host += n;
         int first_rc = FELICS_OK;
         for (size_t i = 0; i < n; i++) {
             const int r = host_decode(ctx, (const uint8_t *)d_streams + offsets[i], lens[i], max_len, hdr, (uint8_t *)d_pixels + i * frame_bytes,
@@ -2354,10 +2569,12 @@ int felics_decompress_batch_device(felics_ctx *ctx, size_t n, const void *d_stre
     if (by_lane) {
         const size_t tb = decode8_lanes_table_bytes((uint32_t)n, hdr.color_type);
         if ((rc = reserve(ctx, ctx->dec_lane_table, tb)) != 0) return fail_all(rc);
+        ds.lanes8 += n;
         HIP_TRY(ctx, hipMemsetAsync(ctx->dec_lane_table.p, 0, tb, s));
         HIP_TRY(ctx, launch_decode8_lanes(s, (const uint8_t *)d_streams, d_off, d_len, (uint32_t)n, hdr.width, hdr.height, hdr.color_type,
                                           (uint8_t *)d_pixels, d_planes, (uint32_t *)ctx->dec_lane_table.p, d_status));
     } else {
+        ds.wave8 += n;
         HIP_TRY(ctx, launch_decode8(s, (const uint8_t *)d_streams, d_off, d_len, (uint32_t)n, hdr.width, hdr.height, hdr.color_type,
                                     (uint8_t *)d_pixels, d_planes, d_status));
     }

@@ -938,6 +938,273 @@ __global__ __launch_bounds__(256) void k_ycocg16_to_rgb(const int32_t *__restric
     if (bad) atomicCAS(&status[img], FELICS_OK, FELICS_E_INVALID_VALUE);
 }
 
+// ------------------------------------------------------------------------------------------
+// 16-bit streams, sixty-four of one shape per wave, LANE = stream: the walk of k_decode8_lanes with the arithmetic of k_decode16.
+//
+// (x, y) is wave-uniform, the bit reader is a LaneReader, the row above is read back from the lane's own output four samples at a
+// time and a load ahead.  Per pixel every lane works out the in-range code off the top 32 bits of its window (an in-range code has
+// at most 18 bits); the lanes whose pixel is out of range then take the estimator path together: the context's row (fifteen 32-bit
+// counters in named registers -- counter 0 can gain 131 071 per event while the smallest gains one, so several million accumulate
+// between two halvings; `(S << 4) | rank` still fits 32 bits: below 2^28), get_k with ties to the largest k, the Rice code off the
+// same 32 bits when its unary part, the zero and the k bits lie inside them and through LaneReader::unary0 (bounded by the stream's
+// length) when they do not -- a valid stream holds unary runs of tens of thousands of bits --, the update, the halving.
+//
+// The estimator table is the lane's own, sized by what the stream can use (felics_lanetable.h: rows = 2 x (pixels - 2) rounded up to
+// a power of two, hashed and open-addressed; from 65 536 rows on the dense table of k_decode16), one per plane, in HBM: rows of 64
+// bytes read and written with 16-byte accesses, the tag word = (epoch << 17) | context.  A row of another epoch is empty, so nothing
+// is zeroed per call.  A search is bounded by the row count; a table found full is FELICS_E_IO for that lane (the sizing rule does
+// not let it happen), not a loop.
+//
+// Visibility: PLAIN loads and stores, as k_decode8_lanes has them, not the agent-scope loads of k_decode16.  A row is written and
+// read by one lane of one wave only, in program order and through that CU's write-through L1 -- the same path by which the lane
+// reads the row above back from its own output --, so there is no other CU's store to miss within a launch; rows left by earlier
+// launches (other epochs) were made visible by the kernel boundary.  The L1 then serves a smooth plane's few hot rows.
+//
+// Error behaviour as in k_decode8_lanes: every read of a stream is bounded by its length; a lane that has failed keeps walking with
+// its samples clamped into the plane's range, so its contexts stay below 131 071, its rows inside its own table (a row index is
+// always below the row count) and its stores inside its own frame (x < W, y < H); it reports its first error.
+// Needs W >= 8 (the read-back of the row above looks four samples ahead of a row's end).
+// ------------------------------------------------------------------------------------------
+
+namespace {
+
+template <>
+struct Four<uint16_t> {
+    uint32_t lo, hi;
+    __device__ __forceinline__ void clear() { lo = hi = 0; }
+    __device__ __forceinline__ void load(const uint16_t *p) {
+        uint32_t v[2];
+        __builtin_memcpy(v, p, 8);
+        lo = v[0];
+        hi = v[1];
+    }
+    __device__ __forceinline__ void store(uint16_t *p) const {
+        const uint32_t v[2] = {lo, hi};
+        __builtin_memcpy(p, v, 8);
+    }
+    __device__ __forceinline__ int get(uint32_t j) const { return (int)((((j & 2u) ? hi : lo) >> (16u * (j & 1u))) & 0xFFFFu); }
+    __device__ __forceinline__ void set(uint32_t j, int s) {  // (0 <= s <= 65535, the field still zero)
+        const uint32_t f = (uint32_t)s << (16u * (j & 1u));
+        lo |= (j & 2u) ? 0u : f;
+        hi |= (j & 2u) ? f : 0u;
+    }
+};
+template <>
+struct Four<int32_t> {
+    uint64_t lo, hi;  // samples 0 | 1 and 2 | 3 (picked out with shifts: selects between four named dwords came back as an indexed array)
+    typedef uint32_t Quad __attribute__((ext_vector_type(4), aligned(4)));  // one 16-byte access at the samples' own alignment
+    __device__ __forceinline__ void clear() { lo = hi = 0; }
+    __device__ __forceinline__ void load(const int32_t *p) {
+        const Quad q = *reinterpret_cast<const Quad *>(p);
+        lo = (uint64_t)q.x | ((uint64_t)q.y << 32);
+        hi = (uint64_t)q.z | ((uint64_t)q.w << 32);
+    }
+    __device__ __forceinline__ void store(int32_t *p) const {
+        Quad q;
+        q.x = (uint32_t)lo;
+        q.y = (uint32_t)(lo >> 32);
+        q.z = (uint32_t)hi;
+        q.w = (uint32_t)(hi >> 32);
+        *reinterpret_cast<Quad *>(p) = q;
+    }
+    __device__ __forceinline__ int get(uint32_t j) const { return (int)(uint32_t)(((j & 2u) ? hi : lo) >> (32u * (j & 1u))); }
+    __device__ __forceinline__ void set(uint32_t j, int s) {  // (the field still zero)
+        const uint64_t f = (uint64_t)(uint32_t)s << (32u * (j & 1u));
+        lo |= (j & 2u) ? 0ull : f;
+        hi |= (j & 2u) ? f : 0ull;
+    }
+};
+
+// first row of a lane's tables in the launch's table buffer
+__device__ __forceinline__ uint64_t lane_table_row(const LaneUniform &, const LaneView &v, uint32_t np, uint32_t rows) {
+    return (uint64_t)v.slot * np * rows;
+}
+__device__ __forceinline__ uint64_t lane_table_row(const LaneMixed &g, const LaneView &v, uint32_t, uint32_t) { return g.slots[v.slot].table_row; }
+
+}  // namespace
+
+// RGB = false: gray16 streams, u16 frames straight to `out_base`.  RGB = true: Y / Co / Cg off the same reader as int32 planes
+// (k_ycocg16_to_rgb converts them).  `table`: decode16_lanes_table_bytes of the launch's streams; epoch0 .. epoch0 + 2 are this
+// launch's (one per plane).  G: LaneUniform or LaneMixed.
+template <bool RGB, typename G>
+__global__ __launch_bounds__(64) void k_decode16_lanes(const uint8_t *__restrict__ streams, const uint64_t *__restrict__ offsets,
+                                                       const uint64_t *__restrict__ lens, G geo, void *out_base, uint4 *table,
+                                                       uint32_t epoch0, int *__restrict__ status) {
+    using ST = typename std::conditional<RGB, int32_t, uint16_t>::type;
+    constexpr uint32_t NP = RGB ? 3u : 1u;
+    const uint32_t lane = lane_id();
+    LaneView v;
+    if (!lane_view(geo, lane, v)) return;
+    const uint32_t img = v.img, W = v.W, H = v.H;
+    const uint8_t *s = streams + offsets[img];
+    const uint64_t slen = lens[img];
+    const uint64_t npix = (uint64_t)W * H;
+    int rc = FELICS_OK;
+    if (slen < FELICS_HEADER_BYTES) {
+        rc = FELICS_E_IO;
+    } else {
+        const uint32_t w = ((uint32_t)s[6] << 24) | ((uint32_t)s[7] << 16) | ((uint32_t)s[8] << 8) | s[9];
+        const uint32_t h = ((uint32_t)s[10] << 24) | ((uint32_t)s[11] << 16) | ((uint32_t)s[12] << 8) | s[13];
+        if (s[0] != 'F' || s[1] != 'L' || s[2] != 'C' || s[3] != 'S') rc = FELICS_E_INVALID_SIGNATURE;
+        else if (s[4] > 1) rc = FELICS_E_INVALID_COLOR_TYPE;
+        else if (s[5] > 1) rc = FELICS_E_INVALID_PIXEL_DEPTH;
+        else if (s[4] != (RGB ? 1 : 0) || s[5] != 1 || w != W || h != H) rc = FELICS_E_INVALID_DIMENSIONS;
+    }
+    if (rc != FELICS_OK) {  // nothing of this stream is decoded (its lane leaves; the others go on)
+        status[img] = rc;
+        return;
+    }
+    LaneReader br;
+    br.init(s + FELICS_HEADER_BYTES, slen - FELICS_HEADER_BYTES);
+    const uint32_t rows = dec16l_rows(npix, NP);  // (wave-uniform)
+    uint4 *tab0 = table + lane_table_row(geo, v, NP, rows) * 4u;
+    for (uint32_t plane = 0; plane < NP; plane++) {
+    const int32_t p0 = (int32_t)br.get(32), p1 = (int32_t)br.get(32);  // compression.rs:166-167
+    if (br.failed() && rc == FELICS_OK) rc = FELICS_E_IO;
+    if (npix == 0) continue;
+    uint4 *tab = tab0 + (uint64_t)plane * rows * 4u;
+    const uint32_t epoch = epoch0 + plane;  // KEstimator::new: rows of other epochs are empty
+    ST *out = lane_plane<ST>(geo, out_base, v, NP, plane, npix);
+    const int lo_ok = (RGB && plane > 0) ? -65535 : 0, hi_ok = 65535;  // Y 0..65535, Co / Cg -65535..65535
+    int left = 0, left2 = 0;
+    Four<ST> up4, up4_next, out4;
+    up4.clear();
+    up4_next.clear();
+    out4.clear();
+    uint32_t out_of_range = 0;
+    int first_col2 = 0;
+    for (uint32_t y = 0; y < H; y++) {
+      ST *row = out + (uint64_t)y * W;
+      const ST *prow = row - W;
+      if (y > 0) {
+          up4.load(prow);
+          if (4 < W) up4_next.load(prow + 4);
+          first_col2 = y >= 2 ? (int)prow[-(int64_t)W] : (W > 1 ? up4.get(1) : 0);
+      }
+      for (uint32_t x = 0; x < W; x++) {
+        const uint32_t xs = x & 3u;
+        if (xs == 0 && y > 0 && x != 0) {
+            up4 = up4_next;
+            if (x + 4 < W) up4_next.load(prow + x + 4);
+        }
+        int pv;
+        if (y == 0 && x < 2) {
+            pv = x == 0 ? p0 : p1;
+        } else {
+            const int above = up4.get(xs);
+            const bool row0 = y == 0, col0 = x == 0 && !row0;
+            const int v1 = col0 ? above : left;
+            const int v2 = col0 ? first_col2 : (row0 ? left2 : above);
+            const int hi = max(v1, v2), lo = min(v1, v2);
+            const uint32_t ctx = (uint32_t)(hi - lo);  // <= 131 070: every sample kept is in range
+            br.refill();  // >= 33 valid bits: both kinds of code are read off the top 32 of them where they fit
+            const uint32_t top = (uint32_t)(br.acc >> 32);
+            const bool in_range = (top >> 31) != 0;
+            // -- in range: `1`, then the phased-in code of p - L in m or m + 1 bits (phase_in_coding.rs:86-112), m <= 16
+            const uint32_t nn = ctx + 1;
+            const uint32_t m = 31u - (uint32_t)__builtin_clz(nn);
+            const uint32_t right_p = (2u << m) - nn, left_p = nn - (1u << m);
+            const uint32_t t1 = top << 1;
+            uint32_t r = (t1 >> 1) >> (31u - m);
+            const uint32_t extra = (t1 >> (31u - m)) & 1u;
+            const uint32_t longer = r >= right_p ? 1u : 0u;
+            r = longer ? (r - right_p) * 2u + right_p + extra : r;
+            uint32_t rot = r + left_p;
+            rot = rot >= nn ? rot - nn : rot;
+            pv = lo + (int)rot;
+            uint32_t nbits = 1u + m + longer;  // <= 18
+            if (!in_range) {
+                // -- out of range: `0`, above / below flag, q ones, `0`, k bits
+                const bool above_flag = ((top >> 30) & 1u) != 0;
+                uint4 q0, q1, q2, q3;
+                q0 = q1 = q2 = q3 = make_uint4(0, 0, 0, 0);
+                bool found;
+                const uint32_t at = dec16l_find(ctx, rows, epoch,
+                                                [&](uint32_t rw) {
+                                                    const uint4 *p = tab + (uint64_t)rw * 4u;
+                                                    q0 = p[0];
+                                                    q1 = p[1];
+                                                    q2 = p[2];
+                                                    q3 = p[3];
+                                                    return q3.w;
+                                                },
+                                                found);
+                const bool full = at == DEC16L_FULL;
+                if (full && rc == FELICS_OK) rc = FELICS_E_IO;  // (internal: the sizing rule admits every context a plane can use)
+                uint32_t S[15] = {q0.x, q0.y, q0.z, q0.w, q1.x, q1.y, q1.z, q1.w, q2.x, q2.y, q2.z, q2.w, q3.x, q3.y, q3.z};
+                if (!found) {
+#pragma unroll
+                    for (uint32_t kk = 0; kk < 15; kk++) S[kk] = 0;
+                }
+                // get_k: smallest counter, ties to the largest k (parameter_selection.rs:71-85)
+                uint32_t key = 0xFFFFFFFFu;
+#pragma unroll
+                for (uint32_t kk = 0; kk < 15; kk++) key = min(key, (S[kk] << 4) | (15u - kk));
+                const uint32_t k = 15u - (key & 15u);
+                const uint32_t t2 = top << 2;                        // 30 bits of the stream, two zeros behind them
+                const uint32_t ones = (uint32_t)__builtin_clz(~t2);  // (<= 30: ~t2 ends in ones)
+                uint32_t e;
+                if (ones + 1u + k <= 30u) {  // unary part, its zero and the k bits lie inside the 30
+                    e = (ones << k) + (((t2 << (ones & 31u)) << 1 >> 1) >> (31u - k));
+                    nbits = 3u + ones + k;  // <= 32 < the valid bits
+                    if (e > 262144u) {
+                        if (rc == FELICS_OK) rc = FELICS_E_INVALID_VALUE;
+                        e = 0;
+                    }
+                } else {
+                    // a long code (or the end of the stream): the general reader, bit field by bit field
+                    br.take(2);
+                    const uint64_t q = br.unary0();
+                    const uint64_t e64 = (q << k) + br.get(k);
+                    e = (uint32_t)e64;
+                    if (e64 > 262144u) {  // no sample of a 16-bit plane is that far from its neighbours
+                        if (rc == FELICS_OK) rc = e64 > 0xFFFFFFFFull ? FELICS_E_VALUE_OVERFLOW : FELICS_E_INVALID_VALUE;
+                        e = 0;
+                    }
+                    nbits = 0;
+                }
+                // update (parameter_selection.rs:49-68): add the fifteen Rice lengths, halve when the smallest passes 1024
+                uint32_t mn = 0xFFFFFFFFu;
+#pragma unroll
+                for (uint32_t kk = 0; kk < 15; kk++) {
+                    S[kk] += (e >> kk) + 1u + kk;
+                    mn = min(mn, S[kk]);
+                }
+                const uint32_t hsh = mn > 1024u ? 1u : 0u;
+                if (!full) {
+                    uint4 *p = tab + (uint64_t)at * 4u;
+                    p[0] = make_uint4(S[0] >> hsh, S[1] >> hsh, S[2] >> hsh, S[3] >> hsh);
+                    p[1] = make_uint4(S[4] >> hsh, S[5] >> hsh, S[6] >> hsh, S[7] >> hsh);
+                    p[2] = make_uint4(S[8] >> hsh, S[9] >> hsh, S[10] >> hsh, S[11] >> hsh);
+                    p[3] = make_uint4(S[12] >> hsh, S[13] >> hsh, S[14] >> hsh, dec16l_tag(epoch, ctx));
+                }
+                pv = above_flag ? hi + (int)e + 1 : lo - (int)e - 1;
+            }
+            br.acc <<= nbits;
+            br.navail -= nbits;
+        }
+        // try_into::<u16>() (Co / Cg: the estimator's context bound) would fail on anything outside lo_ok .. hi_ok: remembered and
+        // reported at the end of the row; the sample is cut into the range so that a failed stream's contexts stay below 131 071
+        out_of_range |= (uint32_t)pv - (uint32_t)lo_ok > (uint32_t)(hi_ok - lo_ok) ? 1u : 0u;  // (the raw samples are any 32 bits)
+        pv = min(max(pv, lo_ok), hi_ok);
+        out4.set(xs, pv);
+        left2 = left;
+        left = pv;
+        if (xs == 3u) {  // four samples complete: one (unaligned) store to the stream's plane
+            out4.store(row + (x - 3u));
+            out4.clear();
+        } else if (x + 1 == W) {  // the last one to three samples of a row
+            for (uint32_t j = 0; j <= xs; j++) row[(x - xs) + j] = (ST)out4.get(j);
+            out4.clear();
+        }
+      }
+      if (rc == FELICS_OK) rc = br.failed() ? FELICS_E_IO : (out_of_range ? FELICS_E_INVALID_VALUE : FELICS_OK);
+    }
+    }
+    if (br.failed() && rc == FELICS_OK) rc = FELICS_E_IO;  // (whatever else: it was decoding padding)
+    status[img] = rc;
+}
+
 uint32_t decode16_lds_bytes(uint32_t W) {
     return DEC16_SLOTS * DEC16_ROW * 4 + DEC16_SLOTS * 4 + 2u * decode8_row_stride(W) * 4u;
 }
@@ -960,6 +1227,23 @@ hipError_t launch_decode16(hipStream_t s, const uint8_t *streams, const uint64_t
         const uint32_t bx = (uint32_t)std::min<uint64_t>((npix + 255) / 256, 1024u);
         if (bx) hipLaunchKernelGGL(k_ycocg16_to_rgb<ConvUniform>, dim3(bx, n), dim3(256), 0, s, planes, pixels, ConvUniform{(uint32_t)npix}, status);
     }
+    return hipGetLastError();
+}
+
+hipError_t launch_decode16_lanes(hipStream_t s, const uint8_t *streams, const uint64_t *offsets, const uint64_t *lens, uint32_t n,
+                                 uint32_t W, uint32_t H, uint32_t color, uint16_t *pixels, int32_t *planes, uint32_t *table,
+                                 uint32_t epoch0, int *status) {
+    if (n == 0) return hipSuccess;
+    if (!color) {
+        hipLaunchKernelGGL((k_decode16_lanes<false, LaneUniform>), dim3((n + 63) / 64), dim3(64), 0, s, streams, offsets, lens,
+                           LaneUniform{n, W, H}, (void *)pixels, reinterpret_cast<uint4 *>(table), epoch0, status);
+        return hipGetLastError();
+    }
+    hipLaunchKernelGGL((k_decode16_lanes<true, LaneUniform>), dim3((n + 63) / 64), dim3(64), 0, s, streams, offsets, lens,
+                       LaneUniform{n, W, H}, (void *)planes, reinterpret_cast<uint4 *>(table), epoch0, status);
+    const uint64_t npix = (uint64_t)W * H;
+    const uint32_t bx = (uint32_t)std::min<uint64_t>((npix + 255) / 256, 1024u);
+    if (bx) hipLaunchKernelGGL(k_ycocg16_to_rgb<ConvUniform>, dim3(bx, n), dim3(256), 0, s, planes, pixels, ConvUniform{(uint32_t)npix}, status);
     return hipGetLastError();
 }
 
@@ -1089,6 +1373,21 @@ hipError_t launch_decode8_lanes_waves(hipStream_t s, const uint8_t *streams, con
     }
     hipLaunchKernelGGL((k_decode8_lanes<true, LaneMixed>), dim3(nwaves), dim3(64), 0, s, streams, offsets, lens, LaneMixed{waves, slots},
                        (void *)planes, table, status);
+    launch_conv_rows(s, conv, nconv, max_npix, planes, pixels, status);
+    return hipGetLastError();
+}
+
+hipError_t launch_decode16_lanes_waves(hipStream_t s, const uint8_t *streams, const uint64_t *offsets, const uint64_t *lens, const LaneWave *waves,
+                                       uint32_t nwaves, const LaneSlot *slots, uint32_t color, const DecodeRow *conv, uint32_t nconv,
+                                       uint64_t max_npix, uint16_t *pixels, int32_t *planes, uint32_t *table, uint32_t epoch0, int *status) {
+    if (nwaves == 0) return hipSuccess;
+    if (!color) {
+        hipLaunchKernelGGL((k_decode16_lanes<false, LaneMixed>), dim3(nwaves), dim3(64), 0, s, streams, offsets, lens, LaneMixed{waves, slots},
+                           (void *)pixels, reinterpret_cast<uint4 *>(table), epoch0, status);
+        return hipGetLastError();
+    }
+    hipLaunchKernelGGL((k_decode16_lanes<true, LaneMixed>), dim3(nwaves), dim3(64), 0, s, streams, offsets, lens, LaneMixed{waves, slots},
+                       (void *)planes, reinterpret_cast<uint4 *>(table), epoch0, status);
     launch_conv_rows(s, conv, nconv, max_npix, planes, pixels, status);
     return hipGetLastError();
 }

@@ -8,6 +8,8 @@
 
 #include <algorithm>
 
+#include "felics_lanetable.h"
+
 namespace felics {
 
 // Contexts (H - L of a pixel's two neighbours, traits.rs:28): 0..255 for u8 samples, 0..510 for the Y/Co/Cg planes of
@@ -261,6 +263,22 @@ hipError_t launch_decode8_lanes(hipStream_t s, const uint8_t *streams, const uin
                                 uint32_t W, uint32_t H, uint32_t color, uint8_t *pixels, int16_t *planes, uint32_t *table, int *status);
 hipError_t launch_decode8(hipStream_t s, const uint8_t *streams, const uint64_t *offsets, const uint64_t *lens, uint32_t n,
                           uint32_t W, uint32_t H, uint32_t color, uint8_t *pixels, int16_t *planes, int *status);
+// The same for 16-bit streams, gray or RGB (k_decode16_lanes): 64 streams per wave, lane = stream; needs W >= 8 and a table of
+// decode16_lanes_table_bytes(n, W, H, color) bytes = n * planes * dec16l_rows(W * H, planes) * 64 (felics_lanetable.h: sized by the
+// pixel count, 512 KB per plane of a 64 x 64 stream, the wave form's 8.4 MB from 32 771 pixels on), zero-initialised ONCE: rows carry
+// the epoch they were written in; a launch uses epochs epoch0 .. epoch0 + 2, in 1 .. DEC16L_EPOCH_MAX and never reused on the same
+// buffer.  RGB: `planes` takes the int32 planes (n * 3 * W * H), `pixels` the converted frames.
+constexpr uint32_t DECODE16_LANES_NEVER = 0xFFFFFFFFu;  // a threshold no call reaches (the form then only when forced); not needed today
+// measured (profiles/decode16_lanes.txt, 64 x 64 streams, both forms in one run): the wave form saturates at 1.3 - 2.0 GPix/s from
+// ~1000 streams, a lane decodes 0.5 - 1.0 MPix/s whatever the batch; at 1 024 streams the lane form has half the wave form's rate
+// on synth, natural and noise content alike, at 4 096 it is 1.8 - 2.0x faster on all three (16 384: 6.7 - 6.8x, 8.4 - 13.6 GPix/s)
+constexpr uint32_t DECODE16_LANES_MIN_STREAMS = 4096;
+// RGB16 (same file): the wave form's 0.38 - 0.54 GPix/s against 0.19 - 0.29 at 1 024 streams, 0.38 - 0.55 against 0.76 - 1.10 at 4 096 (2.0 - 2.1x)
+constexpr uint32_t DECODE16_LANES_MIN_STREAMS_RGB = 4096;
+// size_t decode16_lanes_table_bytes(uint32_t n, uint32_t W, uint32_t H, uint32_t color): felics_lanetable.h (the native check compiles it too)
+hipError_t launch_decode16_lanes(hipStream_t s, const uint8_t *streams, const uint64_t *offsets, const uint64_t *lens, uint32_t n,
+                                 uint32_t W, uint32_t H, uint32_t color, uint16_t *pixels, int32_t *planes, uint32_t *table,
+                                 uint32_t epoch0, int *status);
 // The headers of n streams in device memory (felics_read_headers_device, felics_decompress_images_device): a lane per stream,
 // felics_read_header's checks in its order, every read inside [offsets[i], offsets[i] + lens[i]).  Fields are zero where
 // status != FELICS_OK.  dstatus: status, or for a valid header the decode call's own rules -- w * h < 2^32
@@ -287,7 +305,7 @@ struct LaneWave {
 };
 struct LaneSlot {
     uint32_t stream;     // index into offsets / lens / status; the slot's index names its estimator table
-    uint32_t pad;
+    uint32_t table_row;  // k_decode16_lanes: first row of the slot's estimator tables in the launch's table (k_decode8_lanes: unused, 0)
     uint64_t out_off;    // element offset: gray, of the frame in the caller's pixels; RGB, of its planes in `planes`
 };
 // one launch per LDS class: lds = decode8_lds_bytes of the class's widest row; RGB rows through the int16 `planes`
@@ -297,6 +315,11 @@ hipError_t launch_decode8_rows(hipStream_t s, const uint8_t *streams, const uint
 hipError_t launch_decode8_lanes_waves(hipStream_t s, const uint8_t *streams, const uint64_t *offsets, const uint64_t *lens, const LaneWave *waves,
                                       uint32_t nwaves, const LaneSlot *slots, uint32_t color, const DecodeRow *conv, uint32_t nconv,
                                       uint64_t max_npix, uint8_t *pixels, int16_t *planes, uint32_t *table, int *status);
+// 16-bit waves of one colour (k_decode16_lanes<.., LaneMixed>): slot j's tables start at row slots[j].table_row of `table` and take
+// planes * dec16l_rows(W * H, planes) rows; out_off in samples (u16 of the caller's pixels / int32 of `planes`)
+hipError_t launch_decode16_lanes_waves(hipStream_t s, const uint8_t *streams, const uint64_t *offsets, const uint64_t *lens, const LaneWave *waves,
+                                       uint32_t nwaves, const LaneSlot *slots, uint32_t color, const DecodeRow *conv, uint32_t nconv,
+                                       uint64_t max_npix, uint16_t *pixels, int32_t *planes, uint32_t *table, uint32_t epoch0, int *status);
 // a pass of 16-bit rows: row j uses estimator table j
 hipError_t launch_decode16_rows(hipStream_t s, const uint8_t *streams, const uint64_t *offsets, const uint64_t *lens, const DecodeRow *rows,
                                 uint32_t n, uint32_t lds, uint64_t max_npix, bool any_rgb, uint16_t *pixels, int32_t *planes, uint32_t *table,

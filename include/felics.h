@@ -219,8 +219,11 @@ int felics_decompress_with_header(const uint8_t *in, size_t len, const felics_he
  * DecompressionError code of stream i; the function returns the first non-zero status (or a HIP / argument
  * error).  *hdr (optional) receives the header all streams must share; it is read from stream 0.
  * Replaces n calls of `decompress_image` (compression.rs:420-441).  The format is bit-serial per stream (and the
- * planes of an RGB image share one bit stream), so the only parallelism is across streams: one wave per stream
- * for 8-bit and for 16-bit data (k_decode16: a 8.4 MB estimator table per stream in device memory, rows tagged with an epoch).
+ * planes of an RGB image share one bit stream), so the only parallelism is across streams: one wave per stream, or, in large
+ * batches of streams at least 8 pixels wide, 64 streams per wave with a stream per lane.  16-bit data: k_decode16 (a wave per
+ * stream, a 8.4 MB estimator table per stream in device memory, rows tagged with an epoch) or k_decode16_lanes (a lane per stream,
+ * a hashed table sized by the stream's pixel count: 512 KB per plane of a 64 x 64 stream), the latter from
+ * felics_decode_lanes_min_streams(1, color) streams on; felics_get_decode_stats says which form a call's streams took.
  * status[] is written for all n streams on every return (a call that ends before decoding -- bad header of stream 0, buffer too
  * small, a HIP error -- puts its own code in every entry).  The kernel loads a stream as whole ALIGNED 32-bit words: it may
  * touch up to three bytes on either side of a stream, always inside an aligned word that also holds a byte of the stream,
@@ -260,9 +263,27 @@ int felics_read_headers_device(felics_ctx *ctx, size_t n, const void *d_streams,
  *   - The stream contract of felics_decompress_batch_device holds (complete in memory when the call is made; the kernels load
  *     whole aligned words).  The same stream may be referenced several times.
  * Returns the first non-zero status.  8-bit streams decode one wave per stream, or 64 streams of one shape per wave in calls of
- * many 8-bit streams; 16-bit streams one wave per stream; streams whose rows do not fit the LDS on the host. */
+ * many 8-bit streams; 16-bit streams likewise: one wave per stream, or, in calls of at least
+ * felics_decode_lanes_min_streams(1, color) 16-bit streams, whole waves of 64 streams of one shape and colour (the rest of such a
+ * group a wave per stream); streams whose rows do not fit the LDS on the host.  felics_get_decode_stats counts the forms. */
 int felics_decompress_images_device(felics_ctx *ctx, size_t n, const void *d_streams, const uint64_t *offsets, const uint64_t *lens,
                                     void *d_pixels, size_t d_pixels_cap, uint64_t *pix_offsets, felics_header *hdrs, int *status);
+
+/* Which form the streams of a context's device decode calls took so far. */
+typedef struct felics_decode_stats {   /* cumulative per context */
+    uint64_t streams;       /* streams handed to the two device decode calls (calls that passed the checks) */
+    uint64_t wave8, lanes8; /* 8-bit streams decoded a wave per stream / a lane per stream */
+    uint64_t wave16, lanes16;
+    uint64_t host;          /* streams that went to the host decoder (rows too wide for the LDS) */
+    uint64_t undecoded;     /* streams that got a status without being decoded (bad header, too short, buffer too small) */
+    uint64_t lanes16_table_bytes; /* table memory the last call's 16-bit lane launches used (its largest pass) */
+} felics_decode_stats;
+/* Writes min(out_size, sizeof(felics_decode_stats)) bytes, never more: a caller built against a shorter struct stays valid. */
+int felics_get_decode_stats(const felics_ctx *ctx, felics_decode_stats *out, size_t out_size);
+/* Streams of a depth (0: 8 bits, 1: 16) a device decode call must hold for them to go 64 to a wave (color: 0 gray, 1 RGB);
+ * 0xFFFFFFFF: no call does.  FELICS_TEST_DECODE16_LANES=1 / =0 in the environment (read per call) forces / forbids that form for
+ * 16-bit streams whatever the count. */
+uint32_t felics_decode_lanes_min_streams(int depth, int color);
 
 /* Text for a code above; for FELICS_E_HIP felics_last_error(ctx) has the HIP message. */
 const char *felics_strerror(int code);
