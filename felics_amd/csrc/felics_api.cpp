@@ -567,7 +567,7 @@ int run_wide(felics_ctx *ctx, Lane &l, uint8_t *d_out, uint64_t slot_stride) {
                              g.pack_tiles);
         launch_finish_sizes(s, plane_carry, plane_base, (uint64_t *)l.image_bytes.p, g);
     }
-    if (slot_stride != 0) {
+    if (slot_stride != 0 || g.mixed) {  // (a mixed sub-batch: every stream into the slot its table row names)
         {
             StageTimer t(ctx, l, ST_ZERO, s);
             launch_zero_edges(s, d_out, nullptr, slot_stride, (const uint64_t *)l.tile_bitoff.p,
@@ -915,8 +915,10 @@ bool any_pending(const felics_ctx *ctx) {
 // ---- mixed shapes (felics_compress_images*) ------------------------------------------------------------------------------
 // 8-bit images go in BUCKETS of similar size: sorted by sort tiles T = ceil(w h / SORT_TILE), a bucket holds T_min .. ceil(1.25 T_min)
 // (at most 25 % of a bucket's tiles are padding), and a bucket is one sub-batch whose tile count is uniform at its T_max; what
-// differs per plane (samples, W, H, npix, the image's slot) comes from a table (Geometry::mixed).  16-bit images go through the
-// uniform path, one group per shape.  The sub-batches are queued over the lanes like felics_compress_batch's chunks.
+// differs per plane (samples, W, H, npix, the image's slot) comes from a table (Geometry::mixed).  16-bit images are bucketed by the
+// same rule; a bucket (or a pass of one) of ONE shape takes the uniform path (frames gathered in mix_in, streams copied out of
+// mix_stage), every other one is a mixed 16-bit sub-batch: run_wide with the table, frames read in place, streams straight into
+// their slots.  The sub-batches are queued over the lanes like felics_compress_batch's chunks.
 
 constexpr size_t MIX_MAX_IMAGES = 8192;  // images of one mixed sub-batch (k_concat_planes / k_rgb8_to_planes_mixed: one grid row per image)
 
@@ -989,11 +991,12 @@ uint64_t mix_slot(size_t frame_bytes) { return ((uint64_t)frame_bytes + frame_by
 uint32_t sort_tiles_of(uint64_t npix) { return (uint32_t)((npix + SORT_TILE - 1) / SORT_TILE); }
 
 struct MixJob {
-    bool wide = false;          // a 16-bit group of one shape (uniform path), else a mixed 8-bit sub-batch
+    bool wide = false;          // a 16-bit group of one shape (uniform path), else a mixed sub-batch ...
+    bool wide_mixed = false;    // ... of 16-bit images (launch_mixed_wide), else of 8-bit ones (launch_mixed)
     std::vector<size_t> idx;    // its images
     int lane = -1;
-    size_t in_off = 0, stage_off = 0;  // 16-bit: where its frames are gathered (mix_in) and its streams land (mix_stage)
-    uint64_t slot = 0;                 // 16-bit: the group's slot in mix_stage
+    size_t in_off = 0, stage_off = 0;  // 16-bit: where its frames are gathered (mix_in; mixed: its views only) and, one shape, its streams land (mix_stage)
+    uint64_t slot = 0;                 // 16-bit group of one shape: its slot in mix_stage
 };
 
 // Where a call's streams go: image i at base + off[i], at most slot[i] bytes.  lens[i] = the size of stream i whether it fit or
@@ -1004,6 +1007,17 @@ struct MixOut {
     uint64_t *lens;
     bool overflow;
 };
+
+// The lane's pinned plane table, for nplanes rows (and one extra row per plane: launch_mixed)
+int reserve_table(felics_ctx *ctx, Lane &l, uint32_t nplanes) {
+    if (nplanes > l.h_table_cap) {
+        if (l.h_table) HIP_TRY(ctx, hipHostFree(l.h_table));
+        l.h_table = nullptr;
+        HIP_TRY(ctx, hipHostMalloc((void **)&l.h_table, (size_t)nplanes * (sizeof(PlaneGeom) + sizeof(PitchedGeom)), hipHostMallocDefault));
+        l.h_table_cap = nplanes;
+    }
+    return FELICS_OK;
+}
 
 // Queues a mixed 8-bit sub-batch on lane l (see launch_sub_batch).
 int launch_mixed(felics_ctx *ctx, Lane &l, const std::vector<MixImage> &im, const std::vector<size_t> &idx, const MixOut &o, int nslices) {
@@ -1038,12 +1052,7 @@ int launch_mixed(felics_ctx *ctx, Lane &l, const std::vector<MixImage> &im, cons
     if (planes == 3 && (rc = reserve(ctx, l.planes, (size_t)g.nplanes * pstride * 2 + STAGE_PAD)) != 0) return rc;
     // (behind the table, room for what views add to it: the pitched policy's rows of a gray sub-batch, the views of an RGB one)
     static_assert(sizeof(PitchedGeom) >= sizeof(ViewRow) && sizeof(PlaneGeom) % 8 == 0, "one extra row per plane holds either");
-    if (g.nplanes > l.h_table_cap) {
-        if (l.h_table) HIP_TRY(ctx, hipHostFree(l.h_table));
-        l.h_table = nullptr;
-        HIP_TRY(ctx, hipHostMalloc((void **)&l.h_table, (size_t)g.nplanes * (sizeof(PlaneGeom) + sizeof(PitchedGeom)), hipHostMallocDefault));
-        l.h_table_cap = g.nplanes;
-    }
+    if ((rc = reserve_table(ctx, l, g.nplanes)) != 0) return rc;
     bool any_view = false;
     for (size_t i : idx) any_view = any_view || im[i].view;
     const size_t extra_off = (size_t)g.nplanes * sizeof(PlaneGeom);
@@ -1082,6 +1091,82 @@ int launch_mixed(felics_ctx *ctx, Lane &l, const std::vector<MixImage> &im, cons
             launch_rgb8_to_planes_mixed(fs, g.mixed, pstride, (uint32_t)max_npix, (uint32_t)cnt);
     }
     return planes == 3 ? run_lane<int16_t, uint16_t>(ctx, l, o.base, 0) : run_lane<uint8_t, uint8_t>(ctx, l, o.base, 0);
+}
+
+// a view's dense copy in a mixed 16-bit job's part of mix_in: 256-byte steps
+size_t gather_step(const MixImage &m) { return m.view ? (m.frame_bytes + 255) & ~(size_t)255 : 0; }
+
+// Queues a mixed 16-bit sub-batch on lane l: run_wide on the padded geometry (npix = T_max * SORT_TILE: the stride of k_map and, RGB16, of
+// the i32 planes) with the plane table.  gray16 frames are read where the caller has them, RGB16 frames by the plane transform; a
+// view is gathered to `gathered` first (stage_frame: counted in bytes_staged) and its rows point there.  Everything on the lane's
+// one stream, behind the caller's ready event.
+int launch_mixed_wide(felics_ctx *ctx, Lane &l, const std::vector<MixImage> &im, const std::vector<size_t> &idx, const MixOut &o, uint8_t *gathered,
+                      int nslices) {
+    const MixImage &f = im[idx[0]];
+    const uint32_t planes = f.planes;
+    const size_t cnt = idx.size();
+    uint32_t tmax = 0;
+    uint64_t max_npix = 0;
+    for (size_t i : idx) {
+        tmax = std::max(tmax, sort_tiles_of(im[i].npix));
+        max_npix = std::max(max_npix, im[i].npix);
+    }
+    l.nslices = std::max(1, std::min(nslices, SLICES));
+    l.queued = true;
+    ctx->stats.submissions++;
+    for (int i = 0; i < ST_COUNT; i++) l.ev_used[i] = 0;
+    Geometry &g = l.g;
+    g.W = SORT_TILE;  // (the uniform fields describe the padded planes, as in launch_mixed)
+    g.H = tmax;
+    g.npix = tmax * SORT_TILE;
+    g.nimages = (uint32_t)cnt;
+    g.planes_per_image = planes;
+    g.nplanes = (uint32_t)(cnt * planes);
+    g.sort_tiles = tmax;
+    g.pack_tiles = tmax;
+    g.color = (uint32_t)f.color;
+    g.depth = FELICS_DEPTH_16;
+    g.nctx = planes == 3 ? nctx_of<int16_t>() : nctx_of<uint8_t>();  // (unused: run_wide has tables of its own)
+    g.pitched = nullptr;
+    l.first_image = 0;
+    int rc;
+    const uint64_t pstride = g.npix;
+    if (planes == 3 && (rc = reserve(ctx, l.planes, (size_t)g.nplanes * pstride * 4 + STAGE_PAD)) != 0) return rc;
+    if ((rc = reserve_table(ctx, l, g.nplanes)) != 0) return rc;
+    const size_t tbytes = (size_t)g.nplanes * sizeof(PlaneGeom);
+    if ((rc = reserve(ctx, l.mtable, tbytes)) != 0) return rc;
+    hipStream_t s = l.stream;
+    if ((rc = wait_ready(ctx, s)) != 0) return rc;
+    if (ctx->profiling) HIP_TRY(ctx, hipEventRecord(l.span_begin, s));
+    size_t at = 0;
+    for (size_t j = 0; j < cnt; j++) {
+        const MixImage &m = im[idx[j]];
+        const uint8_t *frame = m.px;
+        if (m.view) {
+            frame = gathered + at;
+            if ((rc = stage_frame(ctx, s, gathered + at, m)) != 0) return rc;
+            at += gather_step(m);
+        }
+        for (uint32_t c = 0; c < planes; c++) {
+            PlaneGeom &pg = l.h_table[j * planes + c];
+            pg.samples = planes == 3 ? (const void *)((int32_t *)l.planes.p + (j * planes + c) * pstride) : (const void *)frame;
+            pg.image = frame;
+            pg.W = m.w;
+            pg.H = m.h;
+            pg.npix = (uint32_t)m.npix;
+            pg.ntiles = (uint32_t)((m.npix + PACK_TILE - 1) / PACK_TILE);
+            pg.out_off = o.off[idx[j]];
+            pg.out_slot = o.slot[idx[j]];
+        }
+    }
+    HIP_TRY(ctx, hipMemcpyAsync(l.mtable.p, l.h_table, tbytes, hipMemcpyHostToDevice, s));
+    g.mixed = (const PlaneGeom *)l.mtable.p;
+    l.d_planes = planes == 3 ? l.planes.p : nullptr;  // (the mixed kernels take every plane from the table)
+    if (planes == 3) {
+        StageTimer t(ctx, l, ST_PLANES, s, true);
+        launch_rgb16_to_planes_mixed(s, g.mixed, (uint32_t)max_npix, (uint32_t)cnt);
+    }
+    return planes == 3 ? run_wide<int32_t>(ctx, l, o.base, 0) : run_wide<uint16_t>(ctx, l, o.base, 0);
 }
 
 // The remedy: the images of `idx` once more through encode_device (its whole ladder), one group per shape, frames gathered
@@ -1152,6 +1237,22 @@ int land_job(felics_ctx *ctx, MixJob &j, const std::vector<MixImage> &im, MixOut
         collect_timing(ctx, l);
         return FELICS_OK;
     }
+    if (j.wide_mixed) {  // (run_wide copies the sizes and nothing else: no error / flags word to read)
+        bool overflow = false;
+        for (size_t k = 0; k < cnt; k++) {
+            const size_t i = j.idx[k];
+            o.lens[i] = l.h_sizes[k];
+            if (l.h_sizes[k] > o.slot[i]) overflow = true;
+        }
+        if (!overflow) {
+            if (ctx->profiling && (rc = sync_lane(ctx, l)) != 0) return rc;  // (span_end is recorded behind `sized`)
+            collect_timing(ctx, l);
+            return FELICS_OK;
+        }
+        if ((rc = sync_lane(ctx, l)) != 0) return rc;
+        ctx->stats.slot_overflows++;
+        return redo_by_shape(ctx, l, im, j.idx, o);
+    }
     const uint32_t err = (uint32_t)l.h_sizes[cnt], flags = (uint32_t)(l.h_sizes[cnt] >> 32);
     SlotOutcome so;
     so.lookback_failed = (err & 1u) != 0 || (ctx->test_lookback && l.m_fused);
@@ -1208,28 +1309,55 @@ int run_images(felics_ctx *ctx, const std::vector<MixImage> &im, MixOut &o) {
         }
     }
     size_t in_total = 0, stage_total = 0;
-    {  // 16-bit: one group per shape, frames gathered back to back
-        std::vector<bool> taken(n, false);
-        for (size_t i = 0; i < n; i++) {
-            if (taken[i] || !im[i].npix || im[i].depth != FELICS_DEPTH_16) continue;
-            std::vector<size_t> grp;
-            for (size_t k = i; k < n; k++)
-                if (!taken[k] && im[k].npix && im[k].depth == FELICS_DEPTH_16 && im[k].w == im[i].w && im[k].h == im[i].h && im[k].color == im[i].color) {
-                    taken[k] = true;
-                    grp.push_back(k);
+    // 16-bit: the same buckets.  One shape: the uniform path, frames gathered back to back; else a mixed 16-bit sub-batch.
+    auto uniform_job = [&](std::vector<size_t> idx) {
+        const MixImage &f = im[idx[0]];
+        MixJob j;
+        j.wide = true;
+        j.idx = std::move(idx);
+        j.slot = mix_slot(f.frame_bytes);
+        j.in_off = in_total;
+        j.stage_off = stage_total;
+        in_total += ((f.frame_bytes * j.idx.size()) + 255) & ~(size_t)255;
+        stage_total += (size_t)(j.slot * j.idx.size());
+        jobs.push_back(std::move(j));
+    };
+    auto one_shape = [&](const size_t *first, const size_t *last) {
+        for (const size_t *p = first; p != last; p++)
+            if (im[*p].w != im[*first].w || im[*p].h != im[*first].h) return false;
+        return true;
+    };
+    for (int color : {FELICS_COLOR_GRAY, FELICS_COLOR_RGB}) {
+        std::vector<size_t> v;
+        for (size_t i = 0; i < n; i++)
+            if (im[i].npix && im[i].depth == FELICS_DEPTH_16 && im[i].color == color) v.push_back(i);
+        std::stable_sort(v.begin(), v.end(), [&](size_t a, size_t b) { return sort_tiles_of(im[a].npix) < sort_tiles_of(im[b].npix); });
+        const uint32_t planes = color == FELICS_COLOR_RGB ? 3 : 1;
+        for (size_t a = 0; a < v.size();) {
+            const uint64_t tmin = sort_tiles_of(im[v[a]].npix), lim = (5 * tmin + 3) / 4;  // ceil(1.25 T_min)
+            size_t b = a;
+            while (b < v.size() && sort_tiles_of(im[v[b]].npix) <= lim) b++;
+            const bool uniform = one_shape(&v[a], &v[a] + (b - a));
+            // The pass bound with the padded npix = T_max * SORT_TILE keeps planes * npix of a mixed sub-batch <= 2^30 samples, so the
+            // chain kernels' 32-bit kbase = plane * npix (k_map is strided by the padded npix) stays valid.  (A bucket of one shape:
+            // its own npix, the passes that shape always had.)
+            const size_t per = uniform ? max_images_per_pass(im[v[a]].npix, planes, FELICS_DEPTH_16)
+                                       : std::min(MIX_MAX_IMAGES, max_images_per_pass((uint64_t)sort_tiles_of(im[v[b - 1]].npix) * SORT_TILE, planes,
+                                                                                      FELICS_DEPTH_16));
+            for (size_t c = a; c < b; c += per) {
+                const size_t e = std::min(b, c + per);
+                if (uniform || one_shape(&v[c], &v[c] + (e - c))) {
+                    uniform_job(std::vector<size_t>(v.begin() + c, v.begin() + e));
+                    continue;
                 }
-            const size_t per = max_images_per_pass(im[i].npix, im[i].planes, FELICS_DEPTH_16);
-            for (size_t c = 0; c < grp.size(); c += per) {
                 MixJob j;
-                j.wide = true;
-                j.idx.assign(grp.begin() + c, grp.begin() + std::min(grp.size(), c + per));
-                j.slot = mix_slot(im[i].frame_bytes);
+                j.wide_mixed = true;
+                j.idx.assign(v.begin() + c, v.begin() + e);
                 j.in_off = in_total;
-                j.stage_off = stage_total;
-                in_total += ((im[i].frame_bytes * j.idx.size()) + 255) & ~(size_t)255;
-                stage_total += (size_t)(j.slot * j.idx.size());
+                for (size_t i : j.idx) in_total += gather_step(im[i]);
                 jobs.push_back(std::move(j));
             }
+            a = b;
         }
     }
     if (in_total && (rc = reserve(ctx, ctx->mix_in, in_total + 64)) != 0) return rc;
@@ -1259,7 +1387,7 @@ int run_images(felics_ctx *ctx, const std::vector<MixImage> &im, MixOut &o) {
             if (rc) return drain(rc);
         }
         MixJob &j = jobs[q];
-        if (!j.wide && ctx->two_pass) {  // (the mixed kernels are single-pass: a context on the two-pass kernels takes the uniform path,
+        if (!j.wide && !j.wide_mixed && ctx->two_pass) {  // (the mixed kernels are single-pass: a context on the two-pass kernels takes the uniform path,
                                          // blocking, once every lane is idle)
             while (!flying.empty()) {
                 rc = land_job(ctx, jobs[flying.front()], im, o);
@@ -1280,6 +1408,8 @@ int run_images(felics_ctx *ctx, const std::vector<MixImage> &im, MixOut &o) {
                 if ((rc = stage_frame(ctx, l.stream, in + k * f.frame_bytes, im[j.idx[k]])) != 0) return drain(rc);
             for (int i = 0; i < ST_COUNT; i++) l.ev_used[i] = 0;
             rc = launch_sub_batch(ctx, l, 0, j.idx.size(), in, f.w, f.h, f.color, f.depth, (uint8_t *)ctx->mix_stage.p + j.stage_off, j.slot, nslices, true);
+        } else if (j.wide_mixed) {
+            rc = launch_mixed_wide(ctx, l, im, j.idx, o, (uint8_t *)ctx->mix_in.p + j.in_off, nslices);
         } else {
             rc = launch_mixed(ctx, l, im, j.idx, o, nslices);
         }

@@ -67,9 +67,11 @@ struct Geometry {
     uint32_t pack_tiles;        // ceil(npix / PACK_TILE)
     uint32_t color, depth;      // header fields
     uint32_t nctx;              // contexts per plane: nctx_of<sample type>()
-    // A MIXED sub-batch (8-bit images of different sizes, felics_compress_images*): the tile count stays uniform (sort_tiles =
-    // pack_tiles = the largest image's, npix = sort_tiles * SORT_TILE), what differs per plane is read from this device table
-    // (nullptr: the uniform geometry above).
+    // A MIXED sub-batch (images of one depth and colour but different sizes, felics_compress_images*): the tile count stays uniform
+    // (sort_tiles = pack_tiles = the largest image's, npix = sort_tiles * SORT_TILE), what differs per plane is read from this device
+    // table (nullptr: the uniform geometry above).  16-bit samples: launch_wide_events, launch_lengths, launch_zero_edges and
+    // launch_pack take their mixed kernels, the planes pointer they are given is unused, and npix is the stride of k_map (and of the
+    // record's plane in the chain kernels).
     const struct PlaneGeom *mixed = nullptr;
     // A mixed sub-batch of gray8 planes some of which are PITCHED (views read where they lie): beside `mixed`, which the kernels
     // that see bits and not pixels go on reading, a table of the pitched policy's own row type for k_front and k_pack_t
@@ -80,8 +82,8 @@ struct Geometry {
 // One plane of a mixed sub-batch.  The kernels index it by plane (wave-uniform: scalar loads).  Tiles past the plane's own end
 // produce no events and no bits; the plane's size is still published by the last of the sub-batch's tiles.
 struct PlaneGeom {
-    const void *samples;   // the plane's first sample: the caller's frame (gray8), or its Y / Co / Cg plane in the lane's planes buffer
-    const void *image;     // the image's interleaved pixels as the caller gave them (RGB8: what k_rgb8_to_planes reads)
+    const void *samples;   // the plane's first sample: the caller's frame (gray), or its Y / Co / Cg plane in the lane's planes buffer
+    const void *image;     // the image's interleaved pixels as the caller gave them (RGB: what the plane transform reads)
     uint32_t W, H, npix;   // the image's size
     uint32_t ntiles;       // the plane's own pack tiles, ceil(npix / PACK_TILE) (<= Geometry::pack_tiles)
     uint64_t out_off;      // the image's slot in the output: byte offset from PackTarget::out, and size (writes beyond it are dropped)
@@ -332,6 +334,8 @@ hipError_t launch_decode16_rows(hipStream_t s, const uint8_t *streams, const uin
 constexpr uint32_t WIDE_MAX_PLANE_PIXELS = 1u << 29;  // the sample index in a record has 29 bits
 
 void launch_rgb16_to_planes(hipStream_t s, const uint16_t *rgb, int32_t *planes, uint32_t npix, uint32_t nimg);
+// mixed sub-batch: image i's pixels from table[3 i].image, its i32 planes to table[3 i + c].samples
+void launch_rgb16_to_planes_mixed(hipStream_t s, const PlaneGeom *table, uint32_t max_npix, uint32_t nimg);
 
 struct WideSizes {
     uint32_t px_tiles, max_sort_tiles;

@@ -797,18 +797,26 @@ __device__ __forceinline__ void walk_group(const TileLDS<T> &t, const uint8_t *k
 // Plane 0 of an image also carries the 112 header bits.
 // ------------------------------------------------------------------------------------------
 
-template <typename T>
-__global__ __launch_bounds__(PACK_THREADS) void k_lengths(const T *__restrict__ planes, const uint8_t *__restrict__ k_map,
-                                                          group_bits_t<T> *__restrict__ group_bits,
-                                                          uint32_t *__restrict__ tile_bits, uint32_t W, uint32_t npix,
-                                                          uint32_t ntiles, uint32_t planes_per_image,
-                                                          uint32_t tile_begin) {
+// (MIXED: a sub-batch of 16-bit images of different shapes, Geometry::mixed -- pl / W / npix are the plane's own, from its PlaneGeom
+// row; kpl is its k_map plane, ntiles * PACK_TILE bytes from the next; group_bits / tile_bits stay indexed with the uniform ntiles
+// = T_max.  A tile at or past the plane's end has no pixels: zero bits for every thread and for the tile, which k_bitscan_slice
+// reads like any other.  stage_span bounds every load by npix, so a plane read in place is never read outside its frame.)
+template <typename T, bool MIXED>
+__device__ __forceinline__ void lengths_tile(const T *__restrict__ pl, const uint8_t *__restrict__ kpl,
+                                             group_bits_t<T> *__restrict__ group_bits, uint32_t *__restrict__ tile_bits, uint32_t W,
+                                             uint32_t npix, uint32_t ntiles, uint32_t planes_per_image, uint32_t tile_begin) {
     __shared__ TileLDS<T> tl;
     __shared__ uint32_t wsum[PACK_THREADS / 64];
     const uint32_t tile = tile_begin + blockIdx.x, plane = blockIdx.y;
-    const T *pl = planes + (uint64_t)plane * npix;
     const uint32_t tile_first = tile * PACK_TILE;
-    stage_tile(tl, pl, k_map + (uint64_t)plane * npix, tile_first, W, npix);
+    if constexpr (MIXED) {
+        if (tile_first >= npix) {
+            group_bits[((uint64_t)plane * ntiles + tile) * PACK_THREADS + threadIdx.x] = 0;
+            if (threadIdx.x == 0) tile_bits[(uint64_t)plane * ntiles + tile] = 0;
+            return;
+        }
+    }
+    stage_tile(tl, pl, kpl, tile_first, W, npix);
     __syncthreads();
     const uint32_t first = tile_first + threadIdx.x * PACK_PER_THREAD;
     const uint32_t end = min(tile_first + PACK_TILE, npix);
@@ -826,6 +834,26 @@ __global__ __launch_bounds__(PACK_THREADS) void k_lengths(const T *__restrict__ 
         for (uint32_t w = 0; w < PACK_THREADS / 64; w++) tot += wsum[w];
         tile_bits[(uint64_t)plane * ntiles + tile] = tot;
     }
+}
+template <typename T>
+__global__ __launch_bounds__(PACK_THREADS) void k_lengths(const T *__restrict__ planes, const uint8_t *__restrict__ k_map,
+                                                          group_bits_t<T> *__restrict__ group_bits,
+                                                          uint32_t *__restrict__ tile_bits, uint32_t W, uint32_t npix,
+                                                          uint32_t ntiles, uint32_t planes_per_image,
+                                                          uint32_t tile_begin) {
+    const uint32_t plane = blockIdx.y;
+    lengths_tile<T, false>(planes + (uint64_t)plane * npix, k_map + (uint64_t)plane * npix, group_bits, tile_bits, W, npix, ntiles,
+                           planes_per_image, tile_begin);
+}
+template <typename T>
+__global__ __launch_bounds__(PACK_THREADS) void k_lengths_mixed(const PlaneGeom *__restrict__ table, const uint8_t *__restrict__ k_map,
+                                                                group_bits_t<T> *__restrict__ group_bits,
+                                                                uint32_t *__restrict__ tile_bits, uint32_t ntiles,
+                                                                uint32_t planes_per_image, uint32_t tile_begin) {
+    const uint32_t plane = blockIdx.y;
+    const PlaneView<T> pv = plane_view<T>((const T *)nullptr, plane, table);
+    lengths_tile<T, true>(pv.pl, k_map + (uint64_t)plane * ntiles * PACK_TILE, group_bits, tile_bits, pv.W, pv.npix, ntiles,
+                          planes_per_image, tile_begin);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -893,21 +921,50 @@ __device__ __forceinline__ uint32_t *stream_words(uint8_t *out, const Placement 
     return reinterpret_cast<uint32_t *>(out + pl.image_off[img]);
 }
 
+// A mixed sub-batch (16-bit images of different shapes): image i's stream at out + out_off of its first plane's PlaneGeom row, words
+// at or past out_slot / 4 dropped.  A placement type of its own: Placement, which the uniform kernels take by value, stays as it is.
+struct MixedPlacement {
+    const PlaneGeom *table;
+};
+__device__ __forceinline__ uint32_t *stream_words(uint8_t *out, const MixedPlacement &pl, uint32_t first_plane, uint64_t &limit_words) {
+    const PlaneGeom *pg = pl.table + first_plane;
+    limit_words = pg->out_slot >> 2;
+    return reinterpret_cast<uint32_t *>(out + pg->out_off);
+}
+// the row of `place` that names image img's stream: the image itself, or the first of its planes
+__device__ __forceinline__ uint32_t stream_row(const Placement &, uint32_t img, uint32_t) { return img; }
+__device__ __forceinline__ uint32_t stream_row(const MixedPlacement &, uint32_t img, uint32_t planes_per_image) { return img * planes_per_image; }
+
 // pack ORs a tile's last word (and its first word when the previous tile ends inside it) into the
 // output: zero the last word of every tile of the range.  A tile that lies inside one word shared
 // with its predecessor leaves that word alone (the predecessor zeroed it, and may already have packed).
-__global__ void k_zero_edges(uint8_t *__restrict__ out, Placement place, const uint64_t *__restrict__ tile_bitoff,
-                             const uint32_t *__restrict__ tile_bits, const uint64_t *__restrict__ plane_base,
-                             uint32_t ntiles, uint32_t t0, uint32_t t1, uint32_t planes_per_image) {
+// (MixedPlacement: a padding tile -- one past its plane's end -- has no bits and therefore no last word; it zeroes nothing.)
+template <typename PL>
+__device__ __forceinline__ void zero_edge(uint8_t *__restrict__ out, const PL &place, const uint64_t *__restrict__ tile_bitoff,
+                                          const uint32_t *__restrict__ tile_bits, const uint64_t *__restrict__ plane_base,
+                                          uint32_t ntiles, uint32_t t0, uint32_t t1, uint32_t planes_per_image) {
     const uint32_t tile = t0 + blockIdx.x * blockDim.x + threadIdx.x, plane = blockIdx.y;
     if (tile >= t1) return;
     const uint64_t lo = plane_base[plane] + tile_bitoff[(uint64_t)plane * ntiles + tile];
     const uint64_t hi = lo + tile_bits[(uint64_t)plane * ntiles + tile];
+    if constexpr (std::is_same<PL, MixedPlacement>::value) {
+        if (hi == lo) return;
+    }
     const uint64_t first_word = lo >> 5, last_word = (hi - 1) >> 5;
     if (first_word == last_word && (lo & 31u) != 0) return;
     uint64_t limit;
-    uint32_t *words = stream_words(out, place, plane / planes_per_image, limit);
+    uint32_t *words = stream_words(out, place, stream_row(place, plane / planes_per_image, planes_per_image), limit);
     if (last_word < limit) words[last_word] = 0;
+}
+__global__ void k_zero_edges(uint8_t *__restrict__ out, Placement place, const uint64_t *__restrict__ tile_bitoff,
+                             const uint32_t *__restrict__ tile_bits, const uint64_t *__restrict__ plane_base,
+                             uint32_t ntiles, uint32_t t0, uint32_t t1, uint32_t planes_per_image) {
+    zero_edge(out, place, tile_bitoff, tile_bits, plane_base, ntiles, t0, t1, planes_per_image);
+}
+__global__ void k_zero_edges_mixed(uint8_t *__restrict__ out, MixedPlacement place, const uint64_t *__restrict__ tile_bitoff,
+                                   const uint32_t *__restrict__ tile_bits, const uint64_t *__restrict__ plane_base,
+                                   uint32_t ntiles, uint32_t t0, uint32_t t1, uint32_t planes_per_image) {
+    zero_edge(out, place, tile_bitoff, tile_bits, plane_base, ntiles, t0, t1, planes_per_image);
 }
 
 // Stream placement: offsets[i] = sum of 16-byte-rounded sizes before i; one thread (n is small).
@@ -941,28 +998,39 @@ __global__ void k_zero_streams(uint32_t *__restrict__ out, const uint64_t *__res
 // atomically into the zeroed output, everything between is a plain store.
 // ------------------------------------------------------------------------------------------
 
-template <typename T>
-__global__ __launch_bounds__(PACK_THREADS) void k_pack(const T *__restrict__ planes, const uint8_t *__restrict__ k_map,
-                                                       const group_bits_t<T> *__restrict__ group_bits,
-                                                       const uint64_t *__restrict__ tile_bitoff,
-                                                       const uint32_t *__restrict__ tile_bits,
-                                                       const uint64_t *__restrict__ plane_base, Placement place,
-                                                       uint8_t *__restrict__ out, uint32_t W, uint32_t H,
-                                                       uint32_t npix, uint32_t ntiles, uint32_t planes_per_image,
-                                                       uint32_t color, uint32_t depth, uint32_t tile_begin) {
+// (PL = MixedPlacement: pl / W / H / npix are the plane's own, from its PlaneGeom row -- the arguments of those names are unused --
+// and k_map's planes are ntiles * PACK_TILE bytes apart; a padding tile has tile_bits = 0 -- no last word, nothing to pack -- and
+// returns before anything is staged.  The header carries the image's own W and H.
+// No __restrict__ on this body's pointers: the kernels' own arguments carry it, and said again here it cost k_pack<i32> an SGPR.)
+template <typename T, typename PL>
+__device__ __forceinline__ void pack_tile(const T *planes, const uint8_t *k_map,
+                                          const group_bits_t<T> *group_bits, const uint64_t *tile_bitoff,
+                                          const uint32_t *tile_bits, const uint64_t *plane_base, const PL place,
+                                          uint8_t *out, uint32_t W, uint32_t H, uint32_t npix, uint32_t ntiles,
+                                          uint32_t planes_per_image, uint32_t color, uint32_t depth, uint32_t tile_begin) {
     __shared__ TileLDS<T> tl;
     __shared__ uint32_t win[PACK_WIN_WORDS];
     __shared__ uint32_t wsum[PACK_THREADS / 64];
     const uint32_t tile = tile_begin + blockIdx.x, plane = blockIdx.y;
     const uint32_t img = plane / planes_per_image;
     const bool first_plane = (plane % planes_per_image) == 0;
+    constexpr bool MIXED = std::is_same<PL, MixedPlacement>::value;
     const T *pl = planes + (uint64_t)plane * npix;
+    uint64_t kstride = npix;  // bytes between two planes of k_map
+    if constexpr (MIXED) {
+        const PlaneView<T> pv = plane_view<T>(planes, plane, place.table);
+        pl = pv.pl, W = pv.W, H = pv.H, npix = pv.npix;
+        kstride = (uint64_t)ntiles * PACK_TILE;
+    }
     const uint32_t tile_first = tile * PACK_TILE;
+    if constexpr (MIXED) {
+        if (tile_first >= npix) return;
+    }
     const uint32_t first = tile_first + threadIdx.x * PACK_PER_THREAD;
     const uint32_t end = min(tile_first + PACK_TILE, npix);
     const bool has_header = tile == 0 && threadIdx.x == 0 && first_plane;
 
-    stage_tile(tl, pl, k_map + (uint64_t)plane * npix, tile_first, W, npix);
+    stage_tile(tl, pl, k_map + (uint64_t)plane * kstride, tile_first, W, npix);
     // this thread's bit offset inside the tile: scan of the group sizes k_lengths left behind
     const uint32_t bits = group_bits[((uint64_t)plane * ntiles + tile) * PACK_THREADS + threadIdx.x];
     const uint32_t inc = wave_incl_scan(bits);
@@ -975,7 +1043,7 @@ __global__ __launch_bounds__(PACK_THREADS) void k_pack(const T *__restrict__ pla
     const uint64_t my_lo = tile_lo + woff + inc - bits;
 
     uint64_t limit_words;  // a stream that outgrows its slot is cut here (the host then re-packs with exact placement)
-    uint32_t *out_words = stream_words(out, place, img, limit_words);
+    uint32_t *out_words = stream_words(out, place, stream_row(place, img, planes_per_image), limit_words);
     const uint64_t first_word = tile_lo >> 5, last_word = (tile_hi - 1) >> 5;
     const bool first_shared = (tile_lo & 31u) != 0;  // the previous tile ends inside our first word
 
@@ -1016,6 +1084,29 @@ __global__ __launch_bounds__(PACK_THREADS) void k_pack(const T *__restrict__ pla
         }
         __syncthreads();
     }
+}
+template <typename T>
+__global__ __launch_bounds__(PACK_THREADS) void k_pack(const T *__restrict__ planes, const uint8_t *__restrict__ k_map,
+                                                       const group_bits_t<T> *__restrict__ group_bits,
+                                                       const uint64_t *__restrict__ tile_bitoff,
+                                                       const uint32_t *__restrict__ tile_bits,
+                                                       const uint64_t *__restrict__ plane_base, Placement place,
+                                                       uint8_t *__restrict__ out, uint32_t W, uint32_t H,
+                                                       uint32_t npix, uint32_t ntiles, uint32_t planes_per_image,
+                                                       uint32_t color, uint32_t depth, uint32_t tile_begin) {
+    pack_tile<T>(planes, k_map, group_bits, tile_bitoff, tile_bits, plane_base, place, out, W, H, npix, ntiles, planes_per_image, color, depth,
+                 tile_begin);
+}
+template <typename T>
+__global__ __launch_bounds__(PACK_THREADS) void k_pack_mixed(const PlaneGeom *__restrict__ table, const uint8_t *__restrict__ k_map,
+                                                             const group_bits_t<T> *__restrict__ group_bits,
+                                                             const uint64_t *__restrict__ tile_bitoff,
+                                                             const uint32_t *__restrict__ tile_bits,
+                                                             const uint64_t *__restrict__ plane_base, uint8_t *__restrict__ out,
+                                                             uint32_t ntiles, uint32_t planes_per_image, uint32_t color, uint32_t depth,
+                                                             uint32_t tile_begin) {
+    pack_tile<T>((const T *)nullptr, k_map, group_bits, tile_bitoff, tile_bits, plane_base, MixedPlacement{table}, out, 0u, 0u, 0u, ntiles,
+                 planes_per_image, color, depth, tile_begin);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -1934,6 +2025,13 @@ template <typename T>
 void launch_lengths(hipStream_t s, const T *planes, const uint8_t *k_map, group_bits_t<T> *group_bits,
                     uint32_t *tile_bits, const Geometry &g, uint32_t t0, uint32_t t1) {
     if (t1 <= t0) return;
+    if constexpr (sizeof(group_bits_t<T>) == 4) {  // (a mixed sub-batch takes these kernels with 16-bit samples only)
+        if (g.mixed) {
+            FELICS_LAUNCH((k_lengths_mixed<T>), dim3(t1 - t0, g.nplanes), dim3(PACK_THREADS), s, g.mixed, k_map, group_bits, tile_bits,
+                          g.pack_tiles, g.planes_per_image, t0);
+            return;
+        }
+    }
     FELICS_LAUNCH((k_lengths<T>), dim3(t1 - t0, g.nplanes), dim3(PACK_THREADS), s, planes, k_map, group_bits,
                        tile_bits, g.W, g.npix, g.pack_tiles, g.planes_per_image, t0);
 }
@@ -1971,6 +2069,11 @@ void launch_zero_edges(hipStream_t s, uint8_t *out, const uint64_t *image_off, u
                        const uint64_t *tile_bitoff, const uint32_t *tile_bits, const uint64_t *plane_base,
                        const Geometry &g, uint32_t t0, uint32_t t1) {
     if (t1 <= t0) return;
+    if (g.mixed) {  // (placement from the table: image_off / slot_stride unused)
+        FELICS_LAUNCH(k_zero_edges_mixed, dim3(cdiv(t1 - t0, 256), g.nplanes), dim3(256), s, out, MixedPlacement{g.mixed}, tile_bitoff, tile_bits,
+                      plane_base, g.pack_tiles, t0, t1, g.planes_per_image);
+        return;
+    }
     Placement pl{image_off, slot_stride};
     FELICS_LAUNCH(k_zero_edges, dim3(cdiv(t1 - t0, 256), g.nplanes), dim3(256), s, out, pl, tile_bitoff, tile_bits,
                        plane_base, g.pack_tiles, t0, t1, g.planes_per_image);
@@ -1982,6 +2085,13 @@ void launch_pack(hipStream_t s, const T *planes, const uint8_t *k_map, const gro
                  const uint64_t *image_off, uint64_t slot_stride, uint8_t *out, const Geometry &g, uint32_t t0,
                  uint32_t t1) {
     if (t1 <= t0) return;
+    if constexpr (sizeof(group_bits_t<T>) == 4) {
+        if (g.mixed) {
+            FELICS_LAUNCH((k_pack_mixed<T>), dim3(t1 - t0, g.nplanes), dim3(PACK_THREADS), s, g.mixed, k_map, group_bits, tile_bitoff, tile_bits,
+                          plane_base, out, g.pack_tiles, g.planes_per_image, g.color, g.depth, t0);
+            return;
+        }
+    }
     Placement pl{image_off, slot_stride};
     FELICS_LAUNCH((k_pack<T>), dim3(t1 - t0, g.nplanes), dim3(PACK_THREADS), s, planes, k_map, group_bits,
                        tile_bitoff, tile_bits, plane_base, pl, out, g.W, g.H, g.npix, g.pack_tiles, g.planes_per_image,

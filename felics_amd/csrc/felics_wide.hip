@@ -17,6 +17,13 @@ namespace felics {
 
 // interleaved RGB16 -> three i32 planes Y, Co, Cg (color_transform.rs:11-17; compression.rs:346-356
 // widens to i32 first, so Co / Cg of 16-bit samples need 18 bits).
+__device__ __forceinline__ void rgb16_pixel(const uint16_t *__restrict__ s, int &yv, int &co, int &cg) {
+    const int r = s[0], gr = s[1], b = s[2];
+    co = r - b;
+    const int t = b + co / 2;
+    cg = gr - t;
+    yv = t + cg / 2;
+}
 __global__ void k_rgb16_to_planes(const uint16_t *__restrict__ rgb, int32_t *__restrict__ planes, uint32_t npix,
                                   uint32_t nimg) {
     const uint64_t total = (uint64_t)npix * nimg;
@@ -24,16 +31,26 @@ __global__ void k_rgb16_to_planes(const uint16_t *__restrict__ rgb, int32_t *__r
          g += (uint64_t)gridDim.x * blockDim.x) {
         const uint32_t img = (uint32_t)(g / npix);
         const uint32_t i = (uint32_t)(g - (uint64_t)img * npix);
-        const uint16_t *s = rgb + g * 3;
-        const int r = s[0], gr = s[1], b = s[2];
-        const int co = r - b;
-        const int t = b + co / 2;
-        const int cg = gr - t;
-        const int yv = t + cg / 2;
+        int yv, co, cg;
+        rgb16_pixel(rgb + g * 3, yv, co, cg);
         int32_t *o = planes + (uint64_t)img * 3 * npix;
         o[i] = yv;
         o[(uint64_t)npix + i] = co;
         o[2ull * npix + i] = cg;
+    }
+}
+// A mixed sub-batch: image blockIdx.y from its own pointer and size (PlaneGeom rows 3 i .. 3 i + 2), every plane where its row says.
+__global__ __launch_bounds__(256) void k_rgb16_to_planes_mixed(const PlaneGeom *__restrict__ table) {
+    const PlaneGeom *pg = table + 3ull * blockIdx.y;
+    const uint32_t npix = pg->npix;
+    const uint16_t *rgb = (const uint16_t *)pg->image;
+    int32_t *py = (int32_t *)pg[0].samples, *pco = (int32_t *)pg[1].samples, *pcg = (int32_t *)pg[2].samples;
+    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < npix; i += gridDim.x * blockDim.x) {
+        int yv, co, cg;
+        rgb16_pixel(rgb + (uint64_t)i * 3, yv, co, cg);
+        py[i] = yv;
+        pco[i] = co;
+        pcg[i] = cg;
     }
 }
 
@@ -108,16 +125,41 @@ __device__ __forceinline__ void for_my_events(const T *__restrict__ pl, uint32_t
     }
 }
 
+// Where plane blockIdx.y of a sub-batch lies and how large it is.  Uniform: every plane W x (npix / W), back to back from `planes`.
+// Mixed (Geometry::mixed, 16-bit images of different shapes in one sub-batch): the plane's PlaneGeom row -- the plane is
+// workgroup-uniform, so these are scalar loads.  The grid is (T_max, planes): a tile at or past the plane's own end finds
+// first >= npix in for_my_events, counts nothing and emits nothing.  Every load for_my_events issues is bounded by the plane's own
+// npix, so a plane read in place (a gray16 frame of the caller, 2-byte aligned like a uniform batch's planes of odd w h) is never
+// read outside the frame.
 template <typename T>
-__global__ __launch_bounds__(WTHREADS) void k_wide_count(const T *__restrict__ planes, uint32_t W, uint32_t npix,
-                                                         uint32_t *__restrict__ tile_cnt) {
+struct WidePlane {
+    const T *pl;
+    uint32_t W, npix;
+};
+template <typename T>
+__device__ __forceinline__ WidePlane<T> wide_plane(const PlaneGeom *__restrict__ table) {
+    const PlaneGeom *pg = table + blockIdx.y;
+    return WidePlane<T>{(const T *)pg->samples, pg->W, pg->npix};
+}
+
+template <typename T>
+__device__ __forceinline__ void wide_count_tile(const T *__restrict__ pl, uint32_t W, uint32_t npix, uint32_t *__restrict__ tile_cnt) {
     __shared__ uint32_t wsum[WTHREADS / 64];
-    const T *pl = planes + (uint64_t)blockIdx.y * npix;
     uint32_t n = 0;
     for_my_events(pl, W, npix, [&](uint32_t, uint32_t, const PixelClass &) { n++; });
     uint32_t total;
     (void)block_excl_scan(n, wsum, &total);
     if (threadIdx.x == 0) tile_cnt[blockIdx.y * gridDim.x + blockIdx.x] = total;
+}
+template <typename T>
+__global__ __launch_bounds__(WTHREADS) void k_wide_count(const T *__restrict__ planes, uint32_t W, uint32_t npix,
+                                                         uint32_t *__restrict__ tile_cnt) {
+    wide_count_tile(planes + (uint64_t)blockIdx.y * npix, W, npix, tile_cnt);
+}
+template <typename T>
+__global__ __launch_bounds__(WTHREADS) void k_wide_count_mixed(const PlaneGeom *__restrict__ table, uint32_t *__restrict__ tile_cnt) {
+    const WidePlane<T> p = wide_plane<T>(table);
+    wide_count_tile(p.pl, p.W, p.npix, tile_cnt);
 }
 
 // One workgroup: exclusive scan of the tile counts (plane-major) in place; per plane its first record, its
@@ -164,10 +206,9 @@ __global__ __launch_bounds__(1024) void k_wide_plan(uint32_t *__restrict__ tile_
 }
 
 template <typename T>
-__global__ __launch_bounds__(WTHREADS) void k_wide_emit(const T *__restrict__ planes, uint32_t W, uint32_t npix,
-                                                        const uint32_t *__restrict__ tile_base, uint64_t *__restrict__ recs) {
+__device__ __forceinline__ void wide_emit_tile(const T *__restrict__ pl, uint32_t W, uint32_t npix, const uint32_t *__restrict__ tile_base,
+                                               uint64_t *__restrict__ recs) {
     __shared__ uint32_t wsum[WTHREADS / 64];
-    const T *pl = planes + (uint64_t)blockIdx.y * npix;
     // classify once: the thread's records wait in registers for their place (raster order: thread by thread)
     uint64_t mine[16];
     uint32_t n = 0;
@@ -191,6 +232,18 @@ __global__ __launch_bounds__(WTHREADS) void k_wide_emit(const T *__restrict__ pl
     __syncthreads();
     uint64_t *out = recs + tile_base[blockIdx.y * gridDim.x + blockIdx.x];
     for (uint32_t i = threadIdx.x; i < total; i += WTHREADS) out[i] = lined[i];
+}
+template <typename T>
+__global__ __launch_bounds__(WTHREADS) void k_wide_emit(const T *__restrict__ planes, uint32_t W, uint32_t npix,
+                                                        const uint32_t *__restrict__ tile_base, uint64_t *__restrict__ recs) {
+    wide_emit_tile(planes + (uint64_t)blockIdx.y * npix, W, npix, tile_base, recs);
+}
+// (the record's sample index is the index in the image's own plane, y W + x, as in the uniform kernel)
+template <typename T>
+__global__ __launch_bounds__(WTHREADS) void k_wide_emit_mixed(const PlaneGeom *__restrict__ table, const uint32_t *__restrict__ tile_base,
+                                                              uint64_t *__restrict__ recs) {
+    const WidePlane<T> p = wide_plane<T>(table);
+    wide_emit_tile(p.pl, p.W, p.npix, tile_base, recs);
 }
 
 // Which plane a sort tile belongs to, and its record range.
@@ -807,6 +860,10 @@ void launch_rgb16_to_planes(hipStream_t s, const uint16_t *rgb, int32_t *planes,
     const uint32_t blocks = (uint32_t)std::min<uint64_t>(cdiv(total, 256), 256u * 32u);
     FELICS_LAUNCH(k_rgb16_to_planes, dim3(blocks), dim3(256), s, rgb, planes, npix, nimg);
 }
+void launch_rgb16_to_planes_mixed(hipStream_t s, const PlaneGeom *table, uint32_t max_npix, uint32_t nimg) {
+    const uint32_t bx = std::max(1u, std::min(cdiv(max_npix, 256), 256u));
+    FELICS_LAUNCH(k_rgb16_to_planes_mixed, dim3(bx, nimg), dim3(256), s, table);
+}
 
 WideSizes wide_sizes(const Geometry &g) {
     WideSizes z;
@@ -825,6 +882,12 @@ WideSizes wide_sizes(const Geometry &g) {
 template <typename T>
 void launch_wide_events(hipStream_t s, const T *planes, uint32_t *tile_cnt, uint32_t *meta, uint64_t *recs, const Geometry &g) {
     const WideSizes z = wide_sizes(g);
+    if (g.mixed) {  // (px_tiles = T_max; everything behind k_wide_emit sees the padded npix as the stride of k_map only)
+        FELICS_LAUNCH((k_wide_count_mixed<T>), dim3(z.px_tiles, g.nplanes), dim3(WTHREADS), s, g.mixed, tile_cnt);
+        FELICS_LAUNCH(k_wide_plan, dim3(1), dim3(1024), s, tile_cnt, z.px_tiles, g.nplanes, meta);
+        FELICS_LAUNCH((k_wide_emit_mixed<T>), dim3(z.px_tiles, g.nplanes), dim3(WTHREADS), s, g.mixed, tile_cnt, recs);
+        return;
+    }
     FELICS_LAUNCH((k_wide_count<T>), dim3(z.px_tiles, g.nplanes), dim3(WTHREADS), s, planes, g.W, g.npix, tile_cnt);
     FELICS_LAUNCH(k_wide_plan, dim3(1), dim3(1024), s, tile_cnt, z.px_tiles, g.nplanes, meta);
     FELICS_LAUNCH((k_wide_emit<T>), dim3(z.px_tiles, g.nplanes), dim3(WTHREADS), s, planes, g.W, g.npix, tile_cnt, recs);

@@ -126,9 +126,9 @@ typedef struct felics_image {
 
 /* n images of ANY shapes and types in one call: what felics_compress_batch is for one shape.  Every stream is byte-identical to
  * what felics_compress writes for that image alone.  Every image is checked before anything is launched (the first error in
- * image order is returned; NULL pixels only for a zero-sized image).  8-bit images of similar size share a submission (their
- * tile counts padded to the largest of the group, at most 25 %); 16-bit images go through the same-shape path, one group per
- * shape.  outs[i], caps[i], lens[i] per image; on FELICS_E_BUFFER_TOO_SMALL every lens[i] holds the size stream i needs and
+ * image order is returned; NULL pixels only for a zero-sized image).  Images of one depth and colour and of similar size share a
+ * submission (their tile counts padded to the largest of the group, at most 25 %), 8-bit and 16-bit alike; 16-bit images of one
+ * shape keep the same-shape path.  outs[i], caps[i], lens[i] per image; on FELICS_E_BUFFER_TOO_SMALL every lens[i] holds the size stream i needs and
  * nothing is written to a buffer that is too small.  The reference has no counterpart (it is one call per image). */
 int felics_compress_images(felics_ctx *ctx, size_t n, const felics_image *images, uint8_t *const *outs, const size_t *caps,
                            size_t *lens);
