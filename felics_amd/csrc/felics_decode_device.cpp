@@ -1,0 +1,710 @@
+// felics_decode_device.cpp -- host side of the GPU decoder: streams of one shape (felics_decompress_batch_device), of any shapes
+// (felics_decompress_images_device), and their headers (felics_read_headers_device).
+#include "felics_host.h"
+
+namespace felics {
+
+namespace {
+
+// ---- GPU decoder helpers shared by felics_decompress_batch_device and felics_decompress_images_device -----------------------
+
+// Every stream gets a status on every path out of a decode call (felics.h): a call that ends before the streams are decoded reports
+// its own error for all of them, and counts them as undecoded.
+int fail_decode(felics_ctx *ctx, size_t n, int *status, int code) {
+    for (size_t i = 0; i < n; i++) status[i] = code;
+    ctx->dstats.undecoded += n;
+    return code;
+}
+
+// The same before a call has counted its streams, for the entry points that also hand out headers and frame offsets.
+int fail_call(size_t n, int *status, felics_header *hdrs, uint64_t *pix_offsets, int code) {
+    for (size_t i = 0; i < n; i++) {
+        status[i] = code;
+        if (hdrs) hdrs[i] = felics_header{};
+        if (pix_offsets) pix_offsets[i] = 0;
+    }
+    return code;
+}
+
+// 16-bit streams: estimator tables for passes of `per` <= n streams (at most DEC16_PASS, a stream's table is 8.4 MB of HBM, and at
+// most a quarter of the free HBM; an allocation that fails all the same halves the pass)
+int dec16_tables(felics_ctx *ctx, size_t n, size_t &per) {
+    constexpr size_t DEC16_PASS = 1024;
+    per = std::min(n, DEC16_PASS);
+    size_t free_b = 0, total_b = 0;
+    if (hipMemGetInfo(&free_b, &total_b) == hipSuccess && ctx->dec_table.cap < decode16_table_bytes((uint32_t)per))
+        per = std::max<size_t>(1, std::min(per, (free_b / 4 + ctx->dec_table.cap) / decode16_table_bytes(1)));
+    for (;;) {
+        const size_t table_bytes = decode16_table_bytes((uint32_t)per);
+        if (table_bytes > ctx->dec_table.cap) ctx->dec_epoch = 0;  // a fresh (zeroed) buffer: epochs start over
+        const int rc = reserve_zeroed(ctx, ctx->dec_table, table_bytes);
+        if (rc == 0) return FELICS_OK;
+        (void)hipGetLastError();
+        if (per == 1) return rc;
+        per = (per + 1) / 2;
+    }
+}
+
+// the first of the three epochs (one per plane) of the next pass on stream s
+int dec16_epoch(felics_ctx *ctx, hipStream_t s, uint32_t &epoch0) {
+    if (ctx->dec_epoch > 0xFFFFFFF0u) {  // epochs used up: clear the tables, start over
+        HIP_TRY(ctx, hipMemsetAsync(ctx->dec_table.p, 0, ctx->dec_table.cap, s));
+        ctx->dec_epoch = 0;
+    }
+    epoch0 = ctx->dec_epoch + 1;
+    ctx->dec_epoch += 3;
+    return FELICS_OK;
+}
+
+// FELICS_TEST_DECODE16_LANES, read per call: 1 = 16-bit streams take the lane form wherever the shape allows it (W >= 8; in a mixed
+// call: whole waves of 64 streams of one shape), 0 = never, unset (-1) = from the measured thresholds on
+int dec16_lanes_forced() {
+    const char *e = getenv("FELICS_TEST_DECODE16_LANES");
+    return e ? (atoi(e) != 0 ? 1 : 0) : -1;
+}
+
+// FELICS_TEST_DECODE16_LANES_PASS=k: at most k streams (rounded down to whole waves, at least one) in a pass of the 16-bit lane form (tests)
+size_t dec16_lanes_pass_cap() {
+    const char *e = getenv("FELICS_TEST_DECODE16_LANES_PASS");
+    if (!e || atoll(e) <= 0) return SIZE_MAX / 2;
+    return std::max<size_t>(64, (size_t)atoll(e) / 64 * 64);
+}
+
+// 16-bit lane form: the table buffer for passes of `bytes` <= want bytes (what the whole call would like), at least `least` (one
+// wave's tables).  Bounded as dec16_tables bounds the wave form's: at most a quarter of the free HBM, and an allocation that fails
+// all the same halves the pass.  "Free" counts the buffer the context already holds, so the bound is the same call after call: with
+// free / 4 + cap a buffer of tens of GB grew a little with every call, and every growth is a free, an allocation and a memset
+// (seconds: profiles/decode16_lanes.txt, first run).
+int dec16_lanes_tables(felics_ctx *ctx, size_t want, size_t least, size_t &bytes) {
+    bytes = want;
+    size_t free_b = 0, total_b = 0;
+    if (hipMemGetInfo(&free_b, &total_b) == hipSuccess && ctx->dec_lane16_table.cap < bytes)
+        bytes = std::max(least, std::min(bytes, std::max(ctx->dec_lane16_table.cap, (free_b + ctx->dec_lane16_table.cap) / 4)));
+    for (;;) {
+        if (bytes > ctx->dec_lane16_table.cap) ctx->dec_lane16_epoch = 0;  // a fresh (zeroed) buffer: epochs start over
+        const int rc = reserve_zeroed(ctx, ctx->dec_lane16_table, bytes);
+        if (rc == 0) return FELICS_OK;
+        (void)hipGetLastError();
+        if (bytes <= least) return rc;
+        bytes = std::max(least, bytes / 2);
+    }
+}
+
+// the first of the three epochs (one per plane) of the next lane-form launch on stream s
+int dec16_lanes_epoch(felics_ctx *ctx, hipStream_t s, uint32_t &epoch0) {
+    if (ctx->dec_lane16_epoch + 3 > DEC16L_EPOCH_MAX) {  // epochs used up: clear the tables, start over
+        HIP_TRY(ctx, hipMemsetAsync(ctx->dec_lane16_table.p, 0, ctx->dec_lane16_table.cap, s));
+        ctx->dec_lane16_epoch = 0;
+    }
+    epoch0 = ctx->dec_lane16_epoch + 1;
+    ctx->dec_lane16_epoch += 3;
+    return FELICS_OK;
+}
+
+constexpr int HOST_DECODE_NO_MEMORY = 1;  // (not a status: the host could not hold the stream)
+
+// One stream through the host decoder (rows too wide for the LDS): copied to the host, decoded, the frame copied to d_dst.  A stream
+// longer than max_len is FELICS_E_INVALID_VALUE before anything is sized by it; a header other than `want`,
+// FELICS_E_INVALID_DIMENSIONS.  Returns the stream's status, FELICS_E_HIP (HIP error, ctx->err set) or HOST_DECODE_NO_MEMORY.
+int host_decode(felics_ctx *ctx, const uint8_t *d_src, uint64_t len, uint64_t max_len, const felics_header &want, uint8_t *d_dst,
+                std::vector<uint8_t> &sbuf, std::vector<uint8_t> &pbuf) {
+    if (len > max_len) return FELICS_E_INVALID_VALUE;
+    const uint64_t frame_bytes = (uint64_t)want.width * want.height * (want.color_type ? 3 : 1) * (want.pixel_depth ? 2 : 1);
+    try {
+        sbuf.resize((size_t)len);
+        pbuf.resize((size_t)frame_bytes);
+    } catch (const std::bad_alloc &) {
+        return HOST_DECODE_NO_MEMORY;
+    }
+    if (len && hipMemcpy(sbuf.data(), d_src, (size_t)len, hipMemcpyDeviceToHost) != hipSuccess)
+        return hip_fail(ctx, hipGetLastError(), "copying a stream to the host decoder");
+    felics_header hi;
+    int r = felics_read_header(sbuf.data(), sbuf.size(), &hi);
+    if (!r && (hi.width != want.width || hi.height != want.height || hi.color_type != want.color_type || hi.pixel_depth != want.pixel_depth))
+        r = FELICS_E_INVALID_DIMENSIONS;
+    if (!r) r = felics_decompress(sbuf.data(), sbuf.size(), pbuf.data(), pbuf.size(), nullptr);
+    if (!r && frame_bytes && hipMemcpy(d_dst, pbuf.data(), (size_t)frame_bytes, hipMemcpyHostToDevice) != hipSuccess)
+        return hip_fail(ctx, hipGetLastError(), "copying decoded pixels to the device");
+    return r;
+}
+
+// k_read_headers over n streams: offsets | lens | records in ctx->dec_meta (`extra` more bytes reserved behind them), the records
+// copied back to `rec`; d_off / d_len stay on the device
+int read_headers(felics_ctx *ctx, size_t n, const void *d_streams, const uint64_t *offsets, const uint64_t *lens, std::vector<DecodeHeader> &rec,
+                 hipStream_t s) {
+    int rc = reserve(ctx, ctx->dec_meta, n * 16 + n * sizeof(DecodeHeader));
+    if (rc) return rc;
+    try {
+        rec.resize(n);
+    } catch (const std::bad_alloc &) {
+        return FELICS_E_IO;
+    }
+    uint64_t *d_off = (uint64_t *)ctx->dec_meta.p, *d_len = d_off + n;
+    DecodeHeader *d_rec = (DecodeHeader *)(d_len + n);
+    HIP_TRY(ctx, hipMemcpyAsync(d_off, offsets, n * 8, hipMemcpyHostToDevice, s));
+    HIP_TRY(ctx, hipMemcpyAsync(d_len, lens, n * 8, hipMemcpyHostToDevice, s));
+    HIP_TRY(ctx, launch_read_headers(s, (const uint8_t *)d_streams, d_off, d_len, (uint32_t)n, d_rec));
+    HIP_TRY(ctx, hipMemcpyAsync(rec.data(), d_rec, n * sizeof(DecodeHeader), hipMemcpyDeviceToHost, s));
+    HIP_TRY(ctx, hipStreamSynchronize(s));
+    return FELICS_OK;
+}
+
+// Streams `idx` grouped by (colour, W, H), stream order kept within a group: of every group the first take(header, count) streams
+// become a lane group of their colour, the others are appended to `rest`.
+template <typename Take>
+void same_shape_groups(const std::vector<DecodeHeader> &rec, std::vector<size_t> idx, std::vector<std::vector<size_t>> (&groups)[2],
+                       std::vector<size_t> &rest, Take take) {
+    auto shape = [&](size_t i) { return std::make_tuple(rec[i].color, rec[i].W, rec[i].H); };
+    std::stable_sort(idx.begin(), idx.end(), [&](size_t a, size_t b) { return shape(a) < shape(b); });
+    for (size_t k = 0; k < idx.size();) {
+        size_t e = k;
+        while (e < idx.size() && shape(idx[e]) == shape(idx[k])) e++;
+        const size_t lanes = take(rec[idx[k]], e - k);
+        if (lanes) groups[rec[idx[k]].color].emplace_back(idx.begin() + k, idx.begin() + k + lanes);
+        rest.insert(rest.end(), idx.begin() + k + lanes, idx.begin() + e);
+        k = e;
+    }
+}
+
+// felics_decompress_images_device after the argument checks.  Every stream's header is read on the device (k_read_headers); the
+// frames are laid out in stream order; each stream then takes one of five forms:
+//   - 8-bit, 64 streams of one shape per wave (k_decode8_lanes) -- groups of >= 64 streams of one shape, W >= 8, in a call with
+//     as many 8-bit streams as the same-shape entry point wants for that form;
+//   - 8-bit, a wave per stream (k_decode8), rows in LDS classes, longest streams first, a class per launch and stream;
+//   - 16-bit, 64 streams of one shape per wave (k_decode16_lanes) -- whole waves out of groups of >= 64 streams of one shape and colour,
+//     W >= 8, in a call with as many 16-bit streams as the same-shape entry point wants for that form; passes bounded by the
+//     hashed tables' memory;
+//   - 16-bit, a wave per stream (k_decode16), passes bounded by the estimator tables' memory;
+//   - the host decoder, stream by stream (rows wider than the LDS holds).
+// The GPU forms run on distinct streams of the context, joined with events before the statuses come back.
+int decompress_images(felics_ctx *ctx, size_t n, const void *d_streams, const uint64_t *offsets, const uint64_t *lens, uint8_t *d_pixels,
+                      size_t cap, uint64_t *pix_offsets, felics_header *hdrs, int *status) {
+    Lane &l0 = ctx->lanes[0];
+    hipStream_t s = l0.stream;
+    felics_decode_stats &ds = ctx->dstats;
+    ds.streams += n;
+    ds.lanes16_table_bytes = 0;
+    auto fail_all = [&](int code) { return fail_decode(ctx, n, status, code); };
+    std::vector<DecodeHeader> rec;
+    int rc = read_headers(ctx, n, d_streams, offsets, lens, rec, s);
+    if (rc) return fail_all(rc);
+    // layout in stream order; a stream that will not be decoded gets no bytes
+    uint64_t at = 0;
+    std::vector<uint64_t> npix(n, 0);
+    for (size_t i = 0; i < n; i++) {
+        const DecodeHeader &h = rec[i];
+        if (hdrs) hdrs[i] = h.status == FELICS_OK ? felics_header{h.color, h.depth, h.W, h.H} : felics_header{};
+        status[i] = h.dstatus;
+        pix_offsets[i] = at;
+        if (h.dstatus != FELICS_OK) continue;
+        npix[i] = (uint64_t)h.W * h.H;
+        at = (at + npix[i] * (h.color ? 3 : 1) * (h.depth ? 2 : 1) + 15) & ~15ull;
+    }
+    const uint64_t needed = at;
+    if (needed > cap) {
+        for (size_t i = 0; i < n; i++)
+            if (status[i] == FELICS_OK) status[i] = FELICS_E_BUFFER_TOO_SMALL;
+        pix_offsets[0] = needed;
+        ds.undecoded += n;
+        return FELICS_E_BUFFER_TOO_SMALL;
+    }
+    if (needed && !d_pixels) return fail_all(FELICS_E_INVALID_ARGUMENT);
+    // forms
+    int forced = -1;  // FELICS_TEST_DECODE_LANES=1 / =0: every same-shape group with W >= 8 / none in the lane form (tests)
+    if (const char *e = getenv("FELICS_TEST_DECODE_LANES")) forced = atoi(e) != 0;
+    std::vector<size_t> idx8, wave8, rows16, host;
+    for (size_t i = 0; i < n; i++) {
+        const DecodeHeader &h = rec[i];
+        if (status[i] != FELICS_OK) continue;
+        if (!h.depth && decode8_lds_bytes(h.W, h.color) <= DECODE_LDS_LIMIT) idx8.push_back(i);
+        else if (h.depth && decode16_lds_bytes(h.W) <= DECODE_LDS_LIMIT) rows16.push_back(i);
+        else host.push_back(i);
+    }
+    const size_t n8 = idx8.size(), n16 = rows16.size();
+    // lane groups [colour]: GPU streams of one shape, in stream order within a group.  8-bit: in a call with as many 8-bit streams as
+    // the same-shape entry point wants for that form, the whole waves of every group with W >= 8 (FELICS_TEST_DECODE_LANES=1: all of
+    // it, =0: none).  16-bit: the same rule over the 16-bit GPU streams (FELICS_TEST_DECODE16_LANES=1: in any call; =0: none).  The
+    // rest of a group and every other stream keep the wave form.
+    std::vector<std::vector<size_t>> lane_groups[2], lane16_groups[2];
+    same_shape_groups(rec, idx8, lane_groups, wave8, [&](const DecodeHeader &h, size_t cnt) -> size_t {
+        if (h.W < 8) return 0;
+        if (forced >= 0) return forced ? cnt : 0;
+        return n8 >= (h.color ? DECODE8_LANES_MIN_STREAMS_RGB : DECODE8_LANES_MIN_STREAMS) ? cnt / 64 * 64 : 0;
+    });
+    const int forced16 = dec16_lanes_forced();
+    if (forced16 != 0 && n16 >= 64) {
+        std::vector<size_t> rest;
+        same_shape_groups(rec, rows16, lane16_groups, rest, [&](const DecodeHeader &h, size_t cnt) -> size_t {
+            const bool enough = forced16 == 1 || n16 >= (h.color ? DECODE16_LANES_MIN_STREAMS_RGB : DECODE16_LANES_MIN_STREAMS);
+            return h.W >= 8 && enough ? cnt / 64 * 64 : 0;
+        });
+        std::sort(rest.begin(), rest.end());  // (stream order again, as without this form)
+        rows16.swap(rest);
+    }
+    auto longest_first = [&](std::vector<size_t> &v) {
+        std::stable_sort(v.begin(), v.end(), [&](size_t a, size_t b) { return npix[a] > npix[b]; });
+    };
+    longest_first(wave8);
+    longest_first(rows16);
+    // RGB8 planes (int16) of the wave rows and the lane slots
+    uint64_t planes8 = 0;
+    auto plane8_of = [&](size_t i) {
+        const uint64_t o = planes8;
+        planes8 += 3 * npix[i];
+        return o;
+    };
+    // wave-form rows in LDS classes: a class's launch asks for its widest row's LDS, so a thin image does not share a
+    // launch (and its residency) with a very wide one
+    constexpr uint32_t LDS_CLASS[] = {16u << 10, 32u << 10, 64u << 10, DECODE_LDS_LIMIT};
+    constexpr int NCLASS = 4;
+    std::vector<DecodeRow> rows;
+    struct Launch {
+        size_t first, cnt;
+        uint32_t lds;
+        uint64_t max_npix;
+        bool rgb;
+    };
+    std::vector<Launch> classes;
+    for (int c = 0; c < NCLASS; c++) {
+        Launch L{rows.size(), 0, 0, 0, false};
+        for (size_t i : wave8) {
+            const uint32_t lds = decode8_lds_bytes(rec[i].W, rec[i].color);
+            if (lds > LDS_CLASS[c] || (c > 0 && lds <= LDS_CLASS[c - 1])) continue;
+            const uint64_t poff = rec[i].color ? plane8_of(i) : 0;
+            rows.push_back(DecodeRow{(uint32_t)i, rec[i].W, rec[i].H, rec[i].color, pix_offsets[i], poff});
+            L.cnt++;
+            L.lds = std::max(L.lds, lds);
+            L.max_npix = std::max(L.max_npix, npix[i]);
+            L.rgb = L.rgb || rec[i].color;
+        }
+        if (L.cnt) classes.push_back(L);
+    }
+    // lane form: waves of up to 64 slots of one shape; gray slots first, then RGB (each colour one launch, its tables behind the other's)
+    std::vector<LaneWave> waves;
+    std::vector<LaneSlot> slots;
+    Launch lanes[2] = {};  // first / cnt index waves; max_npix; conversion rows of the RGB slots: `conv`
+    size_t slot0[2] = {0, 0};
+    Launch conv{0, 0, 0, 0, true};
+    for (int col = 0; col < 2; col++) {
+        lanes[col].first = waves.size();
+        slot0[col] = slots.size();
+        for (const auto &g : lane_groups[col]) {
+            for (size_t k = 0; k < g.size(); k += 64) {
+                const uint32_t cnt = (uint32_t)std::min<size_t>(64, g.size() - k);
+                waves.push_back(LaneWave{rec[g[k]].W, rec[g[k]].H, (uint32_t)(slots.size() - slot0[col]), cnt});
+                for (uint32_t j = 0; j < cnt; j++) {
+                    const size_t i = g[k + j];
+                    const uint64_t poff = col ? plane8_of(i) : 0;
+                    slots.push_back(LaneSlot{(uint32_t)i, 0, col ? poff : pix_offsets[i]});
+                    if (col) {
+                        if (!conv.cnt) conv.first = rows.size();
+                        rows.push_back(DecodeRow{(uint32_t)i, rec[i].W, rec[i].H, 1, pix_offsets[i], poff});
+                        conv.cnt++;
+                    }
+                    lanes[col].max_npix = std::max(lanes[col].max_npix, npix[i]);
+                }
+            }
+        }
+        lanes[col].cnt = waves.size() - lanes[col].first;
+    }
+    const size_t nslots8 = slots.size();  // (the 16-bit lane form's slots and waves follow)
+    // 16-bit lane form: passes of whole waves of one colour, each within the table memory dec16_lanes_tables grants; a pass's slots
+    // name their tables by row (LaneSlot::table_row) and its RGB planes start over at the front of dec_planes16
+    struct LanePass16 {
+        int col;
+        size_t wave_first, wave_cnt, slot_first, conv_first, conv_cnt;
+        uint64_t max_npix;
+    };
+    std::vector<LanePass16> passes16;
+    uint64_t lane_planes16 = 0;  // int32 samples of the largest lane pass's RGB planes
+    size_t nlanes16 = 0;
+    {
+        uint64_t want_rows = 0, least_rows = 0;
+        auto slot_rows = [&](size_t i) { return (uint64_t)(rec[i].color ? 3 : 1) * dec16l_rows(npix[i], rec[i].color ? 3 : 1); };
+        for (int col = 0; col < 2; col++)
+            for (const auto &g : lane16_groups[col]) {
+                want_rows += slot_rows(g[0]) * g.size();
+                least_rows = std::max(least_rows, slot_rows(g[0]) * 64);
+                nlanes16 += g.size();
+            }
+        size_t tbytes = 0;
+        if (nlanes16 && (rc = dec16_lanes_tables(ctx, (size_t)want_rows * DEC16L_ROW_BYTES, (size_t)least_rows * DEC16L_ROW_BYTES, tbytes)) != 0)
+            return fail_all(rc);
+        const uint64_t pass_rows = tbytes / DEC16L_ROW_BYTES;
+        const size_t pass_streams = dec16_lanes_pass_cap();
+        uint64_t used_rows = 0, poff = 0, most_rows = 0;
+        size_t in_pass = 0;
+        for (int col = 0; col < 2; col++)
+            for (const auto &g : lane16_groups[col])
+                for (size_t k = 0; k < g.size(); k += 64) {
+                    const uint64_t wave_rows = slot_rows(g[k]) * 64;
+                    if (passes16.empty() || passes16.back().col != col || used_rows + wave_rows > pass_rows || in_pass + 64 > pass_streams) {
+                        passes16.push_back(LanePass16{col, waves.size(), 0, slots.size(), rows.size(), 0, 0});
+                        used_rows = poff = 0;
+                        in_pass = 0;
+                    }
+                    LanePass16 &P = passes16.back();
+                    waves.push_back(LaneWave{rec[g[k]].W, rec[g[k]].H, (uint32_t)(slots.size() - P.slot_first), 64});
+                    P.wave_cnt++;
+                    for (uint32_t j = 0; j < 64; j++) {
+                        const size_t i = g[k + j];
+                        slots.push_back(LaneSlot{(uint32_t)i, (uint32_t)used_rows, col ? poff : pix_offsets[i] / 2});
+                        if (col) {
+                            rows.push_back(DecodeRow{(uint32_t)i, rec[i].W, rec[i].H, 1, pix_offsets[i], poff});
+                            P.conv_cnt++;
+                            poff += 3 * npix[i];
+                        }
+                        used_rows += slot_rows(i);
+                        P.max_npix = std::max(P.max_npix, npix[i]);
+                    }
+                    in_pass += 64;
+                    lane_planes16 = std::max(lane_planes16, poff);
+                    most_rows = std::max(most_rows, used_rows);
+                }
+        ds.lanes16_table_bytes = most_rows * DEC16L_ROW_BYTES;
+    }
+    // 16-bit rows (passes below) behind the others
+    const size_t rows16_first = rows.size();
+    size_t per16 = 0;
+    uint64_t planes16 = lane_planes16;  // int32 samples: the lane passes' RGB planes, the largest wave pass's behind them
+    if (!rows16.empty()) {
+        if ((rc = dec16_tables(ctx, rows16.size(), per16)) != 0) return fail_all(rc);
+        for (size_t p = 0; p < rows16.size(); p += per16) {
+            uint64_t poff = lane_planes16;
+            for (size_t k = p; k < std::min(rows16.size(), p + per16); k++) {
+                const size_t i = rows16[k];
+                rows.push_back(DecodeRow{(uint32_t)i, rec[i].W, rec[i].H, rec[i].color, pix_offsets[i], poff});
+                if (rec[i].color) poff += 3 * npix[i];
+            }
+            planes16 = std::max(planes16, poff);
+        }
+    }
+    // device side: offsets | lens | status | rows | waves | slots (offsets and lens again: the buffer may have moved)
+    auto al = [](size_t b) { return (b + 15) & ~(size_t)15; };
+    const size_t o_status = n * 16, o_rows = o_status + al(n * 4), o_waves = o_rows + al(rows.size() * sizeof(DecodeRow)),
+                 o_slots = o_waves + al(waves.size() * sizeof(LaneWave)), o_end = o_slots + slots.size() * sizeof(LaneSlot);
+    if ((rc = reserve(ctx, ctx->dec_meta, o_end)) != 0) return fail_all(rc);
+    uint8_t *meta = (uint8_t *)ctx->dec_meta.p;
+    uint64_t *d_off = (uint64_t *)meta, *d_len = d_off + n;
+    int *d_status = (int *)(meta + o_status);
+    DecodeRow *d_rows = (DecodeRow *)(meta + o_rows);
+    LaneWave *d_waves = (LaneWave *)(meta + o_waves);
+    LaneSlot *d_slots = (LaneSlot *)(meta + o_slots);
+    if (planes8 && (rc = reserve(ctx, ctx->dec_planes, planes8 * 2 + 64)) != 0) return fail_all(rc);
+    if (planes16 && (rc = reserve(ctx, ctx->dec_planes16, planes16 * 4 + 64)) != 0) return fail_all(rc);
+    const size_t lt_gray = decode8_lanes_table_bytes((uint32_t)(slot0[1] - slot0[0]), 0);
+    const size_t lt_bytes = lt_gray + decode8_lanes_table_bytes((uint32_t)(nslots8 - slot0[1]), 1);
+    if (nslots8 && (rc = reserve(ctx, ctx->dec_lane_table, lt_bytes)) != 0) return fail_all(rc);
+    std::vector<int> dev_status(status, status + n);
+    for (size_t i = 0; i < n; i++)
+        if (dev_status[i] == FELICS_OK) dev_status[i] = FELICS_E_HIP;  // until the kernel's own word arrives
+    for (size_t i : host) dev_status[i] = FELICS_OK;
+    for (size_t i = 0; i < n; i++) ds.undecoded += status[i] != FELICS_OK;
+    ds.wave8 += wave8.size();
+    ds.lanes8 += n8 - wave8.size();
+    ds.wave16 += rows16.size();
+    ds.lanes16 += nlanes16;
+    ds.host += host.size();
+    auto queue = [&]() -> int {
+        HIP_TRY(ctx, hipMemcpyAsync(d_off, offsets, n * 8, hipMemcpyHostToDevice, s));
+        HIP_TRY(ctx, hipMemcpyAsync(d_len, lens, n * 8, hipMemcpyHostToDevice, s));
+        HIP_TRY(ctx, hipMemcpyAsync(d_status, dev_status.data(), n * 4, hipMemcpyHostToDevice, s));
+        if (!rows.empty()) HIP_TRY(ctx, hipMemcpyAsync(d_rows, rows.data(), rows.size() * sizeof(DecodeRow), hipMemcpyHostToDevice, s));
+        if (!waves.empty()) HIP_TRY(ctx, hipMemcpyAsync(d_waves, waves.data(), waves.size() * sizeof(LaneWave), hipMemcpyHostToDevice, s));
+        if (!slots.empty()) HIP_TRY(ctx, hipMemcpyAsync(d_slots, slots.data(), slots.size() * sizeof(LaneSlot), hipMemcpyHostToDevice, s));
+        // the launches that do not depend on each other go to distinct streams of the context, behind the uploads
+        std::vector<hipStream_t> work;
+        for (int li = 0; li < ctx->nlanes; li++) {
+            Lane &l = ctx->lanes[li];
+            for (hipStream_t w : {l.front, l.kstream, li ? l.stream : l.tail})
+                if (w && std::find(work.begin(), work.end(), w) == work.end()) work.push_back(w);
+        }
+        HIP_TRY(ctx, hipEventRecord(l0.slice_done[0], s));
+        for (hipStream_t w : work) HIP_TRY(ctx, hipStreamWaitEvent(w, l0.slice_done[0], 0));
+        size_t next = 0;
+        auto stream_for = [&]() { return work[next++ % work.size()]; };
+        const uint8_t *st = (const uint8_t *)d_streams;
+        if (!rows16.empty()) {
+            hipStream_t w = stream_for();
+            for (size_t p = 0; p < rows16.size(); p += per16) {
+                const size_t cnt = std::min(per16, rows16.size() - p);
+                uint32_t lds = 0, epoch0 = 0;
+                uint64_t mx = 0;
+                bool rgb = false;
+                for (size_t k = p; k < p + cnt; k++) {
+                    const size_t i = rows16[k];
+                    lds = std::max(lds, decode16_lds_bytes(rec[i].W));
+                    mx = std::max(mx, npix[i]);
+                    rgb = rgb || rec[i].color;
+                }
+                int r = dec16_epoch(ctx, w, epoch0);
+                if (r) return r;
+                HIP_TRY(ctx, launch_decode16_rows(w, st, d_off, d_len, d_rows + rows16_first + p, (uint32_t)cnt, lds, mx, rgb, (uint16_t *)d_pixels,
+                                                  (int32_t *)ctx->dec_planes16.p, (uint32_t *)ctx->dec_table.p, epoch0, d_status));
+            }
+        }
+        if (nslots8) {
+            hipStream_t w = stream_for();
+            HIP_TRY(ctx, hipMemsetAsync(ctx->dec_lane_table.p, 0, lt_bytes, w));
+            for (int col = 0; col < 2; col++)
+                HIP_TRY(ctx, launch_decode8_lanes_waves(w, st, d_off, d_len, d_waves + lanes[col].first, (uint32_t)lanes[col].cnt, d_slots + slot0[col],
+                                                        col, d_rows + conv.first, (uint32_t)conv.cnt, lanes[1].max_npix, d_pixels,
+                                                        (int16_t *)ctx->dec_planes.p, (uint32_t *)((uint8_t *)ctx->dec_lane_table.p + (col ? lt_gray : 0)),
+                                                        d_status));
+        }
+        if (!passes16.empty()) {
+            hipStream_t w = stream_for();
+            for (const LanePass16 &P : passes16) {
+                uint32_t epoch0 = 0;
+                int r = dec16_lanes_epoch(ctx, w, epoch0);
+                if (r) return r;
+                HIP_TRY(ctx, launch_decode16_lanes_waves(w, st, d_off, d_len, d_waves + P.wave_first, (uint32_t)P.wave_cnt, d_slots + P.slot_first, P.col,
+                                                         d_rows + P.conv_first, (uint32_t)P.conv_cnt, P.max_npix, (uint16_t *)d_pixels,
+                                                         (int32_t *)ctx->dec_planes16.p, (uint32_t *)ctx->dec_lane16_table.p, epoch0, d_status));
+            }
+        }
+        for (const Launch &L : classes)
+            HIP_TRY(ctx, launch_decode8_rows(stream_for(), st, d_off, d_len, d_rows + L.first, (uint32_t)L.cnt, L.lds, L.max_npix, L.rgb, d_pixels,
+                                             (int16_t *)ctx->dec_planes.p, d_status));
+        // the host decoder meanwhile (into frames no kernel writes)
+        std::vector<uint8_t> sbuf, pbuf;
+        for (size_t i : host) {
+            const felics_header want{rec[i].color, rec[i].depth, rec[i].W, rec[i].H};
+            const int r = host_decode(ctx, st + offsets[i], lens[i], felics_max_compressed_size(rec[i].W, rec[i].H, rec[i].color, rec[i].depth), want,
+                                      d_pixels + pix_offsets[i], sbuf, pbuf);
+            if (r == FELICS_E_HIP) return r;
+            status[i] = r == HOST_DECODE_NO_MEMORY ? FELICS_E_IO : r;
+        }
+        const size_t used = std::min(next, work.size());
+        for (size_t k = 0; k < used; k++) {
+            HIP_TRY(ctx, hipEventRecord(l0.spine_done[k], work[k]));
+            HIP_TRY(ctx, hipStreamWaitEvent(s, l0.spine_done[k], 0));
+        }
+        HIP_TRY(ctx, hipMemcpyAsync(dev_status.data(), d_status, n * 4, hipMemcpyDeviceToHost, s));
+        HIP_TRY(ctx, hipStreamSynchronize(s));
+        return FELICS_OK;
+    };
+    if ((rc = queue()) != 0) {
+        for (size_t i = 0; i < n; i++) status[i] = FELICS_E_HIP;
+        return rc;
+    }
+    std::vector<char> on_host(n, 0);
+    for (size_t i : host) on_host[i] = 1;
+    int first = FELICS_OK;
+    for (size_t i = 0; i < n; i++) {
+        if (!on_host[i]) status[i] = dev_status[i];
+        if (status[i] && !first) first = status[i];
+    }
+    return first;
+}
+
+// What a pass of `most` same-shape 16-bit streams needs beside its tables: offsets | lens | status in dec_meta and, RGB, the int32
+// planes in dec_planes.
+int dec16_buffers(felics_ctx *ctx, size_t most, const felics_header &hdr) {
+    int rc = reserve(ctx, ctx->dec_meta, most * 8 * 2 + most * 4);
+    if (!rc && hdr.color_type == FELICS_COLOR_RGB) rc = reserve(ctx, ctx->dec_planes, (size_t)((uint64_t)hdr.width * hdr.height * 3 * 4 * most) + 64);
+    return rc;
+}
+
+// The passes of the same-shape 16-bit decoders (a wave per stream: launch_decode16 on dec_table; 64 streams per wave:
+// launch_decode16_lanes on dec_lane16_table): n streams of shape `hdr`, `per` to a pass, every pass with fresh epochs on its table.
+int decode16_passes(felics_ctx *ctx, size_t n, size_t per, const void *d_streams, const uint64_t *offsets, const uint64_t *lens, const felics_header &hdr,
+                    void *d_pixels, decltype(&launch_decode16) launch, const DevBuf &table, int (*next_epoch)(felics_ctx *, hipStream_t, uint32_t &),
+                    int *status) {
+    const bool rgb = hdr.color_type == FELICS_COLOR_RGB;
+    const uint64_t frame_samples = (uint64_t)hdr.width * hdr.height * (rgb ? 3 : 1);
+    int32_t *d_planes32 = rgb ? (int32_t *)ctx->dec_planes.p : nullptr;
+    int rc;
+    hipStream_t s = ctx->lanes[0].stream;
+    for (size_t i = 0; i < n; i++) status[i] = FELICS_E_HIP;  // until the kernel's own word arrives
+    int first_rc = FELICS_OK;
+    for (size_t first = 0; first < n; first += per) {
+        const size_t cnt = std::min(per, n - first);
+        uint32_t epoch0 = 0;
+        if ((rc = next_epoch(ctx, s, epoch0)) != 0) return rc;
+        uint64_t *d_off = (uint64_t *)ctx->dec_meta.p, *d_len = d_off + cnt;
+        int *d_status = (int *)(d_len + cnt);
+        HIP_TRY(ctx, hipMemcpyAsync(d_off, offsets + first, cnt * 8, hipMemcpyHostToDevice, s));
+        HIP_TRY(ctx, hipMemcpyAsync(d_len, lens + first, cnt * 8, hipMemcpyHostToDevice, s));
+        HIP_TRY(ctx, hipMemsetAsync(d_status, 0xFF, cnt * 4, s));
+        HIP_TRY(ctx, launch(s, (const uint8_t *)d_streams, d_off, d_len, (uint32_t)cnt, hdr.width, hdr.height, hdr.color_type,
+                            (uint16_t *)d_pixels + first * frame_samples, d_planes32, (uint32_t *)table.p, epoch0, d_status));
+        HIP_TRY(ctx, hipMemcpyAsync(status + first, d_status, cnt * 4, hipMemcpyDeviceToHost, s));
+        HIP_TRY(ctx, hipStreamSynchronize(s));
+        for (size_t i = first; i < first + cnt && !first_rc; i++)
+            if (status[i]) first_rc = status[i];
+    }
+    return first_rc;
+}
+
+}  // namespace
+
+}  // namespace felics
+
+extern "C" {
+
+int felics_get_decode_stats(const felics_ctx *ctx, felics_decode_stats *out, size_t out_size) {
+    if (!ctx || !out) return FELICS_E_INVALID_ARGUMENT;
+    memcpy(out, &ctx->dstats, std::min(out_size, sizeof(felics_decode_stats)));
+    return FELICS_OK;
+}
+
+uint32_t felics_decode_lanes_min_streams(int depth, int color) {
+    if (depth) return color ? DECODE16_LANES_MIN_STREAMS_RGB : DECODE16_LANES_MIN_STREAMS;
+    return color ? DECODE8_LANES_MIN_STREAMS_RGB : DECODE8_LANES_MIN_STREAMS;
+}
+
+int felics_decompress_batch_device(felics_ctx *ctx, size_t n, const void *d_streams, const uint64_t *offsets,
+                                   const uint64_t *lens, void *d_pixels, size_t d_pixels_cap, felics_header *hdr_out,
+                                   int *status) {
+    if (!ctx || (n && (!d_streams || !offsets || !lens || !status))) return FELICS_E_INVALID_ARGUMENT;
+    if (ctx->failed) return FELICS_E_HIP;
+    if (n == 0) return FELICS_OK;
+    if (any_pending(ctx)) return FELICS_E_INVALID_ARGUMENT;  // felics_wait_batch first
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    Lane &l = ctx->lanes[0];
+    // the shape every stream must have: header of stream 0
+    uint8_t h0[FELICS_HEADER_BYTES] = {0};
+    const size_t hl = (size_t)std::min<uint64_t>(lens[0], FELICS_HEADER_BYTES);
+    if (hl) HIP_TRY(ctx, hipMemcpy(h0, (const uint8_t *)d_streams + offsets[0], hl, hipMemcpyDeviceToHost));
+    felics_decode_stats &ds = ctx->dstats;
+    ds.streams += n;
+    ds.lanes16_table_bytes = 0;
+    auto fail_all = [&](int code) { return fail_decode(ctx, n, status, code); };
+    felics_header hdr;
+    int rc = felics_read_header(h0, hl, &hdr);
+    if (rc) return fail_all(rc);  // stream 0 names the shape: without it nothing is decoded
+    if (hdr_out) *hdr_out = hdr;
+    const uint32_t planes = hdr.color_type == FELICS_COLOR_RGB ? 3 : 1;
+    const size_t bps = hdr.pixel_depth == FELICS_DEPTH_16 ? 2 : 1;
+    const uint64_t npix = (uint64_t)hdr.width * hdr.height;
+    if (npix > 0xFFFFFFFFull) return fail_all(FELICS_E_INVALID_DIMENSIONS);
+    const uint64_t frame_bytes = npix * planes * bps;
+    if (frame_bytes * n > d_pixels_cap) return fail_all(FELICS_E_BUFFER_TOO_SMALL);
+    if (frame_bytes && !d_pixels) return fail_all(FELICS_E_INVALID_ARGUMENT);
+    // a stream of this shape is never longer than this: a caller's length beyond it is not a stream (and not a size to allocate)
+    const uint64_t max_len = felics_max_compressed_size(hdr.width, hdr.height, hdr.color_type, hdr.pixel_depth);
+    const int forced16 = dec16_lanes_forced();
+    if (bps == 2 && hdr.width >= 8 && decode16_lds_bytes(hdr.width) <= DECODE_LDS_LIMIT &&
+        (forced16 == 1 || (forced16 < 0 && n >= (planes == 3 ? DECODE16_LANES_MIN_STREAMS_RGB : DECODE16_LANES_MIN_STREAMS)))) {
+        // 16-bit streams 64 to a wave (k_decode16_lanes): passes of whole waves, bounded by the hashed tables' memory
+        const size_t tb1 = decode16_lanes_table_bytes(1, hdr.width, hdr.height, hdr.color_type);
+        const size_t n64 = (n + 63) / 64 * 64;
+        size_t tbytes = 0;
+        if ((rc = dec16_lanes_tables(ctx, std::min(n64, dec16_lanes_pass_cap()) * tb1, 64 * tb1, tbytes)) != 0) return fail_all(rc);
+        const size_t per = std::min(n64, tbytes / tb1 / 64 * 64);
+        const size_t most = std::min(per, n);
+        if ((rc = dec16_buffers(ctx, most, hdr)) != 0) return fail_all(rc);
+        ds.lanes16 += n;
+        ds.lanes16_table_bytes = most * tb1;
+        return decode16_passes(ctx, n, per, d_streams, offsets, lens, hdr, d_pixels, launch_decode16_lanes, ctx->dec_lane16_table, dec16_lanes_epoch, status);
+    }
+    if (bps == 2 && decode16_lds_bytes(hdr.width) <= DECODE_LDS_LIMIT) {
+        // 16-bit streams a wave each: passes of at most DEC16_PASS streams (a stream's estimator table is 8.4 MB of HBM)
+        // (and of at most a quarter of the free HBM; an allocation that fails all the same halves the pass)
+        size_t per = 0;
+        if ((rc = dec16_tables(ctx, n, per)) != 0) return fail_all(rc);
+        if ((rc = dec16_buffers(ctx, per, hdr)) != 0) return fail_all(rc);
+        ds.wave16 += n;
+        return decode16_passes(ctx, n, per, d_streams, offsets, lens, hdr, d_pixels, launch_decode16, ctx->dec_table, dec16_epoch, status);
+    }
+    if (bps == 2 || decode8_lds_bytes(hdr.width, hdr.color_type) > DECODE_LDS_LIMIT) {
+        // host decoder, stream by stream
+        std::vector<uint8_t> sbuf, pbuf;
+        try {
+            pbuf.resize((size_t)frame_bytes);
+            sbuf.reserve((size_t)std::min<uint64_t>(max_len, 1ull << 32));
+        } catch (const std::bad_alloc &) {
+            return fail_all(FELICS_E_IO);
+        }
+        ds.host += n;
+        int first_rc = FELICS_OK;
+        for (size_t i = 0; i < n; i++) {
+            const int r = host_decode(ctx, (const uint8_t *)d_streams + offsets[i], lens[i], max_len, hdr, (uint8_t *)d_pixels + i * frame_bytes,
+                                      sbuf, pbuf);
+            if (r == FELICS_E_HIP) {
+                for (size_t k = i; k < n; k++) status[k] = FELICS_E_HIP;
+                return r;
+            }
+            if (r == HOST_DECODE_NO_MEMORY) {
+                for (size_t k = i; k < n; k++) status[k] = FELICS_E_IO;
+                return first_rc ? first_rc : FELICS_E_IO;
+            }
+            status[i] = r;
+            if (r && !first_rc) first_rc = r;
+        }
+        return first_rc;
+    }
+    // offsets | lens | status on the device
+    const size_t meta = n * 8 * 2 + n * 4;
+    if ((rc = reserve(ctx, ctx->dec_meta, meta)) != 0) return fail_all(rc);
+    uint64_t *d_off = (uint64_t *)ctx->dec_meta.p, *d_len = d_off + n;
+    int *d_status = (int *)(d_len + n);
+    int16_t *d_planes = nullptr;
+    if (planes == 3) {
+        if ((rc = reserve(ctx, ctx->dec_planes, (size_t)(npix * 3 * 2 * n) + 64)) != 0) return fail_all(rc);
+        d_planes = (int16_t *)ctx->dec_planes.p;
+    }
+    hipStream_t s = l.stream;
+    for (size_t i = 0; i < n; i++) status[i] = FELICS_E_HIP;  // until the kernel's own word arrives
+    HIP_TRY(ctx, hipMemcpyAsync(d_off, offsets, n * 8, hipMemcpyHostToDevice, s));
+    HIP_TRY(ctx, hipMemcpyAsync(d_len, lens, n * 8, hipMemcpyHostToDevice, s));
+    HIP_TRY(ctx, hipMemsetAsync(d_status, 0xFF, n * 4, s));
+    // hundreds of streams and more: 64 streams per wave (lane = stream); fewer: one wave per stream
+    // (FELICS_TEST_DECODE_LANES=1 / =0 force one form whatever the batch: tests)
+    bool by_lane = hdr.width >= 8 && n >= (planes == 3 ? DECODE8_LANES_MIN_STREAMS_RGB : DECODE8_LANES_MIN_STREAMS);
+    if (const char *e = getenv("FELICS_TEST_DECODE_LANES")) by_lane = hdr.width >= 8 && atoi(e) != 0;
+    if (by_lane) {
+        const size_t tb = decode8_lanes_table_bytes((uint32_t)n, hdr.color_type);
+        if ((rc = reserve(ctx, ctx->dec_lane_table, tb)) != 0) return fail_all(rc);
+        ds.lanes8 += n;
+        HIP_TRY(ctx, hipMemsetAsync(ctx->dec_lane_table.p, 0, tb, s));
+        HIP_TRY(ctx, launch_decode8_lanes(s, (const uint8_t *)d_streams, d_off, d_len, (uint32_t)n, hdr.width, hdr.height, hdr.color_type,
+                                          (uint8_t *)d_pixels, d_planes, (uint32_t *)ctx->dec_lane_table.p, d_status));
+    } else {
+        ds.wave8 += n;
+        HIP_TRY(ctx, launch_decode8(s, (const uint8_t *)d_streams, d_off, d_len, (uint32_t)n, hdr.width, hdr.height, hdr.color_type,
+                                    (uint8_t *)d_pixels, d_planes, d_status));
+    }
+    HIP_TRY(ctx, hipMemcpyAsync(status, d_status, n * 4, hipMemcpyDeviceToHost, s));
+    HIP_TRY(ctx, hipStreamSynchronize(s));
+    for (size_t i = 0; i < n; i++)
+        if (status[i]) return status[i];
+    return FELICS_OK;
+}
+
+int felics_read_headers_device(felics_ctx *ctx, size_t n, const void *d_streams, const uint64_t *offsets, const uint64_t *lens,
+                               felics_header *hdrs, int *status) {
+    if (!ctx || (n && (!d_streams || !offsets || !lens || !hdrs || !status))) return FELICS_E_INVALID_ARGUMENT;
+    auto fail_all = [&](int code) { return fail_call(n, status, hdrs, nullptr, code); };
+    if (ctx->failed) return fail_all(FELICS_E_HIP);
+    if (n == 0) return FELICS_OK;
+    if (any_pending(ctx)) return fail_all(FELICS_E_INVALID_ARGUMENT);  // felics_wait_batch first
+    if (n > 0xFFFFFFFFull) return fail_all(FELICS_E_INVALID_ARGUMENT);
+    if (hipSetDevice(ctx->device) != hipSuccess) return fail_all(hip_fail(ctx, hipGetLastError(), "hipSetDevice"));
+    // one launch, one copy back
+    std::vector<DecodeHeader> rec;
+    const int rc = read_headers(ctx, n, d_streams, offsets, lens, rec, ctx->lanes[0].stream);
+    if (rc) return fail_all(rc);
+    int first = FELICS_OK;
+    for (size_t i = 0; i < n; i++) {
+        status[i] = rec[i].status;
+        hdrs[i] = rec[i].status == FELICS_OK ? felics_header{rec[i].color, rec[i].depth, rec[i].W, rec[i].H} : felics_header{};
+        if (rec[i].status && !first) first = rec[i].status;
+    }
+    return first;
+}
+
+int felics_decompress_images_device(felics_ctx *ctx, size_t n, const void *d_streams, const uint64_t *offsets, const uint64_t *lens,
+                                    void *d_pixels, size_t d_pixels_cap, uint64_t *pix_offsets, felics_header *hdrs, int *status) {
+    if (!ctx || (n && (!d_streams || !offsets || !lens || !pix_offsets || !status))) return FELICS_E_INVALID_ARGUMENT;
+    auto fail_all = [&](int code) { return fail_call(n, status, hdrs, pix_offsets, code); };
+    if (ctx->failed) return fail_all(FELICS_E_HIP);
+    if (n == 0) return FELICS_OK;
+    if (any_pending(ctx)) return fail_all(FELICS_E_INVALID_ARGUMENT);  // felics_wait_batch first
+    if (n > 0xFFFFFFFFull) return fail_all(FELICS_E_INVALID_ARGUMENT);
+    if (hipSetDevice(ctx->device) != hipSuccess) return fail_all(hip_fail(ctx, hipGetLastError(), "hipSetDevice"));
+    return decompress_images(ctx, n, d_streams, offsets, lens, (uint8_t *)d_pixels, d_pixels_cap, pix_offsets, hdrs, status);
+}
+
+}  // extern "C"

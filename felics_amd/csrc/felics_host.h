@@ -1,0 +1,253 @@
+// felics_host.h -- what the host side of libfelics shares between its translation units (felics_context.cpp, felics_encode.cpp,
+// felics_mixed.cpp, felics_decode_device.cpp): the context, a lane's streams and workspace, and the helpers that cross files.
+// Internal: everything declared here has hidden visibility, the library exports the C ABI of include/felics.h only.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <chrono>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <thread>
+#include <type_traits>
+#include <string>
+#include <algorithm>
+#include <new>
+#include <tuple>
+#include <vector>
+
+#include "../../include/felics.h"
+#include "felics_kernels.h"
+
+using namespace felics;
+
+#pragma GCC visibility push(hidden)
+
+namespace felics {
+
+enum Stage { ST_PLANES = 0, ST_HIST, ST_OFFSETS, ST_SCATTER, ST_SPINE, ST_ASSIGN, ST_LENGTHS, ST_BITSCAN, ST_ZERO, ST_PACK,
+             ST_WIDE_KEYS, ST_WIDE_SORT, ST_WIDE_CHAINS, ST_COUNT };
+extern const char *const kStageNames[ST_COUNT];
+static_assert(ST_COUNT <= FELICS_MAX_STAGES, "felics.h promises at most FELICS_MAX_STAGES stages");
+
+constexpr int SLICES = 12;              // at most; a submission uses lane.nslices of them
+constexpr uint64_t PASS_MAX_CHAINS = 1u << 23;  // chains (plane x context) of one 8-bit pass at most: max_images_per_pass
+constexpr int EV_PAIRS = SLICES + 2;    // launches of one stage per sub-batch that can be timed
+constexpr int MAX_LANES = 4;            // upper bound of the submissions in flight (felics_submit_batch_device), each with streams and workspace of its own
+constexpr int DEFAULT_LANES = 2;        // what a context uses unless FELICS_LANES says otherwise (measured round 3: 2 lanes x 4 slices 3.03-3.06 ms per step,
+                                        // 3 lanes x 3 slices 2.97-3.16, 4 lanes 3.18-3.47: the kernels are issue-bound, so more of them side by side gain nothing)
+enum AssignOn { ASSIGN_OWN, ASSIGN_FRONT, ASSIGN_TAIL };  // the stream k_assign3 is queued on (felics_ctx_create)
+int lanes_from_env();  // FELICS_LANES
+
+struct DevBuf {
+    void *p = nullptr;
+    size_t cap = 0;
+};
+
+// One pipeline lane: HIP streams, stage events and a workspace in HBM of its own.  A submission (or one pass of
+// a huge one) runs on one lane; felics_submit_batch_device hands the lanes out in turn, so that the GPU starts
+// on the next batch while it finishes the last pack slices of this one.
+struct Lane {
+    hipStream_t stream = nullptr;      // spine slices; everything of a 16-bit sub-batch (run_wide)
+    hipStream_t front = nullptr;       // colour planes; per slice the front kernel (classify + sort a tile's events) and the chains' records (k_enum)
+    hipStream_t kstream = nullptr;     // assign slices (k of the events); with four lanes there is none and they go to the front stream (felics_ctx_create)
+    hipStream_t tail = nullptr;        // pack slices (k_pack_t), sizes; the two-pass kernels (lengths, bit scan, pack); shared by the lanes unless FELICS_OWN_TAILS
+    hipEvent_t slice_done[SLICES] = {};
+    hipEvent_t spine_done[SLICES] = {};
+    hipEvent_t assign_done[SLICES] = {};
+    hipEvent_t ev[ST_COUNT][EV_PAIRS][2] = {};  // profiling: one start/stop pair per launch of a stage
+    int ev_used[ST_COUNT] = {};                  // pairs used by the current sub-batch
+    hipEvent_t sized = nullptr;       // stream sizes have landed in h_sizes
+    hipEvent_t span_begin = nullptr, span_end = nullptr;  // profiling: in front of the sub-batch's first kernel / behind its last byte
+    uint64_t *h_sizes = nullptr;      // pinned: image_bytes[n] followed by image_off[n + 1]
+    size_t h_sizes_cap = 0;
+    // 8-bit samples, tile-local layout (felics_kernels.h): ev / pix_of / k_sorted = the tiles' slots (event value, pixel, k), counts = the
+    // run table, tile_slots, desc / block_state = the records of the chains in chain order (place + events, start state), partial =
+    // the chains' record ranges per slice
+    // (8-bit: image_bytes is the head of the lane's CLEARED BLOCK -- sizes, error word, counters, plane sums, chain_state: run_lane)
+    DevBuf planes, counts, scalars, evs, pix_of, k_map, k_sorted, block_state, group_bits, tile_slots, desc,
+        tile_bits, tile_bitoff, plane_sums, image_bytes, image_off, partial, status, edge_first, edge_last, pscratch;
+    uint64_t *plane_base = nullptr;   // the sub-batch's plane bases (behind its plane carries; pack_exact reads them)
+    DevBuf wrecs[2], wtile_cnt, wmeta, whist, wdigtot, heads, wlong;  // 16-bit samples: event records (sort double buffer), tile counts, plane ranges, digit histograms, chain heads
+    uint32_t epoch = 0;               // sub-batches this lane has run: block tags are (epoch, slice)
+    // the submission in flight on this lane (felics_submit_batch_device .. felics_wait_batch)
+    bool pending = false;
+    bool finished = false;            // it took the synchronous path: results are in r_off / r_len / r_rc
+    size_t p_n = 0;
+    const void *p_pixels = nullptr;
+    uint32_t p_w = 0, p_h = 0;
+    int p_color = 0, p_depth = 0;
+    uint8_t *p_out = nullptr;
+    size_t p_cap = 0;
+    uint64_t p_slot = 0;
+    std::vector<uint64_t> r_off, r_len;
+    int r_rc = 0;
+    // the sub-batch in flight
+    int nslices = SLICES;             // slices its tiles are cut into (see felics_ctx::slices_*)
+    bool m_tickets = false;           // the sub-batch's pack kernels took their tiles by ticket (what a look-back failure escalates from)
+    bool m_fused = false;             // ... and were the single-pass kernels at all
+    bool queued = false;              // this sub-batch came through felics_submit_batch_device (other submissions share the GPU with it)
+    Geometry g;
+    size_t first_image = 0;
+    const void *d_planes = nullptr;
+    // a mixed sub-batch (felics_compress_images*): its plane table, written on the host (pinned) and copied to the device
+    DevBuf mtable;
+    PlaneGeom *h_table = nullptr;
+    size_t h_table_cap = 0;
+};
+
+}  // namespace felics
+
+struct felics_ctx {
+    int device = -1;
+    int next_lane = 0;          // lane of the next felics_submit_batch_device
+    int nlanes = DEFAULT_LANES; // lanes in use (FELICS_LANES)
+    // Slices per sub-batch: the stages follow each other slice by slice, so more slices let assign / pack start earlier behind the
+    // spine -- and every slice costs a launch, a hand-over per stage and a resume of every chain.  Round 5, blocking calls
+    // (profiles/r05/experiments.txt): 64 S1 frames 2 / 3 / 4 / 6 / 8 slices 2.95 / 2.68 / 2.75 / 2.79 / 2.76 ms, noise 4.19 / 4.37 /
+    // 4.52 / 4.96 / 5.37, one 4K frame 1.99 / 1.93 / 1.95 / 2.04 / 2.15 (round 4's pipeline wanted 6).
+    int slices_blocking = 3;    // FELICS_SLICES
+    int slices_queued = 2;      // (round 5, tile-local pipeline: 1 slice 3.05, 2 2.54, 3 2.90, 4 2.86, 6 2.82 ms per step with two lanes; round 3 measured 2-4 lanes x 1-6 slices within 3 % of each other: profiles/r03/experiments.txt;
+                                // round 4's pipeline: 2 slices 2.94, 3 2.82-2.89, 4 2.78-2.80, 6 2.89-2.91, 8 2.96 ms; three lanes 3.06)
+    // k_pack_t takes its tiles from the workgroup index while the lanes share the tail stream: one pack kernel then has the
+    // look-back to itself.  With a tail stream per lane (FELICS_OWN_TAILS=1), and after a look-back has given up once, tiles are
+    // handed out by a ticket counter instead: a tile then only ever waits for tiles held by workgroups that are already running,
+    // whatever else shares the GPU.  The counter is one memory-side atomic per tile on one address -- 130 000 per step at the
+    // ~88 per microsecond one address sustains (MI355X_MICROARCH.md, dequeue) -- measured 1.59 against 1.26 ms of pack launches per step.
+    bool pack_tickets = false;
+    bool two_pass = false;      // FELICS_TWO_PASS=1, or a look-back gave up with ticketed tiles as well: lengths + pack kernels
+    bool own_tails = false;     // FELICS_OWN_TAILS=1: a tail stream per lane (pack kernels of two submissions side by side, tiles by ticket)
+    int assign_on = ASSIGN_OWN; // up to three lanes; ASSIGN_FRONT with four (felics_ctx_create); FELICS_ASSIGN_STREAM=own|front|tail (tuning sweeps: profiles/hw_queues.txt)
+    bool serial = false;        // FELICS_SERIAL=1 (profiling tools: every kernel alone): all stages of a lane on one stream
+    bool test_timeout = false;  // FELICS_TEST_TIMEOUT=1: every wait for the GPU reports a time-out (tests of the failed state)
+    bool test_lookback = false; // FELICS_TEST_LOOKBACK_FAIL=1: pretend the first single-pass submission gave up (tests)
+    // The front kernel ranks a tile's events with returning LDS atomics and CHECKS the order it produced (felics_kernels.hip,
+    // k_front); a context whose check fails once ranks with ballots from then on (FELICS_SCATTER=ballot starts that way: tests).
+    bool scatter_ballot = false;
+    // Slots per tile of the tile-local layout: the default covers anything but adversarial content; a tile that needs more
+    // raises TL_FLAG_OVERFLOW, the batch is redone with the worst case and the context keeps to it (FELICS_TEST_TILE_CAP=1
+    // starts with a cap so small that the first batch overflows: tests).
+    bool cap_max = false;
+    bool test_tile_cap = false;
+    bool test_scatter_order = false; // FELICS_TEST_SCATTER_ORDER=1: k_front reports a violation whatever it produced (tests)
+    bool poison = false;        // FELICS_POISON=1: overwrite the workspace before every sub-batch (tests)
+    bool trace = false;         // FELICS_TRACE=1: synchronise and report after every stage (debugging)
+    int timeout_s = 120;        // FELICS_TIMEOUT_S: give up waiting for a submission after this long
+    // A wait for the GPU timed out: kernels of this context may still be running (or never return), so nothing
+    // of it may be reused or freed.  Every later call fails with FELICS_E_HIP; the caller should exit (or run
+    // further work in a fresh process).
+    bool failed = false;
+    felics_stats stats = {};
+    Lane lanes[MAX_LANES];
+    std::string err;
+    bool profiling = false;
+    float stage_ms[ST_COUNT] = {};
+    float span_ms = 0.f;        // profiling: first kernel -> sizes on the host, of the last submission collected
+    int stage_launches[ST_COUNT] = {};
+    DevBuf in, out;  // staging of the host-pointer entry point: the batch's frames, the chunks' output slots
+    hipStream_t copy_in = nullptr, copy_out = nullptr;  // felics_compress_batch: frames to the device / streams back, beside the kernels
+    std::vector<hipEvent_t> h2d_done;                   // a chunk's frames have arrived (one per chunk of a host-buffer batch; grown on demand)
+    hipEvent_t wait_before_submit = nullptr;            // the next sub-batch's first kernel waits for this event (set around one submit)
+    DevBuf mix_in, mix_stage, mix_out, mix_redo;  // felics_compress_images*: 16-bit frames gathered per shape and their streams, the first
+                                                  // run of a call whose buffer cannot hold the slots, frames gathered for a remedy
+    // felics_compress_views_device: the caller's ready event (every stream waits for it before it first reads a view or writes the
+    // output: wait_ready), the dense copies of gray8 views that cannot be read in place, the counts of felics_get_view_stats
+    hipEvent_t view_ready = nullptr;
+    DevBuf view_stage;
+    felics_view_stats vstats = {};
+    DevBuf own;      // encode_device's own output when the caller gives none (the host entry point's fall-back for a chunk whose streams outgrew their slots)
+    DevBuf dec_meta, dec_planes;  // GPU decoder: offsets | lens | status of a batch; Y / Co / Cg planes of RGB streams
+    DevBuf dec_planes16;          // mixed decode call: the int32 planes of its RGB16 streams (beside dec_planes, used at the same time)
+    DevBuf dec_lane_table;        // gray streams decoded 64 to a wave: the estimator rows that do not fit in LDS (3 KB per stream, zeroed per call)
+    DevBuf dec_table;             // 16-bit streams: estimator tables in HBM (8.4 MB per stream of a pass), zeroed once, rows tagged with an epoch
+    uint32_t dec_epoch = 0;       // last epoch handed out (three per call: one per plane)
+    DevBuf dec_lane16_table;      // 16-bit streams decoded 64 to a wave: their hashed estimator tables (felics_lanetable.h), zeroed once, rows tagged with an epoch
+    uint32_t dec_lane16_epoch = 0;  // last epoch handed out on dec_lane16_table (three per launch, 1 .. DEC16L_EPOCH_MAX)
+    felics_decode_stats dstats = {};  // felics_get_decode_stats
+};
+
+namespace felics {
+
+#define HIP_TRY(ctx, call)                                          \
+    do {                                                            \
+        hipError_t e__ = (call);                                    \
+        if (e__ != hipSuccess) return hip_fail(ctx, e__, #call);    \
+    } while (0)
+
+int hip_fail(felics_ctx *ctx, hipError_t e, const char *what);  // sets ctx->err, returns FELICS_E_HIP
+
+// ---- felics_context.cpp
+int wait_event(felics_ctx *ctx, hipEvent_t ev, const char *what);
+int sync_lane(felics_ctx *ctx, Lane &l);
+int reserve(felics_ctx *ctx, DevBuf &b, size_t bytes);
+int reserve_zeroed(felics_ctx *ctx, DevBuf &b, size_t bytes);
+int reserve_pinned(felics_ctx *ctx, void **p, size_t &cap, size_t count, size_t bytes);
+void collect_timing(felics_ctx *ctx, Lane &l);
+int check_args(uint32_t w, uint32_t h, int color, int depth);
+void header_bytes(uint8_t *o, uint32_t w, uint32_t h, int color, int depth);
+bool any_pending(const felics_ctx *ctx);
+
+// ---- felics_encode.cpp
+struct SlotOutcome;
+size_t max_images_per_pass(uint64_t npix, uint32_t planes, int depth);
+Geometry &begin_sub_batch(felics_ctx *ctx, Lane &l, size_t first, size_t cnt, uint32_t w, uint32_t h, int color, int depth, int nslices, bool queued);
+int run_sub_batch(felics_ctx *ctx, Lane &l, uint8_t *d_out, uint64_t slot_stride);
+int launch_sub_batch(felics_ctx *ctx, Lane &l, size_t first, size_t cnt, const void *d_pixels, uint32_t w, uint32_t h, int color, int depth,
+                     uint8_t *lane_out, uint64_t slot, int nslices, bool queued = false);
+SlotOutcome decode_status(const felics_ctx *ctx, const Lane &l, uint64_t word);
+SlotOutcome read_sizes(felics_ctx *ctx, Lane &l, bool wide, uint64_t slot, uint64_t *offsets, uint64_t *lens);
+int apply_remedy(felics_ctx *ctx, const Lane &l, const SlotOutcome &o);
+int encode_device(felics_ctx *ctx, Lane &l, size_t n, const void *d_pixels, uint32_t w, uint32_t h, int color, int depth, uint8_t *d_out,
+                  size_t d_out_cap, uint64_t *offsets, uint64_t *lens, uint8_t **used_out, bool start_exact = false);
+
+// the slot a stream gets unless the caller's buffer dictates another: the frame's size and a quarter, 16-byte aligned
+inline uint64_t default_slot(size_t frame_bytes) { return ((uint64_t)frame_bytes + frame_bytes / 4 + 64 + 15) & ~15ull; }
+
+// Brackets one launch (or a few back-to-back launches) of a stage with HIP events on the stream it runs
+// on; a stage's time is the sum over its launches of a sub-batch.
+struct StageTimer {
+    felics_ctx *ctx;
+    Lane &lane;
+    int st;
+    hipStream_t stream;
+    int slot = -1;
+    bool exact;  // one kernel launch inside: record that kernel's own begin / end (see LaunchTiming)
+    StageTimer(felics_ctx *c, Lane &l, int s, hipStream_t on, bool single_kernel = false)
+        : ctx(c), lane(l), st(s), stream(on), exact(single_kernel) {
+        if (ctx->profiling && lane.ev_used[st] < EV_PAIRS) {
+            slot = lane.ev_used[st]++;
+            if (exact)
+                g_launch_timing = LaunchTiming{lane.ev[st][slot][0], lane.ev[st][slot][1]};
+            else
+                (void)hipEventRecord(lane.ev[st][slot][0], stream);
+        }
+    }
+    ~StageTimer() {
+        if (slot >= 0) {
+            if (!exact) {
+                (void)hipEventRecord(lane.ev[st][slot][1], stream);
+            } else if (g_launch_timing.start) {  // nothing was launched: give the pair back
+                g_launch_timing = LaunchTiming{};
+                lane.ev_used[st]--;
+            }
+        }
+        if (ctx->trace) {  // FELICS_TRACE: wait for the stage and say so (locating a kernel that does not return)
+            hipError_t e = hipStreamSynchronize(stream);
+            fprintf(stderr, "[felics] %s done (%s)\n", kStageNames[st], hipGetErrorString(e));
+        }
+    }
+};
+
+// What the sizes that came back say about a sub-batch packed into fixed slots.
+struct SlotOutcome {
+    bool lookback_failed = false;  // a tile of the single-pass pack gave up waiting for the tiles before it
+    bool overflow = false;         // a stream outgrew its slot, or an RGB plane its scratch slot
+    bool order_violation = false;  // the front kernel's check of its own output failed: nothing of this sub-batch is to be used
+    bool tile_overflow = false;    // a tile's events did not fit its slots (tile_cap_default): nothing of this sub-batch is to be used
+    bool spine_error = false;      // the spine's search lost its invariant (never seen): an internal error, reported as such
+    bool redo() const { return lookback_failed || order_violation || tile_overflow; }
+};
+
+}  // namespace felics
+
+#pragma GCC visibility pop

@@ -1,0 +1,651 @@
+// felics_mixed.cpp -- images of different shapes in one call (felics_compress_images*) and strided views of device surfaces
+// (felics_compress_views_device): buckets, the mixed sub-batches' plane tables, landing and remedies.
+#include "felics_host.h"
+
+namespace felics {
+
+namespace {
+
+// ---- mixed shapes (felics_compress_images*) ------------------------------------------------------------------------------
+// 8-bit images go in BUCKETS of similar size: sorted by sort tiles T = ceil(w h / SORT_TILE), a bucket holds T_min .. ceil(1.25 T_min)
+// (at most 25 % of a bucket's tiles are padding), and a bucket is one sub-batch whose tile count is uniform at its T_max; what
+// differs per plane (samples, W, H, npix, the image's slot) comes from a table (Geometry::mixed).  16-bit images are bucketed by the
+// same rule; a bucket (or a pass of one) of ONE shape takes the uniform path (frames gathered in mix_in, streams copied out of
+// mix_stage), every other one is a mixed 16-bit sub-batch: run_wide with the table, frames read in place, streams straight into
+// their slots.  The sub-batches are queued over the lanes like felics_compress_batch's chunks.
+
+constexpr size_t MIX_MAX_IMAGES = 8192;  // images of one mixed sub-batch (k_concat_planes / k_rgb8_to_planes_mixed: one grid row per image)
+
+struct MixImage {
+    const uint8_t *px;  // device
+    uint32_t w, h;
+    int color, depth;
+    uint64_t npix;
+    uint32_t planes;
+    size_t frame_bytes;
+    // felics_compress_views_device: the frame is not dense at px but the view vr -- read where it lies by the mixed path (gray8
+    // rows `pitch` bytes apart; RGB8 of any strides through the plane transform), gathered into a dense frame where a path wants
+    // one (16-bit groups, remedies: stage_frame)
+    bool view = false;
+    uint64_t pitch = 0;
+    ViewRow vr = {};
+};
+
+// The caller's ready event in front of a stream's first access to a view or to the output (felics_compress_views_device).
+int wait_ready(felics_ctx *ctx, hipStream_t s) {
+    if (ctx->view_ready) HIP_TRY(ctx, hipStreamWaitEvent(s, ctx->view_ready, 0));
+    return FELICS_OK;
+}
+
+// Image m as a dense frame at dst: a copy, or the gather of its view (counted: felics_view_stats::bytes_staged).
+int stage_frame(felics_ctx *ctx, hipStream_t s, void *dst, const MixImage &m) {
+    if (!m.frame_bytes) return FELICS_OK;
+    if (!m.view) {
+        HIP_TRY(ctx, hipMemcpyAsync(dst, m.px, m.frame_bytes, hipMemcpyDeviceToDevice, s));
+        return FELICS_OK;
+    }
+    if (m.depth == FELICS_DEPTH_16)
+        launch_gather_view<uint16_t>(s, m.vr, m.w, m.h, m.planes, (uint16_t *)dst);
+    else
+        launch_gather_view<uint8_t>(s, m.vr, m.w, m.h, m.planes, (uint8_t *)dst);
+    HIP_TRY(ctx, hipGetLastError());
+    ctx->vstats.bytes_staged += m.frame_bytes;
+    return FELICS_OK;
+}
+
+MixImage mix_image(const felics_image &im) {
+    MixImage m;
+    m.px = (const uint8_t *)im.pixels;
+    m.w = im.width;
+    m.h = im.height;
+    m.color = im.color;
+    m.depth = im.depth;
+    m.npix = (uint64_t)im.width * im.height;
+    m.planes = im.color == FELICS_COLOR_RGB ? 3 : 1;
+    m.frame_bytes = (size_t)(m.npix * m.planes * (im.depth == FELICS_DEPTH_16 ? 2 : 1));
+    return m;
+}
+
+// every image checked before anything is launched: the first error in image order
+int check_images(size_t n, const felics_image *images) {
+    for (size_t i = 0; i < n; i++) {
+        const felics_image &im = images[i];
+        int rc = check_args(im.width, im.height, im.color, im.depth);
+        if (rc) return rc;
+        const MixImage m = mix_image(im);
+        if (!im.pixels && m.npix) return FELICS_E_INVALID_ARGUMENT;
+        if (m.npix * m.planes >= 0xE0000000ull) return FELICS_E_UNSUPPORTED;
+        if (m.depth == FELICS_DEPTH_16 && m.npix > WIDE_MAX_PLANE_PIXELS) return FELICS_E_UNSUPPORTED;
+    }
+    return FELICS_OK;
+}
+
+uint32_t sort_tiles_of(uint64_t npix) { return (uint32_t)((npix + SORT_TILE - 1) / SORT_TILE); }
+
+struct MixJob {
+    bool wide = false;          // a 16-bit group of one shape (uniform path), else a mixed sub-batch ...
+    bool wide_mixed = false;    // ... of 16-bit images (launch_mixed_wide), else of 8-bit ones (launch_mixed)
+    std::vector<size_t> idx;    // its images
+    int lane = -1;
+    size_t in_off = 0, stage_off = 0;  // 16-bit: where its frames are gathered (mix_in; mixed: its views only) and, one shape, its streams land (mix_stage)
+    uint64_t slot = 0;                 // 16-bit group of one shape: its slot in mix_stage
+};
+
+// Where a call's streams go: image i at base + off[i], at most slot[i] bytes.  lens[i] = the size of stream i whether it fit or
+// not; overflow = one did not (the caller places the streams exactly and runs again).
+struct MixOut {
+    uint8_t *base;
+    const uint64_t *off, *slot;
+    uint64_t *lens;
+    bool overflow;
+};
+
+// a view's dense copy in a mixed 16-bit job's part of mix_in: 256-byte steps
+size_t gather_step(const MixImage &m) { return m.view ? (m.frame_bytes + 255) & ~(size_t)255 : 0; }
+
+// The head of a mixed sub-batch of either depth on lane l, whose first kernel runs on stream s: the padded geometry (every plane
+// T_max tiles of SORT_TILE samples: the stride of the RGB planes buffer and of k_map), the planes buffer, the pinned table (with
+// one extra row per plane for what views add) and its device copy of tbytes, and -- behind the caller's ready event -- the
+// profiling span.  max_npix = the largest image's pixels.  The caller fills the rows (plane_rows) and uploads them (upload_table).
+int begin_mixed(felics_ctx *ctx, Lane &l, const std::vector<MixImage> &im, const std::vector<size_t> &idx, int depth, int nslices, hipStream_t s,
+                size_t tbytes, uint64_t &max_npix) {
+    const MixImage &f = im[idx[0]];
+    uint32_t tmax = 0;
+    max_npix = 0;
+    for (size_t i : idx) {
+        tmax = std::max(tmax, sort_tiles_of(im[i].npix));
+        max_npix = std::max(max_npix, im[i].npix);
+    }
+    const Geometry &g = begin_sub_batch(ctx, l, 0, idx.size(), SORT_TILE, tmax, f.color, depth, nslices, true);
+    int rc;
+    if (f.planes == 3 && (rc = reserve(ctx, l.planes, (size_t)g.nplanes * g.npix * (depth == FELICS_DEPTH_16 ? 4 : 2) + STAGE_PAD)) != 0) return rc;
+    static_assert(sizeof(PitchedGeom) >= sizeof(ViewRow) && sizeof(PlaneGeom) % 8 == 0, "one extra row per plane holds either");
+    if ((rc = reserve_pinned(ctx, (void **)&l.h_table, l.h_table_cap, g.nplanes, (size_t)g.nplanes * (sizeof(PlaneGeom) + sizeof(PitchedGeom)))) != 0)
+        return rc;
+    if ((rc = reserve(ctx, l.mtable, tbytes)) != 0) return rc;
+    if ((rc = wait_ready(ctx, s)) != 0) return rc;
+    if (ctx->profiling) HIP_TRY(ctx, hipEventRecord(l.span_begin, s));
+    return FELICS_OK;
+}
+
+// The table rows of image j of the sub-batch (image i of the call, dense at `frame`): gray samples are read where the frame lies, the
+// planes of an RGB image from the lane's planes buffer (int16 / int32 samples: sample_bytes), where the plane transform puts them.
+void plane_rows(Lane &l, size_t j, const MixImage &m, const void *frame, size_t sample_bytes, const MixOut &o, size_t i) {
+    for (uint32_t c = 0; c < m.planes; c++) {
+        PlaneGeom &pg = l.h_table[j * m.planes + c];
+        pg.samples = m.planes == 3 ? (const void *)((const uint8_t *)l.planes.p + (j * m.planes + c) * l.g.npix * sample_bytes) : frame;
+        pg.image = frame;
+        pg.W = m.w;
+        pg.H = m.h;
+        pg.npix = (uint32_t)m.npix;
+        pg.ntiles = (uint32_t)((m.npix + PACK_TILE - 1) / PACK_TILE);
+        pg.out_off = o.off[i];
+        pg.out_slot = o.slot[i];
+    }
+}
+
+// The filled table to the device; from here on the sub-batch is a mixed one (every plane's samples come from the table).
+int upload_table(felics_ctx *ctx, Lane &l, size_t tbytes, hipStream_t s) {
+    HIP_TRY(ctx, hipMemcpyAsync(l.mtable.p, l.h_table, tbytes, hipMemcpyHostToDevice, s));
+    l.g.mixed = (const PlaneGeom *)l.mtable.p;
+    l.d_planes = l.g.planes_per_image == 3 ? l.planes.p : nullptr;
+    return FELICS_OK;
+}
+
+// Queues a mixed 8-bit sub-batch on lane l (see launch_sub_batch).  Views are read where they lie: behind the table, the pitched
+// policy's rows of a gray sub-batch (Geometry::pitched), the views of an RGB one (the dense images as views of their own).
+int launch_mixed(felics_ctx *ctx, Lane &l, const std::vector<MixImage> &im, const std::vector<size_t> &idx, const MixOut &o, int nslices) {
+    const uint32_t planes = im[idx[0]].planes;
+    const size_t cnt = idx.size();
+    bool any_view = false;
+    for (size_t i : idx) any_view = any_view || im[i].view;
+    const size_t extra_off = cnt * planes * sizeof(PlaneGeom);
+    const size_t tbytes = extra_off + (any_view ? (planes == 1 ? cnt * sizeof(PitchedGeom) : cnt * sizeof(ViewRow)) : 0);
+    hipStream_t fs = ctx->serial ? l.stream : l.front;
+    uint64_t max_npix;
+    int rc = begin_mixed(ctx, l, im, idx, FELICS_DEPTH_8, nslices, fs, tbytes, max_npix);
+    if (rc) return rc;
+    PitchedGeom *h_pitched = (PitchedGeom *)((uint8_t *)l.h_table + extra_off);  // gray
+    ViewRow *h_views = (ViewRow *)((uint8_t *)l.h_table + extra_off);            // RGB
+    for (size_t j = 0; j < cnt; j++) {
+        const MixImage &m = im[idx[j]];
+        plane_rows(l, j, m, m.px, 2, o, idx[j]);
+        if (any_view && planes == 1) h_pitched[j] = PitchedGeom{l.h_table[j], m.pitch ? m.pitch : (uint64_t)m.w};  // (a dense plane: pitch = W)
+        if (any_view && planes == 3) h_views[j] = m.view ? m.vr : ViewRow{m.px, 3ll * m.w, 3, 1};
+    }
+    if ((rc = upload_table(ctx, l, tbytes, fs)) != 0) return rc;
+    Geometry &g = l.g;
+    if (any_view && planes == 1) g.pitched = (const PitchedGeom *)((const uint8_t *)l.mtable.p + extra_off);
+    if (planes == 3) {
+        StageTimer t(ctx, l, ST_PLANES, fs, true);
+        if (any_view)
+            launch_rgb8_view_to_planes(fs, g.mixed, (const ViewRow *)((const uint8_t *)l.mtable.p + extra_off), g.npix, (uint32_t)max_npix, (uint32_t)cnt);
+        else
+            launch_rgb8_to_planes_mixed(fs, g.mixed, g.npix, (uint32_t)max_npix, (uint32_t)cnt);
+    }
+    return run_sub_batch(ctx, l, o.base, 0);
+}
+
+// Queues a mixed 16-bit sub-batch on lane l: run_wide with the plane table.  gray16 frames are read where the caller has them, RGB16
+// frames by the plane transform; a view is gathered to `gathered` first (stage_frame: counted in bytes_staged) and its rows point
+// there.  Everything on the lane's one stream.
+int launch_mixed_wide(felics_ctx *ctx, Lane &l, const std::vector<MixImage> &im, const std::vector<size_t> &idx, const MixOut &o, uint8_t *gathered,
+                      int nslices) {
+    const size_t cnt = idx.size();
+    const size_t tbytes = cnt * im[idx[0]].planes * sizeof(PlaneGeom);
+    hipStream_t s = l.stream;
+    uint64_t max_npix;
+    int rc = begin_mixed(ctx, l, im, idx, FELICS_DEPTH_16, nslices, s, tbytes, max_npix);
+    if (rc) return rc;
+    size_t at = 0;
+    for (size_t j = 0; j < cnt; j++) {
+        const MixImage &m = im[idx[j]];
+        const uint8_t *frame = m.px;
+        if (m.view) {
+            frame = gathered + at;
+            if ((rc = stage_frame(ctx, s, gathered + at, m)) != 0) return rc;
+            at += gather_step(m);
+        }
+        plane_rows(l, j, m, frame, 4, o, idx[j]);
+    }
+    if ((rc = upload_table(ctx, l, tbytes, s)) != 0) return rc;
+    if (l.g.planes_per_image == 3) {
+        StageTimer t(ctx, l, ST_PLANES, s, true);
+        launch_rgb16_to_planes_mixed(s, l.g.mixed, (uint32_t)max_npix, (uint32_t)cnt);
+    }
+    return run_sub_batch(ctx, l, o.base, 0);
+}
+
+// Streams k of a group (lens[k] bytes at from + offs[k]) into the slots of the call's images idx[k], on the lane's main stream, and
+// waits for them; a stream that outgrew its slot is not copied (o.overflow: the caller places the streams exactly and runs again).
+int copy_to_slots(felics_ctx *ctx, Lane &l, const std::vector<size_t> &idx, const uint8_t *from, const uint64_t *offs, const uint64_t *lens, MixOut &o) {
+    for (size_t k = 0; k < idx.size(); k++) {
+        const size_t i = idx[k];
+        o.lens[i] = lens[k];
+        if (lens[k] > o.slot[i]) {
+            o.overflow = true;
+            continue;
+        }
+        HIP_TRY(ctx, hipMemcpyAsync(o.base + o.off[i], from + offs[k], (size_t)lens[k], hipMemcpyDeviceToDevice, l.stream));
+    }
+    HIP_TRY(ctx, hipStreamSynchronize(l.stream));
+    return FELICS_OK;
+}
+
+// The remedy: the images of `idx` once more through encode_device (its whole ladder), one group per shape, frames gathered
+// into one buffer, streams copied into their slots.
+int redo_by_shape(felics_ctx *ctx, Lane &l, const std::vector<MixImage> &im, const std::vector<size_t> &idx, MixOut &o) {
+    std::vector<size_t> rest = idx;
+    int rc;
+    while (!rest.empty()) {
+        const MixImage &f = im[rest[0]];
+        std::vector<size_t> grp, other;
+        for (size_t i : rest) {
+            const MixImage &m = im[i];
+            (m.w == f.w && m.h == f.h && m.color == f.color && m.depth == f.depth ? grp : other).push_back(i);
+        }
+        rest.swap(other);
+        const size_t cnt = grp.size();
+        if ((rc = reserve(ctx, ctx->mix_redo, f.frame_bytes * cnt + 64)) != 0) return rc;
+        if ((rc = wait_ready(ctx, l.stream)) != 0) return rc;
+        for (size_t j = 0; j < cnt && f.frame_bytes; j++)  // (a view: gathered, the path wants dense frames)
+            if ((rc = stage_frame(ctx, l.stream, (uint8_t *)ctx->mix_redo.p + j * f.frame_bytes, im[grp[j]])) != 0) return rc;
+        HIP_TRY(ctx, hipStreamSynchronize(l.stream));
+        std::vector<uint64_t> offs(cnt), lens(cnt);
+        uint8_t *used = nullptr;
+        if ((rc = encode_device(ctx, l, cnt, ctx->mix_redo.p, f.w, f.h, f.color, f.depth, nullptr, 0, offs.data(), lens.data(), &used)) != 0)
+            return rc;
+        if ((rc = copy_to_slots(ctx, l, grp, used, offs.data(), lens.data(), o)) != 0) return rc;  // (waits: ctx->own is reused by the next group)
+    }
+    return FELICS_OK;
+}
+
+// A job's sub-batch is complete: sizes, its own checks, and the remedy where one is needed.
+int land_job(felics_ctx *ctx, MixJob &j, const std::vector<MixImage> &im, MixOut &o) {
+    Lane &l = ctx->lanes[j.lane];
+    int rc = wait_event(ctx, l.sized, "stream sizes");
+    if (rc) return rc;
+    const size_t cnt = j.idx.size();
+    if (j.wide) {
+        std::vector<uint64_t> offs(cnt), lens(cnt);
+        const SlotOutcome so = read_sizes(ctx, l, true, j.slot, offs.data(), lens.data());
+        uint8_t *from = (uint8_t *)ctx->mix_stage.p + j.stage_off;
+        if ((rc = sync_lane(ctx, l)) != 0) return rc;
+        if (so.overflow) {  // a stream outgrew its slot: the group again with exact placement (encode_device)
+            (void)apply_remedy(ctx, l, so);
+            const MixImage &f = im[j.idx[0]];
+            if ((rc = encode_device(ctx, l, cnt, (uint8_t *)ctx->mix_in.p + j.in_off, f.w, f.h, f.color, f.depth, nullptr, 0, offs.data(),
+                                    lens.data(), &from, true)) != 0)
+                return rc;
+        }
+        if ((rc = copy_to_slots(ctx, l, j.idx, from, offs.data(), lens.data(), o)) != 0) return rc;
+        collect_timing(ctx, l);
+        return FELICS_OK;
+    }
+    // a mixed sub-batch: its table lists the images in the order of j.idx (run_wide copies the sizes and nothing else: no status word)
+    SlotOutcome so = j.wide_mixed ? SlotOutcome{} : decode_status(ctx, l, l.h_sizes[cnt]);
+    for (size_t k = 0; k < cnt; k++) {
+        const size_t i = j.idx[k];
+        o.lens[i] = l.h_sizes[k];
+        if (l.h_sizes[k] > o.slot[i]) so.overflow = true;
+    }
+    if (!so.redo() && !so.overflow && !so.spine_error) {
+        if (j.wide_mixed && ctx->profiling && (rc = sync_lane(ctx, l)) != 0) return rc;  // (run_wide records span_end behind `sized`)
+        collect_timing(ctx, l);
+        return FELICS_OK;
+    }
+    if ((rc = sync_lane(ctx, l)) != 0) return rc;
+    if ((rc = apply_remedy(ctx, l, so)) != 0) return rc;
+    return redo_by_shape(ctx, l, im, j.idx, o);
+}
+
+// The jobs of the call's images of one depth and colour, appended to `jobs`.  Sorted by sort tiles T, a BUCKET holds T_min ..
+// ceil(1.25 T_min); it is cut into passes by the pass bound of its padded planes (T_max * SORT_TILE samples: for 16-bit images that
+// keeps planes * npix of a mixed sub-batch <= 2^30 samples, so the chain kernels' 32-bit kbase = plane * npix -- k_map is strided by
+// the padded npix -- stays valid).  Every pass of 8-bit images is a mixed sub-batch.  A 16-bit bucket of ONE shape is cut by that
+// shape's own npix (the passes that shape always had) and takes the uniform path, as does any other 16-bit pass that holds one shape.
+void bucket_images(const std::vector<MixImage> &im, int depth, int color, std::vector<MixJob> &jobs) {
+    const bool wide = depth == FELICS_DEPTH_16;
+    const uint32_t planes = color == FELICS_COLOR_RGB ? 3 : 1;
+    std::vector<size_t> v;
+    for (size_t i = 0; i < im.size(); i++)
+        if (im[i].npix && im[i].depth == depth && im[i].color == color) v.push_back(i);
+    std::stable_sort(v.begin(), v.end(), [&](size_t a, size_t b) { return sort_tiles_of(im[a].npix) < sort_tiles_of(im[b].npix); });
+    auto one_shape = [&](size_t first, size_t last) {
+        for (size_t k = first; k < last; k++)
+            if (im[v[k]].w != im[v[first]].w || im[v[k]].h != im[v[first]].h) return false;
+        return true;
+    };
+    for (size_t a = 0; a < v.size();) {
+        const uint64_t tmin = sort_tiles_of(im[v[a]].npix), lim = (5 * tmin + 3) / 4;  // ceil(1.25 T_min)
+        size_t b = a;
+        while (b < v.size() && sort_tiles_of(im[v[b]].npix) <= lim) b++;
+        const bool uniform = wide && one_shape(a, b);
+        const size_t per = uniform ? max_images_per_pass(im[v[a]].npix, planes, depth)
+                                   : std::min(MIX_MAX_IMAGES, max_images_per_pass((uint64_t)sort_tiles_of(im[v[b - 1]].npix) * SORT_TILE, planes, depth));
+        for (size_t c = a; c < b; c += per) {
+            const size_t e = std::min(b, c + per);
+            MixJob j;
+            j.wide = wide && (uniform || one_shape(c, e));
+            j.wide_mixed = wide && !j.wide;
+            j.idx.assign(v.begin() + c, v.begin() + e);
+            jobs.push_back(std::move(j));
+        }
+        a = b;
+    }
+}
+
+// Every image of the call into the slots of `o`: zero-sized images on the host path, the jobs queued over the lanes.
+int run_images(felics_ctx *ctx, const std::vector<MixImage> &im, MixOut &o) {
+    const size_t n = im.size();
+    int rc;
+    o.overflow = false;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    std::vector<MixJob> jobs;
+    for (int depth : {FELICS_DEPTH_8, FELICS_DEPTH_16})
+        for (int color : {FELICS_COLOR_GRAY, FELICS_COLOR_RGB}) bucket_images(im, depth, color, jobs);
+    size_t in_total = 0, stage_total = 0;  // 16-bit jobs: their parts of mix_in and mix_stage
+    for (MixJob &j : jobs) {
+        j.in_off = in_total;
+        if (j.wide) {  // frames gathered back to back, streams into slots of one size
+            const size_t fb = im[j.idx[0]].frame_bytes;
+            j.slot = default_slot(fb);
+            j.stage_off = stage_total;
+            in_total += ((fb * j.idx.size()) + 255) & ~(size_t)255;
+            stage_total += (size_t)(j.slot * j.idx.size());
+        } else if (j.wide_mixed) {  // its views only
+            for (size_t i : j.idx) in_total += gather_step(im[i]);
+        }
+    }
+    if (in_total && (rc = reserve(ctx, ctx->mix_in, in_total + 64)) != 0) return rc;
+    if (stage_total && (rc = reserve(ctx, ctx->mix_stage, stage_total + 64)) != 0) return rc;
+    for (size_t i = 0; i < n; i++) {  // zero-sized images: header + two zero words per plane, encode_device's host path
+        if (im[i].npix) continue;
+        if (ctx->view_ready) HIP_TRY(ctx, hipStreamWaitEvent(nullptr, ctx->view_ready, 0));  // (the copy below runs on the null stream)
+        uint64_t off = 0, len = 0;
+        if ((rc = encode_device(ctx, ctx->lanes[0], 1, nullptr, im[i].w, im[i].h, im[i].color, im[i].depth, o.base + o.off[i], (size_t)o.slot[i], &off,
+                                &len, nullptr)) != 0)
+            return rc;
+        o.lens[i] = len;
+    }
+    const int nslices = jobs.size() > 1 ? ctx->slices_queued : ctx->slices_blocking;
+    std::vector<size_t> flying;  // jobs in flight, oldest first (lanes handed out in turn: the oldest holds the next lane)
+    auto drain = [&](int r) {
+        for (size_t f : flying) {
+            (void)wait_event(ctx, ctx->lanes[jobs[f].lane].sized, "stream sizes");
+            (void)sync_lane(ctx, ctx->lanes[jobs[f].lane]);
+        }
+        return r;
+    };
+    for (size_t q = 0; q < jobs.size(); q++) {
+        if ((int)flying.size() == ctx->nlanes) {
+            rc = land_job(ctx, jobs[flying.front()], im, o);
+            flying.erase(flying.begin());
+            if (rc) return drain(rc);
+        }
+        MixJob &j = jobs[q];
+        if (!j.wide && !j.wide_mixed && ctx->two_pass) {  // (the mixed kernels are single-pass: a context on the two-pass kernels takes the uniform path,
+                                         // blocking, once every lane is idle)
+            while (!flying.empty()) {
+                rc = land_job(ctx, jobs[flying.front()], im, o);
+                flying.erase(flying.begin());
+                if (rc) return drain(rc);
+            }
+            if ((rc = redo_by_shape(ctx, ctx->lanes[ctx->next_lane], im, j.idx, o)) != 0) return rc;
+            continue;
+        }
+        j.lane = ctx->next_lane;
+        Lane &l = ctx->lanes[j.lane];
+        ctx->next_lane = (ctx->next_lane + 1) % ctx->nlanes;
+        if (j.wide) {
+            const MixImage &f = im[j.idx[0]];
+            uint8_t *in = (uint8_t *)ctx->mix_in.p + j.in_off;
+            if ((rc = wait_ready(ctx, l.stream)) != 0) return drain(rc);
+            for (size_t k = 0; k < j.idx.size(); k++)  // (a view is gathered by a kernel instead of copied)
+                if ((rc = stage_frame(ctx, l.stream, in + k * f.frame_bytes, im[j.idx[k]])) != 0) return drain(rc);
+            rc = launch_sub_batch(ctx, l, 0, j.idx.size(), in, f.w, f.h, f.color, f.depth, (uint8_t *)ctx->mix_stage.p + j.stage_off, j.slot, nslices, true);
+        } else if (j.wide_mixed) {
+            rc = launch_mixed_wide(ctx, l, im, j.idx, o, (uint8_t *)ctx->mix_in.p + j.in_off, nslices);
+        } else {
+            rc = launch_mixed(ctx, l, im, j.idx, o, nslices);
+        }
+        if (rc) {
+            (void)sync_lane(ctx, l);
+            return drain(rc);
+        }
+        flying.push_back(q);
+    }
+    while (!flying.empty()) {
+        rc = land_job(ctx, jobs[flying.front()], im, o);
+        flying.erase(flying.begin());
+        if (rc) return drain(rc);
+    }
+    return FELICS_OK;
+}
+
+// felics_compress_images_device without the argument checks: slots as encode_device sizes them if d_out holds them, else (or if
+// a stream outgrew its slot) a second run with every stream placed exactly, back to back.
+int images_device(felics_ctx *ctx, const std::vector<MixImage> &im, uint8_t *d_out, size_t d_out_cap, uint64_t *offsets, uint64_t *lens) {
+    const size_t n = im.size();
+    std::vector<uint64_t> off(n), slot(n);
+    uint64_t total = 0;
+    for (size_t i = 0; i < n; i++) {
+        slot[i] = default_slot(im[i].frame_bytes);
+        off[i] = total;
+        total += slot[i];
+    }
+    MixOut o{d_out, off.data(), slot.data(), lens, false};
+    int rc;
+    if (total > d_out_cap) {  // the sizes first, into a buffer of the library's own
+        if ((rc = reserve(ctx, ctx->mix_out, (size_t)total + 64)) != 0) return rc;
+        o.base = (uint8_t *)ctx->mix_out.p;
+    }
+    if ((rc = run_images(ctx, im, o)) != 0) return rc;
+    if (o.base == d_out && !o.overflow) {
+        for (size_t i = 0; i < n; i++) offsets[i] = off[i];
+        return FELICS_OK;
+    }
+    uint64_t need = 0;
+    for (size_t i = 0; i < n; i++) {
+        off[i] = need;
+        slot[i] = (lens[i] + 15) & ~15ull;
+        need += slot[i];
+    }
+    if (need > d_out_cap) {
+        if (n) lens[0] = need;
+        return FELICS_E_BUFFER_TOO_SMALL;
+    }
+    o = MixOut{d_out, off.data(), slot.data(), lens, false};
+    if ((rc = run_images(ctx, im, o)) != 0) return rc;
+    if (o.overflow) {
+        ctx->err = "internal error: a stream outgrew the exact size it had before";
+        return FELICS_E_HIP;
+    }
+    for (size_t i = 0; i < n; i++) offsets[i] = off[i];
+    return FELICS_OK;
+}
+
+// A view's checks (felics_view_extent and felics_compress_views_device alike) and the hull of its samples' bytes relative to data.
+int check_view(const felics_view &v, int64_t &lo, int64_t &hi) {
+    lo = hi = 0;
+    int rc = check_args(v.width, v.height, v.color, v.depth);
+    if (rc) return rc;
+    const uint64_t npix = (uint64_t)v.width * v.height;
+    const uint32_t planes = v.color == FELICS_COLOR_RGB ? 3 : 1;
+    const int bytes = v.depth == FELICS_DEPTH_16 ? 2 : 1;
+    if (!v.data && npix) return FELICS_E_INVALID_ARGUMENT;
+    if (bytes == 2 && (((uintptr_t)v.data | (uint64_t)v.row_stride | (uint64_t)v.pixel_stride | (planes == 3 ? (uint64_t)v.channel_stride : 0u)) & 1u))
+        return FELICS_E_INVALID_ARGUMENT;
+    if (npix * planes >= 0xE0000000ull) return FELICS_E_UNSUPPORTED;
+    if (v.depth == FELICS_DEPTH_16 && npix > WIDE_MAX_PLANE_PIXELS) return FELICS_E_UNSUPPORTED;
+    if (!npix) return FELICS_OK;
+    __int128 l = 0, h = bytes;
+    const int64_t steps[3] = {(int64_t)v.height - 1, (int64_t)v.width - 1, (int64_t)planes - 1};
+    const int64_t strides[3] = {v.row_stride, v.pixel_stride, planes == 3 ? v.channel_stride : 0};
+    for (int d = 0; d < 3; d++) {
+        const __int128 span = (__int128)steps[d] * strides[d];
+        (span < 0 ? l : h) += span;
+    }
+    if (l < INT64_MIN || h > INT64_MAX) return FELICS_E_INVALID_ARGUMENT;  // (addresses are computed in 64 bits)
+    lo = (int64_t)l;
+    hi = (int64_t)h;
+    return FELICS_OK;
+}
+
+}  // namespace
+
+}  // namespace felics
+
+extern "C" {
+
+int felics_compress_images_device(felics_ctx *ctx, size_t n, const felics_image *images, void *d_out, size_t d_out_cap, uint64_t *offsets,
+                                  uint64_t *lens) {
+    if (!ctx || (n && (!images || !d_out || !offsets || !lens))) return FELICS_E_INVALID_ARGUMENT;
+    if (ctx->failed) return FELICS_E_HIP;
+    int rc = check_images(n, images);
+    if (rc) return rc;
+    if (n == 0) return FELICS_OK;
+    if (any_pending(ctx)) return FELICS_E_INVALID_ARGUMENT;  // felics_wait_batch first
+    std::vector<MixImage> im(n);
+    for (size_t i = 0; i < n; i++) im[i] = mix_image(images[i]);
+    return images_device(ctx, im, (uint8_t *)d_out, d_out_cap, offsets, lens);
+}
+
+int felics_view_extent(const felics_view *v, int64_t *lo, int64_t *hi) {
+    if (!v || !lo || !hi) return FELICS_E_INVALID_ARGUMENT;
+    return check_view(*v, *lo, *hi);
+}
+
+int felics_get_view_stats(const felics_ctx *ctx, felics_view_stats *out, size_t out_size) {
+    if (!ctx || !out) return FELICS_E_INVALID_ARGUMENT;
+    memcpy(out, &ctx->vstats, std::min(out_size, sizeof(felics_view_stats)));
+    return FELICS_OK;
+}
+
+int felics_compress_views_device(felics_ctx *ctx, size_t n, const felics_view *views, void *ready_event, void *d_out, size_t d_out_cap,
+                                 uint64_t *offsets, uint64_t *lens) {
+    if (!ctx || (n && (!views || !d_out || !offsets || !lens))) return FELICS_E_INVALID_ARGUMENT;
+    if (ctx->failed) return FELICS_E_HIP;
+    for (size_t i = 0; i < n; i++) {  // every view checked before anything is launched: the first error in view order
+        int64_t lo, hi;
+        int rc = check_view(views[i], lo, hi);
+        if (rc) return rc;
+    }
+    if (n == 0) return FELICS_OK;
+    if (any_pending(ctx)) return FELICS_E_INVALID_ARGUMENT;  // felics_wait_batch first
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    // the class of every view: dense, read in place, or gathered (gray8 now, into view_stage; 16-bit where its group is queued)
+    std::vector<MixImage> im(n);
+    std::vector<size_t> stage_at(n, 0);
+    size_t stage_total = 0;
+    felics_view_stats add = {};
+    for (size_t i = 0; i < n; i++) {
+        const felics_view &v = views[i];
+        MixImage &m = im[i];
+        m = mix_image(felics_image{v.data, v.width, v.height, v.color, v.depth});
+        const int64_t bytes = v.depth == FELICS_DEPTH_16 ? 2 : 1;
+        const bool rgb = v.color == FELICS_COLOR_RGB;
+        add.views++;
+        const bool dense = !m.npix || (v.pixel_stride == bytes * (rgb ? 3 : 1) && v.row_stride == (int64_t)v.width * v.pixel_stride &&
+                                       (!rgb || v.channel_stride == bytes));
+        if (dense) {
+            add.dense++;
+            continue;
+        }
+        m.view = true;
+        m.vr = ViewRow{v.data, v.row_stride, v.pixel_stride, rgb ? v.channel_stride : 0};
+        if (v.depth == FELICS_DEPTH_8 && rgb) {
+            add.in_place++;
+        } else if (v.depth == FELICS_DEPTH_8 && v.pixel_stride == 1 && v.row_stride >= (int64_t)v.width) {
+            add.in_place++;
+            m.pitch = (uint64_t)v.row_stride;
+        } else {
+            add.gathered++;
+            if (v.depth == FELICS_DEPTH_8) {
+                stage_at[i] = stage_total;
+                stage_total += (m.frame_bytes + 255) & ~(size_t)255;
+            }
+        }
+    }
+    int rc;
+    ctx->view_ready = (hipEvent_t)ready_event;
+    ctx->wait_before_submit = (hipEvent_t)ready_event;  // (the uniform path's sub-batches: launch_sub_batch)
+    auto leave = [&](int r) {
+        ctx->view_ready = nullptr;
+        ctx->wait_before_submit = nullptr;
+        return r;
+    };
+    if (stage_total) {
+        Lane &l = ctx->lanes[0];
+        if ((rc = reserve(ctx, ctx->view_stage, stage_total + 64)) != 0) return leave(rc);
+        if ((rc = wait_ready(ctx, l.stream)) != 0) return leave(rc);
+        for (size_t i = 0; i < n; i++) {
+            MixImage &m = im[i];
+            if (!m.view || m.depth != FELICS_DEPTH_8 || m.planes == 3 || m.pitch) continue;
+            uint8_t *dst = (uint8_t *)ctx->view_stage.p + stage_at[i];
+            if ((rc = stage_frame(ctx, l.stream, dst, m)) != 0) return leave(rc);
+            m.px = dst;
+            m.view = false;
+        }
+        if (hipStreamSynchronize(l.stream) != hipSuccess) return leave(hip_fail(ctx, hipGetLastError(), "gathering views"));
+    }
+    ctx->vstats.views += add.views;
+    ctx->vstats.dense += add.dense;
+    ctx->vstats.in_place += add.in_place;
+    ctx->vstats.gathered += add.gathered;
+    return leave(images_device(ctx, im, (uint8_t *)d_out, d_out_cap, offsets, lens));
+}
+
+// Host frames in, host streams out: the frames are copied to the device (16-byte aligned, back to back), encoded as above into the
+// context's own buffer, and every stream that fits its caller's buffer is copied back.
+int felics_compress_images(felics_ctx *ctx, size_t n, const felics_image *images, uint8_t *const *outs, const size_t *caps, size_t *lens) {
+    if (!ctx || (n && (!images || !outs || !caps || !lens))) return FELICS_E_INVALID_ARGUMENT;
+    if (ctx->failed) return FELICS_E_HIP;
+    int rc = check_images(n, images);
+    if (rc) return rc;
+    if (n == 0) return FELICS_OK;
+    if (any_pending(ctx)) return FELICS_E_INVALID_ARGUMENT;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    if (!ctx->copy_in) {
+        HIP_TRY(ctx, hipStreamCreateWithFlags(&ctx->copy_in, hipStreamNonBlocking));
+        HIP_TRY(ctx, hipStreamCreateWithFlags(&ctx->copy_out, hipStreamNonBlocking));
+    }
+    std::vector<MixImage> im(n);
+    std::vector<size_t> at(n);
+    size_t in_total = 0;
+    uint64_t out_total = 64;
+    for (size_t i = 0; i < n; i++) {
+        im[i] = mix_image(images[i]);
+        at[i] = in_total;
+        in_total += (im[i].frame_bytes + 15) & ~(size_t)15;
+        out_total += default_slot(im[i].frame_bytes);
+    }
+    if ((rc = reserve(ctx, ctx->in, in_total + 64)) != 0) return rc;
+    if ((rc = reserve(ctx, ctx->out, (size_t)out_total)) != 0) return rc;
+    for (size_t i = 0; i < n; i++) {
+        uint8_t *dst = (uint8_t *)ctx->in.p + at[i];
+        if (im[i].frame_bytes) HIP_TRY(ctx, hipMemcpyAsync(dst, images[i].pixels, im[i].frame_bytes, hipMemcpyHostToDevice, ctx->copy_in));
+        im[i].px = dst;
+    }
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->copy_in));
+    std::vector<uint64_t> offs(n), sizes(n);
+    rc = images_device(ctx, im, (uint8_t *)ctx->out.p, ctx->out.cap, offs.data(), sizes.data());
+    if (rc == FELICS_E_BUFFER_TOO_SMALL) {  // a stream outgrew its slot and the slots' room: exact placement in a larger buffer
+        if ((rc = reserve(ctx, ctx->out, (size_t)sizes[0] + 64)) != 0) return rc;
+        rc = images_device(ctx, im, (uint8_t *)ctx->out.p, ctx->out.cap, offs.data(), sizes.data());
+    }
+    if (rc) return rc;
+    int result = FELICS_OK;
+    for (size_t i = 0; i < n; i++) {
+        lens[i] = (size_t)sizes[i];
+        if (sizes[i] > caps[i] || !outs[i]) {
+            result = FELICS_E_BUFFER_TOO_SMALL;  // lens[] reports every size needed; nothing is written to this buffer
+            continue;
+        }
+        HIP_TRY(ctx, hipMemcpyAsync(outs[i], (const uint8_t *)ctx->out.p + offs[i], (size_t)sizes[i], hipMemcpyDeviceToHost, ctx->copy_out));
+    }
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->copy_out));
+    return result;
+}
+
+}  // extern "C"

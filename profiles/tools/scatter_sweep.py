@@ -1,5 +1,5 @@
 """The two event sorts against content: 64 4K gray8 frames of a smooth surface plus noise of growing strength, ms per queued
-step and per blocking call with FELICS_SCATTER=ballot and =sorted (felics_api.cpp: scatter_mode).  Runs ON THE GPU BOX."""
+step and per blocking call with FELICS_SCATTER=ballot and =sorted (felics_host.h: felics_ctx::scatter_ballot).  Runs ON THE GPU BOX."""
 import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
 os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")

@@ -17,9 +17,11 @@ KERNELS="felics_kernels felics_wide felics_gpudecode"
 [ -f felics_chain.hip ] && KERNELS="$KERNELS felics_chain"   # (round 5 on; an older checkout has no such file)
 OBJS=""
 for f in $KERNELS; do hipcc $F -c $f.hip -o "$O/$f.o" & OBJS="$OBJS $O/$f.o"; done
-hipcc $F -x hip -c felics_api.cpp -o "$O/felics_api.o" &
+HOST="felics_context felics_encode felics_mixed felics_decode_device"
+[ -f felics_api.cpp ] && HOST="felics_api"   # (a checkout from before the host pipeline was split into files)
+for f in $HOST; do hipcc $F -x hip -c $f.cpp -o "$O/$f.o" & OBJS="$OBJS $O/$f.o"; done
 hipcc -O3 -std=c++17 -fPIC -c felics_decode.cpp -o "$O/felics_decode.o" &
 wait
-hipcc --offload-arch=gfx950 -shared -o "$O/libfelics.so" $OBJS "$O"/felics_api.o "$O"/felics_decode.o -Wl,-rpath,/opt/rocm/lib
+hipcc --offload-arch=gfx950 -shared -o "$O/libfelics.so" $OBJS "$O"/felics_decode.o -Wl,-rpath,/opt/rocm/lib
 rm -f "$O"/*.o
 ls -la "$O/libfelics.so"

@@ -35,6 +35,17 @@ def test_library_exports_every_declared_symbol(api):
     assert declared == set(api.EXPORTS)
 
 
+def test_library_exports_nothing_else(api):
+    """The dynamic symbol table holds the C ABI and nothing beside it under a C name: every defined symbol that is not C++-mangled
+    (_Z...: the kernels' stubs and launch wrappers) and not a __hip_* registration symbol is in api.EXPORTS.  A helper of the host
+    pipeline that crosses translation units must stay hidden."""
+    out = subprocess.run(["nm", "-D", "--defined-only", os.path.join(BUILD, "libfelics.so")], capture_output=True, text=True, check=True).stdout
+    names = [line.split()[-1] for line in out.splitlines() if line.strip()]
+    assert len(names) >= len(api.EXPORTS)
+    stray = sorted(s for s in names if not s.startswith("_Z") and not s.startswith("__hip_") and s not in api.EXPORTS)
+    assert not stray, stray
+
+
 def test_no_gpu_means_loud_failure(api):
     """Without a HIP device the encoder must refuse; there is no CPU encode path to fall back to."""
     import torch

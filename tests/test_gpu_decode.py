@@ -244,6 +244,26 @@ def test_sixteen_bit_streams_on_the_device(enc, oracle):
             assert (host[i * img.size:(i + 1) * img.size].reshape(img.shape) == want).all(), i
 
 
+def test_sixteen_bit_wave_form_in_two_passes(enc, oracle):
+    """felics_decompress_batch_device on 1 030 gray16 and then 1 030 RGB16 streams of 5 x 3: W < 8 keeps them out of the lane form
+    whatever the switches say, and 1 030 > DEC16_PASS = 1 024 makes two passes (1 024 + 6) of the wave form -- the second pass reads
+    its offsets, lengths and frames at `first` = 1 024.  (A box that grants the tables less than a full pass makes more passes; nothing
+    here depends on their number.)  Pixels against the oracle's decoder, every status 0, and the call counted as wave16 alone."""
+    from felics_amd import synth
+
+    n = 1030
+    gray = [synth.gray16(5, 3, f) for f in range(n)]
+    for color, frames in (("gray", gray), ("rgb", [np.stack([f, np.roll(f, 3, axis=1), 65535 - f], -1).copy() for f in gray])):
+        streams = [oracle.compress(f) for f in frames]
+        before = enc.decode_stats()
+        _, back = _decode_batch(enc, streams, frames[0].shape, np.uint16)  # (asserts every status == 0)
+        after = enc.decode_stats()
+        wrong = [i for i, (b, s) in enumerate(zip(back, streams)) if not (b == oracle.decompress(s)).all()]
+        assert not wrong, (color, wrong[:10])
+        moved = {k: after[k] - before[k] for k in ("streams", "wave8", "lanes8", "wave16", "lanes16", "host", "undecoded")}
+        assert moved == {"streams": n, "wave8": 0, "lanes8": 0, "wave16": n, "lanes16": 0, "host": 0, "undecoded": 0}, (color, moved)
+
+
 def _forced(value):
     """context manager: FELICS_TEST_DECODE_LANES for the calls inside (read per call by the library)"""
     import contextlib

@@ -319,7 +319,7 @@ def test_lookback_failure_with_two_submissions_in_flight(oracle):
     """Two queued submissions, both launched without tickets, whose look-backs both give up (FELICS_TEST_LOOKBACK_FAIL): the first
     wait turns tickets on and -- its redo failing with tickets as well -- moves the context to the two-pass kernels; the second
     wait finds a sub-batch that ran WITHOUT tickets, so it counts a fallback but does not escalate on its own account
-    (felics_api.cpp: note_lookback_failure looks at what the failed sub-batch was launched with).  Streams equal the oracle's."""
+    (felics_encode.cpp: note_lookback_failure looks at what the failed sub-batch was launched with).  Streams equal the oracle's."""
     import torch
     import felics_amd
     from felics_amd import synth

@@ -1,7 +1,7 @@
 """The 32-bit edges: passes of more than 2^31 samples, the real pass split, decodes of more than 2^32 bytes, many tiny 8-bit frames.
 
 Every expected byte comes from the CPU oracle (one call per DISTINCT frame of a batch), every expected pixel from the source frame,
-every expected pass count from the bounds documented in felics_api.cpp (restated below as constants); nothing is compared with
+every expected pass count from the bounds documented in felics_encode.cpp (restated below as constants); nothing is compared with
 another output of the library.  The big batches are built on the device: frame[i] = base[i % 7] (seven contents, noise and flat
 among them, so stream sizes differ widely and no power-of-two wrap lands on a frame of the same content), except for a few frames
 with content of their own: the first, the last, and the two around every 2^31 / 2^32 boundary of the sample index and of the input's
@@ -23,19 +23,19 @@ E_BUFFER_TOO_SMALL = -8
 GIB = 1 << 30
 K = 7  # distinct contents of a big batch
 
-# ---- the library's constants (felics_kernels.h) and bounds (felics_api.cpp, max_images_per_pass) -------------------------------
+# ---- the library's constants (felics_kernels.h) and bounds (felics_encode.cpp, max_images_per_pass) -------------------------------
 SORT_TILE = 4096           # felics_kernels.h: SORT_TILE == PACK_TILE
 REC = 16                   # felics_kernels.h: events per record
 PACK_THREADS = 256
-SLICES = 12                # felics_api.cpp
+SLICES = 12                # felics_host.h
 STAGE_PAD = 64
 NCTX = {1: 256, 3: 512}    # nctx_of<>: contexts per plane of gray8 / of the Y, Co, Cg planes of RGB8
 NCTX_MAX = 512             # NCTX
 PASS_MAX_SAMPLES_8 = 0xE0000000   # max_images_per_pass: samples and records of an 8-bit pass
 PASS_MAX_SAMPLES_16 = 0x40000000  # max_images_per_pass: samples of a 16-bit pass
 WIDE_MAX_PLANES = 1 << 16         # max_images_per_pass: planes of a 16-bit pass
-PASS_MAX_CHAINS = 1 << 23         # felics_api.cpp, PASS_MAX_CHAINS: chains (plane x context) of an 8-bit pass
-MIX_MAX_IMAGES = 8192             # felics_api.cpp: images of one mixed sub-batch
+PASS_MAX_CHAINS = 1 << 23         # felics_host.h, PASS_MAX_CHAINS: chains (plane x context) of an 8-bit pass
+MIX_MAX_IMAGES = 8192             # felics_mixed.cpp: images of one mixed sub-batch
 DECODE_LDS_LIMIT = 160 * 1024     # felics_kernels.h
 DEC16_TABLE_BYTES = (2 * 65535 + 1) * 16 * 4  # felics_gpudecode.hip, decode16_table_bytes(1): 8.4 MB per stream of a pass
 FALLBACKS = ("lookback_fallbacks", "scatter_fallbacks", "tile_overflows", "slot_overflows")
@@ -55,7 +55,7 @@ def tile_cap_default(nctx, npix):
 
 
 def images_per_pass(npix, planes, sixteen=False):
-    """max_images_per_pass (felics_api.cpp)"""
+    """max_images_per_pass (felics_encode.cpp)"""
     per_image = npix * planes
     if sixteen:
         return max(1, min(PASS_MAX_SAMPLES_16 // per_image, WIDE_MAX_PLANES // planes))
@@ -145,7 +145,7 @@ N_TINY_GRAY, N_TINY_RGB, TINY_CONTENTS = 200000, 70000, 257
 N_TINY_MIXED, TINY_MIXED_CONTENTS = 40000, 300
 TINY_PASSES_GRAY = cdiv(N_TINY_GRAY * 1 * NCTX[1], PASS_MAX_CHAINS)   # 7
 TINY_PASSES_RGB = cdiv(N_TINY_RGB * 3 * NCTX[3], PASS_MAX_CHAINS)     # 13
-MAX_LANES = 4                     # felics_api.cpp: submissions in flight, each with a workspace of its own (felics_compress_batch's chunks)
+MAX_LANES = 4                     # felics_host.h: submissions in flight, each with a workspace of its own (felics_compress_batch's chunks)
 NEED_TINY = MAX_LANES * max(lane_need_8(images_per_pass(64, 1), 1, 64), lane_need_8(images_per_pass(64, 3), 3, 64)) + SLACK
 # (a mixed job's geometry: one tile of SORT_TILE pixels a plane)
 NEED_TINY_MIXED = MAX_LANES * max(lane_need_8(MIX_MAX_IMAGES, 1, SORT_TILE), lane_need_8(images_per_pass(SORT_TILE, 3), 3, SORT_TILE)) + SLACK
@@ -651,7 +651,7 @@ def test_many_tiny_8bit_frames_host(oracle, planes, n):
 @pytest.mark.parametrize("planes,n,passes", [(1, N_TINY_GRAY, TINY_PASSES_GRAY), (3, N_TINY_RGB, TINY_PASSES_RGB)])
 def test_many_tiny_8bit_frames_device(oracle, planes, n, passes):
     """The same frames through felics_compress_batch_device: a submission carries at most PASS_MAX_CHAINS = 2^23 chains (plane x
-    context; felics_api.cpp, max_images_per_pass), so `submissions` grows by ceil(n * planes * nctx / 2^23) = 7 (gray) / 13 (RGB), and
+    context; felics_encode.cpp, max_images_per_pass), so `submissions` grows by ceil(n * planes * nctx / 2^23) = 7 (gray) / 13 (RGB), and
     every stream is exact across the pass joins.  Prints the device memory the library holds after the call.
     Needs NEED_TINY = 8.0 GB (one lane's workspace of a full pass is 1.5 GB; the need is stated for four lanes)."""
     import felics_amd
