@@ -79,6 +79,11 @@ class _CViewStats(C.Structure):  # felics_view_stats
                 ("bytes_staged", C.c_uint64)]
 
 
+class _CDecodeViewStats(C.Structure):  # felics_decode_view_stats
+    _fields_ = [("views", C.c_uint64), ("dense", C.c_uint64), ("in_place", C.c_uint64), ("scattered", C.c_uint64),
+                ("bytes_staged", C.c_uint64)]
+
+
 class _CDecodeStats(C.Structure):  # felics_decode_stats
     _fields_ = [("streams", C.c_uint64), ("wave8", C.c_uint64), ("lanes8", C.c_uint64), ("wave16", C.c_uint64), ("lanes16", C.c_uint64),
                 ("host", C.c_uint64), ("undecoded", C.c_uint64), ("lanes16_table_bytes", C.c_uint64)]
@@ -110,6 +115,7 @@ EXPORTS = [
     "felics_decompress_images_device",
     "felics_compress_views_device", "felics_view_extent", "felics_get_view_stats",
     "felics_get_decode_stats", "felics_decode_lanes_min_streams",
+    "felics_decompress_views_device", "felics_view_writable", "felics_get_decode_view_stats",
 ]
 
 _lib = None
@@ -174,6 +180,10 @@ def lib():
     L.felics_view_extent.argtypes = [C.POINTER(_CView), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
     L.felics_get_view_stats.argtypes = [vp, C.POINTER(_CViewStats), sz]
     L.felics_get_decode_stats.argtypes = [vp, C.POINTER(_CDecodeStats), sz]
+    L.felics_decompress_views_device.argtypes = [vp, sz, vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(_CView), vp,
+                                                 C.POINTER(_CHeader), C.POINTER(C.c_int)]
+    L.felics_view_writable.argtypes = [C.POINTER(_CView)]
+    L.felics_get_decode_view_stats.argtypes = [vp, C.POINTER(_CDecodeViewStats), sz]
     L.felics_decode_lanes_min_streams.argtypes = [C.c_int, C.c_int]
     L.felics_decode_lanes_min_streams.restype = C.c_uint32
     L.felics_strerror.argtypes = [C.c_int]
@@ -223,6 +233,14 @@ def view_extent(view):
     if rc != 0:
         raise FelicsError(rc)
     return int(lo.value), int(hi.value)
+
+
+def view_writable(view):
+    """felics_view_writable: the code Encoder.decompress_views_device gives a view before anything is launched -- 0, or the error
+    of felics_view_extent's checks, or FELICS_E_INVALID_ARGUMENT (-11) for a view whose samples may share bytes (the nested-strides
+    rule of felics.h).  Host only, needs no GPU."""
+    v = _cview(view)
+    return int(lib().felics_view_writable(C.byref(v)))
 
 
 def view_of_array(array):
@@ -496,6 +514,50 @@ class Encoder:
         if rc != 0:
             self._raise(rc)
         return pix[:n], headers, status[:n]
+
+    def decompress_views_device(self, d_streams, offsets, lens, views, ready_event=None):
+        """felics_decompress_views_device: stream i (device memory, raw pointer) decoded straight into views[i] = (device pointer, w,
+        h, color, depth, row_stride, pixel_stride, channel_stride); only sample bytes are written.  ready_event: a hipEvent_t handle
+        (torch: Event.cuda_event) recorded behind whatever produces the streams and last used the views; the library's streams wait
+        for it, the host does not.  Returns (list of Header -- zeros where a header is invalid --, status array); a refused view
+        raises FelicsError, a failing stream DecompressionError with .status and .headers."""
+        offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+        lens = np.ascontiguousarray(lens, dtype=np.uint64)
+        n = len(offsets)
+        if len(views) != n:
+            raise ValueError("a view per stream")
+        cv = (_CView * max(n, 1))(*[_cview(v) for v in views])
+        status = np.zeros(max(n, 1), dtype=np.int32)
+        hdrs = (_CHeader * max(n, 1))()
+        rc = lib().felics_decompress_views_device(
+            self._h, n, d_streams, offsets.ctypes.data_as(C.POINTER(C.c_uint64)), lens.ctypes.data_as(C.POINTER(C.c_uint64)), cv,
+            int(ready_event) if ready_event else None, hdrs, status.ctypes.data_as(C.POINTER(C.c_int)))
+        headers = [Header(h.color_type, h.pixel_depth, h.width, h.height) for h in hdrs[:n]]  # (zeros where the header is invalid)
+        if rc in DecompressionError.KINDS:
+            err = DecompressionError(rc)
+            err.status, err.headers = status[:n], headers
+            raise err
+        if rc != 0:
+            try:
+                self._raise(rc)
+            except FelicsError as err:
+                err.status = status[:n]
+                raise
+        return headers, status[:n]
+
+    def decompress_arrays_device(self, d_streams, offsets, lens, arrays, ready_event=None):
+        """decompress_views_device into objects with __cuda_array_interface__ (view_of_array): a batch tensor's t[i],
+        chw.permute(1, 2, 0), rgba[..., :3] and mosaic[y0:y1, x0:x1] are decoded into where they lie."""
+        return self.decompress_views_device(d_streams, offsets, lens, [view_of_array(a) for a in arrays], ready_event)
+
+    def decode_view_stats(self):
+        """felics_get_decode_view_stats: views handed to decompress_views_device and how they were written (dense / in_place /
+        scattered, bytes_staged); cumulative."""
+        st = _CDecodeViewStats()
+        rc = lib().felics_get_decode_view_stats(self._h, C.byref(st), C.sizeof(st))
+        if rc != 0:
+            self._raise(rc)
+        return {k: int(getattr(st, k)) for k, _ in _CDecodeViewStats._fields_}
 
     def decode_stats(self):
         """felics_get_decode_stats: how many streams the two device decode calls were handed and which form they took (wave8 / lanes8 /

@@ -166,6 +166,21 @@ void same_shape_groups(const std::vector<DecodeHeader> &rec, std::vector<size_t>
     }
 }
 
+// felics_decompress_views_device: where the streams of one pass of the call write.  cls[i] is view i's class, worked out from the
+// view alone (a stream whose header differs from its view is not decoded at all); stage[i] is the offset of a scattered stream's
+// dense frame in ctx->view_stage.
+enum : uint8_t { VIEW_DENSE = 0, VIEW_IN_PLACE, VIEW_SCATTERED };
+struct ViewPlan {
+    const felics_view *views;
+    const uint8_t *cls;
+    const uint64_t *stage;
+};
+
+// rows too wide for the LDS of either wave form: the host decoder's
+bool rows_for_host(uint32_t W, uint32_t color, uint32_t depth) {
+    return depth ? decode16_lds_bytes(W) > DECODE_LDS_LIMIT : decode8_lds_bytes(W, color) > DECODE_LDS_LIMIT;
+}
+
 // felics_decompress_images_device after the argument checks.  Every stream's header is read on the device (k_read_headers); the
 // frames are laid out in stream order; each stream then takes one of five forms:
 //   - 8-bit, 64 streams of one shape per wave (k_decode8_lanes) -- groups of >= 64 streams of one shape, W >= 8, in a call with
@@ -177,8 +192,14 @@ void same_shape_groups(const std::vector<DecodeHeader> &rec, std::vector<size_t>
 //   - 16-bit, a wave per stream (k_decode16), passes bounded by the estimator tables' memory;
 //   - the host decoder, stream by stream (rows wider than the LDS holds).
 // The GPU forms run on distinct streams of the context, joined with events before the statuses come back.
+//
+// With a ViewPlan (felics_decompress_views_device) the same call writes views: d_pixels is nullptr and pix_offsets[i] becomes the
+// ADDRESS of stream i's dense frame (the view itself if it is dense, its frame in view_stage if it is scattered) or of its view's
+// first sample, so the tables' out_off are absolute; a table of ViewRow runs beside the rows and one beside the slots, and a launch
+// that holds a pitched gray view or a strided RGB one takes the kernels' pitched / strided policies.  Behind the join, one kernel
+// per sample type writes the staged frames through their views.  The caller's ready event goes in front of everything (wait_ready).
 int decompress_images(felics_ctx *ctx, size_t n, const void *d_streams, const uint64_t *offsets, const uint64_t *lens, uint8_t *d_pixels,
-                      size_t cap, uint64_t *pix_offsets, felics_header *hdrs, int *status) {
+                      size_t cap, uint64_t *pix_offsets, felics_header *hdrs, int *status, const ViewPlan *vp = nullptr) {
     Lane &l0 = ctx->lanes[0];
     hipStream_t s = l0.stream;
     felics_decode_stats &ds = ctx->dstats;
@@ -186,7 +207,8 @@ int decompress_images(felics_ctx *ctx, size_t n, const void *d_streams, const ui
     ds.lanes16_table_bytes = 0;
     auto fail_all = [&](int code) { return fail_decode(ctx, n, status, code); };
     std::vector<DecodeHeader> rec;
-    int rc = read_headers(ctx, n, d_streams, offsets, lens, rec, s);
+    int rc = vp ? wait_ready(ctx, s) : FELICS_OK;  // (the header kernel reads stream bytes)
+    if (!rc) rc = read_headers(ctx, n, d_streams, offsets, lens, rec, s);
     if (rc) return fail_all(rc);
     // layout in stream order; a stream that will not be decoded gets no bytes
     uint64_t at = 0;
@@ -197,6 +219,18 @@ int decompress_images(felics_ctx *ctx, size_t n, const void *d_streams, const ui
         status[i] = h.dstatus;
         pix_offsets[i] = at;
         if (h.dstatus != FELICS_OK) continue;
+        if (vp) {  // the view names the shape: another one is not decoded, and nothing of the view is written
+            const felics_view &w = vp->views[i];
+            if ((int)h.color != w.color || (int)h.depth != w.depth || h.W != w.width || h.H != w.height) {
+                status[i] = FELICS_E_INVALID_DIMENSIONS;
+                continue;
+            }
+            npix[i] = (uint64_t)h.W * h.H;
+            const bool staged = vp->cls[i] == VIEW_SCATTERED;
+            pix_offsets[i] = staged ? (uint64_t)(uintptr_t)ctx->view_stage.p + vp->stage[i] : (uint64_t)(uintptr_t)w.data;
+            if (staged) ctx->dvstats.bytes_staged += npix[i] * (h.color ? 3 : 1) * (h.depth ? 2 : 1);
+            continue;
+        }
         npix[i] = (uint64_t)h.W * h.H;
         at = (at + npix[i] * (h.color ? 3 : 1) * (h.depth ? 2 : 1) + 15) & ~15ull;
     }
@@ -216,9 +250,9 @@ int decompress_images(felics_ctx *ctx, size_t n, const void *d_streams, const ui
     for (size_t i = 0; i < n; i++) {
         const DecodeHeader &h = rec[i];
         if (status[i] != FELICS_OK) continue;
-        if (!h.depth && decode8_lds_bytes(h.W, h.color) <= DECODE_LDS_LIMIT) idx8.push_back(i);
-        else if (h.depth && decode16_lds_bytes(h.W) <= DECODE_LDS_LIMIT) rows16.push_back(i);
-        else host.push_back(i);
+        if (rows_for_host(h.W, h.color, h.depth)) host.push_back(i);
+        else if (!h.depth) idx8.push_back(i);
+        else rows16.push_back(i);
     }
     const size_t n8 = idx8.size(), n16 = rows16.size();
     // lane groups [colour]: GPU streams of one shape, in stream order within a group.  8-bit: in a call with as many 8-bit streams as
@@ -258,11 +292,33 @@ int decompress_images(felics_ctx *ctx, size_t n, const void *d_streams, const ui
     constexpr uint32_t LDS_CLASS[] = {16u << 10, 32u << 10, 64u << 10, DECODE_LDS_LIMIT};
     constexpr int NCLASS = 4;
     std::vector<DecodeRow> rows;
+    std::vector<LaneWave> waves;
+    std::vector<LaneSlot> slots;
+    // views: a ViewRow beside every row and every slot (felics_kernels.h, DecodeViews)
+    std::vector<ViewRow> rviews, sviews;
+    auto pitched = [&](size_t i) { return vp && !rec[i].color && vp->cls[i] == VIEW_IN_PLACE; };
+    auto strided = [&](size_t i) { return vp && rec[i].color && vp->cls[i] == VIEW_IN_PLACE; };
+    auto view_row = [&](size_t i) {
+        const felics_view &w = vp->views[i];
+        if (w.color) return ViewRow{w.data, w.row_stride, w.pixel_stride, w.channel_stride};
+        const int64_t size = w.depth ? 2 : 1;  // gray: the view's pitch, or the dense frame's (the view's own or the staged one)
+        if (pitched(i)) return ViewRow{w.data, w.row_stride, size, 0};
+        return ViewRow{(const void *)(uintptr_t)pix_offsets[i], (int64_t)w.width * size, size, 0};
+    };
+    auto push_row = [&](const DecodeRow &r) {
+        rows.push_back(r);
+        if (vp) rviews.push_back(view_row(r.stream));
+    };
+    auto push_slot = [&](const LaneSlot &sl) {
+        slots.push_back(sl);
+        if (vp) sviews.push_back(view_row(sl.stream));
+    };
     struct Launch {
         size_t first, cnt;
         uint32_t lds;
         uint64_t max_npix;
         bool rgb;
+        bool pitched = false, strided = false;  // (views) it holds a pitched gray view / a strided RGB one
     };
     std::vector<Launch> classes;
     for (int c = 0; c < NCLASS; c++) {
@@ -271,7 +327,9 @@ int decompress_images(felics_ctx *ctx, size_t n, const void *d_streams, const ui
             const uint32_t lds = decode8_lds_bytes(rec[i].W, rec[i].color);
             if (lds > LDS_CLASS[c] || (c > 0 && lds <= LDS_CLASS[c - 1])) continue;
             const uint64_t poff = rec[i].color ? plane8_of(i) : 0;
-            rows.push_back(DecodeRow{(uint32_t)i, rec[i].W, rec[i].H, rec[i].color, pix_offsets[i], poff});
+            push_row(DecodeRow{(uint32_t)i, rec[i].W, rec[i].H, rec[i].color, pix_offsets[i], poff});
+            L.pitched = L.pitched || pitched(i);
+            L.strided = L.strided || strided(i);
             L.cnt++;
             L.lds = std::max(L.lds, lds);
             L.max_npix = std::max(L.max_npix, npix[i]);
@@ -280,8 +338,6 @@ int decompress_images(felics_ctx *ctx, size_t n, const void *d_streams, const ui
         if (L.cnt) classes.push_back(L);
     }
     // lane form: waves of up to 64 slots of one shape; gray slots first, then RGB (each colour one launch, its tables behind the other's)
-    std::vector<LaneWave> waves;
-    std::vector<LaneSlot> slots;
     Launch lanes[2] = {};  // first / cnt index waves; max_npix; conversion rows of the RGB slots: `conv`
     size_t slot0[2] = {0, 0};
     Launch conv{0, 0, 0, 0, true};
@@ -295,10 +351,12 @@ int decompress_images(felics_ctx *ctx, size_t n, const void *d_streams, const ui
                 for (uint32_t j = 0; j < cnt; j++) {
                     const size_t i = g[k + j];
                     const uint64_t poff = col ? plane8_of(i) : 0;
-                    slots.push_back(LaneSlot{(uint32_t)i, 0, col ? poff : pix_offsets[i]});
+                    push_slot(LaneSlot{(uint32_t)i, 0, col ? poff : pix_offsets[i]});
+                    lanes[col].pitched = lanes[col].pitched || pitched(i);
                     if (col) {
                         if (!conv.cnt) conv.first = rows.size();
-                        rows.push_back(DecodeRow{(uint32_t)i, rec[i].W, rec[i].H, 1, pix_offsets[i], poff});
+                        push_row(DecodeRow{(uint32_t)i, rec[i].W, rec[i].H, 1, pix_offsets[i], poff});
+                        conv.strided = conv.strided || strided(i);
                         conv.cnt++;
                     }
                     lanes[col].max_npix = std::max(lanes[col].max_npix, npix[i]);
@@ -314,6 +372,7 @@ int decompress_images(felics_ctx *ctx, size_t n, const void *d_streams, const ui
         int col;
         size_t wave_first, wave_cnt, slot_first, conv_first, conv_cnt;
         uint64_t max_npix;
+        bool pitched = false, strided = false;
     };
     std::vector<LanePass16> passes16;
     uint64_t lane_planes16 = 0;  // int32 samples of the largest lane pass's RGB planes
@@ -348,9 +407,11 @@ int decompress_images(felics_ctx *ctx, size_t n, const void *d_streams, const ui
                     P.wave_cnt++;
                     for (uint32_t j = 0; j < 64; j++) {
                         const size_t i = g[k + j];
-                        slots.push_back(LaneSlot{(uint32_t)i, (uint32_t)used_rows, col ? poff : pix_offsets[i] / 2});
+                        push_slot(LaneSlot{(uint32_t)i, (uint32_t)used_rows, col ? poff : pix_offsets[i] / 2});
+                        P.pitched = P.pitched || pitched(i);
+                        P.strided = P.strided || strided(i);
                         if (col) {
-                            rows.push_back(DecodeRow{(uint32_t)i, rec[i].W, rec[i].H, 1, pix_offsets[i], poff});
+                            push_row(DecodeRow{(uint32_t)i, rec[i].W, rec[i].H, 1, pix_offsets[i], poff});
                             P.conv_cnt++;
                             poff += 3 * npix[i];
                         }
@@ -373,16 +434,22 @@ int decompress_images(felics_ctx *ctx, size_t n, const void *d_streams, const ui
             uint64_t poff = lane_planes16;
             for (size_t k = p; k < std::min(rows16.size(), p + per16); k++) {
                 const size_t i = rows16[k];
-                rows.push_back(DecodeRow{(uint32_t)i, rec[i].W, rec[i].H, rec[i].color, pix_offsets[i], poff});
+                push_row(DecodeRow{(uint32_t)i, rec[i].W, rec[i].H, rec[i].color, pix_offsets[i], poff});
                 if (rec[i].color) poff += 3 * npix[i];
             }
             planes16 = std::max(planes16, poff);
         }
     }
-    // device side: offsets | lens | status | rows | waves | slots (offsets and lens again: the buffer may have moved)
+    // views: the scattered streams that may be decoded -- their frames are written through the views behind the join
+    size_t nscat = 0;
+    for (size_t i = 0; vp && i < n; i++) nscat += status[i] == FELICS_OK && vp->cls[i] == VIEW_SCATTERED;
+    // device side: offsets | lens | status | rows | waves | slots (offsets and lens again: the buffer may have moved); views: | the
+    // rows' views | the slots' views | the scatter table
     auto al = [](size_t b) { return (b + 15) & ~(size_t)15; };
     const size_t o_status = n * 16, o_rows = o_status + al(n * 4), o_waves = o_rows + al(rows.size() * sizeof(DecodeRow)),
-                 o_slots = o_waves + al(waves.size() * sizeof(LaneWave)), o_end = o_slots + slots.size() * sizeof(LaneSlot);
+                 o_slots = o_waves + al(waves.size() * sizeof(LaneWave)), o_rviews = o_slots + al(slots.size() * sizeof(LaneSlot)),
+                 o_sviews = o_rviews + al(rviews.size() * sizeof(ViewRow)), o_scat = o_sviews + al(sviews.size() * sizeof(ViewRow)),
+                 o_end = o_scat + nscat * sizeof(ScatterRow);
     if ((rc = reserve(ctx, ctx->dec_meta, o_end)) != 0) return fail_all(rc);
     uint8_t *meta = (uint8_t *)ctx->dec_meta.p;
     uint64_t *d_off = (uint64_t *)meta, *d_len = d_off + n;
@@ -390,6 +457,9 @@ int decompress_images(felics_ctx *ctx, size_t n, const void *d_streams, const ui
     DecodeRow *d_rows = (DecodeRow *)(meta + o_rows);
     LaneWave *d_waves = (LaneWave *)(meta + o_waves);
     LaneSlot *d_slots = (LaneSlot *)(meta + o_slots);
+    ViewRow *d_rviews = (ViewRow *)(meta + o_rviews), *d_sviews = (ViewRow *)(meta + o_sviews);
+    ScatterRow *d_scat = (ScatterRow *)(meta + o_scat);
+    std::vector<ScatterRow> scat[2];  // [depth]
     if (planes8 && (rc = reserve(ctx, ctx->dec_planes, planes8 * 2 + 64)) != 0) return fail_all(rc);
     if (planes16 && (rc = reserve(ctx, ctx->dec_planes16, planes16 * 4 + 64)) != 0) return fail_all(rc);
     const size_t lt_gray = decode8_lanes_table_bytes((uint32_t)(slot0[1] - slot0[0]), 0);
@@ -412,6 +482,8 @@ int decompress_images(felics_ctx *ctx, size_t n, const void *d_streams, const ui
         if (!rows.empty()) HIP_TRY(ctx, hipMemcpyAsync(d_rows, rows.data(), rows.size() * sizeof(DecodeRow), hipMemcpyHostToDevice, s));
         if (!waves.empty()) HIP_TRY(ctx, hipMemcpyAsync(d_waves, waves.data(), waves.size() * sizeof(LaneWave), hipMemcpyHostToDevice, s));
         if (!slots.empty()) HIP_TRY(ctx, hipMemcpyAsync(d_slots, slots.data(), slots.size() * sizeof(LaneSlot), hipMemcpyHostToDevice, s));
+        if (!rviews.empty()) HIP_TRY(ctx, hipMemcpyAsync(d_rviews, rviews.data(), rviews.size() * sizeof(ViewRow), hipMemcpyHostToDevice, s));
+        if (!sviews.empty()) HIP_TRY(ctx, hipMemcpyAsync(d_sviews, sviews.data(), sviews.size() * sizeof(ViewRow), hipMemcpyHostToDevice, s));
         // the launches that do not depend on each other go to distinct streams of the context, behind the uploads
         std::vector<hipStream_t> work;
         for (int li = 0; li < ctx->nlanes; li++) {
@@ -431,26 +503,41 @@ int decompress_images(felics_ctx *ctx, size_t n, const void *d_streams, const ui
                 uint32_t lds = 0, epoch0 = 0;
                 uint64_t mx = 0;
                 bool rgb = false;
+                DecodeViews dv{d_rviews + rows16_first + p, false, false};
                 for (size_t k = p; k < p + cnt; k++) {
                     const size_t i = rows16[k];
                     lds = std::max(lds, decode16_lds_bytes(rec[i].W));
                     mx = std::max(mx, npix[i]);
                     rgb = rgb || rec[i].color;
+                    dv.pitched = dv.pitched || pitched(i);
+                    dv.strided = dv.strided || strided(i);
                 }
                 int r = dec16_epoch(ctx, w, epoch0);
                 if (r) return r;
-                HIP_TRY(ctx, launch_decode16_rows(w, st, d_off, d_len, d_rows + rows16_first + p, (uint32_t)cnt, lds, mx, rgb, (uint16_t *)d_pixels,
-                                                  (int32_t *)ctx->dec_planes16.p, (uint32_t *)ctx->dec_table.p, epoch0, d_status));
+                if (vp)
+                    HIP_TRY(ctx, launch_decode16_rows_views(w, st, d_off, d_len, d_rows + rows16_first + p, (uint32_t)cnt, lds, mx, rgb,
+                                                            (int32_t *)ctx->dec_planes16.p, (uint32_t *)ctx->dec_table.p, epoch0, d_status, dv));
+                else
+                    HIP_TRY(ctx, launch_decode16_rows(w, st, d_off, d_len, d_rows + rows16_first + p, (uint32_t)cnt, lds, mx, rgb, (uint16_t *)d_pixels,
+                                                      (int32_t *)ctx->dec_planes16.p, (uint32_t *)ctx->dec_table.p, epoch0, d_status));
             }
         }
         if (nslots8) {
             hipStream_t w = stream_for();
             HIP_TRY(ctx, hipMemsetAsync(ctx->dec_lane_table.p, 0, lt_bytes, w));
             for (int col = 0; col < 2; col++)
-                HIP_TRY(ctx, launch_decode8_lanes_waves(w, st, d_off, d_len, d_waves + lanes[col].first, (uint32_t)lanes[col].cnt, d_slots + slot0[col],
-                                                        col, d_rows + conv.first, (uint32_t)conv.cnt, lanes[1].max_npix, d_pixels,
-                                                        (int16_t *)ctx->dec_planes.p, (uint32_t *)((uint8_t *)ctx->dec_lane_table.p + (col ? lt_gray : 0)),
-                                                        d_status));
+                if (vp)
+                    HIP_TRY(ctx, launch_decode8_lanes_waves_views(w, st, d_off, d_len, d_waves + lanes[col].first, (uint32_t)lanes[col].cnt,
+                                                                  d_slots + slot0[col], col, d_rows + conv.first, (uint32_t)conv.cnt, lanes[1].max_npix,
+                                                                  (int16_t *)ctx->dec_planes.p,
+                                                                  (uint32_t *)((uint8_t *)ctx->dec_lane_table.p + (col ? lt_gray : 0)), d_status,
+                                                                  DecodeViews{d_sviews + slot0[col], lanes[col].pitched, false},
+                                                                  DecodeViews{d_rviews + conv.first, false, conv.strided}));
+                else
+                    HIP_TRY(ctx, launch_decode8_lanes_waves(w, st, d_off, d_len, d_waves + lanes[col].first, (uint32_t)lanes[col].cnt, d_slots + slot0[col],
+                                                            col, d_rows + conv.first, (uint32_t)conv.cnt, lanes[1].max_npix, d_pixels,
+                                                            (int16_t *)ctx->dec_planes.p, (uint32_t *)((uint8_t *)ctx->dec_lane_table.p + (col ? lt_gray : 0)),
+                                                            d_status));
         }
         if (!passes16.empty()) {
             hipStream_t w = stream_for();
@@ -458,16 +545,28 @@ int decompress_images(felics_ctx *ctx, size_t n, const void *d_streams, const ui
                 uint32_t epoch0 = 0;
                 int r = dec16_lanes_epoch(ctx, w, epoch0);
                 if (r) return r;
-                HIP_TRY(ctx, launch_decode16_lanes_waves(w, st, d_off, d_len, d_waves + P.wave_first, (uint32_t)P.wave_cnt, d_slots + P.slot_first, P.col,
-                                                         d_rows + P.conv_first, (uint32_t)P.conv_cnt, P.max_npix, (uint16_t *)d_pixels,
-                                                         (int32_t *)ctx->dec_planes16.p, (uint32_t *)ctx->dec_lane16_table.p, epoch0, d_status));
+                if (vp)
+                    HIP_TRY(ctx, launch_decode16_lanes_waves_views(w, st, d_off, d_len, d_waves + P.wave_first, (uint32_t)P.wave_cnt, d_slots + P.slot_first,
+                                                                   P.col, d_rows + P.conv_first, (uint32_t)P.conv_cnt, P.max_npix,
+                                                                   (int32_t *)ctx->dec_planes16.p, (uint32_t *)ctx->dec_lane16_table.p, epoch0, d_status,
+                                                                   DecodeViews{d_sviews + P.slot_first, P.pitched, false},
+                                                                   DecodeViews{d_rviews + P.conv_first, false, P.strided}));
+                else
+                    HIP_TRY(ctx, launch_decode16_lanes_waves(w, st, d_off, d_len, d_waves + P.wave_first, (uint32_t)P.wave_cnt, d_slots + P.slot_first, P.col,
+                                                             d_rows + P.conv_first, (uint32_t)P.conv_cnt, P.max_npix, (uint16_t *)d_pixels,
+                                                             (int32_t *)ctx->dec_planes16.p, (uint32_t *)ctx->dec_lane16_table.p, epoch0, d_status));
             }
         }
         for (const Launch &L : classes)
-            HIP_TRY(ctx, launch_decode8_rows(stream_for(), st, d_off, d_len, d_rows + L.first, (uint32_t)L.cnt, L.lds, L.max_npix, L.rgb, d_pixels,
-                                             (int16_t *)ctx->dec_planes.p, d_status));
+            if (vp)
+                HIP_TRY(ctx, launch_decode8_rows_views(stream_for(), st, d_off, d_len, d_rows + L.first, (uint32_t)L.cnt, L.lds, L.max_npix, L.rgb,
+                                                       (int16_t *)ctx->dec_planes.p, d_status, DecodeViews{d_rviews + L.first, L.pitched, L.strided}));
+            else
+                HIP_TRY(ctx, launch_decode8_rows(stream_for(), st, d_off, d_len, d_rows + L.first, (uint32_t)L.cnt, L.lds, L.max_npix, L.rgb, d_pixels,
+                                                 (int16_t *)ctx->dec_planes.p, d_status));
         // the host decoder meanwhile (into frames no kernel writes)
         std::vector<uint8_t> sbuf, pbuf;
+        if (vp && ctx->view_ready && !host.empty()) HIP_TRY(ctx, hipStreamWaitEvent(nullptr, ctx->view_ready, 0));  // (its copies run on the null stream)
         for (size_t i : host) {
             const felics_header want{rec[i].color, rec[i].depth, rec[i].W, rec[i].H};
             const int r = host_decode(ctx, st + offsets[i], lens[i], felics_max_compressed_size(rec[i].W, rec[i].H, rec[i].color, rec[i].depth), want,
@@ -479,6 +578,29 @@ int decompress_images(felics_ctx *ctx, size_t n, const void *d_streams, const ui
         for (size_t k = 0; k < used; k++) {
             HIP_TRY(ctx, hipEventRecord(l0.spine_done[k], work[k]));
             HIP_TRY(ctx, hipStreamWaitEvent(s, l0.spine_done[k], 0));
+        }
+        if (nscat) {
+            // the staged frames through their views: the kernels' (they look at the stream's status on the device) and the host
+            // decoder's (those it decoded)
+            uint32_t row_samples[2] = {0, 0}, max_h[2] = {0, 0};
+            for (size_t i = 0; i < n; i++) {
+                if (status[i] != FELICS_OK || vp->cls[i] != VIEW_SCATTERED || !npix[i]) continue;
+                const felics_view &w = vp->views[i];
+                const uint32_t C = w.color ? 3 : 1, d = w.depth ? 1 : 0;
+                scat[d].push_back(ScatterRow{(uint32_t)i, w.width, w.height, C, (const void *)(uintptr_t)pix_offsets[i],
+                                             ViewRow{w.data, w.row_stride, w.pixel_stride, w.color ? w.channel_stride : 0}});
+                row_samples[d] = (uint32_t)std::min<uint64_t>(std::max<uint64_t>(row_samples[d], (uint64_t)w.width * C), 0xFFFFFFFFu);
+                max_h[d] = std::max(max_h[d], w.height);
+            }
+            ScatterRow *d_scat16 = d_scat + scat[0].size();
+            if (!scat[0].empty()) {
+                HIP_TRY(ctx, hipMemcpyAsync(d_scat, scat[0].data(), scat[0].size() * sizeof(ScatterRow), hipMemcpyHostToDevice, s));
+                HIP_TRY(ctx, launch_scatter_views<uint8_t>(s, d_scat, (uint32_t)scat[0].size(), row_samples[0], max_h[0], d_status));
+            }
+            if (!scat[1].empty()) {
+                HIP_TRY(ctx, hipMemcpyAsync(d_scat16, scat[1].data(), scat[1].size() * sizeof(ScatterRow), hipMemcpyHostToDevice, s));
+                HIP_TRY(ctx, launch_scatter_views<uint16_t>(s, d_scat16, (uint32_t)scat[1].size(), row_samples[1], max_h[1], d_status));
+            }
         }
         HIP_TRY(ctx, hipMemcpyAsync(dev_status.data(), d_status, n * 4, hipMemcpyDeviceToHost, s));
         HIP_TRY(ctx, hipStreamSynchronize(s));
@@ -546,6 +668,36 @@ extern "C" {
 int felics_get_decode_stats(const felics_ctx *ctx, felics_decode_stats *out, size_t out_size) {
     if (!ctx || !out) return FELICS_E_INVALID_ARGUMENT;
     memcpy(out, &ctx->dstats, std::min(out_size, sizeof(felics_decode_stats)));
+    return FELICS_OK;
+}
+
+int felics_get_decode_view_stats(const felics_ctx *ctx, felics_decode_view_stats *out, size_t out_size) {
+    if (!ctx || !out) return FELICS_E_INVALID_ARGUMENT;
+    memcpy(out, &ctx->dvstats, std::min(out_size, sizeof(felics_decode_view_stats)));
+    return FELICS_OK;
+}
+
+int felics_view_writable(const felics_view *v) {
+    if (!v) return FELICS_E_INVALID_ARGUMENT;
+    int64_t lo, hi;
+    const int rc = check_view(*v, lo, hi, false);
+    if (rc || !v->width || !v->height) return rc;
+    // the nested rule: of the axes with more than one step, each stride (by size) at least the whole extent of the one below it
+    struct Axis {
+        unsigned __int128 stride;
+        uint64_t extent;
+    } ax[3];
+    int na = 0;
+    auto mag = [](int64_t s) { return s < 0 ? (unsigned __int128)(-(__int128)s) : (unsigned __int128)s; };
+    if (v->width > 1) ax[na++] = Axis{mag(v->pixel_stride), v->width};
+    if (v->height > 1) ax[na++] = Axis{mag(v->row_stride), v->height};
+    if (v->color == FELICS_COLOR_RGB) ax[na++] = Axis{mag(v->channel_stride), 3};
+    std::sort(ax, ax + na, [](const Axis &a, const Axis &b) { return a.stride < b.stride; });
+    unsigned __int128 least = v->depth == FELICS_DEPTH_16 ? 2 : 1;  // the sample itself is the innermost extent
+    for (int k = 0; k < na; k++) {
+        if (ax[k].stride < least) return FELICS_E_INVALID_ARGUMENT;
+        least = ax[k].stride * ax[k].extent;
+    }
     return FELICS_OK;
 }
 
@@ -705,6 +857,98 @@ int felics_decompress_images_device(felics_ctx *ctx, size_t n, const void *d_str
     if (n > 0xFFFFFFFFull) return fail_all(FELICS_E_INVALID_ARGUMENT);
     if (hipSetDevice(ctx->device) != hipSuccess) return fail_all(hip_fail(ctx, hipGetLastError(), "hipSetDevice"));
     return decompress_images(ctx, n, d_streams, offsets, lens, (uint8_t *)d_pixels, d_pixels_cap, pix_offsets, hdrs, status);
+}
+
+int felics_decompress_views_device(felics_ctx *ctx, size_t n, const void *d_streams, const uint64_t *offsets, const uint64_t *lens,
+                                   const felics_view *views, void *ready_event, felics_header *hdrs, int *status) {
+    if (!ctx || (n && (!d_streams || !offsets || !lens || !views || !status))) return FELICS_E_INVALID_ARGUMENT;
+    auto fail_all = [&](int code) { return fail_call(n, status, hdrs, nullptr, code); };
+    for (size_t i = 0; i < n; i++) {  // every view checked before anything is launched: the first error in view order
+        const int rc = felics_view_writable(&views[i]);
+        if (rc) return fail_all(rc);
+    }
+    if (ctx->failed) return fail_all(FELICS_E_HIP);
+    if (n == 0) return FELICS_OK;
+    if (any_pending(ctx)) return fail_all(FELICS_E_INVALID_ARGUMENT);  // felics_wait_batch first
+    if (n > 0xFFFFFFFFull) return fail_all(FELICS_E_INVALID_ARGUMENT);
+    if (hipSetDevice(ctx->device) != hipSuccess) return fail_all(hip_fail(ctx, hipGetLastError(), "hipSetDevice"));
+    // the class of every view, and the staged frames of the scattered ones (256-byte steps)
+    std::vector<uint8_t> cls(n, VIEW_DENSE);
+    std::vector<uint64_t> stage(n, 0), frame(n, 0);
+    felics_decode_view_stats add = {};
+    uint64_t stage_total = 0, stage_largest = 0;
+    for (size_t i = 0; i < n; i++) {
+        const felics_view &v = views[i];
+        const int64_t size = v.depth == FELICS_DEPTH_16 ? 2 : 1;
+        const bool rgb = v.color == FELICS_COLOR_RGB;
+        const uint64_t npix = (uint64_t)v.width * v.height;
+        add.views++;
+        const bool dense = v.pixel_stride == size * (rgb ? 3 : 1) && v.row_stride == (int64_t)v.width * v.pixel_stride && (!rgb || v.channel_stride == size);
+        if (!npix) {
+            add.dense++;
+        } else if (rows_for_host(v.width, rgb, v.depth)) {
+            cls[i] = VIEW_SCATTERED;
+        } else if (dense) {
+            add.dense++;
+        } else if (rgb || (v.pixel_stride == size && v.row_stride >= (int64_t)v.width * size)) {
+            cls[i] = VIEW_IN_PLACE;
+            add.in_place++;
+        } else {
+            cls[i] = VIEW_SCATTERED;
+        }
+        if (cls[i] == VIEW_SCATTERED) {
+            add.scattered++;
+            frame[i] = (npix * (rgb ? 3 : 1) * size + 255) & ~255ull;
+            stage_total += frame[i];
+            stage_largest = std::max(stage_largest, frame[i]);
+        }
+    }
+    // The staging is bounded as the 16-bit lane tables are: passes of consecutive streams whose staged frames fit a quarter of the free
+    // device memory (the buffer the context already holds counted as free); a single larger frame is a pass of its own.
+    // FELICS_TEST_VIEW_STAGE_BYTES=k: at most k bytes a pass (tests).
+    uint64_t budget = UINT64_MAX;
+    size_t free_b = 0, total_b = 0;
+    if (stage_total > ctx->view_stage.cap && hipMemGetInfo(&free_b, &total_b) == hipSuccess) budget = ((uint64_t)free_b + ctx->view_stage.cap) / 4;
+    if (const char *e = getenv("FELICS_TEST_VIEW_STAGE_BYTES"))
+        if (atoll(e) > 0) budget = (uint64_t)atoll(e);
+    std::vector<size_t> pass_end;
+    uint64_t acc = 0, most = 0;
+    for (size_t i = 0; i < n; i++) {
+        if (acc && acc + frame[i] > budget) {
+            pass_end.push_back(i);
+            acc = 0;
+        }
+        stage[i] = acc;
+        acc += frame[i];
+        most = std::max(most, acc);
+    }
+    pass_end.push_back(n);
+    int rc;
+    if (most && (rc = reserve(ctx, ctx->view_stage, (size_t)most + 64)) != 0) return fail_all(rc);
+    ctx->dvstats.views += add.views;
+    ctx->dvstats.dense += add.dense;
+    ctx->dvstats.in_place += add.in_place;
+    ctx->dvstats.scattered += add.scattered;
+    ctx->view_ready = (hipEvent_t)ready_event;
+    std::vector<uint64_t> addr(n, 0);
+    int first = FELICS_OK;
+    uint64_t table_bytes = 0;
+    size_t i0 = 0;
+    for (size_t i1 : pass_end) {
+        const ViewPlan vp{views + i0, cls.data() + i0, stage.data() + i0};
+        rc = decompress_images(ctx, i1 - i0, d_streams, offsets + i0, lens + i0, nullptr, SIZE_MAX, addr.data() + i0, hdrs ? hdrs + i0 : nullptr,
+                               status + i0, &vp);
+        table_bytes = std::max(table_bytes, ctx->dstats.lanes16_table_bytes);
+        if (rc && !first) first = rc;
+        if (rc == FELICS_E_HIP && ctx->err.size() && i1 < n) {  // (not a stream's status: the call ends here)
+            fail_call(n - i1, status + i1, hdrs ? hdrs + i1 : nullptr, nullptr, rc);
+            break;
+        }
+        i0 = i1;
+    }
+    ctx->dstats.lanes16_table_bytes = table_bytes;
+    ctx->view_ready = nullptr;
+    return first;
 }
 
 }  // extern "C"

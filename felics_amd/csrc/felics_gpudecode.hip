@@ -130,6 +130,11 @@ struct DecUniform {
 struct DecMixed {
     const DecodeRow *rows;
 };
+// DecPitched (felics_decompress_views_device): a DecMixed table whose GRAY rows write where views[row] says -- data is the address
+// of the row's first sample, row_stride the bytes between two of its rows (>= W samples).  RGB rows go to their planes as ever.
+struct DecPitched : DecMixed {
+    const ViewRow *views;
+};
 struct DecView {
     uint32_t img, W, H, color;  // img: the stream's index into offsets / lens / status
     uint64_t out_off, plane_off;
@@ -149,6 +154,10 @@ __device__ __forceinline__ T *dec_frame(const DecUniform &, T *pixels, const Dec
 template <typename T>
 __device__ __forceinline__ T *dec_frame(const DecMixed &, T *pixels, const DecView &v, uint64_t) {
     return reinterpret_cast<T *>(reinterpret_cast<uint8_t *>(pixels) + v.out_off);
+}
+template <typename T>
+__device__ __forceinline__ T *dec_frame(const DecPitched &g, T *, const DecView &, uint64_t) {
+    return reinterpret_cast<T *>(const_cast<void *>(g.views[blockIdx.x].data));
 }
 template <typename T>
 __device__ __forceinline__ T *dec_plane(const DecUniform &, T *planes, const DecView &v, uint32_t nplanes, uint32_t c, uint64_t npix) {
@@ -220,6 +229,9 @@ __global__ __launch_bounds__(64) void k_decode8(const uint8_t *__restrict__ stre
         const bool rgb = dec_rgb(geo, v, planes);
         int16_t *outp = rgb ? dec_plane(geo, planes, v, nplanes, c, npix) : nullptr;
         uint8_t *outg = rgb ? nullptr : dec_frame(geo, pixels, v, npix);
+        // DecPitched: the row's offset in the view, the pitch added in 64 bits once per row (the row above stays in LDS: the view is only written)
+        uint64_t opitch = 0, orow = 0;
+        if constexpr (std::is_same<G, DecPitched>::value) opitch = (uint64_t)geo.views[blockIdx.x].row_stride;
         const int lo_ok = color ? -255 : 0, hi_ok = 255;  // what a sample of this plane can be (Y 0..255, Co / Cg -255..255)
         // rows: cur = the row being decoded, prev = the one above; both in LDS, written 64 samples at a time
         uint32_t x = 0, y = 0;
@@ -303,7 +315,12 @@ __global__ __launch_bounds__(64) void k_decode8(const uint8_t *__restrict__ stre
                 const uint32_t xb = x & ~63u;
                 if (xb + lane <= x) {
                     cur[xb + lane] = (int16_t)rowv;
-                    if (outg)
+                    if constexpr (std::is_same<G, DecPitched>::value) {
+                        if (outg)
+                            outg[orow + xb + lane] = (uint8_t)rowv;  // (xb + lane <= x < W: never the bytes between W and the pitch)
+                        else
+                            outp[(uint64_t)y * W + xb + lane] = (int16_t)rowv;
+                    } else if (outg)
                         outg[(uint64_t)y * W + xb + lane] = (uint8_t)rowv;
                     else
                         outp[(uint64_t)y * W + xb + lane] = (int16_t)rowv;
@@ -317,6 +334,7 @@ __global__ __launch_bounds__(64) void k_decode8(const uint8_t *__restrict__ stre
                 __builtin_amdgcn_wave_barrier();
                 x = 0;
                 y++;
+                if constexpr (std::is_same<G, DecPitched>::value) orow += opitch;
                 int16_t *t = cur;
                 cur = prev;
                 prev = t;
@@ -429,6 +447,10 @@ struct Four<uint8_t> {
     uint32_t v;
     __device__ __forceinline__ void clear() { v = 0; }
     __device__ __forceinline__ void load(const uint8_t *p) { __builtin_memcpy(&v, p, 4); }
+    __device__ __forceinline__ void load_n(const uint8_t *p, uint32_t n) {  // samples 0 .. n - 1 only (n < 4), nothing behind them touched
+        v = 0;
+        for (uint32_t j = 0; j < n; j++) v |= (uint32_t)p[j] << (8u * j);
+    }
     __device__ __forceinline__ void store(uint8_t *p) const { __builtin_memcpy(p, &v, 4); }
     __device__ __forceinline__ int get(uint32_t j) const { return (int)((v >> (8u * j)) & 0xFFu); }
     __device__ __forceinline__ void set(uint32_t j, int s) { v |= (uint32_t)s << (8u * j); }  // (0 <= s <= 255, the field still zero)
@@ -463,6 +485,12 @@ struct LaneUniform {
 struct LaneMixed {
     const LaneWave *waves;
     const LaneSlot *slots;
+};
+// LanePitched (felics_decompress_views_device, gray only): a LaneMixed launch whose lanes write where views[slot] says -- data is the
+// address of the lane's first sample, row_stride the bytes between two of its rows (>= W samples).  The 64 lanes of a wave have 64
+// bases and pitches (per-lane data, as LaneSlot is); (x, y) stays wave-uniform: a wave's views have one shape.
+struct LanePitched : LaneMixed {
+    const ViewRow *views;
 };
 struct LaneView {
     uint32_t W, H, img, slot;  // img: index into offsets / lens / status; slot: the estimator table
@@ -543,6 +571,16 @@ __global__ __launch_bounds__(64) void k_decode8_lanes(const uint8_t *__restrict_
     if (npix == 0) continue;
     uint32_t *tab = table + ((uint64_t)v.slot * NP + plane) * TABLE_DW;
     ST *out = lane_plane<ST>(geo, out_base, v, NP, plane, npix);
+    // LanePitched: this lane's view; the rows lie `pitch` samples apart, and no load or store leaves [0, W) of its row -- the bytes
+    // between a row's end and the pitch are somebody else's (a neighbouring cell of a mosaic: another lane's, another wave's)
+    constexpr bool PITCHED = std::is_same<G, LanePitched>::value;
+    int64_t pitch = 0;
+    if constexpr (PITCHED) {
+        static_assert(!PITCHED || !RGB, "RGB lanes write planes; their views are the conversion kernel's");
+        const ViewRow vr = geo.views[v.slot];
+        out = reinterpret_cast<ST *>(const_cast<void *>(vr.data));
+        pitch = vr.row_stride / (int64_t)sizeof(ST);
+    }
     // (x, y) and everything derived from them alone is wave-uniform: every stream has the same shape
     int left = 0, left2 = 0;
     Four<ST> up4, up4_next, out4;
@@ -554,17 +592,29 @@ __global__ __launch_bounds__(64) void k_decode8_lanes(const uint8_t *__restrict_
     for (uint32_t y = 0; y < H; y++) {
       ST *row = out + (uint64_t)y * W;  // this row of the stream's plane, and the one above it
       const ST *prow = row - W;
+      if constexpr (PITCHED) {
+          row = out + (int64_t)y * pitch;
+          prow = row - pitch;
+      }
       if (y > 0) {
           up4.load(prow);                   // row above, samples 0 .. 3 (later groups are asked for four samples ahead)
           if (4 < W) up4_next.load(prow + 4);
           // second neighbour of a row's first pixel (misc.rs:14-23): two rows up, or above-right in row 1
-          first_col2 = y >= 2 ? (int)prow[-(int64_t)W] : (W > 1 ? up4.get(1) : 0);
+          if constexpr (PITCHED)
+              first_col2 = y >= 2 ? (int)prow[-pitch] : up4.get(1);  // (W >= 8)
+          else
+              first_col2 = y >= 2 ? (int)prow[-(int64_t)W] : (W > 1 ? up4.get(1) : 0);
       }
       for (uint32_t x = 0; x < W; x++) {
         const uint32_t xs = x & 3u;
         if (xs == 0 && y > 0 && x != 0) {
             up4 = up4_next;
-            if (x + 4 < W) up4_next.load(prow + x + 4);
+            if constexpr (PITCHED) {  // (wave-uniform: x and W) the row's last group may be short: sample by sample, never past W
+                if (x + 8 <= W) up4_next.load(prow + x + 4);
+                else if (x + 4 < W) up4_next.load_n(prow + x + 4, W - (x + 4));
+            } else if (x + 4 < W) {
+                up4_next.load(prow + x + 4);
+            }
         }
         int pv;
         if (y == 0 && x < 2) {
@@ -684,6 +734,10 @@ __global__ __launch_bounds__(64) void k_decode8_lanes(const uint8_t *__restrict_
 struct ConvUniform {
     uint32_t npix;
 };
+// ConvStrided (felics_decompress_views_device): a DecMixed table whose RGB rows are written through views[row], any strides.
+struct ConvStrided : DecMixed {
+    const ViewRow *views;
+};
 template <typename P, typename T>
 struct ConvView {
     uint32_t img, npix;
@@ -719,14 +773,33 @@ __global__ __launch_bounds__(256) void k_ycocg8_to_rgb(const int16_t *__restrict
     const int16_t *pl = cv.pl;
     uint8_t *dst = cv.dst;
     bool bad = false;
-    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < npix; i += gridDim.x * blockDim.x) {
-        const int yv = pl[i], co = pl[(uint64_t)npix + i], cg = pl[2ull * npix + i];
-        const int t = yv - cg / 2;  // `/` truncates toward zero like Rust's
-        const int g = cg + t, b = t - co / 2, r = b + co;
-        if ((r | g | b) < 0 || r > 255 || g > 255 || b > 255) bad = true;
-        dst[(uint64_t)i * 3] = (uint8_t)r;
-        dst[(uint64_t)i * 3 + 1] = (uint8_t)g;
-        dst[(uint64_t)i * 3 + 2] = (uint8_t)b;
+    if constexpr (std::is_same<G, ConvStrided>::value) {
+        // Sample by sample through the view's strides: three one-byte stores per pixel (what the dense loop below issues as well), so
+        // whatever lies between the samples -- an alpha byte, the rest of a pitch, another cell, another plane -- is never stored to.
+        const ViewRow vr = geo.views[blockIdx.y];
+        const uint32_t W = geo.rows[blockIdx.y].W;
+        uint8_t *base = reinterpret_cast<uint8_t *>(const_cast<void *>(vr.data));
+        for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < npix; i += gridDim.x * blockDim.x) {
+            const int yv = pl[i], co = pl[(uint64_t)npix + i], cg = pl[2ull * npix + i];
+            const int t = yv - cg / 2;
+            const int g = cg + t, b = t - co / 2, r = b + co;
+            if ((r | g | b) < 0 || r > 255 || g > 255 || b > 255) bad = true;
+            const uint32_t y = i / W, x = i - y * W;
+            uint8_t *p = base + (int64_t)y * vr.row_stride + (int64_t)x * vr.pixel_stride;
+            p[0] = (uint8_t)r;
+            p[vr.channel_stride] = (uint8_t)g;
+            p[2 * vr.channel_stride] = (uint8_t)b;
+        }
+    } else {
+        for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < npix; i += gridDim.x * blockDim.x) {
+            const int yv = pl[i], co = pl[(uint64_t)npix + i], cg = pl[2ull * npix + i];
+            const int t = yv - cg / 2;  // `/` truncates toward zero like Rust's
+            const int g = cg + t, b = t - co / 2, r = b + co;
+            if ((r | g | b) < 0 || r > 255 || g > 255 || b > 255) bad = true;
+            dst[(uint64_t)i * 3] = (uint8_t)r;
+            dst[(uint64_t)i * 3 + 1] = (uint8_t)g;
+            dst[(uint64_t)i * 3 + 2] = (uint8_t)b;
+        }
     }
     if (bad) atomicCAS(&status[img], FELICS_OK, FELICS_E_INVALID_VALUE);
 }
@@ -805,6 +878,8 @@ __global__ __launch_bounds__(64) void k_decode16(const uint8_t *__restrict__ str
         const bool rgb = dec_rgb(geo, v, planes);
         int32_t *outp = rgb ? dec_plane(geo, planes, v, nplanes, c, npix) : nullptr;
         uint16_t *outg = rgb ? nullptr : dec_frame(geo, pixels, v, npix);
+        uint64_t opitch = 0, orow = 0;  // DecPitched, in samples (strides are even at depth 16)
+        if constexpr (std::is_same<G, DecPitched>::value) opitch = (uint64_t)geo.views[blockIdx.x].row_stride / 2u;
         const int lo_ok = (color && c > 0) ? -65535 : 0, hi_ok = 65535;  // Y 0..65535, Co / Cg -65535..65535
         uint32_t x = 0, y = 0;
         int32_t *cur = rows, *prev = rows + rstride;
@@ -889,7 +964,12 @@ __global__ __launch_bounds__(64) void k_decode16(const uint8_t *__restrict__ str
                 const uint32_t xb = x & ~63u;
                 if (xb + lane <= x) {
                     cur[xb + lane] = rowv;
-                    if (outg)
+                    if constexpr (std::is_same<G, DecPitched>::value) {
+                        if (outg)
+                            outg[orow + xb + lane] = (uint16_t)rowv;  // (xb + lane <= x < W)
+                        else
+                            outp[(uint64_t)y * W + xb + lane] = rowv;
+                    } else if (outg)
                         outg[(uint64_t)y * W + xb + lane] = (uint16_t)rowv;
                     else
                         outp[(uint64_t)y * W + xb + lane] = rowv;
@@ -903,6 +983,7 @@ __global__ __launch_bounds__(64) void k_decode16(const uint8_t *__restrict__ str
                 __builtin_amdgcn_wave_barrier();
                 x = 0;
                 y++;
+                if constexpr (std::is_same<G, DecPitched>::value) orow += opitch;
                 int32_t *t = cur;
                 cur = prev;
                 prev = t;
@@ -926,14 +1007,32 @@ __global__ __launch_bounds__(256) void k_ycocg16_to_rgb(const int32_t *__restric
     const int32_t *pl = cv.pl;
     uint16_t *dst = cv.dst;
     bool bad = false;
-    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < npix; i += gridDim.x * blockDim.x) {
-        const int yv = pl[i], co = pl[(uint64_t)npix + i], cg = pl[2ull * npix + i];
-        const int t = yv - cg / 2;  // `/` truncates toward zero like Rust's
-        const int g = cg + t, b = t - co / 2, r = b + co;
-        if ((r | g | b) < 0 || r > 65535 || g > 65535 || b > 65535) bad = true;
-        dst[(uint64_t)i * 3] = (uint16_t)r;
-        dst[(uint64_t)i * 3 + 1] = (uint16_t)g;
-        dst[(uint64_t)i * 3 + 2] = (uint16_t)b;
+    if constexpr (std::is_same<G, ConvStrided>::value) {
+        // (as k_ycocg8_to_rgb: one two-byte store per sample; addresses and strides are even)
+        const ViewRow vr = geo.views[blockIdx.y];
+        const uint32_t W = geo.rows[blockIdx.y].W;
+        uint8_t *base = reinterpret_cast<uint8_t *>(const_cast<void *>(vr.data));
+        for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < npix; i += gridDim.x * blockDim.x) {
+            const int yv = pl[i], co = pl[(uint64_t)npix + i], cg = pl[2ull * npix + i];
+            const int t = yv - cg / 2;
+            const int g = cg + t, b = t - co / 2, r = b + co;
+            if ((r | g | b) < 0 || r > 65535 || g > 65535 || b > 65535) bad = true;
+            const uint32_t y = i / W, x = i - y * W;
+            uint8_t *p = base + (int64_t)y * vr.row_stride + (int64_t)x * vr.pixel_stride;
+            *reinterpret_cast<uint16_t *>(p) = (uint16_t)r;
+            *reinterpret_cast<uint16_t *>(p + vr.channel_stride) = (uint16_t)g;
+            *reinterpret_cast<uint16_t *>(p + 2 * vr.channel_stride) = (uint16_t)b;
+        }
+    } else {
+        for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < npix; i += gridDim.x * blockDim.x) {
+            const int yv = pl[i], co = pl[(uint64_t)npix + i], cg = pl[2ull * npix + i];
+            const int t = yv - cg / 2;  // `/` truncates toward zero like Rust's
+            const int g = cg + t, b = t - co / 2, r = b + co;
+            if ((r | g | b) < 0 || r > 65535 || g > 65535 || b > 65535) bad = true;
+            dst[(uint64_t)i * 3] = (uint16_t)r;
+            dst[(uint64_t)i * 3 + 1] = (uint16_t)g;
+            dst[(uint64_t)i * 3 + 2] = (uint16_t)b;
+        }
     }
     if (bad) atomicCAS(&status[img], FELICS_OK, FELICS_E_INVALID_VALUE);
 }
@@ -977,6 +1076,10 @@ struct Four<uint16_t> {
         __builtin_memcpy(v, p, 8);
         lo = v[0];
         hi = v[1];
+    }
+    __device__ __forceinline__ void load_n(const uint16_t *p, uint32_t n) {  // samples 0 .. n - 1 only (n < 4)
+        lo = hi = 0;
+        for (uint32_t j = 0; j < n; j++) set(j, (int)p[j]);
     }
     __device__ __forceinline__ void store(uint16_t *p) const {
         const uint32_t v[2] = {lo, hi};
@@ -1065,6 +1168,16 @@ __global__ __launch_bounds__(64) void k_decode16_lanes(const uint8_t *__restrict
     uint4 *tab = tab0 + (uint64_t)plane * rows * 4u;
     const uint32_t epoch = epoch0 + plane;  // KEstimator::new: rows of other epochs are empty
     ST *out = lane_plane<ST>(geo, out_base, v, NP, plane, npix);
+    // LanePitched: this lane's view; the rows lie `pitch` samples apart, and no load or store leaves [0, W) of its row -- the bytes
+    // between a row's end and the pitch are somebody else's (a neighbouring cell of a mosaic: another lane's, another wave's)
+    constexpr bool PITCHED = std::is_same<G, LanePitched>::value;
+    int64_t pitch = 0;
+    if constexpr (PITCHED) {
+        static_assert(!PITCHED || !RGB, "RGB lanes write planes; their views are the conversion kernel's");
+        const ViewRow vr = geo.views[v.slot];
+        out = reinterpret_cast<ST *>(const_cast<void *>(vr.data));
+        pitch = vr.row_stride / (int64_t)sizeof(ST);
+    }
     const int lo_ok = (RGB && plane > 0) ? -65535 : 0, hi_ok = 65535;  // Y 0..65535, Co / Cg -65535..65535
     int left = 0, left2 = 0;
     Four<ST> up4, up4_next, out4;
@@ -1076,16 +1189,28 @@ __global__ __launch_bounds__(64) void k_decode16_lanes(const uint8_t *__restrict
     for (uint32_t y = 0; y < H; y++) {
       ST *row = out + (uint64_t)y * W;
       const ST *prow = row - W;
+      if constexpr (PITCHED) {
+          row = out + (int64_t)y * pitch;
+          prow = row - pitch;
+      }
       if (y > 0) {
           up4.load(prow);
           if (4 < W) up4_next.load(prow + 4);
-          first_col2 = y >= 2 ? (int)prow[-(int64_t)W] : (W > 1 ? up4.get(1) : 0);
+          if constexpr (PITCHED)
+              first_col2 = y >= 2 ? (int)prow[-pitch] : up4.get(1);  // (W >= 8)
+          else
+              first_col2 = y >= 2 ? (int)prow[-(int64_t)W] : (W > 1 ? up4.get(1) : 0);
       }
       for (uint32_t x = 0; x < W; x++) {
         const uint32_t xs = x & 3u;
         if (xs == 0 && y > 0 && x != 0) {
             up4 = up4_next;
-            if (x + 4 < W) up4_next.load(prow + x + 4);
+            if constexpr (PITCHED) {  // (wave-uniform: x and W) the row's last group may be short: sample by sample, never past W
+                if (x + 8 <= W) up4_next.load(prow + x + 4);
+                else if (x + 4 < W) up4_next.load_n(prow + x + 4, W - (x + 4));
+            } else if (x + 4 < W) {
+                up4_next.load(prow + x + 4);
+            }
         }
         int pv;
         if (y == 0 && x < 2) {
@@ -1404,6 +1529,138 @@ hipError_t launch_decode16_rows(hipStream_t s, const uint8_t *streams, const uin
     hipLaunchKernelGGL(k_decode16<DecMixed>, dim3(n), dim3(64), lds, s, streams, offsets, lens, DecMixed{rows}, pixels, planes, table, epoch0,
                        status);
     if (any_rgb) launch_conv_rows(s, rows, n, max_npix, planes, pixels, status);
+    return hipGetLastError();
+}
+
+// ------------------------------------------------------------------------------------------
+// felics_decompress_views_device: the launches above with the pitched / strided policies where a launch needs them.
+// ------------------------------------------------------------------------------------------
+
+namespace {
+
+// the RGB conversion of `n` rows through their views (ConvStrided), or, where every row is the dense layout, launch_conv_rows as it is
+template <typename P, typename T>
+void launch_conv_views(hipStream_t s, const DecodeRow *rows, uint32_t n, uint64_t max_npix, P *planes, int *status, const DecodeViews &cv) {
+    if (!cv.strided) return launch_conv_rows(s, rows, n, max_npix, planes, (T *)nullptr, status);
+    const uint32_t bx = (uint32_t)std::min<uint64_t>((max_npix + 255) / 256, 1024u);
+    if (!bx) return;
+    for (uint32_t r0 = 0; r0 < n; r0 += 65535u) {
+        const uint32_t cnt = std::min(n - r0, 65535u);
+        const ConvStrided g{{rows + r0}, cv.views + r0};
+        if constexpr (sizeof(T) == 1)
+            hipLaunchKernelGGL(k_ycocg8_to_rgb<ConvStrided>, dim3(bx, cnt), dim3(256), 0, s, planes, (T *)nullptr, g, status);
+        else
+            hipLaunchKernelGGL(k_ycocg16_to_rgb<ConvStrided>, dim3(bx, cnt), dim3(256), 0, s, planes, (T *)nullptr, g, status);
+    }
+}
+
+// k_scatter_view: the inverse of k_gather_view (felics_wide.hip) for a table of frames -- a dense frame in the context's staging
+// buffer written through its view's strides, sample by sample.  blockIdx.z names the table row, a workgroup row (blockIdx.y, strided)
+// an image row, consecutive threads consecutive samples of it: the reads are coalesced, the writes as far as the view allows.
+template <typename T>
+__global__ __launch_bounds__(256) void k_scatter_view(const ScatterRow *__restrict__ rows, const int *__restrict__ status) {
+    const ScatterRow r = rows[blockIdx.z];
+    if (status[r.stream] != FELICS_OK) return;
+    uint8_t *data = reinterpret_cast<uint8_t *>(const_cast<void *>(r.v.data));
+    const uint64_t row = (uint64_t)r.W * r.C;  // samples
+    for (uint32_t y = blockIdx.y; y < r.H; y += gridDim.y) {
+        uint8_t *dst = data + (int64_t)y * r.v.row_stride;
+        const T *src = reinterpret_cast<const T *>(r.src) + (uint64_t)y * row;
+        for (uint64_t j = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; j < row; j += (uint64_t)gridDim.x * blockDim.x) {
+            const uint64_t x = r.C == 1 ? j : j / 3u;
+            const int64_t c = (int64_t)(j - x * r.C);
+            *reinterpret_cast<T *>(dst + (int64_t)x * r.v.pixel_stride + c * r.v.channel_stride) = src[j];
+        }
+    }
+}
+
+}  // namespace
+
+template <typename T>
+hipError_t launch_scatter_views(hipStream_t s, const ScatterRow *rows, uint32_t n, uint32_t max_row_samples, uint32_t max_h, const int *status) {
+    if (!n || !max_row_samples || !max_h) return hipSuccess;
+    const uint32_t bx = std::max(1u, std::min((max_row_samples + 255u) / 256u, 64u));
+    const uint32_t by = std::min(max_h, 1024u);
+    for (uint32_t r0 = 0; r0 < n; r0 += 65535u)
+        hipLaunchKernelGGL((k_scatter_view<T>), dim3(bx, by, std::min(n - r0, 65535u)), dim3(256), 0, s, rows + r0, status);
+    return hipGetLastError();
+}
+template hipError_t launch_scatter_views<uint8_t>(hipStream_t, const ScatterRow *, uint32_t, uint32_t, uint32_t, const int *);
+template hipError_t launch_scatter_views<uint16_t>(hipStream_t, const ScatterRow *, uint32_t, uint32_t, uint32_t, const int *);
+
+hipError_t launch_decode8_rows_views(hipStream_t s, const uint8_t *streams, const uint64_t *offsets, const uint64_t *lens, const DecodeRow *rows,
+                                     uint32_t n, uint32_t lds, uint64_t max_npix, bool any_rgb, int16_t *planes, int *status, const DecodeViews &dv) {
+    if (n == 0) return hipSuccess;
+    const void *kernel = dv.pitched ? reinterpret_cast<const void *>(&k_decode8<DecPitched>) : reinterpret_cast<const void *>(&k_decode8<DecMixed>);
+    if (lds > 64u * 1024u) {
+        const hipError_t e = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)DECODE_LDS_LIMIT);
+        if (e != hipSuccess) return e;
+    }
+    if (dv.pitched)
+        hipLaunchKernelGGL(k_decode8<DecPitched>, dim3(n), dim3(64), lds, s, streams, offsets, lens, DecPitched{{rows}, dv.views}, (uint8_t *)nullptr,
+                           planes, status);
+    else
+        hipLaunchKernelGGL(k_decode8<DecMixed>, dim3(n), dim3(64), lds, s, streams, offsets, lens, DecMixed{rows}, (uint8_t *)nullptr, planes, status);
+    if (any_rgb) launch_conv_views<int16_t, uint8_t>(s, rows, n, max_npix, planes, status, dv);
+    return hipGetLastError();
+}
+
+hipError_t launch_decode16_rows_views(hipStream_t s, const uint8_t *streams, const uint64_t *offsets, const uint64_t *lens, const DecodeRow *rows,
+                                      uint32_t n, uint32_t lds, uint64_t max_npix, bool any_rgb, int32_t *planes, uint32_t *table, uint32_t epoch0,
+                                      int *status, const DecodeViews &dv) {
+    if (n == 0) return hipSuccess;
+    const void *kernel = dv.pitched ? reinterpret_cast<const void *>(&k_decode16<DecPitched>) : reinterpret_cast<const void *>(&k_decode16<DecMixed>);
+    if (lds > 64u * 1024u) {
+        const hipError_t e = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)DECODE_LDS_LIMIT);
+        if (e != hipSuccess) return e;
+    }
+    if (dv.pitched)
+        hipLaunchKernelGGL(k_decode16<DecPitched>, dim3(n), dim3(64), lds, s, streams, offsets, lens, DecPitched{{rows}, dv.views},
+                           (uint16_t *)nullptr, planes, table, epoch0, status);
+    else
+        hipLaunchKernelGGL(k_decode16<DecMixed>, dim3(n), dim3(64), lds, s, streams, offsets, lens, DecMixed{rows}, (uint16_t *)nullptr, planes, table,
+                           epoch0, status);
+    if (any_rgb) launch_conv_views<int32_t, uint16_t>(s, rows, n, max_npix, planes, status, dv);
+    return hipGetLastError();
+}
+
+hipError_t launch_decode8_lanes_waves_views(hipStream_t s, const uint8_t *streams, const uint64_t *offsets, const uint64_t *lens, const LaneWave *waves,
+                                            uint32_t nwaves, const LaneSlot *slots, uint32_t color, const DecodeRow *conv, uint32_t nconv,
+                                            uint64_t max_npix, int16_t *planes, uint32_t *table, int *status, const DecodeViews &dv,
+                                            const DecodeViews &cv) {
+    if (nwaves == 0) return hipSuccess;
+    if (!color) {
+        if (dv.pitched)
+            hipLaunchKernelGGL((k_decode8_lanes<false, LanePitched>), dim3(nwaves), dim3(64), 0, s, streams, offsets, lens,
+                               LanePitched{{waves, slots}, dv.views}, (void *)nullptr, table, status);
+        else
+            hipLaunchKernelGGL((k_decode8_lanes<false, LaneMixed>), dim3(nwaves), dim3(64), 0, s, streams, offsets, lens, LaneMixed{waves, slots},
+                               (void *)nullptr, table, status);
+        return hipGetLastError();
+    }
+    hipLaunchKernelGGL((k_decode8_lanes<true, LaneMixed>), dim3(nwaves), dim3(64), 0, s, streams, offsets, lens, LaneMixed{waves, slots},
+                       (void *)planes, table, status);
+    launch_conv_views<int16_t, uint8_t>(s, conv, nconv, max_npix, planes, status, cv);
+    return hipGetLastError();
+}
+
+hipError_t launch_decode16_lanes_waves_views(hipStream_t s, const uint8_t *streams, const uint64_t *offsets, const uint64_t *lens, const LaneWave *waves,
+                                             uint32_t nwaves, const LaneSlot *slots, uint32_t color, const DecodeRow *conv, uint32_t nconv,
+                                             uint64_t max_npix, int32_t *planes, uint32_t *table, uint32_t epoch0, int *status,
+                                             const DecodeViews &dv, const DecodeViews &cv) {
+    if (nwaves == 0) return hipSuccess;
+    if (!color) {
+        if (dv.pitched)
+            hipLaunchKernelGGL((k_decode16_lanes<false, LanePitched>), dim3(nwaves), dim3(64), 0, s, streams, offsets, lens,
+                               LanePitched{{waves, slots}, dv.views}, (void *)nullptr, reinterpret_cast<uint4 *>(table), epoch0, status);
+        else
+            hipLaunchKernelGGL((k_decode16_lanes<false, LaneMixed>), dim3(nwaves), dim3(64), 0, s, streams, offsets, lens, LaneMixed{waves, slots},
+                               (void *)nullptr, reinterpret_cast<uint4 *>(table), epoch0, status);
+        return hipGetLastError();
+    }
+    hipLaunchKernelGGL((k_decode16_lanes<true, LaneMixed>), dim3(nwaves), dim3(64), 0, s, streams, offsets, lens, LaneMixed{waves, slots},
+                       (void *)planes, reinterpret_cast<uint4 *>(table), epoch0, status);
+    launch_conv_views<int32_t, uint16_t>(s, conv, nconv, max_npix, planes, status, cv);
     return hipGetLastError();
 }
 

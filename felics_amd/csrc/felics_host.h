@@ -164,6 +164,10 @@ struct felics_ctx {
     DevBuf dec_lane16_table;      // 16-bit streams decoded 64 to a wave: their hashed estimator tables (felics_lanetable.h), zeroed once, rows tagged with an epoch
     uint32_t dec_lane16_epoch = 0;  // last epoch handed out on dec_lane16_table (three per launch, 1 .. DEC16L_EPOCH_MAX)
     felics_decode_stats dstats = {};  // felics_get_decode_stats
+    // felics_decompress_views_device: view_ready is its ready event too (every stream waits for it before it first reads a stream byte
+    // or writes a view: wait_ready), view_stage holds the dense frames of its scattered class, dvstats the counts of
+    // felics_get_decode_view_stats
+    felics_decode_view_stats dvstats = {};
 };
 
 namespace felics {
@@ -186,6 +190,13 @@ void collect_timing(felics_ctx *ctx, Lane &l);
 int check_args(uint32_t w, uint32_t h, int color, int depth);
 void header_bytes(uint8_t *o, uint32_t w, uint32_t h, int color, int depth);
 bool any_pending(const felics_ctx *ctx);
+
+// ---- felics_mixed.cpp
+// A view's checks (felics_view_extent's) and the hull [lo, hi) of its samples' bytes relative to data.  encode_limits: the size
+// limits of felics_compress_images as well (FELICS_E_UNSUPPORTED); the decoder has its own.
+int check_view(const felics_view &v, int64_t &lo, int64_t &hi, bool encode_limits = true);
+// the caller's ready event (ctx->view_ready, if any) in front of whatever is queued on s next
+int wait_ready(felics_ctx *ctx, hipStream_t s);
 
 // ---- felics_encode.cpp
 struct SlotOutcome;

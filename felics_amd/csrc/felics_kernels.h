@@ -326,6 +326,41 @@ hipError_t launch_decode16_lanes_waves(hipStream_t s, const uint8_t *streams, co
 hipError_t launch_decode16_rows(hipStream_t s, const uint8_t *streams, const uint64_t *offsets, const uint64_t *lens, const DecodeRow *rows,
                                 uint32_t n, uint32_t lds, uint64_t max_npix, bool any_rgb, uint16_t *pixels, int32_t *planes, uint32_t *table,
                                 uint32_t epoch0, int *status);
+// ---- Decoding into views (felics_decompress_views_device).  The tables above stay as they are; a launch whose streams write through
+// views gets a PARALLEL table of ViewRow, one per DecodeRow (views[j] belongs to rows[j]) or per LaneSlot (views[j] to slots[j]):
+//   gray  : data = the first sample's address, row_stride = the pitch (>= W samples; the other strides are unused) -- the pitched
+//           policies DecPitched / LanePitched, for surfaces and crops written where they lie;
+//   RGB   : the view's four fields as the caller gave them -- the conversion kernels' ConvStrided policy (any strides).
+// pitched / strided say whether the launch needs those policies at all: without them it is the launch above, views unused, and the
+// rows' and slots' out_off are absolute addresses (`pixels` = nullptr).
+struct DecodeViews {
+    const ViewRow *views = nullptr;
+    bool pitched = false;   // a gray row / slot of the launch has a pitch other than its width
+    bool strided = false;   // an RGB row of the launch is not the dense interleaved layout
+};
+hipError_t launch_decode8_rows_views(hipStream_t s, const uint8_t *streams, const uint64_t *offsets, const uint64_t *lens, const DecodeRow *rows,
+                                     uint32_t n, uint32_t lds, uint64_t max_npix, bool any_rgb, int16_t *planes, int *status, const DecodeViews &dv);
+hipError_t launch_decode16_rows_views(hipStream_t s, const uint8_t *streams, const uint64_t *offsets, const uint64_t *lens, const DecodeRow *rows,
+                                      uint32_t n, uint32_t lds, uint64_t max_npix, bool any_rgb, int32_t *planes, uint32_t *table, uint32_t epoch0,
+                                      int *status, const DecodeViews &dv);
+// lane form: dv.views is per slot for the gray launch (pitched), cv.views per conversion row for the RGB one (strided)
+hipError_t launch_decode8_lanes_waves_views(hipStream_t s, const uint8_t *streams, const uint64_t *offsets, const uint64_t *lens, const LaneWave *waves,
+                                            uint32_t nwaves, const LaneSlot *slots, uint32_t color, const DecodeRow *conv, uint32_t nconv,
+                                            uint64_t max_npix, int16_t *planes, uint32_t *table, int *status, const DecodeViews &dv,
+                                            const DecodeViews &cv);
+hipError_t launch_decode16_lanes_waves_views(hipStream_t s, const uint8_t *streams, const uint64_t *offsets, const uint64_t *lens, const LaneWave *waves,
+                                             uint32_t nwaves, const LaneSlot *slots, uint32_t color, const DecodeRow *conv, uint32_t nconv,
+                                             uint64_t max_npix, int32_t *planes, uint32_t *table, uint32_t epoch0, int *status,
+                                             const DecodeViews &dv, const DecodeViews &cv);
+// A dense frame (W * H * C samples of T at src) written through a view: the inverse of launch_gather_view, for a whole table in one
+// launch per sample type.  Row j is skipped unless status[rows[j].stream] == FELICS_OK.
+struct ScatterRow {
+    uint32_t stream, W, H, C;
+    const void *src;
+    ViewRow v;
+};
+template <typename T>
+hipError_t launch_scatter_views(hipStream_t s, const ScatterRow *rows, uint32_t n, uint32_t max_row_samples, uint32_t max_h, const int *status);
 
 // ---- 16-bit samples (felics_wide.hip): contexts 0..131070 and 15 Rice parameters (traits.rs:35-43).
 // The events of a batch are compacted into 64-bit records {context, Rice operand, sample index in its plane},

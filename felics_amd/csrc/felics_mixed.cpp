@@ -31,12 +31,6 @@ struct MixImage {
     ViewRow vr = {};
 };
 
-// The caller's ready event in front of a stream's first access to a view or to the output (felics_compress_views_device).
-int wait_ready(felics_ctx *ctx, hipStream_t s) {
-    if (ctx->view_ready) HIP_TRY(ctx, hipStreamWaitEvent(s, ctx->view_ready, 0));
-    return FELICS_OK;
-}
-
 // Image m as a dense frame at dst: a copy, or the gather of its view (counted: felics_view_stats::bytes_staged).
 int stage_frame(felics_ctx *ctx, hipStream_t s, void *dst, const MixImage &m) {
     if (!m.frame_bytes) return FELICS_OK;
@@ -465,8 +459,16 @@ int images_device(felics_ctx *ctx, const std::vector<MixImage> &im, uint8_t *d_o
     return FELICS_OK;
 }
 
+}  // namespace
+
+// The caller's ready event in front of a stream's first access to a view or to the output (felics_compress_views_device).
+int wait_ready(felics_ctx *ctx, hipStream_t s) {
+    if (ctx->view_ready) HIP_TRY(ctx, hipStreamWaitEvent(s, ctx->view_ready, 0));
+    return FELICS_OK;
+}
+
 // A view's checks (felics_view_extent and felics_compress_views_device alike) and the hull of its samples' bytes relative to data.
-int check_view(const felics_view &v, int64_t &lo, int64_t &hi) {
+int check_view(const felics_view &v, int64_t &lo, int64_t &hi, bool encode_limits) {
     lo = hi = 0;
     int rc = check_args(v.width, v.height, v.color, v.depth);
     if (rc) return rc;
@@ -476,8 +478,8 @@ int check_view(const felics_view &v, int64_t &lo, int64_t &hi) {
     if (!v.data && npix) return FELICS_E_INVALID_ARGUMENT;
     if (bytes == 2 && (((uintptr_t)v.data | (uint64_t)v.row_stride | (uint64_t)v.pixel_stride | (planes == 3 ? (uint64_t)v.channel_stride : 0u)) & 1u))
         return FELICS_E_INVALID_ARGUMENT;
-    if (npix * planes >= 0xE0000000ull) return FELICS_E_UNSUPPORTED;
-    if (v.depth == FELICS_DEPTH_16 && npix > WIDE_MAX_PLANE_PIXELS) return FELICS_E_UNSUPPORTED;
+    if (encode_limits && npix * planes >= 0xE0000000ull) return FELICS_E_UNSUPPORTED;
+    if (encode_limits && v.depth == FELICS_DEPTH_16 && npix > WIDE_MAX_PLANE_PIXELS) return FELICS_E_UNSUPPORTED;
     if (!npix) return FELICS_OK;
     __int128 l = 0, h = bytes;
     const int64_t steps[3] = {(int64_t)v.height - 1, (int64_t)v.width - 1, (int64_t)planes - 1};
@@ -491,8 +493,6 @@ int check_view(const felics_view &v, int64_t &lo, int64_t &hi) {
     hi = (int64_t)h;
     return FELICS_OK;
 }
-
-}  // namespace
 
 }  // namespace felics
 

@@ -285,6 +285,65 @@ int felics_get_decode_stats(const felics_ctx *ctx, felics_decode_stats *out, siz
  * 16-bit streams whatever the count. */
 uint32_t felics_decode_lanes_min_streams(int depth, int color);
 
+/* felics_decompress_images_device into views: stream i (at d_streams + offsets[i], lens[i] bytes) is decoded straight into views[i]
+ * -- sample (x, y, c) of the decoded image lands at data + y * row_stride + x * pixel_stride + c * channel_stride, sample for sample
+ * what felics_decompress yields for that stream.  felics_view is the encoder's, unchanged; its `data` is `const void *`, and THIS CALL
+ * WRITES THROUGH IT.  The tiles of a loader go where they are wanted -- the images of an N x C x H x W batch tensor, the cells of a
+ * mosaic, a pitched or RGBA surface the next kernel or a display owns -- with no second buffer and no re-layout pass.  The reference
+ * has no counterpart (its decoder returns a fresh `ImageBuffer`, compression.rs:420-441).
+ * Everything felics_decompress_images_device says holds unless named here: per-stream headers (hdrs, optional) and status[] filled on
+ * every return, one bad stream does not fail the others, the device header check and its "header claims more than the stream
+ * holds" rule, the same stream may be referenced several times, refused while a ticket is outstanding, FELICS_E_HIP on a failed
+ * context, n = 0 returns FELICS_OK, the first non-zero status is returned.  offsets / lens / views / hdrs / status are HOST arrays.
+ *   Checked before anything is launched (the first error in view order is returned and put in every status[i]):
+ *     - every view as felics_view_extent checks it (enums, NULL data only for a zero-sized view, even addresses and strides at
+ *       depth 16, an extent that fits 64 bits) -- without the encoder's size limits: the decoder's are those of the mixed call;
+ *     - a written view must not alias itself.  Of the axes whose extent exceeds 1 (x: width, y: height, c: 3 for RGB), sorted by
+ *       |stride| into a1 <= a2 <= a3, |stride(a1)| >= the sample size and |stride(a(k+1))| >= |stride(ak)| * extent(ak) must hold;
+ *       anything else, zero strides included, is FELICS_E_INVALID_ARGUMENT (felics_view_writable gives the code without a context).
+ *       The rule admits interleaved, BGR, RGBA, planar, bottom-up, crops and every-other-column views.  It is SUFFICIENT, NOT
+ *       NECESSARY: some layouts whose samples do not share bytes (interleaved strides that are not nested) are refused.
+ *   NOT checked, the caller's contract: the views of one call share no sample with each other, nor with the streams (the cells of a
+ *   mosaic have interleaved hulls, so hulls cannot be compared).
+ *   Per stream, after the headers are read: a valid header whose colour, depth, width or height differs from views[i] gets
+ *   FELICS_E_INVALID_DIMENSIONS; nothing is written for that stream; hdrs[i] still receives the header the stream has.
+ *   The write guarantee: the call stores SAMPLE BYTES ONLY.  It never writes the alpha byte of an RGBA pixel, the bytes between a
+ *   row's end and the pitch, anything between the cells of a mosaic, or anything outside felics_view_extent's hull; no wide store
+ *   covers a byte that is not a sample (unlike the encoder, which may READ pad bytes).  A stream that fails while decoding may leave
+ *   any of its own view's samples written or unwritten, and nothing else.
+ *   ready_event : a hipEvent_t the caller has recorded behind whatever produces the streams and last used the views, or NULL.  If
+ *                 given, every stream of the library waits for it (hipStreamWaitEvent) before it first reads a stream byte or
+ *                 writes a view in this call, the header kernel included, and the caller need not synchronise the host.  NULL keeps
+ *                 the contract of felics_decompress_batch_device: the streams are complete in memory when the call is made.
+ * How a view is written (felics_get_decode_view_stats counts them; the streams are counted in felics_decode_stats by form as well):
+ *   dense     : the view is the layout the mixed call writes (a zero-sized view counts here); it takes that call's path as it is;
+ *   in place  : nothing is staged -- RGB8 and RGB16 of ANY strides in every form (the decode kernels write Y / Co / Cg planes as
+ *               for dense frames; the conversion kernel writes the view, sample by sample), and gray8 / gray16 with pixel_stride =
+ *               the sample size and row_stride >= width * sample size (pitched surfaces, crops, mosaic cells: the kernels of both
+ *               forms take the pitch);
+ *   scattered : every other gray view (another pixel stride, a negative or short row stride) and every stream that goes to the host
+ *               decoder (rows too wide for the LDS) is decoded to a dense frame in a staging buffer of the context; one kernel then
+ *               writes its samples through the strides.  The staging is bounded: streams are taken in passes of consecutive
+ *               streams whose frames fit a quarter of the free device memory (a single larger frame is a pass of its own).
+ * The call is blocking: the views are complete when it returns.  It creates no HIP stream. */
+int felics_decompress_views_device(felics_ctx *ctx, size_t n, const void *d_streams, const uint64_t *offsets, const uint64_t *lens,
+                                   const felics_view *views, void *ready_event, felics_header *hdrs /* optional */, int *status);
+
+/* Host only, no context: the code felics_decompress_views_device's checks give this view before anything is launched --
+ * FELICS_OK, felics_view_extent's error, or FELICS_E_INVALID_ARGUMENT for strides that fail the nested rule above. */
+int felics_view_writable(const felics_view *v);
+
+/* How the views of a context's decode calls were written so far (cumulative). */
+typedef struct felics_decode_view_stats {
+    uint64_t views;         /* views handed to felics_decompress_views_device (calls that passed the checks) */
+    uint64_t dense;         /* ... that were the dense layout (zero-sized ones included) */
+    uint64_t in_place;      /* ... written where they lie */
+    uint64_t scattered;     /* ... decoded to a staged dense frame and written by the scatter kernel */
+    uint64_t bytes_staged;  /* bytes of the frames staged for scattered views whose stream was decoded */
+} felics_decode_view_stats;
+/* Writes min(out_size, sizeof(felics_decode_view_stats)) bytes, never more. */
+int felics_get_decode_view_stats(const felics_ctx *ctx, felics_decode_view_stats *out, size_t out_size);
+
 /* Text for a code above; for FELICS_E_HIP felics_last_error(ctx) has the HIP message. */
 const char *felics_strerror(int code);
 const char *felics_last_error(const felics_ctx *ctx);
