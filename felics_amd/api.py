@@ -79,6 +79,15 @@ class _CViewStats(C.Structure):  # felics_view_stats
                 ("bytes_staged", C.c_uint64)]
 
 
+class _CSurfaces(C.Structure):  # felics_surfaces
+    _fields_ = [("frame0", _CView), ("frame_stride", C.c_int64), ("count", C.c_uint64)]
+
+
+class _CSurfaceStats(C.Structure):  # felics_surface_stats
+    _fields_ = [("submissions", C.c_uint64), ("queued", C.c_uint64), ("immediate", C.c_uint64), ("frames_in_place", C.c_uint64),
+                ("frames_gathered", C.c_uint64), ("bytes_staged", C.c_uint64)]
+
+
 class _CDecodeViewStats(C.Structure):  # felics_decode_view_stats
     _fields_ = [("views", C.c_uint64), ("dense", C.c_uint64), ("in_place", C.c_uint64), ("scattered", C.c_uint64),
                 ("bytes_staged", C.c_uint64)]
@@ -116,6 +125,7 @@ EXPORTS = [
     "felics_compress_views_device", "felics_view_extent", "felics_get_view_stats",
     "felics_get_decode_stats", "felics_decode_lanes_min_streams",
     "felics_decompress_views_device", "felics_view_writable", "felics_get_decode_view_stats",
+    "felics_surfaces_extent", "felics_submit_surfaces_device", "felics_compress_surfaces_device", "felics_get_surface_stats",
 ]
 
 _lib = None
@@ -179,6 +189,11 @@ def lib():
     L.felics_compress_views_device.argtypes = [vp, sz, C.POINTER(_CView), vp, vp, sz, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
     L.felics_view_extent.argtypes = [C.POINTER(_CView), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
     L.felics_get_view_stats.argtypes = [vp, C.POINTER(_CViewStats), sz]
+    if hasattr(L, "felics_submit_surfaces_device"):  # (FELICS_LIB_PATH may name an older build: A/B measurements against the parent's library)
+        L.felics_surfaces_extent.argtypes = [C.POINTER(_CSurfaces), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
+        L.felics_submit_surfaces_device.argtypes = [vp, C.POINTER(_CSurfaces), vp, vp, sz, C.POINTER(C.c_int)]
+        L.felics_compress_surfaces_device.argtypes = [vp, C.POINTER(_CSurfaces), vp, vp, sz, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+        L.felics_get_surface_stats.argtypes = [vp, C.POINTER(_CSurfaceStats), sz]
     L.felics_get_decode_stats.argtypes = [vp, C.POINTER(_CDecodeStats), sz]
     L.felics_decompress_views_device.argtypes = [vp, sz, vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(_CView), vp,
                                                  C.POINTER(_CHeader), C.POINTER(C.c_int)]
@@ -271,6 +286,67 @@ def view_of_array(array):
     strides = [int(v) for v in strides]
     ptr = int(cai["data"][0]) if shape[0] * shape[1] else 0
     return (ptr, shape[1], shape[0], color, depth, strides[0], strides[1], strides[2] if len(shape) == 3 else 0)
+
+
+def _csurfaces(surfaces):
+    """A surfaces tuple (view tuple of frame 0, frame_stride in bytes, count) as ONE felics_surfaces: no per-frame objects."""
+    view, frame_stride, count = surfaces
+    return _CSurfaces(_cview(view), int(frame_stride), int(count))
+
+
+def surfaces_extent(surfaces):
+    """felics_surfaces_extent: the half-open byte range (lo, hi) relative to frame 0's pointer that an encode of the n frames may
+    read; checked exactly as Encoder.submit_surfaces_device checks the descriptor (FelicsError otherwise).  Host only, needs no GPU."""
+    lo, hi = C.c_int64(0), C.c_int64(0)
+    cs = _csurfaces(surfaces)
+    rc = lib().felics_surfaces_extent(C.byref(cs), C.byref(lo), C.byref(hi))
+    if rc != 0:
+        raise FelicsError(rc)
+    return int(lo.value), int(hi.value)
+
+
+class _Frames:
+    """Dimension 0 of an array interface peeled off: what view_of_array sees of frame 0."""
+
+    def __init__(self, cai, shape, strides):
+        self.__cuda_array_interface__ = dict(cai, shape=shape, strides=strides)
+
+
+def surfaces_of_array(array):
+    """The surfaces tuple (view of frame 0, frame_stride, count) of an object with __cuda_array_interface__ of shape N x H x W (gray),
+    N x H x W x 3 or N x 3 x H x W (RGB; a last dimension of 3 reads as channels), or of a slice / channel selection / permutation
+    of one: t[:, 3:20, 5:40], rgba[..., :3], rgb[..., ::-1], nchw.permute(0, 2, 3, 1).  Frame 0 is whatever view_of_array accepts.
+    A list or tuple of such frames is accepted if they are one shape and layout and a constant number of bytes apart; anything else
+    raises ValueError.  No copy is made."""
+    if isinstance(array, (list, tuple)):
+        views = [view_of_array(a) for a in array]
+        if not views:
+            raise ValueError("no frames")
+        if any(v[1:] != views[0][1:] for v in views):
+            raise ValueError("the frames of a surfaces descriptor have one shape, type and layout")
+        step = views[1][0] - views[0][0] if len(views) > 1 else 0
+        if any(views[i + 1][0] - views[i][0] != step for i in range(len(views) - 1)):
+            raise ValueError("the frames are not a constant stride apart")
+        return (views[0], step, len(views))
+    cai = array.__cuda_array_interface__
+    shape = tuple(int(v) for v in cai["shape"])
+    if len(shape) not in (3, 4):
+        raise TypeError("Unsupported surfaces: shape %s" % (shape,))
+    strides = cai.get("strides")
+    if strides is None:  # C-contiguous
+        size = 2 if cai["typestr"] == "<u2" else 1
+        strides, step = [], size
+        for extent in reversed(shape):
+            strides.insert(0, step)
+            step *= extent
+    strides = [int(v) for v in strides]
+    fshape, fstrides = list(shape[1:]), list(strides[1:])
+    if len(shape) == 4 and shape[3] != 3:
+        if shape[1] != 3:
+            raise TypeError("Unsupported surfaces: shape %s" % (shape,))
+        fshape, fstrides = [shape[2], shape[3], 3], [strides[2], strides[3], strides[1]]  # N x C x H x W
+    view = view_of_array(_Frames(cai, tuple(fshape), tuple(fstrides)))
+    return (view, strides[0] if shape[0] > 1 else 0, shape[0])
 
 
 class Encoder:
@@ -405,6 +481,43 @@ class Encoder:
             self._raise(rc)
         return {k: int(getattr(st, k)) for k, _ in _CViewStats._fields_}
 
+    def submit_surfaces_device(self, surfaces, d_out, d_out_cap, ready_event=None):
+        """felics_submit_surfaces_device: surfaces = (view tuple of frame 0, frame_stride, count) or an object surfaces_of_array
+        takes; streams into d_out (device) behind ready_event (a hipEvent_t handle, torch: Event.cuda_event).  Returns a ticket for
+        wait_batch; tickets of this call and of submit_batch_device share the lanes and the waiting order."""
+        if not isinstance(surfaces, tuple) or len(surfaces) != 3 or not isinstance(surfaces[0], tuple):
+            surfaces = surfaces_of_array(surfaces)
+        cs = _csurfaces(surfaces)
+        ticket = C.c_int(-1)
+        rc = lib().felics_submit_surfaces_device(self._h, C.byref(cs), int(ready_event) if ready_event else None, d_out, d_out_cap, C.byref(ticket))
+        if rc != 0:
+            self._raise(rc)
+        return ticket.value, int(cs.count)
+
+    def compress_surfaces_device(self, surfaces, d_out, d_out_cap, ready_event=None):
+        """felics_compress_surfaces_device: submit_surfaces_device and wait_batch in one blocking call.  Returns (offsets, lens)."""
+        if not isinstance(surfaces, tuple) or len(surfaces) != 3 or not isinstance(surfaces[0], tuple):
+            surfaces = surfaces_of_array(surfaces)
+        cs = _csurfaces(surfaces)
+        n = int(cs.count)
+        offs = np.zeros(max(n, 1), dtype=np.uint64)
+        lens = np.zeros(max(n, 1), dtype=np.uint64)
+        rc = lib().felics_compress_surfaces_device(self._h, C.byref(cs), int(ready_event) if ready_event else None, d_out, d_out_cap,
+                                                   offs.ctypes.data_as(C.POINTER(C.c_uint64)), lens.ctypes.data_as(C.POINTER(C.c_uint64)))
+        if rc == -8:
+            raise FelicsError(rc, "need %d bytes" % int(lens[0]))
+        if rc != 0:
+            self._raise(rc)
+        return offs[:n], lens[:n]
+
+    def surface_stats(self):
+        """felics_get_surface_stats: submissions, queued / immediate, frames_in_place / frames_gathered, bytes_staged; cumulative."""
+        st = _CSurfaceStats()
+        rc = lib().felics_get_surface_stats(self._h, C.byref(st), C.sizeof(st))
+        if rc != 0:
+            self._raise(rc)
+        return {k: int(getattr(st, k)) for k, _ in _CSurfaceStats._fields_}
+
     def compress_batch_host(self, pixel_ptrs, n, w, h, color, depth, out_ptrs, caps):
         """felics_compress_batch on raw HOST pointers (lists of n addresses: frames in, buffers of caps[i] bytes out): the
         reference's call shape without Python objects in the way -- the copies run at the link's rate when the memory behind the
@@ -443,7 +556,7 @@ class Encoder:
         return ticket.value, n
 
     def wait_batch(self, submission):
-        """Blocks until the batch of `submission` (from submit_batch_device) is complete: (offsets, lens)."""
+        """Blocks until the batch of `submission` (from submit_batch_device or submit_surfaces_device) is complete: (offsets, lens)."""
         ticket, n = submission
         offs = np.zeros(n, dtype=np.uint64)
         lens = np.zeros(n, dtype=np.uint64)

@@ -83,6 +83,27 @@ __device__ __forceinline__ PixelClass classify(const T *__restrict__ pl, uint32_
     return classify_values((int)pl[i], (int)pl[a], (int)pl[b]);
 }
 
+// classify() on a pitched plane: the same neighbour rule (misc.rs:6-24), addresses from (x, y)
+template <typename T>
+__device__ __forceinline__ PixelClass classify_pitched(const T *__restrict__ pl, uint32_t x, uint32_t y, uint64_t pitch) {
+    const uint64_t i = (uint64_t)y * pitch + x;
+    uint64_t a, b;
+    if (x > 0 && y > 0) {
+        a = i - 1;
+        b = i - pitch;
+    } else if (y == 0) {  // first row, x >= 2
+        a = i - 1;
+        b = i - 2;
+    } else if (y >= 2) {  // first column
+        a = i - pitch;
+        b = i - 2 * pitch;
+    } else {  // pixel (0,1); W >= 2
+        a = i - pitch;
+        b = i - pitch + 1;
+    }
+    return classify_values((int)pl[i], (int)pl[a], (int)pl[b]);
+}
+
 // Interior pixel (x > 0, y > 0): left and above, no case analysis.
 template <typename T>
 __device__ __forceinline__ PixelClass classify_interior(const T *__restrict__ pl, uint32_t i, uint32_t W) {
@@ -160,6 +181,9 @@ __device__ __forceinline__ void classify_interior4(const T *__restrict__ pl, uin
 #pragma unroll
     for (int j = 1; j < 4; j++) pc[j] = classify_values(cur[j], cur[j - 1], up[j]);
 }
+
+// What the kernels of a dense plane pass where those of a pitched 16-bit plane pass the pitch in samples (uint64_t).
+struct NoPitch {};
 
 // (x, y) of linear index i; advance() moves forward by `step` pixels without dividing again.
 struct Coord {

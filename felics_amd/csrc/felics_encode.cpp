@@ -343,6 +343,7 @@ Geometry &begin_sub_batch(felics_ctx *ctx, Lane &l, size_t first, size_t cnt, ui
     Geometry &g = l.g;
     g.mixed = nullptr;
     g.pitched = nullptr;
+    g.pitched16 = nullptr;
     g.W = w;
     g.H = h;
     g.npix = (uint32_t)npix;
@@ -626,6 +627,7 @@ int felics_submit_batch_device(felics_ctx *ctx, size_t n, const void *d_pixels, 
     l.p_out = (uint8_t *)d_out;
     l.p_cap = d_out_cap;
     l.finished = false;
+    l.p_surfaces = false;
     const uint32_t planes = color == FELICS_COLOR_RGB ? 3 : 1;
     const uint64_t npix = (uint64_t)w * h;
     const size_t frame_bytes = (size_t)npix * planes * (depth == FELICS_DEPTH_16 ? 2 : 1);
@@ -671,6 +673,7 @@ int felics_wait_batch(felics_ctx *ctx, int ticket, uint64_t *offsets, uint64_t *
         }
         return l.r_rc;
     }
+    if (l.p_surfaces) return land_surfaces(ctx, l, offsets, lens);
     int rc;
     const SlotOutcome o = read_sizes(ctx, l, l.p_depth == FELICS_DEPTH_16, l.p_slot, offsets, lens);
     if (!o.redo() && !o.overflow && !o.spine_error) {

@@ -44,6 +44,25 @@ struct DevBuf {
     size_t cap = 0;
 };
 
+// One image of a mixed sub-batch (felics_mixed.cpp): a dense frame at px, or a view read where it lies / gathered.
+struct MixImage {
+    const uint8_t *px;  // device
+    uint32_t w, h;
+    int color, depth;
+    uint64_t npix;
+    uint32_t planes;
+    size_t frame_bytes;
+    // felics_compress_views_device: the frame is not dense at px but the view vr -- read where it lies by the mixed path (gray8
+    // rows `pitch` bytes apart; RGB8 of any strides through the plane transform), gathered into a dense frame where a path wants
+    // one (16-bit groups, remedies: stage_frame)
+    bool view = false;
+    uint64_t pitch = 0;
+    ViewRow vr = {};
+    // felics_submit_surfaces_device: a 16-bit view the mixed 16-bit path reads where it lies (gray16: rows `pitch` BYTES apart, RGB16
+    // through the plane transform) instead of gathering it
+    bool wide_in_place = false;
+};
+
 // One pipeline lane: HIP streams, stage events and a workspace in HBM of its own.  A submission (or one pass of
 // a huge one) runs on one lane; felics_submit_batch_device hands the lanes out in turn, so that the GPU starts
 // on the next batch while it finishes the last pack slices of this one.
@@ -82,6 +101,10 @@ struct Lane {
     uint64_t p_slot = 0;
     std::vector<uint64_t> r_off, r_len;
     int r_rc = 0;
+    // ... of felics_submit_surfaces_device (p_n, p_out, p_cap as above): what landing needs -- the frames and their slots
+    bool p_surfaces = false;
+    std::vector<MixImage> s_im;
+    std::vector<uint64_t> s_off, s_slot;
     // the sub-batch in flight
     int nslices = SLICES;             // slices its tiles are cut into (see felics_ctx::slices_*)
     bool m_tickets = false;           // the sub-batch's pack kernels took their tiles by ticket (what a look-back failure escalates from)
@@ -155,6 +178,11 @@ struct felics_ctx {
     hipEvent_t view_ready = nullptr;
     DevBuf view_stage;
     felics_view_stats vstats = {};
+    // felics_submit_surfaces_device: its counts; where stage_frame counts the bytes it writes (vstats.bytes_staged unless a surfaces
+    // call is at work); the one lane run_images may use while other lanes hold tickets (-1: all of them)
+    felics_surface_stats sstats = {};
+    uint64_t *staged_bytes = nullptr;
+    int only_lane = -1;
     DevBuf own;      // encode_device's own output when the caller gives none (the host entry point's fall-back for a chunk whose streams outgrew their slots)
     DevBuf dec_meta, dec_planes;  // GPU decoder: offsets | lens | status of a batch; Y / Co / Cg planes of RGB streams
     DevBuf dec_planes16;          // mixed decode call: the int32 planes of its RGB16 streams (beside dec_planes, used at the same time)
@@ -197,6 +225,8 @@ bool any_pending(const felics_ctx *ctx);
 int check_view(const felics_view &v, int64_t &lo, int64_t &hi, bool encode_limits = true);
 // the caller's ready event (ctx->view_ready, if any) in front of whatever is queued on s next
 int wait_ready(felics_ctx *ctx, hipStream_t s);
+// felics_wait_batch for a queued ticket of felics_submit_surfaces_device (the lane's `sized` has been waited for)
+int land_surfaces(felics_ctx *ctx, Lane &l, uint64_t *offsets, uint64_t *lens);
 
 // ---- felics_encode.cpp
 struct SlotOutcome;

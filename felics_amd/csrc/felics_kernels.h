@@ -77,6 +77,9 @@ struct Geometry {
     // that see bits and not pixels go on reading, a table of the pitched policy's own row type for k_front and k_pack_t
     // (nullptr: every plane is dense).
     const struct PitchedGeom *pitched = nullptr;
+    // A mixed sub-batch of gray16 planes read where they lie (felics_submit_surfaces_device): the 16-bit pitched row type, for
+    // launch_wide_events, launch_lengths and launch_pack, which then take their pitched kernels (nullptr: every plane is dense).
+    const struct PitchedGeom16 *pitched16 = nullptr;
 };
 
 // One plane of a mixed sub-batch.  The kernels index it by plane (wave-uniform: scalar loads).  Tiles past the plane's own end
@@ -104,6 +107,12 @@ void launch_gather_view(hipStream_t s, const ViewRow &v, uint32_t W, uint32_t H,
 // One plane of a sub-batch with pitched planes: the plane as in the mixed table, and the bytes between two of its rows (>= W; W: a
 // dense plane).  A row type of its own: PlaneGeom, which the mixed kernels load, stays as it is.
 struct PitchedGeom {
+    PlaneGeom g;
+    uint64_t pitch;
+};
+
+// The same for a plane of u16 samples: the pitch in SAMPLES (>= W).  A row type of its own, as PitchedGeom is.
+struct PitchedGeom16 {
     PlaneGeom g;
     uint64_t pitch;
 };
@@ -371,6 +380,8 @@ constexpr uint32_t WIDE_MAX_PLANE_PIXELS = 1u << 29;  // the sample index in a r
 void launch_rgb16_to_planes(hipStream_t s, const uint16_t *rgb, int32_t *planes, uint32_t npix, uint32_t nimg);
 // mixed sub-batch: image i's pixels from table[3 i].image, its i32 planes to table[3 i + c].samples
 void launch_rgb16_to_planes_mixed(hipStream_t s, const PlaneGeom *table, uint32_t max_npix, uint32_t nimg);
+// mixed sub-batch of RGB16 views: image i read through rows[i] (strides in bytes, even), its i32 planes as launch_rgb16_to_planes_mixed
+void launch_rgb16_view_to_planes(hipStream_t s, const PlaneGeom *table, const ViewRow *rows, uint32_t max_npix, uint32_t nimg);
 
 struct WideSizes {
     uint32_t px_tiles, max_sort_tiles;

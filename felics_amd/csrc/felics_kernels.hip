@@ -298,27 +298,6 @@ __device__ __forceinline__ uint64_t plane_pitch(S, uint32_t) { return 0; }
 __device__ __forceinline__ uint64_t plane_pitch(const PitchedGeom *rows, uint32_t plane) {
     return rows[(uint32_t)__builtin_amdgcn_readfirstlane((int)plane)].pitch;
 }
-// classify() on a pitched plane: the same neighbour rule (misc.rs:6-24), addresses from (x, y)
-template <typename T>
-__device__ __forceinline__ PixelClass classify_pitched(const T *__restrict__ pl, uint32_t x, uint32_t y, uint64_t pitch) {
-    const uint64_t i = (uint64_t)y * pitch + x;
-    uint64_t a, b;
-    if (x > 0 && y > 0) {
-        a = i - 1;
-        b = i - pitch;
-    } else if (y == 0) {  // first row, x >= 2
-        a = i - 1;
-        b = i - 2;
-    } else if (y >= 2) {  // first column
-        a = i - pitch;
-        b = i - 2 * pitch;
-    } else {  // pixel (0,1); W >= 2
-        a = i - pitch;
-        b = i - pitch + 1;
-    }
-    return classify_values((int)pl[i], (int)pl[a], (int)pl[b]);
-}
-
 // (S: const T * -- the uniform planes --, const PlaneGeom * -- a mixed sub-batch's table; W and npix are then unused -- or
 // const PitchedGeom *: the table of a sub-batch with pitched planes)
 template <typename T, typename ET, typename S>
@@ -709,15 +688,63 @@ __device__ __forceinline__ void stage_tile(TileLDS<T> &t, const T *__restrict__ 
     stage_span<T>(t.up, pl, (int64_t)tile_first - W, PACK_TILE + 16, npix);
     stage_span<uint8_t>(t.kq, kpl, (int64_t)tile_first, PACK_TILE, npix);
 }
+template <typename T>
+__device__ __forceinline__ void stage_tile(TileLDS<T> &t, const T *__restrict__ pl, const uint8_t *__restrict__ kpl,
+                                           uint32_t tile_first, uint32_t W, uint32_t npix, NoPitch) {
+    stage_tile(t, pl, kpl, tile_first, W, npix);
+}
+
+// The same from a PITCHED plane (rows `pitch` samples apart): the LDS spans stay dense in linear order -- lds[j] = sample
+// first + j of the plane, y W + x -- so walk_group reads them as it does; the SOURCE is row-wise.  A 16-byte chunk that lies in one
+// row, inside the plane, and is 16-byte aligned in memory is one vector load; a chunk that straddles a row end, is misaligned or
+// touches the plane's ends goes sample by sample through (x, y).  Every load is made of samples of the plane: nothing outside the
+// hull of the surface is read, pad bytes included.
+template <typename U>
+__device__ __forceinline__ void stage_span_pitched(U *lds, const U *__restrict__ g, int64_t first, uint32_t count, uint32_t limit,
+                                                   uint32_t W, uint64_t pitch) {
+    constexpr uint32_t EPC = 16 / sizeof(U);
+    const uint32_t nchunks = (count + EPC - 1) / EPC;
+    for (uint32_t c = threadIdx.x; c < nchunks; c += PACK_THREADS) {
+        const int64_t g0 = first + (int64_t)c * EPC;
+        if (g0 + (int64_t)EPC <= 0 || g0 >= (int64_t)limit) continue;
+        const uint32_t i0 = (uint32_t)max(g0, (int64_t)0);
+        Coord xy;
+        xy.set(i0, W);
+        const U *at = g + (uint64_t)xy.y * pitch + xy.x;
+        if (g0 >= 0 && g0 + EPC <= (int64_t)limit && xy.x + EPC <= W && (reinterpret_cast<uintptr_t>(at) & 15u) == 0) {
+            reinterpret_cast<uint4 *>(lds)[c] = *reinterpret_cast<const uint4 *>(at);
+        } else {
+            for (uint32_t e = (uint32_t)(i0 - g0); e < EPC; e++) {
+                if (g0 + e >= (int64_t)limit || c * EPC + e >= count) break;
+                lds[c * EPC + e] = g[(uint64_t)xy.y * pitch + xy.x];
+                xy.advance(1, W);
+            }
+        }
+    }
+}
+template <typename T>
+__device__ __forceinline__ void stage_tile(TileLDS<T> &t, const T *__restrict__ pl, const uint8_t *__restrict__ kpl,
+                                           uint32_t tile_first, uint32_t W, uint32_t npix, uint64_t pitch) {
+    stage_span_pitched<T>(t.cur, pl, (int64_t)tile_first - STAGE_LEAD, STAGE_LEAD + PACK_TILE, npix, W, pitch);
+    stage_span_pitched<T>(t.up, pl, (int64_t)tile_first - W, PACK_TILE + 16, npix, W, pitch);
+    stage_span<uint8_t>(t.kq, kpl, (int64_t)tile_first, PACK_TILE, npix);
+}
+// the address of sample i = y W + x (and of the sample two rows above a first-column pixel) for walk_group's two direct reads
+__device__ __forceinline__ uint64_t sample_index(uint32_t i, uint32_t, NoPitch) { return i; }
+__device__ __forceinline__ uint64_t sample_index(uint32_t i, uint32_t W, uint64_t pitch) {
+    const uint32_t y = i / W;
+    return (uint64_t)y * pitch + (i - y * W);
+}
 
 // Calls raw(i, value) for pixels 0 and 1 of the plane (stored as 32-bit values,
 // compression.rs:105-106) and f(pc, k) for every other pixel of this thread's group, in raster order.
 // The neighbour rule (misc.rs:6-24) is applied from registers: the left neighbours come from the
 // group itself, the row above from `up`; only the second neighbour of a first-column pixel
 // (two rows up) is fetched from global memory, once per image row.
-template <typename T, typename FR, typename F>
+// (P = NoPitch: a dense plane; uint64_t: a pitched one, whose two direct reads take the pitched address)
+template <typename T, typename FR, typename F, typename P = NoPitch>
 __device__ __forceinline__ void walk_group(const TileLDS<T> &t, const uint8_t *kq, const T *__restrict__ pl, uint32_t first,
-                                           uint32_t end, uint32_t W, FR &&raw, F &&f) {
+                                           uint32_t end, uint32_t W, FR &&raw, F &&f, P pitch = P{}) {
     if (first >= end) return;
     constexpr uint32_t NW = PACK_PER_THREAD * sizeof(T) / 4;  // dwords holding the group's pixels
     const uint32_t off = threadIdx.x * PACK_PER_THREAD;
@@ -734,7 +761,7 @@ __device__ __forceinline__ void walk_group(const TileLDS<T> &t, const uint8_t *k
         kw[0] = c.x; kw[1] = c.y; kw[2] = c.z; kw[3] = c.w;
     }
     int left = (int)t.cur[STAGE_LEAD + off - 1], left2 = (int)t.cur[STAGE_LEAD + off - 2];
-    for (uint32_t i = first; i < min(end, 2u); i++) raw(i, (uint32_t)(int)pl[i]);
+    for (uint32_t i = first; i < min(end, 2u); i++) raw(i, (uint32_t)(int)pl[sample_index(i, W, pitch)]);
     Coord xy;
     xy.set(first, W);
     // Four pixels per trip; the register arrays are shifted down after each trip so that every
@@ -757,7 +784,7 @@ __device__ __forceinline__ void walk_group(const TileLDS<T> &t, const uint8_t *k
                 const bool row0 = xy.y == 0, col0 = xy.x == 0 && !row0;
                 const int v1 = col0 ? above : left;
                 int v2 = row0 ? left2 : above;
-                if (col0) v2 = xy.y >= 2 ? (int)pl[i - 2 * W] : (j < 3 ? sample_at(uw, (j + 1) & 3u, T()) : sample_at(&un, 0, T()));
+                if (col0) v2 = xy.y >= 2 ? (int)pl[sample_index(i - 2 * W, W, pitch)] : (j < 3 ? sample_at(uw, (j + 1) & 3u, T()) : sample_at(&un, 0, T()));
                 const int H = max(v1, v2), L = min(v1, v2);
                 const int d = p - L, ctx = H - L;  // in range: 0 <= d <= ctx
                 const bool below = d < 0, over = d > ctx;
@@ -801,10 +828,10 @@ __device__ __forceinline__ void walk_group(const TileLDS<T> &t, const uint8_t *k
 // row; kpl is its k_map plane, ntiles * PACK_TILE bytes from the next; group_bits / tile_bits stay indexed with the uniform ntiles
 // = T_max.  A tile at or past the plane's end has no pixels: zero bits for every thread and for the tile, which k_bitscan_slice
 // reads like any other.  stage_span bounds every load by npix, so a plane read in place is never read outside its frame.)
-template <typename T, bool MIXED>
+template <typename T, bool MIXED, typename P = NoPitch>
 __device__ __forceinline__ void lengths_tile(const T *__restrict__ pl, const uint8_t *__restrict__ kpl,
                                              group_bits_t<T> *__restrict__ group_bits, uint32_t *__restrict__ tile_bits, uint32_t W,
-                                             uint32_t npix, uint32_t ntiles, uint32_t planes_per_image, uint32_t tile_begin) {
+                                             uint32_t npix, uint32_t ntiles, uint32_t planes_per_image, uint32_t tile_begin, P pitch = P{}) {
     __shared__ TileLDS<T> tl;
     __shared__ uint32_t wsum[PACK_THREADS / 64];
     const uint32_t tile = tile_begin + blockIdx.x, plane = blockIdx.y;
@@ -816,13 +843,13 @@ __device__ __forceinline__ void lengths_tile(const T *__restrict__ pl, const uin
             return;
         }
     }
-    stage_tile(tl, pl, kpl, tile_first, W, npix);
+    stage_tile(tl, pl, kpl, tile_first, W, npix, pitch);
     __syncthreads();
     const uint32_t first = tile_first + threadIdx.x * PACK_PER_THREAD;
     const uint32_t end = min(tile_first + PACK_TILE, npix);
     uint32_t bits = 0;
     walk_group(tl, tl.kq, pl, first, end, W, [&](uint32_t, uint32_t) { bits += 32u; },
-               [&](const PixelClass &pc, uint32_t k) { bits += code_length(pc, k); });
+               [&](const PixelClass &pc, uint32_t k) { bits += code_length(pc, k); }, pitch);
     if (npix == 1 && first == 0) bits += 32;  // 1x1: second raw value is a literal 0 (compression.rs:99-103)
     if (tile == 0 && threadIdx.x == 0 && (plane % planes_per_image) == 0) bits += 8 * 14;  // header
     group_bits[((uint64_t)plane * ntiles + tile) * PACK_THREADS + threadIdx.x] = (group_bits_t<T>)bits;
@@ -854,6 +881,15 @@ __global__ __launch_bounds__(PACK_THREADS) void k_lengths_mixed(const PlaneGeom 
     const PlaneView<T> pv = plane_view<T>((const T *)nullptr, plane, table);
     lengths_tile<T, true>(pv.pl, k_map + (uint64_t)plane * ntiles * PACK_TILE, group_bits, tile_bits, pv.W, pv.npix, ntiles,
                           planes_per_image, tile_begin);
+}
+// gray16 planes read where they lie (Geometry::pitched16): k_lengths_mixed with the plane's pitch
+__global__ __launch_bounds__(PACK_THREADS) void k_lengths_pitched(const PitchedGeom16 *__restrict__ rows, const uint8_t *__restrict__ k_map,
+                                                                  uint32_t *__restrict__ group_bits, uint32_t *__restrict__ tile_bits,
+                                                                  uint32_t ntiles, uint32_t planes_per_image, uint32_t tile_begin) {
+    const uint32_t plane = blockIdx.y;
+    const PitchedGeom16 *pg = rows + (uint32_t)__builtin_amdgcn_readfirstlane((int)plane);
+    lengths_tile<uint16_t, true, uint64_t>((const uint16_t *)pg->g.samples, k_map + (uint64_t)plane * ntiles * PACK_TILE, group_bits, tile_bits,
+                                           pg->g.W, pg->g.npix, ntiles, planes_per_image, tile_begin, pg->pitch);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -1002,12 +1038,12 @@ __global__ void k_zero_streams(uint32_t *__restrict__ out, const uint64_t *__res
 // and k_map's planes are ntiles * PACK_TILE bytes apart; a padding tile has tile_bits = 0 -- no last word, nothing to pack -- and
 // returns before anything is staged.  The header carries the image's own W and H.
 // No __restrict__ on this body's pointers: the kernels' own arguments carry it, and said again here it cost k_pack<i32> an SGPR.)
-template <typename T, typename PL>
+template <typename T, typename PL, typename P = NoPitch>
 __device__ __forceinline__ void pack_tile(const T *planes, const uint8_t *k_map,
                                           const group_bits_t<T> *group_bits, const uint64_t *tile_bitoff,
                                           const uint32_t *tile_bits, const uint64_t *plane_base, const PL place,
                                           uint8_t *out, uint32_t W, uint32_t H, uint32_t npix, uint32_t ntiles,
-                                          uint32_t planes_per_image, uint32_t color, uint32_t depth, uint32_t tile_begin) {
+                                          uint32_t planes_per_image, uint32_t color, uint32_t depth, uint32_t tile_begin, P pitch = P{}) {
     __shared__ TileLDS<T> tl;
     __shared__ uint32_t win[PACK_WIN_WORDS];
     __shared__ uint32_t wsum[PACK_THREADS / 64];
@@ -1030,7 +1066,7 @@ __device__ __forceinline__ void pack_tile(const T *planes, const uint8_t *k_map,
     const uint32_t end = min(tile_first + PACK_TILE, npix);
     const bool has_header = tile == 0 && threadIdx.x == 0 && first_plane;
 
-    stage_tile(tl, pl, k_map + (uint64_t)plane * kstride, tile_first, W, npix);
+    stage_tile(tl, pl, k_map + (uint64_t)plane * kstride, tile_first, W, npix, pitch);
     // this thread's bit offset inside the tile: scan of the group sizes k_lengths left behind
     const uint32_t bits = group_bits[((uint64_t)plane * ntiles + tile) * PACK_THREADS + threadIdx.x];
     const uint32_t inc = wave_incl_scan(bits);
@@ -1068,7 +1104,7 @@ __device__ __forceinline__ void pack_tile(const T *planes, const uint8_t *k_map,
                            bw.put(rv, 32);  // write_signed(32, p): sign-extended sample
                            if (npix == 1) bw.put(0u, 32);
                        },
-                       [&](const PixelClass &pc, uint32_t k) { put_pixel(bw, pc, k); });
+                       [&](const PixelClass &pc, uint32_t k) { put_pixel(bw, pc, k); }, pitch);
             bw.finish();
         }
         __syncthreads();
@@ -1107,6 +1143,16 @@ __global__ __launch_bounds__(PACK_THREADS) void k_pack_mixed(const PlaneGeom *__
                                                              uint32_t tile_begin) {
     pack_tile<T>((const T *)nullptr, k_map, group_bits, tile_bitoff, tile_bits, plane_base, MixedPlacement{table}, out, 0u, 0u, 0u, ntiles,
                  planes_per_image, color, depth, tile_begin);
+}
+// gray16 planes read where they lie: k_pack_mixed with the plane's pitch (`table` = the same planes' PlaneGeom rows: placement)
+__global__ __launch_bounds__(PACK_THREADS) void k_pack_pitched(const PlaneGeom *__restrict__ table, const PitchedGeom16 *__restrict__ rows,
+                                                               const uint8_t *__restrict__ k_map, const uint32_t *__restrict__ group_bits,
+                                                               const uint64_t *__restrict__ tile_bitoff, const uint32_t *__restrict__ tile_bits,
+                                                               const uint64_t *__restrict__ plane_base, uint8_t *__restrict__ out, uint32_t ntiles,
+                                                               uint32_t planes_per_image, uint32_t color, uint32_t depth, uint32_t tile_begin) {
+    const uint64_t pitch = rows[(uint32_t)__builtin_amdgcn_readfirstlane((int)blockIdx.y)].pitch;
+    pack_tile<uint16_t, MixedPlacement, uint64_t>((const uint16_t *)nullptr, k_map, group_bits, tile_bitoff, tile_bits, plane_base,
+                                                  MixedPlacement{table}, out, 0u, 0u, 0u, ntiles, planes_per_image, color, depth, tile_begin, pitch);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -2025,6 +2071,13 @@ template <typename T>
 void launch_lengths(hipStream_t s, const T *planes, const uint8_t *k_map, group_bits_t<T> *group_bits,
                     uint32_t *tile_bits, const Geometry &g, uint32_t t0, uint32_t t1) {
     if (t1 <= t0) return;
+    if constexpr (std::is_same<T, uint16_t>::value) {
+        if (g.mixed && g.pitched16) {
+            FELICS_LAUNCH(k_lengths_pitched, dim3(t1 - t0, g.nplanes), dim3(PACK_THREADS), s, g.pitched16, k_map, group_bits, tile_bits,
+                          g.pack_tiles, g.planes_per_image, t0);
+            return;
+        }
+    }
     if constexpr (sizeof(group_bits_t<T>) == 4) {  // (a mixed sub-batch takes these kernels with 16-bit samples only)
         if (g.mixed) {
             FELICS_LAUNCH((k_lengths_mixed<T>), dim3(t1 - t0, g.nplanes), dim3(PACK_THREADS), s, g.mixed, k_map, group_bits, tile_bits,
@@ -2085,6 +2138,13 @@ void launch_pack(hipStream_t s, const T *planes, const uint8_t *k_map, const gro
                  const uint64_t *image_off, uint64_t slot_stride, uint8_t *out, const Geometry &g, uint32_t t0,
                  uint32_t t1) {
     if (t1 <= t0) return;
+    if constexpr (std::is_same<T, uint16_t>::value) {
+        if (g.mixed && g.pitched16) {
+            FELICS_LAUNCH(k_pack_pitched, dim3(t1 - t0, g.nplanes), dim3(PACK_THREADS), s, g.mixed, g.pitched16, k_map, group_bits, tile_bitoff,
+                          tile_bits, plane_base, out, g.pack_tiles, g.planes_per_image, g.color, g.depth, t0);
+            return;
+        }
+    }
     if constexpr (sizeof(group_bits_t<T>) == 4) {
         if (g.mixed) {
             FELICS_LAUNCH((k_pack_mixed<T>), dim3(t1 - t0, g.nplanes), dim3(PACK_THREADS), s, g.mixed, k_map, group_bits, tile_bitoff, tile_bits,

@@ -16,22 +16,8 @@ namespace {
 
 constexpr size_t MIX_MAX_IMAGES = 8192;  // images of one mixed sub-batch (k_concat_planes / k_rgb8_to_planes_mixed: one grid row per image)
 
-struct MixImage {
-    const uint8_t *px;  // device
-    uint32_t w, h;
-    int color, depth;
-    uint64_t npix;
-    uint32_t planes;
-    size_t frame_bytes;
-    // felics_compress_views_device: the frame is not dense at px but the view vr -- read where it lies by the mixed path (gray8
-    // rows `pitch` bytes apart; RGB8 of any strides through the plane transform), gathered into a dense frame where a path wants
-    // one (16-bit groups, remedies: stage_frame)
-    bool view = false;
-    uint64_t pitch = 0;
-    ViewRow vr = {};
-};
-
-// Image m as a dense frame at dst: a copy, or the gather of its view (counted: felics_view_stats::bytes_staged).
+// Image m as a dense frame at dst: a copy, or the gather of its view (counted: felics_view_stats::bytes_staged, or -- a surfaces call
+// at work -- felics_surface_stats::bytes_staged).
 int stage_frame(felics_ctx *ctx, hipStream_t s, void *dst, const MixImage &m) {
     if (!m.frame_bytes) return FELICS_OK;
     if (!m.view) {
@@ -43,7 +29,7 @@ int stage_frame(felics_ctx *ctx, hipStream_t s, void *dst, const MixImage &m) {
     else
         launch_gather_view<uint8_t>(s, m.vr, m.w, m.h, m.planes, (uint8_t *)dst);
     HIP_TRY(ctx, hipGetLastError());
-    ctx->vstats.bytes_staged += m.frame_bytes;
+    *(ctx->staged_bytes ? ctx->staged_bytes : &ctx->vstats.bytes_staged) += m.frame_bytes;
     return FELICS_OK;
 }
 
@@ -95,7 +81,7 @@ struct MixOut {
 };
 
 // a view's dense copy in a mixed 16-bit job's part of mix_in: 256-byte steps
-size_t gather_step(const MixImage &m) { return m.view ? (m.frame_bytes + 255) & ~(size_t)255 : 0; }
+size_t gather_step(const MixImage &m) { return m.view && !m.wide_in_place ? (m.frame_bytes + 255) & ~(size_t)255 : 0; }
 
 // The head of a mixed sub-batch of either depth on lane l, whose first kernel runs on stream s: the padded geometry (every plane
 // T_max tiles of SORT_TILE samples: the stride of the RGB planes buffer and of k_map), the planes buffer, the pinned table (with
@@ -182,30 +168,46 @@ int launch_mixed(felics_ctx *ctx, Lane &l, const std::vector<MixImage> &im, cons
 
 // Queues a mixed 16-bit sub-batch on lane l: run_wide with the plane table.  gray16 frames are read where the caller has them, RGB16
 // frames by the plane transform; a view is gathered to `gathered` first (stage_frame: counted in bytes_staged) and its rows point
-// there.  Everything on the lane's one stream.
+// there -- unless it is marked wide_in_place (felics_submit_surfaces_device): then, behind the table, the 16-bit pitched rows of a gray
+// sub-batch (Geometry::pitched16) or the views of an RGB one (the other images as views of their own), and nothing is gathered.
+// Everything on the lane's one stream.
 int launch_mixed_wide(felics_ctx *ctx, Lane &l, const std::vector<MixImage> &im, const std::vector<size_t> &idx, const MixOut &o, uint8_t *gathered,
                       int nslices) {
     const size_t cnt = idx.size();
-    const size_t tbytes = cnt * im[idx[0]].planes * sizeof(PlaneGeom);
+    const uint32_t planes = im[idx[0]].planes;
+    bool in_place = false;
+    for (size_t i : idx) in_place = in_place || im[i].wide_in_place;
+    static_assert(sizeof(PitchedGeom16) == sizeof(PitchedGeom), "the extra row begin_mixed reserves per plane holds either");
+    const size_t extra_off = cnt * planes * sizeof(PlaneGeom);
+    const size_t tbytes = extra_off + (in_place ? (planes == 1 ? cnt * sizeof(PitchedGeom16) : cnt * sizeof(ViewRow)) : 0);
     hipStream_t s = l.stream;
     uint64_t max_npix;
     int rc = begin_mixed(ctx, l, im, idx, FELICS_DEPTH_16, nslices, s, tbytes, max_npix);
     if (rc) return rc;
+    PitchedGeom16 *h_pitched = (PitchedGeom16 *)((uint8_t *)l.h_table + extra_off);  // gray
+    ViewRow *h_views = (ViewRow *)((uint8_t *)l.h_table + extra_off);                // RGB
     size_t at = 0;
     for (size_t j = 0; j < cnt; j++) {
         const MixImage &m = im[idx[j]];
         const uint8_t *frame = m.px;
-        if (m.view) {
+        if (m.view && !m.wide_in_place) {
             frame = gathered + at;
             if ((rc = stage_frame(ctx, s, gathered + at, m)) != 0) return rc;
             at += gather_step(m);
         }
         plane_rows(l, j, m, frame, 4, o, idx[j]);
+        if (in_place && planes == 1) h_pitched[j] = PitchedGeom16{l.h_table[j], m.wide_in_place ? m.pitch / 2 : (uint64_t)m.w};  // (in samples)
+        if (in_place && planes == 3) h_views[j] = m.wide_in_place ? m.vr : ViewRow{frame, 6ll * m.w, 6, 2};
     }
     if ((rc = upload_table(ctx, l, tbytes, s)) != 0) return rc;
-    if (l.g.planes_per_image == 3) {
+    const uint8_t *extra = (const uint8_t *)l.mtable.p + extra_off;
+    if (in_place && planes == 1) l.g.pitched16 = (const PitchedGeom16 *)extra;
+    if (planes == 3) {
         StageTimer t(ctx, l, ST_PLANES, s, true);
-        launch_rgb16_to_planes_mixed(s, l.g.mixed, (uint32_t)max_npix, (uint32_t)cnt);
+        if (in_place)
+            launch_rgb16_view_to_planes(s, l.g.mixed, (const ViewRow *)extra, (uint32_t)max_npix, (uint32_t)cnt);
+        else
+            launch_rgb16_to_planes_mixed(s, l.g.mixed, (uint32_t)max_npix, (uint32_t)cnt);
     }
     return run_sub_batch(ctx, l, o.base, 0);
 }
@@ -362,7 +364,7 @@ int run_images(felics_ctx *ctx, const std::vector<MixImage> &im, MixOut &o) {
             return rc;
         o.lens[i] = len;
     }
-    const int nslices = jobs.size() > 1 ? ctx->slices_queued : ctx->slices_blocking;
+    const int nslices = jobs.size() > 1 || ctx->only_lane >= 0 ? ctx->slices_queued : ctx->slices_blocking;
     std::vector<size_t> flying;  // jobs in flight, oldest first (lanes handed out in turn: the oldest holds the next lane)
     auto drain = [&](int r) {
         for (size_t f : flying) {
@@ -371,8 +373,11 @@ int run_images(felics_ctx *ctx, const std::vector<MixImage> &im, MixOut &o) {
         }
         return r;
     };
+    // (a surfaces submission done at once while other lanes hold tickets: its own lane only, and the turn of the lanes stays)
+    const int nlanes = ctx->only_lane >= 0 ? 1 : ctx->nlanes;
     for (size_t q = 0; q < jobs.size(); q++) {
-        if ((int)flying.size() == ctx->nlanes) {
+        const int use_lane = ctx->only_lane >= 0 ? ctx->only_lane : ctx->next_lane;
+        if ((int)flying.size() == nlanes) {
             rc = land_job(ctx, jobs[flying.front()], im, o);
             flying.erase(flying.begin());
             if (rc) return drain(rc);
@@ -385,12 +390,12 @@ int run_images(felics_ctx *ctx, const std::vector<MixImage> &im, MixOut &o) {
                 flying.erase(flying.begin());
                 if (rc) return drain(rc);
             }
-            if ((rc = redo_by_shape(ctx, ctx->lanes[ctx->next_lane], im, j.idx, o)) != 0) return rc;
+            if ((rc = redo_by_shape(ctx, ctx->lanes[use_lane], im, j.idx, o)) != 0) return rc;
             continue;
         }
-        j.lane = ctx->next_lane;
+        j.lane = use_lane;
         Lane &l = ctx->lanes[j.lane];
-        ctx->next_lane = (ctx->next_lane + 1) % ctx->nlanes;
+        if (ctx->only_lane < 0) ctx->next_lane = (ctx->next_lane + 1) % ctx->nlanes;
         if (j.wide) {
             const MixImage &f = im[j.idx[0]];
             uint8_t *in = (uint8_t *)ctx->mix_in.p + j.in_off;
@@ -494,9 +499,209 @@ int check_view(const felics_view &v, int64_t &lo, int64_t &hi, bool encode_limit
     return FELICS_OK;
 }
 
+int views_device(felics_ctx *ctx, size_t n, const felics_view *views, void *ready_event, void *d_out, size_t d_out_cap, uint64_t *offsets,
+                 uint64_t *lens, felics_view_stats &counted);
+
+// felics_surfaces_extent: the view's checks on frame 0, the frame axis, and the hull of all frames' sample bytes relative to frame0.data.
+int check_surfaces(const felics_surfaces &s, int64_t &lo, int64_t &hi) {
+    int rc = check_view(s.frame0, lo, hi);
+    if (rc) return rc;
+    if (s.frame0.depth == FELICS_DEPTH_16 && (s.frame_stride & 1)) return FELICS_E_INVALID_ARGUMENT;
+    if (!s.count || !s.frame0.width || !s.frame0.height) {
+        lo = hi = 0;
+        return FELICS_OK;
+    }
+    const __int128 span = (__int128)(s.count - 1) * s.frame_stride;
+    const __int128 l = (__int128)lo + (span < 0 ? span : 0), h = (__int128)hi + (span > 0 ? span : 0);
+    lo = hi = 0;
+    if (l < INT64_MIN || h > INT64_MAX) return FELICS_E_INVALID_ARGUMENT;
+    lo = (int64_t)l;
+    hi = (int64_t)h;
+    return FELICS_OK;
+}
+
+// A queued surfaces ticket has come back (felics_wait_batch; the lane's sizes are on the host): land_job's body for its one mixed
+// sub-batch, judged by the mode it was launched with.  A sub-batch that is not to be used is redone from gathered frames
+// (redo_by_shape on this lane alone: other lanes may hold tickets); after a slot overflow the streams are placed exactly in d_out.
+int land_surfaces(felics_ctx *ctx, Lane &l, uint64_t *offsets, uint64_t *lens) {
+    const size_t n = l.p_n;
+    const std::vector<MixImage> &im = l.s_im;
+    const bool wide = im[0].depth == FELICS_DEPTH_16;
+    std::vector<size_t> idx(n);
+    for (size_t i = 0; i < n; i++) idx[i] = i;
+    MixOut o{l.p_out, l.s_off.data(), l.s_slot.data(), lens, false};
+    SlotOutcome so = wide ? SlotOutcome{} : decode_status(ctx, l, l.h_sizes[n]);  // (run_wide copies the sizes and nothing else)
+    for (size_t k = 0; k < n; k++) {
+        lens[k] = l.h_sizes[k];
+        if (lens[k] > l.s_slot[k]) so.overflow = true;
+    }
+    int rc;
+    if (!so.redo() && !so.overflow && !so.spine_error) {
+        if (wide && ctx->profiling && (rc = sync_lane(ctx, l)) != 0) return rc;
+        collect_timing(ctx, l);
+        for (size_t k = 0; k < n; k++) offsets[k] = l.s_off[k];
+        return FELICS_OK;
+    }
+    if ((rc = sync_lane(ctx, l)) != 0) return rc;
+    if ((rc = apply_remedy(ctx, l, so)) != 0) return rc;
+    ctx->staged_bytes = &ctx->sstats.bytes_staged;
+    auto leave = [&](int r) {
+        ctx->staged_bytes = nullptr;
+        return r;
+    };
+    if (so.redo()) {  // nothing of the sub-batch is to be used, its sizes included: into the slots once more
+        if ((rc = redo_by_shape(ctx, l, im, idx, o)) != 0) return leave(rc);
+        if (!o.overflow) {
+            for (size_t k = 0; k < n; k++) offsets[k] = l.s_off[k];
+            return leave(FELICS_OK);
+        }
+    }
+    // a stream outgrew its slot (lens holds every stream's size): exact placement, back to back
+    std::vector<uint64_t> off(n), slot(n);
+    uint64_t need = 0;
+    for (size_t k = 0; k < n; k++) {
+        off[k] = need;
+        slot[k] = (lens[k] + 15) & ~15ull;
+        need += slot[k];
+    }
+    if (need > l.p_cap) {
+        lens[0] = need;
+        return leave(FELICS_E_BUFFER_TOO_SMALL);
+    }
+    MixOut exact{l.p_out, off.data(), slot.data(), lens, false};
+    if ((rc = redo_by_shape(ctx, l, im, idx, exact)) != 0) return leave(rc);
+    if (exact.overflow) {
+        ctx->err = "internal error: a stream outgrew the exact size it had before";
+        return leave(FELICS_E_HIP);
+    }
+    for (size_t k = 0; k < n; k++) offsets[k] = off[k];
+    return leave(FELICS_OK);
+}
+
+// felics_submit_surfaces_device behind its checks (the next lane is free).
+static int submit_surfaces(felics_ctx *ctx, const felics_surfaces &s, void *ready_event, void *d_out, size_t d_out_cap, int *ticket) {
+    const felics_view &v = s.frame0;
+    const size_t n = (size_t)s.count;
+    const int L = ctx->next_lane;
+    Lane &l = ctx->lanes[L];
+    const MixImage m0 = mix_image(felics_image{v.data, v.width, v.height, v.color, v.depth});
+    const bool wide = v.depth == FELICS_DEPTH_16, rgb = v.color == FELICS_COLOR_RGB;
+    const int64_t bytes = wide ? 2 : 1;
+    const bool dense_frame = v.pixel_stride == bytes * (rgb ? 3 : 1) && v.row_stride == (int64_t)v.width * v.pixel_stride && (!rgb || v.channel_stride == bytes);
+    int rc;
+    if (m0.npix && dense_frame && (n == 1 || s.frame_stride == (int64_t)m0.frame_bytes)) {
+        // the layout of felics_submit_batch_device: that call's path as it is, the event in front of its first kernel
+        ctx->wait_before_submit = (hipEvent_t)ready_event;
+        rc = felics_submit_batch_device(ctx, n, v.data, v.width, v.height, v.color, v.depth, d_out, d_out_cap, ticket);
+        ctx->wait_before_submit = nullptr;
+        if (rc) return rc;
+        ctx->sstats.submissions++;
+        (l.finished ? ctx->sstats.immediate : ctx->sstats.queued)++;
+        ctx->sstats.frames_in_place += n;
+        return FELICS_OK;
+    }
+    const bool readable = m0.npix && (rgb || (v.pixel_stride == bytes && v.row_stride >= bytes * (int64_t)v.width));
+    const uint64_t slot = default_slot(m0.frame_bytes);
+    const size_t per = std::min(MIX_MAX_IMAGES, max_images_per_pass((uint64_t)sort_tiles_of(m0.npix) * SORT_TILE, m0.planes, v.depth));
+    l.p_n = n;
+    l.p_out = (uint8_t *)d_out;
+    l.p_cap = d_out_cap;
+    l.finished = false;
+    l.p_surfaces = false;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    if (readable && n <= per && n <= d_out_cap / slot && !ctx->two_pass) {
+        l.s_im.assign(n, m0);
+        l.s_off.resize(n);
+        l.s_slot.assign(n, slot);
+        std::vector<size_t> idx(n);
+        for (size_t i = 0; i < n; i++) {
+            MixImage &m = l.s_im[i];
+            m.px = (const uint8_t *)v.data + (int64_t)i * s.frame_stride;
+            m.view = true;
+            m.vr = ViewRow{m.px, v.row_stride, v.pixel_stride, rgb ? v.channel_stride : 0};
+            m.pitch = rgb ? 0 : (uint64_t)v.row_stride;  // (bytes)
+            m.wide_in_place = wide;
+            l.s_off[i] = i * slot;
+            idx[i] = i;
+        }
+        const MixOut o{l.p_out, l.s_off.data(), l.s_slot.data(), nullptr, false};
+        ctx->view_ready = (hipEvent_t)ready_event;  // (around the launch only)
+        rc = wide ? launch_mixed_wide(ctx, l, l.s_im, idx, o, nullptr, ctx->slices_queued) : launch_mixed(ctx, l, l.s_im, idx, o, ctx->slices_queued);
+        ctx->view_ready = nullptr;
+        if (rc) {
+            (void)sync_lane(ctx, l);
+            return rc;
+        }
+        l.p_surfaces = true;
+        ctx->sstats.queued++;
+        ctx->sstats.frames_in_place += n;
+    } else {
+        // not the queued case: the n views through the views call's path now, on this lane alone, handed over at the wait
+        std::vector<felics_view> views(n, v);
+        for (size_t i = 0; i < n; i++) views[i].data = (const uint8_t *)v.data + (int64_t)i * s.frame_stride;
+        l.r_off.assign(n, 0);
+        l.r_len.assign(n, 0);
+        felics_view_stats add = {};
+        ctx->staged_bytes = &ctx->sstats.bytes_staged;
+        ctx->only_lane = L;
+        l.r_rc = views_device(ctx, n, views.data(), ready_event, d_out, d_out_cap, l.r_off.data(), l.r_len.data(), add);
+        ctx->staged_bytes = nullptr;
+        ctx->only_lane = -1;
+        l.finished = true;
+        ctx->sstats.immediate++;
+        ctx->sstats.frames_in_place += add.in_place + add.dense;
+        ctx->sstats.frames_gathered += add.gathered;
+    }
+    ctx->sstats.submissions++;
+    l.pending = true;
+    *ticket = L;
+    ctx->next_lane = (L + 1) % ctx->nlanes;
+    return FELICS_OK;
+}
+
 }  // namespace felics
 
 extern "C" {
+
+int felics_surfaces_extent(const felics_surfaces *s, int64_t *lo, int64_t *hi) {
+    if (!s || !lo || !hi) return FELICS_E_INVALID_ARGUMENT;
+    return check_surfaces(*s, *lo, *hi);
+}
+
+int felics_get_surface_stats(const felics_ctx *ctx, felics_surface_stats *out, size_t out_size) {
+    if (!ctx || !out) return FELICS_E_INVALID_ARGUMENT;
+    memcpy(out, &ctx->sstats, std::min(out_size, sizeof(felics_surface_stats)));
+    return FELICS_OK;
+}
+
+constexpr uint64_t SURFACES_MAX_COUNT = 1ull << 24;  // frames of one descriptor (the host keeps a row per frame)
+
+int felics_submit_surfaces_device(felics_ctx *ctx, const felics_surfaces *s, void *ready_event, void *d_out, size_t d_out_cap, int *ticket) {
+    if (!ctx || !s || !ticket || !d_out) return FELICS_E_INVALID_ARGUMENT;
+    if (ctx->failed) return FELICS_E_HIP;
+    int64_t lo, hi;
+    int rc = check_surfaces(*s, lo, hi);
+    if (rc) return rc;
+    if (s->count == 0) return FELICS_E_INVALID_ARGUMENT;
+    if (s->count > SURFACES_MAX_COUNT) return FELICS_E_UNSUPPORTED;
+    if (ctx->lanes[ctx->next_lane].pending) return FELICS_E_INVALID_ARGUMENT;  // every lane holds a ticket: wait for the oldest
+    return submit_surfaces(ctx, *s, ready_event, d_out, d_out_cap, ticket);
+}
+
+int felics_compress_surfaces_device(felics_ctx *ctx, const felics_surfaces *s, void *ready_event, void *d_out, size_t d_out_cap,
+                                    uint64_t *offsets, uint64_t *lens) {
+    if (!ctx || !s || (s->count && (!d_out || !offsets || !lens))) return FELICS_E_INVALID_ARGUMENT;
+    if (ctx->failed) return FELICS_E_HIP;
+    int64_t lo, hi;
+    int rc = check_surfaces(*s, lo, hi);
+    if (rc) return rc;
+    if (s->count == 0) return FELICS_OK;
+    if (s->count > SURFACES_MAX_COUNT) return FELICS_E_UNSUPPORTED;
+    if (any_pending(ctx)) return FELICS_E_INVALID_ARGUMENT;  // felics_wait_batch first
+    int ticket = -1;
+    if ((rc = submit_surfaces(ctx, *s, ready_event, d_out, d_out_cap, &ticket)) != 0) return rc;
+    return felics_wait_batch(ctx, ticket, offsets, lens);
+}
 
 int felics_compress_images_device(felics_ctx *ctx, size_t n, const felics_image *images, void *d_out, size_t d_out_cap, uint64_t *offsets,
                                   uint64_t *lens) {
@@ -533,6 +738,23 @@ int felics_compress_views_device(felics_ctx *ctx, size_t n, const felics_view *v
     }
     if (n == 0) return FELICS_OK;
     if (any_pending(ctx)) return FELICS_E_INVALID_ARGUMENT;  // felics_wait_batch first
+    felics_view_stats add = {};
+    const int rc = views_device(ctx, n, views, ready_event, d_out, d_out_cap, offsets, lens, add);
+    ctx->vstats.views += add.views;  // (bytes_staged: stage_frame has counted)
+    ctx->vstats.dense += add.dense;
+    ctx->vstats.in_place += add.in_place;
+    ctx->vstats.gathered += add.gathered;
+    return rc;
+}
+
+}  // extern "C"
+
+namespace felics {
+
+// felics_compress_views_device behind its checks; `add` = the classes of the views (counted once the gathering has succeeded).  Also
+// the immediate case of felics_submit_surfaces_device (ctx->only_lane: the one lane it may use).
+int views_device(felics_ctx *ctx, size_t n, const felics_view *views, void *ready_event, void *d_out, size_t d_out_cap, uint64_t *offsets,
+                 uint64_t *lens, felics_view_stats &counted) {
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     // the class of every view: dense, read in place, or gathered (gray8 now, into view_stage; 16-bit where its group is queued)
     std::vector<MixImage> im(n);
@@ -576,7 +798,7 @@ int felics_compress_views_device(felics_ctx *ctx, size_t n, const felics_view *v
         return r;
     };
     if (stage_total) {
-        Lane &l = ctx->lanes[0];
+        Lane &l = ctx->lanes[std::max(0, ctx->only_lane)];
         if ((rc = reserve(ctx, ctx->view_stage, stage_total + 64)) != 0) return leave(rc);
         if ((rc = wait_ready(ctx, l.stream)) != 0) return leave(rc);
         for (size_t i = 0; i < n; i++) {
@@ -589,12 +811,13 @@ int felics_compress_views_device(felics_ctx *ctx, size_t n, const felics_view *v
         }
         if (hipStreamSynchronize(l.stream) != hipSuccess) return leave(hip_fail(ctx, hipGetLastError(), "gathering views"));
     }
-    ctx->vstats.views += add.views;
-    ctx->vstats.dense += add.dense;
-    ctx->vstats.in_place += add.in_place;
-    ctx->vstats.gathered += add.gathered;
+    counted = add;
     return leave(images_device(ctx, im, (uint8_t *)d_out, d_out_cap, offsets, lens));
 }
+
+}  // namespace felics
+
+extern "C" {
 
 // Host frames in, host streams out: the frames are copied to the device (16-byte aligned, back to back), encoded as above into the
 // context's own buffer, and every stream that fits its caller's buffer is copied back.

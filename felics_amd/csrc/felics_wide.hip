@@ -10,6 +10,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <type_traits>
+
 #include "felics_device.h"
 #include "felics_kernels.h"
 
@@ -48,6 +50,26 @@ __global__ __launch_bounds__(256) void k_rgb16_to_planes_mixed(const PlaneGeom *
     for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < npix; i += gridDim.x * blockDim.x) {
         int yv, co, cg;
         rgb16_pixel(rgb + (uint64_t)i * 3, yv, co, cg);
+        py[i] = yv;
+        pco[i] = co;
+        pcg[i] = cg;
+    }
+}
+// A mixed sub-batch of RGB16 VIEWS (felics_submit_surfaces_device): image blockIdx.y read where it lies -- sample (x, y, c) at
+// data + y * row_stride + x * pixel_stride + c * channel_stride, signed even 64-bit strides in bytes -- into the same planes.  One
+// pixel per thread, sample by sample: every load is a sample of the view.
+__global__ __launch_bounds__(256) void k_rgb16_view_to_planes(const PlaneGeom *__restrict__ table, const ViewRow *__restrict__ rows) {
+    const PlaneGeom *pg = table + 3ull * blockIdx.y;
+    const ViewRow vr = rows[blockIdx.y];
+    const uint32_t npix = pg->npix, W = pg->W;
+    const uint8_t *data = (const uint8_t *)vr.data;
+    int32_t *py = (int32_t *)pg[0].samples, *pco = (int32_t *)pg[1].samples, *pcg = (int32_t *)pg[2].samples;
+    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < npix; i += gridDim.x * blockDim.x) {
+        const uint32_t y = i / W, x = i - y * W;
+        const uint8_t *p = data + (int64_t)y * vr.row_stride + (int64_t)x * vr.pixel_stride;
+        const uint16_t s[3] = {*(const uint16_t *)p, *(const uint16_t *)(p + vr.channel_stride), *(const uint16_t *)(p + 2 * vr.channel_stride)};
+        int yv, co, cg;
+        rgb16_pixel(s, yv, co, cg);
         py[i] = yv;
         pco[i] = co;
         pcg[i] = cg;
@@ -125,6 +147,49 @@ __device__ __forceinline__ void for_my_events(const T *__restrict__ pl, uint32_t
     }
 }
 
+// The same on a PITCHED plane (gray16 surfaces read where they lie): rows `pitch` samples apart.  The linear index i = y W + x still
+// names the sample's tile and its record; only its address changes, y * pitch + x in 64 bits.  The fast path is a piece of one row
+// already: it loads from the row's address (the row above at - pitch, the left sample at - 1); every other group goes through
+// classify_pitched.  Every load is a sample of the plane.
+template <typename T, typename F>
+__device__ __forceinline__ void for_my_events_pitched(const T *__restrict__ pl, uint32_t W, uint32_t npix, uint64_t pitch, F &&f) {
+    const uint32_t first = blockIdx.x * WT + threadIdx.x * 16u;
+    if (first >= npix) return;
+    Coord xy;
+    xy.set(first, W);
+    if (xy.y > 0 && xy.x > 0 && xy.x + 16u <= W && first + 16u <= npix) {
+        const T *at = pl + (uint64_t)xy.y * pitch + xy.x;
+        T cur[16], up[16];
+        __builtin_memcpy(cur, at, sizeof cur);
+        __builtin_memcpy(up, at - pitch, sizeof up);
+        int left = (int)at[-1];
+#pragma unroll
+        for (uint32_t j = 0; j < 16u; j++) {
+            const PixelClass pc = classify_values((int)cur[j], left, (int)up[j]);
+            if (pc.cls != CLS_IN) f(j, first + j, pc);
+            left = (int)cur[j];
+        }
+        return;
+    }
+    for (uint32_t j = 0; j < 16u && first + j < npix; j++) {
+        const uint32_t i = first + j;
+        if (i >= 2) {
+            const PixelClass pc = classify_pitched(pl, xy.x, xy.y, pitch);
+            if (pc.cls != CLS_IN) f(j, i, pc);
+        }
+        xy.advance(1, W);
+    }
+}
+// (PITCH = NoPitch: the dense plane, for_my_events as it stands; uint64_t: the pitch in samples)
+template <typename T, typename F>
+__device__ __forceinline__ void my_events(const T *__restrict__ pl, uint32_t W, uint32_t npix, NoPitch, F &&f) {
+    for_my_events(pl, W, npix, f);
+}
+template <typename T, typename F>
+__device__ __forceinline__ void my_events(const T *__restrict__ pl, uint32_t W, uint32_t npix, uint64_t pitch, F &&f) {
+    for_my_events_pitched(pl, W, npix, pitch, f);
+}
+
 // Where plane blockIdx.y of a sub-batch lies and how large it is.  Uniform: every plane W x (npix / W), back to back from `planes`.
 // Mixed (Geometry::mixed, 16-bit images of different shapes in one sub-batch): the plane's PlaneGeom row -- the plane is
 // workgroup-uniform, so these are scalar loads.  The grid is (T_max, planes): a tile at or past the plane's own end finds
@@ -142,11 +207,12 @@ __device__ __forceinline__ WidePlane<T> wide_plane(const PlaneGeom *__restrict__
     return WidePlane<T>{(const T *)pg->samples, pg->W, pg->npix};
 }
 
-template <typename T>
-__device__ __forceinline__ void wide_count_tile(const T *__restrict__ pl, uint32_t W, uint32_t npix, uint32_t *__restrict__ tile_cnt) {
+template <typename T, typename PITCH = NoPitch>
+__device__ __forceinline__ void wide_count_tile(const T *__restrict__ pl, uint32_t W, uint32_t npix, uint32_t *__restrict__ tile_cnt,
+                                                PITCH pitch = PITCH{}) {
     __shared__ uint32_t wsum[WTHREADS / 64];
     uint32_t n = 0;
-    for_my_events(pl, W, npix, [&](uint32_t, uint32_t, const PixelClass &) { n++; });
+    my_events(pl, W, npix, pitch, [&](uint32_t, uint32_t, const PixelClass &) { n++; });
     uint32_t total;
     (void)block_excl_scan(n, wsum, &total);
     if (threadIdx.x == 0) tile_cnt[blockIdx.y * gridDim.x + blockIdx.x] = total;
@@ -160,6 +226,11 @@ template <typename T>
 __global__ __launch_bounds__(WTHREADS) void k_wide_count_mixed(const PlaneGeom *__restrict__ table, uint32_t *__restrict__ tile_cnt) {
     const WidePlane<T> p = wide_plane<T>(table);
     wide_count_tile(p.pl, p.W, p.npix, tile_cnt);
+}
+// gray16 planes read where they lie: the plane and its pitch from the PitchedGeom16 row
+__global__ __launch_bounds__(WTHREADS) void k_wide_count_pitched(const PitchedGeom16 *__restrict__ rows, uint32_t *__restrict__ tile_cnt) {
+    const PitchedGeom16 *pg = rows + blockIdx.y;
+    wide_count_tile((const uint16_t *)pg->g.samples, pg->g.W, pg->g.npix, tile_cnt, pg->pitch);
 }
 
 // One workgroup: exclusive scan of the tile counts (plane-major) in place; per plane its first record, its
@@ -205,16 +276,16 @@ __global__ __launch_bounds__(1024) void k_wide_plan(uint32_t *__restrict__ tile_
     }
 }
 
-template <typename T>
+template <typename T, typename PITCH = NoPitch>
 __device__ __forceinline__ void wide_emit_tile(const T *__restrict__ pl, uint32_t W, uint32_t npix, const uint32_t *__restrict__ tile_base,
-                                               uint64_t *__restrict__ recs) {
+                                               uint64_t *__restrict__ recs, PITCH pitch = PITCH{}) {
     __shared__ uint32_t wsum[WTHREADS / 64];
     // classify once: the thread's records wait in registers for their place (raster order: thread by thread)
     uint64_t mine[16];
     uint32_t n = 0;
 #pragma unroll
     for (uint32_t j = 0; j < 16u; j++) mine[j] = ~0ull;
-    for_my_events(pl, W, npix, [&](uint32_t j, uint32_t i, const PixelClass &pc) {
+    my_events(pl, W, npix, pitch, [&](uint32_t j, uint32_t i, const PixelClass &pc) {
         // (j is a compile-time constant on the fast path; the general path is rare enough for a select chain)
 #pragma unroll
         for (uint32_t q = 0; q < 16u; q++)
@@ -244,6 +315,11 @@ __global__ __launch_bounds__(WTHREADS) void k_wide_emit_mixed(const PlaneGeom *_
                                                               uint64_t *__restrict__ recs) {
     const WidePlane<T> p = wide_plane<T>(table);
     wide_emit_tile(p.pl, p.W, p.npix, tile_base, recs);
+}
+__global__ __launch_bounds__(WTHREADS) void k_wide_emit_pitched(const PitchedGeom16 *__restrict__ rows, const uint32_t *__restrict__ tile_base,
+                                                                uint64_t *__restrict__ recs) {
+    const PitchedGeom16 *pg = rows + blockIdx.y;
+    wide_emit_tile((const uint16_t *)pg->g.samples, pg->g.W, pg->g.npix, tile_base, recs, pg->pitch);
 }
 
 // Which plane a sort tile belongs to, and its record range.
@@ -865,6 +941,12 @@ void launch_rgb16_to_planes_mixed(hipStream_t s, const PlaneGeom *table, uint32_
     FELICS_LAUNCH(k_rgb16_to_planes_mixed, dim3(bx, nimg), dim3(256), s, table);
 }
 
+void launch_rgb16_view_to_planes(hipStream_t s, const PlaneGeom *table, const ViewRow *rows, uint32_t max_npix, uint32_t nimg) {
+    if (!nimg || !max_npix) return;
+    const uint32_t bx = std::max(1u, std::min(cdiv(max_npix, 256), 256u));
+    FELICS_LAUNCH(k_rgb16_view_to_planes, dim3(bx, nimg), dim3(256), s, table, rows);
+}
+
 WideSizes wide_sizes(const Geometry &g) {
     WideSizes z;
     const uint64_t nsamples = (uint64_t)g.nplanes * g.npix;
@@ -882,6 +964,14 @@ WideSizes wide_sizes(const Geometry &g) {
 template <typename T>
 void launch_wide_events(hipStream_t s, const T *planes, uint32_t *tile_cnt, uint32_t *meta, uint64_t *recs, const Geometry &g) {
     const WideSizes z = wide_sizes(g);
+    if constexpr (std::is_same<T, uint16_t>::value) {
+        if (g.mixed && g.pitched16) {  // (the mixed launches below with the pitched rows)
+            FELICS_LAUNCH(k_wide_count_pitched, dim3(z.px_tiles, g.nplanes), dim3(WTHREADS), s, g.pitched16, tile_cnt);
+            FELICS_LAUNCH(k_wide_plan, dim3(1), dim3(1024), s, tile_cnt, z.px_tiles, g.nplanes, meta);
+            FELICS_LAUNCH(k_wide_emit_pitched, dim3(z.px_tiles, g.nplanes), dim3(WTHREADS), s, g.pitched16, tile_cnt, recs);
+            return;
+        }
+    }
     if (g.mixed) {  // (px_tiles = T_max; everything behind k_wide_emit sees the padded npix as the stride of k_map only)
         FELICS_LAUNCH((k_wide_count_mixed<T>), dim3(z.px_tiles, g.nplanes), dim3(WTHREADS), s, g.mixed, tile_cnt);
         FELICS_LAUNCH(k_wide_plan, dim3(1), dim3(1024), s, tile_cnt, z.px_tiles, g.nplanes, meta);

@@ -98,7 +98,7 @@ int felics_compress_batch(felics_ctx *ctx, size_t n, const void *const *pixels, 
  * On FELICS_E_BUFFER_TOO_SMALL lens[0] holds the capacity needed.
  * The library works on HIP streams of its own (created non-blocking): the frames must be COMPLETE in memory when the
  * call is made -- synchronise the stream that produced them first (hipStreamSynchronize / an event the host has
- * waited for); the same holds for felics_submit_batch_device and for the streams handed to
+ * waited for); the same holds for felics_submit_batch_device (felics_submit_surfaces_device takes a producer event instead) and for the streams handed to
  * felics_decompress_batch_device.  What the library wrote is complete when the blocking call / felics_wait_batch returns. */
 int felics_compress_batch_device(felics_ctx *ctx, size_t n, const void *d_pixels, uint32_t w,
                                  uint32_t h, int color, int depth, void *d_out,
@@ -115,6 +115,7 @@ int felics_compress_batch_device(felics_ctx *ctx, size_t n, const void *d_pixels
 int felics_submit_batch_device(felics_ctx *ctx, size_t n, const void *d_pixels, uint32_t w,
                                uint32_t h, int color, int depth, void *d_out, size_t d_out_cap,
                                int *ticket);
+/* (also serves the tickets of felics_submit_surfaces_device) */
 int felics_wait_batch(felics_ctx *ctx, int ticket, uint64_t *offsets, uint64_t *lens);
 
 /* One image of a mixed-shape batch: its own size, colour and depth. */
@@ -173,7 +174,8 @@ typedef struct felics_view {
  *   in place  : gray8 with pixel_stride = 1 and row_stride >= width (the kernels take the row pitch), and RGB8 of ANY strides
  *               (the plane transform reads the view; the Y / Co / Cg planes it writes exist for dense frames as well);
  *   gathered  : everything else -- gray8 with another pixel stride or a row stride below the width, every 16-bit view -- is copied
- *               to a dense frame in a staging buffer of the context first (one kernel).  So is a view of a sub-batch that has to
+ *               to a dense frame in a staging buffer of the context first (one kernel; felics_submit_surfaces_device reads 16-bit
+ *               surfaces in place).  So is a view of a sub-batch that has to
  *               be redone (a remedy of felics_stats).
  * The call is blocking: the streams are complete when it returns. */
 int felics_compress_views_device(felics_ctx *ctx, size_t n, const felics_view *views, void *ready_event, void *d_out,
@@ -194,6 +196,71 @@ typedef struct felics_view_stats {
 } felics_view_stats;
 /* Writes min(out_size, sizeof(felics_view_stats)) bytes, never more: a caller built against a shorter struct stays valid. */
 int felics_get_view_stats(const felics_ctx *ctx, felics_view_stats *out, size_t out_size);
+
+/* n frames of ONE shape, a fixed stride apart, in any layout a view can describe: the ring of pitched surfaces a capture or decode
+ * pipeline on the GPU holds, the windows of an N x H x W tensor, the images of an N x C x H x W batch.  Frame i is the view frame0
+ * with data + i * frame_stride. */
+typedef struct felics_surfaces {
+    felics_view frame0;    /* frame 0, with the meaning felics_view has */
+    int64_t frame_stride;  /* bytes from sample (x, y, c) of frame i to the same sample of frame i + 1; signed, 0 legal (the frames are only
+                              read); a multiple of 2 at depth 16 */
+    uint64_t count;        /* n frames */
+} felics_surfaces;
+
+/* Host only, no context: felics_view_extent's checks on frame0, then the frame axis (an even frame_stride at depth 16, an extent
+ * that fits 64 bits: FELICS_E_INVALID_ARGUMENT), and the half-open byte range [*lo, *hi) relative to frame0.data that an encode of the
+ * n frames may read -- the hull of all their samples; both 0 for count == 0 or a zero-sized frame.  Where the kernels read such
+ * surfaces in place they load samples only, one at a time or as aligned 16-byte words made of samples and pad bytes of ONE row
+ * (8-bit surfaces: the words of felics_compress_views_device's in-place class, which lie inside the hull or are aligned 16-byte words
+ * that also hold a byte of it); pad bytes may be read and are never interpreted. */
+int felics_surfaces_extent(const felics_surfaces *s, int64_t *lo, int64_t *hi);
+
+/* felics_submit_batch_device for surfaces, behind a producer event: queues the batch and returns; felics_wait_batch(ticket) fills
+ * offsets / lens (s->count entries each).  Stream i is byte-identical to felics_compress of the dense copy of frame i.  The descriptor
+ * is copied at the call; the surfaces, d_out and the event must stay valid and untouched until the ticket has been waited for.
+ * Every argument is checked before anything is launched (felics_surfaces_extent's checks and the size limits of
+ * felics_compress_images; NULL pointers and count == 0: FELICS_E_INVALID_ARGUMENT; count > 2^24: FELICS_E_UNSUPPORTED; FELICS_E_HIP on a
+ * failed context); with every lane
+ * holding a ticket it returns FELICS_E_INVALID_ARGUMENT.  Tickets of felics_submit_batch_device and of this call share the lanes
+ * (felics_ctx_lane_count) and the waiting order, and the synchronous entry points refuse to run while either kind is outstanding.
+ *   ready_event : as in felics_compress_views_device -- a hipEvent_t recorded behind whatever produces the surfaces and last used
+ *                 d_out, or NULL.  Every stream of the library waits for it before its first read of a surface or write of d_out;
+ *                 the caller does not synchronise the host.  NULL: the surfaces are complete in memory when the call is made.
+ * The call creates no HIP stream.
+ * QUEUED (the kernels read the surfaces where they lie, nothing is staged) when all of these hold:
+ *   - the layout can be read in place: gray8 with pixel_stride = 1 and row_stride >= width; RGB8 of any strides; gray16 with
+ *     pixel_stride = 2 and row_stride >= 2 * width; RGB16 of any (even) strides;
+ *   - the frames are not zero-sized and count fits one sub-batch (8192 frames, fewer for large frames: the pass bound of
+ *     felics_compress_images);
+ *   - d_out_cap holds count slots of felics_compress_images_device's size (frame bytes * 1.25 + 64, rounded up to 16): stream i is
+ *     then at i * slot;
+ *   - the context is not on the two-pass kernels (felics_stats).
+ *   A descriptor that is exactly the dense back-to-back layout of felics_submit_batch_device takes that call's path as it is (its
+ *   slots: (d_out_cap / count) & ~15), with the event in front of its first kernel: the event-ordered form of that call.
+ *   A queued sub-batch that needs a remedy of felics_stats is redone at the wait from gathered frames (counted in bytes_staged);
+ *   after a slot overflow the streams are placed exactly, back to back, in d_out; if d_out cannot hold them the wait returns
+ *   FELICS_E_BUFFER_TOO_SMALL and lens[0] holds the capacity needed.
+ * IMMEDIATE: everything else is encoded during the call and handed over at the wait, with the result felics_compress_views_device
+ *   gives for the n views -- its classes, its exact placement, FELICS_E_BUFFER_TOO_SMALL with lens[0] -- counted in
+ *   felics_surface_stats and not in felics_view_stats. */
+int felics_submit_surfaces_device(felics_ctx *ctx, const felics_surfaces *s, void *ready_event, void *d_out, size_t d_out_cap, int *ticket);
+
+/* Submit and wait in one blocking call; offsets / lens are HOST arrays of s->count entries.  Refused (FELICS_E_INVALID_ARGUMENT) while
+ * a ticket is outstanding; count == 0 returns FELICS_OK. */
+int felics_compress_surfaces_device(felics_ctx *ctx, const felics_surfaces *s, void *ready_event, void *d_out, size_t d_out_cap,
+                                    uint64_t *offsets, uint64_t *lens);
+
+/* What became of a context's surface submissions so far (cumulative). */
+typedef struct felics_surface_stats {
+    uint64_t submissions;      /* calls of the two functions above that passed the checks (count > 0) */
+    uint64_t queued;           /* ... that were queued */
+    uint64_t immediate;        /* ... that were encoded during the call */
+    uint64_t frames_in_place;  /* frames read where they lay (dense descriptors included) */
+    uint64_t frames_gathered;  /* frames of immediate submissions that were copied to a dense frame first */
+    uint64_t bytes_staged;     /* bytes written by such copies, those of redone sub-batches included */
+} felics_surface_stats;
+/* Writes min(out_size, sizeof(felics_surface_stats)) bytes, never more. */
+int felics_get_surface_stats(const felics_ctx *ctx, felics_surface_stats *out, size_t out_size);
 
 /* Replaces `read_header` (format.rs:63-84). */
 int felics_read_header(const uint8_t *in, size_t len, felics_header *hdr);
