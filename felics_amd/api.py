@@ -98,6 +98,14 @@ class _CDecodeStats(C.Structure):  # felics_decode_stats
                 ("host", C.c_uint64), ("undecoded", C.c_uint64), ("lanes16_table_bytes", C.c_uint64)]
 
 
+class _CIndexStats(C.Structure):  # felics_index_stats
+    _fields_ = [("streams", C.c_uint64), ("segments8", C.c_uint64)]
+
+
+INDEX_GRANULE = 4096  # FELICS_INDEX_GRANULE
+E_INVALID_INDEX = -12
+
+
 class Header:  # format.rs:44-49
     def __init__(self, color_type, pixel_depth, width, height):
         self.color_type = ColorType(color_type)
@@ -126,6 +134,8 @@ EXPORTS = [
     "felics_get_decode_stats", "felics_decode_lanes_min_streams",
     "felics_decompress_views_device", "felics_view_writable", "felics_get_decode_view_stats",
     "felics_surfaces_extent", "felics_submit_surfaces_device", "felics_compress_surfaces_device", "felics_get_surface_stats",
+    "felics_index_size", "felics_index_build", "felics_decompress_indexed", "felics_decompress_batch_device_indexed",
+    "felics_get_index_stats", "felics_compress_batch_device_indexed",
 ]
 
 _lib = None
@@ -201,6 +211,15 @@ def lib():
     L.felics_get_decode_view_stats.argtypes = [vp, C.POINTER(_CDecodeViewStats), sz]
     L.felics_decode_lanes_min_streams.argtypes = [C.c_int, C.c_int]
     L.felics_decode_lanes_min_streams.restype = C.c_uint32
+    L.felics_index_size.argtypes = [C.c_uint32, C.c_uint32, C.c_int, C.c_int, C.c_uint32]
+    L.felics_index_size.restype = sz
+    L.felics_index_build.argtypes = [vp, sz, C.c_uint32, vp, sz, C.POINTER(sz)]
+    L.felics_decompress_indexed.argtypes = [vp, sz, vp, sz, vp, sz, C.POINTER(_CHeader)]
+    L.felics_decompress_batch_device_indexed.argtypes = [vp, sz, vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), vp, sz, vp, sz,
+                                                        C.POINTER(_CHeader), C.POINTER(C.c_int)]
+    L.felics_compress_batch_device_indexed.argtypes = [vp, sz, vp, C.c_uint32, C.c_uint32, C.c_int, C.c_int, vp, sz, C.c_uint32, vp, sz,
+                                                      C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+    L.felics_get_index_stats.argtypes = [vp, C.POINTER(_CIndexStats), sz]
     L.felics_strerror.argtypes = [C.c_int]
     L.felics_strerror.restype = C.c_char_p
     L.felics_last_error.argtypes = [vp]
@@ -546,6 +565,20 @@ class Encoder:
             self._raise(rc)
         return offs, lens
 
+    def compress_batch_device_indexed(self, d_pixels, n, w, h, color, depth, d_out, d_out_cap, segment_pixels, d_index, d_index_cap):
+        """felics_compress_batch_device_indexed: compress_batch_device plus the restart index of stream i at
+        d_index + i * index_size(w, h, color, depth, segment_pixels) (raw device pointers).  Returns (offsets, lens)."""
+        offs = np.zeros(n, dtype=np.uint64)
+        lens = np.zeros(n, dtype=np.uint64)
+        rc = lib().felics_compress_batch_device_indexed(
+            self._h, n, d_pixels, w, h, int(color), int(depth), d_out, d_out_cap, segment_pixels, d_index, d_index_cap,
+            offs.ctypes.data_as(C.POINTER(C.c_uint64)), lens.ctypes.data_as(C.POINTER(C.c_uint64)))
+        if rc == -8:
+            raise FelicsError(rc, "need %d bytes" % int(lens[0]) if lens[0] else "the index buffer is too small")
+        if rc != 0:
+            self._raise(rc)
+        return offs, lens
+
     def submit_batch_device(self, d_pixels, n, w, h, color, depth, d_out, d_out_cap):
         """Queues a batch and returns a ticket; up to two can be in flight (felics_submit_batch_device)."""
         ticket = C.c_int(-1)
@@ -585,6 +618,24 @@ class Encoder:
             raise err
         if rc != 0:
             self._raise(rc)
+        return Header(ch.color_type, ch.pixel_depth, ch.width, ch.height), status
+
+    def decompress_batch_device_indexed(self, d_streams, offsets, lens, d_index, index_stride, d_pixels, d_pixels_cap):
+        """felics_decompress_batch_device_indexed: streams of one shape, their restart indexes (index i at d_index + i * index_stride)
+        and the pixels in device memory (raw pointers); a wave per (stream, plane, segment).  Returns (Header, status array); raises
+        DecompressionError with the first failing stream's code if it is a stream error, FelicsError otherwise (both carry .status)."""
+        offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+        lens = np.ascontiguousarray(lens, dtype=np.uint64)
+        n = len(offsets)
+        status = np.zeros(n, dtype=np.int32)
+        ch = _CHeader()
+        rc = lib().felics_decompress_batch_device_indexed(
+            self._h, n, d_streams, offsets.ctypes.data_as(C.POINTER(C.c_uint64)), lens.ctypes.data_as(C.POINTER(C.c_uint64)),
+            d_index, index_stride, d_pixels, d_pixels_cap, C.byref(ch), status.ctypes.data_as(C.POINTER(C.c_int)))
+        if rc != 0:
+            err = DecompressionError(rc) if rc in DecompressionError.KINDS else FelicsError(rc, lib().felics_last_error(self._h).decode() if rc == -9 else "")
+            err.status = status
+            raise err
         return Header(ch.color_type, ch.pixel_depth, ch.width, ch.height), status
 
     def read_headers_device(self, d_streams, offsets, lens):
@@ -679,7 +730,14 @@ class Encoder:
         rc = lib().felics_get_decode_stats(self._h, C.byref(st), C.sizeof(st))
         if rc != 0:
             self._raise(rc)
-        return {k: int(getattr(st, k)) for k, _ in _CDecodeStats._fields_}
+        out = {k: int(getattr(st, k)) for k, _ in _CDecodeStats._fields_}
+        # (felics_index_stats: the segments decompress_batch_device_indexed gave a wave each, n * C * K)
+        ist = _CIndexStats()
+        rc = lib().felics_get_index_stats(self._h, C.byref(ist), C.sizeof(ist))
+        if rc != 0:
+            self._raise(rc)
+        out["segments8"] = int(ist.segments8)
+        return out
 
     def lane_count(self):
         """felics_ctx_lane_count: submissions this context can have in flight (fixed when it was created)."""
@@ -805,6 +863,48 @@ def decompress_with_header(from_, header):
                                              out.ctypes.data if out.size else None, out.nbytes)
     if rc != 0:
         raise DecompressionError(rc)
+    return out
+
+
+def index_size(width, height, color, depth, segment_pixels):
+    """felics_index_size: bytes of the restart index of a width x height image; 0 if there is none (16-bit, bad segment_pixels)."""
+    return int(lib().felics_index_size(width, height, int(color), int(depth), segment_pixels))
+
+
+def index_build(data, segment_pixels):
+    """felics_index_build: the restart index (bytes) of an 8-bit stream, built by decoding it once on the CPU."""
+    arr = np.frombuffer(bytes(data), dtype=np.uint8)
+    need = C.c_size_t(0)
+    L = lib()
+    rc = L.felics_index_build(arr.ctypes.data if len(arr) else None, len(arr), segment_pixels, None, 0, C.byref(need))
+    if rc == 0:
+        return b""
+    if rc != -8:
+        raise DecompressionError(rc) if rc in DecompressionError.KINDS else FelicsError(rc)
+    out = np.zeros(need.value, dtype=np.uint8)
+    rc = L.felics_index_build(arr.ctypes.data, len(arr), segment_pixels, out.ctypes.data, out.nbytes, C.byref(need))
+    if rc != 0:
+        raise DecompressionError(rc) if rc in DecompressionError.KINDS else FelicsError(rc)
+    return out[:need.value].tobytes()
+
+
+def decompress_indexed(data, index):
+    """felics_decompress_indexed: the image of an 8-bit stream, decoded segment by segment through its restart index."""
+    arr = np.frombuffer(bytes(data), dtype=np.uint8)
+    idx = np.frombuffer(bytes(index), dtype=np.uint8)
+    ch = _CHeader()
+    rc = lib().felics_read_header(arr.ctypes.data if len(arr) else None, len(arr), C.byref(ch))
+    if rc != 0:
+        raise DecompressionError(rc)
+    planes = 3 if ch.color_type else 1
+    if ch.width * ch.height * planes > max(len(arr), 1) * 8 + 2 * planes:  # a pixel costs at least one bit
+        raise DecompressionError(-1)
+    shape = (ch.height, ch.width, 3) if planes == 3 else (ch.height, ch.width)
+    out = np.zeros(shape, dtype=np.uint16 if ch.pixel_depth else np.uint8)
+    rc = lib().felics_decompress_indexed(arr.ctypes.data, len(arr), idx.ctypes.data if len(idx) else None, len(idx),
+                                         out.ctypes.data if out.size else None, out.nbytes, None)
+    if rc != 0:
+        raise DecompressionError(rc) if rc in DecompressionError.KINDS else FelicsError(rc)
     return out
 
 

@@ -274,6 +274,7 @@ void felics_ctx_destroy(felics_ctx *ctx) {
     release(ctx->mix_redo);
     release(ctx->view_stage);
     release(ctx->dec_meta);
+    release(ctx->dec_seg_status);
     release(ctx->dec_planes);
     release(ctx->dec_planes16);
     release(ctx->dec_table);
@@ -313,6 +314,7 @@ const char *felics_strerror(int code) {
         case FELICS_E_HIP: return "no usable HIP device or HIP runtime error";
         case FELICS_E_UNSUPPORTED: return "not supported by the GPU encoder in this build";
         case FELICS_E_INVALID_ARGUMENT: return "invalid argument";
+        case FELICS_E_INVALID_INDEX: return "restart index is malformed or does not fit the stream";
         default: return "unknown error";
     }
 }

@@ -13,112 +13,11 @@
 #include <vector>
 
 #include "../../include/felics.h"
+#include "felics_hostdec.h"
 
 namespace {
 
-// MSB-first bit reader over a byte range (bitstream-io BitReader<_, BigEndian> semantics).
-class BitReader {
-  public:
-    BitReader(const uint8_t *p, size_t n) : p_(p), end_(p + n) {}
-
-    bool failed() const { return failed_; }
-
-    uint32_t bit() {
-        if (have_ == 0 && !refill()) return 0;
-        have_--;
-        return (uint32_t)(window_ >> have_) & 1u;
-    }
-
-    // up to 32 bits, most significant first
-    uint32_t bits(unsigned n) {
-        uint64_t v = 0;
-        while (n) {
-            if (have_ == 0 && !refill()) return 0;
-            const unsigned take = n < have_ ? n : have_;  // <= 32
-            have_ -= take;
-            v = (v << take) | ((window_ >> have_) & ((1ull << take) - 1ull));
-            n -= take;
-        }
-        return (uint32_t)v;
-    }
-
-    // read_unary0: number of one-bits before the first zero-bit
-    uint32_t unary0() {
-        uint32_t q = 0;
-        for (;;) {
-            if (have_ == 0 && !refill()) return q;
-            // count leading ones of the `have_` unread bits
-            uint64_t unread = window_ << (64 - have_);
-            unsigned ones = unread == ~0ull ? 64 : (unsigned)__builtin_clzll(~unread);
-            if (ones >= have_) {
-                q += have_;
-                have_ = 0;
-                continue;
-            }
-            q += ones;
-            have_ -= ones + 1;
-            return q;
-        }
-    }
-
-  private:
-    bool refill() {
-        if (p_ == end_) {
-            failed_ = true;
-            return false;
-        }
-        window_ = 0;
-        have_ = 0;
-        while (p_ != end_ && have_ <= 48) {
-            window_ = (window_ << 8) | *p_++;
-            have_ += 8;
-        }
-        return true;
-    }
-
-    const uint8_t *p_, *end_;
-    uint64_t window_ = 0;  // low `have_` bits are unread, MSB of them first
-    unsigned have_ = 0;
-    bool failed_ = false;
-};
-
-struct Options {  // traits.rs:25-43
-    uint32_t max_context;
-    unsigned nk;  // k in 0..nk-1
-};
-
-// KEstimator (parameter_selection.rs:24-85) with a flat table.
-class Estimator {
-  public:
-    Estimator(const Options &o) : nk_(o.nk), table_((size_t)(o.max_context + 1) * o.nk, 0u) {}
-
-    unsigned get_k(uint32_t ctx) const {
-        const uint32_t *row = &table_[(size_t)ctx * nk_];
-        uint32_t best = row[0];
-        unsigned k = 0;
-        for (unsigned i = 1; i < nk_; i++)
-            if (row[i] <= best) {  // ties: last wins
-                best = row[i];
-                k = i;
-            }
-        return k;
-    }
-
-    void update(uint32_t ctx, uint32_t v) {
-        uint32_t *row = &table_[(size_t)ctx * nk_];
-        uint32_t mn = 0xFFFFFFFFu;
-        for (unsigned i = 0; i < nk_; i++) {
-            row[i] += (v >> i) + 1 + i;
-            if (row[i] < mn) mn = row[i];
-        }
-        if (mn > 1024)
-            for (unsigned i = 0; i < nk_; i++) row[i] >>= 1;
-    }
-
-  private:
-    unsigned nk_;
-    std::vector<uint32_t> table_;
-};
+using namespace felics_hostdec;  // BitReader, Options, Estimator, decode_span
 
 // decompress_channel (compression.rs:151-248)
 int decode_plane(BitReader &br, uint32_t W, uint32_t H, const Options &opt, std::vector<int32_t> &out) {
@@ -141,54 +40,7 @@ int decode_plane(BitReader &br, uint32_t W, uint32_t H, const Options &opt, std:
     out[0] = p0;
     out[1] = p1;
     Estimator est(opt);
-    uint32_t x = 2 % W, y = 2 / W;
-    for (size_t i = 2; i < (size_t)total; i++) {
-        size_t a, b;  // misc.rs:6-24
-        if (x > 0 && y > 0) {
-            a = i - 1;
-            b = i - W;
-        } else if (y == 0) {
-            a = i - 1;
-            b = i - 2;
-        } else if (y >= 2) {
-            a = i - W;
-            b = i - 2 * (size_t)W;
-        } else {
-            a = i - W;
-            b = i - W + 1;
-        }
-        const int64_t v1 = out[a], v2 = out[b];
-        const int64_t hi = v1 > v2 ? v1 : v2, lo = v1 < v2 ? v1 : v2;
-        if (hi - lo > (int64_t)opt.max_context) return FELICS_E_INVALID_VALUE;
-        const uint32_t ctx = (uint32_t)(hi - lo);
-        int64_t pv;
-        if (br.bit()) {  // in range: phased-in code of p - L in [0, ctx]
-            const uint32_t n = ctx + 1;
-            const unsigned m = 31u - (unsigned)__builtin_clz(n);
-            const uint32_t right_p = (2u << m) - n, left_p = n - (1u << m);
-            uint32_t r = br.bits(m);
-            if (r >= right_p) r = (r - right_p) * 2 + right_p + br.bit();
-            pv = lo + (int64_t)(((uint64_t)r + left_p) % n);  // rotate_left, phase_in_coding.rs:50-52
-        } else {
-            const bool above = br.bit() != 0;
-            const unsigned k = est.get_k(ctx);
-            const uint64_t q = br.unary0();
-            const uint64_t e = (q << k) + br.bits(k);
-            if (br.failed()) return FELICS_E_IO;
-            if (e > 0xFFFFFFFFull) return FELICS_E_VALUE_OVERFLOW;
-            est.update(ctx, (uint32_t)e);
-            if (e > 0x7FFFFFFFull) return FELICS_E_INVALID_VALUE;
-            pv = above ? hi + (int64_t)e + 1 : lo - (int64_t)e - 1;
-        }
-        if (br.failed()) return FELICS_E_IO;
-        if (pv > INT32_MAX || pv < INT32_MIN) return FELICS_E_VALUE_OVERFLOW;
-        out[i] = (int32_t)pv;
-        if (++x == W) {
-            x = 0;
-            y++;
-        }
-    }
-    return FELICS_OK;
+    return decode_span(br, W, opt, est, out.data(), 2, (size_t)total, nullptr);
 }
 
 template <typename S>

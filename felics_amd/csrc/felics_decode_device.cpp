@@ -1,6 +1,7 @@
 // felics_decode_device.cpp -- host side of the GPU decoder: streams of one shape (felics_decompress_batch_device), of any shapes
 // (felics_decompress_images_device), and their headers (felics_read_headers_device).
 #include "felics_host.h"
+#include "felics_index.h"
 
 namespace felics {
 
@@ -818,6 +819,76 @@ int felics_decompress_batch_device(felics_ctx *ctx, size_t n, const void *d_stre
         HIP_TRY(ctx, launch_decode8(s, (const uint8_t *)d_streams, d_off, d_len, (uint32_t)n, hdr.width, hdr.height, hdr.color_type,
                                     (uint8_t *)d_pixels, d_planes, d_status));
     }
+    HIP_TRY(ctx, hipMemcpyAsync(status, d_status, n * 4, hipMemcpyDeviceToHost, s));
+    HIP_TRY(ctx, hipStreamSynchronize(s));
+    for (size_t i = 0; i < n; i++)
+        if (status[i]) return status[i];
+    return FELICS_OK;
+}
+
+int felics_get_index_stats(const felics_ctx *ctx, felics_index_stats *out, size_t out_size) {
+    if (!ctx || !out) return FELICS_E_INVALID_ARGUMENT;
+    memcpy(out, &ctx->istats, std::min(out_size, sizeof(felics_index_stats)));
+    return FELICS_OK;
+}
+
+int felics_decompress_batch_device_indexed(felics_ctx *ctx, size_t n, const void *d_streams, const uint64_t *offsets, const uint64_t *lens,
+                                           const void *d_index, size_t index_stride, void *d_pixels, size_t d_pixels_cap, felics_header *hdr_out,
+                                           int *status) {
+    if (!ctx || (n && (!d_streams || !offsets || !lens || !d_index || !status))) return FELICS_E_INVALID_ARGUMENT;
+    if (ctx->failed) return FELICS_E_HIP;
+    if (n == 0) return FELICS_OK;
+    if (any_pending(ctx)) return FELICS_E_INVALID_ARGUMENT;  // felics_wait_batch first
+    if (((uintptr_t)d_index | index_stride) & 15u) return FELICS_E_INVALID_ARGUMENT;  // the kernel loads a checkpoint as aligned words
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    auto fail_all = [&](int code) {
+        for (size_t i = 0; i < n; i++) status[i] = code;
+        return code;
+    };
+    // the shape every stream must have: header of stream 0; how every index is cut: header of index 0
+    uint8_t h0[FELICS_HEADER_BYTES] = {0}, ih[INDEX_HEADER_BYTES];
+    const size_t hl = (size_t)std::min<uint64_t>(lens[0], FELICS_HEADER_BYTES);
+    if (hl) HIP_TRY(ctx, hipMemcpy(h0, (const uint8_t *)d_streams + offsets[0], hl, hipMemcpyDeviceToHost));
+    felics_header hdr;
+    int rc = felics_read_header(h0, hl, &hdr);
+    if (rc) return fail_all(rc);
+    if (hdr_out) *hdr_out = hdr;
+    if (hdr.pixel_depth != FELICS_DEPTH_8) return fail_all(FELICS_E_UNSUPPORTED);  // 16-bit streams have no index
+    const uint32_t planes = hdr.color_type == FELICS_COLOR_RGB ? 3 : 1;
+    const uint64_t npix = (uint64_t)hdr.width * hdr.height;
+    if (npix > 0xFFFFFFFFull) return fail_all(FELICS_E_INVALID_DIMENSIONS);
+    const uint64_t frame_bytes = npix * planes;
+    if (frame_bytes * n > d_pixels_cap) return fail_all(FELICS_E_BUFFER_TOO_SMALL);
+    if (frame_bytes && !d_pixels) return fail_all(FELICS_E_INVALID_ARGUMENT);
+    if (decode8_lds_bytes(hdr.width, hdr.color_type) > DECODE_LDS_LIMIT) return fail_all(FELICS_E_UNSUPPORTED);  // no host fallback here
+    if (index_stride < INDEX_HEADER_BYTES) return fail_all(FELICS_E_INVALID_INDEX);
+    HIP_TRY(ctx, hipMemcpy(ih, d_index, INDEX_HEADER_BYTES, hipMemcpyDeviceToHost));
+    IndexLayout L;
+    if (index_header_check(ih, hdr.color_type, hdr.width, hdr.height, lens[0], L) != FELICS_OK || L.total > index_stride)
+        return fail_all(FELICS_E_INVALID_INDEX);
+    const uint32_t seg = idx_rd32(ih + IDX_SEGPIX);
+    const uint64_t per = (uint64_t)planes * std::max(L.K, 1u);
+    if (n > 0x7FFFFFFFull / per) return fail_all(FELICS_E_UNSUPPORTED);  // one block per segment
+    // offsets | lens | status on the device; a word per segment beside them
+    if ((rc = reserve(ctx, ctx->dec_meta, n * 8 * 2 + n * 4)) != 0) return fail_all(rc);
+    if ((rc = reserve(ctx, ctx->dec_seg_status, (size_t)(n * per) * 4)) != 0) return fail_all(rc);
+    uint64_t *d_off = (uint64_t *)ctx->dec_meta.p, *d_len = d_off + n;
+    int *d_status = (int *)(d_len + n);
+    int16_t *d_planes = nullptr;
+    if (planes == 3) {
+        if ((rc = reserve(ctx, ctx->dec_planes, (size_t)(npix * 3 * 2 * n) + 64)) != 0) return fail_all(rc);
+        d_planes = (int16_t *)ctx->dec_planes.p;
+    }
+    ctx->istats.streams += n;
+    ctx->istats.segments8 += n * planes * L.K;
+    hipStream_t s = ctx->lanes[0].stream;
+    for (size_t i = 0; i < n; i++) status[i] = FELICS_E_HIP;  // until the kernel's own word arrives
+    HIP_TRY(ctx, hipMemcpyAsync(d_off, offsets, n * 8, hipMemcpyHostToDevice, s));
+    HIP_TRY(ctx, hipMemcpyAsync(d_len, lens, n * 8, hipMemcpyHostToDevice, s));
+    HIP_TRY(ctx, hipMemsetAsync(d_status, 0xFF, n * 4, s));
+    HIP_TRY(ctx, hipMemsetAsync(ctx->dec_seg_status.p, 0xFF, (size_t)(n * per) * 4, s));
+    HIP_TRY(ctx, launch_decode8_seg(s, (const uint8_t *)d_streams, d_off, d_len, (const uint8_t *)d_index, index_stride, (uint32_t)n, hdr.width,
+                                    hdr.height, hdr.color_type, seg, L.K, (uint8_t *)d_pixels, d_planes, (int *)ctx->dec_seg_status.p, d_status));
     HIP_TRY(ctx, hipMemcpyAsync(status, d_status, n * 4, hipMemcpyDeviceToHost, s));
     HIP_TRY(ctx, hipStreamSynchronize(s));
     for (size_t i = 0; i < n; i++)

@@ -3,6 +3,7 @@
 //
 // Encode is GPU-only by design: there is no CPU encode path in this library.
 #include "felics_host.h"
+#include "felics_index.h"
 
 namespace felics {
 
@@ -89,6 +90,7 @@ int run_lane(felics_ctx *ctx, Lane &l, uint8_t *d_out, uint64_t slot_stride) {
     const TileLocal<ET> tloc{(ET *)l.evs.p, (uint16_t *)l.pix_of.p, (uint8_t *)l.k_sorted.p, (uint32_t *)l.counts.p, (uint32_t *)l.tile_slots.p, cap};
     l.m_tickets = ctx->pack_tickets;
     l.m_fused = fused;
+    l.m_cap = cap;
 
     uint32_t bounds[SLICES + 1];  // slice boundaries in sort tiles (= pack tiles)
     for (int q = 0; q <= ns; q++) bounds[q] = (uint32_t)((uint64_t)g.sort_tiles * q / ns);
@@ -473,7 +475,8 @@ int apply_remedy(felics_ctx *ctx, const Lane &l, const SlotOutcome &o) {
 // Encode `n` same-shape frames resident in device memory into d_out (device), on one lane, and wait.
 // If d_out is NULL the context's own output buffer is used (and grown).
 int encode_device(felics_ctx *ctx, Lane &l, size_t n, const void *d_pixels, uint32_t w, uint32_t h, int color, int depth,
-                  uint8_t *d_out, size_t d_out_cap, uint64_t *offsets, uint64_t *lens, uint8_t **used_out, bool start_exact) {
+                  uint8_t *d_out, size_t d_out_cap, uint64_t *offsets, uint64_t *lens, uint8_t **used_out, bool start_exact,
+                  const IndexRequest *index) {
     const uint32_t planes = color == FELICS_COLOR_RGB ? 3 : 1;
     const uint64_t npix = (uint64_t)w * h;
     const bool wide = depth == FELICS_DEPTH_16;
@@ -577,6 +580,16 @@ int encode_device(felics_ctx *ctx, Lane &l, size_t n, const void *d_pixels, uint
                 }
                 out_base = need;
             }
+            if (index && !outcome.redo() && !outcome.overflow) {
+                // The pass has packed (in its slots, or exactly just now) and is what the caller gets: its restart indexes, from the
+                // run table, the records' states, the tiles' bit offsets and the planes, all still in the lane's workspace.  (A pass
+                // that is redone by a remedy comes here again and rewrites them.)
+                uint8_t *at = index->d_index + done * index->bytes;
+                HIP_TRY(ctx, hipMemsetAsync(at, 0, (size_t)(cnt * index->bytes), l.tail));
+                launch_index_emit(l.tail, l.d_planes, (const uint32_t *)l.counts.p, (const uint4 *)l.block_state.p, l.m_cap,
+                                  (const uint64_t *)l.tile_bitoff.p, l.plane_base, l.plane_base - l.g.nplanes, l.g, at, index->segment_pixels);
+                HIP_TRY(ctx, hipGetLastError());
+            }
             if ((rc = sync_lane(ctx, l)) != 0) return rc;
             done = first;
         }
@@ -607,6 +620,42 @@ int felics_compress_batch_device(felics_ctx *ctx, size_t n, const void *d_pixels
     if (any_pending(ctx)) return FELICS_E_INVALID_ARGUMENT;  // felics_wait_batch first
     return encode_device(ctx, ctx->lanes[0], n, d_pixels, w, h, color, depth, (uint8_t *)d_out, d_out_cap, offsets, lens,
                          nullptr);
+}
+
+int felics_compress_batch_device_indexed(felics_ctx *ctx, size_t n, const void *d_pixels, uint32_t w, uint32_t h, int color, int depth, void *d_out,
+                                         size_t d_out_cap, uint32_t segment_pixels, void *d_index, size_t d_index_cap, uint64_t *offsets,
+                                         uint64_t *lens) {
+    if (!ctx || !offsets || !lens || !d_out || !d_index || (!d_pixels && n && (uint64_t)w * h)) return FELICS_E_INVALID_ARGUMENT;
+    if (ctx->failed) return FELICS_E_HIP;
+    int rc = check_args(w, h, color, depth);
+    if (rc) return rc;
+    if (depth != FELICS_DEPTH_8) return FELICS_E_UNSUPPORTED;  // 16-bit streams have no index
+    const size_t bytes = felics_index_size(w, h, color, depth, segment_pixels);
+    if (bytes == 0 || ((uintptr_t)d_index & 15u)) return FELICS_E_INVALID_ARGUMENT;
+    if (n == 0) return FELICS_OK;
+    if (any_pending(ctx)) return FELICS_E_INVALID_ARGUMENT;  // felics_wait_batch first
+    if (d_index_cap / bytes < n) return FELICS_E_BUFFER_TOO_SMALL;
+    const IndexRequest req{(uint8_t *)d_index, bytes, segment_pixels};
+    rc = encode_device(ctx, ctx->lanes[0], n, d_pixels, w, h, color, depth, (uint8_t *)d_out, d_out_cap, offsets, lens, nullptr, false, &req);
+    if (rc == FELICS_OK && (uint64_t)w * h == 0) {
+        // an empty image (K = 0) is encoded on the host and so is its index: the header, every plane its two raw samples long
+        std::vector<uint8_t> ih(bytes, 0);
+        IndexLayout L = index_layout(w, h, (uint32_t)color, segment_pixels);
+        memcpy(ih.data(), "FLCX", 4);
+        ih[IDX_VERSION] = INDEX_VERSION;
+        ih[IDX_COLOR] = (uint8_t)color;
+        for (int k = 0; k < 4; k++) {
+            ih[IDX_WIDTH + k] = (uint8_t)(w >> (8 * k));
+            ih[IDX_HEIGHT + k] = (uint8_t)(h >> (8 * k));
+            ih[IDX_SEGPIX + k] = (uint8_t)(segment_pixels >> (8 * k));
+        }
+        for (uint32_t c = 0; c < L.planes; c++) {
+            const uint64_t end = STREAM_HEADER_BITS + 64u * (c + 1);
+            for (int k = 0; k < 8; k++) ih[IDX_PLANE_END + 8 * c + k] = (uint8_t)(end >> (8 * k));
+        }
+        for (size_t i = 0; i < n; i++) HIP_TRY(ctx, hipMemcpy((uint8_t *)d_index + i * bytes, ih.data(), bytes, hipMemcpyHostToDevice));
+    }
+    return rc;
 }
 
 int felics_submit_batch_device(felics_ctx *ctx, size_t n, const void *d_pixels, uint32_t w, uint32_t h, int color,

@@ -22,6 +22,7 @@
 
 #include "../../include/felics.h"
 #include "felics_device.h"
+#include "felics_index.h"
 #include "felics_kernels.h"
 
 namespace felics {
@@ -71,6 +72,28 @@ struct ScalarBits {
             acc <<= 8u * skew;
             navail -= 8u * skew;
         }
+    }
+    // the same, positioned `bit` bits behind p (bit <= 8 n: the caller's check, so the first chunk fetched holds a stream byte or lies
+    // right behind the last one; like every fetch it is bounded by total_dw)
+    __device__ __forceinline__ void init_at(const uint8_t *p, uint64_t n, uint64_t bit) {
+        const uint32_t skew = (uint32_t)(reinterpret_cast<uintptr_t>(p) & 3u);
+        al = reinterpret_cast<const uint32_t *>(p - skew);
+        total_dw = (skew + n + 3u) >> 2;
+        end_bit = (skew + n) * 8u;
+        const uint64_t at = 8u * skew + bit, dw = at >> 5;
+        chunk0 = dw & ~63ull;
+        cur = fetch(chunk0);
+        nxt = fetch(chunk0 + 64u);
+        cpos = (uint32_t)(dw - chunk0);
+        acc = 0;
+        navail = 0;
+        refill();
+        acc <<= (uint32_t)(at & 31u);
+        navail -= (uint32_t)(at & 31u);
+    }
+    // bits consumed so far, counted from p (the pointer init / init_at was given)
+    __device__ __forceinline__ uint64_t pos(const uint8_t *p) const {
+        return (chunk0 + cpos) * 32u - navail - 8u * (uint32_t)(reinterpret_cast<uintptr_t>(p) & 3u);
     }
     // at least 33 valid bits in acc afterwards (zeros past the end of the stream)
     __device__ __forceinline__ void refill() {
@@ -345,6 +368,229 @@ __global__ __launch_bounds__(64) void k_decode8(const uint8_t *__restrict__ stre
     }
     if (br.failed()) rc = FELICS_E_IO;  // (whatever else stopped the decoding: it was decoding padding)
     if (lane == 0) status[img] = rc;
+}
+
+// ------------------------------------------------------------------------------------------
+// One wave per SEGMENT of a plane of a stream (felics_decompress_batch_device_indexed; the restart index: felics.h, felics_index.h).
+//
+// k_decode8's walk, started in the middle of a plane from a checkpoint: the LDS table comes out of the checkpoint's counters, the two
+// LDS rows out of its window of 2 W samples, (x, y) from the segment's first pixel p0, the bit reader is positioned on its
+// bit_offset.  Block b is segment (img, c, j) = (b / (C Keff), b / Keff % C, b % Keff), Keff = max(K, 1): an empty image has no
+// checkpoint, and its pseudo segment reads the plane's two raw samples only.  Every check of felics.h is made here: the stream's
+// header, the index header against it and against the launch's (segment_pixels, K: what the host sized the index by, so that no
+// checkpoint is read outside index_stride), the segment's bit range, the window's samples, and at the end that the reader stands
+// exactly on the next checkpoint.  seg_status[b] = FELICS_OK or the code; k_seg_status picks a stream's first.
+// The per-pixel path is k_decode8's, statement for statement (that kernel is left as it is: the unindexed call is what this one is
+// measured against); what differs is where the walk starts, where it ends, and that a 64-sample block is stored from the segment's
+// first pixel on and up to its last one only -- the samples before and behind belong to other waves.
+// LDS (dynamic): as k_decode8 (decode8_lds_bytes).
+// ------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(64) void k_decode8_seg(const uint8_t *__restrict__ streams, const uint64_t *__restrict__ offsets,
+                                                    const uint64_t *__restrict__ lens, const uint8_t *__restrict__ index, uint64_t index_stride,
+                                                    DecUniform geo, uint32_t segment_pixels, uint32_t K, uint8_t *__restrict__ pixels,
+                                                    int16_t *__restrict__ planes, int *__restrict__ seg_status) {
+    extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
+    const uint32_t W = geo.W, H = geo.H, color = geo.color;
+    const uint32_t nplanes = color ? 3u : 1u, keff = max(K, 1u);
+    const uint32_t img = blockIdx.x / (nplanes * keff), c = blockIdx.x / keff % nplanes, j = blockIdx.x % keff;
+    uint32_t *table = reinterpret_cast<uint32_t *>(smem);
+    const uint32_t nctx = color ? nctx_of<int16_t>() : nctx_of<uint8_t>();
+    int16_t *rows = reinterpret_cast<int16_t *>(smem + nctx * 6 * 4);
+    const uint32_t rstride = decode8_row_stride(W);
+    const uint32_t lane = lane_id();
+    const uint8_t *s = streams + offsets[img];
+    const uint64_t slen = lens[img];
+    const uint8_t *idx = index + (uint64_t)img * index_stride;
+    const uint64_t npix = (uint64_t)W * H;
+    // the stream's header (format.rs:63-84) must be the one the caller announced, the index header must fit both
+    int rc = FELICS_OK;
+    IndexLayout L;
+    uint64_t start = 0, end = 0;
+    if (slen < FELICS_HEADER_BYTES) {
+        rc = FELICS_E_IO;
+    } else {
+        const uint32_t w = ((uint32_t)s[6] << 24) | ((uint32_t)s[7] << 16) | ((uint32_t)s[8] << 8) | s[9];
+        const uint32_t h = ((uint32_t)s[10] << 24) | ((uint32_t)s[11] << 16) | ((uint32_t)s[12] << 8) | s[13];
+        if (s[0] != 'F' || s[1] != 'L' || s[2] != 'C' || s[3] != 'S') rc = FELICS_E_INVALID_SIGNATURE;
+        else if (s[4] > 1) rc = FELICS_E_INVALID_COLOR_TYPE;
+        else if (s[5] > 1) rc = FELICS_E_INVALID_PIXEL_DEPTH;
+        else if (s[4] != color || s[5] != 0 || w != W || h != H) rc = FELICS_E_INVALID_DIMENSIONS;
+        else if (index_header_check(idx, color, W, H, slen, L) != FELICS_OK || idx_rd32(idx + IDX_SEGPIX) != segment_pixels || L.K != K)
+            rc = FELICS_E_INVALID_INDEX;
+        else
+            rc = index_segment_bounds(idx, L, c, j, slen, start, end);
+    }
+    rc = unii(rc);
+    if (rc != FELICS_OK) {
+        if (lane == 0) seg_status[blockIdx.x] = rc;
+        return;
+    }
+    const uint64_t p0 = (uint64_t)j * segment_pixels, pend = min(npix, p0 + segment_pixels);  // this segment's pixels
+    uint32_t x = 0, y = 0;
+    int16_t *cur = rows, *prev = rows + rstride;
+    if (K) {
+        // the checkpoint: counters (u16 pairs -> u32 rows), then the window into the two rows -- with (x0, y0) = p0's place, window
+        // sample t is pixel p0 - 2 W + t: row y0 from t = 2 W - x0 on (cur), row y0 - 1 from t = W - x0 on (prev), and in front of that
+        // row y0 - 2, of which only (0, y0 - 2) is ever looked at, and only if x0 = 0 (the first-column rule: what cur[0] holds)
+        const uint8_t *cp = idx + INDEX_HEADER_BYTES + ((uint64_t)c * K + j) * L.cp_bytes;
+        const uint32_t *st = reinterpret_cast<const uint32_t *>(cp + CP_STATE_OFF);  // (index and checkpoints are 16-byte aligned)
+        for (uint32_t i = lane; i < nctx * 3; i += 64) {
+            const uint32_t w2 = st[i];
+            table[2 * i] = w2 & 0xFFFFu;
+            table[2 * i + 1] = w2 >> 16;
+        }
+        x = (uint32_t)(p0 % W);
+        y = (uint32_t)(p0 / W);
+        const uint8_t *win = cp + L.win_off;
+        const int lo_w = color && c ? -255 : 0;
+        bool bad = false;
+        for (uint64_t t = lane; t < 2ull * W; t += 64) {
+            if (p0 + t < 2ull * W) continue;  // in front of the plane: zeros, never looked at
+            const int v = color ? (int)reinterpret_cast<const int16_t *>(win)[t] : (int)win[t];
+            bad |= v < lo_w || v > 255;
+            if (t >= 2ull * W - x) cur[t - (2ull * W - x)] = (int16_t)v;
+            else if (t >= (uint64_t)W - x) prev[t - ((uint64_t)W - x)] = (int16_t)v;
+            else if (t == 0 && x == 0) cur[0] = (int16_t)v;
+        }
+        if (__ballot(bad) != 0) {
+            if (lane == 0) seg_status[blockIdx.x] = FELICS_E_INVALID_INDEX;
+            return;
+        }
+    }
+    __builtin_amdgcn_wave_barrier();
+    ScalarBits br;
+    br.init_at(s, slen, start);
+    int32_t raw0 = 0, raw1 = 0;
+    if (j == 0) {  // the plane's two raw samples (compression.rs:166-167) stand in front of its first segment only
+        raw0 = (int32_t)br.get(32);
+        raw1 = (int32_t)br.get(32);
+        if (br.failed()) rc = FELICS_E_IO;
+    }
+    if (rc == FELICS_OK && pend > p0) {
+        int16_t *outp = color ? planes + ((uint64_t)img * nplanes + c) * npix : nullptr;
+        uint8_t *outg = color ? nullptr : pixels + (uint64_t)img * npix;
+        const int lo_ok = color ? -255 : 0, hi_ok = 255;  // what a sample of this plane can be (Y 0..255, Co / Cg -255..255)
+        const uint32_t xl0 = x & 63u;
+        int upv = 0;   // VECTOR: prev[xb + lane] for the 64-sample block xb the walk stands in
+        int rowv = 0;  // VECTOR: the samples of this block decoded so far
+        if (xl0) {     // a start inside a block: the block's samples in front of it are the window's
+            if (y > 0) upv = (int)prev[(x & ~63u) + lane];
+            rowv = (int)cur[(x & ~63u) + lane];
+        }
+        int left = x >= 1 ? unii((int)cur[x - 1]) : 0, left2 = x >= 2 ? unii((int)cur[x - 2]) : 0;
+        int first_col2 = 0;  // cur[0] as it was before this row: the sample two rows up (first-column rule)
+        for (uint64_t i = p0; i < pend; i++) {
+            const uint32_t xl = x & 63u;
+            if (xl == 0) {
+                if (y > 0) upv = (int)prev[x + lane];  // (rows are padded to whole blocks)
+                if (x == 0 && y > 0) first_col2 = y >= 2 ? unii((int)cur[0]) : (W > 1 ? __builtin_amdgcn_readlane(upv, 1) : 0);
+            }
+            int pv;
+            if (i < 2) {
+                pv = i == 0 ? raw0 : raw1;
+            } else {
+                const int above = __builtin_amdgcn_readlane(upv, (int)xl);
+                const bool row0 = y == 0, col0 = x == 0 && !row0;  // misc.rs:6-24 with selects
+                const int v1 = col0 ? above : left;
+                const int v2 = col0 ? first_col2 : (row0 ? left2 : above);
+                const int hi = max(v1, v2), lo = min(v1, v2);
+                const uint32_t ctx = (uint32_t)(hi - lo);  // <= 510 because every stored sample is in range
+                br.refill();  // >= 33 bits: an in-range code has at most 11, the two flags of the other kind 2
+                if (br.take(1)) {  // in range: phased-in code of p - L (phase_in_coding.rs:86-112)
+                    const uint32_t n = ctx + 1;
+                    const uint32_t m = 31u - (uint32_t)__builtin_clz(n);
+                    const uint32_t right_p = (2u << m) - n, left_p = n - (1u << m);
+                    uint32_t r = br.take(m);
+                    const uint32_t longer = r >= right_p ? 1u : 0u;  // the code has one more bit
+                    const uint32_t r2 = (r - right_p) * 2u + right_p + br.take(longer);
+                    r = longer ? r2 : r;
+                    uint32_t rot = r + left_p;  // rotate_left: (r + left_p) mod n, r < n
+                    rot = rot >= n ? rot - n : rot;
+                    pv = lo + (int)rot;
+                } else {
+                    const bool above_flag = br.take(1) != 0;
+                    const uint64_t *row = reinterpret_cast<const uint64_t *>(table + ctx * 6);  // 24-byte rows: 8-byte aligned
+                    const uint64_t r01 = row[0], r23 = row[1], r45 = row[2];                 // one LDS round trip for the row
+                    uint32_t S[6] = {uni((uint32_t)r01), uni((uint32_t)(r01 >> 32)), uni((uint32_t)r23),
+                                     uni((uint32_t)(r23 >> 32)), uni((uint32_t)r45), uni((uint32_t)(r45 >> 32))};
+                    // get_k: smallest counter, ties to the largest k (parameter_selection.rs:71-85)
+                    const uint32_t key = min(min(min((S[0] << 3) | 7u, (S[1] << 3) | 6u), min((S[2] << 3) | 5u, (S[3] << 3) | 4u)),
+                                             min((S[4] << 3) | 3u, (S[5] << 3) | 2u));
+                    const uint32_t k = 7u - (key & 7u);
+                    const uint64_t q = br.unary0();
+                    const uint64_t e64 = (q << k) + br.get(k);
+                    if (e64 > 1024u) {  // no sample of an 8-bit plane is that far from its neighbours
+                        rc = e64 > 0xFFFFFFFFull ? FELICS_E_VALUE_OVERFLOW : FELICS_E_INVALID_VALUE;
+                        break;
+                    }
+                    const uint32_t e = (uint32_t)e64;
+                    uint32_t mn = 0xFFFFFFFFu;
+#pragma unroll
+                    for (uint32_t kk = 0; kk < 6; kk++) {
+                        S[kk] += (e >> kk) + 1u + kk;
+                        mn = min(mn, S[kk]);
+                    }
+                    const uint32_t hsh = mn > 1024u ? 1u : 0u;
+                    uint64_t *wrow = reinterpret_cast<uint64_t *>(table + ctx * 6);  // (every lane: same address, same value)
+                    wrow[0] = (uint64_t)(S[0] >> hsh) | ((uint64_t)(S[1] >> hsh) << 32);
+                    wrow[1] = (uint64_t)(S[2] >> hsh) | ((uint64_t)(S[3] >> hsh) << 32);
+                    wrow[2] = (uint64_t)(S[4] >> hsh) | ((uint64_t)(S[5] >> hsh) << 32);
+                    pv = above_flag ? hi + (int)e + 1 : lo - (int)e - 1;
+                }
+            }
+            if (pv < lo_ok || pv > hi_ok) {  // try_into::<u8>() / the estimator's context bound would fail
+                rc = FELICS_E_INVALID_VALUE;
+                break;
+            }
+            rowv = lane == xl ? pv : rowv;
+            left2 = left;
+            left = pv;
+            const bool row_end = x + 1 == W;
+            if (xl == 63u || row_end || i + 1 == pend) {  // a block of the row is complete, or the segment is
+                const uint32_t xb = x & ~63u;
+                if (xb + lane <= x) {
+                    cur[xb + lane] = (int16_t)rowv;  // (lanes in front of a mid-block start store back what they loaded)
+                    const uint64_t at = (uint64_t)y * W + xb + lane;  // < pend: xb + lane <= x
+                    if (at >= p0) {  // the samples in front of p0 are the segment's before this one
+                        if (outg) outg[at] = (uint8_t)rowv;
+                        else outp[at] = (int16_t)rowv;
+                    }
+                }
+            }
+            if (row_end) {
+                if (br.failed()) {
+                    rc = FELICS_E_IO;
+                    break;
+                }
+                __builtin_amdgcn_wave_barrier();
+                x = 0;
+                y++;
+                int16_t *t = cur;
+                cur = prev;
+                prev = t;
+            } else {
+                x++;
+            }
+        }
+    }
+    if (br.failed()) rc = FELICS_E_IO;  // (whatever else stopped the decoding: it was decoding padding)
+    else if (rc == FELICS_OK && br.pos(s) != end) rc = FELICS_E_INVALID_INDEX;  // the end check: exactly on the next checkpoint
+    if (lane == 0) seg_status[blockIdx.x] = rc;
+}
+
+// status[i] = the code of stream i's first failing segment in (plane, segment) order; one wave per stream over its `per` words
+__global__ __launch_bounds__(64) void k_seg_status(const int *__restrict__ seg_status, uint32_t per, int *__restrict__ status) {
+    __shared__ uint32_t first;
+    if (threadIdx.x == 0) first = 0xFFFFFFFFu;
+    __syncthreads();
+    const int *mine = seg_status + (uint64_t)blockIdx.x * per;
+    for (uint32_t k = threadIdx.x; k < per; k += 64)
+        if (mine[k] != FELICS_OK) {
+            atomicMin(&first, k);
+            break;
+        }
+    __syncthreads();
+    if (threadIdx.x == 0) status[blockIdx.x] = first == 0xFFFFFFFFu ? FELICS_OK : mine[first];
 }
 
 // ------------------------------------------------------------------------------------------
@@ -1466,6 +1712,28 @@ hipError_t launch_decode8(hipStream_t s, const uint8_t *streams, const uint64_t 
     }
     hipLaunchKernelGGL(k_decode8<DecUniform>, dim3(n), dim3(64), lds, s, streams, offsets, lens, DecUniform{W, H, color}, pixels, planes,
                        status);
+    if (color) {
+        const uint64_t npix = (uint64_t)W * H;
+        const uint32_t bx = (uint32_t)std::min<uint64_t>((npix + 255) / 256, 1024u);
+        if (bx) hipLaunchKernelGGL(k_ycocg8_to_rgb<ConvUniform>, dim3(bx, n), dim3(256), 0, s, planes, pixels, ConvUniform{(uint32_t)npix}, status);
+    }
+    return hipGetLastError();
+}
+
+hipError_t launch_decode8_seg(hipStream_t s, const uint8_t *streams, const uint64_t *offsets, const uint64_t *lens, const uint8_t *index,
+                              uint64_t index_stride, uint32_t n, uint32_t W, uint32_t H, uint32_t color, uint32_t segment_pixels, uint32_t K,
+                              uint8_t *pixels, int16_t *planes, int *seg_status, int *status) {
+    if (n == 0) return hipSuccess;
+    const uint32_t lds = decode8_lds_bytes(W, color);
+    if (lds > 64u * 1024u) {
+        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&k_decode8_seg), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                                 (int)DECODE_LDS_LIMIT);
+        if (e != hipSuccess) return e;
+    }
+    const uint32_t per = (color ? 3u : 1u) * std::max(K, 1u);  // (n * per < 2^31: the caller's check)
+    hipLaunchKernelGGL(k_decode8_seg, dim3(n * per), dim3(64), lds, s, streams, offsets, lens, index, index_stride, DecUniform{W, H, color},
+                       segment_pixels, K, pixels, planes, seg_status);
+    hipLaunchKernelGGL(k_seg_status, dim3(n), dim3(64), 0, s, seg_status, per, status);
     if (color) {
         const uint64_t npix = (uint64_t)W * H;
         const uint32_t bx = (uint32_t)std::min<uint64_t>((npix + 255) / 256, 1024u);

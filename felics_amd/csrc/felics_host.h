@@ -109,6 +109,7 @@ struct Lane {
     int nslices = SLICES;             // slices its tiles are cut into (see felics_ctx::slices_*)
     bool m_tickets = false;           // the sub-batch's pack kernels took their tiles by ticket (what a look-back failure escalates from)
     bool m_fused = false;             // ... and were the single-pass kernels at all
+    uint32_t m_cap = 0;               // slots per tile of its tile-local layout (8-bit: what indexes state16; launch_index_emit)
     bool queued = false;              // this sub-batch came through felics_submit_batch_device (other submissions share the GPU with it)
     Geometry g;
     size_t first_image = 0;
@@ -196,6 +197,9 @@ struct felics_ctx {
     // or writes a view: wait_ready), view_stage holds the dense frames of its scattered class, dvstats the counts of
     // felics_get_decode_view_stats
     felics_decode_view_stats dvstats = {};
+    // felics_decompress_batch_device_indexed: a status word per (stream, plane, segment); the counts of felics_get_index_stats
+    DevBuf dec_seg_status;
+    felics_index_stats istats = {};
 };
 
 namespace felics {
@@ -238,8 +242,15 @@ int launch_sub_batch(felics_ctx *ctx, Lane &l, size_t first, size_t cnt, const v
 SlotOutcome decode_status(const felics_ctx *ctx, const Lane &l, uint64_t word);
 SlotOutcome read_sizes(felics_ctx *ctx, Lane &l, bool wide, uint64_t slot, uint64_t *offsets, uint64_t *lens);
 int apply_remedy(felics_ctx *ctx, const Lane &l, const SlotOutcome &o);
+// (index: felics_compress_batch_device_indexed -- 8-bit frames; every pass that comes out usable leaves the restart indexes of its images)
+struct IndexRequest {
+    uint8_t *d_index;         // image i's index at d_index + i * bytes
+    uint64_t bytes;           // felics_index_size of the shape
+    uint32_t segment_pixels;
+};
 int encode_device(felics_ctx *ctx, Lane &l, size_t n, const void *d_pixels, uint32_t w, uint32_t h, int color, int depth, uint8_t *d_out,
-                  size_t d_out_cap, uint64_t *offsets, uint64_t *lens, uint8_t **used_out, bool start_exact = false);
+                  size_t d_out_cap, uint64_t *offsets, uint64_t *lens, uint8_t **used_out, bool start_exact = false,
+                  const IndexRequest *index = nullptr);
 
 // the slot a stream gets unless the caller's buffer dictates another: the frame's size and a quarter, 16-byte aligned
 inline uint64_t default_slot(size_t frame_bytes) { return ((uint64_t)frame_bytes + frame_bytes / 4 + 64 + 15) & ~15ull; }

@@ -1,0 +1,108 @@
+// felics_index.h -- layout of the restart index (include/felics.h), for the host builder / decoder
+// (felics_index.cpp), the host side of the device call and the segment kernel alike.  Little-endian throughout.
+#ifndef FELICS_INDEX_H
+#define FELICS_INDEX_H
+
+#include <stddef.h>
+#include <stdint.h>
+
+#include "../../include/felics.h"
+
+#ifdef __HIPCC__
+#define FELICS_IDX_HD __host__ __device__
+#else
+#define FELICS_IDX_HD
+#endif
+
+namespace felics {
+
+constexpr uint32_t INDEX_HEADER_BYTES = 64;
+constexpr uint32_t INDEX_VERSION = 1;
+// byte offsets of the header's fields: "FLCX" | u16 version | u8 colour | u8 depth | u32 width | u32 height | u32 segment_pixels |
+// u32 K | u64 plane_end_bit[3] | 16 reserved zero bytes
+constexpr uint32_t IDX_VERSION = 4, IDX_COLOR = 6, IDX_DEPTH = 7, IDX_WIDTH = 8, IDX_HEIGHT = 12, IDX_SEGPIX = 16, IDX_K = 20, IDX_PLANE_END = 24,
+                   IDX_RESERVED = 48;
+constexpr uint64_t STREAM_HEADER_BITS = 8ull * FELICS_HEADER_BYTES;  // 112: where plane 0 starts
+
+// A checkpoint: u64 bit_offset | u16 state[nctx][6] | window[2 W] (u8 gray, i16 Y / Co / Cg) | zeros up to a multiple of 16.
+// Checkpoint (plane c, segment j) lies at INDEX_HEADER_BYTES + (c * K + j) * cp_bytes.
+struct IndexLayout {
+    uint32_t planes, nctx, K;
+    uint32_t sample_bytes;  // of a window sample
+    uint64_t win_off;       // of the window in a checkpoint (the state is at CP_STATE_OFF)
+    uint64_t cp_bytes;
+    uint64_t total;         // bytes of the whole index
+};
+constexpr uint32_t CP_STATE_OFF = 8;
+
+FELICS_IDX_HD inline bool index_segment_ok(uint32_t segment_pixels) {
+    return segment_pixels >= FELICS_INDEX_GRANULE && segment_pixels % FELICS_INDEX_GRANULE == 0;
+}
+// (w * h < 2^32 and index_segment_ok: the caller's checks)
+FELICS_IDX_HD inline IndexLayout index_layout(uint32_t w, uint32_t h, uint32_t color, uint32_t segment_pixels) {
+    IndexLayout L;
+    L.planes = color ? 3u : 1u;
+    L.nctx = color ? 512u : 256u;
+    L.sample_bytes = color ? 2u : 1u;
+    const uint64_t npix = (uint64_t)w * h;
+    L.K = (uint32_t)((npix + segment_pixels - 1) / segment_pixels);
+    L.win_off = CP_STATE_OFF + (uint64_t)L.nctx * 6u * 2u;
+    L.cp_bytes = (L.win_off + 2ull * w * L.sample_bytes + 15u) & ~15ull;
+    L.total = INDEX_HEADER_BYTES + (uint64_t)L.planes * L.K * L.cp_bytes;
+    return L;
+}
+
+FELICS_IDX_HD inline uint32_t idx_rd16(const uint8_t *p) { return (uint32_t)p[0] | ((uint32_t)p[1] << 8); }
+FELICS_IDX_HD inline uint32_t idx_rd32(const uint8_t *p) { return idx_rd16(p) | (idx_rd16(p + 2) << 16); }
+FELICS_IDX_HD inline uint64_t idx_rd64(const uint8_t *p) { return (uint64_t)idx_rd32(p) | ((uint64_t)idx_rd32(p + 4) << 32); }
+
+// The checks of an index header against the stream's (felics.h): 0, or FELICS_E_INVALID_INDEX.  `ih` holds INDEX_HEADER_BYTES bytes;
+// the stream is 8-bit (FELICS_E_UNSUPPORTED is the caller's answer otherwise) with w * h < 2^32.  On success L is the layout the
+// header names, and the caller compares L.total with the bytes it was given.
+FELICS_IDX_HD inline int index_header_check(const uint8_t *ih, uint32_t color, uint32_t w, uint32_t h, uint64_t stream_len, IndexLayout &L) {
+    if (ih[0] != 'F' || ih[1] != 'L' || ih[2] != 'C' || ih[3] != 'X' || idx_rd16(ih + IDX_VERSION) != INDEX_VERSION) return FELICS_E_INVALID_INDEX;
+    if (ih[IDX_COLOR] != color || ih[IDX_DEPTH] != FELICS_DEPTH_8 || idx_rd32(ih + IDX_WIDTH) != w || idx_rd32(ih + IDX_HEIGHT) != h)
+        return FELICS_E_INVALID_INDEX;
+    const uint32_t seg = idx_rd32(ih + IDX_SEGPIX);
+    if (!index_segment_ok(seg)) return FELICS_E_INVALID_INDEX;
+    L = index_layout(w, h, color, seg);
+    if (idx_rd32(ih + IDX_K) != L.K) return FELICS_E_INVALID_INDEX;
+    // the planes follow each other from the header on and the last one ends in the stream's last byte
+    uint64_t prev = STREAM_HEADER_BITS;
+    for (uint32_t c = 0; c < 3; c++) {
+        const uint64_t e = idx_rd64(ih + IDX_PLANE_END + 8 * c);
+        if (c >= L.planes) {
+            if (e) return FELICS_E_INVALID_INDEX;
+            continue;
+        }
+        if (e < prev + 64u || e > 8u * stream_len) return FELICS_E_INVALID_INDEX;  // (a plane holds its two raw samples at least)
+        prev = e;
+    }
+    if ((prev + 7u) / 8u != stream_len) return FELICS_E_INVALID_INDEX;
+    for (uint32_t i = IDX_RESERVED; i < INDEX_HEADER_BYTES; i++)
+        if (ih[i]) return FELICS_E_INVALID_INDEX;
+    return FELICS_OK;
+}
+
+// Where segment (c, j) must start and end, and what is wrong with that before a bit is decoded: 0, or FELICS_E_INVALID_INDEX.
+// idx: the whole index (header checked); K = 0 (an empty image) has one pseudo segment per plane, the two raw samples.
+FELICS_IDX_HD inline int index_segment_bounds(const uint8_t *idx, const IndexLayout &L, uint32_t c, uint32_t j, uint64_t stream_len, uint64_t &start,
+                                          uint64_t &end) {
+    const uint64_t plane_start = c ? idx_rd64(idx + IDX_PLANE_END + 8 * (c - 1)) : STREAM_HEADER_BITS;
+    const uint64_t plane_end = idx_rd64(idx + IDX_PLANE_END + 8 * c);
+    if (L.K == 0) {
+        start = plane_start;
+        end = plane_end;
+        return FELICS_OK;
+    }
+    const uint8_t *cp = idx + INDEX_HEADER_BYTES + ((uint64_t)c * L.K + j) * L.cp_bytes;
+    start = idx_rd64(cp);
+    end = j + 1 < L.K ? idx_rd64(cp + L.cp_bytes) : plane_end;
+    if (start < STREAM_HEADER_BITS || start > 8u * stream_len || end > 8u * stream_len || end < start) return FELICS_E_INVALID_INDEX;
+    if (j == 0 ? start != plane_start : start < idx_rd64(cp - L.cp_bytes)) return FELICS_E_INVALID_INDEX;
+    return FELICS_OK;
+}
+
+}  // namespace felics
+
+#endif

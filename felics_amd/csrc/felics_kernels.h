@@ -178,6 +178,20 @@ void launch_assign3(hipStream_t s, const TileLocal<ET> &tl, const uint4 *state16
 void launch_k_to_pixels_tl(hipStream_t s, const uint8_t *kq, const uint16_t *pix, const uint32_t *tile_slots, uint32_t cap, uint8_t *k_map,
                            const Geometry &g);
 
+// The restart index of every image of an 8-bit same-shape pass (felics_index.hip; format: felics.h, felics_index.h), from what the pass
+// leaves behind: runtab and state16 (the contexts' states at the checkpoints), tile_bitoff / plane_base / plane_carry (the bit
+// positions), the planes' samples (the windows).  index: image i's at index + i * felics_index_size(...), 16-byte aligned and
+// ZEROED beforehand.  Everything of the pass, packing included, has been queued on s or is complete.
+struct IndexEmit {
+    uint8_t *index;
+    uint64_t index_bytes, cp_bytes, win_off;  // bytes of an index, of a checkpoint; where its window starts
+    uint32_t W, H, npix, tiles, nctx, planes_per_image;
+    uint32_t K, seg_tiles;                    // checkpoints per plane, tiles between two of them
+    uint32_t color;
+};
+void launch_index_emit(hipStream_t s, const void *planes, const uint32_t *runtab, const uint4 *state16, uint32_t cap, const uint64_t *tile_bitoff,
+                       const uint64_t *plane_base, const uint64_t *plane_carry, const Geometry &g, uint8_t *index, uint32_t segment_pixels);
+
 // k_map / plane / slot buffers are read in whole 16-byte chunks by the tile staging
 constexpr size_t STAGE_PAD = 64;
 
@@ -274,6 +288,11 @@ hipError_t launch_decode8_lanes(hipStream_t s, const uint8_t *streams, const uin
                                 uint32_t W, uint32_t H, uint32_t color, uint8_t *pixels, int16_t *planes, uint32_t *table, int *status);
 hipError_t launch_decode8(hipStream_t s, const uint8_t *streams, const uint64_t *offsets, const uint64_t *lens, uint32_t n,
                           uint32_t W, uint32_t H, uint32_t color, uint8_t *pixels, int16_t *planes, int *status);
+// n streams of one shape, each with its restart index (felics.h; index i at index + i * index_stride, 16-byte aligned): one wave per
+// (stream, plane, segment), grid n * C * max(K, 1) < 2^31.  seg_status: a word per wave; status[i] = stream i's first failing one.
+hipError_t launch_decode8_seg(hipStream_t s, const uint8_t *streams, const uint64_t *offsets, const uint64_t *lens, const uint8_t *index,
+                              uint64_t index_stride, uint32_t n, uint32_t W, uint32_t H, uint32_t color, uint32_t segment_pixels, uint32_t K,
+                              uint8_t *pixels, int16_t *planes, int *seg_status, int *status);
 // The same for 16-bit streams, gray or RGB (k_decode16_lanes): 64 streams per wave, lane = stream; needs W >= 8 and a table of
 // decode16_lanes_table_bytes(n, W, H, color) bytes = n * planes * dec16l_rows(W * H, planes) * 64 (felics_lanetable.h: sized by the
 // pixel count, 512 KB per plane of a 64 x 64 stream, the wave form's 8.4 MB from 32 771 pixels on), zero-initialised ONCE: rows carry

@@ -1,0 +1,136 @@
+// index_fuzz -- sanitizer driver for the restart index's host functions (CPU only: felics_index.cpp + felics_decode.cpp, nothing
+// of HIP).  Every file NAME of a directory that does not end in ".idx" is taken as a stream:
+//   * felics_index_build at two segment sizes; where it succeeds, felics_decompress_indexed must give felics_decompress's pixels,
+//     and the index then goes through a few hundred byte mutations of its own (header fields, bit offsets, counters, window
+//     samples), each of which must be accepted or refused with a code;
+//   * if NAME.idx exists it is used as the index of NAME as it is (an index of the unmutated stream beside a mutated stream, a
+//     mutated index beside a good stream): any code, no crash.
+// Built with -fsanitize=address,undefined by `make asan`; tests/test_index_cpu.py feeds it a mutated corpus.
+// Exit code 0 = every input was handled without a sanitizer report and every accepted pair decoded to the right pixels.
+#include <dirent.h>
+
+#include <cstdio>
+#include <cstring>
+#include <string>
+#include <vector>
+
+#include "../../include/felics.h"
+
+static bool slurp(const std::string &p, std::vector<uint8_t> &b) {
+    FILE *f = fopen(p.c_str(), "rb");
+    if (!f) return false;
+    uint8_t chunk[1 << 16];
+    size_t got;
+    b.clear();
+    while ((got = fread(chunk, 1, sizeof chunk, f)) > 0) b.insert(b.end(), chunk, chunk + got);
+    fclose(f);
+    return true;
+}
+
+static bool ends_with(const std::string &s, const char *suffix) {
+    const size_t n = strlen(suffix);
+    return s.size() >= n && s.compare(s.size() - n, n, suffix) == 0;
+}
+
+int main(int argc, char **argv) {
+    if (argc < 2) {
+        fprintf(stderr, "usage: index_fuzz DIR\n");
+        return 2;
+    }
+    {  // argument checks
+        size_t n = 7;
+        uint8_t b[64] = {0};
+        int bad = 0;
+        bad += felics_index_build(nullptr, 5, 4096, b, sizeof b, &n) != FELICS_E_INVALID_ARGUMENT;
+        bad += felics_index_build(b, sizeof b, 4096, b, sizeof b, nullptr) != FELICS_E_INVALID_ARGUMENT;
+        bad += felics_decompress_indexed(nullptr, 5, b, sizeof b, b, sizeof b, nullptr) != FELICS_E_INVALID_ARGUMENT;
+        bad += felics_decompress_indexed(b, sizeof b, nullptr, 5, b, sizeof b, nullptr) != FELICS_E_INVALID_ARGUMENT;
+        bad += felics_index_size(1, 1, 0, 1, 4096) != 0 || felics_index_size(1, 1, 0, 0, 4095) != 0 || felics_index_size(1, 1, 2, 0, 4096) != 0;
+        bad += felics_index_size(0xFFFFFFFFu, 0xFFFFFFFFu, 1, 0, 4096) != 0;
+        if (bad) {
+            fprintf(stderr, "argument checks: %d unexpected results\n", bad);
+            return 1;
+        }
+    }
+    DIR *d = opendir(argv[1]);
+    if (!d) return 2;
+    std::vector<std::string> names;
+    while (dirent *e = readdir(d))
+        if (e->d_name[0] != '.' && !ends_with(e->d_name, ".idx")) names.push_back(e->d_name);
+    closedir(d);
+    size_t built = 0, refused = 0, mutations = 0, mut_accepted = 0, pairs = 0, pairs_ok = 0;
+    const size_t cap = 32u << 20;  // decoders and the builder get bounded buffers whatever a header claims
+    std::vector<uint8_t> buf, idx, given, px(cap), ref(cap), index(cap);
+    uint64_t rng = 0x9E3779B97F4A7C15ull;
+    auto next = [&]() {
+        rng ^= rng << 13;
+        rng ^= rng >> 7;
+        rng ^= rng << 17;
+        return rng;
+    };
+    for (const std::string &n : names) {
+        const std::string path = std::string(argv[1]) + "/" + n;
+        if (!slurp(path, buf)) continue;
+        felics_header h, h2;
+        const int rc_plain = felics_decompress(buf.data(), buf.size(), ref.data(), ref.size(), &h);
+        if (rc_plain == FELICS_E_BUFFER_TOO_SMALL) continue;  // (larger than this driver's buffers)
+        const size_t frame = rc_plain == FELICS_OK ? (size_t)h.width * h.height * (h.color_type ? 3 : 1) * (h.pixel_depth ? 2 : 1) : 0;
+        if (slurp(path + ".idx", given)) {
+            pairs++;
+            // (any code: a flipped bit that keeps a segment's length decodes through the index -- the damage ends at the next
+            // checkpoint -- where the plain decoder carries it on and fails; the checks do not prove the pairing, felics.h)
+            if (felics_decompress_indexed(buf.data(), buf.size(), given.data(), given.size(), px.data(), px.size(), &h2) == FELICS_OK) pairs_ok++;
+        }
+        for (uint32_t seg : {4096u, 12288u}) {
+            size_t ilen = 0;
+            const int rb = felics_index_build(buf.data(), buf.size(), seg, index.data(), index.size(), &ilen);
+            if (rb != FELICS_OK) {
+                refused++;
+                continue;
+            }
+            built++;
+            if (rc_plain != FELICS_OK) {
+                fprintf(stderr, "%s: an index was built of a stream felics_decompress refuses (%d)\n", n.c_str(), rc_plain);
+                return 1;
+            }
+            if (ilen != felics_index_size(h.width, h.height, h.color_type, h.pixel_depth, seg)) {
+                fprintf(stderr, "%s: index of %zu bytes, felics_index_size says otherwise\n", n.c_str(), ilen);
+                return 1;
+            }
+            size_t need = 0;  // a short buffer: refused with the size, nothing written behind it
+            if (ilen && (felics_index_build(buf.data(), buf.size(), seg, index.data() + ilen, ilen - 1, &need) != FELICS_E_BUFFER_TOO_SMALL || need != ilen)) {
+                fprintf(stderr, "%s: short buffer not refused with the size\n", n.c_str());
+                return 1;
+            }
+            const int rc = felics_decompress_indexed(buf.data(), buf.size(), index.data(), ilen, px.data(), px.size(), &h2);
+            if (rc != FELICS_OK || memcmp(px.data(), ref.data(), frame) != 0) {
+                fprintf(stderr, "%s: indexed decode %d, or other pixels than felics_decompress\n", n.c_str(), rc);
+                return 1;
+            }
+            idx.assign(index.begin(), index.begin() + ilen);
+            const int rounds = ilen > (1u << 20) ? 10 : 60;
+            for (int m = 0; m < rounds; m++) {
+                std::vector<uint8_t> bad = idx;
+                const int flips = 1 + (int)(next() % 3);
+                for (int f = 0; f < flips; f++) {
+                    // header fields, the first checkpoints' offsets, or anywhere
+                    const uint64_t r = next();
+                    const size_t pos = (r & 3) == 0 ? (size_t)(next() % 64) : ((r & 3) == 1 && ilen > 64 ? 64 + (size_t)(next() % 8) : (size_t)(next() % ilen));
+                    bad[pos] ^= (uint8_t)(1u << (next() % 8));
+                }
+                mutations++;
+                if (felics_decompress_indexed(buf.data(), buf.size(), bad.data(), bad.size(), px.data(), px.size(), &h2) == FELICS_OK) mut_accepted++;
+                if (m % 10 == 0) {  // and cut short
+                    const size_t cut = (size_t)(next() % ilen);
+                    if (felics_decompress_indexed(buf.data(), buf.size(), bad.data(), cut, px.data(), px.size(), &h2) == FELICS_OK) {
+                        fprintf(stderr, "%s: an index cut to %zu of %zu bytes was accepted\n", n.c_str(), cut, ilen);
+                        return 1;
+                    }
+                }
+            }
+        }
+    }
+    printf("index_fuzz: %zu files, %zu indexes built, %zu refused, %zu pairs (%zu accepted), %zu mutations (%zu accepted)\n", names.size(), built, refused,
+           pairs, pairs_ok, mutations, mut_accepted);
+    return 0;
+}

@@ -44,6 +44,7 @@ extern "C" {
 #define FELICS_E_HIP (-9)                 /* no device / HIP runtime error (see felics_last_error) */
 #define FELICS_E_UNSUPPORTED (-10)        /* valid request this build cannot run on the GPU (one image of >= 3.7 G samples; a 16-bit image of > 2^29 pixels) */
 #define FELICS_E_INVALID_ARGUMENT (-11)   /* NULL pointer, bad enum value */
+#define FELICS_E_INVALID_INDEX (-12)      /* a restart index is malformed or does not fit the stream it came with */
 
 /* format.rs:8-12 ColorType, format.rs:27-31 PixelDepth (wire values) */
 #define FELICS_COLOR_GRAY 0
@@ -351,6 +352,88 @@ int felics_get_decode_stats(const felics_ctx *ctx, felics_decode_stats *out, siz
  * 0xFFFFFFFF: no call does.  FELICS_TEST_DECODE16_LANES=1 / =0 in the environment (read per call) forces / forbids that form for
  * 16-bit streams whatever the count. */
 uint32_t felics_decode_lanes_min_streams(int depth, int color);
+
+/* ---- Restart index: one large 8-bit stream decoded on many waves ----
+ * A FELICS stream is bit-serial: the context and the Rice parameter of a pixel depend on everything decoded before it, so a stream
+ * decodes on one wave however large it is.  The restart index is a SIDECAR beside the unchanged .felics stream (the reference has no
+ * counterpart; a stream without one decodes as ever): for every `segment_pixels` pixels of every plane it holds what a decoder
+ * needs to start at that pixel -- the bit position, the estimator's counters, and the 2 W samples in front of it.  With it
+ * felics_decompress_batch_device_indexed gives every segment of every plane a wave of its own.
+ *
+ * Format (one blob per stream, little-endian).  segment_pixels is the caller's choice, a multiple of
+ * FELICS_INDEX_GRANULE and at least that; K = ceil(W * H / segment_pixels) segments per plane (K = 0 for an empty image).
+ *   header, 64 bytes : "FLCX" | u16 version = 1 | u8 colour | u8 depth (0) | u32 width | u32 height | u32 segment_pixels | u32 K |
+ *                      u64 plane_end_bit[3] (the bit behind plane c's last code, counted from the stream's first byte, header
+ *                      included; unused entries 0) | 16 reserved zero bytes
+ *   checkpoints      : for plane c = 0 .. C - 1, segment j = 0 .. K - 1, at 64 + (c * K + j) * S, S = the fields below rounded up to
+ *                      a multiple of 16 (zero padded).  With p0 = j * segment_pixels:
+ *       u64 bit_offset      : bits from the stream's first byte to the first bit of pixel p0's code; for j = 0 the plane's start, in
+ *                             front of its two raw 32-bit samples
+ *       u16 state[nctx][6]  : the KEstimator counters (parameter_selection.rs:24-85) of every context as they stand before pixel
+ *                             p0; nctx = 256 for gray, 512 for Y / Co / Cg (row 511 is zero); all zero for j = 0.  CANONICAL FORM:
+ *                             a context with no out-of-range pixel at or behind p0 in this plane is stored as zeros (its state is
+ *                             never read again).  Counters of planes that decode to 8-bit samples stay below 2^16 (e <= 510: a
+ *                             counter grows at most 511 / 21 times as fast as the one that triggers the halving at 1024)
+ *       window[2 W]         : the plane's samples p0 - 2 W .. p0 - 1 in raster order, zero where the index is negative; u8 for
+ *                             gray, i16 for Y / Co / Cg.  Two rows, not one: a segment that starts mid-row at (x0, y0) needs
+ *                             (0, y0 - 1) for the first pixel of row y0 + 1, one that starts at x0 = 0 needs (0, y0 - 2)
+ *                             (misc.rs:14-23)
+ * Checks, the same on the host and on the GPU; any failure is FELICS_E_INVALID_INDEX: magic, version, size = felics_index_size;
+ * colour, depth, width, height equal the stream header's; every bit_offset is >= 112 and <= 8 * len and ascends in (plane, segment)
+ * order, a plane's first one standing on the end of the plane before it; ceil(plane_end_bit[C - 1] / 8) = len; window samples are in
+ * the plane's range (Y 0..255, Co / Cg -255..255); and the END CHECK: a segment that has decoded its pixels stands exactly on the
+ * next checkpoint's bit_offset (plane_end_bit[c] for a plane's last segment).
+ * WHAT THE CHECKS DO NOT PROVE: an index that passes all of this but was built from another stream can still yield wrong pixels,
+ * as a corrupt stream can.  Pairing index and stream is the caller's contract.  No index makes the decoder read or write out of
+ * bounds.  16-bit streams have no index: every call here returns FELICS_E_UNSUPPORTED for them. */
+#define FELICS_INDEX_GRANULE 4096u
+
+/* Host only: the size of the index of a w x h 8-bit image; 0 for depth 16, a bad colour, w * h >= 2^32 or a segment_pixels that
+ * is not a positive multiple of FELICS_INDEX_GRANULE. */
+size_t felics_index_size(uint32_t w, uint32_t h, int color, int depth, uint32_t segment_pixels);
+
+/* Host only: builds the index of ANY 8-bit stream (files written by the reference included) by decoding it once on the CPU.
+ * `len` is the stream's exact length (bytes behind the last code: FELICS_E_INVALID_ARGUMENT).  Returns the stream's own decode
+ * error if the stream is bad, FELICS_E_INVALID_ARGUMENT for a bad segment_pixels, FELICS_E_BUFFER_TOO_SMALL with *index_len = the
+ * size needed if cap is short, FELICS_E_UNSUPPORTED for a 16-bit stream or a counter that does not fit 16 bits (never truncated). */
+int felics_index_build(const uint8_t *in, size_t len, uint32_t segment_pixels, uint8_t *index, size_t cap, size_t *index_len);
+
+/* Host only: felics_decompress through the index -- segment by segment, each from its checkpoint alone (bit position, table and
+ * window are re-initialised from the index, nothing is carried over from the segment before).  The pixels are those of
+ * felics_decompress; the first failing check or segment in (plane, segment) order gives the code. */
+int felics_decompress_indexed(const uint8_t *in, size_t len, const uint8_t *index, size_t index_len, void *pixels, size_t pixels_cap,
+                              felics_header *hdr);
+
+/* GPU, the index for free: felics_compress_batch_device (blocking, one shape, 8-bit) plus the restart index of stream i at
+ * d_index + i * felics_index_size(w, h, color, depth, segment_pixels) (d_index 16-byte aligned).  The streams are byte-identical to
+ * felics_compress_batch_device's and the indexes to felics_index_build's of those streams: the encoder already computes the
+ * estimator's state at every 16-event record, every tile's bit offset and, for RGB, the Y / Co / Cg planes, and a small kernel per
+ * pass collects them (felics_index.hip) -- on both placements of the streams, after every remedy of felics_stats (a pass that is
+ * redone rewrites its indexes) and for batches of several passes.  FELICS_E_BUFFER_TOO_SMALL for a short d_index_cap and
+ * FELICS_E_INVALID_ARGUMENT for a bad segment_pixels, before anything is launched; FELICS_E_UNSUPPORTED for depth 16; refused like
+ * the other synchronous entry points while a ticket is outstanding. */
+int felics_compress_batch_device_indexed(felics_ctx *ctx, size_t n, const void *d_pixels, uint32_t w, uint32_t h, int color, int depth,
+                                         void *d_out, size_t d_out_cap, uint32_t segment_pixels, void *d_index, size_t d_index_cap,
+                                         uint64_t *offsets, uint64_t *lens);
+
+/* GPU: n 8-bit streams of ONE shape, each with its index (index i at d_index + i * index_stride; d_index and index_stride multiples
+ * of 16, index_stride >= the index's size), decoded a wave per (stream, plane, segment): k_decode8_seg.  Output layout and status
+ * conventions of felics_decompress_batch_device; stream 0's header names the shape, index 0's header names segment_pixels and K,
+ * and a stream whose own index header differs gets FELICS_E_INVALID_INDEX.  All checks above are made on the device; status[i] is
+ * the code of stream i's first failing segment in (plane, segment) order; a failing segment leaves only its own pixels undefined
+ * (for RGB: the frame is not converted).  Rows too wide for the LDS and 16-bit streams: FELICS_E_UNSUPPORTED in every status (no
+ * host fallback in this call).  Refused like the other synchronous entry points while a ticket is outstanding. */
+int felics_decompress_batch_device_indexed(felics_ctx *ctx, size_t n, const void *d_streams, const uint64_t *offsets, const uint64_t *lens,
+                                           const void *d_index, size_t index_stride, void *d_pixels, size_t d_pixels_cap, felics_header *hdr,
+                                           int *status);
+
+/* What a context's indexed decode calls did so far (cumulative).  (felics_decode_stats keeps its eight fields: these are counted here.) */
+typedef struct felics_index_stats {
+    uint64_t streams;    /* streams handed to felics_decompress_batch_device_indexed (calls that passed the checks) */
+    uint64_t segments8;  /* segments launched, a wave each: n * C * K */
+} felics_index_stats;
+/* Writes min(out_size, sizeof(felics_index_stats)) bytes, never more. */
+int felics_get_index_stats(const felics_ctx *ctx, felics_index_stats *out, size_t out_size);
 
 /* felics_decompress_images_device into views: stream i (at d_streams + offsets[i], lens[i] bytes) is decoded straight into views[i]
  * -- sample (x, y, c) of the decoded image lands at data + y * row_stride + x * pixel_stride + c * channel_stride, sample for sample
