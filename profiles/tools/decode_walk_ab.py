@@ -1,0 +1,226 @@
+"""The wave-per-stream decoders of this build against another build of the library (the parent commit's), call by call.
+
+    python profiles/tools/decode_walk_ab.py --parent-lib PARENT/libfelics.so [--parent-source HASH] [--reps 15] [--out FILE]
+
+Workloads, each one blocking decode call of well under a second, in the wave form (FELICS_TEST_DECODE_LANES=0 and
+FELICS_TEST_DECODE16_LANES=0 around the call) but for the last:
+  gray8     64 gray8 S1 streams of 512 x 512, felics_decompress_batch_device          k_decode8<DecUniform>
+  rgb8      64 RGB8 streams of 512 x 512                                               k_decode8<DecUniform>, three planes
+  gray16    64 gray16 streams of 512 x 512                                             k_decode16<DecUniform>
+  rgb16     64 RGB16 streams of 256 x 256                                              k_decode16<DecUniform>, three planes
+  pitched8  the gray8 streams into 512 x 512 views of pitch 576, felics_decompress_views_device   k_decode8<DecPitched>
+  mixed8    the gray8 streams through felics_decompress_images_device                  k_decode8<DecMixed>
+  indexed   one 2048 x 2048 gray8 S1 stream, indexed at segment 32 768                 k_decode8_seg
+  lanes8    4 096 gray8 streams of 64 x 64 in the lane form (FELICS_TEST_DECODE_LANES=1): the control, code a change to the walk leaves alone
+Each library is loaded in a child process of its own (FELICS_LIB_PATH); the parent process never opens the GPU and asks the two
+children for one call at a time, seat a then seat b, workload after workload, --reps rounds after two warm-up rounds.  A time is
+what two device events around the blocking call measure, in milliseconds; medians with min .. max.  Every child compares what its
+first call of a workload decoded with the frames and prints a digest of it.
+
+The protocol runs twice.  First with the parent's library in BOTH seats: the relative difference of the two seats' medians is the
+workload's margin -- what the protocol itself cannot tell apart.  Then the parent's library against this build: no workload's median
+may exceed the parent's by more than its margin (exit status 1 otherwise)."""
+import argparse
+import hashlib
+import os
+import statistics
+import subprocess
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+WORKLOADS = ("gray8", "rgb8", "gray16", "rgb16", "pitched8", "mixed8", "indexed", "lanes8")
+SEGMENT = 32768
+PITCH = 576
+
+
+def child():
+    sys.path.insert(0, ROOT)
+    import numpy as np
+    import torch
+
+    import felics_amd
+    from felics_amd import api, build, synth
+
+    enc = felics_amd.Encoder(0)
+
+    def encode(frames, w, h, color, depth, seg=0):
+        """frames: a numpy array (n, h, w[, 3]); -> (device frames, device streams, offsets, lens[, device index, index size])"""
+        d = torch.from_numpy(np.ascontiguousarray(frames)).cuda()
+        n = frames.shape[0]
+        per = max(int(api.lib().felics_max_compressed_size(w, h, color, depth)), frames[0].nbytes * 5 // 4 + 96)
+        cap = n * ((per + 15) // 16 * 16)
+        out = torch.empty(cap, dtype=torch.uint8, device="cuda")
+        torch.cuda.synchronize()
+        if seg:
+            isize = api.index_size(w, h, color, depth, seg)
+            idx = torch.empty(n * isize, dtype=torch.uint8, device="cuda")
+            offs, lens = enc.compress_batch_device_indexed(d.data_ptr(), n, w, h, color, depth, out.data_ptr(), cap, seg, idx.data_ptr(), n * isize)
+            return d, out, offs, lens, idx, isize
+        offs, lens = enc.compress_batch_device(d.data_ptr(), n, w, h, color, depth, out.data_ptr(), cap)
+        return d, out, offs, lens
+
+    g8 = np.stack([synth.gray8(512, 512, f, "S1") for f in range(64)])
+    c8 = np.stack([synth.rgb8(512, 512, f) for f in range(64)])
+    g16 = np.stack([synth.gray16(512, 512, f) for f in range(64)])
+    c16 = np.stack([np.stack([synth.gray16(256, 256, 3 * f + c) for c in range(3)], axis=-1) for f in range(64)])
+    big = synth.gray8(2048, 2048, 0, "S1")[None]
+    small = np.stack([synth.gray8(64, 64, f, "S1") for f in range(4096)])
+    sets = {"gray8": encode(g8, 512, 512, 0, 0), "rgb8": encode(c8, 512, 512, 1, 0), "gray16": encode(g16, 512, 512, 0, 1),
+            "rgb16": encode(c16, 256, 256, 1, 1), "indexed": encode(big, 2048, 2048, 0, 0, SEGMENT), "lanes8": encode(small, 64, 64, 0, 0)}
+    sets["pitched8"] = sets["mixed8"] = sets["gray8"]
+    dest = {k: torch.zeros(v[0].numel() * v[0].element_size(), dtype=torch.uint8, device="cuda") for k, v in sets.items() if k != "pitched8"}
+    mosaic = torch.zeros((64, 512, PITCH), dtype=torch.uint8, device="cuda")
+    views = [mosaic[i, :, :512] for i in range(64)]
+
+    def decoded(name):  # the bytes a call of `name` wrote, as the frames lie
+        return mosaic[:, :, :512].contiguous().view(-1) if name == "pitched8" else dest[name]
+
+    def call(name):
+        s = sets[name]
+        os.environ["FELICS_TEST_DECODE_LANES"] = "1" if name == "lanes8" else "0"  # (read per call)
+        os.environ["FELICS_TEST_DECODE16_LANES"] = "0"
+        if name == "pitched8":
+            enc.decompress_arrays_device(s[1].data_ptr(), s[2], s[3], views)
+        elif name == "mixed8":
+            enc.decompress_images_device(s[1].data_ptr(), s[2], s[3], dest[name].data_ptr(), dest[name].numel())
+        elif name == "indexed":
+            enc.decompress_batch_device_indexed(s[1].data_ptr(), s[2], s[3], s[4].data_ptr(), s[5], dest[name].data_ptr(), dest[name].numel())
+        else:
+            enc.decompress_batch_device(s[1].data_ptr(), s[2], s[3], dest[name].data_ptr(), dest[name].numel())
+
+    for name in WORKLOADS:  # untimed: allocations, code objects; the pixels checked and their digest printed
+        call(name)
+        torch.cuda.synchronize()
+        got = decoded(name).cpu().numpy()
+        want = sets[name][0].cpu().numpy().view(np.uint8).reshape(-1)
+        print("INFO %s ok=%d sha=%s" % (name, int(np.array_equal(got, want)), hashlib.sha256(got.tobytes()).hexdigest()[:16]), flush=True)
+    lib_sha = hashlib.sha256(open(build.ensure_lib(), "rb").read()).hexdigest()[:16]
+    print("READY %s %s" % (torch.cuda.get_device_name(0).replace(" ", "_"), lib_sha), flush=True)
+    t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    for line in sys.stdin:
+        cmd = line.split()
+        if not cmd or cmd[0] == "quit":
+            break
+        torch.cuda.synchronize()
+        t0.record()
+        call(cmd[0])
+        t1.record()
+        torch.cuda.synchronize()
+        print("MS %.5f" % t0.elapsed_time(t1), flush=True)
+    enc.close()
+
+
+class Child:
+    def __init__(self, lib):
+        env = dict(os.environ)
+        if lib:
+            env["FELICS_LIB_PATH"] = os.path.abspath(lib)
+        self.p = subprocess.Popen([sys.executable, os.path.abspath(__file__), "--child"], stdin=subprocess.PIPE, stdout=subprocess.PIPE, text=True,
+                                  env=env, cwd=ROOT)
+        self.info = {}
+        self.ready = None
+        for line in self.p.stdout:
+            f = line.split()
+            if f and f[0] == "INFO":
+                self.info[f[1]] = dict(kv.split("=") for kv in f[2:])
+            elif f and f[0] == "READY":
+                self.ready = f[1:]
+                break
+        if self.ready is None:
+            raise RuntimeError("child for %s did not come up (exit %s)" % (lib or "this build", self.p.wait()))
+
+    def ms(self, name):
+        self.p.stdin.write(name + "\n")
+        self.p.stdin.flush()
+        f = self.p.stdout.readline().split()
+        if len(f) != 2 or f[0] != "MS":
+            raise RuntimeError("child died (exit %s)" % self.p.wait())
+        return float(f[1])
+
+    def close(self):
+        try:
+            self.p.stdin.write("quit\n")
+            self.p.stdin.flush()
+        except OSError:
+            pass
+        self.p.wait(timeout=120)
+
+
+def protocol(lib_a, lib_b, reps):
+    """{workload: (times of seat a, times of seat b)}, the two children's READY and INFO lines"""
+    a = Child(lib_a)
+    try:
+        b = Child(lib_b)  # (a child that does not come up must not leave the other one behind)
+    except Exception:
+        a.close()
+        raise
+    try:
+        ts = {w: ([], []) for w in WORKLOADS}
+        for r in range(reps + 2):
+            for w in WORKLOADS:
+                ta, tb = a.ms(w), b.ms(w)
+                if r >= 2:
+                    ts[w][0].append(ta)
+                    ts[w][1].append(tb)
+    finally:
+        a.close()
+        b.close()
+    return ts, (a.ready, b.ready), (a.info, b.info)
+
+
+def fmt(v):
+    return "%10.4f ms (%.4f .. %.4f)" % (statistics.median(v), min(v), max(v))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--child", action="store_true")
+    ap.add_argument("--parent-lib", default=None)
+    ap.add_argument("--parent-source", default="not given", help="the parent build's source hash (felics_amd.build.source_hash() in its tree)")
+    ap.add_argument("--reps", type=int, default=15)
+    ap.add_argument("--out", default=None)
+    a = ap.parse_args()
+    if a.child:
+        return child()
+    if not a.parent_lib:
+        ap.error("--parent-lib is needed")
+    sys.path.insert(0, ROOT)
+    from felics_amd import build
+
+    lines = []
+
+    def say(s):
+        lines.append(s)
+        print(s, flush=True)
+
+    ok = True
+    same_ts, ready, info = protocol(a.parent_lib, a.parent_lib, a.reps)
+    say("decode_walk_ab.py: device %s; a child process per library, seats alternating call by call, medians of %d after 2 warm-up rounds"
+        % (ready[0][0], a.reps))
+    say("parent: source %s, library sha256 %s...; this build: source %s" % (a.parent_source, ready[0][1], build.source_hash()))
+    say("run 1, the parent's library in both seats (margin = |a - b| / min(a, b) of the medians):")
+    margin = {}
+    for w in WORKLOADS:
+        ma, mb = statistics.median(same_ts[w][0]), statistics.median(same_ts[w][1])
+        margin[w] = abs(ma - mb) / min(ma, mb)
+        good = info[0][w]["ok"] == "1" and info[1][w]["ok"] == "1"
+        ok = ok and good
+        say("  %-9s a %s  b %s  margin %.4f %%  pixels %s" % (w, fmt(same_ts[w][0]), fmt(same_ts[w][1]), 100 * margin[w], "ok" if good else "WRONG"))
+    ts, ready, info = protocol(a.parent_lib, None, a.reps)
+    say("run 2, seat a = the parent's library, seat b = this build (library sha256 %s...):" % ready[1][1])
+    for w in WORKLOADS:
+        ma, mb = statistics.median(ts[w][0]), statistics.median(ts[w][1])
+        good = info[1][w]["ok"] == "1" and info[0][w]["sha"] == info[1][w]["sha"]
+        within = mb <= ma * (1 + margin[w])
+        ok = ok and good and within
+        say("  %-9s parent %s  this %s  this / parent - 1 = %+.4f %%  (margin %.4f %%): %s; pixels %s"
+            % (w, fmt(ts[w][0]), fmt(ts[w][1]), 100 * (mb / ma - 1), 100 * margin[w], "within" if within else "EXCEEDS", "identical" if good else "DIFFER"))
+    say("verdict: %s" % ("every workload within its margin, pixels identical" if ok else "MISSED (see above)"))
+    if a.out:
+        with open(a.out, "w") as f:
+            f.write("\n".join(lines) + "\n")
+    return 0 if ok else 1
+
+
+if __name__ == "__main__":
+    sys.exit(main())

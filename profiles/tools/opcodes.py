@@ -4,6 +4,8 @@
 Extracts the code objects from the library (llvm-objdump --offloading), disassembles them and prints, per kernel, the static count of
 every opcode with its issue class (profiles/r04/valu_rate.txt): C = 1.0 ns per wave64 instruction and SIMD (32-bit add / sub / logic /
 shift-right, v_bitop3, the 16-bit VOP2 instructions), E = 1.7 ns (everything else vector), S = scalar, L = LDS, M = vector memory.
+python3 profiles/tools/opcodes.py --totals PARENT_LIB LIB [name part ...]: the static instruction count of every kernel whose name holds
+one of the parts (default: every felics:: kernel) in two builds, and the difference.
 Static counts: the hot loops are unrolled straight-line code, so for k_pack_g / k_hist / k_scatter / k_assign_serial the histogram of
 the kernel is close to the mix it executes; felics_amd/_build/libfelics.so by default.  Writes nothing into the repository but its stdout.
 """
@@ -66,7 +68,19 @@ def cheap_share(ctr):
     return valu, cls["C"] / max(valu, 1)
 
 
+def totals(lib_a, lib_b, parts):
+    a, b = histograms(lib_a), histograms(lib_b)
+    print("# static instructions per kernel: parent, this build, difference")
+    for n in sorted(set(a) | set(b)):
+        if parts and not any(p in n for p in parts):
+            continue
+        sa, sb = sum(a.get(n, {}).values()), sum(b.get(n, {}).values())
+        print("%6d %6d %+5d  %s" % (sa, sb, sb - sa, n.replace("(anonymous namespace)::", "").split("felics::", 1)[1].split("(")[0].replace("felics::", "")))
+
+
 def main():
+    if len(sys.argv) > 3 and sys.argv[1] == "--totals":
+        return totals(os.path.abspath(sys.argv[2]), os.path.abspath(sys.argv[3]), sys.argv[4:])
     lib = os.path.abspath(sys.argv[1] if len(sys.argv) > 1 else os.path.join(ROOT, "felics_amd", "_build", "libfelics.so"))
     want = sys.argv[2:] or ["k_pack_t<unsigned char>", "k_front<unsigned char, unsigned char>", "k_spine3<unsigned char>", "k_assign3<unsigned char>", "k_enum"]
     kernels = histograms(lib)
