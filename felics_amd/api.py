@@ -102,6 +102,14 @@ class _CIndexStats(C.Structure):  # felics_index_stats
     _fields_ = [("streams", C.c_uint64), ("segments8", C.c_uint64)]
 
 
+class _CRegion(C.Structure):  # felics_region
+    _fields_ = [("stream", C.c_uint32), ("x", C.c_uint32), ("y", C.c_uint32), ("w", C.c_uint32), ("h", C.c_uint32)]
+
+
+class _CRegionStats(C.Structure):  # felics_region_stats
+    _fields_ = [("regions", C.c_uint64), ("segments_walked", C.c_uint64), ("segments_skipped", C.c_uint64), ("pixels_walked", C.c_uint64)]
+
+
 INDEX_GRANULE = 4096  # FELICS_INDEX_GRANULE
 E_INVALID_INDEX = -12
 
@@ -136,6 +144,7 @@ EXPORTS = [
     "felics_surfaces_extent", "felics_submit_surfaces_device", "felics_compress_surfaces_device", "felics_get_surface_stats",
     "felics_index_size", "felics_index_build", "felics_decompress_indexed", "felics_decompress_batch_device_indexed",
     "felics_get_index_stats", "felics_compress_batch_device_indexed",
+    "felics_region_segments", "felics_decompress_region_indexed", "felics_decompress_regions_device_indexed", "felics_get_region_stats",
 ]
 
 _lib = None
@@ -220,6 +229,13 @@ def lib():
     L.felics_compress_batch_device_indexed.argtypes = [vp, sz, vp, C.c_uint32, C.c_uint32, C.c_int, C.c_int, vp, sz, C.c_uint32, vp, sz,
                                                       C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
     L.felics_get_index_stats.argtypes = [vp, C.POINTER(_CIndexStats), sz]
+    if hasattr(L, "felics_region_segments"):  # (as above: an older build has no regions)
+        L.felics_region_segments.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(_CRegion), C.POINTER(C.c_uint32), sz, C.POINTER(sz)]
+        L.felics_decompress_region_indexed.argtypes = [vp, sz, vp, sz, C.POINTER(_CRegion), vp, sz, C.POINTER(_CHeader)]
+        L.felics_decompress_regions_device_indexed.argtypes = [vp, sz, vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), vp, sz, sz,
+                                                              C.POINTER(_CRegion), vp, sz, C.POINTER(C.c_uint64), C.POINTER(_CHeader),
+                                                              C.POINTER(C.c_int)]
+        L.felics_get_region_stats.argtypes = [vp, C.POINTER(_CRegionStats), sz]
     L.felics_strerror.argtypes = [C.c_int]
     L.felics_strerror.restype = C.c_char_p
     L.felics_last_error.argtypes = [vp]
@@ -638,6 +654,36 @@ class Encoder:
             raise err
         return Header(ch.color_type, ch.pixel_depth, ch.width, ch.height), status
 
+    def decompress_regions_device_indexed(self, d_streams, offsets, lens, d_index, index_stride, regions, d_pixels, d_pixels_cap):
+        """felics_decompress_regions_device_indexed: windows of streams of one shape through their restart indexes, everything in
+        device memory (raw pointers).  regions: (stream, x, y, w, h) each; crop r is dense at d_pixels + out_offsets[r].  Only the
+        segments that hold a pixel of a region are walked.  Returns (Header, status array, out_offsets); raises like
+        decompress_batch_device_indexed (the error carries .status, one per region)."""
+        offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+        lens = np.ascontiguousarray(lens, dtype=np.uint64)
+        regs = (_CRegion * max(len(regions), 1))(*[_CRegion(*(int(v) for v in r)) for r in regions])
+        status = np.zeros(len(regions), dtype=np.int32)
+        out_offsets = np.zeros(len(regions), dtype=np.uint64)
+        ch = _CHeader()
+        rc = lib().felics_decompress_regions_device_indexed(
+            self._h, len(offsets), d_streams, offsets.ctypes.data_as(C.POINTER(C.c_uint64)), lens.ctypes.data_as(C.POINTER(C.c_uint64)),
+            d_index, index_stride, len(regions), regs, d_pixels, d_pixels_cap, out_offsets.ctypes.data_as(C.POINTER(C.c_uint64)),
+            C.byref(ch), status.ctypes.data_as(C.POINTER(C.c_int)))
+        if rc != 0:
+            err = DecompressionError(rc) if rc in DecompressionError.KINDS else FelicsError(rc, lib().felics_last_error(self._h).decode() if rc == -9 else "")
+            err.status = status
+            raise err
+        return Header(ch.color_type, ch.pixel_depth, ch.width, ch.height), status, out_offsets
+
+    def region_stats(self):
+        """felics_get_region_stats: regions handed to decompress_regions_device_indexed, the segments walked for them, the segments
+        of their frames that were not (C * K per region minus the walked), the pixels those walks cover; cumulative."""
+        st = _CRegionStats()
+        rc = lib().felics_get_region_stats(self._h, C.byref(st), C.sizeof(st))
+        if rc != 0:
+            self._raise(rc)
+        return {k: int(getattr(st, k)) for k, _ in _CRegionStats._fields_}
+
     def read_headers_device(self, d_streams, offsets, lens):
         """felics_read_headers_device: the headers of streams in device memory (raw pointer), read on the GPU.
         Returns (list of Header, or None where the header is invalid; status array of felics_read_header codes)."""
@@ -903,6 +949,42 @@ def decompress_indexed(data, index):
     out = np.zeros(shape, dtype=np.uint16 if ch.pixel_depth else np.uint8)
     rc = lib().felics_decompress_indexed(arr.ctypes.data, len(arr), idx.ctypes.data if len(idx) else None, len(idx),
                                          out.ctypes.data if out.size else None, out.nbytes, None)
+    if rc != 0:
+        raise DecompressionError(rc) if rc in DecompressionError.KINDS else FelicsError(rc)
+    return out
+
+
+def region_segments(width, height, segment_pixels, x, y, w, h):
+    """felics_region_segments: the segments (ascending list) of a plane of a width x height image cut every segment_pixels pixels that
+    hold a pixel of the w x h window at (x, y)."""
+    reg = _CRegion(0, x, y, w, h)
+    need = C.c_size_t(0)
+    L = lib()
+    rc = L.felics_region_segments(width, height, segment_pixels, C.byref(reg), None, 0, C.byref(need))
+    if rc == 0:
+        return []
+    if rc != -8:
+        raise FelicsError(rc)
+    segs = (C.c_uint32 * need.value)()
+    rc = L.felics_region_segments(width, height, segment_pixels, C.byref(reg), segs, need.value, C.byref(need))
+    if rc != 0:
+        raise FelicsError(rc)
+    return list(segs)
+
+
+def decompress_region_indexed(data, index, x, y, w, h):
+    """felics_decompress_region_indexed: the w x h window at (x, y) of an 8-bit stream's image (ndarray, h x w or h x w x 3), decoded
+    from the checkpoints of the segments that hold its pixels and from nothing else."""
+    arr = np.frombuffer(bytes(data), dtype=np.uint8)
+    idx = np.frombuffer(bytes(index), dtype=np.uint8)
+    ch = _CHeader()
+    rc = lib().felics_read_header(arr.ctypes.data if len(arr) else None, len(arr), C.byref(ch))
+    if rc != 0:
+        raise DecompressionError(rc)
+    reg = _CRegion(0, x, y, w, h)
+    out = np.zeros((h, w, 3) if ch.color_type else (h, w), dtype=np.uint8)
+    rc = lib().felics_decompress_region_indexed(arr.ctypes.data, len(arr), idx.ctypes.data if len(idx) else None, len(idx), C.byref(reg),
+                                                out.ctypes.data if out.size else None, out.nbytes, None)
     if rc != 0:
         raise DecompressionError(rc) if rc in DecompressionError.KINDS else FelicsError(rc)
     return out

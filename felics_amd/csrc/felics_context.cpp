@@ -275,6 +275,7 @@ void felics_ctx_destroy(felics_ctx *ctx) {
     release(ctx->view_stage);
     release(ctx->dec_meta);
     release(ctx->dec_seg_status);
+    release(ctx->dec_region_work);
     release(ctx->dec_planes);
     release(ctx->dec_planes16);
     release(ctx->dec_table);

@@ -896,6 +896,131 @@ int felics_decompress_batch_device_indexed(felics_ctx *ctx, size_t n, const void
     return FELICS_OK;
 }
 
+int felics_get_region_stats(const felics_ctx *ctx, felics_region_stats *out, size_t out_size) {
+    if (!ctx || !out) return FELICS_E_INVALID_ARGUMENT;
+    memcpy(out, &ctx->rstats, std::min(out_size, sizeof(felics_region_stats)));
+    return FELICS_OK;
+}
+
+int felics_decompress_regions_device_indexed(felics_ctx *ctx, size_t n_streams, const void *d_streams, const uint64_t *offsets,
+                                             const uint64_t *lens, const void *d_index, size_t index_stride, size_t n_regions,
+                                             const felics_region *regions, void *d_pixels, size_t d_pixels_cap, uint64_t *out_offsets,
+                                             felics_header *hdr_out, int *status) {
+    if (!ctx || (n_streams && (!d_streams || !offsets || !lens || !d_index)) || (n_regions && (!regions || !status)))
+        return FELICS_E_INVALID_ARGUMENT;
+    if (ctx->failed) return FELICS_E_HIP;
+    if (n_regions == 0) return FELICS_OK;
+    auto fail_all = [&](int code) {
+        for (size_t i = 0; i < n_regions; i++) status[i] = code;
+        return code;
+    };
+    if (any_pending(ctx)) return fail_all(FELICS_E_INVALID_ARGUMENT);  // felics_wait_batch first
+    if (n_streams == 0 || n_streams > 0xFFFFFFFFull || n_regions > 0x7FFFFFFFull) return fail_all(FELICS_E_INVALID_ARGUMENT);
+    if (((uintptr_t)d_index | index_stride) & 15u) return fail_all(FELICS_E_INVALID_ARGUMENT);  // the kernel loads a checkpoint as aligned words
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    // the shape every stream must have: header of stream 0; how every index is cut: header of index 0
+    uint8_t h0[FELICS_HEADER_BYTES] = {0}, ih[INDEX_HEADER_BYTES];
+    const size_t hl = (size_t)std::min<uint64_t>(lens[0], FELICS_HEADER_BYTES);
+    if (hl) HIP_TRY(ctx, hipMemcpy(h0, (const uint8_t *)d_streams + offsets[0], hl, hipMemcpyDeviceToHost));
+    felics_header hdr;
+    int rc = felics_read_header(h0, hl, &hdr);
+    if (rc) return fail_all(rc);
+    if (hdr_out) *hdr_out = hdr;
+    if (hdr.pixel_depth != FELICS_DEPTH_8) return fail_all(FELICS_E_UNSUPPORTED);  // 16-bit streams have no index
+    const uint32_t W = hdr.width, H = hdr.height, planes = hdr.color_type == FELICS_COLOR_RGB ? 3 : 1;
+    const uint64_t npix = (uint64_t)W * H;
+    if (npix > 0xFFFFFFFFull) return fail_all(FELICS_E_INVALID_DIMENSIONS);
+    // the requests: inside the image, of a stream of the call; the crops back to back
+    for (size_t r = 0; r < n_regions; r++)
+        if (regions[r].stream >= n_streams || !region_inside(W, H, regions[r])) return fail_all(FELICS_E_INVALID_ARGUMENT);
+    uint64_t total = 0;
+    for (size_t r = 0; r < n_regions; r++) {
+        total += (uint64_t)regions[r].w * regions[r].h * planes;  // (a crop has < 3 * 2^32 bytes: the sum is looked at before it can wrap)
+        if (total > d_pixels_cap) return fail_all(FELICS_E_BUFFER_TOO_SMALL);
+    }
+    if (total && !d_pixels) return fail_all(FELICS_E_INVALID_ARGUMENT);
+    if (decode8_lds_bytes(W, hdr.color_type) > DECODE_LDS_LIMIT) return fail_all(FELICS_E_UNSUPPORTED);  // no host fallback here
+    if (index_stride < INDEX_HEADER_BYTES) return fail_all(FELICS_E_INVALID_INDEX);
+    HIP_TRY(ctx, hipMemcpy(ih, d_index, INDEX_HEADER_BYTES, hipMemcpyDeviceToHost));
+    IndexLayout L;
+    if (index_header_check(ih, hdr.color_type, W, H, lens[0], L) != FELICS_OK || L.total > index_stride) return fail_all(FELICS_E_INVALID_INDEX);
+    const uint32_t seg = idx_rd32(ih + IDX_SEGPIX);
+    // the plan: a region's items are contiguous, in (plane, segment) order; an empty region has the header-only item
+    std::vector<RegionRow> rows;
+    std::vector<RegionItem> items;
+    std::vector<uint32_t> segs;
+    uint64_t walked = 0, pixels_walked = 0, max_crop = 0, plane_at = 0, out_at = 0;
+    try {
+        rows.reserve(n_regions);
+        for (size_t r = 0; r < n_regions; r++) {
+            const felics_region &g = regions[r];
+            segs.clear();
+            if (!region_empty(g)) {
+                uint32_t first, last;
+                region_span(W, seg, g, first, last);
+                for (uint32_t j = first; j <= last; j++)
+                    if (region_needs(W, npix, seg, g, j)) segs.push_back(j);
+            }
+            const uint64_t cnt = segs.empty() ? 1 : (uint64_t)planes * segs.size();
+            if (items.size() + cnt > 0x7FFFFFFFull) return fail_all(FELICS_E_UNSUPPORTED);  // one block per item
+            const uint64_t cpix = (uint64_t)g.w * g.h;
+            rows.push_back(RegionRow{g.stream, g.x, g.y, g.w, g.h, (uint32_t)items.size(), (uint32_t)cnt, 0, out_at, plane_at});
+            if (out_offsets) out_offsets[r] = out_at;
+            out_at += cpix * planes;
+            if (planes == 3) {
+                plane_at += cpix * 3;
+                max_crop = std::max(max_crop, cpix);
+            }
+            if (segs.empty()) items.push_back(RegionItem{(uint32_t)r, 0, REGION_HEADER_ONLY});
+            for (uint32_t c = 0; c < planes && !segs.empty(); c++)
+                for (const uint32_t j : segs) items.push_back(RegionItem{(uint32_t)r, c, j});
+            const uint64_t stop_at = region_empty(g) ? 0 : region_last(W, g);
+            for (const uint32_t j : segs) {
+                const uint64_t p0 = (uint64_t)j * seg;
+                pixels_walked += (std::min({npix, p0 + seg, stop_at}) - p0) * planes;
+            }
+            walked += (uint64_t)planes * segs.size();
+        }
+    } catch (const std::bad_alloc &) {
+        return fail_all(FELICS_E_IO);
+    }
+    const size_t n_items = items.size();
+    // offsets | lens | status on the device; the region table and the work list; a word per item
+    if ((rc = reserve(ctx, ctx->dec_meta, n_streams * 8 * 2 + n_regions * 4)) != 0) return fail_all(rc);
+    if ((rc = reserve(ctx, ctx->dec_region_work, n_regions * sizeof(RegionRow) + n_items * sizeof(RegionItem))) != 0) return fail_all(rc);
+    if ((rc = reserve(ctx, ctx->dec_seg_status, n_items * 4)) != 0) return fail_all(rc);
+    uint64_t *d_off = (uint64_t *)ctx->dec_meta.p, *d_len = d_off + n_streams;
+    int *d_status = (int *)(d_len + n_streams);
+    RegionRow *d_rows = (RegionRow *)ctx->dec_region_work.p;
+    RegionItem *d_items = (RegionItem *)(d_rows + n_regions);
+    int16_t *d_planes = nullptr;
+    if (planes == 3) {
+        if ((rc = reserve(ctx, ctx->dec_planes, (size_t)(plane_at * 2) + 64)) != 0) return fail_all(rc);
+        d_planes = (int16_t *)ctx->dec_planes.p;
+    }
+    felics_region_stats &rs = ctx->rstats;
+    rs.regions += n_regions;
+    rs.segments_walked += walked;
+    rs.segments_skipped += (uint64_t)n_regions * planes * L.K - walked;
+    rs.pixels_walked += pixels_walked;
+    hipStream_t s = ctx->lanes[0].stream;
+    for (size_t i = 0; i < n_regions; i++) status[i] = FELICS_E_HIP;  // until the kernel's own word arrives
+    HIP_TRY(ctx, hipMemcpyAsync(d_off, offsets, n_streams * 8, hipMemcpyHostToDevice, s));
+    HIP_TRY(ctx, hipMemcpyAsync(d_len, lens, n_streams * 8, hipMemcpyHostToDevice, s));
+    HIP_TRY(ctx, hipMemcpyAsync(d_rows, rows.data(), n_regions * sizeof(RegionRow), hipMemcpyHostToDevice, s));
+    HIP_TRY(ctx, hipMemcpyAsync(d_items, items.data(), n_items * sizeof(RegionItem), hipMemcpyHostToDevice, s));
+    HIP_TRY(ctx, hipMemsetAsync(d_status, 0xFF, n_regions * 4, s));
+    HIP_TRY(ctx, hipMemsetAsync(ctx->dec_seg_status.p, 0xFF, n_items * 4, s));
+    HIP_TRY(ctx, launch_decode8_regions(s, (const uint8_t *)d_streams, d_off, d_len, (const uint8_t *)d_index, index_stride, W, H, hdr.color_type,
+                                        seg, L.K, d_rows, (uint32_t)n_regions, d_items, (uint32_t)n_items, max_crop, (uint8_t *)d_pixels,
+                                        d_planes, (int *)ctx->dec_seg_status.p, d_status));
+    HIP_TRY(ctx, hipMemcpyAsync(status, d_status, n_regions * 4, hipMemcpyDeviceToHost, s));
+    HIP_TRY(ctx, hipStreamSynchronize(s));  // (rows and items live until here)
+    for (size_t i = 0; i < n_regions; i++)
+        if (status[i]) return status[i];
+    return FELICS_OK;
+}
+
 int felics_read_headers_device(felics_ctx *ctx, size_t n, const void *d_streams, const uint64_t *offsets, const uint64_t *lens,
                                felics_header *hdrs, int *status) {
     if (!ctx || (n && (!d_streams || !offsets || !lens || !hdrs || !status))) return FELICS_E_INVALID_ARGUMENT;

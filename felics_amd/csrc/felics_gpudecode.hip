@@ -594,6 +594,239 @@ __global__ __launch_bounds__(64) void k_seg_status(const int *__restrict__ seg_s
 }
 
 // ------------------------------------------------------------------------------------------
+// One wave per WORK ITEM = (region, plane, needed segment) of felics_decompress_regions_device_indexed (felics.h "Restart index:
+// regions"; host model: felics_decompress_region_indexed).
+//
+// k_decode8_seg's header checks, checkpoint load, window check, seek and per-pixel path, statement for statement -- a kernel of its
+// own with its own copy of the walk, so that k_decode8_seg and what it is measured against stay as they are.  Three things differ:
+// the loop ends at stop = min(the segment's end, the pixel behind the region's last one); the end check is made only where stop is
+// the segment's end (a walk that stops early has no checkpoint to stand on: only that the reader did not run off the stream); and
+// the block store writes a lane's sample only if its (column, row) lies inside the region, to (row - y) * w + (column - x) of the
+// dense crop (u8 gray, or the crop-sized int16 planes) -- the LDS row is written for every lane, because later rows read it.
+// An item with seg = REGION_HEADER_ONLY ends after the header checks.  item_status[b] = FELICS_OK or the code; k_region_status picks
+// a region's first.  LDS (dynamic): as k_decode8 (decode8_lds_bytes).
+// ------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(64) void k_decode8_region(const uint8_t *__restrict__ streams, const uint64_t *__restrict__ offsets,
+                                                       const uint64_t *__restrict__ lens, const uint8_t *__restrict__ index, uint64_t index_stride,
+                                                       DecUniform geo, uint32_t segment_pixels, uint32_t K, const RegionRow *__restrict__ regions,
+                                                       const RegionItem *__restrict__ items, uint8_t *__restrict__ pixels,
+                                                       int16_t *__restrict__ planes, int *__restrict__ item_status) {
+    extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
+    const uint32_t W = geo.W, H = geo.H, color = geo.color;
+    const RegionItem item = items[blockIdx.x];
+    const RegionRow reg = regions[item.region];
+    const uint32_t img = reg.stream, c = item.plane, j = item.seg;
+    uint32_t *table = reinterpret_cast<uint32_t *>(smem);
+    const uint32_t nctx = color ? nctx_of<int16_t>() : nctx_of<uint8_t>();
+    int16_t *rows = reinterpret_cast<int16_t *>(smem + nctx * 6 * 4);
+    const uint32_t rstride = decode8_row_stride(W);
+    const uint32_t lane = lane_id();
+    const uint8_t *s = streams + offsets[img];
+    const uint64_t slen = lens[img];
+    const uint8_t *idx = index + (uint64_t)img * index_stride;
+    const uint64_t npix = (uint64_t)W * H;
+    // the stream's header (format.rs:63-84) must be the one the caller announced, the index header must fit both
+    int rc = FELICS_OK;
+    IndexLayout L;
+    uint64_t start = 0, end = 0;
+    if (slen < FELICS_HEADER_BYTES) {
+        rc = FELICS_E_IO;
+    } else {
+        const uint32_t w = ((uint32_t)s[6] << 24) | ((uint32_t)s[7] << 16) | ((uint32_t)s[8] << 8) | s[9];
+        const uint32_t h = ((uint32_t)s[10] << 24) | ((uint32_t)s[11] << 16) | ((uint32_t)s[12] << 8) | s[13];
+        if (s[0] != 'F' || s[1] != 'L' || s[2] != 'C' || s[3] != 'S') rc = FELICS_E_INVALID_SIGNATURE;
+        else if (s[4] > 1) rc = FELICS_E_INVALID_COLOR_TYPE;
+        else if (s[5] > 1) rc = FELICS_E_INVALID_PIXEL_DEPTH;
+        else if (s[4] != color || s[5] != 0 || w != W || h != H) rc = FELICS_E_INVALID_DIMENSIONS;
+        else if (index_header_check(idx, color, W, H, slen, L) != FELICS_OK || idx_rd32(idx + IDX_SEGPIX) != segment_pixels || L.K != K)
+            rc = FELICS_E_INVALID_INDEX;
+        else if (j != REGION_HEADER_ONLY)
+            rc = index_segment_bounds(idx, L, c, j, slen, start, end);
+    }
+    rc = unii(rc);
+    if (rc != FELICS_OK || j == REGION_HEADER_ONLY) {
+        if (lane == 0) item_status[blockIdx.x] = rc;
+        return;
+    }
+    // this segment's pixels, and where the walk ends: the host names needed segments only (j < K, p0 < stop), and a region inside the
+    // image (x + w <= W, y + h <= H, both sides non-zero)
+    const uint64_t p0 = (uint64_t)j * segment_pixels, pend = min(npix, p0 + segment_pixels);
+    const uint64_t stop = min(pend, (uint64_t)(reg.y + reg.h - 1) * W + reg.x + reg.w);
+    uint32_t x = 0, y = 0;
+    int16_t *cur = rows, *prev = rows + rstride;
+    {
+        // the checkpoint: counters (u16 pairs -> u32 rows), then the window into the two rows -- with (x0, y0) = p0's place, window
+        // sample t is pixel p0 - 2 W + t: row y0 from t = 2 W - x0 on (cur), row y0 - 1 from t = W - x0 on (prev), and in front of that
+        // row y0 - 2, of which only (0, y0 - 2) is ever looked at, and only if x0 = 0 (the first-column rule: what cur[0] holds)
+        const uint8_t *cp = idx + INDEX_HEADER_BYTES + ((uint64_t)c * K + j) * L.cp_bytes;
+        const uint32_t *st = reinterpret_cast<const uint32_t *>(cp + CP_STATE_OFF);  // (index and checkpoints are 16-byte aligned)
+        for (uint32_t i = lane; i < nctx * 3; i += 64) {
+            const uint32_t w2 = st[i];
+            table[2 * i] = w2 & 0xFFFFu;
+            table[2 * i + 1] = w2 >> 16;
+        }
+        x = (uint32_t)(p0 % W);
+        y = (uint32_t)(p0 / W);
+        const uint8_t *win = cp + L.win_off;
+        const int lo_w = color && c ? -255 : 0;
+        bool bad = false;
+        for (uint64_t t = lane; t < 2ull * W; t += 64) {
+            if (p0 + t < 2ull * W) continue;  // in front of the plane: zeros, never looked at
+            const int v = color ? (int)reinterpret_cast<const int16_t *>(win)[t] : (int)win[t];
+            bad |= v < lo_w || v > 255;
+            if (t >= 2ull * W - x) cur[t - (2ull * W - x)] = (int16_t)v;
+            else if (t >= (uint64_t)W - x) prev[t - ((uint64_t)W - x)] = (int16_t)v;
+            else if (t == 0 && x == 0) cur[0] = (int16_t)v;
+        }
+        if (__ballot(bad) != 0) {
+            if (lane == 0) item_status[blockIdx.x] = FELICS_E_INVALID_INDEX;
+            return;
+        }
+    }
+    __builtin_amdgcn_wave_barrier();
+    ScalarBits br;
+    br.init_at(s, slen, start);
+    int32_t raw0 = 0, raw1 = 0;
+    if (j == 0) {  // the plane's two raw samples (compression.rs:166-167) stand in front of its first segment only
+        raw0 = (int32_t)br.get(32);
+        raw1 = (int32_t)br.get(32);
+        if (br.failed()) rc = FELICS_E_IO;
+    }
+    if (rc == FELICS_OK && stop > p0) {
+        const uint64_t cpix = (uint64_t)reg.w * reg.h;
+        int16_t *outp = color ? planes + reg.plane_off + (uint64_t)c * cpix : nullptr;
+        uint8_t *outg = color ? nullptr : pixels + reg.out_off;
+        const int lo_ok = color ? -255 : 0, hi_ok = 255;  // what a sample of this plane can be (Y 0..255, Co / Cg -255..255)
+        const uint32_t xl0 = x & 63u;
+        int upv = 0;   // VECTOR: prev[xb + lane] for the 64-sample block xb the walk stands in
+        int rowv = 0;  // VECTOR: the samples of this block decoded so far
+        if (xl0) {     // a start inside a block: the block's samples in front of it are the window's
+            if (y > 0) upv = (int)prev[(x & ~63u) + lane];
+            rowv = (int)cur[(x & ~63u) + lane];
+        }
+        int left = x >= 1 ? unii((int)cur[x - 1]) : 0, left2 = x >= 2 ? unii((int)cur[x - 2]) : 0;
+        int first_col2 = 0;  // cur[0] as it was before this row: the sample two rows up (first-column rule)
+        for (uint64_t i = p0; i < stop; i++) {
+            const uint32_t xl = x & 63u;
+            if (xl == 0) {
+                if (y > 0) upv = (int)prev[x + lane];  // (rows are padded to whole blocks)
+                if (x == 0 && y > 0) first_col2 = y >= 2 ? unii((int)cur[0]) : (W > 1 ? __builtin_amdgcn_readlane(upv, 1) : 0);
+            }
+            int pv;
+            if (i < 2) {
+                pv = i == 0 ? raw0 : raw1;
+            } else {
+                const int above = __builtin_amdgcn_readlane(upv, (int)xl);
+                const bool row0 = y == 0, col0 = x == 0 && !row0;  // misc.rs:6-24 with selects
+                const int v1 = col0 ? above : left;
+                const int v2 = col0 ? first_col2 : (row0 ? left2 : above);
+                const int hi = max(v1, v2), lo = min(v1, v2);
+                const uint32_t ctx = (uint32_t)(hi - lo);  // <= 510 because every stored sample is in range
+                br.refill();  // >= 33 bits: an in-range code has at most 11, the two flags of the other kind 2
+                if (br.take(1)) {  // in range: phased-in code of p - L (phase_in_coding.rs:86-112)
+                    const uint32_t n = ctx + 1;
+                    const uint32_t m = 31u - (uint32_t)__builtin_clz(n);
+                    const uint32_t right_p = (2u << m) - n, left_p = n - (1u << m);
+                    uint32_t r = br.take(m);
+                    const uint32_t longer = r >= right_p ? 1u : 0u;  // the code has one more bit
+                    const uint32_t r2 = (r - right_p) * 2u + right_p + br.take(longer);
+                    r = longer ? r2 : r;
+                    uint32_t rot = r + left_p;  // rotate_left: (r + left_p) mod n, r < n
+                    rot = rot >= n ? rot - n : rot;
+                    pv = lo + (int)rot;
+                } else {
+                    const bool above_flag = br.take(1) != 0;
+                    const uint64_t *row = reinterpret_cast<const uint64_t *>(table + ctx * 6);  // 24-byte rows: 8-byte aligned
+                    const uint64_t r01 = row[0], r23 = row[1], r45 = row[2];                 // one LDS round trip for the row
+                    uint32_t S[6] = {uni((uint32_t)r01), uni((uint32_t)(r01 >> 32)), uni((uint32_t)r23),
+                                     uni((uint32_t)(r23 >> 32)), uni((uint32_t)r45), uni((uint32_t)(r45 >> 32))};
+                    // get_k: smallest counter, ties to the largest k (parameter_selection.rs:71-85)
+                    const uint32_t key = min(min(min((S[0] << 3) | 7u, (S[1] << 3) | 6u), min((S[2] << 3) | 5u, (S[3] << 3) | 4u)),
+                                             min((S[4] << 3) | 3u, (S[5] << 3) | 2u));
+                    const uint32_t k = 7u - (key & 7u);
+                    const uint64_t q = br.unary0();
+                    const uint64_t e64 = (q << k) + br.get(k);
+                    if (e64 > 1024u) {  // no sample of an 8-bit plane is that far from its neighbours
+                        rc = e64 > 0xFFFFFFFFull ? FELICS_E_VALUE_OVERFLOW : FELICS_E_INVALID_VALUE;
+                        break;
+                    }
+                    const uint32_t e = (uint32_t)e64;
+                    uint32_t mn = 0xFFFFFFFFu;
+#pragma unroll
+                    for (uint32_t kk = 0; kk < 6; kk++) {
+                        S[kk] += (e >> kk) + 1u + kk;
+                        mn = min(mn, S[kk]);
+                    }
+                    const uint32_t hsh = mn > 1024u ? 1u : 0u;
+                    uint64_t *wrow = reinterpret_cast<uint64_t *>(table + ctx * 6);  // (every lane: same address, same value)
+                    wrow[0] = (uint64_t)(S[0] >> hsh) | ((uint64_t)(S[1] >> hsh) << 32);
+                    wrow[1] = (uint64_t)(S[2] >> hsh) | ((uint64_t)(S[3] >> hsh) << 32);
+                    wrow[2] = (uint64_t)(S[4] >> hsh) | ((uint64_t)(S[5] >> hsh) << 32);
+                    pv = above_flag ? hi + (int)e + 1 : lo - (int)e - 1;
+                }
+            }
+            if (pv < lo_ok || pv > hi_ok) {  // try_into::<u8>() / the estimator's context bound would fail
+                rc = FELICS_E_INVALID_VALUE;
+                break;
+            }
+            rowv = lane == xl ? pv : rowv;
+            left2 = left;
+            left = pv;
+            const bool row_end = x + 1 == W;
+            if (xl == 63u || row_end || i + 1 == stop) {  // a block of the row is complete, or the walk is
+                const uint32_t xb = x & ~63u;
+                if (xb + lane <= x) {
+                    cur[xb + lane] = (int16_t)rowv;  // (lanes in front of a mid-block start store back what they loaded)
+                    const uint32_t col = xb + lane;
+                    const uint64_t at = (uint64_t)y * W + col;  // < stop: col <= x
+                    // the samples in front of p0 are the segment's before this one; the crop takes those inside the region only:
+                    // column in [x, x + w), row in [y, y + h) (row < y + h: at < stop) -- an offset below w * h
+                    if (at >= p0 && col >= reg.x && col - reg.x < reg.w && y >= reg.y && y - reg.y < reg.h) {
+                        const uint64_t to = (uint64_t)(y - reg.y) * reg.w + (col - reg.x);
+                        if (outg) outg[to] = (uint8_t)rowv;
+                        else outp[to] = (int16_t)rowv;
+                    }
+                }
+            }
+            if (row_end) {
+                if (br.failed()) {
+                    rc = FELICS_E_IO;
+                    break;
+                }
+                __builtin_amdgcn_wave_barrier();
+                x = 0;
+                y++;
+                int16_t *t = cur;
+                cur = prev;
+                prev = t;
+            } else {
+                x++;
+            }
+        }
+    }
+    if (br.failed()) rc = FELICS_E_IO;  // (whatever else stopped the decoding: it was decoding padding)
+    else if (rc == FELICS_OK && stop == pend && br.pos(s) != end) rc = FELICS_E_INVALID_INDEX;  // the end check: exactly on the next checkpoint
+    if (lane == 0) item_status[blockIdx.x] = rc;
+}
+
+// status[r] = the code of region r's first failing item in (plane, segment) order; one wave per region over its items' words
+__global__ __launch_bounds__(64) void k_region_status(const int *__restrict__ item_status, const RegionRow *__restrict__ regions,
+                                                      int *__restrict__ status) {
+    __shared__ uint32_t first;
+    if (threadIdx.x == 0) first = 0xFFFFFFFFu;
+    __syncthreads();
+    const RegionRow reg = regions[blockIdx.x];
+    const int *mine = item_status + reg.item0;
+    for (uint32_t k = threadIdx.x; k < reg.nitems; k += 64)
+        if (mine[k] != FELICS_OK) {
+            atomicMin(&first, k);
+            break;
+        }
+    __syncthreads();
+    if (threadIdx.x == 0) status[blockIdx.x] = first == 0xFFFFFFFFu ? FELICS_OK : mine[first];
+}
+
+// ------------------------------------------------------------------------------------------
 // Sixty-four streams per wave, LANE = stream (8-bit gray, batches of hundreds of streams and more).
 //
 // The streams of a call have one shape, so all of them are at the same pixel at the same time: the walk over (x, y) and the
@@ -1006,6 +1239,22 @@ __device__ __forceinline__ bool conv_view(const DecMixed &g, const P *planes, T 
     c.pl = planes + r.plane_off;
     c.dst = reinterpret_cast<T *>(reinterpret_cast<uint8_t *>(pixels) + r.out_off);
     return r.color != 0;
+}
+
+// ConvRegion (felics_decompress_regions_device_indexed): row base + blockIdx.y of a RegionRow table -- crop-sized planes, the crop
+// dense at its out_off; status is per region.
+struct ConvRegion {
+    const RegionRow *rows;
+    uint32_t base;
+};
+template <typename P, typename T>
+__device__ __forceinline__ bool conv_view(const ConvRegion &g, const P *planes, T *pixels, ConvView<P, T> &c) {
+    const RegionRow r = g.rows[g.base + blockIdx.y];
+    c.img = g.base + blockIdx.y;
+    c.npix = r.w * r.h;
+    c.pl = planes + r.plane_off;
+    c.dst = reinterpret_cast<T *>(reinterpret_cast<uint8_t *>(pixels) + r.out_off);
+    return true;
 }
 
 // ycocg_to_rgb (color_transform.rs:20-26) on the decoded planes, range-checked like try_into::<u8>()
@@ -1739,6 +1988,29 @@ hipError_t launch_decode8_seg(hipStream_t s, const uint8_t *streams, const uint6
         const uint32_t bx = (uint32_t)std::min<uint64_t>((npix + 255) / 256, 1024u);
         if (bx) hipLaunchKernelGGL(k_ycocg8_to_rgb<ConvUniform>, dim3(bx, n), dim3(256), 0, s, planes, pixels, ConvUniform{(uint32_t)npix}, status);
     }
+    return hipGetLastError();
+}
+
+hipError_t launch_decode8_regions(hipStream_t s, const uint8_t *streams, const uint64_t *offsets, const uint64_t *lens, const uint8_t *index,
+                                  uint64_t index_stride, uint32_t W, uint32_t H, uint32_t color, uint32_t segment_pixels, uint32_t K,
+                                  const RegionRow *rows, uint32_t nregions, const RegionItem *items, uint32_t nitems, uint64_t max_crop,
+                                  uint8_t *pixels, int16_t *planes, int *item_status, int *status) {
+    if (nregions == 0 || nitems == 0) return hipSuccess;
+    const uint32_t lds = decode8_lds_bytes(W, color);
+    if (lds > 64u * 1024u) {
+        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&k_decode8_region), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                                 (int)DECODE_LDS_LIMIT);
+        if (e != hipSuccess) return e;
+    }
+    hipLaunchKernelGGL(k_decode8_region, dim3(nitems), dim3(64), lds, s, streams, offsets, lens, index, index_stride, DecUniform{W, H, color},
+                       segment_pixels, K, rows, items, pixels, planes, item_status);
+    hipLaunchKernelGGL(k_region_status, dim3(nregions), dim3(64), 0, s, item_status, rows, status);
+    // the crops differ in size: one launch (per 65 535 regions) sized by the largest, a region's blocks stride over its own w * h
+    const uint32_t bx = (uint32_t)std::min<uint64_t>((max_crop + 255) / 256, 1024u);
+    if (color && bx)
+        for (uint32_t r0 = 0; r0 < nregions; r0 += 65535u)
+            hipLaunchKernelGGL(k_ycocg8_to_rgb<ConvRegion>, dim3(bx, std::min(nregions - r0, 65535u)), dim3(256), 0, s, planes, pixels,
+                               ConvRegion{rows, r0}, status);
     return hipGetLastError();
 }
 

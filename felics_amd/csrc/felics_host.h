@@ -200,6 +200,10 @@ struct felics_ctx {
     // felics_decompress_batch_device_indexed: a status word per (stream, plane, segment); the counts of felics_get_index_stats
     DevBuf dec_seg_status;
     felics_index_stats istats = {};
+    // felics_decompress_regions_device_indexed: its region table and work list (RegionRow[] | RegionItem[]; the items' status words
+    // are dec_seg_status, the crop-sized planes dec_planes); the counts of felics_get_region_stats
+    DevBuf dec_region_work;
+    felics_region_stats rstats = {};
 };
 
 namespace felics {

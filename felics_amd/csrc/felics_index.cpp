@@ -214,4 +214,92 @@ int felics_decompress_indexed(const uint8_t *in, size_t len, const uint8_t *inde
     return store_rgb8(ch, planes, (uint8_t *)pixels);
 }
 
+int felics_region_segments(uint32_t W, uint32_t H, uint32_t segment_pixels, const felics_region *r, uint32_t *segs, size_t cap, size_t *count) {
+    if (!r || !count || (!segs && cap)) return FELICS_E_INVALID_ARGUMENT;
+    *count = 0;
+    const uint64_t npix = (uint64_t)W * H;
+    if (!index_segment_ok(segment_pixels) || npix > 0xFFFFFFFFull || !region_inside(W, H, *r)) return FELICS_E_INVALID_ARGUMENT;
+    if (region_empty(*r)) return FELICS_OK;
+    uint32_t first, last;
+    region_span(W, segment_pixels, *r, first, last);
+    size_t n = 0;
+    for (uint32_t j = first; j <= last; j++)
+        if (region_needs(W, npix, segment_pixels, *r, j)) {
+            if (n < cap) segs[n] = j;
+            n++;
+        }
+    *count = n;
+    return n > cap ? FELICS_E_BUFFER_TOO_SMALL : FELICS_OK;
+}
+
+int felics_decompress_region_indexed(const uint8_t *in, size_t len, const uint8_t *index, size_t index_len, const felics_region *rp, void *pixels,
+                                     size_t pixels_cap, felics_header *hdr_out) {
+    if ((!in && len) || (!index && index_len) || !rp) return FELICS_E_INVALID_ARGUMENT;
+    felics_header hdr;
+    int rc = check_stream(in, len, hdr);
+    if (hdr_out && (rc == FELICS_OK || rc == FELICS_E_UNSUPPORTED)) *hdr_out = hdr;
+    if (rc) return rc;
+    const uint32_t W = hdr.width, H = hdr.height, color = hdr.color_type;
+    const felics_region r = *rp;
+    if (!region_inside(W, H, r)) return FELICS_E_INVALID_ARGUMENT;
+    const size_t npix = (size_t)W * H, cpix = (size_t)r.w * r.h;
+    const unsigned planes = color ? 3 : 1;
+    if ((uint64_t)cpix * planes > pixels_cap) return FELICS_E_BUFFER_TOO_SMALL;
+    if (cpix && !pixels) return FELICS_E_INVALID_ARGUMENT;
+    IndexLayout L;
+    if (index_len < INDEX_HEADER_BYTES || index_header_check(index, color, W, H, len, L) || L.total != index_len) return FELICS_E_INVALID_INDEX;
+    if (region_empty(r)) return FELICS_OK;
+    const uint32_t seg = idx_rd32(index + IDX_SEGPIX);
+    const uint64_t last = region_last(W, r);
+    uint32_t jfirst, jlast;
+    region_span(W, seg, r, jfirst, jlast);
+    std::vector<int32_t> ch[3], buf;
+    try {
+        Estimator est(OPT8);
+        for (uint32_t c = 0; c < L.planes; c++) {
+            ch[c].assign(cpix, 0);
+            for (uint32_t j = jfirst; j <= jlast; j++) {
+                if (!region_needs(W, npix, seg, r, j)) continue;
+                uint64_t start, end;
+                if (index_segment_bounds(index, L, c, j, len, start, end)) return FELICS_E_INVALID_INDEX;
+                BitReader br(in, len, start);
+                const size_t s0 = (size_t)j * seg, s1 = std::min(npix, s0 + seg), stop = (size_t)std::min<uint64_t>(s1, last);
+                // The walk's samples live in `buf`: whole rows from two rows above s0's on (the window's reach), up to `stop`.  The rows
+                // dropped in front are an even count when s0's row is >= 2, none otherwise: the neighbour rule sees the same cases.
+                const size_t y0 = s0 / W, base = y0 >= 2 ? (y0 - 2) * W : 0;
+                buf.assign(stop - base, 0);
+                int32_t *out = buf.data();
+                const uint8_t *cp = index + INDEX_HEADER_BYTES + ((uint64_t)c * L.K + j) * L.cp_bytes;
+                const uint32_t stored = (color ? OPT8.max_context + 1 : 256u) * 6;  // (gray has contexts 0 .. 255)
+                for (uint32_t i = 0; i < (OPT8.max_context + 1) * 6; i++) est.row(0)[i] = i < stored ? idx_rd16(cp + CP_STATE_OFF + 2 * i) : 0u;
+                for (uint64_t s = 0; s < 2ull * W; s++) {
+                    if (s0 + s < 2ull * W) continue;
+                    const int32_t v = color ? (int32_t)(int16_t)idx_rd16(cp + L.win_off + 2 * s) : (int32_t)cp[L.win_off + s];
+                    if (!in_plane_range(v, color, c)) return FELICS_E_INVALID_INDEX;
+                    out[s0 + s - 2ull * W - base] = v;
+                }
+                if (j == 0) {
+                    const int32_t p0 = (int32_t)br.bits(32), p1 = (int32_t)br.bits(32);
+                    if (br.failed()) return FELICS_E_IO;
+                    out[0] = p0;
+                    if (stop > 1) out[1] = p1;
+                }
+                rc = decode_span(br, W, OPT8, est, out, std::max<size_t>(s0, 2) - base, std::max<size_t>(stop, 2) - base, nullptr);
+                if (rc) return rc;
+                for (size_t i = s0; i < stop; i++) {
+                    const int32_t v = out[i - base];
+                    if (!in_plane_range(v, color, c)) return FELICS_E_INVALID_VALUE;
+                    const size_t yy = i / W, xx = i - yy * W;
+                    if (xx >= r.x && xx < (size_t)r.x + r.w && yy >= r.y) ch[c][(yy - r.y) * r.w + (xx - r.x)] = v;
+                }
+                // the end check where the walk reached the segment's end; a walk that stops early has no bit position to stand on
+                if (stop == s1 && br.pos() != end) return FELICS_E_INVALID_INDEX;
+            }
+        }
+    } catch (const std::bad_alloc &) {
+        return FELICS_E_INVALID_DIMENSIONS;
+    }
+    return store_rgb8(ch, planes, (uint8_t *)pixels);
+}
+
 }  // extern "C"

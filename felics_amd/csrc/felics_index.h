@@ -103,6 +103,30 @@ FELICS_IDX_HD inline int index_segment_bounds(const uint8_t *idx, const IndexLay
     return FELICS_OK;
 }
 
+// ---- regions (felics.h "Restart index: regions"): the planner's arithmetic, for felics_region_segments, the host model and the host
+// side of the device call alike.  W * H < 2^32, index_segment_ok(seg) and region_inside are the caller's checks.
+FELICS_IDX_HD inline bool region_inside(uint32_t W, uint32_t H, const felics_region &r) {
+    return (uint64_t)r.x + r.w <= W && (uint64_t)r.y + r.h <= H;
+}
+FELICS_IDX_HD inline bool region_empty(const felics_region &r) { return r.w == 0 || r.h == 0; }
+// the pixel behind the region's last one: no walk goes further
+FELICS_IDX_HD inline uint64_t region_last(uint32_t W, const felics_region &r) { return (uint64_t)(r.y + r.h - 1) * W + r.x + r.w; }
+// Does segment j = pixels [a, b) hold a pixel of the (non-empty) region?  Row yy's span [yy W + x, yy W + x + w) meets [a, b) iff
+// yy W + x < b and yy W + x + w > a: yy <= (b - x - 1) / W and, where a >= x + w, yy >= (a - x - w) / W + 1; some yy of
+// [y, y + h) must satisfy both.
+FELICS_IDX_HD inline bool region_needs(uint32_t W, uint64_t npix, uint32_t seg, const felics_region &r, uint32_t j) {
+    const uint64_t a = (uint64_t)j * seg, b = a + seg < npix ? a + seg : npix;
+    if (b <= r.x) return false;
+    const uint64_t hi_row = (b - r.x - 1) / W, hi = hi_row < (uint64_t)r.y + r.h - 1 ? hi_row : (uint64_t)r.y + r.h - 1;
+    const uint64_t lo_row = a >= (uint64_t)r.x + r.w ? (a - r.x - r.w) / W + 1 : 0, lo = lo_row > r.y ? lo_row : r.y;
+    return lo <= hi;
+}
+// the segments that can be needed at all: those of the region's first and last pixel and the ones between
+FELICS_IDX_HD inline void region_span(uint32_t W, uint32_t seg, const felics_region &r, uint32_t &first, uint32_t &last) {
+    first = (uint32_t)(((uint64_t)r.y * W + r.x) / seg);
+    last = (uint32_t)((region_last(W, r) - 1) / seg);
+}
+
 }  // namespace felics
 
 #endif

@@ -293,6 +293,28 @@ hipError_t launch_decode8(hipStream_t s, const uint8_t *streams, const uint64_t 
 hipError_t launch_decode8_seg(hipStream_t s, const uint8_t *streams, const uint64_t *offsets, const uint64_t *lens, const uint8_t *index,
                               uint64_t index_stride, uint32_t n, uint32_t W, uint32_t H, uint32_t color, uint32_t segment_pixels, uint32_t K,
                               uint8_t *pixels, int16_t *planes, int *seg_status, int *status);
+// Regions of such streams (felics_decompress_regions_device_indexed, felics.h "Restart index: regions"): one wave per work item =
+// (region, plane, needed segment), k_decode8_region.  A region's items are contiguous, in (plane, segment) order; an item whose
+// segment is REGION_HEADER_ONLY makes the checks of its stream's header and index header and nothing else (the one item of an empty
+// region).  Crops are dense: gray at pixels + out_off (bytes), RGB through crop-sized int16 planes at planes + plane_off (three
+// planes of w * h samples), converted by k_ycocg8_to_rgb where status[region] is clean.
+constexpr uint32_t REGION_HEADER_ONLY = 0xFFFFFFFFu;
+struct RegionRow {
+    uint32_t stream;         // index into offsets / lens and of the index
+    uint32_t x, y, w, h;
+    uint32_t item0, nitems;  // its items: item0 .. item0 + nitems - 1, nitems >= 1
+    uint32_t pad;
+    uint64_t out_off, plane_off;
+};
+struct RegionItem {
+    uint32_t region, plane, seg;
+};
+// nitems < 2^31 items over nregions rows; item_status: a word per item; status[r] = region r's first failing one; max_crop: the
+// largest w * h of an RGB region (0: gray)
+hipError_t launch_decode8_regions(hipStream_t s, const uint8_t *streams, const uint64_t *offsets, const uint64_t *lens, const uint8_t *index,
+                                  uint64_t index_stride, uint32_t W, uint32_t H, uint32_t color, uint32_t segment_pixels, uint32_t K,
+                                  const RegionRow *rows, uint32_t nregions, const RegionItem *items, uint32_t nitems, uint64_t max_crop,
+                                  uint8_t *pixels, int16_t *planes, int *item_status, int *status);
 // The same for 16-bit streams, gray or RGB (k_decode16_lanes): 64 streams per wave, lane = stream; needs W >= 8 and a table of
 // decode16_lanes_table_bytes(n, W, H, color) bytes = n * planes * dec16l_rows(W * H, planes) * 64 (felics_lanetable.h: sized by the
 // pixel count, 512 KB per plane of a 64 x 64 stream, the wave form's 8.4 MB from 32 771 pixels on), zero-initialised ONCE: rows carry

@@ -4,11 +4,15 @@
 //     and the index then goes through a few hundred byte mutations of its own (header fields, bit offsets, counters, window
 //     samples), each of which must be accepted or refused with a code;
 //   * if NAME.idx exists it is used as the index of NAME as it is (an index of the unmutated stream beside a mutated stream, a
-//     mutated index beside a good stream): any code, no crash.
+//     mutated index beside a good stream): any code, no crash;
+//   * felics_decompress_region_indexed with random regions on all of these pairs: on a good pair every crop must equal the same
+//     window of felics_decompress's pixels and felics_region_segments must name what a pixel-by-pixel marking names; on a mutated
+//     or foreign pair any code, no crash.
 // Built with -fsanitize=address,undefined by `make asan`; tests/test_index_cpu.py feeds it a mutated corpus.
 // Exit code 0 = every input was handled without a sanitizer report and every accepted pair decoded to the right pixels.
 #include <dirent.h>
 
+#include <algorithm>
 #include <cstdio>
 #include <cstring>
 #include <string>
@@ -47,6 +51,15 @@ int main(int argc, char **argv) {
         bad += felics_decompress_indexed(b, sizeof b, nullptr, 5, b, sizeof b, nullptr) != FELICS_E_INVALID_ARGUMENT;
         bad += felics_index_size(1, 1, 0, 1, 4096) != 0 || felics_index_size(1, 1, 0, 0, 4095) != 0 || felics_index_size(1, 1, 2, 0, 4096) != 0;
         bad += felics_index_size(0xFFFFFFFFu, 0xFFFFFFFFu, 1, 0, 4096) != 0;
+        const felics_region in{0, 1, 1, 2, 2}, out{0, 0xFFFFFFFFu, 0, 2, 1};
+        uint32_t segs[4];
+        bad += felics_region_segments(8, 8, 4096, nullptr, segs, 4, &n) != FELICS_E_INVALID_ARGUMENT;
+        bad += felics_region_segments(8, 8, 4096, &in, segs, 4, nullptr) != FELICS_E_INVALID_ARGUMENT;
+        bad += felics_region_segments(8, 8, 4095, &in, segs, 4, &n) != FELICS_E_INVALID_ARGUMENT;
+        bad += felics_region_segments(8, 8, 4096, &out, segs, 4, &n) != FELICS_E_INVALID_ARGUMENT;  // x + w wraps in 32 bits
+        bad += felics_region_segments(8, 8, 4096, &in, nullptr, 0, &n) != FELICS_E_BUFFER_TOO_SMALL || n != 1;
+        bad += felics_region_segments(8, 8, 4096, &in, segs, 4, &n) != FELICS_OK || n != 1 || segs[0] != 0;
+        bad += felics_decompress_region_indexed(b, sizeof b, b, sizeof b, nullptr, b, sizeof b, nullptr) != FELICS_E_INVALID_ARGUMENT;
         if (bad) {
             fprintf(stderr, "argument checks: %d unexpected results\n", bad);
             return 1;
@@ -58,7 +71,7 @@ int main(int argc, char **argv) {
     while (dirent *e = readdir(d))
         if (e->d_name[0] != '.' && !ends_with(e->d_name, ".idx")) names.push_back(e->d_name);
     closedir(d);
-    size_t built = 0, refused = 0, mutations = 0, mut_accepted = 0, pairs = 0, pairs_ok = 0;
+    size_t regions = 0, built = 0, refused = 0, mutations = 0, mut_accepted = 0, pairs = 0, pairs_ok = 0;
     const size_t cap = 32u << 20;  // decoders and the builder get bounded buffers whatever a header claims
     std::vector<uint8_t> buf, idx, given, px(cap), ref(cap), index(cap);
     uint64_t rng = 0x9E3779B97F4A7C15ull;
@@ -67,6 +80,38 @@ int main(int argc, char **argv) {
         rng ^= rng >> 7;
         rng ^= rng << 17;
         return rng;
+    };
+    // a random region of a w x h image: mostly small windows, now and then whole rows, whole columns or nothing
+    auto region_of = [&](uint32_t w, uint32_t h) {
+        felics_region r = {0, 0, 0, 0, 0};
+        if (!w || !h) return r;
+        r.x = (uint32_t)(next() % w);
+        r.y = (uint32_t)(next() % h);
+        const uint64_t kind = next() % 8;
+        r.w = kind == 0 ? w - r.x : (uint32_t)(next() % std::min<uint64_t>(w - r.x, 64) + (kind != 1));
+        r.h = kind == 2 ? h - r.y : (uint32_t)(next() % std::min<uint64_t>(h - r.y, 64) + (kind != 3));
+        r.w = std::min(r.w, w - r.x);
+        r.h = std::min(r.h, h - r.y);
+        return r;
+    };
+    std::vector<uint8_t> crop, mark;
+    std::vector<uint32_t> segs;
+    // the region decoder on a pair; `good`: the crop must then be ref's window (ref holds h's image)
+    auto regions_on = [&](const std::vector<uint8_t> &index_bytes, size_t index_len, const felics_header &h, bool good, int count) {
+        const size_t planes = h.color_type ? 3 : 1;
+        for (int k = 0; k < count; k++) {
+            const felics_region r = region_of(h.width, h.height);
+            crop.assign((size_t)r.w * r.h * planes + 1, 0xA5);
+            felics_header hr;
+            const int rc = felics_decompress_region_indexed(buf.data(), buf.size(), index_bytes.data(), index_len, &r, crop.data(), crop.size() - 1, &hr);
+            regions++;
+            if (crop.back() != 0xA5) return false;
+            if (!good) continue;
+            if (rc != FELICS_OK) return false;
+            for (uint32_t yy = 0; yy < r.h; yy++)
+                if (memcmp(&crop[(size_t)yy * r.w * planes], &ref[((size_t)(r.y + yy) * h.width + r.x) * planes], (size_t)r.w * planes) != 0) return false;
+        }
+        return true;
     };
     for (const std::string &n : names) {
         const std::string path = std::string(argv[1]) + "/" + n;
@@ -80,6 +125,12 @@ int main(int argc, char **argv) {
             // (any code: a flipped bit that keeps a segment's length decodes through the index -- the damage ends at the next
             // checkpoint -- where the plain decoder carries it on and fails; the checks do not prove the pairing, felics.h)
             if (felics_decompress_indexed(buf.data(), buf.size(), given.data(), given.size(), px.data(), px.size(), &h2) == FELICS_OK) pairs_ok++;
+            felics_header hh;  // (a stream felics_decompress refuses is walked too, as far as its header names a shape)
+            if (felics_read_header(buf.data(), buf.size(), &hh) == FELICS_OK && (uint64_t)hh.width * hh.height <= (1u << 22) &&  // (crops are this driver's to allocate)
+                !regions_on(given, given.size(), hh, false, 8)) {
+                fprintf(stderr, "%s: a region of a given pair wrote past its crop\n", n.c_str());
+                return 1;
+            }
         }
         for (uint32_t seg : {4096u, 12288u}) {
             size_t ilen = 0;
@@ -107,6 +158,27 @@ int main(int argc, char **argv) {
                 fprintf(stderr, "%s: indexed decode %d, or other pixels than felics_decompress\n", n.c_str(), rc);
                 return 1;
             }
+            if (!regions_on(index, ilen, h, true, 24)) {
+                fprintf(stderr, "%s: a region of a good pair failed, differs from felics_decompress's window or wrote past its crop\n", n.c_str());
+                return 1;
+            }
+            for (int k = 0; k < 8; k++) {  // the planner against a marking of the region's pixels
+                const felics_region r = region_of(h.width, h.height);
+                const size_t K = ((size_t)h.width * h.height + seg - 1) / seg;
+                size_t cnt = 0;
+                segs.assign(K + 1, 0);
+                mark.assign(K + 1, 0);
+                for (uint32_t yy = 0; yy < r.h; yy++)
+                    for (uint32_t xx = 0; xx < r.w; xx++) mark[((size_t)(r.y + yy) * h.width + r.x + xx) / seg] = 1;
+                bool same = felics_region_segments(h.width, h.height, seg, &r, segs.data(), K, &cnt) == FELICS_OK;
+                size_t at = 0;
+                for (size_t j = 0; same && j < K; j++)
+                    if (mark[j]) same = at < cnt && segs[at++] == j;
+                if (!same || at != cnt) {
+                    fprintf(stderr, "%s: felics_region_segments differs from the marking\n", n.c_str());
+                    return 1;
+                }
+            }
             idx.assign(index.begin(), index.begin() + ilen);
             const int rounds = ilen > (1u << 20) ? 10 : 60;
             for (int m = 0; m < rounds; m++) {
@@ -120,6 +192,10 @@ int main(int argc, char **argv) {
                 }
                 mutations++;
                 if (felics_decompress_indexed(buf.data(), buf.size(), bad.data(), bad.size(), px.data(), px.size(), &h2) == FELICS_OK) mut_accepted++;
+                if (!regions_on(bad, bad.size(), h, false, 2)) {
+                    fprintf(stderr, "%s: a region of a mutated index wrote past its crop\n", n.c_str());
+                    return 1;
+                }
                 if (m % 10 == 0) {  // and cut short
                     const size_t cut = (size_t)(next() % ilen);
                     if (felics_decompress_indexed(buf.data(), buf.size(), bad.data(), cut, px.data(), px.size(), &h2) == FELICS_OK) {
@@ -130,7 +206,7 @@ int main(int argc, char **argv) {
             }
         }
     }
-    printf("index_fuzz: %zu files, %zu indexes built, %zu refused, %zu pairs (%zu accepted), %zu mutations (%zu accepted)\n", names.size(), built, refused,
-           pairs, pairs_ok, mutations, mut_accepted);
+    printf("index_fuzz: %zu files, %zu indexes built, %zu refused, %zu pairs (%zu accepted), %zu mutations (%zu accepted), %zu regions\n", names.size(), built,
+           refused, pairs, pairs_ok, mutations, mut_accepted, regions);
     return 0;
 }

@@ -385,7 +385,8 @@ uint32_t felics_decode_lanes_min_streams(int depth, int color);
  * next checkpoint's bit_offset (plane_end_bit[c] for a plane's last segment).
  * WHAT THE CHECKS DO NOT PROVE: an index that passes all of this but was built from another stream can still yield wrong pixels,
  * as a corrupt stream can.  Pairing index and stream is the caller's contract.  No index makes the decoder read or write out of
- * bounds.  16-bit streams have no index: every call here returns FELICS_E_UNSUPPORTED for them. */
+ * bounds.  The REGION calls (below) prove less still: they make the checks of the segments a region needs and of no other, and
+ * no end check where a walk stops early.  16-bit streams have no index: every call here returns FELICS_E_UNSUPPORTED for them. */
 #define FELICS_INDEX_GRANULE 4096u
 
 /* Host only: the size of the index of a w x h 8-bit image; 0 for depth 16, a bad colour, w * h >= 2^32 or a segment_pixels that
@@ -434,6 +435,62 @@ typedef struct felics_index_stats {
 } felics_index_stats;
 /* Writes min(out_size, sizeof(felics_index_stats)) bytes, never more. */
 int felics_get_index_stats(const felics_ctx *ctx, felics_index_stats *out, size_t out_size);
+
+/* ---- Restart index: regions ----
+ * Random access through the index: the w x h window at (x, y) of a frame, from the segments that hold a pixel of it and from no
+ * other.  A plane's segment j covers its pixels [j * segment_pixels, min(W * H, (j + 1) * segment_pixels)) in raster order; it is
+ * NEEDED iff that range meets [yy * W + x, yy * W + x + w) for some row yy of the region.  The needed segments are not always one
+ * range: where a row is wider than a segment, those wholly between two rows' column spans are skipped.  The stream is serial, so a
+ * needed segment is walked from its first pixel, and up to stop = min(its end, (y + h - 1) * W + x + w) -- not to its end.
+ * WHAT A REGION'S CHECKS COVER: the stream header and the index header in full; of the NEEDED segments the bit range
+ * (bit_offset rules above) and the window samples; the end check of a segment that is walked to its end; of a walk that stops
+ * early only that the reader did not run off the stream.  WHAT THEY LEAVE OUT: every check of a segment the region does not need,
+ * and the end check of a walk that stops early -- a region call can succeed on a pair felics_decompress_indexed refuses, and it
+ * proves no more about the rest of the index than the paragraph above says of the whole. */
+typedef struct felics_region {
+    uint32_t stream;      /* which stream of the call (device call only) */
+    uint32_t x, y, w, h;  /* the window: x + w <= W, y + h <= H; w = 0 or h = 0 is an empty region */
+} felics_region;
+
+/* Host only, the planner: the needed segments of a plane of a W x H image cut every segment_pixels pixels, ascending, worked out
+ * per segment in closed form.  *count = how many there are (0 for an empty region); FELICS_E_BUFFER_TOO_SMALL if cap is short (segs
+ * may be NULL then), FELICS_E_INVALID_ARGUMENT for x + w > W or y + h > H (64-bit sums), W * H >= 2^32 or a bad segment_pixels.
+ * r->stream is ignored. */
+int felics_region_segments(uint32_t W, uint32_t H, uint32_t segment_pixels, const felics_region *r, uint32_t *segs, size_t cap,
+                           size_t *count);
+
+/* Host only: the dense w x h x C crop of the stream's image (every sample that of felics_decompress at its place), decoded from the
+ * checkpoints of the needed segments alone, in (plane, segment) order; the first failure gives the code.  The host model of
+ * k_decode8_region: the same checks in the same order (above).  FELICS_E_INVALID_ARGUMENT for a region outside the image,
+ * FELICS_E_BUFFER_TOO_SMALL for w * h * C > pixels_cap.  r->stream is ignored. */
+int felics_decompress_region_indexed(const uint8_t *in, size_t len, const uint8_t *index, size_t index_len, const felics_region *r,
+                                     void *pixels, size_t pixels_cap, felics_header *hdr);
+
+/* GPU: n_regions windows of n_streams 8-bit streams of ONE shape with their indexes, all in device memory as for
+ * felics_decompress_batch_device_indexed (same alignment rules; stream 0's header names the shape, index 0's segment_pixels and K).
+ * Region r is a window of stream regions[r].stream (`regions` is host memory; several may name one stream); its crop is written
+ * dense at d_pixels + out_offsets[r], the crops back to back in request order (out_offsets: host, optional).  One wave per
+ * (region, plane, needed segment): k_decode8_region, a walk of its own that stops at `stop`; RGB scratch is crop-sized.  status[r]
+ * (n_regions of them) is the code of region r's first failing item in (plane, segment) order, after the header checks of its stream
+ * and index (made for an empty region too).  A failing region leaves only its own crop undefined.
+ * Before anything is launched: FELICS_E_INVALID_ARGUMENT for a region outside the image or a stream number >= n_streams,
+ * FELICS_E_BUFFER_TOO_SMALL if the crops do not fit d_pixels_cap; rows too wide for the LDS and 16-bit streams: FELICS_E_UNSUPPORTED
+ * (a call that ends so puts its code into every status).  Refused like the other synchronous entry points while a ticket is
+ * outstanding.  Dense output only: no views, no ready event, no queued form. */
+int felics_decompress_regions_device_indexed(felics_ctx *ctx, size_t n_streams, const void *d_streams, const uint64_t *offsets,
+                                             const uint64_t *lens, const void *d_index, size_t index_stride, size_t n_regions,
+                                             const felics_region *regions, void *d_pixels, size_t d_pixels_cap, uint64_t *out_offsets,
+                                             felics_header *hdr, int *status);
+
+/* What a context's region calls did so far (cumulative; calls that passed the checks before the launch). */
+typedef struct felics_region_stats {
+    uint64_t regions;           /* regions handed in */
+    uint64_t segments_walked;   /* (region, plane, segment) waves launched */
+    uint64_t segments_skipped;  /* C * K per region minus what was walked */
+    uint64_t pixels_walked;     /* pixels those waves were asked to decode: stop - first pixel, summed */
+} felics_region_stats;
+/* Writes min(out_size, sizeof(felics_region_stats)) bytes, never more. */
+int felics_get_region_stats(const felics_ctx *ctx, felics_region_stats *out, size_t out_size);
 
 /* felics_decompress_images_device into views: stream i (at d_streams + offsets[i], lens[i] bytes) is decoded straight into views[i]
  * -- sample (x, y, c) of the decoded image lands at data + y * row_stride + x * pixel_stride + c * channel_stride, sample for sample
