@@ -99,7 +99,7 @@ class _CDecodeStats(C.Structure):  # felics_decode_stats
 
 
 class _CIndexStats(C.Structure):  # felics_index_stats
-    _fields_ = [("streams", C.c_uint64), ("segments8", C.c_uint64)]
+    _fields_ = [("streams", C.c_uint64), ("segments8", C.c_uint64), ("lane_segments8", C.c_uint64), ("lane_passes", C.c_uint64)]
 
 
 class _CRegion(C.Structure):  # felics_region
@@ -143,7 +143,7 @@ EXPORTS = [
     "felics_decompress_views_device", "felics_view_writable", "felics_get_decode_view_stats",
     "felics_surfaces_extent", "felics_submit_surfaces_device", "felics_compress_surfaces_device", "felics_get_surface_stats",
     "felics_index_size", "felics_index_build", "felics_decompress_indexed", "felics_decompress_batch_device_indexed",
-    "felics_get_index_stats", "felics_compress_batch_device_indexed",
+    "felics_get_index_stats", "felics_compress_batch_device_indexed", "felics_index_lanes_min_items",
     "felics_region_segments", "felics_decompress_region_indexed", "felics_decompress_regions_device_indexed", "felics_get_region_stats",
 ]
 
@@ -229,6 +229,9 @@ def lib():
     L.felics_compress_batch_device_indexed.argtypes = [vp, sz, vp, C.c_uint32, C.c_uint32, C.c_int, C.c_int, vp, sz, C.c_uint32, vp, sz,
                                                       C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
     L.felics_get_index_stats.argtypes = [vp, C.POINTER(_CIndexStats), sz]
+    if hasattr(L, "felics_index_lanes_min_items"):  # (as above: an older build has one form of the indexed decode call)
+        L.felics_index_lanes_min_items.argtypes = [C.c_int]
+        L.felics_index_lanes_min_items.restype = C.c_uint32
     if hasattr(L, "felics_region_segments"):  # (as above: an older build has no regions)
         L.felics_region_segments.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(_CRegion), C.POINTER(C.c_uint32), sz, C.POINTER(sz)]
         L.felics_decompress_region_indexed.argtypes = [vp, sz, vp, sz, C.POINTER(_CRegion), vp, sz, C.POINTER(_CHeader)]
@@ -638,7 +641,10 @@ class Encoder:
 
     def decompress_batch_device_indexed(self, d_streams, offsets, lens, d_index, index_stride, d_pixels, d_pixels_cap):
         """felics_decompress_batch_device_indexed: streams of one shape, their restart indexes (index i at d_index + i * index_stride)
-        and the pixels in device memory (raw pointers); a wave per (stream, plane, segment).  Returns (Header, status array); raises
+        and the pixels in device memory (raw pointers).  A wave per (stream, plane, segment); from index_lanes_min_items(color)
+        items on (n // 64 * 64 * C * K, with W >= 8 and n >= 64) the first n // 64 * 64 streams are decoded 64 segments to a wave, a
+        lane per stream, and the rest a wave per segment beside them: same pixels, same statuses, decode_stats() says which form ran
+        (FELICS_TEST_INDEX_LANES=1 / =0 forces / forbids the lane form).  Returns (Header, status array); raises
         DecompressionError with the first failing stream's code if it is a stream error, FelicsError otherwise (both carry .status)."""
         offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
         lens = np.ascontiguousarray(lens, dtype=np.uint64)
@@ -777,12 +783,15 @@ class Encoder:
         if rc != 0:
             self._raise(rc)
         out = {k: int(getattr(st, k)) for k, _ in _CDecodeStats._fields_}
-        # (felics_index_stats: the segments decompress_batch_device_indexed gave a wave each, n * C * K)
+        # (felics_index_stats: the segments decompress_batch_device_indexed gave a wave each / a lane each -- together n * C * K per
+        # call -- and the lane-form passes it launched)
         ist = _CIndexStats()
         rc = lib().felics_get_index_stats(self._h, C.byref(ist), C.sizeof(ist))
         if rc != 0:
             self._raise(rc)
         out["segments8"] = int(ist.segments8)
+        out["lane_segments8"] = int(ist.lane_segments8)
+        out["lane_passes"] = int(ist.lane_passes)
         return out
 
     def lane_count(self):
@@ -825,6 +834,13 @@ def decode16_lanes_min_streams(color=0):
     """felics_decode_lanes_min_streams(1, color): streams a device decode call must hold for its 16-bit streams (color: 0 gray, 1 RGB) to be
     decoded 64 to a wave; 0xFFFFFFFF: never (the form is then reached with FELICS_TEST_DECODE16_LANES=1 only)."""
     return int(lib().felics_decode_lanes_min_streams(1, int(color)))
+
+
+def index_lanes_min_items(color=0):
+    """felics_index_lanes_min_items(color): lane-form items (n // 64 * 64 * C * K) from which decompress_batch_device_indexed decodes
+    64 segments to a wave by itself (color: 0 gray, 1 RGB); 0xFFFFFFFF: never (the form is then reached with
+    FELICS_TEST_INDEX_LANES=1 only)."""
+    return int(lib().felics_index_lanes_min_items(int(color)))
 
 
 def default_encoder(device=0):

@@ -102,6 +102,30 @@ int dec16_lanes_epoch(felics_ctx *ctx, hipStream_t s, uint32_t &epoch0) {
     return FELICS_OK;
 }
 
+// FELICS_TEST_INDEX_LANES_PASS=k: at most k items (rounded down to whole waves, at least one) in a pass of the indexed lane form (tests)
+uint64_t index_lanes_pass_cap() {
+    const char *e = getenv("FELICS_TEST_INDEX_LANES_PASS");
+    if (!e || atoll(e) <= 0) return UINT64_MAX;
+    return std::max<uint64_t>(64, (uint64_t)atoll(e) / 64 * 64);
+}
+
+// Indexed lane form: dec_lane_table for passes of `bytes` <= want bytes (what the whole call would like), at least `least` (one
+// wave's tables), bounded as dec16_lanes_tables bounds the 16-bit lane tables: at most a quarter of the free HBM, counting what the
+// context already holds, and an allocation that fails all the same halves the pass.  (Nothing to zero: the kernel loads the rows.)
+int index_lanes_tables(felics_ctx *ctx, size_t want, size_t least, size_t &bytes) {
+    bytes = want;
+    size_t free_b = 0, total_b = 0;
+    if (hipMemGetInfo(&free_b, &total_b) == hipSuccess && ctx->dec_lane_table.cap < bytes)
+        bytes = std::max(least, std::min(bytes, std::max(ctx->dec_lane_table.cap, (free_b + ctx->dec_lane_table.cap) / 4)));
+    for (;;) {
+        const int rc = reserve(ctx, ctx->dec_lane_table, bytes);
+        if (rc == 0) return FELICS_OK;
+        (void)hipGetLastError();
+        if (bytes <= least) return rc;
+        bytes = std::max(least, bytes / 2);
+    }
+}
+
 constexpr int HOST_DECODE_NO_MEMORY = 1;  // (not a status: the host could not hold the stream)
 
 // One stream through the host decoder (rows too wide for the LDS): copied to the host, decoded, the frame copied to d_dst.  A stream
@@ -826,6 +850,8 @@ int felics_decompress_batch_device(felics_ctx *ctx, size_t n, const void *d_stre
     return FELICS_OK;
 }
 
+uint32_t felics_index_lanes_min_items(int color) { return color ? INDEX8_LANES_MIN_ITEMS_RGB : INDEX8_LANES_MIN_ITEMS; }
+
 int felics_get_index_stats(const felics_ctx *ctx, felics_index_stats *out, size_t out_size) {
     if (!ctx || !out) return FELICS_E_INVALID_ARGUMENT;
     memcpy(out, &ctx->istats, std::min(out_size, sizeof(felics_index_stats)));
@@ -879,16 +905,58 @@ int felics_decompress_batch_device_indexed(felics_ctx *ctx, size_t n, const void
         if ((rc = reserve(ctx, ctx->dec_planes, (size_t)(npix * 3 * 2 * n) + 64)) != 0) return fail_all(rc);
         d_planes = (int16_t *)ctx->dec_planes.p;
     }
+    // Which form (felics.h): the first n64 streams 64 segments to a wave, the others a wave per segment beside them
+    size_t n64 = 0;
+    if (hdr.width >= 8 && L.K >= 1 && n >= 64) {
+        const uint64_t items = (uint64_t)(n / 64 * 64) * planes * L.K;
+        const uint32_t least = felics_index_lanes_min_items(hdr.color_type);
+        bool by_lane = least != INDEX8_LANES_NEVER && items >= least;
+        if (const char *e = getenv("FELICS_TEST_INDEX_LANES")) by_lane = atoi(e) != 0;
+        if (by_lane) n64 = n / 64 * 64;
+    }
+    // the lane form's passes: whole waves, within the table memory index_lanes_tables grants
+    const uint64_t waves = (uint64_t)(n64 / 64) * planes * L.K;
+    uint64_t pass_waves = 0;
+    if (waves) {
+        const size_t wave_bytes = index8_lanes_table_bytes(64, hdr.color_type);
+        size_t tbytes = 0;
+        if ((rc = index_lanes_tables(ctx, (size_t)std::min<uint64_t>(waves, index_lanes_pass_cap() / 64) * wave_bytes, wave_bytes, tbytes)) != 0)
+            return fail_all(rc);
+        pass_waves = std::min<uint64_t>(waves, tbytes / wave_bytes);
+    }
     ctx->istats.streams += n;
-    ctx->istats.segments8 += n * planes * L.K;
-    hipStream_t s = ctx->lanes[0].stream;
+    ctx->istats.lane_segments8 += waves * 64;
+    ctx->istats.segments8 += (n - n64) * planes * L.K;
+    Lane &l = ctx->lanes[0];
+    hipStream_t s = l.stream;
+    int *seg_status = (int *)ctx->dec_seg_status.p;
     for (size_t i = 0; i < n; i++) status[i] = FELICS_E_HIP;  // until the kernel's own word arrives
     HIP_TRY(ctx, hipMemcpyAsync(d_off, offsets, n * 8, hipMemcpyHostToDevice, s));
     HIP_TRY(ctx, hipMemcpyAsync(d_len, lens, n * 8, hipMemcpyHostToDevice, s));
     HIP_TRY(ctx, hipMemsetAsync(d_status, 0xFF, n * 4, s));
-    HIP_TRY(ctx, hipMemsetAsync(ctx->dec_seg_status.p, 0xFF, (size_t)(n * per) * 4, s));
-    HIP_TRY(ctx, launch_decode8_seg(s, (const uint8_t *)d_streams, d_off, d_len, (const uint8_t *)d_index, index_stride, (uint32_t)n, hdr.width,
-                                    hdr.height, hdr.color_type, seg, L.K, (uint8_t *)d_pixels, d_planes, (int *)ctx->dec_seg_status.p, d_status));
+    HIP_TRY(ctx, hipMemsetAsync(seg_status, 0xFF, (size_t)(n * per) * 4, s));
+    const bool beside = n64 && n64 < n;  // the wave form's streams run on the lane's front stream, between two events
+    hipStream_t s2 = beside ? l.front : s;
+    if (beside) {
+        HIP_TRY(ctx, hipEventRecord(l.slice_done[0], s));
+        HIP_TRY(ctx, hipStreamWaitEvent(s2, l.slice_done[0], 0));
+    }
+    // (the kernel is handed the pointers of stream n64 on and knows nothing of the streams in front)
+    HIP_TRY(ctx, launch_decode8_seg(s2, (const uint8_t *)d_streams, d_off + n64, d_len + n64, (const uint8_t *)d_index + n64 * index_stride,
+                                    index_stride, (uint32_t)(n - n64), hdr.width, hdr.height, hdr.color_type, seg, L.K,
+                                    (uint8_t *)d_pixels + n64 * frame_bytes, d_planes ? d_planes + n64 * 3 * npix : nullptr, seg_status + n64 * per,
+                                    d_status + n64));
+    for (uint64_t w0 = 0; w0 < waves; w0 += pass_waves) {  // behind one another: they share the tables
+        HIP_TRY(ctx, launch_decode8_seg_lanes(s, (const uint8_t *)d_streams, d_off, d_len, (const uint8_t *)d_index, index_stride, hdr.width, hdr.height,
+                                              hdr.color_type, seg, L.K, (uint32_t)w0, (uint32_t)std::min(pass_waves, waves - w0),
+                                              (uint8_t *)d_pixels, d_planes, (uint32_t *)ctx->dec_lane_table.p, seg_status));
+        ctx->istats.lane_passes++;
+    }
+    HIP_TRY(ctx, launch_seg_finish(s, (uint32_t)n64, hdr.width, hdr.height, hdr.color_type, L.K, (uint8_t *)d_pixels, d_planes, seg_status, d_status));
+    if (beside) {
+        HIP_TRY(ctx, hipEventRecord(l.spine_done[0], s2));
+        HIP_TRY(ctx, hipStreamWaitEvent(s, l.spine_done[0], 0));
+    }
     HIP_TRY(ctx, hipMemcpyAsync(status, d_status, n * 4, hipMemcpyDeviceToHost, s));
     HIP_TRY(ctx, hipStreamSynchronize(s));
     for (size_t i = 0; i < n; i++)

@@ -880,6 +880,26 @@ struct LaneReader {
             navail -= 8u * skew;
         }
     }
+    // the same, positioned `bit` bits behind p (bit <= 8 n: the caller's check, so the first dword asked for holds a stream byte or lies
+    // right behind the last one; like every fetch it is bounded by total_dw)
+    __device__ __forceinline__ void init_at(const uint8_t *p, uint64_t n, uint64_t bit) {
+        const uint32_t skew = (uint32_t)(reinterpret_cast<uintptr_t>(p) & 3u);
+        al = reinterpret_cast<const uint32_t *>(p - skew);
+        total_dw = (uint32_t)std::min<uint64_t>((skew + n + 3u) >> 2, 0xFFFFFFFFull);
+        end_bit = (skew + n) * 8u;
+        const uint64_t at = 8u * skew + bit;
+        pos = (uint32_t)std::min<uint64_t>(at >> 5, 0xFFFFFFFEull);
+        nxt = fetch(pos);
+        acc = 0;
+        navail = 0;
+        refill();
+        acc <<= (uint32_t)(at & 31u);
+        navail -= (uint32_t)(at & 31u);
+    }
+    // bits consumed so far, counted from p (the pointer init / init_at was given)
+    __device__ __forceinline__ uint64_t bit_pos(const uint8_t *p) const {
+        return (uint64_t)pos * 32u - navail - 8u * (uint32_t)(reinterpret_cast<uintptr_t>(p) & 3u);
+    }
     // at least 33 valid bits in acc afterwards (zeros past the end of the stream)
     __device__ __forceinline__ void refill() {
         if (navail <= 32u) {
@@ -1206,6 +1226,300 @@ __global__ __launch_bounds__(64) void k_decode8_lanes(const uint8_t *__restrict_
     }
     if (br.failed() && rc == FELICS_OK) rc = FELICS_E_IO;  // (whatever else: it was decoding padding)
     status[img] = rc;
+}
+
+// ------------------------------------------------------------------------------------------
+// Sixty-four SEGMENTS per wave, LANE = stream (felics_decompress_batch_device_indexed on large batches).
+//
+// Segment j of 64 streams of one shape starts at the same pixel p0, so at the same (x, y): 64 such segments share a wave exactly as 64
+// streams share one in k_decode8_lanes, with (x, y) wave-uniform.  Wave wave0 + blockIdx.x is (group g of 64 consecutive streams,
+// plane c, segment j) = (w / (C K), w / K % C, w % K); lane l is stream 64 g + l (the launch covers whole groups only).  The
+// per-pixel path is k_decode8_lanes's, statement for statement; what differs is k_decode8_seg's business:
+//   * every lane makes k_decode8_seg's checks, in its order: the stream's header, the index header against it and the launch's
+//     (segment_pixels, K: no checkpoint is read outside index_stride), the segment's bit range, the window's samples (a u8 sample is
+//     in range whatever it holds: only the int16 windows are looked through).  A lane that fails one writes its code and leaves;
+//   * the reader is a LaneReader positioned on the checkpoint's bit_offset (init_at); segment 0 reads the plane's two raw samples;
+//   * the estimator is LOADED, not zeroed: the checkpoint's u16 state[nctx][6] is three dwords per context in the lane table's
+//     pairing, so the first DEC8L_HOT contexts are a dword copy into the lane's LDS column and the others a dword copy into the item's
+//     rows of `table` (TABLE_DW dwords per item of the launch, nothing to zero) -- the wave copies one lane's rows after the other,
+//     coalesced.  d_index is only read.  The 16-bit bound of k_decode8_lanes holds for every checkpoint felics_index_build or the
+//     encoder writes: its counters are a snapshot of an estimator that obeys the bound at every pixel.  A forged checkpoint can hold
+//     up to 65 535 per counter; a pair's low counter can then carry into the high one -- wrong values of k for a segment whose index
+//     is wrong anyway (the end check is what judges it), and no address depends on a counter;
+//   * the row above: pixel q >= p0 is read back from the lane's own output plane (it wrote it itself), q < p0 from the checkpoint's
+//     window at 2 W - (p0 - q) -- the pixels in front of p0 are another wave's, which may not have written them yet: the output is
+//     NEVER read below p0.  p0, x and y are wave-uniform, so each choice is a uniform branch.  A group of four that straddles p0,
+//     and a row's short last group, are assembled sample by sample: no load runs past sample W - 1 of a row, in the window or in the
+//     plane.  Window positions in front of the plane (p0 + t < 2 W) are never looked at;
+//   * only pixels p0 .. pend - 1 are written: a first group with x0 & 3 != 0 is stored from x0 on, a last group that ends inside
+//     four samples is flushed sample by sample;
+//   * at the end FELICS_E_IO if the reader ran off the stream, else the end check: the bit position equals the next checkpoint's
+//     bit_offset (plane_end_bit[c] behind the last), else FELICS_E_INVALID_INDEX.
+// seg_status[(img * C + c) * K + j] = FELICS_OK or the code, as k_decode8_seg writes it: k_seg_status picks a stream's first.
+// A lane that fails mid-walk keeps walking on zeros, its samples clamped (the lane form's rule), inside its own segment and rows.
+// Needs W >= 8 and K >= 1.
+// ------------------------------------------------------------------------------------------
+template <bool RGB>
+__global__ __launch_bounds__(64) void k_decode8_seg_lanes(const uint8_t *__restrict__ streams, const uint64_t *__restrict__ offsets,
+                                                          const uint64_t *__restrict__ lens, const uint8_t *__restrict__ index,
+                                                          uint64_t index_stride, uint32_t W, uint32_t H, uint32_t segment_pixels, uint32_t K,
+                                                          uint32_t wave0, void *out_base, uint32_t *table, int *seg_status) {
+    using ST = typename std::conditional<RGB, int16_t, uint8_t>::type;
+    constexpr uint32_t NP = RGB ? 3u : 1u;
+    constexpr uint32_t NCTX = RGB ? 512u : 256u;                                // rows of a checkpoint's state (IndexLayout::nctx)
+    constexpr uint32_t TABLE_DW = RGB ? DEC8L_TABLE_DW_RGB : DEC8L_TABLE_DW;  // per item
+    static_assert(TABLE_DW == NCTX * 3, "a checkpoint's state is the lane table's rows");
+    constexpr int LO_OK = RGB ? -255 : 0, HI_OK = 255;
+    __shared__ uint32_t hot[DEC8L_HOT * 3 * 64];  // [context][pair of counters][lane]
+    const uint32_t lane = lane_id();
+    const uint32_t wv = wave0 + blockIdx.x;
+    const uint32_t g = wv / (NP * K), c = wv / K % NP, j = wv % K;
+    const uint32_t img = g * 64 + lane;
+    const uint8_t *s = streams + offsets[img];
+    const uint64_t slen = lens[img];
+    const uint8_t *idx = index + (uint64_t)img * index_stride;
+    const uint64_t npix = (uint64_t)W * H;
+    // the stream's header (format.rs:63-84) must be the one the caller announced, the index header must fit both
+    int rc = FELICS_OK;
+    uint64_t start = 0, end = 0;
+    if (slen < FELICS_HEADER_BYTES) {
+        rc = FELICS_E_IO;
+    } else {
+        IndexLayout L;
+        const uint32_t w = ((uint32_t)s[6] << 24) | ((uint32_t)s[7] << 16) | ((uint32_t)s[8] << 8) | s[9];
+        const uint32_t h = ((uint32_t)s[10] << 24) | ((uint32_t)s[11] << 16) | ((uint32_t)s[12] << 8) | s[13];
+        if (s[0] != 'F' || s[1] != 'L' || s[2] != 'C' || s[3] != 'S') rc = FELICS_E_INVALID_SIGNATURE;
+        else if (s[4] > 1) rc = FELICS_E_INVALID_COLOR_TYPE;
+        else if (s[5] > 1) rc = FELICS_E_INVALID_PIXEL_DEPTH;
+        else if (s[4] != (RGB ? 1 : 0) || s[5] != 0 || w != W || h != H) rc = FELICS_E_INVALID_DIMENSIONS;
+        else if (index_header_check(idx, RGB ? 1u : 0u, W, H, slen, L) != FELICS_OK || idx_rd32(idx + IDX_SEGPIX) != segment_pixels || L.K != K)
+            rc = FELICS_E_INVALID_INDEX;
+        else
+            rc = index_segment_bounds(idx, L, c, j, slen, start, end);
+    }
+    // (a lane that passed has the launch's layout: shape, colour and segment_pixels are what the layout is made of)
+    const IndexLayout LL = index_layout(W, H, RGB ? 1u : 0u, segment_pixels);
+    const uint64_t cp_off = INDEX_HEADER_BYTES + ((uint64_t)c * K + j) * LL.cp_bytes;
+    const uint64_t p0 = (uint64_t)j * segment_pixels, pend = min(npix, p0 + segment_pixels);  // this segment's pixels
+    // The wave's part of the set-up, one lane's checkpoint after the other (only lanes whose checks passed: their checkpoints lie
+    // inside index_stride): the cold rows of the state into the item's table rows, and the int16 window looked through.
+    const uint64_t okmask = __ballot(rc == FELICS_OK);
+    uint64_t badmask = 0;
+    uint32_t *wtab = table + (uint64_t)blockIdx.x * 64u * TABLE_DW;
+    for (uint32_t l = 0; l < 64; l++) {
+        if (!((okmask >> l) & 1u)) continue;
+        const uint8_t *cpl = index + (uint64_t)(g * 64 + l) * index_stride + cp_off;
+        // (index, index_stride and cp_bytes are multiples of 16, the state starts 8 bytes in: 8-byte loads)
+        const uint2 *src = reinterpret_cast<const uint2 *>(cpl + CP_STATE_OFF);
+        uint2 *dst = reinterpret_cast<uint2 *>(wtab + (uint64_t)l * TABLE_DW);
+        for (uint32_t i = DEC8L_HOT * 3 / 2 + lane; i < TABLE_DW / 2; i += 64) dst[i] = src[i];
+        if (RGB) {
+            const uint32_t *wd = reinterpret_cast<const uint32_t *>(cpl + LL.win_off);  // samples 2 t | 2 t + 1
+            const int lo_w = c ? -255 : 0;
+            bool bad = false;
+            for (uint32_t t = lane; t < W; t += 64) {
+                const uint32_t v2 = wd[t];
+                const int a = (int)(int16_t)(v2 & 0xFFFFu), b = (int)(int16_t)(v2 >> 16);
+                if (p0 + 2ull * t >= 2ull * W) bad |= a < lo_w || a > 255;  // (in front of the plane: zeros, never looked at)
+                if (p0 + 2ull * t + 1 >= 2ull * W) bad |= b < lo_w || b > 255;
+            }
+            if (__ballot(bad) != 0) badmask |= 1ull << l;
+        }
+    }
+    __threadfence_block();  // a lane reads rows that other lanes of its wave stored
+    __builtin_amdgcn_wave_barrier();
+    if (rc == FELICS_OK && ((badmask >> lane) & 1u)) rc = FELICS_E_INVALID_INDEX;
+    int *my_status = seg_status + ((uint64_t)img * NP + c) * K + j;
+    if (rc != FELICS_OK) {  // nothing of this segment is decoded (its lane leaves; the others go on)
+        *my_status = rc;
+        return;
+    }
+    const uint8_t *cp = idx + cp_off;
+    const ST *win = reinterpret_cast<const ST *>(cp + LL.win_off);  // sample t is pixel p0 - 2 W + t
+    uint32_t *myhot = hot + lane;
+    {
+        const uint2 *st = reinterpret_cast<const uint2 *>(cp + CP_STATE_OFF);
+        for (uint32_t i = 0; i < DEC8L_HOT * 3 / 2; i++) {  // the checkpoint's hot rows: a lane's own column
+            const uint2 v2 = st[i];
+            myhot[(2 * i) * 64] = v2.x;
+            myhot[(2 * i + 1) * 64] = v2.y;
+        }
+    }
+    uint32_t *tab = wtab + (uint64_t)lane * TABLE_DW;
+    ST *out = reinterpret_cast<ST *>(out_base) + ((uint64_t)img * NP + c) * npix;
+    LaneReader br;
+    br.init_at(s, slen, start);
+    int32_t raw0 = 0, raw1 = 0;
+    if (j == 0) {  // the plane's two raw samples (compression.rs:166-167) stand in front of its first segment only
+        raw0 = (int32_t)br.get(32);
+        raw1 = (int32_t)br.get(32);
+        if (br.failed()) rc = FELICS_E_IO;
+    }
+    // pixel q of the plane as this lane may read it: its own output from p0 on, the window in front (p0 - 2 W <= q: the callers' business)
+    auto rd = [&](uint64_t q) -> int { return q >= p0 ? (int)out[q] : (int)win[2ull * W - (p0 - q)]; };
+    // (x, y) and everything derived from them alone is wave-uniform
+    uint32_t x = (uint32_t)(p0 % W), y = (uint32_t)(p0 / W);
+    // row y - 1 from column xg (a multiple of four below W) on: four samples, or the row's last one to three
+    auto load_up = [&](uint32_t xg) {
+        Four<ST> f;
+        const uint64_t q0 = (uint64_t)(y - 1) * W + xg;
+        const uint32_t cnt = min(4u, W - xg);
+        if (cnt == 4u && q0 >= p0) {
+            f.load(out + q0);
+        } else if (cnt == 4u && q0 + 4u <= p0) {
+            f.load(win + (2ull * W - (p0 - q0)));
+        } else {
+            f.clear();
+            for (uint32_t k = 0; k < cnt; k++) f.set(k, rd(q0 + k));
+        }
+        return f;
+    };
+    int left = x >= 1 ? (int)win[2ull * W - 1] : 0, left2 = x >= 2 ? (int)win[2ull * W - 2] : 0;
+    Four<ST> up4, up4_next, out4;
+    up4.clear();
+    up4_next.clear();
+    out4.clear();
+    if (x != 0 && y > 0) {  // a start inside a row: the groups of the row above that the row's start would have asked for
+        if ((x & 3u) == 0) {
+            up4_next = load_up(x);  // (moved into up4 by the first pixel)
+        } else {
+            up4 = load_up(x & ~3u);
+            if ((x & ~3u) + 4 < W) up4_next = load_up((x & ~3u) + 4);
+        }
+    }
+    uint32_t gfirst = x & 3u;   // first sample of the current group that is this segment's to store
+    uint32_t out_of_range = 0;  // gray: OR of every sample as decoded (above 255 if one did not fit); RGB: nonzero if one was outside LO_OK .. HI_OK
+    int first_col2 = 0;
+    for (uint64_t i = p0; i < pend; i++) {
+        const uint32_t xs = x & 3u;
+        if (x == 0 && y > 0) {
+            up4 = load_up(0);  // row above, samples 0 .. 3 (later groups are asked for four samples ahead); W >= 8
+            up4_next = load_up(4);
+            // second neighbour of a row's first pixel (misc.rs:14-23): two rows up, or above-right in row 1
+            first_col2 = y >= 2 ? rd((uint64_t)(y - 2) * W) : up4.get(1);
+        } else if (xs == 0 && y > 0) {
+            up4 = up4_next;
+            if (x + 4 < W) up4_next = load_up(x + 4);
+        }
+        int pv;
+        if (i < 2) {
+            pv = i == 0 ? raw0 : raw1;
+        } else {
+            const int above = up4.get(xs);
+            const bool row0 = y == 0, col0 = x == 0 && !row0;
+            const int v1 = col0 ? above : left;
+            const int v2 = col0 ? first_col2 : (row0 ? left2 : above);
+            const int hi = max(v1, v2), lo = min(v1, v2);
+            const uint32_t ctx = (uint32_t)(hi - lo);  // <= 255 (510): every sample kept is in range, every window sample checked
+            const bool is_hot = ctx < DEC8L_HOT;
+            const uint32_t hrow = min(ctx, DEC8L_HOT - 1u) * 3u * 64u;
+            uint32_t w01 = myhot[hrow], w23 = myhot[hrow + 64], w45 = myhot[hrow + 128];
+            br.refill();  // >= 33 valid bits: both kinds of code are read off the top 32 of them, then consumed in one go
+            const uint32_t top = (uint32_t)(br.acc >> 32);
+            const bool in_range = (top >> 31) != 0;
+            // -- in range: `1`, then the phased-in code of p - L in m or m + 1 bits (phase_in_coding.rs:86-112)
+            const uint32_t nn = ctx + 1;
+            const uint32_t m = 31u - (uint32_t)__builtin_clz(nn);
+            const uint32_t right_p = (2u << m) - nn, left_p = nn - (1u << m);
+            const uint32_t t1 = top << 1;
+            uint32_t r = (t1 >> 1) >> (31u - m);               // the m bits behind the flag
+            const uint32_t extra = (t1 >> (31u - m)) & 1u;      // the bit behind them
+            const uint32_t longer = r >= right_p ? 1u : 0u;     // the code has one more bit
+            r = longer ? (r - right_p) * 2u + right_p + extra : r;
+            uint32_t rot = r + left_p;                          // rotate_left: (r + left_p) mod n, r < n
+            rot = rot >= nn ? rot - nn : rot;
+            const int pv_in = lo + (int)rot;
+            const uint32_t bits_in = 1u + m + longer;
+            // -- out of range: `0`, above / below flag, q ones, `0`, k bits -- off the same 32 bits when it fits in them
+            const bool above_flag = ((top >> 30) & 1u) != 0;
+            if (!in_range && !is_hot) {  // (noise: a cold context's row comes from the item's table in HBM)
+                w01 = tab[ctx * 3 + 0];
+                w23 = tab[ctx * 3 + 1];
+                w45 = tab[ctx * 3 + 2];
+            }
+            uint32_t S[6] = {w01 & 0xFFFFu, w01 >> 16, w23 & 0xFFFFu, w23 >> 16, w45 & 0xFFFFu, w45 >> 16};
+            // get_k: smallest counter, ties to the largest k (parameter_selection.rs:71-85)
+            const uint32_t key = min(min(min((S[0] << 3) | 7u, (S[1] << 3) | 6u), min((S[2] << 3) | 5u, (S[3] << 3) | 4u)),
+                                     min((S[4] << 3) | 3u, (S[5] << 3) | 2u));
+            const uint32_t k = 7u - (key & 7u);
+            const uint32_t t2 = top << 2;                                  // 30 bits of the stream, two zeros behind them
+            const uint32_t ones = (uint32_t)__builtin_clz(~t2);            // (<= 30: ~t2 ends in ones)
+            const bool fits = ones + 1u + k <= 30u;                        // unary part, its zero and the k bits lie inside the 30
+            uint32_t e = (ones << k) + (((t2 << (ones & 31u)) << 1 >> 1) >> (31u - k));  // k bits behind the zero (k <= 5)
+            uint32_t nbits = in_range ? bits_in : 3u + ones + k;
+            if (!in_range && !fits) {
+                // a long code (or the end of the stream): the general reader, bit field by bit field
+                br.take(2);
+                const uint64_t q = br.unary0();
+                const uint64_t e64 = (q << k) + br.get(k);
+                e = (uint32_t)e64;
+                if (e64 > 1024u) {  // no sample of an 8-bit plane is that far from its neighbours
+                    if (rc == FELICS_OK) rc = e64 > 0xFFFFFFFFull ? FELICS_E_VALUE_OVERFLOW : FELICS_E_INVALID_VALUE;
+                    e = 0;
+                }
+                nbits = 0;
+            }
+            br.acc <<= nbits;  // (nbits <= 32 < the valid bits)
+            br.navail -= nbits;
+            if (!in_range) {
+                // update (parameter_selection.rs:49-68): add the six Rice lengths, halve when the smallest passes 1024
+                uint32_t mn = 0xFFFFFFFFu;
+#pragma unroll
+                for (uint32_t kk = 0; kk < 6; kk++) {
+                    S[kk] += (e >> kk) + 1u + kk;
+                    mn = min(mn, S[kk]);
+                }
+                const uint32_t hsh = mn > 1024u ? 1u : 0u;
+                w01 = (S[0] >> hsh) | ((S[1] >> hsh) << 16);
+                w23 = (S[2] >> hsh) | ((S[3] >> hsh) << 16);
+                w45 = (S[4] >> hsh) | ((S[5] >> hsh) << 16);
+                if (is_hot) {
+                    myhot[hrow] = w01;
+                    myhot[hrow + 64] = w23;
+                    myhot[hrow + 128] = w45;
+                } else {
+                    tab[ctx * 3 + 0] = w01;
+                    tab[ctx * 3 + 1] = w23;
+                    tab[ctx * 3 + 2] = w45;
+                }
+            }
+            pv = in_range ? pv_in : (above_flag ? hi + (int)e + 1 : lo - (int)e - 1);
+        }
+        // out of LO_OK .. HI_OK: remembered and reported at the end of the row; the sample is cut into the range so that a failed
+        // lane's contexts stay inside the table
+        if (RGB) {
+            out_of_range |= (uint32_t)(pv - LO_OK) > (uint32_t)(HI_OK - LO_OK) ? 1u : 0u;
+            pv = min(max(pv, LO_OK), HI_OK);
+        } else {
+            out_of_range |= (uint32_t)pv;
+            pv &= 255;
+        }
+        out4.set(xs, pv);
+        left2 = left;
+        left = pv;
+        const bool row_end = x + 1 == W;
+        if (xs == 3u || row_end || i + 1 == pend) {  // a group is complete, or the row is, or the segment
+            ST *grp = out + (i - xs);                 // the group's first sample; samples gfirst .. xs of it are this segment's
+            if (xs == 3u && gfirst == 0) {
+                out4.store(grp);  // four samples: one (unaligned) store to the lane's plane
+            } else {
+                for (uint32_t k = gfirst; k <= xs; k++) grp[k] = (ST)out4.get(k);
+            }
+            out4.clear();
+            gfirst = 0;
+        }
+        if (row_end) {
+            if (rc == FELICS_OK) rc = br.failed() ? FELICS_E_IO : ((RGB ? out_of_range != 0 : out_of_range > 255u) ? FELICS_E_INVALID_VALUE : FELICS_OK);
+            x = 0;
+            y++;
+        } else {
+            x++;
+        }
+    }
+    if (br.failed()) rc = FELICS_E_IO;  // (whatever else stopped the decoding: it was decoding padding)
+    else if (rc == FELICS_OK && (RGB ? out_of_range != 0 : out_of_range > 255u)) rc = FELICS_E_INVALID_VALUE;
+    else if (rc == FELICS_OK && br.bit_pos(s) != end) rc = FELICS_E_INVALID_INDEX;  // the end check: exactly on the next checkpoint
+    *my_status = rc;
 }
 
 // The conversions' geometry: ConvUniform -- npix of every stream, stream = blockIdx.y, planes and frames back to back; DecMixed --
@@ -1983,6 +2297,33 @@ hipError_t launch_decode8_seg(hipStream_t s, const uint8_t *streams, const uint6
     hipLaunchKernelGGL(k_decode8_seg, dim3(n * per), dim3(64), lds, s, streams, offsets, lens, index, index_stride, DecUniform{W, H, color},
                        segment_pixels, K, pixels, planes, seg_status);
     hipLaunchKernelGGL(k_seg_status, dim3(n), dim3(64), 0, s, seg_status, per, status);
+    if (color) {
+        const uint64_t npix = (uint64_t)W * H;
+        const uint32_t bx = (uint32_t)std::min<uint64_t>((npix + 255) / 256, 1024u);
+        if (bx) hipLaunchKernelGGL(k_ycocg8_to_rgb<ConvUniform>, dim3(bx, n), dim3(256), 0, s, planes, pixels, ConvUniform{(uint32_t)npix}, status);
+    }
+    return hipGetLastError();
+}
+
+size_t index8_lanes_table_bytes(uint64_t items, uint32_t color) { return (size_t)items * (color ? DEC8L_TABLE_DW_RGB : DEC8L_TABLE_DW) * 4; }
+
+hipError_t launch_decode8_seg_lanes(hipStream_t s, const uint8_t *streams, const uint64_t *offsets, const uint64_t *lens, const uint8_t *index,
+                                    uint64_t index_stride, uint32_t W, uint32_t H, uint32_t color, uint32_t segment_pixels, uint32_t K,
+                                    uint32_t wave0, uint32_t nwaves, uint8_t *pixels, int16_t *planes, uint32_t *table, int *seg_status) {
+    if (nwaves == 0) return hipSuccess;
+    if (color)
+        hipLaunchKernelGGL(k_decode8_seg_lanes<true>, dim3(nwaves), dim3(64), 0, s, streams, offsets, lens, index, index_stride, W, H, segment_pixels,
+                           K, wave0, (void *)planes, table, seg_status);
+    else
+        hipLaunchKernelGGL(k_decode8_seg_lanes<false>, dim3(nwaves), dim3(64), 0, s, streams, offsets, lens, index, index_stride, W, H, segment_pixels,
+                           K, wave0, (void *)pixels, table, seg_status);
+    return hipGetLastError();
+}
+
+hipError_t launch_seg_finish(hipStream_t s, uint32_t n, uint32_t W, uint32_t H, uint32_t color, uint32_t K, uint8_t *pixels, int16_t *planes,
+                             const int *seg_status, int *status) {
+    if (n == 0) return hipSuccess;
+    hipLaunchKernelGGL(k_seg_status, dim3(n), dim3(64), 0, s, seg_status, (color ? 3u : 1u) * std::max(K, 1u), status);
     if (color) {
         const uint64_t npix = (uint64_t)W * H;
         const uint32_t bx = (uint32_t)std::min<uint64_t>((npix + 255) / 256, 1024u);

@@ -293,6 +293,26 @@ hipError_t launch_decode8(hipStream_t s, const uint8_t *streams, const uint64_t 
 hipError_t launch_decode8_seg(hipStream_t s, const uint8_t *streams, const uint64_t *offsets, const uint64_t *lens, const uint8_t *index,
                               uint64_t index_stride, uint32_t n, uint32_t W, uint32_t H, uint32_t color, uint32_t segment_pixels, uint32_t K,
                               uint8_t *pixels, int16_t *planes, int *seg_status, int *status);
+// The same call on large batches (k_decode8_seg_lanes): 64 segments per wave, lane = stream.  Wave w of the n / 64 * C * K waves of a
+// call is (group of 64 consecutive streams, plane, segment) = (w / (C K), w / K % C, w % K); a launch takes waves wave0 .. wave0 +
+// nwaves - 1 and a table of index8_lanes_table_bytes(64 * nwaves, color) bytes (3 KB per gray item, 6 KB per RGB item: the estimator
+// rows that do not live in LDS, loaded from the checkpoints: nothing to zero).  Needs W >= 8 and K >= 1.  It writes seg_status as
+// launch_decode8_seg's kernel does; launch_seg_finish is that launcher's tail for streams 0 .. n - 1: status[i] = stream i's first
+// failing word, then the RGB conversion of the clean ones.
+// The lane form is taken from this many lane-form items (n / 64 * 64 * C * K) on.  INDEX8_LANES_NEVER: no call takes the form by
+// itself (FELICS_TEST_INDEX_LANES=1 still does).  The values are to come from the sweep of profiles/tools/indexed_lanes.py, and that
+// sweep HAS NOT RUN YET (profiles/indexed_lanes.txt says so): until it has, neither colour takes the form by itself.  Where the sweep
+// is expected to put them: DECODE8_LANES_MIN_STREAMS (1536) and DECODE8_LANES_MIN_STREAMS_RGB (2048), an item being a stream as far as
+// both kernels are concerned.
+constexpr uint32_t INDEX8_LANES_NEVER = 0xFFFFFFFFu;
+constexpr uint32_t INDEX8_LANES_MIN_ITEMS = INDEX8_LANES_NEVER;
+constexpr uint32_t INDEX8_LANES_MIN_ITEMS_RGB = INDEX8_LANES_NEVER;
+size_t index8_lanes_table_bytes(uint64_t items, uint32_t color);
+hipError_t launch_decode8_seg_lanes(hipStream_t s, const uint8_t *streams, const uint64_t *offsets, const uint64_t *lens, const uint8_t *index,
+                                    uint64_t index_stride, uint32_t W, uint32_t H, uint32_t color, uint32_t segment_pixels, uint32_t K,
+                                    uint32_t wave0, uint32_t nwaves, uint8_t *pixels, int16_t *planes, uint32_t *table, int *seg_status);
+hipError_t launch_seg_finish(hipStream_t s, uint32_t n, uint32_t W, uint32_t H, uint32_t color, uint32_t K, uint8_t *pixels, int16_t *planes,
+                             const int *seg_status, int *status);
 // Regions of such streams (felics_decompress_regions_device_indexed, felics.h "Restart index: regions"): one wave per work item =
 // (region, plane, needed segment), k_decode8_region.  A region's items are contiguous, in (plane, segment) order; an item whose
 // segment is REGION_HEADER_ONLY makes the checks of its stream's header and index header and nothing else (the one item of an empty

@@ -423,7 +423,17 @@ int felics_compress_batch_device_indexed(felics_ctx *ctx, size_t n, const void *
  * and a stream whose own index header differs gets FELICS_E_INVALID_INDEX.  All checks above are made on the device; status[i] is
  * the code of stream i's first failing segment in (plane, segment) order; a failing segment leaves only its own pixels undefined
  * (for RGB: the frame is not converted).  Rows too wide for the LDS and 16-bit streams: FELICS_E_UNSUPPORTED in every status (no
- * host fallback in this call).  Refused like the other synchronous entry points while a ticket is outstanding. */
+ * host fallback in this call).  Refused like the other synchronous entry points while a ticket is outstanding.
+ * WHICH FORM A CALL TAKES.  A wave per segment is the form for a few frames; once the segments fill the chip, 63 of such a wave's 64
+ * lanes idle.  Segment j of 64 frames of one shape starts at the same pixel, so a large call decodes 64 segments per wave, a lane
+ * per stream (k_decode8_seg_lanes): with W >= 8, K >= 1 and n >= 64, the first n / 64 * 64 streams take that form if they make
+ * felics_index_lanes_min_items(color) items (n / 64 * 64 * C * K) or more, and the other n % 64 streams a wave per segment beside
+ * them in the same call.  Checks, statuses and pixels are the same in both forms; felics_index_stats says which ran.
+ * FELICS_TEST_INDEX_LANES=1 / =0 in the environment (read per call) forces / forbids the lane form for calls with W >= 8, K >= 1 and
+ * n >= 64, whatever the item count; FELICS_TEST_INDEX_LANES_PASS=k caps one pass of that form at k items (rounded down to whole
+ * waves of 64, at least one wave; tests).  The lane form runs in passes of whole waves, each within the table memory the context
+ * may take (6 KB per RGB item, 3 KB per gray one; at most a quarter of the free device memory).  The region call, 16-bit streams,
+ * W < 8 and n < 64 keep a wave per segment. */
 int felics_decompress_batch_device_indexed(felics_ctx *ctx, size_t n, const void *d_streams, const uint64_t *offsets, const uint64_t *lens,
                                            const void *d_index, size_t index_stride, void *d_pixels, size_t d_pixels_cap, felics_header *hdr,
                                            int *status);
@@ -431,10 +441,15 @@ int felics_decompress_batch_device_indexed(felics_ctx *ctx, size_t n, const void
 /* What a context's indexed decode calls did so far (cumulative).  (felics_decode_stats keeps its eight fields: these are counted here.) */
 typedef struct felics_index_stats {
     uint64_t streams;    /* streams handed to felics_decompress_batch_device_indexed (calls that passed the checks) */
-    uint64_t segments8;  /* segments launched, a wave each: n * C * K */
+    uint64_t segments8;  /* segments that got a wave each */
+    uint64_t lane_segments8;  /* segments walked by a lane each, 64 to a wave; segments8 + lane_segments8 = n * C * K per call */
+    uint64_t lane_passes;     /* lane-form passes launched */
 } felics_index_stats;
-/* Writes min(out_size, sizeof(felics_index_stats)) bytes, never more. */
+/* Writes min(out_size, sizeof(felics_index_stats)) bytes, never more: a caller built against the two-field struct stays valid. */
 int felics_get_index_stats(const felics_ctx *ctx, felics_index_stats *out, size_t out_size);
+/* Lane-form items (n / 64 * 64 * C * K) from which felics_decompress_batch_device_indexed takes the lane form by itself (color: 0
+ * gray, 1 RGB); 0xFFFFFFFF: no call does, the form is reachable through FELICS_TEST_INDEX_LANES=1 only. */
+uint32_t felics_index_lanes_min_items(int color);
 
 /* ---- Restart index: regions ----
  * Random access through the index: the w x h window at (x, y) of a frame, from the segments that hold a pixel of it and from no
