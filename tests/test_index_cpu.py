@@ -100,13 +100,17 @@ def test_roundtrip_golden_streams(api):
 # ---- the format, from its description: a plain decoder that snapshots at every granule --------------------------------------
 
 class _Bits:
+    """reads of at most 57 bits: the 8 bytes at the bit position hold them, so a read costs the same anywhere in the stream"""
+
     def __init__(self, data):
-        self.v, self.total, self.pos = int.from_bytes(data, "big"), 8 * len(data), 0
+        self.data, self.total, self.pos = bytes(data) + bytes(8), 8 * len(data), 0
 
     def get(self, n):
         assert self.pos + n <= self.total
+        at, skip = self.pos >> 3, self.pos & 7
+        assert skip + n <= 64
         self.pos += n
-        return (self.v >> (self.total - self.pos)) & ((1 << n) - 1)
+        return (int.from_bytes(self.data[at:at + 8], "big") >> (64 - skip - n)) & ((1 << n) - 1)
 
 
 def _model_checkpoints(stream):
@@ -208,6 +212,47 @@ def test_index_bytes_equal_the_model(api, cases):
             assert len(got) == len(want) and got == want, (w, h, rgb, seg, next(i for i in range(min(len(got), len(want))) if got[i] != want[i]))
             checked += 1
     assert checked == 2 * 2 * sum(1 for w, h in ic.SHAPES if w * h <= 3 * ic.GRANULE)
+
+
+MODEL_FRAMES = [(4096, 132, 0, (0, 1, 130, 131)), (1000, 541, 0, (0, 65, 131)), (1000, 271, 1, (0, 1, 66))]
+MODEL_SEGMENTS = (4096, 4096 * 9, 65536)
+
+
+@pytest.mark.parametrize("w,h,rgb,loud", MODEL_FRAMES, ids=lambda v: str(v).replace(" ", ""))
+def test_index_bytes_equal_the_model_past_64_checkpoints(api, oracle, w, h, rgb, loud):
+    """felics_index_build's bytes against the model on banded frames of more than 64 checkpoints and of 9 and 16 tiles per segment
+    (K = 132, 133 and 67 at 4096): the builder is what the encoder's index is held against at these sizes (test_index_large_gpu.py).
+    The model decodes each frame once."""
+    stream = oracle.compress(ic.banded(w, h, rgb, loud))
+    model = _model_checkpoints(stream)
+    for seg in MODEL_SEGMENTS:
+        got, want = api.index_build(stream, seg), _model_index(model, seg)
+        assert ic.Layout(got).k == (w * h + seg - 1) // seg
+        d = ic.first_difference(got, want)
+        assert len(got) == len(want) and d is None, (w, h, rgb, seg, d, ic.where_in_index(want, d))
+
+
+def test_banded_frames_silence_contexts(api, oracle):
+    """The content of test_index_large_gpu.py does what it is there for, measured on felics_index_build's rows alone: between two
+    loud intervals at least MEASURE_MIN contexts hold one non-zero row over the whole gap (the state of their first later record),
+    and as many go from a non-zero row to zeros behind the last loud interval.  A frame on which these were 0 would let an index
+    writer pass that never carries a find across its chunks of 64 intervals.  Prints the counts."""
+    seen = 0
+    for w, h, seg_tiles, plans in ic.LARGE:
+        for rgb in (0, 1):
+            for plan in plans:
+                stream = oracle.compress(ic.banded(w, h, rgb, plan))
+                for st in seg_tiles:
+                    rows = ic.state_rows(api.index_build(stream, st * ic.GRANULE))
+                    assert not rows[:, 0].any()  # segment 0 starts on a zeroed table
+                    todo = ic.measures(w, h, st, plan)
+                    for what, least in todo:
+                        got = ic.measure(rows, what)
+                        print("%d x %d %s seg_tiles %d loud %s: %s = %d" % (w, h, "RGB" if rgb else "gray", st, plan, what, got))
+                        assert got >= least, (w, h, rgb, st, plan, what, got)
+                        seen += 1
+                    assert todo or tuple(plan) == (0, 8)  # (everything loud in interval 0: only beside the other plan of its shape)
+    assert seen == 2 * 20
 
 
 # ---- refusals ----------------------------------------------------------------------------------------------------------------

@@ -23,33 +23,7 @@ def enc():
     e.close()
 
 
-def _decode_indexed(enc, streams, indexes, frame_bytes, guard=0, expect=None):
-    """streams + their indexes -> (status, frames as uint8 rows, the guard bytes intact).  expect: the code the call must raise."""
-    import torch
-
-    import felics_amd
-
-    n = len(streams)
-    blob, offs, lens = ic.pack_streams(streams)
-    stride = max((max(len(i) for i in indexes) + 15) // 16 * 16, 64)
-    iblob = b"".join(i + bytes(stride - len(i)) for i in indexes)
-    d_in = torch.from_numpy(np.frombuffer(blob, dtype=np.uint8).copy()).cuda()
-    d_idx = torch.from_numpy(np.frombuffer(iblob, dtype=np.uint8).copy()).cuda()
-    total = frame_bytes * n
-    d_px = torch.full((guard + max(total, 16) + guard,), 0xA5, dtype=torch.uint8, device="cuda")
-    torch.cuda.synchronize()
-    args = (d_in.data_ptr(), offs, lens, d_idx.data_ptr(), stride, d_px.data_ptr() + guard, total)
-    if expect is None:
-        _, status = enc.decompress_batch_device_indexed(*args)
-    else:
-        with pytest.raises(felics_amd.FelicsError) as ei:
-            enc.decompress_batch_device_indexed(*args)
-        assert ei.value.code == expect
-        status = ei.value.status
-    host = d_px.cpu().numpy()
-    if guard:
-        assert (host[:guard] == 0xA5).all() and (host[guard + max(total, 16):] == 0xA5).all()
-    return status, [host[guard + i * frame_bytes:guard + (i + 1) * frame_bytes] for i in range(n)]
+_decode_indexed = ic.decode_indexed  # (shared with test_index_large_gpu.py)
 
 
 @pytest.mark.parametrize("rgb", (0, 1))
@@ -167,29 +141,7 @@ def test_unsupported(enc, oracle):
 
 # ---- the encoder's index -------------------------------------------------------------------------------------------------------
 
-def _encode_indexed(e, imgs, seg, d_out_cap=None):
-    """frames of one shape -> (streams, indexes) as bytes, through felics_compress_batch_device_indexed; guard bytes around both"""
-    import torch
-
-    from felics_amd import api
-
-    n = len(imgs)
-    h, w = imgs[0].shape[:2]
-    rgb = int(imgs[0].ndim == 3)
-    isize = api.index_size(w, h, rgb, 0, seg)
-    d_in = torch.from_numpy(np.stack(imgs)).cuda()
-    cap = d_out_cap if d_out_cap is not None else n * ((imgs[0].size * 5 // 4 + 64 + 15) // 16 * 16)
-    guard = 256
-    d_out = torch.full((guard + cap + guard,), 0x5A, dtype=torch.uint8, device="cuda")
-    d_idx = torch.full((guard + n * isize + guard,), 0x5A, dtype=torch.uint8, device="cuda")
-    torch.cuda.synchronize()
-    offs, lens = e.compress_batch_device_indexed(d_in.data_ptr(), n, w, h, rgb, 0, d_out.data_ptr() + guard, cap, seg,
-                                                 d_idx.data_ptr() + guard, n * isize)
-    out, idx = d_out.cpu().numpy(), d_idx.cpu().numpy()
-    for buf, size in ((out, cap), (idx, n * isize)):
-        assert (buf[:guard] == 0x5A).all() and (buf[guard + size:] == 0x5A).all()
-    streams = [out[guard + int(o):guard + int(o) + int(ln)].tobytes() for o, ln in zip(offs, lens)]
-    return streams, [idx[guard + i * isize:guard + (i + 1) * isize].tobytes() for i in range(n)]
+_encode_indexed = ic.encode_indexed  # (shared with test_index_large_gpu.py)
 
 
 def _first_difference(a, b):

@@ -221,7 +221,10 @@ def test_refusals_before_launch(enc, oracle):
 
 def test_cfelics_index(tmp_path, oracle):
     """cfelics --index writes felics_index_build's bytes of the stream it wrote (64 x 65 gray8, --segment 4096; 65536 by default)
-    and refuses a 16-bit input with the library's message."""
+    and refuses a 16-bit input with the library's message; at its default on a 1024 x 1024 gray original of tests/golden/suite/ (K = 16,
+    16 tiles per interval) the stream is the committed one and the index felics_index_build's."""
+    import glob
+
     from PIL import Image
 
     from felics_amd import api
@@ -246,3 +249,18 @@ def test_cfelics_index(tmp_path, oracle):
     assert not out16.exists() and not idx16.exists()
     r = subprocess.run([cfelics, "-i", src, "-o", str(out), "--segment", "4096"], capture_output=True, text=True)
     assert r.returncode == 2  # a usage error: no index named
+    # the first 1024 x 1024 gray original of the suite, chosen the way test_index_gpu.py::test_suite_originals_at_65536 does
+    for path in sorted(glob.glob(os.path.join(GOLDEN, "suite", "*.felics"))):
+        real = np.array(Image.open(path[:-len(".felics")]))
+        if real.dtype == np.uint8 and real.shape == (1024, 1024):
+            break
+    else:
+        pytest.fail("no 1024 x 1024 gray original in tests/golden/suite")
+    big, bigidx = tmp_path / "big.felics", tmp_path / "big.idx"
+    r = subprocess.run([cfelics, "-i", path[:-len(".felics")], "-o", str(big), "--index", str(bigidx)], capture_output=True, text=True)
+    assert r.returncode == 0, r.stdout + r.stderr
+    assert big.read_bytes() == open(path, "rb").read(), path
+    got, ref = bigidx.read_bytes(), api.index_build(big.read_bytes(), 65536)
+    assert ic.Layout(ref).k == 16 and ic.Layout(ref).seg == 65536
+    d = ic.first_difference(got, ref)
+    assert len(got) == len(ref) and d is None, (path, d, ic.where_in_index(ref, d))

@@ -149,6 +149,8 @@ MAX_LANES = 4                     # felics_host.h: submissions in flight, each w
 NEED_TINY = MAX_LANES * max(lane_need_8(images_per_pass(64, 1), 1, 64), lane_need_8(images_per_pass(64, 3), 3, 64)) + SLACK
 # (a mixed job's geometry: one tile of SORT_TILE pixels a plane)
 NEED_TINY_MIXED = MAX_LANES * max(lane_need_8(MIX_MAX_IMAGES, 1, SORT_TILE), lane_need_8(images_per_pass(SORT_TILE, 3), 3, SORT_TILE)) + SLACK
+W_IDX2, H_IDX2, SEG_IDX2 = 64, 65, 4096                # two checkpoints a frame
+N_IDX2 = images_per_pass(W_IDX2 * H_IDX2, 1) + 3      # 32 771 gray8 frames: two real passes, each with its indexes
 MIXED_JOBS = sum(cdiv(N_TINY_MIXED // 2, min(MIX_MAX_IMAGES, images_per_pass(SORT_TILE, planes))) for planes in (1, 3))  # 3 + 4
 
 
@@ -168,6 +170,7 @@ def test_size_arithmetic():
     assert boundary_frames(N_ODD, NPIX_ODD, NPIX_ODD) == [0, 1035, 1036, 1204]
     assert images_per_pass(64, 1) == 1 << 15 and images_per_pass(64, 3) == 5461
     assert (TINY_PASSES_GRAY, TINY_PASSES_RGB, MIXED_JOBS) == (7, 13, 7)
+    assert N_IDX2 == (1 << 15) + 3 and cdiv(N_IDX2, images_per_pass(W_IDX2 * H_IDX2, 1)) == 2 and cdiv(W_IDX2 * H_IDX2, SEG_IDX2) == 2
     assert TINY_PASSES_GRAY == cdiv(N_TINY_GRAY, images_per_pass(64, 1)) and TINY_PASSES_RGB == cdiv(N_TINY_RGB, images_per_pass(64, 3))
     for n, per in ((N_DEC_WAVES, NPIX_4K), (N_DEC_LANES, WH_DEC_LANES ** 2), (N_DEC_RGB, 3 * WH_DEC_LANES ** 2), (N_DEC16, 2 * NPIX_4K)):
         assert n * per > 1 << 32
@@ -714,6 +717,47 @@ def test_forty_thousand_tiny_mixed_images(oracle):
         assert (host[o:o + b.nbytes].reshape(b.shape) == b).all(), i
         used[o:o + b.nbytes] = True
     assert (host[~used] == FILL).all()
+
+
+@pytest.mark.gpu
+def test_two_real_passes_with_an_index(oracle):
+    """32 771 gray8 frames of 64 x 65 (2^23 chains are 32 768 of them; K = 2 at 4096 pixels per segment), seven contents in turn, in
+    ONE felics_compress_batch_device_indexed call with no test switch: two submissions, the second pass's indexes behind the first's.
+    Every stream equals the oracle's stream of its content, every index felics_index_build's of it, 0x5A guards around both intact.
+    Holds about 0.6 GB on the device."""
+    import torch
+    from felics_amd import api
+    from tests import index_common as ic
+
+    n, w, h, seg, guard = N_IDX2, W_IDX2, H_IDX2, SEG_IDX2, 256
+    base = ic.images(w, h, 0, 4) + [ic.banded(w, h, 0, loud) for loud in ((0,), (1,), ())]
+    assert len(base) == K and len({b.tobytes() for b in base}) == K
+    streams = [oracle.compress(b) for b in base]
+    want = [(np.frombuffer(s, np.uint8), np.frombuffer(api.index_build(s, seg), np.uint8)) for s in streams]
+    isize = api.index_size(w, h, 0, 0, seg)
+    assert all(len(x) == isize for _, x in want)
+    frames = torch.from_numpy(np.stack(base)).cuda()[torch.arange(n, device="cuda") % K].contiguous()
+    cap = n * ((w * h * 5 // 4 + 64 + 15) // 16 * 16)
+    d_out = torch.full((guard + cap + guard,), 0x5A, dtype=torch.uint8, device="cuda")
+    d_idx = torch.full((guard + n * isize + guard,), 0x5A, dtype=torch.uint8, device="cuda")
+    torch.cuda.synchronize()
+    with _fresh_encoder() as e:
+        before = e.stats()
+        offs, lens = e.compress_batch_device_indexed(frames.data_ptr(), n, w, h, 0, 0, d_out.data_ptr() + guard, cap, seg,
+                                                     d_idx.data_ptr() + guard, n * isize)
+        assert _delta(e, before) == _clean(2)
+    out, idx = d_out.cpu().numpy(), d_idx.cpu().numpy()
+    for buf, size in ((out, cap), (idx, n * isize)):
+        assert (buf[:guard] == 0x5A).all() and (buf[guard + size:] == 0x5A).all()
+    idx = idx[guard:guard + n * isize].reshape(n, isize)
+    for i in range(n):
+        s, x = want[i % K]
+        got = out[guard + int(offs[i]):guard + int(offs[i]) + int(lens[i])]
+        assert len(got) == len(s) and (got == s).all(), "stream %d of %d (content %d)" % (i, n, i % K)
+        if not (idx[i] == x).all():
+            d = int(np.flatnonzero(idx[i] != x)[0])
+            pytest.fail("index %d of %d (content %d) differs at byte %d: %s" % (i, n, i % K, d, ic.where_in_index(x.tobytes(), d)))
+    del frames, d_out, d_idx
 
 
 # ---- 4. the stage-by-stage check of the tile-local pipeline ----------------------------------------------------------------------
