@@ -684,6 +684,38 @@ int decode16_passes(felics_ctx *ctx, size_t n, size_t per, const void *d_streams
     return first_rc;
 }
 
+// ---- what the two indexed calls (felics_decompress_batch_device_indexed, felics_decompress_regions_device_indexed) open with ----
+// Both halves answer FELICS_OK or the call's return value; a code of their own is in status[0 .. n) already (a HIP failure, as
+// everywhere, leaves status alone).  Between the two halves each call makes the checks that are its own.
+
+// The shape every stream must have: header of stream 0, which must be 8-bit with w * h < 2^32.
+int indexed_stream_shape(felics_ctx *ctx, const void *d_streams, const uint64_t *offsets, const uint64_t *lens, felics_header &hdr,
+                         felics_header *hdr_out, size_t n, int *status) {
+    uint8_t h0[FELICS_HEADER_BYTES] = {0};
+    const size_t hl = (size_t)std::min<uint64_t>(lens[0], FELICS_HEADER_BYTES);
+    if (hl) HIP_TRY(ctx, hipMemcpy(h0, (const uint8_t *)d_streams + offsets[0], hl, hipMemcpyDeviceToHost));
+    const int rc = felics_read_header(h0, hl, &hdr);
+    if (rc) return fail_call(n, status, nullptr, nullptr, rc);
+    if (hdr_out) *hdr_out = hdr;
+    if (hdr.pixel_depth != FELICS_DEPTH_8) return fail_call(n, status, nullptr, nullptr, FELICS_E_UNSUPPORTED);  // 16-bit streams have no index
+    if ((uint64_t)hdr.width * hdr.height > 0xFFFFFFFFull) return fail_call(n, status, nullptr, nullptr, FELICS_E_INVALID_DIMENSIONS);
+    return FELICS_OK;
+}
+
+// Whether the wave kernels can hold a row of that shape, then how every index is cut: header of index 0 (L, seg), which must fit
+// stream 0 and the stride.
+int indexed_index_shape(felics_ctx *ctx, const felics_header &hdr, uint64_t len0, const void *d_index, size_t index_stride, IndexLayout &L,
+                        uint32_t &seg, size_t n, int *status) {
+    if (decode8_lds_bytes(hdr.width, hdr.color_type) > DECODE_LDS_LIMIT) return fail_call(n, status, nullptr, nullptr, FELICS_E_UNSUPPORTED);  // no host fallback here
+    if (index_stride < INDEX_HEADER_BYTES) return fail_call(n, status, nullptr, nullptr, FELICS_E_INVALID_INDEX);
+    uint8_t ih[INDEX_HEADER_BYTES];
+    HIP_TRY(ctx, hipMemcpy(ih, d_index, INDEX_HEADER_BYTES, hipMemcpyDeviceToHost));
+    if (index_header_check(ih, hdr.color_type, hdr.width, hdr.height, len0, L) != FELICS_OK || L.total > index_stride)
+        return fail_call(n, status, nullptr, nullptr, FELICS_E_INVALID_INDEX);
+    seg = idx_rd32(ih + IDX_SEGPIX);
+    return FELICS_OK;
+}
+
 }  // namespace
 
 }  // namespace felics
@@ -871,28 +903,17 @@ int felics_decompress_batch_device_indexed(felics_ctx *ctx, size_t n, const void
         for (size_t i = 0; i < n; i++) status[i] = code;
         return code;
     };
-    // the shape every stream must have: header of stream 0; how every index is cut: header of index 0
-    uint8_t h0[FELICS_HEADER_BYTES] = {0}, ih[INDEX_HEADER_BYTES];
-    const size_t hl = (size_t)std::min<uint64_t>(lens[0], FELICS_HEADER_BYTES);
-    if (hl) HIP_TRY(ctx, hipMemcpy(h0, (const uint8_t *)d_streams + offsets[0], hl, hipMemcpyDeviceToHost));
     felics_header hdr;
-    int rc = felics_read_header(h0, hl, &hdr);
-    if (rc) return fail_all(rc);
-    if (hdr_out) *hdr_out = hdr;
-    if (hdr.pixel_depth != FELICS_DEPTH_8) return fail_all(FELICS_E_UNSUPPORTED);  // 16-bit streams have no index
+    int rc = indexed_stream_shape(ctx, d_streams, offsets, lens, hdr, hdr_out, n, status);
+    if (rc) return rc;
     const uint32_t planes = hdr.color_type == FELICS_COLOR_RGB ? 3 : 1;
     const uint64_t npix = (uint64_t)hdr.width * hdr.height;
-    if (npix > 0xFFFFFFFFull) return fail_all(FELICS_E_INVALID_DIMENSIONS);
     const uint64_t frame_bytes = npix * planes;
     if (frame_bytes * n > d_pixels_cap) return fail_all(FELICS_E_BUFFER_TOO_SMALL);
     if (frame_bytes && !d_pixels) return fail_all(FELICS_E_INVALID_ARGUMENT);
-    if (decode8_lds_bytes(hdr.width, hdr.color_type) > DECODE_LDS_LIMIT) return fail_all(FELICS_E_UNSUPPORTED);  // no host fallback here
-    if (index_stride < INDEX_HEADER_BYTES) return fail_all(FELICS_E_INVALID_INDEX);
-    HIP_TRY(ctx, hipMemcpy(ih, d_index, INDEX_HEADER_BYTES, hipMemcpyDeviceToHost));
     IndexLayout L;
-    if (index_header_check(ih, hdr.color_type, hdr.width, hdr.height, lens[0], L) != FELICS_OK || L.total > index_stride)
-        return fail_all(FELICS_E_INVALID_INDEX);
-    const uint32_t seg = idx_rd32(ih + IDX_SEGPIX);
+    uint32_t seg;
+    if ((rc = indexed_index_shape(ctx, hdr, lens[0], d_index, index_stride, L, seg, n, status)) != 0) return rc;
     const uint64_t per = (uint64_t)planes * std::max(L.K, 1u);
     if (n > 0x7FFFFFFFull / per) return fail_all(FELICS_E_UNSUPPORTED);  // one block per segment
     // offsets | lens | status on the device; a word per segment beside them
@@ -986,18 +1007,11 @@ int felics_decompress_regions_device_indexed(felics_ctx *ctx, size_t n_streams, 
     if (n_streams == 0 || n_streams > 0xFFFFFFFFull || n_regions > 0x7FFFFFFFull) return fail_all(FELICS_E_INVALID_ARGUMENT);
     if (((uintptr_t)d_index | index_stride) & 15u) return fail_all(FELICS_E_INVALID_ARGUMENT);  // the kernel loads a checkpoint as aligned words
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    // the shape every stream must have: header of stream 0; how every index is cut: header of index 0
-    uint8_t h0[FELICS_HEADER_BYTES] = {0}, ih[INDEX_HEADER_BYTES];
-    const size_t hl = (size_t)std::min<uint64_t>(lens[0], FELICS_HEADER_BYTES);
-    if (hl) HIP_TRY(ctx, hipMemcpy(h0, (const uint8_t *)d_streams + offsets[0], hl, hipMemcpyDeviceToHost));
     felics_header hdr;
-    int rc = felics_read_header(h0, hl, &hdr);
-    if (rc) return fail_all(rc);
-    if (hdr_out) *hdr_out = hdr;
-    if (hdr.pixel_depth != FELICS_DEPTH_8) return fail_all(FELICS_E_UNSUPPORTED);  // 16-bit streams have no index
+    int rc = indexed_stream_shape(ctx, d_streams, offsets, lens, hdr, hdr_out, n_regions, status);
+    if (rc) return rc;
     const uint32_t W = hdr.width, H = hdr.height, planes = hdr.color_type == FELICS_COLOR_RGB ? 3 : 1;
     const uint64_t npix = (uint64_t)W * H;
-    if (npix > 0xFFFFFFFFull) return fail_all(FELICS_E_INVALID_DIMENSIONS);
     // the requests: inside the image, of a stream of the call; the crops back to back
     for (size_t r = 0; r < n_regions; r++)
         if (regions[r].stream >= n_streams || !region_inside(W, H, regions[r])) return fail_all(FELICS_E_INVALID_ARGUMENT);
@@ -1007,12 +1021,9 @@ int felics_decompress_regions_device_indexed(felics_ctx *ctx, size_t n_streams, 
         if (total > d_pixels_cap) return fail_all(FELICS_E_BUFFER_TOO_SMALL);
     }
     if (total && !d_pixels) return fail_all(FELICS_E_INVALID_ARGUMENT);
-    if (decode8_lds_bytes(W, hdr.color_type) > DECODE_LDS_LIMIT) return fail_all(FELICS_E_UNSUPPORTED);  // no host fallback here
-    if (index_stride < INDEX_HEADER_BYTES) return fail_all(FELICS_E_INVALID_INDEX);
-    HIP_TRY(ctx, hipMemcpy(ih, d_index, INDEX_HEADER_BYTES, hipMemcpyDeviceToHost));
     IndexLayout L;
-    if (index_header_check(ih, hdr.color_type, W, H, lens[0], L) != FELICS_OK || L.total > index_stride) return fail_all(FELICS_E_INVALID_INDEX);
-    const uint32_t seg = idx_rd32(ih + IDX_SEGPIX);
+    uint32_t seg;
+    if ((rc = indexed_index_shape(ctx, hdr, lens[0], d_index, index_stride, L, seg, n_regions, status)) != 0) return rc;
     // the plan: a region's items are contiguous, in (plane, segment) order; an empty region has the header-only item
     std::vector<RegionRow> rows;
     std::vector<RegionItem> items;

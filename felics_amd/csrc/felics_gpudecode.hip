@@ -371,61 +371,64 @@ __global__ __launch_bounds__(64) void k_decode8(const uint8_t *__restrict__ stre
 }
 
 // ------------------------------------------------------------------------------------------
-// One wave per SEGMENT of a plane of a stream (felics_decompress_batch_device_indexed; the restart index: felics.h, felics_index.h).
+// The restart index (felics.h, felics_index.h): ONE walk from a checkpoint, and the two kernels that are its sinks.
 //
-// k_decode8's walk, started in the middle of a plane from a checkpoint: the LDS table comes out of the checkpoint's counters, the two
-// LDS rows out of its window of 2 W samples, (x, y) from the segment's first pixel p0, the bit reader is positioned on its
-// bit_offset.  Block b is segment (img, c, j) = (b / (C Keff), b / Keff % C, b % Keff), Keff = max(K, 1): an empty image has no
-// checkpoint, and its pseudo segment reads the plane's two raw samples only.  Every check of felics.h is made here: the stream's
-// header, the index header against it and against the launch's (segment_pixels, K: what the host sized the index by, so that no
-// checkpoint is read outside index_stride), the segment's bit range, the window's samples, and at the end that the reader stands
-// exactly on the next checkpoint.  seg_status[b] = FELICS_OK or the code; k_seg_status picks a stream's first.
-// The per-pixel path is k_decode8's, statement for statement (that kernel is left as it is: the unindexed call is what this one is
-// measured against); what differs is where the walk starts, where it ends, and that a 64-sample block is stored from the segment's
-// first pixel on and up to its last one only -- the samples before and behind belong to other waves.
-// LDS (dynamic): as k_decode8 (decode8_lds_bytes).
+// decode8_from_checkpoint is k_decode8's walk, started in the middle of a plane: the LDS table comes out of the checkpoint's
+// counters, the two LDS rows out of its window of 2 W samples, (x, y) from the segment's first pixel p0, the bit reader is positioned
+// on its bit_offset.  Every check of felics.h is made here, in this order: the stream's header, the index header against it and
+// against the launch's (segment_pixels, K: what the host sized the index by, so that no checkpoint is read outside index_stride), the
+// segment's bit range, the window's samples, and at the end that the reader stands exactly on the next checkpoint.  The per-pixel
+// path is k_decode8's (that kernel is left as it is: the unindexed call is what the indexed one is measured against).  A 64-sample
+// block goes to the LDS row for every lane, because later rows read it, and to the sink from the segment's first pixel on -- the
+// samples in front of p0 belong to other waves.  An empty image (K = 0) has no checkpoint: its pseudo segment reads the plane's two
+// raw samples only.  LDS (dynamic): as k_decode8 (decode8_lds_bytes).
+//
+// What a caller of the walk decides is its Sink:
+//   stop(pend)              the pixel behind the last one to decode, <= pend (the segment's end).  The end check is made only where
+//                           stop is the segment's end: a walk that stops early has no checkpoint to stand on, only that the reader did
+//                           not run off the stream;
+//   store(col, y, at, v)    sample v of pixel at = y W + col, p0 <= at < stop, to the output.
 // ------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(64) void k_decode8_seg(const uint8_t *__restrict__ streams, const uint64_t *__restrict__ offsets,
-                                                    const uint64_t *__restrict__ lens, const uint8_t *__restrict__ index, uint64_t index_stride,
-                                                    DecUniform geo, uint32_t segment_pixels, uint32_t K, uint8_t *__restrict__ pixels,
-                                                    int16_t *__restrict__ planes, int *__restrict__ seg_status) {
-    extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
+namespace {
+
+// The checks of a segment before a bit is decoded, for one (stream, index) pair: the stream's header (format.rs:63-84) must be the one
+// the caller announced, the index header must fit both and the launch's (segment_pixels, K); then, if `bounds`, the bit range of
+// segment (c, j).  FELICS_OK (L, and start / end if asked for, are set) or the code.  Plain per-thread code: the lane kernel
+// evaluates it with a stream per lane, the wave kernels make the result uniform themselves.
+__device__ __forceinline__ int indexed_segment_check(const uint8_t *s, uint64_t slen, const uint8_t *idx, uint32_t color, uint32_t W, uint32_t H,
+                                                     uint32_t segment_pixels, uint32_t K, bool bounds, uint32_t c, uint32_t j, IndexLayout &L,
+                                                     uint64_t &start, uint64_t &end) {
+    if (slen < FELICS_HEADER_BYTES) return FELICS_E_IO;
+    const uint32_t w = ((uint32_t)s[6] << 24) | ((uint32_t)s[7] << 16) | ((uint32_t)s[8] << 8) | s[9];
+    const uint32_t h = ((uint32_t)s[10] << 24) | ((uint32_t)s[11] << 16) | ((uint32_t)s[12] << 8) | s[13];
+    if (s[0] != 'F' || s[1] != 'L' || s[2] != 'C' || s[3] != 'S') return FELICS_E_INVALID_SIGNATURE;
+    if (s[4] > 1) return FELICS_E_INVALID_COLOR_TYPE;
+    if (s[5] > 1) return FELICS_E_INVALID_PIXEL_DEPTH;
+    if (s[4] != color || s[5] != 0 || w != W || h != H) return FELICS_E_INVALID_DIMENSIONS;
+    if (index_header_check(idx, color, W, H, slen, L) != FELICS_OK || idx_rd32(idx + IDX_SEGPIX) != segment_pixels || L.K != K)
+        return FELICS_E_INVALID_INDEX;
+    return bounds ? index_segment_bounds(idx, L, c, j, slen, start, end) : FELICS_OK;
+}
+
+// Segment (c, j) of stream s / index idx, decoded by the calling wave into `sink`; `smem` is the kernel's dynamic LDS.  Returns the
+// segment's status, wave-uniform.  header_only: the checks of the two headers and nothing else (c and j are not looked at).
+template <typename Sink>
+__device__ __forceinline__ int decode8_from_checkpoint(uint8_t *smem, const uint8_t *s, uint64_t slen, const uint8_t *idx, const DecUniform &geo,
+                                                       uint32_t segment_pixels, uint32_t K, uint32_t c, uint32_t j, bool header_only,
+                                                       const Sink &sink) {
     const uint32_t W = geo.W, H = geo.H, color = geo.color;
-    const uint32_t nplanes = color ? 3u : 1u, keff = max(K, 1u);
-    const uint32_t img = blockIdx.x / (nplanes * keff), c = blockIdx.x / keff % nplanes, j = blockIdx.x % keff;
     uint32_t *table = reinterpret_cast<uint32_t *>(smem);
     const uint32_t nctx = color ? nctx_of<int16_t>() : nctx_of<uint8_t>();
     int16_t *rows = reinterpret_cast<int16_t *>(smem + nctx * 6 * 4);
     const uint32_t rstride = decode8_row_stride(W);
     const uint32_t lane = lane_id();
-    const uint8_t *s = streams + offsets[img];
-    const uint64_t slen = lens[img];
-    const uint8_t *idx = index + (uint64_t)img * index_stride;
     const uint64_t npix = (uint64_t)W * H;
-    // the stream's header (format.rs:63-84) must be the one the caller announced, the index header must fit both
-    int rc = FELICS_OK;
     IndexLayout L;
     uint64_t start = 0, end = 0;
-    if (slen < FELICS_HEADER_BYTES) {
-        rc = FELICS_E_IO;
-    } else {
-        const uint32_t w = ((uint32_t)s[6] << 24) | ((uint32_t)s[7] << 16) | ((uint32_t)s[8] << 8) | s[9];
-        const uint32_t h = ((uint32_t)s[10] << 24) | ((uint32_t)s[11] << 16) | ((uint32_t)s[12] << 8) | s[13];
-        if (s[0] != 'F' || s[1] != 'L' || s[2] != 'C' || s[3] != 'S') rc = FELICS_E_INVALID_SIGNATURE;
-        else if (s[4] > 1) rc = FELICS_E_INVALID_COLOR_TYPE;
-        else if (s[5] > 1) rc = FELICS_E_INVALID_PIXEL_DEPTH;
-        else if (s[4] != color || s[5] != 0 || w != W || h != H) rc = FELICS_E_INVALID_DIMENSIONS;
-        else if (index_header_check(idx, color, W, H, slen, L) != FELICS_OK || idx_rd32(idx + IDX_SEGPIX) != segment_pixels || L.K != K)
-            rc = FELICS_E_INVALID_INDEX;
-        else
-            rc = index_segment_bounds(idx, L, c, j, slen, start, end);
-    }
-    rc = unii(rc);
-    if (rc != FELICS_OK) {
-        if (lane == 0) seg_status[blockIdx.x] = rc;
-        return;
-    }
+    int rc = unii(indexed_segment_check(s, slen, idx, color, W, H, segment_pixels, K, !header_only, c, j, L, start, end));
+    if (rc != FELICS_OK || header_only) return rc;
     const uint64_t p0 = (uint64_t)j * segment_pixels, pend = min(npix, p0 + segment_pixels);  // this segment's pixels
+    const uint64_t stop = sink.stop(pend);
     uint32_t x = 0, y = 0;
     int16_t *cur = rows, *prev = rows + rstride;
     if (K) {
@@ -452,236 +455,7 @@ __global__ __launch_bounds__(64) void k_decode8_seg(const uint8_t *__restrict__ 
             else if (t >= (uint64_t)W - x) prev[t - ((uint64_t)W - x)] = (int16_t)v;
             else if (t == 0 && x == 0) cur[0] = (int16_t)v;
         }
-        if (__ballot(bad) != 0) {
-            if (lane == 0) seg_status[blockIdx.x] = FELICS_E_INVALID_INDEX;
-            return;
-        }
-    }
-    __builtin_amdgcn_wave_barrier();
-    ScalarBits br;
-    br.init_at(s, slen, start);
-    int32_t raw0 = 0, raw1 = 0;
-    if (j == 0) {  // the plane's two raw samples (compression.rs:166-167) stand in front of its first segment only
-        raw0 = (int32_t)br.get(32);
-        raw1 = (int32_t)br.get(32);
-        if (br.failed()) rc = FELICS_E_IO;
-    }
-    if (rc == FELICS_OK && pend > p0) {
-        int16_t *outp = color ? planes + ((uint64_t)img * nplanes + c) * npix : nullptr;
-        uint8_t *outg = color ? nullptr : pixels + (uint64_t)img * npix;
-        const int lo_ok = color ? -255 : 0, hi_ok = 255;  // what a sample of this plane can be (Y 0..255, Co / Cg -255..255)
-        const uint32_t xl0 = x & 63u;
-        int upv = 0;   // VECTOR: prev[xb + lane] for the 64-sample block xb the walk stands in
-        int rowv = 0;  // VECTOR: the samples of this block decoded so far
-        if (xl0) {     // a start inside a block: the block's samples in front of it are the window's
-            if (y > 0) upv = (int)prev[(x & ~63u) + lane];
-            rowv = (int)cur[(x & ~63u) + lane];
-        }
-        int left = x >= 1 ? unii((int)cur[x - 1]) : 0, left2 = x >= 2 ? unii((int)cur[x - 2]) : 0;
-        int first_col2 = 0;  // cur[0] as it was before this row: the sample two rows up (first-column rule)
-        for (uint64_t i = p0; i < pend; i++) {
-            const uint32_t xl = x & 63u;
-            if (xl == 0) {
-                if (y > 0) upv = (int)prev[x + lane];  // (rows are padded to whole blocks)
-                if (x == 0 && y > 0) first_col2 = y >= 2 ? unii((int)cur[0]) : (W > 1 ? __builtin_amdgcn_readlane(upv, 1) : 0);
-            }
-            int pv;
-            if (i < 2) {
-                pv = i == 0 ? raw0 : raw1;
-            } else {
-                const int above = __builtin_amdgcn_readlane(upv, (int)xl);
-                const bool row0 = y == 0, col0 = x == 0 && !row0;  // misc.rs:6-24 with selects
-                const int v1 = col0 ? above : left;
-                const int v2 = col0 ? first_col2 : (row0 ? left2 : above);
-                const int hi = max(v1, v2), lo = min(v1, v2);
-                const uint32_t ctx = (uint32_t)(hi - lo);  // <= 510 because every stored sample is in range
-                br.refill();  // >= 33 bits: an in-range code has at most 11, the two flags of the other kind 2
-                if (br.take(1)) {  // in range: phased-in code of p - L (phase_in_coding.rs:86-112)
-                    const uint32_t n = ctx + 1;
-                    const uint32_t m = 31u - (uint32_t)__builtin_clz(n);
-                    const uint32_t right_p = (2u << m) - n, left_p = n - (1u << m);
-                    uint32_t r = br.take(m);
-                    const uint32_t longer = r >= right_p ? 1u : 0u;  // the code has one more bit
-                    const uint32_t r2 = (r - right_p) * 2u + right_p + br.take(longer);
-                    r = longer ? r2 : r;
-                    uint32_t rot = r + left_p;  // rotate_left: (r + left_p) mod n, r < n
-                    rot = rot >= n ? rot - n : rot;
-                    pv = lo + (int)rot;
-                } else {
-                    const bool above_flag = br.take(1) != 0;
-                    const uint64_t *row = reinterpret_cast<const uint64_t *>(table + ctx * 6);  // 24-byte rows: 8-byte aligned
-                    const uint64_t r01 = row[0], r23 = row[1], r45 = row[2];                 // one LDS round trip for the row
-                    uint32_t S[6] = {uni((uint32_t)r01), uni((uint32_t)(r01 >> 32)), uni((uint32_t)r23),
-                                     uni((uint32_t)(r23 >> 32)), uni((uint32_t)r45), uni((uint32_t)(r45 >> 32))};
-                    // get_k: smallest counter, ties to the largest k (parameter_selection.rs:71-85)
-                    const uint32_t key = min(min(min((S[0] << 3) | 7u, (S[1] << 3) | 6u), min((S[2] << 3) | 5u, (S[3] << 3) | 4u)),
-                                             min((S[4] << 3) | 3u, (S[5] << 3) | 2u));
-                    const uint32_t k = 7u - (key & 7u);
-                    const uint64_t q = br.unary0();
-                    const uint64_t e64 = (q << k) + br.get(k);
-                    if (e64 > 1024u) {  // no sample of an 8-bit plane is that far from its neighbours
-                        rc = e64 > 0xFFFFFFFFull ? FELICS_E_VALUE_OVERFLOW : FELICS_E_INVALID_VALUE;
-                        break;
-                    }
-                    const uint32_t e = (uint32_t)e64;
-                    uint32_t mn = 0xFFFFFFFFu;
-#pragma unroll
-                    for (uint32_t kk = 0; kk < 6; kk++) {
-                        S[kk] += (e >> kk) + 1u + kk;
-                        mn = min(mn, S[kk]);
-                    }
-                    const uint32_t hsh = mn > 1024u ? 1u : 0u;
-                    uint64_t *wrow = reinterpret_cast<uint64_t *>(table + ctx * 6);  // (every lane: same address, same value)
-                    wrow[0] = (uint64_t)(S[0] >> hsh) | ((uint64_t)(S[1] >> hsh) << 32);
-                    wrow[1] = (uint64_t)(S[2] >> hsh) | ((uint64_t)(S[3] >> hsh) << 32);
-                    wrow[2] = (uint64_t)(S[4] >> hsh) | ((uint64_t)(S[5] >> hsh) << 32);
-                    pv = above_flag ? hi + (int)e + 1 : lo - (int)e - 1;
-                }
-            }
-            if (pv < lo_ok || pv > hi_ok) {  // try_into::<u8>() / the estimator's context bound would fail
-                rc = FELICS_E_INVALID_VALUE;
-                break;
-            }
-            rowv = lane == xl ? pv : rowv;
-            left2 = left;
-            left = pv;
-            const bool row_end = x + 1 == W;
-            if (xl == 63u || row_end || i + 1 == pend) {  // a block of the row is complete, or the segment is
-                const uint32_t xb = x & ~63u;
-                if (xb + lane <= x) {
-                    cur[xb + lane] = (int16_t)rowv;  // (lanes in front of a mid-block start store back what they loaded)
-                    const uint64_t at = (uint64_t)y * W + xb + lane;  // < pend: xb + lane <= x
-                    if (at >= p0) {  // the samples in front of p0 are the segment's before this one
-                        if (outg) outg[at] = (uint8_t)rowv;
-                        else outp[at] = (int16_t)rowv;
-                    }
-                }
-            }
-            if (row_end) {
-                if (br.failed()) {
-                    rc = FELICS_E_IO;
-                    break;
-                }
-                __builtin_amdgcn_wave_barrier();
-                x = 0;
-                y++;
-                int16_t *t = cur;
-                cur = prev;
-                prev = t;
-            } else {
-                x++;
-            }
-        }
-    }
-    if (br.failed()) rc = FELICS_E_IO;  // (whatever else stopped the decoding: it was decoding padding)
-    else if (rc == FELICS_OK && br.pos(s) != end) rc = FELICS_E_INVALID_INDEX;  // the end check: exactly on the next checkpoint
-    if (lane == 0) seg_status[blockIdx.x] = rc;
-}
-
-// status[i] = the code of stream i's first failing segment in (plane, segment) order; one wave per stream over its `per` words
-__global__ __launch_bounds__(64) void k_seg_status(const int *__restrict__ seg_status, uint32_t per, int *__restrict__ status) {
-    __shared__ uint32_t first;
-    if (threadIdx.x == 0) first = 0xFFFFFFFFu;
-    __syncthreads();
-    const int *mine = seg_status + (uint64_t)blockIdx.x * per;
-    for (uint32_t k = threadIdx.x; k < per; k += 64)
-        if (mine[k] != FELICS_OK) {
-            atomicMin(&first, k);
-            break;
-        }
-    __syncthreads();
-    if (threadIdx.x == 0) status[blockIdx.x] = first == 0xFFFFFFFFu ? FELICS_OK : mine[first];
-}
-
-// ------------------------------------------------------------------------------------------
-// One wave per WORK ITEM = (region, plane, needed segment) of felics_decompress_regions_device_indexed (felics.h "Restart index:
-// regions"; host model: felics_decompress_region_indexed).
-//
-// k_decode8_seg's header checks, checkpoint load, window check, seek and per-pixel path, statement for statement -- a kernel of its
-// own with its own copy of the walk, so that k_decode8_seg and what it is measured against stay as they are.  Three things differ:
-// the loop ends at stop = min(the segment's end, the pixel behind the region's last one); the end check is made only where stop is
-// the segment's end (a walk that stops early has no checkpoint to stand on: only that the reader did not run off the stream); and
-// the block store writes a lane's sample only if its (column, row) lies inside the region, to (row - y) * w + (column - x) of the
-// dense crop (u8 gray, or the crop-sized int16 planes) -- the LDS row is written for every lane, because later rows read it.
-// An item with seg = REGION_HEADER_ONLY ends after the header checks.  item_status[b] = FELICS_OK or the code; k_region_status picks
-// a region's first.  LDS (dynamic): as k_decode8 (decode8_lds_bytes).
-// ------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(64) void k_decode8_region(const uint8_t *__restrict__ streams, const uint64_t *__restrict__ offsets,
-                                                       const uint64_t *__restrict__ lens, const uint8_t *__restrict__ index, uint64_t index_stride,
-                                                       DecUniform geo, uint32_t segment_pixels, uint32_t K, const RegionRow *__restrict__ regions,
-                                                       const RegionItem *__restrict__ items, uint8_t *__restrict__ pixels,
-                                                       int16_t *__restrict__ planes, int *__restrict__ item_status) {
-    extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
-    const uint32_t W = geo.W, H = geo.H, color = geo.color;
-    const RegionItem item = items[blockIdx.x];
-    const RegionRow reg = regions[item.region];
-    const uint32_t img = reg.stream, c = item.plane, j = item.seg;
-    uint32_t *table = reinterpret_cast<uint32_t *>(smem);
-    const uint32_t nctx = color ? nctx_of<int16_t>() : nctx_of<uint8_t>();
-    int16_t *rows = reinterpret_cast<int16_t *>(smem + nctx * 6 * 4);
-    const uint32_t rstride = decode8_row_stride(W);
-    const uint32_t lane = lane_id();
-    const uint8_t *s = streams + offsets[img];
-    const uint64_t slen = lens[img];
-    const uint8_t *idx = index + (uint64_t)img * index_stride;
-    const uint64_t npix = (uint64_t)W * H;
-    // the stream's header (format.rs:63-84) must be the one the caller announced, the index header must fit both
-    int rc = FELICS_OK;
-    IndexLayout L;
-    uint64_t start = 0, end = 0;
-    if (slen < FELICS_HEADER_BYTES) {
-        rc = FELICS_E_IO;
-    } else {
-        const uint32_t w = ((uint32_t)s[6] << 24) | ((uint32_t)s[7] << 16) | ((uint32_t)s[8] << 8) | s[9];
-        const uint32_t h = ((uint32_t)s[10] << 24) | ((uint32_t)s[11] << 16) | ((uint32_t)s[12] << 8) | s[13];
-        if (s[0] != 'F' || s[1] != 'L' || s[2] != 'C' || s[3] != 'S') rc = FELICS_E_INVALID_SIGNATURE;
-        else if (s[4] > 1) rc = FELICS_E_INVALID_COLOR_TYPE;
-        else if (s[5] > 1) rc = FELICS_E_INVALID_PIXEL_DEPTH;
-        else if (s[4] != color || s[5] != 0 || w != W || h != H) rc = FELICS_E_INVALID_DIMENSIONS;
-        else if (index_header_check(idx, color, W, H, slen, L) != FELICS_OK || idx_rd32(idx + IDX_SEGPIX) != segment_pixels || L.K != K)
-            rc = FELICS_E_INVALID_INDEX;
-        else if (j != REGION_HEADER_ONLY)
-            rc = index_segment_bounds(idx, L, c, j, slen, start, end);
-    }
-    rc = unii(rc);
-    if (rc != FELICS_OK || j == REGION_HEADER_ONLY) {
-        if (lane == 0) item_status[blockIdx.x] = rc;
-        return;
-    }
-    // this segment's pixels, and where the walk ends: the host names needed segments only (j < K, p0 < stop), and a region inside the
-    // image (x + w <= W, y + h <= H, both sides non-zero)
-    const uint64_t p0 = (uint64_t)j * segment_pixels, pend = min(npix, p0 + segment_pixels);
-    const uint64_t stop = min(pend, (uint64_t)(reg.y + reg.h - 1) * W + reg.x + reg.w);
-    uint32_t x = 0, y = 0;
-    int16_t *cur = rows, *prev = rows + rstride;
-    {
-        // the checkpoint: counters (u16 pairs -> u32 rows), then the window into the two rows -- with (x0, y0) = p0's place, window
-        // sample t is pixel p0 - 2 W + t: row y0 from t = 2 W - x0 on (cur), row y0 - 1 from t = W - x0 on (prev), and in front of that
-        // row y0 - 2, of which only (0, y0 - 2) is ever looked at, and only if x0 = 0 (the first-column rule: what cur[0] holds)
-        const uint8_t *cp = idx + INDEX_HEADER_BYTES + ((uint64_t)c * K + j) * L.cp_bytes;
-        const uint32_t *st = reinterpret_cast<const uint32_t *>(cp + CP_STATE_OFF);  // (index and checkpoints are 16-byte aligned)
-        for (uint32_t i = lane; i < nctx * 3; i += 64) {
-            const uint32_t w2 = st[i];
-            table[2 * i] = w2 & 0xFFFFu;
-            table[2 * i + 1] = w2 >> 16;
-        }
-        x = (uint32_t)(p0 % W);
-        y = (uint32_t)(p0 / W);
-        const uint8_t *win = cp + L.win_off;
-        const int lo_w = color && c ? -255 : 0;
-        bool bad = false;
-        for (uint64_t t = lane; t < 2ull * W; t += 64) {
-            if (p0 + t < 2ull * W) continue;  // in front of the plane: zeros, never looked at
-            const int v = color ? (int)reinterpret_cast<const int16_t *>(win)[t] : (int)win[t];
-            bad |= v < lo_w || v > 255;
-            if (t >= 2ull * W - x) cur[t - (2ull * W - x)] = (int16_t)v;
-            else if (t >= (uint64_t)W - x) prev[t - ((uint64_t)W - x)] = (int16_t)v;
-            else if (t == 0 && x == 0) cur[0] = (int16_t)v;
-        }
-        if (__ballot(bad) != 0) {
-            if (lane == 0) item_status[blockIdx.x] = FELICS_E_INVALID_INDEX;
-            return;
-        }
+        if (__ballot(bad) != 0) return FELICS_E_INVALID_INDEX;
     }
     __builtin_amdgcn_wave_barrier();
     ScalarBits br;
@@ -693,9 +467,6 @@ __global__ __launch_bounds__(64) void k_decode8_region(const uint8_t *__restrict
         if (br.failed()) rc = FELICS_E_IO;
     }
     if (rc == FELICS_OK && stop > p0) {
-        const uint64_t cpix = (uint64_t)reg.w * reg.h;
-        int16_t *outp = color ? planes + reg.plane_off + (uint64_t)c * cpix : nullptr;
-        uint8_t *outg = color ? nullptr : pixels + reg.out_off;
         const int lo_ok = color ? -255 : 0, hi_ok = 255;  // what a sample of this plane can be (Y 0..255, Co / Cg -255..255)
         const uint32_t xl0 = x & 63u;
         int upv = 0;   // VECTOR: prev[xb + lane] for the 64-sample block xb the walk stands in
@@ -777,15 +548,8 @@ __global__ __launch_bounds__(64) void k_decode8_region(const uint8_t *__restrict
                 const uint32_t xb = x & ~63u;
                 if (xb + lane <= x) {
                     cur[xb + lane] = (int16_t)rowv;  // (lanes in front of a mid-block start store back what they loaded)
-                    const uint32_t col = xb + lane;
-                    const uint64_t at = (uint64_t)y * W + col;  // < stop: col <= x
-                    // the samples in front of p0 are the segment's before this one; the crop takes those inside the region only:
-                    // column in [x, x + w), row in [y, y + h) (row < y + h: at < stop) -- an offset below w * h
-                    if (at >= p0 && col >= reg.x && col - reg.x < reg.w && y >= reg.y && y - reg.y < reg.h) {
-                        const uint64_t to = (uint64_t)(y - reg.y) * reg.w + (col - reg.x);
-                        if (outg) outg[to] = (uint8_t)rowv;
-                        else outp[to] = (int16_t)rowv;
-                    }
+                    const uint64_t at = (uint64_t)y * W + xb + lane;  // < stop: xb + lane <= x
+                    if (at >= p0) sink.store(xb + lane, y, at, rowv);  // the samples in front of p0 are the segment's before this one
                 }
             }
             if (row_end) {
@@ -806,18 +570,87 @@ __global__ __launch_bounds__(64) void k_decode8_region(const uint8_t *__restrict
     }
     if (br.failed()) rc = FELICS_E_IO;  // (whatever else stopped the decoding: it was decoding padding)
     else if (rc == FELICS_OK && stop == pend && br.pos(s) != end) rc = FELICS_E_INVALID_INDEX;  // the end check: exactly on the next checkpoint
-    if (lane == 0) item_status[blockIdx.x] = rc;
+    return rc;
 }
 
-// status[r] = the code of region r's first failing item in (plane, segment) order; one wave per region over its items' words
-__global__ __launch_bounds__(64) void k_region_status(const int *__restrict__ item_status, const RegionRow *__restrict__ regions,
-                                                      int *__restrict__ status) {
+// The whole segment into the stream's frame (u8 gray) or plane c of its planes (int16): pixel `at` to out[at].  The walk hands it
+// p0 <= at < pend only, so a wave writes its own segment's samples and no other.
+struct SegmentSink {
+    uint8_t *outg;   // gray: the stream's frame; else null
+    int16_t *outp;   // RGB: plane c of the stream's planes
+    __device__ __forceinline__ uint64_t stop(uint64_t pend) const { return pend; }
+    __device__ __forceinline__ void store(uint32_t, uint32_t, uint64_t at, int v) const {
+        if (outg) outg[at] = (uint8_t)v;
+        else outp[at] = (int16_t)v;
+    }
+};
+
+// The segment's part of a region into the region's dense crop (u8 gray, or plane c of the crop-sized int16 planes): the walk ends
+// behind the region's last pixel, and a sample is written only if its (column, row) lies inside the region -- column in [x, x + w),
+// row in [y, y + h) (row < y + h holds for every at < stop) -- to (row - y) * w + (column - x), an offset below w * h.
+struct RegionSink {
+    RegionRow reg;  // (inside the image, both sides non-zero: the host's checks)
+    uint32_t W;
+    uint8_t *outg;
+    int16_t *outp;
+    __device__ __forceinline__ uint64_t stop(uint64_t pend) const { return min(pend, (uint64_t)(reg.y + reg.h - 1) * W + reg.x + reg.w); }
+    __device__ __forceinline__ void store(uint32_t col, uint32_t y, uint64_t, int v) const {
+        if (col >= reg.x && col - reg.x < reg.w && y >= reg.y && y - reg.y < reg.h) {
+            const uint64_t to = (uint64_t)(y - reg.y) * reg.w + (col - reg.x);
+            if (outg) outg[to] = (uint8_t)v;
+            else outp[to] = (int16_t)v;
+        }
+    }
+};
+
+}  // namespace
+
+// One wave per SEGMENT of a plane of a stream (felics_decompress_batch_device_indexed).  Block b is segment (img, c, j) =
+// (b / (C Keff), b / Keff % C, b % Keff), Keff = max(K, 1).  seg_status[b] = FELICS_OK or the code; k_seg_status picks a stream's first.
+__global__ __launch_bounds__(64) void k_decode8_seg(const uint8_t *__restrict__ streams, const uint64_t *__restrict__ offsets,
+                                                    const uint64_t *__restrict__ lens, const uint8_t *__restrict__ index, uint64_t index_stride,
+                                                    DecUniform geo, uint32_t segment_pixels, uint32_t K, uint8_t *__restrict__ pixels,
+                                                    int16_t *__restrict__ planes, int *__restrict__ seg_status) {
+    extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
+    const uint32_t nplanes = geo.color ? 3u : 1u, keff = max(K, 1u);
+    const uint32_t img = blockIdx.x / (nplanes * keff), c = blockIdx.x / keff % nplanes, j = blockIdx.x % keff;
+    const uint64_t npix = (uint64_t)geo.W * geo.H;
+    const SegmentSink sink{geo.color ? nullptr : pixels + (uint64_t)img * npix, geo.color ? planes + ((uint64_t)img * nplanes + c) * npix : nullptr};
+    const int rc = decode8_from_checkpoint(smem, streams + offsets[img], lens[img], index + (uint64_t)img * index_stride, geo, segment_pixels, K, c,
+                                           j, false, sink);
+    if (lane_id() == 0) seg_status[blockIdx.x] = rc;
+}
+
+// One wave per WORK ITEM = (region, plane, needed segment) of felics_decompress_regions_device_indexed (felics.h "Restart index:
+// regions"; host model: felics_decompress_region_indexed).  The host names needed segments only (j < K, p0 < stop); an item with
+// seg = REGION_HEADER_ONLY ends after the header checks.  item_status[b] = FELICS_OK or the code; k_seg_status picks a region's first.
+__global__ __launch_bounds__(64) void k_decode8_region(const uint8_t *__restrict__ streams, const uint64_t *__restrict__ offsets,
+                                                       const uint64_t *__restrict__ lens, const uint8_t *__restrict__ index, uint64_t index_stride,
+                                                       DecUniform geo, uint32_t segment_pixels, uint32_t K, const RegionRow *__restrict__ regions,
+                                                       const RegionItem *__restrict__ items, uint8_t *__restrict__ pixels,
+                                                       int16_t *__restrict__ planes, int *__restrict__ item_status) {
+    extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
+    const RegionItem item = items[blockIdx.x];
+    const RegionRow reg = regions[item.region];
+    const uint32_t img = reg.stream, c = item.plane;
+    const RegionSink sink{reg, geo.W, geo.color ? nullptr : pixels + reg.out_off,
+                          geo.color ? planes + reg.plane_off + (uint64_t)c * reg.w * reg.h : nullptr};
+    const int rc = decode8_from_checkpoint(smem, streams + offsets[img], lens[img], index + (uint64_t)img * index_stride, geo, segment_pixels, K, c,
+                                           item.seg, item.seg == REGION_HEADER_ONLY, sink);
+    if (lane_id() == 0) item_status[blockIdx.x] = rc;
+}
+
+// status[r] = the code of row r's first failing word in (plane, segment) order; one wave per row.  A row's words are
+// regions[r]'s items (item0, nitems), or, without a region table, the `per` segment words of stream r.
+__global__ __launch_bounds__(64) void k_seg_status(const int *__restrict__ words, const RegionRow *__restrict__ regions, uint32_t per,
+                                                   int *__restrict__ status) {
     __shared__ uint32_t first;
     if (threadIdx.x == 0) first = 0xFFFFFFFFu;
     __syncthreads();
-    const RegionRow reg = regions[blockIdx.x];
-    const int *mine = item_status + reg.item0;
-    for (uint32_t k = threadIdx.x; k < reg.nitems; k += 64)
+    const uint64_t word0 = regions ? regions[blockIdx.x].item0 : (uint64_t)blockIdx.x * per;
+    const uint32_t count = regions ? regions[blockIdx.x].nitems : per;
+    const int *mine = words + word0;
+    for (uint32_t k = threadIdx.x; k < count; k += 64)
         if (mine[k] != FELICS_OK) {
             atomicMin(&first, k);
             break;
@@ -1279,24 +1112,10 @@ __global__ __launch_bounds__(64) void k_decode8_seg_lanes(const uint8_t *__restr
     const uint64_t slen = lens[img];
     const uint8_t *idx = index + (uint64_t)img * index_stride;
     const uint64_t npix = (uint64_t)W * H;
-    // the stream's header (format.rs:63-84) must be the one the caller announced, the index header must fit both
-    int rc = FELICS_OK;
+    // the wave kernels' checks, a stream per lane
     uint64_t start = 0, end = 0;
-    if (slen < FELICS_HEADER_BYTES) {
-        rc = FELICS_E_IO;
-    } else {
-        IndexLayout L;
-        const uint32_t w = ((uint32_t)s[6] << 24) | ((uint32_t)s[7] << 16) | ((uint32_t)s[8] << 8) | s[9];
-        const uint32_t h = ((uint32_t)s[10] << 24) | ((uint32_t)s[11] << 16) | ((uint32_t)s[12] << 8) | s[13];
-        if (s[0] != 'F' || s[1] != 'L' || s[2] != 'C' || s[3] != 'S') rc = FELICS_E_INVALID_SIGNATURE;
-        else if (s[4] > 1) rc = FELICS_E_INVALID_COLOR_TYPE;
-        else if (s[5] > 1) rc = FELICS_E_INVALID_PIXEL_DEPTH;
-        else if (s[4] != (RGB ? 1 : 0) || s[5] != 0 || w != W || h != H) rc = FELICS_E_INVALID_DIMENSIONS;
-        else if (index_header_check(idx, RGB ? 1u : 0u, W, H, slen, L) != FELICS_OK || idx_rd32(idx + IDX_SEGPIX) != segment_pixels || L.K != K)
-            rc = FELICS_E_INVALID_INDEX;
-        else
-            rc = index_segment_bounds(idx, L, c, j, slen, start, end);
-    }
+    IndexLayout L;
+    int rc = indexed_segment_check(s, slen, idx, RGB ? 1u : 0u, W, H, segment_pixels, K, true, c, j, L, start, end);
     // (a lane that passed has the launch's layout: shape, colour and segment_pixels are what the layout is made of)
     const IndexLayout LL = index_layout(W, H, RGB ? 1u : 0u, segment_pixels);
     const uint64_t cp_off = INDEX_HEADER_BYTES + ((uint64_t)c * K + j) * LL.cp_bytes;
@@ -2283,26 +2102,28 @@ hipError_t launch_decode8(hipStream_t s, const uint8_t *streams, const uint64_t 
     return hipGetLastError();
 }
 
+namespace {
+
+// the dynamic LDS of an indexed wave kernel (k_decode8_seg, k_decode8_region), with the kernel's limit raised where it needs more than 64 KiB
+hipError_t indexed_lds(const void *kernel, uint32_t W, uint32_t color, uint32_t &lds) {
+    lds = decode8_lds_bytes(W, color);
+    if (lds <= 64u * 1024u) return hipSuccess;
+    return hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)DECODE_LDS_LIMIT);
+}
+
+}  // namespace
+
 hipError_t launch_decode8_seg(hipStream_t s, const uint8_t *streams, const uint64_t *offsets, const uint64_t *lens, const uint8_t *index,
                               uint64_t index_stride, uint32_t n, uint32_t W, uint32_t H, uint32_t color, uint32_t segment_pixels, uint32_t K,
                               uint8_t *pixels, int16_t *planes, int *seg_status, int *status) {
     if (n == 0) return hipSuccess;
-    const uint32_t lds = decode8_lds_bytes(W, color);
-    if (lds > 64u * 1024u) {
-        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&k_decode8_seg), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                                 (int)DECODE_LDS_LIMIT);
-        if (e != hipSuccess) return e;
-    }
+    uint32_t lds;
+    const hipError_t e = indexed_lds(reinterpret_cast<const void *>(&k_decode8_seg), W, color, lds);
+    if (e != hipSuccess) return e;
     const uint32_t per = (color ? 3u : 1u) * std::max(K, 1u);  // (n * per < 2^31: the caller's check)
     hipLaunchKernelGGL(k_decode8_seg, dim3(n * per), dim3(64), lds, s, streams, offsets, lens, index, index_stride, DecUniform{W, H, color},
                        segment_pixels, K, pixels, planes, seg_status);
-    hipLaunchKernelGGL(k_seg_status, dim3(n), dim3(64), 0, s, seg_status, per, status);
-    if (color) {
-        const uint64_t npix = (uint64_t)W * H;
-        const uint32_t bx = (uint32_t)std::min<uint64_t>((npix + 255) / 256, 1024u);
-        if (bx) hipLaunchKernelGGL(k_ycocg8_to_rgb<ConvUniform>, dim3(bx, n), dim3(256), 0, s, planes, pixels, ConvUniform{(uint32_t)npix}, status);
-    }
-    return hipGetLastError();
+    return launch_seg_finish(s, n, W, H, color, K, pixels, planes, seg_status, status);
 }
 
 size_t index8_lanes_table_bytes(uint64_t items, uint32_t color) { return (size_t)items * (color ? DEC8L_TABLE_DW_RGB : DEC8L_TABLE_DW) * 4; }
@@ -2323,7 +2144,7 @@ hipError_t launch_decode8_seg_lanes(hipStream_t s, const uint8_t *streams, const
 hipError_t launch_seg_finish(hipStream_t s, uint32_t n, uint32_t W, uint32_t H, uint32_t color, uint32_t K, uint8_t *pixels, int16_t *planes,
                              const int *seg_status, int *status) {
     if (n == 0) return hipSuccess;
-    hipLaunchKernelGGL(k_seg_status, dim3(n), dim3(64), 0, s, seg_status, (color ? 3u : 1u) * std::max(K, 1u), status);
+    hipLaunchKernelGGL(k_seg_status, dim3(n), dim3(64), 0, s, seg_status, (const RegionRow *)nullptr, (color ? 3u : 1u) * std::max(K, 1u), status);
     if (color) {
         const uint64_t npix = (uint64_t)W * H;
         const uint32_t bx = (uint32_t)std::min<uint64_t>((npix + 255) / 256, 1024u);
@@ -2337,15 +2158,12 @@ hipError_t launch_decode8_regions(hipStream_t s, const uint8_t *streams, const u
                                   const RegionRow *rows, uint32_t nregions, const RegionItem *items, uint32_t nitems, uint64_t max_crop,
                                   uint8_t *pixels, int16_t *planes, int *item_status, int *status) {
     if (nregions == 0 || nitems == 0) return hipSuccess;
-    const uint32_t lds = decode8_lds_bytes(W, color);
-    if (lds > 64u * 1024u) {
-        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&k_decode8_region), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                                 (int)DECODE_LDS_LIMIT);
-        if (e != hipSuccess) return e;
-    }
+    uint32_t lds;
+    const hipError_t e = indexed_lds(reinterpret_cast<const void *>(&k_decode8_region), W, color, lds);
+    if (e != hipSuccess) return e;
     hipLaunchKernelGGL(k_decode8_region, dim3(nitems), dim3(64), lds, s, streams, offsets, lens, index, index_stride, DecUniform{W, H, color},
                        segment_pixels, K, rows, items, pixels, planes, item_status);
-    hipLaunchKernelGGL(k_region_status, dim3(nregions), dim3(64), 0, s, item_status, rows, status);
+    hipLaunchKernelGGL(k_seg_status, dim3(nregions), dim3(64), 0, s, item_status, rows, 0u, status);
     // the crops differ in size: one launch (per 65 535 regions) sized by the largest, a region's blocks stride over its own w * h
     const uint32_t bx = (uint32_t)std::min<uint64_t>((max_crop + 255) / 256, 1024u);
     if (color && bx)

@@ -70,6 +70,23 @@ int store_rgb8(const std::vector<int32_t> (&ch)[3], unsigned planes, uint8_t *ds
     return FELICS_OK;
 }
 
+// Everything a segment starts from but its bit position comes out of checkpoint (c, j) (K >= 1): the counters into `est`, and the 2 W
+// samples in front of s0 = the segment's first pixel, range-checked, to the caller's samples (out[0] is pixel `base`, base <= s0 - 2 W
+// where that is a pixel of the plane).  Window positions in front of the plane are never looked at.  0, or FELICS_E_INVALID_INDEX.
+int load_checkpoint(const uint8_t *index, const IndexLayout &L, uint32_t color, uint32_t c, uint32_t j, uint32_t W, size_t s0, Estimator &est,
+                    int32_t *out, size_t base) {
+    const uint8_t *cp = index + INDEX_HEADER_BYTES + ((uint64_t)c * L.K + j) * L.cp_bytes;
+    const uint32_t stored = (color ? OPT8.max_context + 1 : 256u) * 6;  // (gray has contexts 0 .. 255)
+    for (uint32_t i = 0; i < (OPT8.max_context + 1) * 6; i++) est.row(0)[i] = i < stored ? idx_rd16(cp + CP_STATE_OFF + 2 * i) : 0u;
+    for (uint64_t s = 0; s < 2ull * W; s++) {
+        if (s0 + s < 2ull * W) continue;
+        const int32_t v = color ? (int32_t)(int16_t)idx_rd16(cp + L.win_off + 2 * s) : (int32_t)cp[L.win_off + s];
+        if (!in_plane_range(v, color, c)) return FELICS_E_INVALID_INDEX;
+        out[s0 + s - 2ull * W - base] = v;
+    }
+    return FELICS_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -182,17 +199,7 @@ int felics_decompress_indexed(const uint8_t *in, size_t len, const uint8_t *inde
                 // everything a segment starts from comes out of its checkpoint: bit position, table, the 2 W samples in front of it
                 BitReader br(in, len, start);
                 const size_t s0 = (size_t)j * seg, s1 = std::min(npix, s0 + seg);
-                if (L.K) {
-                    const uint8_t *cp = index + INDEX_HEADER_BYTES + ((uint64_t)c * L.K + j) * L.cp_bytes;
-                    const uint32_t stored = (color ? OPT8.max_context + 1 : 256u) * 6;  // (gray has contexts 0 .. 255)
-                    for (uint32_t i = 0; i < (OPT8.max_context + 1) * 6; i++) est.row(0)[i] = i < stored ? idx_rd16(cp + CP_STATE_OFF + 2 * i) : 0u;
-                    for (uint64_t s = 0; s < 2ull * W; s++) {
-                        if (s0 + s < 2ull * W) continue;
-                        const int32_t v = color ? (int32_t)(int16_t)idx_rd16(cp + L.win_off + 2 * s) : (int32_t)cp[L.win_off + s];
-                        if (!in_plane_range(v, color, c)) return FELICS_E_INVALID_INDEX;
-                        out[s0 + s - 2ull * W] = v;
-                    }
-                }
+                if (L.K && (rc = load_checkpoint(index, L, color, c, j, W, s0, est, out, 0)) != 0) return rc;
                 if (j == 0) {
                     const int32_t p0 = (int32_t)br.bits(32), p1 = (int32_t)br.bits(32);
                     if (br.failed()) return FELICS_E_IO;
@@ -269,15 +276,7 @@ int felics_decompress_region_indexed(const uint8_t *in, size_t len, const uint8_
                 const size_t y0 = s0 / W, base = y0 >= 2 ? (y0 - 2) * W : 0;
                 buf.assign(stop - base, 0);
                 int32_t *out = buf.data();
-                const uint8_t *cp = index + INDEX_HEADER_BYTES + ((uint64_t)c * L.K + j) * L.cp_bytes;
-                const uint32_t stored = (color ? OPT8.max_context + 1 : 256u) * 6;  // (gray has contexts 0 .. 255)
-                for (uint32_t i = 0; i < (OPT8.max_context + 1) * 6; i++) est.row(0)[i] = i < stored ? idx_rd16(cp + CP_STATE_OFF + 2 * i) : 0u;
-                for (uint64_t s = 0; s < 2ull * W; s++) {
-                    if (s0 + s < 2ull * W) continue;
-                    const int32_t v = color ? (int32_t)(int16_t)idx_rd16(cp + L.win_off + 2 * s) : (int32_t)cp[L.win_off + s];
-                    if (!in_plane_range(v, color, c)) return FELICS_E_INVALID_INDEX;
-                    out[s0 + s - 2ull * W - base] = v;
-                }
+                if ((rc = load_checkpoint(index, L, color, c, j, W, s0, est, out, base)) != 0) return rc;
                 if (j == 0) {
                     const int32_t p0 = (int32_t)br.bits(32), p1 = (int32_t)br.bits(32);
                     if (br.failed()) return FELICS_E_IO;

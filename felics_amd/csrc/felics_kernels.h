@@ -290,6 +290,7 @@ hipError_t launch_decode8(hipStream_t s, const uint8_t *streams, const uint64_t 
                           uint32_t W, uint32_t H, uint32_t color, uint8_t *pixels, int16_t *planes, int *status);
 // n streams of one shape, each with its restart index (felics.h; index i at index + i * index_stride, 16-byte aligned): one wave per
 // (stream, plane, segment), grid n * C * max(K, 1) < 2^31.  seg_status: a word per wave; status[i] = stream i's first failing one.
+// k_decode8_seg (the walk from a checkpoint with the segment sink: pixel `at` of a segment to out[at]), then launch_seg_finish.
 hipError_t launch_decode8_seg(hipStream_t s, const uint8_t *streams, const uint64_t *offsets, const uint64_t *lens, const uint8_t *index,
                               uint64_t index_stride, uint32_t n, uint32_t W, uint32_t H, uint32_t color, uint32_t segment_pixels, uint32_t K,
                               uint8_t *pixels, int16_t *planes, int *seg_status, int *status);
@@ -314,7 +315,8 @@ hipError_t launch_decode8_seg_lanes(hipStream_t s, const uint8_t *streams, const
 hipError_t launch_seg_finish(hipStream_t s, uint32_t n, uint32_t W, uint32_t H, uint32_t color, uint32_t K, uint8_t *pixels, int16_t *planes,
                              const int *seg_status, int *status);
 // Regions of such streams (felics_decompress_regions_device_indexed, felics.h "Restart index: regions"): one wave per work item =
-// (region, plane, needed segment), k_decode8_region.  A region's items are contiguous, in (plane, segment) order; an item whose
+// (region, plane, needed segment), k_decode8_region: k_decode8_seg's walk with the region sink (it stops behind the region's last
+// pixel and writes the samples inside the region to the crop).  A region's items are contiguous, in (plane, segment) order; an item whose
 // segment is REGION_HEADER_ONLY makes the checks of its stream's header and index header and nothing else (the one item of an empty
 // region).  Crops are dense: gray at pixels + out_off (bytes), RGB through crop-sized int16 planes at planes + plane_off (three
 // planes of w * h samples), converted by k_ycocg8_to_rgb where status[region] is clean.
@@ -329,7 +331,8 @@ struct RegionRow {
 struct RegionItem {
     uint32_t region, plane, seg;
 };
-// nitems < 2^31 items over nregions rows; item_status: a word per item; status[r] = region r's first failing one; max_crop: the
+// nitems < 2^31 items over nregions rows; item_status: a word per item; status[r] = region r's first failing one (k_seg_status
+// over the rows' items); max_crop: the
 // largest w * h of an RGB region (0: gray)
 hipError_t launch_decode8_regions(hipStream_t s, const uint8_t *streams, const uint64_t *offsets, const uint64_t *lens, const uint8_t *index,
                                   uint64_t index_stride, uint32_t W, uint32_t H, uint32_t color, uint32_t segment_pixels, uint32_t K,

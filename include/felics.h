@@ -485,7 +485,7 @@ int felics_decompress_region_indexed(const uint8_t *in, size_t len, const uint8_
  * felics_decompress_batch_device_indexed (same alignment rules; stream 0's header names the shape, index 0's segment_pixels and K).
  * Region r is a window of stream regions[r].stream (`regions` is host memory; several may name one stream); its crop is written
  * dense at d_pixels + out_offsets[r], the crops back to back in request order (out_offsets: host, optional).  One wave per
- * (region, plane, needed segment): k_decode8_region, a walk of its own that stops at `stop`; RGB scratch is crop-sized.  status[r]
+ * (region, plane, needed segment): k_decode8_region, the indexed call's walk stopped at `stop`; RGB scratch is crop-sized.  status[r]
  * (n_regions of them) is the code of region r's first failing item in (plane, segment) order, after the header checks of its stream
  * and index (made for an empty region too).  A failing region leaves only its own crop undefined.
  * Before anything is launched: FELICS_E_INVALID_ARGUMENT for a region outside the image or a stream number >= n_streams,

@@ -11,6 +11,8 @@ FELICS_TEST_DECODE16_LANES=0 around the call) but for the last:
   pitched8  the gray8 streams into 512 x 512 views of pitch 576, felics_decompress_views_device   k_decode8<DecPitched>
   mixed8    the gray8 streams through felics_decompress_images_device                  k_decode8<DecMixed>
   indexed   one 2048 x 2048 gray8 S1 stream, indexed at segment 32 768                 k_decode8_seg
+  indexed_rgb  one 1024 x 1024 RGB8 stream, indexed at segment 32 768                  k_decode8_seg, three planes
+  regions   64 windows of 256 x 256 at seeded positions over the `indexed` stream, felics_decompress_regions_device_indexed   k_decode8_region
   lanes8    4 096 gray8 streams of 64 x 64 in the lane form (FELICS_TEST_DECODE_LANES=1): the control, code a change to the walk leaves alone
 Each library is loaded in a child process of its own (FELICS_LIB_PATH); the parent process never opens the GPU and asks the two
 children for one call at a time, seat a then seat b, workload after workload, --reps rounds after two warm-up rounds.  A time is
@@ -28,7 +30,7 @@ import subprocess
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-WORKLOADS = ("gray8", "rgb8", "gray16", "rgb16", "pitched8", "mixed8", "indexed", "lanes8")
+WORKLOADS = ("gray8", "rgb8", "gray16", "rgb16", "pitched8", "mixed8", "indexed", "indexed_rgb", "regions", "lanes8")
 SEGMENT = 32768
 PITCH = 576
 
@@ -47,7 +49,9 @@ def child():
         """frames: a numpy array (n, h, w[, 3]); -> (device frames, device streams, offsets, lens[, device index, index size])"""
         d = torch.from_numpy(np.ascontiguousarray(frames)).cuda()
         n = frames.shape[0]
-        per = max(int(api.lib().felics_max_compressed_size(w, h, color, depth)), frames[0].nbytes * 5 // 4 + 96)
+        # (twice the frame: the worst-case bound of a 16-bit frame is 49 KB per pixel, 320 GB for these sets; a stream that does not fit is
+        # the encoder's FELICS_E_BUFFER_TOO_SMALL)
+        per = frames[0].nbytes * 2 + 96
         cap = n * ((per + 15) // 16 * 16)
         out = torch.empty(cap, dtype=torch.uint8, device="cuda")
         torch.cuda.synchronize()
@@ -64,11 +68,18 @@ def child():
     g16 = np.stack([synth.gray16(512, 512, f) for f in range(64)])
     c16 = np.stack([np.stack([synth.gray16(256, 256, 3 * f + c) for c in range(3)], axis=-1) for f in range(64)])
     big = synth.gray8(2048, 2048, 0, "S1")[None]
+    bigc = synth.rgb8(1024, 1024, 0)[None]
+    rng = np.random.default_rng(0)
+    windows = [(0, int(x), int(y), 256, 256) for x, y in rng.integers(0, 2048 - 256 + 1, size=(64, 2))]
     small = np.stack([synth.gray8(64, 64, f, "S1") for f in range(4096)])
     sets = {"gray8": encode(g8, 512, 512, 0, 0), "rgb8": encode(c8, 512, 512, 1, 0), "gray16": encode(g16, 512, 512, 0, 1),
-            "rgb16": encode(c16, 256, 256, 1, 1), "indexed": encode(big, 2048, 2048, 0, 0, SEGMENT), "lanes8": encode(small, 64, 64, 0, 0)}
+            "rgb16": encode(c16, 256, 256, 1, 1), "indexed": encode(big, 2048, 2048, 0, 0, SEGMENT),
+            "indexed_rgb": encode(bigc, 1024, 1024, 1, 0, SEGMENT), "lanes8": encode(small, 64, 64, 0, 0)}
     sets["pitched8"] = sets["mixed8"] = sets["gray8"]
-    dest = {k: torch.zeros(v[0].numel() * v[0].element_size(), dtype=torch.uint8, device="cuda") for k, v in sets.items() if k != "pitched8"}
+    sets["regions"] = sets["indexed"]
+    want = {k: v[0].cpu().numpy().view(np.uint8).reshape(-1) for k, v in sets.items()}
+    want["regions"] = np.concatenate([big[0, y:y + h, x:x + w].reshape(-1) for _, x, y, w, h in windows])
+    dest = {k: torch.zeros(len(v), dtype=torch.uint8, device="cuda") for k, v in want.items() if k != "pitched8"}
     mosaic = torch.zeros((64, 512, PITCH), dtype=torch.uint8, device="cuda")
     views = [mosaic[i, :, :512] for i in range(64)]
 
@@ -83,7 +94,9 @@ def child():
             enc.decompress_arrays_device(s[1].data_ptr(), s[2], s[3], views)
         elif name == "mixed8":
             enc.decompress_images_device(s[1].data_ptr(), s[2], s[3], dest[name].data_ptr(), dest[name].numel())
-        elif name == "indexed":
+        elif name == "regions":
+            enc.decompress_regions_device_indexed(s[1].data_ptr(), s[2], s[3], s[4].data_ptr(), s[5], windows, dest[name].data_ptr(), dest[name].numel())
+        elif name in ("indexed", "indexed_rgb"):
             enc.decompress_batch_device_indexed(s[1].data_ptr(), s[2], s[3], s[4].data_ptr(), s[5], dest[name].data_ptr(), dest[name].numel())
         else:
             enc.decompress_batch_device(s[1].data_ptr(), s[2], s[3], dest[name].data_ptr(), dest[name].numel())
@@ -92,8 +105,7 @@ def child():
         call(name)
         torch.cuda.synchronize()
         got = decoded(name).cpu().numpy()
-        want = sets[name][0].cpu().numpy().view(np.uint8).reshape(-1)
-        print("INFO %s ok=%d sha=%s" % (name, int(np.array_equal(got, want)), hashlib.sha256(got.tobytes()).hexdigest()[:16]), flush=True)
+        print("INFO %s ok=%d sha=%s" % (name, int(np.array_equal(got, want[name])), hashlib.sha256(got.tobytes()).hexdigest()[:16]), flush=True)
     lib_sha = hashlib.sha256(open(build.ensure_lib(), "rb").read()).hexdigest()[:16]
     print("READY %s %s" % (torch.cuda.get_device_name(0).replace(" ", "_"), lib_sha), flush=True)
     t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -205,7 +217,7 @@ def main():
         margin[w] = abs(ma - mb) / min(ma, mb)
         good = info[0][w]["ok"] == "1" and info[1][w]["ok"] == "1"
         ok = ok and good
-        say("  %-9s a %s  b %s  margin %.4f %%  pixels %s" % (w, fmt(same_ts[w][0]), fmt(same_ts[w][1]), 100 * margin[w], "ok" if good else "WRONG"))
+        say("  %-11s a %s  b %s  margin %.4f %%  pixels %s" % (w, fmt(same_ts[w][0]), fmt(same_ts[w][1]), 100 * margin[w], "ok" if good else "WRONG"))
     ts, ready, info = protocol(a.parent_lib, None, a.reps)
     say("run 2, seat a = the parent's library, seat b = this build (library sha256 %s...):" % ready[1][1])
     for w in WORKLOADS:
@@ -213,7 +225,7 @@ def main():
         good = info[1][w]["ok"] == "1" and info[0][w]["sha"] == info[1][w]["sha"]
         within = mb <= ma * (1 + margin[w])
         ok = ok and good and within
-        say("  %-9s parent %s  this %s  this / parent - 1 = %+.4f %%  (margin %.4f %%): %s; pixels %s"
+        say("  %-11s parent %s  this %s  this / parent - 1 = %+.4f %%  (margin %.4f %%): %s; pixels %s"
             % (w, fmt(ts[w][0]), fmt(ts[w][1]), 100 * (mb / ma - 1), 100 * margin[w], "within" if within else "EXCEEDS", "identical" if good else "DIFFER"))
     say("verdict: %s" % ("every workload within its margin, pixels identical" if ok else "MISSED (see above)"))
     if a.out:

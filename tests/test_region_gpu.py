@@ -70,6 +70,28 @@ class Device:
             assert list(out_offsets) == list(np.cumsum([0] + [r[3] * r[4] * planes for r in requests[:-1]]))
         return status, crops, out_offsets
 
+    def frames(self, enc, frame_bytes, guard=256, expect=None):
+        """felics_decompress_batch_device_indexed over the same device streams and indexes -> (status, frames as flat uint8
+        arrays); the poisoned bands in front of the first frame and behind the last one must be intact."""
+        import torch
+
+        import felics_amd
+
+        n = len(self.offs)
+        d_px = torch.full((guard + frame_bytes * n + guard,), POISON, dtype=torch.uint8, device="cuda")
+        torch.cuda.synchronize()
+        args = (self.d_in.data_ptr(), self.offs, self.lens, self.d_idx.data_ptr(), self.stride, d_px.data_ptr() + guard, frame_bytes * n)
+        if expect is None:
+            _, status = enc.decompress_batch_device_indexed(*args)
+        else:
+            with pytest.raises(felics_amd.FelicsError) as ei:
+                enc.decompress_batch_device_indexed(*args)
+            assert ei.value.code == expect
+            status = ei.value.status
+        host = d_px.cpu().numpy()
+        assert (host[:guard] == POISON).all() and (host[guard + frame_bytes * n:] == POISON).all()
+        return status, [host[guard + i * frame_bytes:guard + (i + 1) * frame_bytes] for i in range(n)]
+
 
 def _shape_cases():
     for w, h in ic.SHAPES:
@@ -109,6 +131,33 @@ def test_regions_of_three_streams(enc, oracle, w, h, rgb, seg):
         status, crops, _ = dev.regions(enc, [(2,) + win], planes)
         want = rc.crop(imgs[2], win)
         assert status[0] == 0 and (crops[0].reshape(want.shape) == want).all(), (w, h, rgb, seg, win)
+
+
+@pytest.mark.parametrize("w,h,rgb,corrupt", [(100, 100, 1, None), (4096, 3, 0, None), (100, 100, 1, "offset_plus_1")])
+def test_full_frame_region_equals_indexed_decode(enc, oracle, w, h, rgb, corrupt):
+    """k_decode8_region and k_decode8_seg are two sinks of one walk (decode8_from_checkpoint), so the full-frame region of every
+    stream is felics_decompress_batch_device_indexed's frame: three streams at segment 4096, both calls on the same device streams
+    and indexes -- the same bytes, the same per-stream statuses, both the original frames, the guard bands intact on both.  With
+    stream 1's index corrupted (the end check of segment (0, 0)) both calls raise FELICS_E_INVALID_INDEX with statuses
+    [0, E_INVALID_INDEX, 0], and streams 0 and 2 are exact in both."""
+    from felics_amd import api
+
+    imgs = ic.images(w, h, rgb, 3)
+    streams = [oracle.compress(im) for im in imgs]
+    indexes = [api.index_build(s, 4096) for s in streams]
+    if corrupt:
+        indexes[1] = ic.corruptions(indexes[1])[corrupt]
+    dev = Device(streams, indexes)
+    planes = 3 if rgb else 1
+    expect = ic.E_INVALID_INDEX if corrupt else None
+    want = [0, ic.E_INVALID_INDEX, 0] if corrupt else [0, 0, 0]
+    rstatus, crops, _ = dev.regions(enc, [(s, 0, 0, w, h) for s in range(3)], planes, expect=expect)
+    fstatus, frames = dev.frames(enc, w * h * planes, expect=expect)
+    assert list(rstatus) == want and list(fstatus) == want
+    for s in range(3):
+        if want[s] == 0:
+            assert (crops[s] == frames[s]).all(), s
+            assert (crops[s] == imgs[s].reshape(-1)).all() and (frames[s] == imgs[s].reshape(-1)).all(), s
 
 
 def test_empty_regions_write_nothing(enc, oracle):
