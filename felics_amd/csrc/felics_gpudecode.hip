@@ -24,6 +24,7 @@
 #include "felics_device.h"
 #include "felics_index.h"
 #include "felics_kernels.h"
+#include "felics_lanewalk.h"
 
 namespace felics {
 
@@ -678,136 +679,13 @@ __global__ __launch_bounds__(64) void k_seg_status(const int *__restrict__ words
 // Error behaviour as in k_decode8: every read of a stream is bounded by its length, a lane that has failed keeps walking
 // (on zeros, its samples clamped into range so that contexts stay inside the table) and reports its first error.
 // Needs W >= 8 (the read-back of the row above looks four samples ahead of a row's end).
+//
+// What ONE lane does -- LaneReader, the groups of four samples, the pixel step, the estimators, the walk over a plane and the walk over a
+// segment -- is felics_lanewalk.h, compiled by the three lane kernels here and by the host check lanewalk_check.cpp.  A kernel keeps
+// what needs the wave or the grid: the lane's view, the checks, the set-up of reader and estimator, the status.
 // ------------------------------------------------------------------------------------------
 
-constexpr uint32_t DEC8L_HOT = 32;                 // contexts per stream in LDS: 64 x 32 x 12 B = 24 KB per wave
-constexpr uint32_t DEC8L_TABLE_DW = 256 * 3;       // dwords per stream in HBM: 256 contexts x three pairs of u16 counters
-constexpr uint32_t DEC8L_TABLE_DW_RGB = 512 * 3;   // per plane of an RGB stream (contexts 0 .. 510)
-
 namespace {
-
-// MSB-first bit reader of ONE LANE over [base, base + len) (bitstream-io BitReader<_, BigEndian>)
-struct LaneReader {
-    const uint32_t *al;   // aligned-down dword pointer of the stream's first byte
-    uint32_t total_dw;    // dwords from `al` that hold stream bytes
-    uint32_t pos;         // dwords moved into acc so far
-    uint32_t nxt;         // dword `pos` as it lies in memory (zero past the end): asked for when dword pos - 1 was taken and first
-                          // LOOKED AT when it is taken itself (the byte swap at the load would be a wait for the load)
-    uint64_t acc;         // unread bits, left-aligned
-    uint32_t navail;      // valid bits in acc
-    uint64_t end_bit;     // bits from `al` to the end of the stream
-
-    __device__ __forceinline__ uint32_t fetch(uint32_t i) const { return i < total_dw ? al[i] : 0u; }
-    __device__ __forceinline__ void init(const uint8_t *p, uint64_t n) {
-        const uint32_t skew = (uint32_t)(reinterpret_cast<uintptr_t>(p) & 3u);
-        al = reinterpret_cast<const uint32_t *>(p - skew);
-        total_dw = (uint32_t)std::min<uint64_t>((skew + n + 3u) >> 2, 0xFFFFFFFFull);
-        pos = 0;
-        nxt = fetch(0);
-        acc = 0;
-        navail = 0;
-        end_bit = (skew + n) * 8u;
-        refill();
-        if (skew) {  // the first dword starts before the stream: drop those bytes
-            acc <<= 8u * skew;
-            navail -= 8u * skew;
-        }
-    }
-    // the same, positioned `bit` bits behind p (bit <= 8 n: the caller's check, so the first dword asked for holds a stream byte or lies
-    // right behind the last one; like every fetch it is bounded by total_dw)
-    __device__ __forceinline__ void init_at(const uint8_t *p, uint64_t n, uint64_t bit) {
-        const uint32_t skew = (uint32_t)(reinterpret_cast<uintptr_t>(p) & 3u);
-        al = reinterpret_cast<const uint32_t *>(p - skew);
-        total_dw = (uint32_t)std::min<uint64_t>((skew + n + 3u) >> 2, 0xFFFFFFFFull);
-        end_bit = (skew + n) * 8u;
-        const uint64_t at = 8u * skew + bit;
-        pos = (uint32_t)std::min<uint64_t>(at >> 5, 0xFFFFFFFEull);
-        nxt = fetch(pos);
-        acc = 0;
-        navail = 0;
-        refill();
-        acc <<= (uint32_t)(at & 31u);
-        navail -= (uint32_t)(at & 31u);
-    }
-    // bits consumed so far, counted from p (the pointer init / init_at was given)
-    __device__ __forceinline__ uint64_t bit_pos(const uint8_t *p) const {
-        return (uint64_t)pos * 32u - navail - 8u * (uint32_t)(reinterpret_cast<uintptr_t>(p) & 3u);
-    }
-    // at least 33 valid bits in acc afterwards (zeros past the end of the stream)
-    __device__ __forceinline__ void refill() {
-        if (navail <= 32u) {
-            acc |= (uint64_t)__builtin_bswap32(nxt) << (32u - navail);
-            navail += 32u;
-            pos++;
-            nxt = fetch(pos);
-        }
-    }
-    __device__ __forceinline__ uint32_t take(uint32_t n) {  // the next n <= 32 bits; the caller has refilled (n <= navail)
-        const uint32_t v = n ? (uint32_t)(acc >> (64u - n)) : 0u;
-        acc <<= n;
-        navail -= n;
-        return v;
-    }
-    __device__ __forceinline__ uint32_t get(uint32_t n) {
-        refill();
-        return take(n);
-    }
-    __device__ __forceinline__ bool failed() const { return (uint64_t)pos * 32u - navail > end_bit; }
-    __device__ __forceinline__ uint64_t unary0() {  // ones before the first zero, the zero consumed (read_unary0)
-        uint64_t q = 0;
-        while (true) {
-            refill();
-            const uint32_t top = (uint32_t)(acc >> 32);
-            const uint32_t ones = top == 0xFFFFFFFFu ? 32u : (uint32_t)__builtin_clz(~top);
-            if (ones == 32u) {
-                q += 32u;
-                take(32u);
-                if (failed()) return q;
-                continue;
-            }
-            take(ones + 1u);
-            return q + ones;
-        }
-    }
-};
-
-// four consecutive samples of a stream's own output plane (one unaligned load / store; the plane is this wave's to write and to read)
-template <typename ST>
-struct Four;
-template <>
-struct Four<uint8_t> {
-    uint32_t v;
-    __device__ __forceinline__ void clear() { v = 0; }
-    __device__ __forceinline__ void load(const uint8_t *p) { __builtin_memcpy(&v, p, 4); }
-    __device__ __forceinline__ void load_n(const uint8_t *p, uint32_t n) {  // samples 0 .. n - 1 only (n < 4), nothing behind them touched
-        v = 0;
-        for (uint32_t j = 0; j < n; j++) v |= (uint32_t)p[j] << (8u * j);
-    }
-    __device__ __forceinline__ void store(uint8_t *p) const { __builtin_memcpy(p, &v, 4); }
-    __device__ __forceinline__ int get(uint32_t j) const { return (int)((v >> (8u * j)) & 0xFFu); }
-    __device__ __forceinline__ void set(uint32_t j, int s) { v |= (uint32_t)s << (8u * j); }  // (0 <= s <= 255, the field still zero)
-};
-template <>
-struct Four<int16_t> {
-    uint32_t lo, hi;  // (two named dwords: an array indexed by the sample's number went to scratch memory)
-    __device__ __forceinline__ void clear() { lo = hi = 0; }
-    __device__ __forceinline__ void load(const int16_t *p) {
-        uint32_t v[2];
-        __builtin_memcpy(v, p, 8);
-        lo = v[0];
-        hi = v[1];
-    }
-    __device__ __forceinline__ void store(int16_t *p) const {
-        const uint32_t v[2] = {lo, hi};
-        __builtin_memcpy(p, v, 8);
-    }
-    __device__ __forceinline__ int get(uint32_t j) const { return (int)(int16_t)(((j & 2u) ? hi : lo) >> (16u * (j & 1u))); }
-    __device__ __forceinline__ void set(uint32_t j, int s) {  // (the field still zero)
-        const uint32_t f = ((uint32_t)s & 0xFFFFu) << (16u * (j & 1u));
-        lo |= (j & 2u) ? 0u : f;
-        hi |= (j & 2u) ? f : 0u;
-    }
-};
 
 // The lane form's geometry policy.  LaneUniform: the same-shape call's arguments -- lane j of wave b is stream 64 b + j, outputs
 // back to back.  LaneMixed: the wave's row (W, H, its slots: scalar loads) and the lane's slot (stream, output).
@@ -853,6 +731,26 @@ __device__ __forceinline__ ST *lane_plane(const LaneMixed &, void *out_base, con
     return reinterpret_cast<ST *>(out_base) + v.out_off + (uint64_t)plane * npix;
 }
 
+// LanePitched: this lane's view -- its first sample, and the samples between two of its rows (the walk leaves [0, W) of no row)
+template <typename ST>
+__device__ __forceinline__ ST *lane_pitched(const LanePitched &g, const LaneView &v, int64_t &pitch) {
+    const ViewRow vr = g.views[v.slot];
+    pitch = vr.row_stride / (int64_t)sizeof(ST);
+    return reinterpret_cast<ST *>(const_cast<void *>(vr.data));
+}
+// The header (format.rs:63-84) of a whole-stream lane must be the one the caller announced: FELICS_OK, or the code with which the
+// lane leaves before it decodes anything
+__device__ __forceinline__ int lane_header_check(const uint8_t *s, uint64_t slen, uint32_t color, uint32_t depth, uint32_t W, uint32_t H) {
+    if (slen < FELICS_HEADER_BYTES) return FELICS_E_IO;
+    const uint32_t w = ((uint32_t)s[6] << 24) | ((uint32_t)s[7] << 16) | ((uint32_t)s[8] << 8) | s[9];
+    const uint32_t h = ((uint32_t)s[10] << 24) | ((uint32_t)s[11] << 16) | ((uint32_t)s[12] << 8) | s[13];
+    if (s[0] != 'F' || s[1] != 'L' || s[2] != 'C' || s[3] != 'S') return FELICS_E_INVALID_SIGNATURE;
+    if (s[4] > 1) return FELICS_E_INVALID_COLOR_TYPE;
+    if (s[5] > 1) return FELICS_E_INVALID_PIXEL_DEPTH;
+    if (s[4] != color || s[5] != depth || w != W || h != H) return FELICS_E_INVALID_DIMENSIONS;
+    return FELICS_OK;
+}
+
 }  // namespace
 
 // RGB = false: gray8 streams, u8 frames straight to `out_base`.  RGB = true: the three planes of an RGB8 stream, one after the other from
@@ -868,7 +766,8 @@ __global__ __launch_bounds__(64) void k_decode8_lanes(const uint8_t *__restrict_
     using ST = typename std::conditional<RGB, int16_t, uint8_t>::type;
     constexpr uint32_t NP = RGB ? 3u : 1u;
     constexpr uint32_t TABLE_DW = RGB ? DEC8L_TABLE_DW_RGB : DEC8L_TABLE_DW;  // per plane
-    constexpr int LO_OK = RGB ? -255 : 0, HI_OK = 255;
+    constexpr bool PITCHED = std::is_same<G, LanePitched>::value;
+    static_assert(!PITCHED || !RGB, "RGB lanes write planes; their views are the conversion kernel's");
     __shared__ uint32_t hot[DEC8L_HOT * 3 * 64];  // [context][pair of counters][lane]
     const uint32_t lane = lane_id();
     LaneView v;
@@ -877,185 +776,24 @@ __global__ __launch_bounds__(64) void k_decode8_lanes(const uint8_t *__restrict_
     const uint8_t *s = streams + offsets[img];
     const uint64_t slen = lens[img];
     const uint64_t npix = (uint64_t)W * H;
-    // header (format.rs:63-84) must be the one the caller announced
-    int rc = FELICS_OK;
-    if (slen < FELICS_HEADER_BYTES) {
-        rc = FELICS_E_IO;
-    } else {
-        const uint32_t w = ((uint32_t)s[6] << 24) | ((uint32_t)s[7] << 16) | ((uint32_t)s[8] << 8) | s[9];
-        const uint32_t h = ((uint32_t)s[10] << 24) | ((uint32_t)s[11] << 16) | ((uint32_t)s[12] << 8) | s[13];
-        if (s[0] != 'F' || s[1] != 'L' || s[2] != 'C' || s[3] != 'S') rc = FELICS_E_INVALID_SIGNATURE;
-        else if (s[4] > 1) rc = FELICS_E_INVALID_COLOR_TYPE;
-        else if (s[5] > 1) rc = FELICS_E_INVALID_PIXEL_DEPTH;
-        else if (s[4] != (RGB ? 1 : 0) || s[5] != 0 || w != W || h != H) rc = FELICS_E_INVALID_DIMENSIONS;
-    }
+    int rc = lane_header_check(s, slen, RGB ? 1 : 0, 0, W, H);
     if (rc != FELICS_OK) {  // nothing of this stream is decoded (its lane leaves; the others go on)
         status[img] = rc;
         return;
     }
     LaneReader br;
     br.init(s + FELICS_HEADER_BYTES, slen - FELICS_HEADER_BYTES);
-    uint32_t *myhot = hot + lane;
+    Lane8Step<RGB> step{{hot + lane, nullptr}, 0};
     for (uint32_t plane = 0; plane < NP; plane++) {
-    for (uint32_t i = 0; i < DEC8L_HOT * 3; i++) myhot[i * 64] = 0;  // KEstimator::new (the HBM rows arrive zeroed); a lane's own column
-    const int32_t p0 = (int32_t)br.get(32), p1 = (int32_t)br.get(32);  // compression.rs:166-167
-    if (br.failed() && rc == FELICS_OK) rc = FELICS_E_IO;
-    if (npix == 0) continue;
-    uint32_t *tab = table + ((uint64_t)v.slot * NP + plane) * TABLE_DW;
-    ST *out = lane_plane<ST>(geo, out_base, v, NP, plane, npix);
-    // LanePitched: this lane's view; the rows lie `pitch` samples apart, and no load or store leaves [0, W) of its row -- the bytes
-    // between a row's end and the pitch are somebody else's (a neighbouring cell of a mosaic: another lane's, another wave's)
-    constexpr bool PITCHED = std::is_same<G, LanePitched>::value;
-    int64_t pitch = 0;
-    if constexpr (PITCHED) {
-        static_assert(!PITCHED || !RGB, "RGB lanes write planes; their views are the conversion kernel's");
-        const ViewRow vr = geo.views[v.slot];
-        out = reinterpret_cast<ST *>(const_cast<void *>(vr.data));
-        pitch = vr.row_stride / (int64_t)sizeof(ST);
-    }
-    // (x, y) and everything derived from them alone is wave-uniform: every stream has the same shape
-    int left = 0, left2 = 0;
-    Four<ST> up4, up4_next, out4;
-    up4.clear();
-    up4_next.clear();
-    out4.clear();
-    uint32_t out_of_range = 0;  // gray: OR of every sample as decoded (above 255 if one did not fit); RGB: nonzero if one was outside LO_OK .. HI_OK
-    int first_col2 = 0;
-    for (uint32_t y = 0; y < H; y++) {
-      ST *row = out + (uint64_t)y * W;  // this row of the stream's plane, and the one above it
-      const ST *prow = row - W;
-      if constexpr (PITCHED) {
-          row = out + (int64_t)y * pitch;
-          prow = row - pitch;
-      }
-      if (y > 0) {
-          up4.load(prow);                   // row above, samples 0 .. 3 (later groups are asked for four samples ahead)
-          if (4 < W) up4_next.load(prow + 4);
-          // second neighbour of a row's first pixel (misc.rs:14-23): two rows up, or above-right in row 1
-          if constexpr (PITCHED)
-              first_col2 = y >= 2 ? (int)prow[-pitch] : up4.get(1);  // (W >= 8)
-          else
-              first_col2 = y >= 2 ? (int)prow[-(int64_t)W] : (W > 1 ? up4.get(1) : 0);
-      }
-      for (uint32_t x = 0; x < W; x++) {
-        const uint32_t xs = x & 3u;
-        if (xs == 0 && y > 0 && x != 0) {
-            up4 = up4_next;
-            if constexpr (PITCHED) {  // (wave-uniform: x and W) the row's last group may be short: sample by sample, never past W
-                if (x + 8 <= W) up4_next.load(prow + x + 4);
-                else if (x + 4 < W) up4_next.load_n(prow + x + 4, W - (x + 4));
-            } else if (x + 4 < W) {
-                up4_next.load(prow + x + 4);
-            }
-        }
-        int pv;
-        if (y == 0 && x < 2) {
-            pv = x == 0 ? p0 : p1;
-        } else {
-            const int above = up4.get(xs);
-            const bool row0 = y == 0, col0 = x == 0 && !row0;
-            const int v1 = col0 ? above : left;
-            const int v2 = col0 ? first_col2 : (row0 ? left2 : above);
-            const int hi = max(v1, v2), lo = min(v1, v2);
-            const uint32_t ctx = (uint32_t)(hi - lo);  // <= 255 (510): every sample kept is in range
-            // The context's row for every lane, whether its pixel turns out to be an event or not (no divergence, and the LDS
-            // round trip runs beside the arithmetic below): three pairs of 16-bit counters; hot contexts from LDS.
-            const bool is_hot = ctx < DEC8L_HOT;
-            const uint32_t hrow = min(ctx, DEC8L_HOT - 1u) * 3u * 64u;
-            uint32_t w01 = myhot[hrow], w23 = myhot[hrow + 64], w45 = myhot[hrow + 128];
-            br.refill();  // >= 33 valid bits: both kinds of code are read off the top 32 of them, then consumed in one go
-            const uint32_t top = (uint32_t)(br.acc >> 32);
-            const bool in_range = (top >> 31) != 0;
-            // -- in range: `1`, then the phased-in code of p - L in m or m + 1 bits (phase_in_coding.rs:86-112), m <= 8 (context 255: n = 256)
-            const uint32_t nn = ctx + 1;
-            const uint32_t m = 31u - (uint32_t)__builtin_clz(nn);
-            const uint32_t right_p = (2u << m) - nn, left_p = nn - (1u << m);
-            const uint32_t t1 = top << 1;
-            uint32_t r = (t1 >> 1) >> (31u - m);               // the m bits behind the flag
-            const uint32_t extra = (t1 >> (31u - m)) & 1u;      // the bit behind them
-            const uint32_t longer = r >= right_p ? 1u : 0u;     // the code has one more bit
-            r = longer ? (r - right_p) * 2u + right_p + extra : r;
-            uint32_t rot = r + left_p;                          // rotate_left: (r + left_p) mod n, r < n
-            rot = rot >= nn ? rot - nn : rot;
-            const int pv_in = lo + (int)rot;
-            const uint32_t bits_in = 1u + m + longer;
-            // -- out of range: `0`, above / below flag, q ones, `0`, k bits -- off the same 32 bits when it fits in them
-            const bool above_flag = ((top >> 30) & 1u) != 0;
-            if (!in_range && !is_hot) {  // (noise: a cold context's row comes from the stream's table in HBM)
-                w01 = tab[ctx * 3 + 0];
-                w23 = tab[ctx * 3 + 1];
-                w45 = tab[ctx * 3 + 2];
-            }
-            uint32_t S[6] = {w01 & 0xFFFFu, w01 >> 16, w23 & 0xFFFFu, w23 >> 16, w45 & 0xFFFFu, w45 >> 16};
-            // get_k: smallest counter, ties to the largest k (parameter_selection.rs:71-85)
-            const uint32_t key = min(min(min((S[0] << 3) | 7u, (S[1] << 3) | 6u), min((S[2] << 3) | 5u, (S[3] << 3) | 4u)),
-                                     min((S[4] << 3) | 3u, (S[5] << 3) | 2u));
-            const uint32_t k = 7u - (key & 7u);
-            const uint32_t t2 = top << 2;                                  // 30 bits of the stream, two zeros behind them
-            const uint32_t ones = (uint32_t)__builtin_clz(~t2);            // (<= 30: ~t2 ends in ones)
-            const bool fits = ones + 1u + k <= 30u;                        // unary part, its zero and the k bits lie inside the 30
-            uint32_t e = (ones << k) + (((t2 << (ones & 31u)) << 1 >> 1) >> (31u - k));  // k bits behind the zero (k <= 5)
-            uint32_t nbits = in_range ? bits_in : 3u + ones + k;
-            if (!in_range && !fits) {
-                // a long code (or the end of the stream): the general reader, bit field by bit field
-                br.take(2);
-                const uint64_t q = br.unary0();
-                const uint64_t e64 = (q << k) + br.get(k);
-                e = (uint32_t)e64;
-                if (e64 > 1024u) {  // no sample of an 8-bit plane is that far from its neighbours
-                    if (rc == FELICS_OK) rc = e64 > 0xFFFFFFFFull ? FELICS_E_VALUE_OVERFLOW : FELICS_E_INVALID_VALUE;
-                    e = 0;
-                }
-                nbits = 0;
-            }
-            br.acc <<= nbits;  // (nbits <= 32 < the valid bits)
-            br.navail -= nbits;
-            if (!in_range) {
-                // update (parameter_selection.rs:49-68): add the six Rice lengths, halve when the smallest passes 1024
-                uint32_t mn = 0xFFFFFFFFu;
-#pragma unroll
-                for (uint32_t kk = 0; kk < 6; kk++) {
-                    S[kk] += (e >> kk) + 1u + kk;
-                    mn = min(mn, S[kk]);
-                }
-                const uint32_t hsh = mn > 1024u ? 1u : 0u;
-                w01 = (S[0] >> hsh) | ((S[1] >> hsh) << 16);
-                w23 = (S[2] >> hsh) | ((S[3] >> hsh) << 16);
-                w45 = (S[4] >> hsh) | ((S[5] >> hsh) << 16);
-                if (is_hot) {
-                    myhot[hrow] = w01;
-                    myhot[hrow + 64] = w23;
-                    myhot[hrow + 128] = w45;
-                } else {
-                    tab[ctx * 3 + 0] = w01;
-                    tab[ctx * 3 + 1] = w23;
-                    tab[ctx * 3 + 2] = w45;
-                }
-            }
-            pv = in_range ? pv_in : (above_flag ? hi + (int)e + 1 : lo - (int)e - 1);
-        }
-        // try_into::<u8>() (for RGB: the estimator's context bound) would fail on anything outside LO_OK .. HI_OK: remembered and
-        // reported at the end of the row; the sample is cut into the range so that a failed stream's contexts stay inside the table
-        if (RGB) {
-            out_of_range |= (uint32_t)(pv - LO_OK) > (uint32_t)(HI_OK - LO_OK) ? 1u : 0u;
-            pv = min(max(pv, LO_OK), HI_OK);
-        } else {
-            out_of_range |= (uint32_t)pv;  // (two instructions per pixel: above 255 if one did not fit eight bits, negative ones included)
-            pv &= 255;
-        }
-        out4.set(xs, pv);
-        left2 = left;
-        left = pv;
-        if (xs == 3u) {  // four samples complete: one (unaligned) store to the stream's plane
-            out4.store(row + (x - 3u));
-            out4.clear();
-        } else if (x + 1 == W) {  // the last one to three samples of a row
-            for (uint32_t j = 0; j <= xs; j++) row[(x - xs) + j] = (ST)out4.get(j);
-            out4.clear();
-        }
-      }
-      if (rc == FELICS_OK) rc = br.failed() ? FELICS_E_IO : ((RGB ? out_of_range != 0 : out_of_range > 255u) ? FELICS_E_INVALID_VALUE : FELICS_OK);
-    }
+        for (uint32_t i = 0; i < DEC8L_HOT * 3; i++) step.est.myhot[i * 64] = 0;  // KEstimator::new (the HBM rows arrive zeroed); a lane's own column
+        const int32_t p0 = (int32_t)br.get(32), p1 = (int32_t)br.get(32);  // compression.rs:166-167
+        if (br.failed() && rc == FELICS_OK) rc = FELICS_E_IO;
+        if (npix == 0) continue;
+        step.est.tab = table + ((uint64_t)v.slot * NP + plane) * TABLE_DW;
+        ST *out = lane_plane<ST>(geo, out_base, v, NP, plane, npix);
+        int64_t pitch = 0;
+        if constexpr (PITCHED) out = lane_pitched<ST>(geo, v, pitch);
+        lane_walk_plane<ST, PITCHED>(br, step, out, pitch, W, H, p0, p1, rc);
     }
     if (br.failed() && rc == FELICS_OK) rc = FELICS_E_IO;  // (whatever else: it was decoding padding)
     status[img] = rc;
@@ -1067,7 +805,7 @@ __global__ __launch_bounds__(64) void k_decode8_lanes(const uint8_t *__restrict_
 // Segment j of 64 streams of one shape starts at the same pixel p0, so at the same (x, y): 64 such segments share a wave exactly as 64
 // streams share one in k_decode8_lanes, with (x, y) wave-uniform.  Wave wave0 + blockIdx.x is (group g of 64 consecutive streams,
 // plane c, segment j) = (w / (C K), w / K % C, w % K); lane l is stream 64 g + l (the launch covers whole groups only).  The
-// per-pixel path is k_decode8_lanes's, statement for statement; what differs is k_decode8_seg's business:
+// per-pixel path is k_decode8_lanes's (lane8_pixel, felics_lanewalk.h); what differs is k_decode8_seg's business:
 //   * every lane makes k_decode8_seg's checks, in its order: the stream's header, the index header against it and the launch's
 //     (segment_pixels, K: no checkpoint is read outside index_stride), the segment's bit range, the window's samples (a u8 sample is
 //     in range whatever it holds: only the int16 windows are looked through).  A lane that fails one writes its code and leaves;
@@ -1079,13 +817,8 @@ __global__ __launch_bounds__(64) void k_decode8_lanes(const uint8_t *__restrict_
 //     encoder writes: its counters are a snapshot of an estimator that obeys the bound at every pixel.  A forged checkpoint can hold
 //     up to 65 535 per counter; a pair's low counter can then carry into the high one -- wrong values of k for a segment whose index
 //     is wrong anyway (the end check is what judges it), and no address depends on a counter;
-//   * the row above: pixel q >= p0 is read back from the lane's own output plane (it wrote it itself), q < p0 from the checkpoint's
-//     window at 2 W - (p0 - q) -- the pixels in front of p0 are another wave's, which may not have written them yet: the output is
-//     NEVER read below p0.  p0, x and y are wave-uniform, so each choice is a uniform branch.  A group of four that straddles p0,
-//     and a row's short last group, are assembled sample by sample: no load runs past sample W - 1 of a row, in the window or in the
-//     plane.  Window positions in front of the plane (p0 + t < 2 W) are never looked at;
-//   * only pixels p0 .. pend - 1 are written: a first group with x0 & 3 != 0 is stored from x0 on, a last group that ends inside
-//     four samples is flushed sample by sample;
+//   * the walk from p0 to pend is lane8_walk_segment (felics_lanewalk.h): which samples of the row above come from the window and
+//     which from the lane's own output, and which samples of a group are this segment's to store, is said and checked there;
 //   * at the end FELICS_E_IO if the reader ran off the stream, else the end check: the bit position equals the next checkpoint's
 //     bit_offset (plane_end_bit[c] behind the last), else FELICS_E_INVALID_INDEX.
 // seg_status[(img * C + c) * K + j] = FELICS_OK or the code, as k_decode8_seg writes it: k_seg_status picks a stream's first.
@@ -1102,7 +835,6 @@ __global__ __launch_bounds__(64) void k_decode8_seg_lanes(const uint8_t *__restr
     constexpr uint32_t NCTX = RGB ? 512u : 256u;                                // rows of a checkpoint's state (IndexLayout::nctx)
     constexpr uint32_t TABLE_DW = RGB ? DEC8L_TABLE_DW_RGB : DEC8L_TABLE_DW;  // per item
     static_assert(TABLE_DW == NCTX * 3, "a checkpoint's state is the lane table's rows");
-    constexpr int LO_OK = RGB ? -255 : 0, HI_OK = 255;
     __shared__ uint32_t hot[DEC8L_HOT * 3 * 64];  // [context][pair of counters][lane]
     const uint32_t lane = lane_id();
     const uint32_t wv = wave0 + blockIdx.x;
@@ -1155,16 +887,15 @@ __global__ __launch_bounds__(64) void k_decode8_seg_lanes(const uint8_t *__restr
     }
     const uint8_t *cp = idx + cp_off;
     const ST *win = reinterpret_cast<const ST *>(cp + LL.win_off);  // sample t is pixel p0 - 2 W + t
-    uint32_t *myhot = hot + lane;
+    const Lane8Estimator est{hot + lane, wtab + (uint64_t)lane * TABLE_DW};
     {
         const uint2 *st = reinterpret_cast<const uint2 *>(cp + CP_STATE_OFF);
         for (uint32_t i = 0; i < DEC8L_HOT * 3 / 2; i++) {  // the checkpoint's hot rows: a lane's own column
             const uint2 v2 = st[i];
-            myhot[(2 * i) * 64] = v2.x;
-            myhot[(2 * i + 1) * 64] = v2.y;
+            est.myhot[(2 * i) * 64] = v2.x;
+            est.myhot[(2 * i + 1) * 64] = v2.y;
         }
     }
-    uint32_t *tab = wtab + (uint64_t)lane * TABLE_DW;
     ST *out = reinterpret_cast<ST *>(out_base) + ((uint64_t)img * NP + c) * npix;
     LaneReader br;
     br.init_at(s, slen, start);
@@ -1174,169 +905,179 @@ __global__ __launch_bounds__(64) void k_decode8_seg_lanes(const uint8_t *__restr
         raw1 = (int32_t)br.get(32);
         if (br.failed()) rc = FELICS_E_IO;
     }
-    // pixel q of the plane as this lane may read it: its own output from p0 on, the window in front (p0 - 2 W <= q: the callers' business)
-    auto rd = [&](uint64_t q) -> int { return q >= p0 ? (int)out[q] : (int)win[2ull * W - (p0 - q)]; };
-    // (x, y) and everything derived from them alone is wave-uniform
-    uint32_t x = (uint32_t)(p0 % W), y = (uint32_t)(p0 / W);
-    // row y - 1 from column xg (a multiple of four below W) on: four samples, or the row's last one to three
-    auto load_up = [&](uint32_t xg) {
-        Four<ST> f;
-        const uint64_t q0 = (uint64_t)(y - 1) * W + xg;
-        const uint32_t cnt = min(4u, W - xg);
-        if (cnt == 4u && q0 >= p0) {
-            f.load(out + q0);
-        } else if (cnt == 4u && q0 + 4u <= p0) {
-            f.load(win + (2ull * W - (p0 - q0)));
-        } else {
-            f.clear();
-            for (uint32_t k = 0; k < cnt; k++) f.set(k, rd(q0 + k));
-        }
-        return f;
-    };
-    int left = x >= 1 ? (int)win[2ull * W - 1] : 0, left2 = x >= 2 ? (int)win[2ull * W - 2] : 0;
-    Four<ST> up4, up4_next, out4;
-    up4.clear();
-    up4_next.clear();
-    out4.clear();
-    if (x != 0 && y > 0) {  // a start inside a row: the groups of the row above that the row's start would have asked for
-        if ((x & 3u) == 0) {
-            up4_next = load_up(x);  // (moved into up4 by the first pixel)
-        } else {
-            up4 = load_up(x & ~3u);
-            if ((x & ~3u) + 4 < W) up4_next = load_up((x & ~3u) + 4);
-        }
-    }
-    uint32_t gfirst = x & 3u;   // first sample of the current group that is this segment's to store
-    uint32_t out_of_range = 0;  // gray: OR of every sample as decoded (above 255 if one did not fit); RGB: nonzero if one was outside LO_OK .. HI_OK
-    int first_col2 = 0;
-    for (uint64_t i = p0; i < pend; i++) {
-        const uint32_t xs = x & 3u;
-        if (x == 0 && y > 0) {
-            up4 = load_up(0);  // row above, samples 0 .. 3 (later groups are asked for four samples ahead); W >= 8
-            up4_next = load_up(4);
-            // second neighbour of a row's first pixel (misc.rs:14-23): two rows up, or above-right in row 1
-            first_col2 = y >= 2 ? rd((uint64_t)(y - 2) * W) : up4.get(1);
-        } else if (xs == 0 && y > 0) {
-            up4 = up4_next;
-            if (x + 4 < W) up4_next = load_up(x + 4);
-        }
-        int pv;
-        if (i < 2) {
-            pv = i == 0 ? raw0 : raw1;
-        } else {
-            const int above = up4.get(xs);
-            const bool row0 = y == 0, col0 = x == 0 && !row0;
-            const int v1 = col0 ? above : left;
-            const int v2 = col0 ? first_col2 : (row0 ? left2 : above);
-            const int hi = max(v1, v2), lo = min(v1, v2);
-            const uint32_t ctx = (uint32_t)(hi - lo);  // <= 255 (510): every sample kept is in range, every window sample checked
-            const bool is_hot = ctx < DEC8L_HOT;
-            const uint32_t hrow = min(ctx, DEC8L_HOT - 1u) * 3u * 64u;
-            uint32_t w01 = myhot[hrow], w23 = myhot[hrow + 64], w45 = myhot[hrow + 128];
-            br.refill();  // >= 33 valid bits: both kinds of code are read off the top 32 of them, then consumed in one go
-            const uint32_t top = (uint32_t)(br.acc >> 32);
-            const bool in_range = (top >> 31) != 0;
-            // -- in range: `1`, then the phased-in code of p - L in m or m + 1 bits (phase_in_coding.rs:86-112)
-            const uint32_t nn = ctx + 1;
-            const uint32_t m = 31u - (uint32_t)__builtin_clz(nn);
-            const uint32_t right_p = (2u << m) - nn, left_p = nn - (1u << m);
-            const uint32_t t1 = top << 1;
-            uint32_t r = (t1 >> 1) >> (31u - m);               // the m bits behind the flag
-            const uint32_t extra = (t1 >> (31u - m)) & 1u;      // the bit behind them
-            const uint32_t longer = r >= right_p ? 1u : 0u;     // the code has one more bit
-            r = longer ? (r - right_p) * 2u + right_p + extra : r;
-            uint32_t rot = r + left_p;                          // rotate_left: (r + left_p) mod n, r < n
-            rot = rot >= nn ? rot - nn : rot;
-            const int pv_in = lo + (int)rot;
-            const uint32_t bits_in = 1u + m + longer;
-            // -- out of range: `0`, above / below flag, q ones, `0`, k bits -- off the same 32 bits when it fits in them
-            const bool above_flag = ((top >> 30) & 1u) != 0;
-            if (!in_range && !is_hot) {  // (noise: a cold context's row comes from the item's table in HBM)
-                w01 = tab[ctx * 3 + 0];
-                w23 = tab[ctx * 3 + 1];
-                w45 = tab[ctx * 3 + 2];
-            }
-            uint32_t S[6] = {w01 & 0xFFFFu, w01 >> 16, w23 & 0xFFFFu, w23 >> 16, w45 & 0xFFFFu, w45 >> 16};
-            // get_k: smallest counter, ties to the largest k (parameter_selection.rs:71-85)
-            const uint32_t key = min(min(min((S[0] << 3) | 7u, (S[1] << 3) | 6u), min((S[2] << 3) | 5u, (S[3] << 3) | 4u)),
-                                     min((S[4] << 3) | 3u, (S[5] << 3) | 2u));
-            const uint32_t k = 7u - (key & 7u);
-            const uint32_t t2 = top << 2;                                  // 30 bits of the stream, two zeros behind them
-            const uint32_t ones = (uint32_t)__builtin_clz(~t2);            // (<= 30: ~t2 ends in ones)
-            const bool fits = ones + 1u + k <= 30u;                        // unary part, its zero and the k bits lie inside the 30
-            uint32_t e = (ones << k) + (((t2 << (ones & 31u)) << 1 >> 1) >> (31u - k));  // k bits behind the zero (k <= 5)
-            uint32_t nbits = in_range ? bits_in : 3u + ones + k;
-            if (!in_range && !fits) {
-                // a long code (or the end of the stream): the general reader, bit field by bit field
-                br.take(2);
-                const uint64_t q = br.unary0();
-                const uint64_t e64 = (q << k) + br.get(k);
-                e = (uint32_t)e64;
-                if (e64 > 1024u) {  // no sample of an 8-bit plane is that far from its neighbours
-                    if (rc == FELICS_OK) rc = e64 > 0xFFFFFFFFull ? FELICS_E_VALUE_OVERFLOW : FELICS_E_INVALID_VALUE;
-                    e = 0;
-                }
-                nbits = 0;
-            }
-            br.acc <<= nbits;  // (nbits <= 32 < the valid bits)
-            br.navail -= nbits;
-            if (!in_range) {
-                // update (parameter_selection.rs:49-68): add the six Rice lengths, halve when the smallest passes 1024
-                uint32_t mn = 0xFFFFFFFFu;
-#pragma unroll
-                for (uint32_t kk = 0; kk < 6; kk++) {
-                    S[kk] += (e >> kk) + 1u + kk;
-                    mn = min(mn, S[kk]);
-                }
-                const uint32_t hsh = mn > 1024u ? 1u : 0u;
-                w01 = (S[0] >> hsh) | ((S[1] >> hsh) << 16);
-                w23 = (S[2] >> hsh) | ((S[3] >> hsh) << 16);
-                w45 = (S[4] >> hsh) | ((S[5] >> hsh) << 16);
-                if (is_hot) {
-                    myhot[hrow] = w01;
-                    myhot[hrow + 64] = w23;
-                    myhot[hrow + 128] = w45;
-                } else {
-                    tab[ctx * 3 + 0] = w01;
-                    tab[ctx * 3 + 1] = w23;
-                    tab[ctx * 3 + 2] = w45;
-                }
-            }
-            pv = in_range ? pv_in : (above_flag ? hi + (int)e + 1 : lo - (int)e - 1);
-        }
-        // out of LO_OK .. HI_OK: remembered and reported at the end of the row; the sample is cut into the range so that a failed
-        // lane's contexts stay inside the table
-        if (RGB) {
-            out_of_range |= (uint32_t)(pv - LO_OK) > (uint32_t)(HI_OK - LO_OK) ? 1u : 0u;
-            pv = min(max(pv, LO_OK), HI_OK);
-        } else {
-            out_of_range |= (uint32_t)pv;
-            pv &= 255;
-        }
-        out4.set(xs, pv);
-        left2 = left;
-        left = pv;
-        const bool row_end = x + 1 == W;
-        if (xs == 3u || row_end || i + 1 == pend) {  // a group is complete, or the row is, or the segment
-            ST *grp = out + (i - xs);                 // the group's first sample; samples gfirst .. xs of it are this segment's
-            if (xs == 3u && gfirst == 0) {
-                out4.store(grp);  // four samples: one (unaligned) store to the lane's plane
+    uint32_t out_of_range;
+    if constexpr (!RGB) {
+        out_of_range = lane8_walk_segment<RGB>(br, est, out, win, W, p0, pend, raw0, raw1, rc);
+    } else {
+        // The RGB kernel keeps the walk and the pixel step as its own text: through the shared functions the same statements came back
+        // from the compiler about 1 % slower on this instantiation, twice in two runs (profiles/lane_fold.txt), while the gray one
+        // gained.  It is lane8_walk_segment over lane8_pixel, statement for statement; the host check runs those, not this copy.
+        constexpr int LO_OK = -255, HI_OK = 255;
+        uint32_t *const myhot = est.myhot, *const tab = est.tab;
+        // pixel q of the plane as this lane may read it: its own output from p0 on, the window in front (p0 - 2 W <= q: the callers' business)
+        auto rd = [&](uint64_t q) -> int { return q >= p0 ? (int)out[q] : (int)win[2ull * W - (p0 - q)]; };
+        // (x, y) and everything derived from them alone is wave-uniform
+        uint32_t x = (uint32_t)(p0 % W), y = (uint32_t)(p0 / W);
+        // row y - 1 from column xg (a multiple of four below W) on: four samples, or the row's last one to three
+        auto load_up = [&](uint32_t xg) {
+            Four<ST> f;
+            const uint64_t q0 = (uint64_t)(y - 1) * W + xg;
+            const uint32_t cnt = min(4u, W - xg);
+            if (cnt == 4u && q0 >= p0) {
+                f.load(out + q0);
+            } else if (cnt == 4u && q0 + 4u <= p0) {
+                f.load(win + (2ull * W - (p0 - q0)));
             } else {
-                for (uint32_t k = gfirst; k <= xs; k++) grp[k] = (ST)out4.get(k);
+                f.clear();
+                for (uint32_t k = 0; k < cnt; k++) f.set(k, rd(q0 + k));
             }
-            out4.clear();
-            gfirst = 0;
+            return f;
+        };
+        int left = x >= 1 ? (int)win[2ull * W - 1] : 0, left2 = x >= 2 ? (int)win[2ull * W - 2] : 0;
+        Four<ST> up4, up4_next, out4;
+        up4.clear();
+        up4_next.clear();
+        out4.clear();
+        if (x != 0 && y > 0) {  // a start inside a row: the groups of the row above that the row's start would have asked for
+            if ((x & 3u) == 0) {
+                up4_next = load_up(x);  // (moved into up4 by the first pixel)
+            } else {
+                up4 = load_up(x & ~3u);
+                if ((x & ~3u) + 4 < W) up4_next = load_up((x & ~3u) + 4);
+            }
         }
-        if (row_end) {
-            if (rc == FELICS_OK) rc = br.failed() ? FELICS_E_IO : ((RGB ? out_of_range != 0 : out_of_range > 255u) ? FELICS_E_INVALID_VALUE : FELICS_OK);
-            x = 0;
-            y++;
-        } else {
-            x++;
+        uint32_t gfirst = x & 3u;   // first sample of the current group that is this segment's to store
+        out_of_range = 0;  // nonzero if a sample was outside LO_OK .. HI_OK
+        int first_col2 = 0;
+        for (uint64_t i = p0; i < pend; i++) {
+            const uint32_t xs = x & 3u;
+            if (x == 0 && y > 0) {
+                up4 = load_up(0);  // row above, samples 0 .. 3 (later groups are asked for four samples ahead); W >= 8
+                up4_next = load_up(4);
+                // second neighbour of a row's first pixel (misc.rs:14-23): two rows up, or above-right in row 1
+                first_col2 = y >= 2 ? rd((uint64_t)(y - 2) * W) : up4.get(1);
+            } else if (xs == 0 && y > 0) {
+                up4 = up4_next;
+                if (x + 4 < W) up4_next = load_up(x + 4);
+            }
+            int pv;
+            if (i < 2) {
+                pv = i == 0 ? raw0 : raw1;
+            } else {
+                const int above = up4.get(xs);
+                const bool row0 = y == 0, col0 = x == 0 && !row0;
+                const int v1 = col0 ? above : left;
+                const int v2 = col0 ? first_col2 : (row0 ? left2 : above);
+                const int hi = max(v1, v2), lo = min(v1, v2);
+                const uint32_t ctx = (uint32_t)(hi - lo);  // <= 255 (510): every sample kept is in range, every window sample checked
+                const bool is_hot = ctx < DEC8L_HOT;
+                const uint32_t hrow = min(ctx, DEC8L_HOT - 1u) * 3u * 64u;
+                uint32_t w01 = myhot[hrow], w23 = myhot[hrow + 64], w45 = myhot[hrow + 128];
+                br.refill();  // >= 33 valid bits: both kinds of code are read off the top 32 of them, then consumed in one go
+                const uint32_t top = (uint32_t)(br.acc >> 32);
+                const bool in_range = (top >> 31) != 0;
+                // -- in range: `1`, then the phased-in code of p - L in m or m + 1 bits (phase_in_coding.rs:86-112)
+                const uint32_t nn = ctx + 1;
+                const uint32_t m = 31u - (uint32_t)__builtin_clz(nn);
+                const uint32_t right_p = (2u << m) - nn, left_p = nn - (1u << m);
+                const uint32_t t1 = top << 1;
+                uint32_t r = (t1 >> 1) >> (31u - m);               // the m bits behind the flag
+                const uint32_t extra = (t1 >> (31u - m)) & 1u;      // the bit behind them
+                const uint32_t longer = r >= right_p ? 1u : 0u;     // the code has one more bit
+                r = longer ? (r - right_p) * 2u + right_p + extra : r;
+                uint32_t rot = r + left_p;                          // rotate_left: (r + left_p) mod n, r < n
+                rot = rot >= nn ? rot - nn : rot;
+                const int pv_in = lo + (int)rot;
+                const uint32_t bits_in = 1u + m + longer;
+                // -- out of range: `0`, above / below flag, q ones, `0`, k bits -- off the same 32 bits when it fits in them
+                const bool above_flag = ((top >> 30) & 1u) != 0;
+                if (!in_range && !is_hot) {  // (noise: a cold context's row comes from the item's table in HBM)
+                    w01 = tab[ctx * 3 + 0];
+                    w23 = tab[ctx * 3 + 1];
+                    w45 = tab[ctx * 3 + 2];
+                }
+                uint32_t S[6] = {w01 & 0xFFFFu, w01 >> 16, w23 & 0xFFFFu, w23 >> 16, w45 & 0xFFFFu, w45 >> 16};
+                // get_k: smallest counter, ties to the largest k (parameter_selection.rs:71-85)
+                const uint32_t key = min(min(min((S[0] << 3) | 7u, (S[1] << 3) | 6u), min((S[2] << 3) | 5u, (S[3] << 3) | 4u)),
+                                         min((S[4] << 3) | 3u, (S[5] << 3) | 2u));
+                const uint32_t k = 7u - (key & 7u);
+                const uint32_t t2 = top << 2;                                  // 30 bits of the stream, two zeros behind them
+                const uint32_t ones = (uint32_t)__builtin_clz(~t2);            // (<= 30: ~t2 ends in ones)
+                const bool fits = ones + 1u + k <= 30u;                        // unary part, its zero and the k bits lie inside the 30
+                uint32_t e = (ones << k) + (((t2 << (ones & 31u)) << 1 >> 1) >> (31u - k));  // k bits behind the zero (k <= 5)
+                uint32_t nbits = in_range ? bits_in : 3u + ones + k;
+                if (!in_range && !fits) {
+                    // a long code (or the end of the stream): the general reader, bit field by bit field
+                    br.take(2);
+                    const uint64_t q = br.unary0();
+                    const uint64_t e64 = (q << k) + br.get(k);
+                    e = (uint32_t)e64;
+                    if (e64 > 1024u) {  // no sample of an 8-bit plane is that far from its neighbours
+                        if (rc == FELICS_OK) rc = e64 > 0xFFFFFFFFull ? FELICS_E_VALUE_OVERFLOW : FELICS_E_INVALID_VALUE;
+                        e = 0;
+                    }
+                    nbits = 0;
+                }
+                br.acc <<= nbits;  // (nbits <= 32 < the valid bits)
+                br.navail -= nbits;
+                if (!in_range) {
+                    // update (parameter_selection.rs:49-68): add the six Rice lengths, halve when the smallest passes 1024
+                    uint32_t mn = 0xFFFFFFFFu;
+    #pragma unroll
+                    for (uint32_t kk = 0; kk < 6; kk++) {
+                        S[kk] += (e >> kk) + 1u + kk;
+                        mn = min(mn, S[kk]);
+                    }
+                    const uint32_t hsh = mn > 1024u ? 1u : 0u;
+                    w01 = (S[0] >> hsh) | ((S[1] >> hsh) << 16);
+                    w23 = (S[2] >> hsh) | ((S[3] >> hsh) << 16);
+                    w45 = (S[4] >> hsh) | ((S[5] >> hsh) << 16);
+                    if (is_hot) {
+                        myhot[hrow] = w01;
+                        myhot[hrow + 64] = w23;
+                        myhot[hrow + 128] = w45;
+                    } else {
+                        tab[ctx * 3 + 0] = w01;
+                        tab[ctx * 3 + 1] = w23;
+                        tab[ctx * 3 + 2] = w45;
+                    }
+                }
+                pv = in_range ? pv_in : (above_flag ? hi + (int)e + 1 : lo - (int)e - 1);
+            }
+            // out of LO_OK .. HI_OK: remembered and reported at the end of the row; the sample is cut into the range so that a failed
+            // lane's contexts stay inside the table
+            if (RGB) {
+                out_of_range |= (uint32_t)(pv - LO_OK) > (uint32_t)(HI_OK - LO_OK) ? 1u : 0u;
+                pv = min(max(pv, LO_OK), HI_OK);
+            } else {
+                out_of_range |= (uint32_t)pv;
+                pv &= 255;
+            }
+            out4.set(xs, pv);
+            left2 = left;
+            left = pv;
+            const bool row_end = x + 1 == W;
+            if (xs == 3u || row_end || i + 1 == pend) {  // a group is complete, or the row is, or the segment
+                ST *grp = out + (i - xs);                 // the group's first sample; samples gfirst .. xs of it are this segment's
+                if (xs == 3u && gfirst == 0) {
+                    out4.store(grp);  // four samples: one (unaligned) store to the lane's plane
+                } else {
+                    for (uint32_t k = gfirst; k <= xs; k++) grp[k] = (ST)out4.get(k);
+                }
+                out4.clear();
+                gfirst = 0;
+            }
+            if (row_end) {
+                if (rc == FELICS_OK) rc = br.failed() ? FELICS_E_IO : ((RGB ? out_of_range != 0 : out_of_range > 255u) ? FELICS_E_INVALID_VALUE : FELICS_OK);
+                x = 0;
+                y++;
+            } else {
+                x++;
+            }
         }
     }
     if (br.failed()) rc = FELICS_E_IO;  // (whatever else stopped the decoding: it was decoding padding)
-    else if (rc == FELICS_OK && (RGB ? out_of_range != 0 : out_of_range > 255u)) rc = FELICS_E_INVALID_VALUE;
+    else if (rc == FELICS_OK && lane8_bad<RGB>(out_of_range)) rc = FELICS_E_INVALID_VALUE;
     else if (rc == FELICS_OK && br.bit_pos(s) != end) rc = FELICS_E_INVALID_INDEX;  // the end check: exactly on the next checkpoint
     *my_status = rc;
 }
@@ -1695,57 +1436,6 @@ __global__ __launch_bounds__(256) void k_ycocg16_to_rgb(const int32_t *__restric
 
 namespace {
 
-template <>
-struct Four<uint16_t> {
-    uint32_t lo, hi;
-    __device__ __forceinline__ void clear() { lo = hi = 0; }
-    __device__ __forceinline__ void load(const uint16_t *p) {
-        uint32_t v[2];
-        __builtin_memcpy(v, p, 8);
-        lo = v[0];
-        hi = v[1];
-    }
-    __device__ __forceinline__ void load_n(const uint16_t *p, uint32_t n) {  // samples 0 .. n - 1 only (n < 4)
-        lo = hi = 0;
-        for (uint32_t j = 0; j < n; j++) set(j, (int)p[j]);
-    }
-    __device__ __forceinline__ void store(uint16_t *p) const {
-        const uint32_t v[2] = {lo, hi};
-        __builtin_memcpy(p, v, 8);
-    }
-    __device__ __forceinline__ int get(uint32_t j) const { return (int)((((j & 2u) ? hi : lo) >> (16u * (j & 1u))) & 0xFFFFu); }
-    __device__ __forceinline__ void set(uint32_t j, int s) {  // (0 <= s <= 65535, the field still zero)
-        const uint32_t f = (uint32_t)s << (16u * (j & 1u));
-        lo |= (j & 2u) ? 0u : f;
-        hi |= (j & 2u) ? f : 0u;
-    }
-};
-template <>
-struct Four<int32_t> {
-    uint64_t lo, hi;  // samples 0 | 1 and 2 | 3 (picked out with shifts: selects between four named dwords came back as an indexed array)
-    typedef uint32_t Quad __attribute__((ext_vector_type(4), aligned(4)));  // one 16-byte access at the samples' own alignment
-    __device__ __forceinline__ void clear() { lo = hi = 0; }
-    __device__ __forceinline__ void load(const int32_t *p) {
-        const Quad q = *reinterpret_cast<const Quad *>(p);
-        lo = (uint64_t)q.x | ((uint64_t)q.y << 32);
-        hi = (uint64_t)q.z | ((uint64_t)q.w << 32);
-    }
-    __device__ __forceinline__ void store(int32_t *p) const {
-        Quad q;
-        q.x = (uint32_t)lo;
-        q.y = (uint32_t)(lo >> 32);
-        q.z = (uint32_t)hi;
-        q.w = (uint32_t)(hi >> 32);
-        *reinterpret_cast<Quad *>(p) = q;
-    }
-    __device__ __forceinline__ int get(uint32_t j) const { return (int)(uint32_t)(((j & 2u) ? hi : lo) >> (32u * (j & 1u))); }
-    __device__ __forceinline__ void set(uint32_t j, int s) {  // (the field still zero)
-        const uint64_t f = (uint64_t)(uint32_t)s << (32u * (j & 1u));
-        lo |= (j & 2u) ? 0ull : f;
-        hi |= (j & 2u) ? f : 0ull;
-    }
-};
-
 // first row of a lane's tables in the launch's table buffer
 __device__ __forceinline__ uint64_t lane_table_row(const LaneUniform &, const LaneView &v, uint32_t np, uint32_t rows) {
     return (uint64_t)v.slot * np * rows;
@@ -1763,6 +1453,8 @@ __global__ __launch_bounds__(64) void k_decode16_lanes(const uint8_t *__restrict
                                                        uint32_t epoch0, int *__restrict__ status) {
     using ST = typename std::conditional<RGB, int32_t, uint16_t>::type;
     constexpr uint32_t NP = RGB ? 3u : 1u;
+    constexpr bool PITCHED = std::is_same<G, LanePitched>::value;
+    static_assert(!PITCHED || !RGB, "RGB lanes write planes; their views are the conversion kernel's");
     const uint32_t lane = lane_id();
     LaneView v;
     if (!lane_view(geo, lane, v)) return;
@@ -1770,17 +1462,7 @@ __global__ __launch_bounds__(64) void k_decode16_lanes(const uint8_t *__restrict
     const uint8_t *s = streams + offsets[img];
     const uint64_t slen = lens[img];
     const uint64_t npix = (uint64_t)W * H;
-    int rc = FELICS_OK;
-    if (slen < FELICS_HEADER_BYTES) {
-        rc = FELICS_E_IO;
-    } else {
-        const uint32_t w = ((uint32_t)s[6] << 24) | ((uint32_t)s[7] << 16) | ((uint32_t)s[8] << 8) | s[9];
-        const uint32_t h = ((uint32_t)s[10] << 24) | ((uint32_t)s[11] << 16) | ((uint32_t)s[12] << 8) | s[13];
-        if (s[0] != 'F' || s[1] != 'L' || s[2] != 'C' || s[3] != 'S') rc = FELICS_E_INVALID_SIGNATURE;
-        else if (s[4] > 1) rc = FELICS_E_INVALID_COLOR_TYPE;
-        else if (s[5] > 1) rc = FELICS_E_INVALID_PIXEL_DEPTH;
-        else if (s[4] != (RGB ? 1 : 0) || s[5] != 1 || w != W || h != H) rc = FELICS_E_INVALID_DIMENSIONS;
-    }
+    int rc = lane_header_check(s, slen, RGB ? 1 : 0, 1, W, H);
     if (rc != FELICS_OK) {  // nothing of this stream is decoded (its lane leaves; the others go on)
         status[img] = rc;
         return;
@@ -1788,171 +1470,17 @@ __global__ __launch_bounds__(64) void k_decode16_lanes(const uint8_t *__restrict
     LaneReader br;
     br.init(s + FELICS_HEADER_BYTES, slen - FELICS_HEADER_BYTES);
     const uint32_t rows = dec16l_rows(npix, NP);  // (wave-uniform)
-    uint4 *tab0 = table + lane_table_row(geo, v, NP, rows) * 4u;
+    LaneQuad *tab0 = reinterpret_cast<LaneQuad *>(table) + lane_table_row(geo, v, NP, rows) * 4u;
     for (uint32_t plane = 0; plane < NP; plane++) {
-    const int32_t p0 = (int32_t)br.get(32), p1 = (int32_t)br.get(32);  // compression.rs:166-167
-    if (br.failed() && rc == FELICS_OK) rc = FELICS_E_IO;
-    if (npix == 0) continue;
-    uint4 *tab = tab0 + (uint64_t)plane * rows * 4u;
-    const uint32_t epoch = epoch0 + plane;  // KEstimator::new: rows of other epochs are empty
-    ST *out = lane_plane<ST>(geo, out_base, v, NP, plane, npix);
-    // LanePitched: this lane's view; the rows lie `pitch` samples apart, and no load or store leaves [0, W) of its row -- the bytes
-    // between a row's end and the pitch are somebody else's (a neighbouring cell of a mosaic: another lane's, another wave's)
-    constexpr bool PITCHED = std::is_same<G, LanePitched>::value;
-    int64_t pitch = 0;
-    if constexpr (PITCHED) {
-        static_assert(!PITCHED || !RGB, "RGB lanes write planes; their views are the conversion kernel's");
-        const ViewRow vr = geo.views[v.slot];
-        out = reinterpret_cast<ST *>(const_cast<void *>(vr.data));
-        pitch = vr.row_stride / (int64_t)sizeof(ST);
-    }
-    const int lo_ok = (RGB && plane > 0) ? -65535 : 0, hi_ok = 65535;  // Y 0..65535, Co / Cg -65535..65535
-    int left = 0, left2 = 0;
-    Four<ST> up4, up4_next, out4;
-    up4.clear();
-    up4_next.clear();
-    out4.clear();
-    uint32_t out_of_range = 0;
-    int first_col2 = 0;
-    for (uint32_t y = 0; y < H; y++) {
-      ST *row = out + (uint64_t)y * W;
-      const ST *prow = row - W;
-      if constexpr (PITCHED) {
-          row = out + (int64_t)y * pitch;
-          prow = row - pitch;
-      }
-      if (y > 0) {
-          up4.load(prow);
-          if (4 < W) up4_next.load(prow + 4);
-          if constexpr (PITCHED)
-              first_col2 = y >= 2 ? (int)prow[-pitch] : up4.get(1);  // (W >= 8)
-          else
-              first_col2 = y >= 2 ? (int)prow[-(int64_t)W] : (W > 1 ? up4.get(1) : 0);
-      }
-      for (uint32_t x = 0; x < W; x++) {
-        const uint32_t xs = x & 3u;
-        if (xs == 0 && y > 0 && x != 0) {
-            up4 = up4_next;
-            if constexpr (PITCHED) {  // (wave-uniform: x and W) the row's last group may be short: sample by sample, never past W
-                if (x + 8 <= W) up4_next.load(prow + x + 4);
-                else if (x + 4 < W) up4_next.load_n(prow + x + 4, W - (x + 4));
-            } else if (x + 4 < W) {
-                up4_next.load(prow + x + 4);
-            }
-        }
-        int pv;
-        if (y == 0 && x < 2) {
-            pv = x == 0 ? p0 : p1;
-        } else {
-            const int above = up4.get(xs);
-            const bool row0 = y == 0, col0 = x == 0 && !row0;
-            const int v1 = col0 ? above : left;
-            const int v2 = col0 ? first_col2 : (row0 ? left2 : above);
-            const int hi = max(v1, v2), lo = min(v1, v2);
-            const uint32_t ctx = (uint32_t)(hi - lo);  // <= 131 070: every sample kept is in range
-            br.refill();  // >= 33 valid bits: both kinds of code are read off the top 32 of them where they fit
-            const uint32_t top = (uint32_t)(br.acc >> 32);
-            const bool in_range = (top >> 31) != 0;
-            // -- in range: `1`, then the phased-in code of p - L in m or m + 1 bits (phase_in_coding.rs:86-112), m <= 16
-            const uint32_t nn = ctx + 1;
-            const uint32_t m = 31u - (uint32_t)__builtin_clz(nn);
-            const uint32_t right_p = (2u << m) - nn, left_p = nn - (1u << m);
-            const uint32_t t1 = top << 1;
-            uint32_t r = (t1 >> 1) >> (31u - m);
-            const uint32_t extra = (t1 >> (31u - m)) & 1u;
-            const uint32_t longer = r >= right_p ? 1u : 0u;
-            r = longer ? (r - right_p) * 2u + right_p + extra : r;
-            uint32_t rot = r + left_p;
-            rot = rot >= nn ? rot - nn : rot;
-            pv = lo + (int)rot;
-            uint32_t nbits = 1u + m + longer;  // <= 18
-            if (!in_range) {
-                // -- out of range: `0`, above / below flag, q ones, `0`, k bits
-                const bool above_flag = ((top >> 30) & 1u) != 0;
-                uint4 q0, q1, q2, q3;
-                q0 = q1 = q2 = q3 = make_uint4(0, 0, 0, 0);
-                bool found;
-                const uint32_t at = dec16l_find(ctx, rows, epoch,
-                                                [&](uint32_t rw) {
-                                                    const uint4 *p = tab + (uint64_t)rw * 4u;
-                                                    q0 = p[0];
-                                                    q1 = p[1];
-                                                    q2 = p[2];
-                                                    q3 = p[3];
-                                                    return q3.w;
-                                                },
-                                                found);
-                const bool full = at == DEC16L_FULL;
-                if (full && rc == FELICS_OK) rc = FELICS_E_IO;  // (internal: the sizing rule admits every context a plane can use)
-                uint32_t S[15] = {q0.x, q0.y, q0.z, q0.w, q1.x, q1.y, q1.z, q1.w, q2.x, q2.y, q2.z, q2.w, q3.x, q3.y, q3.z};
-                if (!found) {
-#pragma unroll
-                    for (uint32_t kk = 0; kk < 15; kk++) S[kk] = 0;
-                }
-                // get_k: smallest counter, ties to the largest k (parameter_selection.rs:71-85)
-                uint32_t key = 0xFFFFFFFFu;
-#pragma unroll
-                for (uint32_t kk = 0; kk < 15; kk++) key = min(key, (S[kk] << 4) | (15u - kk));
-                const uint32_t k = 15u - (key & 15u);
-                const uint32_t t2 = top << 2;                        // 30 bits of the stream, two zeros behind them
-                const uint32_t ones = (uint32_t)__builtin_clz(~t2);  // (<= 30: ~t2 ends in ones)
-                uint32_t e;
-                if (ones + 1u + k <= 30u) {  // unary part, its zero and the k bits lie inside the 30
-                    e = (ones << k) + (((t2 << (ones & 31u)) << 1 >> 1) >> (31u - k));
-                    nbits = 3u + ones + k;  // <= 32 < the valid bits
-                    if (e > 262144u) {
-                        if (rc == FELICS_OK) rc = FELICS_E_INVALID_VALUE;
-                        e = 0;
-                    }
-                } else {
-                    // a long code (or the end of the stream): the general reader, bit field by bit field
-                    br.take(2);
-                    const uint64_t q = br.unary0();
-                    const uint64_t e64 = (q << k) + br.get(k);
-                    e = (uint32_t)e64;
-                    if (e64 > 262144u) {  // no sample of a 16-bit plane is that far from its neighbours
-                        if (rc == FELICS_OK) rc = e64 > 0xFFFFFFFFull ? FELICS_E_VALUE_OVERFLOW : FELICS_E_INVALID_VALUE;
-                        e = 0;
-                    }
-                    nbits = 0;
-                }
-                // update (parameter_selection.rs:49-68): add the fifteen Rice lengths, halve when the smallest passes 1024
-                uint32_t mn = 0xFFFFFFFFu;
-#pragma unroll
-                for (uint32_t kk = 0; kk < 15; kk++) {
-                    S[kk] += (e >> kk) + 1u + kk;
-                    mn = min(mn, S[kk]);
-                }
-                const uint32_t hsh = mn > 1024u ? 1u : 0u;
-                if (!full) {
-                    uint4 *p = tab + (uint64_t)at * 4u;
-                    p[0] = make_uint4(S[0] >> hsh, S[1] >> hsh, S[2] >> hsh, S[3] >> hsh);
-                    p[1] = make_uint4(S[4] >> hsh, S[5] >> hsh, S[6] >> hsh, S[7] >> hsh);
-                    p[2] = make_uint4(S[8] >> hsh, S[9] >> hsh, S[10] >> hsh, S[11] >> hsh);
-                    p[3] = make_uint4(S[12] >> hsh, S[13] >> hsh, S[14] >> hsh, dec16l_tag(epoch, ctx));
-                }
-                pv = above_flag ? hi + (int)e + 1 : lo - (int)e - 1;
-            }
-            br.acc <<= nbits;
-            br.navail -= nbits;
-        }
-        // try_into::<u16>() (Co / Cg: the estimator's context bound) would fail on anything outside lo_ok .. hi_ok: remembered and
-        // reported at the end of the row; the sample is cut into the range so that a failed stream's contexts stay below 131 071
-        out_of_range |= (uint32_t)pv - (uint32_t)lo_ok > (uint32_t)(hi_ok - lo_ok) ? 1u : 0u;  // (the raw samples are any 32 bits)
-        pv = min(max(pv, lo_ok), hi_ok);
-        out4.set(xs, pv);
-        left2 = left;
-        left = pv;
-        if (xs == 3u) {  // four samples complete: one (unaligned) store to the stream's plane
-            out4.store(row + (x - 3u));
-            out4.clear();
-        } else if (x + 1 == W) {  // the last one to three samples of a row
-            for (uint32_t j = 0; j <= xs; j++) row[(x - xs) + j] = (ST)out4.get(j);
-            out4.clear();
-        }
-      }
-      if (rc == FELICS_OK) rc = br.failed() ? FELICS_E_IO : (out_of_range ? FELICS_E_INVALID_VALUE : FELICS_OK);
-    }
+        const int32_t p0 = (int32_t)br.get(32), p1 = (int32_t)br.get(32);  // compression.rs:166-167
+        if (br.failed() && rc == FELICS_OK) rc = FELICS_E_IO;
+        if (npix == 0) continue;
+        // KEstimator::new: the plane's own table and epoch (rows of other epochs are empty); Y 0..65535, Co / Cg -65535..65535
+        Lane16Step step{tab0 + (uint64_t)plane * rows * 4u, rows, epoch0 + plane, (RGB && plane > 0) ? -65535 : 0, 65535, 0};
+        ST *out = lane_plane<ST>(geo, out_base, v, NP, plane, npix);
+        int64_t pitch = 0;
+        if constexpr (PITCHED) out = lane_pitched<ST>(geo, v, pitch);
+        lane_walk_plane<ST, PITCHED>(br, step, out, pitch, W, H, p0, p1, rc);
     }
     if (br.failed() && rc == FELICS_OK) rc = FELICS_E_IO;  // (whatever else: it was decoding padding)
     status[img] = rc;
@@ -1983,21 +1511,44 @@ hipError_t launch_decode16(hipStream_t s, const uint8_t *streams, const uint64_t
     return hipGetLastError();
 }
 
+namespace {
+
+// The lane launchers' pattern, a wave per workgroup: gray streams by `gray` straight into `pixels`; RGB streams by `rgb` into `planes`,
+// then the conversion conv().  tail: the kernel's arguments behind its output (table, [epoch0,] status).
+template <typename KG, typename GG, typename KR, typename GR, typename Conv, typename... Tail>
+hipError_t launch_lanes(hipStream_t s, const uint8_t *streams, const uint64_t *offsets, const uint64_t *lens, uint32_t nwaves, uint32_t color,
+                        KG gray, const GG &ggeo, void *pixels, KR rgb, const GR &rgeo, void *planes, Conv conv, Tail... tail) {
+    if (nwaves == 0) return hipSuccess;
+    if (!color) {
+        hipLaunchKernelGGL(gray, dim3(nwaves), dim3(64), 0, s, streams, offsets, lens, ggeo, pixels, tail...);
+        return hipGetLastError();
+    }
+    hipLaunchKernelGGL(rgb, dim3(nwaves), dim3(64), 0, s, streams, offsets, lens, rgeo, planes, tail...);
+    conv();
+    return hipGetLastError();
+}
+
+// the conversion of n same-shape RGB streams
+template <typename P, typename T>
+void launch_conv_uniform(hipStream_t s, uint32_t n, uint32_t W, uint32_t H, P *planes, T *pixels, int *status) {
+    const uint64_t npix = (uint64_t)W * H;
+    const uint32_t bx = (uint32_t)std::min<uint64_t>((npix + 255) / 256, 1024u);
+    if (!bx) return;
+    if constexpr (sizeof(T) == 1)
+        hipLaunchKernelGGL(k_ycocg8_to_rgb<ConvUniform>, dim3(bx, n), dim3(256), 0, s, planes, pixels, ConvUniform{(uint32_t)npix}, status);
+    else
+        hipLaunchKernelGGL(k_ycocg16_to_rgb<ConvUniform>, dim3(bx, n), dim3(256), 0, s, planes, pixels, ConvUniform{(uint32_t)npix}, status);
+}
+
+}  // namespace
+
 hipError_t launch_decode16_lanes(hipStream_t s, const uint8_t *streams, const uint64_t *offsets, const uint64_t *lens, uint32_t n,
                                  uint32_t W, uint32_t H, uint32_t color, uint16_t *pixels, int32_t *planes, uint32_t *table,
                                  uint32_t epoch0, int *status) {
-    if (n == 0) return hipSuccess;
-    if (!color) {
-        hipLaunchKernelGGL((k_decode16_lanes<false, LaneUniform>), dim3((n + 63) / 64), dim3(64), 0, s, streams, offsets, lens,
-                           LaneUniform{n, W, H}, (void *)pixels, reinterpret_cast<uint4 *>(table), epoch0, status);
-        return hipGetLastError();
-    }
-    hipLaunchKernelGGL((k_decode16_lanes<true, LaneUniform>), dim3((n + 63) / 64), dim3(64), 0, s, streams, offsets, lens,
-                       LaneUniform{n, W, H}, (void *)planes, reinterpret_cast<uint4 *>(table), epoch0, status);
-    const uint64_t npix = (uint64_t)W * H;
-    const uint32_t bx = (uint32_t)std::min<uint64_t>((npix + 255) / 256, 1024u);
-    if (bx) hipLaunchKernelGGL(k_ycocg16_to_rgb<ConvUniform>, dim3(bx, n), dim3(256), 0, s, planes, pixels, ConvUniform{(uint32_t)npix}, status);
-    return hipGetLastError();
+    const LaneUniform g{n, W, H};
+    return launch_lanes(s, streams, offsets, lens, (n + 63) / 64, color, k_decode16_lanes<false, LaneUniform>, g, pixels,
+                        k_decode16_lanes<true, LaneUniform>, g, planes, [&] { launch_conv_uniform(s, n, W, H, planes, pixels, status); },
+                        reinterpret_cast<uint4 *>(table), epoch0, status);
 }
 
 size_t decode8_lanes_table_bytes(uint32_t n, uint32_t color) { return (size_t)n * (color ? 3u * DEC8L_TABLE_DW_RGB : DEC8L_TABLE_DW) * 4; }
@@ -2006,18 +1557,10 @@ size_t decode8_lanes_table_bytes(uint32_t n, uint32_t color) { return (size_t)n 
 // planes (n * 3 * W * H), `pixels` the converted frames
 hipError_t launch_decode8_lanes(hipStream_t s, const uint8_t *streams, const uint64_t *offsets, const uint64_t *lens, uint32_t n,
                                 uint32_t W, uint32_t H, uint32_t color, uint8_t *pixels, int16_t *planes, uint32_t *table, int *status) {
-    if (n == 0) return hipSuccess;
-    if (!color) {
-        hipLaunchKernelGGL((k_decode8_lanes<false, LaneUniform>), dim3((n + 63) / 64), dim3(64), 0, s, streams, offsets, lens,
-                           LaneUniform{n, W, H}, (void *)pixels, table, status);
-        return hipGetLastError();
-    }
-    hipLaunchKernelGGL((k_decode8_lanes<true, LaneUniform>), dim3((n + 63) / 64), dim3(64), 0, s, streams, offsets, lens,
-                       LaneUniform{n, W, H}, (void *)planes, table, status);
-    const uint64_t npix = (uint64_t)W * H;
-    const uint32_t bx = (uint32_t)std::min<uint64_t>((npix + 255) / 256, 1024u);
-    if (bx) hipLaunchKernelGGL(k_ycocg8_to_rgb<ConvUniform>, dim3(bx, n), dim3(256), 0, s, planes, pixels, ConvUniform{(uint32_t)npix}, status);
-    return hipGetLastError();
+    const LaneUniform g{n, W, H};
+    return launch_lanes(s, streams, offsets, lens, (n + 63) / 64, color, k_decode8_lanes<false, LaneUniform>, g, pixels,
+                        k_decode8_lanes<true, LaneUniform>, g, planes, [&] { launch_conv_uniform(s, n, W, H, planes, pixels, status); }, table,
+                        status);
 }
 
 namespace {
@@ -2189,31 +1732,18 @@ hipError_t launch_decode8_rows(hipStream_t s, const uint8_t *streams, const uint
 hipError_t launch_decode8_lanes_waves(hipStream_t s, const uint8_t *streams, const uint64_t *offsets, const uint64_t *lens, const LaneWave *waves,
                                       uint32_t nwaves, const LaneSlot *slots, uint32_t color, const DecodeRow *conv, uint32_t nconv,
                                       uint64_t max_npix, uint8_t *pixels, int16_t *planes, uint32_t *table, int *status) {
-    if (nwaves == 0) return hipSuccess;
-    if (!color) {
-        hipLaunchKernelGGL((k_decode8_lanes<false, LaneMixed>), dim3(nwaves), dim3(64), 0, s, streams, offsets, lens, LaneMixed{waves, slots},
-                           (void *)pixels, table, status);
-        return hipGetLastError();
-    }
-    hipLaunchKernelGGL((k_decode8_lanes<true, LaneMixed>), dim3(nwaves), dim3(64), 0, s, streams, offsets, lens, LaneMixed{waves, slots},
-                       (void *)planes, table, status);
-    launch_conv_rows(s, conv, nconv, max_npix, planes, pixels, status);
-    return hipGetLastError();
+    const LaneMixed g{waves, slots};
+    return launch_lanes(s, streams, offsets, lens, nwaves, color, k_decode8_lanes<false, LaneMixed>, g, pixels, k_decode8_lanes<true, LaneMixed>, g,
+                        planes, [&] { launch_conv_rows(s, conv, nconv, max_npix, planes, pixels, status); }, table, status);
 }
 
 hipError_t launch_decode16_lanes_waves(hipStream_t s, const uint8_t *streams, const uint64_t *offsets, const uint64_t *lens, const LaneWave *waves,
                                        uint32_t nwaves, const LaneSlot *slots, uint32_t color, const DecodeRow *conv, uint32_t nconv,
                                        uint64_t max_npix, uint16_t *pixels, int32_t *planes, uint32_t *table, uint32_t epoch0, int *status) {
-    if (nwaves == 0) return hipSuccess;
-    if (!color) {
-        hipLaunchKernelGGL((k_decode16_lanes<false, LaneMixed>), dim3(nwaves), dim3(64), 0, s, streams, offsets, lens, LaneMixed{waves, slots},
-                           (void *)pixels, reinterpret_cast<uint4 *>(table), epoch0, status);
-        return hipGetLastError();
-    }
-    hipLaunchKernelGGL((k_decode16_lanes<true, LaneMixed>), dim3(nwaves), dim3(64), 0, s, streams, offsets, lens, LaneMixed{waves, slots},
-                       (void *)planes, reinterpret_cast<uint4 *>(table), epoch0, status);
-    launch_conv_rows(s, conv, nconv, max_npix, planes, pixels, status);
-    return hipGetLastError();
+    const LaneMixed g{waves, slots};
+    return launch_lanes(s, streams, offsets, lens, nwaves, color, k_decode16_lanes<false, LaneMixed>, g, pixels, k_decode16_lanes<true, LaneMixed>, g,
+                        planes, [&] { launch_conv_rows(s, conv, nconv, max_npix, planes, pixels, status); }, reinterpret_cast<uint4 *>(table), epoch0,
+                        status);
 }
 
 hipError_t launch_decode16_rows(hipStream_t s, const uint8_t *streams, const uint64_t *offsets, const uint64_t *lens, const DecodeRow *rows,
@@ -2327,40 +1857,27 @@ hipError_t launch_decode8_lanes_waves_views(hipStream_t s, const uint8_t *stream
                                             uint32_t nwaves, const LaneSlot *slots, uint32_t color, const DecodeRow *conv, uint32_t nconv,
                                             uint64_t max_npix, int16_t *planes, uint32_t *table, int *status, const DecodeViews &dv,
                                             const DecodeViews &cv) {
-    if (nwaves == 0) return hipSuccess;
-    if (!color) {
-        if (dv.pitched)
-            hipLaunchKernelGGL((k_decode8_lanes<false, LanePitched>), dim3(nwaves), dim3(64), 0, s, streams, offsets, lens,
-                               LanePitched{{waves, slots}, dv.views}, (void *)nullptr, table, status);
-        else
-            hipLaunchKernelGGL((k_decode8_lanes<false, LaneMixed>), dim3(nwaves), dim3(64), 0, s, streams, offsets, lens, LaneMixed{waves, slots},
-                               (void *)nullptr, table, status);
-        return hipGetLastError();
-    }
-    hipLaunchKernelGGL((k_decode8_lanes<true, LaneMixed>), dim3(nwaves), dim3(64), 0, s, streams, offsets, lens, LaneMixed{waves, slots},
-                       (void *)planes, table, status);
-    launch_conv_views<int16_t, uint8_t>(s, conv, nconv, max_npix, planes, status, cv);
-    return hipGetLastError();
+    const LaneMixed g{waves, slots};
+    const auto convert = [&] { launch_conv_views<int16_t, uint8_t>(s, conv, nconv, max_npix, planes, status, cv); };
+    if (dv.pitched)  // (gray lanes write through their views; RGB lanes write planes either way)
+        return launch_lanes(s, streams, offsets, lens, nwaves, color, k_decode8_lanes<false, LanePitched>, LanePitched{g, dv.views}, nullptr,
+                            k_decode8_lanes<true, LaneMixed>, g, planes, convert, table, status);
+    return launch_lanes(s, streams, offsets, lens, nwaves, color, k_decode8_lanes<false, LaneMixed>, g, nullptr, k_decode8_lanes<true, LaneMixed>, g,
+                        planes, convert, table, status);
 }
 
 hipError_t launch_decode16_lanes_waves_views(hipStream_t s, const uint8_t *streams, const uint64_t *offsets, const uint64_t *lens, const LaneWave *waves,
                                              uint32_t nwaves, const LaneSlot *slots, uint32_t color, const DecodeRow *conv, uint32_t nconv,
                                              uint64_t max_npix, int32_t *planes, uint32_t *table, uint32_t epoch0, int *status,
                                              const DecodeViews &dv, const DecodeViews &cv) {
-    if (nwaves == 0) return hipSuccess;
-    if (!color) {
-        if (dv.pitched)
-            hipLaunchKernelGGL((k_decode16_lanes<false, LanePitched>), dim3(nwaves), dim3(64), 0, s, streams, offsets, lens,
-                               LanePitched{{waves, slots}, dv.views}, (void *)nullptr, reinterpret_cast<uint4 *>(table), epoch0, status);
-        else
-            hipLaunchKernelGGL((k_decode16_lanes<false, LaneMixed>), dim3(nwaves), dim3(64), 0, s, streams, offsets, lens, LaneMixed{waves, slots},
-                               (void *)nullptr, reinterpret_cast<uint4 *>(table), epoch0, status);
-        return hipGetLastError();
-    }
-    hipLaunchKernelGGL((k_decode16_lanes<true, LaneMixed>), dim3(nwaves), dim3(64), 0, s, streams, offsets, lens, LaneMixed{waves, slots},
-                       (void *)planes, reinterpret_cast<uint4 *>(table), epoch0, status);
-    launch_conv_views<int32_t, uint16_t>(s, conv, nconv, max_npix, planes, status, cv);
-    return hipGetLastError();
+    const LaneMixed g{waves, slots};
+    const auto convert = [&] { launch_conv_views<int32_t, uint16_t>(s, conv, nconv, max_npix, planes, status, cv); };
+    uint4 *const tab = reinterpret_cast<uint4 *>(table);
+    if (dv.pitched)
+        return launch_lanes(s, streams, offsets, lens, nwaves, color, k_decode16_lanes<false, LanePitched>, LanePitched{g, dv.views}, nullptr,
+                            k_decode16_lanes<true, LaneMixed>, g, planes, convert, tab, epoch0, status);
+    return launch_lanes(s, streams, offsets, lens, nwaves, color, k_decode16_lanes<false, LaneMixed>, g, nullptr, k_decode16_lanes<true, LaneMixed>, g,
+                        planes, convert, tab, epoch0, status);
 }
 
 }  // namespace felics

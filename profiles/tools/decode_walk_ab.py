@@ -1,9 +1,9 @@
-"""The wave-per-stream decoders of this build against another build of the library (the parent commit's), call by call.
+"""The GPU decoders of this build, wave per stream and lane per stream, against another build of the library (the parent commit's), call by call.
 
     python profiles/tools/decode_walk_ab.py --parent-lib PARENT/libfelics.so [--parent-source HASH] [--reps 15] [--out FILE]
 
 Workloads, each one blocking decode call of well under a second, in the wave form (FELICS_TEST_DECODE_LANES=0 and
-FELICS_TEST_DECODE16_LANES=0 around the call) but for the last:
+FELICS_TEST_DECODE16_LANES=0 around the call):
   gray8     64 gray8 S1 streams of 512 x 512, felics_decompress_batch_device          k_decode8<DecUniform>
   rgb8      64 RGB8 streams of 512 x 512                                               k_decode8<DecUniform>, three planes
   gray16    64 gray16 streams of 512 x 512                                             k_decode16<DecUniform>
@@ -13,7 +13,16 @@ FELICS_TEST_DECODE16_LANES=0 around the call) but for the last:
   indexed   one 2048 x 2048 gray8 S1 stream, indexed at segment 32 768                 k_decode8_seg
   indexed_rgb  one 1024 x 1024 RGB8 stream, indexed at segment 32 768                  k_decode8_seg, three planes
   regions   64 windows of 256 x 256 at seeded positions over the `indexed` stream, felics_decompress_regions_device_indexed   k_decode8_region
-  lanes8    4 096 gray8 streams of 64 x 64 in the lane form (FELICS_TEST_DECODE_LANES=1): the control, code a change to the walk leaves alone
+and in the lane form (FELICS_TEST_DECODE_LANES=1, FELICS_TEST_DECODE16_LANES=1 or FELICS_TEST_INDEX_LANES=1 around the call) -- to a
+change of one form the other form's workloads are the control, code it leaves alone:
+  lanes8    4 096 gray8 streams of 64 x 64                                             k_decode8_lanes<false, LaneUniform>
+  lanes8_rgb   1 024 RGB8 streams of 64 x 64                                           k_decode8_lanes<true, LaneUniform>
+  lanes16   1 024 gray16 streams of 64 x 64                                            k_decode16_lanes<false, LaneUniform>
+  lanes16_rgb  512 RGB16 streams of 64 x 64                                            k_decode16_lanes<true, LaneUniform>
+  lanes8_pitched  the lanes8 streams into 64 x 64 views of pitch 80                    k_decode8_lanes<false, LanePitched>
+  lanes8_mixed    the lanes8 streams through felics_decompress_images_device           k_decode8_lanes<false, LaneMixed>
+  indexed_lanes      128 gray8 streams of 256 x 256, indexed at segment 4 096          k_decode8_seg_lanes<false>
+  indexed_lanes_rgb  128 RGB8 streams of 256 x 256, indexed at segment 4 096           k_decode8_seg_lanes<true>
 Each library is loaded in a child process of its own (FELICS_LIB_PATH); the parent process never opens the GPU and asks the two
 children for one call at a time, seat a then seat b, workload after workload, --reps rounds after two warm-up rounds.  A time is
 what two device events around the blocking call measure, in milliseconds; medians with min .. max.  Every child compares what its
@@ -30,9 +39,12 @@ import subprocess
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-WORKLOADS = ("gray8", "rgb8", "gray16", "rgb16", "pitched8", "mixed8", "indexed", "indexed_rgb", "regions", "lanes8")
+WORKLOADS = ("gray8", "rgb8", "gray16", "rgb16", "pitched8", "mixed8", "indexed", "indexed_rgb", "regions", "lanes8", "lanes8_rgb", "lanes16",
+             "lanes16_rgb", "lanes8_pitched", "lanes8_mixed", "indexed_lanes", "indexed_lanes_rgb")
 SEGMENT = 32768
 PITCH = 576
+LANE_SEGMENT = 4096
+LANE_PITCH = 80
 
 
 def child():
@@ -74,29 +86,38 @@ def child():
     small = np.stack([synth.gray8(64, 64, f, "S1") for f in range(4096)])
     sets = {"gray8": encode(g8, 512, 512, 0, 0), "rgb8": encode(c8, 512, 512, 1, 0), "gray16": encode(g16, 512, 512, 0, 1),
             "rgb16": encode(c16, 256, 256, 1, 1), "indexed": encode(big, 2048, 2048, 0, 0, SEGMENT),
-            "indexed_rgb": encode(bigc, 1024, 1024, 1, 0, SEGMENT), "lanes8": encode(small, 64, 64, 0, 0)}
+            "indexed_rgb": encode(bigc, 1024, 1024, 1, 0, SEGMENT), "lanes8": encode(small, 64, 64, 0, 0),
+            "lanes8_rgb": encode(np.stack([synth.rgb8(64, 64, f) for f in range(1024)]), 64, 64, 1, 0),
+            "lanes16": encode(np.stack([synth.gray16(64, 64, f) for f in range(1024)]), 64, 64, 0, 1),
+            "lanes16_rgb": encode(np.stack([np.stack([synth.gray16(64, 64, 3 * f + c) for c in range(3)], axis=-1) for f in range(512)]), 64, 64, 1, 1),
+            "indexed_lanes": encode(np.stack([synth.gray8(256, 256, f, "S1") for f in range(128)]), 256, 256, 0, 0, LANE_SEGMENT),
+            "indexed_lanes_rgb": encode(np.stack([synth.rgb8(256, 256, f) for f in range(128)]), 256, 256, 1, 0, LANE_SEGMENT)}
     sets["pitched8"] = sets["mixed8"] = sets["gray8"]
+    sets["lanes8_pitched"] = sets["lanes8_mixed"] = sets["lanes8"]
     sets["regions"] = sets["indexed"]
     want = {k: v[0].cpu().numpy().view(np.uint8).reshape(-1) for k, v in sets.items()}
     want["regions"] = np.concatenate([big[0, y:y + h, x:x + w].reshape(-1) for _, x, y, w, h in windows])
-    dest = {k: torch.zeros(len(v), dtype=torch.uint8, device="cuda") for k, v in want.items() if k != "pitched8"}
-    mosaic = torch.zeros((64, 512, PITCH), dtype=torch.uint8, device="cuda")
-    views = [mosaic[i, :, :512] for i in range(64)]
+    mosaics = {"pitched8": torch.zeros((64, 512, PITCH), dtype=torch.uint8, device="cuda"),
+               "lanes8_pitched": torch.zeros((4096, 64, LANE_PITCH), dtype=torch.uint8, device="cuda")}
+    views = {"pitched8": [mosaics["pitched8"][i, :, :512] for i in range(64)],
+             "lanes8_pitched": [mosaics["lanes8_pitched"][i, :, :64] for i in range(4096)]}
+    dest = {k: torch.zeros(len(v), dtype=torch.uint8, device="cuda") for k, v in want.items() if k not in mosaics}
 
     def decoded(name):  # the bytes a call of `name` wrote, as the frames lie
-        return mosaic[:, :, :512].contiguous().view(-1) if name == "pitched8" else dest[name]
+        return mosaics[name][:, :, :views[name][0].shape[1]].contiguous().view(-1) if name in mosaics else dest[name]
 
     def call(name):
         s = sets[name]
-        os.environ["FELICS_TEST_DECODE_LANES"] = "1" if name == "lanes8" else "0"  # (read per call)
-        os.environ["FELICS_TEST_DECODE16_LANES"] = "0"
-        if name == "pitched8":
-            enc.decompress_arrays_device(s[1].data_ptr(), s[2], s[3], views)
-        elif name == "mixed8":
+        os.environ["FELICS_TEST_DECODE_LANES"] = "1" if name.startswith("lanes8") else "0"  # (read per call)
+        os.environ["FELICS_TEST_DECODE16_LANES"] = "1" if name.startswith("lanes16") else "0"
+        os.environ["FELICS_TEST_INDEX_LANES"] = "1" if name.startswith("indexed_lanes") else "0"
+        if name in mosaics:
+            enc.decompress_arrays_device(s[1].data_ptr(), s[2], s[3], views[name])
+        elif name in ("mixed8", "lanes8_mixed"):
             enc.decompress_images_device(s[1].data_ptr(), s[2], s[3], dest[name].data_ptr(), dest[name].numel())
         elif name == "regions":
             enc.decompress_regions_device_indexed(s[1].data_ptr(), s[2], s[3], s[4].data_ptr(), s[5], windows, dest[name].data_ptr(), dest[name].numel())
-        elif name in ("indexed", "indexed_rgb"):
+        elif name.startswith("indexed"):
             enc.decompress_batch_device_indexed(s[1].data_ptr(), s[2], s[3], s[4].data_ptr(), s[5], dest[name].data_ptr(), dest[name].numel())
         else:
             enc.decompress_batch_device(s[1].data_ptr(), s[2], s[3], dest[name].data_ptr(), dest[name].numel())
@@ -217,7 +238,7 @@ def main():
         margin[w] = abs(ma - mb) / min(ma, mb)
         good = info[0][w]["ok"] == "1" and info[1][w]["ok"] == "1"
         ok = ok and good
-        say("  %-11s a %s  b %s  margin %.4f %%  pixels %s" % (w, fmt(same_ts[w][0]), fmt(same_ts[w][1]), 100 * margin[w], "ok" if good else "WRONG"))
+        say("  %-17s a %s  b %s  margin %.4f %%  pixels %s" % (w, fmt(same_ts[w][0]), fmt(same_ts[w][1]), 100 * margin[w], "ok" if good else "WRONG"))
     ts, ready, info = protocol(a.parent_lib, None, a.reps)
     say("run 2, seat a = the parent's library, seat b = this build (library sha256 %s...):" % ready[1][1])
     for w in WORKLOADS:
@@ -225,7 +246,7 @@ def main():
         good = info[1][w]["ok"] == "1" and info[0][w]["sha"] == info[1][w]["sha"]
         within = mb <= ma * (1 + margin[w])
         ok = ok and good and within
-        say("  %-11s parent %s  this %s  this / parent - 1 = %+.4f %%  (margin %.4f %%): %s; pixels %s"
+        say("  %-17s parent %s  this %s  this / parent - 1 = %+.4f %%  (margin %.4f %%): %s; pixels %s"
             % (w, fmt(ts[w][0]), fmt(ts[w][1]), 100 * (mb / ma - 1), 100 * margin[w], "within" if within else "EXCEEDS", "identical" if good else "DIFFER"))
     say("verdict: %s" % ("every workload within its margin, pixels identical" if ok else "MISSED (see above)"))
     if a.out:

@@ -15,13 +15,17 @@ F="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -Wall -Wextra -Wno-unused-paramete
 cd "$SRC/felics_amd/csrc"
 KERNELS="felics_kernels felics_wide felics_gpudecode"
 [ -f felics_chain.hip ] && KERNELS="$KERNELS felics_chain"   # (round 5 on; an older checkout has no such file)
+[ -f felics_index.hip ] && KERNELS="$KERNELS felics_index"   # (the restart index's encoder side)
 OBJS=""
 for f in $KERNELS; do hipcc $F -c $f.hip -o "$O/$f.o" & OBJS="$OBJS $O/$f.o"; done
 HOST="felics_context felics_encode felics_mixed felics_decode_device"
 [ -f felics_api.cpp ] && HOST="felics_api"   # (a checkout from before the host pipeline was split into files)
 for f in $HOST; do hipcc $F -x hip -c $f.cpp -o "$O/$f.o" & OBJS="$OBJS $O/$f.o"; done
 hipcc -O3 -std=c++17 -fPIC -c felics_decode.cpp -o "$O/felics_decode.o" &
+OBJS="$OBJS $O/felics_decode.o"
+# (the restart index's host side; its object must not take felics_index.hip's name)
+[ -f felics_index.cpp ] && { hipcc -O3 -std=c++17 -fPIC -c felics_index.cpp -o "$O/felics_index_host.o" & OBJS="$OBJS $O/felics_index_host.o"; }
 wait
-hipcc --offload-arch=gfx950 -shared -o "$O/libfelics.so" $OBJS "$O"/felics_decode.o -Wl,-rpath,/opt/rocm/lib
+hipcc --offload-arch=gfx950 -shared -Wl,--no-undefined -o "$O/libfelics.so" $OBJS -L/opt/rocm/lib -lamdhip64 -Wl,-rpath,/opt/rocm/lib
 rm -f "$O"/*.o
 ls -la "$O/libfelics.so"
