@@ -187,6 +187,7 @@ __device__ __forceinline__ uint32_t bitop3(uint32_t a, uint32_t b, uint32_t c) {
 constexpr uint32_t BT_SEL = 0xE4;      // c ? a : b  =  (a & c) | (b & ~c)
 constexpr uint32_t BT_OR_ANDN = 0xF4;  // a | (b & ~c)
 constexpr uint32_t BT_ANDN = 0x30;     // a & ~b
+constexpr uint32_t BT_OR3 = 0xFE;      // a | b | c
 __device__ __forceinline__ uint32_t min_u16(uint32_t a, uint32_t b) {  // operands < 2^16
     uint32_t r;
     asm("v_min_u16 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
@@ -1230,11 +1231,36 @@ struct FusedLDS {
 #ifdef FELICS_PACK_STAMPS
     unsigned long long t_last, t_acc[12];
 #endif
-    uint32_t win[FUSED_WIN_WORDS + 2];  // (+ 1: the second word of a code that starts in the window's last word)
+    alignas(16) uint32_t win[FUSED_WIN_WORDS + 2];  // (+ 1: the second word of a code that starts in the window's last word)
     uint32_t wsum[PACK_THREADS / 64];
     uint64_t tile_lo_sh;
     uint32_t ticket_sh;
 };
+
+// Zeroes the bit window.  WIDE: 16-byte stores, and the two words behind the last of them.
+template <bool WIDE>
+__device__ __forceinline__ void clear_window(uint32_t (&win)[FUSED_WIN_WORDS + 2]) {
+    if constexpr (WIDE) {
+        static_assert(FUSED_WIN_WORDS % (4 * PACK_THREADS) == 0, "whole rounds of 16-byte stores");
+#pragma unroll
+        for (uint32_t u = 0; u < FUSED_WIN_WORDS / (4 * PACK_THREADS); u++) reinterpret_cast<uint4 *>(win)[threadIdx.x + u * PACK_THREADS] = make_uint4(0u, 0u, 0u, 0u);
+        if (threadIdx.x < 2) win[FUSED_WIN_WORDS + threadIdx.x] = 0;
+    } else {
+        for (uint32_t j = threadIdx.x; j < FUSED_WIN_WORDS + 2; j += PACK_THREADS) win[j] = 0;
+    }
+}
+
+// What of k_pack_t's placement and flush an instantiation takes, by its sample type.  The 8-bit kernels take all three: a quad of
+// codes per window OR (PACK_QUADS), a flush of only the words the tile holds (PACK_SHORT_FLUSH), the window cleared with 16-byte stores
+// (PACK_WIDE_CLEAR).  The int16 kernels (the Y / Co / Cg planes of RGB8) hold eight more registers of samples at the 80-register cap:
+// each of the three moved spill code into their code phase and among their window ORs, and their step was 2 % slower
+// (profiles/pack_words.txt); they place code by code, walk the whole window and clear it word by word.
+#ifndef FELICS_PACK16_PARTS
+#define FELICS_PACK16_PARTS 0  // (bit 0: quads, bit 1: the short flush, bit 2: the wide clearing; A/B builds: profiles/tools/variant.sh)
+#endif
+template <typename T> constexpr bool PACK_QUADS = sizeof(T) == 1 || (FELICS_PACK16_PARTS & 1) != 0;
+template <typename T> constexpr bool PACK_SHORT_FLUSH = sizeof(T) == 1 || (FELICS_PACK16_PARTS & 2) != 0;
+template <typename T> constexpr bool PACK_WIDE_CLEAR = sizeof(T) == 1 || (FELICS_PACK16_PARTS & 4) != 0;
 
 // Whether this thread's 16-pixel group takes the branch-free path (group_codes), and what that path needs from outside the
 // tile's LDS image: the position of the group's first-column pixel (PACK_PER_THREAD: none) and that pixel's second neighbour
@@ -1769,8 +1795,11 @@ __device__ __forceinline__ void pack_tile_fused(const GroupSamples<T> &gsm, cons
         const uint32_t hi = min(nwords - (last_shared ? 1u : 0u), limit_rel);
         const uint32_t span = hi > lo ? hi - lo : 0u;
         auto word = [&](uint32_t j) { return __builtin_amdgcn_alignbit(j ? win[j - 1] : 0u, win[j], s); };  // (s = 0: win[j])
+        // (only the rounds whose words the tile holds -- an S1 tile fills a quarter of the window; the count is the same for every thread)
+        const uint32_t held = PACK_SHORT_FLUSH<T> ? (uint32_t)__builtin_amdgcn_readfirstlane((int)min(nwords - wb, FUSED_WIN_WORDS)) : FUSED_WIN_WORDS;
 #pragma unroll
         for (uint32_t u = 0; u < FUSED_WIN_WORDS / PACK_THREADS; u++) {
+            if (u * PACK_THREADS >= held) break;
             const uint32_t j = threadIdx.x + u * PACK_THREADS, r = wb + j;  // word r of the tile
             if (r - lo < span) out_rel[r] = __builtin_bswap32(word(j));
         }
@@ -1785,16 +1814,31 @@ __device__ __forceinline__ void pack_tile_fused(const GroupSamples<T> &gsm, cons
         // from other tiles, so the look-back comes behind it, when the tiles in front have long published.  Code j at bit `at`:
         // its upper part into word at >> 5, what is left of it into the next word (zero if the code ends in the first one; an
         // LDS OR of zero is cheaper than a branch around it).
+        // Four codes at a time: a quad of at most 32 bits (an S1 tile has 3.8 bits per pixel) is strung together in a register --
+        // every code is left-aligned with zeros below its length -- and placed like one code; a longer quad code by code.
         if (in_registers) {
             uint32_t at = my_rel;
             char *wbytes = reinterpret_cast<char *>(win);
-#pragma unroll
-            for (uint32_t j = 0; j < PACK_PER_THREAD; j++) {
-                const uint32_t hi = c32[j] >> (at & 31u), lo = __builtin_amdgcn_alignbit(c32[j], 0u, at & 31u);
-                uint32_t *w2 = reinterpret_cast<uint32_t *>(wbytes + ((at >> 3) & ~3u));
+            auto place = [&](uint32_t c, uint32_t pos) {
+                const uint32_t hi = c >> (pos & 31u), lo = __builtin_amdgcn_alignbit(c, 0u, pos & 31u);
+                uint32_t *w2 = reinterpret_cast<uint32_t *>(wbytes + ((pos >> 3) & ~3u));
                 atomicOr(w2, hi);
                 atomicOr(w2 + 1, lo);
-                at += len[j];
+            };
+#pragma unroll
+            for (uint32_t q = 0; q < PACK_PER_THREAD; q += 4) {
+                const uint32_t l1 = len[q] + len[q + 1], l2 = l1 + len[q + 2], l3 = l2 + len[q + 3];
+                // (every code of a fast group has at least one bit -- the group lies inside the plane, and a pixel costs a bit or more --
+                // so l3 <= 32 leaves len[q], l1, l2 <= 31: no shift by 32 below)
+                if (PACK_QUADS<T> && l3 <= 32u) {
+                    place(bitop3<BT_OR3>(bitop3<BT_OR3>(c32[q], c32[q + 1] >> len[q], c32[q + 2] >> l1), c32[q + 3] >> l2, 0u), at);
+                } else {
+                    place(c32[q], at);
+                    place(c32[q + 1], at + len[q]);
+                    place(c32[q + 2], at + l1);
+                    place(c32[q + 3], at + l2);
+                }
+                at += l3;
             }
         }
         if (!in_registers && bits != 0) general_group_place<T, PO_OF(FA)>(words, pl, general, win, FUSED_WIN_WORDS, 0, my_rel);
@@ -1819,7 +1863,7 @@ __device__ __forceinline__ void pack_tile_fused(const GroupSamples<T> &gsm, cons
         for (uint32_t wb = 0; wb < nwords; wb += FUSED_WIN_WORDS) {
             if (wb != 0) {  // (the first window arrives cleared)
                 __syncthreads();
-                for (uint32_t j = threadIdx.x; j < FUSED_WIN_WORDS + 2; j += PACK_THREADS) win[j] = 0;
+                clear_window<PACK_WIDE_CLEAR<T>>(win);
                 __syncthreads();
             }
             if (bits != 0 && my_last >= wb && my_first < wb + FUSED_WIN_WORDS)
@@ -1907,7 +1951,7 @@ __attribute__((amdgpu_waves_per_eu(FELICS_PACK_WAVES))) __global__ __launch_boun
         gg = group_geometry<T>(pl, st, view.W, view.npix);
         if (gg.fast) load_group(pl, st * PACK_TILE + threadIdx.x * PACK_PER_THREAD, view.W, gsm);
     }
-    for (uint32_t j = threadIdx.x; j < FUSED_WIN_WORDS + 2; j += PACK_THREADS) fl.win[j] = 0;  // the bit window (barrier: behind the gather)
+    clear_window<PACK_WIDE_CLEAR<T>>(fl.win);  // the bit window (barrier: behind the gather)
     const uint8_t *ksrc = ts.kq + pt * ts.cap;
     const uint16_t *psrc = ts.pix + pt * ts.cap;
     constexpr uint32_t GR = 3;  // rounds in flight together: 3072 slots
