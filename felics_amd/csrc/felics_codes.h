@@ -5,6 +5,7 @@
 #pragma once
 
 #include "felics_device.h"
+#include "felics_epochs.h"
 #include "felics_kernels.h"
 
 namespace felics {
@@ -229,7 +230,7 @@ __device__ __forceinline__ uint32_t *plane_words(const PitchedOut &po, uint32_t 
 
 constexpr uint32_t ST_AGGREGATE = 1, ST_PREFIX = 2;
 constexpr uint32_t ST_VALUE_BITS = 44;        // bits of a plane fit: < 2^32 pixels x < 2^10 bits
-constexpr uint32_t ST_EPOCH_MASK = 0x3FFFFu;  // 18 bits of the lane's epoch (status is cleared when they wrap)
+constexpr uint32_t ST_EPOCH_MASK = LOOKBACK_EPOCH_MASK;  // 18 bits of the lane's epoch (status is cleared when they wrap: felics_epochs.h)
 constexpr uint32_t LOOKBACK_SPIN_LIMIT = 1u << 19;  // polls of >= 1 us each: gives up after about a second
 
 __device__ __forceinline__ uint64_t status_word(uint32_t epoch, uint32_t state, uint64_t value) {

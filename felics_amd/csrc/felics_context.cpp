@@ -176,9 +176,17 @@ int felics_ctx_create(int device, felics_ctx **out) {
     ctx->assign_on = ctx->nlanes > 3 ? ASSIGN_FRONT : ASSIGN_OWN;
     if (const char *e = getenv("FELICS_ASSIGN_STREAM")) ctx->assign_on = !strcmp(e, "tail") ? ASSIGN_TAIL : !strcmp(e, "front") ? ASSIGN_FRONT : ASSIGN_OWN;
     ctx->test_timeout = getenv("FELICS_TEST_TIMEOUT") != nullptr;
+    // (tests of the epoch wraps, felics_epochs.h: the LAST epoch each counter pretends to have handed out when its buffer is fresh --
+    // a lane's look-back status, dec_table, dec_lane16_table -- so that a few calls reach a wrap that is days or thousands of calls away)
+    if (const char *e = getenv("FELICS_TEST_LOOKBACK_EPOCH"))
+        for (Lane &l : ctx->lanes) l.epoch = (uint32_t)strtoull(e, nullptr, 0);
+    if (const char *e = getenv("FELICS_TEST_DECODE16_EPOCH")) ctx->dec_epoch = ctx->dec_epoch_start = (uint32_t)strtoull(e, nullptr, 0);
+    if (const char *e = getenv("FELICS_TEST_DECODE16_LANES_EPOCH"))
+        ctx->dec_lane16_epoch = ctx->dec_lane16_epoch_start = (uint32_t)std::min<unsigned long long>(strtoull(e, nullptr, 0), DEC16L_EPOCH_MAX);
     if (const char *e = getenv("FELICS_SLICES")) ctx->slices_blocking = std::max(1, std::min(atoi(e), SLICES));
     if (const char *e = getenv("FELICS_SLICES_QUEUED")) ctx->slices_queued = std::max(1, std::min(atoi(e), SLICES));  // (tuning sweeps: profiles/tools/sweep_queue.sh)
     ctx->trace = getenv("FELICS_TRACE") != nullptr;
+    ctx->trace_epochs = getenv("FELICS_TRACE_EPOCHS") != nullptr;
     if (const char *e = getenv("FELICS_TIMEOUT_S")) ctx->timeout_s = std::max(1, atoi(e));
     bool ok = hipSetDevice(device) == hipSuccess;
     // Oldest work first: the spine (the one sequential chain) and the tail, which finishes the submission that is

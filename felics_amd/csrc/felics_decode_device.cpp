@@ -37,7 +37,7 @@ int dec16_tables(felics_ctx *ctx, size_t n, size_t &per) {
         per = std::max<size_t>(1, std::min(per, (free_b / 4 + ctx->dec_table.cap) / decode16_table_bytes(1)));
     for (;;) {
         const size_t table_bytes = decode16_table_bytes((uint32_t)per);
-        if (table_bytes > ctx->dec_table.cap) ctx->dec_epoch = 0;  // a fresh (zeroed) buffer: epochs start over
+        if (table_bytes > ctx->dec_table.cap) ctx->dec_epoch = ctx->dec_epoch_start;  // a fresh (zeroed) buffer: epochs start over
         const int rc = reserve_zeroed(ctx, ctx->dec_table, table_bytes);
         if (rc == 0) return FELICS_OK;
         (void)hipGetLastError();
@@ -48,12 +48,11 @@ int dec16_tables(felics_ctx *ctx, size_t n, size_t &per) {
 
 // the first of the three epochs (one per plane) of the next pass on stream s
 int dec16_epoch(felics_ctx *ctx, hipStream_t s, uint32_t &epoch0) {
-    if (ctx->dec_epoch > 0xFFFFFFF0u) {  // epochs used up: clear the tables, start over
-        HIP_TRY(ctx, hipMemsetAsync(ctx->dec_table.p, 0, ctx->dec_table.cap, s));
-        ctx->dec_epoch = 0;
-    }
-    epoch0 = ctx->dec_epoch + 1;
-    ctx->dec_epoch += 3;
+    const EpochStep e = dec16_epoch_next(ctx->dec_epoch);  // (felics_epochs.h)
+    if (e.clear) HIP_TRY(ctx, hipMemsetAsync(ctx->dec_table.p, 0, ctx->dec_table.cap, s));  // epochs used up: clear the tables, start over
+    epoch0 = e.epoch;
+    ctx->dec_epoch = e.epoch + 2;
+    if (ctx->trace_epochs) fprintf(stderr, "[felics] decode16 epoch 0x%x clear %d\n", e.epoch, (int)e.clear);
     return FELICS_OK;
 }
 
@@ -82,7 +81,7 @@ int dec16_lanes_tables(felics_ctx *ctx, size_t want, size_t least, size_t &bytes
     if (hipMemGetInfo(&free_b, &total_b) == hipSuccess && ctx->dec_lane16_table.cap < bytes)
         bytes = std::max(least, std::min(bytes, std::max(ctx->dec_lane16_table.cap, (free_b + ctx->dec_lane16_table.cap) / 4)));
     for (;;) {
-        if (bytes > ctx->dec_lane16_table.cap) ctx->dec_lane16_epoch = 0;  // a fresh (zeroed) buffer: epochs start over
+        if (bytes > ctx->dec_lane16_table.cap) ctx->dec_lane16_epoch = ctx->dec_lane16_epoch_start;  // a fresh (zeroed) buffer: epochs start over
         const int rc = reserve_zeroed(ctx, ctx->dec_lane16_table, bytes);
         if (rc == 0) return FELICS_OK;
         (void)hipGetLastError();
@@ -93,12 +92,11 @@ int dec16_lanes_tables(felics_ctx *ctx, size_t want, size_t least, size_t &bytes
 
 // the first of the three epochs (one per plane) of the next lane-form launch on stream s
 int dec16_lanes_epoch(felics_ctx *ctx, hipStream_t s, uint32_t &epoch0) {
-    if (ctx->dec_lane16_epoch + 3 > DEC16L_EPOCH_MAX) {  // epochs used up: clear the tables, start over
-        HIP_TRY(ctx, hipMemsetAsync(ctx->dec_lane16_table.p, 0, ctx->dec_lane16_table.cap, s));
-        ctx->dec_lane16_epoch = 0;
-    }
-    epoch0 = ctx->dec_lane16_epoch + 1;
-    ctx->dec_lane16_epoch += 3;
+    const EpochStep e = dec16_lanes_epoch_next(ctx->dec_lane16_epoch);  // (felics_epochs.h)
+    if (e.clear) HIP_TRY(ctx, hipMemsetAsync(ctx->dec_lane16_table.p, 0, ctx->dec_lane16_table.cap, s));  // epochs used up: clear the tables, start over
+    epoch0 = e.epoch;
+    ctx->dec_lane16_epoch = e.epoch + 2;
+    if (ctx->trace_epochs) fprintf(stderr, "[felics] decode16 lanes epoch 0x%x clear %d\n", e.epoch, (int)e.clear);
     return FELICS_OK;
 }
 

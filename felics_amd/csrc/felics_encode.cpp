@@ -74,9 +74,10 @@ int run_lane(felics_ctx *ctx, Lane &l, uint8_t *d_out, uint64_t slot_stride) {
     auto *plane_carry = (uint64_t *)(block + o_sums);
     auto *plane_base = plane_carry + g.nplanes;
     l.plane_base = plane_base;
-    if (++l.epoch >= 0x03FFFFFFu) l.epoch = 1;
-    if ((l.epoch & 0x3FFFFu) == 0) HIP_TRY(ctx, hipMemsetAsync(l.status.p, 0, l.status.cap, f));  // look-back tags: 18 epoch bits
-    const uint32_t epoch = l.epoch;
+    const EpochStep tag = lookback_epoch_next(l.epoch);  // look-back tags: 18 epoch bits, cleared in front of the front kernel when they wrap (felics_epochs.h)
+    if (tag.clear) HIP_TRY(ctx, hipMemsetAsync(l.status.p, 0, l.status.cap, f));
+    const uint32_t epoch = l.epoch = tag.epoch;
+    if (ctx->trace_epochs) fprintf(stderr, "[felics] look-back lane %d epoch 0x%x clear %d\n", (int)(&l - ctx->lanes), epoch, (int)tag.clear);
     PackTarget target{d_out, slot_stride, nullptr, 0};
     if (fused && g.planes_per_image > 1) {
         target.plane_slot = ((uint64_t)g.npix + g.npix / 4 + 64 + 15) & ~15ull;

@@ -17,6 +17,7 @@
 #include <vector>
 
 #include "../../include/felics.h"
+#include "felics_epochs.h"
 #include "felics_kernels.h"
 
 using namespace felics;
@@ -88,7 +89,7 @@ struct Lane {
         tile_bits, tile_bitoff, plane_sums, image_bytes, image_off, partial, status, edge_first, edge_last, pscratch;
     uint64_t *plane_base = nullptr;   // the sub-batch's plane bases (behind its plane carries; pack_exact reads them)
     DevBuf wrecs[2], wtile_cnt, wmeta, whist, wdigtot, heads, wlong;  // 16-bit samples: event records (sort double buffer), tile counts, plane ranges, digit histograms, chain heads
-    uint32_t epoch = 0;               // sub-batches this lane has run: block tags are (epoch, slice)
+    uint32_t epoch = 0;               // 8-bit sub-batches this lane has run (FELICS_TEST_LOOKBACK_EPOCH: plus a start value): its low 18 bits tag the look-back status words (felics_epochs.h)
     // the submission in flight on this lane (felics_submit_batch_device .. felics_wait_batch)
     bool pending = false;
     bool finished = false;            // it took the synchronous path: results are in r_off / r_len / r_rc
@@ -156,6 +157,7 @@ struct felics_ctx {
     bool test_scatter_order = false; // FELICS_TEST_SCATTER_ORDER=1: k_front reports a violation whatever it produced (tests)
     bool poison = false;        // FELICS_POISON=1: overwrite the workspace before every sub-batch (tests)
     bool trace = false;         // FELICS_TRACE=1: synchronise and report after every stage (debugging)
+    bool trace_epochs = false;  // FELICS_TRACE_EPOCHS=1: a line on stderr for every epoch handed out (felics_epochs.h) and whether it clears; nothing is synchronised (tests)
     int timeout_s = 120;        // FELICS_TIMEOUT_S: give up waiting for a submission after this long
     // A wait for the GPU timed out: kernels of this context may still be running (or never return), so nothing
     // of it may be reused or freed.  Every later call fails with FELICS_E_HIP; the caller should exit (or run
@@ -190,8 +192,10 @@ struct felics_ctx {
     DevBuf dec_lane_table;        // gray streams decoded 64 to a wave: the estimator rows that do not fit in LDS (3 KB per stream, zeroed per call)
     DevBuf dec_table;             // 16-bit streams: estimator tables in HBM (8.4 MB per stream of a pass), zeroed once, rows tagged with an epoch
     uint32_t dec_epoch = 0;       // last epoch handed out (three per call: one per plane)
+    uint32_t dec_epoch_start = 0; // what dec_epoch starts from on a fresh (zeroed) dec_table: 0, or FELICS_TEST_DECODE16_EPOCH (tests: close to the wrap)
     DevBuf dec_lane16_table;      // 16-bit streams decoded 64 to a wave: their hashed estimator tables (felics_lanetable.h), zeroed once, rows tagged with an epoch
     uint32_t dec_lane16_epoch = 0;  // last epoch handed out on dec_lane16_table (three per launch, 1 .. DEC16L_EPOCH_MAX)
+    uint32_t dec_lane16_epoch_start = 0;  // what it starts from on a fresh (zeroed) table: 0, or FELICS_TEST_DECODE16_LANES_EPOCH (tests; at most DEC16L_EPOCH_MAX)
     felics_decode_stats dstats = {};  // felics_get_decode_stats
     // felics_decompress_views_device: view_ready is its ready event too (every stream waits for it before it first reads a stream byte
     // or writes a view: wait_ready), view_stage holds the dense frames of its scattered class, dvstats the counts of

@@ -126,8 +126,10 @@ static int walk8(const uint8_t *bytes, size_t len, uint32_t W, uint32_t H, int64
     if (br.failed() && rc == FELICS_OK) rc = FELICS_E_IO;
     return rc;
 }
+// (kept: a table that outlives the call, as a slot's rows of dec_lane16_table outlive a launch, and the first of the call's epochs --
+// otherwise every plane gets zeroed rows of its own)
 template <bool RGB, bool PITCHED, typename ST, typename PlaneAt>
-static int walk16(const uint8_t *bytes, size_t len, uint32_t W, uint32_t H, int64_t pitch, PlaneAt plane) {
+static int walk16(const uint8_t *bytes, size_t len, uint32_t W, uint32_t H, int64_t pitch, PlaneAt plane, LaneQuad *kept = nullptr, uint32_t epoch0 = 7) {
     const StreamCopy sc(bytes, len);
     int rc = FELICS_OK;
     LaneReader br;
@@ -136,8 +138,8 @@ static int walk16(const uint8_t *bytes, size_t len, uint32_t W, uint32_t H, int6
     for (uint32_t c = 0; c < (RGB ? 3u : 1u); c++) {
         const int32_t p0 = (int32_t)br.get(32), p1 = (int32_t)br.get(32);
         if (br.failed() && rc == FELICS_OK) rc = FELICS_E_IO;
-        const std::unique_ptr<LaneQuad[]> tab(new LaneQuad[(size_t)rows * 4]());
-        Lane16Step step{tab.get(), rows, 7u + c, (RGB && c > 0) ? -65535 : 0, 65535, 0};
+        const std::unique_ptr<LaneQuad[]> tab(new LaneQuad[kept ? 0 : (size_t)rows * 4]());
+        Lane16Step step{kept ? kept + (size_t)c * rows * 4 : tab.get(), rows, epoch0 + c, (RGB && c > 0) ? -65535 : 0, 65535, 0};
         lane_walk_plane<ST, PITCHED>(br, step, plane(c), pitch, W, H, p0, p1, rc);
     }
     if (br.failed() && rc == FELICS_OK) rc = FELICS_E_IO;
@@ -365,11 +367,115 @@ static void damage() {
     if (host_ok_flips == flips) FAIL("damage: no flip fails on the host: another seed is needed");
 }
 
+// The rows a launch leaves are another launch's only while the epochs differ or a clear lies between (felics_epochs.h): 8 x 8 gray16
+// frames whose samples are a few widely spaced values -- every pixel out of range, the same few contexts again and again, large
+// errors -- decoded into the rows ANOTHER such frame left in the SAME epoch, nothing between, come out wrong; in another epoch, or
+// behind a clear, they come out right.  (Whether such rows are still there after a whole period of epochs is whole_cycle's question.)
+static void stale_table() {
+    constexpr uint32_t W = 8, H = 8, FRAMES = 300, APART = 8;
+    const uint32_t rows = dec16l_rows((uint64_t)W * H, 1);
+    std::vector<std::vector<uint16_t>> px(FRAMES);
+    std::vector<std::vector<uint8_t>> st(FRAMES);
+    for (uint32_t i = 0; i < FRAMES; i++) {
+        px[i].resize(W * H);
+        for (uint16_t &v : px[i]) v = (uint16_t)((lcg() & 15u) * 4096u);
+        st[i] = compress(px[i], W, H, 0, 1);
+    }
+    const std::unique_ptr<LaneQuad[]> tab(new LaneQuad[(size_t)rows * 4]);
+    const std::unique_ptr<uint16_t[]> out(new uint16_t[W * H]);
+    const auto at = [&](uint32_t) { return out.get(); };
+    const auto decodes = [&](uint32_t i, uint32_t epoch) {
+        const int rc = walk16<false, false, uint16_t>(st[i].data(), st[i].size(), W, H, 0, at, tab.get(), epoch);
+        return rc == FELICS_OK && std::equal(px[i].begin(), px[i].end(), out.get());
+    };
+    unsigned long wrong = 0;
+    for (uint32_t i = 0; i < FRAMES; i++) {
+        const uint32_t later = (i + APART) % FRAMES;
+        memset(tab.get(), 0, (size_t)rows * 4 * sizeof(LaneQuad));
+        if (!decodes(i, 1)) FAIL("stale table: frame %u on zeroed rows", i);
+        wrong += !decodes(later, 1);  // the same epoch, no clear: frame i's counters pass for this frame's
+        memset(tab.get(), 0, (size_t)rows * 4 * sizeof(LaneQuad));
+        if (!decodes(i, 1) || !decodes(later, 2)) FAIL("stale table: frame %u behind frame %u in another epoch", later, i);
+        memset(tab.get(), 0, (size_t)rows * 4 * sizeof(LaneQuad));
+        if (!decodes(later, 1)) FAIL("stale table: frame %u behind a clear", later);
+    }
+    printf("stale table: %lu of %u frames decode wrongly on the rows another frame left in the same epoch; none in another epoch or behind a clear\n", wrong,
+           FRAMES);
+    if (wrong * 10 < FRAMES * 9) FAIL("stale table: fewer than nine in ten of these frames notice stale rows");
+}
+
+// ---- the whole cycle of the lane form's epochs in one slot, as tests/test_gpu_epochs.py runs it on the GPU, on a table that is NEVER
+// cleared: launches 1 .. 10 922 in epochs 1, 4, 7, ..., launch 10 923 in epoch 1 again.  A row of another epoch is an empty row and is
+// reclaimed by whoever probes it, so launch 1's rows survive 10 921 launches only where those never probe: launches 1 and 10 923
+// decode "edge" frames (samples k * CYCLE_EDGE_STEP: contexts of their own), the launches between them "middle" frames (k * 4096),
+// whose sixteen contexts and probe rows leave most of the edge contexts' rows alone.  The simulation must find launch 10 923 decoding
+// wrongly in at least half the slots (one is enough for the GPU test to fail; measured: all 64, nine or ten rows of launch 1 left in
+// each) -- and rightly once the table is cleared in front of it; it also counts what a schedule of middle frames alone
+// would leave (nothing: every row reclaimed).  The frames come from cycle_frame, which the GPU test writes out again in Python.
+constexpr uint32_t CYCLE_EDGE_STEP = 3001, CYCLE_MIDDLE = 300, CYCLE_EDGE = 72, CYCLE_APART = 8, CYCLE_LAUNCHES = 10923;
+static std::vector<uint16_t> cycle_frame(bool edge, uint32_t index) {
+    uint32_t state = (index + 1u) * 2654435761u ^ (edge ? 0x5BD1E995u : 0u);
+    std::vector<uint16_t> px(64);
+    for (uint16_t &v : px) {
+        state = state * 1664525u + 1013904223u;
+        v = (uint16_t)(((state >> 8) & 15u) * (edge ? CYCLE_EDGE_STEP : 4096u));
+    }
+    return px;
+}
+static void whole_cycle() {
+    constexpr uint32_t W = 8, H = 8;
+    const uint32_t rows = dec16l_rows((uint64_t)W * H, 1);
+    std::vector<std::vector<uint16_t>> px[2];
+    std::vector<std::vector<uint8_t>> st[2];
+    for (int edge = 0; edge < 2; edge++)
+        for (uint32_t i = 0; i < (edge ? CYCLE_EDGE : CYCLE_MIDDLE); i++) {
+            px[edge].push_back(cycle_frame(edge, i));
+            st[edge].push_back(compress(px[edge].back(), W, H, 0, 1));
+        }
+    const std::unique_ptr<LaneQuad[]> tab(new LaneQuad[(size_t)rows * 4]);
+    const std::unique_ptr<uint16_t[]> out(new uint16_t[W * H]);
+    const auto at = [&](uint32_t) { return out.get(); };
+    const auto decodes = [&](int edge, uint32_t i, uint32_t epoch) {
+        const int rc = walk16<false, false, uint16_t>(st[edge][i].data(), st[edge][i].size(), W, H, 0, at, tab.get(), epoch);
+        return rc == FELICS_OK && std::equal(px[edge][i].begin(), px[edge][i].end(), out.get());
+    };
+    const auto tagged = [&](uint32_t epoch) {
+        unsigned long n = 0;
+        for (uint32_t r = 0; r < rows; r++) n += (tab[(size_t)r * 4 + 3].w >> 17) == epoch;
+        return n;
+    };
+    unsigned long wrong = 0, left = 0, wrong_plain = 0, left_plain = 0;
+#if defined(__SANITIZE_ADDRESS__)
+    constexpr uint32_t SLOTS = 8;  // (the sanitizer build: the same walks, fewer of them)
+#else
+    constexpr uint32_t SLOTS = 64;
+#endif
+    for (int plain = 0; plain < 2; plain++)  // plain: middle frames in every launch
+        for (uint32_t slot = 0; slot < (plain ? 8u : SLOTS); slot++) {
+            memset(tab.get(), 0, (size_t)rows * 4 * sizeof(LaneQuad));
+            for (uint32_t launch = 1; launch < CYCLE_LAUNCHES; launch++) {
+                const bool edge = !plain && launch == 1;
+                const uint32_t frame = edge ? slot : ((launch - 1) * 64 + slot) % CYCLE_MIDDLE;
+                if (!decodes(edge, frame, 1 + 3 * (launch - 1))) FAIL("whole cycle: slot %u launch %u on rows of other epochs", slot, launch);
+            }
+            const uint32_t last = plain ? ((CYCLE_LAUNCHES - 1) * 64 + slot) % CYCLE_MIDDLE : slot + CYCLE_APART;
+            (plain ? left_plain : left) += tagged(1);
+            (plain ? wrong_plain : wrong) += !decodes(!plain, last, 1);  // no clear: epoch 1 again
+            memset(tab.get(), 0, (size_t)rows * 4 * sizeof(LaneQuad));
+            if (!decodes(!plain, last, 1)) FAIL("whole cycle: slot %u launch %u behind a clear", slot, CYCLE_LAUNCHES);
+        }
+    printf("whole cycle: without the clear %lu of %u slots decode wrongly in launch %u (rows still tagged epoch 1 in front of it: %lu); "
+           "middle frames in every launch: %lu of 8 (rows: %lu)\n", wrong, SLOTS, CYCLE_LAUNCHES, left, wrong_plain, left_plain);
+    if (wrong * 2 < SLOTS) FAIL("whole cycle: fewer than half the slots notice the missing clear");
+}
+
 int main() {
     whole_planes();
     pitched();
     from_checkpoints();
     damage();
+    stale_table();
+    whole_cycle();
     printf("all checks held\n");
     return 0;
 }
