@@ -102,6 +102,11 @@ class _CIndexStats(C.Structure):  # felics_index_stats
     _fields_ = [("streams", C.c_uint64), ("segments8", C.c_uint64), ("lane_segments8", C.c_uint64), ("lane_passes", C.c_uint64)]
 
 
+class _CIndexViewStats(C.Structure):  # felics_index_view_stats
+    _fields_ = [("streams", C.c_uint64), ("undecoded", C.c_uint64), ("items", C.c_uint64), ("launches", C.c_uint64), ("passes", C.c_uint64),
+                ("plane_bytes", C.c_uint64)]
+
+
 class _CRegion(C.Structure):  # felics_region
     _fields_ = [("stream", C.c_uint32), ("x", C.c_uint32), ("y", C.c_uint32), ("w", C.c_uint32), ("h", C.c_uint32)]
 
@@ -145,6 +150,7 @@ EXPORTS = [
     "felics_index_size", "felics_index_build", "felics_decompress_indexed", "felics_decompress_batch_device_indexed",
     "felics_get_index_stats", "felics_compress_batch_device_indexed", "felics_index_lanes_min_items",
     "felics_region_segments", "felics_decompress_region_indexed", "felics_decompress_regions_device_indexed", "felics_get_region_stats",
+    "felics_decompress_views_device_indexed", "felics_decompress_indexed_view", "felics_get_index_view_stats",
 ]
 
 _lib = None
@@ -239,6 +245,11 @@ def lib():
                                                               C.POINTER(_CRegion), vp, sz, C.POINTER(C.c_uint64), C.POINTER(_CHeader),
                                                               C.POINTER(C.c_int)]
         L.felics_get_region_stats.argtypes = [vp, C.POINTER(_CRegionStats), sz]
+    if hasattr(L, "felics_decompress_views_device_indexed"):  # (as above: an older build has no indexed views call)
+        L.felics_decompress_views_device_indexed.argtypes = [vp, sz, vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), vp, C.POINTER(C.c_uint64),
+                                                             C.POINTER(C.c_uint64), C.POINTER(_CView), vp, C.POINTER(_CHeader), C.POINTER(C.c_int)]
+        L.felics_decompress_indexed_view.argtypes = [vp, sz, vp, sz, C.POINTER(_CView), C.POINTER(_CHeader)]
+        L.felics_get_index_view_stats.argtypes = [vp, C.POINTER(_CIndexViewStats), sz]
     L.felics_strerror.argtypes = [C.c_int]
     L.felics_strerror.restype = C.c_char_p
     L.felics_last_error.argtypes = [vp]
@@ -766,6 +777,50 @@ class Encoder:
         chw.permute(1, 2, 0), rgba[..., :3] and mosaic[y0:y1, x0:x1] are decoded into where they lie."""
         return self.decompress_views_device(d_streams, offsets, lens, [view_of_array(a) for a in arrays], ready_event)
 
+    def decompress_views_device_indexed(self, d_streams, offsets, lens, d_index, idx_offsets, idx_lens, views, ready_event=None):
+        """felics_decompress_views_device_indexed: 8-bit streams of any shapes, each with its restart index at d_index + idx_offsets[i]
+        (a multiple of 16; idx_lens[i] bytes, the index's exact size), decoded a wave per (stream, plane, segment) straight into
+        views[i] (tuples as for decompress_views_device); only sample bytes are written, gray through any strides with nothing staged.
+        ready_event as for decompress_views_device.  Returns (list of Header -- zeros where a header is invalid --, status array); a
+        refused view or index address raises FelicsError, a failing stream DecompressionError or FelicsError (a 16-bit stream, a bad
+        index) with .status and .headers."""
+        offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+        lens = np.ascontiguousarray(lens, dtype=np.uint64)
+        idx_offsets = np.ascontiguousarray(idx_offsets, dtype=np.uint64)
+        idx_lens = np.ascontiguousarray(idx_lens, dtype=np.uint64)
+        n = len(offsets)
+        if len(views) != n or len(lens) != n or len(idx_offsets) != n or len(idx_lens) != n:
+            raise ValueError("a length, an index and a view per stream")
+        cv = (_CView * max(n, 1))(*[_cview(v) for v in views])
+        status = np.zeros(max(n, 1), dtype=np.int32)
+        hdrs = (_CHeader * max(n, 1))()
+        u64 = C.POINTER(C.c_uint64)
+        rc = lib().felics_decompress_views_device_indexed(
+            self._h, n, d_streams, offsets.ctypes.data_as(u64), lens.ctypes.data_as(u64), d_index, idx_offsets.ctypes.data_as(u64),
+            idx_lens.ctypes.data_as(u64), cv, int(ready_event) if ready_event else None, hdrs, status.ctypes.data_as(C.POINTER(C.c_int)))
+        headers = [Header(h.color_type, h.pixel_depth, h.width, h.height) for h in hdrs[:n]]  # (zeros where the header is invalid)
+        if rc != 0:
+            err = DecompressionError(rc) if rc in DecompressionError.KINDS else FelicsError(rc, lib().felics_last_error(self._h).decode() if rc == -9 else "")
+            err.status, err.headers = status[:n], headers
+            raise err
+        return headers, status[:n]
+
+    def decompress_arrays_device_indexed(self, d_streams, offsets, lens, d_index, idx_offsets, idx_lens, arrays, ready_event=None):
+        """decompress_views_device_indexed into objects with __cuda_array_interface__ (view_of_array), as decompress_arrays_device: the
+        images of an N x C x H x W tensor (t[i].permute(1, 2, 0)), rgba[..., :3], the cells of a mosaic."""
+        return self.decompress_views_device_indexed(d_streams, offsets, lens, d_index, idx_offsets, idx_lens, [view_of_array(a) for a in arrays],
+                                                    ready_event)
+
+    def index_view_stats(self):
+        """felics_get_index_view_stats: streams handed to decompress_views_device_indexed, those that got a code before a wave was
+        launched for them, the waves (items), launches and passes; cumulative -- and plane_bytes, the RGB scratch of the last call's
+        largest pass."""
+        st = _CIndexViewStats()
+        rc = lib().felics_get_index_view_stats(self._h, C.byref(st), C.sizeof(st))
+        if rc != 0:
+            self._raise(rc)
+        return {k: int(getattr(st, k)) for k, _ in _CIndexViewStats._fields_}
+
     def decode_view_stats(self):
         """felics_get_decode_view_stats: views handed to decompress_views_device and how they were written (dense / in_place /
         scattered, bytes_staged); cumulative."""
@@ -968,6 +1023,27 @@ def decompress_indexed(data, index):
     if rc != 0:
         raise DecompressionError(rc) if rc in DecompressionError.KINDS else FelicsError(rc)
     return out
+
+
+def decompress_indexed_view(data, index, array):
+    """felics_decompress_indexed_view: an 8-bit stream decoded through its restart index INTO `array`, a writable numpy array of shape
+    (H, W) or (H, W, 3) and any admissible strides (a slice of a pitched buffer, buf[::-1], rgba[..., :3], chw.transpose(1, 2, 0), a
+    mosaic cell): only the array's own samples are written.  The host model of Encoder.decompress_views_device_indexed."""
+    if not isinstance(array, np.ndarray) or array.dtype not in (np.uint8, np.uint16) or array.ndim not in (2, 3) or (array.ndim == 3 and array.shape[2] != 3):
+        raise TypeError("Unsupported image format")
+    if not array.flags.writeable:
+        raise ValueError("the array is read-only")
+    arr = np.frombuffer(bytes(data), dtype=np.uint8)
+    idx = np.frombuffer(bytes(index), dtype=np.uint8)
+    h, w = array.shape[:2]
+    rgb = array.ndim == 3
+    view = _CView(array.ctypes.data if array.size else None, w, h, int(rgb), int(array.dtype == np.uint16), array.strides[0], array.strides[1],
+                  array.strides[2] if rgb else 0)
+    rc = lib().felics_decompress_indexed_view(arr.ctypes.data if len(arr) else None, len(arr), idx.ctypes.data if len(idx) else None, len(idx),
+                                              C.byref(view), None)
+    if rc != 0:
+        raise DecompressionError(rc) if rc in DecompressionError.KINDS else FelicsError(rc)
+    return array
 
 
 def region_segments(width, height, segment_pixels, x, y, w, h):

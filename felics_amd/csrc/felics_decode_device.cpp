@@ -1,7 +1,9 @@
 // felics_decode_device.cpp -- host side of the GPU decoder: streams of one shape (felics_decompress_batch_device), of any shapes
-// (felics_decompress_images_device), and their headers (felics_read_headers_device).
+// (felics_decompress_images_device), into views (felics_decompress_views_device), through restart indexes (the dense, the region and
+// the views call), and their headers (felics_read_headers_device).
 #include "felics_host.h"
 #include "felics_index.h"
+#include "felics_viewcheck.h"
 
 namespace felics {
 
@@ -714,6 +716,233 @@ int indexed_index_shape(felics_ctx *ctx, const felics_header &hdr, uint64_t len0
     return FELICS_OK;
 }
 
+// FELICS_TEST_INDEX_VIEWS_PASS=<bytes>: at most that many bytes of RGB planes in a pass of felics_decompress_views_device_indexed (tests)
+uint64_t index_views_pass_cap() {
+    const char *e = getenv("FELICS_TEST_INDEX_VIEWS_PASS");
+    return e && atoll(e) > 0 ? (uint64_t)atoll(e) : UINT64_MAX;
+}
+
+// felics_decompress_views_device_indexed after the checks that need no device (felics.h "Restart index: views and mixed shapes"):
+//   1. the ready event in front of the lane's stream, on which everything below runs;
+//   2. k_read_headers and k_read_index_headers, both records copied back, ONE synchronise;
+//   3. every stream classified on the host, in the order felics.h lists the codes (index_header_check with the stream's own header
+//      and length; the index's exact size);
+//   4. the streams in passes of consecutive streams whose RGB planes fit the scratch; within a pass the rows in LDS classes as
+//      decompress_images cuts them for k_decode8, a class per launch, so a narrow stream does not pay a 4K row's LDS.  A row's items
+//      are contiguous in (plane, segment) order; rows, items and the finish tables go up on the lane's stream;
+//   5. per pass: the launches, k_seg_status over the pass's rows (a RegionRow per row names its items), the strided conversion of
+//      its clean RGB rows -- behind one another on the one stream, since the passes share the planes;
+//   6. one copy back of the rows' statuses.
+int decompress_views_indexed(felics_ctx *ctx, size_t n, const void *d_streams, const uint64_t *offsets, const uint64_t *lens, const void *d_index,
+                             const uint64_t *idx_offsets, const uint64_t *idx_lens, const felics_view *views, felics_header *hdrs, int *status) {
+    hipStream_t s = ctx->lanes[0].stream;
+    felics_index_view_stats &vs = ctx->ivstats;
+    vs.streams += n;
+    vs.plane_bytes = 0;
+    auto fail_all = [&](int code) {
+        for (size_t i = 0; i < n; i++) status[i] = code;
+        vs.undecoded += n;
+        return code;
+    };
+    auto al = [](size_t b) { return (b + 15) & ~(size_t)15; };
+    // offsets | lens | index offsets | index lens | stream headers | index headers in dec_meta
+    const size_t o_rec = n * 32, o_ih = o_rec + al(n * sizeof(DecodeHeader)), o_meta_end = o_ih + n * INDEX_HEADER_BYTES;
+    int rc = reserve(ctx, ctx->dec_meta, o_meta_end);
+    if (rc) return fail_all(rc);
+    // (one copy up -- the four arrays back to back -- and one copy back: the two kinds of headers as they lie in dec_meta)
+    std::vector<uint64_t> up;
+    std::vector<uint8_t> back;
+    try {
+        up.resize(4 * n);
+        back.resize(o_meta_end - o_rec);
+    } catch (const std::bad_alloc &) {
+        return fail_all(FELICS_E_IO);
+    }
+    std::copy(offsets, offsets + n, up.begin());
+    std::copy(lens, lens + n, up.begin() + n);
+    std::copy(idx_offsets, idx_offsets + n, up.begin() + 2 * n);
+    std::copy(idx_lens, idx_lens + n, up.begin() + 3 * n);
+    const DecodeHeader *rec = reinterpret_cast<const DecodeHeader *>(back.data());
+    const uint8_t *ih = back.data() + (o_ih - o_rec);
+    uint8_t *meta = (uint8_t *)ctx->dec_meta.p;
+    uint64_t *d_off = (uint64_t *)meta, *d_len = d_off + n, *d_ioff = d_len + n, *d_ilen = d_ioff + n;
+    DecodeHeader *d_rec = (DecodeHeader *)(meta + o_rec);
+    uint8_t *d_ih = meta + o_ih;
+    const uint8_t *st = (const uint8_t *)d_streams, *ix = (const uint8_t *)d_index;
+    auto headers = [&]() -> int {
+        int r = wait_ready(ctx, s);  // (the header kernels read stream and index bytes)
+        if (r) return r;
+        HIP_TRY(ctx, hipMemcpyAsync(d_off, up.data(), n * 32, hipMemcpyHostToDevice, s));
+        HIP_TRY(ctx, launch_read_headers(s, st, d_off, d_len, (uint32_t)n, d_rec));
+        HIP_TRY(ctx, launch_read_index_headers(s, ix, d_ioff, d_ilen, (uint32_t)n, d_ih));
+        HIP_TRY(ctx, hipMemcpyAsync(back.data(), d_rec, back.size(), hipMemcpyDeviceToHost, s));
+        HIP_TRY(ctx, hipStreamSynchronize(s));
+        return FELICS_OK;
+    };
+    if ((rc = headers()) != 0) return fail_all(rc);
+    // the streams one by one: the first code of felics.h's list
+    std::vector<IndexLayout> lay;
+    std::vector<uint32_t> segpix;
+    try {
+        lay.resize(n);
+        segpix.assign(n, 0);
+    } catch (const std::bad_alloc &) {
+        return fail_all(FELICS_E_IO);
+    }
+    uint64_t total_items = 0;
+    size_t nrows = 0;
+    for (size_t i = 0; i < n; i++) {
+        const DecodeHeader &h = rec[i];
+        const felics_view &w = views[i];
+        if (hdrs) hdrs[i] = h.status == FELICS_OK ? felics_header{h.color, h.depth, h.W, h.H} : felics_header{};
+        int code = h.dstatus;
+        if (!code && h.depth != FELICS_DEPTH_8) code = FELICS_E_UNSUPPORTED;  // 16-bit streams have no index
+        if (!code && index_lds_bytes(h.W, h.color) > DECODE_LDS_LIMIT) code = FELICS_E_UNSUPPORTED;  // no host fallback here
+        if (!code && ((int)h.color != w.color || (int)h.depth != w.depth || h.W != w.width || h.H != w.height)) code = FELICS_E_INVALID_DIMENSIONS;
+        if (!code && (idx_lens[i] < INDEX_HEADER_BYTES || index_header_check(ih + i * INDEX_HEADER_BYTES, h.color, h.W, h.H, lens[i], lay[i]) != FELICS_OK ||
+                      lay[i].total != idx_lens[i]))
+            code = FELICS_E_INVALID_INDEX;
+        status[i] = code;
+        if (code) continue;
+        segpix[i] = idx_rd32(ih + i * INDEX_HEADER_BYTES + IDX_SEGPIX);
+        total_items += (uint64_t)lay[i].planes * std::max(lay[i].K, 1u);
+        nrows++;
+    }
+    if (total_items > 0x7FFFFFFFull) return fail_all(FELICS_E_UNSUPPORTED);  // one block per item, a word per item
+    // passes: consecutive streams whose planes (6 bytes per RGB pixel) fit the budget; a single larger stream is a pass of its own
+    auto plane_bytes_of = [&](size_t i) { return status[i] == FELICS_OK && rec[i].color ? 6ull * rec[i].W * rec[i].H : 0ull; };
+    uint64_t plane_total = 0;
+    for (size_t i = 0; i < n; i++) plane_total += plane_bytes_of(i);
+    uint64_t budget = UINT64_MAX;
+    size_t free_b = 0, total_b = 0;
+    if (plane_total && plane_total + 64 > ctx->dec_planes.cap && hipMemGetInfo(&free_b, &total_b) == hipSuccess)
+        budget = ((uint64_t)free_b + ctx->dec_planes.cap) / 4;
+    budget = std::min(budget, index_views_pass_cap());
+    std::vector<size_t> pass_end;
+    std::vector<uint64_t> plane_off;
+    uint64_t most = 0;
+    // the tables: rows in (pass, LDS class, stream) order, a row's items contiguous
+    constexpr uint32_t LDS_CLASS[] = {16u << 10, 32u << 10, 64u << 10, DECODE_LDS_LIMIT};
+    struct Launch {
+        size_t item0, cnt;
+        uint32_t lds;
+    };
+    struct Pass {
+        size_t row0, rows, launch0, launches;
+        uint64_t max_npix;  // of its RGB rows
+    };
+    // rows | items | the finish tables (a RegionRow, a DecodeRow and a ViewRow per row), built where they are copied from in one piece
+    const size_t n_items = (size_t)total_items;
+    const size_t o_items = al(nrows * sizeof(IndexViewRow)), o_regions = o_items + al(n_items * sizeof(IndexViewItem)),
+                 o_conv = o_regions + al(nrows * sizeof(RegionRow)), o_cviews = o_conv + al(nrows * sizeof(DecodeRow)),
+                 o_end = o_cviews + nrows * sizeof(ViewRow);
+    std::vector<uint8_t> tables;
+    std::vector<int> row_status;
+    std::vector<Launch> launches;
+    std::vector<Pass> passes;
+    IndexViewRow *rows = nullptr;
+    size_t nr = 0, ni = 0;  // rows and items so far
+    try {
+        tables.assign(o_end, 0);
+        row_status.assign(nrows, FELICS_E_HIP);  // until the kernels' own word arrives
+        rows = reinterpret_cast<IndexViewRow *>(tables.data());
+        IndexViewItem *items = reinterpret_cast<IndexViewItem *>(tables.data() + o_items);
+        RegionRow *regions = reinterpret_cast<RegionRow *>(tables.data() + o_regions);
+        DecodeRow *conv = reinterpret_cast<DecodeRow *>(tables.data() + o_conv);
+        ViewRow *cviews = reinterpret_cast<ViewRow *>(tables.data() + o_cviews);
+        plane_off.assign(n, 0);
+        uint64_t acc = 0;
+        for (size_t i = 0; i < n; i++) {
+            const uint64_t b = plane_bytes_of(i);
+            if (acc && acc + b > budget) {
+                pass_end.push_back(i);
+                acc = 0;
+            }
+            plane_off[i] = acc / 2;  // int16 elements
+            acc += b;
+            most = std::max(most, acc);
+        }
+        pass_end.push_back(n);
+        size_t i0 = 0;
+        for (const size_t i1 : pass_end) {
+            Pass P{nr, 0, launches.size(), 0, 0};
+            for (int c = 0; c < 4; c++) {
+                Launch L{ni, 0, 0};
+                for (size_t i = i0; i < i1; i++) {
+                    if (status[i] != FELICS_OK) continue;
+                    const DecodeHeader &h = rec[i];
+                    const uint32_t lds = decode8_lds_bytes(h.W, h.color);
+                    if (lds > LDS_CLASS[c] || (c > 0 && lds <= LDS_CLASS[c - 1])) continue;
+                    const felics_view &w = views[i];
+                    const uint32_t K = lay[i].K, keff = std::max(K, 1u), cnt = lay[i].planes * keff;
+                    const uint32_t r = (uint32_t)nr++;
+                    const ViewRow vr{w.data, w.row_stride, w.pixel_stride, h.color ? w.channel_stride : 0};
+                    rows[r] = IndexViewRow{(uint32_t)i, h.W, h.H, h.color, segpix[i], K, (uint32_t)ni, cnt, idx_offsets[i], plane_off[i], vr};
+                    regions[r] = RegionRow{(uint32_t)i, 0, 0, h.W, h.H, (uint32_t)ni, cnt, 0, 0, plane_off[i]};
+                    conv[r] = DecodeRow{r - (uint32_t)P.row0, h.W, h.H, h.color, 0, plane_off[i]};  // (stream: the row within its pass, as status is)
+                    cviews[r] = vr;
+                    for (uint32_t p = 0; p < lay[i].planes; p++)
+                        for (uint32_t j = 0; j < keff; j++) items[ni++] = IndexViewItem{r, p, j};
+                    L.cnt += cnt;
+                    L.lds = std::max(L.lds, lds);
+                    if (h.color) P.max_npix = std::max(P.max_npix, (uint64_t)h.W * h.H);
+                }
+                if (L.cnt) launches.push_back(L);
+            }
+            P.rows = nr - P.row0;
+            P.launches = launches.size() - P.launch0;
+            passes.push_back(P);
+            i0 = i1;
+        }
+    } catch (const std::bad_alloc &) {
+        return fail_all(FELICS_E_IO);
+    }
+    // device side: the tables in dec_region_work; a word per item and one per row in dec_seg_status
+    if (nrows && (rc = reserve(ctx, ctx->dec_region_work, o_end)) != 0) return fail_all(rc);
+    if (nrows && (rc = reserve(ctx, ctx->dec_seg_status, al(n_items * 4) + nrows * 4)) != 0) return fail_all(rc);
+    if (most && (rc = reserve(ctx, ctx->dec_planes, (size_t)most + 64)) != 0) return fail_all(rc);
+    for (size_t i = 0; i < n; i++) vs.undecoded += status[i] != FELICS_OK;
+    vs.items += n_items;
+    vs.launches += launches.size();
+    vs.passes += passes.size();
+    vs.plane_bytes = most;
+    int first = FELICS_OK;
+    if (nrows) {
+        uint8_t *work = (uint8_t *)ctx->dec_region_work.p;
+        IndexViewRow *d_rows = (IndexViewRow *)work;
+        IndexViewItem *d_items = (IndexViewItem *)(work + o_items);
+        RegionRow *d_regions = (RegionRow *)(work + o_regions);
+        DecodeRow *d_conv = (DecodeRow *)(work + o_conv);
+        ViewRow *d_cviews = (ViewRow *)(work + o_cviews);
+        int *d_item_status = (int *)ctx->dec_seg_status.p, *d_row_status = (int *)((uint8_t *)ctx->dec_seg_status.p + al(n_items * 4));
+        int16_t *d_planes = (int16_t *)ctx->dec_planes.p;
+        auto queue = [&]() -> int {
+            HIP_TRY(ctx, hipMemcpyAsync(work, tables.data(), o_end, hipMemcpyHostToDevice, s));  // (the five tables in one copy)
+            HIP_TRY(ctx, hipMemsetAsync(d_item_status, 0xFF, al(n_items * 4) + nrows * 4, s));
+            for (const Pass &P : passes) {
+                for (size_t k = P.launch0; k < P.launch0 + P.launches; k++) {
+                    const Launch &L = launches[k];
+                    HIP_TRY(ctx, launch_decode8_seg_views(s, st, d_off, d_len, ix, d_rows, d_items + L.item0, (uint32_t)L.cnt, L.lds, d_planes,
+                                                          d_item_status + L.item0));
+                }
+                HIP_TRY(ctx, launch_seg_views_finish(s, (uint32_t)P.rows, d_regions + P.row0, d_item_status, d_conv + P.row0, d_cviews + P.row0,
+                                                     P.max_npix, d_planes, d_row_status + P.row0));
+            }
+            HIP_TRY(ctx, hipMemcpyAsync(row_status.data(), d_row_status, nrows * 4, hipMemcpyDeviceToHost, s));
+            HIP_TRY(ctx, hipStreamSynchronize(s));  // (the host tables live until here)
+            return FELICS_OK;
+        };
+        if ((rc = queue()) != 0) {
+            for (size_t r = 0; r < nrows; r++) status[rows[r].stream] = FELICS_E_HIP;
+            return rc;
+        }
+        for (size_t r = 0; r < nrows; r++) status[rows[r].stream] = row_status[r];
+    }
+    for (size_t i = 0; i < n; i++)
+        if (status[i] && !first) first = status[i];
+    return first;
+}
+
 }  // namespace
 
 }  // namespace felics
@@ -733,27 +962,7 @@ int felics_get_decode_view_stats(const felics_ctx *ctx, felics_decode_view_stats
 }
 
 int felics_view_writable(const felics_view *v) {
-    if (!v) return FELICS_E_INVALID_ARGUMENT;
-    int64_t lo, hi;
-    const int rc = check_view(*v, lo, hi, false);
-    if (rc || !v->width || !v->height) return rc;
-    // the nested rule: of the axes with more than one step, each stride (by size) at least the whole extent of the one below it
-    struct Axis {
-        unsigned __int128 stride;
-        uint64_t extent;
-    } ax[3];
-    int na = 0;
-    auto mag = [](int64_t s) { return s < 0 ? (unsigned __int128)(-(__int128)s) : (unsigned __int128)s; };
-    if (v->width > 1) ax[na++] = Axis{mag(v->pixel_stride), v->width};
-    if (v->height > 1) ax[na++] = Axis{mag(v->row_stride), v->height};
-    if (v->color == FELICS_COLOR_RGB) ax[na++] = Axis{mag(v->channel_stride), 3};
-    std::sort(ax, ax + na, [](const Axis &a, const Axis &b) { return a.stride < b.stride; });
-    unsigned __int128 least = v->depth == FELICS_DEPTH_16 ? 2 : 1;  // the sample itself is the innermost extent
-    for (int k = 0; k < na; k++) {
-        if (ax[k].stride < least) return FELICS_E_INVALID_ARGUMENT;
-        least = ax[k].stride * ax[k].extent;
-    }
-    return FELICS_OK;
+    return v ? view_writable_code(*v) : FELICS_E_INVALID_ARGUMENT;  // (felics_viewcheck.h: check_view's checks and the nested rule)
 }
 
 uint32_t felics_decode_lanes_min_streams(int depth, int color) {
@@ -1222,6 +1431,34 @@ int felics_decompress_views_device(felics_ctx *ctx, size_t n, const void *d_stre
     ctx->dstats.lanes16_table_bytes = table_bytes;
     ctx->view_ready = nullptr;
     return first;
+}
+
+int felics_get_index_view_stats(const felics_ctx *ctx, felics_index_view_stats *out, size_t out_size) {
+    if (!ctx || !out) return FELICS_E_INVALID_ARGUMENT;
+    memcpy(out, &ctx->ivstats, std::min(out_size, sizeof(felics_index_view_stats)));
+    return FELICS_OK;
+}
+
+int felics_decompress_views_device_indexed(felics_ctx *ctx, size_t n, const void *d_streams, const uint64_t *offsets, const uint64_t *lens,
+                                           const void *d_index, const uint64_t *idx_offsets, const uint64_t *idx_lens, const felics_view *views,
+                                           void *ready_event, felics_header *hdrs, int *status) {
+    if (!ctx || (n && !status)) return FELICS_E_INVALID_ARGUMENT;
+    auto fail_all = [&](int code) { return fail_call(n, status, hdrs, nullptr, code); };
+    if (n && (!d_streams || !offsets || !lens || !d_index || !idx_offsets || !idx_lens || !views)) return fail_all(FELICS_E_INVALID_ARGUMENT);
+    for (size_t i = 0; i < n; i++) {  // every view and every index address before anything is launched: the first error in view order
+        const int rc = felics_view_writable(&views[i]);
+        if (rc) return fail_all(rc);
+        if (((uintptr_t)d_index + idx_offsets[i]) & 15u) return fail_all(FELICS_E_INVALID_ARGUMENT);  // the kernel loads a checkpoint as aligned words
+    }
+    if (ctx->failed) return fail_all(FELICS_E_HIP);
+    if (n == 0) return FELICS_OK;
+    if (any_pending(ctx)) return fail_all(FELICS_E_INVALID_ARGUMENT);  // felics_wait_batch first
+    if (n > 0xFFFFFFFFull) return fail_all(FELICS_E_INVALID_ARGUMENT);
+    if (hipSetDevice(ctx->device) != hipSuccess) return fail_all(hip_fail(ctx, hipGetLastError(), "hipSetDevice"));
+    ctx->view_ready = (hipEvent_t)ready_event;
+    const int rc = decompress_views_indexed(ctx, n, d_streams, offsets, lens, d_index, idx_offsets, idx_lens, views, hdrs, status);
+    ctx->view_ready = nullptr;
+    return rc;
 }
 
 }  // extern "C"

@@ -660,6 +660,66 @@ __global__ __launch_bounds__(64) void k_seg_status(const int *__restrict__ words
     if (threadIdx.x == 0) status[blockIdx.x] = first == 0xFFFFFFFFu ? FELICS_OK : mine[first];
 }
 
+namespace {
+
+// The whole segment into a view (felics_decompress_views_device_indexed): a gray sample as ONE BYTE at the place the view's strides
+// give pixel (col, y) -- whatever lies between the samples is never stored to, and any strides do, negative ones and pixel strides
+// other than 1 included; an RGB sample to plane c of the row's int16 planes as the segment sink does (the conversion writes the view).
+// The walk hands it p0 <= at < pend only, and (col, y) is a pixel of the image the view was checked against.
+struct ViewSink {
+    uint8_t *data;   // gray: the view's first sample; else null
+    int64_t row_stride, pixel_stride;
+    int16_t *outp;   // RGB: plane c of the row's planes
+    __device__ __forceinline__ uint64_t stop(uint64_t pend) const { return pend; }
+    __device__ __forceinline__ void store(uint32_t col, uint32_t y, uint64_t at, int v) const {
+        if (data) data[view_sample_offset(row_stride, pixel_stride, 0, col, y, 0)] = (uint8_t)v;
+        else outp[at] = (int16_t)v;
+    }
+};
+
+}  // namespace
+
+// One wave per WORK ITEM = (row, plane, segment) of felics_decompress_views_device_indexed (felics_kernels.h; host model:
+// felics_decompress_indexed_view).  Item and row are wave-uniform (blockIdx.x: scalar loads); the walk's geometry, segment_pixels and
+// K are the row's, so the streams of a launch need not share a shape -- only the launch's dynamic LDS, which holds its widest row.
+// item_status[b] = FELICS_OK or the code; k_seg_status picks a row's first.
+__global__ __launch_bounds__(64) void k_decode8_seg_views(const uint8_t *__restrict__ streams, const uint64_t *__restrict__ offsets,
+                                                          const uint64_t *__restrict__ lens, const uint8_t *__restrict__ index,
+                                                          const IndexViewRow *__restrict__ rows, const IndexViewItem *__restrict__ items,
+                                                          int16_t *__restrict__ planes, int *__restrict__ item_status) {
+    extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
+    const IndexViewItem item = items[blockIdx.x];
+    const IndexViewRow r = rows[item.row];
+    const DecUniform geo{r.W, r.H, r.color};
+    const uint32_t c = item.plane;
+    const ViewSink sink{r.color ? nullptr : reinterpret_cast<uint8_t *>(const_cast<void *>(r.view.data)), r.view.row_stride, r.view.pixel_stride,
+                        r.color ? planes + r.plane_off + (uint64_t)c * r.W * r.H : nullptr};
+    const int rc = decode8_from_checkpoint(smem, streams + offsets[r.stream], lens[r.stream], index + r.index_off, geo, r.segment_pixels, r.K, c,
+                                           item.seg, false, sink);
+    if (lane_id() == 0) item_status[blockIdx.x] = rc;
+}
+
+// The first 64 bytes of every index of felics_decompress_views_device_indexed for the host's checks: four lanes per index, a
+// 16-byte word each (the indexes are 16-byte aligned), bytes where an index ends inside the word, zeros behind its end.
+__global__ __launch_bounds__(256) void k_read_index_headers(const uint8_t *__restrict__ index, const uint64_t *__restrict__ idx_offsets,
+                                                            const uint64_t *__restrict__ idx_lens, uint32_t n, uint8_t *__restrict__ out) {
+    const uint64_t t = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    const uint64_t i = t / 4;
+    const uint32_t q = (uint32_t)(t % 4) * 16u;
+    if (i >= n) return;
+    const uint8_t *src = index + idx_offsets[i] + q;
+    const uint64_t len = idx_lens[i];
+    uint4 w = make_uint4(0, 0, 0, 0);
+    if (len >= q + 16u) {
+        w = *reinterpret_cast<const uint4 *>(src);
+    } else if (len > q) {
+        uint8_t b[16] = {0};
+        for (uint32_t k = 0; k < (uint32_t)(len - q); k++) b[k] = src[k];
+        w = make_uint4(idx_rd32(b), idx_rd32(b + 4), idx_rd32(b + 8), idx_rd32(b + 12));
+    }
+    *reinterpret_cast<uint4 *>(out + i * INDEX_HEADER_BYTES + q) = w;
+}
+
 // ------------------------------------------------------------------------------------------
 // Sixty-four streams per wave, LANE = stream (8-bit gray, batches of hundreds of streams and more).
 //
@@ -1878,6 +1938,40 @@ hipError_t launch_decode16_lanes_waves_views(hipStream_t s, const uint8_t *strea
                             k_decode16_lanes<true, LaneMixed>, g, planes, convert, tab, epoch0, status);
     return launch_lanes(s, streams, offsets, lens, nwaves, color, k_decode16_lanes<false, LaneMixed>, g, nullptr, k_decode16_lanes<true, LaneMixed>, g,
                         planes, convert, tab, epoch0, status);
+}
+
+// ------------------------------------------------------------------------------------------
+// felics_decompress_views_device_indexed: the walk from a checkpoint with the view sink, per LDS class; a pass's tail.
+// ------------------------------------------------------------------------------------------
+
+static_assert(INDEX_LDS_LIMIT == DECODE_LDS_LIMIT, "felics_index.h names the wave form's LDS limit for the host model");
+
+hipError_t launch_decode8_seg_views(hipStream_t s, const uint8_t *streams, const uint64_t *offsets, const uint64_t *lens, const uint8_t *index,
+                                    const IndexViewRow *rows, const IndexViewItem *items, uint32_t nitems, uint32_t lds, int16_t *planes,
+                                    int *item_status) {
+    if (nitems == 0) return hipSuccess;
+    if (lds > 64u * 1024u) {
+        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&k_decode8_seg_views), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                                 (int)DECODE_LDS_LIMIT);
+        if (e != hipSuccess) return e;
+    }
+    hipLaunchKernelGGL(k_decode8_seg_views, dim3(nitems), dim3(64), lds, s, streams, offsets, lens, index, rows, items, planes, item_status);
+    return hipGetLastError();
+}
+
+hipError_t launch_seg_views_finish(hipStream_t s, uint32_t n, const RegionRow *regions, const int *item_status, const DecodeRow *conv,
+                                   const ViewRow *views, uint64_t max_npix, int16_t *planes, int *status) {
+    if (n == 0) return hipSuccess;
+    hipLaunchKernelGGL(k_seg_status, dim3(n), dim3(64), 0, s, item_status, regions, 0u, status);
+    if (max_npix) launch_conv_views<int16_t, uint8_t>(s, conv, n, max_npix, planes, status, DecodeViews{views, false, true});
+    return hipGetLastError();
+}
+
+hipError_t launch_read_index_headers(hipStream_t s, const uint8_t *index, const uint64_t *idx_offsets, const uint64_t *idx_lens, uint32_t n,
+                                     uint8_t *out) {
+    if (n == 0) return hipSuccess;
+    hipLaunchKernelGGL(k_read_index_headers, dim3((uint32_t)(((uint64_t)n * 4 + 255) / 256)), dim3(256), 0, s, index, idx_offsets, idx_lens, n, out);
+    return hipGetLastError();
 }
 
 }  // namespace felics

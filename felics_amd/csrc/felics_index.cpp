@@ -1,6 +1,7 @@
 // felics_index.cpp -- host side of the restart index (felics.h): felics_index_size, felics_index_build (the index
 // of any 8-bit stream, from one pass of the host decoder) and felics_decompress_indexed (the stream decoded segment by segment,
-// each from its checkpoint alone: the host model of k_decode8_seg, with the same checks in the same order).
+// each from its checkpoint alone: the host model of k_decode8_seg, with the same checks in the same order) and
+// felics_decompress_indexed_view (the same walk written through a view's strides: the host model of k_decode8_seg_views).
 #include <cstdint>
 #include <cstring>
 #include <new>
@@ -9,6 +10,7 @@
 #include "../../include/felics.h"
 #include "felics_hostdec.h"
 #include "felics_index.h"
+#include "felics_viewcheck.h"
 
 namespace {
 
@@ -48,8 +50,10 @@ int check_stream(const uint8_t *in, size_t len, felics_header &hdr) {
     return FELICS_OK;
 }
 
-// ycocg_to_rgb (color_transform.rs:20-26) of the planes, range-checked like try_into::<u8>(); dst may be NULL (check only)
-int store_rgb8(const std::vector<int32_t> (&ch)[3], unsigned planes, uint8_t *dst) {
+// ycocg_to_rgb (color_transform.rs:20-26) of the planes, range-checked like try_into::<u8>(): put(i, c, v) for sample c of pixel i, in
+// pixel order, up to the first one out of range
+template <typename Put>
+int convert_rgb8(const std::vector<int32_t> (&ch)[3], unsigned planes, Put put) {
     const size_t n = ch[0].size();
     for (size_t i = 0; i < n; i++) {
         int32_t v[3];
@@ -64,10 +68,17 @@ int store_rgb8(const std::vector<int32_t> (&ch)[3], unsigned planes, uint8_t *ds
         }
         for (unsigned c = 0; c < planes; c++) {
             if (v[c] < 0 || v[c] > 255) return FELICS_E_INVALID_VALUE;
-            if (dst) dst[i * planes + c] = (uint8_t)v[c];
+            put(i, c, (uint8_t)v[c]);
         }
     }
     return FELICS_OK;
+}
+
+// ... to a dense interleaved frame; dst may be NULL (check only)
+int store_rgb8(const std::vector<int32_t> (&ch)[3], unsigned planes, uint8_t *dst) {
+    return convert_rgb8(ch, planes, [&](size_t i, unsigned c, uint8_t v) {
+        if (dst) dst[i * planes + c] = v;
+    });
 }
 
 // Everything a segment starts from but its bit position comes out of checkpoint (c, j) (K >= 1): the counters into `est`, and the 2 W
@@ -219,6 +230,74 @@ int felics_decompress_indexed(const uint8_t *in, size_t len, const uint8_t *inde
         return FELICS_E_INVALID_DIMENSIONS;
     }
     return store_rgb8(ch, planes, (uint8_t *)pixels);
+}
+
+int felics_decompress_indexed_view(const uint8_t *in, size_t len, const uint8_t *index, size_t index_len, const felics_view *view,
+                                   felics_header *hdr_out) {
+    if ((!in && len) || (!index && index_len) || !view) return FELICS_E_INVALID_ARGUMENT;
+    int rc = view_writable_code(*view);
+    if (rc) return rc;
+    // the per-stream codes of felics_decompress_views_device_indexed, in its order
+    felics_header hdr;
+    rc = felics_read_header(in, len, &hdr);
+    if (hdr_out) *hdr_out = rc ? felics_header{} : hdr;
+    if (rc) return rc;
+    const uint32_t W = hdr.width, H = hdr.height, color = hdr.color_type;
+    const unsigned planes = color ? 3 : 1;
+    if ((uint64_t)W * H > 0xFFFFFFFFull) return FELICS_E_INVALID_DIMENSIONS;
+    const size_t npix = (size_t)W * H;
+    // (k_read_headers' rule: two raw 32-bit samples per plane, then at least one flag bit per pixel, padded to a byte)
+    const uint64_t bits = (uint64_t)planes * (64u + (npix > 2 ? npix - 2 : 0));
+    if (len - FELICS_HEADER_BYTES < (bits + 7) / 8) return FELICS_E_IO;
+    if (hdr.pixel_depth != FELICS_DEPTH_8) return FELICS_E_UNSUPPORTED;
+    if (index_lds_bytes(W, color) > INDEX_LDS_LIMIT) return FELICS_E_UNSUPPORTED;  // what the wave form cannot hold, the model refuses too
+    if ((int)color != view->color || (int)hdr.pixel_depth != view->depth || W != view->width || H != view->height) return FELICS_E_INVALID_DIMENSIONS;
+    IndexLayout L;
+    if (index_len < INDEX_HEADER_BYTES || index_header_check(index, color, W, H, len, L) || L.total != index_len) return FELICS_E_INVALID_INDEX;
+    const uint32_t seg = idx_rd32(index + IDX_SEGPIX);
+    uint8_t *data = (uint8_t *)const_cast<void *>(view->data);
+    const int64_t rs = view->row_stride, ps = view->pixel_stride, cs = color ? view->channel_stride : 0;
+    std::vector<int32_t> ch[3];
+    try {
+        Estimator est(OPT8);
+        for (uint32_t c = 0; c < L.planes; c++) {
+            ch[c].assign(npix, 0);
+            int32_t *out = ch[c].data();
+            for (uint32_t j = 0; j < std::max(L.K, 1u); j++) {
+                uint64_t start, end;
+                if (index_segment_bounds(index, L, c, j, len, start, end)) return FELICS_E_INVALID_INDEX;
+                BitReader br(in, len, start);
+                const size_t s0 = (size_t)j * seg, s1 = std::min(npix, s0 + seg);
+                if (L.K && (rc = load_checkpoint(index, L, color, c, j, W, s0, est, out, 0)) != 0) return rc;
+                if (j == 0) {
+                    const int32_t p0 = (int32_t)br.bits(32), p1 = (int32_t)br.bits(32);
+                    if (br.failed()) return FELICS_E_IO;
+                    if (npix > 0) out[0] = p0;
+                    if (npix > 1) out[1] = p1;
+                }
+                if (s1 > s0) {
+                    rc = decode_span(br, W, OPT8, est, out, std::max<size_t>(s0, 2), s1, nullptr);
+                    if (rc) return rc;
+                    for (size_t i = s0; i < s1; i++)
+                        if (!in_plane_range(out[i], color, c)) return FELICS_E_INVALID_VALUE;
+                    // gray: the segment's samples through the view, as the kernel's sink stores them (an RGB plane waits for the other two)
+                    for (size_t i = s0; i < s1 && !color; i++) {
+                        const uint32_t y = (uint32_t)(i / W), x = (uint32_t)(i - (size_t)y * W);
+                        data[view_sample_offset(rs, ps, 0, x, y, 0)] = (uint8_t)out[i];
+                    }
+                }
+                if (br.pos() != end) return FELICS_E_INVALID_INDEX;  // the end check: exactly on the next checkpoint
+            }
+        }
+    } catch (const std::bad_alloc &) {
+        return FELICS_E_INVALID_DIMENSIONS;
+    }
+    if (!color) return FELICS_OK;
+    if ((rc = store_rgb8(ch, planes, nullptr)) != 0) return rc;  // (checked first: a stream that fails here leaves the view as it was)
+    return convert_rgb8(ch, planes, [&](size_t i, unsigned c, uint8_t v) {
+        const uint32_t y = (uint32_t)(i / W), x = (uint32_t)(i - (size_t)y * W);
+        data[view_sample_offset(rs, ps, cs, x, y, c)] = v;
+    });
 }
 
 int felics_region_segments(uint32_t W, uint32_t H, uint32_t segment_pixels, const felics_region *r, uint32_t *segs, size_t cap, size_t *count) {

@@ -1,5 +1,5 @@
 // felics_index.h -- layout of the restart index (include/felics.h), for the host builder / decoder
-// (felics_index.cpp), the host side of the device call and the segment kernel alike.  Little-endian throughout.
+// (felics_index.cpp), the host side of the device calls and the segment kernels alike.  Little-endian throughout.
 #ifndef FELICS_INDEX_H
 #define FELICS_INDEX_H
 
@@ -125,6 +125,22 @@ FELICS_IDX_HD inline bool region_needs(uint32_t W, uint64_t npix, uint32_t seg, 
 FELICS_IDX_HD inline void region_span(uint32_t W, uint32_t seg, const felics_region &r, uint32_t &first, uint32_t &last) {
     first = (uint32_t)(((uint64_t)r.y * W + r.x) / seg);
     last = (uint32_t)((region_last(W, r) - 1) / seg);
+}
+
+// ---- views (felics.h "Restart index: views and mixed shapes"): what felics_decompress_views_device_indexed's host side, its kernel's
+// sink and the host model share.
+// Where sample (col, y) of channel c of a view lies, in bytes from the view's `data`: the one place this is worked out for
+// k_decode8_seg_views' ViewSink and for felics_decompress_indexed_view.
+FELICS_IDX_HD inline int64_t view_sample_offset(int64_t row_stride, int64_t pixel_stride, int64_t channel_stride, uint32_t col, uint32_t y,
+                                                uint32_t c) {
+    return (int64_t)y * row_stride + (int64_t)col * pixel_stride + (int64_t)c * channel_stride;
+}
+// The dynamic LDS the wave form asks for a row of W samples (what decode8_lds_bytes returns: the estimator table of 256 or 512 rows
+// of six words, two rows of int16 padded to whole blocks of 64), and the most a workgroup may ask for (DECODE_LDS_LIMIT).  A wider
+// row is FELICS_E_UNSUPPORTED in every indexed call, on the host as on the device.
+constexpr uint32_t INDEX_LDS_LIMIT = 160u * 1024u;
+FELICS_IDX_HD inline uint64_t index_lds_bytes(uint32_t W, uint32_t color) {
+    return (color ? 512u : 256u) * 6u * 4u + 2ull * (((uint64_t)W + 63u) & ~63ull) * 2u;
 }
 
 }  // namespace felics

@@ -338,6 +338,40 @@ hipError_t launch_decode8_regions(hipStream_t s, const uint8_t *streams, const u
                                   uint64_t index_stride, uint32_t W, uint32_t H, uint32_t color, uint32_t segment_pixels, uint32_t K,
                                   const RegionRow *rows, uint32_t nregions, const RegionItem *items, uint32_t nitems, uint64_t max_crop,
                                   uint8_t *pixels, int16_t *planes, int *item_status, int *status);
+// Indexed streams of ANY shapes into views (felics_decompress_views_device_indexed, felics.h "Restart index: views and mixed shapes"):
+// one wave per work item = (row, plane, segment), k_decode8_seg_views: k_decode8_seg's walk with the view sink.  A row is one stream
+// of the call that passed the host's checks; the walk's geometry, segment_pixels and K come from the row (what the host read out of
+// the stream's and the index's own headers; the walk checks both again), so every row has its own.  Gray samples go through the
+// row's view, one byte each: data + y * row_stride + col * pixel_stride (view_sample_offset, felics_index.h), any strides; RGB rows
+// write int16 planes at planes + plane_off (three planes of W * H samples), converted through the view by k_ycocg8_to_rgb<ConvStrided>.
+// A row's items are contiguous, in (plane, segment) order; an empty image (K = 0) has one pseudo item per plane, segment 0.
+struct IndexViewRow {
+    uint32_t stream;             // index into offsets / lens
+    uint32_t W, H, color;
+    uint32_t segment_pixels, K;
+    uint32_t item0, nitems;      // its items in the call's work list: item0 .. item0 + nitems - 1, nitems = C * max(K, 1)
+    uint64_t index_off;          // byte offset of its index in `index` (index + index_off is a multiple of 16)
+    uint64_t plane_off;          // RGB: element offset of its planes in `planes`
+    ViewRow view;                // gray: where its samples go
+};
+struct IndexViewItem {
+    uint32_t row, plane, seg;
+};
+// One launch: `nitems` < 2^31 consecutive items of the work list, whose rows all fit `lds` bytes of dynamic LDS (decode8_lds_bytes of
+// the widest); item_status: a word per item of the launch.
+hipError_t launch_decode8_seg_views(hipStream_t s, const uint8_t *streams, const uint64_t *offsets, const uint64_t *lens, const uint8_t *index,
+                                    const IndexViewRow *rows, const IndexViewItem *items, uint32_t nitems, uint32_t lds, int16_t *planes,
+                                    int *item_status);
+// The tail of a pass of that call for rows 0 .. n - 1 of its tables: status[r] = row r's first failing word (k_seg_status over
+// `regions`, a RegionRow per row of which item0 / nitems are read), then the conversion of the clean RGB rows through their views
+// (conv[r].stream = r: status is per row; a gray row has nothing to convert).  max_npix: the largest W * H of an RGB row (0: none).
+struct DecodeRow;  // (below, with the mixed decode call)
+hipError_t launch_seg_views_finish(hipStream_t s, uint32_t n, const RegionRow *regions, const int *item_status, const DecodeRow *conv,
+                                   const ViewRow *views, uint64_t max_npix, int16_t *planes, int *status);
+// The first 64 bytes of each of n restart indexes (index i at index + idx_offsets[i], a multiple of 16; idx_lens[i] bytes) to
+// out + 64 i, zeros behind an index shorter than that: no byte outside [idx_offsets[i], idx_offsets[i] + idx_lens[i]) is read.
+hipError_t launch_read_index_headers(hipStream_t s, const uint8_t *index, const uint64_t *idx_offsets, const uint64_t *idx_lens, uint32_t n,
+                                     uint8_t *out);
 // The same for 16-bit streams, gray or RGB (k_decode16_lanes): 64 streams per wave, lane = stream; needs W >= 8 and a table of
 // decode16_lanes_table_bytes(n, W, H, color) bytes = n * planes * dec16l_rows(W * H, planes) * 64 (felics_lanetable.h: sized by the
 // pixel count, 512 KB per plane of a 64 x 64 stream, the wave form's 8.4 MB from 32 771 pixels on), zero-initialised ONCE: rows carry

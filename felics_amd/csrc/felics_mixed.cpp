@@ -1,6 +1,7 @@
 // felics_mixed.cpp -- images of different shapes in one call (felics_compress_images*) and strided views of device surfaces
 // (felics_compress_views_device): buckets, the mixed sub-batches' plane tables, landing and remedies.
 #include "felics_host.h"
+#include "felics_viewcheck.h"
 
 namespace felics {
 
@@ -475,28 +476,13 @@ int wait_ready(felics_ctx *ctx, hipStream_t s) {
 // A view's checks (felics_view_extent and felics_compress_views_device alike) and the hull of its samples' bytes relative to data.
 int check_view(const felics_view &v, int64_t &lo, int64_t &hi, bool encode_limits) {
     lo = hi = 0;
-    int rc = check_args(v.width, v.height, v.color, v.depth);
+    const int rc = view_args_check(v);  // (felics_viewcheck.h: the host model of the indexed views call makes the same checks)
     if (rc) return rc;
     const uint64_t npix = (uint64_t)v.width * v.height;
     const uint32_t planes = v.color == FELICS_COLOR_RGB ? 3 : 1;
-    const int bytes = v.depth == FELICS_DEPTH_16 ? 2 : 1;
-    if (!v.data && npix) return FELICS_E_INVALID_ARGUMENT;
-    if (bytes == 2 && (((uintptr_t)v.data | (uint64_t)v.row_stride | (uint64_t)v.pixel_stride | (planes == 3 ? (uint64_t)v.channel_stride : 0u)) & 1u))
-        return FELICS_E_INVALID_ARGUMENT;
     if (encode_limits && npix * planes >= 0xE0000000ull) return FELICS_E_UNSUPPORTED;
     if (encode_limits && v.depth == FELICS_DEPTH_16 && npix > WIDE_MAX_PLANE_PIXELS) return FELICS_E_UNSUPPORTED;
-    if (!npix) return FELICS_OK;
-    __int128 l = 0, h = bytes;
-    const int64_t steps[3] = {(int64_t)v.height - 1, (int64_t)v.width - 1, (int64_t)planes - 1};
-    const int64_t strides[3] = {v.row_stride, v.pixel_stride, planes == 3 ? v.channel_stride : 0};
-    for (int d = 0; d < 3; d++) {
-        const __int128 span = (__int128)steps[d] * strides[d];
-        (span < 0 ? l : h) += span;
-    }
-    if (l < INT64_MIN || h > INT64_MAX) return FELICS_E_INVALID_ARGUMENT;  // (addresses are computed in 64 bits)
-    lo = (int64_t)l;
-    hi = (int64_t)h;
-    return FELICS_OK;
+    return view_hull(v, lo, hi);
 }
 
 int views_device(felics_ctx *ctx, size_t n, const felics_view *views, void *ready_event, void *d_out, size_t d_out_cap, uint64_t *offsets,

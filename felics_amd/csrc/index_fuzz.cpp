@@ -7,7 +7,11 @@
 //     mutated index beside a good stream): any code, no crash;
 //   * felics_decompress_region_indexed with random regions on all of these pairs: on a good pair every crop must equal the same
 //     window of felics_decompress's pixels and felics_region_segments must name what a pixel-by-pixel marking names; on a mutated
-//     or foreign pair any code, no crash.
+//     or foreign pair any code, no crash;
+//   * felics_decompress_indexed_view, the host model of the indexed views call, on all of these pairs too, each time into a random
+//     admissible view (a pitch, pixel stride 1 or 2, a flipped row or channel axis, interleaved or planar) whose target buffer is
+//     EXACTLY the size of the view's hull, so a store outside it is the sanitizer's to report: on a good pair every sample must be
+//     felics_decompress's and every other byte of the hull untouched; on a mutated or foreign pair any code, no crash.
 // Built with -fsanitize=address,undefined by `make asan`; tests/test_index_cpu.py feeds it a mutated corpus.
 // Exit code 0 = every input was handled without a sanitizer report and every accepted pair decoded to the right pixels.
 #include <dirent.h>
@@ -60,6 +64,10 @@ int main(int argc, char **argv) {
         bad += felics_region_segments(8, 8, 4096, &in, nullptr, 0, &n) != FELICS_E_BUFFER_TOO_SMALL || n != 1;
         bad += felics_region_segments(8, 8, 4096, &in, segs, 4, &n) != FELICS_OK || n != 1 || segs[0] != 0;
         bad += felics_decompress_region_indexed(b, sizeof b, b, sizeof b, nullptr, b, sizeof b, nullptr) != FELICS_E_INVALID_ARGUMENT;
+        const felics_view ok{b, 8, 8, FELICS_COLOR_GRAY, FELICS_DEPTH_8, 8, 1, 0}, alias{b, 8, 8, FELICS_COLOR_GRAY, FELICS_DEPTH_8, 4, 1, 0};
+        bad += felics_decompress_indexed_view(b, sizeof b, b, sizeof b, nullptr, nullptr) != FELICS_E_INVALID_ARGUMENT;
+        bad += felics_decompress_indexed_view(nullptr, 5, b, sizeof b, &ok, nullptr) != FELICS_E_INVALID_ARGUMENT;
+        bad += felics_decompress_indexed_view(b, sizeof b, b, sizeof b, &alias, nullptr) != FELICS_E_INVALID_ARGUMENT;  // rows that share bytes
         if (bad) {
             fprintf(stderr, "argument checks: %d unexpected results\n", bad);
             return 1;
@@ -71,7 +79,7 @@ int main(int argc, char **argv) {
     while (dirent *e = readdir(d))
         if (e->d_name[0] != '.' && !ends_with(e->d_name, ".idx")) names.push_back(e->d_name);
     closedir(d);
-    size_t regions = 0, built = 0, refused = 0, mutations = 0, mut_accepted = 0, pairs = 0, pairs_ok = 0;
+    size_t regions = 0, views = 0, built = 0, refused = 0, mutations = 0, mut_accepted = 0, pairs = 0, pairs_ok = 0;
     const size_t cap = 32u << 20;  // decoders and the builder get bounded buffers whatever a header claims
     std::vector<uint8_t> buf, idx, given, px(cap), ref(cap), index(cap);
     uint64_t rng = 0x9E3779B97F4A7C15ull;
@@ -113,6 +121,42 @@ int main(int argc, char **argv) {
         }
         return true;
     };
+    // the host model of the views call on a pair, into a random admissible view of the header's shape over a buffer that is exactly
+    // the view's hull; `good`: it must succeed, the samples must be ref's and the bytes between them must keep their pattern
+    std::vector<uint8_t> target, expect;
+    auto view_on = [&](const std::vector<uint8_t> &index_bytes, size_t index_len, const felics_header &h, bool good) {
+        const int64_t W = h.width, H = h.height, C = h.color_type ? 3 : 1;
+        if ((uint64_t)W * H > (1u << 22)) return true;  // (targets are this driver's to allocate: larger ones are left out)
+        felics_view v = {nullptr, h.width, h.height, h.color_type, FELICS_DEPTH_8, 0, 0, 0};
+        const int64_t ps = 1 + (int64_t)(next() % 2), pad = (int64_t)(next() % 16);
+        const bool planar = C == 3 && next() % 2, flip_rows = next() % 2, flip_ch = C == 3 && next() % 2;
+        if (C == 1 || planar) {
+            v.pixel_stride = ps;
+            v.row_stride = W * ps + pad;
+            v.channel_stride = C == 3 ? H * v.row_stride + pad : 0;
+        } else {
+            v.channel_stride = 1;
+            v.pixel_stride = (3 + (int64_t)(next() % 2)) * ps;  // RGB or RGBA pixels, every one or every other
+            v.row_stride = W * v.pixel_stride + pad;
+        }
+        if (flip_rows) v.row_stride = -v.row_stride;
+        if (flip_ch) v.channel_stride = -v.channel_stride;
+        int64_t lo = 0, hi = W && H ? 1 : 0;
+        const int64_t spans[3] = {(H - 1) * v.row_stride, (W - 1) * v.pixel_stride, (C - 1) * v.channel_stride};
+        for (int d = 0; d < 3 && W && H; d++) (spans[d] < 0 ? lo : hi) += spans[d];
+        target.assign((size_t)(hi - lo), 0xA5);
+        if (W && H) v.data = target.data() - lo;
+        felics_header hv;
+        const int rc = felics_decompress_indexed_view(buf.data(), buf.size(), index_bytes.data(), index_len, &v, &hv);
+        views++;
+        if (!good) return true;
+        if (rc != FELICS_OK) return false;
+        expect.assign(target.size(), 0xA5);
+        for (int64_t y = 0; y < H; y++)
+            for (int64_t x = 0; x < W; x++)
+                for (int64_t c = 0; c < C; c++) expect[(size_t)(y * v.row_stride + x * v.pixel_stride + c * v.channel_stride - lo)] = ref[(size_t)((y * W + x) * C + c)];
+        return target == expect;
+    };
     for (const std::string &n : names) {
         const std::string path = std::string(argv[1]) + "/" + n;
         if (!slurp(path, buf)) continue;
@@ -131,6 +175,7 @@ int main(int argc, char **argv) {
                 fprintf(stderr, "%s: a region of a given pair wrote past its crop\n", n.c_str());
                 return 1;
             }
+            if (felics_read_header(buf.data(), buf.size(), &hh) == FELICS_OK) view_on(given, given.size(), hh, false);
         }
         for (uint32_t seg : {4096u, 12288u}) {
             size_t ilen = 0;
@@ -162,6 +207,12 @@ int main(int argc, char **argv) {
                 fprintf(stderr, "%s: a region of a good pair failed, differs from felics_decompress's window or wrote past its crop\n", n.c_str());
                 return 1;
             }
+            for (int k = 0; k < 4; k++)
+                if (!view_on(index, ilen, h, true)) {
+                    fprintf(stderr, "%s: the view model failed on a good pair, wrote other samples than felics_decompress's or a byte that is no sample\n",
+                            n.c_str());
+                    return 1;
+                }
             for (int k = 0; k < 8; k++) {  // the planner against a marking of the region's pixels
                 const felics_region r = region_of(h.width, h.height);
                 const size_t K = ((size_t)h.width * h.height + seg - 1) / seg;
@@ -196,6 +247,7 @@ int main(int argc, char **argv) {
                     fprintf(stderr, "%s: a region of a mutated index wrote past its crop\n", n.c_str());
                     return 1;
                 }
+                view_on(bad, bad.size(), h, false);
                 if (m % 10 == 0) {  // and cut short
                     const size_t cut = (size_t)(next() % ilen);
                     if (felics_decompress_indexed(buf.data(), buf.size(), bad.data(), cut, px.data(), px.size(), &h2) == FELICS_OK) {
@@ -206,7 +258,7 @@ int main(int argc, char **argv) {
             }
         }
     }
-    printf("index_fuzz: %zu files, %zu indexes built, %zu refused, %zu pairs (%zu accepted), %zu mutations (%zu accepted), %zu regions\n", names.size(), built,
-           refused, pairs, pairs_ok, mutations, mut_accepted, regions);
+    printf("index_fuzz: %zu files, %zu indexes built, %zu refused, %zu pairs (%zu accepted), %zu mutations (%zu accepted), %zu regions, %zu views\n", names.size(),
+           built, refused, pairs, pairs_ok, mutations, mut_accepted, regions, views);
     return 0;
 }

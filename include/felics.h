@@ -566,6 +566,68 @@ typedef struct felics_decode_view_stats {
 /* Writes min(out_size, sizeof(felics_decode_view_stats)) bytes, never more. */
 int felics_get_decode_view_stats(const felics_ctx *ctx, felics_decode_view_stats *out, size_t out_size);
 
+/* ---- Restart index: views and mixed shapes ----
+ * felics_decompress_views_device through restart indexes: stream i (at d_streams + offsets[i], lens[i] bytes; any 8-bit stream, with
+ * its own shape, colour, segment_pixels and K) has its index at d_index + idx_offsets[i], idx_lens[i] bytes long, and is decoded one
+ * wave per (stream, plane, segment) straight into views[i]: k_decode8_seg_views, the walk of felics_decompress_batch_device_indexed
+ * with a sink that writes through the view.  Every sample equals what felics_decompress yields for that stream.  A small image takes
+ * part with the K = 1 index felics_index_build gives it; a stream without an index does not.
+ * Everything felics_decompress_views_device says holds unless named here: per-stream headers (hdrs, optional: hdrs[i] gets the
+ * stream's header where felics_read_header accepts it, zeros otherwise) and status[] filled on every return, one bad stream does not
+ * fail the others, the same stream (and index) may be referenced several times, refused while a ticket is outstanding, FELICS_E_HIP on
+ * a failed context, n = 0 returns FELICS_OK, the first non-zero status is returned.  offsets / lens / idx_offsets / idx_lens / views /
+ * hdrs / status are HOST arrays.
+ *   Checked before anything is launched (the first error in view order is returned and put in every status[i]): NULL pointers
+ *   (FELICS_E_INVALID_ARGUMENT); every view as felics_view_writable checks it; d_index + idx_offsets[i] a multiple of 16
+ *   (FELICS_E_INVALID_ARGUMENT: the kernel loads a checkpoint as aligned words); a call of 2^31 work items or more (the sum of
+ *   C * max(K, 1) cannot be known yet: it is refused with FELICS_E_UNSUPPORTED in every status once the headers are read, before a
+ *   stream is decoded).
+ *   Per stream, in this order: the header codes of felics_read_header; the mixed call's "header claims more than the stream holds"
+ *   rule (FELICS_E_IO; w * h >= 2^32: FELICS_E_INVALID_DIMENSIONS); FELICS_E_UNSUPPORTED for a 16-bit stream; FELICS_E_UNSUPPORTED for
+ *   a row too wide for the wave form's LDS (no host fallback, as in the other indexed calls); FELICS_E_INVALID_DIMENSIONS for a header
+ *   whose colour, depth, width or height differs from views[i] (nothing is written for that stream); FELICS_E_INVALID_INDEX if
+ *   idx_lens[i] < 64, if the index header fails the checks above against the stream's header and length, or if idx_lens[i] is not the
+ *   index's exact size (felics_index_size); then whatever the walk reports for the first failing segment in (plane, segment) order,
+ *   all checks of "Restart index" made on the device.  A failing stream may leave any of its own view's samples written or unwritten,
+ *   and nothing else.
+ *   The write guarantee is felics_decompress_views_device's: SAMPLE BYTES ONLY.  Gray is stored sample by sample, one byte through all
+ *   three strides -- negative strides and pixel strides other than 1 included, so NO gray view is staged, whatever its layout.  RGB is
+ *   decoded as int16 Y / Co / Cg planes into the context's plane scratch (6 bytes per pixel) and the strided conversion of the
+ *   unindexed call writes the view.  The scratch is bounded: streams are taken in passes of consecutive streams whose planes fit a
+ *   quarter of the free device memory (what the context already holds counted as free); a single larger stream is a pass of its own.
+ *   FELICS_TEST_INDEX_VIEWS_PASS=<bytes> in the environment (read per call) caps a pass's planes (tests).
+ *   ready_event : as for felics_decompress_views_device.  If given, every stream of the library waits for it before the first byte of
+ *                 a stream, an index or a view is touched in this call, the two header kernels included.
+ * The stream headers and the first 64 bytes of every index are read by two kernels and come back in one synchronise; no header is
+ * fetched with a blocking copy.  The call is blocking: the views are complete when it returns.  It creates no HIP stream.
+ * NOT HERE: a lane-per-segment form, regions into views, a queued form, 16-bit streams, streams without an index in the same call,
+ * an indexed encode of views or mixed shapes. */
+int felics_decompress_views_device_indexed(felics_ctx *ctx, size_t n, const void *d_streams, const uint64_t *offsets, const uint64_t *lens,
+                                           const void *d_index, const uint64_t *idx_offsets, const uint64_t *idx_lens,
+                                           const felics_view *views, void *ready_event, felics_header *hdrs /* optional */, int *status);
+
+/* Host only, the model of k_decode8_seg_views as felics_decompress_indexed is k_decode8_seg's: the same checks in the same order
+ * (the per-stream list above), decoded segment by segment from the checkpoints alone, written through the view's strides into HOST
+ * memory by the offset function the kernel's sink compiles (sample bytes only).  A view that is not felics_view_writable
+ * (its code) or whose shape differs from the stream's (FELICS_E_INVALID_DIMENSIONS) is refused before a byte is written; an RGB
+ * stream that fails leaves the view untouched, a gray one may have written the segments in front of the failing one.  hdr (optional)
+ * gets the stream's header where felics_read_header accepts it. */
+int felics_decompress_indexed_view(const uint8_t *in, size_t len, const uint8_t *index, size_t index_len, const felics_view *view,
+                                   felics_header *hdr);
+
+/* What a context's felics_decompress_views_device_indexed calls did so far (cumulative; calls that passed the checks before the
+ * launch). */
+typedef struct felics_index_view_stats {
+    uint64_t streams;      /* streams handed in */
+    uint64_t undecoded;    /* ... that got a code before a wave was launched for them */
+    uint64_t items;        /* waves launched: C * max(K, 1) for every decoded stream */
+    uint64_t launches;     /* k_decode8_seg_views launches (one per LDS class of a pass) */
+    uint64_t passes;       /* passes (consecutive streams whose RGB planes share the scratch) */
+    uint64_t plane_bytes;  /* NOT cumulative: the RGB scratch of the last call's largest pass */
+} felics_index_view_stats;
+/* Writes min(out_size, sizeof(felics_index_view_stats)) bytes, never more. */
+int felics_get_index_view_stats(const felics_ctx *ctx, felics_index_view_stats *out, size_t out_size);
+
 /* Text for a code above; for FELICS_E_HIP felics_last_error(ctx) has the HIP message. */
 const char *felics_strerror(int code);
 const char *felics_last_error(const felics_ctx *ctx);
