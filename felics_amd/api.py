@@ -107,6 +107,10 @@ class _CIndexViewStats(C.Structure):  # felics_index_view_stats
                 ("plane_bytes", C.c_uint64)]
 
 
+class _CIndexEmitStats(C.Structure):  # felics_index_emit_stats
+    _fields_ = [("indexes", C.c_uint64), ("checkpoints", C.c_uint64), ("in_mixed", C.c_uint64), ("redone", C.c_uint64)]
+
+
 class _CRegion(C.Structure):  # felics_region
     _fields_ = [("stream", C.c_uint32), ("x", C.c_uint32), ("y", C.c_uint32), ("w", C.c_uint32), ("h", C.c_uint32)]
 
@@ -151,6 +155,7 @@ EXPORTS = [
     "felics_get_index_stats", "felics_compress_batch_device_indexed", "felics_index_lanes_min_items",
     "felics_region_segments", "felics_decompress_region_indexed", "felics_decompress_regions_device_indexed", "felics_get_region_stats",
     "felics_decompress_views_device_indexed", "felics_decompress_indexed_view", "felics_get_index_view_stats",
+    "felics_index_plan", "felics_compress_views_device_indexed", "felics_get_index_emit_stats",
 ]
 
 _lib = None
@@ -250,6 +255,11 @@ def lib():
                                                              C.POINTER(C.c_uint64), C.POINTER(_CView), vp, C.POINTER(_CHeader), C.POINTER(C.c_int)]
         L.felics_decompress_indexed_view.argtypes = [vp, sz, vp, sz, C.POINTER(_CView), C.POINTER(_CHeader)]
         L.felics_get_index_view_stats.argtypes = [vp, C.POINTER(_CIndexViewStats), sz]
+    if hasattr(L, "felics_compress_views_device_indexed"):  # (as above: an older build writes indexes for one shape only)
+        u64, u32 = C.POINTER(C.c_uint64), C.POINTER(C.c_uint32)
+        L.felics_index_plan.argtypes = [sz, C.POINTER(_CView), u32, u64, u64, u64]
+        L.felics_compress_views_device_indexed.argtypes = [vp, sz, C.POINTER(_CView), u32, vp, vp, sz, vp, sz, u64, u64, u64]
+        L.felics_get_index_emit_stats.argtypes = [vp, C.POINTER(_CIndexEmitStats), sz]
     L.felics_strerror.argtypes = [C.c_int]
     L.felics_strerror.restype = C.c_char_p
     L.felics_last_error.argtypes = [vp]
@@ -335,6 +345,31 @@ def view_of_array(array):
     strides = [int(v) for v in strides]
     ptr = int(cai["data"][0]) if shape[0] * shape[1] else 0
     return (ptr, shape[1], shape[0], color, depth, strides[0], strides[1], strides[2] if len(shape) == 3 else 0)
+
+
+def _segments(segment_pixels, n):
+    """segment_pixels of n views as a uint32 array: one int for all of them, or a sequence of n"""
+    segs = np.full(n, segment_pixels, dtype=np.uint32) if np.isscalar(segment_pixels) else np.ascontiguousarray(segment_pixels, dtype=np.uint32)
+    if len(segs) != n:
+        raise ValueError("a segment per view")
+    return np.resize(segs, max(n, 1))
+
+
+def index_plan(views, segment_pixels):
+    """felics_index_plan: where the restart indexes of views (tuples as for Encoder.compress_views_device) go in one buffer.
+    segment_pixels: an int for all views or one per view; 0 = no index for that view.  Returns (idx_offsets, idx_lens, total):
+    offsets are multiples of 16 in view order, a view without an index has length 0.  Host only, needs no GPU."""
+    n = len(views)
+    cv = (_CView * max(n, 1))(*[_cview(v) for v in views])
+    segs = _segments(segment_pixels, n)
+    offs = np.zeros(max(n, 1), dtype=np.uint64)
+    lens = np.zeros(max(n, 1), dtype=np.uint64)
+    total = C.c_uint64(0)
+    u64 = C.POINTER(C.c_uint64)
+    rc = lib().felics_index_plan(n, cv, segs.ctypes.data_as(C.POINTER(C.c_uint32)), offs.ctypes.data_as(u64), lens.ctypes.data_as(u64), C.byref(total))
+    if rc != 0:
+        raise FelicsError(rc)
+    return offs[:n], lens[:n], int(total.value)
 
 
 def _csurfaces(surfaces):
@@ -521,6 +556,44 @@ class Encoder:
         """compress_views_device on objects with __cuda_array_interface__ (view_of_array): slices, channel selections and permuted
         tensors are encoded from the memory they lie in."""
         return self.compress_views_device([view_of_array(a) for a in arrays], d_out, d_out_cap, ready_event)
+
+    def compress_views_device_indexed(self, views, segment_pixels, d_out, d_out_cap, d_index, d_index_cap, idx_offsets=None, ready_event=None):
+        """felics_compress_views_device_indexed: compress_views_device plus, for every view whose segment_pixels (an int for all views,
+        or one per view; 0: none) is not 0, the restart index of its stream at d_index + idx_offsets[i] (device; idx_offsets=None:
+        where index_plan puts them).  Every index equals index_build(stream i, segment_pixels[i]).  Returns (offsets, lens,
+        idx_offsets, idx_lens)."""
+        n = len(views)
+        planned, idx_lens, _ = index_plan(views, segment_pixels)
+        idx_offsets = planned if idx_offsets is None else np.ascontiguousarray(idx_offsets, dtype=np.uint64)
+        if len(idx_offsets) != n:
+            raise ValueError("an index offset per view")
+        cv = (_CView * max(n, 1))(*[_cview(v) for v in views])
+        segs = _segments(segment_pixels, n)
+        offs = np.zeros(max(n, 1), dtype=np.uint64)
+        lens = np.zeros(max(n, 1), dtype=np.uint64)
+        u64 = C.POINTER(C.c_uint64)
+        rc = lib().felics_compress_views_device_indexed(
+            self._h, n, cv, segs.ctypes.data_as(C.POINTER(C.c_uint32)), int(ready_event) if ready_event else None, d_out, d_out_cap, d_index,
+            d_index_cap, np.resize(idx_offsets, max(n, 1)).ctypes.data_as(u64) if n else None, offs.ctypes.data_as(u64), lens.ctypes.data_as(u64))
+        if rc == -8:
+            raise FelicsError(rc, "need %d bytes" % int(lens[0]) if lens[0] else "the index buffer is too small")
+        if rc != 0:
+            self._raise(rc)
+        return offs[:n], lens[:n], idx_offsets, idx_lens
+
+    def compress_arrays_device_indexed(self, arrays, segment_pixels, d_out, d_out_cap, d_index, d_index_cap, idx_offsets=None, ready_event=None):
+        """compress_views_device_indexed on objects with __cuda_array_interface__ (view_of_array), as compress_arrays_device."""
+        return self.compress_views_device_indexed([view_of_array(a) for a in arrays], segment_pixels, d_out, d_out_cap, d_index, d_index_cap,
+                                                  idx_offsets, ready_event)
+
+    def index_emit_stats(self):
+        """felics_get_index_emit_stats: indexes written by compress_views_device_indexed and their checkpoints, how many of them by
+        the mixed kernels (in_mixed) and how many by the uniform writer inside a remedy (redone); cumulative."""
+        st = _CIndexEmitStats()
+        rc = lib().felics_get_index_emit_stats(self._h, C.byref(st), C.sizeof(st))
+        if rc != 0:
+            self._raise(rc)
+        return {k: int(getattr(st, k)) for k, _ in _CIndexEmitStats._fields_}
 
     def view_stats(self):
         """felics_get_view_stats: views seen, and how they were read (dense / in_place / gathered, bytes_staged); cumulative."""

@@ -280,6 +280,7 @@ void felics_ctx_destroy(felics_ctx *ctx) {
     release(ctx->mix_stage);
     release(ctx->mix_out);
     release(ctx->mix_redo);
+    release(ctx->mix_index);
     release(ctx->view_stage);
     release(ctx->dec_meta);
     release(ctx->dec_seg_status);

@@ -159,6 +159,14 @@ int run_lane(felics_ctx *ctx, Lane &l, uint8_t *d_out, uint64_t slot_stride) {
         launch_join_edges(tl, (const uint64_t *)l.tile_bitoff.p, (const uint32_t *)l.tile_bits.p,
                           (const uint32_t *)l.edge_first.p, (const uint32_t *)l.edge_last.p, target, g);
         launch_concat_planes(tl, plane_base, plane_carry, target, g);
+        if (l.idx_rows) {
+            // A mixed sub-batch whose images want restart indexes: here, behind the pack, join and concat of every tile and in front
+            // of the copy of the sizes, so that `sized` -- what the host waits for before it reuses the lane or returns -- stands
+            // behind the indexes too.  Written whatever the sub-batch's flags will say: one that is redone gets them again.
+            for (const auto &z : l.idx_zero) HIP_TRY(ctx, hipMemsetAsync(z.first, 0, z.second, tl));
+            launch_index_emit_mixed(tl, tloc.runtab, (const uint4 *)l.block_state.p, cap, (const uint64_t *)l.tile_bitoff.p, plane_base, plane_carry, g,
+                                    l.idx_rows, l.idx_max_K);
+        }
     } else {
         HIP_TRY(ctx, hipStreamWaitEvent(tl, l.assign_done[ns - 1], 0));
         {
@@ -339,6 +347,9 @@ Geometry &begin_sub_batch(felics_ctx *ctx, Lane &l, size_t first, size_t cnt, ui
     l.nslices = std::max(1, std::min(nslices, SLICES));
     l.queued = queued;
     l.first_image = first;
+    l.idx_rows = nullptr;
+    l.idx_max_K = 0;
+    l.idx_zero.clear();
     ctx->stats.submissions++;
     for (int i = 0; i < ST_COUNT; i++) l.ev_used[i] = 0;
     const uint32_t planes = color == FELICS_COLOR_RGB ? 3 : 1;
@@ -640,21 +651,9 @@ int felics_compress_batch_device_indexed(felics_ctx *ctx, size_t n, const void *
     rc = encode_device(ctx, ctx->lanes[0], n, d_pixels, w, h, color, depth, (uint8_t *)d_out, d_out_cap, offsets, lens, nullptr, false, &req);
     if (rc == FELICS_OK && (uint64_t)w * h == 0) {
         // an empty image (K = 0) is encoded on the host and so is its index: the header, every plane its two raw samples long
-        std::vector<uint8_t> ih(bytes, 0);
-        IndexLayout L = index_layout(w, h, (uint32_t)color, segment_pixels);
-        memcpy(ih.data(), "FLCX", 4);
-        ih[IDX_VERSION] = INDEX_VERSION;
-        ih[IDX_COLOR] = (uint8_t)color;
-        for (int k = 0; k < 4; k++) {
-            ih[IDX_WIDTH + k] = (uint8_t)(w >> (8 * k));
-            ih[IDX_HEIGHT + k] = (uint8_t)(h >> (8 * k));
-            ih[IDX_SEGPIX + k] = (uint8_t)(segment_pixels >> (8 * k));
-        }
-        for (uint32_t c = 0; c < L.planes; c++) {
-            const uint64_t end = STREAM_HEADER_BITS + 64u * (c + 1);
-            for (int k = 0; k < 8; k++) ih[IDX_PLANE_END + 8 * c + k] = (uint8_t)(end >> (8 * k));
-        }
-        for (size_t i = 0; i < n; i++) HIP_TRY(ctx, hipMemcpy((uint8_t *)d_index + i * bytes, ih.data(), bytes, hipMemcpyHostToDevice));
+        uint8_t ih[INDEX_HEADER_BYTES];
+        empty_index(ih, w, h, (uint32_t)color, segment_pixels);
+        for (size_t i = 0; i < n; i++) HIP_TRY(ctx, hipMemcpy((uint8_t *)d_index + i * bytes, ih, bytes, hipMemcpyHostToDevice));
     }
     return rc;
 }

@@ -62,6 +62,10 @@ struct MixImage {
     // felics_submit_surfaces_device: a 16-bit view the mixed 16-bit path reads where it lies (gray16: rows `pitch` BYTES apart, RGB16
     // through the plane transform) instead of gathering it
     bool wide_in_place = false;
+    // felics_compress_views_device_indexed: where the restart index of this image's stream goes (device, 16-byte aligned, checked by
+    // the entry point) and its segment; nullptr / 0: no index (every 16-bit image)
+    uint8_t *index = nullptr;
+    uint32_t segment_pixels = 0;
 };
 
 // One pipeline lane: HIP streams, stage events and a workspace in HBM of its own.  A submission (or one pass of
@@ -119,6 +123,11 @@ struct Lane {
     DevBuf mtable;
     PlaneGeom *h_table = nullptr;
     size_t h_table_cap = 0;
+    // ... whose images want restart indexes (felics_compress_views_device_indexed; set by launch_mixed, cleared by begin_sub_batch):
+    // the IndexGeom rows in mtable and their largest K, and the index ranges run_lane zeroes in front of the two emit kernels
+    const IndexGeom *idx_rows = nullptr;
+    uint32_t idx_max_K = 0;
+    std::vector<std::pair<uint8_t *, size_t>> idx_zero;
 };
 
 }  // namespace felics
@@ -212,6 +221,10 @@ struct felics_ctx {
     // two kinds of headers in dec_meta; rows, items and the finish tables in dec_region_work; item and row status words in
     // dec_seg_status; a pass's planes in dec_planes); view_ready is its ready event; the counts of felics_get_index_view_stats
     felics_index_view_stats ivstats = {};
+    // felics_compress_views_device_indexed: the indexes of a remedy's group (redo_by_shape: written back to back by the uniform
+    // writer, copied to where the caller wants them); the counts of felics_get_index_emit_stats
+    DevBuf mix_index;
+    felics_index_emit_stats iestats = {};
 };
 
 namespace felics {

@@ -52,6 +52,23 @@ FELICS_IDX_HD inline IndexLayout index_layout(uint32_t w, uint32_t h, uint32_t c
     return L;
 }
 
+// The whole index of an empty image (K = 0, INDEX_HEADER_BYTES bytes): the header, every plane its two raw samples long.
+inline void empty_index(uint8_t *ih, uint32_t w, uint32_t h, uint32_t color, uint32_t segment_pixels) {
+    for (uint32_t i = 0; i < INDEX_HEADER_BYTES; i++) ih[i] = 0;
+    ih[0] = 'F', ih[1] = 'L', ih[2] = 'C', ih[3] = 'X';
+    ih[IDX_VERSION] = INDEX_VERSION;
+    ih[IDX_COLOR] = (uint8_t)color;
+    for (int k = 0; k < 4; k++) {
+        ih[IDX_WIDTH + k] = (uint8_t)(w >> (8 * k));
+        ih[IDX_HEIGHT + k] = (uint8_t)(h >> (8 * k));
+        ih[IDX_SEGPIX + k] = (uint8_t)(segment_pixels >> (8 * k));
+    }
+    for (uint32_t c = 0; c < (color ? 3u : 1u); c++) {
+        const uint64_t end = STREAM_HEADER_BITS + 64u * (c + 1);
+        for (int k = 0; k < 8; k++) ih[IDX_PLANE_END + 8 * c + k] = (uint8_t)(end >> (8 * k));
+    }
+}
+
 FELICS_IDX_HD inline uint32_t idx_rd16(const uint8_t *p) { return (uint32_t)p[0] | ((uint32_t)p[1] << 8); }
 FELICS_IDX_HD inline uint32_t idx_rd32(const uint8_t *p) { return idx_rd16(p) | (idx_rd16(p + 2) << 16); }
 FELICS_IDX_HD inline uint64_t idx_rd64(const uint8_t *p) { return (uint64_t)idx_rd32(p) | ((uint64_t)idx_rd32(p + 4) << 32); }

@@ -192,6 +192,17 @@ struct IndexEmit {
 void launch_index_emit(hipStream_t s, const void *planes, const uint32_t *runtab, const uint4 *state16, uint32_t cap, const uint64_t *tile_bitoff,
                        const uint64_t *plane_base, const uint64_t *plane_carry, const Geometry &g, uint8_t *index, uint32_t segment_pixels);
 
+// The same for a MIXED 8-bit sub-batch (felics_compress_views_device_indexed): every plane has a row of its own beside its PlaneGeom
+// row -- a row type of its own, the tables the encode kernels load stay as they are.  index: the IMAGE's index (16-byte aligned,
+// zeroed beforehand; nullptr: this image gets none), the rest its layout (index_layout of the image's own W, H and segment).
+struct IndexGeom {
+    uint8_t *index;
+    uint32_t K, seg_tiles;       // checkpoints per plane, tiles between two of them
+    uint64_t cp_bytes, win_off;  // bytes of a checkpoint; where its window starts
+};
+void launch_index_emit_mixed(hipStream_t s, const uint32_t *runtab, const uint4 *state16, uint32_t cap, const uint64_t *tile_bitoff,
+                             const uint64_t *plane_base, const uint64_t *plane_carry, const Geometry &g, const IndexGeom *rows, uint32_t max_K);
+
 // k_map / plane / slot buffers are read in whole 16-byte chunks by the tile staging
 constexpr size_t STAGE_PAD = 64;
 

@@ -1,6 +1,8 @@
 // felics_mixed.cpp -- images of different shapes in one call (felics_compress_images*) and strided views of device surfaces
-// (felics_compress_views_device): buckets, the mixed sub-batches' plane tables, landing and remedies.
+// (felics_compress_views_device): buckets, the mixed sub-batches' plane tables, landing and remedies; the restart indexes of
+// such a call (felics_compress_views_device_indexed, felics_index_plan).
 #include "felics_host.h"
+#include "felics_index.h"
 #include "felics_viewcheck.h"
 
 namespace felics {
@@ -79,7 +81,18 @@ struct MixOut {
     const uint64_t *off, *slot;
     uint64_t *lens;
     bool overflow;
+    bool want_index = true;  // the images' restart indexes as well (MixImage::index); false: a run for the sizes alone
 };
+
+// image m's index is to be written by this run
+bool wants_index(const MixImage &m, const MixOut &o) { return o.want_index && m.index != nullptr; }
+
+// an index has been written by a kernel (felics_index_emit_stats)
+void count_index(felics_ctx *ctx, const MixImage &m, bool mixed) {
+    ctx->iestats.indexes++;
+    ctx->iestats.checkpoints += (uint64_t)m.planes * index_layout(m.w, m.h, (uint32_t)m.color, m.segment_pixels).K;
+    (mixed ? ctx->iestats.in_mixed : ctx->iestats.redone)++;
+}
 
 // a view's dense copy in a mixed 16-bit job's part of mix_in: 256-byte steps
 size_t gather_step(const MixImage &m) { return m.view && !m.wide_in_place ? (m.frame_bytes + 255) & ~(size_t)255 : 0; }
@@ -101,7 +114,9 @@ int begin_mixed(felics_ctx *ctx, Lane &l, const std::vector<MixImage> &im, const
     int rc;
     if (f.planes == 3 && (rc = reserve(ctx, l.planes, (size_t)g.nplanes * g.npix * (depth == FELICS_DEPTH_16 ? 4 : 2) + STAGE_PAD)) != 0) return rc;
     static_assert(sizeof(PitchedGeom) >= sizeof(ViewRow) && sizeof(PlaneGeom) % 8 == 0, "one extra row per plane holds either");
-    if ((rc = reserve_pinned(ctx, (void **)&l.h_table, l.h_table_cap, g.nplanes, (size_t)g.nplanes * (sizeof(PlaneGeom) + sizeof(PitchedGeom)))) != 0)
+    // (... and one IndexGeom per plane for the indexes of felics_compress_views_device_indexed)
+    if ((rc = reserve_pinned(ctx, (void **)&l.h_table, l.h_table_cap, g.nplanes,
+                             (size_t)g.nplanes * (sizeof(PlaneGeom) + sizeof(PitchedGeom) + sizeof(IndexGeom)))) != 0)
         return rc;
     if ((rc = reserve(ctx, l.mtable, tbytes)) != 0) return rc;
     if ((rc = wait_ready(ctx, s)) != 0) return rc;
@@ -141,7 +156,11 @@ int launch_mixed(felics_ctx *ctx, Lane &l, const std::vector<MixImage> &im, cons
     bool any_view = false;
     for (size_t i : idx) any_view = any_view || im[i].view;
     const size_t extra_off = cnt * planes * sizeof(PlaneGeom);
-    const size_t tbytes = extra_off + (any_view ? (planes == 1 ? cnt * sizeof(PitchedGeom) : cnt * sizeof(ViewRow)) : 0);
+    bool any_index = false;
+    for (size_t i : idx) any_index = any_index || wants_index(im[i], o);
+    static_assert(sizeof(PitchedGeom) % 8 == 0 && sizeof(ViewRow) % 8 == 0, "the IndexGeom rows behind them hold pointers");
+    const size_t index_off = extra_off + (any_view ? (planes == 1 ? cnt * sizeof(PitchedGeom) : cnt * sizeof(ViewRow)) : 0);
+    const size_t tbytes = index_off + (any_index ? cnt * planes * sizeof(IndexGeom) : 0);
     hipStream_t fs = ctx->serial ? l.stream : l.front;
     uint64_t max_npix;
     int rc = begin_mixed(ctx, l, im, idx, FELICS_DEPTH_8, nslices, fs, tbytes, max_npix);
@@ -153,8 +172,20 @@ int launch_mixed(felics_ctx *ctx, Lane &l, const std::vector<MixImage> &im, cons
         plane_rows(l, j, m, m.px, 2, o, idx[j]);
         if (any_view && planes == 1) h_pitched[j] = PitchedGeom{l.h_table[j], m.pitch ? m.pitch : (uint64_t)m.w};  // (a dense plane: pitch = W)
         if (any_view && planes == 3) h_views[j] = m.view ? m.vr : ViewRow{m.px, 3ll * m.w, 3, 1};
+        if (!any_index) continue;
+        // the image's index, one row per plane (uploaded with the table: on the front stream, behind the ready event); its range is
+        // zeroed and the rows are read on the tail stream, behind the sub-batch's last pack kernel (run_lane)
+        IndexGeom ig{};
+        if (wants_index(m, o)) {
+            const IndexLayout L = index_layout(m.w, m.h, (uint32_t)m.color, m.segment_pixels);
+            ig = IndexGeom{m.index, L.K, m.segment_pixels / SORT_TILE, L.cp_bytes, L.win_off};
+            l.idx_max_K = std::max(l.idx_max_K, L.K);
+            l.idx_zero.emplace_back(m.index, (size_t)L.total);
+        }
+        for (uint32_t c = 0; c < planes; c++) ((IndexGeom *)((uint8_t *)l.h_table + index_off))[j * planes + c] = ig;
     }
     if ((rc = upload_table(ctx, l, tbytes, fs)) != 0) return rc;
+    if (any_index) l.idx_rows = (const IndexGeom *)((const uint8_t *)l.mtable.p + index_off);
     Geometry &g = l.g;
     if (any_view && planes == 1) g.pitched = (const PitchedGeom *)((const uint8_t *)l.mtable.p + extra_off);
     if (planes == 3) {
@@ -239,7 +270,9 @@ int redo_by_shape(felics_ctx *ctx, Lane &l, const std::vector<MixImage> &im, con
         std::vector<size_t> grp, other;
         for (size_t i : rest) {
             const MixImage &m = im[i];
-            (m.w == f.w && m.h == f.h && m.color == f.color && m.depth == f.depth ? grp : other).push_back(i);
+            const bool same = m.w == f.w && m.h == f.h && m.color == f.color && m.depth == f.depth;
+            // (the uniform writer takes one segment per call: images that want indexes are grouped by their segment as well)
+            (same && (wants_index(m, o) ? m.segment_pixels : 0u) == (wants_index(f, o) ? f.segment_pixels : 0u) ? grp : other).push_back(i);
         }
         rest.swap(other);
         const size_t cnt = grp.size();
@@ -250,8 +283,21 @@ int redo_by_shape(felics_ctx *ctx, Lane &l, const std::vector<MixImage> &im, con
         HIP_TRY(ctx, hipStreamSynchronize(l.stream));
         std::vector<uint64_t> offs(cnt), lens(cnt);
         uint8_t *used = nullptr;
-        if ((rc = encode_device(ctx, l, cnt, ctx->mix_redo.p, f.w, f.h, f.color, f.depth, nullptr, 0, offs.data(), lens.data(), &used)) != 0)
+        // the group's indexes back to back in a buffer of the context, then each to where the caller wants it
+        IndexRequest req{nullptr, 0, 0};
+        if (wants_index(f, o)) {
+            req.bytes = index_layout(f.w, f.h, (uint32_t)f.color, f.segment_pixels).total;
+            req.segment_pixels = f.segment_pixels;
+            if ((rc = reserve(ctx, ctx->mix_index, (size_t)(req.bytes * cnt))) != 0) return rc;
+            req.d_index = (uint8_t *)ctx->mix_index.p;
+        }
+        if ((rc = encode_device(ctx, l, cnt, ctx->mix_redo.p, f.w, f.h, f.color, f.depth, nullptr, 0, offs.data(), lens.data(), &used, false,
+                                req.d_index ? &req : nullptr)) != 0)
             return rc;
+        for (size_t j = 0; j < cnt && req.d_index; j++) {  // (encode_device has waited for its writer; copy_to_slots waits for these)
+            HIP_TRY(ctx, hipMemcpyAsync(im[grp[j]].index, req.d_index + j * req.bytes, (size_t)req.bytes, hipMemcpyDeviceToDevice, l.stream));
+            count_index(ctx, im[grp[j]], false);
+        }
         if ((rc = copy_to_slots(ctx, l, grp, used, offs.data(), lens.data(), o)) != 0) return rc;  // (waits: ctx->own is reused by the next group)
     }
     return FELICS_OK;
@@ -289,6 +335,8 @@ int land_job(felics_ctx *ctx, MixJob &j, const std::vector<MixImage> &im, MixOut
     if (!so.redo() && !so.overflow && !so.spine_error) {
         if (j.wide_mixed && ctx->profiling && (rc = sync_lane(ctx, l)) != 0) return rc;  // (run_wide records span_end behind `sized`)
         collect_timing(ctx, l);
+        for (size_t i : j.idx)  // (the mixed writers ran in front of `sized`: the indexes are complete)
+            if (!j.wide_mixed && wants_index(im[i], o)) count_index(ctx, im[i], true);
         return FELICS_OK;
     }
     if ((rc = sync_lane(ctx, l)) != 0) return rc;
@@ -364,6 +412,11 @@ int run_images(felics_ctx *ctx, const std::vector<MixImage> &im, MixOut &o) {
                                 &len, nullptr)) != 0)
             return rc;
         o.lens[i] = len;
+        if (wants_index(im[i], o)) {  // (K = 0: the header alone, built on the host as felics_compress_batch_device_indexed builds it)
+            uint8_t ih[INDEX_HEADER_BYTES];
+            empty_index(ih, im[i].w, im[i].h, (uint32_t)im[i].color, im[i].segment_pixels);
+            HIP_TRY(ctx, hipMemcpy(im[i].index, ih, INDEX_HEADER_BYTES, hipMemcpyHostToDevice));
+        }
     }
     const int nslices = jobs.size() > 1 || ctx->only_lane >= 0 ? ctx->slices_queued : ctx->slices_blocking;
     std::vector<size_t> flying;  // jobs in flight, oldest first (lanes handed out in turn: the oldest holds the next lane)
@@ -439,6 +492,7 @@ int images_device(felics_ctx *ctx, const std::vector<MixImage> &im, uint8_t *d_o
     if (total > d_out_cap) {  // the sizes first, into a buffer of the library's own
         if ((rc = reserve(ctx, ctx->mix_out, (size_t)total + 64)) != 0) return rc;
         o.base = (uint8_t *)ctx->mix_out.p;
+        o.want_index = false;  // (the run below places the streams and writes the indexes that remain)
     }
     if ((rc = run_images(ctx, im, o)) != 0) return rc;
     if (o.base == d_out && !o.overflow) {
@@ -485,8 +539,14 @@ int check_view(const felics_view &v, int64_t &lo, int64_t &hi, bool encode_limit
     return view_hull(v, lo, hi);
 }
 
+// (ask: felics_compress_views_device_indexed -- view i's index at d_index + offsets[i], segment_pixels[i] pixels per segment, 0: none)
+struct IndexAsk {
+    uint8_t *d_index;
+    const uint64_t *offsets;
+    const uint32_t *segment_pixels;
+};
 int views_device(felics_ctx *ctx, size_t n, const felics_view *views, void *ready_event, void *d_out, size_t d_out_cap, uint64_t *offsets,
-                 uint64_t *lens, felics_view_stats &counted);
+                 uint64_t *lens, felics_view_stats &counted, const IndexAsk *ask = nullptr);
 
 // felics_surfaces_extent: the view's checks on frame 0, the frame axis, and the hull of all frames' sample bytes relative to frame0.data.
 int check_surfaces(const felics_surfaces &s, int64_t &lo, int64_t &hi) {
@@ -733,6 +793,73 @@ int felics_compress_views_device(felics_ctx *ctx, size_t n, const felics_view *v
     return rc;
 }
 
+// A view's segment by felics_index_plan's rules (the view has passed check_view): the size of its index, 0 for segment 0.
+static int index_ask_check(const felics_view &v, uint32_t seg, uint64_t &bytes) {
+    bytes = 0;
+    if (seg == 0) return FELICS_OK;
+    if (!index_segment_ok(seg)) return FELICS_E_INVALID_ARGUMENT;
+    if (v.depth != FELICS_DEPTH_8) return FELICS_E_UNSUPPORTED;  // 16-bit streams have no index
+    bytes = index_layout(v.width, v.height, (uint32_t)v.color, seg).total;
+    return FELICS_OK;
+}
+
+int felics_index_plan(size_t n, const felics_view *views, const uint32_t *segment_pixels, uint64_t *idx_offsets, uint64_t *idx_lens,
+                      uint64_t *total) {
+    if (!total || (n && (!views || !segment_pixels || !idx_offsets || !idx_lens))) return FELICS_E_INVALID_ARGUMENT;
+    *total = 0;
+    uint64_t at = 0;
+    for (size_t i = 0; i < n; i++) {
+        int64_t lo, hi;
+        int rc = check_view(views[i], lo, hi);
+        if (rc) return rc;
+        if ((rc = index_ask_check(views[i], segment_pixels[i], idx_lens[i])) != 0) return rc;
+        idx_offsets[i] = at;
+        at += (idx_lens[i] + 15) & ~15ull;
+    }
+    *total = at;
+    return FELICS_OK;
+}
+
+int felics_get_index_emit_stats(const felics_ctx *ctx, felics_index_emit_stats *out, size_t out_size) {
+    if (!ctx || !out) return FELICS_E_INVALID_ARGUMENT;
+    memcpy(out, &ctx->iestats, std::min(out_size, sizeof(felics_index_emit_stats)));
+    return FELICS_OK;
+}
+
+int felics_compress_views_device_indexed(felics_ctx *ctx, size_t n, const felics_view *views, const uint32_t *segment_pixels,
+                                         void *ready_event, void *d_out, size_t d_out_cap, void *d_index, size_t d_index_cap,
+                                         const uint64_t *idx_offsets, uint64_t *offsets, uint64_t *lens) {
+    if (!ctx || (n && (!views || !segment_pixels || !idx_offsets || !d_out || !offsets || !lens))) return FELICS_E_INVALID_ARGUMENT;
+    if (ctx->failed) return FELICS_E_HIP;
+    std::vector<std::pair<uint64_t, uint64_t>> ranges;  // the indexes asked for: offset, bytes
+    for (size_t i = 0; i < n; i++) {  // every view and its segment checked before anything is launched: the first error in view order
+        int64_t lo, hi;
+        uint64_t bytes;
+        int rc = check_view(views[i], lo, hi);
+        if (rc) return rc;
+        if ((rc = index_ask_check(views[i], segment_pixels[i], bytes)) != 0) return rc;
+        if (bytes) ranges.emplace_back(idx_offsets[i], bytes);
+    }
+    if (!ranges.empty() && !d_index) return FELICS_E_INVALID_ARGUMENT;
+    for (const auto &r : ranges)  // (the writers store aligned words)
+        if (((uintptr_t)d_index + r.first) & 15u) return FELICS_E_INVALID_ARGUMENT;
+    for (const auto &r : ranges)
+        if (r.first > d_index_cap || r.second > d_index_cap - r.first) return FELICS_E_BUFFER_TOO_SMALL;
+    std::sort(ranges.begin(), ranges.end());
+    for (size_t k = 1; k < ranges.size(); k++)
+        if (ranges[k - 1].first + ranges[k - 1].second > ranges[k].first) return FELICS_E_INVALID_ARGUMENT;
+    if (n == 0) return FELICS_OK;
+    if (any_pending(ctx)) return FELICS_E_INVALID_ARGUMENT;  // felics_wait_batch first
+    felics_view_stats add = {};
+    const IndexAsk ask{(uint8_t *)d_index, idx_offsets, segment_pixels};
+    const int rc = views_device(ctx, n, views, ready_event, d_out, d_out_cap, offsets, lens, add, &ask);
+    ctx->vstats.views += add.views;  // (bytes_staged: stage_frame has counted)
+    ctx->vstats.dense += add.dense;
+    ctx->vstats.in_place += add.in_place;
+    ctx->vstats.gathered += add.gathered;
+    return rc;
+}
+
 }  // extern "C"
 
 namespace felics {
@@ -740,7 +867,7 @@ namespace felics {
 // felics_compress_views_device behind its checks; `add` = the classes of the views (counted once the gathering has succeeded).  Also
 // the immediate case of felics_submit_surfaces_device (ctx->only_lane: the one lane it may use).
 int views_device(felics_ctx *ctx, size_t n, const felics_view *views, void *ready_event, void *d_out, size_t d_out_cap, uint64_t *offsets,
-                 uint64_t *lens, felics_view_stats &counted) {
+                 uint64_t *lens, felics_view_stats &counted, const IndexAsk *ask) {
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     // the class of every view: dense, read in place, or gathered (gray8 now, into view_stage; 16-bit where its group is queued)
     std::vector<MixImage> im(n);
@@ -751,6 +878,10 @@ int views_device(felics_ctx *ctx, size_t n, const felics_view *views, void *read
         const felics_view &v = views[i];
         MixImage &m = im[i];
         m = mix_image(felics_image{v.data, v.width, v.height, v.color, v.depth});
+        if (ask && ask->segment_pixels[i]) {
+            m.index = ask->d_index + ask->offsets[i];
+            m.segment_pixels = ask->segment_pixels[i];
+        }
         const int64_t bytes = v.depth == FELICS_DEPTH_16 ? 2 : 1;
         const bool rgb = v.color == FELICS_COLOR_RGB;
         add.views++;

@@ -600,8 +600,8 @@ int felics_get_decode_view_stats(const felics_ctx *ctx, felics_decode_view_stats
  *                 a stream, an index or a view is touched in this call, the two header kernels included.
  * The stream headers and the first 64 bytes of every index are read by two kernels and come back in one synchronise; no header is
  * fetched with a blocking copy.  The call is blocking: the views are complete when it returns.  It creates no HIP stream.
- * NOT HERE: a lane-per-segment form, regions into views, a queued form, 16-bit streams, streams without an index in the same call,
- * an indexed encode of views or mixed shapes. */
+ * NOT HERE: a lane-per-segment form, regions into views, a queued form, 16-bit streams, streams without an index in the same call.
+ * (The encode side of this call is felics_compress_views_device_indexed, below.) */
 int felics_decompress_views_device_indexed(felics_ctx *ctx, size_t n, const void *d_streams, const uint64_t *offsets, const uint64_t *lens,
                                            const void *d_index, const uint64_t *idx_offsets, const uint64_t *idx_lens,
                                            const felics_view *views, void *ready_event, felics_header *hdrs /* optional */, int *status);
@@ -627,6 +627,49 @@ typedef struct felics_index_view_stats {
 } felics_index_view_stats;
 /* Writes min(out_size, sizeof(felics_index_view_stats)) bytes, never more. */
 int felics_get_index_view_stats(const felics_ctx *ctx, felics_index_view_stats *out, size_t out_size);
+
+/* ---- Restart index: written while encoding views and mixed shapes ----
+ * Host only, no device: where the indexes of n views go in one buffer.  segment_pixels[i] is view i's segment (a positive multiple of
+ * FELICS_INDEX_GRANULE), or 0: no index for view i.  idx_lens[i] = felics_index_size of view i's shape and segment (0 for segment 0),
+ * idx_offsets[i] = the running sum of the lengths before it, each rounded up to 16 (a view without an index gets the offset the next
+ * index will get and does not advance it), *total = the end: the capacity felics_compress_views_device_indexed needs.  The first error
+ * in view order: the view's own code where felics_view_extent refuses it, FELICS_E_INVALID_ARGUMENT for a non-zero segment that is
+ * not a positive multiple of FELICS_INDEX_GRANULE (and for NULL arrays with n > 0), FELICS_E_UNSUPPORTED for a 16-bit view with a
+ * non-zero segment (16-bit streams have no index). */
+int felics_index_plan(size_t n, const felics_view *views, const uint32_t *segment_pixels, uint64_t *idx_offsets, uint64_t *idx_lens,
+                      uint64_t *total);
+
+/* felics_compress_views_device plus, for every view with segment_pixels[i] != 0, the restart index of stream i at
+ * d_index + idx_offsets[i] (felics_index_size bytes): views of any shapes, colours, layouts and segments in one call.  The streams
+ * are byte-identical to felics_compress_views_device's and every index to felics_index_build(stream i, segment_pixels[i]).
+ * Everything felics_compress_views_device says holds: the classes of the views, slots and the exact second run (the indexes of the
+ * run that places the streams are the ones that remain), the remedies of felics_stats, ready_event (d_index counts as d_out does:
+ * nothing of it is touched before the event), refusal while a ticket is outstanding, zero-sized views (which get the 64-byte index
+ * of an empty image, built on the host).  16-bit views and 8-bit views with segment_pixels[i] == 0 take part and get their streams
+ * as ever.  segment_pixels and idx_offsets are HOST arrays of n entries (felics_index_plan fills idx_offsets; any other placement
+ * that passes the checks will do); d_index may be NULL if no view asks for an index.
+ * Checked before anything is launched, beside felics_compress_views_device's checks: segment_pixels by felics_index_plan's rules
+ * (16-bit views included); d_index + idx_offsets[i] a multiple of 16 (FELICS_E_INVALID_ARGUMENT); every index inside d_index_cap
+ * (FELICS_E_BUFFER_TOO_SMALL); no two indexes overlapping (FELICS_E_INVALID_ARGUMENT).  No byte of d_index outside the indexes' own
+ * ranges is written.
+ * How the indexes are written (felics_get_index_emit_stats counts them): the mixed sub-batches of the call compute everything an
+ * index holds, and two kernels per sub-batch collect it for all its images (k_index_states_mixed, k_index_windows_mixed:
+ * felics_index.hip), reading the windows where the views lie; a sub-batch that is redone by a remedy gets its indexes from the
+ * writer of felics_compress_batch_device_indexed, one shape and segment at a time. */
+int felics_compress_views_device_indexed(felics_ctx *ctx, size_t n, const felics_view *views, const uint32_t *segment_pixels,
+                                         void *ready_event, void *d_out, size_t d_out_cap, void *d_index, size_t d_index_cap,
+                                         const uint64_t *idx_offsets, uint64_t *offsets, uint64_t *lens);
+
+/* What a context's felics_compress_views_device_indexed calls wrote so far (cumulative). */
+typedef struct felics_index_emit_stats {
+    uint64_t indexes;      /* indexes written by kernels (an index written again by a second run or a remedy counts again; the
+                              host-built ones of zero-sized views do not count) */
+    uint64_t checkpoints;  /* their checkpoints: the sum of C * K */
+    uint64_t in_mixed;     /* indexes written by the mixed kernels */
+    uint64_t redone;       /* indexes written by the uniform writer inside a remedy */
+} felics_index_emit_stats;
+/* Writes min(out_size, sizeof(felics_index_emit_stats)) bytes, never more. */
+int felics_get_index_emit_stats(const felics_ctx *ctx, felics_index_emit_stats *out, size_t out_size);
 
 /* Text for a code above; for FELICS_E_HIP felics_last_error(ctx) has the HIP message. */
 const char *felics_strerror(int code);
