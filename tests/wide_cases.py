@@ -86,8 +86,9 @@ def replay(es, rule="true", at=None, halvings=None):
     return out
 
 
-def replay_records(ev):
-    """k of every record of a plane by the true rule, all chains side by side (numpy over the chains, one step per chain index)."""
+def replay_records(ev, nk=NK):
+    """k of every record of a plane by the true rule, all chains side by side (numpy over the chains, one step per chain index);
+    nk counters (the 8-bit estimator has six: tests/chain_cases.py)."""
     val = ev["val"][ev["order"]]
     _, first, length = chains_of(ev)
     out = np.zeros(len(val), np.int64)
@@ -95,13 +96,13 @@ def replay_records(ev):
         return out
     by_len = np.argsort(-length, kind="stable")
     first, length = first[by_len], length[by_len]
-    S = np.zeros((len(first), NK), np.int64)
-    ks = np.arange(NK)
+    S = np.zeros((len(first), nk), np.int64)
+    ks = np.arange(nk)
     for t in range(int(length[0])):
         n = int(np.searchsorted(-length, -t, side="left"))  # chains longer than t: a prefix
         A = S[:n]
         at = first[:n] + t
-        out[at] = NK - 1 - np.argmin(A[:, ::-1], axis=1)
+        out[at] = nk - 1 - np.argmin(A[:, ::-1], axis=1)
         A += (val[at][:, None] >> ks) + 1 + ks
         A[A.min(axis=1) > HALVE] >>= 1
     return out
