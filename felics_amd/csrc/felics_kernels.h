@@ -143,7 +143,7 @@ inline uint32_t tile_cap_max(uint32_t nctx, uint32_t npix) {
 }
 inline uint32_t tile_cap_default(uint32_t nctx, uint32_t npix) { return std::min(nctx == 256 ? 6144u : 8192u, tile_cap_max(nctx, npix)); }
 constexpr uint32_t TL_FLAG_ORDER = 1u, TL_FLAG_OVERFLOW = 2u, TL_FLAG_SPINE = 4u;
-constexpr uint32_t FRONT_TEST_VIOLATION = 1u, FRONT_SAFE_RANK = 2u;  // k_front's `mode` bits
+constexpr uint32_t FRONT_TEST_VIOLATION = 1u, FRONT_SAFE_RANK = 2u;  // launch_front's `mode` bits (FRONT_SAFE_RANK: which k_front instantiation)
 
 template <typename ET>
 struct TileLocal {

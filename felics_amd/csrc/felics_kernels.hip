@@ -188,6 +188,9 @@ constexpr uint32_t BT_SEL = 0xE4;      // c ? a : b  =  (a & c) | (b & ~c)
 constexpr uint32_t BT_OR_ANDN = 0xF4;  // a | (b & ~c)
 constexpr uint32_t BT_ANDN = 0x30;     // a & ~b
 constexpr uint32_t BT_OR3 = 0xFE;      // a | b | c
+constexpr uint32_t BT_SEL_NOT = 0x72;  // c ? ~b : a
+constexpr uint32_t BT_NOR = 0x03;      // ~(a | b)
+constexpr uint32_t BT_OR_AND = 0xF8;   // a | (b & c)
 __device__ __forceinline__ uint32_t min_u16(uint32_t a, uint32_t b) {  // operands < 2^16
     uint32_t r;
     asm("v_min_u16 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
@@ -196,6 +199,12 @@ __device__ __forceinline__ uint32_t min_u16(uint32_t a, uint32_t b) {  // operan
 __device__ __forceinline__ uint32_t max_u16(uint32_t a, uint32_t b) {
     uint32_t r;
     asm("v_max_u16 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
+    return r;
+}
+template <uint32_t N>
+__device__ __forceinline__ uint32_t shl_u16(uint32_t a) {  // a << N where the result is < 2^16 (the 32-bit shift is of the 1.7 ns class)
+    uint32_t r;
+    asm("v_lshlrev_b16 %0, %1, %2" : "=v"(r) : "n"(N), "v"(a));
     return r;
 }
 __device__ __forceinline__ uint32_t twice(uint32_t a) {  // a + a as an add (the compiler would make it a left shift)
@@ -253,14 +262,22 @@ __device__ __forceinline__ uint32_t field_of(int v, int16_t) { return ((uint32_t
 //      tiles.  Each event is compared with its successor: (context, pixel offset) must ascend strictly.  That is exactly
 //      "stable partition": the set of events of a context is fixed by the counts, and ascending pixel offsets are the one
 //      raster order of that set.  A violation raises TL_FLAG_ORDER; the host then redoes the batch with ranks from ballots.
-//   mode & FRONT_SAFE_RANK: ranks from ballots instead of the returning add (a context's fallback once the order check has
-//   failed: no assumption about the LDS); mode & FRONT_TEST_VIOLATION: report a violation whatever the order (tests).
+//   BALLOT (the launcher's mode & FRONT_SAFE_RANK picks the instantiation): ranks from ballots instead of the returning add (a
+//   context's fallback once the order check has failed: no assumption about the LDS); mode & FRONT_TEST_VIOLATION, read once
+//   behind the loops: report a violation whatever the order (tests).
 //
 // Record in LDS: context << 22 | value << 13 | above << 12 | pixel offset in the tile (9 + 9 + 1 + 12 bits; above = the sample lies
 // above its neighbours, the second flag bit of its code: compression.rs:139-144).  pix[slot] = the low 13 bits.
 // The chain of a context is the sequence of its runs over the tiles (felics_chain.hip).
 // (six workgroups per CU is what the LDS allows -- five for Y / Co / Cg planes -- and the registers are held to that)
 // ------------------------------------------------------------------------------------------
+// The instruction forms of profiles/front_pack_forms.txt, one bit a part (A/B builds: profiles/tools/variant.sh -DFELICS_FORMS=n):
+//   1  k_front: the rank form is a template parameter        2  k_front: scalar row bases, the lane as the loads' one offset
+//   4  k_front: cheap forms in the interior loop             8  k_pack_t: load_group from scalar bases
+//   16 code_pixel: cheap forms
+#ifndef FELICS_FORMS
+#define FELICS_FORMS 31
+#endif
 #ifndef FELICS_FRONT_WAVES
 #define FELICS_FRONT_WAVES 6  // (gray planes; what the LDS allows.  A/B builds: profiles/tools/variant.sh)
 #endif
@@ -301,7 +318,9 @@ __device__ __forceinline__ uint64_t plane_pitch(const PitchedGeom *rows, uint32_
 }
 // (S: const T * -- the uniform planes --, const PlaneGeom * -- a mixed sub-batch's table; W and npix are then unused -- or
 // const PitchedGeom *: the table of a sub-batch with pitched planes)
-template <typename T, typename ET, typename S>
+// (BALLOT: the rank form, chosen by the launcher from its mode -- the interior loop of the returning-add form then holds no
+// branch and nothing between its adds)
+template <typename T, typename ET, typename S, bool BALLOT>
 __attribute__((amdgpu_waves_per_eu(sizeof(T) == 1 ? FELICS_FRONT_WAVES : 5))) __global__ __launch_bounds__(256) void k_front(
     S __restrict__ planes, ET *__restrict__ ev, uint16_t *__restrict__ pix, uint32_t *__restrict__ runtab,
     uint32_t *__restrict__ tile_slots, uint32_t W_, uint32_t npix_, uint32_t ntiles, uint32_t tile_begin, uint32_t tile_end,
@@ -342,7 +361,7 @@ __attribute__((amdgpu_waves_per_eu(sizeof(T) == 1 ? FELICS_FRONT_WAVES : 5))) __
     const uint32_t begin = tile * SORT_TILE;
     const uint32_t qbegin = min(begin + wave * QUARTER, npix);
     const uint32_t end = min(qbegin + QUARTER, npix);  // of this wave's quarter
-    const bool safe_rank = (mode & FRONT_SAFE_RANK) != 0;
+    const bool safe_rank = (FELICS_FORMS & 1) ? BALLOT : (mode & FRONT_SAFE_RANK) != 0;
     // ---- 1, 2. classify and rank, no compaction: a trip is 256 consecutive pixels, lane l takes pixels l, l + 64, l + 128, l + 192
     // of it -- so that the raster order of a trip's pixels is (sub-row, lane) and ONE returning LDS add per sub-row ranks its events
     // within (wave, context) in raster order (ascending lanes).  Every pixel keeps a static slot of this lane: its record
@@ -356,13 +375,28 @@ __attribute__((amdgpu_waves_per_eu(sizeof(T) == 1 ? FELICS_FRONT_WAVES : 5))) __
         uint32_t cur[4], up[4], left0;
     };
     auto load_trip = [&](Index r, Index left_index, Trip &t) {
+        if constexpr ((FELICS_FORMS & 2) != 0) {
+            // (r is wave-uniform: the trip's row and the row above it as 64-bit bases in scalar registers, the lane as the one
+            // 32-bit vector offset of all eight loads, 64 * j as their immediates -- no vector address arithmetic per load, and
+            // no bound on where the plane lies)
+            const T *row = pl + r, *above = row - W;
+            if constexpr (PITCHED) above = row - pitch;
+            uint32_t at = lane;
+            asm volatile("" : "+v"(at));  // (named here: the offset's extension to 64 bits stays next to the loads that fold it away)
 #pragma unroll
-        for (uint32_t j = 0; j < 4; j++) {
-            t.cur[j] = field_of((int)pl[r + 64 * j + lane], T());
-            if constexpr (PITCHED)
-                t.up[j] = field_of((int)pl[r + 64 * j + lane - pitch], T());
-            else
-                t.up[j] = field_of((int)pl[r + 64 * j + lane - W], T());
+            for (uint32_t j = 0; j < 4; j++) {
+                t.cur[j] = field_of((int)(row + 64 * j)[at], T());
+                t.up[j] = field_of((int)(above + 64 * j)[at], T());
+            }
+        } else {
+#pragma unroll
+            for (uint32_t j = 0; j < 4; j++) {
+                t.cur[j] = field_of((int)pl[r + 64 * j + lane], T());
+                if constexpr (PITCHED)
+                    t.up[j] = field_of((int)pl[r + 64 * j + lane - pitch], T());
+                else
+                    t.up[j] = field_of((int)pl[r + 64 * j + lane - W], T());
+            }
         }
         t.left0 = field_of((int)pl[left_index], T());  // (the same address in every lane)
     };
@@ -420,14 +454,30 @@ __attribute__((amdgpu_waves_per_eu(sizeof(T) == 1 ? FELICS_FRONT_WAVES : 5))) __
                 const uint32_t ctx = H - L;
                 const int dd = (int)(p - L);         // in range: 0 <= dd <= ctx
                 const int below = dd >> 31;          // all ones: p < L
-                const int o = (int)(p - H) - 1;      // >= 0: p > H
-                const int not_above = o >> 31;
-                const uint32_t val = bitop3<BT_SEL>((uint32_t)(dd ^ below), (uint32_t)o, (uint32_t)not_above);  // L - p - 1 | p - L | p - H - 1
-                const uint32_t in_range = bitop3<BT_ANDN>((uint32_t)not_above, (uint32_t)below, 0u);               // all ones: no event
-                const uint32_t off = (row0 - begin + 64 * j + lane) | bitop3<BT_ANDN>(0x1000u, (uint32_t)not_above, 0u);  // | above << 12
-                rec[d * 4 + j] = ((ctx << 22) | (val << 13) | off) | in_range;
+                uint32_t val, in_range, above12, ctx4;
+                if constexpr ((FELICS_FORMS & 4) != 0) {
+                    // p - H - 1 = ~(H - p): the subtraction the other way round and the NOTs in the tables, not a v_xad_u32
+                    const uint32_t t = H - p;
+                    const uint32_t above = (uint32_t)((int)t >> 31);  // all ones: p > H
+                    val = bitop3<BT_SEL_NOT>((uint32_t)(dd ^ below), t, above);  // L - p - 1 | p - L | p - H - 1
+                    in_range = bitop3<BT_NOR>(above, (uint32_t)below, 0u);      // all ones: no event
+                    above12 = above & 0x1000u;
+                    ctx4 = shl_u16<2>(ctx);  // (the counter's offset as a 16-bit shift: ctx < 2^9)
+                } else {
+                    const int o = (int)(p - H) - 1;  // >= 0: p > H
+                    const int not_above = o >> 31;
+                    val = bitop3<BT_SEL>((uint32_t)(dd ^ below), (uint32_t)o, (uint32_t)not_above);
+                    in_range = bitop3<BT_ANDN>((uint32_t)not_above, (uint32_t)below, 0u);
+                    above12 = bitop3<BT_ANDN>(0x1000u, (uint32_t)not_above, 0u);
+                    ctx4 = ctx << 2;
+                }
+                const uint32_t off = row0 - begin + 64 * j + lane;
+                if constexpr ((FELICS_FORMS & 4) != 0)  // (the ORs as v_bitop3_b32)
+                    rec[d * 4 + j] = bitop3<BT_OR3>(bitop3<BT_OR3>(ctx << 22, val << 13, off), above12, in_range);
+                else
+                    rec[d * 4 + j] = ((ctx << 22) | (val << 13) | off | above12) | in_range;
                 // rank: the counter of the event's context, or this lane's own
-                const uint32_t at = cnt_at + bitop3<BT_SEL>(dummy_at, ctx << 2, in_range);
+                const uint32_t at = cnt_at + bitop3<BT_SEL>(dummy_at, ctx4, in_range);
                 if (!safe_rank)
                     rk[d * 4 + j] = __hip_atomic_fetch_add((__attribute__((address_space(3))) uint32_t *)(uintptr_t)at, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
             }
@@ -1261,6 +1311,8 @@ __device__ __forceinline__ void clear_window(uint32_t (&win)[FUSED_WIN_WORDS + 2
 template <typename T> constexpr bool PACK_QUADS = sizeof(T) == 1 || (FELICS_PACK16_PARTS & 1) != 0;
 template <typename T> constexpr bool PACK_SHORT_FLUSH = sizeof(T) == 1 || (FELICS_PACK16_PARTS & 2) != 0;
 template <typename T> constexpr bool PACK_WIDE_CLEAR = sizeof(T) == 1 || (FELICS_PACK16_PARTS & 4) != 0;
+// (code_pixel's named forms and load_group_at, profiles/front_pack_forms.txt: the int16 kernels gained spills from either)
+template <typename T> constexpr bool PACK_CODE_FORMS = sizeof(T) == 1 && (FELICS_FORMS & 16) != 0;
 
 // Whether this thread's 16-pixel group takes the branch-free path (group_codes), and what that path needs from outside the
 // tile's LDS image: the position of the group's first-column pixel (PACK_PER_THREAD: none) and that pixel's second neighbour
@@ -1375,14 +1427,27 @@ static_assert(PACK_TILE == 4096 && PACK_PER_THREAD == 16, "word_index: 256 threa
 //   below / above: `00` / `01`, then L - p - 1 / p - H - 1 Rice-coded: q ones, `0`, k low bits (rice_coding.rs:26-38).
 // Both are built and one is kept.  A Rice code longer than 32 bits comes out as garbage with len > 32: the caller redoes
 // such a group the general way.  K31 = 0x80000000, K7F = 0x7FFFFFFF in vector registers (vgpr_const).
+// (FORMS: the three forms below that are not the compiler's own choice -- k_pack_t's 8-bit instantiations take them, the int16
+// ones, which spill at the first change, stay as they were: PACK_CODE_FORMS)
+template <bool FORMS>
 __device__ __forceinline__ PixelCode code_pixel(uint32_t p, uint32_t a, uint32_t b, uint32_t k, uint32_t K31, uint32_t K7F) {
     const uint32_t L = min_u16(a, b), H = max_u16(a, b);
     const uint32_t ctx = H - L;
     const int d = (int)(p - L);              // in range: 0 <= d <= ctx
     const int below = d >> 31;               // all ones: p < L
-    const int o = (int)p - (int)H - 1;       // >= 0: p > H
-    const int not_above = o >> 31;
-    const uint32_t val = bitop3<BT_SEL>((uint32_t)(d ^ below), (uint32_t)o, (uint32_t)not_above);  // ~d = L - p - 1 | d | p - H - 1
+    uint32_t val, in_range, above = 0;
+    int not_above = 0;
+    if constexpr (FORMS) {  // p - H - 1 = ~(H - p): the NOTs in the tables (k_front's interior loop has the same)
+        const uint32_t t = H - p;
+        above = (uint32_t)((int)t >> 31);  // all ones: p > H
+        val = bitop3<BT_SEL_NOT>((uint32_t)(d ^ below), t, above);  // ~d = L - p - 1 | d | p - H - 1
+        in_range = bitop3<BT_NOR>(above, (uint32_t)below, 0u);
+    } else {
+        const int o = (int)p - (int)H - 1;  // >= 0: p > H
+        not_above = o >> 31;
+        val = bitop3<BT_SEL>((uint32_t)(d ^ below), (uint32_t)o, (uint32_t)not_above);
+        in_range = bitop3<BT_ANDN>((uint32_t)not_above, (uint32_t)below, 0u);
+    }
     // phased-in
     const uint32_t n = ctx + 1u;
     const uint32_t z = (uint32_t)__builtin_clz(n);  // n >= 1
@@ -1396,10 +1461,12 @@ __device__ __forceinline__ PixelCode code_pixel(uint32_t p, uint32_t a, uint32_t
     // Rice
     const uint32_t q = val >> k;
     const uint32_t ones = K7F >> (31u - q);                                             // q ones (q <= 31)
-    const uint32_t head = bitop3<BT_OR_ANDN>(ones, ones + 1u, (uint32_t)not_above);    // `0` / `1` (above) in front of them
-    const uint32_t rice = bitop3<BT_OR_ANDN>(head << (k + 1u), val, ~0u << k);          // then `0` and the k low bits of val
+    const uint32_t head = FORMS ? bitop3<BT_OR_AND>(ones, ones + 1u, above)
+                                                   : bitop3<BT_OR_ANDN>(ones, ones + 1u, (uint32_t)not_above);  // `0` / `1` (above) in front of them
+    // then `0` and the k low bits of val: (head << (k + 1)) | (val & ~(~0u << k)) -- or, val being q << k | its low bits, one shift
+    // of 2 head - q and an add (two shifts fewer in the 1.7 ns class for one more add)
+    const uint32_t rice = FORMS ? ((twice(head) - q) << k) + val : bitop3<BT_OR_ANDN>(head << (k + 1u), val, ~0u << k);
     const uint32_t len_rice = q + k + 3u;
-    const uint32_t in_range = bitop3<BT_ANDN>((uint32_t)not_above, (uint32_t)below, 0u);
     const uint32_t code = bitop3<BT_SEL>(code_in, rice, in_range);
     PixelCode pc;
     pc.len = bitop3<BT_SEL>(len_in, len_rice, in_range);
@@ -1421,6 +1488,15 @@ __device__ __forceinline__ void load_group(const T *__restrict__ pl, uint32_t fi
     __builtin_memcpy(g.cw, pl + first, PACK_PER_THREAD * sizeof(T));      // (unaligned when W or the plane's base is odd: the hardware takes it)
     __builtin_memcpy(g.uw, pl + first - W, PACK_PER_THREAD * sizeof(T));
     g.before = (int)pl[first - 1];
+}
+// The same from the tile's first sample (wave-uniform: the tile and the span above it as 64-bit bases in scalar registers) and the
+// group's place in the tile: one 32-bit vector offset for the three loads, - 1 as an immediate.
+template <typename T>
+__device__ __forceinline__ void load_group_at(const T *__restrict__ tile, uint32_t in_tile, uint32_t W, GroupSamples<T> &g) {
+    const T *above = tile - W;
+    __builtin_memcpy(g.cw, tile + in_tile, PACK_PER_THREAD * sizeof(T));
+    __builtin_memcpy(g.uw, above + in_tile, PACK_PER_THREAD * sizeof(T));
+    g.before = (int)(tile - 1)[in_tile];
 }
 
 // Pitched: the group at `at`, a piece of one row -- or, 0 < j0 < 16, the last j0 samples of a row and the first 16 - j0 of the
@@ -1535,7 +1611,7 @@ __device__ __forceinline__ uint32_t group_codes_k(const GroupSamples<T> &g, cons
 #pragma unroll
     for (uint32_t j = 0; j < PACK_PER_THREAD; j++) {
         const uint32_t p = field_at(g.cw, j, T());
-        const PixelCode pc = code_pixel(p, left, field_at(g.uw, j, T()), field_at(kw, j, uint8_t()), K31, K7F);
+        const PixelCode pc = code_pixel<PACK_CODE_FORMS<T>>(p, left, field_at(g.uw, j, T()), field_at(kw, j, uint8_t()), K31, K7F);
         c32[j] = pc.c32;
         len[j] = pc.len;
         longest = max_u16(longest, pc.len);
@@ -1544,8 +1620,8 @@ __device__ __forceinline__ uint32_t group_codes_k(const GroupSamples<T> &g, cons
     if (__ballot(j0 < PACK_PER_THREAD) != 0) {  // (wave-uniform: a quarter of the waves of a 4K plane)
         if (j0 < PACK_PER_THREAD) {
             const IX i0 = first + j0;
-            const PixelCode pc = code_pixel(field_of((int)pl[i0], T()), field_of(special, T()), field_of((int)pl[i0 - W], T()),
-                                            (uint32_t)kq[off + j0], K31, K7F);
+            const PixelCode pc = code_pixel<PACK_CODE_FORMS<T>>(field_of((int)pl[i0], T()), field_of(special, T()), field_of((int)pl[i0 - W], T()),
+                                                                (uint32_t)kq[off + j0], K31, K7F);
 #pragma unroll
             for (uint32_t j = 0; j < PACK_PER_THREAD; j++) {
                 c32[j] = j == j0 ? pc.c32 : c32[j];
@@ -1949,14 +2025,18 @@ __attribute__((amdgpu_waves_per_eu(FELICS_PACK_WAVES))) __global__ __launch_boun
         if (gg.j0 - 1u < PACK_PER_THREAD - 1u) group_at += pitch - view.W;
     } else {
         gg = group_geometry<T>(pl, st, view.W, view.npix);
-        if (gg.fast) load_group(pl, st * PACK_TILE + threadIdx.x * PACK_PER_THREAD, view.W, gsm);
+        if constexpr ((FELICS_FORMS & 8) != 0 && sizeof(T) == 1) {
+            if (gg.fast) load_group_at(pl + (uint64_t)st * PACK_TILE, threadIdx.x * PACK_PER_THREAD, view.W, gsm);
+        } else {
+            if (gg.fast) load_group(pl, st * PACK_TILE + threadIdx.x * PACK_PER_THREAD, view.W, gsm);
+        }
     }
     clear_window<PACK_WIDE_CLEAR<T>>(fl.win);  // the bit window (barrier: behind the gather)
     const uint8_t *ksrc = ts.kq + pt * ts.cap;
     const uint16_t *psrc = ts.pix + pt * ts.cap;
     constexpr uint32_t GR = 3;  // rounds in flight together: 3072 slots
     if (ns <= WORD_PATH_MAX_SLOTS) {
-        // ---- round trip 2, few events (smooth and natural content: a 4K S1 tile has ~600 slots in use): every event's code built
+        // ---- round trip 2, few events (flat and natural content; a 4K S1 tile has about 2 264 slots in use and takes the other side): every event's code built
         // here, once per event.  Only the waves whose slots exist do that (wave w of round u: slots u * 1024 + w * 256 ..).
 #pragma unroll
         for (uint32_t u = 0; u < 4; u++) reinterpret_cast<uint4 *>(words)[threadIdx.x + u * PACK_THREADS] = make_uint4(0u, 0u, 0u, 0u);
@@ -2253,19 +2333,26 @@ void launch_front(hipStream_t s, const T *planes, const TileLocal<ET> &tl, const
                   uint32_t *flags, uint32_t mode) {
     if (tile_end <= tile_begin) return;
     const dim3 grid(8u * cdiv(g.nplanes, 8) * (tile_end - tile_begin));  // one workgroup per tile, the planes dealt to the XCDs by the kernel
+    // (the rank form picks the instantiation; FRONT_TEST_VIOLATION stays an argument: it is read once, behind the loops)
+    auto launch = [&](auto geometry, uint32_t W, uint32_t npix) {
+        using S = decltype(geometry);
+        if (mode & FRONT_SAFE_RANK)
+            FELICS_LAUNCH((k_front<T, ET, S, true>), grid, dim3(256), s, geometry, tl.ev, tl.pix, tl.runtab, tl.tile_slots, W, npix, g.sort_tiles,
+                          tile_begin, tile_end, g.nplanes, tl.cap, flags, mode);
+        else
+            FELICS_LAUNCH((k_front<T, ET, S, false>), grid, dim3(256), s, geometry, tl.ev, tl.pix, tl.runtab, tl.tile_slots, W, npix, g.sort_tiles,
+                          tile_begin, tile_end, g.nplanes, tl.cap, flags, mode);
+    };
     if constexpr (sizeof(T) == 1) {
         if (g.mixed && g.pitched) {
-            FELICS_LAUNCH((k_front<T, ET, const PitchedGeom *>), grid, dim3(256), s, g.pitched, tl.ev, tl.pix, tl.runtab, tl.tile_slots, 0u, 0u,
-                          g.sort_tiles, tile_begin, tile_end, g.nplanes, tl.cap, flags, mode);
+            launch(g.pitched, 0u, 0u);
             return;
         }
     }
     if (g.mixed)
-        FELICS_LAUNCH((k_front<T, ET, const PlaneGeom *>), grid, dim3(256), s, g.mixed, tl.ev, tl.pix, tl.runtab, tl.tile_slots, 0u, 0u, g.sort_tiles,
-                      tile_begin, tile_end, g.nplanes, tl.cap, flags, mode);
+        launch(g.mixed, 0u, 0u);
     else
-        FELICS_LAUNCH((k_front<T, ET, const T *>), grid, dim3(256), s, planes, tl.ev, tl.pix, tl.runtab, tl.tile_slots, g.W, g.npix, g.sort_tiles,
-                      tile_begin, tile_end, g.nplanes, tl.cap, flags, mode);
+        launch(planes, g.W, g.npix);
 }
 template void launch_front<uint8_t, uint8_t>(hipStream_t, const uint8_t *, const TileLocal<uint8_t> &, const Geometry &, uint32_t, uint32_t,
                                              uint32_t *, uint32_t);
