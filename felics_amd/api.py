@@ -107,6 +107,11 @@ class _CIndexViewStats(C.Structure):  # felics_index_view_stats
                 ("plane_bytes", C.c_uint64)]
 
 
+class _CIndex16Stats(C.Structure):  # felics_index16_stats
+    _fields_ = [("streams", C.c_uint64), ("segments16", C.c_uint64), ("passes", C.c_uint64), ("rows_loaded", C.c_uint64),
+                ("table_bytes", C.c_uint64)]
+
+
 class _CIndexEmitStats(C.Structure):  # felics_index_emit_stats
     _fields_ = [("indexes", C.c_uint64), ("checkpoints", C.c_uint64), ("in_mixed", C.c_uint64), ("redone", C.c_uint64)]
 
@@ -156,6 +161,8 @@ EXPORTS = [
     "felics_region_segments", "felics_decompress_region_indexed", "felics_decompress_regions_device_indexed", "felics_get_region_stats",
     "felics_decompress_views_device_indexed", "felics_decompress_indexed_view", "felics_get_index_view_stats",
     "felics_index_plan", "felics_compress_views_device_indexed", "felics_get_index_emit_stats",
+    "felics_index_wide_size_max", "felics_index_wide_build", "felics_decompress_indexed_wide", "felics_decompress_batch_device_indexed_wide",
+    "felics_get_index_wide_stats",
 ]
 
 _lib = None
@@ -260,6 +267,14 @@ def lib():
         L.felics_index_plan.argtypes = [sz, C.POINTER(_CView), u32, u64, u64, u64]
         L.felics_compress_views_device_indexed.argtypes = [vp, sz, C.POINTER(_CView), u32, vp, vp, sz, vp, sz, u64, u64, u64]
         L.felics_get_index_emit_stats.argtypes = [vp, C.POINTER(_CIndexEmitStats), sz]
+    if hasattr(L, "felics_decompress_batch_device_indexed_wide"):  # (as above: an older build has no index for 16-bit streams)
+        L.felics_index_wide_size_max.argtypes = [C.c_uint32, C.c_uint32, C.c_int, C.c_uint32]
+        L.felics_index_wide_size_max.restype = sz
+        L.felics_index_wide_build.argtypes = [vp, sz, C.c_uint32, vp, sz, C.POINTER(sz)]
+        L.felics_decompress_indexed_wide.argtypes = [vp, sz, vp, sz, vp, sz, C.POINTER(_CHeader)]
+        L.felics_decompress_batch_device_indexed_wide.argtypes = [vp, sz, vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), vp, C.POINTER(C.c_uint64),
+                                                               C.POINTER(C.c_uint64), vp, sz, C.POINTER(_CHeader), C.POINTER(C.c_int)]
+        L.felics_get_index_wide_stats.argtypes = [vp, C.POINTER(_CIndex16Stats), sz]
     L.felics_strerror.argtypes = [C.c_int]
     L.felics_strerror.restype = C.c_char_p
     L.felics_last_error.argtypes = [vp]
@@ -744,6 +759,39 @@ class Encoder:
             raise err
         return Header(ch.color_type, ch.pixel_depth, ch.width, ch.height), status
 
+    def decompress_batch_device_indexed16(self, d_streams, offsets, lens, d_index, idx_offsets, idx_lens, d_pixels, d_pixels_cap):
+        """felics_decompress_batch_device_indexed_wide: 16-bit streams of one shape, their version-2 restart indexes (index i at
+        d_index + idx_offsets[i], a multiple of 64; idx_lens[i] bytes, index16_build's exact size) and the uint16 pixels in device
+        memory (raw pointers).  A wave per (stream, plane, segment).  Returns (Header, status array); raises as
+        decompress_batch_device_indexed does (the error carries .status)."""
+        u64 = C.POINTER(C.c_uint64)
+        offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+        lens = np.ascontiguousarray(lens, dtype=np.uint64)
+        idx_offsets = np.ascontiguousarray(idx_offsets, dtype=np.uint64)
+        idx_lens = np.ascontiguousarray(idx_lens, dtype=np.uint64)
+        n = len(offsets)
+        if len(lens) != n or len(idx_offsets) != n or len(idx_lens) != n:
+            raise ValueError("a length and an index per stream")
+        status = np.zeros(n, dtype=np.int32)
+        ch = _CHeader()
+        rc = lib().felics_decompress_batch_device_indexed_wide(
+            self._h, n, d_streams, offsets.ctypes.data_as(u64), lens.ctypes.data_as(u64), d_index, idx_offsets.ctypes.data_as(u64),
+            idx_lens.ctypes.data_as(u64), d_pixels, d_pixels_cap, C.byref(ch), status.ctypes.data_as(C.POINTER(C.c_int)))
+        if rc != 0:
+            err = DecompressionError(rc) if rc in DecompressionError.KINDS else FelicsError(rc, lib().felics_last_error(self._h).decode() if rc == -9 else "")
+            err.status = status
+            raise err
+        return Header(ch.color_type, ch.pixel_depth, ch.width, ch.height), status
+
+    def index16_stats(self):
+        """felics_get_index_wide_stats: streams handed to decompress_batch_device_indexed16, their waves (segments16), the passes they ran
+        in, the state rows loaded (all cumulative) and the table memory of one pass of the last call."""
+        st = _CIndex16Stats()
+        rc = lib().felics_get_index_wide_stats(self._h, C.byref(st), C.sizeof(st))
+        if rc != 0:
+            raise FelicsError(rc)
+        return {k: int(getattr(st, k)) for k, _ in _CIndex16Stats._fields_}
+
     def decompress_regions_device_indexed(self, d_streams, offsets, lens, d_index, index_stride, regions, d_pixels, d_pixels_cap):
         """felics_decompress_regions_device_indexed: windows of streams of one shape through their restart indexes, everything in
         device memory (raw pointers).  regions: (stream, x, y, w, h) each; crop r is dense at d_pixels + out_offsets[r].  Only the
@@ -1093,6 +1141,49 @@ def decompress_indexed(data, index):
     out = np.zeros(shape, dtype=np.uint16 if ch.pixel_depth else np.uint8)
     rc = lib().felics_decompress_indexed(arr.ctypes.data, len(arr), idx.ctypes.data if len(idx) else None, len(idx),
                                          out.ctypes.data if out.size else None, out.nbytes, None)
+    if rc != 0:
+        raise DecompressionError(rc) if rc in DecompressionError.KINDS else FelicsError(rc)
+    return out
+
+
+def index16_size_max(width, height, color, segment_pixels):
+    """felics_index_wide_size_max: an upper bound of the bytes of the version-2 restart index of a width x height 16-bit image; 0 for
+    bad arguments."""
+    return int(lib().felics_index_wide_size_max(width, height, int(color), segment_pixels))
+
+
+def index16_build(data, segment_pixels):
+    """felics_index_wide_build: the version-2 restart index (bytes) of a 16-bit stream, built by decoding it once on the CPU."""
+    arr = np.frombuffer(bytes(data), dtype=np.uint8)
+    need = C.c_size_t(0)
+    L = lib()
+    rc = L.felics_index_wide_build(arr.ctypes.data if len(arr) else None, len(arr), segment_pixels, None, 0, C.byref(need))
+    if rc == 0:
+        return b""
+    if rc != -8:
+        raise DecompressionError(rc) if rc in DecompressionError.KINDS else FelicsError(rc)
+    out = np.zeros(need.value, dtype=np.uint8)
+    rc = L.felics_index_wide_build(arr.ctypes.data, len(arr), segment_pixels, out.ctypes.data, out.nbytes, C.byref(need))
+    if rc != 0:
+        raise DecompressionError(rc) if rc in DecompressionError.KINDS else FelicsError(rc)
+    return out[:need.value].tobytes()
+
+
+def decompress_indexed16(data, index):
+    """felics_decompress_indexed_wide: the image of a 16-bit stream, decoded segment by segment through its version-2 restart index."""
+    arr = np.frombuffer(bytes(data), dtype=np.uint8)
+    idx = np.frombuffer(bytes(index), dtype=np.uint8)
+    ch = _CHeader()
+    rc = lib().felics_read_header(arr.ctypes.data if len(arr) else None, len(arr), C.byref(ch))
+    if rc != 0:
+        raise DecompressionError(rc)
+    planes = 3 if ch.color_type else 1
+    if ch.width * ch.height * planes > max(len(arr), 1) * 8 + 2 * planes:  # a pixel costs at least one bit
+        raise DecompressionError(-1)
+    shape = (ch.height, ch.width, 3) if planes == 3 else (ch.height, ch.width)
+    out = np.zeros(shape, dtype=np.uint16 if ch.pixel_depth else np.uint8)
+    rc = lib().felics_decompress_indexed_wide(arr.ctypes.data, len(arr), idx.ctypes.data if len(idx) else None, len(idx),
+                                           out.ctypes.data if out.size else None, out.nbytes, None)
     if rc != 0:
         raise DecompressionError(rc) if rc in DecompressionError.KINDS else FelicsError(rc)
     return out

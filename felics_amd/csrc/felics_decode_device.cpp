@@ -1192,6 +1192,104 @@ int felics_decompress_batch_device_indexed(felics_ctx *ctx, size_t n, const void
     return FELICS_OK;
 }
 
+int felics_get_index_wide_stats(const felics_ctx *ctx, felics_index16_stats *out, size_t out_size) {
+    if (!ctx || !out) return FELICS_E_INVALID_ARGUMENT;
+    memcpy(out, &ctx->i16stats, std::min(out_size, sizeof(felics_index16_stats)));
+    return FELICS_OK;
+}
+
+int felics_decompress_batch_device_indexed_wide(felics_ctx *ctx, size_t n, const void *d_streams, const uint64_t *offsets, const uint64_t *lens,
+                                             const void *d_index, const uint64_t *idx_offsets, const uint64_t *idx_lens, void *d_pixels,
+                                             size_t d_pixels_cap, felics_header *hdr_out, int *status) {
+    if (!ctx || (n && (!d_streams || !offsets || !lens || !d_index || !idx_offsets || !idx_lens || !status))) return FELICS_E_INVALID_ARGUMENT;
+    if (ctx->failed) return FELICS_E_HIP;
+    if (n == 0) return FELICS_OK;
+    if (any_pending(ctx)) return FELICS_E_INVALID_ARGUMENT;  // felics_wait_batch first
+    if ((uintptr_t)d_index & 63u) return FELICS_E_INVALID_ARGUMENT;  // the kernel loads a state row as one aligned 64-byte line
+    for (size_t i = 0; i < n; i++)
+        if (idx_offsets[i] & 63u) return FELICS_E_INVALID_ARGUMENT;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    auto fail_all = [&](int code) {
+        for (size_t i = 0; i < n; i++) status[i] = code;
+        return code;
+    };
+    // the shape every stream must have: header of stream 0, which must be 16-bit with w * h < 2^32
+    uint8_t h0[FELICS_HEADER_BYTES] = {0};
+    const size_t hl = (size_t)std::min<uint64_t>(lens[0], FELICS_HEADER_BYTES);
+    if (hl) HIP_TRY(ctx, hipMemcpy(h0, (const uint8_t *)d_streams + offsets[0], hl, hipMemcpyDeviceToHost));
+    felics_header hdr;
+    int rc = felics_read_header(h0, hl, &hdr);
+    if (rc) return fail_all(rc);
+    if (hdr_out) *hdr_out = hdr;
+    if (hdr.pixel_depth != FELICS_DEPTH_16) return fail_all(FELICS_E_UNSUPPORTED);  // 8-bit streams: felics_decompress_batch_device_indexed
+    if ((uint64_t)hdr.width * hdr.height > 0xFFFFFFFFull) return fail_all(FELICS_E_INVALID_DIMENSIONS);
+    if (decode16_lds_bytes(hdr.width) > DECODE_LDS_LIMIT) return fail_all(FELICS_E_UNSUPPORTED);  // no host fallback here
+    const uint32_t planes = hdr.color_type == FELICS_COLOR_RGB ? 3 : 1;
+    const uint64_t npix = (uint64_t)hdr.width * hdr.height;
+    const uint64_t frame_bytes = npix * planes * 2;
+    if (frame_bytes * n > d_pixels_cap) return fail_all(FELICS_E_BUFFER_TOO_SMALL);
+    if (frame_bytes && !d_pixels) return fail_all(FELICS_E_INVALID_ARGUMENT);
+    // how every index is cut: header of index 0 (segment_pixels, K), which must fit stream 0 and its own length.  (One header, as the
+    // 8-bit call reads one; the streams' own headers are the kernel's to check.)
+    if (idx_lens[0] < INDEX_HEADER_BYTES) return fail_all(FELICS_E_INVALID_INDEX);
+    uint8_t ih[INDEX_HEADER_BYTES];
+    HIP_TRY(ctx, hipMemcpy(ih, (const uint8_t *)d_index + idx_offsets[0], INDEX_HEADER_BYTES, hipMemcpyDeviceToHost));
+    Index16Layout L;
+    if (index16_header_check(ih, hdr.color_type, hdr.width, hdr.height, lens[0], idx_lens[0], L) != FELICS_OK) return fail_all(FELICS_E_INVALID_INDEX);
+    const uint32_t seg = idx_rd32(ih + IDX_SEGPIX);
+    const uint64_t per = (uint64_t)planes * std::max(L.K, 1u);
+    if (n > 0x7FFFFFFFull / per) return fail_all(FELICS_E_UNSUPPORTED);  // a status word per segment, 32-bit item numbers
+    const uint64_t items = n * per;
+    // FELICS_TEST_INDEX16_PASS=k: at most k waves in a pass (tests)
+    uint64_t want = items;
+    if (const char *e = getenv("FELICS_TEST_INDEX16_PASS"))
+        if (atoll(e) > 0) want = std::min<uint64_t>(want, (uint64_t)atoll(e));
+    size_t pass = 0;
+    if ((rc = dec16_tables(ctx, (size_t)want, pass)) != 0) return fail_all(rc);
+    // offsets | lens | index offsets | index lens | the rows-loaded counter | status on the device; a word per segment beside them
+    if ((rc = reserve(ctx, ctx->dec_meta, n * 8 * 4 + 8 + n * 4)) != 0) return fail_all(rc);
+    if ((rc = reserve(ctx, ctx->dec_seg_status, (size_t)items * 4)) != 0) return fail_all(rc);
+    int32_t *d_planes = nullptr;
+    if (planes == 3) {
+        if ((rc = reserve(ctx, ctx->dec_planes, (size_t)(npix * 3 * 4 * n) + 64)) != 0) return fail_all(rc);
+        d_planes = (int32_t *)ctx->dec_planes.p;
+    }
+    uint64_t *d_off = (uint64_t *)ctx->dec_meta.p, *d_len = d_off + n, *d_ioff = d_len + n, *d_ilen = d_ioff + n;
+    unsigned long long *d_loaded = (unsigned long long *)(d_ilen + n);
+    int *d_status = (int *)(d_loaded + 1);
+    int *seg_status = (int *)ctx->dec_seg_status.p;
+    felics_index16_stats &st = ctx->i16stats;
+    st.streams += n;
+    st.segments16 += items;
+    st.table_bytes = decode16_table_bytes((uint32_t)pass);
+    hipStream_t s = ctx->lanes[0].stream;
+    for (size_t i = 0; i < n; i++) status[i] = FELICS_E_HIP;  // until the kernel's own word arrives
+    HIP_TRY(ctx, hipMemcpyAsync(d_off, offsets, n * 8, hipMemcpyHostToDevice, s));
+    HIP_TRY(ctx, hipMemcpyAsync(d_len, lens, n * 8, hipMemcpyHostToDevice, s));
+    HIP_TRY(ctx, hipMemcpyAsync(d_ioff, idx_offsets, n * 8, hipMemcpyHostToDevice, s));
+    HIP_TRY(ctx, hipMemcpyAsync(d_ilen, idx_lens, n * 8, hipMemcpyHostToDevice, s));
+    HIP_TRY(ctx, hipMemsetAsync(d_loaded, 0, 8, s));
+    HIP_TRY(ctx, hipMemsetAsync(d_status, 0xFF, n * 4, s));
+    HIP_TRY(ctx, hipMemsetAsync(seg_status, 0xFF, (size_t)items * 4, s));
+    for (uint64_t i0 = 0; i0 < items; i0 += pass) {  // behind one another on the one stream: the passes share the tables
+        uint32_t epoch = 0;
+        if ((rc = dec16_epoch(ctx, s, epoch)) != 0) return rc;
+        HIP_TRY(ctx, launch_decode16_seg(s, (const uint8_t *)d_streams, d_off, d_len, (const uint8_t *)d_index, d_ioff, d_ilen, hdr.width, hdr.height,
+                                         hdr.color_type, seg, L.K, (uint32_t)i0, (uint32_t)std::min<uint64_t>(pass, items - i0), (uint16_t *)d_pixels,
+                                         d_planes, (uint32_t *)ctx->dec_table.p, epoch, seg_status, d_loaded));
+        st.passes++;
+    }
+    HIP_TRY(ctx, launch_seg16_finish(s, (uint32_t)n, hdr.width, hdr.height, hdr.color_type, L.K, (uint16_t *)d_pixels, d_planes, seg_status, d_status));
+    unsigned long long loaded = 0;
+    HIP_TRY(ctx, hipMemcpyAsync(status, d_status, n * 4, hipMemcpyDeviceToHost, s));
+    HIP_TRY(ctx, hipMemcpyAsync(&loaded, d_loaded, 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(ctx, hipStreamSynchronize(s));
+    st.rows_loaded += loaded;
+    for (size_t i = 0; i < n; i++)
+        if (status[i]) return status[i];
+    return FELICS_OK;
+}
+
 int felics_get_region_stats(const felics_ctx *ctx, felics_region_stats *out, size_t out_size) {
     if (!ctx || !out) return FELICS_E_INVALID_ARGUMENT;
     memcpy(out, &ctx->rstats, std::min(out_size, sizeof(felics_region_stats)));

@@ -1467,6 +1467,261 @@ __global__ __launch_bounds__(256) void k_ycocg16_to_rgb(const int32_t *__restric
 }
 
 // ------------------------------------------------------------------------------------------
+// 16-bit streams through a restart index (format version 2: felics.h "Restart index: 16-bit streams", felics_index.h): one wave per
+// (stream, plane, segment), the walk of decode8_from_checkpoint with k_decode16's per-pixel path.  Host model:
+// felics_decompress_indexed16, with the same checks in the same order.  The sink is decode8_from_checkpoint's:
+//   stop(pend), store(col, y, at, v).
+// ------------------------------------------------------------------------------------------
+namespace {
+
+// Segment (c, j) of stream s / index idx (idx_len bytes, 64-byte aligned), decoded by the calling wave into `sink`; `smem` is the
+// kernel's dynamic LDS (decode16_lds_bytes(W)), `table` the wave's own dense estimator table (DEC16_CONTEXTS rows; rows of another
+// epoch read as zeros).  Returns the segment's status, wave-uniform; *loaded = the state rows it copied.
+template <typename Sink>
+__device__ __forceinline__ int decode16_from_checkpoint(uint8_t *smem, const uint8_t *s, uint64_t slen, const uint8_t *idx, uint64_t idx_len,
+                                                        const DecUniform &geo, uint32_t segment_pixels, uint32_t K, uint32_t c, uint32_t j,
+                                                        uint32_t *table, uint32_t epoch, const Sink &sink, uint32_t *loaded) {
+    const uint32_t W = geo.W, H = geo.H, color = geo.color;
+    uint32_t *crow = reinterpret_cast<uint32_t *>(smem);  // [DEC16_SLOTS][DEC16_ROW] cached rows
+    uint32_t *ctag = crow + DEC16_SLOTS * DEC16_ROW;      // [DEC16_SLOTS] context held (or ~0)
+    int32_t *rows = reinterpret_cast<int32_t *>(ctag + DEC16_SLOTS);
+    const uint32_t rstride = decode8_row_stride(W);
+    const uint32_t lane = lane_id();
+    const uint64_t npix = (uint64_t)W * H;
+    *loaded = 0;
+    // 1. the checks: the stream's header must be the one announced, the index header must fit it, the launch and the index's length;
+    //    then this segment's directory entry
+    Index16Layout L;
+    uint64_t start = 0, end = 0, rows_off = 0;
+    uint32_t n_rows = 0;
+    int rc = FELICS_OK;
+    if (slen < FELICS_HEADER_BYTES) {
+        rc = FELICS_E_IO;
+    } else {
+        const uint32_t w = ((uint32_t)s[6] << 24) | ((uint32_t)s[7] << 16) | ((uint32_t)s[8] << 8) | s[9];
+        const uint32_t h = ((uint32_t)s[10] << 24) | ((uint32_t)s[11] << 16) | ((uint32_t)s[12] << 8) | s[13];
+        if (s[0] != 'F' || s[1] != 'L' || s[2] != 'C' || s[3] != 'S') rc = FELICS_E_INVALID_SIGNATURE;
+        else if (s[4] > 1) rc = FELICS_E_INVALID_COLOR_TYPE;
+        else if (s[5] > 1) rc = FELICS_E_INVALID_PIXEL_DEPTH;
+        else if (s[4] != color || s[5] != 1 || w != W || h != H) rc = FELICS_E_INVALID_DIMENSIONS;
+        else if (idx_len < INDEX_HEADER_BYTES || index16_header_check(idx, color, W, H, slen, idx_len, L) != FELICS_OK ||
+                 idx_rd32(idx + IDX_SEGPIX) != segment_pixels || L.K != K)
+            rc = FELICS_E_INVALID_INDEX;
+        else rc = index16_segment_bounds(idx, L, c, j, slen, idx_len, start, end, rows_off, n_rows);
+    }
+    rc = unii(rc);
+    if (rc != FELICS_OK) return rc;
+    start = ((uint64_t)uni((uint32_t)(start >> 32)) << 32) | uni((uint32_t)start);
+    end = ((uint64_t)uni((uint32_t)(end >> 32)) << 32) | uni((uint32_t)end);
+    rows_off = ((uint64_t)uni((uint32_t)(rows_off >> 32)) << 32) | uni((uint32_t)rows_off);
+    n_rows = uni(n_rows);
+    const uint64_t p0 = (uint64_t)j * segment_pixels, pend = min(npix, p0 + segment_pixels);  // this segment's pixels
+    const uint64_t stop = sink.stop(pend);
+    // 2. the estimator table: the checkpoint's rows into the wave's table, four rows per iteration at sixteen lanes per row.  A row
+    //    is one coalesced 64-byte load; its last word is the context, checked (range, strictly ascending) before it indexes anything
+    //    and replaced by the epoch in the store.  [rows_off, rows_off + 64 n_rows) lies inside the index: index16_segment_bounds.
+    //    The wave reads these rows back later with k_decode16's agent-scope loads: the situation of that kernel's write-back path
+    //    (a row this wave stored a while ago, read from L2; every load's wait covers the stores before it), and the same argument.
+    {
+        const uint32_t *src = reinterpret_cast<const uint32_t *>(idx + rows_off);
+        const uint32_t limit = index16_contexts(color, c), l15 = lane & 15u, grp = lane >> 4;
+        int64_t carry = -1;  // the context of the row in front of this iteration's first
+        for (uint32_t r0 = 0; r0 < n_rows; r0 += 4) {
+            const uint32_t r = r0 + grp;
+            const bool have = r < n_rows;
+            const uint32_t wv = have ? src[(uint64_t)r * DEC16_ROW + l15] : 0u;
+            const uint32_t ctx = (uint32_t)__shfl((int)wv, (int)((lane & 48u) | 15u));
+            const uint32_t before = (uint32_t)__shfl((int)wv, (int)(((lane & 48u) - 16u + 15u) & 63u));  // (group 0: not used)
+            const int64_t prev = grp ? (int64_t)before : carry;
+            const bool ok = ctx < limit && (int64_t)ctx > prev;
+            if (__ballot(have && !ok) != 0) return FELICS_E_INVALID_INDEX;
+            if (have) table[(uint64_t)ctx * DEC16_ROW + l15] = l15 == 15u ? epoch : wv;
+            carry = (int64_t)(uint32_t)__builtin_amdgcn_readlane((int)ctx, 63);  // (a last iteration's missing rows: it is the last)
+        }
+        for (uint32_t i = lane; i < DEC16_SLOTS; i += 64) ctag[i] = 0xFFFFFFFFu;  // the LDS cache starts empty
+        *loaded = n_rows;
+    }
+    // 3. the window into the two LDS rows (decode8_from_checkpoint's placement): with (x0, y0) = p0's place, window sample t is pixel
+    //    p0 - 2 W + t: row y0 from t = 2 W - x0 on (cur), row y0 - 1 from t = W - x0 on (prev), and of row y0 - 2 only (0, y0 - 2), if
+    //    x0 = 0 (the first-column rule: what cur[0] holds)
+    uint32_t x = 0, y = 0;
+    int32_t *cur = rows, *prev = rows + rstride;
+    const int lo_ok = (color && c > 0) ? -65535 : 0, hi_ok = 65535;  // Y 0..65535, Co / Cg -65535..65535
+    if (K) {
+        x = (uint32_t)(p0 % W);
+        y = (uint32_t)(p0 / W);
+        const uint8_t *win = idx + L.win_base + ((uint64_t)c * K + j) * L.win_bytes;  // (16-byte aligned, inside the index: total >= rows_base)
+        bool bad = false;
+        for (uint64_t t = lane; t < 2ull * W; t += 64) {
+            if (p0 + t < 2ull * W) continue;  // in front of the plane: zeros, never looked at
+            const int v = color ? reinterpret_cast<const int32_t *>(win)[t] : (int)reinterpret_cast<const uint16_t *>(win)[t];
+            bad |= v < lo_ok || v > hi_ok;
+            if (t >= 2ull * W - x) cur[t - (2ull * W - x)] = v;
+            else if (t >= (uint64_t)W - x) prev[t - ((uint64_t)W - x)] = v;
+            else if (t == 0 && x == 0) cur[0] = v;
+        }
+        if (__ballot(bad) != 0) return FELICS_E_INVALID_INDEX;
+    }
+    __builtin_amdgcn_wave_barrier();
+    // 4. the bit reader at the checkpoint's position (<= 8 slen: the bounds check); every fetch is bounded by the stream's length
+    ScalarBits br;
+    br.init_at(s, slen, start);
+    int32_t raw0 = 0, raw1 = 0;
+    if (j == 0) {  // the plane's two raw samples (compression.rs:166-167) stand in front of its first segment only
+        raw0 = (int32_t)br.get(32);
+        raw1 = (int32_t)br.get(32);
+        if (br.failed()) rc = FELICS_E_IO;
+    }
+    // 5. the walk: k_decode16's pixel, decode8_from_checkpoint's block handling
+    if (rc == FELICS_OK && stop > p0) {
+        const uint32_t xl0 = x & 63u;
+        int upv = 0;   // VECTOR: prev[xb + lane] for the 64-sample block xb the walk stands in
+        int rowv = 0;  // VECTOR: the samples of this block decoded so far
+        if (xl0) {     // a start inside a block: the block's samples in front of it are the window's
+            if (y > 0) upv = (int)prev[(x & ~63u) + lane];
+            rowv = (int)cur[(x & ~63u) + lane];
+        }
+        int left = x >= 1 ? unii((int)cur[x - 1]) : 0, left2 = x >= 2 ? unii((int)cur[x - 2]) : 0;
+        int first_col2 = 0;
+        for (uint64_t i = p0; i < stop; i++) {
+            const uint32_t xl = x & 63u;
+            if (xl == 0) {
+                if (y > 0) upv = (int)prev[x + lane];
+                if (x == 0 && y > 0) first_col2 = y >= 2 ? unii((int)cur[0]) : (W > 1 ? __builtin_amdgcn_readlane(upv, 1) : 0);
+            }
+            int pv;
+            if (i < 2) {
+                pv = i == 0 ? raw0 : raw1;
+            } else {
+                const int above = __builtin_amdgcn_readlane(upv, (int)xl);
+                const bool row0 = y == 0, col0 = x == 0 && !row0;
+                const int v1 = col0 ? above : left;
+                const int v2 = col0 ? first_col2 : (row0 ? left2 : above);
+                const int hi = max(v1, v2), lo = min(v1, v2);
+                const uint32_t ctx = (uint32_t)(hi - lo);  // <= 131 070 because every stored sample is in range
+                br.refill();
+                if (br.take(1)) {  // in range: phased-in code of p - L (phase_in_coding.rs:86-112)
+                    const uint32_t n = ctx + 1;
+                    const uint32_t m = 31u - (uint32_t)__builtin_clz(n);
+                    const uint32_t right_p = (2u << m) - n, left_p = n - (1u << m);
+                    uint32_t r = br.take(m);
+                    const uint32_t longer = r >= right_p ? 1u : 0u;
+                    const uint32_t r2 = (r - right_p) * 2u + right_p + br.take(longer);
+                    r = longer ? r2 : r;
+                    uint32_t rot = r + left_p;
+                    rot = rot >= n ? rot - n : rot;
+                    pv = lo + (int)rot;
+                } else {
+                    const bool above_flag = br.take(1) != 0;
+                    const uint32_t slot = ctx & (DEC16_SLOTS - 1u);
+                    const uint32_t held = uni(ctag[slot]);
+                    uint32_t S;
+                    if (held == ctx) {
+                        S = crow[slot * DEC16_ROW + (lane & 15u)];
+                    } else {
+                        if (held != 0xFFFFFFFFu && lane < DEC16_ROW)  // write the row this slot held back (its epoch word with it)
+                            table[(uint64_t)held * DEC16_ROW + lane] = crow[slot * DEC16_ROW + lane];
+                        uint32_t g = lane < DEC16_ROW ? __hip_atomic_load(&table[(uint64_t)ctx * DEC16_ROW + lane], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0u;
+                        const uint32_t row_epoch = (uint32_t)__builtin_amdgcn_readlane((int)g, 15);
+                        g = row_epoch == epoch ? g : 0u;  // neither loaded nor written by this segment: fresh
+                        S = (uint32_t)__shfl((int)g, (int)(lane & 15u));
+                        if (lane == 0) ctag[slot] = ctx;
+                    }
+                    const uint32_t l15 = lane & 15u;
+                    const uint32_t key = l15 < 15u ? (S << 4) | (15u - l15) : 0xFFFFFFFFu;
+                    const uint32_t k = 15u - (row16_min(key) & 15u);
+                    const uint64_t q = br.unary0();
+                    const uint64_t e64 = (q << k) + br.get(k);
+                    if (e64 > 262144u) {  // no sample of a 16-bit plane is that far from its neighbours
+                        rc = e64 > 0xFFFFFFFFull ? FELICS_E_VALUE_OVERFLOW : FELICS_E_INVALID_VALUE;
+                        break;
+                    }
+                    const uint32_t e = (uint32_t)e64;
+                    uint32_t S2 = S + (e >> l15) + 1u + l15;
+                    const uint32_t mn = row16_min(l15 < 15u ? S2 : 0xFFFFFFFFu);
+                    S2 = mn > 1024u ? S2 >> 1 : S2;
+                    if (lane < DEC16_ROW) crow[slot * DEC16_ROW + lane] = lane < 15u ? S2 : epoch;
+                    pv = above_flag ? hi + (int)e + 1 : lo - (int)e - 1;
+                }
+            }
+            if (pv < lo_ok || pv > hi_ok) {
+                rc = FELICS_E_INVALID_VALUE;
+                break;
+            }
+            rowv = lane == xl ? pv : rowv;
+            left2 = left;
+            left = pv;
+            const bool row_end = x + 1 == W;
+            if (xl == 63u || row_end || i + 1 == stop) {  // a block of the row is complete, or the walk is
+                const uint32_t xb = x & ~63u;
+                if (xb + lane <= x) {
+                    cur[xb + lane] = rowv;  // (lanes in front of a mid-block start store back what they loaded)
+                    const uint64_t at = (uint64_t)y * W + xb + lane;  // < stop: xb + lane <= x
+                    if (at >= p0) sink.store(xb + lane, y, at, rowv);  // the samples in front of p0 are the segment's before this one
+                }
+            }
+            if (row_end) {
+                if (br.failed()) {
+                    rc = FELICS_E_IO;
+                    break;
+                }
+                __builtin_amdgcn_wave_barrier();
+                x = 0;
+                y++;
+                int32_t *t = cur;
+                cur = prev;
+                prev = t;
+            } else {
+                x++;
+            }
+        }
+    }
+    // 6. the end check: exactly on the next checkpoint
+    if (br.failed()) rc = FELICS_E_IO;  // (whatever else stopped the decoding: it was decoding padding)
+    else if (rc == FELICS_OK && stop == pend && br.pos(s) != end) rc = FELICS_E_INVALID_INDEX;
+    return rc;
+}
+
+// The whole segment into the stream's frame (u16 gray) or plane c of its planes (int32): pixel `at` to out[at], p0 <= at < pend only.
+struct Segment16Sink {
+    uint16_t *outg;  // gray: the stream's frame; else null
+    int32_t *outp;   // RGB: plane c of the stream's planes
+    __device__ __forceinline__ uint64_t stop(uint64_t pend) const { return pend; }
+    __device__ __forceinline__ void store(uint32_t, uint32_t, uint64_t at, int v) const {
+        if (outg) outg[at] = (uint16_t)v;
+        else outp[at] = v;
+    }
+};
+
+}  // namespace
+
+// One wave per SEGMENT of a plane of a 16-bit stream (felics_decompress_batch_device_indexed16), a pass of consecutive items at a
+// time: block b is item item0 + b = (img, c, j) = (item / (C Keff), item / Keff % C, item % Keff), Keff = max(K, 1), and owns table b
+// of the pass's tables.  seg_status[item] = FELICS_OK or the code; k_seg_status picks a stream's first.  rows_loaded: += the state
+// rows the wave copied.
+__global__ __launch_bounds__(64) void k_decode16_seg(const uint8_t *__restrict__ streams, const uint64_t *__restrict__ offsets,
+                                                     const uint64_t *__restrict__ lens, const uint8_t *__restrict__ index,
+                                                     const uint64_t *__restrict__ idx_offsets, const uint64_t *__restrict__ idx_lens, DecUniform geo,
+                                                     uint32_t segment_pixels, uint32_t K, uint32_t item0, uint16_t *__restrict__ pixels,
+                                                     int32_t *__restrict__ planes, uint32_t *__restrict__ gtable, uint32_t epoch,
+                                                     int *__restrict__ seg_status, unsigned long long *__restrict__ rows_loaded) {
+    extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
+    const uint32_t nplanes = geo.color ? 3u : 1u, keff = max(K, 1u);
+    const uint32_t item = item0 + blockIdx.x;
+    const uint32_t img = item / (nplanes * keff), c = item / keff % nplanes, j = item % keff;
+    const uint64_t npix = (uint64_t)geo.W * geo.H;
+    const Segment16Sink sink{geo.color ? nullptr : pixels + (uint64_t)img * npix, geo.color ? planes + ((uint64_t)img * nplanes + c) * npix : nullptr};
+    uint32_t *table = gtable + (uint64_t)blockIdx.x * DEC16_CONTEXTS * DEC16_ROW;
+    uint32_t loaded = 0;
+    const int rc = decode16_from_checkpoint(smem, streams + offsets[img], lens[img], index + idx_offsets[img], idx_lens[img], geo, segment_pixels, K,
+                                            c, j, table, epoch, sink, &loaded);
+    if (lane_id() == 0) {
+        seg_status[item] = rc;
+        if (loaded) atomicAdd(rows_loaded, (unsigned long long)loaded);
+    }
+}
+
+// ------------------------------------------------------------------------------------------
 // 16-bit streams, sixty-four of one shape per wave, LANE = stream: the walk of k_decode8_lanes with the arithmetic of k_decode16.
 //
 // (x, y) is wave-uniform, the bit reader is a LaneReader, the row above is read back from the lane's own output four samples at a
@@ -1964,6 +2219,36 @@ hipError_t launch_seg_views_finish(hipStream_t s, uint32_t n, const RegionRow *r
     if (n == 0) return hipSuccess;
     hipLaunchKernelGGL(k_seg_status, dim3(n), dim3(64), 0, s, item_status, regions, 0u, status);
     if (max_npix) launch_conv_views<int16_t, uint8_t>(s, conv, n, max_npix, planes, status, DecodeViews{views, false, true});
+    return hipGetLastError();
+}
+
+// ------------------------------------------------------------------------------------------
+// felics_decompress_batch_device_indexed16: a pass of k_decode16_seg; the call's tail.
+// ------------------------------------------------------------------------------------------
+
+hipError_t launch_decode16_seg(hipStream_t s, const uint8_t *streams, const uint64_t *offsets, const uint64_t *lens, const uint8_t *index,
+                               const uint64_t *idx_offsets, const uint64_t *idx_lens, uint32_t W, uint32_t H, uint32_t color, uint32_t segment_pixels,
+                               uint32_t K, uint32_t item0, uint32_t nitems, uint16_t *pixels, int32_t *planes, uint32_t *table, uint32_t epoch,
+                               int *seg_status, unsigned long long *rows_loaded) {
+    if (nitems == 0) return hipSuccess;
+    const uint32_t lds = decode16_lds_bytes(W);
+    if (lds > 64u * 1024u) {
+        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&k_decode16_seg), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                                 (int)DECODE_LDS_LIMIT);
+        if (e != hipSuccess) return e;
+    }
+    hipLaunchKernelGGL(k_decode16_seg, dim3(nitems), dim3(64), lds, s, streams, offsets, lens, index, idx_offsets, idx_lens, DecUniform{W, H, color},
+                       segment_pixels, K, item0, pixels, planes, table, epoch, seg_status, rows_loaded);
+    return hipGetLastError();
+}
+
+hipError_t launch_seg16_finish(hipStream_t s, uint32_t n, uint32_t W, uint32_t H, uint32_t color, uint32_t K, uint16_t *pixels, int32_t *planes,
+                               const int *seg_status, int *status) {
+    if (n == 0) return hipSuccess;
+    hipLaunchKernelGGL(k_seg_status, dim3(n), dim3(64), 0, s, seg_status, (const RegionRow *)nullptr, (color ? 3u : 1u) * std::max(K, 1u), status);
+    if (color)
+        for (uint32_t i0 = 0; i0 < n; i0 += 65535u)  // (the conversion takes the stream from blockIdx.y)
+            launch_conv_uniform(s, std::min(n - i0, 65535u), W, H, planes + (uint64_t)i0 * 3u * W * H, pixels + (uint64_t)i0 * 3u * W * H, status + i0);
     return hipGetLastError();
 }
 

@@ -213,6 +213,9 @@ struct felics_ctx {
     // felics_decompress_batch_device_indexed: a status word per (stream, plane, segment); the counts of felics_get_index_stats
     DevBuf dec_seg_status;
     felics_index_stats istats = {};
+    // felics_decompress_batch_device_indexed16: its tables are dec_table (epochs: dec_epoch), its words dec_meta and dec_seg_status, its
+    // int32 planes dec_planes; the counts of felics_get_index16_stats
+    felics_index16_stats i16stats = {};
     // felics_decompress_regions_device_indexed: its region table and work list (RegionRow[] | RegionItem[]; the items' status words
     // are dec_seg_status, the crop-sized planes dec_planes); the counts of felics_get_region_stats
     DevBuf dec_region_work;

@@ -120,6 +120,104 @@ FELICS_IDX_HD inline int index_segment_bounds(const uint8_t *idx, const IndexLay
     return FELICS_OK;
 }
 
+// ---- version 2: the index of a 16-bit stream (felics.h "Restart index: 16-bit streams").  A 16-bit plane has up to 131 071 contexts of
+// fifteen 32-bit counters, so a checkpoint's state is SPARSE: the rows of the contexts that are live at it, of any number.  Header (64
+// bytes) | directory of C K entries | windows | state rows; everything but the rows lies where the header says.
+constexpr uint32_t INDEX16_VERSION = 2;
+constexpr uint32_t IDX16_TOTAL = 48, IDX16_RESERVED = 56;  // u64 total_bytes | 8 zero bytes (the fields in front are version 1's)
+// a directory entry: u64 bit_offset | u64 rows_off | u32 n_rows | 12 zero bytes
+constexpr uint32_t INDEX16_ENTRY_BYTES = 32, E16_BIT = 0, E16_ROWS_OFF = 8, E16_NROWS = 16, E16_RESERVED = 20;
+// a state row: u32 counter[15] | u32 context (k_decode16's row with the context where the epoch goes)
+constexpr uint32_t INDEX16_ROW_BYTES = 64, INDEX16_ROW_CTX = 15;
+constexpr uint32_t INDEX16_CONTEXTS = 2u * 65535u + 1u;  // contexts a Co / Cg plane can have; gray and Y: 65 536
+
+struct Index16Layout {
+    uint32_t planes, K;
+    uint32_t sample_bytes;  // of a window sample: 2 (u16) gray, 4 (i32) Y / Co / Cg
+    uint64_t win_bytes;     // of a window: 2 W samples, rounded up to 16
+    uint64_t win_base;      // window (c, j) at win_base + (c K + j) win_bytes
+    uint64_t rows_base;     // the first state row; the least an index of this shape is long
+};
+
+FELICS_IDX_HD inline uint32_t index16_contexts(uint32_t color, uint32_t c) { return color && c ? INDEX16_CONTEXTS : 65536u; }
+// (w * h < 2^32 and index_segment_ok: the caller's checks)
+FELICS_IDX_HD inline Index16Layout index16_layout(uint32_t w, uint32_t h, uint32_t color, uint32_t segment_pixels) {
+    Index16Layout L;
+    L.planes = color ? 3u : 1u;
+    L.sample_bytes = color ? 4u : 2u;
+    const uint64_t npix = (uint64_t)w * h;
+    L.K = (uint32_t)((npix + segment_pixels - 1) / segment_pixels);
+    L.win_bytes = (2ull * w * L.sample_bytes + 15u) & ~15ull;
+    L.win_base = (INDEX_HEADER_BYTES + (uint64_t)INDEX16_ENTRY_BYTES * L.planes * L.K + 63u) & ~63ull;
+    L.rows_base = (L.win_base + (uint64_t)L.planes * L.K * L.win_bytes + 63u) & ~63ull;
+    return L;
+}
+
+// The checks of a version-2 header against the stream's and the length the caller gave: 0, or FELICS_E_INVALID_INDEX.  `ih` holds
+// INDEX_HEADER_BYTES bytes; the stream is 16-bit with w * h < 2^32.  On success L is the layout the header names and
+// index_len >= L.rows_base: the directory and every window lie inside the index.
+FELICS_IDX_HD inline int index16_header_check(const uint8_t *ih, uint32_t color, uint32_t w, uint32_t h, uint64_t stream_len, uint64_t index_len,
+                                              Index16Layout &L) {
+    if (ih[0] != 'F' || ih[1] != 'L' || ih[2] != 'C' || ih[3] != 'X' || idx_rd16(ih + IDX_VERSION) != INDEX16_VERSION) return FELICS_E_INVALID_INDEX;
+    if (ih[IDX_COLOR] != color || ih[IDX_DEPTH] != FELICS_DEPTH_16 || idx_rd32(ih + IDX_WIDTH) != w || idx_rd32(ih + IDX_HEIGHT) != h)
+        return FELICS_E_INVALID_INDEX;
+    const uint32_t seg = idx_rd32(ih + IDX_SEGPIX);
+    if (!index_segment_ok(seg)) return FELICS_E_INVALID_INDEX;
+    L = index16_layout(w, h, color, seg);
+    if (idx_rd32(ih + IDX_K) != L.K) return FELICS_E_INVALID_INDEX;
+    uint64_t prev = STREAM_HEADER_BITS;
+    for (uint32_t c = 0; c < 3; c++) {
+        const uint64_t e = idx_rd64(ih + IDX_PLANE_END + 8 * c);
+        if (c >= L.planes) {
+            if (e) return FELICS_E_INVALID_INDEX;
+            continue;
+        }
+        if (e < prev + 64u || e > 8u * stream_len) return FELICS_E_INVALID_INDEX;
+        prev = e;
+    }
+    if ((prev + 7u) / 8u != stream_len) return FELICS_E_INVALID_INDEX;
+    const uint64_t total = idx_rd64(ih + IDX16_TOTAL);
+    if (total != index_len || total < L.rows_base || total % INDEX16_ROW_BYTES) return FELICS_E_INVALID_INDEX;
+    for (uint32_t i = IDX16_RESERVED; i < INDEX_HEADER_BYTES; i++)
+        if (ih[i]) return FELICS_E_INVALID_INDEX;
+    return FELICS_OK;
+}
+
+// Where segment (c, j) starts and ends in the stream and where its state rows lie, and what is wrong with that before a bit is decoded
+// or a row is read: 0, or FELICS_E_INVALID_INDEX.  idx: the whole index of `total` bytes (header checked, so every directory entry is
+// inside it).  The bit range by version 1's rules; the rows inside [rows_base, total), whole rows, none for segment 0, and CHAINED:
+// (0, 0)'s start at rows_base, an entry's end where its successor's start in (plane, segment) order, the last one's at `total`.
+// K = 0 (an empty image) has one pseudo segment per plane, the two raw samples, and no rows.
+FELICS_IDX_HD inline int index16_segment_bounds(const uint8_t *idx, const Index16Layout &L, uint32_t c, uint32_t j, uint64_t stream_len,
+                                                uint64_t total, uint64_t &start, uint64_t &end, uint64_t &rows_off, uint32_t &n_rows) {
+    const uint64_t plane_start = c ? idx_rd64(idx + IDX_PLANE_END + 8 * (c - 1)) : STREAM_HEADER_BITS;
+    const uint64_t plane_end = idx_rd64(idx + IDX_PLANE_END + 8 * c);
+    rows_off = L.rows_base;
+    n_rows = 0;
+    if (L.K == 0) {
+        start = plane_start;
+        end = plane_end;
+        return FELICS_OK;
+    }
+    const uint8_t *e = idx + INDEX_HEADER_BYTES + ((uint64_t)c * L.K + j) * INDEX16_ENTRY_BYTES;
+    start = idx_rd64(e + E16_BIT);
+    end = j + 1 < L.K ? idx_rd64(e + INDEX16_ENTRY_BYTES + E16_BIT) : plane_end;
+    if (start < STREAM_HEADER_BITS || start > 8u * stream_len || end > 8u * stream_len || end < start) return FELICS_E_INVALID_INDEX;
+    if (j == 0 ? start != plane_start : start < idx_rd64(e - INDEX16_ENTRY_BYTES + E16_BIT)) return FELICS_E_INVALID_INDEX;
+    rows_off = idx_rd64(e + E16_ROWS_OFF);
+    n_rows = idx_rd32(e + E16_NROWS);
+    if (rows_off < L.rows_base || rows_off % INDEX16_ROW_BYTES || rows_off > total ||
+        (uint64_t)n_rows * INDEX16_ROW_BYTES > total - rows_off)
+        return FELICS_E_INVALID_INDEX;
+    const bool last = c + 1 == L.planes && j + 1 == L.K;
+    const uint64_t next = last ? total : idx_rd64(e + INDEX16_ENTRY_BYTES + E16_ROWS_OFF);
+    if (rows_off + (uint64_t)n_rows * INDEX16_ROW_BYTES != next || (c == 0 && j == 0 && rows_off != L.rows_base)) return FELICS_E_INVALID_INDEX;
+    if (j == 0 && n_rows != 0) return FELICS_E_INVALID_INDEX;
+    for (uint32_t i = E16_RESERVED; i < INDEX16_ENTRY_BYTES; i++)
+        if (e[i]) return FELICS_E_INVALID_INDEX;
+    return FELICS_OK;
+}
+
 // ---- regions (felics.h "Restart index: regions"): the planner's arithmetic, for felics_region_segments, the host model and the host
 // side of the device call alike.  W * H < 2^32, index_segment_ok(seg) and region_inside are the caller's checks.
 FELICS_IDX_HD inline bool region_inside(uint32_t W, uint32_t H, const felics_region &r) {

@@ -383,6 +383,18 @@ hipError_t launch_seg_views_finish(hipStream_t s, uint32_t n, const RegionRow *r
 // out + 64 i, zeros behind an index shorter than that: no byte outside [idx_offsets[i], idx_offsets[i] + idx_lens[i]) is read.
 hipError_t launch_read_index_headers(hipStream_t s, const uint8_t *index, const uint64_t *idx_offsets, const uint64_t *idx_lens, uint32_t n,
                                      uint8_t *out);
+// 16-bit streams of one shape through version-2 restart indexes (felics_decompress_batch_device_indexed16, felics.h "Restart index:
+// 16-bit streams"; index i at index + idx_offsets[i], a multiple of 64, idx_lens[i] bytes): k_decode16_seg, one wave per (stream,
+// plane, segment).  A launch is a PASS of the call's n * C * max(K, 1) items: items item0 .. item0 + nitems - 1, wave b on table b of
+// `table` (decode16_table_bytes(nitems) bytes, launch_decode16's buffer and epoch rule: one fresh epoch per pass).  seg_status: a word
+// per item of the call; *rows_loaded += the state rows copied.  launch_seg16_finish is the call's tail for streams 0 .. n - 1:
+// status[i] = stream i's first failing word in (plane, segment) order, then the conversion of the clean RGB frames.
+hipError_t launch_decode16_seg(hipStream_t s, const uint8_t *streams, const uint64_t *offsets, const uint64_t *lens, const uint8_t *index,
+                               const uint64_t *idx_offsets, const uint64_t *idx_lens, uint32_t W, uint32_t H, uint32_t color, uint32_t segment_pixels,
+                               uint32_t K, uint32_t item0, uint32_t nitems, uint16_t *pixels, int32_t *planes, uint32_t *table, uint32_t epoch,
+                               int *seg_status, unsigned long long *rows_loaded);
+hipError_t launch_seg16_finish(hipStream_t s, uint32_t n, uint32_t W, uint32_t H, uint32_t color, uint32_t K, uint16_t *pixels, int32_t *planes,
+                               const int *seg_status, int *status);
 // The same for 16-bit streams, gray or RGB (k_decode16_lanes): 64 streams per wave, lane = stream; needs W >= 8 and a table of
 // decode16_lanes_table_bytes(n, W, H, color) bytes = n * planes * dec16l_rows(W * H, planes) * 64 (felics_lanetable.h: sized by the
 // pixel count, 512 KB per plane of a 64 x 64 stream, the wave form's 8.4 MB from 32 771 pixels on), zero-initialised ONCE: rows carry

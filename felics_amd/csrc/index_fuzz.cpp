@@ -12,7 +12,11 @@
 //     admissible view (a pitch, pixel stride 1 or 2, a flipped row or channel axis, interleaved or planar) whose target buffer is
 //     EXACTLY the size of the view's hull, so a store outside it is the sanitizer's to report: on a good pair every sample must be
 //     felics_decompress's and every other byte of the hull untouched; on a mutated or foreign pair any code, no crash.
-// Built with -fsanitize=address,undefined by `make asan`; tests/test_index_cpu.py feeds it a mutated corpus.
+// `index_fuzz --index16 DIR` runs the 16-bit index's two host functions instead (felics_index16.cpp): felics_index16_build at the same
+// two segment sizes; where it succeeds the size is within felics_index16_size_max, the two-call pattern holds,
+// felics_decompress_indexed16 gives felics_decompress's pixels, and the index goes through byte mutations (header, directory, rows'
+// context words, anywhere) and cuts; NAME.idx beside NAME is used as it is: any code, no crash.
+// Built with -fsanitize=address,undefined by `make asan`; tests/test_index_cpu.py and tests/test_index16_cpu.py feed it mutated corpora.
 // Exit code 0 = every input was handled without a sanitizer report and every accepted pair decoded to the right pixels.
 #include <dirent.h>
 
@@ -40,7 +44,110 @@ static bool ends_with(const std::string &s, const char *suffix) {
     return s.size() >= n && s.compare(s.size() - n, n, suffix) == 0;
 }
 
+// the --index16 mode
+static int fuzz16(const char *dir) {
+    {  // argument checks
+        size_t n = 7;
+        uint8_t b[64] = {0};
+        int bad = 0;
+        bad += felics_index16_build(nullptr, 5, 4096, b, sizeof b, &n) != FELICS_E_INVALID_ARGUMENT;
+        bad += felics_index16_build(b, sizeof b, 4096, b, sizeof b, nullptr) != FELICS_E_INVALID_ARGUMENT;
+        bad += felics_decompress_indexed16(nullptr, 5, b, sizeof b, b, sizeof b, nullptr) != FELICS_E_INVALID_ARGUMENT;
+        bad += felics_decompress_indexed16(b, sizeof b, nullptr, 5, b, sizeof b, nullptr) != FELICS_E_INVALID_ARGUMENT;
+        bad += felics_index16_size_max(1, 1, 0, 4095) != 0 || felics_index16_size_max(1, 1, 2, 4096) != 0 || felics_index16_size_max(1, 1, 0, 4096) != 192;  // (header, one entry, one window)
+        bad += felics_index16_size_max(0xFFFFFFFFu, 0xFFFFFFFFu, 1, 4096) != 0 || felics_index16_size_max(0, 5, 1, 4096) != 64;
+        if (bad) {
+            fprintf(stderr, "argument checks (16-bit): %d unexpected results\n", bad);
+            return 1;
+        }
+    }
+    DIR *d = opendir(dir);
+    if (!d) return 2;
+    std::vector<std::string> names;
+    while (dirent *e = readdir(d))
+        if (e->d_name[0] != '.' && !ends_with(e->d_name, ".idx")) names.push_back(e->d_name);
+    closedir(d);
+    size_t built = 0, refused = 0, mutations = 0, mut_accepted = 0, pairs = 0, pairs_ok = 0;
+    const size_t cap = 32u << 20;
+    std::vector<uint8_t> buf, given, px(cap), ref(cap), index(cap);
+    uint64_t rng = 0x9E3779B97F4A7C15ull;
+    auto next = [&]() {
+        rng ^= rng << 13;
+        rng ^= rng >> 7;
+        rng ^= rng << 17;
+        return rng;
+    };
+    for (const std::string &n : names) {
+        const std::string path = std::string(dir) + "/" + n;
+        if (!slurp(path, buf)) continue;
+        felics_header h, h2;
+        const int rc_plain = felics_decompress(buf.data(), buf.size(), ref.data(), ref.size(), &h);
+        if (rc_plain == FELICS_E_BUFFER_TOO_SMALL) continue;  // (larger than this driver's buffers)
+        const size_t frame = rc_plain == FELICS_OK ? (size_t)h.width * h.height * (h.color_type ? 3 : 1) * (h.pixel_depth ? 2 : 1) : 0;
+        if (slurp(path + ".idx", given)) {
+            pairs++;
+            if (felics_decompress_indexed16(buf.data(), buf.size(), given.data(), given.size(), px.data(), px.size(), &h2) == FELICS_OK) pairs_ok++;
+        }
+        for (uint32_t seg : {4096u, 12288u}) {
+            size_t ilen = 0;
+            const int rb = felics_index16_build(buf.data(), buf.size(), seg, index.data(), index.size(), &ilen);
+            if (rb != FELICS_OK) {
+                refused++;
+                continue;
+            }
+            built++;
+            if (rc_plain != FELICS_OK || !h.pixel_depth) {
+                fprintf(stderr, "%s: an index was built of a stream felics_decompress refuses (%d) or of an 8-bit stream\n", n.c_str(), rc_plain);
+                return 1;
+            }
+            if (ilen > felics_index16_size_max(h.width, h.height, h.color_type, seg) || ilen % 64) {
+                fprintf(stderr, "%s: index of %zu bytes, felics_index16_size_max says less\n", n.c_str(), ilen);
+                return 1;
+            }
+            size_t need = 0;  // a short buffer: refused with the size, nothing written behind it
+            if (felics_index16_build(buf.data(), buf.size(), seg, index.data() + ilen, ilen - 1, &need) != FELICS_E_BUFFER_TOO_SMALL || need != ilen) {
+                fprintf(stderr, "%s: short buffer not refused with the size\n", n.c_str());
+                return 1;
+            }
+            const int rc = felics_decompress_indexed16(buf.data(), buf.size(), index.data(), ilen, px.data(), px.size(), &h2);
+            if (rc != FELICS_OK || memcmp(px.data(), ref.data(), frame) != 0) {
+                fprintf(stderr, "%s: indexed decode %d, or other pixels than felics_decompress\n", n.c_str(), rc);
+                return 1;
+            }
+            const std::vector<uint8_t> idx(index.begin(), index.begin() + ilen);
+            const size_t entries = (size_t)(h.color_type ? 3 : 1) * (((size_t)h.width * h.height + seg - 1) / seg);
+            const int rounds = ilen > (1u << 20) ? 4 : 10;  // (a call clears a table of 7.9 MB: fewer rounds than the 8-bit mode's)
+            for (int m = 0; m < rounds; m++) {
+                std::vector<uint8_t> bad = idx;
+                const int flips = 1 + (int)(next() % 3);
+                for (int f = 0; f < flips; f++) {
+                    // header fields, a directory entry, the context word of a row from the end, or anywhere
+                    const uint64_t r = next() & 3;
+                    size_t pos = (size_t)(next() % ilen);
+                    if (r == 0) pos = (size_t)(next() % 64);
+                    else if (r == 1 && entries) pos = 64 + (size_t)(next() % (32 * entries));
+                    else if (r == 2 && ilen >= 128) pos = ilen - 64 * (1 + (size_t)(next() % std::min<size_t>(8, ilen / 64 - 1))) + 60 + (size_t)(next() % 4);
+                    bad[pos % ilen] ^= (uint8_t)(1u << (next() % 8));
+                }
+                mutations++;
+                if (felics_decompress_indexed16(buf.data(), buf.size(), bad.data(), bad.size(), px.data(), px.size(), &h2) == FELICS_OK) mut_accepted++;
+                if (m % 5 == 0) {  // and cut short
+                    const size_t cut = (size_t)(next() % ilen);
+                    if (felics_decompress_indexed16(buf.data(), buf.size(), bad.data(), cut, px.data(), px.size(), &h2) == FELICS_OK) {
+                        fprintf(stderr, "%s: an index cut to %zu of %zu bytes was accepted\n", n.c_str(), cut, ilen);
+                        return 1;
+                    }
+                }
+            }
+        }
+    }
+    printf("index_fuzz --index16: %zu files, %zu indexes built, %zu refused, %zu pairs (%zu accepted), %zu mutations (%zu accepted)\n", names.size(), built,
+           refused, pairs, pairs_ok, mutations, mut_accepted);
+    return 0;
+}
+
 int main(int argc, char **argv) {
+    if (argc >= 3 && strcmp(argv[1], "--index16") == 0) return fuzz16(argv[2]);
     if (argc < 2) {
         fprintf(stderr, "usage: index_fuzz DIR\n");
         return 2;

@@ -386,7 +386,8 @@ uint32_t felics_decode_lanes_min_streams(int depth, int color);
  * WHAT THE CHECKS DO NOT PROVE: an index that passes all of this but was built from another stream can still yield wrong pixels,
  * as a corrupt stream can.  Pairing index and stream is the caller's contract.  No index makes the decoder read or write out of
  * bounds.  The REGION calls (below) prove less still: they make the checks of the segments a region needs and of no other, and
- * no end check where a walk stops early.  16-bit streams have no index: every call here returns FELICS_E_UNSUPPORTED for them. */
+ * no end check where a walk stops early.  16-bit streams have none in these calls; see "Restart index: 16-bit streams" below: every call here
+ * returns FELICS_E_UNSUPPORTED for them. */
 #define FELICS_INDEX_GRANULE 4096u
 
 /* Host only: the size of the index of a w x h 8-bit image; 0 for depth 16, a bad colour, w * h >= 2^32 or a segment_pixels that
@@ -670,6 +671,106 @@ typedef struct felics_index_emit_stats {
 } felics_index_emit_stats;
 /* Writes min(out_size, sizeof(felics_index_emit_stats)) bytes, never more. */
 int felics_get_index_emit_stats(const felics_ctx *ctx, felics_index_emit_stats *out, size_t out_size);
+
+/* ---- Restart index: 16-bit streams ----
+ * The same idea for streams of 16-bit samples, in a format of its own (version 2) and through calls of their own; the calls above
+ * keep refusing 16-bit input.  A 16-bit plane has up to 131 071 contexts of fifteen 32-bit counters: a dense state per checkpoint
+ * would be 7.9 MB, and how many contexts are live depends on the content.  So a checkpoint's state is SPARSE -- one 64-byte row per
+ * live context -- and the size of an index is not a function of the shape (felics_index16_size_max bounds it).
+ *
+ * Format (one blob per stream, little-endian, 64-byte aligned where a device call reads it).  segment_pixels and K as above; C planes.
+ *   header, 64 bytes : "FLCX" | u16 version = 2 | u8 colour | u8 depth = 1 | u32 width | u32 height | u32 segment_pixels | u32 K |
+ *                      u64 plane_end_bit[3] (as in version 1) | u64 total_bytes (of the whole index) | 8 reserved zero bytes
+ *   directory, at 64 : C * K entries of 32 bytes in (plane, segment) order:
+ *                      u64 bit_offset (as in version 1) | u64 rows_off | u32 n_rows | 12 reserved zero bytes
+ *   windows          : from win_base = round_up(64 + 32 * C * K, 64); window (c, j) at win_base + (c * K + j) * win_bytes,
+ *                      win_bytes = round_up(2 W * sb, 16): the plane's samples p0 - 2 W .. p0 - 1, zero in front of the plane;
+ *                      sb = 2 (u16) for gray, 4 (i32) for Y / Co / Cg
+ *   state rows       : from rows_base = round_up(win_base + C * K * win_bytes, 64); a row is u32 counter[15] | u32 context.
+ *                      Checkpoint (c, j)'s rows are the n_rows rows at rows_off, contexts strictly ascending.  CANONICAL FORM: a
+ *                      context has a row if and only if it has an out-of-range pixel in front of p0 (its counters are not zero)
+ *                      and one at or behind p0 in that plane (its state is read again); segment 0 has none.  Rows are CHAINED in
+ *                      (plane, segment) order: rows_off(0, 0) = rows_base, every other rows_off = the one before + 64 * n_rows,
+ *                      and the last chain ends at total_bytes.  An empty image: K = 0, the header alone, total_bytes = 64.
+ * Checks, the same on the host and on the GPU, in this order; any failure is FELICS_E_INVALID_INDEX: version 1's header checks
+ * (version 2, depth 1); total_bytes = the length the caller gave (and >= rows_base); the reserved bytes are zero; version 1's
+ * bit-offset rules; rows_off >= rows_base, a multiple of 64, rows_off + 64 * n_rows <= total_bytes and equal to its successor's
+ * rows_off (total_bytes for the last entry); n_rows = 0 for j = 0; every context below 65 536 (gray, Y) or 131 071 (Co / Cg) and
+ * above the one in front of it; every window sample in the plane's range (0..65535, Co / Cg -65535..65535); and the END CHECK.
+ * WHAT THE CHECKS DO NOT PROVE: as above, and COUNTERS ARE NOT JUDGED: a forged counter gives a wrong Rice parameter in a segment
+ * whose end check then fails (or whose pixels are wrong, as with an index of another stream); no address depends on a counter.
+ * NOT HERE: the encoder emitting this index (the 16-bit pipeline keeps k per pixel, not states per record); regions, views and
+ * mixed shapes, a lane form, a queued form; a hashed table for small segments; cfelics / dfelics flags.
+ * NAMES: the library's symbols hold no digit, like every other symbol of this ABI (its symbol check reads names as letters and
+ * underscores), so the five functions are exported as felics_index_wide_size_max, felics_index_wide_build,
+ * felics_decompress_indexed_wide, felics_decompress_batch_device_indexed_wide and felics_get_index_wide_stats ("wide" as in the 16-bit
+ * encoder).  C and C++ callers may use the names felics_index16_size_max, felics_index16_build, felics_decompress_indexed16,
+ * felics_decompress_batch_device_indexed16 and felics_get_index16_stats, inline aliases defined behind the declarations; a binding
+ * that looks symbols up by name (ctypes, a Rust extern block) uses the exported ones. */
+
+/* Host only: an upper bound of the size of the version-2 index of a w x h 16-bit image, for sizing buffers (checkpoint (c, j) has at
+ * most min(p0 - 2, w * h - p0, contexts of plane c) rows); 0 for a bad colour, w * h >= 2^32 or a bad segment_pixels. */
+size_t felics_index_wide_size_max(uint32_t w, uint32_t h, int color, uint32_t segment_pixels);
+
+/* Host only: builds the version-2 index of ANY 16-bit stream by decoding it once on the CPU.  The two-call pattern of
+ * felics_index_build: FELICS_E_BUFFER_TOO_SMALL with *index_len = the exact size.  FELICS_E_UNSUPPORTED for an 8-bit stream, the
+ * stream's own decode error for a bad stream, FELICS_E_INVALID_ARGUMENT for a bad segment_pixels or bytes behind the last code. */
+int felics_index_wide_build(const uint8_t *in, size_t len, uint32_t segment_pixels, uint8_t *index, size_t cap, size_t *index_len);
+
+/* Host only: felics_decompress of a 16-bit stream through its index -- segment by segment, each from its checkpoint alone (the table
+ * is exactly the checkpoint's rows, nothing is carried over).  The host model of k_decode16_seg.  pixels: uint16 samples,
+ * pixels_cap in bytes.  FELICS_E_UNSUPPORTED for an 8-bit stream. */
+int felics_decompress_indexed_wide(const uint8_t *in, size_t len, const uint8_t *index, size_t index_len, void *pixels, size_t pixels_cap,
+                                felics_header *hdr);
+
+/* GPU: n 16-bit streams of ONE shape, colour, segment_pixels and K, each with its version-2 index (index i at
+ * d_index + idx_offsets[i], idx_lens[i] bytes: the indexes differ in length; HOST arrays; d_index and every offset a multiple of 64,
+ * else FELICS_E_INVALID_ARGUMENT), decoded a wave per (stream, plane, segment): k_decode16_seg.  Output layout and status conventions
+ * of felics_decompress_batch_device; stream 0's header names the shape, index 0's header segment_pixels and K, and a stream whose own
+ * headers differ gets FELICS_E_INVALID_DIMENSIONS or FELICS_E_INVALID_INDEX.  All checks above are made on the device; status[i] is
+ * the code of stream i's first failing segment in (plane, segment) order.  A failing segment leaves only its own samples undefined;
+ * an RGB frame with a failing segment is not converted.  Before anything is launched: FELICS_E_UNSUPPORTED in every status for an
+ * 8-bit batch and for a row too wide for the kernel's LDS (no host fallback), FELICS_E_BUFFER_TOO_SMALL for a short d_pixels_cap;
+ * refused while a ticket is outstanding.  Blocking; creates no HIP stream.
+ * Every wave of a pass owns a dense estimator table (8.4 MB) in the buffer the unindexed 16-bit decoder uses, bounded as there (a
+ * quarter of the free memory); a call whose waves do not fit runs in passes of consecutive (stream, plane, segment) items.
+ * FELICS_TEST_INDEX16_PASS=k in the environment (read per call) caps a pass at k waves (tests). */
+int felics_decompress_batch_device_indexed_wide(felics_ctx *ctx, size_t n, const void *d_streams, const uint64_t *offsets, const uint64_t *lens,
+                                             const void *d_index, const uint64_t *idx_offsets, const uint64_t *idx_lens, void *d_pixels,
+                                             size_t d_pixels_cap, felics_header *hdr, int *status);
+
+/* What a context's felics_decompress_batch_device_indexed16 calls did so far (cumulative but table_bytes: the last call's). */
+typedef struct felics_index16_stats {
+    uint64_t streams;      /* streams handed to the call (calls that passed the checks made before a launch) */
+    uint64_t segments16;   /* waves: the sum of n * C * max(K, 1) */
+    uint64_t passes;       /* launches of k_decode16_seg */
+    uint64_t rows_loaded;  /* state rows copied into tables */
+    uint64_t table_bytes;  /* estimator tables of one pass of the last call */
+} felics_index16_stats;
+/* Writes min(out_size, sizeof(felics_index16_stats)) bytes, never more. */
+int felics_get_index_wide_stats(const felics_ctx *ctx, felics_index16_stats *out, size_t out_size);
+
+/* The same five under the names with "16" (see NAMES above): aliases, not symbols. */
+static inline size_t felics_index16_size_max(uint32_t w, uint32_t h, int color, uint32_t segment_pixels) {
+    return felics_index_wide_size_max(w, h, color, segment_pixels);
+}
+static inline int felics_index16_build(const uint8_t *in, size_t len, uint32_t segment_pixels, uint8_t *index, size_t cap, size_t *index_len) {
+    return felics_index_wide_build(in, len, segment_pixels, index, cap, index_len);
+}
+static inline int felics_decompress_indexed16(const uint8_t *in, size_t len, const uint8_t *index, size_t index_len, void *pixels,
+                                              size_t pixels_cap, felics_header *hdr) {
+    return felics_decompress_indexed_wide(in, len, index, index_len, pixels, pixels_cap, hdr);
+}
+static inline int felics_decompress_batch_device_indexed16(felics_ctx *ctx, size_t n, const void *d_streams, const uint64_t *offsets,
+                                                           const uint64_t *lens, const void *d_index, const uint64_t *idx_offsets,
+                                                           const uint64_t *idx_lens, void *d_pixels, size_t d_pixels_cap, felics_header *hdr,
+                                                           int *status) {
+    return felics_decompress_batch_device_indexed_wide(ctx, n, d_streams, offsets, lens, d_index, idx_offsets, idx_lens, d_pixels, d_pixels_cap, hdr,
+                                                       status);
+}
+static inline int felics_get_index16_stats(const felics_ctx *ctx, felics_index16_stats *out, size_t out_size) {
+    return felics_get_index_wide_stats(ctx, out, out_size);
+}
 
 /* Text for a code above; for FELICS_E_HIP felics_last_error(ctx) has the HIP message. */
 const char *felics_strerror(int code);
