@@ -13,6 +13,9 @@ FELICS_TEST_DECODE16_LANES=0 around the call):
   indexed   one 2048 x 2048 gray8 S1 stream, indexed at segment 32 768                 k_decode8_seg
   indexed_rgb  one 1024 x 1024 RGB8 stream, indexed at segment 32 768                  k_decode8_seg, three planes
   regions   64 windows of 256 x 256 at seeded positions over the `indexed` stream, felics_decompress_regions_device_indexed   k_decode8_region
+  indexed_views  the `indexed` stream into a 2048 x 2048 view of pitch 2 112, felics_decompress_views_device_indexed   k_decode8_seg_views
+  indexed16      one 1024 x 1024 gray16 stream, its index built on the host at segment 32 768, felics_decompress_batch_device_indexed_wide   k_decode16_seg
+  indexed16_rgb  one 512 x 512 RGB16 stream, indexed at segment 8 192                  k_decode16_seg, three planes
 and in the lane form (FELICS_TEST_DECODE_LANES=1, FELICS_TEST_DECODE16_LANES=1 or FELICS_TEST_INDEX_LANES=1 around the call) -- to a
 change of one form the other form's workloads are the control, code it leaves alone:
   lanes8    4 096 gray8 streams of 64 x 64                                             k_decode8_lanes<false, LaneUniform>
@@ -30,7 +33,13 @@ first call of a workload decoded with the frames and prints a digest of it.
 
 The protocol runs twice.  First with the parent's library in BOTH seats: the relative difference of the two seats' medians is the
 workload's margin -- what the protocol itself cannot tell apart.  Then the parent's library against this build: no workload's median
-may exceed the parent's by more than its margin (exit status 1 otherwise)."""
+may exceed the parent's by more than its margin (exit status 1 otherwise).
+
+That margin comes from one pair of seats and is smaller than what two invocations differ by on code that did not change
+(profiles/lane_fold.txt).  --first FILE names the --out file of an earlier invocation; this one then adds, per workload: the noise =
+(max - min) / min over the parent's six medians (both seats of run 1 and seat a of run 2, of both invocations), and SLOWER only if this
+build's median exceeds the parent's seat-a median of the same run 2 by more than that noise in BOTH invocations; the exit status is
+then this rule's (1: a workload is slower, or pixels differ)."""
 import argparse
 import hashlib
 import os
@@ -39,11 +48,14 @@ import subprocess
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-WORKLOADS = ("gray8", "rgb8", "gray16", "rgb16", "pitched8", "mixed8", "indexed", "indexed_rgb", "regions", "lanes8", "lanes8_rgb", "lanes16",
+WORKLOADS = ("gray8", "rgb8", "gray16", "rgb16", "pitched8", "mixed8", "indexed", "indexed_rgb", "regions", "indexed_views", "indexed16",
+             "indexed16_rgb", "lanes8", "lanes8_rgb", "lanes16",
              "lanes16_rgb", "lanes8_pitched", "lanes8_mixed", "indexed_lanes", "indexed_lanes_rgb")
 SEGMENT = 32768
 PITCH = 576
 LANE_SEGMENT = 4096
+VIEW_PITCH = 2112
+SEGMENT16_RGB = 8192
 LANE_PITCH = 80
 
 
@@ -75,6 +87,18 @@ def child():
         offs, lens = enc.compress_batch_device(d.data_ptr(), n, w, h, color, depth, out.data_ptr(), cap)
         return d, out, offs, lens
 
+    def encode16_indexed(frames, w, h, color, seg):
+        """a 16-bit set whose version-2 indexes are built on the host from the streams: -> (..., device indexes, their offsets, lengths)"""
+        d, out, offs, lens = encode(frames, w, h, color, 1)
+        host = out.cpu().numpy()
+        blob, ioffs, ilens = bytearray(), [], []
+        for o, l in zip(offs, lens):
+            ix = api.index16_build(host[int(o):int(o) + int(l)].tobytes(), seg)
+            ioffs.append(len(blob))
+            ilens.append(len(ix))
+            blob += ix + bytes((-len(ix)) % 64)
+        return d, out, offs, lens, torch.from_numpy(np.frombuffer(bytes(blob), np.uint8).copy()).cuda(), ioffs, ilens
+
     g8 = np.stack([synth.gray8(512, 512, f, "S1") for f in range(64)])
     c8 = np.stack([synth.rgb8(512, 512, f) for f in range(64)])
     g16 = np.stack([synth.gray16(512, 512, f) for f in range(64)])
@@ -86,7 +110,10 @@ def child():
     small = np.stack([synth.gray8(64, 64, f, "S1") for f in range(4096)])
     sets = {"gray8": encode(g8, 512, 512, 0, 0), "rgb8": encode(c8, 512, 512, 1, 0), "gray16": encode(g16, 512, 512, 0, 1),
             "rgb16": encode(c16, 256, 256, 1, 1), "indexed": encode(big, 2048, 2048, 0, 0, SEGMENT),
-            "indexed_rgb": encode(bigc, 1024, 1024, 1, 0, SEGMENT), "lanes8": encode(small, 64, 64, 0, 0),
+            "indexed_rgb": encode(bigc, 1024, 1024, 1, 0, SEGMENT),
+            "indexed16": encode16_indexed(synth.gray16(1024, 1024, 0)[None], 1024, 1024, 0, SEGMENT),
+            "indexed16_rgb": encode16_indexed(np.stack([synth.gray16(512, 512, c) for c in range(3)], axis=-1)[None], 512, 512, 1, SEGMENT16_RGB),
+            "lanes8": encode(small, 64, 64, 0, 0),
             "lanes8_rgb": encode(np.stack([synth.rgb8(64, 64, f) for f in range(1024)]), 64, 64, 1, 0),
             "lanes16": encode(np.stack([synth.gray16(64, 64, f) for f in range(1024)]), 64, 64, 0, 1),
             "lanes16_rgb": encode(np.stack([np.stack([synth.gray16(64, 64, 3 * f + c) for c in range(3)], axis=-1) for f in range(512)]), 64, 64, 1, 1),
@@ -94,13 +121,15 @@ def child():
             "indexed_lanes_rgb": encode(np.stack([synth.rgb8(256, 256, f) for f in range(128)]), 256, 256, 1, 0, LANE_SEGMENT)}
     sets["pitched8"] = sets["mixed8"] = sets["gray8"]
     sets["lanes8_pitched"] = sets["lanes8_mixed"] = sets["lanes8"]
-    sets["regions"] = sets["indexed"]
+    sets["regions"] = sets["indexed_views"] = sets["indexed"]
     want = {k: v[0].cpu().numpy().view(np.uint8).reshape(-1) for k, v in sets.items()}
     want["regions"] = np.concatenate([big[0, y:y + h, x:x + w].reshape(-1) for _, x, y, w, h in windows])
     mosaics = {"pitched8": torch.zeros((64, 512, PITCH), dtype=torch.uint8, device="cuda"),
-               "lanes8_pitched": torch.zeros((4096, 64, LANE_PITCH), dtype=torch.uint8, device="cuda")}
+               "lanes8_pitched": torch.zeros((4096, 64, LANE_PITCH), dtype=torch.uint8, device="cuda"),
+               "indexed_views": torch.zeros((1, 2048, VIEW_PITCH), dtype=torch.uint8, device="cuda")}
     views = {"pitched8": [mosaics["pitched8"][i, :, :512] for i in range(64)],
-             "lanes8_pitched": [mosaics["lanes8_pitched"][i, :, :64] for i in range(4096)]}
+             "lanes8_pitched": [mosaics["lanes8_pitched"][i, :, :64] for i in range(4096)],
+             "indexed_views": [mosaics["indexed_views"][0, :, :2048]]}
     dest = {k: torch.zeros(len(v), dtype=torch.uint8, device="cuda") for k, v in want.items() if k not in mosaics}
 
     def decoded(name):  # the bytes a call of `name` wrote, as the frames lie
@@ -111,7 +140,11 @@ def child():
         os.environ["FELICS_TEST_DECODE_LANES"] = "1" if name.startswith("lanes8") else "0"  # (read per call)
         os.environ["FELICS_TEST_DECODE16_LANES"] = "1" if name.startswith("lanes16") else "0"
         os.environ["FELICS_TEST_INDEX_LANES"] = "1" if name.startswith("indexed_lanes") else "0"
-        if name in mosaics:
+        if name == "indexed_views":
+            enc.decompress_arrays_device_indexed(s[1].data_ptr(), s[2], s[3], s[4].data_ptr(), [0], [s[5]], views[name])
+        elif name.startswith("indexed16"):
+            enc.decompress_batch_device_indexed16(s[1].data_ptr(), s[2], s[3], s[4].data_ptr(), s[5], s[6], dest[name].data_ptr(), dest[name].numel())
+        elif name in mosaics:
             enc.decompress_arrays_device(s[1].data_ptr(), s[2], s[3], views[name])
         elif name in ("mixed8", "lanes8_mixed"):
             enc.decompress_images_device(s[1].data_ptr(), s[2], s[3], dest[name].data_ptr(), dest[name].numel())
@@ -205,6 +238,18 @@ def fmt(v):
     return "%10.4f ms (%.4f .. %.4f)" % (statistics.median(v), min(v), max(v))
 
 
+def medians_of(path):
+    """{workload: (run 1 seat a, run 1 seat b, run 2 parent, run 2 this build)} of an --out file's medians"""
+    m = {}
+    for line in open(path):
+        f = line.split()
+        if len(f) > 9 and f[0] in WORKLOADS and f[1] == "a":
+            m[f[0]] = [float(f[2]), float(f[f.index("b") + 1])]
+        elif len(f) > 9 and f[0] in WORKLOADS and f[1] == "parent":
+            m[f[0]] += [float(f[2]), float(f[f.index("this") + 1])]
+    return m
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--child", action="store_true")
@@ -212,6 +257,7 @@ def main():
     ap.add_argument("--parent-source", default="not given", help="the parent build's source hash (felics_amd.build.source_hash() in its tree)")
     ap.add_argument("--reps", type=int, default=15)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--first", default=None, help="the --out file of an earlier invocation: judge both by the parent's spread over the two")
     a = ap.parse_args()
     if a.child:
         return child()
@@ -226,7 +272,7 @@ def main():
         lines.append(s)
         print(s, flush=True)
 
-    ok = True
+    ok = pixels = True
     same_ts, ready, info = protocol(a.parent_lib, a.parent_lib, a.reps)
     say("decode_walk_ab.py: device %s; a child process per library, seats alternating call by call, medians of %d after 2 warm-up rounds"
         % (ready[0][0], a.reps))
@@ -237,7 +283,7 @@ def main():
         ma, mb = statistics.median(same_ts[w][0]), statistics.median(same_ts[w][1])
         margin[w] = abs(ma - mb) / min(ma, mb)
         good = info[0][w]["ok"] == "1" and info[1][w]["ok"] == "1"
-        ok = ok and good
+        ok, pixels = ok and good, pixels and good
         say("  %-17s a %s  b %s  margin %.4f %%  pixels %s" % (w, fmt(same_ts[w][0]), fmt(same_ts[w][1]), 100 * margin[w], "ok" if good else "WRONG"))
     ts, ready, info = protocol(a.parent_lib, None, a.reps)
     say("run 2, seat a = the parent's library, seat b = this build (library sha256 %s...):" % ready[1][1])
@@ -245,10 +291,24 @@ def main():
         ma, mb = statistics.median(ts[w][0]), statistics.median(ts[w][1])
         good = info[1][w]["ok"] == "1" and info[0][w]["sha"] == info[1][w]["sha"]
         within = mb <= ma * (1 + margin[w])
-        ok = ok and good and within
+        ok, pixels = ok and good and within, pixels and good
         say("  %-17s parent %s  this %s  this / parent - 1 = %+.4f %%  (margin %.4f %%): %s; pixels %s"
             % (w, fmt(ts[w][0]), fmt(ts[w][1]), 100 * (mb / ma - 1), 100 * margin[w], "within" if within else "EXCEEDS", "identical" if good else "DIFFER"))
     say("verdict: %s" % ("every workload within its margin, pixels identical" if ok else "MISSED (see above)"))
+    if a.first:
+        first = medians_of(a.first)
+        say("both invocations (%s and this one): noise = (max - min) / min of the parent's six medians; this / parent - 1 of each run 2:" % a.first)
+        slower = []
+        for w in WORKLOADS:
+            here = [statistics.median(same_ts[w][0]), statistics.median(same_ts[w][1]), statistics.median(ts[w][0]), statistics.median(ts[w][1])]
+            par = first[w][:3] + here[:3]
+            noise = (max(par) - min(par)) / min(par)
+            d1, d2 = first[w][3] / first[w][2] - 1, here[3] / here[2] - 1
+            if d1 > noise and d2 > noise:
+                slower.append(w)
+            say("  %-17s noise %.4f %%  first %+.4f %%  this %+.4f %%: %s" % (w, 100 * noise, 100 * d1, 100 * d2, "SLOWER" if d1 > noise and d2 > noise else "not slower"))
+        say("by that rule: %s" % ("slower: " + ", ".join(slower) if slower else "no workload is slower"))
+        ok = pixels and not slower  # (the exit status is this rule's then)
     if a.out:
         with open(a.out, "w") as f:
             f.write("\n".join(lines) + "\n")
