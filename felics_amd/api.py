@@ -13,6 +13,7 @@ binary file objects, standing in for `W: Write` / `R: Read`.
 Encode runs on the GPU through the C ABI; this module has no other encode path and raises
 FelicsError if the HIP device or libfelics.so is missing.
 """
+import collections
 import ctypes as C
 import enum
 import importlib.util
@@ -112,6 +113,10 @@ class _CIndex16Stats(C.Structure):  # felics_index16_stats
                 ("table_bytes", C.c_uint64)]
 
 
+class _CIndex16EmitStats(C.Structure):  # felics_index16_emit_stats
+    _fields_ = [("streams", C.c_uint64), ("rows_written", C.c_uint64), ("index_bytes", C.c_uint64), ("passes", C.c_uint64)]
+
+
 class _CIndexEmitStats(C.Structure):  # felics_index_emit_stats
     _fields_ = [("indexes", C.c_uint64), ("checkpoints", C.c_uint64), ("in_mixed", C.c_uint64), ("redone", C.c_uint64)]
 
@@ -143,6 +148,8 @@ class Header:  # format.rs:44-49
         return "Header(%s, %s, %d, %d)" % (self.color_type.name, self.pixel_depth.name, self.width, self.height)
 
 
+IndexedStreams16 = collections.namedtuple("IndexedStreams16", "streams offsets lens index idx_offsets idx_lens")
+
 EXPORTS = [
     "felics_ctx_create", "felics_ctx_destroy", "felics_max_compressed_size", "felics_compress",
     "felics_compress_batch", "felics_compress_batch_device", "felics_submit_batch_device", "felics_wait_batch",
@@ -163,6 +170,7 @@ EXPORTS = [
     "felics_index_plan", "felics_compress_views_device_indexed", "felics_get_index_emit_stats",
     "felics_index_wide_size_max", "felics_index_wide_build", "felics_decompress_indexed_wide", "felics_decompress_batch_device_indexed_wide",
     "felics_get_index_wide_stats",
+    "felics_compress_batch_device_indexed_wide", "felics_get_index_wide_emit_stats",
 ]
 
 _lib = None
@@ -275,6 +283,11 @@ def lib():
         L.felics_decompress_batch_device_indexed_wide.argtypes = [vp, sz, vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), vp, C.POINTER(C.c_uint64),
                                                                C.POINTER(C.c_uint64), vp, sz, C.POINTER(_CHeader), C.POINTER(C.c_int)]
         L.felics_get_index_wide_stats.argtypes = [vp, C.POINTER(_CIndex16Stats), sz]
+    if hasattr(L, "felics_compress_batch_device_indexed_wide"):  # (as above: an older build's encoder writes no index for 16-bit streams)
+        u64 = C.POINTER(C.c_uint64)
+        L.felics_compress_batch_device_indexed_wide.argtypes = [vp, sz, vp, C.c_uint32, C.c_uint32, C.c_int, vp, sz, C.c_uint32, vp, sz, u64, u64,
+                                                               u64, u64, u64]
+        L.felics_get_index_wide_emit_stats.argtypes = [vp, C.POINTER(_CIndex16EmitStats), sz]
     L.felics_strerror.argtypes = [C.c_int]
     L.felics_strerror.restype = C.c_char_p
     L.felics_last_error.argtypes = [vp]
@@ -696,6 +709,76 @@ class Encoder:
         if rc != 0:
             self._raise(rc)
         return offs, lens
+
+    def compress_batch_device_indexed16_raw(self, d_pixels, n, w, h, color, d_out, d_out_cap, segment_pixels, d_index, d_index_cap):
+        """felics_compress_batch_device_indexed_wide on raw device pointers, one call: (rc, offsets, lens, idx_offsets, idx_lens,
+        idx_total).  rc = -8 with idx_total != 0: the index buffer is short of idx_total bytes (streams, offsets and lens are
+        complete); with idx_total == 0 it is the stream buffer, lens[0] = the bytes needed."""
+        u64 = C.POINTER(C.c_uint64)
+        arr = [np.zeros(n, dtype=np.uint64) for _ in range(4)]
+        total = C.c_uint64(0)
+        rc = lib().felics_compress_batch_device_indexed_wide(self._h, n, d_pixels, w, h, int(color), d_out, d_out_cap, segment_pixels, d_index,
+                                                             d_index_cap, *(a.ctypes.data_as(u64) for a in arr), C.byref(total))
+        return (rc, *arr, int(total.value))
+
+    def compress_batch_device_indexed16(self, frames, segment_pixels, alloc=None):
+        """felics_compress_batch_device_indexed_wide: `frames`, an object with __cuda_array_interface__ holding N dense uint16 frames of
+        one shape (N x H x W gray16, N x H x W x 3 RGB16), encoded as compress_batch_device encodes them, with the version-2 restart
+        index of every stream written on the GPU beside it.  The two buffers come from alloc(nbytes) -> an object with
+        __cuda_array_interface__ whose memory is 64-byte aligned (default: a torch uint8 tensor on the current device); the index
+        buffer is sized by the two-call pattern -- a first call with a guess, a second with idx_total bytes if the guess was short.
+        Returns IndexedStreams16(streams, offsets, lens, index, idx_offsets, idx_lens): the two device buffers and four numpy arrays,
+        what decompress_batch_device_indexed16 takes.  8-bit frames are refused (FELICS_E_UNSUPPORTED): compress_batch_device_indexed
+        is their call."""
+        cai = frames.__cuda_array_interface__
+        shape = tuple(cai["shape"])
+        if cai["typestr"] not in ("<u2", "=u2", "|u2"):
+            raise FelicsError(-10, "compress_batch_device_indexed16 takes uint16 frames")
+        if len(shape) not in (3, 4) or (len(shape) == 4 and shape[3] != 3):
+            raise ValueError("frames: N x H x W or N x H x W x 3")
+        if cai.get("strides") is not None:
+            dense = tuple(int(np.prod(shape[i + 1:])) * 2 for i in range(len(shape)))
+            if tuple(cai["strides"]) != dense:
+                raise ValueError("frames must be dense")
+        if alloc is None:
+            import torch
+
+            def alloc(nbytes):
+                return torch.empty(max(int(nbytes), 64), dtype=torch.uint8, device="cuda")
+        n, h, w = shape[:3]
+        color = 1 if len(shape) == 4 else 0
+        ptr = lambda buf: int(buf.__cuda_array_interface__["data"][0])
+        frame_bytes = h * w * 2 * (3 if color else 1)
+        out_cap = max(n, 1) * (frame_bytes + frame_bytes // 4 + 80)
+        idx_cap = 0
+        if n and index16_size_max(w, h, color, segment_pixels):  # the guess: header, directory, windows and 64 rows per checkpoint
+            planes, k = (3 if color else 1), -(-(h * w) // segment_pixels)
+            idx_cap = n * (256 + planes * k * (32 + 4 * w * (4 if color else 2) + 16 + 64 * 64))
+        streams, index = alloc(out_cap), alloc(max(idx_cap, 64))
+        for _ in range(8):
+            rc, offs, lens, ioffs, ilens, total = self.compress_batch_device_indexed16_raw(
+                int(cai["data"][0]), n, w, h, color, ptr(streams), out_cap, segment_pixels, ptr(index), idx_cap)
+            if rc == -8 and total:  # the streams are done; their indexes need `total` bytes
+                idx_cap = total
+                index = alloc(idx_cap)
+                continue
+            if rc == -8 and n and lens[0] > out_cap:
+                out_cap = int(lens[0]) + 64
+                streams = alloc(out_cap)
+                continue
+            break
+        if rc != 0:
+            self._raise(rc)
+        return IndexedStreams16(streams, offs, lens, index, ioffs, ilens)
+
+    def index16_emit_stats(self):
+        """felics_get_index_wide_emit_stats: streams handed to compress_batch_device_indexed16, the state rows and bytes of the indexes
+        written and the passes that wrote them (all cumulative)."""
+        st = _CIndex16EmitStats()
+        rc = lib().felics_get_index_wide_emit_stats(self._h, C.byref(st), C.sizeof(st))
+        if rc != 0:
+            raise FelicsError(rc)
+        return {k: int(getattr(st, k)) for k, _ in _CIndex16EmitStats._fields_}
 
     def submit_batch_device(self, d_pixels, n, w, h, color, depth, d_out, d_out_cap):
         """Queues a batch and returns a ticket; up to two can be in flight (felics_submit_batch_device)."""

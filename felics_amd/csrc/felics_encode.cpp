@@ -484,11 +484,64 @@ int apply_remedy(felics_ctx *ctx, const Lane &l, const SlotOutcome &o) {
     return FELICS_OK;
 }
 
+// The version-2 restart indexes of a 16-bit pass that has packed and is what the caller gets (felics_compress_batch_device_indexed16;
+// launch_index16_scan / _write, felics_kernels.h), from the lane's workspace: the sorted records and chain heads, the tiles' bit offsets,
+// the planes.  The size of an index depends on the content, so the host reads the totals between the two steps, places the pass's
+// indexes behind the ones before them and has only those written whose end lies inside the caller's buffer.  Queued on the tail
+// stream, behind pack_exact where that ran; returns with the tail stream's work queued (the caller's sync_lane waits for it).
+static int emit_index16(felics_ctx *ctx, Lane &l, size_t first, Index16Request &rq) {
+    const Geometry &g = l.g;
+    const Index16Layout L = index16_layout(g.W, g.H, g.color, rq.segment_pixels);
+    const size_t cps = (size_t)g.nplanes * L.K;
+    const uint32_t wpc = index16_words_per_checkpoint(g.color);
+    int rc;
+    if ((rc = reserve(ctx, l.i16_bitmap, cps * wpc * 4)) != 0) return rc;
+    if ((rc = reserve(ctx, l.i16_prefix, cps * wpc * 4)) != 0) return rc;
+    if ((rc = reserve(ctx, l.i16_nrows, cps * 4)) != 0) return rc;
+    if ((rc = reserve(ctx, l.i16_rows_off, cps * 8)) != 0) return rc;
+    if ((rc = reserve(ctx, l.i16_totals, (size_t)g.nimages * 16)) != 0) return rc;
+    if ((rc = reserve(ctx, l.i16_index_off, (size_t)g.nimages * 8)) != 0) return rc;
+    hipStream_t s = l.tail;
+    if (ctx->poison) {
+        DevBuf *bufs[] = {&l.i16_bitmap, &l.i16_prefix, &l.i16_nrows, &l.i16_rows_off, &l.i16_totals, &l.i16_index_off};
+        for (DevBuf *b : bufs) HIP_TRY(ctx, hipMemsetAsync(b->p, 0xA5, b->cap, s));
+    }
+    const Index16Emit e{rq.d_index, (const uint64_t *)l.i16_index_off.p, (uint32_t *)l.i16_bitmap.p, (uint32_t *)l.i16_prefix.p,
+                        (uint32_t *)l.i16_nrows.p, (uint64_t *)l.i16_rows_off.p, (uint64_t *)l.i16_totals.p, g.W, g.H, g.npix, g.color,
+                        g.planes_per_image, g.nplanes, g.nimages, L.K, rq.segment_pixels, wpc};
+    launch_index16_scan(s, (const uint64_t *)l.wrecs[0].p, (const uint32_t *)l.wmeta.p, g, e);
+    HIP_TRY(ctx, hipGetLastError());
+    std::vector<uint64_t> totals((size_t)g.nimages * 2), where(g.nimages);
+    HIP_TRY(ctx, hipMemcpyAsync(totals.data(), l.i16_totals.p, totals.size() * 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(ctx, hipStreamSynchronize(s));
+    uint64_t fit = 0, rows = 0;
+    for (size_t i = 0; i < g.nimages; i++) {
+        const uint64_t bytes = totals[2 * i];
+        rq.idx_offsets[first + i] = rq.total;
+        rq.idx_lens[first + i] = bytes;
+        const bool fits = bytes <= rq.cap && rq.total <= rq.cap - bytes;
+        where[i] = fits ? rq.total : ~0ull;
+        if (fits) fit++, rows += totals[2 * i + 1], rq.bytes += bytes;
+        else rq.too_small = true;
+        rq.total += bytes;  // (rows_base and a row are multiples of 64: so is every offset)
+    }
+    if (fit == 0) return FELICS_OK;
+    HIP_TRY(ctx, hipMemcpyAsync(l.i16_index_off.p, where.data(), where.size() * 8, hipMemcpyHostToDevice, s));
+    HIP_TRY(ctx, hipStreamSynchronize(s));  // (`where` is pageable and leaves scope)
+    launch_index16_write(s, l.d_planes, (const uint64_t *)l.wrecs[0].p, (const uint32_t *)l.wmeta.p, (const uint64_t *)l.heads.p,
+                         (const uint32_t *)l.scalars.p, (const uint64_t *)l.tile_bitoff.p, l.plane_base, l.plane_base - g.nplanes, g, e);
+    HIP_TRY(ctx, hipGetLastError());
+    rq.written += fit;
+    rq.rows += rows;
+    rq.passes++;
+    return FELICS_OK;
+}
+
 // Encode `n` same-shape frames resident in device memory into d_out (device), on one lane, and wait.
 // If d_out is NULL the context's own output buffer is used (and grown).
 int encode_device(felics_ctx *ctx, Lane &l, size_t n, const void *d_pixels, uint32_t w, uint32_t h, int color, int depth,
                   uint8_t *d_out, size_t d_out_cap, uint64_t *offsets, uint64_t *lens, uint8_t **used_out, bool start_exact,
-                  const IndexRequest *index) {
+                  const IndexRequest *index, Index16Request *index16) {
     const uint32_t planes = color == FELICS_COLOR_RGB ? 3 : 1;
     const uint64_t npix = (uint64_t)w * h;
     const bool wide = depth == FELICS_DEPTH_16;
@@ -524,7 +577,8 @@ int encode_device(felics_ctx *ctx, Lane &l, size_t n, const void *d_pixels, uint
     }
 
     const size_t frame_bytes = (size_t)npix * planes * (wide ? 2 : 1);
-    const size_t per_pass = max_images_per_pass(npix, planes, depth);
+    size_t per_pass = max_images_per_pass(npix, planes, depth);
+    if (index16) per_pass = std::max<size_t>(1, std::min(per_pass, index16->pass_images));  // (its workspace per checkpoint: the entry point's bound)
     int rc;
     // Placement.  Preferred: every stream gets a fixed slot (stream i at i * slot), so packing needs no
     // size from the host and follows the spine slice by slice.  If a stream outgrows its slot, or the
@@ -548,6 +602,7 @@ int encode_device(felics_ctx *ctx, Lane &l, size_t n, const void *d_pixels, uint
         size_t done = 0;
         uint64_t out_base = 0;  // exact placement: where the next pass's streams start
         SlotOutcome outcome;
+        if (index16) index16->total = index16->written = index16->bytes = index16->rows = index16->passes = 0, index16->too_small = false;
         // passes of up to per_pass frames (one pass unless the batch is huge)
         while (done < n && !outcome.overflow && !outcome.redo()) {
             const size_t cnt = std::min(per_pass, n - done);
@@ -601,6 +656,10 @@ int encode_device(felics_ctx *ctx, Lane &l, size_t n, const void *d_pixels, uint
                 launch_index_emit(l.tail, l.d_planes, (const uint32_t *)l.counts.p, (const uint4 *)l.block_state.p, l.m_cap,
                                   (const uint64_t *)l.tile_bitoff.p, l.plane_base, l.plane_base - l.g.nplanes, l.g, at, index->segment_pixels);
                 HIP_TRY(ctx, hipGetLastError());
+            }
+            if (index16 && !outcome.redo() && !outcome.overflow && (rc = emit_index16(ctx, l, done, *index16)) != 0) {
+                (void)sync_lane(ctx, l);
+                return rc;
             }
             if ((rc = sync_lane(ctx, l)) != 0) return rc;
             done = first;
@@ -656,6 +715,73 @@ int felics_compress_batch_device_indexed(felics_ctx *ctx, size_t n, const void *
         for (size_t i = 0; i < n; i++) HIP_TRY(ctx, hipMemcpy((uint8_t *)d_index + i * bytes, ih, bytes, hipMemcpyHostToDevice));
     }
     return rc;
+}
+
+int felics_compress_batch_device_indexed_wide(felics_ctx *ctx, size_t n, const void *d_pixels, uint32_t w, uint32_t h, int color, void *d_out,
+                                              size_t d_out_cap, uint32_t segment_pixels, void *d_index, size_t d_index_cap, uint64_t *offsets,
+                                              uint64_t *lens, uint64_t *idx_offsets, uint64_t *idx_lens, uint64_t *idx_total) {
+    if (!ctx || !d_out || !d_index || (!d_pixels && n && (uint64_t)w * h)) return FELICS_E_INVALID_ARGUMENT;
+    if (n && (!offsets || !lens || !idx_offsets || !idx_lens)) return FELICS_E_INVALID_ARGUMENT;
+    if (ctx->failed) return FELICS_E_HIP;
+    int rc = check_args(w, h, color, FELICS_DEPTH_16);
+    if (rc) return rc;
+    if (!index_segment_ok(segment_pixels) || ((uintptr_t)d_index & 63u)) return FELICS_E_INVALID_ARGUMENT;
+    if (idx_total) *idx_total = 0;
+    if (n == 0) return FELICS_OK;
+    if (any_pending(ctx)) return FELICS_E_INVALID_ARGUMENT;  // felics_wait_batch first
+    const uint32_t planes = color == FELICS_COLOR_RGB ? 3 : 1;
+    const uint64_t npix = (uint64_t)w * h;
+    Index16Request rq{(uint8_t *)d_index, d_index_cap, segment_pixels, SIZE_MAX, idx_offsets, idx_lens};
+    if (npix != 0) {
+        // the workspace per checkpoint (bitmap and prefix, a bit and a share of a word per context) bounds the images of a pass, within a
+        // quarter of the free device memory -- the 16-bit decoder's rule; an image whose own checkpoints do not fit is refused
+        if (npix > 0xFFFFFFFFull) return FELICS_E_UNSUPPORTED;
+        HIP_TRY(ctx, hipSetDevice(ctx->device));
+        size_t free_b = 0, total_b = 0;
+        HIP_TRY(ctx, hipMemGetInfo(&free_b, &total_b));
+        const Index16Layout L = index16_layout(w, h, (uint32_t)color, segment_pixels);
+        const uint64_t per_image = (uint64_t)planes * L.K * (index16_words_per_checkpoint((uint32_t)color) * 8ull + 12u) + 24u;
+        uint64_t budget = free_b / 4;
+        for (const Lane &l : ctx->lanes) budget += l.i16_bitmap.cap + l.i16_prefix.cap;  // (what this context holds already is its to use)
+        rq.pass_images = (size_t)(budget / per_image);
+        if (rq.pass_images == 0) return FELICS_E_UNSUPPORTED;
+    }
+    rc = encode_device(ctx, ctx->lanes[0], n, d_pixels, w, h, color, FELICS_DEPTH_16, (uint8_t *)d_out, d_out_cap, offsets, lens, nullptr, false,
+                       nullptr, &rq);
+    if (rc) return rc;
+    if (npix == 0) {
+        // an empty image (K = 0) is encoded on the host and so is its index: the version-2 header alone, as felics_index16_build writes it
+        uint8_t ih[INDEX_HEADER_BYTES];
+        empty_index(ih, w, h, (uint32_t)color, segment_pixels);
+        ih[IDX_VERSION] = (uint8_t)INDEX16_VERSION;
+        ih[IDX_DEPTH] = FELICS_DEPTH_16;
+        ih[IDX16_TOTAL] = (uint8_t)INDEX_HEADER_BYTES;
+        for (size_t i = 0; i < n; i++) {
+            idx_offsets[i] = rq.total;
+            idx_lens[i] = INDEX_HEADER_BYTES;
+            if (rq.total + INDEX_HEADER_BYTES <= d_index_cap) {
+                HIP_TRY(ctx, hipMemcpy((uint8_t *)d_index + rq.total, ih, INDEX_HEADER_BYTES, hipMemcpyHostToDevice));
+                rq.written++;
+                rq.bytes += INDEX_HEADER_BYTES;
+            } else {
+                rq.too_small = true;
+            }
+            rq.total += INDEX_HEADER_BYTES;
+        }
+    }
+    if (idx_total) *idx_total = rq.total;
+    felics_index16_emit_stats &st = ctx->i16estats;
+    st.streams += n;
+    st.rows_written += rq.rows;
+    st.index_bytes += rq.bytes;
+    st.passes += rq.passes;
+    return rq.too_small ? FELICS_E_BUFFER_TOO_SMALL : FELICS_OK;
+}
+
+int felics_get_index_wide_emit_stats(const felics_ctx *ctx, felics_index16_emit_stats *out, size_t out_size) {
+    if (!ctx || !out) return FELICS_E_INVALID_ARGUMENT;
+    memcpy(out, &ctx->i16estats, std::min(out_size, sizeof(felics_index16_emit_stats)));
+    return FELICS_OK;
 }
 
 int felics_submit_batch_device(felics_ctx *ctx, size_t n, const void *d_pixels, uint32_t w, uint32_t h, int color,

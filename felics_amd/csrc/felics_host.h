@@ -93,6 +93,9 @@ struct Lane {
         tile_bits, tile_bitoff, plane_sums, image_bytes, image_off, partial, status, edge_first, edge_last, pscratch;
     uint64_t *plane_base = nullptr;   // the sub-batch's plane bases (behind its plane carries; pack_exact reads them)
     DevBuf wrecs[2], wtile_cnt, wmeta, whist, wdigtot, heads, wlong;  // 16-bit samples: event records (sort double buffer), tile counts, plane ranges, digit histograms, chain heads
+    // felics_compress_batch_device_indexed16: per (plane, checkpoint) the contexts' bitmap and its popcount prefix, n_rows and rows_off;
+    // per image the index's bytes and rows (totals) and where it goes (index_off, written by the host): Index16Emit, felics_kernels.h
+    DevBuf i16_bitmap, i16_prefix, i16_nrows, i16_rows_off, i16_totals, i16_index_off;
     uint32_t epoch = 0;               // 8-bit sub-batches this lane has run (FELICS_TEST_LOOKBACK_EPOCH: plus a start value): its low 18 bits tag the look-back status words (felics_epochs.h)
     // the submission in flight on this lane (felics_submit_batch_device .. felics_wait_batch)
     bool pending = false;
@@ -228,6 +231,7 @@ struct felics_ctx {
     // writer, copied to where the caller wants them); the counts of felics_get_index_emit_stats
     DevBuf mix_index;
     felics_index_emit_stats iestats = {};
+    felics_index16_emit_stats i16estats = {};  // felics_compress_batch_device_indexed16: the counts of felics_get_index16_emit_stats
 };
 
 namespace felics {
@@ -276,9 +280,22 @@ struct IndexRequest {
     uint64_t bytes;           // felics_index_size of the shape
     uint32_t segment_pixels;
 };
+// (index16: felics_compress_batch_device_indexed16 -- 16-bit frames; every pass that comes out usable leaves the version-2 indexes of its
+// images one behind the other, as far as they fit, and what all of them need.  An attempt that redoes the batch starts the counts again.)
+struct Index16Request {
+    uint8_t *d_index;
+    uint64_t cap;             // bytes at d_index
+    uint32_t segment_pixels;
+    size_t pass_images;       // images of a pass at most: what the per-checkpoint workspace allows
+    uint64_t *idx_offsets, *idx_lens;  // [n], host
+    // the outcome of the last attempt
+    uint64_t total = 0;       // bytes all indexes need (each a multiple of 64)
+    uint64_t written = 0, bytes = 0, rows = 0, passes = 0;  // indexes written, their bytes and rows; passes that wrote any
+    bool too_small = false;   // an index did not fit and was not written
+};
 int encode_device(felics_ctx *ctx, Lane &l, size_t n, const void *d_pixels, uint32_t w, uint32_t h, int color, int depth, uint8_t *d_out,
                   size_t d_out_cap, uint64_t *offsets, uint64_t *lens, uint8_t **used_out, bool start_exact = false,
-                  const IndexRequest *index = nullptr);
+                  const IndexRequest *index = nullptr, Index16Request *index16 = nullptr);
 
 // the slot a stream gets unless the caller's buffer dictates another: the frame's size and a quarter, 16-byte aligned
 inline uint64_t default_slot(size_t frame_bytes) { return ((uint64_t)frame_bytes + frame_bytes / 4 + 64 + 15) & ~15ull; }

@@ -203,6 +203,29 @@ struct IndexGeom {
 void launch_index_emit_mixed(hipStream_t s, const uint32_t *runtab, const uint4 *state16, uint32_t cap, const uint64_t *tile_bitoff,
                              const uint64_t *plane_base, const uint64_t *plane_carry, const Geometry &g, const IndexGeom *rows, uint32_t max_K);
 
+// The version-2 restart index of every image of a 16-bit same-shape pass (felics_index16.hip; format: felics.h, felics_index.h), from what
+// run_wide leaves behind: the sorted records, their plane ranges (meta) and the chain heads, tile_bitoff / plane_base / plane_carry,
+// the planes' samples.  Two steps with the host between them, because an index's size depends on the content:
+//   launch_index16_scan   clears the bitmaps, marks, ranks and plans: n_rows and rows_off of every checkpoint, totals[2 i] = the bytes of
+//                         image i's index and totals[2 i + 1] = its rows
+//   launch_index16_write  image i's index to index + index_off[i] (64-byte aligned; ~0: this image's index is not written), every byte
+//                         of it -- nothing need be cleared beforehand
+// Workspace: bitmap and prefix hold wpc words per (plane, checkpoint) -- index16_words_per_checkpoint, a bit per context --,
+// n_rows a word and rows_off two.
+struct Index16Emit {
+    uint8_t *index;
+    const uint64_t *index_off;  // [nimages], device
+    uint32_t *bitmap, *prefix, *n_rows;
+    uint64_t *rows_off, *totals;
+    uint32_t W, H, npix, color, planes_per_image, nplanes, nimages;
+    uint32_t K, segment_pixels, wpc;
+};
+uint32_t index16_words_per_checkpoint(uint32_t color);
+void launch_index16_scan(hipStream_t s, const uint64_t *recs, const uint32_t *meta, const Geometry &g, const Index16Emit &e);
+void launch_index16_write(hipStream_t s, const void *planes, const uint64_t *recs, const uint32_t *meta, const uint64_t *heads, const uint32_t *nheads,
+                          const uint64_t *tile_bitoff, const uint64_t *plane_base, const uint64_t *plane_carry, const Geometry &g,
+                          const Index16Emit &e);
+
 // k_map / plane / slot buffers are read in whole 16-byte chunks by the tile staging
 constexpr size_t STAGE_PAD = 64;
 

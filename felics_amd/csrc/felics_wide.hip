@@ -14,6 +14,7 @@
 
 #include "felics_device.h"
 #include "felics_kernels.h"
+#include "felics_widerec.h"
 
 namespace felics {
 
@@ -90,14 +91,7 @@ __global__ __launch_bounds__(256) void k_rgb16_view_to_planes(const PlaneGeom *_
 constexpr uint32_t WT = 4096;       // samples per tile (count / emit), records per tile (sort passes)
 constexpr uint32_t WTHREADS = 256;  // threads per tile: 16 samples / records each
 constexpr uint32_t WDIG = 512;      // 9-bit digits
-constexpr uint32_t REC_CTX_BITS = 18, REC_E_BITS = 17;
-
-__device__ __forceinline__ uint64_t make_rec(uint32_t ctx, uint32_t e, uint32_t pix) {
-    return (uint64_t)ctx | ((uint64_t)e << REC_CTX_BITS) | ((uint64_t)pix << (REC_CTX_BITS + REC_E_BITS));
-}
-__device__ __forceinline__ uint32_t rec_ctx(uint64_t r) { return (uint32_t)r & ((1u << REC_CTX_BITS) - 1u); }
-__device__ __forceinline__ uint32_t rec_e(uint64_t r) { return (uint32_t)(r >> REC_CTX_BITS) & ((1u << REC_E_BITS) - 1u); }
-__device__ __forceinline__ uint32_t rec_pix(uint64_t r) { return (uint32_t)(r >> (REC_CTX_BITS + REC_E_BITS)); }
+// (the record's fields and their accessors: felics_widerec.h)
 
 // exclusive prefix of v over the WTHREADS threads of a workgroup (wsum: 4 words of LDS); *total = sum
 __device__ __forceinline__ uint32_t block_excl_scan(uint32_t v, uint32_t *wsum, uint32_t *total) {
@@ -235,8 +229,7 @@ __global__ __launch_bounds__(WTHREADS) void k_wide_count_pitched(const PitchedGe
 
 // One workgroup: exclusive scan of the tile counts (plane-major) in place; per plane its first record, its
 // number of sort tiles and the first of them.  meta (u32): [0] records in all, [1] sort tiles in all, then
-// plane_ev0[P + 1] at WMETA_EV0, stile_first[P + 1] behind it.
-constexpr uint32_t WMETA_EV0 = 4;
+// plane_ev0[P + 1] at WMETA_EV0 (felics_widerec.h), stile_first[P + 1] behind it.
 __global__ __launch_bounds__(1024) void k_wide_plan(uint32_t *__restrict__ tile_cnt, uint32_t ntiles, uint32_t nplanes,
                                                     uint32_t *__restrict__ meta) {
     __shared__ uint32_t wsum[16];
@@ -622,8 +615,7 @@ __global__ __launch_bounds__(WTHREADS) void k_wide_heads(const uint64_t *__restr
     }
 }
 
-constexpr int WIDE_NK = 15;             // K_VALUES = 0..=14 (traits.rs:36)
-constexpr uint32_t WIDE_HALVE = 1024;   // COUNT_SCALING (traits.rs:40)
+// (WIDE_NK = 15 counters, WIDE_HALVE = 1024: felics_widerec.h)
 
 // Four lanes per chain, sixteen chains per wave.  A batch of 4K frames has tens of thousands of chains of a few thousand
 // events each; replaying them event by event, the fifteen counters of a chain spread over four lanes (lane s of the four

@@ -699,14 +699,17 @@ int felics_get_index_emit_stats(const felics_ctx *ctx, felics_index_emit_stats *
  * above the one in front of it; every window sample in the plane's range (0..65535, Co / Cg -65535..65535); and the END CHECK.
  * WHAT THE CHECKS DO NOT PROVE: as above, and COUNTERS ARE NOT JUDGED: a forged counter gives a wrong Rice parameter in a segment
  * whose end check then fails (or whose pixels are wrong, as with an index of another stream); no address depends on a counter.
- * NOT HERE: the encoder emitting this index (the 16-bit pipeline keeps k per pixel, not states per record); regions, views and
- * mixed shapes, a lane form, a queued form; a hashed table for small segments; cfelics / dfelics flags.
+ * The encoder writes this index beside the streams of a blocking same-shape batch: felics_compress_batch_device_indexed16 below.
+ * NOT HERE: the encoder's index for views, mixed shapes, queued and host-buffer calls; regions, views and mixed shapes in the decoder,
+ * a lane form, a queued form; a hashed table for small segments; cfelics / dfelics flags (--index keeps refusing 16-bit images).
  * NAMES: the library's symbols hold no digit, like every other symbol of this ABI (its symbol check reads names as letters and
  * underscores), so the five functions are exported as felics_index_wide_size_max, felics_index_wide_build,
  * felics_decompress_indexed_wide, felics_decompress_batch_device_indexed_wide and felics_get_index_wide_stats ("wide" as in the 16-bit
  * encoder).  C and C++ callers may use the names felics_index16_size_max, felics_index16_build, felics_decompress_indexed16,
  * felics_decompress_batch_device_indexed16 and felics_get_index16_stats, inline aliases defined behind the declarations; a binding
- * that looks symbols up by name (ctypes, a Rust extern block) uses the exported ones. */
+ * that looks symbols up by name (ctypes, a Rust extern block) uses the exported ones.  The encoder's call and its counts follow the
+ * same rule: felics_compress_batch_device_indexed_wide and felics_get_index_wide_emit_stats, with the aliases
+ * felics_compress_batch_device_indexed16 and felics_get_index16_emit_stats. */
 
 /* Host only: an upper bound of the size of the version-2 index of a w x h 16-bit image, for sizing buffers (checkpoint (c, j) has at
  * most min(p0 - 2, w * h - p0, contexts of plane c) rows); 0 for a bad colour, w * h >= 2^32 or a bad segment_pixels. */
@@ -750,7 +753,52 @@ typedef struct felics_index16_stats {
 /* Writes min(out_size, sizeof(felics_index16_stats)) bytes, never more. */
 int felics_get_index_wide_stats(const felics_ctx *ctx, felics_index16_stats *out, size_t out_size);
 
-/* The same five under the names with "16" (see NAMES above): aliases, not symbols. */
+/* GPU: felics_compress_batch_device for depth = 16 (blocking, one shape, gray16 or RGB16; the call has no depth argument: 8-bit
+ * frames go to felics_compress_batch_device_indexed, which keeps refusing 16-bit ones) that also WRITES THE VERSION-2 INDEX of every
+ * stream, from what the encoder has in device memory anyway.  The streams are byte for byte felics_compress_batch_device's, placed as
+ * that call places them (fixed slots, or back to back after a slot overflow); offsets / lens as there.
+ * The indexes follow each other in stream order: index i at d_index + idx_offsets[i], idx_lens[i] bytes, idx_offsets[i] a multiple of 64
+ * (d_index 64-byte aligned, else FELICS_E_INVALID_ARGUMENT), each byte for byte what felics_index16_build makes of stream i with the
+ * same segment_pixels.  idx_offsets / idx_lens are HOST arrays, exactly what felics_decompress_batch_device_indexed16 takes.
+ * The size of an index depends on the content (felics_index16_size_max is a bound far above it), so *idx_total (may be NULL) receives
+ * the bytes all indexes need, and a d_index_cap below that is FELICS_E_BUFFER_TOO_SMALL: the streams, offsets and lens are then complete
+ * and valid as after felics_compress_batch_device, idx_offsets / idx_lens / *idx_total say what is needed, the indexes whose end lies
+ * inside d_index_cap are written and nothing is written behind d_index_cap; call again with *idx_total bytes.  (An error of the stream
+ * part -- FELICS_E_BUFFER_TOO_SMALL for d_out among them, lens[0] = the bytes needed -- comes back as from felics_compress_batch_device,
+ * with *idx_total = 0.)
+ * Before anything is launched: FELICS_E_INVALID_ARGUMENT for a bad segment_pixels, a misaligned or NULL d_index, NULL arrays with
+ * n > 0; refused while a ticket is outstanding; FELICS_E_UNSUPPORTED for an image whose per-checkpoint workspace (a bit per context
+ * and checkpoint and the bits' prefix counts: 16 KB per gray checkpoint, 32 KB per RGB plane's) does not fit a quarter of the free
+ * device memory.  That workspace also bounds the images of a pass; FELICS_TEST_PASS_IMAGES applies as in the unindexed call.
+ * An empty image gets the 64-byte header alone (K = 0).
+ * NOT HERE: views, mixed shapes and a queued form of this call; host-buffer entry points; cfelics / dfelics --index for 16-bit files. */
+int felics_compress_batch_device_indexed_wide(felics_ctx *ctx, size_t n, const void *d_pixels, uint32_t w, uint32_t h, int color, void *d_out,
+                                              size_t d_out_cap, uint32_t segment_pixels, void *d_index, size_t d_index_cap, uint64_t *offsets,
+                                              uint64_t *lens, uint64_t *idx_offsets, uint64_t *idx_lens, uint64_t *idx_total);
+
+/* What a context's felics_compress_batch_device_indexed16 calls wrote so far (cumulative; calls that returned FELICS_OK or
+ * FELICS_E_BUFFER_TOO_SMALL for the index buffer). */
+typedef struct felics_index16_emit_stats {
+    uint64_t streams;       /* streams of those calls */
+    uint64_t rows_written;  /* state rows of the indexes written: the sum of their directories' n_rows */
+    uint64_t index_bytes;   /* bytes of the indexes written */
+    uint64_t passes;        /* passes that wrote an index (a batch that is redone counts its last run) */
+} felics_index16_emit_stats;
+/* Writes min(out_size, sizeof(felics_index16_emit_stats)) bytes, never more. */
+int felics_get_index_wide_emit_stats(const felics_ctx *ctx, felics_index16_emit_stats *out, size_t out_size);
+
+/* The same under the names with "16" (see NAMES above): aliases, not symbols. */
+static inline int felics_compress_batch_device_indexed16(felics_ctx *ctx, size_t n, const void *d_pixels, uint32_t w, uint32_t h, int color,
+                                                         void *d_out, size_t d_out_cap, uint32_t segment_pixels, void *d_index,
+                                                         size_t d_index_cap, uint64_t *offsets, uint64_t *lens, uint64_t *idx_offsets,
+                                                         uint64_t *idx_lens, uint64_t *idx_total) {
+    return felics_compress_batch_device_indexed_wide(ctx, n, d_pixels, w, h, color, d_out, d_out_cap, segment_pixels, d_index, d_index_cap, offsets,
+                                                     lens, idx_offsets, idx_lens, idx_total);
+}
+static inline int felics_get_index16_emit_stats(const felics_ctx *ctx, felics_index16_emit_stats *out, size_t out_size) {
+    return felics_get_index_wide_emit_stats(ctx, out, out_size);
+}
+/* ... and the five above. */
 static inline size_t felics_index16_size_max(uint32_t w, uint32_t h, int color, uint32_t segment_pixels) {
     return felics_index_wide_size_max(w, h, color, segment_pixels);
 }
