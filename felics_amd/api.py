@@ -129,6 +129,11 @@ class _CRegionStats(C.Structure):  # felics_region_stats
     _fields_ = [("regions", C.c_uint64), ("segments_walked", C.c_uint64), ("segments_skipped", C.c_uint64), ("pixels_walked", C.c_uint64)]
 
 
+class _CRegion16Stats(C.Structure):  # felics_region16_stats
+    _fields_ = [("regions", C.c_uint64), ("segments_walked", C.c_uint64), ("segments_skipped", C.c_uint64), ("pixels_walked", C.c_uint64),
+                ("rows_loaded", C.c_uint64), ("passes", C.c_uint64)]
+
+
 INDEX_GRANULE = 4096  # FELICS_INDEX_GRANULE
 E_INVALID_INDEX = -12
 
@@ -171,6 +176,7 @@ EXPORTS = [
     "felics_index_wide_size_max", "felics_index_wide_build", "felics_decompress_indexed_wide", "felics_decompress_batch_device_indexed_wide",
     "felics_get_index_wide_stats",
     "felics_compress_batch_device_indexed_wide", "felics_get_index_wide_emit_stats",
+    "felics_decompress_region_indexed_wide", "felics_decompress_regions_device_indexed_wide", "felics_get_region_wide_stats",
 ]
 
 _lib = None
@@ -288,6 +294,12 @@ def lib():
         L.felics_compress_batch_device_indexed_wide.argtypes = [vp, sz, vp, C.c_uint32, C.c_uint32, C.c_int, vp, sz, C.c_uint32, vp, sz, u64, u64,
                                                                u64, u64, u64]
         L.felics_get_index_wide_emit_stats.argtypes = [vp, C.POINTER(_CIndex16EmitStats), sz]
+    if hasattr(L, "felics_decompress_regions_device_indexed_wide"):  # (as above: an older build has no regions of 16-bit streams)
+        u64 = C.POINTER(C.c_uint64)
+        L.felics_decompress_region_indexed_wide.argtypes = [vp, sz, vp, sz, C.POINTER(_CRegion), vp, sz, C.POINTER(_CHeader)]
+        L.felics_decompress_regions_device_indexed_wide.argtypes = [vp, sz, vp, u64, u64, vp, u64, u64, sz, C.POINTER(_CRegion), vp, sz, u64,
+                                                                   C.POINTER(_CHeader), C.POINTER(C.c_int)]
+        L.felics_get_region_wide_stats.argtypes = [vp, C.POINTER(_CRegion16Stats), sz]
     L.felics_strerror.argtypes = [C.c_int]
     L.felics_strerror.restype = C.c_char_p
     L.felics_last_error.argtypes = [vp]
@@ -905,6 +917,43 @@ class Encoder:
             self._raise(rc)
         return {k: int(getattr(st, k)) for k, _ in _CRegionStats._fields_}
 
+    def decompress_regions_device_indexed16(self, d_streams, offsets, lens, d_index, idx_offsets, idx_lens, regions, d_pixels, d_pixels_cap):
+        """felics_decompress_regions_device_indexed_wide: windows of 16-bit streams of one shape through their version-2 restart indexes
+        (index i at d_index + idx_offsets[i], a multiple of 64; idx_lens[i] bytes), everything in device memory (raw pointers).
+        regions: (stream, x, y, w, h) each; crop r is dense uint16 at d_pixels + out_offsets[r] (bytes).  Only the segments that hold a
+        pixel of a region are walked, a wave each.  Returns (Header, status array, out_offsets); raises like
+        decompress_regions_device_indexed (the error carries .status, one per region)."""
+        u64 = C.POINTER(C.c_uint64)
+        offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+        lens = np.ascontiguousarray(lens, dtype=np.uint64)
+        idx_offsets = np.ascontiguousarray(idx_offsets, dtype=np.uint64)
+        idx_lens = np.ascontiguousarray(idx_lens, dtype=np.uint64)
+        n = len(offsets)
+        if len(lens) != n or len(idx_offsets) != n or len(idx_lens) != n:
+            raise ValueError("a length and an index per stream")
+        regs = (_CRegion * max(len(regions), 1))(*[_CRegion(*(int(v) for v in r)) for r in regions])
+        status = np.zeros(len(regions), dtype=np.int32)
+        out_offsets = np.zeros(len(regions), dtype=np.uint64)
+        ch = _CHeader()
+        rc = lib().felics_decompress_regions_device_indexed_wide(
+            self._h, n, d_streams, offsets.ctypes.data_as(u64), lens.ctypes.data_as(u64), d_index, idx_offsets.ctypes.data_as(u64),
+            idx_lens.ctypes.data_as(u64), len(regions), regs, d_pixels, d_pixels_cap, out_offsets.ctypes.data_as(u64), C.byref(ch),
+            status.ctypes.data_as(C.POINTER(C.c_int)))
+        if rc != 0:
+            err = DecompressionError(rc) if rc in DecompressionError.KINDS else FelicsError(rc, lib().felics_last_error(self._h).decode() if rc == -9 else "")
+            err.status = status
+            raise err
+        return Header(ch.color_type, ch.pixel_depth, ch.width, ch.height), status, out_offsets
+
+    def region16_stats(self):
+        """felics_get_region_wide_stats: regions handed to decompress_regions_device_indexed16, the segments walked for them, the
+        segments of their frames that were not, the pixels those walks cover, the state rows loaded and the passes; cumulative."""
+        st = _CRegion16Stats()
+        rc = lib().felics_get_region_wide_stats(self._h, C.byref(st), C.sizeof(st))
+        if rc != 0:
+            self._raise(rc)
+        return {k: int(getattr(st, k)) for k, _ in _CRegion16Stats._fields_}
+
     def read_headers_device(self, d_streams, offsets, lens):
         """felics_read_headers_device: the headers of streams in device memory (raw pointer), read on the GPU.
         Returns (list of Header, or None where the header is invalid; status array of felics_read_header codes)."""
@@ -1324,6 +1373,24 @@ def decompress_region_indexed(data, index, x, y, w, h):
     out = np.zeros((h, w, 3) if ch.color_type else (h, w), dtype=np.uint8)
     rc = lib().felics_decompress_region_indexed(arr.ctypes.data, len(arr), idx.ctypes.data if len(idx) else None, len(idx), C.byref(reg),
                                                 out.ctypes.data if out.size else None, out.nbytes, None)
+    if rc != 0:
+        raise DecompressionError(rc) if rc in DecompressionError.KINDS else FelicsError(rc)
+    return out
+
+
+def decompress_region_indexed16(data, index, x, y, w, h):
+    """felics_decompress_region_indexed_wide: the w x h window at (x, y) of a 16-bit stream's image (uint16 ndarray, h x w or
+    h x w x 3), decoded from the checkpoints of the segments that hold its pixels and from nothing else."""
+    arr = np.frombuffer(bytes(data), dtype=np.uint8)
+    idx = np.frombuffer(bytes(index), dtype=np.uint8)
+    ch = _CHeader()
+    rc = lib().felics_read_header(arr.ctypes.data if len(arr) else None, len(arr), C.byref(ch))
+    if rc != 0:
+        raise DecompressionError(rc)
+    reg = _CRegion(0, x, y, w, h)
+    out = np.zeros((h, w, 3) if ch.color_type else (h, w), dtype=np.uint16)
+    rc = lib().felics_decompress_region_indexed_wide(arr.ctypes.data, len(arr), idx.ctypes.data if len(idx) else None, len(idx), C.byref(reg),
+                                                     out.ctypes.data if out.size else None, out.nbytes, None)
     if rc != 0:
         raise DecompressionError(rc) if rc in DecompressionError.KINDS else FelicsError(rc)
     return out

@@ -716,6 +716,49 @@ int indexed_index_shape(felics_ctx *ctx, const felics_header &hdr, uint64_t len0
     return FELICS_OK;
 }
 
+// ---- what the two indexed calls for 16-bit streams (felics_decompress_batch_device_indexed16, felics_decompress_regions_device_indexed16)
+// open with ----
+// d_index and every idx_offsets[i] a multiple of 64: the kernels load a state row as one aligned 64-byte line
+bool index16_aligned(const void *d_index, const uint64_t *idx_offsets, size_t n) {
+    if ((uintptr_t)d_index & 63u) return false;
+    for (size_t i = 0; i < n; i++)
+        if (idx_offsets[i] & 63u) return false;
+    return true;
+}
+
+// The shape every stream must have (header of stream 0: 16-bit, w * h < 2^32, a row the kernels' LDS holds), then own(hdr) -- the
+// checks of the call's own output, made before the index is looked at --, then how every index is cut (header of index 0: L, seg),
+// which must fit stream 0 and its own length.  (One index header, as the 8-bit calls read one; the streams' own headers are the
+// kernels' to check.)  FELICS_OK, or the code the call puts into every status and returns; FELICS_E_HIP leaves status alone.
+template <typename Own>
+int indexed16_open(felics_ctx *ctx, const void *d_streams, const uint64_t *offsets, const uint64_t *lens, const void *d_index,
+                   const uint64_t *idx_offsets, const uint64_t *idx_lens, felics_header &hdr, felics_header *hdr_out, Index16Layout &L, uint32_t &seg,
+                   Own own) {
+    uint8_t h0[FELICS_HEADER_BYTES] = {0};
+    const size_t hl = (size_t)std::min<uint64_t>(lens[0], FELICS_HEADER_BYTES);
+    if (hl) HIP_TRY(ctx, hipMemcpy(h0, (const uint8_t *)d_streams + offsets[0], hl, hipMemcpyDeviceToHost));
+    int rc = felics_read_header(h0, hl, &hdr);
+    if (rc) return rc;
+    if (hdr_out) *hdr_out = hdr;
+    if (hdr.pixel_depth != FELICS_DEPTH_16) return FELICS_E_UNSUPPORTED;  // 8-bit streams: the calls without "16"
+    if ((uint64_t)hdr.width * hdr.height > 0xFFFFFFFFull) return FELICS_E_INVALID_DIMENSIONS;
+    if (decode16_lds_bytes(hdr.width) > DECODE_LDS_LIMIT) return FELICS_E_UNSUPPORTED;  // no host fallback here
+    if ((rc = own(hdr)) != 0) return rc;
+    if (idx_lens[0] < INDEX_HEADER_BYTES) return FELICS_E_INVALID_INDEX;
+    uint8_t ih[INDEX_HEADER_BYTES];
+    HIP_TRY(ctx, hipMemcpy(ih, (const uint8_t *)d_index + idx_offsets[0], INDEX_HEADER_BYTES, hipMemcpyDeviceToHost));
+    if (index16_header_check(ih, hdr.color_type, hdr.width, hdr.height, lens[0], idx_lens[0], L) != FELICS_OK) return FELICS_E_INVALID_INDEX;
+    seg = idx_rd32(ih + IDX_SEGPIX);
+    return FELICS_OK;
+}
+
+// FELICS_TEST_INDEX16_PASS=k: at most k waves in a pass of those two calls (tests)
+uint64_t index16_pass_cap(uint64_t items) {
+    if (const char *e = getenv("FELICS_TEST_INDEX16_PASS"))
+        if (atoll(e) > 0) return std::min<uint64_t>(items, (uint64_t)atoll(e));
+    return items;
+}
+
 // FELICS_TEST_INDEX_VIEWS_PASS=<bytes>: at most that many bytes of RGB planes in a pass of felics_decompress_views_device_indexed (tests)
 uint64_t index_views_pass_cap() {
     const char *e = getenv("FELICS_TEST_INDEX_VIEWS_PASS");
@@ -1205,47 +1248,29 @@ int felics_decompress_batch_device_indexed_wide(felics_ctx *ctx, size_t n, const
     if (ctx->failed) return FELICS_E_HIP;
     if (n == 0) return FELICS_OK;
     if (any_pending(ctx)) return FELICS_E_INVALID_ARGUMENT;  // felics_wait_batch first
-    if ((uintptr_t)d_index & 63u) return FELICS_E_INVALID_ARGUMENT;  // the kernel loads a state row as one aligned 64-byte line
-    for (size_t i = 0; i < n; i++)
-        if (idx_offsets[i] & 63u) return FELICS_E_INVALID_ARGUMENT;
+    if (!index16_aligned(d_index, idx_offsets, n)) return FELICS_E_INVALID_ARGUMENT;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     auto fail_all = [&](int code) {
         for (size_t i = 0; i < n; i++) status[i] = code;
         return code;
     };
-    // the shape every stream must have: header of stream 0, which must be 16-bit with w * h < 2^32
-    uint8_t h0[FELICS_HEADER_BYTES] = {0};
-    const size_t hl = (size_t)std::min<uint64_t>(lens[0], FELICS_HEADER_BYTES);
-    if (hl) HIP_TRY(ctx, hipMemcpy(h0, (const uint8_t *)d_streams + offsets[0], hl, hipMemcpyDeviceToHost));
+    // the opening checks; between the two headers this call's own: the frames must fit
     felics_header hdr;
-    int rc = felics_read_header(h0, hl, &hdr);
-    if (rc) return fail_all(rc);
-    if (hdr_out) *hdr_out = hdr;
-    if (hdr.pixel_depth != FELICS_DEPTH_16) return fail_all(FELICS_E_UNSUPPORTED);  // 8-bit streams: felics_decompress_batch_device_indexed
-    if ((uint64_t)hdr.width * hdr.height > 0xFFFFFFFFull) return fail_all(FELICS_E_INVALID_DIMENSIONS);
-    if (decode16_lds_bytes(hdr.width) > DECODE_LDS_LIMIT) return fail_all(FELICS_E_UNSUPPORTED);  // no host fallback here
+    Index16Layout L;
+    uint32_t seg = 0;
+    int rc = indexed16_open(ctx, d_streams, offsets, lens, d_index, idx_offsets, idx_lens, hdr, hdr_out, L, seg, [&](const felics_header &h) {
+        const uint64_t bytes = (uint64_t)h.width * h.height * (h.color_type == FELICS_COLOR_RGB ? 3 : 1) * 2;
+        if (bytes * n > d_pixels_cap) return (int)FELICS_E_BUFFER_TOO_SMALL;
+        return bytes && !d_pixels ? (int)FELICS_E_INVALID_ARGUMENT : (int)FELICS_OK;
+    });
+    if (rc) return rc == FELICS_E_HIP ? rc : fail_all(rc);
     const uint32_t planes = hdr.color_type == FELICS_COLOR_RGB ? 3 : 1;
     const uint64_t npix = (uint64_t)hdr.width * hdr.height;
-    const uint64_t frame_bytes = npix * planes * 2;
-    if (frame_bytes * n > d_pixels_cap) return fail_all(FELICS_E_BUFFER_TOO_SMALL);
-    if (frame_bytes && !d_pixels) return fail_all(FELICS_E_INVALID_ARGUMENT);
-    // how every index is cut: header of index 0 (segment_pixels, K), which must fit stream 0 and its own length.  (One header, as the
-    // 8-bit call reads one; the streams' own headers are the kernel's to check.)
-    if (idx_lens[0] < INDEX_HEADER_BYTES) return fail_all(FELICS_E_INVALID_INDEX);
-    uint8_t ih[INDEX_HEADER_BYTES];
-    HIP_TRY(ctx, hipMemcpy(ih, (const uint8_t *)d_index + idx_offsets[0], INDEX_HEADER_BYTES, hipMemcpyDeviceToHost));
-    Index16Layout L;
-    if (index16_header_check(ih, hdr.color_type, hdr.width, hdr.height, lens[0], idx_lens[0], L) != FELICS_OK) return fail_all(FELICS_E_INVALID_INDEX);
-    const uint32_t seg = idx_rd32(ih + IDX_SEGPIX);
     const uint64_t per = (uint64_t)planes * std::max(L.K, 1u);
     if (n > 0x7FFFFFFFull / per) return fail_all(FELICS_E_UNSUPPORTED);  // a status word per segment, 32-bit item numbers
     const uint64_t items = n * per;
-    // FELICS_TEST_INDEX16_PASS=k: at most k waves in a pass (tests)
-    uint64_t want = items;
-    if (const char *e = getenv("FELICS_TEST_INDEX16_PASS"))
-        if (atoll(e) > 0) want = std::min<uint64_t>(want, (uint64_t)atoll(e));
     size_t pass = 0;
-    if ((rc = dec16_tables(ctx, (size_t)want, pass)) != 0) return fail_all(rc);
+    if ((rc = dec16_tables(ctx, (size_t)index16_pass_cap(items), pass)) != 0) return fail_all(rc);
     // offsets | lens | index offsets | index lens | the rows-loaded counter | status on the device; a word per segment beside them
     if ((rc = reserve(ctx, ctx->dec_meta, n * 8 * 4 + 8 + n * 4)) != 0) return fail_all(rc);
     if ((rc = reserve(ctx, ctx->dec_seg_status, (size_t)items * 4)) != 0) return fail_all(rc);
@@ -1400,6 +1425,141 @@ int felics_decompress_regions_device_indexed(felics_ctx *ctx, size_t n_streams, 
                                         d_planes, (int *)ctx->dec_seg_status.p, d_status));
     HIP_TRY(ctx, hipMemcpyAsync(status, d_status, n_regions * 4, hipMemcpyDeviceToHost, s));
     HIP_TRY(ctx, hipStreamSynchronize(s));  // (rows and items live until here)
+    for (size_t i = 0; i < n_regions; i++)
+        if (status[i]) return status[i];
+    return FELICS_OK;
+}
+
+int felics_get_region_wide_stats(const felics_ctx *ctx, felics_region16_stats *out, size_t out_size) {
+    if (!ctx || !out) return FELICS_E_INVALID_ARGUMENT;
+    memcpy(out, &ctx->r16stats, std::min(out_size, sizeof(felics_region16_stats)));
+    return FELICS_OK;
+}
+
+int felics_decompress_regions_device_indexed_wide(felics_ctx *ctx, size_t n_streams, const void *d_streams, const uint64_t *offsets,
+                                                  const uint64_t *lens, const void *d_index, const uint64_t *idx_offsets,
+                                                  const uint64_t *idx_lens, size_t n_regions, const felics_region *regions, void *d_pixels,
+                                                  size_t d_pixels_cap, uint64_t *out_offsets, felics_header *hdr_out, int *status) {
+    if (!ctx || (n_streams && (!d_streams || !offsets || !lens || !d_index || !idx_offsets || !idx_lens)) || (n_regions && (!regions || !status)))
+        return FELICS_E_INVALID_ARGUMENT;
+    if (ctx->failed) return FELICS_E_HIP;
+    if (n_regions == 0) return FELICS_OK;
+    auto fail_all = [&](int code) {
+        for (size_t i = 0; i < n_regions; i++) status[i] = code;
+        return code;
+    };
+    if (any_pending(ctx)) return fail_all(FELICS_E_INVALID_ARGUMENT);  // felics_wait_batch first
+    if (n_streams == 0 || n_streams > 0xFFFFFFFFull || n_regions > 0x7FFFFFFFull) return fail_all(FELICS_E_INVALID_ARGUMENT);
+    if (!index16_aligned(d_index, idx_offsets, n_streams) || ((uintptr_t)d_pixels & 1u)) return fail_all(FELICS_E_INVALID_ARGUMENT);
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    // the opening checks; between the two headers this call's own: the requests inside the image, of a stream of the call; the crops,
+    // back to back, must fit
+    felics_header hdr;
+    Index16Layout L;
+    uint32_t seg = 0;
+    int rc = indexed16_open(ctx, d_streams, offsets, lens, d_index, idx_offsets, idx_lens, hdr, hdr_out, L, seg, [&](const felics_header &h) {
+        for (size_t r = 0; r < n_regions; r++)
+            if (regions[r].stream >= n_streams || !region_inside(h.width, h.height, regions[r])) return (int)FELICS_E_INVALID_ARGUMENT;
+        const uint64_t sample_bytes = h.color_type == FELICS_COLOR_RGB ? 6 : 2;
+        uint64_t total = 0;
+        for (size_t r = 0; r < n_regions; r++) {
+            total += (uint64_t)regions[r].w * regions[r].h * sample_bytes;  // (a crop has < 6 * 2^32 bytes: the sum is looked at before it can wrap)
+            if (total > d_pixels_cap) return (int)FELICS_E_BUFFER_TOO_SMALL;
+        }
+        return total && !d_pixels ? (int)FELICS_E_INVALID_ARGUMENT : (int)FELICS_OK;
+    });
+    if (rc) return rc == FELICS_E_HIP ? rc : fail_all(rc);
+    const uint32_t W = hdr.width, H = hdr.height, planes = hdr.color_type == FELICS_COLOR_RGB ? 3 : 1;
+    const uint64_t npix = (uint64_t)W * H;
+    // the plan: a region's items are contiguous, in (plane, segment) order; an empty region has the header-only item
+    std::vector<RegionRow> rows;
+    std::vector<RegionItem> items;
+    std::vector<uint32_t> segs;
+    uint64_t walked = 0, pixels_walked = 0, max_crop = 0, plane_at = 0, out_at = 0;
+    try {
+        rows.reserve(n_regions);
+        for (size_t r = 0; r < n_regions; r++) {
+            const felics_region &g = regions[r];
+            segs.clear();
+            if (!region_empty(g)) {
+                uint32_t first, last;
+                region_span(W, seg, g, first, last);
+                for (uint32_t j = first; j <= last; j++)
+                    if (region_needs(W, npix, seg, g, j)) segs.push_back(j);
+            }
+            const uint64_t cnt = segs.empty() ? 1 : (uint64_t)planes * segs.size();
+            if (items.size() + cnt > 0x7FFFFFFFull) return fail_all(FELICS_E_UNSUPPORTED);  // one block per item, 32-bit item numbers
+            const uint64_t cpix = (uint64_t)g.w * g.h;
+            rows.push_back(RegionRow{g.stream, g.x, g.y, g.w, g.h, (uint32_t)items.size(), (uint32_t)cnt, 0, out_at, plane_at});
+            if (out_offsets) out_offsets[r] = out_at;
+            out_at += cpix * planes * 2;  // bytes
+            if (planes == 3) {
+                plane_at += cpix * 3;     // int32 samples
+                max_crop = std::max(max_crop, cpix);
+            }
+            if (segs.empty()) items.push_back(RegionItem{(uint32_t)r, 0, REGION_HEADER_ONLY});
+            for (uint32_t c = 0; c < planes && !segs.empty(); c++)
+                for (const uint32_t j : segs) items.push_back(RegionItem{(uint32_t)r, c, j});
+            const uint64_t stop_at = region_empty(g) ? 0 : region_last(W, g);
+            for (const uint32_t j : segs) {
+                const uint64_t p0 = (uint64_t)j * seg;
+                pixels_walked += (std::min({npix, p0 + seg, stop_at}) - p0) * planes;
+            }
+            walked += (uint64_t)planes * segs.size();
+        }
+    } catch (const std::bad_alloc &) {
+        return fail_all(FELICS_E_IO);
+    }
+    const size_t n_items = items.size();
+    // the items in passes of at most `pass` waves: a wave owns a table of the pass; a pass boundary may fall inside a region
+    size_t pass = 0;
+    if ((rc = dec16_tables(ctx, (size_t)index16_pass_cap(n_items), pass)) != 0) return fail_all(rc);
+    // offsets | lens | index offsets | index lens | the rows-loaded counter | status on the device; the region table and the work list;
+    // a word per item
+    if ((rc = reserve(ctx, ctx->dec_meta, n_streams * 8 * 4 + 8 + n_regions * 4)) != 0) return fail_all(rc);
+    if ((rc = reserve(ctx, ctx->dec_region_work, n_regions * sizeof(RegionRow) + n_items * sizeof(RegionItem))) != 0) return fail_all(rc);
+    if ((rc = reserve(ctx, ctx->dec_seg_status, n_items * 4)) != 0) return fail_all(rc);
+    int32_t *d_planes = nullptr;
+    if (planes == 3) {  // crop-sized: 3 * w * h int32 per region
+        if ((rc = reserve(ctx, ctx->dec_planes, (size_t)(plane_at * 4) + 64)) != 0) return fail_all(rc);
+        d_planes = (int32_t *)ctx->dec_planes.p;
+    }
+    uint64_t *d_off = (uint64_t *)ctx->dec_meta.p, *d_len = d_off + n_streams, *d_ioff = d_len + n_streams, *d_ilen = d_ioff + n_streams;
+    unsigned long long *d_loaded = (unsigned long long *)(d_ilen + n_streams);
+    int *d_status = (int *)(d_loaded + 1);
+    int *item_status = (int *)ctx->dec_seg_status.p;
+    RegionRow *d_rows = (RegionRow *)ctx->dec_region_work.p;
+    RegionItem *d_items = (RegionItem *)(d_rows + n_regions);
+    felics_region16_stats &rs = ctx->r16stats;
+    rs.regions += n_regions;
+    rs.segments_walked += walked;
+    rs.segments_skipped += (uint64_t)n_regions * planes * L.K - walked;
+    rs.pixels_walked += pixels_walked;
+    hipStream_t s = ctx->lanes[0].stream;
+    for (size_t i = 0; i < n_regions; i++) status[i] = FELICS_E_HIP;  // until the kernel's own word arrives
+    HIP_TRY(ctx, hipMemcpyAsync(d_off, offsets, n_streams * 8, hipMemcpyHostToDevice, s));
+    HIP_TRY(ctx, hipMemcpyAsync(d_len, lens, n_streams * 8, hipMemcpyHostToDevice, s));
+    HIP_TRY(ctx, hipMemcpyAsync(d_ioff, idx_offsets, n_streams * 8, hipMemcpyHostToDevice, s));
+    HIP_TRY(ctx, hipMemcpyAsync(d_ilen, idx_lens, n_streams * 8, hipMemcpyHostToDevice, s));
+    HIP_TRY(ctx, hipMemcpyAsync(d_rows, rows.data(), n_regions * sizeof(RegionRow), hipMemcpyHostToDevice, s));
+    HIP_TRY(ctx, hipMemcpyAsync(d_items, items.data(), n_items * sizeof(RegionItem), hipMemcpyHostToDevice, s));
+    HIP_TRY(ctx, hipMemsetAsync(d_loaded, 0, 8, s));
+    HIP_TRY(ctx, hipMemsetAsync(d_status, 0xFF, n_regions * 4, s));
+    HIP_TRY(ctx, hipMemsetAsync(item_status, 0xFF, n_items * 4, s));
+    for (size_t i0 = 0; i0 < n_items; i0 += pass) {  // behind one another on the one stream: the passes share the tables
+        uint32_t epoch = 0;
+        if ((rc = dec16_epoch(ctx, s, epoch)) != 0) return rc;
+        HIP_TRY(ctx, launch_decode16_regions(s, (const uint8_t *)d_streams, d_off, d_len, (const uint8_t *)d_index, d_ioff, d_ilen, W, H, hdr.color_type,
+                                             seg, L.K, d_rows, d_items, (uint32_t)i0, (uint32_t)std::min(pass, n_items - i0), (uint8_t *)d_pixels,
+                                             d_planes, (uint32_t *)ctx->dec_table.p, epoch, item_status, d_loaded));
+        rs.passes++;
+    }
+    HIP_TRY(ctx, launch_regions16_finish(s, d_rows, (uint32_t)n_regions, max_crop, (uint8_t *)d_pixels, d_planes, item_status, d_status));
+    unsigned long long loaded = 0;
+    HIP_TRY(ctx, hipMemcpyAsync(status, d_status, n_regions * 4, hipMemcpyDeviceToHost, s));
+    HIP_TRY(ctx, hipMemcpyAsync(&loaded, d_loaded, 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(ctx, hipStreamSynchronize(s));  // (rows and items live until here)
+    rs.rows_loaded += loaded;
     for (size_t i = 0; i < n_regions; i++)
         if (status[i]) return status[i];
     return FELICS_OK;

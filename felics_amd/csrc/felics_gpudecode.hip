@@ -1175,7 +1175,7 @@ __device__ __forceinline__ bool conv_view(const DecMixed &g, const P *planes, T 
     return r.color != 0;
 }
 
-// ConvRegion (felics_decompress_regions_device_indexed): row base + blockIdx.y of a RegionRow table -- crop-sized planes, the crop
+// ConvRegion (felics_decompress_regions_device_indexed and its 16-bit form): row base + blockIdx.y of a RegionRow table -- crop-sized planes, the crop
 // dense at its out_off; status is per region.
 struct ConvRegion {
     const RegionRow *rows;
@@ -1476,11 +1476,12 @@ namespace {
 
 // Segment (c, j) of stream s / index idx (idx_len bytes, 64-byte aligned), decoded by the calling wave into `sink`; `smem` is the
 // kernel's dynamic LDS (decode16_lds_bytes(W)), `table` the wave's own dense estimator table (DEC16_CONTEXTS rows; rows of another
-// epoch read as zeros).  Returns the segment's status, wave-uniform; *loaded = the state rows it copied.
+// epoch read as zeros).  Returns the segment's status, wave-uniform; *loaded = the state rows it copied.  header_only: the checks of
+// the two headers and nothing else (c and j are not looked at, no table row is touched).
 template <typename Sink>
 __device__ __forceinline__ int decode16_from_checkpoint(uint8_t *smem, const uint8_t *s, uint64_t slen, const uint8_t *idx, uint64_t idx_len,
                                                         const DecUniform &geo, uint32_t segment_pixels, uint32_t K, uint32_t c, uint32_t j,
-                                                        uint32_t *table, uint32_t epoch, const Sink &sink, uint32_t *loaded) {
+                                                        bool header_only, uint32_t *table, uint32_t epoch, const Sink &sink, uint32_t *loaded) {
     const uint32_t W = geo.W, H = geo.H, color = geo.color;
     uint32_t *crow = reinterpret_cast<uint32_t *>(smem);  // [DEC16_SLOTS][DEC16_ROW] cached rows
     uint32_t *ctag = crow + DEC16_SLOTS * DEC16_ROW;      // [DEC16_SLOTS] context held (or ~0)
@@ -1507,10 +1508,10 @@ __device__ __forceinline__ int decode16_from_checkpoint(uint8_t *smem, const uin
         else if (idx_len < INDEX_HEADER_BYTES || index16_header_check(idx, color, W, H, slen, idx_len, L) != FELICS_OK ||
                  idx_rd32(idx + IDX_SEGPIX) != segment_pixels || L.K != K)
             rc = FELICS_E_INVALID_INDEX;
-        else rc = index16_segment_bounds(idx, L, c, j, slen, idx_len, start, end, rows_off, n_rows);
+        else if (!header_only) rc = index16_segment_bounds(idx, L, c, j, slen, idx_len, start, end, rows_off, n_rows);
     }
     rc = unii(rc);
-    if (rc != FELICS_OK) return rc;
+    if (rc != FELICS_OK || header_only) return rc;
     start = ((uint64_t)uni((uint32_t)(start >> 32)) << 32) | uni((uint32_t)start);
     end = ((uint64_t)uni((uint32_t)(end >> 32)) << 32) | uni((uint32_t)end);
     rows_off = ((uint64_t)uni((uint32_t)(rows_off >> 32)) << 32) | uni((uint32_t)rows_off);
@@ -1714,9 +1715,61 @@ __global__ __launch_bounds__(64) void k_decode16_seg(const uint8_t *__restrict__
     uint32_t *table = gtable + (uint64_t)blockIdx.x * DEC16_CONTEXTS * DEC16_ROW;
     uint32_t loaded = 0;
     const int rc = decode16_from_checkpoint(smem, streams + offsets[img], lens[img], index + idx_offsets[img], idx_lens[img], geo, segment_pixels, K,
-                                            c, j, table, epoch, sink, &loaded);
+                                            c, j, false, table, epoch, sink, &loaded);
     if (lane_id() == 0) {
         seg_status[item] = rc;
+        if (loaded) atomicAdd(rows_loaded, (unsigned long long)loaded);
+    }
+}
+
+namespace {
+
+// The segment's part of a region into the region's dense crop (u16 gray, or plane c of the crop-sized int32 planes): RegionSink for
+// 16-bit samples.  The walk ends behind the region's last pixel; a sample is written only if its (column, row) lies inside the
+// region -- column in [x, x + w), row in [y, y + h) (row < y + h holds for every at < stop) -- to (row - y) * w + (column - x), an
+// offset below w * h.  reg and W are wave-uniform (scalar loads of the kernel); the store's predicate is the only divergence, once
+// per 64-sample block.
+struct Region16Sink {
+    RegionRow reg;  // (inside the image, both sides non-zero: the host's checks)
+    uint32_t W;
+    uint16_t *outg;
+    int32_t *outp;
+    __device__ __forceinline__ uint64_t stop(uint64_t pend) const { return min(pend, (uint64_t)(reg.y + reg.h - 1) * W + reg.x + reg.w); }
+    __device__ __forceinline__ void store(uint32_t col, uint32_t y, uint64_t, int v) const {
+        if (col >= reg.x && col - reg.x < reg.w && y >= reg.y && y - reg.y < reg.h) {
+            const uint64_t to = (uint64_t)(y - reg.y) * reg.w + (col - reg.x);
+            if (outg) outg[to] = (uint16_t)v;
+            else outp[to] = v;
+        }
+    }
+};
+
+}  // namespace
+
+// One wave per WORK ITEM = (region, plane, needed segment) of felics_decompress_regions_device_indexed16 (felics.h "Restart index:
+// regions of 16-bit streams"; host model: felics_decompress_region_indexed16), a pass of consecutive items at a time: block b is item
+// item0 + b and owns table b of the pass's tables, exactly as in k_decode16_seg.  The host names needed segments only (j < K,
+// p0 < stop); an item with seg = REGION_HEADER_ONLY ends after the header checks.  item_status[item] = FELICS_OK or the code;
+// k_seg_status picks a region's first.  Gray crops lie at pixels + out_off (bytes, even), RGB planes at planes + plane_off.
+__global__ __launch_bounds__(64) void k_decode16_region(const uint8_t *__restrict__ streams, const uint64_t *__restrict__ offsets,
+                                                        const uint64_t *__restrict__ lens, const uint8_t *__restrict__ index,
+                                                        const uint64_t *__restrict__ idx_offsets, const uint64_t *__restrict__ idx_lens,
+                                                        DecUniform geo, uint32_t segment_pixels, uint32_t K, const RegionRow *__restrict__ regions,
+                                                        const RegionItem *__restrict__ items, uint32_t item0, uint8_t *__restrict__ pixels,
+                                                        int32_t *__restrict__ planes, uint32_t *__restrict__ gtable, uint32_t epoch,
+                                                        int *__restrict__ item_status, unsigned long long *__restrict__ rows_loaded) {
+    extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
+    const RegionItem item = items[item0 + blockIdx.x];
+    const RegionRow reg = regions[item.region];
+    const uint32_t img = reg.stream, c = item.plane;
+    const Region16Sink sink{reg, geo.W, geo.color ? nullptr : reinterpret_cast<uint16_t *>(pixels + reg.out_off),
+                            geo.color ? planes + reg.plane_off + (uint64_t)c * reg.w * reg.h : nullptr};
+    uint32_t *table = gtable + (uint64_t)blockIdx.x * DEC16_CONTEXTS * DEC16_ROW;
+    uint32_t loaded = 0;
+    const int rc = decode16_from_checkpoint(smem, streams + offsets[img], lens[img], index + idx_offsets[img], idx_lens[img], geo, segment_pixels, K,
+                                            c, item.seg, item.seg == REGION_HEADER_ONLY, table, epoch, sink, &loaded);
+    if (lane_id() == 0) {
+        item_status[item0 + blockIdx.x] = rc;
         if (loaded) atomicAdd(rows_loaded, (unsigned long long)loaded);
     }
 }
@@ -2249,6 +2302,40 @@ hipError_t launch_seg16_finish(hipStream_t s, uint32_t n, uint32_t W, uint32_t H
     if (color)
         for (uint32_t i0 = 0; i0 < n; i0 += 65535u)  // (the conversion takes the stream from blockIdx.y)
             launch_conv_uniform(s, std::min(n - i0, 65535u), W, H, planes + (uint64_t)i0 * 3u * W * H, pixels + (uint64_t)i0 * 3u * W * H, status + i0);
+    return hipGetLastError();
+}
+
+// ------------------------------------------------------------------------------------------
+// felics_decompress_regions_device_indexed16: a pass of k_decode16_region; the call's tail.
+// ------------------------------------------------------------------------------------------
+
+hipError_t launch_decode16_regions(hipStream_t s, const uint8_t *streams, const uint64_t *offsets, const uint64_t *lens, const uint8_t *index,
+                                   const uint64_t *idx_offsets, const uint64_t *idx_lens, uint32_t W, uint32_t H, uint32_t color,
+                                   uint32_t segment_pixels, uint32_t K, const RegionRow *rows, const RegionItem *items, uint32_t item0, uint32_t nitems,
+                                   uint8_t *pixels, int32_t *planes, uint32_t *table, uint32_t epoch, int *item_status,
+                                   unsigned long long *rows_loaded) {
+    if (nitems == 0) return hipSuccess;
+    const uint32_t lds = decode16_lds_bytes(W);
+    if (lds > 64u * 1024u) {
+        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&k_decode16_region), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                                 (int)DECODE_LDS_LIMIT);
+        if (e != hipSuccess) return e;
+    }
+    hipLaunchKernelGGL(k_decode16_region, dim3(nitems), dim3(64), lds, s, streams, offsets, lens, index, idx_offsets, idx_lens,
+                       DecUniform{W, H, color}, segment_pixels, K, rows, items, item0, pixels, planes, table, epoch, item_status, rows_loaded);
+    return hipGetLastError();
+}
+
+hipError_t launch_regions16_finish(hipStream_t s, const RegionRow *rows, uint32_t nregions, uint64_t max_crop, uint8_t *pixels, int32_t *planes,
+                                   const int *item_status, int *status) {
+    if (nregions == 0) return hipSuccess;
+    hipLaunchKernelGGL(k_seg_status, dim3(nregions), dim3(64), 0, s, item_status, rows, 0u, status);
+    // the crops differ in size: one launch (per 65 535 regions) sized by the largest, a region's blocks stride over its own w * h
+    const uint32_t bx = (uint32_t)std::min<uint64_t>((max_crop + 255) / 256, 1024u);
+    if (bx)
+        for (uint32_t r0 = 0; r0 < nregions; r0 += 65535u)
+            hipLaunchKernelGGL(k_ycocg16_to_rgb<ConvRegion>, dim3(bx, std::min(nregions - r0, 65535u)), dim3(256), 0, s, planes,
+                               reinterpret_cast<uint16_t *>(pixels), ConvRegion{rows, r0}, status);
     return hipGetLastError();
 }
 

@@ -223,6 +223,10 @@ struct felics_ctx {
     // are dec_seg_status, the crop-sized planes dec_planes); the counts of felics_get_region_stats
     DevBuf dec_region_work;
     felics_region_stats rstats = {};
+    // felics_decompress_regions_device_indexed16: the same buffers (dec_region_work, dec_seg_status, crop-sized int32 planes in
+    // dec_planes), the tables and epochs of felics_decompress_batch_device_indexed16 (dec_table, dec_epoch); the counts of
+    // felics_get_region16_stats
+    felics_region16_stats r16stats = {};
     // felics_decompress_views_device_indexed: its tables live in the buffers above (offsets | lens | index offsets | index lens | the
     // two kinds of headers in dec_meta; rows, items and the finish tables in dec_region_work; item and row status words in
     // dec_seg_status; a pass's planes in dec_planes); view_ready is its ready event; the counts of felics_get_index_view_stats

@@ -418,6 +418,20 @@ hipError_t launch_decode16_seg(hipStream_t s, const uint8_t *streams, const uint
                                int *seg_status, unsigned long long *rows_loaded);
 hipError_t launch_seg16_finish(hipStream_t s, uint32_t n, uint32_t W, uint32_t H, uint32_t color, uint32_t K, uint16_t *pixels, int32_t *planes,
                                const int *seg_status, int *status);
+// Regions of such streams (felics_decompress_regions_device_indexed16, felics.h "Restart index: regions of 16-bit streams"):
+// k_decode16_region, one wave per work item = (region, plane, needed segment) -- k_decode16_seg's walk with the region sink.  The
+// tables are launch_decode8_regions' (RegionRow, RegionItem, REGION_HEADER_ONLY), with out_off in bytes (even) and plane_off in
+// int32 samples of crop-sized planes.  A launch is a PASS: items item0 .. item0 + nitems - 1 of `items`, wave b on table b of `table`
+// (launch_decode16_seg's buffer and epoch rule); item_status: a word per item of the call; *rows_loaded += the state rows copied.
+// launch_regions16_finish is the call's tail, once behind the last pass: status[r] = region r's first failing item (k_seg_status over
+// the rows' items), then the conversion of the clean RGB crops; max_crop: the largest w * h of an RGB region (0: gray).
+hipError_t launch_decode16_regions(hipStream_t s, const uint8_t *streams, const uint64_t *offsets, const uint64_t *lens, const uint8_t *index,
+                                   const uint64_t *idx_offsets, const uint64_t *idx_lens, uint32_t W, uint32_t H, uint32_t color,
+                                   uint32_t segment_pixels, uint32_t K, const RegionRow *rows, const RegionItem *items, uint32_t item0, uint32_t nitems,
+                                   uint8_t *pixels, int32_t *planes, uint32_t *table, uint32_t epoch, int *item_status,
+                                   unsigned long long *rows_loaded);
+hipError_t launch_regions16_finish(hipStream_t s, const RegionRow *rows, uint32_t nregions, uint64_t max_crop, uint8_t *pixels, int32_t *planes,
+                                   const int *item_status, int *status);
 // The same for 16-bit streams, gray or RGB (k_decode16_lanes): 64 streams per wave, lane = stream; needs W >= 8 and a table of
 // decode16_lanes_table_bytes(n, W, H, color) bytes = n * planes * dec16l_rows(W * H, planes) * 64 (felics_lanetable.h: sized by the
 // pixel count, 512 KB per plane of a 64 x 64 stream, the wave form's 8.4 MB from 32 771 pixels on), zero-initialised ONCE: rows carry

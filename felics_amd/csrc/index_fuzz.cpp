@@ -14,8 +14,9 @@
 //     felics_decompress's and every other byte of the hull untouched; on a mutated or foreign pair any code, no crash.
 // `index_fuzz --index16 DIR` runs the 16-bit index's two host functions instead (felics_index16.cpp): felics_index16_build at the same
 // two segment sizes; where it succeeds the size is within felics_index16_size_max, the two-call pattern holds,
-// felics_decompress_indexed16 gives felics_decompress's pixels, and the index goes through byte mutations (header, directory, rows'
-// context words, anywhere) and cuts; NAME.idx beside NAME is used as it is: any code, no crash.
+// felics_decompress_indexed16 gives felics_decompress's pixels, felics_decompress_region_indexed16 gives the full frame, a seeded
+// interior window and an empty one, and the index goes through byte mutations (header, directory, rows' context words, anywhere)
+// and cuts, each with the same three windows; NAME.idx beside NAME is used as it is: any code, no crash.
 // Built with -fsanitize=address,undefined by `make asan`; tests/test_index_cpu.py and tests/test_index16_cpu.py feed it mutated corpora.
 // Exit code 0 = every input was handled without a sanitizer report and every accepted pair decoded to the right pixels.
 #include <dirent.h>
@@ -77,6 +78,37 @@ static int fuzz16(const char *dir) {
         rng ^= rng << 17;
         return rng;
     };
+    // felics_decompress_region_indexed16 on a pair, for three windows of the header's shape -- the full frame, a seeded interior
+    // window, an empty one --, each into a crop of exactly its size (a store behind it is the sanitizer's to report).  `good`: every
+    // call must succeed, the full-frame crop must be px's frame (the caller has felics_decompress_indexed16's output there) and the interior one
+    // ref's window (ref holds h's image).
+    std::vector<uint8_t> crop;
+    auto regions16_on = [&](const uint8_t *index_bytes, size_t index_len, const felics_header &h, bool good) {
+        const size_t planes = h.color_type ? 3 : 1;
+        felics_region inner = {0, 0, 0, 0, 0};
+        if (h.width && h.height) {
+            inner.x = (uint32_t)(next() % h.width);
+            inner.y = (uint32_t)(next() % h.height);
+            inner.w = (uint32_t)(1 + next() % std::min<uint64_t>(h.width - inner.x, 96));
+            inner.h = (uint32_t)(1 + next() % std::min<uint64_t>(h.height - inner.y, 48));
+        }
+        const felics_region wins[3] = {{0, 0, 0, h.width, h.height}, inner, {0, h.width / 2, h.height / 2, 0, h.height ? 1u : 0u}};
+        for (int k = 0; k < 3; k++) {
+            const felics_region &r = wins[k];
+            const size_t bytes = (size_t)r.w * r.h * planes * 2;
+            if (bytes > cap) continue;  // (crops are this driver's to allocate)
+            crop.assign(bytes, 0xA5);
+            felics_header hr;
+            const int rc = felics_decompress_region_indexed16(buf.data(), buf.size(), index_bytes, index_len, &r, crop.data(), bytes, &hr);
+            if (!good) continue;
+            if (rc != FELICS_OK) return false;
+            if (k == 0 && memcmp(crop.data(), px.data(), bytes) != 0) return false;  // (px: felics_decompress_indexed16's frame)
+            for (uint32_t yy = 0; k == 1 && yy < r.h; yy++)
+                if (memcmp(&crop[(size_t)yy * r.w * planes * 2], &ref[((size_t)(r.y + yy) * h.width + r.x) * planes * 2], (size_t)r.w * planes * 2) != 0)
+                    return false;
+        }
+        return true;
+    };
     for (const std::string &n : names) {
         const std::string path = std::string(dir) + "/" + n;
         if (!slurp(path, buf)) continue;
@@ -114,6 +146,10 @@ static int fuzz16(const char *dir) {
                 fprintf(stderr, "%s: indexed decode %d, or other pixels than felics_decompress\n", n.c_str(), rc);
                 return 1;
             }
+            if (!regions16_on(index.data(), ilen, h, true)) {
+                fprintf(stderr, "%s: a region of a good pair failed or differs from felics_decompress_indexed16's window\n", n.c_str());
+                return 1;
+            }
             const std::vector<uint8_t> idx(index.begin(), index.begin() + ilen);
             const size_t entries = (size_t)(h.color_type ? 3 : 1) * (((size_t)h.width * h.height + seg - 1) / seg);
             const int rounds = ilen > (1u << 20) ? 4 : 10;  // (a call clears a table of 7.9 MB: fewer rounds than the 8-bit mode's)
@@ -131,6 +167,7 @@ static int fuzz16(const char *dir) {
                 }
                 mutations++;
                 if (felics_decompress_indexed16(buf.data(), buf.size(), bad.data(), bad.size(), px.data(), px.size(), &h2) == FELICS_OK) mut_accepted++;
+                regions16_on(bad.data(), bad.size(), h, false);
                 if (m % 5 == 0) {  // and cut short
                     const size_t cut = (size_t)(next() % ilen);
                     if (felics_decompress_indexed16(buf.data(), buf.size(), bad.data(), cut, px.data(), px.size(), &h2) == FELICS_OK) {

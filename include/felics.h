@@ -700,8 +700,9 @@ int felics_get_index_emit_stats(const felics_ctx *ctx, felics_index_emit_stats *
  * WHAT THE CHECKS DO NOT PROVE: as above, and COUNTERS ARE NOT JUDGED: a forged counter gives a wrong Rice parameter in a segment
  * whose end check then fails (or whose pixels are wrong, as with an index of another stream); no address depends on a counter.
  * The encoder writes this index beside the streams of a blocking same-shape batch: felics_compress_batch_device_indexed16 below.
- * NOT HERE: the encoder's index for views, mixed shapes, queued and host-buffer calls; regions, views and mixed shapes in the decoder,
- * a lane form, a queued form; a hashed table for small segments; cfelics / dfelics flags (--index keeps refusing 16-bit images).
+ * NOT HERE: the encoder's index for views, mixed shapes, queued and host-buffer calls; views and mixed shapes in the decoder, a lane
+ * form, a queued form; a hashed table for small segments; cfelics / dfelics flags (--index keeps refusing 16-bit images).  (Regions
+ * are built: "Restart index: regions of 16-bit streams", below.)
  * NAMES: the library's symbols hold no digit, like every other symbol of this ABI (its symbol check reads names as letters and
  * underscores), so the five functions are exported as felics_index_wide_size_max, felics_index_wide_build,
  * felics_decompress_indexed_wide, felics_decompress_batch_device_indexed_wide and felics_get_index_wide_stats ("wide" as in the 16-bit
@@ -818,6 +819,75 @@ static inline int felics_decompress_batch_device_indexed16(felics_ctx *ctx, size
 }
 static inline int felics_get_index16_stats(const felics_ctx *ctx, felics_index16_stats *out, size_t out_size) {
     return felics_get_index_wide_stats(ctx, out, out_size);
+}
+
+/* ---- Restart index: regions of 16-bit streams ----
+ * "Restart index: regions" for version-2 indexes: a window of a 16-bit stream decoded from the checkpoints of the segments that hold
+ * its pixels and from nothing else.  The planner is felics_region_segments (its arithmetic knows no depth).  The 8-bit region calls
+ * keep refusing 16-bit streams; these refuse 8-bit ones (FELICS_E_UNSUPPORTED).
+ * NAMES: exported as felics_decompress_region_indexed_wide, felics_decompress_regions_device_indexed_wide and
+ * felics_get_region_wide_stats; the aliases felics_decompress_region_indexed16, felics_decompress_regions_device_indexed16 and
+ * felics_get_region16_stats follow the declarations.
+ * NOT HERE: regions into views, mixed shapes, a lane form, a queued form; dfelics --region for 16-bit files. */
+
+/* Host only: the w x h window *r of a 16-bit stream through its version-2 index, as dense uint16 samples (w * h * C of them;
+ * pixels_cap in bytes).  The host model of k_decode16_region: every needed segment, in (plane, segment) order, from its checkpoint
+ * alone -- the table is exactly the checkpoint's rows, nothing is carried from one segment to the next -- with the checks of
+ * "Restart index: 16-bit streams" in that section's order: the stream header, the index header (for an empty region too), then per
+ * needed segment its directory entry, its state rows, its window samples, the two raw samples (j = 0), the walk up to
+ * min(segment end, the pixel behind the region's last one), every decoded sample in range, and the end check where the walk reaches
+ * the segment's end.  The first failure is the code.  FELICS_E_UNSUPPORTED for an 8-bit stream, FELICS_E_INVALID_ARGUMENT for a
+ * region outside the image, FELICS_E_BUFFER_TOO_SMALL for 2 * w * h * C > pixels_cap.  r->stream is ignored. */
+int felics_decompress_region_indexed_wide(const uint8_t *in, size_t len, const uint8_t *index, size_t index_len, const felics_region *r,
+                                          void *pixels, size_t pixels_cap, felics_header *hdr);
+
+/* GPU: felics_decompress_regions_device_indexed for 16-bit streams.  Streams, indexes and their alignment rules are
+ * felics_decompress_batch_device_indexed_wide's (one shape, colour, segment_pixels and K; stream 0's header names the shape, index
+ * 0's header the cut; d_index and every idx_offsets[i] multiples of 64); regions, crops, out_offsets (bytes, optional) and status
+ * (n_regions words) are felics_decompress_regions_device_indexed's, the crops dense uint16 back to back in request order.  One wave
+ * per (region, plane, needed segment): k_decode16_region, the walk of k_decode16_seg with a sink that stops behind the region's last
+ * pixel and stores the samples inside the window.  status[r] is the code of region r's first failing item in (plane, segment) order,
+ * after the header checks, which are made for empty regions too; a failing region leaves only its own crop undefined; an RGB crop
+ * with a failing item is not converted.
+ * Before anything is launched: FELICS_E_INVALID_ARGUMENT for a region outside the image, a stream number >= n_streams, a misaligned
+ * index or a d_pixels that is not 2-byte aligned; FELICS_E_BUFFER_TOO_SMALL if the crops do not fit d_pixels_cap;
+ * FELICS_E_UNSUPPORTED in every status for 8-bit streams and for rows too wide for the kernel's LDS (no host fallback); refused while
+ * a ticket is outstanding.  Blocking; creates no HIP stream.
+ * Every wave of a pass owns a dense estimator table as in felics_decompress_batch_device_indexed_wide, so the items run in passes
+ * bounded the same way (FELICS_TEST_INDEX16_PASS applies); a pass boundary may fall inside a region.  RGB crops go through crop-sized
+ * int32 planes (12 bytes per crop pixel), not frame-sized ones. */
+int felics_decompress_regions_device_indexed_wide(felics_ctx *ctx, size_t n_streams, const void *d_streams, const uint64_t *offsets,
+                                                  const uint64_t *lens, const void *d_index, const uint64_t *idx_offsets,
+                                                  const uint64_t *idx_lens, size_t n_regions, const felics_region *regions, void *d_pixels,
+                                                  size_t d_pixels_cap, uint64_t *out_offsets /* optional */, felics_header *hdr, int *status);
+
+/* What a context's felics_decompress_regions_device_indexed16 calls did so far (cumulative; calls that passed the checks made before
+ * a launch).  felics_region_stats and felics_index16_stats do not count these calls. */
+typedef struct felics_region16_stats {
+    uint64_t regions;           /* regions handed in */
+    uint64_t segments_walked;   /* waves that walked a segment: C per needed segment */
+    uint64_t segments_skipped;  /* C * K per region minus the walked */
+    uint64_t pixels_walked;     /* pixels those walks cover */
+    uint64_t rows_loaded;       /* state rows copied into tables */
+    uint64_t passes;            /* launches of k_decode16_region */
+} felics_region16_stats;
+/* Writes min(out_size, sizeof(felics_region16_stats)) bytes, never more. */
+int felics_get_region_wide_stats(const felics_ctx *ctx, felics_region16_stats *out, size_t out_size);
+
+static inline int felics_decompress_region_indexed16(const uint8_t *in, size_t len, const uint8_t *index, size_t index_len,
+                                                     const felics_region *r, void *pixels, size_t pixels_cap, felics_header *hdr) {
+    return felics_decompress_region_indexed_wide(in, len, index, index_len, r, pixels, pixels_cap, hdr);
+}
+static inline int felics_decompress_regions_device_indexed16(felics_ctx *ctx, size_t n_streams, const void *d_streams, const uint64_t *offsets,
+                                                             const uint64_t *lens, const void *d_index, const uint64_t *idx_offsets,
+                                                             const uint64_t *idx_lens, size_t n_regions, const felics_region *regions,
+                                                             void *d_pixels, size_t d_pixels_cap, uint64_t *out_offsets, felics_header *hdr,
+                                                             int *status) {
+    return felics_decompress_regions_device_indexed_wide(ctx, n_streams, d_streams, offsets, lens, d_index, idx_offsets, idx_lens, n_regions, regions,
+                                                         d_pixels, d_pixels_cap, out_offsets, hdr, status);
+}
+static inline int felics_get_region16_stats(const felics_ctx *ctx, felics_region16_stats *out, size_t out_size) {
+    return felics_get_region_wide_stats(ctx, out, out_size);
 }
 
 /* Text for a code above; for FELICS_E_HIP felics_last_error(ctx) has the HIP message. */
