@@ -113,6 +113,11 @@ class _CIndex16Stats(C.Structure):  # felics_index16_stats
                 ("table_bytes", C.c_uint64)]
 
 
+class _CIndex16ViewStats(C.Structure):  # felics_index16_view_stats
+    _fields_ = [("streams", C.c_uint64), ("undecoded", C.c_uint64), ("items", C.c_uint64), ("launches", C.c_uint64), ("passes", C.c_uint64),
+                ("rows_loaded", C.c_uint64), ("plane_bytes", C.c_uint64), ("table_bytes", C.c_uint64)]
+
+
 class _CIndex16EmitStats(C.Structure):  # felics_index16_emit_stats
     _fields_ = [("streams", C.c_uint64), ("rows_written", C.c_uint64), ("index_bytes", C.c_uint64), ("passes", C.c_uint64)]
 
@@ -177,6 +182,7 @@ EXPORTS = [
     "felics_get_index_wide_stats",
     "felics_compress_batch_device_indexed_wide", "felics_get_index_wide_emit_stats",
     "felics_decompress_region_indexed_wide", "felics_decompress_regions_device_indexed_wide", "felics_get_region_wide_stats",
+    "felics_decompress_views_device_indexed_wide", "felics_decompress_indexed_view_wide", "felics_get_index_view_wide_stats",
 ]
 
 _lib = None
@@ -300,6 +306,12 @@ def lib():
         L.felics_decompress_regions_device_indexed_wide.argtypes = [vp, sz, vp, u64, u64, vp, u64, u64, sz, C.POINTER(_CRegion), vp, sz, u64,
                                                                    C.POINTER(_CHeader), C.POINTER(C.c_int)]
         L.felics_get_region_wide_stats.argtypes = [vp, C.POINTER(_CRegion16Stats), sz]
+    if hasattr(L, "felics_decompress_views_device_indexed_wide"):
+        u64 = C.POINTER(C.c_uint64)
+        L.felics_decompress_views_device_indexed_wide.argtypes = [vp, sz, vp, u64, u64, vp, u64, u64, C.POINTER(_CView), vp, C.POINTER(_CHeader),
+                                                                  C.POINTER(C.c_int)]
+        L.felics_decompress_indexed_view_wide.argtypes = [vp, sz, vp, sz, C.POINTER(_CView), C.POINTER(_CHeader)]
+        L.felics_get_index_view_wide_stats.argtypes = [vp, C.POINTER(_CIndex16ViewStats), sz]
     L.felics_strerror.argtypes = [C.c_int]
     L.felics_strerror.restype = C.c_char_p
     L.felics_last_error.argtypes = [vp]
@@ -1037,6 +1049,11 @@ class Encoder:
         ready_event as for decompress_views_device.  Returns (list of Header -- zeros where a header is invalid --, status array); a
         refused view or index address raises FelicsError, a failing stream DecompressionError or FelicsError (a 16-bit stream, a bad
         index) with .status and .headers."""
+        return self._views_indexed(lib().felics_decompress_views_device_indexed, d_streams, offsets, lens, d_index, idx_offsets, idx_lens, views,
+                                   ready_event)
+
+    def _views_indexed(self, call, d_streams, offsets, lens, d_index, idx_offsets, idx_lens, views, ready_event):
+        """what decompress_views_device_indexed and decompress_views_device_indexed16 share: the arrays, the call, the errors"""
         offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
         lens = np.ascontiguousarray(lens, dtype=np.uint64)
         idx_offsets = np.ascontiguousarray(idx_offsets, dtype=np.uint64)
@@ -1048,7 +1065,7 @@ class Encoder:
         status = np.zeros(max(n, 1), dtype=np.int32)
         hdrs = (_CHeader * max(n, 1))()
         u64 = C.POINTER(C.c_uint64)
-        rc = lib().felics_decompress_views_device_indexed(
+        rc = call(
             self._h, n, d_streams, offsets.ctypes.data_as(u64), lens.ctypes.data_as(u64), d_index, idx_offsets.ctypes.data_as(u64),
             idx_lens.ctypes.data_as(u64), cv, int(ready_event) if ready_event else None, hdrs, status.ctypes.data_as(C.POINTER(C.c_int)))
         headers = [Header(h.color_type, h.pixel_depth, h.width, h.height) for h in hdrs[:n]]  # (zeros where the header is invalid)
@@ -1063,6 +1080,30 @@ class Encoder:
         images of an N x C x H x W tensor (t[i].permute(1, 2, 0)), rgba[..., :3], the cells of a mosaic."""
         return self.decompress_views_device_indexed(d_streams, offsets, lens, d_index, idx_offsets, idx_lens, [view_of_array(a) for a in arrays],
                                                     ready_event)
+
+    def decompress_views_device_indexed16(self, d_streams, offsets, lens, d_index, idx_offsets, idx_lens, views, ready_event=None):
+        """felics_decompress_views_device_indexed16: decompress_views_device_indexed for 16-bit streams, each with its version-2 index at
+        d_index + idx_offsets[i] (a multiple of 64; idx_lens[i] bytes), into views of depth 16 (even addresses and strides); gray is one
+        2-byte store per sample through any strides, nothing staged.  Returns and raises as decompress_views_device_indexed (an 8-bit
+        stream is FelicsError -10)."""
+        return self._views_indexed(lib().felics_decompress_views_device_indexed_wide, d_streams, offsets, lens, d_index, idx_offsets, idx_lens,
+                                   views, ready_event)
+
+    def decompress_arrays_device_indexed16(self, d_streams, offsets, lens, d_index, idx_offsets, idx_lens, arrays, ready_event=None):
+        """decompress_views_device_indexed16 into uint16 objects with __cuda_array_interface__ (view_of_array), as
+        decompress_arrays_device_indexed."""
+        return self.decompress_views_device_indexed16(d_streams, offsets, lens, d_index, idx_offsets, idx_lens, [view_of_array(a) for a in arrays],
+                                                      ready_event)
+
+    def index16_view_stats(self):
+        """felics_get_index16_view_stats: streams handed to decompress_views_device_indexed16, those that got a code before a wave was
+        launched for them, the waves (items), kernel launches, stream passes and state rows loaded; cumulative -- and plane_bytes (the
+        RGB scratch of the last call's largest pass) and table_bytes (the last call's estimator tables)."""
+        st = _CIndex16ViewStats()
+        rc = lib().felics_get_index_view_wide_stats(self._h, C.byref(st), C.sizeof(st))
+        if rc != 0:
+            self._raise(rc)
+        return {k: int(getattr(st, k)) for k, _ in _CIndex16ViewStats._fields_}
 
     def index_view_stats(self):
         """felics_get_index_view_stats: streams handed to decompress_views_device_indexed, those that got a code before a wave was
@@ -1325,6 +1366,16 @@ def decompress_indexed_view(data, index, array):
     """felics_decompress_indexed_view: an 8-bit stream decoded through its restart index INTO `array`, a writable numpy array of shape
     (H, W) or (H, W, 3) and any admissible strides (a slice of a pitched buffer, buf[::-1], rgba[..., :3], chw.transpose(1, 2, 0), a
     mosaic cell): only the array's own samples are written.  The host model of Encoder.decompress_views_device_indexed."""
+    return _indexed_view(lib().felics_decompress_indexed_view, data, index, array)
+
+
+def decompress_indexed16_view(data, index, array):
+    """felics_decompress_indexed16_view: decompress_indexed_view for a 16-bit stream and its version-2 index, into a uint16 array.  The
+    host model of Encoder.decompress_views_device_indexed16."""
+    return _indexed_view(lib().felics_decompress_indexed_view_wide, data, index, array)
+
+
+def _indexed_view(call, data, index, array):
     if not isinstance(array, np.ndarray) or array.dtype not in (np.uint8, np.uint16) or array.ndim not in (2, 3) or (array.ndim == 3 and array.shape[2] != 3):
         raise TypeError("Unsupported image format")
     if not array.flags.writeable:
@@ -1335,8 +1386,7 @@ def decompress_indexed_view(data, index, array):
     rgb = array.ndim == 3
     view = _CView(array.ctypes.data if array.size else None, w, h, int(rgb), int(array.dtype == np.uint16), array.strides[0], array.strides[1],
                   array.strides[2] if rgb else 0)
-    rc = lib().felics_decompress_indexed_view(arr.ctypes.data if len(arr) else None, len(arr), idx.ctypes.data if len(idx) else None, len(idx),
-                                              C.byref(view), None)
+    rc = call(arr.ctypes.data if len(arr) else None, len(arr), idx.ctypes.data if len(idx) else None, len(idx), C.byref(view), None)
     if rc != 0:
         raise DecompressionError(rc) if rc in DecompressionError.KINDS else FelicsError(rc)
     return array

@@ -765,21 +765,116 @@ uint64_t index_views_pass_cap() {
     return e && atoll(e) > 0 ? (uint64_t)atoll(e) : UINT64_MAX;
 }
 
-// felics_decompress_views_device_indexed after the checks that need no device (felics.h "Restart index: views and mixed shapes"):
+// What the two indexed views calls differ in: a form names the sample depth it takes, the LDS a row asks for, the check of an index
+// header, the type of an RGB plane sample, and how a launch of one LDS class, a stream pass's tail and the call's counters are made.
+// Everything else -- the header round trip, the classification, the passes over the plane scratch, the tables, the status hand-back --
+// is decompress_views_indexed below.
+
+// felics_decompress_views_device_indexed: 8-bit streams, version-1 indexes, k_decode8_seg_views.  A launch holds any number of items
+// and needs nothing beside its tables.
+struct IndexViews8 {
+    using Layout = IndexLayout;
+    using Plane = int16_t;
+    using Stats = felics_index_view_stats;
+    static constexpr int DEPTH = FELICS_DEPTH_8;
+    static constexpr uintptr_t INDEX_ALIGN = 16;  // of every index address: the kernel loads a checkpoint as aligned words
+    static constexpr size_t EXTRA = 0;            // bytes behind the status words
+    static Stats &stats(felics_ctx *ctx) { return ctx->ivstats; }
+    static uint32_t lds_bytes(const DecodeHeader &h) { return decode8_lds_bytes(h.W, h.color); }
+    static bool lds_ok(const DecodeHeader &h) { return index_lds_bytes(h.W, h.color) <= DECODE_LDS_LIMIT; }
+    static bool index_ok(const uint8_t *ih, const DecodeHeader &h, uint64_t len, uint64_t idx_len, Layout &L) {
+        return index_header_check(ih, h.color, h.W, h.H, len, L) == FELICS_OK && L.total == idx_len;
+    }
+    int tables(felics_ctx *, size_t) { return FELICS_OK; }
+    size_t launches_of(size_t) const { return 1; }
+    int begin(felics_ctx *, hipStream_t, void *) { return FELICS_OK; }
+    int launch(felics_ctx *ctx, hipStream_t s, const uint8_t *st, const uint64_t *d_off, const uint64_t *d_len, const uint8_t *ix, const uint64_t *,
+               const IndexViewRow *d_rows, const IndexViewItem *d_items, size_t cnt, uint32_t lds, Plane *d_planes, int *d_item_status) {
+        HIP_TRY(ctx, launch_decode8_seg_views(s, st, d_off, d_len, ix, d_rows, d_items, (uint32_t)cnt, lds, d_planes, d_item_status));
+        return FELICS_OK;
+    }
+    static hipError_t finish(hipStream_t s, uint32_t n, const RegionRow *regions, const int *item_status, const DecodeRow *conv, const ViewRow *views,
+                             uint64_t max_npix, Plane *planes, int *status) {
+        return launch_seg_views_finish(s, n, regions, item_status, conv, views, max_npix, planes, status);
+    }
+    int end(felics_ctx *, hipStream_t) { return FELICS_OK; }
+    void done(felics_ctx *) {}
+};
+
+// felics_decompress_views_device_indexed16: 16-bit streams, version-2 indexes, k_decode16_seg_views.  Every wave of a launch owns a
+// dense estimator table in dec_table, so a launch holds at most `per` items (dec16_tables' bound, FELICS_TEST_INDEX16_PASS) and takes
+// a fresh epoch; a class's items are cut into such launches wherever the cut falls -- inside a stream, inside a plane: an item
+// needs its own table and nothing of its neighbours'.  Behind the status words lies the rows-loaded counter.
+struct IndexViews16 {
+    using Layout = Index16Layout;
+    using Plane = int32_t;
+    using Stats = felics_index16_view_stats;
+    static constexpr int DEPTH = FELICS_DEPTH_16;
+    static constexpr uintptr_t INDEX_ALIGN = 64;  // the kernel loads a state row as one aligned 64-byte line
+    static constexpr size_t EXTRA = 8;
+    size_t per = 1;
+    unsigned long long *d_loaded = nullptr, loaded = 0;
+    static Stats &stats(felics_ctx *ctx) { return ctx->iv16stats; }
+    static uint32_t lds_bytes(const DecodeHeader &h) { return decode16_lds_bytes(h.W); }
+    static bool lds_ok(const DecodeHeader &h) { return decode16_lds_bytes(h.W) <= DECODE_LDS_LIMIT; }
+    static bool index_ok(const uint8_t *ih, const DecodeHeader &h, uint64_t len, uint64_t idx_len, Layout &L) {
+        return index16_header_check(ih, h.color, h.W, h.H, len, idx_len, L) == FELICS_OK;  // (total_bytes = idx_len is one of its checks)
+    }
+    int tables(felics_ctx *ctx, size_t most_items) {  // most_items >= 1: the largest class of a pass
+        const int rc = dec16_tables(ctx, (size_t)index16_pass_cap(most_items), per);
+        if (!rc) stats(ctx).table_bytes = decode16_table_bytes((uint32_t)per);
+        return rc;
+    }
+    size_t launches_of(size_t cnt) const { return (cnt + per - 1) / per; }
+    int begin(felics_ctx *ctx, hipStream_t s, void *extra) {
+        d_loaded = (unsigned long long *)extra;
+        HIP_TRY(ctx, hipMemsetAsync(d_loaded, 0, 8, s));
+        return FELICS_OK;
+    }
+    int launch(felics_ctx *ctx, hipStream_t s, const uint8_t *st, const uint64_t *d_off, const uint64_t *d_len, const uint8_t *ix,
+               const uint64_t *d_ilen, const IndexViewRow *d_rows, const IndexViewItem *d_items, size_t cnt, uint32_t lds, Plane *d_planes,
+               int *d_item_status) {
+        for (size_t o = 0; o < cnt; o += per) {  // behind one another on the one stream: the launches share the tables
+            uint32_t epoch = 0;
+            const int rc = dec16_epoch(ctx, s, epoch);
+            if (rc) return rc;
+            HIP_TRY(ctx, launch_decode16_seg_views(s, st, d_off, d_len, ix, d_ilen, d_rows, d_items + o, (uint32_t)std::min(per, cnt - o), lds, d_planes,
+                                                   (uint32_t *)ctx->dec_table.p, epoch, d_item_status + o, d_loaded));
+        }
+        return FELICS_OK;
+    }
+    static hipError_t finish(hipStream_t s, uint32_t n, const RegionRow *regions, const int *item_status, const DecodeRow *conv, const ViewRow *views,
+                             uint64_t max_npix, Plane *planes, int *status) {
+        return launch_seg16_views_finish(s, n, regions, item_status, conv, views, max_npix, planes, status);
+    }
+    int end(felics_ctx *ctx, hipStream_t s) {
+        HIP_TRY(ctx, hipMemcpyAsync(&loaded, d_loaded, 8, hipMemcpyDeviceToHost, s));
+        return FELICS_OK;
+    }
+    void done(felics_ctx *ctx) { stats(ctx).rows_loaded += loaded; }
+};
+
+// felics_decompress_views_device_indexed and felics_decompress_views_device_indexed16 after the checks that need no device (felics.h
+// "Restart index: views and mixed shapes", "Restart index: 16-bit streams into views and mixed shapes"), `form` being what they
+// differ in:
 //   1. the ready event in front of the lane's stream, on which everything below runs;
 //   2. k_read_headers and k_read_index_headers, both records copied back, ONE synchronise;
-//   3. every stream classified on the host, in the order felics.h lists the codes (index_header_check with the stream's own header
-//      and length; the index's exact size);
+//   3. every stream classified on the host, in the order felics.h lists the codes (the form's index header check with the stream's own
+//      header and length; the index's exact size);
 //   4. the streams in passes of consecutive streams whose RGB planes fit the scratch; within a pass the rows in LDS classes as
-//      decompress_images cuts them for k_decode8, a class per launch, so a narrow stream does not pay a 4K row's LDS.  A row's items
-//      are contiguous in (plane, segment) order; rows, items and the finish tables go up on the lane's stream;
+//      decompress_images cuts them for k_decode8, a class per launch (the 16-bit form: per launches of as many items as it has
+//      tables), so a narrow stream does not pay a 4K row's LDS.  A row's items are contiguous in (plane, segment) order; rows, items
+//      and the finish tables go up on the lane's stream;
 //   5. per pass: the launches, k_seg_status over the pass's rows (a RegionRow per row names its items), the strided conversion of
-//      its clean RGB rows -- behind one another on the one stream, since the passes share the planes;
-//   6. one copy back of the rows' statuses.
+//      its clean RGB rows -- behind one another on the one stream, since the passes share the planes (and the launches the tables);
+//   6. one copy back of the rows' statuses (and of what the form counted).
+template <typename Form>
 int decompress_views_indexed(felics_ctx *ctx, size_t n, const void *d_streams, const uint64_t *offsets, const uint64_t *lens, const void *d_index,
-                             const uint64_t *idx_offsets, const uint64_t *idx_lens, const felics_view *views, felics_header *hdrs, int *status) {
+                             const uint64_t *idx_offsets, const uint64_t *idx_lens, const felics_view *views, felics_header *hdrs, int *status,
+                             Form form) {
+    using Plane = typename Form::Plane;
     hipStream_t s = ctx->lanes[0].stream;
-    felics_index_view_stats &vs = ctx->ivstats;
+    typename Form::Stats &vs = Form::stats(ctx);
     vs.streams += n;
     vs.plane_bytes = 0;
     auto fail_all = [&](int code) {
@@ -824,7 +919,7 @@ int decompress_views_indexed(felics_ctx *ctx, size_t n, const void *d_streams, c
     };
     if ((rc = headers()) != 0) return fail_all(rc);
     // the streams one by one: the first code of felics.h's list
-    std::vector<IndexLayout> lay;
+    std::vector<typename Form::Layout> lay;
     std::vector<uint32_t> segpix;
     try {
         lay.resize(n);
@@ -839,11 +934,10 @@ int decompress_views_indexed(felics_ctx *ctx, size_t n, const void *d_streams, c
         const felics_view &w = views[i];
         if (hdrs) hdrs[i] = h.status == FELICS_OK ? felics_header{h.color, h.depth, h.W, h.H} : felics_header{};
         int code = h.dstatus;
-        if (!code && h.depth != FELICS_DEPTH_8) code = FELICS_E_UNSUPPORTED;  // 16-bit streams have no index
-        if (!code && index_lds_bytes(h.W, h.color) > DECODE_LDS_LIMIT) code = FELICS_E_UNSUPPORTED;  // no host fallback here
+        if (!code && h.depth != Form::DEPTH) code = FELICS_E_UNSUPPORTED;  // the other depth has a format and a call of its own
+        if (!code && !Form::lds_ok(h)) code = FELICS_E_UNSUPPORTED;  // no host fallback here
         if (!code && ((int)h.color != w.color || (int)h.depth != w.depth || h.W != w.width || h.H != w.height)) code = FELICS_E_INVALID_DIMENSIONS;
-        if (!code && (idx_lens[i] < INDEX_HEADER_BYTES || index_header_check(ih + i * INDEX_HEADER_BYTES, h.color, h.W, h.H, lens[i], lay[i]) != FELICS_OK ||
-                      lay[i].total != idx_lens[i]))
+        if (!code && (idx_lens[i] < INDEX_HEADER_BYTES || !Form::index_ok(ih + i * INDEX_HEADER_BYTES, h, lens[i], idx_lens[i], lay[i])))
             code = FELICS_E_INVALID_INDEX;
         status[i] = code;
         if (code) continue;
@@ -852,8 +946,8 @@ int decompress_views_indexed(felics_ctx *ctx, size_t n, const void *d_streams, c
         nrows++;
     }
     if (total_items > 0x7FFFFFFFull) return fail_all(FELICS_E_UNSUPPORTED);  // one block per item, a word per item
-    // passes: consecutive streams whose planes (6 bytes per RGB pixel) fit the budget; a single larger stream is a pass of its own
-    auto plane_bytes_of = [&](size_t i) { return status[i] == FELICS_OK && rec[i].color ? 6ull * rec[i].W * rec[i].H : 0ull; };
+    // passes: consecutive streams whose planes (three Plane samples per RGB pixel) fit the budget; a single larger stream is a pass of its own
+    auto plane_bytes_of = [&](size_t i) { return status[i] == FELICS_OK && rec[i].color ? 3ull * sizeof(Plane) * rec[i].W * rec[i].H : 0ull; };
     uint64_t plane_total = 0;
     for (size_t i = 0; i < n; i++) plane_total += plane_bytes_of(i);
     uint64_t budget = UINT64_MAX;
@@ -901,7 +995,7 @@ int decompress_views_indexed(felics_ctx *ctx, size_t n, const void *d_streams, c
                 pass_end.push_back(i);
                 acc = 0;
             }
-            plane_off[i] = acc / 2;  // int16 elements
+            plane_off[i] = acc / sizeof(Plane);  // elements
             acc += b;
             most = std::max(most, acc);
         }
@@ -914,7 +1008,7 @@ int decompress_views_indexed(felics_ctx *ctx, size_t n, const void *d_streams, c
                 for (size_t i = i0; i < i1; i++) {
                     if (status[i] != FELICS_OK) continue;
                     const DecodeHeader &h = rec[i];
-                    const uint32_t lds = decode8_lds_bytes(h.W, h.color);
+                    const uint32_t lds = Form::lds_bytes(h);
                     if (lds > LDS_CLASS[c] || (c > 0 && lds <= LDS_CLASS[c - 1])) continue;
                     const felics_view &w = views[i];
                     const uint32_t K = lay[i].K, keff = std::max(K, 1u), cnt = lay[i].planes * keff;
@@ -940,13 +1034,19 @@ int decompress_views_indexed(felics_ctx *ctx, size_t n, const void *d_streams, c
     } catch (const std::bad_alloc &) {
         return fail_all(FELICS_E_IO);
     }
-    // device side: the tables in dec_region_work; a word per item and one per row in dec_seg_status
+    // device side: the tables in dec_region_work; a word per item and one per row in dec_seg_status, what the form keeps behind them;
+    // the form's own tables for the largest class of a pass
+    const size_t o_extra = al(n_items * 4) + al(nrows * 4);
+    size_t most_items = 0, n_launches = 0;
+    for (const Launch &L : launches) most_items = std::max(most_items, L.cnt);
     if (nrows && (rc = reserve(ctx, ctx->dec_region_work, o_end)) != 0) return fail_all(rc);
-    if (nrows && (rc = reserve(ctx, ctx->dec_seg_status, al(n_items * 4) + nrows * 4)) != 0) return fail_all(rc);
+    if (nrows && (rc = reserve(ctx, ctx->dec_seg_status, o_extra + Form::EXTRA)) != 0) return fail_all(rc);
     if (most && (rc = reserve(ctx, ctx->dec_planes, (size_t)most + 64)) != 0) return fail_all(rc);
+    if (nrows && (rc = form.tables(ctx, most_items)) != 0) return fail_all(rc);
+    for (const Launch &L : launches) n_launches += form.launches_of(L.cnt);
     for (size_t i = 0; i < n; i++) vs.undecoded += status[i] != FELICS_OK;
     vs.items += n_items;
-    vs.launches += launches.size();
+    vs.launches += n_launches;
     vs.passes += passes.size();
     vs.plane_bytes = most;
     int first = FELICS_OK;
@@ -958,21 +1058,26 @@ int decompress_views_indexed(felics_ctx *ctx, size_t n, const void *d_streams, c
         DecodeRow *d_conv = (DecodeRow *)(work + o_conv);
         ViewRow *d_cviews = (ViewRow *)(work + o_cviews);
         int *d_item_status = (int *)ctx->dec_seg_status.p, *d_row_status = (int *)((uint8_t *)ctx->dec_seg_status.p + al(n_items * 4));
-        int16_t *d_planes = (int16_t *)ctx->dec_planes.p;
+        Plane *d_planes = (Plane *)ctx->dec_planes.p;
         auto queue = [&]() -> int {
+            int r;
             HIP_TRY(ctx, hipMemcpyAsync(work, tables.data(), o_end, hipMemcpyHostToDevice, s));  // (the five tables in one copy)
             HIP_TRY(ctx, hipMemsetAsync(d_item_status, 0xFF, al(n_items * 4) + nrows * 4, s));
+            if ((r = form.begin(ctx, s, (uint8_t *)ctx->dec_seg_status.p + o_extra)) != 0) return r;
             for (const Pass &P : passes) {
                 for (size_t k = P.launch0; k < P.launch0 + P.launches; k++) {
                     const Launch &L = launches[k];
-                    HIP_TRY(ctx, launch_decode8_seg_views(s, st, d_off, d_len, ix, d_rows, d_items + L.item0, (uint32_t)L.cnt, L.lds, d_planes,
-                                                          d_item_status + L.item0));
+                    if ((r = form.launch(ctx, s, st, d_off, d_len, ix, d_ilen, d_rows, d_items + L.item0, L.cnt, L.lds, d_planes,
+                                         d_item_status + L.item0)) != 0)
+                        return r;
                 }
-                HIP_TRY(ctx, launch_seg_views_finish(s, (uint32_t)P.rows, d_regions + P.row0, d_item_status, d_conv + P.row0, d_cviews + P.row0,
-                                                     P.max_npix, d_planes, d_row_status + P.row0));
+                HIP_TRY(ctx, Form::finish(s, (uint32_t)P.rows, d_regions + P.row0, d_item_status, d_conv + P.row0, d_cviews + P.row0, P.max_npix,
+                                          d_planes, d_row_status + P.row0));
             }
             HIP_TRY(ctx, hipMemcpyAsync(row_status.data(), d_row_status, nrows * 4, hipMemcpyDeviceToHost, s));
+            if ((r = form.end(ctx, s)) != 0) return r;
             HIP_TRY(ctx, hipStreamSynchronize(s));  // (the host tables live until here)
+            form.done(ctx);
             return FELICS_OK;
         };
         if ((rc = queue()) != 0) {
@@ -984,6 +1089,31 @@ int decompress_views_indexed(felics_ctx *ctx, size_t n, const void *d_streams, c
     for (size_t i = 0; i < n; i++)
         if (status[i] && !first) first = status[i];
     return first;
+}
+
+// The two calls' entry: the checks that need no device, made before anything is launched, then decompress_views_indexed between the
+// setting and the clearing of the ready event.
+template <typename Form>
+int views_indexed_call(felics_ctx *ctx, size_t n, const void *d_streams, const uint64_t *offsets, const uint64_t *lens, const void *d_index,
+                       const uint64_t *idx_offsets, const uint64_t *idx_lens, const felics_view *views, void *ready_event, felics_header *hdrs,
+                       int *status, Form form) {
+    if (!ctx || (n && !status)) return FELICS_E_INVALID_ARGUMENT;
+    auto fail_all = [&](int code) { return fail_call(n, status, hdrs, nullptr, code); };
+    if (n && (!d_streams || !offsets || !lens || !d_index || !idx_offsets || !idx_lens || !views)) return fail_all(FELICS_E_INVALID_ARGUMENT);
+    for (size_t i = 0; i < n; i++) {  // every view and every index address before anything is launched: the first error in view order
+        const int rc = felics_view_writable(&views[i]);
+        if (rc) return fail_all(rc);
+        if (((uintptr_t)d_index + idx_offsets[i]) & (Form::INDEX_ALIGN - 1u)) return fail_all(FELICS_E_INVALID_ARGUMENT);
+    }
+    if (ctx->failed) return fail_all(FELICS_E_HIP);
+    if (n == 0) return FELICS_OK;
+    if (any_pending(ctx)) return fail_all(FELICS_E_INVALID_ARGUMENT);  // felics_wait_batch first
+    if (n > 0xFFFFFFFFull) return fail_all(FELICS_E_INVALID_ARGUMENT);
+    if (hipSetDevice(ctx->device) != hipSuccess) return fail_all(hip_fail(ctx, hipGetLastError(), "hipSetDevice"));
+    ctx->view_ready = (hipEvent_t)ready_event;
+    const int rc = decompress_views_indexed(ctx, n, d_streams, offsets, lens, d_index, idx_offsets, idx_lens, views, hdrs, status, form);
+    ctx->view_ready = nullptr;
+    return rc;
 }
 
 }  // namespace
@@ -1700,23 +1830,21 @@ int felics_get_index_view_stats(const felics_ctx *ctx, felics_index_view_stats *
 int felics_decompress_views_device_indexed(felics_ctx *ctx, size_t n, const void *d_streams, const uint64_t *offsets, const uint64_t *lens,
                                            const void *d_index, const uint64_t *idx_offsets, const uint64_t *idx_lens, const felics_view *views,
                                            void *ready_event, felics_header *hdrs, int *status) {
-    if (!ctx || (n && !status)) return FELICS_E_INVALID_ARGUMENT;
-    auto fail_all = [&](int code) { return fail_call(n, status, hdrs, nullptr, code); };
-    if (n && (!d_streams || !offsets || !lens || !d_index || !idx_offsets || !idx_lens || !views)) return fail_all(FELICS_E_INVALID_ARGUMENT);
-    for (size_t i = 0; i < n; i++) {  // every view and every index address before anything is launched: the first error in view order
-        const int rc = felics_view_writable(&views[i]);
-        if (rc) return fail_all(rc);
-        if (((uintptr_t)d_index + idx_offsets[i]) & 15u) return fail_all(FELICS_E_INVALID_ARGUMENT);  // the kernel loads a checkpoint as aligned words
-    }
-    if (ctx->failed) return fail_all(FELICS_E_HIP);
-    if (n == 0) return FELICS_OK;
-    if (any_pending(ctx)) return fail_all(FELICS_E_INVALID_ARGUMENT);  // felics_wait_batch first
-    if (n > 0xFFFFFFFFull) return fail_all(FELICS_E_INVALID_ARGUMENT);
-    if (hipSetDevice(ctx->device) != hipSuccess) return fail_all(hip_fail(ctx, hipGetLastError(), "hipSetDevice"));
-    ctx->view_ready = (hipEvent_t)ready_event;
-    const int rc = decompress_views_indexed(ctx, n, d_streams, offsets, lens, d_index, idx_offsets, idx_lens, views, hdrs, status);
-    ctx->view_ready = nullptr;
-    return rc;
+    return felics::views_indexed_call(ctx, n, d_streams, offsets, lens, d_index, idx_offsets, idx_lens, views, ready_event, hdrs, status,
+                                      felics::IndexViews8{});
+}
+
+int felics_get_index_view_wide_stats(const felics_ctx *ctx, felics_index16_view_stats *out, size_t out_size) {
+    if (!ctx || !out) return FELICS_E_INVALID_ARGUMENT;
+    memcpy(out, &ctx->iv16stats, std::min(out_size, sizeof(felics_index16_view_stats)));
+    return FELICS_OK;
+}
+
+int felics_decompress_views_device_indexed_wide(felics_ctx *ctx, size_t n, const void *d_streams, const uint64_t *offsets, const uint64_t *lens,
+                                                const void *d_index, const uint64_t *idx_offsets, const uint64_t *idx_lens,
+                                                const felics_view *views, void *ready_event, felics_header *hdrs, int *status) {
+    return felics::views_indexed_call(ctx, n, d_streams, offsets, lens, d_index, idx_offsets, idx_lens, views, ready_event, hdrs, status,
+                                      felics::IndexViews16{});
 }
 
 }  // extern "C"

@@ -1774,6 +1774,56 @@ __global__ __launch_bounds__(64) void k_decode16_region(const uint8_t *__restric
     }
 }
 
+namespace {
+
+// The whole segment into a view (felics_decompress_views_device_indexed16): ViewSink for 16-bit samples.  A gray sample is ONE aligned
+// two-byte store at the place the view's strides give pixel (col, y) -- address and strides are even (felics_view_writable), whatever
+// lies between the samples is never stored to, negative strides and pixel strides other than 2 included; an RGB sample goes to plane c
+// of the row's int32 planes as the segment sink does (the conversion writes the view).  The walk hands it p0 <= at < pend only, and
+// (col, y) is a pixel of the image the view was checked against.
+struct View16Sink {
+    uint8_t *data;   // gray: the view's first sample; else null
+    int64_t row_stride, pixel_stride;
+    int32_t *outp;   // RGB: plane c of the row's planes
+    __device__ __forceinline__ uint64_t stop(uint64_t pend) const { return pend; }
+    __device__ __forceinline__ void store(uint32_t col, uint32_t y, uint64_t at, int v) const {
+        if (data) *reinterpret_cast<uint16_t *>(data + view_sample_offset(row_stride, pixel_stride, 0, col, y, 0)) = (uint16_t)v;
+        else outp[at] = v;
+    }
+};
+
+}  // namespace
+
+// One wave per WORK ITEM = (row, plane, segment) of felics_decompress_views_device_indexed16 (felics_kernels.h; host model:
+// felics_decompress_indexed16_view): k_decode8_seg_views for version-2 indexes.  The tables are that kernel's own (IndexViewRow,
+// IndexViewItem: every field fits; plane_off counts int32 samples); the one thing a version-2 walk needs beside them, the index's
+// length, is read from idx_lens[row.stream], which the call has on the device anyway.  Item and row are wave-uniform (blockIdx.x:
+// scalar loads); geometry, segment_pixels and K are the row's.  Block b of a launch works on items[b] with table b of the launch's
+// tables and the launch's epoch, as in k_decode16_seg; item_status[b] = FELICS_OK or the code (k_seg_status picks a row's first);
+// rows_loaded: += the state rows the wave copied.
+__global__ __launch_bounds__(64) void k_decode16_seg_views(const uint8_t *__restrict__ streams, const uint64_t *__restrict__ offsets,
+                                                           const uint64_t *__restrict__ lens, const uint8_t *__restrict__ index,
+                                                           const uint64_t *__restrict__ idx_lens, const IndexViewRow *__restrict__ rows,
+                                                           const IndexViewItem *__restrict__ items, int32_t *__restrict__ planes,
+                                                           uint32_t *__restrict__ gtable, uint32_t epoch, int *__restrict__ item_status,
+                                                           unsigned long long *__restrict__ rows_loaded) {
+    extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
+    const IndexViewItem item = items[blockIdx.x];
+    const IndexViewRow r = rows[item.row];
+    const DecUniform geo{r.W, r.H, r.color};
+    const uint32_t c = item.plane;
+    const View16Sink sink{r.color ? nullptr : reinterpret_cast<uint8_t *>(const_cast<void *>(r.view.data)), r.view.row_stride, r.view.pixel_stride,
+                          r.color ? planes + r.plane_off + (uint64_t)c * r.W * r.H : nullptr};
+    uint32_t *table = gtable + (uint64_t)blockIdx.x * DEC16_CONTEXTS * DEC16_ROW;
+    uint32_t loaded = 0;
+    const int rc = decode16_from_checkpoint(smem, streams + offsets[r.stream], lens[r.stream], index + r.index_off, idx_lens[r.stream], geo,
+                                            r.segment_pixels, r.K, c, item.seg, false, table, epoch, sink, &loaded);
+    if (lane_id() == 0) {
+        item_status[blockIdx.x] = rc;
+        if (loaded) atomicAdd(rows_loaded, (unsigned long long)loaded);
+    }
+}
+
 // ------------------------------------------------------------------------------------------
 // 16-bit streams, sixty-four of one shape per wave, LANE = stream: the walk of k_decode8_lanes with the arithmetic of k_decode16.
 //
@@ -2253,6 +2303,8 @@ hipError_t launch_decode16_lanes_waves_views(hipStream_t s, const uint8_t *strea
 // ------------------------------------------------------------------------------------------
 
 static_assert(INDEX_LDS_LIMIT == DECODE_LDS_LIMIT, "felics_index.h names the wave form's LDS limit for the host model");
+static_assert(index16_lds_bytes(0) == DEC16_SLOTS * DEC16_ROW * 4 + DEC16_SLOTS * 4 && index16_lds_bytes(65) - index16_lds_bytes(0) == 2u * 128u * 4u,
+              "felics_index.h repeats decode16_lds_bytes for the host model");
 
 hipError_t launch_decode8_seg_views(hipStream_t s, const uint8_t *streams, const uint64_t *offsets, const uint64_t *lens, const uint8_t *index,
                                     const IndexViewRow *rows, const IndexViewItem *items, uint32_t nitems, uint32_t lds, int16_t *planes,
@@ -2336,6 +2388,32 @@ hipError_t launch_regions16_finish(hipStream_t s, const RegionRow *rows, uint32_
         for (uint32_t r0 = 0; r0 < nregions; r0 += 65535u)
             hipLaunchKernelGGL(k_ycocg16_to_rgb<ConvRegion>, dim3(bx, std::min(nregions - r0, 65535u)), dim3(256), 0, s, planes,
                                reinterpret_cast<uint16_t *>(pixels), ConvRegion{rows, r0}, status);
+    return hipGetLastError();
+}
+
+// ------------------------------------------------------------------------------------------
+// felics_decompress_views_device_indexed16: a launch of k_decode16_seg_views; a stream pass's tail.
+// ------------------------------------------------------------------------------------------
+
+hipError_t launch_decode16_seg_views(hipStream_t s, const uint8_t *streams, const uint64_t *offsets, const uint64_t *lens, const uint8_t *index,
+                                     const uint64_t *idx_lens, const IndexViewRow *rows, const IndexViewItem *items, uint32_t nitems, uint32_t lds,
+                                     int32_t *planes, uint32_t *table, uint32_t epoch, int *item_status, unsigned long long *rows_loaded) {
+    if (nitems == 0) return hipSuccess;
+    if (lds > 64u * 1024u) {
+        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&k_decode16_seg_views), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                                 (int)DECODE_LDS_LIMIT);
+        if (e != hipSuccess) return e;
+    }
+    hipLaunchKernelGGL(k_decode16_seg_views, dim3(nitems), dim3(64), lds, s, streams, offsets, lens, index, idx_lens, rows, items, planes, table,
+                       epoch, item_status, rows_loaded);
+    return hipGetLastError();
+}
+
+hipError_t launch_seg16_views_finish(hipStream_t s, uint32_t n, const RegionRow *regions, const int *item_status, const DecodeRow *conv,
+                                     const ViewRow *views, uint64_t max_npix, int32_t *planes, int *status) {
+    if (n == 0) return hipSuccess;
+    hipLaunchKernelGGL(k_seg_status, dim3(n), dim3(64), 0, s, item_status, regions, 0u, status);
+    if (max_npix) launch_conv_views<int32_t, uint16_t>(s, conv, n, max_npix, planes, status, DecodeViews{views, false, true});
     return hipGetLastError();
 }
 

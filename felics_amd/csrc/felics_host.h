@@ -231,6 +231,10 @@ struct felics_ctx {
     // two kinds of headers in dec_meta; rows, items and the finish tables in dec_region_work; item and row status words in
     // dec_seg_status; a pass's planes in dec_planes); view_ready is its ready event; the counts of felics_get_index_view_stats
     felics_index_view_stats ivstats = {};
+    // felics_decompress_views_device_indexed16: the same buffers (int32 planes in dec_planes, the rows-loaded counter behind the
+    // status words), the tables and epochs of felics_decompress_batch_device_indexed16 (dec_table, dec_epoch); the counts of
+    // felics_get_index16_view_stats
+    felics_index16_view_stats iv16stats = {};
     // felics_compress_views_device_indexed: the indexes of a remedy's group (redo_by_shape: written back to back by the uniform
     // writer, copied to where the caller wants them); the counts of felics_get_index_emit_stats
     DevBuf mix_index;

@@ -257,6 +257,9 @@ constexpr uint32_t INDEX_LDS_LIMIT = 160u * 1024u;
 FELICS_IDX_HD inline uint64_t index_lds_bytes(uint32_t W, uint32_t color) {
     return (color ? 512u : 256u) * 6u * 4u + 2ull * (((uint64_t)W + 63u) & ~63ull) * 2u;
 }
+// The same for the 16-bit wave form (what decode16_lds_bytes returns: 512 cached estimator rows of sixteen words, their 512 tags, two
+// rows of int32 padded to whole blocks of 64): the widest row is 16 128 samples.  For the host model of k_decode16_seg_views.
+FELICS_IDX_HD constexpr uint64_t index16_lds_bytes(uint32_t W) { return 512u * 16u * 4u + 512u * 4u + 2ull * (((uint64_t)W + 63u) & ~63ull) * 4u; }
 
 }  // namespace felics
 

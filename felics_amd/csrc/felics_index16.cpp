@@ -1,7 +1,8 @@
 // felics_index16.cpp -- host side of the restart index of 16-bit streams (felics.h "Restart index: 16-bit streams", format version 2;
 // DESIGN.md §3.4): felics_index16_size_max, felics_index16_build (the index of any 16-bit stream, from one pass of the host decoder
 // and a replay of the estimator over the decoded samples) and felics_decompress_indexed16 (the stream decoded segment by segment, each from its
-// checkpoint alone: the host model of k_decode16_seg, with the same checks in the same order).
+// checkpoint alone: the host model of k_decode16_seg, with the same checks in the same order) and felics_decompress_indexed16_view (the
+// same walk written through a view's strides: the host model of k_decode16_seg_views).
 #include <algorithm>
 #include <cstdint>
 #include <cstring>
@@ -11,6 +12,7 @@
 #include "../../include/felics.h"
 #include "felics_hostdec.h"
 #include "felics_index.h"
+#include "felics_viewcheck.h"
 
 namespace {
 
@@ -69,6 +71,76 @@ int store_rgb16(const std::vector<int32_t> (&ch)[3], unsigned planes, uint16_t *
             if (v[c] < 0 || v[c] > 65535) return FELICS_E_INVALID_VALUE;
             if (dst) dst[i * planes + c] = (uint16_t)v[c];
         }
+    }
+    return FELICS_OK;
+}
+
+// A 16-bit stream decoded through its version-2 index, segment by segment in (plane, segment) order, each from its checkpoint alone:
+// what felics_decompress_indexed16 and felics_decompress_indexed16_view share, and the model of the kernels' walk -- the directory
+// entry, the state rows (the table holds exactly the checkpoint's rows: what a segment loaded or touched is cleared behind it), the
+// window samples, the two raw samples (j = 0), the walk, every decoded sample in range, done(c, s0, s1, plane c's samples) for the
+// segment's pixels [s0, s1), then the end check.  hdr and L: the stream's header and the layout index16_header_check gave.  ch[c]:
+// plane c, W * H samples.  The first failure is the code.
+template <typename Done>
+int walk_segments16(const uint8_t *in, size_t len, const uint8_t *index, size_t index_len, const Index16Layout &L, const felics_header &hdr,
+                    std::vector<int32_t> (&ch)[3], Done done) {
+    const uint32_t W = hdr.width, color = hdr.color_type, seg = idx_rd32(index + IDX_SEGPIX);
+    const size_t npix = (size_t)W * hdr.height;
+    try {
+        Estimator est(OPT16);
+        std::vector<uint32_t> touched(OPT16.max_context + 1, 0u);  // [ctx] != 0: the segment had an event of that context
+        for (uint32_t c = 0; c < L.planes; c++) {
+            ch[c].assign(npix, 0);
+            int32_t *out = ch[c].data();
+            for (uint32_t j = 0; j < std::max(L.K, 1u); j++) {
+                uint64_t start, end, rows_off;
+                uint32_t n_rows;
+                if (index16_segment_bounds(index, L, c, j, len, index_len, start, end, rows_off, n_rows)) return FELICS_E_INVALID_INDEX;
+                const uint8_t *rows = index + rows_off;
+                int64_t prev = -1;
+                for (uint32_t k = 0; k < n_rows; k++) {
+                    const uint8_t *row = rows + (uint64_t)k * INDEX16_ROW_BYTES;
+                    const uint32_t ctx = idx_rd32(row + 4 * INDEX16_ROW_CTX);
+                    if (ctx >= index16_contexts(color, c) || (int64_t)ctx <= prev) return FELICS_E_INVALID_INDEX;
+                    prev = ctx;
+                    for (unsigned i = 0; i < 15; i++) est.row(ctx)[i] = idx_rd32(row + 4 * i);
+                }
+                const size_t s0 = (size_t)j * seg, s1 = std::min(npix, s0 + seg);
+                if (L.K) {  // the 2 W samples in front of s0, range-checked; window positions in front of the plane are never looked at
+                    const uint8_t *win = index + L.win_base + ((uint64_t)c * L.K + j) * L.win_bytes;
+                    for (uint64_t s = 0; s < 2ull * W; s++) {
+                        if (s0 + s < 2ull * W) continue;
+                        const int32_t v = color ? (int32_t)idx_rd32(win + 4 * s) : (int32_t)idx_rd16(win + 2 * s);
+                        if (!in_plane_range(v, color, c)) return FELICS_E_INVALID_INDEX;
+                        out[s0 + s - 2ull * W] = v;
+                    }
+                }
+                BitReader br(in, len, start);
+                if (j == 0) {
+                    const int32_t p0 = (int32_t)br.bits(32), p1 = (int32_t)br.bits(32);
+                    if (br.failed()) return FELICS_E_IO;
+                    if (npix > 0) out[0] = p0;
+                    if (npix > 1) out[1] = p1;
+                }
+                if (s1 > s0) {
+                    const int rc = decode_span(br, W, OPT16, est, out, std::max<size_t>(s0, 2), s1, touched.data());
+                    if (rc) return rc;
+                    for (size_t i = s0; i < s1; i++)
+                        if (!in_plane_range(out[i], color, c)) return FELICS_E_INVALID_VALUE;
+                    done(c, s0, s1, out);
+                }
+                if (br.pos() != end) return FELICS_E_INVALID_INDEX;  // the end check: exactly on the next checkpoint
+                for (uint32_t k = 0; k < n_rows; k++)
+                    memset(est.row(idx_rd32(rows + (uint64_t)k * INDEX16_ROW_BYTES + 4 * INDEX16_ROW_CTX)), 0, 15 * 4);
+                for (uint32_t ctx = 0; ctx <= OPT16.max_context; ctx++)
+                    if (touched[ctx]) {
+                        touched[ctx] = 0;
+                        memset(est.row(ctx), 0, 15 * 4);
+                    }
+            }
+        }
+    } catch (const std::bad_alloc &) {
+        return FELICS_E_INVALID_DIMENSIONS;
     }
     return FELICS_OK;
 }
@@ -230,75 +302,9 @@ int felics_decompress_indexed_wide(const uint8_t *in, size_t len, const uint8_t 
     if (npix && !pixels) return FELICS_E_INVALID_ARGUMENT;
     Index16Layout L;
     if (index_len < INDEX_HEADER_BYTES || index16_header_check(index, color, W, H, len, index_len, L)) return FELICS_E_INVALID_INDEX;
-    const uint32_t seg = idx_rd32(index + IDX_SEGPIX);
     std::vector<int32_t> ch[3];
-    try {
-        Estimator est(OPT16);
-        std::vector<uint32_t> touched(OPT16.max_context + 1, 0u);  // [ctx] != 0: the segment had an event of that context
-        for (uint32_t c = 0; c < L.planes; c++) {
-            ch[c].assign(npix, 0);
-            int32_t *out = ch[c].data();
-            for (uint32_t j = 0; j < std::max(L.K, 1u); j++) {
-                uint64_t start, end, rows_off;
-                uint32_t n_rows;
-                if (index16_segment_bounds(index, L, c, j, len, index_len, start, end, rows_off, n_rows)) return FELICS_E_INVALID_INDEX;
-                // everything a segment starts from comes out of its checkpoint.  The table: exactly the checkpoint's rows (the
-                // table is all zero here: what a segment loaded or touched is cleared behind it)
-                const uint8_t *rows = index + rows_off;
-                int64_t prev = -1;
-                int bad = 0;
-                uint32_t loaded = 0;
-                for (; loaded < n_rows; loaded++) {
-                    const uint8_t *r = rows + (uint64_t)loaded * INDEX16_ROW_BYTES;
-                    const uint32_t ctx = idx_rd32(r + 4 * INDEX16_ROW_CTX);
-                    if (ctx >= index16_contexts(color, c) || (int64_t)ctx <= prev) {
-                        bad = 1;
-                        break;
-                    }
-                    prev = ctx;
-                    for (unsigned k = 0; k < 15; k++) est.row(ctx)[k] = idx_rd32(r + 4 * k);
-                }
-                auto clear_loaded = [&] {
-                    for (uint32_t k = 0; k < loaded; k++)
-                        memset(est.row(idx_rd32(rows + (uint64_t)k * INDEX16_ROW_BYTES + 4 * INDEX16_ROW_CTX)), 0, 15 * 4);
-                };
-                if (bad) return FELICS_E_INVALID_INDEX;
-                const size_t s0 = (size_t)j * seg, s1 = std::min(npix, s0 + seg);
-                // the 2 W samples in front of s0, range-checked; window positions in front of the plane are never looked at
-                if (L.K) {
-                    const uint8_t *win = index + L.win_base + ((uint64_t)c * L.K + j) * L.win_bytes;
-                    for (uint64_t s = 0; s < 2ull * W; s++) {
-                        if (s0 + s < 2ull * W) continue;
-                        const int32_t v = color ? (int32_t)idx_rd32(win + 4 * s) : (int32_t)idx_rd16(win + 2 * s);
-                        if (!in_plane_range(v, color, c)) return FELICS_E_INVALID_INDEX;
-                        out[s0 + s - 2ull * W] = v;
-                    }
-                }
-                BitReader br(in, len, start);
-                if (j == 0) {
-                    const int32_t p0 = (int32_t)br.bits(32), p1 = (int32_t)br.bits(32);
-                    if (br.failed()) return FELICS_E_IO;
-                    if (npix > 0) out[0] = p0;
-                    if (npix > 1) out[1] = p1;
-                }
-                if (s1 > s0) {
-                    rc = decode_span(br, W, OPT16, est, out, std::max<size_t>(s0, 2), s1, touched.data());
-                    if (rc) return rc;
-                    for (size_t i = s0; i < s1; i++)
-                        if (!in_plane_range(out[i], color, c)) return FELICS_E_INVALID_VALUE;
-                }
-                if (br.pos() != end) return FELICS_E_INVALID_INDEX;  // the end check: exactly on the next checkpoint
-                clear_loaded();
-                for (uint32_t ctx = 0; ctx <= OPT16.max_context; ctx++)
-                    if (touched[ctx]) {
-                        touched[ctx] = 0;
-                        memset(est.row(ctx), 0, 15 * 4);
-                    }
-            }
-        }
-    } catch (const std::bad_alloc &) {
-        return FELICS_E_INVALID_DIMENSIONS;
-    }
+    rc = walk_segments16(in, len, index, index_len, L, hdr, ch, [](uint32_t, size_t, size_t, const int32_t *) {});
+    if (rc) return rc;
     return store_rgb16(ch, planes, (uint16_t *)pixels);
 }
 
@@ -387,6 +393,51 @@ int felics_decompress_region_indexed_wide(const uint8_t *in, size_t len, const u
         return FELICS_E_INVALID_DIMENSIONS;
     }
     return store_rgb16(ch, planes, (uint16_t *)pixels);
+}
+
+int felics_decompress_indexed_view_wide(const uint8_t *in, size_t len, const uint8_t *index, size_t index_len, const felics_view *view,
+                                        felics_header *hdr_out) {
+    if ((!in && len) || (!index && index_len) || !view) return FELICS_E_INVALID_ARGUMENT;
+    int rc = view_writable_code(*view);
+    if (rc) return rc;
+    // the per-stream codes of felics_decompress_views_device_indexed16, in its order
+    felics_header hdr;
+    rc = felics_read_header(in, len, &hdr);
+    if (hdr_out) *hdr_out = rc ? felics_header{} : hdr;
+    if (rc) return rc;
+    const uint32_t W = hdr.width, H = hdr.height, color = hdr.color_type;
+    const unsigned planes = color ? 3 : 1;
+    if ((uint64_t)W * H > 0xFFFFFFFFull) return FELICS_E_INVALID_DIMENSIONS;
+    const size_t npix = (size_t)W * H;
+    // (k_read_headers' rule: two raw 32-bit samples per plane, then at least one flag bit per pixel, padded to a byte)
+    const uint64_t bits = (uint64_t)planes * (64u + (npix > 2 ? npix - 2 : 0));
+    if (len - FELICS_HEADER_BYTES < (bits + 7) / 8) return FELICS_E_IO;
+    if (hdr.pixel_depth != FELICS_DEPTH_16) return FELICS_E_UNSUPPORTED;
+    if (index16_lds_bytes(W) > INDEX_LDS_LIMIT) return FELICS_E_UNSUPPORTED;  // what the wave form cannot hold, the model refuses too
+    if ((int)color != view->color || (int)hdr.pixel_depth != view->depth || W != view->width || H != view->height) return FELICS_E_INVALID_DIMENSIONS;
+    Index16Layout L;
+    if (index_len < INDEX_HEADER_BYTES || index16_header_check(index, color, W, H, len, index_len, L)) return FELICS_E_INVALID_INDEX;
+    uint8_t *data = (uint8_t *)const_cast<void *>(view->data);
+    const int64_t rs = view->row_stride, ps = view->pixel_stride, cs = color ? view->channel_stride : 0;
+    auto sample = [&](size_t i, unsigned c) {  // where the kernel's sink (gray) and the strided conversion (RGB) store pixel i
+        const uint32_t y = (uint32_t)(i / W), x = (uint32_t)(i - (size_t)y * W);
+        return reinterpret_cast<uint16_t *>(data + view_sample_offset(rs, ps, cs, x, y, c));
+    };
+    std::vector<int32_t> ch[3];
+    // gray: a segment's samples through the view, as the kernel's sink stores them (an RGB plane waits for the other two)
+    rc = walk_segments16(in, len, index, index_len, L, hdr, ch, [&](uint32_t, size_t s0, size_t s1, const int32_t *out) {
+        for (size_t i = s0; i < s1 && !color; i++) *sample(i, 0) = (uint16_t)out[i];
+    });
+    if (rc || !color) return rc;
+    try {
+        std::vector<uint16_t> rgb(npix * 3);  // (converted and range-checked first: a stream that fails here leaves the view as it was)
+        if ((rc = store_rgb16(ch, planes, rgb.data())) != 0) return rc;
+        for (size_t i = 0; i < npix; i++)
+            for (unsigned c = 0; c < 3; c++) *sample(i, c) = rgb[i * 3 + c];
+    } catch (const std::bad_alloc &) {
+        return FELICS_E_INVALID_DIMENSIONS;
+    }
+    return FELICS_OK;
 }
 
 }  // extern "C"

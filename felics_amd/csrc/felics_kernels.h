@@ -432,6 +432,20 @@ hipError_t launch_decode16_regions(hipStream_t s, const uint8_t *streams, const 
                                    unsigned long long *rows_loaded);
 hipError_t launch_regions16_finish(hipStream_t s, const RegionRow *rows, uint32_t nregions, uint64_t max_crop, uint8_t *pixels, int32_t *planes,
                                    const int *item_status, int *status);
+// 16-bit streams of ANY shapes through version-2 indexes into views (felics_decompress_views_device_indexed16, felics.h "Restart
+// index: 16-bit streams into views and mixed shapes"): k_decode16_seg_views, one wave per work item = (row, plane, segment) --
+// k_decode16_seg's walk with the view sink, on launch_decode8_seg_views' tables (IndexViewRow, IndexViewItem; index + index_off a
+// multiple of 64, plane_off in int32 samples; the index's length is idx_lens[row.stream]).  Gray samples go through the row's view, one
+// aligned two-byte store each, any (even) strides; RGB rows write int32 planes at planes + plane_off, converted through the view by
+// k_ycocg16_to_rgb<ConvStrided>.  One launch: `nitems` consecutive items of the work list whose rows all fit `lds` bytes of dynamic
+// LDS (decode16_lds_bytes of the widest), wave b on table b of `table` (decode16_table_bytes(nitems) bytes, launch_decode16_seg's
+// buffer and epoch rule: one fresh epoch per launch); item_status: a word per item of the launch; *rows_loaded += the state rows
+// copied.  launch_seg16_views_finish is launch_seg_views_finish for int32 planes and uint16 views.
+hipError_t launch_decode16_seg_views(hipStream_t s, const uint8_t *streams, const uint64_t *offsets, const uint64_t *lens, const uint8_t *index,
+                                     const uint64_t *idx_lens, const IndexViewRow *rows, const IndexViewItem *items, uint32_t nitems, uint32_t lds,
+                                     int32_t *planes, uint32_t *table, uint32_t epoch, int *item_status, unsigned long long *rows_loaded);
+hipError_t launch_seg16_views_finish(hipStream_t s, uint32_t n, const RegionRow *regions, const int *item_status, const DecodeRow *conv,
+                                     const ViewRow *views, uint64_t max_npix, int32_t *planes, int *status);
 // The same for 16-bit streams, gray or RGB (k_decode16_lanes): 64 streams per wave, lane = stream; needs W >= 8 and a table of
 // decode16_lanes_table_bytes(n, W, H, color) bytes = n * planes * dec16l_rows(W * H, planes) * 64 (felics_lanetable.h: sized by the
 // pixel count, 512 KB per plane of a 64 x 64 stream, the wave form's 8.4 MB from 32 771 pixels on), zero-initialised ONCE: rows carry

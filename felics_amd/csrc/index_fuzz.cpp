@@ -12,11 +12,13 @@
 //     admissible view (a pitch, pixel stride 1 or 2, a flipped row or channel axis, interleaved or planar) whose target buffer is
 //     EXACTLY the size of the view's hull, so a store outside it is the sanitizer's to report: on a good pair every sample must be
 //     felics_decompress's and every other byte of the hull untouched; on a mutated or foreign pair any code, no crash.
-// `index_fuzz --index16 DIR` runs the 16-bit index's two host functions instead (felics_index16.cpp): felics_index16_build at the same
+// `index_fuzz --index16 DIR` runs the 16-bit index's host functions instead (felics_index16.cpp): felics_index16_build at the same
 // two segment sizes; where it succeeds the size is within felics_index16_size_max, the two-call pattern holds,
 // felics_decompress_indexed16 gives felics_decompress's pixels, felics_decompress_region_indexed16 gives the full frame, a seeded
-// interior window and an empty one, and the index goes through byte mutations (header, directory, rows' context words, anywhere)
-// and cuts, each with the same three windows; NAME.idx beside NAME is used as it is: any code, no crash.
+// interior window and an empty one, felics_decompress_indexed16_view gives felics_decompress's samples in two random admissible views
+// (as in the 8-bit mode: a target of exactly the hull, every other byte untouched), and the index goes through byte mutations (header,
+// directory, rows' context words, anywhere) and cuts, each with the same three windows and every other one with a view; NAME.idx beside
+// NAME is used as it is: any code, no crash.
 // Built with -fsanitize=address,undefined by `make asan`; tests/test_index_cpu.py and tests/test_index16_cpu.py feed it mutated corpora.
 // Exit code 0 = every input was handled without a sanitizer report and every accepted pair decoded to the right pixels.
 #include <dirent.h>
@@ -109,6 +111,43 @@ static int fuzz16(const char *dir) {
         }
         return true;
     };
+    // felics_decompress_indexed16_view, the host model of the indexed views call for 16-bit streams, on a pair: into a random
+    // admissible view of the header's shape (a pitch, pixel stride 2 or 4 bytes, a flipped row or channel axis, interleaved or planar)
+    // whose target buffer is EXACTLY the size of the view's hull, so a store outside it is the sanitizer's to report.  `good`: the call
+    // must succeed, every sample must be ref's (h's image) and every other byte of the hull untouched.
+    std::vector<uint8_t> target, expect;
+    auto view16_on = [&](const uint8_t *index_bytes, size_t index_len, const felics_header &h, bool good) {
+        const int64_t W = h.width, H = h.height, C = h.color_type ? 3 : 1;
+        if ((uint64_t)W * H * C * 2 * 3 > cap) return true;  // (targets are this driver's to allocate)
+        felics_view v{nullptr, h.width, h.height, h.color_type, FELICS_DEPTH_16, 0, 0, 0};
+        const int64_t gap = 2 * (int64_t)(next() % 2);
+        if (C == 3 && next() % 2) {  // planar
+            v.pixel_stride = 2 + gap;
+            v.row_stride = W * v.pixel_stride + 2 * (int64_t)(next() % 5);
+            v.channel_stride = H * v.row_stride + 2 * (int64_t)(next() % 7);
+        } else {
+            v.channel_stride = 2;
+            v.pixel_stride = 2 * C + gap * C;
+            v.row_stride = W * v.pixel_stride + 2 * (int64_t)(next() % 5);
+        }
+        if (next() % 2) v.row_stride = -v.row_stride;
+        if (C == 3 && next() % 2) v.channel_stride = -v.channel_stride;
+        int64_t lo = 0, hi = W && H ? 2 : 0;
+        const int64_t spans[3] = {(H - 1) * v.row_stride, (W - 1) * v.pixel_stride, (C - 1) * v.channel_stride};
+        for (int k = 0; k < 3 && W && H; k++) (spans[k] < 0 ? lo : hi) += spans[k];
+        target.assign((size_t)(hi - lo), 0xA5);
+        if (W && H) v.data = target.data() - lo;
+        felics_header hv;
+        const int rc = felics_decompress_indexed16_view(buf.data(), buf.size(), index_bytes, index_len, &v, &hv);
+        if (!good) return true;
+        if (rc != FELICS_OK) return false;
+        expect.assign(target.size(), 0xA5);
+        for (int64_t y = 0; y < H; y++)
+            for (int64_t x = 0; x < W; x++)
+                for (int64_t c = 0; c < C; c++)
+                    memcpy(&expect[(size_t)(y * v.row_stride + x * v.pixel_stride + c * v.channel_stride - lo)], &ref[(size_t)((y * W + x) * C + c) * 2], 2);
+        return target == expect;
+    };
     for (const std::string &n : names) {
         const std::string path = std::string(dir) + "/" + n;
         if (!slurp(path, buf)) continue;
@@ -118,6 +157,7 @@ static int fuzz16(const char *dir) {
         const size_t frame = rc_plain == FELICS_OK ? (size_t)h.width * h.height * (h.color_type ? 3 : 1) * (h.pixel_depth ? 2 : 1) : 0;
         if (slurp(path + ".idx", given)) {
             pairs++;
+            if (rc_plain == FELICS_OK && h.pixel_depth) view16_on(given.data(), given.size(), h, false);
             if (felics_decompress_indexed16(buf.data(), buf.size(), given.data(), given.size(), px.data(), px.size(), &h2) == FELICS_OK) pairs_ok++;
         }
         for (uint32_t seg : {4096u, 12288u}) {
@@ -150,6 +190,10 @@ static int fuzz16(const char *dir) {
                 fprintf(stderr, "%s: a region of a good pair failed or differs from felics_decompress_indexed16's window\n", n.c_str());
                 return 1;
             }
+            if (!view16_on(index.data(), ilen, h, true) || !view16_on(index.data(), ilen, h, true)) {
+                fprintf(stderr, "%s: a view of a good pair failed, differs from felics_decompress's samples or lost a byte between them\n", n.c_str());
+                return 1;
+            }
             const std::vector<uint8_t> idx(index.begin(), index.begin() + ilen);
             const size_t entries = (size_t)(h.color_type ? 3 : 1) * (((size_t)h.width * h.height + seg - 1) / seg);
             const int rounds = ilen > (1u << 20) ? 4 : 10;  // (a call clears a table of 7.9 MB: fewer rounds than the 8-bit mode's)
@@ -168,6 +212,7 @@ static int fuzz16(const char *dir) {
                 mutations++;
                 if (felics_decompress_indexed16(buf.data(), buf.size(), bad.data(), bad.size(), px.data(), px.size(), &h2) == FELICS_OK) mut_accepted++;
                 regions16_on(bad.data(), bad.size(), h, false);
+                if (m % 2 == 0) view16_on(bad.data(), bad.size(), h, false);  // (every call clears a 7.9 MB table: every other mutation)
                 if (m % 5 == 0) {  // and cut short
                     const size_t cut = (size_t)(next() % ilen);
                     if (felics_decompress_indexed16(buf.data(), buf.size(), bad.data(), cut, px.data(), px.size(), &h2) == FELICS_OK) {

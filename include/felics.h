@@ -601,7 +601,8 @@ int felics_get_decode_view_stats(const felics_ctx *ctx, felics_decode_view_stats
  *                 a stream, an index or a view is touched in this call, the two header kernels included.
  * The stream headers and the first 64 bytes of every index are read by two kernels and come back in one synchronise; no header is
  * fetched with a blocking copy.  The call is blocking: the views are complete when it returns.  It creates no HIP stream.
- * NOT HERE: a lane-per-segment form, regions into views, a queued form, 16-bit streams, streams without an index in the same call.
+ * NOT HERE: a lane-per-segment form, regions into views, a queued form, streams without an index in the same call; 16-bit streams
+ * (they have a call of their own: "Restart index: 16-bit streams into views and mixed shapes", below).
  * (The encode side of this call is felics_compress_views_device_indexed, below.) */
 int felics_decompress_views_device_indexed(felics_ctx *ctx, size_t n, const void *d_streams, const uint64_t *offsets, const uint64_t *lens,
                                            const void *d_index, const uint64_t *idx_offsets, const uint64_t *idx_lens,
@@ -700,9 +701,10 @@ int felics_get_index_emit_stats(const felics_ctx *ctx, felics_index_emit_stats *
  * WHAT THE CHECKS DO NOT PROVE: as above, and COUNTERS ARE NOT JUDGED: a forged counter gives a wrong Rice parameter in a segment
  * whose end check then fails (or whose pixels are wrong, as with an index of another stream); no address depends on a counter.
  * The encoder writes this index beside the streams of a blocking same-shape batch: felics_compress_batch_device_indexed16 below.
- * NOT HERE: the encoder's index for views, mixed shapes, queued and host-buffer calls; views and mixed shapes in the decoder, a lane
- * form, a queued form; a hashed table for small segments; cfelics / dfelics flags (--index keeps refusing 16-bit images).  (Regions
- * are built: "Restart index: regions of 16-bit streams", below.)
+ * NOT HERE: the encoder's index for views, mixed shapes, queued and host-buffer calls; a lane form and a queued form of the decoder;
+ * a hashed table for small segments; cfelics / dfelics flags (--index keeps refusing 16-bit images).  (Regions are built: "Restart
+ * index: regions of 16-bit streams", below; so are views and mixed shapes in the decoder: "Restart index: 16-bit streams into views
+ * and mixed shapes".)
  * NAMES: the library's symbols hold no digit, like every other symbol of this ABI (its symbol check reads names as letters and
  * underscores), so the five functions are exported as felics_index_wide_size_max, felics_index_wide_build,
  * felics_decompress_indexed_wide, felics_decompress_batch_device_indexed_wide and felics_get_index_wide_stats ("wide" as in the 16-bit
@@ -888,6 +890,84 @@ static inline int felics_decompress_regions_device_indexed16(felics_ctx *ctx, si
 }
 static inline int felics_get_region16_stats(const felics_ctx *ctx, felics_region16_stats *out, size_t out_size) {
     return felics_get_region_wide_stats(ctx, out, out_size);
+}
+
+/* ---- Restart index: 16-bit streams into views and mixed shapes ----
+ * "Restart index: views and mixed shapes" for version-2 indexes: stream i (at d_streams + offsets[i], lens[i] bytes; any 16-bit stream,
+ * with its own shape, colour, segment_pixels and K) has its version-2 index at d_index + idx_offsets[i], idx_lens[i] bytes long, and is
+ * decoded one wave per (stream, plane, segment) straight into views[i]: k_decode16_seg_views, the walk of
+ * felics_decompress_batch_device_indexed16 with a sink that writes through the view.  Every sample equals what felics_decompress yields
+ * for that stream.  A small image takes part with the K = 1 index felics_index16_build gives it.
+ * The contract is felics_decompress_views_device_indexed's, word for word -- hdrs and status[] filled on every return, one bad stream
+ * does not fail the others, the same stream (and index) may be referenced several times, refused while a ticket is outstanding,
+ * FELICS_E_HIP on a failed context, n = 0 returns FELICS_OK, the first non-zero status is returned, the checks made before anything is
+ * launched, ready_event, one synchronise for both kinds of headers, blocking, no HIP stream created -- except where a version-2 index
+ * forces a difference:
+ *   - d_index + idx_offsets[i] must be a multiple of 64, not 16 (FELICS_E_INVALID_ARGUMENT before anything is launched): the kernel
+ *     loads a state row as one aligned 64-byte line.
+ *   - views are 16-bit: felics_view_writable wants an even address and even strides.  A view of depth 8 passes that check and is then
+ *     FELICS_E_INVALID_DIMENSIONS for its stream, nothing written.
+ *   - FELICS_E_UNSUPPORTED is for an 8-BIT stream, and for a row whose 16-bit wave form does not fit the LDS (wider than 16 128).
+ *   - FELICS_E_INVALID_INDEX: idx_lens[i] < 64, or the version-2 header fails its checks against the stream's own header, its length
+ *     and idx_lens[i] (total_bytes must equal idx_lens[i]; the size of a version-2 index is no function of the shape).  Then whatever
+ *     the walk reports for the first failing segment in (plane, segment) order: all checks of "Restart index: 16-bit streams" are
+ *     made on the device.
+ *   - The write guarantee, SAMPLE BYTES ONLY: gray is one aligned 2-byte store per sample through all strides -- negative strides and
+ *     pixel strides other than 2 included, so no gray view is staged; RGB is decoded as int32 Y / Co / Cg planes (12 bytes per pixel)
+ *     into the context's plane scratch and the strided conversion of the unindexed call writes the view.  A stream that fails leaves
+ *     its RGB view unconverted; a failing gray stream may have written its own samples and nothing else.
+ *   - TWO bounds, both met by running in passes on the one stream.  The RGB plane scratch, as in the 8-bit call: consecutive streams
+ *     whose planes fit a quarter of the free device memory make a pass, a single larger stream is a pass of its own,
+ *     FELICS_TEST_INDEX_VIEWS_PASS=<bytes> caps it.  And the estimator tables: every wave of a launch owns a dense table (8.4 MB) in
+ *     the buffer the other 16-bit decoders use, every launch takes a fresh epoch, and a launch holds at most as many items as there
+ *     are tables (bounded as in felics_decompress_batch_device_indexed16; FELICS_TEST_INDEX16_PASS=k caps it).  A table cut may fall
+ *     inside a stream or a plane: an item needs its own table and nothing of its neighbours'.  The conversion of a stream pass runs
+ *     behind its last launch.
+ * NAMES: exported as felics_decompress_views_device_indexed_wide, felics_decompress_indexed_view_wide and
+ * felics_get_index_view_wide_stats; the aliases felics_decompress_views_device_indexed16, felics_decompress_indexed16_view and
+ * felics_get_index16_view_stats follow the declarations.
+ * NOT HERE: regions into views, a lane form, a queued form, 8-bit and 16-bit streams in one call, cfelics / dfelics flags. */
+int felics_decompress_views_device_indexed_wide(felics_ctx *ctx, size_t n, const void *d_streams, const uint64_t *offsets, const uint64_t *lens,
+                                                const void *d_index, const uint64_t *idx_offsets, const uint64_t *idx_lens,
+                                                const felics_view *views, void *ready_event, felics_header *hdrs /* optional */, int *status);
+
+/* Host only, the model of k_decode16_seg_views as felics_decompress_indexed_view is k_decode8_seg_views': the per-stream checks above
+ * in the same order, decoded segment by segment from the checkpoints alone (felics_decompress_indexed16's walk), written through the
+ * view's strides into HOST memory by the offset function the kernel's sink compiles (sample bytes only).  A view that is not
+ * felics_view_writable (its code) or whose shape differs from the stream's (FELICS_E_INVALID_DIMENSIONS) is refused before a byte is
+ * written; an RGB stream that fails leaves the view untouched, a gray one may have written the segments in front of the failing one.
+ * hdr (optional) gets the stream's header where felics_read_header accepts it. */
+int felics_decompress_indexed_view_wide(const uint8_t *in, size_t len, const uint8_t *index, size_t index_len, const felics_view *view,
+                                        felics_header *hdr);
+
+/* What a context's felics_decompress_views_device_indexed16 calls did so far (calls that passed the checks before the launch).
+ * felics_index_view_stats and felics_index16_stats do not count these calls. */
+typedef struct felics_index16_view_stats {
+    uint64_t streams;      /* streams handed in */
+    uint64_t undecoded;    /* ... that got a code before a wave was launched for them */
+    uint64_t items;        /* waves launched: C * max(K, 1) for every decoded stream */
+    uint64_t launches;     /* k_decode16_seg_views launches (per pass and LDS class, cut by the tables) */
+    uint64_t passes;       /* stream passes (consecutive streams whose RGB planes share the scratch) */
+    uint64_t rows_loaded;  /* state rows copied into tables */
+    uint64_t plane_bytes;  /* NOT cumulative: the RGB scratch of the last call's largest pass */
+    uint64_t table_bytes;  /* NOT cumulative: the estimator tables of the last call */
+} felics_index16_view_stats;
+/* Writes min(out_size, sizeof(felics_index16_view_stats)) bytes, never more. */
+int felics_get_index_view_wide_stats(const felics_ctx *ctx, felics_index16_view_stats *out, size_t out_size);
+
+static inline int felics_decompress_views_device_indexed16(felics_ctx *ctx, size_t n, const void *d_streams, const uint64_t *offsets,
+                                                           const uint64_t *lens, const void *d_index, const uint64_t *idx_offsets,
+                                                           const uint64_t *idx_lens, const felics_view *views, void *ready_event,
+                                                           felics_header *hdrs, int *status) {
+    return felics_decompress_views_device_indexed_wide(ctx, n, d_streams, offsets, lens, d_index, idx_offsets, idx_lens, views, ready_event, hdrs,
+                                                       status);
+}
+static inline int felics_decompress_indexed16_view(const uint8_t *in, size_t len, const uint8_t *index, size_t index_len, const felics_view *view,
+                                                   felics_header *hdr) {
+    return felics_decompress_indexed_view_wide(in, len, index, index_len, view, hdr);
+}
+static inline int felics_get_index16_view_stats(const felics_ctx *ctx, felics_index16_view_stats *out, size_t out_size) {
+    return felics_get_index_view_wide_stats(ctx, out, out_size);
 }
 
 /* Text for a code above; for FELICS_E_HIP felics_last_error(ctx) has the HIP message. */
