@@ -399,6 +399,16 @@ def view_of_array(array):
     return (ptr, shape[1], shape[0], color, depth, strides[0], strides[1], strides[2] if len(shape) == 3 else 0)
 
 
+def _stream_arrays(offsets, lens, idx_offsets, idx_lens, also=None, what="a length and an index per stream"):
+    """The four per-stream arrays of an indexed decode call as contiguous uint64, all of the length of `offsets` (and of `also`, if given):
+    -> (n, ctypes pointers to the four; a pointer keeps its array alive)."""
+    arrays = [np.ascontiguousarray(a, dtype=np.uint64) for a in (offsets, lens, idx_offsets, idx_lens)]
+    n = len(arrays[0])
+    if any(len(a) != n for a in arrays) or (also is not None and also != n):
+        raise ValueError(what)
+    return (n, *(a.ctypes.data_as(C.POINTER(C.c_uint64)) for a in arrays))
+
+
 def _segments(segment_pixels, n):
     """segment_pixels of n views as a uint32 array: one int for all of them, or a sequence of n"""
     segs = np.full(n, segment_pixels, dtype=np.uint32) if np.isscalar(segment_pixels) else np.ascontiguousarray(segment_pixels, dtype=np.uint32)
@@ -515,6 +525,25 @@ class Encoder:
 
     def _raise(self, rc):
         raise FelicsError(rc, lib().felics_last_error(self._h).decode())
+
+    def _stats(self, getter_name, struct, bare=False):
+        """what every *_stats method returns: the counts the context's getter fills `struct` with, as a dict.  A failure raises with the
+        context's last error text, or (bare) the code alone."""
+        st = struct()
+        rc = getattr(lib(), getter_name)(self._h, C.byref(st), C.sizeof(st))
+        if rc != 0:
+            if bare:
+                raise FelicsError(rc)
+            self._raise(rc)
+        return {k: int(getattr(st, k)) for k, _ in struct._fields_}
+
+    def _indexed_error(self, rc, **carried):
+        """what an indexed decode call raises for rc != 0: DecompressionError if rc is a stream error, FelicsError otherwise (with the
+        context's text behind a HIP failure); the error carries what the call had filled in (.status, .headers)."""
+        err = DecompressionError(rc) if rc in DecompressionError.KINDS else FelicsError(rc, lib().felics_last_error(self._h).decode() if rc == -9 else "")
+        for name, value in carried.items():
+            setattr(err, name, value)
+        return err
 
     def compress(self, image):
         """The whole .felics file of one image as bytes."""
@@ -641,19 +670,11 @@ class Encoder:
     def index_emit_stats(self):
         """felics_get_index_emit_stats: indexes written by compress_views_device_indexed and their checkpoints, how many of them by
         the mixed kernels (in_mixed) and how many by the uniform writer inside a remedy (redone); cumulative."""
-        st = _CIndexEmitStats()
-        rc = lib().felics_get_index_emit_stats(self._h, C.byref(st), C.sizeof(st))
-        if rc != 0:
-            self._raise(rc)
-        return {k: int(getattr(st, k)) for k, _ in _CIndexEmitStats._fields_}
+        return self._stats("felics_get_index_emit_stats", _CIndexEmitStats)
 
     def view_stats(self):
         """felics_get_view_stats: views seen, and how they were read (dense / in_place / gathered, bytes_staged); cumulative."""
-        st = _CViewStats()
-        rc = lib().felics_get_view_stats(self._h, C.byref(st), C.sizeof(st))
-        if rc != 0:
-            self._raise(rc)
-        return {k: int(getattr(st, k)) for k, _ in _CViewStats._fields_}
+        return self._stats("felics_get_view_stats", _CViewStats)
 
     def submit_surfaces_device(self, surfaces, d_out, d_out_cap, ready_event=None):
         """felics_submit_surfaces_device: surfaces = (view tuple of frame 0, frame_stride, count) or an object surfaces_of_array
@@ -686,11 +707,7 @@ class Encoder:
 
     def surface_stats(self):
         """felics_get_surface_stats: submissions, queued / immediate, frames_in_place / frames_gathered, bytes_staged; cumulative."""
-        st = _CSurfaceStats()
-        rc = lib().felics_get_surface_stats(self._h, C.byref(st), C.sizeof(st))
-        if rc != 0:
-            self._raise(rc)
-        return {k: int(getattr(st, k)) for k, _ in _CSurfaceStats._fields_}
+        return self._stats("felics_get_surface_stats", _CSurfaceStats)
 
     def compress_batch_host(self, pixel_ptrs, n, w, h, color, depth, out_ptrs, caps):
         """felics_compress_batch on raw HOST pointers (lists of n addresses: frames in, buffers of caps[i] bytes out): the
@@ -798,11 +815,7 @@ class Encoder:
     def index16_emit_stats(self):
         """felics_get_index_wide_emit_stats: streams handed to compress_batch_device_indexed16, the state rows and bytes of the indexes
         written and the passes that wrote them (all cumulative)."""
-        st = _CIndex16EmitStats()
-        rc = lib().felics_get_index_wide_emit_stats(self._h, C.byref(st), C.sizeof(st))
-        if rc != 0:
-            raise FelicsError(rc)
-        return {k: int(getattr(st, k)) for k, _ in _CIndex16EmitStats._fields_}
+        return self._stats("felics_get_index_wide_emit_stats", _CIndex16EmitStats, bare=True)
 
     def submit_batch_device(self, d_pixels, n, w, h, color, depth, d_out, d_out_cap):
         """Queues a batch and returns a ticket; up to two can be in flight (felics_submit_batch_device)."""
@@ -861,9 +874,7 @@ class Encoder:
             self._h, n, d_streams, offsets.ctypes.data_as(C.POINTER(C.c_uint64)), lens.ctypes.data_as(C.POINTER(C.c_uint64)),
             d_index, index_stride, d_pixels, d_pixels_cap, C.byref(ch), status.ctypes.data_as(C.POINTER(C.c_int)))
         if rc != 0:
-            err = DecompressionError(rc) if rc in DecompressionError.KINDS else FelicsError(rc, lib().felics_last_error(self._h).decode() if rc == -9 else "")
-            err.status = status
-            raise err
+            raise self._indexed_error(rc, status=status)
         return Header(ch.color_type, ch.pixel_depth, ch.width, ch.height), status
 
     def decompress_batch_device_indexed16(self, d_streams, offsets, lens, d_index, idx_offsets, idx_lens, d_pixels, d_pixels_cap):
@@ -871,33 +882,20 @@ class Encoder:
         d_index + idx_offsets[i], a multiple of 64; idx_lens[i] bytes, index16_build's exact size) and the uint16 pixels in device
         memory (raw pointers).  A wave per (stream, plane, segment).  Returns (Header, status array); raises as
         decompress_batch_device_indexed does (the error carries .status)."""
-        u64 = C.POINTER(C.c_uint64)
-        offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
-        lens = np.ascontiguousarray(lens, dtype=np.uint64)
-        idx_offsets = np.ascontiguousarray(idx_offsets, dtype=np.uint64)
-        idx_lens = np.ascontiguousarray(idx_lens, dtype=np.uint64)
-        n = len(offsets)
-        if len(lens) != n or len(idx_offsets) != n or len(idx_lens) != n:
-            raise ValueError("a length and an index per stream")
+        n, offsets, lens, idx_offsets, idx_lens = _stream_arrays(offsets, lens, idx_offsets, idx_lens)
         status = np.zeros(n, dtype=np.int32)
         ch = _CHeader()
         rc = lib().felics_decompress_batch_device_indexed_wide(
-            self._h, n, d_streams, offsets.ctypes.data_as(u64), lens.ctypes.data_as(u64), d_index, idx_offsets.ctypes.data_as(u64),
-            idx_lens.ctypes.data_as(u64), d_pixels, d_pixels_cap, C.byref(ch), status.ctypes.data_as(C.POINTER(C.c_int)))
+            self._h, n, d_streams, offsets, lens, d_index, idx_offsets, idx_lens, d_pixels, d_pixels_cap, C.byref(ch),
+            status.ctypes.data_as(C.POINTER(C.c_int)))
         if rc != 0:
-            err = DecompressionError(rc) if rc in DecompressionError.KINDS else FelicsError(rc, lib().felics_last_error(self._h).decode() if rc == -9 else "")
-            err.status = status
-            raise err
+            raise self._indexed_error(rc, status=status)
         return Header(ch.color_type, ch.pixel_depth, ch.width, ch.height), status
 
     def index16_stats(self):
         """felics_get_index_wide_stats: streams handed to decompress_batch_device_indexed16, their waves (segments16), the passes they ran
         in, the state rows loaded (all cumulative) and the table memory of one pass of the last call."""
-        st = _CIndex16Stats()
-        rc = lib().felics_get_index_wide_stats(self._h, C.byref(st), C.sizeof(st))
-        if rc != 0:
-            raise FelicsError(rc)
-        return {k: int(getattr(st, k)) for k, _ in _CIndex16Stats._fields_}
+        return self._stats("felics_get_index_wide_stats", _CIndex16Stats, bare=True)
 
     def decompress_regions_device_indexed(self, d_streams, offsets, lens, d_index, index_stride, regions, d_pixels, d_pixels_cap):
         """felics_decompress_regions_device_indexed: windows of streams of one shape through their restart indexes, everything in
@@ -915,19 +913,13 @@ class Encoder:
             d_index, index_stride, len(regions), regs, d_pixels, d_pixels_cap, out_offsets.ctypes.data_as(C.POINTER(C.c_uint64)),
             C.byref(ch), status.ctypes.data_as(C.POINTER(C.c_int)))
         if rc != 0:
-            err = DecompressionError(rc) if rc in DecompressionError.KINDS else FelicsError(rc, lib().felics_last_error(self._h).decode() if rc == -9 else "")
-            err.status = status
-            raise err
+            raise self._indexed_error(rc, status=status)
         return Header(ch.color_type, ch.pixel_depth, ch.width, ch.height), status, out_offsets
 
     def region_stats(self):
         """felics_get_region_stats: regions handed to decompress_regions_device_indexed, the segments walked for them, the segments
         of their frames that were not (C * K per region minus the walked), the pixels those walks cover; cumulative."""
-        st = _CRegionStats()
-        rc = lib().felics_get_region_stats(self._h, C.byref(st), C.sizeof(st))
-        if rc != 0:
-            self._raise(rc)
-        return {k: int(getattr(st, k)) for k, _ in _CRegionStats._fields_}
+        return self._stats("felics_get_region_stats", _CRegionStats)
 
     def decompress_regions_device_indexed16(self, d_streams, offsets, lens, d_index, idx_offsets, idx_lens, regions, d_pixels, d_pixels_cap):
         """felics_decompress_regions_device_indexed_wide: windows of 16-bit streams of one shape through their version-2 restart indexes
@@ -935,36 +927,22 @@ class Encoder:
         regions: (stream, x, y, w, h) each; crop r is dense uint16 at d_pixels + out_offsets[r] (bytes).  Only the segments that hold a
         pixel of a region are walked, a wave each.  Returns (Header, status array, out_offsets); raises like
         decompress_regions_device_indexed (the error carries .status, one per region)."""
-        u64 = C.POINTER(C.c_uint64)
-        offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
-        lens = np.ascontiguousarray(lens, dtype=np.uint64)
-        idx_offsets = np.ascontiguousarray(idx_offsets, dtype=np.uint64)
-        idx_lens = np.ascontiguousarray(idx_lens, dtype=np.uint64)
-        n = len(offsets)
-        if len(lens) != n or len(idx_offsets) != n or len(idx_lens) != n:
-            raise ValueError("a length and an index per stream")
+        n, offsets, lens, idx_offsets, idx_lens = _stream_arrays(offsets, lens, idx_offsets, idx_lens)
         regs = (_CRegion * max(len(regions), 1))(*[_CRegion(*(int(v) for v in r)) for r in regions])
         status = np.zeros(len(regions), dtype=np.int32)
         out_offsets = np.zeros(len(regions), dtype=np.uint64)
         ch = _CHeader()
         rc = lib().felics_decompress_regions_device_indexed_wide(
-            self._h, n, d_streams, offsets.ctypes.data_as(u64), lens.ctypes.data_as(u64), d_index, idx_offsets.ctypes.data_as(u64),
-            idx_lens.ctypes.data_as(u64), len(regions), regs, d_pixels, d_pixels_cap, out_offsets.ctypes.data_as(u64), C.byref(ch),
-            status.ctypes.data_as(C.POINTER(C.c_int)))
+            self._h, n, d_streams, offsets, lens, d_index, idx_offsets, idx_lens, len(regions), regs, d_pixels, d_pixels_cap,
+            out_offsets.ctypes.data_as(C.POINTER(C.c_uint64)), C.byref(ch), status.ctypes.data_as(C.POINTER(C.c_int)))
         if rc != 0:
-            err = DecompressionError(rc) if rc in DecompressionError.KINDS else FelicsError(rc, lib().felics_last_error(self._h).decode() if rc == -9 else "")
-            err.status = status
-            raise err
+            raise self._indexed_error(rc, status=status)
         return Header(ch.color_type, ch.pixel_depth, ch.width, ch.height), status, out_offsets
 
     def region16_stats(self):
         """felics_get_region_wide_stats: regions handed to decompress_regions_device_indexed16, the segments walked for them, the
         segments of their frames that were not, the pixels those walks cover, the state rows loaded and the passes; cumulative."""
-        st = _CRegion16Stats()
-        rc = lib().felics_get_region_wide_stats(self._h, C.byref(st), C.sizeof(st))
-        if rc != 0:
-            self._raise(rc)
-        return {k: int(getattr(st, k)) for k, _ in _CRegion16Stats._fields_}
+        return self._stats("felics_get_region_wide_stats", _CRegion16Stats)
 
     def read_headers_device(self, d_streams, offsets, lens):
         """felics_read_headers_device: the headers of streams in device memory (raw pointer), read on the GPU.
@@ -1054,25 +1032,16 @@ class Encoder:
 
     def _views_indexed(self, call, d_streams, offsets, lens, d_index, idx_offsets, idx_lens, views, ready_event):
         """what decompress_views_device_indexed and decompress_views_device_indexed16 share: the arrays, the call, the errors"""
-        offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
-        lens = np.ascontiguousarray(lens, dtype=np.uint64)
-        idx_offsets = np.ascontiguousarray(idx_offsets, dtype=np.uint64)
-        idx_lens = np.ascontiguousarray(idx_lens, dtype=np.uint64)
-        n = len(offsets)
-        if len(views) != n or len(lens) != n or len(idx_offsets) != n or len(idx_lens) != n:
-            raise ValueError("a length, an index and a view per stream")
+        n, offsets, lens, idx_offsets, idx_lens = _stream_arrays(offsets, lens, idx_offsets, idx_lens, also=len(views),
+                                                                 what="a length, an index and a view per stream")
         cv = (_CView * max(n, 1))(*[_cview(v) for v in views])
         status = np.zeros(max(n, 1), dtype=np.int32)
         hdrs = (_CHeader * max(n, 1))()
-        u64 = C.POINTER(C.c_uint64)
-        rc = call(
-            self._h, n, d_streams, offsets.ctypes.data_as(u64), lens.ctypes.data_as(u64), d_index, idx_offsets.ctypes.data_as(u64),
-            idx_lens.ctypes.data_as(u64), cv, int(ready_event) if ready_event else None, hdrs, status.ctypes.data_as(C.POINTER(C.c_int)))
+        rc = call(self._h, n, d_streams, offsets, lens, d_index, idx_offsets, idx_lens, cv, int(ready_event) if ready_event else None, hdrs,
+                  status.ctypes.data_as(C.POINTER(C.c_int)))
         headers = [Header(h.color_type, h.pixel_depth, h.width, h.height) for h in hdrs[:n]]  # (zeros where the header is invalid)
         if rc != 0:
-            err = DecompressionError(rc) if rc in DecompressionError.KINDS else FelicsError(rc, lib().felics_last_error(self._h).decode() if rc == -9 else "")
-            err.status, err.headers = status[:n], headers
-            raise err
+            raise self._indexed_error(rc, status=status[:n], headers=headers)
         return headers, status[:n]
 
     def decompress_arrays_device_indexed(self, d_streams, offsets, lens, d_index, idx_offsets, idx_lens, arrays, ready_event=None):
@@ -1099,48 +1068,29 @@ class Encoder:
         """felics_get_index16_view_stats: streams handed to decompress_views_device_indexed16, those that got a code before a wave was
         launched for them, the waves (items), kernel launches, stream passes and state rows loaded; cumulative -- and plane_bytes (the
         RGB scratch of the last call's largest pass) and table_bytes (the last call's estimator tables)."""
-        st = _CIndex16ViewStats()
-        rc = lib().felics_get_index_view_wide_stats(self._h, C.byref(st), C.sizeof(st))
-        if rc != 0:
-            self._raise(rc)
-        return {k: int(getattr(st, k)) for k, _ in _CIndex16ViewStats._fields_}
+        return self._stats("felics_get_index_view_wide_stats", _CIndex16ViewStats)
 
     def index_view_stats(self):
         """felics_get_index_view_stats: streams handed to decompress_views_device_indexed, those that got a code before a wave was
         launched for them, the waves (items), launches and passes; cumulative -- and plane_bytes, the RGB scratch of the last call's
         largest pass."""
-        st = _CIndexViewStats()
-        rc = lib().felics_get_index_view_stats(self._h, C.byref(st), C.sizeof(st))
-        if rc != 0:
-            self._raise(rc)
-        return {k: int(getattr(st, k)) for k, _ in _CIndexViewStats._fields_}
+        return self._stats("felics_get_index_view_stats", _CIndexViewStats)
 
     def decode_view_stats(self):
         """felics_get_decode_view_stats: views handed to decompress_views_device and how they were written (dense / in_place /
         scattered, bytes_staged); cumulative."""
-        st = _CDecodeViewStats()
-        rc = lib().felics_get_decode_view_stats(self._h, C.byref(st), C.sizeof(st))
-        if rc != 0:
-            self._raise(rc)
-        return {k: int(getattr(st, k)) for k, _ in _CDecodeViewStats._fields_}
+        return self._stats("felics_get_decode_view_stats", _CDecodeViewStats)
 
     def decode_stats(self):
         """felics_get_decode_stats: how many streams the two device decode calls were handed and which form they took (wave8 / lanes8 /
         wave16 / lanes16 / host / undecoded; cumulative), and lanes16_table_bytes of the last call."""
-        st = _CDecodeStats()
-        rc = lib().felics_get_decode_stats(self._h, C.byref(st), C.sizeof(st))
-        if rc != 0:
-            self._raise(rc)
-        out = {k: int(getattr(st, k)) for k, _ in _CDecodeStats._fields_}
+        out = self._stats("felics_get_decode_stats", _CDecodeStats)
         # (felics_index_stats: the segments decompress_batch_device_indexed gave a wave each / a lane each -- together n * C * K per
         # call -- and the lane-form passes it launched)
-        ist = _CIndexStats()
-        rc = lib().felics_get_index_stats(self._h, C.byref(ist), C.sizeof(ist))
-        if rc != 0:
-            self._raise(rc)
-        out["segments8"] = int(ist.segments8)
-        out["lane_segments8"] = int(ist.lane_segments8)
-        out["lane_passes"] = int(ist.lane_passes)
+        ist = self._stats("felics_get_index_stats", _CIndexStats)
+        out["segments8"] = ist["segments8"]
+        out["lane_segments8"] = ist["lane_segments8"]
+        out["lane_passes"] = ist["lane_passes"]
         return out
 
     def lane_count(self):

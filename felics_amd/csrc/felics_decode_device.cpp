@@ -684,75 +684,18 @@ int decode16_passes(felics_ctx *ctx, size_t n, size_t per, const void *d_streams
     return first_rc;
 }
 
-// ---- what the two indexed calls (felics_decompress_batch_device_indexed, felics_decompress_regions_device_indexed) open with ----
-// Both halves answer FELICS_OK or the call's return value; a code of their own is in status[0 .. n) already (a HIP failure, as
-// everywhere, leaves status alone).  Between the two halves each call makes the checks that are its own.
+// ---- the indexed calls: dense (felics_decompress_batch_device_indexed, _indexed16), regions (felics_decompress_regions_device_indexed,
+// _indexed16) and views (felics_decompress_views_device_indexed, _indexed16).  One driver per call kind (dense_indexed, regions_indexed,
+// decompress_views_indexed); what the depths differ in is a form: Depth8 / Depth16 for every kind, IndexSame8 / IndexSame16 on top
+// of them for the two same-shape kinds, IndexViews8 / IndexViews16 for the views.
 
-// The shape every stream must have: header of stream 0, which must be 8-bit with w * h < 2^32.
-int indexed_stream_shape(felics_ctx *ctx, const void *d_streams, const uint64_t *offsets, const uint64_t *lens, felics_header &hdr,
-                         felics_header *hdr_out, size_t n, int *status) {
-    uint8_t h0[FELICS_HEADER_BYTES] = {0};
-    const size_t hl = (size_t)std::min<uint64_t>(lens[0], FELICS_HEADER_BYTES);
-    if (hl) HIP_TRY(ctx, hipMemcpy(h0, (const uint8_t *)d_streams + offsets[0], hl, hipMemcpyDeviceToHost));
-    const int rc = felics_read_header(h0, hl, &hdr);
-    if (rc) return fail_call(n, status, nullptr, nullptr, rc);
-    if (hdr_out) *hdr_out = hdr;
-    if (hdr.pixel_depth != FELICS_DEPTH_8) return fail_call(n, status, nullptr, nullptr, FELICS_E_UNSUPPORTED);  // 16-bit streams have no index
-    if ((uint64_t)hdr.width * hdr.height > 0xFFFFFFFFull) return fail_call(n, status, nullptr, nullptr, FELICS_E_INVALID_DIMENSIONS);
-    return FELICS_OK;
-}
-
-// Whether the wave kernels can hold a row of that shape, then how every index is cut: header of index 0 (L, seg), which must fit
-// stream 0 and the stride.
-int indexed_index_shape(felics_ctx *ctx, const felics_header &hdr, uint64_t len0, const void *d_index, size_t index_stride, IndexLayout &L,
-                        uint32_t &seg, size_t n, int *status) {
-    if (decode8_lds_bytes(hdr.width, hdr.color_type) > DECODE_LDS_LIMIT) return fail_call(n, status, nullptr, nullptr, FELICS_E_UNSUPPORTED);  // no host fallback here
-    if (index_stride < INDEX_HEADER_BYTES) return fail_call(n, status, nullptr, nullptr, FELICS_E_INVALID_INDEX);
-    uint8_t ih[INDEX_HEADER_BYTES];
-    HIP_TRY(ctx, hipMemcpy(ih, d_index, INDEX_HEADER_BYTES, hipMemcpyDeviceToHost));
-    if (index_header_check(ih, hdr.color_type, hdr.width, hdr.height, len0, L) != FELICS_OK || L.total > index_stride)
-        return fail_call(n, status, nullptr, nullptr, FELICS_E_INVALID_INDEX);
-    seg = idx_rd32(ih + IDX_SEGPIX);
-    return FELICS_OK;
-}
-
-// ---- what the two indexed calls for 16-bit streams (felics_decompress_batch_device_indexed16, felics_decompress_regions_device_indexed16)
-// open with ----
-// d_index and every idx_offsets[i] a multiple of 64: the kernels load a state row as one aligned 64-byte line
-bool index16_aligned(const void *d_index, const uint64_t *idx_offsets, size_t n) {
-    if ((uintptr_t)d_index & 63u) return false;
+int first_error(const int *status, size_t n) {
     for (size_t i = 0; i < n; i++)
-        if (idx_offsets[i] & 63u) return false;
-    return true;
-}
-
-// The shape every stream must have (header of stream 0: 16-bit, w * h < 2^32, a row the kernels' LDS holds), then own(hdr) -- the
-// checks of the call's own output, made before the index is looked at --, then how every index is cut (header of index 0: L, seg),
-// which must fit stream 0 and its own length.  (One index header, as the 8-bit calls read one; the streams' own headers are the
-// kernels' to check.)  FELICS_OK, or the code the call puts into every status and returns; FELICS_E_HIP leaves status alone.
-template <typename Own>
-int indexed16_open(felics_ctx *ctx, const void *d_streams, const uint64_t *offsets, const uint64_t *lens, const void *d_index,
-                   const uint64_t *idx_offsets, const uint64_t *idx_lens, felics_header &hdr, felics_header *hdr_out, Index16Layout &L, uint32_t &seg,
-                   Own own) {
-    uint8_t h0[FELICS_HEADER_BYTES] = {0};
-    const size_t hl = (size_t)std::min<uint64_t>(lens[0], FELICS_HEADER_BYTES);
-    if (hl) HIP_TRY(ctx, hipMemcpy(h0, (const uint8_t *)d_streams + offsets[0], hl, hipMemcpyDeviceToHost));
-    int rc = felics_read_header(h0, hl, &hdr);
-    if (rc) return rc;
-    if (hdr_out) *hdr_out = hdr;
-    if (hdr.pixel_depth != FELICS_DEPTH_16) return FELICS_E_UNSUPPORTED;  // 8-bit streams: the calls without "16"
-    if ((uint64_t)hdr.width * hdr.height > 0xFFFFFFFFull) return FELICS_E_INVALID_DIMENSIONS;
-    if (decode16_lds_bytes(hdr.width) > DECODE_LDS_LIMIT) return FELICS_E_UNSUPPORTED;  // no host fallback here
-    if ((rc = own(hdr)) != 0) return rc;
-    if (idx_lens[0] < INDEX_HEADER_BYTES) return FELICS_E_INVALID_INDEX;
-    uint8_t ih[INDEX_HEADER_BYTES];
-    HIP_TRY(ctx, hipMemcpy(ih, (const uint8_t *)d_index + idx_offsets[0], INDEX_HEADER_BYTES, hipMemcpyDeviceToHost));
-    if (index16_header_check(ih, hdr.color_type, hdr.width, hdr.height, lens[0], idx_lens[0], L) != FELICS_OK) return FELICS_E_INVALID_INDEX;
-    seg = idx_rd32(ih + IDX_SEGPIX);
+        if (status[i]) return status[i];
     return FELICS_OK;
 }
 
-// FELICS_TEST_INDEX16_PASS=k: at most k waves in a pass of those two calls (tests)
+// FELICS_TEST_INDEX16_PASS=k: at most k waves in a pass of the 16-bit calls (tests)
 uint64_t index16_pass_cap(uint64_t items) {
     if (const char *e = getenv("FELICS_TEST_INDEX16_PASS"))
         if (atoll(e) > 0) return std::min<uint64_t>(items, (uint64_t)atoll(e));
@@ -765,91 +708,401 @@ uint64_t index_views_pass_cap() {
     return e && atoll(e) > 0 ? (uint64_t)atoll(e) : UINT64_MAX;
 }
 
-// What the two indexed views calls differ in: a form names the sample depth it takes, the LDS a row asks for, the check of an index
-// header, the type of an RGB plane sample, and how a launch of one LDS class, a stream pass's tail and the call's counters are made.
-// Everything else -- the header round trip, the classification, the passes over the plane scratch, the tables, the status hand-back --
-// is decompress_views_indexed below.
-
-// felics_decompress_views_device_indexed: 8-bit streams, version-1 indexes, k_decode8_seg_views.  A launch holds any number of items
-// and needs nothing beside its tables.
-struct IndexViews8 {
+// 8-bit streams, version-1 indexes.  A launch holds any number of items and needs nothing beside the call's tables.
+struct Depth8 {
     using Layout = IndexLayout;
-    using Plane = int16_t;
-    using Stats = felics_index_view_stats;
+    using Pixel = uint8_t;
+    using Plane = int16_t;  // an RGB plane's sample
     static constexpr int DEPTH = FELICS_DEPTH_8;
     static constexpr uintptr_t INDEX_ALIGN = 16;  // of every index address: the kernel loads a checkpoint as aligned words
-    static constexpr size_t EXTRA = 0;            // bytes behind the status words
-    static Stats &stats(felics_ctx *ctx) { return ctx->ivstats; }
-    static uint32_t lds_bytes(const DecodeHeader &h) { return decode8_lds_bytes(h.W, h.color); }
-    static bool lds_ok(const DecodeHeader &h) { return index_lds_bytes(h.W, h.color) <= DECODE_LDS_LIMIT; }
-    static bool index_ok(const uint8_t *ih, const DecodeHeader &h, uint64_t len, uint64_t idx_len, Layout &L) {
-        return index_header_check(ih, h.color, h.W, h.H, len, L) == FELICS_OK && L.total == idx_len;
+    static constexpr size_t EXTRA = 0;            // bytes the form keeps on the device beside the status words
+    static constexpr bool OWN_BEFORE_LDS = true;  // the opening's order: the call's own output checks, then the LDS bound
+    static uint32_t lds_bytes(uint32_t W, uint32_t color) { return decode8_lds_bytes(W, color); }
+    static bool lds_ok(uint32_t W, uint32_t color) { return index_lds_bytes(W, color) <= DECODE_LDS_LIMIT; }
+    // an index header against its stream's header and length; the index fits the idx_len bytes it was given
+    static bool index_ok(const uint8_t *ih, uint32_t color, uint32_t W, uint32_t H, uint64_t len, uint64_t idx_len, Layout &L) {
+        return index_header_check(ih, color, W, H, len, L) == FELICS_OK && L.total <= idx_len;
     }
     int tables(felics_ctx *, size_t) { return FELICS_OK; }
     size_t launches_of(size_t) const { return 1; }
     int begin(felics_ctx *, hipStream_t, void *) { return FELICS_OK; }
-    int launch(felics_ctx *ctx, hipStream_t s, const uint8_t *st, const uint64_t *d_off, const uint64_t *d_len, const uint8_t *ix, const uint64_t *,
-               const IndexViewRow *d_rows, const IndexViewItem *d_items, size_t cnt, uint32_t lds, Plane *d_planes, int *d_item_status) {
-        HIP_TRY(ctx, launch_decode8_seg_views(s, st, d_off, d_len, ix, d_rows, d_items, (uint32_t)cnt, lds, d_planes, d_item_status));
-        return FELICS_OK;
-    }
-    static hipError_t finish(hipStream_t s, uint32_t n, const RegionRow *regions, const int *item_status, const DecodeRow *conv, const ViewRow *views,
-                             uint64_t max_npix, Plane *planes, int *status) {
-        return launch_seg_views_finish(s, n, regions, item_status, conv, views, max_npix, planes, status);
-    }
     int end(felics_ctx *, hipStream_t) { return FELICS_OK; }
-    void done(felics_ctx *) {}
 };
 
-// felics_decompress_views_device_indexed16: 16-bit streams, version-2 indexes, k_decode16_seg_views.  Every wave of a launch owns a
-// dense estimator table in dec_table, so a launch holds at most `per` items (dec16_tables' bound, FELICS_TEST_INDEX16_PASS) and takes
-// a fresh epoch; a class's items are cut into such launches wherever the cut falls -- inside a stream, inside a plane: an item
-// needs its own table and nothing of its neighbours'.  Behind the status words lies the rows-loaded counter.
-struct IndexViews16 {
+// 16-bit streams, version-2 indexes.  Every wave of a launch owns a dense estimator table in dec_table, so a launch holds at most
+// `per` items (dec16_tables' bound, FELICS_TEST_INDEX16_PASS) and takes a fresh epoch: the items of a call or of an LDS class are cut
+// into such passes wherever the cut falls -- inside a stream, a region or a plane: an item needs its own table and nothing of its
+// neighbours'.  Behind the status words lies the rows-loaded counter.
+struct Depth16 {
     using Layout = Index16Layout;
+    using Pixel = uint16_t;
     using Plane = int32_t;
-    using Stats = felics_index16_view_stats;
     static constexpr int DEPTH = FELICS_DEPTH_16;
     static constexpr uintptr_t INDEX_ALIGN = 64;  // the kernel loads a state row as one aligned 64-byte line
     static constexpr size_t EXTRA = 8;
+    static constexpr bool OWN_BEFORE_LDS = false;  // the LDS bound first
     size_t per = 1;
     unsigned long long *d_loaded = nullptr, loaded = 0;
-    static Stats &stats(felics_ctx *ctx) { return ctx->iv16stats; }
-    static uint32_t lds_bytes(const DecodeHeader &h) { return decode16_lds_bytes(h.W); }
-    static bool lds_ok(const DecodeHeader &h) { return decode16_lds_bytes(h.W) <= DECODE_LDS_LIMIT; }
-    static bool index_ok(const uint8_t *ih, const DecodeHeader &h, uint64_t len, uint64_t idx_len, Layout &L) {
-        return index16_header_check(ih, h.color, h.W, h.H, len, idx_len, L) == FELICS_OK;  // (total_bytes = idx_len is one of its checks)
+    static uint32_t lds_bytes(uint32_t W, uint32_t) { return decode16_lds_bytes(W); }
+    static bool lds_ok(uint32_t W, uint32_t) { return decode16_lds_bytes(W) <= DECODE_LDS_LIMIT; }
+    static bool index_ok(const uint8_t *ih, uint32_t color, uint32_t W, uint32_t H, uint64_t len, uint64_t idx_len, Layout &L) {
+        return index16_header_check(ih, color, W, H, len, idx_len, L) == FELICS_OK;  // (total_bytes = idx_len is one of its checks)
     }
-    int tables(felics_ctx *ctx, size_t most_items) {  // most_items >= 1: the largest class of a pass
-        const int rc = dec16_tables(ctx, (size_t)index16_pass_cap(most_items), per);
-        if (!rc) stats(ctx).table_bytes = decode16_table_bytes((uint32_t)per);
-        return rc;
-    }
+    int tables(felics_ctx *ctx, size_t most_items) { return dec16_tables(ctx, (size_t)index16_pass_cap(most_items), per); }  // most_items >= 1
+    size_t table_bytes() const { return decode16_table_bytes((uint32_t)per); }
     size_t launches_of(size_t cnt) const { return (cnt + per - 1) / per; }
     int begin(felics_ctx *ctx, hipStream_t s, void *extra) {
         d_loaded = (unsigned long long *)extra;
         HIP_TRY(ctx, hipMemsetAsync(d_loaded, 0, 8, s));
         return FELICS_OK;
     }
-    int launch(felics_ctx *ctx, hipStream_t s, const uint8_t *st, const uint64_t *d_off, const uint64_t *d_len, const uint8_t *ix,
-               const uint64_t *d_ilen, const IndexViewRow *d_rows, const IndexViewItem *d_items, size_t cnt, uint32_t lds, Plane *d_planes,
-               int *d_item_status) {
-        for (size_t o = 0; o < cnt; o += per) {  // behind one another on the one stream: the launches share the tables
+    // launch(first item, items, tables, epoch) for every pass of n items, behind one another on the one stream: the passes share the tables
+    template <typename Launch>
+    int passes(felics_ctx *ctx, hipStream_t s, size_t n, Launch launch) {
+        for (size_t o = 0; o < n; o += per) {
             uint32_t epoch = 0;
             const int rc = dec16_epoch(ctx, s, epoch);
             if (rc) return rc;
-            HIP_TRY(ctx, launch_decode16_seg_views(s, st, d_off, d_len, ix, d_ilen, d_rows, d_items + o, (uint32_t)std::min(per, cnt - o), lds, d_planes,
-                                                   (uint32_t *)ctx->dec_table.p, epoch, d_item_status + o, d_loaded));
+            HIP_TRY(ctx, launch(o, std::min(per, n - o), (uint32_t *)ctx->dec_table.p, epoch));
         }
         return FELICS_OK;
-    }
-    static hipError_t finish(hipStream_t s, uint32_t n, const RegionRow *regions, const int *item_status, const DecodeRow *conv, const ViewRow *views,
-                             uint64_t max_npix, Plane *planes, int *status) {
-        return launch_seg16_views_finish(s, n, regions, item_status, conv, views, max_npix, planes, status);
     }
     int end(felics_ctx *ctx, hipStream_t s) {
         HIP_TRY(ctx, hipMemcpyAsync(&loaded, d_loaded, 8, hipMemcpyDeviceToHost, s));
         return FELICS_OK;
+    }
+};
+
+// What a same-shape call hands its launches: the streams of shape `hdr`, their indexes cut in segments of `seg` pixels, K to a plane.
+struct SameShape {
+    const uint8_t *streams;
+    const uint64_t *d_off, *d_len;
+    felics_header hdr;
+    uint32_t seg, K;
+    void *pixels, *planes;
+    int *item_status, *status;  // a word per item; per stream or region
+};
+
+// The same-shape kinds at 8 bits: index i lies at index + i * stride.  The dense call's lane form is this form's own business:
+// felics.h "Restart index: 64 segments per wave".
+struct IndexSame8 : Depth8 {
+    const uint8_t *index;
+    uint64_t stride;
+    static constexpr size_t ARRAYS = 2;  // u64 arrays of the call on the device: offsets | lens
+    size_t n64 = 0;                      // dense: the first n64 streams take the lane form, in passes of pass_waves of their `waves` waves
+    uint64_t waves = 0, pass_waves = 0;
+    bool given() const { return index != nullptr; }
+    bool aligned(size_t) const { return (((uintptr_t)index | stride) & (INDEX_ALIGN - 1u)) == 0; }
+    const uint8_t *index0() const { return index; }
+    uint64_t len0() const { return stride; }
+    int upload(felics_ctx *, hipStream_t, uint64_t *, size_t) { return FELICS_OK; }
+    static felics_region_stats &region_stats(felics_ctx *ctx) { return ctx->rstats; }
+
+    // Which form (felics.h): the first n64 streams 64 segments to a wave, the others a wave per segment beside them; the lane form's
+    // passes: whole waves, within the table memory index_lanes_tables grants
+    int plan_dense(felics_ctx *ctx, size_t n, const felics_header &hdr, uint32_t K) {
+        const uint32_t planes = hdr.color_type == FELICS_COLOR_RGB ? 3 : 1;
+        if (hdr.width >= 8 && K >= 1 && n >= 64) {
+            const uint64_t items = (uint64_t)(n / 64 * 64) * planes * K;
+            const uint32_t least = felics_index_lanes_min_items(hdr.color_type);
+            bool by_lane = least != INDEX8_LANES_NEVER && items >= least;
+            if (const char *e = getenv("FELICS_TEST_INDEX_LANES")) by_lane = atoi(e) != 0;
+            if (by_lane) n64 = n / 64 * 64;
+        }
+        waves = (uint64_t)(n64 / 64) * planes * K;
+        if (waves) {
+            const size_t wave_bytes = index8_lanes_table_bytes(64, hdr.color_type);
+            size_t tbytes = 0;
+            const int rc = index_lanes_tables(ctx, (size_t)std::min<uint64_t>(waves, index_lanes_pass_cap() / 64) * wave_bytes, wave_bytes, tbytes);
+            if (rc) return rc;
+            pass_waves = std::min<uint64_t>(waves, tbytes / wave_bytes);
+        }
+        ctx->istats.streams += n;
+        ctx->istats.lane_segments8 += waves * 64;
+        ctx->istats.segments8 += (n - n64) * planes * K;
+        return FELICS_OK;
+    }
+    int dense(felics_ctx *ctx, hipStream_t s, const SameShape &d, size_t n) {
+        const uint32_t W = d.hdr.width, H = d.hdr.height, color = d.hdr.color_type;
+        const uint64_t npix = (uint64_t)W * H, per = (color ? 3u : 1u) * std::max(d.K, 1u), frame = npix * (color ? 3u : 1u);
+        Pixel *pixels = (Pixel *)d.pixels;
+        Plane *planes = (Plane *)d.planes;
+        Lane &l = ctx->lanes[0];
+        const bool beside = n64 && n64 < n;  // the wave form's streams run on the lane's front stream, between two events
+        hipStream_t s2 = beside ? l.front : s;
+        if (beside) {
+            HIP_TRY(ctx, hipEventRecord(l.slice_done[0], s));
+            HIP_TRY(ctx, hipStreamWaitEvent(s2, l.slice_done[0], 0));
+        }
+        // (the kernel is handed the pointers of stream n64 on and knows nothing of the streams in front)
+        HIP_TRY(ctx, launch_decode8_seg(s2, d.streams, d.d_off + n64, d.d_len + n64, index + n64 * stride, stride, (uint32_t)(n - n64), W, H, color, d.seg,
+                                        d.K, pixels + n64 * frame, planes ? planes + n64 * 3 * npix : nullptr, d.item_status + n64 * per, d.status + n64));
+        for (uint64_t w0 = 0; w0 < waves; w0 += pass_waves) {  // behind one another: they share the tables
+            HIP_TRY(ctx, launch_decode8_seg_lanes(s, d.streams, d.d_off, d.d_len, index, stride, W, H, color, d.seg, d.K, (uint32_t)w0,
+                                                  (uint32_t)std::min(pass_waves, waves - w0), pixels, planes, (uint32_t *)ctx->dec_lane_table.p,
+                                                  d.item_status));
+            ctx->istats.lane_passes++;
+        }
+        HIP_TRY(ctx, launch_seg_finish(s, (uint32_t)n64, W, H, color, d.K, pixels, planes, d.item_status, d.status));
+        if (beside) {
+            HIP_TRY(ctx, hipEventRecord(l.spine_done[0], s2));
+            HIP_TRY(ctx, hipStreamWaitEvent(s, l.spine_done[0], 0));
+        }
+        return FELICS_OK;
+    }
+    void done_dense(felics_ctx *) {}
+    int regions(felics_ctx *ctx, hipStream_t s, const SameShape &d, const RegionRow *d_rows, const RegionItem *d_items, size_t n_items) {
+        HIP_TRY(ctx, launch_decode8_regions(s, d.streams, d.d_off, d.d_len, index, stride, d.hdr.width, d.hdr.height, d.hdr.color_type, d.seg, d.K, d_rows,
+                                            d_items, (uint32_t)n_items, (Pixel *)d.pixels, (Plane *)d.planes, d.item_status));
+        return FELICS_OK;
+    }
+    void done_regions(felics_ctx *) {}
+};
+
+// The same-shape kinds at 16 bits: index i lies at index + offs[i] and is lens[i] bytes long; both arrays go to the device behind the
+// streams'.
+struct IndexSame16 : Depth16 {
+    const uint8_t *index;
+    const uint64_t *offs, *lens;
+    static constexpr size_t ARRAYS = 4;  // offsets | lens | index offsets | index lens
+    const uint64_t *d_ioff = nullptr, *d_ilen = nullptr;
+    bool given() const { return index && offs && lens; }
+    bool aligned(size_t n) const {  // every index address
+        if ((uintptr_t)index & (INDEX_ALIGN - 1u)) return false;
+        for (size_t i = 0; i < n; i++)
+            if (offs[i] & (INDEX_ALIGN - 1u)) return false;
+        return true;
+    }
+    const uint8_t *index0() const { return index + offs[0]; }
+    uint64_t len0() const { return lens[0]; }
+    int upload(felics_ctx *ctx, hipStream_t s, uint64_t *d_ix, size_t n) {
+        HIP_TRY(ctx, hipMemcpyAsync(d_ix, offs, n * 8, hipMemcpyHostToDevice, s));
+        HIP_TRY(ctx, hipMemcpyAsync(d_ix + n, lens, n * 8, hipMemcpyHostToDevice, s));
+        d_ioff = d_ix, d_ilen = d_ix + n;
+        return FELICS_OK;
+    }
+    static felics_region16_stats &region_stats(felics_ctx *ctx) { return ctx->r16stats; }
+
+    int plan_dense(felics_ctx *ctx, size_t n, const felics_header &hdr, uint32_t K) {
+        ctx->i16stats.streams += n;
+        ctx->i16stats.segments16 += n * (hdr.color_type == FELICS_COLOR_RGB ? 3 : 1) * std::max(K, 1u);
+        ctx->i16stats.table_bytes = table_bytes();
+        return FELICS_OK;
+    }
+    int dense(felics_ctx *ctx, hipStream_t s, const SameShape &d, size_t n) {
+        const uint32_t W = d.hdr.width, H = d.hdr.height, color = d.hdr.color_type;
+        const int rc = passes(ctx, s, n * (color ? 3u : 1u) * std::max(d.K, 1u), [&](size_t o, size_t cnt, uint32_t *table, uint32_t epoch) {
+            ctx->i16stats.passes++;
+            return launch_decode16_seg(s, d.streams, d.d_off, d.d_len, index, d_ioff, d_ilen, W, H, color, d.seg, d.K, (uint32_t)o, (uint32_t)cnt,
+                                       (Pixel *)d.pixels, (Plane *)d.planes, table, epoch, d.item_status, d_loaded);
+        });
+        if (rc) return rc;
+        HIP_TRY(ctx, launch_seg_finish(s, (uint32_t)n, W, H, color, d.K, (Pixel *)d.pixels, (Plane *)d.planes, d.item_status, d.status));
+        return FELICS_OK;
+    }
+    void done_dense(felics_ctx *ctx) { ctx->i16stats.rows_loaded += loaded; }
+    int regions(felics_ctx *ctx, hipStream_t s, const SameShape &d, const RegionRow *d_rows, const RegionItem *d_items, size_t n_items) {
+        return passes(ctx, s, n_items, [&](size_t o, size_t cnt, uint32_t *table, uint32_t epoch) {  // (a pass boundary may fall inside a region)
+            ctx->r16stats.passes++;
+            return launch_decode16_regions(s, d.streams, d.d_off, d.d_len, index, d_ioff, d_ilen, d.hdr.width, d.hdr.height, d.hdr.color_type, d.seg, d.K,
+                                           d_rows, d_items, (uint32_t)o, (uint32_t)cnt, (uint8_t *)d.pixels, (Plane *)d.planes, table, epoch,
+                                           d.item_status, d_loaded);
+        });
+    }
+    void done_regions(felics_ctx *ctx) { ctx->r16stats.rows_loaded += loaded; }
+};
+
+// What every same-shape indexed call opens with: the shape every stream must have (header of stream 0: the form's depth, w * h < 2^32,
+// a row the kernels' LDS holds -- there is no host fallback here), own(hdr) -- the checks of the call's own output --, then how every
+// index is cut (header of index 0: L, seg), which must fit stream 0 and the bytes it was given.  (One index header; the streams' own
+// headers are the kernels' to check.)  FELICS_OK, or the code the caller puts into every status and returns; FELICS_E_HIP leaves
+// status alone.  The order of the codes is felics.h's, per depth: Form::OWN_BEFORE_LDS.
+template <typename Form, typename Own>
+int indexed_open(felics_ctx *ctx, const void *d_streams, const uint64_t *offsets, const uint64_t *lens, const Form &form, felics_header &hdr,
+                 felics_header *hdr_out, typename Form::Layout &L, uint32_t &seg, Own own) {
+    uint8_t h0[FELICS_HEADER_BYTES] = {0};
+    const size_t hl = (size_t)std::min<uint64_t>(lens[0], FELICS_HEADER_BYTES);
+    if (hl) HIP_TRY(ctx, hipMemcpy(h0, (const uint8_t *)d_streams + offsets[0], hl, hipMemcpyDeviceToHost));
+    int rc = felics_read_header(h0, hl, &hdr);
+    if (rc) return rc;  // stream 0 names the shape: without it nothing is decoded
+    if (hdr_out) *hdr_out = hdr;
+    if (hdr.pixel_depth != Form::DEPTH) return FELICS_E_UNSUPPORTED;  // the other depth has a format and calls of its own
+    if ((uint64_t)hdr.width * hdr.height > 0xFFFFFFFFull) return FELICS_E_INVALID_DIMENSIONS;
+    const int lds = Form::lds_ok(hdr.width, hdr.color_type) ? FELICS_OK : FELICS_E_UNSUPPORTED;
+    if (!Form::OWN_BEFORE_LDS && lds) return lds;
+    if ((rc = own(hdr)) != 0) return rc;
+    if (lds) return lds;
+    if (form.len0() < INDEX_HEADER_BYTES) return FELICS_E_INVALID_INDEX;
+    uint8_t ih[INDEX_HEADER_BYTES];
+    HIP_TRY(ctx, hipMemcpy(ih, form.index0(), INDEX_HEADER_BYTES, hipMemcpyDeviceToHost));
+    if (!Form::index_ok(ih, hdr.color_type, hdr.width, hdr.height, lens[0], form.len0(), L)) return FELICS_E_INVALID_INDEX;
+    seg = idx_rd32(ih + IDX_SEGPIX);
+    return FELICS_OK;
+}
+
+// felics_decompress_batch_device_indexed and _indexed16 (felics.h "Restart index", "Restart index: 16-bit streams"): n streams of one
+// shape, every (stream, plane, segment) an item with a status word of its own.  The alignment rule and a pending batch return without
+// touching status.
+template <typename Form>
+int dense_indexed(felics_ctx *ctx, size_t n, const void *d_streams, const uint64_t *offsets, const uint64_t *lens, void *d_pixels, size_t d_pixels_cap,
+                  felics_header *hdr_out, int *status, Form form) {
+    using Pixel = typename Form::Pixel;
+    using Plane = typename Form::Plane;
+    if (!ctx || (n && (!d_streams || !offsets || !lens || !form.given() || !status))) return FELICS_E_INVALID_ARGUMENT;
+    if (ctx->failed) return FELICS_E_HIP;
+    if (n == 0) return FELICS_OK;
+    if (any_pending(ctx)) return FELICS_E_INVALID_ARGUMENT;  // felics_wait_batch first
+    if (!form.aligned(n)) return FELICS_E_INVALID_ARGUMENT;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    auto fail_all = [&](int code) { return fail_call(n, status, nullptr, nullptr, code); };
+    // the opening checks; this call's own: the frames must fit
+    felics_header hdr;
+    typename Form::Layout L;
+    uint32_t seg = 0;
+    int rc = indexed_open(ctx, d_streams, offsets, lens, form, hdr, hdr_out, L, seg, [&](const felics_header &h) {
+        const uint64_t bytes = (uint64_t)h.width * h.height * (h.color_type == FELICS_COLOR_RGB ? 3 : 1) * sizeof(Pixel);
+        if (bytes * n > d_pixels_cap) return (int)FELICS_E_BUFFER_TOO_SMALL;
+        return bytes && !d_pixels ? (int)FELICS_E_INVALID_ARGUMENT : (int)FELICS_OK;
+    });
+    if (rc) return rc == FELICS_E_HIP ? rc : fail_all(rc);
+    const uint32_t planes = hdr.color_type == FELICS_COLOR_RGB ? 3 : 1;
+    const uint64_t npix = (uint64_t)hdr.width * hdr.height;
+    const uint64_t per = (uint64_t)planes * std::max(L.K, 1u);
+    if (n > 0x7FFFFFFFull / per) return fail_all(FELICS_E_UNSUPPORTED);  // one block and one status word per segment, 32-bit item numbers
+    const size_t items = (size_t)(n * per);
+    if ((rc = form.tables(ctx, items)) != 0) return fail_all(rc);
+    // the form's arrays | what it keeps | status on the device; a word per segment beside them
+    if ((rc = reserve(ctx, ctx->dec_meta, n * 8 * Form::ARRAYS + Form::EXTRA + n * 4)) != 0) return fail_all(rc);
+    if ((rc = reserve(ctx, ctx->dec_seg_status, items * 4)) != 0) return fail_all(rc);
+    if (planes == 3 && (rc = reserve(ctx, ctx->dec_planes, (size_t)(npix * 3 * sizeof(Plane) * n) + 64)) != 0) return fail_all(rc);
+    if ((rc = form.plan_dense(ctx, n, hdr, L.K)) != 0) return fail_all(rc);
+    uint64_t *d_off = (uint64_t *)ctx->dec_meta.p, *d_len = d_off + n;
+    uint8_t *extra = (uint8_t *)(d_off + n * Form::ARRAYS);
+    int *d_status = (int *)(extra + Form::EXTRA);
+    const SameShape d{(const uint8_t *)d_streams, d_off, d_len, hdr, seg, L.K, d_pixels, planes == 3 ? ctx->dec_planes.p : nullptr,
+                      (int *)ctx->dec_seg_status.p, d_status};
+    hipStream_t s = ctx->lanes[0].stream;
+    for (size_t i = 0; i < n; i++) status[i] = FELICS_E_HIP;  // until the kernel's own word arrives
+    HIP_TRY(ctx, hipMemcpyAsync(d_off, offsets, n * 8, hipMemcpyHostToDevice, s));
+    HIP_TRY(ctx, hipMemcpyAsync(d_len, lens, n * 8, hipMemcpyHostToDevice, s));
+    if ((rc = form.upload(ctx, s, d_len + n, n)) != 0) return rc;
+    if ((rc = form.begin(ctx, s, extra)) != 0) return rc;
+    HIP_TRY(ctx, hipMemsetAsync(d_status, 0xFF, n * 4, s));
+    HIP_TRY(ctx, hipMemsetAsync(d.item_status, 0xFF, items * 4, s));
+    if ((rc = form.dense(ctx, s, d, n)) != 0) return rc;
+    HIP_TRY(ctx, hipMemcpyAsync(status, d_status, n * 4, hipMemcpyDeviceToHost, s));
+    if ((rc = form.end(ctx, s)) != 0) return rc;
+    HIP_TRY(ctx, hipStreamSynchronize(s));
+    form.done_dense(ctx);
+    return first_error(status, n);
+}
+
+// felics_decompress_regions_device_indexed and _indexed16 (felics.h "Restart index: regions", "... of 16-bit streams"): the plan
+// (felics_index.h: region_plan) names the items, a wave each; crops are dense and back to back.
+template <typename Form>
+int regions_indexed(felics_ctx *ctx, size_t n_streams, const void *d_streams, const uint64_t *offsets, const uint64_t *lens, size_t n_regions,
+                    const felics_region *regions, void *d_pixels, size_t d_pixels_cap, uint64_t *out_offsets, felics_header *hdr_out, int *status,
+                    Form form) {
+    using Pixel = typename Form::Pixel;
+    using Plane = typename Form::Plane;
+    if (!ctx || (n_streams && (!d_streams || !offsets || !lens || !form.given())) || (n_regions && (!regions || !status)))
+        return FELICS_E_INVALID_ARGUMENT;
+    if (ctx->failed) return FELICS_E_HIP;
+    if (n_regions == 0) return FELICS_OK;
+    auto fail_all = [&](int code) { return fail_call(n_regions, status, nullptr, nullptr, code); };
+    if (any_pending(ctx)) return fail_all(FELICS_E_INVALID_ARGUMENT);  // felics_wait_batch first
+    if (n_streams == 0 || n_streams > 0xFFFFFFFFull || n_regions > 0x7FFFFFFFull) return fail_all(FELICS_E_INVALID_ARGUMENT);
+    if (!form.aligned(n_streams) || ((uintptr_t)d_pixels & (sizeof(Pixel) - 1u))) return fail_all(FELICS_E_INVALID_ARGUMENT);
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    // the opening checks; this call's own: the requests inside the image, of a stream of the call; the crops, back to back, must fit
+    felics_header hdr;
+    typename Form::Layout L;
+    uint32_t seg = 0;
+    int rc = indexed_open(ctx, d_streams, offsets, lens, form, hdr, hdr_out, L, seg, [&](const felics_header &h) {
+        for (size_t r = 0; r < n_regions; r++)
+            if (regions[r].stream >= n_streams || !region_inside(h.width, h.height, regions[r])) return (int)FELICS_E_INVALID_ARGUMENT;
+        const uint64_t pixel_bytes = (h.color_type == FELICS_COLOR_RGB ? 3 : 1) * sizeof(Pixel);
+        uint64_t total = 0;
+        for (size_t r = 0; r < n_regions; r++) {
+            total += (uint64_t)regions[r].w * regions[r].h * pixel_bytes;  // (a crop has < 6 * 2^32 bytes: the sum is looked at before it can wrap)
+            if (total > d_pixels_cap) return (int)FELICS_E_BUFFER_TOO_SMALL;
+        }
+        return total && !d_pixels ? (int)FELICS_E_INVALID_ARGUMENT : (int)FELICS_OK;
+    });
+    if (rc) return rc == FELICS_E_HIP ? rc : fail_all(rc);
+    const uint32_t planes = hdr.color_type == FELICS_COLOR_RGB ? 3 : 1;
+    RegionPlan P;
+    if ((rc = region_plan(hdr.width, hdr.height, seg, planes, sizeof(Pixel), regions, n_regions, out_offsets, P)) != 0) return fail_all(rc);
+    const size_t n_items = P.items.size();
+    if ((rc = form.tables(ctx, n_items)) != 0) return fail_all(rc);
+    // the form's arrays | what it keeps | status on the device; the region table and the work list; a word per item
+    if ((rc = reserve(ctx, ctx->dec_meta, n_streams * 8 * Form::ARRAYS + Form::EXTRA + n_regions * 4)) != 0) return fail_all(rc);
+    if ((rc = reserve(ctx, ctx->dec_region_work, n_regions * sizeof(RegionRow) + n_items * sizeof(RegionItem))) != 0) return fail_all(rc);
+    if ((rc = reserve(ctx, ctx->dec_seg_status, n_items * 4)) != 0) return fail_all(rc);
+    if (planes == 3 && (rc = reserve(ctx, ctx->dec_planes, (size_t)(P.plane_samples * sizeof(Plane)) + 64)) != 0) return fail_all(rc);  // crop-sized
+    uint64_t *d_off = (uint64_t *)ctx->dec_meta.p, *d_len = d_off + n_streams;
+    uint8_t *extra = (uint8_t *)(d_off + n_streams * Form::ARRAYS);
+    int *d_status = (int *)(extra + Form::EXTRA);
+    RegionRow *d_rows = (RegionRow *)ctx->dec_region_work.p;
+    RegionItem *d_items = (RegionItem *)(d_rows + n_regions);
+    const SameShape d{(const uint8_t *)d_streams, d_off, d_len, hdr, seg, L.K, d_pixels, planes == 3 ? ctx->dec_planes.p : nullptr,
+                      (int *)ctx->dec_seg_status.p, d_status};
+    auto &rs = Form::region_stats(ctx);
+    rs.regions += n_regions;
+    rs.segments_walked += P.walked;
+    rs.segments_skipped += P.skipped;
+    rs.pixels_walked += P.pixels_walked;
+    hipStream_t s = ctx->lanes[0].stream;
+    for (size_t i = 0; i < n_regions; i++) status[i] = FELICS_E_HIP;  // until the kernel's own word arrives
+    HIP_TRY(ctx, hipMemcpyAsync(d_off, offsets, n_streams * 8, hipMemcpyHostToDevice, s));
+    HIP_TRY(ctx, hipMemcpyAsync(d_len, lens, n_streams * 8, hipMemcpyHostToDevice, s));
+    if ((rc = form.upload(ctx, s, d_len + n_streams, n_streams)) != 0) return rc;
+    HIP_TRY(ctx, hipMemcpyAsync(d_rows, P.rows.data(), n_regions * sizeof(RegionRow), hipMemcpyHostToDevice, s));
+    HIP_TRY(ctx, hipMemcpyAsync(d_items, P.items.data(), n_items * sizeof(RegionItem), hipMemcpyHostToDevice, s));
+    if ((rc = form.begin(ctx, s, extra)) != 0) return rc;
+    HIP_TRY(ctx, hipMemsetAsync(d_status, 0xFF, n_regions * 4, s));
+    HIP_TRY(ctx, hipMemsetAsync(d.item_status, 0xFF, n_items * 4, s));
+    if ((rc = form.regions(ctx, s, d, d_rows, d_items, n_items)) != 0) return rc;
+    HIP_TRY(ctx, launch_regions_finish(s, d_rows, (uint32_t)n_regions, P.max_crop, (Pixel *)d_pixels, (Plane *)d.planes, d.item_status, d_status));
+    HIP_TRY(ctx, hipMemcpyAsync(status, d_status, n_regions * 4, hipMemcpyDeviceToHost, s));
+    if ((rc = form.end(ctx, s)) != 0) return rc;
+    HIP_TRY(ctx, hipStreamSynchronize(s));  // (the plan lives until here)
+    form.done_regions(ctx);
+    return first_error(status, n_regions);
+}
+
+// The views kind: the streams have shapes of their own, so every index is addressed by its offset and length, at both depths.
+// felics_decompress_views_device_indexed: k_decode8_seg_views; an index is exactly as long as its layout says.
+struct IndexViews8 : Depth8 {
+    using Stats = felics_index_view_stats;
+    static Stats &stats(felics_ctx *ctx) { return ctx->ivstats; }
+    static bool index_ok(const uint8_t *ih, uint32_t color, uint32_t W, uint32_t H, uint64_t len, uint64_t idx_len, Layout &L) {
+        return Depth8::index_ok(ih, color, W, H, len, idx_len, L) && L.total == idx_len;
+    }
+    int launch(felics_ctx *ctx, hipStream_t s, const uint8_t *st, const uint64_t *d_off, const uint64_t *d_len, const uint8_t *ix, const uint64_t *,
+               const IndexViewRow *d_rows, const IndexViewItem *d_items, size_t cnt, uint32_t lds, Plane *d_planes, int *d_item_status) {
+        HIP_TRY(ctx, launch_decode8_seg_views(s, st, d_off, d_len, ix, d_rows, d_items, (uint32_t)cnt, lds, d_planes, d_item_status));
+        return FELICS_OK;
+    }
+    void done(felics_ctx *) {}
+};
+
+// felics_decompress_views_device_indexed16: k_decode16_seg_views; a class's items in passes of the tables (Depth16).
+struct IndexViews16 : Depth16 {
+    using Stats = felics_index16_view_stats;
+    static Stats &stats(felics_ctx *ctx) { return ctx->iv16stats; }
+    int tables(felics_ctx *ctx, size_t most_items) {  // the largest class of a pass
+        const int rc = Depth16::tables(ctx, most_items);
+        if (!rc) stats(ctx).table_bytes = table_bytes();
+        return rc;
+    }
+    int launch(felics_ctx *ctx, hipStream_t s, const uint8_t *st, const uint64_t *d_off, const uint64_t *d_len, const uint8_t *ix,
+               const uint64_t *d_ilen, const IndexViewRow *d_rows, const IndexViewItem *d_items, size_t cnt, uint32_t lds, Plane *d_planes,
+               int *d_item_status) {
+        return passes(ctx, s, cnt, [&](size_t o, size_t c, uint32_t *table, uint32_t epoch) {
+            return launch_decode16_seg_views(s, st, d_off, d_len, ix, d_ilen, d_rows, d_items + o, (uint32_t)c, lds, d_planes, table, epoch,
+                                             d_item_status + o, d_loaded);
+        });
     }
     void done(felics_ctx *ctx) { stats(ctx).rows_loaded += loaded; }
 };
@@ -935,9 +1188,9 @@ int decompress_views_indexed(felics_ctx *ctx, size_t n, const void *d_streams, c
         if (hdrs) hdrs[i] = h.status == FELICS_OK ? felics_header{h.color, h.depth, h.W, h.H} : felics_header{};
         int code = h.dstatus;
         if (!code && h.depth != Form::DEPTH) code = FELICS_E_UNSUPPORTED;  // the other depth has a format and a call of its own
-        if (!code && !Form::lds_ok(h)) code = FELICS_E_UNSUPPORTED;  // no host fallback here
+        if (!code && !Form::lds_ok(h.W, h.color)) code = FELICS_E_UNSUPPORTED;  // no host fallback here
         if (!code && ((int)h.color != w.color || (int)h.depth != w.depth || h.W != w.width || h.H != w.height)) code = FELICS_E_INVALID_DIMENSIONS;
-        if (!code && (idx_lens[i] < INDEX_HEADER_BYTES || !Form::index_ok(ih + i * INDEX_HEADER_BYTES, h, lens[i], idx_lens[i], lay[i])))
+        if (!code && (idx_lens[i] < INDEX_HEADER_BYTES || !Form::index_ok(ih + i * INDEX_HEADER_BYTES, h.color, h.W, h.H, lens[i], idx_lens[i], lay[i])))
             code = FELICS_E_INVALID_INDEX;
         status[i] = code;
         if (code) continue;
@@ -1008,7 +1261,7 @@ int decompress_views_indexed(felics_ctx *ctx, size_t n, const void *d_streams, c
                 for (size_t i = i0; i < i1; i++) {
                     if (status[i] != FELICS_OK) continue;
                     const DecodeHeader &h = rec[i];
-                    const uint32_t lds = Form::lds_bytes(h);
+                    const uint32_t lds = Form::lds_bytes(h.W, h.color);
                     if (lds > LDS_CLASS[c] || (c > 0 && lds <= LDS_CLASS[c - 1])) continue;
                     const felics_view &w = views[i];
                     const uint32_t K = lay[i].K, keff = std::max(K, 1u), cnt = lay[i].planes * keff;
@@ -1049,7 +1302,6 @@ int decompress_views_indexed(felics_ctx *ctx, size_t n, const void *d_streams, c
     vs.launches += n_launches;
     vs.passes += passes.size();
     vs.plane_bytes = most;
-    int first = FELICS_OK;
     if (nrows) {
         uint8_t *work = (uint8_t *)ctx->dec_region_work.p;
         IndexViewRow *d_rows = (IndexViewRow *)work;
@@ -1071,8 +1323,8 @@ int decompress_views_indexed(felics_ctx *ctx, size_t n, const void *d_streams, c
                                          d_item_status + L.item0)) != 0)
                         return r;
                 }
-                HIP_TRY(ctx, Form::finish(s, (uint32_t)P.rows, d_regions + P.row0, d_item_status, d_conv + P.row0, d_cviews + P.row0, P.max_npix,
-                                          d_planes, d_row_status + P.row0));
+                HIP_TRY(ctx, (launch_seg_views_finish<Plane, typename Form::Pixel>(s, (uint32_t)P.rows, d_regions + P.row0, d_item_status, d_conv + P.row0,
+                                                                                   d_cviews + P.row0, P.max_npix, d_planes, d_row_status + P.row0)));
             }
             HIP_TRY(ctx, hipMemcpyAsync(row_status.data(), d_row_status, nrows * 4, hipMemcpyDeviceToHost, s));
             if ((r = form.end(ctx, s)) != 0) return r;
@@ -1086,9 +1338,7 @@ int decompress_views_indexed(felics_ctx *ctx, size_t n, const void *d_streams, c
         }
         for (size_t r = 0; r < nrows; r++) status[rows[r].stream] = row_status[r];
     }
-    for (size_t i = 0; i < n; i++)
-        if (status[i] && !first) first = status[i];
-    return first;
+    return first_error(status, n);
 }
 
 // The two calls' entry: the checks that need no device, made before anything is launched, then decompress_views_indexed between the
@@ -1123,15 +1373,11 @@ int views_indexed_call(felics_ctx *ctx, size_t n, const void *d_streams, const u
 extern "C" {
 
 int felics_get_decode_stats(const felics_ctx *ctx, felics_decode_stats *out, size_t out_size) {
-    if (!ctx || !out) return FELICS_E_INVALID_ARGUMENT;
-    memcpy(out, &ctx->dstats, std::min(out_size, sizeof(felics_decode_stats)));
-    return FELICS_OK;
+    return copy_stats(ctx, &felics_ctx::dstats, out, out_size);
 }
 
 int felics_get_decode_view_stats(const felics_ctx *ctx, felics_decode_view_stats *out, size_t out_size) {
-    if (!ctx || !out) return FELICS_E_INVALID_ARGUMENT;
-    memcpy(out, &ctx->dvstats, std::min(out_size, sizeof(felics_decode_view_stats)));
-    return FELICS_OK;
+    return copy_stats(ctx, &felics_ctx::dvstats, out, out_size);
 }
 
 int felics_view_writable(const felics_view *v) {
@@ -1257,442 +1503,54 @@ int felics_decompress_batch_device(felics_ctx *ctx, size_t n, const void *d_stre
     }
     HIP_TRY(ctx, hipMemcpyAsync(status, d_status, n * 4, hipMemcpyDeviceToHost, s));
     HIP_TRY(ctx, hipStreamSynchronize(s));
-    for (size_t i = 0; i < n; i++)
-        if (status[i]) return status[i];
-    return FELICS_OK;
+    return first_error(status, n);
 }
 
 uint32_t felics_index_lanes_min_items(int color) { return color ? INDEX8_LANES_MIN_ITEMS_RGB : INDEX8_LANES_MIN_ITEMS; }
 
 int felics_get_index_stats(const felics_ctx *ctx, felics_index_stats *out, size_t out_size) {
-    if (!ctx || !out) return FELICS_E_INVALID_ARGUMENT;
-    memcpy(out, &ctx->istats, std::min(out_size, sizeof(felics_index_stats)));
-    return FELICS_OK;
+    return copy_stats(ctx, &felics_ctx::istats, out, out_size);
 }
 
 int felics_decompress_batch_device_indexed(felics_ctx *ctx, size_t n, const void *d_streams, const uint64_t *offsets, const uint64_t *lens,
                                            const void *d_index, size_t index_stride, void *d_pixels, size_t d_pixels_cap, felics_header *hdr_out,
                                            int *status) {
-    if (!ctx || (n && (!d_streams || !offsets || !lens || !d_index || !status))) return FELICS_E_INVALID_ARGUMENT;
-    if (ctx->failed) return FELICS_E_HIP;
-    if (n == 0) return FELICS_OK;
-    if (any_pending(ctx)) return FELICS_E_INVALID_ARGUMENT;  // felics_wait_batch first
-    if (((uintptr_t)d_index | index_stride) & 15u) return FELICS_E_INVALID_ARGUMENT;  // the kernel loads a checkpoint as aligned words
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    auto fail_all = [&](int code) {
-        for (size_t i = 0; i < n; i++) status[i] = code;
-        return code;
-    };
-    felics_header hdr;
-    int rc = indexed_stream_shape(ctx, d_streams, offsets, lens, hdr, hdr_out, n, status);
-    if (rc) return rc;
-    const uint32_t planes = hdr.color_type == FELICS_COLOR_RGB ? 3 : 1;
-    const uint64_t npix = (uint64_t)hdr.width * hdr.height;
-    const uint64_t frame_bytes = npix * planes;
-    if (frame_bytes * n > d_pixels_cap) return fail_all(FELICS_E_BUFFER_TOO_SMALL);
-    if (frame_bytes && !d_pixels) return fail_all(FELICS_E_INVALID_ARGUMENT);
-    IndexLayout L;
-    uint32_t seg;
-    if ((rc = indexed_index_shape(ctx, hdr, lens[0], d_index, index_stride, L, seg, n, status)) != 0) return rc;
-    const uint64_t per = (uint64_t)planes * std::max(L.K, 1u);
-    if (n > 0x7FFFFFFFull / per) return fail_all(FELICS_E_UNSUPPORTED);  // one block per segment
-    // offsets | lens | status on the device; a word per segment beside them
-    if ((rc = reserve(ctx, ctx->dec_meta, n * 8 * 2 + n * 4)) != 0) return fail_all(rc);
-    if ((rc = reserve(ctx, ctx->dec_seg_status, (size_t)(n * per) * 4)) != 0) return fail_all(rc);
-    uint64_t *d_off = (uint64_t *)ctx->dec_meta.p, *d_len = d_off + n;
-    int *d_status = (int *)(d_len + n);
-    int16_t *d_planes = nullptr;
-    if (planes == 3) {
-        if ((rc = reserve(ctx, ctx->dec_planes, (size_t)(npix * 3 * 2 * n) + 64)) != 0) return fail_all(rc);
-        d_planes = (int16_t *)ctx->dec_planes.p;
-    }
-    // Which form (felics.h): the first n64 streams 64 segments to a wave, the others a wave per segment beside them
-    size_t n64 = 0;
-    if (hdr.width >= 8 && L.K >= 1 && n >= 64) {
-        const uint64_t items = (uint64_t)(n / 64 * 64) * planes * L.K;
-        const uint32_t least = felics_index_lanes_min_items(hdr.color_type);
-        bool by_lane = least != INDEX8_LANES_NEVER && items >= least;
-        if (const char *e = getenv("FELICS_TEST_INDEX_LANES")) by_lane = atoi(e) != 0;
-        if (by_lane) n64 = n / 64 * 64;
-    }
-    // the lane form's passes: whole waves, within the table memory index_lanes_tables grants
-    const uint64_t waves = (uint64_t)(n64 / 64) * planes * L.K;
-    uint64_t pass_waves = 0;
-    if (waves) {
-        const size_t wave_bytes = index8_lanes_table_bytes(64, hdr.color_type);
-        size_t tbytes = 0;
-        if ((rc = index_lanes_tables(ctx, (size_t)std::min<uint64_t>(waves, index_lanes_pass_cap() / 64) * wave_bytes, wave_bytes, tbytes)) != 0)
-            return fail_all(rc);
-        pass_waves = std::min<uint64_t>(waves, tbytes / wave_bytes);
-    }
-    ctx->istats.streams += n;
-    ctx->istats.lane_segments8 += waves * 64;
-    ctx->istats.segments8 += (n - n64) * planes * L.K;
-    Lane &l = ctx->lanes[0];
-    hipStream_t s = l.stream;
-    int *seg_status = (int *)ctx->dec_seg_status.p;
-    for (size_t i = 0; i < n; i++) status[i] = FELICS_E_HIP;  // until the kernel's own word arrives
-    HIP_TRY(ctx, hipMemcpyAsync(d_off, offsets, n * 8, hipMemcpyHostToDevice, s));
-    HIP_TRY(ctx, hipMemcpyAsync(d_len, lens, n * 8, hipMemcpyHostToDevice, s));
-    HIP_TRY(ctx, hipMemsetAsync(d_status, 0xFF, n * 4, s));
-    HIP_TRY(ctx, hipMemsetAsync(seg_status, 0xFF, (size_t)(n * per) * 4, s));
-    const bool beside = n64 && n64 < n;  // the wave form's streams run on the lane's front stream, between two events
-    hipStream_t s2 = beside ? l.front : s;
-    if (beside) {
-        HIP_TRY(ctx, hipEventRecord(l.slice_done[0], s));
-        HIP_TRY(ctx, hipStreamWaitEvent(s2, l.slice_done[0], 0));
-    }
-    // (the kernel is handed the pointers of stream n64 on and knows nothing of the streams in front)
-    HIP_TRY(ctx, launch_decode8_seg(s2, (const uint8_t *)d_streams, d_off + n64, d_len + n64, (const uint8_t *)d_index + n64 * index_stride,
-                                    index_stride, (uint32_t)(n - n64), hdr.width, hdr.height, hdr.color_type, seg, L.K,
-                                    (uint8_t *)d_pixels + n64 * frame_bytes, d_planes ? d_planes + n64 * 3 * npix : nullptr, seg_status + n64 * per,
-                                    d_status + n64));
-    for (uint64_t w0 = 0; w0 < waves; w0 += pass_waves) {  // behind one another: they share the tables
-        HIP_TRY(ctx, launch_decode8_seg_lanes(s, (const uint8_t *)d_streams, d_off, d_len, (const uint8_t *)d_index, index_stride, hdr.width, hdr.height,
-                                              hdr.color_type, seg, L.K, (uint32_t)w0, (uint32_t)std::min(pass_waves, waves - w0),
-                                              (uint8_t *)d_pixels, d_planes, (uint32_t *)ctx->dec_lane_table.p, seg_status));
-        ctx->istats.lane_passes++;
-    }
-    HIP_TRY(ctx, launch_seg_finish(s, (uint32_t)n64, hdr.width, hdr.height, hdr.color_type, L.K, (uint8_t *)d_pixels, d_planes, seg_status, d_status));
-    if (beside) {
-        HIP_TRY(ctx, hipEventRecord(l.spine_done[0], s2));
-        HIP_TRY(ctx, hipStreamWaitEvent(s, l.spine_done[0], 0));
-    }
-    HIP_TRY(ctx, hipMemcpyAsync(status, d_status, n * 4, hipMemcpyDeviceToHost, s));
-    HIP_TRY(ctx, hipStreamSynchronize(s));
-    for (size_t i = 0; i < n; i++)
-        if (status[i]) return status[i];
-    return FELICS_OK;
+    return dense_indexed(ctx, n, d_streams, offsets, lens, d_pixels, d_pixels_cap, hdr_out, status, IndexSame8{{}, (const uint8_t *)d_index, index_stride});
 }
 
 int felics_get_index_wide_stats(const felics_ctx *ctx, felics_index16_stats *out, size_t out_size) {
-    if (!ctx || !out) return FELICS_E_INVALID_ARGUMENT;
-    memcpy(out, &ctx->i16stats, std::min(out_size, sizeof(felics_index16_stats)));
-    return FELICS_OK;
+    return copy_stats(ctx, &felics_ctx::i16stats, out, out_size);
 }
 
 int felics_decompress_batch_device_indexed_wide(felics_ctx *ctx, size_t n, const void *d_streams, const uint64_t *offsets, const uint64_t *lens,
                                              const void *d_index, const uint64_t *idx_offsets, const uint64_t *idx_lens, void *d_pixels,
                                              size_t d_pixels_cap, felics_header *hdr_out, int *status) {
-    if (!ctx || (n && (!d_streams || !offsets || !lens || !d_index || !idx_offsets || !idx_lens || !status))) return FELICS_E_INVALID_ARGUMENT;
-    if (ctx->failed) return FELICS_E_HIP;
-    if (n == 0) return FELICS_OK;
-    if (any_pending(ctx)) return FELICS_E_INVALID_ARGUMENT;  // felics_wait_batch first
-    if (!index16_aligned(d_index, idx_offsets, n)) return FELICS_E_INVALID_ARGUMENT;
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    auto fail_all = [&](int code) {
-        for (size_t i = 0; i < n; i++) status[i] = code;
-        return code;
-    };
-    // the opening checks; between the two headers this call's own: the frames must fit
-    felics_header hdr;
-    Index16Layout L;
-    uint32_t seg = 0;
-    int rc = indexed16_open(ctx, d_streams, offsets, lens, d_index, idx_offsets, idx_lens, hdr, hdr_out, L, seg, [&](const felics_header &h) {
-        const uint64_t bytes = (uint64_t)h.width * h.height * (h.color_type == FELICS_COLOR_RGB ? 3 : 1) * 2;
-        if (bytes * n > d_pixels_cap) return (int)FELICS_E_BUFFER_TOO_SMALL;
-        return bytes && !d_pixels ? (int)FELICS_E_INVALID_ARGUMENT : (int)FELICS_OK;
-    });
-    if (rc) return rc == FELICS_E_HIP ? rc : fail_all(rc);
-    const uint32_t planes = hdr.color_type == FELICS_COLOR_RGB ? 3 : 1;
-    const uint64_t npix = (uint64_t)hdr.width * hdr.height;
-    const uint64_t per = (uint64_t)planes * std::max(L.K, 1u);
-    if (n > 0x7FFFFFFFull / per) return fail_all(FELICS_E_UNSUPPORTED);  // a status word per segment, 32-bit item numbers
-    const uint64_t items = n * per;
-    size_t pass = 0;
-    if ((rc = dec16_tables(ctx, (size_t)index16_pass_cap(items), pass)) != 0) return fail_all(rc);
-    // offsets | lens | index offsets | index lens | the rows-loaded counter | status on the device; a word per segment beside them
-    if ((rc = reserve(ctx, ctx->dec_meta, n * 8 * 4 + 8 + n * 4)) != 0) return fail_all(rc);
-    if ((rc = reserve(ctx, ctx->dec_seg_status, (size_t)items * 4)) != 0) return fail_all(rc);
-    int32_t *d_planes = nullptr;
-    if (planes == 3) {
-        if ((rc = reserve(ctx, ctx->dec_planes, (size_t)(npix * 3 * 4 * n) + 64)) != 0) return fail_all(rc);
-        d_planes = (int32_t *)ctx->dec_planes.p;
-    }
-    uint64_t *d_off = (uint64_t *)ctx->dec_meta.p, *d_len = d_off + n, *d_ioff = d_len + n, *d_ilen = d_ioff + n;
-    unsigned long long *d_loaded = (unsigned long long *)(d_ilen + n);
-    int *d_status = (int *)(d_loaded + 1);
-    int *seg_status = (int *)ctx->dec_seg_status.p;
-    felics_index16_stats &st = ctx->i16stats;
-    st.streams += n;
-    st.segments16 += items;
-    st.table_bytes = decode16_table_bytes((uint32_t)pass);
-    hipStream_t s = ctx->lanes[0].stream;
-    for (size_t i = 0; i < n; i++) status[i] = FELICS_E_HIP;  // until the kernel's own word arrives
-    HIP_TRY(ctx, hipMemcpyAsync(d_off, offsets, n * 8, hipMemcpyHostToDevice, s));
-    HIP_TRY(ctx, hipMemcpyAsync(d_len, lens, n * 8, hipMemcpyHostToDevice, s));
-    HIP_TRY(ctx, hipMemcpyAsync(d_ioff, idx_offsets, n * 8, hipMemcpyHostToDevice, s));
-    HIP_TRY(ctx, hipMemcpyAsync(d_ilen, idx_lens, n * 8, hipMemcpyHostToDevice, s));
-    HIP_TRY(ctx, hipMemsetAsync(d_loaded, 0, 8, s));
-    HIP_TRY(ctx, hipMemsetAsync(d_status, 0xFF, n * 4, s));
-    HIP_TRY(ctx, hipMemsetAsync(seg_status, 0xFF, (size_t)items * 4, s));
-    for (uint64_t i0 = 0; i0 < items; i0 += pass) {  // behind one another on the one stream: the passes share the tables
-        uint32_t epoch = 0;
-        if ((rc = dec16_epoch(ctx, s, epoch)) != 0) return rc;
-        HIP_TRY(ctx, launch_decode16_seg(s, (const uint8_t *)d_streams, d_off, d_len, (const uint8_t *)d_index, d_ioff, d_ilen, hdr.width, hdr.height,
-                                         hdr.color_type, seg, L.K, (uint32_t)i0, (uint32_t)std::min<uint64_t>(pass, items - i0), (uint16_t *)d_pixels,
-                                         d_planes, (uint32_t *)ctx->dec_table.p, epoch, seg_status, d_loaded));
-        st.passes++;
-    }
-    HIP_TRY(ctx, launch_seg16_finish(s, (uint32_t)n, hdr.width, hdr.height, hdr.color_type, L.K, (uint16_t *)d_pixels, d_planes, seg_status, d_status));
-    unsigned long long loaded = 0;
-    HIP_TRY(ctx, hipMemcpyAsync(status, d_status, n * 4, hipMemcpyDeviceToHost, s));
-    HIP_TRY(ctx, hipMemcpyAsync(&loaded, d_loaded, 8, hipMemcpyDeviceToHost, s));
-    HIP_TRY(ctx, hipStreamSynchronize(s));
-    st.rows_loaded += loaded;
-    for (size_t i = 0; i < n; i++)
-        if (status[i]) return status[i];
-    return FELICS_OK;
+    return dense_indexed(ctx, n, d_streams, offsets, lens, d_pixels, d_pixels_cap, hdr_out, status,
+                         IndexSame16{{}, (const uint8_t *)d_index, idx_offsets, idx_lens});
 }
 
 int felics_get_region_stats(const felics_ctx *ctx, felics_region_stats *out, size_t out_size) {
-    if (!ctx || !out) return FELICS_E_INVALID_ARGUMENT;
-    memcpy(out, &ctx->rstats, std::min(out_size, sizeof(felics_region_stats)));
-    return FELICS_OK;
+    return copy_stats(ctx, &felics_ctx::rstats, out, out_size);
 }
 
 int felics_decompress_regions_device_indexed(felics_ctx *ctx, size_t n_streams, const void *d_streams, const uint64_t *offsets,
                                              const uint64_t *lens, const void *d_index, size_t index_stride, size_t n_regions,
                                              const felics_region *regions, void *d_pixels, size_t d_pixels_cap, uint64_t *out_offsets,
                                              felics_header *hdr_out, int *status) {
-    if (!ctx || (n_streams && (!d_streams || !offsets || !lens || !d_index)) || (n_regions && (!regions || !status)))
-        return FELICS_E_INVALID_ARGUMENT;
-    if (ctx->failed) return FELICS_E_HIP;
-    if (n_regions == 0) return FELICS_OK;
-    auto fail_all = [&](int code) {
-        for (size_t i = 0; i < n_regions; i++) status[i] = code;
-        return code;
-    };
-    if (any_pending(ctx)) return fail_all(FELICS_E_INVALID_ARGUMENT);  // felics_wait_batch first
-    if (n_streams == 0 || n_streams > 0xFFFFFFFFull || n_regions > 0x7FFFFFFFull) return fail_all(FELICS_E_INVALID_ARGUMENT);
-    if (((uintptr_t)d_index | index_stride) & 15u) return fail_all(FELICS_E_INVALID_ARGUMENT);  // the kernel loads a checkpoint as aligned words
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    felics_header hdr;
-    int rc = indexed_stream_shape(ctx, d_streams, offsets, lens, hdr, hdr_out, n_regions, status);
-    if (rc) return rc;
-    const uint32_t W = hdr.width, H = hdr.height, planes = hdr.color_type == FELICS_COLOR_RGB ? 3 : 1;
-    const uint64_t npix = (uint64_t)W * H;
-    // the requests: inside the image, of a stream of the call; the crops back to back
-    for (size_t r = 0; r < n_regions; r++)
-        if (regions[r].stream >= n_streams || !region_inside(W, H, regions[r])) return fail_all(FELICS_E_INVALID_ARGUMENT);
-    uint64_t total = 0;
-    for (size_t r = 0; r < n_regions; r++) {
-        total += (uint64_t)regions[r].w * regions[r].h * planes;  // (a crop has < 3 * 2^32 bytes: the sum is looked at before it can wrap)
-        if (total > d_pixels_cap) return fail_all(FELICS_E_BUFFER_TOO_SMALL);
-    }
-    if (total && !d_pixels) return fail_all(FELICS_E_INVALID_ARGUMENT);
-    IndexLayout L;
-    uint32_t seg;
-    if ((rc = indexed_index_shape(ctx, hdr, lens[0], d_index, index_stride, L, seg, n_regions, status)) != 0) return rc;
-    // the plan: a region's items are contiguous, in (plane, segment) order; an empty region has the header-only item
-    std::vector<RegionRow> rows;
-    std::vector<RegionItem> items;
-    std::vector<uint32_t> segs;
-    uint64_t walked = 0, pixels_walked = 0, max_crop = 0, plane_at = 0, out_at = 0;
-    try {
-        rows.reserve(n_regions);
-        for (size_t r = 0; r < n_regions; r++) {
-            const felics_region &g = regions[r];
-            segs.clear();
-            if (!region_empty(g)) {
-                uint32_t first, last;
-                region_span(W, seg, g, first, last);
-                for (uint32_t j = first; j <= last; j++)
-                    if (region_needs(W, npix, seg, g, j)) segs.push_back(j);
-            }
-            const uint64_t cnt = segs.empty() ? 1 : (uint64_t)planes * segs.size();
-            if (items.size() + cnt > 0x7FFFFFFFull) return fail_all(FELICS_E_UNSUPPORTED);  // one block per item
-            const uint64_t cpix = (uint64_t)g.w * g.h;
-            rows.push_back(RegionRow{g.stream, g.x, g.y, g.w, g.h, (uint32_t)items.size(), (uint32_t)cnt, 0, out_at, plane_at});
-            if (out_offsets) out_offsets[r] = out_at;
-            out_at += cpix * planes;
-            if (planes == 3) {
-                plane_at += cpix * 3;
-                max_crop = std::max(max_crop, cpix);
-            }
-            if (segs.empty()) items.push_back(RegionItem{(uint32_t)r, 0, REGION_HEADER_ONLY});
-            for (uint32_t c = 0; c < planes && !segs.empty(); c++)
-                for (const uint32_t j : segs) items.push_back(RegionItem{(uint32_t)r, c, j});
-            const uint64_t stop_at = region_empty(g) ? 0 : region_last(W, g);
-            for (const uint32_t j : segs) {
-                const uint64_t p0 = (uint64_t)j * seg;
-                pixels_walked += (std::min({npix, p0 + seg, stop_at}) - p0) * planes;
-            }
-            walked += (uint64_t)planes * segs.size();
-        }
-    } catch (const std::bad_alloc &) {
-        return fail_all(FELICS_E_IO);
-    }
-    const size_t n_items = items.size();
-    // offsets | lens | status on the device; the region table and the work list; a word per item
-    if ((rc = reserve(ctx, ctx->dec_meta, n_streams * 8 * 2 + n_regions * 4)) != 0) return fail_all(rc);
-    if ((rc = reserve(ctx, ctx->dec_region_work, n_regions * sizeof(RegionRow) + n_items * sizeof(RegionItem))) != 0) return fail_all(rc);
-    if ((rc = reserve(ctx, ctx->dec_seg_status, n_items * 4)) != 0) return fail_all(rc);
-    uint64_t *d_off = (uint64_t *)ctx->dec_meta.p, *d_len = d_off + n_streams;
-    int *d_status = (int *)(d_len + n_streams);
-    RegionRow *d_rows = (RegionRow *)ctx->dec_region_work.p;
-    RegionItem *d_items = (RegionItem *)(d_rows + n_regions);
-    int16_t *d_planes = nullptr;
-    if (planes == 3) {
-        if ((rc = reserve(ctx, ctx->dec_planes, (size_t)(plane_at * 2) + 64)) != 0) return fail_all(rc);
-        d_planes = (int16_t *)ctx->dec_planes.p;
-    }
-    felics_region_stats &rs = ctx->rstats;
-    rs.regions += n_regions;
-    rs.segments_walked += walked;
-    rs.segments_skipped += (uint64_t)n_regions * planes * L.K - walked;
-    rs.pixels_walked += pixels_walked;
-    hipStream_t s = ctx->lanes[0].stream;
-    for (size_t i = 0; i < n_regions; i++) status[i] = FELICS_E_HIP;  // until the kernel's own word arrives
-    HIP_TRY(ctx, hipMemcpyAsync(d_off, offsets, n_streams * 8, hipMemcpyHostToDevice, s));
-    HIP_TRY(ctx, hipMemcpyAsync(d_len, lens, n_streams * 8, hipMemcpyHostToDevice, s));
-    HIP_TRY(ctx, hipMemcpyAsync(d_rows, rows.data(), n_regions * sizeof(RegionRow), hipMemcpyHostToDevice, s));
-    HIP_TRY(ctx, hipMemcpyAsync(d_items, items.data(), n_items * sizeof(RegionItem), hipMemcpyHostToDevice, s));
-    HIP_TRY(ctx, hipMemsetAsync(d_status, 0xFF, n_regions * 4, s));
-    HIP_TRY(ctx, hipMemsetAsync(ctx->dec_seg_status.p, 0xFF, n_items * 4, s));
-    HIP_TRY(ctx, launch_decode8_regions(s, (const uint8_t *)d_streams, d_off, d_len, (const uint8_t *)d_index, index_stride, W, H, hdr.color_type,
-                                        seg, L.K, d_rows, (uint32_t)n_regions, d_items, (uint32_t)n_items, max_crop, (uint8_t *)d_pixels,
-                                        d_planes, (int *)ctx->dec_seg_status.p, d_status));
-    HIP_TRY(ctx, hipMemcpyAsync(status, d_status, n_regions * 4, hipMemcpyDeviceToHost, s));
-    HIP_TRY(ctx, hipStreamSynchronize(s));  // (rows and items live until here)
-    for (size_t i = 0; i < n_regions; i++)
-        if (status[i]) return status[i];
-    return FELICS_OK;
+    return regions_indexed(ctx, n_streams, d_streams, offsets, lens, n_regions, regions, d_pixels, d_pixels_cap, out_offsets, hdr_out, status,
+                           IndexSame8{{}, (const uint8_t *)d_index, index_stride});
 }
 
 int felics_get_region_wide_stats(const felics_ctx *ctx, felics_region16_stats *out, size_t out_size) {
-    if (!ctx || !out) return FELICS_E_INVALID_ARGUMENT;
-    memcpy(out, &ctx->r16stats, std::min(out_size, sizeof(felics_region16_stats)));
-    return FELICS_OK;
+    return copy_stats(ctx, &felics_ctx::r16stats, out, out_size);
 }
 
 int felics_decompress_regions_device_indexed_wide(felics_ctx *ctx, size_t n_streams, const void *d_streams, const uint64_t *offsets,
                                                   const uint64_t *lens, const void *d_index, const uint64_t *idx_offsets,
                                                   const uint64_t *idx_lens, size_t n_regions, const felics_region *regions, void *d_pixels,
                                                   size_t d_pixels_cap, uint64_t *out_offsets, felics_header *hdr_out, int *status) {
-    if (!ctx || (n_streams && (!d_streams || !offsets || !lens || !d_index || !idx_offsets || !idx_lens)) || (n_regions && (!regions || !status)))
-        return FELICS_E_INVALID_ARGUMENT;
-    if (ctx->failed) return FELICS_E_HIP;
-    if (n_regions == 0) return FELICS_OK;
-    auto fail_all = [&](int code) {
-        for (size_t i = 0; i < n_regions; i++) status[i] = code;
-        return code;
-    };
-    if (any_pending(ctx)) return fail_all(FELICS_E_INVALID_ARGUMENT);  // felics_wait_batch first
-    if (n_streams == 0 || n_streams > 0xFFFFFFFFull || n_regions > 0x7FFFFFFFull) return fail_all(FELICS_E_INVALID_ARGUMENT);
-    if (!index16_aligned(d_index, idx_offsets, n_streams) || ((uintptr_t)d_pixels & 1u)) return fail_all(FELICS_E_INVALID_ARGUMENT);
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    // the opening checks; between the two headers this call's own: the requests inside the image, of a stream of the call; the crops,
-    // back to back, must fit
-    felics_header hdr;
-    Index16Layout L;
-    uint32_t seg = 0;
-    int rc = indexed16_open(ctx, d_streams, offsets, lens, d_index, idx_offsets, idx_lens, hdr, hdr_out, L, seg, [&](const felics_header &h) {
-        for (size_t r = 0; r < n_regions; r++)
-            if (regions[r].stream >= n_streams || !region_inside(h.width, h.height, regions[r])) return (int)FELICS_E_INVALID_ARGUMENT;
-        const uint64_t sample_bytes = h.color_type == FELICS_COLOR_RGB ? 6 : 2;
-        uint64_t total = 0;
-        for (size_t r = 0; r < n_regions; r++) {
-            total += (uint64_t)regions[r].w * regions[r].h * sample_bytes;  // (a crop has < 6 * 2^32 bytes: the sum is looked at before it can wrap)
-            if (total > d_pixels_cap) return (int)FELICS_E_BUFFER_TOO_SMALL;
-        }
-        return total && !d_pixels ? (int)FELICS_E_INVALID_ARGUMENT : (int)FELICS_OK;
-    });
-    if (rc) return rc == FELICS_E_HIP ? rc : fail_all(rc);
-    const uint32_t W = hdr.width, H = hdr.height, planes = hdr.color_type == FELICS_COLOR_RGB ? 3 : 1;
-    const uint64_t npix = (uint64_t)W * H;
-    // the plan: a region's items are contiguous, in (plane, segment) order; an empty region has the header-only item
-    std::vector<RegionRow> rows;
-    std::vector<RegionItem> items;
-    std::vector<uint32_t> segs;
-    uint64_t walked = 0, pixels_walked = 0, max_crop = 0, plane_at = 0, out_at = 0;
-    try {
-        rows.reserve(n_regions);
-        for (size_t r = 0; r < n_regions; r++) {
-            const felics_region &g = regions[r];
-            segs.clear();
-            if (!region_empty(g)) {
-                uint32_t first, last;
-                region_span(W, seg, g, first, last);
-                for (uint32_t j = first; j <= last; j++)
-                    if (region_needs(W, npix, seg, g, j)) segs.push_back(j);
-            }
-            const uint64_t cnt = segs.empty() ? 1 : (uint64_t)planes * segs.size();
-            if (items.size() + cnt > 0x7FFFFFFFull) return fail_all(FELICS_E_UNSUPPORTED);  // one block per item, 32-bit item numbers
-            const uint64_t cpix = (uint64_t)g.w * g.h;
-            rows.push_back(RegionRow{g.stream, g.x, g.y, g.w, g.h, (uint32_t)items.size(), (uint32_t)cnt, 0, out_at, plane_at});
-            if (out_offsets) out_offsets[r] = out_at;
-            out_at += cpix * planes * 2;  // bytes
-            if (planes == 3) {
-                plane_at += cpix * 3;     // int32 samples
-                max_crop = std::max(max_crop, cpix);
-            }
-            if (segs.empty()) items.push_back(RegionItem{(uint32_t)r, 0, REGION_HEADER_ONLY});
-            for (uint32_t c = 0; c < planes && !segs.empty(); c++)
-                for (const uint32_t j : segs) items.push_back(RegionItem{(uint32_t)r, c, j});
-            const uint64_t stop_at = region_empty(g) ? 0 : region_last(W, g);
-            for (const uint32_t j : segs) {
-                const uint64_t p0 = (uint64_t)j * seg;
-                pixels_walked += (std::min({npix, p0 + seg, stop_at}) - p0) * planes;
-            }
-            walked += (uint64_t)planes * segs.size();
-        }
-    } catch (const std::bad_alloc &) {
-        return fail_all(FELICS_E_IO);
-    }
-    const size_t n_items = items.size();
-    // the items in passes of at most `pass` waves: a wave owns a table of the pass; a pass boundary may fall inside a region
-    size_t pass = 0;
-    if ((rc = dec16_tables(ctx, (size_t)index16_pass_cap(n_items), pass)) != 0) return fail_all(rc);
-    // offsets | lens | index offsets | index lens | the rows-loaded counter | status on the device; the region table and the work list;
-    // a word per item
-    if ((rc = reserve(ctx, ctx->dec_meta, n_streams * 8 * 4 + 8 + n_regions * 4)) != 0) return fail_all(rc);
-    if ((rc = reserve(ctx, ctx->dec_region_work, n_regions * sizeof(RegionRow) + n_items * sizeof(RegionItem))) != 0) return fail_all(rc);
-    if ((rc = reserve(ctx, ctx->dec_seg_status, n_items * 4)) != 0) return fail_all(rc);
-    int32_t *d_planes = nullptr;
-    if (planes == 3) {  // crop-sized: 3 * w * h int32 per region
-        if ((rc = reserve(ctx, ctx->dec_planes, (size_t)(plane_at * 4) + 64)) != 0) return fail_all(rc);
-        d_planes = (int32_t *)ctx->dec_planes.p;
-    }
-    uint64_t *d_off = (uint64_t *)ctx->dec_meta.p, *d_len = d_off + n_streams, *d_ioff = d_len + n_streams, *d_ilen = d_ioff + n_streams;
-    unsigned long long *d_loaded = (unsigned long long *)(d_ilen + n_streams);
-    int *d_status = (int *)(d_loaded + 1);
-    int *item_status = (int *)ctx->dec_seg_status.p;
-    RegionRow *d_rows = (RegionRow *)ctx->dec_region_work.p;
-    RegionItem *d_items = (RegionItem *)(d_rows + n_regions);
-    felics_region16_stats &rs = ctx->r16stats;
-    rs.regions += n_regions;
-    rs.segments_walked += walked;
-    rs.segments_skipped += (uint64_t)n_regions * planes * L.K - walked;
-    rs.pixels_walked += pixels_walked;
-    hipStream_t s = ctx->lanes[0].stream;
-    for (size_t i = 0; i < n_regions; i++) status[i] = FELICS_E_HIP;  // until the kernel's own word arrives
-    HIP_TRY(ctx, hipMemcpyAsync(d_off, offsets, n_streams * 8, hipMemcpyHostToDevice, s));
-    HIP_TRY(ctx, hipMemcpyAsync(d_len, lens, n_streams * 8, hipMemcpyHostToDevice, s));
-    HIP_TRY(ctx, hipMemcpyAsync(d_ioff, idx_offsets, n_streams * 8, hipMemcpyHostToDevice, s));
-    HIP_TRY(ctx, hipMemcpyAsync(d_ilen, idx_lens, n_streams * 8, hipMemcpyHostToDevice, s));
-    HIP_TRY(ctx, hipMemcpyAsync(d_rows, rows.data(), n_regions * sizeof(RegionRow), hipMemcpyHostToDevice, s));
-    HIP_TRY(ctx, hipMemcpyAsync(d_items, items.data(), n_items * sizeof(RegionItem), hipMemcpyHostToDevice, s));
-    HIP_TRY(ctx, hipMemsetAsync(d_loaded, 0, 8, s));
-    HIP_TRY(ctx, hipMemsetAsync(d_status, 0xFF, n_regions * 4, s));
-    HIP_TRY(ctx, hipMemsetAsync(item_status, 0xFF, n_items * 4, s));
-    for (size_t i0 = 0; i0 < n_items; i0 += pass) {  // behind one another on the one stream: the passes share the tables
-        uint32_t epoch = 0;
-        if ((rc = dec16_epoch(ctx, s, epoch)) != 0) return rc;
-        HIP_TRY(ctx, launch_decode16_regions(s, (const uint8_t *)d_streams, d_off, d_len, (const uint8_t *)d_index, d_ioff, d_ilen, W, H, hdr.color_type,
-                                             seg, L.K, d_rows, d_items, (uint32_t)i0, (uint32_t)std::min(pass, n_items - i0), (uint8_t *)d_pixels,
-                                             d_planes, (uint32_t *)ctx->dec_table.p, epoch, item_status, d_loaded));
-        rs.passes++;
-    }
-    HIP_TRY(ctx, launch_regions16_finish(s, d_rows, (uint32_t)n_regions, max_crop, (uint8_t *)d_pixels, d_planes, item_status, d_status));
-    unsigned long long loaded = 0;
-    HIP_TRY(ctx, hipMemcpyAsync(status, d_status, n_regions * 4, hipMemcpyDeviceToHost, s));
-    HIP_TRY(ctx, hipMemcpyAsync(&loaded, d_loaded, 8, hipMemcpyDeviceToHost, s));
-    HIP_TRY(ctx, hipStreamSynchronize(s));  // (rows and items live until here)
-    rs.rows_loaded += loaded;
-    for (size_t i = 0; i < n_regions; i++)
-        if (status[i]) return status[i];
-    return FELICS_OK;
+    return regions_indexed(ctx, n_streams, d_streams, offsets, lens, n_regions, regions, d_pixels, d_pixels_cap, out_offsets, hdr_out, status,
+                           IndexSame16{{}, (const uint8_t *)d_index, idx_offsets, idx_lens});
 }
 
 int felics_read_headers_device(felics_ctx *ctx, size_t n, const void *d_streams, const uint64_t *offsets, const uint64_t *lens,
@@ -1822,9 +1680,7 @@ int felics_decompress_views_device(felics_ctx *ctx, size_t n, const void *d_stre
 }
 
 int felics_get_index_view_stats(const felics_ctx *ctx, felics_index_view_stats *out, size_t out_size) {
-    if (!ctx || !out) return FELICS_E_INVALID_ARGUMENT;
-    memcpy(out, &ctx->ivstats, std::min(out_size, sizeof(felics_index_view_stats)));
-    return FELICS_OK;
+    return copy_stats(ctx, &felics_ctx::ivstats, out, out_size);
 }
 
 int felics_decompress_views_device_indexed(felics_ctx *ctx, size_t n, const void *d_streams, const uint64_t *offsets, const uint64_t *lens,
@@ -1835,9 +1691,7 @@ int felics_decompress_views_device_indexed(felics_ctx *ctx, size_t n, const void
 }
 
 int felics_get_index_view_wide_stats(const felics_ctx *ctx, felics_index16_view_stats *out, size_t out_size) {
-    if (!ctx || !out) return FELICS_E_INVALID_ARGUMENT;
-    memcpy(out, &ctx->iv16stats, std::min(out_size, sizeof(felics_index16_view_stats)));
-    return FELICS_OK;
+    return copy_stats(ctx, &felics_ctx::iv16stats, out, out_size);
 }
 
 int felics_decompress_views_device_indexed_wide(felics_ctx *ctx, size_t n, const void *d_streams, const uint64_t *offsets, const uint64_t *lens,

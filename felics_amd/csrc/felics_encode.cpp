@@ -779,9 +779,7 @@ int felics_compress_batch_device_indexed_wide(felics_ctx *ctx, size_t n, const v
 }
 
 int felics_get_index_wide_emit_stats(const felics_ctx *ctx, felics_index16_emit_stats *out, size_t out_size) {
-    if (!ctx || !out) return FELICS_E_INVALID_ARGUMENT;
-    memcpy(out, &ctx->i16estats, std::min(out_size, sizeof(felics_index16_emit_stats)));
-    return FELICS_OK;
+    return copy_stats(ctx, &felics_ctx::i16estats, out, out_size);
 }
 
 int felics_submit_batch_device(felics_ctx *ctx, size_t n, const void *d_pixels, uint32_t w, uint32_t h, int color,

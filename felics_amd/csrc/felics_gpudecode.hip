@@ -177,7 +177,10 @@ template <typename T>
 __device__ __forceinline__ T *dec_frame(const DecUniform &, T *pixels, const DecView &v, uint64_t per) { return pixels + (uint64_t)v.img * per; }
 template <typename T>
 __device__ __forceinline__ T *dec_frame(const DecMixed &, T *pixels, const DecView &v, uint64_t) {
-    return reinterpret_cast<T *>(reinterpret_cast<uint8_t *>(pixels) + v.out_off);
+    // (as integers: in a views call `pixels` is null and out_off the frame's address, and null plus an offset is not a pointer; the
+    // sum names device memory, which is said so that the stores stay global ones)
+    using Global = __attribute__((address_space(1))) T;
+    return (T *)reinterpret_cast<Global *>(reinterpret_cast<uintptr_t>(pixels) + v.out_off);
 }
 template <typename T>
 __device__ __forceinline__ T *dec_frame(const DecPitched &g, T *, const DecView &, uint64_t) {
@@ -574,33 +577,56 @@ __device__ __forceinline__ int decode8_from_checkpoint(uint8_t *smem, const uint
     return rc;
 }
 
-// The whole segment into the stream's frame (u8 gray) or plane c of its planes (int16): pixel `at` to out[at].  The walk hands it
+// The three sinks of both depths' walks from a checkpoint.  T is the pixel type (uint8_t, uint16_t), P the type of an RGB plane's
+// sample (int16_t, int32_t): the 8-bit kernels take <uint8_t, int16_t>, the 16-bit ones <uint16_t, int32_t>.
+
+// The whole segment into the stream's frame (gray) or plane c of its planes: pixel `at` to out[at].  The walk hands it
 // p0 <= at < pend only, so a wave writes its own segment's samples and no other.
+template <typename T, typename P>
 struct SegmentSink {
-    uint8_t *outg;   // gray: the stream's frame; else null
-    int16_t *outp;   // RGB: plane c of the stream's planes
+    T *outg;  // gray: the stream's frame; else null
+    P *outp;  // RGB: plane c of the stream's planes
     __device__ __forceinline__ uint64_t stop(uint64_t pend) const { return pend; }
     __device__ __forceinline__ void store(uint32_t, uint32_t, uint64_t at, int v) const {
-        if (outg) outg[at] = (uint8_t)v;
-        else outp[at] = (int16_t)v;
+        if (outg) outg[at] = (T)v;
+        else outp[at] = (P)v;
     }
 };
 
-// The segment's part of a region into the region's dense crop (u8 gray, or plane c of the crop-sized int16 planes): the walk ends
+// The segment's part of a region into the region's dense crop (gray, or plane c of the crop-sized planes): the walk ends
 // behind the region's last pixel, and a sample is written only if its (column, row) lies inside the region -- column in [x, x + w),
-// row in [y, y + h) (row < y + h holds for every at < stop) -- to (row - y) * w + (column - x), an offset below w * h.
+// row in [y, y + h) (row < y + h holds for every at < stop) -- to (row - y) * w + (column - x), an offset below w * h.  reg and W
+// are wave-uniform (scalar loads of the kernel); the store's predicate is the only divergence, once per 64-sample block.
+template <typename T, typename P>
 struct RegionSink {
     RegionRow reg;  // (inside the image, both sides non-zero: the host's checks)
     uint32_t W;
-    uint8_t *outg;
-    int16_t *outp;
+    T *outg;
+    P *outp;
     __device__ __forceinline__ uint64_t stop(uint64_t pend) const { return min(pend, (uint64_t)(reg.y + reg.h - 1) * W + reg.x + reg.w); }
     __device__ __forceinline__ void store(uint32_t col, uint32_t y, uint64_t, int v) const {
         if (col >= reg.x && col - reg.x < reg.w && y >= reg.y && y - reg.y < reg.h) {
             const uint64_t to = (uint64_t)(y - reg.y) * reg.w + (col - reg.x);
-            if (outg) outg[to] = (uint8_t)v;
-            else outp[to] = (int16_t)v;
+            if (outg) outg[to] = (T)v;
+            else outp[to] = (P)v;
         }
+    }
+};
+
+// The whole segment into a view (felics_decompress_views_device_indexed, _indexed16): a gray sample as ONE aligned store of a T at the
+// place the view's strides give pixel (col, y) -- whatever lies between the samples is never stored to, and any strides do, negative
+// ones and pixel strides other than sizeof(T) included (16-bit: address and strides are even, felics_view_writable); an RGB sample to
+// plane c of the row's planes as the segment sink does (the conversion writes the view).  The walk hands it p0 <= at < pend only,
+// and (col, y) is a pixel of the image the view was checked against.
+template <typename T, typename P>
+struct ViewSink {
+    uint8_t *data;  // gray: the view's first sample; else null
+    int64_t row_stride, pixel_stride;
+    P *outp;        // RGB: plane c of the row's planes
+    __device__ __forceinline__ uint64_t stop(uint64_t pend) const { return pend; }
+    __device__ __forceinline__ void store(uint32_t col, uint32_t y, uint64_t at, int v) const {
+        if (data) *reinterpret_cast<T *>(data + view_sample_offset(row_stride, pixel_stride, 0, col, y, 0)) = (T)v;
+        else outp[at] = (P)v;
     }
 };
 
@@ -616,7 +642,7 @@ __global__ __launch_bounds__(64) void k_decode8_seg(const uint8_t *__restrict__ 
     const uint32_t nplanes = geo.color ? 3u : 1u, keff = max(K, 1u);
     const uint32_t img = blockIdx.x / (nplanes * keff), c = blockIdx.x / keff % nplanes, j = blockIdx.x % keff;
     const uint64_t npix = (uint64_t)geo.W * geo.H;
-    const SegmentSink sink{geo.color ? nullptr : pixels + (uint64_t)img * npix, geo.color ? planes + ((uint64_t)img * nplanes + c) * npix : nullptr};
+    const SegmentSink<uint8_t, int16_t> sink{geo.color ? nullptr : pixels + (uint64_t)img * npix, geo.color ? planes + ((uint64_t)img * nplanes + c) * npix : nullptr};
     const int rc = decode8_from_checkpoint(smem, streams + offsets[img], lens[img], index + (uint64_t)img * index_stride, geo, segment_pixels, K, c,
                                            j, false, sink);
     if (lane_id() == 0) seg_status[blockIdx.x] = rc;
@@ -634,8 +660,8 @@ __global__ __launch_bounds__(64) void k_decode8_region(const uint8_t *__restrict
     const RegionItem item = items[blockIdx.x];
     const RegionRow reg = regions[item.region];
     const uint32_t img = reg.stream, c = item.plane;
-    const RegionSink sink{reg, geo.W, geo.color ? nullptr : pixels + reg.out_off,
-                          geo.color ? planes + reg.plane_off + (uint64_t)c * reg.w * reg.h : nullptr};
+    const RegionSink<uint8_t, int16_t> sink{reg, geo.W, geo.color ? nullptr : pixels + reg.out_off,
+                                            geo.color ? planes + reg.plane_off + (uint64_t)c * reg.w * reg.h : nullptr};
     const int rc = decode8_from_checkpoint(smem, streams + offsets[img], lens[img], index + (uint64_t)img * index_stride, geo, segment_pixels, K, c,
                                            item.seg, item.seg == REGION_HEADER_ONLY, sink);
     if (lane_id() == 0) item_status[blockIdx.x] = rc;
@@ -660,25 +686,6 @@ __global__ __launch_bounds__(64) void k_seg_status(const int *__restrict__ words
     if (threadIdx.x == 0) status[blockIdx.x] = first == 0xFFFFFFFFu ? FELICS_OK : mine[first];
 }
 
-namespace {
-
-// The whole segment into a view (felics_decompress_views_device_indexed): a gray sample as ONE BYTE at the place the view's strides
-// give pixel (col, y) -- whatever lies between the samples is never stored to, and any strides do, negative ones and pixel strides
-// other than 1 included; an RGB sample to plane c of the row's int16 planes as the segment sink does (the conversion writes the view).
-// The walk hands it p0 <= at < pend only, and (col, y) is a pixel of the image the view was checked against.
-struct ViewSink {
-    uint8_t *data;   // gray: the view's first sample; else null
-    int64_t row_stride, pixel_stride;
-    int16_t *outp;   // RGB: plane c of the row's planes
-    __device__ __forceinline__ uint64_t stop(uint64_t pend) const { return pend; }
-    __device__ __forceinline__ void store(uint32_t col, uint32_t y, uint64_t at, int v) const {
-        if (data) data[view_sample_offset(row_stride, pixel_stride, 0, col, y, 0)] = (uint8_t)v;
-        else outp[at] = (int16_t)v;
-    }
-};
-
-}  // namespace
-
 // One wave per WORK ITEM = (row, plane, segment) of felics_decompress_views_device_indexed (felics_kernels.h; host model:
 // felics_decompress_indexed_view).  Item and row are wave-uniform (blockIdx.x: scalar loads); the walk's geometry, segment_pixels and
 // K are the row's, so the streams of a launch need not share a shape -- only the launch's dynamic LDS, which holds its widest row.
@@ -692,8 +699,8 @@ __global__ __launch_bounds__(64) void k_decode8_seg_views(const uint8_t *__restr
     const IndexViewRow r = rows[item.row];
     const DecUniform geo{r.W, r.H, r.color};
     const uint32_t c = item.plane;
-    const ViewSink sink{r.color ? nullptr : reinterpret_cast<uint8_t *>(const_cast<void *>(r.view.data)), r.view.row_stride, r.view.pixel_stride,
-                        r.color ? planes + r.plane_off + (uint64_t)c * r.W * r.H : nullptr};
+    const ViewSink<uint8_t, int16_t> sink{r.color ? nullptr : reinterpret_cast<uint8_t *>(const_cast<void *>(r.view.data)), r.view.row_stride,
+                                          r.view.pixel_stride, r.color ? planes + r.plane_off + (uint64_t)c * r.W * r.H : nullptr};
     const int rc = decode8_from_checkpoint(smem, streams + offsets[r.stream], lens[r.stream], index + r.index_off, geo, r.segment_pixels, r.K, c,
                                            item.seg, false, sink);
     if (lane_id() == 0) item_status[blockIdx.x] = rc;
@@ -1683,17 +1690,6 @@ __device__ __forceinline__ int decode16_from_checkpoint(uint8_t *smem, const uin
     return rc;
 }
 
-// The whole segment into the stream's frame (u16 gray) or plane c of its planes (int32): pixel `at` to out[at], p0 <= at < pend only.
-struct Segment16Sink {
-    uint16_t *outg;  // gray: the stream's frame; else null
-    int32_t *outp;   // RGB: plane c of the stream's planes
-    __device__ __forceinline__ uint64_t stop(uint64_t pend) const { return pend; }
-    __device__ __forceinline__ void store(uint32_t, uint32_t, uint64_t at, int v) const {
-        if (outg) outg[at] = (uint16_t)v;
-        else outp[at] = v;
-    }
-};
-
 }  // namespace
 
 // One wave per SEGMENT of a plane of a 16-bit stream (felics_decompress_batch_device_indexed16), a pass of consecutive items at a
@@ -1711,7 +1707,7 @@ __global__ __launch_bounds__(64) void k_decode16_seg(const uint8_t *__restrict__
     const uint32_t item = item0 + blockIdx.x;
     const uint32_t img = item / (nplanes * keff), c = item / keff % nplanes, j = item % keff;
     const uint64_t npix = (uint64_t)geo.W * geo.H;
-    const Segment16Sink sink{geo.color ? nullptr : pixels + (uint64_t)img * npix, geo.color ? planes + ((uint64_t)img * nplanes + c) * npix : nullptr};
+    const SegmentSink<uint16_t, int32_t> sink{geo.color ? nullptr : pixels + (uint64_t)img * npix, geo.color ? planes + ((uint64_t)img * nplanes + c) * npix : nullptr};
     uint32_t *table = gtable + (uint64_t)blockIdx.x * DEC16_CONTEXTS * DEC16_ROW;
     uint32_t loaded = 0;
     const int rc = decode16_from_checkpoint(smem, streams + offsets[img], lens[img], index + idx_offsets[img], idx_lens[img], geo, segment_pixels, K,
@@ -1721,30 +1717,6 @@ __global__ __launch_bounds__(64) void k_decode16_seg(const uint8_t *__restrict__
         if (loaded) atomicAdd(rows_loaded, (unsigned long long)loaded);
     }
 }
-
-namespace {
-
-// The segment's part of a region into the region's dense crop (u16 gray, or plane c of the crop-sized int32 planes): RegionSink for
-// 16-bit samples.  The walk ends behind the region's last pixel; a sample is written only if its (column, row) lies inside the
-// region -- column in [x, x + w), row in [y, y + h) (row < y + h holds for every at < stop) -- to (row - y) * w + (column - x), an
-// offset below w * h.  reg and W are wave-uniform (scalar loads of the kernel); the store's predicate is the only divergence, once
-// per 64-sample block.
-struct Region16Sink {
-    RegionRow reg;  // (inside the image, both sides non-zero: the host's checks)
-    uint32_t W;
-    uint16_t *outg;
-    int32_t *outp;
-    __device__ __forceinline__ uint64_t stop(uint64_t pend) const { return min(pend, (uint64_t)(reg.y + reg.h - 1) * W + reg.x + reg.w); }
-    __device__ __forceinline__ void store(uint32_t col, uint32_t y, uint64_t, int v) const {
-        if (col >= reg.x && col - reg.x < reg.w && y >= reg.y && y - reg.y < reg.h) {
-            const uint64_t to = (uint64_t)(y - reg.y) * reg.w + (col - reg.x);
-            if (outg) outg[to] = (uint16_t)v;
-            else outp[to] = v;
-        }
-    }
-};
-
-}  // namespace
 
 // One wave per WORK ITEM = (region, plane, needed segment) of felics_decompress_regions_device_indexed16 (felics.h "Restart index:
 // regions of 16-bit streams"; host model: felics_decompress_region_indexed16), a pass of consecutive items at a time: block b is item
@@ -1762,8 +1734,8 @@ __global__ __launch_bounds__(64) void k_decode16_region(const uint8_t *__restric
     const RegionItem item = items[item0 + blockIdx.x];
     const RegionRow reg = regions[item.region];
     const uint32_t img = reg.stream, c = item.plane;
-    const Region16Sink sink{reg, geo.W, geo.color ? nullptr : reinterpret_cast<uint16_t *>(pixels + reg.out_off),
-                            geo.color ? planes + reg.plane_off + (uint64_t)c * reg.w * reg.h : nullptr};
+    const RegionSink<uint16_t, int32_t> sink{reg, geo.W, geo.color ? nullptr : reinterpret_cast<uint16_t *>(pixels + reg.out_off),
+                                              geo.color ? planes + reg.plane_off + (uint64_t)c * reg.w * reg.h : nullptr};
     uint32_t *table = gtable + (uint64_t)blockIdx.x * DEC16_CONTEXTS * DEC16_ROW;
     uint32_t loaded = 0;
     const int rc = decode16_from_checkpoint(smem, streams + offsets[img], lens[img], index + idx_offsets[img], idx_lens[img], geo, segment_pixels, K,
@@ -1773,26 +1745,6 @@ __global__ __launch_bounds__(64) void k_decode16_region(const uint8_t *__restric
         if (loaded) atomicAdd(rows_loaded, (unsigned long long)loaded);
     }
 }
-
-namespace {
-
-// The whole segment into a view (felics_decompress_views_device_indexed16): ViewSink for 16-bit samples.  A gray sample is ONE aligned
-// two-byte store at the place the view's strides give pixel (col, y) -- address and strides are even (felics_view_writable), whatever
-// lies between the samples is never stored to, negative strides and pixel strides other than 2 included; an RGB sample goes to plane c
-// of the row's int32 planes as the segment sink does (the conversion writes the view).  The walk hands it p0 <= at < pend only, and
-// (col, y) is a pixel of the image the view was checked against.
-struct View16Sink {
-    uint8_t *data;   // gray: the view's first sample; else null
-    int64_t row_stride, pixel_stride;
-    int32_t *outp;   // RGB: plane c of the row's planes
-    __device__ __forceinline__ uint64_t stop(uint64_t pend) const { return pend; }
-    __device__ __forceinline__ void store(uint32_t col, uint32_t y, uint64_t at, int v) const {
-        if (data) *reinterpret_cast<uint16_t *>(data + view_sample_offset(row_stride, pixel_stride, 0, col, y, 0)) = (uint16_t)v;
-        else outp[at] = v;
-    }
-};
-
-}  // namespace
 
 // One wave per WORK ITEM = (row, plane, segment) of felics_decompress_views_device_indexed16 (felics_kernels.h; host model:
 // felics_decompress_indexed16_view): k_decode8_seg_views for version-2 indexes.  The tables are that kernel's own (IndexViewRow,
@@ -1812,8 +1764,8 @@ __global__ __launch_bounds__(64) void k_decode16_seg_views(const uint8_t *__rest
     const IndexViewRow r = rows[item.row];
     const DecUniform geo{r.W, r.H, r.color};
     const uint32_t c = item.plane;
-    const View16Sink sink{r.color ? nullptr : reinterpret_cast<uint8_t *>(const_cast<void *>(r.view.data)), r.view.row_stride, r.view.pixel_stride,
-                          r.color ? planes + r.plane_off + (uint64_t)c * r.W * r.H : nullptr};
+    const ViewSink<uint16_t, int32_t> sink{r.color ? nullptr : reinterpret_cast<uint8_t *>(const_cast<void *>(r.view.data)), r.view.row_stride,
+                                           r.view.pixel_stride, r.color ? planes + r.plane_off + (uint64_t)c * r.W * r.H : nullptr};
     uint32_t *table = gtable + (uint64_t)blockIdx.x * DEC16_CONTEXTS * DEC16_ROW;
     uint32_t loaded = 0;
     const int rc = decode16_from_checkpoint(smem, streams + offsets[r.stream], lens[r.stream], index + r.index_off, idx_lens[r.stream], geo,
@@ -1909,23 +1861,47 @@ uint32_t decode16_lds_bytes(uint32_t W) {
 }
 size_t decode16_table_bytes(uint32_t n) { return (size_t)n * DEC16_CONTEXTS * DEC16_ROW * 4; }
 
+namespace {
+
+// LDS above 64 KiB: raise the kernel's limit (a launch of `lds` bytes of dynamic LDS follows)
+template <typename Kernel>
+hipError_t raise_lds(Kernel kernel, uint32_t lds) {
+    if (lds <= 64u * 1024u) return hipSuccess;
+    return hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)DECODE_LDS_LIMIT);
+}
+
+// A grid's second dimension holds at most 65 535 rows: every launch that puts a stream, a row or a region there is cut into runs of
+// at most this many (the one rule; launch_conv_uniform, launch_conv_rows, launch_conv_views, the region conversions, launch_scatter_views).
+constexpr uint32_t GRID_ROWS = 65535u;
+
+// the conversion of n same-shape RGB streams: the kernels take the stream from blockIdx.y, so a run starts at its own planes, frames
+// and status words
+template <typename P, typename T>
+void launch_conv_uniform(hipStream_t s, uint32_t n, uint32_t W, uint32_t H, P *planes, T *pixels, int *status) {
+    const uint64_t npix = (uint64_t)W * H;
+    const uint32_t bx = (uint32_t)std::min<uint64_t>((npix + 255) / 256, 1024u);
+    if (!bx) return;
+    for (uint32_t i0 = 0; i0 < n; i0 += GRID_ROWS) {
+        const dim3 grid(bx, std::min(n - i0, GRID_ROWS));
+        P *const pl = planes + (uint64_t)i0 * 3u * npix;
+        T *const px = pixels + (uint64_t)i0 * 3u * npix;
+        if constexpr (sizeof(T) == 1) hipLaunchKernelGGL(k_ycocg8_to_rgb<ConvUniform>, grid, dim3(256), 0, s, pl, px, ConvUniform{(uint32_t)npix}, status + i0);
+        else hipLaunchKernelGGL(k_ycocg16_to_rgb<ConvUniform>, grid, dim3(256), 0, s, pl, px, ConvUniform{(uint32_t)npix}, status + i0);
+    }
+}
+
+}  // namespace
+
 hipError_t launch_decode16(hipStream_t s, const uint8_t *streams, const uint64_t *offsets, const uint64_t *lens, uint32_t n,
                            uint32_t W, uint32_t H, uint32_t color, uint16_t *pixels, int32_t *planes, uint32_t *table,
                            uint32_t epoch0, int *status) {
     if (n == 0) return hipSuccess;
     const uint32_t lds = decode16_lds_bytes(W);
-    if (lds > 64u * 1024u) {
-        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&k_decode16<DecUniform>),
-                                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)DECODE_LDS_LIMIT);
-        if (e != hipSuccess) return e;
-    }
+    const hipError_t e = raise_lds(&k_decode16<DecUniform>, lds);
+    if (e != hipSuccess) return e;
     hipLaunchKernelGGL(k_decode16<DecUniform>, dim3(n), dim3(64), lds, s, streams, offsets, lens, DecUniform{W, H, color}, pixels, planes,
                        table, epoch0, status);
-    if (color) {
-        const uint64_t npix = (uint64_t)W * H;
-        const uint32_t bx = (uint32_t)std::min<uint64_t>((npix + 255) / 256, 1024u);
-        if (bx) hipLaunchKernelGGL(k_ycocg16_to_rgb<ConvUniform>, dim3(bx, n), dim3(256), 0, s, planes, pixels, ConvUniform{(uint32_t)npix}, status);
-    }
+    if (color) launch_conv_uniform(s, n, W, H, planes, pixels, status);
     return hipGetLastError();
 }
 
@@ -1944,18 +1920,6 @@ hipError_t launch_lanes(hipStream_t s, const uint8_t *streams, const uint64_t *o
     hipLaunchKernelGGL(rgb, dim3(nwaves), dim3(64), 0, s, streams, offsets, lens, rgeo, planes, tail...);
     conv();
     return hipGetLastError();
-}
-
-// the conversion of n same-shape RGB streams
-template <typename P, typename T>
-void launch_conv_uniform(hipStream_t s, uint32_t n, uint32_t W, uint32_t H, P *planes, T *pixels, int *status) {
-    const uint64_t npix = (uint64_t)W * H;
-    const uint32_t bx = (uint32_t)std::min<uint64_t>((npix + 255) / 256, 1024u);
-    if (!bx) return;
-    if constexpr (sizeof(T) == 1)
-        hipLaunchKernelGGL(k_ycocg8_to_rgb<ConvUniform>, dim3(bx, n), dim3(256), 0, s, planes, pixels, ConvUniform{(uint32_t)npix}, status);
-    else
-        hipLaunchKernelGGL(k_ycocg16_to_rgb<ConvUniform>, dim3(bx, n), dim3(256), 0, s, planes, pixels, ConvUniform{(uint32_t)npix}, status);
 }
 
 }  // namespace
@@ -2022,8 +1986,8 @@ template <typename P, typename T>
 void launch_conv_rows(hipStream_t s, const DecodeRow *rows, uint32_t n, uint64_t max_npix, P *planes, T *pixels, int *status) {
     const uint32_t bx = (uint32_t)std::min<uint64_t>((max_npix + 255) / 256, 1024u);
     if (!bx) return;
-    for (uint32_t r0 = 0; r0 < n; r0 += 65535u) {
-        const uint32_t cnt = std::min(n - r0, 65535u);
+    for (uint32_t r0 = 0; r0 < n; r0 += GRID_ROWS) {
+        const uint32_t cnt = std::min(n - r0, GRID_ROWS);
         if constexpr (sizeof(T) == 1)
             hipLaunchKernelGGL(k_ycocg8_to_rgb<DecMixed>, dim3(bx, cnt), dim3(256), 0, s, planes, pixels, DecMixed{rows + r0}, status);
         else
@@ -2048,38 +2012,20 @@ hipError_t launch_decode8(hipStream_t s, const uint8_t *streams, const uint64_t 
                           uint32_t W, uint32_t H, uint32_t color, uint8_t *pixels, int16_t *planes, int *status) {
     if (n == 0) return hipSuccess;
     const uint32_t lds = decode8_lds_bytes(W, color);
-    if (lds > 64u * 1024u) {
-        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&k_decode8<DecUniform>),
-                                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)DECODE_LDS_LIMIT);
-        if (e != hipSuccess) return e;
-    }
+    const hipError_t e = raise_lds(&k_decode8<DecUniform>, lds);
+    if (e != hipSuccess) return e;
     hipLaunchKernelGGL(k_decode8<DecUniform>, dim3(n), dim3(64), lds, s, streams, offsets, lens, DecUniform{W, H, color}, pixels, planes,
                        status);
-    if (color) {
-        const uint64_t npix = (uint64_t)W * H;
-        const uint32_t bx = (uint32_t)std::min<uint64_t>((npix + 255) / 256, 1024u);
-        if (bx) hipLaunchKernelGGL(k_ycocg8_to_rgb<ConvUniform>, dim3(bx, n), dim3(256), 0, s, planes, pixels, ConvUniform{(uint32_t)npix}, status);
-    }
+    if (color) launch_conv_uniform(s, n, W, H, planes, pixels, status);
     return hipGetLastError();
 }
-
-namespace {
-
-// the dynamic LDS of an indexed wave kernel (k_decode8_seg, k_decode8_region), with the kernel's limit raised where it needs more than 64 KiB
-hipError_t indexed_lds(const void *kernel, uint32_t W, uint32_t color, uint32_t &lds) {
-    lds = decode8_lds_bytes(W, color);
-    if (lds <= 64u * 1024u) return hipSuccess;
-    return hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)DECODE_LDS_LIMIT);
-}
-
-}  // namespace
 
 hipError_t launch_decode8_seg(hipStream_t s, const uint8_t *streams, const uint64_t *offsets, const uint64_t *lens, const uint8_t *index,
                               uint64_t index_stride, uint32_t n, uint32_t W, uint32_t H, uint32_t color, uint32_t segment_pixels, uint32_t K,
                               uint8_t *pixels, int16_t *planes, int *seg_status, int *status) {
     if (n == 0) return hipSuccess;
-    uint32_t lds;
-    const hipError_t e = indexed_lds(reinterpret_cast<const void *>(&k_decode8_seg), W, color, lds);
+    const uint32_t lds = decode8_lds_bytes(W, color);
+    const hipError_t e = raise_lds(&k_decode8_seg, lds);
     if (e != hipSuccess) return e;
     const uint32_t per = (color ? 3u : 1u) * std::max(K, 1u);  // (n * per < 2^31: the caller's check)
     hipLaunchKernelGGL(k_decode8_seg, dim3(n * per), dim3(64), lds, s, streams, offsets, lens, index, index_stride, DecUniform{W, H, color},
@@ -2102,46 +2048,35 @@ hipError_t launch_decode8_seg_lanes(hipStream_t s, const uint8_t *streams, const
     return hipGetLastError();
 }
 
-hipError_t launch_seg_finish(hipStream_t s, uint32_t n, uint32_t W, uint32_t H, uint32_t color, uint32_t K, uint8_t *pixels, int16_t *planes,
-                             const int *seg_status, int *status) {
+template <typename P, typename T>
+hipError_t launch_seg_finish(hipStream_t s, uint32_t n, uint32_t W, uint32_t H, uint32_t color, uint32_t K, T *pixels, P *planes, const int *seg_status,
+                             int *status) {
     if (n == 0) return hipSuccess;
     hipLaunchKernelGGL(k_seg_status, dim3(n), dim3(64), 0, s, seg_status, (const RegionRow *)nullptr, (color ? 3u : 1u) * std::max(K, 1u), status);
-    if (color) {
-        const uint64_t npix = (uint64_t)W * H;
-        const uint32_t bx = (uint32_t)std::min<uint64_t>((npix + 255) / 256, 1024u);
-        if (bx) hipLaunchKernelGGL(k_ycocg8_to_rgb<ConvUniform>, dim3(bx, n), dim3(256), 0, s, planes, pixels, ConvUniform{(uint32_t)npix}, status);
-    }
+    if (color) launch_conv_uniform(s, n, W, H, planes, pixels, status);
     return hipGetLastError();
 }
+template hipError_t launch_seg_finish(hipStream_t, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t, uint8_t *, int16_t *, const int *, int *);
+template hipError_t launch_seg_finish(hipStream_t, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t, uint16_t *, int32_t *, const int *, int *);
 
 hipError_t launch_decode8_regions(hipStream_t s, const uint8_t *streams, const uint64_t *offsets, const uint64_t *lens, const uint8_t *index,
                                   uint64_t index_stride, uint32_t W, uint32_t H, uint32_t color, uint32_t segment_pixels, uint32_t K,
-                                  const RegionRow *rows, uint32_t nregions, const RegionItem *items, uint32_t nitems, uint64_t max_crop,
-                                  uint8_t *pixels, int16_t *planes, int *item_status, int *status) {
-    if (nregions == 0 || nitems == 0) return hipSuccess;
-    uint32_t lds;
-    const hipError_t e = indexed_lds(reinterpret_cast<const void *>(&k_decode8_region), W, color, lds);
+                                  const RegionRow *rows, const RegionItem *items, uint32_t nitems, uint8_t *pixels, int16_t *planes,
+                                  int *item_status) {
+    if (nitems == 0) return hipSuccess;
+    const uint32_t lds = decode8_lds_bytes(W, color);
+    const hipError_t e = raise_lds(&k_decode8_region, lds);
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(k_decode8_region, dim3(nitems), dim3(64), lds, s, streams, offsets, lens, index, index_stride, DecUniform{W, H, color},
                        segment_pixels, K, rows, items, pixels, planes, item_status);
-    hipLaunchKernelGGL(k_seg_status, dim3(nregions), dim3(64), 0, s, item_status, rows, 0u, status);
-    // the crops differ in size: one launch (per 65 535 regions) sized by the largest, a region's blocks stride over its own w * h
-    const uint32_t bx = (uint32_t)std::min<uint64_t>((max_crop + 255) / 256, 1024u);
-    if (color && bx)
-        for (uint32_t r0 = 0; r0 < nregions; r0 += 65535u)
-            hipLaunchKernelGGL(k_ycocg8_to_rgb<ConvRegion>, dim3(bx, std::min(nregions - r0, 65535u)), dim3(256), 0, s, planes, pixels,
-                               ConvRegion{rows, r0}, status);
     return hipGetLastError();
 }
 
 hipError_t launch_decode8_rows(hipStream_t s, const uint8_t *streams, const uint64_t *offsets, const uint64_t *lens, const DecodeRow *rows,
                                uint32_t n, uint32_t lds, uint64_t max_npix, bool any_rgb, uint8_t *pixels, int16_t *planes, int *status) {
     if (n == 0) return hipSuccess;
-    if (lds > 64u * 1024u) {
-        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&k_decode8<DecMixed>),
-                                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)DECODE_LDS_LIMIT);
-        if (e != hipSuccess) return e;
-    }
+    const hipError_t e = raise_lds(&k_decode8<DecMixed>, lds);
+    if (e != hipSuccess) return e;
     hipLaunchKernelGGL(k_decode8<DecMixed>, dim3(n), dim3(64), lds, s, streams, offsets, lens, DecMixed{rows}, pixels, planes, status);
     if (any_rgb) launch_conv_rows(s, rows, n, max_npix, planes, pixels, status);
     return hipGetLastError();
@@ -2168,11 +2103,8 @@ hipError_t launch_decode16_rows(hipStream_t s, const uint8_t *streams, const uin
                                 uint32_t n, uint32_t lds, uint64_t max_npix, bool any_rgb, uint16_t *pixels, int32_t *planes, uint32_t *table,
                                 uint32_t epoch0, int *status) {
     if (n == 0) return hipSuccess;
-    if (lds > 64u * 1024u) {
-        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&k_decode16<DecMixed>),
-                                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)DECODE_LDS_LIMIT);
-        if (e != hipSuccess) return e;
-    }
+    const hipError_t e = raise_lds(&k_decode16<DecMixed>, lds);
+    if (e != hipSuccess) return e;
     hipLaunchKernelGGL(k_decode16<DecMixed>, dim3(n), dim3(64), lds, s, streams, offsets, lens, DecMixed{rows}, pixels, planes, table, epoch0,
                        status);
     if (any_rgb) launch_conv_rows(s, rows, n, max_npix, planes, pixels, status);
@@ -2191,8 +2123,8 @@ void launch_conv_views(hipStream_t s, const DecodeRow *rows, uint32_t n, uint64_
     if (!cv.strided) return launch_conv_rows(s, rows, n, max_npix, planes, (T *)nullptr, status);
     const uint32_t bx = (uint32_t)std::min<uint64_t>((max_npix + 255) / 256, 1024u);
     if (!bx) return;
-    for (uint32_t r0 = 0; r0 < n; r0 += 65535u) {
-        const uint32_t cnt = std::min(n - r0, 65535u);
+    for (uint32_t r0 = 0; r0 < n; r0 += GRID_ROWS) {
+        const uint32_t cnt = std::min(n - r0, GRID_ROWS);
         const ConvStrided g{{rows + r0}, cv.views + r0};
         if constexpr (sizeof(T) == 1)
             hipLaunchKernelGGL(k_ycocg8_to_rgb<ConvStrided>, dim3(bx, cnt), dim3(256), 0, s, planes, (T *)nullptr, g, status);
@@ -2228,8 +2160,8 @@ hipError_t launch_scatter_views(hipStream_t s, const ScatterRow *rows, uint32_t 
     if (!n || !max_row_samples || !max_h) return hipSuccess;
     const uint32_t bx = std::max(1u, std::min((max_row_samples + 255u) / 256u, 64u));
     const uint32_t by = std::min(max_h, 1024u);
-    for (uint32_t r0 = 0; r0 < n; r0 += 65535u)
-        hipLaunchKernelGGL((k_scatter_view<T>), dim3(bx, by, std::min(n - r0, 65535u)), dim3(256), 0, s, rows + r0, status);
+    for (uint32_t r0 = 0; r0 < n; r0 += GRID_ROWS)
+        hipLaunchKernelGGL((k_scatter_view<T>), dim3(bx, by, std::min(n - r0, GRID_ROWS)), dim3(256), 0, s, rows + r0, status);
     return hipGetLastError();
 }
 template hipError_t launch_scatter_views<uint8_t>(hipStream_t, const ScatterRow *, uint32_t, uint32_t, uint32_t, const int *);
@@ -2239,10 +2171,8 @@ hipError_t launch_decode8_rows_views(hipStream_t s, const uint8_t *streams, cons
                                      uint32_t n, uint32_t lds, uint64_t max_npix, bool any_rgb, int16_t *planes, int *status, const DecodeViews &dv) {
     if (n == 0) return hipSuccess;
     const void *kernel = dv.pitched ? reinterpret_cast<const void *>(&k_decode8<DecPitched>) : reinterpret_cast<const void *>(&k_decode8<DecMixed>);
-    if (lds > 64u * 1024u) {
-        const hipError_t e = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)DECODE_LDS_LIMIT);
-        if (e != hipSuccess) return e;
-    }
+    const hipError_t e = raise_lds(kernel, lds);
+    if (e != hipSuccess) return e;
     if (dv.pitched)
         hipLaunchKernelGGL(k_decode8<DecPitched>, dim3(n), dim3(64), lds, s, streams, offsets, lens, DecPitched{{rows}, dv.views}, (uint8_t *)nullptr,
                            planes, status);
@@ -2257,10 +2187,8 @@ hipError_t launch_decode16_rows_views(hipStream_t s, const uint8_t *streams, con
                                       int *status, const DecodeViews &dv) {
     if (n == 0) return hipSuccess;
     const void *kernel = dv.pitched ? reinterpret_cast<const void *>(&k_decode16<DecPitched>) : reinterpret_cast<const void *>(&k_decode16<DecMixed>);
-    if (lds > 64u * 1024u) {
-        const hipError_t e = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)DECODE_LDS_LIMIT);
-        if (e != hipSuccess) return e;
-    }
+    const hipError_t e = raise_lds(kernel, lds);
+    if (e != hipSuccess) return e;
     if (dv.pitched)
         hipLaunchKernelGGL(k_decode16<DecPitched>, dim3(n), dim3(64), lds, s, streams, offsets, lens, DecPitched{{rows}, dv.views},
                            (uint16_t *)nullptr, planes, table, epoch0, status);
@@ -2310,25 +2238,27 @@ hipError_t launch_decode8_seg_views(hipStream_t s, const uint8_t *streams, const
                                     const IndexViewRow *rows, const IndexViewItem *items, uint32_t nitems, uint32_t lds, int16_t *planes,
                                     int *item_status) {
     if (nitems == 0) return hipSuccess;
-    if (lds > 64u * 1024u) {
-        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&k_decode8_seg_views), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                                 (int)DECODE_LDS_LIMIT);
-        if (e != hipSuccess) return e;
-    }
+    const hipError_t e = raise_lds(&k_decode8_seg_views, lds);
+    if (e != hipSuccess) return e;
     hipLaunchKernelGGL(k_decode8_seg_views, dim3(nitems), dim3(64), lds, s, streams, offsets, lens, index, rows, items, planes, item_status);
     return hipGetLastError();
 }
 
+template <typename P, typename T>
 hipError_t launch_seg_views_finish(hipStream_t s, uint32_t n, const RegionRow *regions, const int *item_status, const DecodeRow *conv,
-                                   const ViewRow *views, uint64_t max_npix, int16_t *planes, int *status) {
+                                   const ViewRow *views, uint64_t max_npix, P *planes, int *status) {
     if (n == 0) return hipSuccess;
     hipLaunchKernelGGL(k_seg_status, dim3(n), dim3(64), 0, s, item_status, regions, 0u, status);
-    if (max_npix) launch_conv_views<int16_t, uint8_t>(s, conv, n, max_npix, planes, status, DecodeViews{views, false, true});
+    if (max_npix) launch_conv_views<P, T>(s, conv, n, max_npix, planes, status, DecodeViews{views, false, true});
     return hipGetLastError();
 }
+template hipError_t launch_seg_views_finish<int16_t, uint8_t>(hipStream_t, uint32_t, const RegionRow *, const int *, const DecodeRow *, const ViewRow *,
+                                                              uint64_t, int16_t *, int *);
+template hipError_t launch_seg_views_finish<int32_t, uint16_t>(hipStream_t, uint32_t, const RegionRow *, const int *, const DecodeRow *, const ViewRow *,
+                                                               uint64_t, int32_t *, int *);
 
 // ------------------------------------------------------------------------------------------
-// felics_decompress_batch_device_indexed16: a pass of k_decode16_seg; the call's tail.
+// felics_decompress_batch_device_indexed16: a pass of k_decode16_seg (its tail: launch_seg_finish).
 // ------------------------------------------------------------------------------------------
 
 hipError_t launch_decode16_seg(hipStream_t s, const uint8_t *streams, const uint64_t *offsets, const uint64_t *lens, const uint8_t *index,
@@ -2337,28 +2267,15 @@ hipError_t launch_decode16_seg(hipStream_t s, const uint8_t *streams, const uint
                                int *seg_status, unsigned long long *rows_loaded) {
     if (nitems == 0) return hipSuccess;
     const uint32_t lds = decode16_lds_bytes(W);
-    if (lds > 64u * 1024u) {
-        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&k_decode16_seg), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                                 (int)DECODE_LDS_LIMIT);
-        if (e != hipSuccess) return e;
-    }
+    const hipError_t e = raise_lds(&k_decode16_seg, lds);
+    if (e != hipSuccess) return e;
     hipLaunchKernelGGL(k_decode16_seg, dim3(nitems), dim3(64), lds, s, streams, offsets, lens, index, idx_offsets, idx_lens, DecUniform{W, H, color},
                        segment_pixels, K, item0, pixels, planes, table, epoch, seg_status, rows_loaded);
     return hipGetLastError();
 }
 
-hipError_t launch_seg16_finish(hipStream_t s, uint32_t n, uint32_t W, uint32_t H, uint32_t color, uint32_t K, uint16_t *pixels, int32_t *planes,
-                               const int *seg_status, int *status) {
-    if (n == 0) return hipSuccess;
-    hipLaunchKernelGGL(k_seg_status, dim3(n), dim3(64), 0, s, seg_status, (const RegionRow *)nullptr, (color ? 3u : 1u) * std::max(K, 1u), status);
-    if (color)
-        for (uint32_t i0 = 0; i0 < n; i0 += 65535u)  // (the conversion takes the stream from blockIdx.y)
-            launch_conv_uniform(s, std::min(n - i0, 65535u), W, H, planes + (uint64_t)i0 * 3u * W * H, pixels + (uint64_t)i0 * 3u * W * H, status + i0);
-    return hipGetLastError();
-}
-
 // ------------------------------------------------------------------------------------------
-// felics_decompress_regions_device_indexed16: a pass of k_decode16_region; the call's tail.
+// felics_decompress_regions_device_indexed16: a pass of k_decode16_region; the finish of both region calls.
 // ------------------------------------------------------------------------------------------
 
 hipError_t launch_decode16_regions(hipStream_t s, const uint8_t *streams, const uint64_t *offsets, const uint64_t *lens, const uint8_t *index,
@@ -2368,52 +2285,42 @@ hipError_t launch_decode16_regions(hipStream_t s, const uint8_t *streams, const 
                                    unsigned long long *rows_loaded) {
     if (nitems == 0) return hipSuccess;
     const uint32_t lds = decode16_lds_bytes(W);
-    if (lds > 64u * 1024u) {
-        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&k_decode16_region), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                                 (int)DECODE_LDS_LIMIT);
-        if (e != hipSuccess) return e;
-    }
+    const hipError_t e = raise_lds(&k_decode16_region, lds);
+    if (e != hipSuccess) return e;
     hipLaunchKernelGGL(k_decode16_region, dim3(nitems), dim3(64), lds, s, streams, offsets, lens, index, idx_offsets, idx_lens,
                        DecUniform{W, H, color}, segment_pixels, K, rows, items, item0, pixels, planes, table, epoch, item_status, rows_loaded);
     return hipGetLastError();
 }
 
-hipError_t launch_regions16_finish(hipStream_t s, const RegionRow *rows, uint32_t nregions, uint64_t max_crop, uint8_t *pixels, int32_t *planes,
-                                   const int *item_status, int *status) {
+template <typename P, typename T>
+hipError_t launch_regions_finish(hipStream_t s, const RegionRow *rows, uint32_t nregions, uint64_t max_crop, T *pixels, P *planes,
+                                 const int *item_status, int *status) {
     if (nregions == 0) return hipSuccess;
     hipLaunchKernelGGL(k_seg_status, dim3(nregions), dim3(64), 0, s, item_status, rows, 0u, status);
-    // the crops differ in size: one launch (per 65 535 regions) sized by the largest, a region's blocks stride over its own w * h
+    // the crops differ in size: one launch (per GRID_ROWS regions) sized by the largest, a region's blocks stride over its own w * h
     const uint32_t bx = (uint32_t)std::min<uint64_t>((max_crop + 255) / 256, 1024u);
-    if (bx)
-        for (uint32_t r0 = 0; r0 < nregions; r0 += 65535u)
-            hipLaunchKernelGGL(k_ycocg16_to_rgb<ConvRegion>, dim3(bx, std::min(nregions - r0, 65535u)), dim3(256), 0, s, planes,
-                               reinterpret_cast<uint16_t *>(pixels), ConvRegion{rows, r0}, status);
+    for (uint32_t r0 = 0; bx && r0 < nregions; r0 += GRID_ROWS) {
+        const dim3 grid(bx, std::min(nregions - r0, GRID_ROWS));
+        if constexpr (sizeof(T) == 1) hipLaunchKernelGGL(k_ycocg8_to_rgb<ConvRegion>, grid, dim3(256), 0, s, planes, pixels, ConvRegion{rows, r0}, status);
+        else hipLaunchKernelGGL(k_ycocg16_to_rgb<ConvRegion>, grid, dim3(256), 0, s, planes, pixels, ConvRegion{rows, r0}, status);
+    }
     return hipGetLastError();
 }
+template hipError_t launch_regions_finish(hipStream_t, const RegionRow *, uint32_t, uint64_t, uint8_t *, int16_t *, const int *, int *);
+template hipError_t launch_regions_finish(hipStream_t, const RegionRow *, uint32_t, uint64_t, uint16_t *, int32_t *, const int *, int *);
 
 // ------------------------------------------------------------------------------------------
-// felics_decompress_views_device_indexed16: a launch of k_decode16_seg_views; a stream pass's tail.
+// felics_decompress_views_device_indexed16: a launch of k_decode16_seg_views (a stream pass's tail: launch_seg_views_finish).
 // ------------------------------------------------------------------------------------------
 
 hipError_t launch_decode16_seg_views(hipStream_t s, const uint8_t *streams, const uint64_t *offsets, const uint64_t *lens, const uint8_t *index,
                                      const uint64_t *idx_lens, const IndexViewRow *rows, const IndexViewItem *items, uint32_t nitems, uint32_t lds,
                                      int32_t *planes, uint32_t *table, uint32_t epoch, int *item_status, unsigned long long *rows_loaded) {
     if (nitems == 0) return hipSuccess;
-    if (lds > 64u * 1024u) {
-        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&k_decode16_seg_views), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                                 (int)DECODE_LDS_LIMIT);
-        if (e != hipSuccess) return e;
-    }
+    const hipError_t e = raise_lds(&k_decode16_seg_views, lds);
+    if (e != hipSuccess) return e;
     hipLaunchKernelGGL(k_decode16_seg_views, dim3(nitems), dim3(64), lds, s, streams, offsets, lens, index, idx_lens, rows, items, planes, table,
                        epoch, item_status, rows_loaded);
-    return hipGetLastError();
-}
-
-hipError_t launch_seg16_views_finish(hipStream_t s, uint32_t n, const RegionRow *regions, const int *item_status, const DecodeRow *conv,
-                                     const ViewRow *views, uint64_t max_npix, int32_t *planes, int *status) {
-    if (n == 0) return hipSuccess;
-    hipLaunchKernelGGL(k_seg_status, dim3(n), dim3(64), 0, s, item_status, regions, 0u, status);
-    if (max_npix) launch_conv_views<int32_t, uint16_t>(s, conv, n, max_npix, planes, status, DecodeViews{views, false, true});
     return hipGetLastError();
 }
 

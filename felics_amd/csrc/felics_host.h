@@ -252,6 +252,14 @@ namespace felics {
 
 int hip_fail(felics_ctx *ctx, hipError_t e, const char *what);  // sets ctx->err, returns FELICS_E_HIP
 
+// What every felics_get_*_stats(ctx, out, out_size) does: the context's counts `member`, as many bytes as both sides know
+template <typename S>
+int copy_stats(const felics_ctx *ctx, S felics_ctx::*member, S *out, size_t out_size) {
+    if (!ctx || !out) return FELICS_E_INVALID_ARGUMENT;
+    memcpy(out, &(ctx->*member), std::min(out_size, sizeof(S)));
+    return FELICS_OK;
+}
+
 // ---- felics_context.cpp
 int wait_event(felics_ctx *ctx, hipEvent_t ev, const char *what);
 int sync_lane(felics_ctx *ctx, Lane &l);

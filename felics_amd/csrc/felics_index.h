@@ -6,6 +6,10 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include <algorithm>
+#include <new>
+#include <vector>
+
 #include "../../include/felics.h"
 
 #ifdef __HIPCC__
@@ -240,6 +244,76 @@ FELICS_IDX_HD inline bool region_needs(uint32_t W, uint64_t npix, uint32_t seg, 
 FELICS_IDX_HD inline void region_span(uint32_t W, uint32_t seg, const felics_region &r, uint32_t &first, uint32_t &last) {
     first = (uint32_t)(((uint64_t)r.y * W + r.x) / seg);
     last = (uint32_t)((region_last(W, r) - 1) / seg);
+}
+
+// The plan of a region call, 8- or 16-bit alike (felics_decompress_regions_device_indexed / _indexed16; index_fuzz checks it under the
+// sanitizers): one wave per work item = (region, plane, needed segment).  A region's items are contiguous, in (plane, segment)
+// order; an item whose segment is REGION_HEADER_ONLY makes the checks of its stream's header and index header and nothing else (the
+// one item of an empty region).  Crops are dense and back to back: out_off in BYTES of the depth's sample; RGB crops go through
+// crop-sized planes at plane_off (SAMPLES of the depth's plane type, three planes of w * h), converted where status[region] is clean.
+constexpr uint32_t REGION_HEADER_ONLY = 0xFFFFFFFFu;
+struct RegionRow {
+    uint32_t stream;         // index into offsets / lens and of the index
+    uint32_t x, y, w, h;
+    uint32_t item0, nitems;  // its items: item0 .. item0 + nitems - 1, nitems >= 1
+    uint32_t pad;
+    uint64_t out_off, plane_off;
+};
+struct RegionItem {
+    uint32_t region, plane, seg;
+};
+struct RegionPlan {
+    std::vector<RegionRow> rows;
+    std::vector<RegionItem> items;
+    uint64_t plane_samples = 0;  // of all the RGB crops' planes
+    uint64_t max_crop = 0;       // the largest w * h of an RGB region (0: gray)
+    uint64_t walked = 0, skipped = 0, pixels_walked = 0;  // segments named / not named, pixels the named ones walk (per plane each)
+};
+// n requests on streams of W x H pixels, `planes` planes, segments of segment_pixels; sample_bytes: of an output sample.
+// out_offsets (may be null): where crop r starts.  0, FELICS_E_UNSUPPORTED past 2^31 - 1 items (one block per item, 32-bit item
+// numbers) or FELICS_E_IO (no memory).
+inline int region_plan(uint32_t W, uint32_t H, uint32_t segment_pixels, uint32_t planes, uint32_t sample_bytes, const felics_region *regions, size_t n,
+                       uint64_t *out_offsets, RegionPlan &P) {
+    const uint64_t npix = (uint64_t)W * H;
+    std::vector<uint32_t> segs;
+    uint64_t out_at = 0;
+    try {
+        P.rows.reserve(n);
+        for (size_t r = 0; r < n; r++) {
+            const felics_region &g = regions[r];
+            segs.clear();
+            uint64_t stop_at = 0;
+            if (!region_empty(g)) {
+                uint32_t first, last;
+                region_span(W, segment_pixels, g, first, last);
+                for (uint32_t j = first; j <= last; j++)
+                    if (region_needs(W, npix, segment_pixels, g, j)) segs.push_back(j);
+                stop_at = region_last(W, g);
+            }
+            const uint64_t cnt = segs.empty() ? 1 : (uint64_t)planes * segs.size();
+            if (P.items.size() + cnt > 0x7FFFFFFFull) return FELICS_E_UNSUPPORTED;
+            const uint64_t cpix = (uint64_t)g.w * g.h;
+            P.rows.push_back(RegionRow{g.stream, g.x, g.y, g.w, g.h, (uint32_t)P.items.size(), (uint32_t)cnt, 0, out_at, P.plane_samples});
+            if (out_offsets) out_offsets[r] = out_at;
+            out_at += cpix * planes * sample_bytes;
+            if (planes == 3) {
+                P.plane_samples += cpix * 3;
+                P.max_crop = std::max(P.max_crop, cpix);
+            }
+            if (segs.empty()) P.items.push_back(RegionItem{(uint32_t)r, 0, REGION_HEADER_ONLY});
+            for (uint32_t c = 0; c < planes && !segs.empty(); c++)
+                for (const uint32_t j : segs) P.items.push_back(RegionItem{(uint32_t)r, c, j});
+            for (const uint32_t j : segs) {
+                const uint64_t p0 = (uint64_t)j * segment_pixels;
+                P.pixels_walked += (std::min({npix, p0 + segment_pixels, stop_at}) - p0) * planes;
+            }
+            P.walked += (uint64_t)planes * segs.size();
+        }
+    } catch (const std::bad_alloc &) {
+        return FELICS_E_IO;
+    }
+    P.skipped = (uint64_t)n * planes * ((npix + segment_pixels - 1) / segment_pixels) - P.walked;
+    return FELICS_OK;
 }
 
 // ---- views (felics.h "Restart index: views and mixed shapes"): what felics_decompress_views_device_indexed's host side, its kernel's

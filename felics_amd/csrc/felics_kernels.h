@@ -8,6 +8,7 @@
 
 #include <algorithm>
 
+#include "felics_index.h"
 #include "felics_lanetable.h"
 
 namespace felics {
@@ -346,32 +347,27 @@ size_t index8_lanes_table_bytes(uint64_t items, uint32_t color);
 hipError_t launch_decode8_seg_lanes(hipStream_t s, const uint8_t *streams, const uint64_t *offsets, const uint64_t *lens, const uint8_t *index,
                                     uint64_t index_stride, uint32_t W, uint32_t H, uint32_t color, uint32_t segment_pixels, uint32_t K,
                                     uint32_t wave0, uint32_t nwaves, uint8_t *pixels, int16_t *planes, uint32_t *table, int *seg_status);
-hipError_t launch_seg_finish(hipStream_t s, uint32_t n, uint32_t W, uint32_t H, uint32_t color, uint32_t K, uint8_t *pixels, int16_t *planes,
-                             const int *seg_status, int *status);
+// The finishes of the three indexed call kinds, for both depths: P is the type of an RGB plane's sample, T the pixel's -- <int16_t,
+// uint8_t> for 8-bit streams, <int32_t, uint16_t> for 16-bit ones (the instantiations felics_gpudecode.hip holds).  Each is
+// k_seg_status, then the conversion of the clean RGB rows in grid rows of at most 65 535.
+// Dense (streams 0 .. n - 1 of one shape): status[i] = stream i's first failing word in (plane, segment) order.
+template <typename P, typename T>
+hipError_t launch_seg_finish(hipStream_t s, uint32_t n, uint32_t W, uint32_t H, uint32_t color, uint32_t K, T *pixels, P *planes, const int *seg_status,
+                             int *status);
 // Regions of such streams (felics_decompress_regions_device_indexed, felics.h "Restart index: regions"): one wave per work item =
-// (region, plane, needed segment), k_decode8_region: k_decode8_seg's walk with the region sink (it stops behind the region's last
-// pixel and writes the samples inside the region to the crop).  A region's items are contiguous, in (plane, segment) order; an item whose
-// segment is REGION_HEADER_ONLY makes the checks of its stream's header and index header and nothing else (the one item of an empty
-// region).  Crops are dense: gray at pixels + out_off (bytes), RGB through crop-sized int16 planes at planes + plane_off (three
-// planes of w * h samples), converted by k_ycocg8_to_rgb where status[region] is clean.
-constexpr uint32_t REGION_HEADER_ONLY = 0xFFFFFFFFu;
-struct RegionRow {
-    uint32_t stream;         // index into offsets / lens and of the index
-    uint32_t x, y, w, h;
-    uint32_t item0, nitems;  // its items: item0 .. item0 + nitems - 1, nitems >= 1
-    uint32_t pad;
-    uint64_t out_off, plane_off;
-};
-struct RegionItem {
-    uint32_t region, plane, seg;
-};
-// nitems < 2^31 items over nregions rows; item_status: a word per item; status[r] = region r's first failing one (k_seg_status
-// over the rows' items); max_crop: the
-// largest w * h of an RGB region (0: gray)
+// (region, plane, needed segment) of the call's plan (felics_index.h: region_plan, RegionRow, RegionItem, REGION_HEADER_ONLY),
+// k_decode8_region: k_decode8_seg's walk with the region sink (it stops behind the region's last pixel and writes the samples inside
+// the region to the crop).  Gray crops at pixels + out_off, RGB ones through crop-sized int16 planes at planes + plane_off.
+// nitems < 2^31 items; item_status: a word per item.
 hipError_t launch_decode8_regions(hipStream_t s, const uint8_t *streams, const uint64_t *offsets, const uint64_t *lens, const uint8_t *index,
                                   uint64_t index_stride, uint32_t W, uint32_t H, uint32_t color, uint32_t segment_pixels, uint32_t K,
-                                  const RegionRow *rows, uint32_t nregions, const RegionItem *items, uint32_t nitems, uint64_t max_crop,
-                                  uint8_t *pixels, int16_t *planes, int *item_status, int *status);
+                                  const RegionRow *rows, const RegionItem *items, uint32_t nitems, uint8_t *pixels, int16_t *planes,
+                                  int *item_status);
+// The region calls' finish, once behind the last launch: status[r] = region r's first failing item (k_seg_status over the rows'
+// items), then the conversion of the clean RGB crops; max_crop: the largest w * h of an RGB region (0: gray).
+template <typename P, typename T>
+hipError_t launch_regions_finish(hipStream_t s, const RegionRow *rows, uint32_t nregions, uint64_t max_crop, T *pixels, P *planes,
+                                 const int *item_status, int *status);
 // Indexed streams of ANY shapes into views (felics_decompress_views_device_indexed, felics.h "Restart index: views and mixed shapes"):
 // one wave per work item = (row, plane, segment), k_decode8_seg_views: k_decode8_seg's walk with the view sink.  A row is one stream
 // of the call that passed the host's checks; the walk's geometry, segment_pixels and K come from the row (what the host read out of
@@ -400,8 +396,9 @@ hipError_t launch_decode8_seg_views(hipStream_t s, const uint8_t *streams, const
 // `regions`, a RegionRow per row of which item0 / nitems are read), then the conversion of the clean RGB rows through their views
 // (conv[r].stream = r: status is per row; a gray row has nothing to convert).  max_npix: the largest W * H of an RGB row (0: none).
 struct DecodeRow;  // (below, with the mixed decode call)
+template <typename P, typename T>
 hipError_t launch_seg_views_finish(hipStream_t s, uint32_t n, const RegionRow *regions, const int *item_status, const DecodeRow *conv,
-                                   const ViewRow *views, uint64_t max_npix, int16_t *planes, int *status);
+                                   const ViewRow *views, uint64_t max_npix, P *planes, int *status);
 // The first 64 bytes of each of n restart indexes (index i at index + idx_offsets[i], a multiple of 16; idx_lens[i] bytes) to
 // out + 64 i, zeros behind an index shorter than that: no byte outside [idx_offsets[i], idx_offsets[i] + idx_lens[i]) is read.
 hipError_t launch_read_index_headers(hipStream_t s, const uint8_t *index, const uint64_t *idx_offsets, const uint64_t *idx_lens, uint32_t n,
@@ -410,28 +407,22 @@ hipError_t launch_read_index_headers(hipStream_t s, const uint8_t *index, const 
 // 16-bit streams"; index i at index + idx_offsets[i], a multiple of 64, idx_lens[i] bytes): k_decode16_seg, one wave per (stream,
 // plane, segment).  A launch is a PASS of the call's n * C * max(K, 1) items: items item0 .. item0 + nitems - 1, wave b on table b of
 // `table` (decode16_table_bytes(nitems) bytes, launch_decode16's buffer and epoch rule: one fresh epoch per pass).  seg_status: a word
-// per item of the call; *rows_loaded += the state rows copied.  launch_seg16_finish is the call's tail for streams 0 .. n - 1:
-// status[i] = stream i's first failing word in (plane, segment) order, then the conversion of the clean RGB frames.
+// per item of the call; *rows_loaded += the state rows copied.  The call's tail is launch_seg_finish.
 hipError_t launch_decode16_seg(hipStream_t s, const uint8_t *streams, const uint64_t *offsets, const uint64_t *lens, const uint8_t *index,
                                const uint64_t *idx_offsets, const uint64_t *idx_lens, uint32_t W, uint32_t H, uint32_t color, uint32_t segment_pixels,
                                uint32_t K, uint32_t item0, uint32_t nitems, uint16_t *pixels, int32_t *planes, uint32_t *table, uint32_t epoch,
                                int *seg_status, unsigned long long *rows_loaded);
-hipError_t launch_seg16_finish(hipStream_t s, uint32_t n, uint32_t W, uint32_t H, uint32_t color, uint32_t K, uint16_t *pixels, int32_t *planes,
-                               const int *seg_status, int *status);
 // Regions of such streams (felics_decompress_regions_device_indexed16, felics.h "Restart index: regions of 16-bit streams"):
 // k_decode16_region, one wave per work item = (region, plane, needed segment) -- k_decode16_seg's walk with the region sink.  The
 // tables are launch_decode8_regions' (RegionRow, RegionItem, REGION_HEADER_ONLY), with out_off in bytes (even) and plane_off in
 // int32 samples of crop-sized planes.  A launch is a PASS: items item0 .. item0 + nitems - 1 of `items`, wave b on table b of `table`
 // (launch_decode16_seg's buffer and epoch rule); item_status: a word per item of the call; *rows_loaded += the state rows copied.
-// launch_regions16_finish is the call's tail, once behind the last pass: status[r] = region r's first failing item (k_seg_status over
-// the rows' items), then the conversion of the clean RGB crops; max_crop: the largest w * h of an RGB region (0: gray).
+// The call's tail, once behind the last pass, is launch_regions_finish.
 hipError_t launch_decode16_regions(hipStream_t s, const uint8_t *streams, const uint64_t *offsets, const uint64_t *lens, const uint8_t *index,
                                    const uint64_t *idx_offsets, const uint64_t *idx_lens, uint32_t W, uint32_t H, uint32_t color,
                                    uint32_t segment_pixels, uint32_t K, const RegionRow *rows, const RegionItem *items, uint32_t item0, uint32_t nitems,
                                    uint8_t *pixels, int32_t *planes, uint32_t *table, uint32_t epoch, int *item_status,
                                    unsigned long long *rows_loaded);
-hipError_t launch_regions16_finish(hipStream_t s, const RegionRow *rows, uint32_t nregions, uint64_t max_crop, uint8_t *pixels, int32_t *planes,
-                                   const int *item_status, int *status);
 // 16-bit streams of ANY shapes through version-2 indexes into views (felics_decompress_views_device_indexed16, felics.h "Restart
 // index: 16-bit streams into views and mixed shapes"): k_decode16_seg_views, one wave per work item = (row, plane, segment) --
 // k_decode16_seg's walk with the view sink, on launch_decode8_seg_views' tables (IndexViewRow, IndexViewItem; index + index_off a
@@ -440,12 +431,10 @@ hipError_t launch_regions16_finish(hipStream_t s, const RegionRow *rows, uint32_
 // k_ycocg16_to_rgb<ConvStrided>.  One launch: `nitems` consecutive items of the work list whose rows all fit `lds` bytes of dynamic
 // LDS (decode16_lds_bytes of the widest), wave b on table b of `table` (decode16_table_bytes(nitems) bytes, launch_decode16_seg's
 // buffer and epoch rule: one fresh epoch per launch); item_status: a word per item of the launch; *rows_loaded += the state rows
-// copied.  launch_seg16_views_finish is launch_seg_views_finish for int32 planes and uint16 views.
+// copied.  A stream pass's tail is launch_seg_views_finish.
 hipError_t launch_decode16_seg_views(hipStream_t s, const uint8_t *streams, const uint64_t *offsets, const uint64_t *lens, const uint8_t *index,
                                      const uint64_t *idx_lens, const IndexViewRow *rows, const IndexViewItem *items, uint32_t nitems, uint32_t lds,
                                      int32_t *planes, uint32_t *table, uint32_t epoch, int *item_status, unsigned long long *rows_loaded);
-hipError_t launch_seg16_views_finish(hipStream_t s, uint32_t n, const RegionRow *regions, const int *item_status, const DecodeRow *conv,
-                                     const ViewRow *views, uint64_t max_npix, int32_t *planes, int *status);
 // The same for 16-bit streams, gray or RGB (k_decode16_lanes): 64 streams per wave, lane = stream; needs W >= 8 and a table of
 // decode16_lanes_table_bytes(n, W, H, color) bytes = n * planes * dec16l_rows(W * H, planes) * 64 (felics_lanetable.h: sized by the
 // pixel count, 512 KB per plane of a 64 x 64 stream, the wave form's 8.4 MB from 32 771 pixels on), zero-initialised ONCE: rows carry

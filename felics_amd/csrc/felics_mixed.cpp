@@ -715,9 +715,7 @@ int felics_surfaces_extent(const felics_surfaces *s, int64_t *lo, int64_t *hi) {
 }
 
 int felics_get_surface_stats(const felics_ctx *ctx, felics_surface_stats *out, size_t out_size) {
-    if (!ctx || !out) return FELICS_E_INVALID_ARGUMENT;
-    memcpy(out, &ctx->sstats, std::min(out_size, sizeof(felics_surface_stats)));
-    return FELICS_OK;
+    return copy_stats(ctx, &felics_ctx::sstats, out, out_size);
 }
 
 constexpr uint64_t SURFACES_MAX_COUNT = 1ull << 24;  // frames of one descriptor (the host keeps a row per frame)
@@ -768,9 +766,7 @@ int felics_view_extent(const felics_view *v, int64_t *lo, int64_t *hi) {
 }
 
 int felics_get_view_stats(const felics_ctx *ctx, felics_view_stats *out, size_t out_size) {
-    if (!ctx || !out) return FELICS_E_INVALID_ARGUMENT;
-    memcpy(out, &ctx->vstats, std::min(out_size, sizeof(felics_view_stats)));
-    return FELICS_OK;
+    return copy_stats(ctx, &felics_ctx::vstats, out, out_size);
 }
 
 int felics_compress_views_device(felics_ctx *ctx, size_t n, const felics_view *views, void *ready_event, void *d_out, size_t d_out_cap,
@@ -821,9 +817,7 @@ int felics_index_plan(size_t n, const felics_view *views, const uint32_t *segmen
 }
 
 int felics_get_index_emit_stats(const felics_ctx *ctx, felics_index_emit_stats *out, size_t out_size) {
-    if (!ctx || !out) return FELICS_E_INVALID_ARGUMENT;
-    memcpy(out, &ctx->iestats, std::min(out_size, sizeof(felics_index_emit_stats)));
-    return FELICS_OK;
+    return copy_stats(ctx, &felics_ctx::iestats, out, out_size);
 }
 
 int felics_compress_views_device_indexed(felics_ctx *ctx, size_t n, const felics_view *views, const uint32_t *segment_pixels,

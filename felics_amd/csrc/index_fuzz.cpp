@@ -12,6 +12,8 @@
 //     admissible view (a pitch, pixel stride 1 or 2, a flipped row or channel axis, interleaved or planar) whose target buffer is
 //     EXACTLY the size of the view's hull, so a store outside it is the sanitizer's to report: on a good pair every sample must be
 //     felics_decompress's and every other byte of the hull untouched; on a mutated or foreign pair any code, no crash.
+// In both modes every stream with a valid header also has the device region calls' plan made for its shape (felics_index.h:
+// region_plan) and checked against felics_region_segments: plan_leg below.
 // `index_fuzz --index16 DIR` runs the 16-bit index's host functions instead (felics_index16.cpp): felics_index16_build at the same
 // two segment sizes; where it succeeds the size is within felics_index16_size_max, the two-call pattern holds,
 // felics_decompress_indexed16 gives felics_decompress's pixels, felics_decompress_region_indexed16 gives the full frame, a seeded
@@ -30,6 +32,7 @@
 #include <vector>
 
 #include "../../include/felics.h"
+#include "felics_index.h"
 
 static bool slurp(const std::string &p, std::vector<uint8_t> &b) {
     FILE *f = fopen(p.c_str(), "rb");
@@ -45,6 +48,68 @@ static bool slurp(const std::string &p, std::vector<uint8_t> &b) {
 static bool ends_with(const std::string &s, const char *suffix) {
     const size_t n = strlen(suffix);
     return s.size() >= n && s.compare(s.size() - n, n, suffix) == 0;
+}
+
+// The region calls' plan (felics_index.h: region_plan, what both device calls upload) for an image of h's shape at segment size seg
+// and `sample_bytes` per output sample, on seeded random regions among which are empty ones, one-pixel ones, the whole image and ones
+// that end on the last pixel: every non-empty region must name exactly felics_region_segments' segments, once per plane, in (plane,
+// segment) order, contiguously; an empty one the single header-only item; the crops back to back in bytes of the sample; `walked` the
+// items that are not header-only.  Returns the regions planned, 0 where the plan is wrong.
+template <typename Next>
+static size_t plan_leg(const felics_header &h, uint32_t seg, uint32_t sample_bytes, Next next) {
+    using namespace felics;
+    const uint32_t W = h.width, H = h.height, planes = h.color_type ? 3 : 1;
+    if ((uint64_t)W * H > 0xFFFFFFFFull) return 1;  // (no call plans such a shape)
+    std::vector<felics_region> regs;
+    regs.push_back(felics_region{0, 0, 0, W, H});            // the whole image (empty if the image is)
+    regs.push_back(felics_region{0, W / 2, H / 2, 0, 0});    // empty
+    regs.push_back(felics_region{0, 0, 0, W, 0});            // empty, one side only
+    if (W && H) {
+        regs.push_back(felics_region{0, W - 1, H - 1, 1, 1});  // the last pixel
+        regs.push_back(felics_region{0, 0, 0, 1, 1});
+        for (int k = 0; k < 8; k++) {
+            felics_region r = {0, (uint32_t)(next() % W), (uint32_t)(next() % H), 0, 0};
+            const bool to_end = k % 4 == 3;  // ends on the last pixel
+            r.w = to_end ? W - r.x : (uint32_t)(1 + next() % std::min<uint64_t>(W - r.x, 300));
+            r.h = to_end ? H - r.y : (uint32_t)(1 + next() % std::min<uint64_t>(H - r.y, 40));
+            if (k == 5) r.w = r.h = 1;
+            regs.push_back(r);
+        }
+    }
+    std::vector<uint64_t> out(regs.size(), ~0ull);
+    RegionPlan P;
+    if (region_plan(W, H, seg, planes, sample_bytes, regs.data(), regs.size(), out.data(), P) != FELICS_OK || P.rows.size() != regs.size()) return 0;
+    const size_t K = (size_t)(((uint64_t)W * H + seg - 1) / seg);
+    std::vector<uint32_t> want(K + 1);
+    uint64_t at = 0, plane_at = 0, header_only = 0, item = 0, max_crop = 0;
+    for (size_t r = 0; r < regs.size(); r++) {
+        const felics_region &g = regs[r];
+        const RegionRow &row = P.rows[r];
+        size_t cnt = 0;
+        if (felics_region_segments(W, H, seg, &g, want.data(), K, &cnt) != FELICS_OK) return 0;
+        const bool empty = g.w == 0 || g.h == 0;
+        if (empty != (cnt == 0) || row.item0 != item || row.nitems != (empty ? 1 : planes * cnt) || out[r] != at || row.out_off != at ||
+            row.plane_off != plane_at || row.stream != g.stream || row.x != g.x || row.y != g.y || row.w != g.w || row.h != g.h)
+            return 0;
+        if (item + row.nitems > P.items.size()) return 0;
+        if (empty) {
+            const RegionItem &it = P.items[item];
+            if (it.region != r || it.plane != 0 || it.seg != REGION_HEADER_ONLY) return 0;
+            header_only++;
+        }
+        for (uint32_t c = 0; !empty && c < planes; c++)
+            for (size_t j = 0; j < cnt; j++) {
+                const RegionItem &it = P.items[item + c * cnt + j];
+                if (it.region != r || it.plane != c || it.seg != want[j]) return 0;
+            }
+        item += row.nitems;
+        at += (uint64_t)g.w * g.h * planes * sample_bytes;
+        if (planes == 3) plane_at += (uint64_t)g.w * g.h * 3, max_crop = std::max(max_crop, (uint64_t)g.w * g.h);
+    }
+    if (item != P.items.size() || P.walked != item - header_only || P.skipped != regs.size() * planes * K - P.walked || P.plane_samples != plane_at ||
+        P.max_crop != max_crop || P.pixels_walked > P.walked * seg)
+        return 0;
+    return regs.size();
 }
 
 // the --index16 mode
@@ -70,7 +135,7 @@ static int fuzz16(const char *dir) {
     while (dirent *e = readdir(d))
         if (e->d_name[0] != '.' && !ends_with(e->d_name, ".idx")) names.push_back(e->d_name);
     closedir(d);
-    size_t built = 0, refused = 0, mutations = 0, mut_accepted = 0, pairs = 0, pairs_ok = 0;
+    size_t built = 0, refused = 0, mutations = 0, mut_accepted = 0, pairs = 0, pairs_ok = 0, plan_streams = 0, plan_regions = 0;
     const size_t cap = 32u << 20;
     std::vector<uint8_t> buf, given, px(cap), ref(cap), index(cap);
     uint64_t rng = 0x9E3779B97F4A7C15ull;
@@ -152,6 +217,17 @@ static int fuzz16(const char *dir) {
         const std::string path = std::string(dir) + "/" + n;
         if (!slurp(path, buf)) continue;
         felics_header h, h2;
+        if (felics_read_header(buf.data(), buf.size(), &h) == FELICS_OK) {  // the region plan, whatever else the stream is good for
+            for (uint32_t seg : {4096u, 12288u}) {
+                const size_t got = plan_leg(h, seg, h.pixel_depth ? 2 : 1, next);
+                if (!got) {
+                    fprintf(stderr, "%s: the region plan at segment %u differs from felics_region_segments or from its own layout rules\n", n.c_str(), seg);
+                    return 1;
+                }
+                plan_regions += got;
+            }
+            plan_streams++;
+        }
         const int rc_plain = felics_decompress(buf.data(), buf.size(), ref.data(), ref.size(), &h);
         if (rc_plain == FELICS_E_BUFFER_TOO_SMALL) continue;  // (larger than this driver's buffers)
         const size_t frame = rc_plain == FELICS_OK ? (size_t)h.width * h.height * (h.color_type ? 3 : 1) * (h.pixel_depth ? 2 : 1) : 0;
@@ -225,6 +301,8 @@ static int fuzz16(const char *dir) {
     }
     printf("index_fuzz --index16: %zu files, %zu indexes built, %zu refused, %zu pairs (%zu accepted), %zu mutations (%zu accepted)\n", names.size(), built,
            refused, pairs, pairs_ok, mutations, mut_accepted);
+    printf("index_fuzz --index16: region plans of %zu streams with a valid header, %zu regions planned as felics_region_segments names them\n", plan_streams,
+           plan_regions);
     return 0;
 }
 
@@ -268,7 +346,7 @@ int main(int argc, char **argv) {
     while (dirent *e = readdir(d))
         if (e->d_name[0] != '.' && !ends_with(e->d_name, ".idx")) names.push_back(e->d_name);
     closedir(d);
-    size_t regions = 0, views = 0, built = 0, refused = 0, mutations = 0, mut_accepted = 0, pairs = 0, pairs_ok = 0;
+    size_t regions = 0, views = 0, built = 0, refused = 0, mutations = 0, mut_accepted = 0, pairs = 0, pairs_ok = 0, plan_streams = 0, plan_regions = 0;
     const size_t cap = 32u << 20;  // decoders and the builder get bounded buffers whatever a header claims
     std::vector<uint8_t> buf, idx, given, px(cap), ref(cap), index(cap);
     uint64_t rng = 0x9E3779B97F4A7C15ull;
@@ -350,6 +428,17 @@ int main(int argc, char **argv) {
         const std::string path = std::string(argv[1]) + "/" + n;
         if (!slurp(path, buf)) continue;
         felics_header h, h2;
+        if (felics_read_header(buf.data(), buf.size(), &h) == FELICS_OK) {  // the region plan, whatever else the stream is good for
+            for (uint32_t seg : {4096u, 12288u}) {
+                const size_t got = plan_leg(h, seg, h.pixel_depth ? 2 : 1, next);
+                if (!got) {
+                    fprintf(stderr, "%s: the region plan at segment %u differs from felics_region_segments or from its own layout rules\n", n.c_str(), seg);
+                    return 1;
+                }
+                plan_regions += got;
+            }
+            plan_streams++;
+        }
         const int rc_plain = felics_decompress(buf.data(), buf.size(), ref.data(), ref.size(), &h);
         if (rc_plain == FELICS_E_BUFFER_TOO_SMALL) continue;  // (larger than this driver's buffers)
         const size_t frame = rc_plain == FELICS_OK ? (size_t)h.width * h.height * (h.color_type ? 3 : 1) * (h.pixel_depth ? 2 : 1) : 0;
@@ -449,5 +538,7 @@ int main(int argc, char **argv) {
     }
     printf("index_fuzz: %zu files, %zu indexes built, %zu refused, %zu pairs (%zu accepted), %zu mutations (%zu accepted), %zu regions, %zu views\n", names.size(),
            built, refused, pairs, pairs_ok, mutations, mut_accepted, regions, views);
+    printf("index_fuzz: region plans of %zu streams with a valid header, %zu regions planned as felics_region_segments names them\n", plan_streams,
+           plan_regions);
     return 0;
 }

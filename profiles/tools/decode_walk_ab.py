@@ -10,12 +10,15 @@ FELICS_TEST_DECODE16_LANES=0 around the call):
   rgb16     64 RGB16 streams of 256 x 256                                              k_decode16<DecUniform>, three planes
   pitched8  the gray8 streams into 512 x 512 views of pitch 576, felics_decompress_views_device   k_decode8<DecPitched>
   mixed8    the gray8 streams through felics_decompress_images_device                  k_decode8<DecMixed>
+  mixed16   the gray16 streams through felics_decompress_images_device                 k_decode16<DecMixed>
   indexed   one 2048 x 2048 gray8 S1 stream, indexed at segment 32 768                 k_decode8_seg
   indexed_rgb  one 1024 x 1024 RGB8 stream, indexed at segment 32 768                  k_decode8_seg, three planes
   regions   64 windows of 256 x 256 at seeded positions over the `indexed` stream, felics_decompress_regions_device_indexed   k_decode8_region
   indexed_views  the `indexed` stream into a 2048 x 2048 view of pitch 2 112, felics_decompress_views_device_indexed   k_decode8_seg_views
   indexed16      one 1024 x 1024 gray16 stream, its index built on the host at segment 32 768, felics_decompress_batch_device_indexed_wide   k_decode16_seg
   indexed16_rgb  one 512 x 512 RGB16 stream, indexed at segment 8 192                  k_decode16_seg, three planes
+  regions16      64 windows of 256 x 256 at seeded positions over the `indexed16` stream, felics_decompress_regions_device_indexed_wide   k_decode16_region
+  indexed_views16  the `indexed16` stream into a 1024 x 1024 view of pitch 1 088 samples, felics_decompress_views_device_indexed_wide   k_decode16_seg_views
 and in the lane form (FELICS_TEST_DECODE_LANES=1, FELICS_TEST_DECODE16_LANES=1 or FELICS_TEST_INDEX_LANES=1 around the call) -- to a
 change of one form the other form's workloads are the control, code it leaves alone:
   lanes8    4 096 gray8 streams of 64 x 64                                             k_decode8_lanes<false, LaneUniform>
@@ -48,13 +51,14 @@ import subprocess
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-WORKLOADS = ("gray8", "rgb8", "gray16", "rgb16", "pitched8", "mixed8", "indexed", "indexed_rgb", "regions", "indexed_views", "indexed16",
-             "indexed16_rgb", "lanes8", "lanes8_rgb", "lanes16",
+WORKLOADS = ("gray8", "rgb8", "gray16", "rgb16", "pitched8", "mixed8", "mixed16", "indexed", "indexed_rgb", "regions", "indexed_views", "indexed16",
+             "indexed16_rgb", "regions16", "indexed_views16", "lanes8", "lanes8_rgb", "lanes16",
              "lanes16_rgb", "lanes8_pitched", "lanes8_mixed", "indexed_lanes", "indexed_lanes_rgb")
 SEGMENT = 32768
 PITCH = 576
 LANE_SEGMENT = 4096
 VIEW_PITCH = 2112
+VIEW16_PITCH = 1088  # samples
 SEGMENT16_RGB = 8192
 LANE_PITCH = 80
 
@@ -107,11 +111,13 @@ def child():
     bigc = synth.rgb8(1024, 1024, 0)[None]
     rng = np.random.default_rng(0)
     windows = [(0, int(x), int(y), 256, 256) for x, y in rng.integers(0, 2048 - 256 + 1, size=(64, 2))]
+    big16 = synth.gray16(1024, 1024, 0)[None]
+    windows16 = [(0, int(x), int(y), 256, 256) for x, y in rng.integers(0, 1024 - 256 + 1, size=(64, 2))]
     small = np.stack([synth.gray8(64, 64, f, "S1") for f in range(4096)])
     sets = {"gray8": encode(g8, 512, 512, 0, 0), "rgb8": encode(c8, 512, 512, 1, 0), "gray16": encode(g16, 512, 512, 0, 1),
             "rgb16": encode(c16, 256, 256, 1, 1), "indexed": encode(big, 2048, 2048, 0, 0, SEGMENT),
             "indexed_rgb": encode(bigc, 1024, 1024, 1, 0, SEGMENT),
-            "indexed16": encode16_indexed(synth.gray16(1024, 1024, 0)[None], 1024, 1024, 0, SEGMENT),
+            "indexed16": encode16_indexed(big16, 1024, 1024, 0, SEGMENT),
             "indexed16_rgb": encode16_indexed(np.stack([synth.gray16(512, 512, c) for c in range(3)], axis=-1)[None], 512, 512, 1, SEGMENT16_RGB),
             "lanes8": encode(small, 64, 64, 0, 0),
             "lanes8_rgb": encode(np.stack([synth.rgb8(64, 64, f) for f in range(1024)]), 64, 64, 1, 0),
@@ -120,20 +126,25 @@ def child():
             "indexed_lanes": encode(np.stack([synth.gray8(256, 256, f, "S1") for f in range(128)]), 256, 256, 0, 0, LANE_SEGMENT),
             "indexed_lanes_rgb": encode(np.stack([synth.rgb8(256, 256, f) for f in range(128)]), 256, 256, 1, 0, LANE_SEGMENT)}
     sets["pitched8"] = sets["mixed8"] = sets["gray8"]
+    sets["mixed16"] = sets["gray16"]
     sets["lanes8_pitched"] = sets["lanes8_mixed"] = sets["lanes8"]
     sets["regions"] = sets["indexed_views"] = sets["indexed"]
+    sets["regions16"] = sets["indexed_views16"] = sets["indexed16"]
     want = {k: v[0].cpu().numpy().view(np.uint8).reshape(-1) for k, v in sets.items()}
     want["regions"] = np.concatenate([big[0, y:y + h, x:x + w].reshape(-1) for _, x, y, w, h in windows])
+    want["regions16"] = np.concatenate([big16[0, y:y + h, x:x + w].reshape(-1) for _, x, y, w, h in windows16]).view(np.uint8)
     mosaics = {"pitched8": torch.zeros((64, 512, PITCH), dtype=torch.uint8, device="cuda"),
                "lanes8_pitched": torch.zeros((4096, 64, LANE_PITCH), dtype=torch.uint8, device="cuda"),
-               "indexed_views": torch.zeros((1, 2048, VIEW_PITCH), dtype=torch.uint8, device="cuda")}
+               "indexed_views": torch.zeros((1, 2048, VIEW_PITCH), dtype=torch.uint8, device="cuda"),
+               "indexed_views16": torch.zeros((1, 1024, VIEW16_PITCH), dtype=torch.int16, device="cuda")}  # (uint16 samples: the bytes are what counts)
     views = {"pitched8": [mosaics["pitched8"][i, :, :512] for i in range(64)],
              "lanes8_pitched": [mosaics["lanes8_pitched"][i, :, :64] for i in range(4096)],
-             "indexed_views": [mosaics["indexed_views"][0, :, :2048]]}
+             "indexed_views": [mosaics["indexed_views"][0, :, :2048]], "indexed_views16": [mosaics["indexed_views16"][0, :, :1024]]}
+    view16 = [(mosaics["indexed_views16"].data_ptr(), 1024, 1024, 0, 1, 2 * VIEW16_PITCH, 2, 0)]
     dest = {k: torch.zeros(len(v), dtype=torch.uint8, device="cuda") for k, v in want.items() if k not in mosaics}
 
     def decoded(name):  # the bytes a call of `name` wrote, as the frames lie
-        return mosaics[name][:, :, :views[name][0].shape[1]].contiguous().view(-1) if name in mosaics else dest[name]
+        return mosaics[name][:, :, :views[name][0].shape[1]].contiguous().view(torch.uint8).view(-1) if name in mosaics else dest[name]
 
     def call(name):
         s = sets[name]
@@ -142,11 +153,16 @@ def child():
         os.environ["FELICS_TEST_INDEX_LANES"] = "1" if name.startswith("indexed_lanes") else "0"
         if name == "indexed_views":
             enc.decompress_arrays_device_indexed(s[1].data_ptr(), s[2], s[3], s[4].data_ptr(), [0], [s[5]], views[name])
+        elif name == "indexed_views16":
+            enc.decompress_views_device_indexed16(s[1].data_ptr(), s[2], s[3], s[4].data_ptr(), s[5], s[6], view16)
+        elif name == "regions16":
+            enc.decompress_regions_device_indexed16(s[1].data_ptr(), s[2], s[3], s[4].data_ptr(), s[5], s[6], windows16, dest[name].data_ptr(),
+                                                    dest[name].numel())
         elif name.startswith("indexed16"):
             enc.decompress_batch_device_indexed16(s[1].data_ptr(), s[2], s[3], s[4].data_ptr(), s[5], s[6], dest[name].data_ptr(), dest[name].numel())
         elif name in mosaics:
             enc.decompress_arrays_device(s[1].data_ptr(), s[2], s[3], views[name])
-        elif name in ("mixed8", "lanes8_mixed"):
+        elif name in ("mixed8", "mixed16", "lanes8_mixed"):
             enc.decompress_images_device(s[1].data_ptr(), s[2], s[3], dest[name].data_ptr(), dest[name].numel())
         elif name == "regions":
             enc.decompress_regions_device_indexed(s[1].data_ptr(), s[2], s[3], s[4].data_ptr(), s[5], windows, dest[name].data_ptr(), dest[name].numel())

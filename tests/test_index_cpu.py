@@ -2,6 +2,7 @@
 the original pixels and a decoder model written here from the format's description; the refusals; index_fuzz under sanitizers."""
 import ctypes as C
 import glob
+import io
 import json
 import os
 import struct
@@ -316,14 +317,19 @@ def test_index_fuzz_under_sanitizers(tmp_path, api, cases):
     d = tmp_path / "corpus"
     d.mkdir()
     rng = np.random.default_rng(99)
-    n = 0
+    n = headers = 0
 
     def put(stream, index=None):
-        nonlocal n
+        nonlocal n, headers
         (d / ("%04d.felics" % n)).write_bytes(stream)
         if index is not None:
             (d / ("%04d.felics.idx" % n)).write_bytes(index)
         n += 1
+        try:  # a stream with a valid header has the region calls' plan made for its shape
+            api.read_header(io.BytesIO(stream))
+            headers += 1
+        except api.DecompressionError:
+            pass
 
     seeds = [cases[k][0][1] for k in ((64, 65, 0), (100, 100, 1), (1, 9000, 0), (4097, 1, 1), (4096, 3, 0), (0, 5, 1), (2048, 5, 1))]
     seeds.append(open(os.path.join(GOLDEN, "6.1.01.tiff.felics"), "rb").read())
@@ -354,3 +360,4 @@ def test_index_fuzz_under_sanitizers(tmp_path, api, cases):
     assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-6000:])
     assert "AddressSanitizer" not in r.stderr and "runtime error" not in r.stderr, r.stderr[-6000:]
     assert "index_fuzz: %d files" % n in r.stdout
+    assert 0 < headers < n and "index_fuzz: region plans of %d streams with a valid header" % headers in r.stdout, r.stdout[-2000:]
