@@ -8,6 +8,8 @@ import os
 import numpy as np
 import pytest
 
+from tests.decode_cases import longest_run_at_k0
+
 pytestmark = pytest.mark.gpu
 
 GOLDEN = os.path.join(os.path.dirname(__file__), "golden")
@@ -83,7 +85,10 @@ def test_extreme_content_and_golden(enc, oracle):
     h, w = 96, 257
     flat = np.full((h, w), 7, np.uint8)
     spikes = flat.copy()
-    spikes[rng.integers(0, h, 200), rng.integers(0, w, 200)] = 255  # long unary runs at k = 0
+    spikes[rng.integers(0, h, 200), rng.integers(0, w, 200)] = 255
+    spikes[0, :8] = 7
+    spikes[0, 3] = 8  # an event of value 0 ahead of the spikes: context 0 learns k = 0, and the first spike is a unary run of 247 ones
+    assert longest_run_at_k0(spikes) >= 247
     checker = ((np.indices((h, w)).sum(0) & 1) * 255).astype(np.uint8)
     ramp = (np.arange(w)[None, :] + np.arange(h)[:, None]).astype(np.uint8)
     imgs = [flat, spikes, checker, ramp]
@@ -184,8 +189,8 @@ def test_baseline_batch_decodes(enc):
 
 def test_sixteen_bit_streams_on_the_device(enc, oracle):
     """16-bit streams never leave the GPU: natural 16-bit files (the golden ones, 256 x 256 and 1081 x 1081), synthetic gray16 and
-    rgb16 frames with more contexts than the LDS cache has rows (evictions, write-backs, reloads), extreme content (65 534-bit
-    codes), two calls in a row on the same tables (epochs), corrupt streams -- against the original pixels and the host decoder."""
+    rgb16 frames with more contexts than the LDS cache has rows (evictions, write-backs, reloads), extreme content (a code of
+    65 528 bits: a unary run of 65 525 ones, asserted from the oracle's trace), two calls in a row on the same tables (epochs), corrupt streams -- against the original pixels and the host decoder."""
     import felics_amd
     import torch
     from PIL import Image
@@ -207,7 +212,10 @@ def test_sixteen_bit_streams_on_the_device(enc, oracle):
     assert all((b == f).all() for b, f in zip(back, rgb))
     quiet = np.full((40, 300), 9, np.uint16)
     spikes = quiet.copy()
-    spikes[rng.integers(0, 40, 60), rng.integers(0, 300, 60)] = 65535  # unary runs of 65 525 ones at k = 0
+    spikes[rng.integers(0, 40, 60), rng.integers(0, 300, 60)] = 65535
+    spikes[0, :8] = 9
+    spikes[0, 3] = 10  # an event of value 0 ahead of the spikes: context 0 learns k = 0, and the first spike is a unary run of 65 525 ones
+    assert longest_run_at_k0(spikes) >= 65525
     _, back = _decode_batch(enc, [oracle.compress(quiet), oracle.compress(spikes)], (40, 300), np.uint16)
     assert (back[0] == quiet).all() and (back[1] == spikes).all()
     # corrupt 16-bit streams: a status for every stream, the good ones intact

@@ -183,14 +183,19 @@ def test_the_table(enc, oracle):
 
 
 def test_long_codes_beside_ordinary_streams(enc, oracle):
-    """A frame of 9s with 60 samples of 65 535 (unary runs of 65 525 ones at k = 0) and the quiet frame in one wave with 62 ordinary
-    streams: the other lanes wait on the long runs and come out unharmed."""
+    """A frame of 9s with 60 samples of 65 535, behind one sample of 10 that teaches context 0 k = 0 (so the first of them is a unary
+    run of 65 525 ones at k = 0, read by lane_rice_long: asserted from the oracle's trace), and the quiet frame in one wave with
+    62 ordinary streams: the other lanes wait on the long runs and come out unharmed."""
     from felics_amd import synth
+    from tests.decode_cases import longest_run_at_k0
 
     rng = np.random.default_rng(12)
     quiet = np.full((40, 300), 9, np.uint16)
     spikes = quiet.copy()
     spikes[rng.integers(0, 40, 60), rng.integers(0, 300, 60)] = 65535
+    spikes[0, :8] = 9
+    spikes[0, 3] = 10
+    assert longest_run_at_k0(spikes) >= 65525
     base = synth.gray16(640, 360, 2)
     imgs = [spikes, quiet] + [base[3 * i:3 * i + 40, 5 * i:5 * i + 300].copy() for i in range(62)]
     with _env(**{VAR: "1"}):
