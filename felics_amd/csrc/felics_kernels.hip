@@ -26,6 +26,7 @@
 #include "felics_device.h"
 #include "felics_kernels.h"
 #include "felics_codes.h"
+#include "felics_pairs.h"
 
 namespace felics {
 
@@ -275,8 +276,10 @@ __device__ __forceinline__ uint32_t field_of(int v, int16_t) { return ((uint32_t
 //   1  k_front: the rank form is a template parameter        2  k_front: scalar row bases, the lane as the loads' one offset
 //   4  k_front: cheap forms in the interior loop             8  k_pack_t: load_group from scalar bases
 //   16 code_pixel: cheap forms
+// and of profiles/pack_pairs.txt (felics_pairs.h: two 8-bit pixels per instruction up to the Rice code):
+//   32 group_codes_k by pairs (k_pack_t's k path)           64 group_codes_w by pairs (its word path)
 #ifndef FELICS_FORMS
-#define FELICS_FORMS 31
+#define FELICS_FORMS 127
 #endif
 #ifndef FELICS_FRONT_WAVES
 #define FELICS_FRONT_WAVES 6  // (gray planes; what the LDS allows.  A/B builds: profiles/tools/variant.sh)
@@ -1313,6 +1316,9 @@ template <typename T> constexpr bool PACK_SHORT_FLUSH = sizeof(T) == 1 || (FELIC
 template <typename T> constexpr bool PACK_WIDE_CLEAR = sizeof(T) == 1 || (FELICS_PACK16_PARTS & 4) != 0;
 // (code_pixel's named forms and load_group_at, profiles/front_pack_forms.txt: the int16 kernels gained spills from either)
 template <typename T> constexpr bool PACK_CODE_FORMS = sizeof(T) == 1 && (FELICS_FORMS & 16) != 0;
+// (the pair builder is for 8-bit samples: an int16 context needs 17 bits, and those kernels spill at the first extra register)
+template <typename T> constexpr bool PACK_PAIRS_K = sizeof(T) == 1 && (FELICS_FORMS & 32) != 0;
+template <typename T> constexpr bool PACK_PAIRS_W = sizeof(T) == 1 && (FELICS_FORMS & 64) != 0;
 
 // Whether this thread's 16-pixel group takes the branch-free path (group_codes), and what that path needs from outside the
 // tile's LDS image: the position of the group's first-column pixel (PACK_PER_THREAD: none) and that pixel's second neighbour
@@ -1474,6 +1480,23 @@ __device__ __forceinline__ PixelCode code_pixel(uint32_t p, uint32_t a, uint32_t
     return pc;
 }
 
+// code_pixel behind the pair builder (felics_pairs.h: pair_codes did two pixels' classification and phased-in code at once): the Rice
+// code of ONE of them, the choice between the two codes and the left-align shift, in 32 bits as above (code_pixel<true>'s forms).
+// val .. len_in = the pixel's half of each of pair_codes' results (pair_value / pair_mask).
+__device__ __forceinline__ PixelCode code_pixel_of_pair(uint32_t val, uint32_t above, uint32_t in_range, uint32_t code_in, uint32_t len_in, uint32_t k,
+                                                        uint32_t K7F) {
+    const uint32_t q = val >> k;
+    const uint32_t ones = K7F >> (31u - q);                                             // q ones (q <= 31)
+    const uint32_t head = bitop3<BT_OR_AND>(ones, ones + 1u, above);                    // `0` / `1` (above) in front of them
+    const uint32_t rice = ((twice(head) - q) << k) + val;                               // then `0` and the k low bits of val
+    const uint32_t len_rice = q + k + 3u;
+    const uint32_t code = bitop3<BT_SEL>(code_in, rice, in_range);
+    PixelCode pc;
+    pc.len = bitop3<BT_SEL>(len_in, len_rice, in_range);
+    pc.c32 = code << (32u - pc.len);
+    return pc;
+}
+
 // The samples a thread's 16-pixel group needs on the branch-free path, straight from memory into registers (the group, the
 // span one row above it, the sample in front of it): coalesced 16-byte loads, a wave reads 1 KB of a row.  The loads are
 // issued at the top of the kernel and first used after the gather of k: their latency hides behind it.
@@ -1541,24 +1564,38 @@ __device__ __forceinline__ uint32_t group_codes_w(const GroupSamples<T> &g, cons
                                                 IX W, uint32_t j0, int special, uint32_t (&c32)[PACK_PER_THREAD],
                                                 uint32_t (&len)[PACK_PER_THREAD], uint32_t &longest) {
     const uint32_t off = threadIdx.x * PACK_PER_THREAD;
-    const uint32_t K31 = vgpr_const(0x80000000u);
-    uint32_t left = field_of(g.before, T());  // the sample in front of the group
+    const uint32_t K31 = vgpr_const(0x80000000u);  // (the pair form: for the first-column pixel below only)
+    [[maybe_unused]] uint32_t left = field_of(g.before, T());  // the sample in front of the group (the scalar form's walk; the pair form selects its left neighbours from the dwords)
     longest = 0;
 #pragma unroll
     for (uint32_t u = 0; u < PACK_PER_THREAD / 4; u++) {  // (four words at a time: sixteen of them at once cost twelve more registers)
         const uint4 c = *reinterpret_cast<const uint4 *>(words + u * (PACK_TILE / 4) + threadIdx.x * 4);  // word_index(off + 4 u ..)
         const uint32_t wq[4] = {c.x, c.y, c.z, c.w};
+        PairCodes pair[2];
+        if constexpr (PACK_PAIRS_W<T>) {  // the dword's two pairs (felics_pairs.h); the left neighbour of its first pixel is in the dword in front
+#pragma unroll
+            for (uint32_t h = 0; h < 2; h++) {
+                const uint32_t ll = (u == 0 && h == 0) ? pair_lefts_first((uint32_t)g.before, g.cw[0]) : pair_lefts(g.cw[u ? u - 1 : 0], g.cw[u], h);
+                pair[h] = pair_codes(pair_samples(g.cw[u], h), ll, pair_samples(g.uw[u], h));
+            }
+        }
 #pragma unroll
         for (uint32_t i = 0; i < 4; i++) {
             const uint32_t j = 4 * u + i;
-            const uint32_t p = field_at(g.cw, j, T());
-            const PixelCode pc = code_in_range(p, left, field_at(g.uw, j, T()), K31);
+            PixelCode pc;
+            if constexpr (PACK_PAIRS_W<T>) {
+                pc.len = pair_value(pair[i >> 1].len_in, i & 1u);
+                pc.c32 = pair_value(pair[i >> 1].code_in, i & 1u) << ((32u - pc.len) & 31u);
+            } else {
+                const uint32_t p = field_at(g.cw, j, T());
+                pc = code_in_range(p, left, field_at(g.uw, j, T()), K31);
+                left = p;
+            }
             const uint32_t lf = wq[i] & 63u;
             const uint32_t in_range = (uint32_t)((int)(lf - 1u) >> 31);  // all ones: the word is 0, no event
             c32[j] = bitop3<BT_SEL>(pc.c32, wq[i] & ~0x1FFu, in_range);
             len[j] = bitop3<BT_SEL>(pc.len, lf, in_range);
             longest = max_u16(longest, len[j]);
-            left = p;
         }
     }
     if (__ballot(j0 < PACK_PER_THREAD) != 0) {  // (wave-uniform: a quarter of the waves of a 4K plane)
@@ -1605,17 +1642,39 @@ __device__ __forceinline__ uint32_t group_codes_k(const GroupSamples<T> &g, cons
         const uint4 c = *reinterpret_cast<const uint4 *>(kq + off);
         kw[0] = c.x; kw[1] = c.y; kw[2] = c.z; kw[3] = c.w;
     }
-    const uint32_t K31 = vgpr_const(0x80000000u), K7F = vgpr_const(0x7FFFFFFFu);
-    uint32_t left = field_of(g.before, T());  // the sample in front of the group
+    const uint32_t K31 = vgpr_const(0x80000000u), K7F = vgpr_const(0x7FFFFFFFu);  // (K31: the scalar form, and the first-column pixel below)
     longest = 0;
+    if constexpr (PACK_PAIRS_K<T>) {
+        // Two pixels at a time up to the Rice code (felics_pairs.h): per dword of samples two pairs; the left neighbour of a dword's first
+        // pixel is byte 3 of the dword in front, or the sample in front of the group.  The Rice code, the choice and the shift per pixel.
 #pragma unroll
-    for (uint32_t j = 0; j < PACK_PER_THREAD; j++) {
-        const uint32_t p = field_at(g.cw, j, T());
-        const PixelCode pc = code_pixel<PACK_CODE_FORMS<T>>(p, left, field_at(g.uw, j, T()), field_at(kw, j, uint8_t()), K31, K7F);
-        c32[j] = pc.c32;
-        len[j] = pc.len;
-        longest = max_u16(longest, pc.len);
-        left = p;
+        for (uint32_t w = 0; w < PACK_PER_THREAD / 4; w++) {
+#pragma unroll
+            for (uint32_t h = 0; h < 2; h++) {
+                const uint32_t ll = (w == 0 && h == 0) ? pair_lefts_first((uint32_t)g.before, g.cw[0]) : pair_lefts(g.cw[w ? w - 1 : 0], g.cw[w], h);
+                const PairCodes pr = pair_codes(pair_samples(g.cw[w], h), ll, pair_samples(g.uw[w], h));
+#pragma unroll
+                for (uint32_t e = 0; e < 2; e++) {
+                    const uint32_t j = 4 * w + 2 * h + e;
+                    const PixelCode pc = code_pixel_of_pair(pair_value(pr.val, e), pair_mask(pr.above, e), pair_mask(pr.in_range, e),
+                                                            pair_value(pr.code_in, e), pair_value(pr.len_in, e), field_at(kw, j, uint8_t()), K7F);
+                    c32[j] = pc.c32;
+                    len[j] = pc.len;
+                    longest = max_u16(longest, pc.len);
+                }
+            }
+        }
+    } else {
+        uint32_t left = field_of(g.before, T());  // the sample in front of the group
+#pragma unroll
+        for (uint32_t j = 0; j < PACK_PER_THREAD; j++) {
+            const uint32_t p = field_at(g.cw, j, T());
+            const PixelCode pc = code_pixel<PACK_CODE_FORMS<T>>(p, left, field_at(g.uw, j, T()), field_at(kw, j, uint8_t()), K31, K7F);
+            c32[j] = pc.c32;
+            len[j] = pc.len;
+            longest = max_u16(longest, pc.len);
+            left = p;
+        }
     }
     if (__ballot(j0 < PACK_PER_THREAD) != 0) {  // (wave-uniform: a quarter of the waves of a 4K plane)
         if (j0 < PACK_PER_THREAD) {
@@ -1974,7 +2033,10 @@ extern "C" __attribute__((visibility("default"))) int felics_debug_pack_stamps(u
 // the tile -- so the gather is one contiguous read: four slots per thread and round, and each event's CODE is built right there,
 // once per event (rice_word), and dropped into the LDS array the code phase indexes by pixel (padding slots, pix = 0xFFFF, into
 // a dump word behind it).  The code phase then builds the phased-in code of every pixel and keeps the event's word where there is
-// one: the Rice code is no longer built for every pixel (of which one in seven is an event).  No run table, no chains here.
+// one: the Rice code is not built for every pixel there (group_codes_w: tiles of at most WORD_PATH_MAX_SLOTS slots in use, flat and
+// natural-like content).  Where events are the majority -- 55 % of the pixels of S1 are events, every pixel of noise -- the gather
+// leaves only k per pixel and the code phase builds both codes of every pixel (group_codes_k).  The 8-bit kernels build either path's
+// classification and phased-in code two pixels per instruction (felics_pairs.h).  No run table, no chains here.
 // ------------------------------------------------------------------------------------------
 struct TSources {
     const uint8_t *kq;

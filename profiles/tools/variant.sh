@@ -16,6 +16,7 @@ cd "$SRC/felics_amd/csrc"
 KERNELS="felics_kernels felics_wide felics_gpudecode"
 [ -f felics_chain.hip ] && KERNELS="$KERNELS felics_chain"   # (round 5 on; an older checkout has no such file)
 [ -f felics_index.hip ] && KERNELS="$KERNELS felics_index"   # (the restart index's encoder side)
+[ -f felics_index16.hip ] && KERNELS="$KERNELS felics_index16"   # (the same for 16-bit streams)
 OBJS=""
 for f in $KERNELS; do hipcc $F -c $f.hip -o "$O/$f.o" & OBJS="$OBJS $O/$f.o"; done
 HOST="felics_context felics_encode felics_mixed felics_decode_device"
@@ -25,6 +26,7 @@ hipcc -O3 -std=c++17 -fPIC -c felics_decode.cpp -o "$O/felics_decode.o" &
 OBJS="$OBJS $O/felics_decode.o"
 # (the restart index's host side; its object must not take felics_index.hip's name)
 [ -f felics_index.cpp ] && { hipcc -O3 -std=c++17 -fPIC -c felics_index.cpp -o "$O/felics_index_host.o" & OBJS="$OBJS $O/felics_index_host.o"; }
+[ -f felics_index16.cpp ] && { hipcc -O3 -std=c++17 -fPIC -c felics_index16.cpp -o "$O/felics_index16_host.o" & OBJS="$OBJS $O/felics_index16_host.o"; }
 wait
 hipcc --offload-arch=gfx950 -shared -Wl,--no-undefined -o "$O/libfelics.so" $OBJS -L/opt/rocm/lib -lamdhip64 -Wl,-rpath,/opt/rocm/lib
 rm -f "$O"/*.o
