@@ -278,8 +278,10 @@ __device__ __forceinline__ uint32_t field_of(int v, int16_t) { return ((uint32_t
 //   16 code_pixel: cheap forms
 // and of profiles/pack_pairs.txt (felics_pairs.h: two 8-bit pixels per instruction up to the Rice code):
 //   32 group_codes_k by pairs (k_pack_t's k path)           64 group_codes_w by pairs (its word path)
+// and of profiles/latency_forms.txt (memory round trips taken off a tile's path):
+//   128 k_front: every trip of a wave's quarter in flight (8-bit samples)
 #ifndef FELICS_FORMS
-#define FELICS_FORMS 127
+#define FELICS_FORMS 255
 #endif
 #ifndef FELICS_FRONT_WAVES
 #define FELICS_FRONT_WAVES 6  // (gray planes; what the LDS allows.  A/B builds: profiles/tools/variant.sh)
@@ -319,6 +321,30 @@ __device__ __forceinline__ uint64_t plane_pitch(S, uint32_t) { return 0; }
 __device__ __forceinline__ uint64_t plane_pitch(const PitchedGeom *rows, uint32_t plane) {
     return rows[(uint32_t)__builtin_amdgcn_readfirstlane((int)plane)].pitch;
 }
+// Stamps of a front workgroup's steps (-DFELICS_FRONT_STAMPS, profiles/tools/front_stamps.py; nothing of it in the product build):
+// s_memtime of every wave, kept in scalar registers, wave 0's summed per tile.  Row of 16: [d] the wait in front of trip d (the stamp
+// is taken once the trip's nine registers have arrived), [4 + d] what ran between the stamp before and that wait (d = 0: the issue
+// of the last trip in flight; else trip d - 1's classification and ranks), [8] the last trip's classification, [9] the barrier behind
+// the loop, [11] the addresses and the first trips issued, [12] step 3, [13] step 4, [14] step 5, [15] tiles.
+#ifdef FELICS_FRONT_STAMPS
+__device__ unsigned long long g_front_stamps[256][16];
+#define FSTAMP(i)                                                              \
+    do {                                                                       \
+        const unsigned long long now_ = __builtin_amdgcn_s_memtime();          \
+        f_acc[i] += now_ - f_last;                                             \
+        f_last = now_;                                                         \
+    } while (0)
+#define FSTAMP_ARRIVED(d, t)                                                                                                              \
+    do {                                                                                                                                  \
+        FSTAMP(4 + (d));                                                                                                                  \
+        asm volatile("" ::"v"(t.cur[0]), "v"(t.cur[1]), "v"(t.cur[2]), "v"(t.cur[3]), "v"(t.up[0]), "v"(t.up[1]), "v"(t.up[2]), "v"(t.up[3]), \
+                     "v"(t.left0));                                                                                                       \
+        FSTAMP(d);                                                                                                                        \
+    } while (0)
+#else
+#define FSTAMP(i)
+#define FSTAMP_ARRIVED(d, t)
+#endif
 // (S: const T * -- the uniform planes --, const PlaneGeom * -- a mixed sub-batch's table; W and npix are then unused -- or
 // const PitchedGeom *: the table of a sub-batch with pitched planes)
 // (BALLOT: the rank form, chosen by the launcher from its mode -- the interior loop of the returning-add form then holds no
@@ -338,6 +364,9 @@ __attribute__((amdgpu_waves_per_eu(sizeof(T) == 1 ? FELICS_FRONT_WAVES : 5))) __
     __shared__ uint32_t cnt[4][NC + 64];      // per wave and context: count, then cursor into srt; [NC + lane]: what slots without an event count on
     __shared__ uint32_t gdst[NC];             // a context's run: its place among the tile's slots minus its place in srt
     __shared__ uint32_t wsum[4];
+#ifdef FELICS_FRONT_STAMPS
+    unsigned long long f_acc[15] = {}, f_last = __builtin_amdgcn_s_memtime();
+#endif
     // (wave-uniform, and said so: the tile, its bounds and the trip bookkeeping then live in scalar registers instead of vector
     // registers under exec masks)
     const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), lane = lane_id();
@@ -428,22 +457,41 @@ __attribute__((amdgpu_waves_per_eu(sizeof(T) == 1 ? FELICS_FRONT_WAVES : 5))) __
     }
     const uint32_t cnt_at = (uint32_t)(uintptr_t)(const __attribute__((address_space(3))) uint32_t *)my_cnt;  // LDS address of the wave's counters
     const uint32_t dummy_at = (NC + lane) * 4u;
-    Trip pre[2];  // two trips in flight
-    if constexpr (PITCHED) {
-        if (have[0]) load_trip(tripat[0], leftidx[0], pre[0]);
+    // Trips in flight.  8-bit samples: all of the quarter's -- every address is known here, one trip's classification is far shorter
+    // than a memory round trip, and the records and ranks grow by eight registers a trip as the samples shrink by nine (36 registers
+    // of samples at the start, when rec[] and rk[] hold nothing).  A wave then waits for memory once a quarter, in front of its
+    // first trip, not once a trip (the loads sit under the have[] branches, so the compiler's wait there is for all of them:
+    // profiles/latency_forms.txt).  The Y / Co / Cg kernels keep two: they have no register to spare (profiles/front_pack_forms.txt).
+    constexpr uint32_t FLIGHT = (sizeof(T) == 1 && (FELICS_FORMS & 128) != 0) ? TRIPS : 2;
+    static_assert(FLIGHT == 2 || FLIGHT == TRIPS, "two trips in turn, or all of the quarter's");
+    Trip pre[FLIGHT];
+    auto issue_trip = [&](uint32_t d) {  // (d: a constant once unrolled)
+        if constexpr (PITCHED) {
+            if (have[d]) load_trip(tripat[d], leftidx[d], pre[d % FLIGHT]);
+        } else {
+            if (have[d]) load_trip(qbegin + d * 256, leftidx[d], pre[d % FLIGHT]);
+        }
+    };
+    if constexpr (FLIGHT == TRIPS) {
+#pragma unroll
+        for (uint32_t d = 0; d < TRIPS; d++) issue_trip(d);
     } else {
-        if (have[0]) load_trip(qbegin, leftidx[0], pre[0]);
+        issue_trip(0);
     }
+    FSTAMP(11);
 #pragma unroll
     for (uint32_t d = 0; d < TRIPS; d++) {
         const uint32_t row0 = qbegin + d * 256;
-        if constexpr (PITCHED) {
-            if (d + 1 < TRIPS && have[d + 1]) load_trip(tripat[d + 1], leftidx[d + 1], pre[(d + 1) & 1u]);
-        } else {
-            if (d + 1 < TRIPS && have[d + 1]) load_trip(row0 + 256, leftidx[d + 1], pre[(d + 1) & 1u]);
+        if constexpr (FLIGHT != TRIPS) {  // (two in flight: trip d + 1 is issued when trip d's classification starts)
+            if constexpr (PITCHED) {
+                if (d + 1 < TRIPS && have[d + 1]) load_trip(tripat[d + 1], leftidx[d + 1], pre[(d + 1) & 1u]);
+            } else {
+                if (d + 1 < TRIPS && have[d + 1]) load_trip(row0 + 256, leftidx[d + 1], pre[(d + 1) & 1u]);
+            }
         }
         if (have[d]) {
-            const Trip &t = pre[d & 1u];
+            const Trip &t = pre[d % FLIGHT];
+            FSTAMP_ARRIVED(d, t);
 #pragma unroll
             for (uint32_t j = 0; j < 4; j++) {
                 // the left neighbour: the lane before; lane 0 takes the last lane of the sub-row before (the sample in front of the
@@ -534,7 +582,9 @@ __attribute__((amdgpu_waves_per_eu(sizeof(T) == 1 ? FELICS_FRONT_WAVES : 5))) __
             }
         }
     }
+    FSTAMP(8);
     __syncthreads();
+    FSTAMP(9);
     // ---- 3. the tile's layout: thread t takes contexts t * PER ..; two running sums in one register: the events in front (low
     // half: the context's place in srt) and the slots in front (high half: every run rounded up to whole records)
     const uint64_t pt = (uint64_t)plane * ntiles + tile;
@@ -596,6 +646,7 @@ __attribute__((amdgpu_waves_per_eu(sizeof(T) == 1 ? FELICS_FRONT_WAVES : 5))) __
         }
     }
     __syncthreads();
+    FSTAMP(12);
     // ---- 4. place: where the context's events of this wave start + the event's rank among them (a slot without an event: a
     // place of this thread's own behind the tile)
 #pragma unroll
@@ -610,6 +661,7 @@ __attribute__((amdgpu_waves_per_eu(sizeof(T) == 1 ? FELICS_FRONT_WAVES : 5))) __
         }
     }
     __syncthreads();
+    FSTAMP(13);
     // ---- 5. out, checked: (context, pixel offset) must ascend strictly -- exactly "stable partition by context"
     uint32_t bad = mode & FRONT_TEST_VIOLATION;
     if (fits) {
@@ -624,7 +676,26 @@ __attribute__((amdgpu_waves_per_eu(sizeof(T) == 1 ? FELICS_FRONT_WAVES : 5))) __
         }
     }
     if (__ballot(bad != 0) != 0 && lane == 0) atomicOr(flags, TL_FLAG_ORDER);
+#ifdef FELICS_FRONT_STAMPS
+    FSTAMP(14);
+    if (tid == 0) {
+        unsigned long long *slot = g_front_stamps[(tile * 7u + plane) & 255u];
+        for (int i = 0; i < 15; i++) atomicAdd(&slot[i], f_acc[i]);
+        atomicAdd(&slot[15], 1ull);
+    }
+#endif
 }
+
+#ifdef FELICS_FRONT_STAMPS
+extern "C" __attribute__((visibility("default"))) int felics_debug_front_stamps(unsigned long long *out, int reset) {
+    if (hipMemcpyFromSymbol(out, HIP_SYMBOL(g_front_stamps), sizeof(g_front_stamps)) != hipSuccess) return -1;
+    if (reset) {
+        static unsigned long long z[256 * 16] = {};
+        if (hipMemcpyToSymbol(HIP_SYMBOL(g_front_stamps), z, sizeof(z)) != hipSuccess) return -1;
+    }
+    return 0;
+}
+#endif
 
 // ------------------------------------------------------------------------------------------
 // code construction shared by lengths / pack
@@ -1277,8 +1348,15 @@ __device__ unsigned long long g_pack_stamps[256][16];
             fl.t_last = now_;                                                                  \
         }                                                                                      \
     } while (0)
+// (the wait for a load on its own: the stamp is taken once register `reg` -- the last one loaded -- has arrived)
+#define PSTAMP_ARRIVED(i, reg)          \
+    do {                                \
+        asm volatile("" ::"v"(reg));    \
+        PSTAMP(i);                      \
+    } while (0)
 #else
 #define PSTAMP(i)
+#define PSTAMP_ARRIVED(i, reg)
 #endif
 struct FusedLDS {
 #ifdef FELICS_PACK_STAMPS
@@ -2075,6 +2153,7 @@ __attribute__((amdgpu_waves_per_eu(FELICS_PACK_WAVES))) __global__ __launch_boun
     // ---- round trip 1: the tile's slots in use and the thread's pixels
     const uint64_t pt = (uint64_t)plane * ts.sort_ntiles + st;
     const uint32_t ns = (uint32_t)__builtin_amdgcn_readfirstlane((int)ts.tile_slots[pt]);  // a multiple of REC
+    PSTAMP(11);
     constexpr bool PITCHED = std::is_same<PO, PitchedOut>::value;
     uint64_t group_at = 0;
     GroupGeom gg;
@@ -2117,6 +2196,7 @@ __attribute__((amdgpu_waves_per_eu(FELICS_PACK_WAVES))) __global__ __launch_boun
             pv[u] = *reinterpret_cast<const uint2 *>(psrc + s);
             __builtin_memcpy(evv[u], esrc + s, 4 * sizeof(ET));
         }
+        PSTAMP_ARRIVED(10, evv[WR - 1][0]);
         __syncthreads();  // the words are cleared before the first of them is written
 #pragma unroll
         for (uint32_t u = 0; u < WR; u++) {
@@ -2152,6 +2232,7 @@ __attribute__((amdgpu_waves_per_eu(FELICS_PACK_WAVES))) __global__ __launch_boun
                 kv[u] = *reinterpret_cast<const uint32_t *>(ksrc + s);
                 pv[u] = *reinterpret_cast<const uint2 *>(psrc + s);
             }
+            PSTAMP_ARRIVED(10, pv[GR - 1].y);
 #pragma unroll
             for (uint32_t u = 0; u < GR; u++) {  // (pix: offset | above << 12; padding 0xFFFF -> the dump byte)
                 kq[min(pv[u].x & 0xEFFFu, PACK_TILE)] = (uint8_t)kv[u];
