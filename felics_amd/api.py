@@ -122,6 +122,11 @@ class _CIndex16EmitStats(C.Structure):  # felics_index16_emit_stats
     _fields_ = [("streams", C.c_uint64), ("rows_written", C.c_uint64), ("index_bytes", C.c_uint64), ("passes", C.c_uint64)]
 
 
+class _CIndex16ViewEmitStats(C.Structure):  # felics_index16_view_emit_stats
+    _fields_ = [("views", C.c_uint64), ("indexes", C.c_uint64), ("rows_written", C.c_uint64), ("index_bytes", C.c_uint64),
+                ("sub_batches", C.c_uint64), ("shapes_max", C.c_uint64), ("redone", C.c_uint64)]
+
+
 class _CIndexEmitStats(C.Structure):  # felics_index_emit_stats
     _fields_ = [("indexes", C.c_uint64), ("checkpoints", C.c_uint64), ("in_mixed", C.c_uint64), ("redone", C.c_uint64)]
 
@@ -183,6 +188,7 @@ EXPORTS = [
     "felics_compress_batch_device_indexed_wide", "felics_get_index_wide_emit_stats",
     "felics_decompress_region_indexed_wide", "felics_decompress_regions_device_indexed_wide", "felics_get_region_wide_stats",
     "felics_decompress_views_device_indexed_wide", "felics_decompress_indexed_view_wide", "felics_get_index_view_wide_stats",
+    "felics_compress_views_device_indexed_wide", "felics_get_index_view_wide_emit_stats",
 ]
 
 _lib = None
@@ -312,6 +318,11 @@ def lib():
                                                                   C.POINTER(C.c_int)]
         L.felics_decompress_indexed_view_wide.argtypes = [vp, sz, vp, sz, C.POINTER(_CView), C.POINTER(_CHeader)]
         L.felics_get_index_view_wide_stats.argtypes = [vp, C.POINTER(_CIndex16ViewStats), sz]
+    if hasattr(L, "felics_compress_views_device_indexed_wide"):  # (as above: an older build writes 16-bit indexes for one shape only)
+        u64 = C.POINTER(C.c_uint64)
+        L.felics_compress_views_device_indexed_wide.argtypes = [vp, sz, C.POINTER(_CView), C.POINTER(C.c_uint32), vp, vp, sz, vp, sz, u64, u64,
+                                                                u64, u64, u64]
+        L.felics_get_index_view_wide_emit_stats.argtypes = [vp, C.POINTER(_CIndex16ViewEmitStats), sz]
     L.felics_strerror.argtypes = [C.c_int]
     L.felics_strerror.restype = C.c_char_p
     L.felics_last_error.argtypes = [vp]
@@ -816,6 +827,74 @@ class Encoder:
         """felics_get_index_wide_emit_stats: streams handed to compress_batch_device_indexed16, the state rows and bytes of the indexes
         written and the passes that wrote them (all cumulative)."""
         return self._stats("felics_get_index_wide_emit_stats", _CIndex16EmitStats, bare=True)
+
+    def compress_views_device_indexed16_raw(self, views, segment_pixels, d_out, d_out_cap, d_index, d_index_cap, ready_event=None):
+        """felics_compress_views_device_indexed_wide on raw device pointers, one call: (rc, offsets, lens, idx_offsets, idx_lens,
+        idx_total).  views as for compress_views_device; segment_pixels: an int for all views or one per view (0: no index).  rc = -8
+        with idx_total != 0: the index buffer is short of idx_total bytes (streams, offsets and lens are complete); with
+        idx_total == 0 it is the stream buffer, lens[0] = the bytes needed."""
+        n = len(views)
+        u64 = C.POINTER(C.c_uint64)
+        cv = (_CView * max(n, 1))(*[_cview(v) for v in views])
+        segs = _segments(segment_pixels, n)
+        arr = [np.zeros(max(n, 1), dtype=np.uint64) for _ in range(4)]
+        total = C.c_uint64(0)
+        rc = lib().felics_compress_views_device_indexed_wide(
+            self._h, n, cv, segs.ctypes.data_as(C.POINTER(C.c_uint32)), int(ready_event) if ready_event else None, d_out, d_out_cap, d_index,
+            d_index_cap, *(a.ctypes.data_as(u64) for a in arr), C.byref(total))
+        return (rc, *(a[:n] for a in arr), int(total.value))
+
+    def compress_views_device_indexed16(self, views, segment_pixels, alloc=None, ready_event=None):
+        """felics_compress_views_device_indexed_wide: compress_views_device plus, for every 16-bit view whose segment_pixels (an int for
+        all views, or one per view; 0: none) is not 0, the version-2 restart index of its stream, written on the GPU and PLACED BY THE
+        LIBRARY (idx_offsets are multiples of 64, in no specified order; a view without an index has idx_lens[i] = 0).  The two buffers
+        come from alloc(nbytes) as in compress_batch_device_indexed16, the index buffer by the two-call pattern: a first call with a
+        guess, a second with idx_total bytes if the guess was short.  Returns IndexedStreams16(streams, offsets, lens, index,
+        idx_offsets, idx_lens): what decompress_views_device_indexed16 takes (for the views that asked for an index)."""
+        if alloc is None:
+            import torch
+
+            def alloc(nbytes):
+                return torch.empty(max(int(nbytes), 64), dtype=torch.uint8, device="cuda")
+        n = len(views)
+        segs = _segments(segment_pixels, n)
+        ptr = lambda buf: int(buf.__cuda_array_interface__["data"][0])
+        out_cap, idx_cap = 64, 0
+        for (_, w, h, color, depth, *_s), seg in zip(views, segs[:n]):
+            planes, sample = (3 if color else 1), (2 if depth == PixelDepth.Sixteen else 1)
+            frame_bytes = h * w * sample * planes
+            out_cap += frame_bytes + frame_bytes // 4 + 80
+            if seg and w * h:  # the guess: header, directory, windows and 64 rows per checkpoint
+                k = -(-(h * w) // int(seg))
+                idx_cap += 256 + planes * k * (32 + 4 * w * (4 if color else 2) + 16 + 64 * 64)
+            elif seg:
+                idx_cap += 64
+        streams, index = alloc(out_cap), alloc(max(idx_cap, 64))
+        for _ in range(8):
+            rc, offs, lens, ioffs, ilens, total = self.compress_views_device_indexed16_raw(views, segs[:n], ptr(streams), out_cap, ptr(index),
+                                                                                          idx_cap, ready_event)
+            if rc == -8 and total:  # the streams are done; their indexes need `total` bytes
+                idx_cap = total
+                index = alloc(idx_cap)
+                continue
+            if rc == -8 and n and lens[0] > out_cap:
+                out_cap = int(lens[0]) + 64
+                streams = alloc(out_cap)
+                continue
+            break
+        if rc != 0:
+            self._raise(rc)
+        return IndexedStreams16(streams, offs, lens, index, ioffs, ilens)
+
+    def compress_arrays_device_indexed16(self, arrays, segment_pixels, alloc=None, ready_event=None):
+        """compress_views_device_indexed16 on objects with __cuda_array_interface__ (view_of_array), as compress_arrays_device."""
+        return self.compress_views_device_indexed16([view_of_array(a) for a in arrays], segment_pixels, alloc, ready_event)
+
+    def index16_view_emit_stats(self):
+        """felics_get_index_view_wide_emit_stats: views handed to compress_views_device_indexed16, the indexes its kernels wrote, their state
+        rows and bytes, the sub-batches the table-driven writer served, the distinct shapes of the last call's most mixed one
+        (shapes_max: not cumulative) and the indexes the uniform writer wrote inside a remedy (redone)."""
+        return self._stats("felics_get_index_view_wide_emit_stats", _CIndex16ViewEmitStats, bare=True)
 
     def submit_batch_device(self, d_pixels, n, w, h, color, depth, d_out, d_out_cap):
         """Queues a batch and returns a ticket; up to two can be in flight (felics_submit_batch_device)."""

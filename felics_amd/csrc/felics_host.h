@@ -66,6 +66,28 @@ struct MixImage {
     // the entry point) and its segment; nullptr / 0: no index (every 16-bit image)
     uint8_t *index = nullptr;
     uint32_t segment_pixels = 0;
+    // felics_compress_views_device_indexed16: this 16-bit image wants a version-2 index with segment_pixels; the library places it
+    // (Index16Place) once its size is known
+    bool index16 = false;
+};
+
+// felics_compress_views_device_indexed16: where a call's version-2 indexes go and what has been placed so far.  The size of an index
+// depends on the content, so the indexes are placed in the order their sub-batches land, each a multiple of 64 bytes behind the one
+// before; an index whose end lies behind `cap` is not begun.  A run that places the streams anew starts again from zero (begin_run).
+struct Index16Place {
+    uint8_t *d_index;
+    uint64_t cap;
+    uint64_t *idx_offsets, *idx_lens;  // [n], host
+    uint64_t budget;                   // bytes of per-checkpoint workspace a sub-batch may take
+    uint64_t test_cps;                 // FELICS_TEST_INDEX16_EMIT_CPS: checkpoints of a sub-batch at most (0: no cap)
+    uint64_t total = 0;                // bytes placed so far
+    bool too_small = false;            // an index did not fit and was not written
+    // what felics_index16_view_emit_stats counts, over every run of the call
+    uint64_t indexes = 0, rows = 0, bytes = 0, sub_batches = 0, shapes_max = 0, redone = 0;
+    void begin_run() {
+        total = 0;
+        too_small = false;
+    }
 };
 
 // One pipeline lane: HIP streams, stage events and a workspace in HBM of its own.  A submission (or one pass of
@@ -96,6 +118,7 @@ struct Lane {
     // felics_compress_batch_device_indexed16: per (plane, checkpoint) the contexts' bitmap and its popcount prefix, n_rows and rows_off;
     // per image the index's bytes and rows (totals) and where it goes (index_off, written by the host): Index16Emit, felics_kernels.h
     DevBuf i16_bitmap, i16_prefix, i16_nrows, i16_rows_off, i16_totals, i16_index_off;
+    DevBuf i16_table;                 // felics_compress_views_device_indexed16: the sub-batch's Index16Geom rows (the same workspace otherwise)
     uint32_t epoch = 0;               // 8-bit sub-batches this lane has run (FELICS_TEST_LOOKBACK_EPOCH: plus a start value): its low 18 bits tag the look-back status words (felics_epochs.h)
     // the submission in flight on this lane (felics_submit_batch_device .. felics_wait_batch)
     bool pending = false;
@@ -240,6 +263,7 @@ struct felics_ctx {
     DevBuf mix_index;
     felics_index_emit_stats iestats = {};
     felics_index16_emit_stats i16estats = {};  // felics_compress_batch_device_indexed16: the counts of felics_get_index16_emit_stats
+    felics_index16_view_emit_stats i16vestats = {};  // felics_compress_views_device_indexed16: the counts of felics_get_index16_view_emit_stats
 };
 
 namespace felics {

@@ -227,6 +227,34 @@ void launch_index16_write(hipStream_t s, const void *planes, const uint64_t *rec
                           const uint64_t *tile_bitoff, const uint64_t *plane_base, const uint64_t *plane_carry, const Geometry &g,
                           const Index16Emit &e);
 
+// The same two steps for a sub-batch whose images differ in shape or segment (felics_compress_views_device_indexed16): every plane has
+// a row of its own beside its PlaneGeom row -- a row type of its own, as IndexGeom is; the tables the encode kernels load stay as
+// they are.  The kernels index it by plane (wave-uniform: scalar loads).  The planes of an image follow each other and share
+// everything but c and samples.  The workspace is Index16Emit's, with checkpoint (plane, j) at cp0 + j.
+struct Index16Geom {
+    const void *samples;      // the plane's first sample: u16 with row length W (gray: the dense frame), or the i32 Y / Co / Cg plane
+    uint32_t image, c;        // the image's ordinal in the sub-batch (indexes index_off / totals), the plane's index in the image
+    uint32_t W, H, npix;
+    uint32_t segment_pixels;
+    uint32_t K;               // checkpoints per plane; 0: this image gets no index, every kernel skips its planes
+    uint32_t cp0;             // the plane's first checkpoint: the sum of K over the planes in front of it
+    uint64_t win_base, win_bytes, rows_base;  // the image's Index16Layout
+};
+struct Index16TableEmit {
+    uint8_t *index;
+    const uint64_t *index_off;  // [nimages], device; ~0: this image's index is not written
+    uint32_t *bitmap, *prefix, *n_rows;
+    uint64_t *rows_off, *totals;
+    const Index16Geom *rows;    // [nplanes], device
+    uint32_t color, planes_per_image, nplanes, nimages;
+    uint32_t ncps, wpc;         // the sub-batch's checkpoints (the sum of K over all planes); words per checkpoint
+};
+// max_npix: the largest plane's pixels; max_rows_base: the largest rows_base (they size grids, nothing else)
+void launch_index16_scan_table(hipStream_t s, const uint64_t *recs, const uint32_t *meta, const Index16TableEmit &t, uint32_t max_npix);
+void launch_index16_write_table(hipStream_t s, const uint64_t *recs, const uint32_t *meta, const uint64_t *heads, const uint32_t *nheads,
+                                const uint64_t *tile_bitoff, const uint64_t *plane_base, const uint64_t *plane_carry, uint32_t pack_tiles,
+                                const Index16TableEmit &t, uint64_t max_rows_base);
+
 // k_map / plane / slot buffers are read in whole 16-byte chunks by the tile staging
 constexpr size_t STAGE_PAD = 64;
 

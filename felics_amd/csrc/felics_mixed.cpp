@@ -1,6 +1,7 @@
 // felics_mixed.cpp -- images of different shapes in one call (felics_compress_images*) and strided views of device surfaces
 // (felics_compress_views_device): buckets, the mixed sub-batches' plane tables, landing and remedies; the restart indexes of
-// such a call (felics_compress_views_device_indexed, felics_index_plan).
+// such a call (felics_compress_views_device_indexed, felics_index_plan; 16-bit: felics_compress_views_device_indexed16, placed by the
+// library where a sub-batch lands -- emit_index16_views).
 #include "felics_host.h"
 #include "felics_index.h"
 #include "felics_viewcheck.h"
@@ -81,11 +82,21 @@ struct MixOut {
     const uint64_t *off, *slot;
     uint64_t *lens;
     bool overflow;
-    bool want_index = true;  // the images' restart indexes as well (MixImage::index); false: a run for the sizes alone
+    bool want_index = true;  // the images' restart indexes as well (MixImage::index / index16); false: a run for the sizes alone
+    Index16Place *ix = nullptr;  // felics_compress_views_device_indexed16: where the version-2 indexes go
 };
 
 // image m's index is to be written by this run
 bool wants_index(const MixImage &m, const MixOut &o) { return o.want_index && m.index != nullptr; }
+// ... its version-2 index (placed by the library: Index16Place)
+bool wants_index16(const MixImage &m, const MixOut &o) { return o.want_index && o.ix && m.index16; }
+// the segment that groups the images of a remedy: the uniform writers take one per call
+uint32_t index_segment(const MixImage &m, const MixOut &o) { return wants_index(m, o) || wants_index16(m, o) ? m.segment_pixels : 0u; }
+
+// The per-checkpoint workspace of the version-2 writers (bitmap and prefix: a bit and a share of a word per context; n_rows, rows_off)
+uint64_t index16_cp_bytes(int color) { return index16_words_per_checkpoint((uint32_t)color) * 8ull + 12u; }
+// the checkpoints image m adds to a sub-batch that writes its index
+uint64_t index16_cps(const MixImage &m) { return (uint64_t)m.planes * index16_layout(m.w, m.h, (uint32_t)m.color, m.segment_pixels).K; }
 
 // an index has been written by a kernel (felics_index_emit_stats)
 void count_index(felics_ctx *ctx, const MixImage &m, bool mixed) {
@@ -272,7 +283,7 @@ int redo_by_shape(felics_ctx *ctx, Lane &l, const std::vector<MixImage> &im, con
             const MixImage &m = im[i];
             const bool same = m.w == f.w && m.h == f.h && m.color == f.color && m.depth == f.depth;
             // (the uniform writer takes one segment per call: images that want indexes are grouped by their segment as well)
-            (same && (wants_index(m, o) ? m.segment_pixels : 0u) == (wants_index(f, o) ? f.segment_pixels : 0u) ? grp : other).push_back(i);
+            (same && index_segment(m, o) == index_segment(f, o) ? grp : other).push_back(i);
         }
         rest.swap(other);
         const size_t cnt = grp.size();
@@ -291,15 +302,135 @@ int redo_by_shape(felics_ctx *ctx, Lane &l, const std::vector<MixImage> &im, con
             if ((rc = reserve(ctx, ctx->mix_index, (size_t)(req.bytes * cnt))) != 0) return rc;
             req.d_index = (uint8_t *)ctx->mix_index.p;
         }
+        // a 16-bit group: the uniform version-2 writer, into the caller's buffer behind what has been placed so far
+        std::vector<uint64_t> ioffs(cnt), ilens(cnt);
+        Index16Request rq16{nullptr, 0, f.segment_pixels, SIZE_MAX, ioffs.data(), ilens.data()};
+        const bool ask16 = wants_index16(f, o);
+        if (ask16) {
+            Index16Place &ix = *o.ix;
+            rq16.d_index = ix.d_index + ix.total;  // (every size is a multiple of 64: so is this)
+            rq16.cap = ix.cap > ix.total ? ix.cap - ix.total : 0;
+            rq16.pass_images = (size_t)std::max<uint64_t>(1, ix.budget / (index16_cps(f) * index16_cp_bytes(f.color) + 24u));
+        }
         if ((rc = encode_device(ctx, l, cnt, ctx->mix_redo.p, f.w, f.h, f.color, f.depth, nullptr, 0, offs.data(), lens.data(), &used, false,
-                                req.d_index ? &req : nullptr)) != 0)
+                                req.d_index ? &req : nullptr, ask16 ? &rq16 : nullptr)) != 0)
             return rc;
+        if (ask16) {  // (encode_device has waited for its writer)
+            Index16Place &ix = *o.ix;
+            for (size_t j = 0; j < cnt; j++) {
+                ix.idx_offsets[grp[j]] = ix.total + ioffs[j];
+                ix.idx_lens[grp[j]] = ilens[j];
+            }
+            ix.total += rq16.total;
+            ix.too_small = ix.too_small || rq16.too_small;
+            ix.indexes += rq16.written;
+            ix.redone += rq16.written;
+            ix.rows += rq16.rows;
+            ix.bytes += rq16.bytes;
+        }
         for (size_t j = 0; j < cnt && req.d_index; j++) {  // (encode_device has waited for its writer; copy_to_slots waits for these)
             HIP_TRY(ctx, hipMemcpyAsync(im[grp[j]].index, req.d_index + j * req.bytes, (size_t)req.bytes, hipMemcpyDeviceToDevice, l.stream));
             count_index(ctx, im[grp[j]], false);
         }
         if ((rc = copy_to_slots(ctx, l, grp, used, offs.data(), lens.data(), o)) != 0) return rc;  // (waits: ctx->own is reused by the next group)
     }
+    return FELICS_OK;
+}
+
+// The version-2 indexes of a 16-bit job that has landed usable (felics_compress_views_device_indexed16), by the table-driven writer
+// (launch_index16_scan_table / _write_table) from what run_wide left in the lane's workspace -- emit_index16's shape: scan, read the
+// totals back, place behind what has been placed so far, upload index_off, write.  One emitter for both kinds of job: a mixed
+// sub-batch's rows take its PlaneGeom rows' samples, a same-shape group's rows all name one shape and point into the lane's planes
+// (the gathered frames, or the Y / Co / Cg planes).  On the lane's stream, and complete on return: the next job reuses the workspace.
+int emit_index16_views(felics_ctx *ctx, Lane &l, const MixJob &j, const std::vector<MixImage> &im, MixOut &o) {
+    Index16Place &ix = *o.ix;
+    const Geometry &g = l.g;
+    const size_t cnt = j.idx.size();
+    const uint32_t C = g.planes_per_image;
+    const size_t sample_bytes = C == 3 ? 4 : 2;
+    std::vector<Index16Geom> rows(cnt * C);
+    std::vector<std::pair<uint32_t, uint32_t>> shapes;
+    uint64_t cps = 0, max_rows_base = 0, max_npix = 0;
+    for (size_t k = 0; k < cnt; k++) {
+        const MixImage &m = im[j.idx[k]];
+        const bool want = wants_index16(m, o);
+        Index16Layout L{};
+        if (want) L = index16_layout(m.w, m.h, (uint32_t)m.color, m.segment_pixels);
+        for (uint32_t c = 0; c < C; c++) {
+            Index16Geom &r = rows[k * C + c];
+            r.samples = j.wide ? (const void *)((const uint8_t *)l.d_planes + (k * C + c) * (size_t)g.npix * sample_bytes) : l.h_table[k * C + c].samples;
+            r.image = (uint32_t)k;
+            r.c = c;
+            r.W = m.w;
+            r.H = m.h;
+            r.npix = (uint32_t)m.npix;
+            r.segment_pixels = want ? m.segment_pixels : 0;
+            r.K = want ? L.K : 0;
+            r.cp0 = (uint32_t)cps;
+            r.win_base = L.win_base;
+            r.win_bytes = L.win_bytes;
+            r.rows_base = L.rows_base;
+            cps += r.K;
+        }
+        if (!want) continue;
+        max_rows_base = std::max(max_rows_base, L.rows_base);
+        max_npix = std::max(max_npix, m.npix);
+        if (std::find(shapes.begin(), shapes.end(), std::make_pair(m.w, m.h)) == shapes.end()) shapes.emplace_back(m.w, m.h);
+    }
+    if (cps == 0) return FELICS_OK;  // no image of the job asks for an index
+    if (cps > 0xFFFFFFFFull) return FELICS_E_UNSUPPORTED;  // (never: the budget cuts a sub-batch far below)
+    const uint32_t wpc = index16_words_per_checkpoint(g.color);
+    int rc;
+    if ((rc = reserve(ctx, l.i16_bitmap, (size_t)cps * wpc * 4)) != 0) return rc;
+    if ((rc = reserve(ctx, l.i16_prefix, (size_t)cps * wpc * 4)) != 0) return rc;
+    if ((rc = reserve(ctx, l.i16_nrows, (size_t)cps * 4)) != 0) return rc;
+    if ((rc = reserve(ctx, l.i16_rows_off, (size_t)cps * 8)) != 0) return rc;
+    if ((rc = reserve(ctx, l.i16_totals, cnt * 16)) != 0) return rc;
+    if ((rc = reserve(ctx, l.i16_index_off, cnt * 8)) != 0) return rc;
+    if ((rc = reserve(ctx, l.i16_table, rows.size() * sizeof(Index16Geom))) != 0) return rc;
+    hipStream_t s = l.stream;
+    if (ctx->poison) {
+        DevBuf *bufs[] = {&l.i16_bitmap, &l.i16_prefix, &l.i16_nrows, &l.i16_rows_off, &l.i16_totals, &l.i16_index_off, &l.i16_table};
+        for (DevBuf *b : bufs) HIP_TRY(ctx, hipMemsetAsync(b->p, 0xA5, b->cap, s));
+    }
+    HIP_TRY(ctx, hipMemcpyAsync(l.i16_table.p, rows.data(), rows.size() * sizeof(Index16Geom), hipMemcpyHostToDevice, s));
+    const Index16TableEmit t{ix.d_index, (const uint64_t *)l.i16_index_off.p, (uint32_t *)l.i16_bitmap.p, (uint32_t *)l.i16_prefix.p,
+                             (uint32_t *)l.i16_nrows.p, (uint64_t *)l.i16_rows_off.p, (uint64_t *)l.i16_totals.p, (const Index16Geom *)l.i16_table.p,
+                             g.color, C, (uint32_t)(cnt * C), (uint32_t)cnt, (uint32_t)cps, wpc};
+    const uint64_t *recs = (const uint64_t *)l.wrecs[0].p;
+    const uint32_t *meta = (const uint32_t *)l.wmeta.p;
+    launch_index16_scan_table(s, recs, meta, t, (uint32_t)max_npix);
+    HIP_TRY(ctx, hipGetLastError());
+    std::vector<uint64_t> totals(cnt * 2), where(cnt);
+    HIP_TRY(ctx, hipMemcpyAsync(totals.data(), l.i16_totals.p, totals.size() * 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(ctx, hipStreamSynchronize(s));
+    uint64_t fit = 0, fit_rows = 0, fit_bytes = 0;
+    for (size_t k = 0; k < cnt; k++) {
+        const size_t i = j.idx[k];
+        where[k] = ~0ull;
+        if (!wants_index16(im[i], o)) continue;
+        const uint64_t bytes = totals[2 * k];
+        ix.idx_offsets[i] = ix.total;
+        ix.idx_lens[i] = bytes;
+        if (bytes <= ix.cap && ix.total <= ix.cap - bytes) {
+            where[k] = ix.total;
+            fit++, fit_rows += totals[2 * k + 1], fit_bytes += bytes;
+        } else {
+            ix.too_small = true;
+        }
+        ix.total += bytes;  // (rows_base and a row are multiples of 64: so is every offset)
+    }
+    if (fit == 0) return FELICS_OK;
+    HIP_TRY(ctx, hipMemcpyAsync(l.i16_index_off.p, where.data(), where.size() * 8, hipMemcpyHostToDevice, s));
+    launch_index16_write_table(s, recs, meta, (const uint64_t *)l.heads.p, (const uint32_t *)l.scalars.p, (const uint64_t *)l.tile_bitoff.p,
+                               l.plane_base, l.plane_base - g.nplanes, g.pack_tiles, t, max_rows_base);
+    HIP_TRY(ctx, hipGetLastError());
+    HIP_TRY(ctx, hipStreamSynchronize(s));  // (`where` is pageable and leaves scope; the workspace is free again)
+    ix.indexes += fit;
+    ix.rows += fit_rows;
+    ix.bytes += fit_bytes;
+    ix.sub_batches++;
+    ix.shapes_max = std::max<uint64_t>(ix.shapes_max, shapes.size());
     return FELICS_OK;
 }
 
@@ -314,6 +445,16 @@ int land_job(felics_ctx *ctx, MixJob &j, const std::vector<MixImage> &im, MixOut
         const SlotOutcome so = read_sizes(ctx, l, true, j.slot, offs.data(), lens.data());
         uint8_t *from = (uint8_t *)ctx->mix_stage.p + j.stage_off;
         if ((rc = sync_lane(ctx, l)) != 0) return rc;
+        bool any16 = false;
+        for (size_t i : j.idx) any16 = any16 || wants_index16(im[i], o);
+        if (so.overflow && any16) {
+            // ... and its images want version-2 indexes: the uniform writer takes one segment per call, so the group goes through the
+            // remedy that groups by segment (frames gathered once more, streams copied into their slots)
+            (void)apply_remedy(ctx, l, so);
+            if ((rc = redo_by_shape(ctx, l, im, j.idx, o)) != 0) return rc;
+            collect_timing(ctx, l);
+            return FELICS_OK;
+        }
         if (so.overflow) {  // a stream outgrew its slot: the group again with exact placement (encode_device)
             (void)apply_remedy(ctx, l, so);
             const MixImage &f = im[j.idx[0]];
@@ -323,6 +464,8 @@ int land_job(felics_ctx *ctx, MixJob &j, const std::vector<MixImage> &im, MixOut
         }
         if ((rc = copy_to_slots(ctx, l, j.idx, from, offs.data(), lens.data(), o)) != 0) return rc;
         collect_timing(ctx, l);
+        // (the pass was usable as it came out: its records, heads and bit offsets are still in the lane's workspace)
+        if (any16 && (rc = emit_index16_views(ctx, l, j, im, o)) != 0) return rc;
         return FELICS_OK;
     }
     // a mixed sub-batch: its table lists the images in the order of j.idx (run_wide copies the sizes and nothing else: no status word)
@@ -337,6 +480,8 @@ int land_job(felics_ctx *ctx, MixJob &j, const std::vector<MixImage> &im, MixOut
         collect_timing(ctx, l);
         for (size_t i : j.idx)  // (the mixed writers ran in front of `sized`: the indexes are complete)
             if (!j.wide_mixed && wants_index(im[i], o)) count_index(ctx, im[i], true);
+        // a mixed 16-bit sub-batch: its version-2 indexes here, behind `sized` and before the lane's workspace is reused
+        if (j.wide_mixed && o.want_index && o.ix) return emit_index16_views(ctx, l, j, im, o);
         return FELICS_OK;
     }
     if ((rc = sync_lane(ctx, l)) != 0) return rc;
@@ -349,7 +494,9 @@ int land_job(felics_ctx *ctx, MixJob &j, const std::vector<MixImage> &im, MixOut
 // keeps planes * npix of a mixed sub-batch <= 2^30 samples, so the chain kernels' 32-bit kbase = plane * npix -- k_map is strided by
 // the padded npix -- stays valid).  Every pass of 8-bit images is a mixed sub-batch.  A 16-bit bucket of ONE shape is cut by that
 // shape's own npix (the passes that shape always had) and takes the uniform path, as does any other 16-bit pass that holds one shape.
-void bucket_images(const std::vector<MixImage> &im, int depth, int color, std::vector<MixJob> &jobs) {
+// A run that writes version-2 indexes (o.ix) also cuts a 16-bit pass where its images' checkpoints would outgrow the workspace budget
+// (or FELICS_TEST_INDEX16_EMIT_CPS), at least one image per pass; every other run is cut exactly as before.
+void bucket_images(const std::vector<MixImage> &im, int depth, int color, const MixOut &o, std::vector<MixJob> &jobs) {
     const bool wide = depth == FELICS_DEPTH_16;
     const uint32_t planes = color == FELICS_COLOR_RGB ? 3 : 1;
     std::vector<size_t> v;
@@ -368,8 +515,17 @@ void bucket_images(const std::vector<MixImage> &im, int depth, int color, std::v
         const bool uniform = wide && one_shape(a, b);
         const size_t per = uniform ? max_images_per_pass(im[v[a]].npix, planes, depth)
                                    : std::min(MIX_MAX_IMAGES, max_images_per_pass((uint64_t)sort_tiles_of(im[v[b - 1]].npix) * SORT_TILE, planes, depth));
-        for (size_t c = a; c < b; c += per) {
-            const size_t e = std::min(b, c + per);
+        const bool cut_cps = wide && o.want_index && o.ix;
+        const uint64_t cps_max = !cut_cps ? 0 : std::max<uint64_t>(1, std::min(o.ix->budget / index16_cp_bytes(color), o.ix->test_cps ? o.ix->test_cps : UINT64_MAX));
+        for (size_t c = a, e; c < b; c = e) {
+            e = std::min(b, c + per);
+            if (cut_cps) {
+                uint64_t cps = 0;
+                for (size_t k = c; k < e; k++) {
+                    cps += wants_index16(im[v[k]], o) ? index16_cps(im[v[k]]) : 0;
+                    if (cps > cps_max && k > c) e = k;
+                }
+            }
             MixJob j;
             j.wide = wide && (uniform || one_shape(c, e));
             j.wide_mixed = wide && !j.wide;
@@ -388,7 +544,7 @@ int run_images(felics_ctx *ctx, const std::vector<MixImage> &im, MixOut &o) {
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     std::vector<MixJob> jobs;
     for (int depth : {FELICS_DEPTH_8, FELICS_DEPTH_16})
-        for (int color : {FELICS_COLOR_GRAY, FELICS_COLOR_RGB}) bucket_images(im, depth, color, jobs);
+        for (int color : {FELICS_COLOR_GRAY, FELICS_COLOR_RGB}) bucket_images(im, depth, color, o, jobs);
     size_t in_total = 0, stage_total = 0;  // 16-bit jobs: their parts of mix_in and mix_stage
     for (MixJob &j : jobs) {
         j.in_off = in_total;
@@ -416,6 +572,23 @@ int run_images(felics_ctx *ctx, const std::vector<MixImage> &im, MixOut &o) {
             uint8_t ih[INDEX_HEADER_BYTES];
             empty_index(ih, im[i].w, im[i].h, (uint32_t)im[i].color, im[i].segment_pixels);
             HIP_TRY(ctx, hipMemcpy(im[i].index, ih, INDEX_HEADER_BYTES, hipMemcpyHostToDevice));
+        }
+        if (wants_index16(im[i], o)) {  // (the version-2 header alone, as felics_compress_batch_device_indexed16 builds it; placed like the others)
+            Index16Place &ix = *o.ix;
+            uint8_t ih[INDEX_HEADER_BYTES];
+            empty_index(ih, im[i].w, im[i].h, (uint32_t)im[i].color, im[i].segment_pixels);
+            ih[IDX_VERSION] = (uint8_t)INDEX16_VERSION;
+            ih[IDX_DEPTH] = FELICS_DEPTH_16;
+            ih[IDX16_TOTAL] = (uint8_t)INDEX_HEADER_BYTES;
+            ix.idx_offsets[i] = ix.total;
+            ix.idx_lens[i] = INDEX_HEADER_BYTES;
+            if (ix.total + INDEX_HEADER_BYTES <= ix.cap) {
+                HIP_TRY(ctx, hipMemcpy(ix.d_index + ix.total, ih, INDEX_HEADER_BYTES, hipMemcpyHostToDevice));
+                ix.bytes += INDEX_HEADER_BYTES;
+            } else {
+                ix.too_small = true;
+            }
+            ix.total += INDEX_HEADER_BYTES;
         }
     }
     const int nslices = jobs.size() > 1 || ctx->only_lane >= 0 ? ctx->slices_queued : ctx->slices_blocking;
@@ -478,7 +651,8 @@ int run_images(felics_ctx *ctx, const std::vector<MixImage> &im, MixOut &o) {
 
 // felics_compress_images_device without the argument checks: slots as encode_device sizes them if d_out holds them, else (or if
 // a stream outgrew its slot) a second run with every stream placed exactly, back to back.
-int images_device(felics_ctx *ctx, const std::vector<MixImage> &im, uint8_t *d_out, size_t d_out_cap, uint64_t *offsets, uint64_t *lens) {
+int images_device(felics_ctx *ctx, const std::vector<MixImage> &im, uint8_t *d_out, size_t d_out_cap, uint64_t *offsets, uint64_t *lens,
+                  Index16Place *ix = nullptr) {
     const size_t n = im.size();
     std::vector<uint64_t> off(n), slot(n);
     uint64_t total = 0;
@@ -488,6 +662,7 @@ int images_device(felics_ctx *ctx, const std::vector<MixImage> &im, uint8_t *d_o
         total += slot[i];
     }
     MixOut o{d_out, off.data(), slot.data(), lens, false};
+    o.ix = ix;
     int rc;
     if (total > d_out_cap) {  // the sizes first, into a buffer of the library's own
         if ((rc = reserve(ctx, ctx->mix_out, (size_t)total + 64)) != 0) return rc;
@@ -510,6 +685,11 @@ int images_device(felics_ctx *ctx, const std::vector<MixImage> &im, uint8_t *d_o
         return FELICS_E_BUFFER_TOO_SMALL;
     }
     o = MixOut{d_out, off.data(), slot.data(), lens, false};
+    o.ix = ix;
+    if (ix) {  // (what the run above placed is written again: the placement starts from 0, the outputs as the entry point left them)
+        ix->begin_run();
+        for (size_t i = 0; i < n; i++) ix->idx_offsets[i] = ix->idx_lens[i] = 0;
+    }
     if ((rc = run_images(ctx, im, o)) != 0) return rc;
     if (o.overflow) {
         ctx->err = "internal error: a stream outgrew the exact size it had before";
@@ -544,6 +724,8 @@ struct IndexAsk {
     uint8_t *d_index;
     const uint64_t *offsets;
     const uint32_t *segment_pixels;
+    // felics_compress_views_device_indexed16: the segments name version-2 indexes of the 16-bit views instead, placed by the library
+    Index16Place *wide = nullptr;
 };
 int views_device(felics_ctx *ctx, size_t n, const felics_view *views, void *ready_event, void *d_out, size_t d_out_cap, uint64_t *offsets,
                  uint64_t *lens, felics_view_stats &counted, const IndexAsk *ask = nullptr);
@@ -854,6 +1036,68 @@ int felics_compress_views_device_indexed(felics_ctx *ctx, size_t n, const felics
     return rc;
 }
 
+int felics_get_index_view_wide_emit_stats(const felics_ctx *ctx, felics_index16_view_emit_stats *out, size_t out_size) {
+    return copy_stats(ctx, &felics_ctx::i16vestats, out, out_size);
+}
+
+int felics_compress_views_device_indexed_wide(felics_ctx *ctx, size_t n, const felics_view *views, const uint32_t *segment_pixels,
+                                              void *ready_event, void *d_out, size_t d_out_cap, void *d_index, size_t d_index_cap,
+                                              uint64_t *offsets, uint64_t *lens, uint64_t *idx_offsets, uint64_t *idx_lens, uint64_t *idx_total) {
+    if (!ctx || (n && (!views || !segment_pixels || !d_out || !offsets || !lens || !idx_offsets || !idx_lens))) return FELICS_E_INVALID_ARGUMENT;
+    if (ctx->failed) return FELICS_E_HIP;
+    if (idx_total) *idx_total = 0;
+    bool asked = false;
+    for (size_t i = 0; i < n; i++) {  // every view and its segment checked before anything is launched: the first error in view order
+        int64_t lo, hi;
+        const int rc = check_view(views[i], lo, hi);
+        if (rc) return rc;
+        if (segment_pixels[i] == 0) continue;
+        if (!index_segment_ok(segment_pixels[i])) return FELICS_E_INVALID_ARGUMENT;
+        if (views[i].depth != FELICS_DEPTH_16) return FELICS_E_UNSUPPORTED;  // (its call is felics_compress_views_device_indexed)
+        asked = true;
+    }
+    if (asked && (!d_index || ((uintptr_t)d_index & 63u))) return FELICS_E_INVALID_ARGUMENT;
+    if (n == 0) return FELICS_OK;
+    if (any_pending(ctx)) return FELICS_E_INVALID_ARGUMENT;  // felics_wait_batch first
+    Index16Place ix{(uint8_t *)d_index, asked ? (uint64_t)d_index_cap : 0, idx_offsets, idx_lens, 0, 0};
+    if (asked) {
+        // the workspace per checkpoint bounds a sub-batch within the batch call's budget: a quarter of the free device memory and what
+        // this context holds for it already; an image whose own checkpoints do not fit is refused
+        HIP_TRY(ctx, hipSetDevice(ctx->device));
+        size_t free_b = 0, total_b = 0;
+        HIP_TRY(ctx, hipMemGetInfo(&free_b, &total_b));
+        ix.budget = free_b / 4;
+        for (const Lane &l : ctx->lanes) ix.budget += l.i16_bitmap.cap + l.i16_prefix.cap;
+        for (size_t i = 0; i < n; i++) {
+            if (!segment_pixels[i]) continue;
+            const felics_view &v = views[i];
+            const uint64_t planes = v.color == FELICS_COLOR_RGB ? 3 : 1;
+            const uint64_t K = index16_layout(v.width, v.height, (uint32_t)v.color, segment_pixels[i]).K;
+            if (planes * K * index16_cp_bytes(v.color) + 24u > ix.budget) return FELICS_E_UNSUPPORTED;
+        }
+        if (const char *e = getenv("FELICS_TEST_INDEX16_EMIT_CPS")) ix.test_cps = (uint64_t)std::max(1, atoi(e));  // tests: several sub-batches
+    }
+    for (size_t i = 0; i < n; i++) idx_offsets[i] = idx_lens[i] = 0;
+    felics_view_stats add = {};
+    const IndexAsk ask{nullptr, nullptr, segment_pixels, &ix};
+    const int rc = views_device(ctx, n, views, ready_event, d_out, d_out_cap, offsets, lens, add, &ask);
+    ctx->vstats.views += add.views;  // (bytes_staged: stage_frame has counted)
+    ctx->vstats.dense += add.dense;
+    ctx->vstats.in_place += add.in_place;
+    ctx->vstats.gathered += add.gathered;
+    if (rc) return rc;  // (an error of the stream part: *idx_total stays 0)
+    if (idx_total) *idx_total = ix.total;
+    felics_index16_view_emit_stats &st = ctx->i16vestats;
+    st.views += n;
+    st.indexes += ix.indexes;
+    st.rows_written += ix.rows;
+    st.index_bytes += ix.bytes;
+    st.sub_batches += ix.sub_batches;
+    st.shapes_max = ix.shapes_max;
+    st.redone += ix.redone;
+    return ix.too_small ? FELICS_E_BUFFER_TOO_SMALL : FELICS_OK;
+}
+
 }  // extern "C"
 
 namespace felics {
@@ -873,7 +1117,8 @@ int views_device(felics_ctx *ctx, size_t n, const felics_view *views, void *read
         MixImage &m = im[i];
         m = mix_image(felics_image{v.data, v.width, v.height, v.color, v.depth});
         if (ask && ask->segment_pixels[i]) {
-            m.index = ask->d_index + ask->offsets[i];
+            if (ask->wide) m.index16 = true;
+            else m.index = ask->d_index + ask->offsets[i];
             m.segment_pixels = ask->segment_pixels[i];
         }
         const int64_t bytes = v.depth == FELICS_DEPTH_16 ? 2 : 1;
@@ -923,7 +1168,7 @@ int views_device(felics_ctx *ctx, size_t n, const felics_view *views, void *read
         if (hipStreamSynchronize(l.stream) != hipSuccess) return leave(hip_fail(ctx, hipGetLastError(), "gathering views"));
     }
     counted = add;
-    return leave(images_device(ctx, im, (uint8_t *)d_out, d_out_cap, offsets, lens));
+    return leave(images_device(ctx, im, (uint8_t *)d_out, d_out_cap, offsets, lens, ask ? ask->wide : nullptr));
 }
 
 }  // namespace felics

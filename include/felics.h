@@ -700,8 +700,9 @@ int felics_get_index_emit_stats(const felics_ctx *ctx, felics_index_emit_stats *
  * above the one in front of it; every window sample in the plane's range (0..65535, Co / Cg -65535..65535); and the END CHECK.
  * WHAT THE CHECKS DO NOT PROVE: as above, and COUNTERS ARE NOT JUDGED: a forged counter gives a wrong Rice parameter in a segment
  * whose end check then fails (or whose pixels are wrong, as with an index of another stream); no address depends on a counter.
- * The encoder writes this index beside the streams of a blocking same-shape batch: felics_compress_batch_device_indexed16 below.
- * NOT HERE: the encoder's index for views, mixed shapes, queued and host-buffer calls; a lane form and a queued form of the decoder;
+ * The encoder writes this index beside the streams of a blocking same-shape batch (felics_compress_batch_device_indexed16 below) and
+ * of views and mixed shapes ("Restart index: 16-bit streams, written while encoding views and mixed shapes").
+ * NOT HERE: the encoder's index in queued and host-buffer calls; a lane form and a queued form of the decoder;
  * a hashed table for small segments; cfelics / dfelics flags (--index keeps refusing 16-bit images).  (Regions are built: "Restart
  * index: regions of 16-bit streams", below; so are views and mixed shapes in the decoder: "Restart index: 16-bit streams into views
  * and mixed shapes".)
@@ -774,7 +775,8 @@ int felics_get_index_wide_stats(const felics_ctx *ctx, felics_index16_stats *out
  * and checkpoint and the bits' prefix counts: 16 KB per gray checkpoint, 32 KB per RGB plane's) does not fit a quarter of the free
  * device memory.  That workspace also bounds the images of a pass; FELICS_TEST_PASS_IMAGES applies as in the unindexed call.
  * An empty image gets the 64-byte header alone (K = 0).
- * NOT HERE: views, mixed shapes and a queued form of this call; host-buffer entry points; cfelics / dfelics --index for 16-bit files. */
+ * NOT HERE: a queued form of this call; host-buffer entry points; cfelics / dfelics --index for 16-bit files.  (Views and mixed shapes
+ * have a call of their own: felics_compress_views_device_indexed16, below.) */
 int felics_compress_batch_device_indexed_wide(felics_ctx *ctx, size_t n, const void *d_pixels, uint32_t w, uint32_t h, int color, void *d_out,
                                               size_t d_out_cap, uint32_t segment_pixels, void *d_index, size_t d_index_cap, uint64_t *offsets,
                                               uint64_t *lens, uint64_t *idx_offsets, uint64_t *idx_lens, uint64_t *idx_total);
@@ -968,6 +970,71 @@ static inline int felics_decompress_indexed16_view(const uint8_t *in, size_t len
 }
 static inline int felics_get_index16_view_stats(const felics_ctx *ctx, felics_index16_view_stats *out, size_t out_size) {
     return felics_get_index_view_wide_stats(ctx, out, out_size);
+}
+
+/* ---- Restart index: 16-bit streams, written while encoding views and mixed shapes ----
+ * felics_compress_views_device that also WRITES THE VERSION-2 INDEX of every 16-bit view i with segment_pixels[i] != 0 -- the encode
+ * side of felics_decompress_views_device_indexed16, which takes this call's buffers and arrays as they come back.  Views of any mix
+ * of shapes, colours and segments in one call; the streams are byte for byte felics_compress_views_device's and placed as that call
+ * places them, every index is byte for byte what felics_index16_build makes of stream i with segment_pixels[i].
+ * Everything felics_compress_views_device says holds unless named here: the view checks and the first error in view order before
+ * anything is launched, the classes (every 16-bit view is gathered), slots or the exact second run, FELICS_E_BUFFER_TOO_SMALL with
+ * lens[0] for d_out, ready_event (d_index counts as d_out does), refused while a ticket is outstanding, n = 0 returns FELICS_OK,
+ * FELICS_E_HIP on a failed context.
+ *   PLACEMENT: the size of a version-2 index depends on the content, so the LIBRARY places the indexes and there is no host planner:
+ *   idx_offsets / idx_lens are HOST arrays the call fills, *idx_total (may be NULL) the bytes all indexes need.  Every offset is a
+ *   multiple of 64 (d_index must be 64-byte aligned, else FELICS_E_INVALID_ARGUMENT); the ranges are disjoint and tile
+ *   [0, *idx_total) without gaps; their ORDER IS UNSPECIFIED (it is the order in which the call's sub-batches land, not view order).
+ *   A view without an index gets idx_lens[i] = idx_offsets[i] = 0.  A zero-sized view that asks for one gets the 64-byte version-2
+ *   header, built on the host and placed like the others.  d_index may be NULL if no view asks for an index.
+ *   A SHORT d_index_cap is FELICS_E_BUFFER_TOO_SMALL as in felics_compress_batch_device_indexed16: the streams, offsets and lens are
+ *   complete and valid, idx_offsets / idx_lens / *idx_total say what is needed, the indexes whose end lies inside d_index_cap are
+ *   written, the others are not begun and nothing behind d_index_cap is written; a second call with *idx_total bytes succeeds.  An
+ *   error of the stream part comes back as from felics_compress_views_device, with *idx_total = 0.
+ *   Checked before anything is launched, per view in view order behind the view's own checks: segment_pixels[i] != 0 that is not a
+ *   multiple of FELICS_INDEX_GRANULE (FELICS_E_INVALID_ARGUMENT); an 8-bit view with a segment (FELICS_E_UNSUPPORTED: its call is
+ *   felics_compress_views_device_indexed; 8-bit views with segment 0 take part and get their streams).  Then NULL arrays with n > 0,
+ *   a NULL d_index with an index asked for, a misaligned d_index (FELICS_E_INVALID_ARGUMENT), and an image whose own checkpoints do
+ *   not fit the workspace budget of felics_compress_batch_device_indexed16 (FELICS_E_UNSUPPORTED): a quarter of the free device memory
+ *   plus what the context already holds for this.
+ * The per-checkpoint workspace (16 KB per gray checkpoint, 32 KB per RGB plane's, in the workspace of the lane the sub-batch ran on)
+ * also bounds a sub-batch: when indexes are asked for, a pass of a bucket is cut so that its checkpoints fit the budget; a call
+ * without indexes is cut exactly as felics_compress_views_device cuts it.  FELICS_TEST_INDEX16_EMIT_CPS=k in the environment (read
+ * per call) caps a sub-batch at k checkpoints, at least one image per sub-batch (tests).
+ * A sub-batch's indexes are written where it lands, by the table-driven kernels (k_wide_index_*_t: K, segment, shape and samples per
+ * plane); a group redone after a slot overflow gets them from the uniform writer of felics_compress_batch_device_indexed16.  A run
+ * for the sizes alone (d_out cannot hold the slots) writes no index: the run that places the streams writes them.
+ * NAMES: exported as felics_compress_views_device_indexed_wide and felics_get_index_view_wide_emit_stats; the aliases
+ * felics_compress_views_device_indexed16 and felics_get_index16_view_emit_stats follow the declarations.
+ * NOT HERE: a queued (ticketed) form; felics_submit_surfaces_device with an index; host-buffer entry points; cfelics / dfelics flags;
+ * 8-bit and 16-bit indexes from one call. */
+int felics_compress_views_device_indexed_wide(felics_ctx *ctx, size_t n, const felics_view *views, const uint32_t *segment_pixels,
+                                              void *ready_event, void *d_out, size_t d_out_cap, void *d_index, size_t d_index_cap,
+                                              uint64_t *offsets, uint64_t *lens, uint64_t *idx_offsets, uint64_t *idx_lens, uint64_t *idx_total);
+
+/* What a context's felics_compress_views_device_indexed16 calls wrote so far (cumulative but shapes_max; calls that returned FELICS_OK
+ * or FELICS_E_BUFFER_TOO_SMALL for the index buffer).  felics_index16_emit_stats does not count these calls. */
+typedef struct felics_index16_view_emit_stats {
+    uint64_t views;         /* views of those calls */
+    uint64_t indexes;       /* indexes written by a kernel (one that is written again counts again; host-built empty ones do not) */
+    uint64_t rows_written;  /* state rows of those indexes: the sum of their directories' n_rows */
+    uint64_t index_bytes;   /* bytes of the indexes written, the empty ones' headers included */
+    uint64_t sub_batches;   /* sub-batches whose indexes the table-driven writer wrote */
+    uint64_t shapes_max;    /* NOT cumulative: the distinct shapes of the last call's most mixed such sub-batch */
+    uint64_t redone;        /* indexes written by the uniform writer inside a remedy */
+} felics_index16_view_emit_stats;
+/* Writes min(out_size, sizeof(felics_index16_view_emit_stats)) bytes, never more. */
+int felics_get_index_view_wide_emit_stats(const felics_ctx *ctx, felics_index16_view_emit_stats *out, size_t out_size);
+
+static inline int felics_compress_views_device_indexed16(felics_ctx *ctx, size_t n, const felics_view *views, const uint32_t *segment_pixels,
+                                                         void *ready_event, void *d_out, size_t d_out_cap, void *d_index, size_t d_index_cap,
+                                                         uint64_t *offsets, uint64_t *lens, uint64_t *idx_offsets, uint64_t *idx_lens,
+                                                         uint64_t *idx_total) {
+    return felics_compress_views_device_indexed_wide(ctx, n, views, segment_pixels, ready_event, d_out, d_out_cap, d_index, d_index_cap, offsets,
+                                                     lens, idx_offsets, idx_lens, idx_total);
+}
+static inline int felics_get_index16_view_emit_stats(const felics_ctx *ctx, felics_index16_view_emit_stats *out, size_t out_size) {
+    return felics_get_index_view_wide_emit_stats(ctx, out, out_size);
 }
 
 /* Text for a code above; for FELICS_E_HIP felics_last_error(ctx) has the HIP message. */
