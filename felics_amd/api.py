@@ -144,6 +144,15 @@ class _CRegion16Stats(C.Structure):  # felics_region16_stats
                 ("rows_loaded", C.c_uint64), ("passes", C.c_uint64)]
 
 
+class _CRegionViewStats(C.Structure):  # felics_region_view_stats
+    _fields_ = [("regions", C.c_uint64), ("undecoded", C.c_uint64), ("segments_walked", C.c_uint64), ("segments_skipped", C.c_uint64),
+                ("pixels_walked", C.c_uint64), ("launches", C.c_uint64), ("passes", C.c_uint64), ("plane_bytes", C.c_uint64)]
+
+
+class _CRegion16ViewStats(C.Structure):  # felics_region16_view_stats
+    _fields_ = _CRegionViewStats._fields_ + [("rows_loaded", C.c_uint64), ("table_bytes", C.c_uint64)]
+
+
 INDEX_GRANULE = 4096  # FELICS_INDEX_GRANULE
 E_INVALID_INDEX = -12
 
@@ -189,6 +198,9 @@ EXPORTS = [
     "felics_decompress_region_indexed_wide", "felics_decompress_regions_device_indexed_wide", "felics_get_region_wide_stats",
     "felics_decompress_views_device_indexed_wide", "felics_decompress_indexed_view_wide", "felics_get_index_view_wide_stats",
     "felics_compress_views_device_indexed_wide", "felics_get_index_view_wide_emit_stats",
+    "felics_decompress_region_views_device_indexed", "felics_decompress_region_views_device_indexed_wide",
+    "felics_decompress_region_indexed_view", "felics_decompress_region_indexed_view_wide",
+    "felics_get_region_view_stats", "felics_get_region_view_wide_stats",
 ]
 
 _lib = None
@@ -318,6 +330,15 @@ def lib():
                                                                   C.POINTER(C.c_int)]
         L.felics_decompress_indexed_view_wide.argtypes = [vp, sz, vp, sz, C.POINTER(_CView), C.POINTER(_CHeader)]
         L.felics_get_index_view_wide_stats.argtypes = [vp, C.POINTER(_CIndex16ViewStats), sz]
+    if hasattr(L, "felics_decompress_region_views_device_indexed"):  # (as above: an older build decodes no regions into views)
+        u64 = C.POINTER(C.c_uint64)
+        for call in (L.felics_decompress_region_views_device_indexed, L.felics_decompress_region_views_device_indexed_wide):
+            call.argtypes = [vp, sz, vp, u64, u64, vp, u64, u64, sz, C.POINTER(_CRegion), C.POINTER(_CView), vp, C.POINTER(_CHeader),
+                             C.POINTER(C.c_int)]
+        for call in (L.felics_decompress_region_indexed_view, L.felics_decompress_region_indexed_view_wide):
+            call.argtypes = [vp, sz, vp, sz, C.POINTER(_CRegion), C.POINTER(_CView), C.POINTER(_CHeader)]
+        L.felics_get_region_view_stats.argtypes = [vp, C.POINTER(_CRegionViewStats), sz]
+        L.felics_get_region_view_wide_stats.argtypes = [vp, C.POINTER(_CRegion16ViewStats), sz]
     if hasattr(L, "felics_compress_views_device_indexed_wide"):  # (as above: an older build writes 16-bit indexes for one shape only)
         u64 = C.POINTER(C.c_uint64)
         L.felics_compress_views_device_indexed_wide.argtypes = [vp, sz, C.POINTER(_CView), C.POINTER(C.c_uint32), vp, vp, sz, vp, sz, u64, u64,
@@ -1143,6 +1164,61 @@ class Encoder:
         return self.decompress_views_device_indexed16(d_streams, offsets, lens, d_index, idx_offsets, idx_lens, [view_of_array(a) for a in arrays],
                                                       ready_event)
 
+    def decompress_region_views_device_indexed(self, d_streams, offsets, lens, d_index, idx_offsets, idx_lens, regions, views, ready_event=None):
+        """felics_decompress_region_views_device_indexed: windows of 8-bit streams of any shapes, each stream with its restart index at
+        d_index + idx_offsets[s] (a multiple of 16; idx_lens[s] bytes), decoded a wave per (region, plane, needed segment) straight
+        into views[r] (tuples as for decompress_views_device, w x h of regions[r] = (stream, x, y, w, h)); only sample bytes are
+        written.  ready_event as for decompress_views_device.  Returns (list of Header per stream -- zeros where a header is invalid
+        --, status array per region); a refused view, region or index address raises FelicsError, a failing region
+        DecompressionError or FelicsError, with .status (per region) and .headers."""
+        return self._region_views_indexed(lib().felics_decompress_region_views_device_indexed, d_streams, offsets, lens, d_index, idx_offsets,
+                                          idx_lens, regions, views, ready_event)
+
+    def _region_views_indexed(self, call, d_streams, offsets, lens, d_index, idx_offsets, idx_lens, regions, views, ready_event):
+        """what decompress_region_views_device_indexed and its 16-bit form share: the arrays, the call, the errors"""
+        n, offsets, lens, idx_offsets, idx_lens = _stream_arrays(offsets, lens, idx_offsets, idx_lens)
+        nr = len(regions)
+        if len(views) != nr:
+            raise ValueError("a view per region")
+        regs = (_CRegion * max(nr, 1))(*[_CRegion(*(int(v) for v in r)) for r in regions])
+        cv = (_CView * max(nr, 1))(*[_cview(v) for v in views])
+        status = np.zeros(max(nr, 1), dtype=np.int32)
+        hdrs = (_CHeader * max(n, 1))()
+        rc = call(self._h, n, d_streams, offsets, lens, d_index, idx_offsets, idx_lens, nr, regs, cv, int(ready_event) if ready_event else None,
+                  hdrs, status.ctypes.data_as(C.POINTER(C.c_int)))
+        headers = [Header(h.color_type, h.pixel_depth, h.width, h.height) for h in hdrs[:n]]  # (zeros where the header is invalid)
+        if rc != 0:
+            raise self._indexed_error(rc, status=status[:nr], headers=headers)
+        return headers, status[:nr]
+
+    def decompress_region_arrays_device_indexed(self, d_streams, offsets, lens, d_index, idx_offsets, idx_lens, regions, arrays, ready_event=None):
+        """decompress_region_views_device_indexed into objects with __cuda_array_interface__ (view_of_array), as
+        decompress_arrays_device_indexed: window r goes into arrays[r] -- batch[r], a cell of a mosaic, rgba[..., :3]."""
+        return self.decompress_region_views_device_indexed(d_streams, offsets, lens, d_index, idx_offsets, idx_lens, regions,
+                                                           [view_of_array(a) for a in arrays], ready_event)
+
+    def decompress_region_views_device_indexed16(self, d_streams, offsets, lens, d_index, idx_offsets, idx_lens, regions, views, ready_event=None):
+        """felics_decompress_region_views_device_indexed16: decompress_region_views_device_indexed for 16-bit streams and their
+        version-2 indexes (index addresses multiples of 64), into views of depth 16."""
+        return self._region_views_indexed(lib().felics_decompress_region_views_device_indexed_wide, d_streams, offsets, lens, d_index, idx_offsets,
+                                          idx_lens, regions, views, ready_event)
+
+    def decompress_region_arrays_device_indexed16(self, d_streams, offsets, lens, d_index, idx_offsets, idx_lens, regions, arrays, ready_event=None):
+        """decompress_region_views_device_indexed16 into uint16 objects with __cuda_array_interface__ (view_of_array)."""
+        return self.decompress_region_views_device_indexed16(d_streams, offsets, lens, d_index, idx_offsets, idx_lens, regions,
+                                                             [view_of_array(a) for a in arrays], ready_event)
+
+    def region_view_stats(self):
+        """felics_get_region_view_stats: regions handed to decompress_region_views_device_indexed, those that got a code before a wave
+        was launched for them, the segments walked and skipped, the pixels walked, launches and passes; cumulative -- and plane_bytes,
+        the RGB scratch of the last call's largest pass."""
+        return self._stats("felics_get_region_view_stats", _CRegionViewStats)
+
+    def region16_view_stats(self):
+        """felics_get_region16_view_stats: region_view_stats for decompress_region_views_device_indexed16, with the state rows loaded
+        (cumulative) and table_bytes (the last call's estimator tables)."""
+        return self._stats("felics_get_region_view_wide_stats", _CRegion16ViewStats)
+
     def index16_view_stats(self):
         """felics_get_index16_view_stats: streams handed to decompress_views_device_indexed16, those that got a code before a wave was
         launched for them, the waves (items), kernel launches, stream passes and state rows loaded; cumulative -- and plane_bytes (the
@@ -1419,6 +1495,21 @@ def _indexed_view(call, data, index, array):
     if rc != 0:
         raise DecompressionError(rc) if rc in DecompressionError.KINDS else FelicsError(rc)
     return array
+
+
+def decompress_region_indexed_view(data, index, x, y, w, h, array):
+    """felics_decompress_region_indexed_view: the w x h window at (x, y) of an 8-bit stream decoded through its restart index INTO
+    `array`, a writable numpy array as for decompress_indexed_view: only the array's own samples are written.  The host model of
+    Encoder.decompress_region_views_device_indexed."""
+    return _indexed_view(lambda d, dl, i, il, view, hdr: lib().felics_decompress_region_indexed_view(
+        d, dl, i, il, C.byref(_CRegion(0, x, y, w, h)), view, hdr), data, index, array)
+
+
+def decompress_region_indexed16_view(data, index, x, y, w, h, array):
+    """felics_decompress_region_indexed16_view: decompress_region_indexed_view for a 16-bit stream and its version-2 index, into a
+    uint16 array.  The host model of Encoder.decompress_region_views_device_indexed16."""
+    return _indexed_view(lambda d, dl, i, il, view, hdr: lib().felics_decompress_region_indexed_view_wide(
+        d, dl, i, il, C.byref(_CRegion(0, x, y, w, h)), view, hdr), data, index, array)
 
 
 def region_segments(width, height, segment_pixels, x, y, w, h):

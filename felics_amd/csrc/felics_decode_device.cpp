@@ -687,7 +687,8 @@ int decode16_passes(felics_ctx *ctx, size_t n, size_t per, const void *d_streams
 // ---- the indexed calls: dense (felics_decompress_batch_device_indexed, _indexed16), regions (felics_decompress_regions_device_indexed,
 // _indexed16) and views (felics_decompress_views_device_indexed, _indexed16).  One driver per call kind (dense_indexed, regions_indexed,
 // decompress_views_indexed); what the depths differ in is a form: Depth8 / Depth16 for every kind, IndexSame8 / IndexSame16 on top
-// of them for the two same-shape kinds, IndexViews8 / IndexViews16 for the views.
+// of them for the two same-shape kinds, IndexViews8 / IndexViews16 for the views.  Regions into views
+// (felics_decompress_region_views_device_indexed, _indexed16) are a fourth kind: region_views_indexed, RegionViews8 / RegionViews16.
 
 int first_error(const int *status, size_t n) {
     for (size_t i = 0; i < n; i++)
@@ -1366,6 +1367,320 @@ int views_indexed_call(felics_ctx *ctx, size_t n, const void *d_streams, const u
     return rc;
 }
 
+// The region views kind (felics.h "Restart index: regions into views and mixed shapes"): the views kind's streams and indexes, a plan
+// per region from its own stream's geometry.  felics_decompress_region_views_device_indexed: k_decode8_region_views.
+struct RegionViews8 : Depth8 {
+    using Stats = felics_region_view_stats;
+    static Stats &stats(felics_ctx *ctx) { return ctx->rvstats; }
+    static bool index_ok(const uint8_t *ih, uint32_t color, uint32_t W, uint32_t H, uint64_t len, uint64_t idx_len, Layout &L) {
+        return IndexViews8::index_ok(ih, color, W, H, len, idx_len, L);
+    }
+    int launch(felics_ctx *ctx, hipStream_t s, const uint8_t *st, const uint64_t *d_off, const uint64_t *d_len, const uint8_t *ix, const uint64_t *,
+               const RegionViewStream *d_srows, const RegionRow *d_regions, const ViewRow *d_views, const RegionItem *d_items, size_t cnt,
+               uint32_t lds, Plane *d_planes, int *d_item_status) {
+        HIP_TRY(ctx, launch_decode8_region_views(s, st, d_off, d_len, ix, d_srows, d_regions, d_views, d_items, (uint32_t)cnt, lds, d_planes,
+                                                 d_item_status));
+        return FELICS_OK;
+    }
+    void done(felics_ctx *) {}
+};
+
+// felics_decompress_region_views_device_indexed16: k_decode16_region_views; a class's items in passes of the tables (Depth16).
+struct RegionViews16 : Depth16 {
+    using Stats = felics_region16_view_stats;
+    static Stats &stats(felics_ctx *ctx) { return ctx->rv16stats; }
+    int tables(felics_ctx *ctx, size_t most_items) {  // the largest class of a pass
+        const int rc = Depth16::tables(ctx, most_items);
+        if (!rc) stats(ctx).table_bytes = table_bytes();
+        return rc;
+    }
+    int launch(felics_ctx *ctx, hipStream_t s, const uint8_t *st, const uint64_t *d_off, const uint64_t *d_len, const uint8_t *ix,
+               const uint64_t *d_ilen, const RegionViewStream *d_srows, const RegionRow *d_regions, const ViewRow *d_views,
+               const RegionItem *d_items, size_t cnt, uint32_t lds, Plane *d_planes, int *d_item_status) {
+        return passes(ctx, s, cnt, [&](size_t o, size_t c, uint32_t *table, uint32_t epoch) {  // (a table cut may fall inside a region or a plane)
+            return launch_decode16_region_views(s, st, d_off, d_len, ix, d_ilen, d_srows, d_regions, d_views, d_items + o, (uint32_t)c, lds, d_planes,
+                                                table, epoch, d_item_status + o, d_loaded);
+        });
+    }
+    void done(felics_ctx *ctx) { stats(ctx).rows_loaded += loaded; }
+};
+
+// felics_decompress_region_views_device_indexed and its 16-bit form after the checks that need no device, `form` being what they
+// differ in.  Steps 1 - 3 are decompress_views_indexed's (the event, the two header kernels and ONE synchronise, every stream
+// classified on the host -- without the comparison with a view, which is per region here); then
+//   4. every region classified: its stream's code, the window inside the stream's image, the view's colour and depth;
+//   5. the plan: the clean, non-empty regions in passes of consecutive regions whose crop-sized RGB planes fit the scratch, within a
+//      pass in the LDS classes of their streams' rows, a row per region with the items region_plan_add names for the stream's own W,
+//      H, segment_pixels and planes (an empty region has no row: its code is final here);
+//   6. per pass: a launch per class (the 16-bit form: cut by its tables), k_seg_status over the pass's rows, the strided conversion
+//      of its clean RGB rows (a DecodeRow of W = w, H = h per row), behind one another on the one stream;
+//   7. one copy back of the rows' statuses (and of what the form counted).
+template <typename Form>
+int region_views_indexed(felics_ctx *ctx, size_t n, const void *d_streams, const uint64_t *offsets, const uint64_t *lens, const void *d_index,
+                         const uint64_t *idx_offsets, const uint64_t *idx_lens, size_t n_regions, const felics_region *regions,
+                         const felics_view *views, felics_header *hdrs, int *status, Form form) {
+    using Plane = typename Form::Plane;
+    using Pixel = typename Form::Pixel;
+    hipStream_t s = ctx->lanes[0].stream;
+    typename Form::Stats &vs = Form::stats(ctx);
+    vs.regions += n_regions;
+    vs.plane_bytes = 0;
+    bool headers_read = false;
+    auto fail_all = [&](int code) {
+        for (size_t r = 0; r < n_regions; r++) status[r] = code;
+        for (size_t i = 0; hdrs && !headers_read && i < n; i++) hdrs[i] = felics_header{};  // (no stale header beside a failure code)
+        vs.undecoded += n_regions;
+        return code;
+    };
+    auto al = [](size_t b) { return (b + 15) & ~(size_t)15; };
+    // offsets | lens | index offsets | index lens | stream headers | index headers in dec_meta
+    const size_t o_rec = n * 32, o_ih = o_rec + al(n * sizeof(DecodeHeader)), o_meta_end = o_ih + n * INDEX_HEADER_BYTES;
+    int rc = reserve(ctx, ctx->dec_meta, o_meta_end);
+    if (rc) return fail_all(rc);
+    std::vector<uint64_t> up;
+    std::vector<uint8_t> back;
+    std::vector<typename Form::Layout> lay;
+    std::vector<RegionViewStream> srows;
+    std::vector<int> scode;
+    try {
+        up.resize(4 * n);
+        back.resize(o_meta_end - o_rec);
+        lay.resize(n);
+        srows.assign(n, RegionViewStream{});
+        scode.assign(n, FELICS_OK);
+    } catch (const std::bad_alloc &) {
+        return fail_all(FELICS_E_IO);
+    }
+    std::copy(offsets, offsets + n, up.begin());
+    std::copy(lens, lens + n, up.begin() + n);
+    std::copy(idx_offsets, idx_offsets + n, up.begin() + 2 * n);
+    std::copy(idx_lens, idx_lens + n, up.begin() + 3 * n);
+    const DecodeHeader *rec = reinterpret_cast<const DecodeHeader *>(back.data());
+    const uint8_t *ih = back.data() + (o_ih - o_rec);
+    uint8_t *meta = (uint8_t *)ctx->dec_meta.p;
+    uint64_t *d_off = (uint64_t *)meta, *d_len = d_off + n, *d_ioff = d_len + n, *d_ilen = d_ioff + n;
+    DecodeHeader *d_rec = (DecodeHeader *)(meta + o_rec);
+    uint8_t *d_ih = meta + o_ih;
+    const uint8_t *st = (const uint8_t *)d_streams, *ix = (const uint8_t *)d_index;
+    auto headers = [&]() -> int {
+        int r = wait_ready(ctx, s);  // (the header kernels read stream and index bytes)
+        if (r) return r;
+        HIP_TRY(ctx, hipMemcpyAsync(d_off, up.data(), n * 32, hipMemcpyHostToDevice, s));
+        HIP_TRY(ctx, launch_read_headers(s, st, d_off, d_len, (uint32_t)n, d_rec));
+        HIP_TRY(ctx, launch_read_index_headers(s, ix, d_ioff, d_ilen, (uint32_t)n, d_ih));
+        HIP_TRY(ctx, hipMemcpyAsync(back.data(), d_rec, back.size(), hipMemcpyDeviceToHost, s));
+        HIP_TRY(ctx, hipStreamSynchronize(s));
+        return FELICS_OK;
+    };
+    if ((rc = headers()) != 0) return fail_all(rc);
+    headers_read = true;  // (hdrs[] is filled below, whatever happens after it)
+    // the streams one by one: the first code of the views call's list, the comparison with a view left out
+    for (size_t i = 0; i < n; i++) {
+        const DecodeHeader &h = rec[i];
+        if (hdrs) hdrs[i] = h.status == FELICS_OK ? felics_header{h.color, h.depth, h.W, h.H} : felics_header{};
+        int code = h.dstatus;
+        if (!code && h.depth != Form::DEPTH) code = FELICS_E_UNSUPPORTED;  // the other depth has a format and a call of its own
+        if (!code && !Form::lds_ok(h.W, h.color)) code = FELICS_E_UNSUPPORTED;  // no host fallback here
+        if (!code && (idx_lens[i] < INDEX_HEADER_BYTES || !Form::index_ok(ih + i * INDEX_HEADER_BYTES, h.color, h.W, h.H, lens[i], idx_lens[i], lay[i])))
+            code = FELICS_E_INVALID_INDEX;
+        scode[i] = code;
+        if (!code) srows[i] = RegionViewStream{h.W, h.H, h.color, idx_rd32(ih + i * INDEX_HEADER_BYTES + IDX_SEGPIX), lay[i].K, 0, idx_offsets[i]};
+    }
+    // the regions one by one; `walks`: a clean region with pixels to decode
+    auto walks = [&](size_t r) { return status[r] == FELICS_OK && !region_empty(regions[r]); };
+    for (size_t r = 0; r < n_regions; r++) {
+        const felics_region &g = regions[r];
+        const DecodeHeader &h = rec[g.stream];
+        int code = scode[g.stream];
+        if (!code && !region_inside(h.W, h.H, g)) code = FELICS_E_INVALID_ARGUMENT;
+        if (!code && ((int)h.color != views[r].color || (int)h.depth != views[r].depth)) code = FELICS_E_INVALID_DIMENSIONS;
+        status[r] = code;
+    }
+    // passes: consecutive regions whose crop-sized planes (three Plane samples per RGB crop pixel) fit the budget; a single larger
+    // region is a pass of its own
+    auto plane_bytes_of = [&](size_t r) {
+        return walks(r) && rec[regions[r].stream].color ? 3ull * sizeof(Plane) * regions[r].w * regions[r].h : 0ull;
+    };
+    uint64_t plane_total = 0;
+    for (size_t r = 0; r < n_regions; r++) plane_total += plane_bytes_of(r);
+    uint64_t budget = UINT64_MAX;
+    size_t free_b = 0, total_b = 0;
+    if (plane_total && plane_total + 64 > ctx->dec_planes.cap && hipMemGetInfo(&free_b, &total_b) == hipSuccess)
+        budget = ((uint64_t)free_b + ctx->dec_planes.cap) / 4;
+    budget = std::min(budget, index_views_pass_cap());
+    constexpr uint32_t LDS_CLASS[] = {16u << 10, 32u << 10, 64u << 10, DECODE_LDS_LIMIT};
+    struct Launch {
+        size_t item0, cnt;
+        uint32_t lds;
+    };
+    struct Pass {
+        size_t row0, rows, launch0, launches;
+        uint64_t max_npix;  // of its RGB rows' crops
+    };
+    RegionPlan P;  // rows in (pass, LDS class, region) order, a row's items contiguous; plane_off within the pass
+    std::vector<uint32_t> row_region, segs;
+    std::vector<ViewRow> cviews;
+    std::vector<DecodeRow> conv;
+    std::vector<Launch> launches;
+    std::vector<Pass> passes;
+    std::vector<int> row_status;
+    std::vector<uint8_t> tables;
+    uint64_t most = 0, skipped = 0;
+    size_t o_regions = 0, o_views = 0, o_items = 0, o_conv = 0, o_end = 0;
+    try {
+        size_t r0 = 0;
+        while (r0 < n_regions) {
+            size_t r1 = r0;
+            uint64_t acc = 0;
+            for (; r1 < n_regions; r1++) {
+                const uint64_t b = plane_bytes_of(r1);
+                if (acc && acc + b > budget) break;
+                acc += b;
+            }
+            most = std::max(most, acc);
+            Pass pass{P.rows.size(), 0, launches.size(), 0, 0};
+            P.plane_samples = 0;
+            P.max_crop = 0;
+            for (int c = 0; c < 4; c++) {
+                Launch L{P.items.size(), 0, 0};
+                for (size_t r = r0; r < r1; r++) {
+                    if (!walks(r)) continue;
+                    const felics_region &g = regions[r];
+                    const RegionViewStream &sr = srows[g.stream];
+                    const uint32_t lds = Form::lds_bytes(sr.W, sr.color);
+                    if (lds > LDS_CLASS[c] || (c > 0 && lds <= LDS_CLASS[c - 1])) continue;
+                    const felics_view &w = views[r];
+                    const uint32_t planes = sr.color ? 3u : 1u, row = (uint32_t)P.rows.size();
+                    const uint64_t walked0 = P.walked;
+                    uint64_t out_at = 0;
+                    if ((rc = region_plan_add(sr.W, sr.H, sr.segment_pixels, planes, sizeof(Pixel), g, row, false, out_at, segs, P)) != 0)
+                        return fail_all(rc);  // 2^31 work items or more
+                    skipped += (uint64_t)planes * sr.K - (P.walked - walked0);
+                    row_region.push_back((uint32_t)r);
+                    cviews.push_back(ViewRow{w.data, w.row_stride, w.pixel_stride, sr.color ? w.channel_stride : 0});
+                    conv.push_back(DecodeRow{row - (uint32_t)pass.row0, g.w, g.h, sr.color, 0, P.rows[row].plane_off});  // (stream: the row within its pass)
+                    L.cnt += P.rows[row].nitems;
+                    L.lds = std::max(L.lds, lds);
+                }
+                if (L.cnt) launches.push_back(L);
+            }
+            pass.rows = P.rows.size() - pass.row0;
+            pass.launches = launches.size() - pass.launch0;
+            pass.max_npix = P.max_crop;
+            if (pass.rows) passes.push_back(pass);
+            r0 = r1;
+        }
+        // stream rows | region rows | their views | items | the conversion rows, copied up in one piece
+        const size_t nrows = P.rows.size(), n_items = P.items.size();
+        o_regions = al(n * sizeof(RegionViewStream));
+        o_views = o_regions + al(nrows * sizeof(RegionRow));
+        o_items = o_views + al(nrows * sizeof(ViewRow));
+        o_conv = o_items + al(n_items * sizeof(RegionItem));
+        o_end = o_conv + nrows * sizeof(DecodeRow);
+        if (nrows) {
+            tables.assign(o_end, 0);
+            memcpy(tables.data(), srows.data(), n * sizeof(RegionViewStream));
+            memcpy(tables.data() + o_regions, P.rows.data(), nrows * sizeof(RegionRow));
+            memcpy(tables.data() + o_views, cviews.data(), nrows * sizeof(ViewRow));
+            memcpy(tables.data() + o_items, P.items.data(), n_items * sizeof(RegionItem));
+            memcpy(tables.data() + o_conv, conv.data(), nrows * sizeof(DecodeRow));
+            row_status.assign(nrows, FELICS_E_HIP);  // until the kernels' own word arrives
+        }
+    } catch (const std::bad_alloc &) {
+        return fail_all(FELICS_E_IO);
+    }
+    const size_t nrows = P.rows.size(), n_items = P.items.size();
+    // device side: the tables in dec_region_work; a word per item and one per row in dec_seg_status, what the form keeps behind them;
+    // the form's own tables for the largest class of a pass
+    const size_t o_extra = al(n_items * 4) + al(nrows * 4);
+    size_t most_items = 0, n_launches = 0;
+    for (const Launch &L : launches) most_items = std::max(most_items, L.cnt);
+    if (nrows && (rc = reserve(ctx, ctx->dec_region_work, o_end)) != 0) return fail_all(rc);
+    if (nrows && (rc = reserve(ctx, ctx->dec_seg_status, o_extra + Form::EXTRA)) != 0) return fail_all(rc);
+    if (most && (rc = reserve(ctx, ctx->dec_planes, (size_t)most + 64)) != 0) return fail_all(rc);
+    if (nrows && (rc = form.tables(ctx, most_items)) != 0) return fail_all(rc);
+    for (const Launch &L : launches) n_launches += form.launches_of(L.cnt);
+    for (size_t r = 0; r < n_regions; r++) vs.undecoded += status[r] != FELICS_OK;
+    for (size_t r = 0; r < n_regions; r++)  // (an empty region skips every segment of its stream)
+        if (status[r] == FELICS_OK && region_empty(regions[r])) skipped += (uint64_t)(srows[regions[r].stream].color ? 3u : 1u) * srows[regions[r].stream].K;
+    vs.segments_walked += P.walked;
+    vs.segments_skipped += skipped;
+    vs.pixels_walked += P.pixels_walked;
+    vs.launches += n_launches;
+    vs.passes += passes.size();
+    vs.plane_bytes = most;
+    if (nrows) {
+        uint8_t *work = (uint8_t *)ctx->dec_region_work.p;
+        const RegionViewStream *d_srows = (const RegionViewStream *)work;
+        const RegionRow *d_regions = (const RegionRow *)(work + o_regions);
+        const ViewRow *d_cviews = (const ViewRow *)(work + o_views);
+        const RegionItem *d_items = (const RegionItem *)(work + o_items);
+        const DecodeRow *d_conv = (const DecodeRow *)(work + o_conv);
+        int *d_item_status = (int *)ctx->dec_seg_status.p, *d_row_status = (int *)((uint8_t *)ctx->dec_seg_status.p + al(n_items * 4));
+        Plane *d_planes = (Plane *)ctx->dec_planes.p;
+        auto queue = [&]() -> int {
+            int r;
+            HIP_TRY(ctx, hipMemcpyAsync(work, tables.data(), o_end, hipMemcpyHostToDevice, s));  // (the five tables in one copy)
+            HIP_TRY(ctx, hipMemsetAsync(d_item_status, 0xFF, al(n_items * 4) + nrows * 4, s));
+            if ((r = form.begin(ctx, s, (uint8_t *)ctx->dec_seg_status.p + o_extra)) != 0) return r;
+            for (const Pass &pass : passes) {
+                for (size_t k = pass.launch0; k < pass.launch0 + pass.launches; k++) {
+                    const Launch &L = launches[k];
+                    if ((r = form.launch(ctx, s, st, d_off, d_len, ix, d_ilen, d_srows, d_regions, d_cviews, d_items + L.item0, L.cnt, L.lds, d_planes,
+                                         d_item_status + L.item0)) != 0)
+                        return r;
+                }
+                HIP_TRY(ctx, (launch_seg_views_finish<Plane, Pixel>(s, (uint32_t)pass.rows, d_regions + pass.row0, d_item_status, d_conv + pass.row0,
+                                                                    d_cviews + pass.row0, pass.max_npix, d_planes, d_row_status + pass.row0)));
+            }
+            HIP_TRY(ctx, hipMemcpyAsync(row_status.data(), d_row_status, nrows * 4, hipMemcpyDeviceToHost, s));
+            if ((r = form.end(ctx, s)) != 0) return r;
+            HIP_TRY(ctx, hipStreamSynchronize(s));  // (the host tables live until here)
+            form.done(ctx);
+            return FELICS_OK;
+        };
+        if ((rc = queue()) != 0) {
+            for (size_t r = 0; r < nrows; r++) status[row_region[r]] = FELICS_E_HIP;
+            return rc;
+        }
+        for (size_t r = 0; r < nrows; r++) status[row_region[r]] = row_status[r];
+    }
+    return first_error(status, n_regions);
+}
+
+// The two calls' entry: the checks that need no device, made before anything is launched, then region_views_indexed between the
+// setting and the clearing of the ready event.
+template <typename Form>
+int region_views_call(felics_ctx *ctx, size_t n_streams, const void *d_streams, const uint64_t *offsets, const uint64_t *lens, const void *d_index,
+                      const uint64_t *idx_offsets, const uint64_t *idx_lens, size_t n_regions, const felics_region *regions, const felics_view *views,
+                      void *ready_event, felics_header *hdrs, int *status, Form form) {
+    if (!ctx || (n_regions && !status)) return FELICS_E_INVALID_ARGUMENT;
+    auto fail_all = [&](int code) {
+        for (size_t i = 0; hdrs && i < n_streams; i++) hdrs[i] = felics_header{};
+        return fail_call(n_regions, status, nullptr, nullptr, code);
+    };
+    if ((n_streams && (!d_streams || !offsets || !lens || !d_index || !idx_offsets || !idx_lens)) || (n_regions && (!regions || !views)))
+        return fail_all(FELICS_E_INVALID_ARGUMENT);
+    if (n_regions > 0x7FFFFFFFull || n_streams > 0xFFFFFFFFull || (n_regions && n_streams == 0)) return fail_all(FELICS_E_INVALID_ARGUMENT);
+    for (size_t r = 0; r < n_regions; r++) {  // every region and its view before anything is launched: the first error in region order
+        if (regions[r].stream >= n_streams) return fail_all(FELICS_E_INVALID_ARGUMENT);
+        const int rc = felics_view_writable(&views[r]);
+        if (rc) return fail_all(rc);
+        if (views[r].width != regions[r].w || views[r].height != regions[r].h) return fail_all(FELICS_E_INVALID_ARGUMENT);
+    }
+    for (size_t i = 0; i < n_streams; i++)  // every index address
+        if (((uintptr_t)d_index + idx_offsets[i]) & (Form::INDEX_ALIGN - 1u)) return fail_all(FELICS_E_INVALID_ARGUMENT);
+    if (ctx->failed) return fail_all(FELICS_E_HIP);
+    if (n_regions == 0) return FELICS_OK;
+    if (any_pending(ctx)) return fail_all(FELICS_E_INVALID_ARGUMENT);  // felics_wait_batch first
+    if (hipSetDevice(ctx->device) != hipSuccess) return fail_all(hip_fail(ctx, hipGetLastError(), "hipSetDevice"));
+    ctx->view_ready = (hipEvent_t)ready_event;
+    const int rc = region_views_indexed(ctx, n_streams, d_streams, offsets, lens, d_index, idx_offsets, idx_lens, n_regions, regions, views, hdrs,
+                                        status, form);
+    ctx->view_ready = nullptr;
+    return rc;
+}
+
 }  // namespace
 
 }  // namespace felics
@@ -1699,6 +2014,30 @@ int felics_decompress_views_device_indexed_wide(felics_ctx *ctx, size_t n, const
                                                 const felics_view *views, void *ready_event, felics_header *hdrs, int *status) {
     return felics::views_indexed_call(ctx, n, d_streams, offsets, lens, d_index, idx_offsets, idx_lens, views, ready_event, hdrs, status,
                                       felics::IndexViews16{});
+}
+
+int felics_get_region_view_stats(const felics_ctx *ctx, felics_region_view_stats *out, size_t out_size) {
+    return copy_stats(ctx, &felics_ctx::rvstats, out, out_size);
+}
+
+int felics_decompress_region_views_device_indexed(felics_ctx *ctx, size_t n_streams, const void *d_streams, const uint64_t *offsets,
+                                                  const uint64_t *lens, const void *d_index, const uint64_t *idx_offsets,
+                                                  const uint64_t *idx_lens, size_t n_regions, const felics_region *regions,
+                                                  const felics_view *views, void *ready_event, felics_header *hdrs, int *status) {
+    return felics::region_views_call(ctx, n_streams, d_streams, offsets, lens, d_index, idx_offsets, idx_lens, n_regions, regions, views,
+                                     ready_event, hdrs, status, felics::RegionViews8{});
+}
+
+int felics_get_region_view_wide_stats(const felics_ctx *ctx, felics_region16_view_stats *out, size_t out_size) {
+    return copy_stats(ctx, &felics_ctx::rv16stats, out, out_size);
+}
+
+int felics_decompress_region_views_device_indexed_wide(felics_ctx *ctx, size_t n_streams, const void *d_streams, const uint64_t *offsets,
+                                                       const uint64_t *lens, const void *d_index, const uint64_t *idx_offsets,
+                                                       const uint64_t *idx_lens, size_t n_regions, const felics_region *regions,
+                                                       const felics_view *views, void *ready_event, felics_header *hdrs, int *status) {
+    return felics::region_views_call(ctx, n_streams, d_streams, offsets, lens, d_index, idx_offsets, idx_lens, n_regions, regions, views,
+                                     ready_event, hdrs, status, felics::RegionViews16{});
 }
 
 }  // extern "C"

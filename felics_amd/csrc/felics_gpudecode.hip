@@ -630,6 +630,39 @@ struct ViewSink {
     }
 };
 
+// A region's part of a segment straight into the region's view (felics_decompress_region_views_device_indexed and its 16-bit form):
+// the walk ends where RegionSink's does, and a sample is written only if its (column, row) lies inside the window -- gray as ONE
+// aligned store of a T at the place the view's strides give window sample (col - x, y - y0), as ViewSink stores a frame's; RGB to
+// plane c of the region's crop-sized planes at (y - y0) * w + (col - x), as RegionSink does (the strided conversion writes the view).
+// One address rule serves both: the plane is handed over as the dense view it is (row stride w * sizeof(P), pixel stride sizeof(P)),
+// so the sink keeps one base and one pair of strides in scalar registers, not two targets.  Region, strides and W are wave-uniform
+// (scalar loads off blockIdx.x); the store's predicate is the only divergence.
+template <typename T, typename P>
+struct RegionViewSink {
+    RegionSink<T, P> crop;  // the window and W (its two targets stay null)
+    uint8_t *base;          // gray: the view's first sample; RGB: plane c of the region's planes
+    int64_t row_stride, pixel_stride;
+    uint32_t rgb;
+    __device__ __forceinline__ uint64_t stop(uint64_t pend) const { return crop.stop(pend); }
+    __device__ __forceinline__ void store(uint32_t col, uint32_t y, uint64_t, int v) const {
+        const RegionRow &reg = crop.reg;
+        if (col >= reg.x && col - reg.x < reg.w && y >= reg.y && y - reg.y < reg.h) {
+            uint8_t *to = base + view_sample_offset(row_stride, pixel_stride, 0, col - reg.x, y - reg.y, 0);
+            if (rgb) *reinterpret_cast<P *>(to) = (P)v;
+            else *reinterpret_cast<T *>(to) = (T)v;
+        }
+    }
+    // region reg of a stream of rows of W samples (rgb: colour) into view, or into plane c of its planes at `planes`
+    __device__ __forceinline__ static RegionViewSink make(const RegionRow &reg, uint32_t W, uint32_t rgb, uint32_t c, const ViewRow &view,
+                                                          P *planes) {
+        if (rgb)
+            return RegionViewSink{{reg, W, nullptr, nullptr}, reinterpret_cast<uint8_t *>(planes + reg.plane_off + (uint64_t)c * reg.w * reg.h),
+                                  (int64_t)reg.w * (int64_t)sizeof(P), (int64_t)sizeof(P), rgb};
+        return RegionViewSink{{reg, W, nullptr, nullptr}, reinterpret_cast<uint8_t *>(const_cast<void *>(view.data)), view.row_stride,
+                              view.pixel_stride, rgb};
+    }
+};
+
 }  // namespace
 
 // One wave per SEGMENT of a plane of a stream (felics_decompress_batch_device_indexed).  Block b is segment (img, c, j) =
@@ -702,6 +735,29 @@ __global__ __launch_bounds__(64) void k_decode8_seg_views(const uint8_t *__restr
     const ViewSink<uint8_t, int16_t> sink{r.color ? nullptr : reinterpret_cast<uint8_t *>(const_cast<void *>(r.view.data)), r.view.row_stride,
                                           r.view.pixel_stride, r.color ? planes + r.plane_off + (uint64_t)c * r.W * r.H : nullptr};
     const int rc = decode8_from_checkpoint(smem, streams + offsets[r.stream], lens[r.stream], index + r.index_off, geo, r.segment_pixels, r.K, c,
+                                           item.seg, false, sink);
+    if (lane_id() == 0) item_status[blockIdx.x] = rc;
+}
+
+// One wave per WORK ITEM = (region, plane, needed segment) of felics_decompress_region_views_device_indexed (felics_kernels.h; host
+// model: felics_decompress_region_indexed_view).  Item, region, view and stream row are wave-uniform (blockIdx.x: scalar loads); the
+// region names its stream, whose row carries the walk's geometry, segment_pixels and K, so the streams of a launch need not share a
+// shape -- only the launch's dynamic LDS, which holds its widest row.  The host names needed segments only (j < K, p0 < stop).
+// item_status[b] = FELICS_OK or the code; k_seg_status picks a region's first.
+__global__ __launch_bounds__(64) void k_decode8_region_views(const uint8_t *__restrict__ streams, const uint64_t *__restrict__ offsets,
+                                                             const uint64_t *__restrict__ lens, const uint8_t *__restrict__ index,
+                                                             const RegionViewStream *__restrict__ srows, const RegionRow *__restrict__ regions,
+                                                             const ViewRow *__restrict__ views, const RegionItem *__restrict__ items,
+                                                             int16_t *__restrict__ planes, int *__restrict__ item_status) {
+    extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
+    const RegionItem item = items[blockIdx.x];
+    const RegionRow reg = regions[item.region];
+    const ViewRow view = views[item.region];
+    const RegionViewStream r = srows[reg.stream];
+    const DecUniform geo{r.W, r.H, r.color};
+    const uint32_t c = item.plane;
+    const auto sink = RegionViewSink<uint8_t, int16_t>::make(reg, r.W, r.color, c, view, planes);
+    const int rc = decode8_from_checkpoint(smem, streams + offsets[reg.stream], lens[reg.stream], index + r.index_off, geo, r.segment_pixels, r.K, c,
                                            item.seg, false, sink);
     if (lane_id() == 0) item_status[blockIdx.x] = rc;
 }
@@ -1776,6 +1832,36 @@ __global__ __launch_bounds__(64) void k_decode16_seg_views(const uint8_t *__rest
     }
 }
 
+// One wave per WORK ITEM = (region, plane, needed segment) of felics_decompress_region_views_device_indexed16 (host model:
+// felics_decompress_region_indexed16_view): k_decode8_region_views for version-2 indexes, on that kernel's tables (plane_off counts
+// int32 samples); the index's length is idx_lens[region.stream].  Block b of a launch works on items[b] with table b of the launch's
+// tables and the launch's epoch, as in k_decode16_seg_views; item_status[b] = FELICS_OK or the code (k_seg_status picks a region's
+// first); rows_loaded: += the state rows the wave copied.
+__global__ __launch_bounds__(64) void k_decode16_region_views(const uint8_t *__restrict__ streams, const uint64_t *__restrict__ offsets,
+                                                              const uint64_t *__restrict__ lens, const uint8_t *__restrict__ index,
+                                                              const uint64_t *__restrict__ idx_lens, const RegionViewStream *__restrict__ srows,
+                                                              const RegionRow *__restrict__ regions, const ViewRow *__restrict__ views,
+                                                              const RegionItem *__restrict__ items, int32_t *__restrict__ planes,
+                                                              uint32_t *__restrict__ gtable, uint32_t epoch, int *__restrict__ item_status,
+                                                              unsigned long long *__restrict__ rows_loaded) {
+    extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
+    const RegionItem item = items[blockIdx.x];
+    const RegionRow reg = regions[item.region];
+    const ViewRow view = views[item.region];
+    const RegionViewStream r = srows[reg.stream];
+    const DecUniform geo{r.W, r.H, r.color};
+    const uint32_t c = item.plane;
+    const auto sink = RegionViewSink<uint16_t, int32_t>::make(reg, r.W, r.color, c, view, planes);
+    uint32_t *table = gtable + (uint64_t)blockIdx.x * DEC16_CONTEXTS * DEC16_ROW;
+    uint32_t loaded = 0;
+    const int rc = decode16_from_checkpoint(smem, streams + offsets[reg.stream], lens[reg.stream], index + r.index_off, idx_lens[reg.stream], geo,
+                                            r.segment_pixels, r.K, c, item.seg, false, table, epoch, sink, &loaded);
+    if (lane_id() == 0) {
+        item_status[blockIdx.x] = rc;
+        if (loaded) atomicAdd(rows_loaded, (unsigned long long)loaded);
+    }
+}
+
 // ------------------------------------------------------------------------------------------
 // 16-bit streams, sixty-four of one shape per wave, LANE = stream: the walk of k_decode8_lanes with the arithmetic of k_decode16.
 //
@@ -2321,6 +2407,34 @@ hipError_t launch_decode16_seg_views(hipStream_t s, const uint8_t *streams, cons
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(k_decode16_seg_views, dim3(nitems), dim3(64), lds, s, streams, offsets, lens, index, idx_lens, rows, items, planes, table,
                        epoch, item_status, rows_loaded);
+    return hipGetLastError();
+}
+
+// ------------------------------------------------------------------------------------------
+// felics_decompress_region_views_device_indexed and its 16-bit form: a launch of the region walk with the region view sink (a pass's
+// tail: launch_seg_views_finish).
+// ------------------------------------------------------------------------------------------
+
+hipError_t launch_decode8_region_views(hipStream_t s, const uint8_t *streams, const uint64_t *offsets, const uint64_t *lens, const uint8_t *index,
+                                       const RegionViewStream *srows, const RegionRow *regions, const ViewRow *views, const RegionItem *items,
+                                       uint32_t nitems, uint32_t lds, int16_t *planes, int *item_status) {
+    if (nitems == 0) return hipSuccess;
+    const hipError_t e = raise_lds(&k_decode8_region_views, lds);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(k_decode8_region_views, dim3(nitems), dim3(64), lds, s, streams, offsets, lens, index, srows, regions, views, items, planes,
+                       item_status);
+    return hipGetLastError();
+}
+
+hipError_t launch_decode16_region_views(hipStream_t s, const uint8_t *streams, const uint64_t *offsets, const uint64_t *lens, const uint8_t *index,
+                                        const uint64_t *idx_lens, const RegionViewStream *srows, const RegionRow *regions, const ViewRow *views,
+                                        const RegionItem *items, uint32_t nitems, uint32_t lds, int32_t *planes, uint32_t *table, uint32_t epoch,
+                                        int *item_status, unsigned long long *rows_loaded) {
+    if (nitems == 0) return hipSuccess;
+    const hipError_t e = raise_lds(&k_decode16_region_views, lds);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(k_decode16_region_views, dim3(nitems), dim3(64), lds, s, streams, offsets, lens, index, idx_lens, srows, regions, views, items,
+                       planes, table, epoch, item_status, rows_loaded);
     return hipGetLastError();
 }
 

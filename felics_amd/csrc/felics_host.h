@@ -258,6 +258,11 @@ struct felics_ctx {
     // status words), the tables and epochs of felics_decompress_batch_device_indexed16 (dec_table, dec_epoch); the counts of
     // felics_get_index16_view_stats
     felics_index16_view_stats iv16stats = {};
+    // felics_decompress_region_views_device_indexed and its 16-bit form: the buffers of the indexed views calls (the stream rows,
+    // region rows, their views, the work list and the conversion rows in dec_region_work; a pass's crop-sized planes in dec_planes);
+    // the counts of felics_get_region_view_stats and felics_get_region16_view_stats
+    felics_region_view_stats rvstats = {};
+    felics_region16_view_stats rv16stats = {};
     // felics_compress_views_device_indexed: the indexes of a remedy's group (redo_by_shape: written back to back by the uniform
     // writer, copied to where the caller wants them); the counts of felics_get_index_emit_stats
     DevBuf mix_index;

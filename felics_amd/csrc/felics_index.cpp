@@ -98,6 +98,64 @@ int load_checkpoint(const uint8_t *index, const IndexLayout &L, uint32_t color, 
     return FELICS_OK;
 }
 
+// The needed segments of the non-empty region r (inside the image) of an 8-bit stream whose two headers passed their checks, in
+// (plane, segment) order, each from its checkpoint alone, walked up to min(segment end, the pixel behind the region's last one):
+// the walk of felics_decompress_region_indexed and felics_decompress_region_indexed_view.  ch[c]: plane c of the crop (w * h samples);
+// put(c, i, j, v): window sample (i, j) of plane c as it is decoded.  0 or the first failing segment's code.
+template <typename Put>
+int walk_region8(const uint8_t *in, size_t len, const uint8_t *index, const IndexLayout &L, const felics_header &hdr, const felics_region &r,
+                 std::vector<int32_t> (&ch)[3], Put put) {
+    const uint32_t W = hdr.width, H = hdr.height, color = hdr.color_type;
+    const size_t npix = (size_t)W * H, cpix = (size_t)r.w * r.h;
+    const uint32_t seg = idx_rd32(index + IDX_SEGPIX);
+    const uint64_t last = region_last(W, r);
+    uint32_t jfirst, jlast;
+    region_span(W, seg, r, jfirst, jlast);
+    std::vector<int32_t> buf;
+    int rc;
+    try {
+        Estimator est(OPT8);
+        for (uint32_t c = 0; c < L.planes; c++) {
+            ch[c].assign(cpix, 0);
+            for (uint32_t j = jfirst; j <= jlast; j++) {
+                if (!region_needs(W, npix, seg, r, j)) continue;
+                uint64_t start, end;
+                if (index_segment_bounds(index, L, c, j, len, start, end)) return FELICS_E_INVALID_INDEX;
+                BitReader br(in, len, start);
+                const size_t s0 = (size_t)j * seg, s1 = std::min(npix, s0 + seg), stop = (size_t)std::min<uint64_t>(s1, last);
+                // The walk's samples live in `buf`: whole rows from two rows above s0's on (the window's reach), up to `stop`.  The rows
+                // dropped in front are an even count when s0's row is >= 2, none otherwise: the neighbour rule sees the same cases.
+                const size_t y0 = s0 / W, base = y0 >= 2 ? (y0 - 2) * W : 0;
+                buf.assign(stop - base, 0);
+                int32_t *out = buf.data();
+                if ((rc = load_checkpoint(index, L, color, c, j, W, s0, est, out, base)) != 0) return rc;
+                if (j == 0) {
+                    const int32_t p0 = (int32_t)br.bits(32), p1 = (int32_t)br.bits(32);
+                    if (br.failed()) return FELICS_E_IO;
+                    out[0] = p0;
+                    if (stop > 1) out[1] = p1;
+                }
+                rc = decode_span(br, W, OPT8, est, out, std::max<size_t>(s0, 2) - base, std::max<size_t>(stop, 2) - base, nullptr);
+                if (rc) return rc;
+                for (size_t i = s0; i < stop; i++) {
+                    const int32_t v = out[i - base];
+                    if (!in_plane_range(v, color, c)) return FELICS_E_INVALID_VALUE;
+                    const size_t yy = i / W, xx = i - yy * W;
+                    if (xx >= r.x && xx < (size_t)r.x + r.w && yy >= r.y) {
+                        ch[c][(yy - r.y) * r.w + (xx - r.x)] = v;
+                        put(c, (uint32_t)(xx - r.x), (uint32_t)(yy - r.y), v);
+                    }
+                }
+                // the end check where the walk reached the segment's end; a walk that stops early has no bit position to stand on
+                if (stop == s1 && br.pos() != end) return FELICS_E_INVALID_INDEX;
+            }
+        }
+    } catch (const std::bad_alloc &) {
+        return FELICS_E_INVALID_DIMENSIONS;
+    }
+    return FELICS_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -328,56 +386,57 @@ int felics_decompress_region_indexed(const uint8_t *in, size_t len, const uint8_
     const uint32_t W = hdr.width, H = hdr.height, color = hdr.color_type;
     const felics_region r = *rp;
     if (!region_inside(W, H, r)) return FELICS_E_INVALID_ARGUMENT;
-    const size_t npix = (size_t)W * H, cpix = (size_t)r.w * r.h;
+    const size_t cpix = (size_t)r.w * r.h;
     const unsigned planes = color ? 3 : 1;
     if ((uint64_t)cpix * planes > pixels_cap) return FELICS_E_BUFFER_TOO_SMALL;
     if (cpix && !pixels) return FELICS_E_INVALID_ARGUMENT;
     IndexLayout L;
     if (index_len < INDEX_HEADER_BYTES || index_header_check(index, color, W, H, len, L) || L.total != index_len) return FELICS_E_INVALID_INDEX;
     if (region_empty(r)) return FELICS_OK;
-    const uint32_t seg = idx_rd32(index + IDX_SEGPIX);
-    const uint64_t last = region_last(W, r);
-    uint32_t jfirst, jlast;
-    region_span(W, seg, r, jfirst, jlast);
-    std::vector<int32_t> ch[3], buf;
-    try {
-        Estimator est(OPT8);
-        for (uint32_t c = 0; c < L.planes; c++) {
-            ch[c].assign(cpix, 0);
-            for (uint32_t j = jfirst; j <= jlast; j++) {
-                if (!region_needs(W, npix, seg, r, j)) continue;
-                uint64_t start, end;
-                if (index_segment_bounds(index, L, c, j, len, start, end)) return FELICS_E_INVALID_INDEX;
-                BitReader br(in, len, start);
-                const size_t s0 = (size_t)j * seg, s1 = std::min(npix, s0 + seg), stop = (size_t)std::min<uint64_t>(s1, last);
-                // The walk's samples live in `buf`: whole rows from two rows above s0's on (the window's reach), up to `stop`.  The rows
-                // dropped in front are an even count when s0's row is >= 2, none otherwise: the neighbour rule sees the same cases.
-                const size_t y0 = s0 / W, base = y0 >= 2 ? (y0 - 2) * W : 0;
-                buf.assign(stop - base, 0);
-                int32_t *out = buf.data();
-                if ((rc = load_checkpoint(index, L, color, c, j, W, s0, est, out, base)) != 0) return rc;
-                if (j == 0) {
-                    const int32_t p0 = (int32_t)br.bits(32), p1 = (int32_t)br.bits(32);
-                    if (br.failed()) return FELICS_E_IO;
-                    out[0] = p0;
-                    if (stop > 1) out[1] = p1;
-                }
-                rc = decode_span(br, W, OPT8, est, out, std::max<size_t>(s0, 2) - base, std::max<size_t>(stop, 2) - base, nullptr);
-                if (rc) return rc;
-                for (size_t i = s0; i < stop; i++) {
-                    const int32_t v = out[i - base];
-                    if (!in_plane_range(v, color, c)) return FELICS_E_INVALID_VALUE;
-                    const size_t yy = i / W, xx = i - yy * W;
-                    if (xx >= r.x && xx < (size_t)r.x + r.w && yy >= r.y) ch[c][(yy - r.y) * r.w + (xx - r.x)] = v;
-                }
-                // the end check where the walk reached the segment's end; a walk that stops early has no bit position to stand on
-                if (stop == s1 && br.pos() != end) return FELICS_E_INVALID_INDEX;
-            }
-        }
-    } catch (const std::bad_alloc &) {
-        return FELICS_E_INVALID_DIMENSIONS;
-    }
+    std::vector<int32_t> ch[3];
+    if ((rc = walk_region8(in, len, index, L, hdr, r, ch, [](uint32_t, uint32_t, uint32_t, int32_t) {})) != 0) return rc;
     return store_rgb8(ch, planes, (uint8_t *)pixels);
+}
+
+int felics_decompress_region_indexed_view(const uint8_t *in, size_t len, const uint8_t *index, size_t index_len, const felics_region *rp,
+                                          const felics_view *view, felics_header *hdr_out) {
+    if ((!in && len) || (!index && index_len) || !rp || !view) return FELICS_E_INVALID_ARGUMENT;
+    int rc = view_writable_code(*view);
+    if (rc) return rc;
+    const felics_region r = *rp;
+    if (view->width != r.w || view->height != r.h) return FELICS_E_INVALID_ARGUMENT;
+    // the per-stream codes of felics_decompress_region_views_device_indexed, in its order; then the region's
+    felics_header hdr;
+    rc = felics_read_header(in, len, &hdr);
+    if (hdr_out) *hdr_out = rc ? felics_header{} : hdr;
+    if (rc) return rc;
+    const uint32_t W = hdr.width, H = hdr.height, color = hdr.color_type;
+    const unsigned planes = color ? 3 : 1;
+    if ((uint64_t)W * H > 0xFFFFFFFFull) return FELICS_E_INVALID_DIMENSIONS;
+    const size_t npix = (size_t)W * H;
+    // (k_read_headers' rule: two raw 32-bit samples per plane, then at least one flag bit per pixel, padded to a byte)
+    const uint64_t bits = (uint64_t)planes * (64u + (npix > 2 ? npix - 2 : 0));
+    if (len - FELICS_HEADER_BYTES < (bits + 7) / 8) return FELICS_E_IO;
+    if (hdr.pixel_depth != FELICS_DEPTH_8) return FELICS_E_UNSUPPORTED;
+    if (index_lds_bytes(W, color) > INDEX_LDS_LIMIT) return FELICS_E_UNSUPPORTED;  // what the wave form cannot hold, the model refuses too
+    IndexLayout L;
+    if (index_len < INDEX_HEADER_BYTES || index_header_check(index, color, W, H, len, L) || L.total != index_len) return FELICS_E_INVALID_INDEX;
+    if (!region_inside(W, H, r)) return FELICS_E_INVALID_ARGUMENT;
+    if ((int)color != view->color || (int)hdr.pixel_depth != view->depth) return FELICS_E_INVALID_DIMENSIONS;
+    if (region_empty(r)) return FELICS_OK;
+    uint8_t *data = (uint8_t *)const_cast<void *>(view->data);
+    const int64_t rs = view->row_stride, ps = view->pixel_stride, cs = color ? view->channel_stride : 0;
+    std::vector<int32_t> ch[3];
+    // gray: a window sample through the view, as the kernel's sink stores it (an RGB plane waits for the other two)
+    rc = walk_region8(in, len, index, L, hdr, r, ch, [&](uint32_t, uint32_t i, uint32_t j, int32_t v) {
+        if (!color) data[view_sample_offset(rs, ps, 0, i, j, 0)] = (uint8_t)v;
+    });
+    if (rc || !color) return rc;
+    if ((rc = store_rgb8(ch, planes, nullptr)) != 0) return rc;  // (checked first: a region that fails here leaves the view as it was)
+    return convert_rgb8(ch, planes, [&](size_t i, unsigned c, uint8_t v) {
+        const uint32_t j = (uint32_t)(i / r.w), k = (uint32_t)(i - (size_t)j * r.w);
+        data[view_sample_offset(rs, ps, cs, k, j, c)] = v;
+    });
 }
 
 }  // extern "C"

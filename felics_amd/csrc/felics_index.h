@@ -269,6 +269,42 @@ struct RegionPlan {
     uint64_t max_crop = 0;       // the largest w * h of an RGB region (0: gray)
     uint64_t walked = 0, skipped = 0, pixels_walked = 0;  // segments named / not named, pixels the named ones walk (per plane each)
 };
+// One request on a stream of W x H pixels, `planes` planes, segments of segment_pixels, added to the plan as region `region` (the
+// number its items carry): its row, its items, what it walks.  The crop starts at out_at (advanced by its bytes; sample_bytes: of an
+// output sample) and its RGB planes at P.plane_samples (advanced).  header_item: an empty region gets the one REGION_HEADER_ONLY
+// item; without it an empty region has no item (felics_decompress_region_views_device_indexed: the header checks are the host's).
+// P.skipped is the caller's.  0, or FELICS_E_UNSUPPORTED past 2^31 - 1 items; may throw std::bad_alloc.
+inline int region_plan_add(uint32_t W, uint32_t H, uint32_t segment_pixels, uint32_t planes, uint32_t sample_bytes, const felics_region &g,
+                           uint32_t region, bool header_item, uint64_t &out_at, std::vector<uint32_t> &segs, RegionPlan &P) {
+    const uint64_t npix = (uint64_t)W * H;
+    segs.clear();
+    uint64_t stop_at = 0;
+    if (!region_empty(g)) {
+        uint32_t first, last;
+        region_span(W, segment_pixels, g, first, last);
+        for (uint32_t j = first; j <= last; j++)
+            if (region_needs(W, npix, segment_pixels, g, j)) segs.push_back(j);
+        stop_at = region_last(W, g);
+    }
+    const uint64_t cnt = segs.empty() ? (header_item ? 1 : 0) : (uint64_t)planes * segs.size();
+    if (P.items.size() + cnt > 0x7FFFFFFFull) return FELICS_E_UNSUPPORTED;
+    const uint64_t cpix = (uint64_t)g.w * g.h;
+    P.rows.push_back(RegionRow{g.stream, g.x, g.y, g.w, g.h, (uint32_t)P.items.size(), (uint32_t)cnt, 0, out_at, P.plane_samples});
+    out_at += cpix * planes * sample_bytes;
+    if (planes == 3) {
+        P.plane_samples += cpix * 3;
+        P.max_crop = std::max(P.max_crop, cpix);
+    }
+    if (segs.empty() && header_item) P.items.push_back(RegionItem{region, 0, REGION_HEADER_ONLY});
+    for (uint32_t c = 0; c < planes && !segs.empty(); c++)
+        for (const uint32_t j : segs) P.items.push_back(RegionItem{region, c, j});
+    for (const uint32_t j : segs) {
+        const uint64_t p0 = (uint64_t)j * segment_pixels;
+        P.pixels_walked += (std::min({npix, p0 + segment_pixels, stop_at}) - p0) * planes;
+    }
+    P.walked += (uint64_t)planes * segs.size();
+    return FELICS_OK;
+}
 // n requests on streams of W x H pixels, `planes` planes, segments of segment_pixels; sample_bytes: of an output sample.
 // out_offsets (may be null): where crop r starts.  0, FELICS_E_UNSUPPORTED past 2^31 - 1 items (one block per item, 32-bit item
 // numbers) or FELICS_E_IO (no memory).
@@ -280,34 +316,9 @@ inline int region_plan(uint32_t W, uint32_t H, uint32_t segment_pixels, uint32_t
     try {
         P.rows.reserve(n);
         for (size_t r = 0; r < n; r++) {
-            const felics_region &g = regions[r];
-            segs.clear();
-            uint64_t stop_at = 0;
-            if (!region_empty(g)) {
-                uint32_t first, last;
-                region_span(W, segment_pixels, g, first, last);
-                for (uint32_t j = first; j <= last; j++)
-                    if (region_needs(W, npix, segment_pixels, g, j)) segs.push_back(j);
-                stop_at = region_last(W, g);
-            }
-            const uint64_t cnt = segs.empty() ? 1 : (uint64_t)planes * segs.size();
-            if (P.items.size() + cnt > 0x7FFFFFFFull) return FELICS_E_UNSUPPORTED;
-            const uint64_t cpix = (uint64_t)g.w * g.h;
-            P.rows.push_back(RegionRow{g.stream, g.x, g.y, g.w, g.h, (uint32_t)P.items.size(), (uint32_t)cnt, 0, out_at, P.plane_samples});
             if (out_offsets) out_offsets[r] = out_at;
-            out_at += cpix * planes * sample_bytes;
-            if (planes == 3) {
-                P.plane_samples += cpix * 3;
-                P.max_crop = std::max(P.max_crop, cpix);
-            }
-            if (segs.empty()) P.items.push_back(RegionItem{(uint32_t)r, 0, REGION_HEADER_ONLY});
-            for (uint32_t c = 0; c < planes && !segs.empty(); c++)
-                for (const uint32_t j : segs) P.items.push_back(RegionItem{(uint32_t)r, c, j});
-            for (const uint32_t j : segs) {
-                const uint64_t p0 = (uint64_t)j * segment_pixels;
-                P.pixels_walked += (std::min({npix, p0 + segment_pixels, stop_at}) - p0) * planes;
-            }
-            P.walked += (uint64_t)planes * segs.size();
+            const int rc = region_plan_add(W, H, segment_pixels, planes, sample_bytes, regions[r], (uint32_t)r, true, out_at, segs, P);
+            if (rc) return rc;
         }
     } catch (const std::bad_alloc &) {
         return FELICS_E_IO;

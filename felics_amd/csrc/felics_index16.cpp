@@ -145,6 +145,90 @@ int walk_segments16(const uint8_t *in, size_t len, const uint8_t *index, size_t 
     return FELICS_OK;
 }
 
+// The needed segments of the non-empty region r (inside the image) of a 16-bit stream whose two headers passed their checks, in
+// (plane, segment) order, each from its checkpoint alone -- the table is exactly the checkpoint's rows --, walked up to
+// min(segment end, the pixel behind the region's last one): the walk of felics_decompress_region_indexed16 and
+// felics_decompress_region_indexed16_view.  ch[c]: plane c of the crop (w * h samples); put(c, i, j, v): window sample (i, j) of
+// plane c as it is decoded.  0 or the first failing segment's code.
+template <typename Put>
+int walk_region16(const uint8_t *in, size_t len, const uint8_t *index, size_t index_len, const Index16Layout &L, const felics_header &hdr,
+                  const felics_region &r, std::vector<int32_t> (&ch)[3], Put put) {
+    const uint32_t W = hdr.width, H = hdr.height, color = hdr.color_type;
+    const size_t npix = (size_t)W * H, cpix = (size_t)r.w * r.h;
+    const uint32_t seg = idx_rd32(index + IDX_SEGPIX);
+    const uint64_t last = region_last(W, r);
+    uint32_t jfirst, jlast;
+    region_span(W, seg, r, jfirst, jlast);
+    std::vector<int32_t> buf;
+    int rc;
+    try {
+        Estimator est(OPT16);
+        std::vector<uint32_t> touched(OPT16.max_context + 1, 0u);  // [ctx] != 0: the segment had an event of that context
+        for (uint32_t c = 0; c < L.planes; c++) {
+            ch[c].assign(cpix, 0);
+            for (uint32_t j = jfirst; j <= jlast; j++) {
+                if (!region_needs(W, npix, seg, r, j)) continue;
+                uint64_t start, end, rows_off;
+                uint32_t n_rows;
+                if (index16_segment_bounds(index, L, c, j, len, index_len, start, end, rows_off, n_rows)) return FELICS_E_INVALID_INDEX;
+                // the table: exactly the checkpoint's rows (it is all zero here: what a segment loaded or touched is cleared behind it)
+                const uint8_t *rows = index + rows_off;
+                int64_t prev = -1;
+                for (uint32_t k = 0; k < n_rows; k++) {
+                    const uint8_t *row = rows + (uint64_t)k * INDEX16_ROW_BYTES;
+                    const uint32_t ctx = idx_rd32(row + 4 * INDEX16_ROW_CTX);
+                    if (ctx >= index16_contexts(color, c) || (int64_t)ctx <= prev) return FELICS_E_INVALID_INDEX;
+                    prev = ctx;
+                    for (unsigned i = 0; i < 15; i++) est.row(ctx)[i] = idx_rd32(row + 4 * i);
+                }
+                const size_t s0 = (size_t)j * seg, s1 = std::min(npix, s0 + seg), stop = (size_t)std::min<uint64_t>(s1, last);
+                // The walk's samples live in `buf`: whole rows from two rows above s0's on (the window's reach), up to `stop`.  The rows
+                // dropped in front are an even count when s0's row is >= 2, none otherwise: the neighbour rule sees the same cases.
+                const size_t y0 = s0 / W, base = y0 >= 2 ? (y0 - 2) * W : 0;
+                buf.assign(stop - base, 0);
+                int32_t *out = buf.data();
+                const uint8_t *win = index + L.win_base + ((uint64_t)c * L.K + j) * L.win_bytes;
+                for (uint64_t s = 0; s < 2ull * W; s++) {  // samples s0 - 2 W .. s0 - 1; those in front of the plane are never looked at
+                    if (s0 + s < 2ull * W) continue;
+                    const int32_t v = color ? (int32_t)idx_rd32(win + 4 * s) : (int32_t)idx_rd16(win + 2 * s);
+                    if (!in_plane_range(v, color, c)) return FELICS_E_INVALID_INDEX;
+                    out[s0 + s - 2ull * W - base] = v;
+                }
+                BitReader br(in, len, start);
+                if (j == 0) {
+                    const int32_t p0 = (int32_t)br.bits(32), p1 = (int32_t)br.bits(32);
+                    if (br.failed()) return FELICS_E_IO;
+                    out[0] = p0;
+                    if (stop > 1) out[1] = p1;
+                }
+                rc = decode_span(br, W, OPT16, est, out, std::max<size_t>(s0, 2) - base, std::max<size_t>(stop, 2) - base, touched.data());
+                if (rc) return rc;
+                for (size_t i = s0; i < stop; i++) {
+                    const int32_t v = out[i - base];
+                    if (!in_plane_range(v, color, c)) return FELICS_E_INVALID_VALUE;
+                    const size_t yy = i / W, xx = i - yy * W;
+                    if (xx >= r.x && xx < (size_t)r.x + r.w && yy >= r.y) {
+                        ch[c][(yy - r.y) * r.w + (xx - r.x)] = v;
+                        put(c, (uint32_t)(xx - r.x), (uint32_t)(yy - r.y), v);
+                    }
+                }
+                // the end check where the walk reached the segment's end; a walk that stops early has no bit position to stand on
+                if (stop == s1 && br.pos() != end) return FELICS_E_INVALID_INDEX;
+                for (uint32_t k = 0; k < n_rows; k++)
+                    memset(est.row(idx_rd32(rows + (uint64_t)k * INDEX16_ROW_BYTES + 4 * INDEX16_ROW_CTX)), 0, 15 * 4);
+                for (uint32_t ctx = 0; ctx <= OPT16.max_context; ctx++)
+                    if (touched[ctx]) {
+                        touched[ctx] = 0;
+                        memset(est.row(ctx), 0, 15 * 4);
+                    }
+            }
+        }
+    } catch (const std::bad_alloc &) {
+        return FELICS_E_INVALID_DIMENSIONS;
+    }
+    return FELICS_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -318,81 +402,64 @@ int felics_decompress_region_indexed_wide(const uint8_t *in, size_t len, const u
     const uint32_t W = hdr.width, H = hdr.height, color = hdr.color_type;
     const felics_region r = *rp;
     if (!region_inside(W, H, r)) return FELICS_E_INVALID_ARGUMENT;
-    const size_t npix = (size_t)W * H, cpix = (size_t)r.w * r.h;
+    const size_t cpix = (size_t)r.w * r.h;
     const unsigned planes = color ? 3 : 1;
     if ((uint64_t)cpix * planes * 2 > pixels_cap) return FELICS_E_BUFFER_TOO_SMALL;
     if (cpix && !pixels) return FELICS_E_INVALID_ARGUMENT;
     Index16Layout L;
     if (index_len < INDEX_HEADER_BYTES || index16_header_check(index, color, W, H, len, index_len, L)) return FELICS_E_INVALID_INDEX;
     if (region_empty(r)) return FELICS_OK;
-    const uint32_t seg = idx_rd32(index + IDX_SEGPIX);
-    const uint64_t last = region_last(W, r);
-    uint32_t jfirst, jlast;
-    region_span(W, seg, r, jfirst, jlast);
-    std::vector<int32_t> ch[3], buf;
+    std::vector<int32_t> ch[3];
+    if ((rc = walk_region16(in, len, index, index_len, L, hdr, r, ch, [](uint32_t, uint32_t, uint32_t, int32_t) {})) != 0) return rc;
+    return store_rgb16(ch, planes, (uint16_t *)pixels);
+}
+
+int felics_decompress_region_indexed_view_wide(const uint8_t *in, size_t len, const uint8_t *index, size_t index_len, const felics_region *rp,
+                                               const felics_view *view, felics_header *hdr_out) {
+    if ((!in && len) || (!index && index_len) || !rp || !view) return FELICS_E_INVALID_ARGUMENT;
+    int rc = view_writable_code(*view);
+    if (rc) return rc;
+    const felics_region r = *rp;
+    if (view->width != r.w || view->height != r.h) return FELICS_E_INVALID_ARGUMENT;
+    // the per-stream codes of felics_decompress_region_views_device_indexed16, in its order; then the region's
+    felics_header hdr;
+    rc = felics_read_header(in, len, &hdr);
+    if (hdr_out) *hdr_out = rc ? felics_header{} : hdr;
+    if (rc) return rc;
+    const uint32_t W = hdr.width, H = hdr.height, color = hdr.color_type;
+    const unsigned planes = color ? 3 : 1;
+    if ((uint64_t)W * H > 0xFFFFFFFFull) return FELICS_E_INVALID_DIMENSIONS;
+    const size_t npix = (size_t)W * H, cpix = (size_t)r.w * r.h;
+    // (k_read_headers' rule: two raw 32-bit samples per plane, then at least one flag bit per pixel, padded to a byte)
+    const uint64_t bits = (uint64_t)planes * (64u + (npix > 2 ? npix - 2 : 0));
+    if (len - FELICS_HEADER_BYTES < (bits + 7) / 8) return FELICS_E_IO;
+    if (hdr.pixel_depth != FELICS_DEPTH_16) return FELICS_E_UNSUPPORTED;
+    if (index16_lds_bytes(W) > INDEX_LDS_LIMIT) return FELICS_E_UNSUPPORTED;  // what the wave form cannot hold, the model refuses too
+    Index16Layout L;
+    if (index_len < INDEX_HEADER_BYTES || index16_header_check(index, color, W, H, len, index_len, L)) return FELICS_E_INVALID_INDEX;
+    if (!region_inside(W, H, r)) return FELICS_E_INVALID_ARGUMENT;
+    if ((int)color != view->color || (int)hdr.pixel_depth != view->depth) return FELICS_E_INVALID_DIMENSIONS;
+    if (region_empty(r)) return FELICS_OK;
+    uint8_t *data = (uint8_t *)const_cast<void *>(view->data);
+    const int64_t rs = view->row_stride, ps = view->pixel_stride, cs = color ? view->channel_stride : 0;
+    auto sample = [&](uint32_t i, uint32_t j, unsigned c) {  // where the kernel's sink (gray) and the strided conversion (RGB) store window sample (i, j)
+        return reinterpret_cast<uint16_t *>(data + view_sample_offset(rs, ps, cs, i, j, c));
+    };
+    std::vector<int32_t> ch[3];
+    // gray: a window sample through the view, as the kernel's sink stores it (an RGB plane waits for the other two)
+    rc = walk_region16(in, len, index, index_len, L, hdr, r, ch, [&](uint32_t, uint32_t i, uint32_t j, int32_t v) {
+        if (!color) *sample(i, j, 0) = (uint16_t)v;
+    });
+    if (rc || !color) return rc;
     try {
-        Estimator est(OPT16);
-        std::vector<uint32_t> touched(OPT16.max_context + 1, 0u);  // [ctx] != 0: the segment had an event of that context
-        for (uint32_t c = 0; c < L.planes; c++) {
-            ch[c].assign(cpix, 0);
-            for (uint32_t j = jfirst; j <= jlast; j++) {
-                if (!region_needs(W, npix, seg, r, j)) continue;
-                uint64_t start, end, rows_off;
-                uint32_t n_rows;
-                if (index16_segment_bounds(index, L, c, j, len, index_len, start, end, rows_off, n_rows)) return FELICS_E_INVALID_INDEX;
-                // the table: exactly the checkpoint's rows (it is all zero here: what a segment loaded or touched is cleared behind it)
-                const uint8_t *rows = index + rows_off;
-                int64_t prev = -1;
-                for (uint32_t k = 0; k < n_rows; k++) {
-                    const uint8_t *row = rows + (uint64_t)k * INDEX16_ROW_BYTES;
-                    const uint32_t ctx = idx_rd32(row + 4 * INDEX16_ROW_CTX);
-                    if (ctx >= index16_contexts(color, c) || (int64_t)ctx <= prev) return FELICS_E_INVALID_INDEX;
-                    prev = ctx;
-                    for (unsigned i = 0; i < 15; i++) est.row(ctx)[i] = idx_rd32(row + 4 * i);
-                }
-                const size_t s0 = (size_t)j * seg, s1 = std::min(npix, s0 + seg), stop = (size_t)std::min<uint64_t>(s1, last);
-                // The walk's samples live in `buf`: whole rows from two rows above s0's on (the window's reach), up to `stop`.  The rows
-                // dropped in front are an even count when s0's row is >= 2, none otherwise: the neighbour rule sees the same cases.
-                const size_t y0 = s0 / W, base = y0 >= 2 ? (y0 - 2) * W : 0;
-                buf.assign(stop - base, 0);
-                int32_t *out = buf.data();
-                const uint8_t *win = index + L.win_base + ((uint64_t)c * L.K + j) * L.win_bytes;
-                for (uint64_t s = 0; s < 2ull * W; s++) {  // samples s0 - 2 W .. s0 - 1; those in front of the plane are never looked at
-                    if (s0 + s < 2ull * W) continue;
-                    const int32_t v = color ? (int32_t)idx_rd32(win + 4 * s) : (int32_t)idx_rd16(win + 2 * s);
-                    if (!in_plane_range(v, color, c)) return FELICS_E_INVALID_INDEX;
-                    out[s0 + s - 2ull * W - base] = v;
-                }
-                BitReader br(in, len, start);
-                if (j == 0) {
-                    const int32_t p0 = (int32_t)br.bits(32), p1 = (int32_t)br.bits(32);
-                    if (br.failed()) return FELICS_E_IO;
-                    out[0] = p0;
-                    if (stop > 1) out[1] = p1;
-                }
-                rc = decode_span(br, W, OPT16, est, out, std::max<size_t>(s0, 2) - base, std::max<size_t>(stop, 2) - base, touched.data());
-                if (rc) return rc;
-                for (size_t i = s0; i < stop; i++) {
-                    const int32_t v = out[i - base];
-                    if (!in_plane_range(v, color, c)) return FELICS_E_INVALID_VALUE;
-                    const size_t yy = i / W, xx = i - yy * W;
-                    if (xx >= r.x && xx < (size_t)r.x + r.w && yy >= r.y) ch[c][(yy - r.y) * r.w + (xx - r.x)] = v;
-                }
-                // the end check where the walk reached the segment's end; a walk that stops early has no bit position to stand on
-                if (stop == s1 && br.pos() != end) return FELICS_E_INVALID_INDEX;
-                for (uint32_t k = 0; k < n_rows; k++)
-                    memset(est.row(idx_rd32(rows + (uint64_t)k * INDEX16_ROW_BYTES + 4 * INDEX16_ROW_CTX)), 0, 15 * 4);
-                for (uint32_t ctx = 0; ctx <= OPT16.max_context; ctx++)
-                    if (touched[ctx]) {
-                        touched[ctx] = 0;
-                        memset(est.row(ctx), 0, 15 * 4);
-                    }
-            }
-        }
+        std::vector<uint16_t> rgb(cpix * 3);  // (converted and range-checked first: a region that fails here leaves the view as it was)
+        if ((rc = store_rgb16(ch, planes, rgb.data())) != 0) return rc;
+        for (size_t i = 0; i < cpix; i++)
+            for (unsigned c = 0; c < 3; c++) *sample((uint32_t)(i % r.w), (uint32_t)(i / r.w), c) = rgb[i * 3 + c];
     } catch (const std::bad_alloc &) {
         return FELICS_E_INVALID_DIMENSIONS;
     }
-    return store_rgb16(ch, planes, (uint16_t *)pixels);
+    return FELICS_OK;
 }
 
 int felics_decompress_indexed_view_wide(const uint8_t *in, size_t len, const uint8_t *index, size_t index_len, const felics_view *view,

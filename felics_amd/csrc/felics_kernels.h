@@ -463,6 +463,32 @@ hipError_t launch_decode16_regions(hipStream_t s, const uint8_t *streams, const 
 hipError_t launch_decode16_seg_views(hipStream_t s, const uint8_t *streams, const uint64_t *offsets, const uint64_t *lens, const uint8_t *index,
                                      const uint64_t *idx_lens, const IndexViewRow *rows, const IndexViewItem *items, uint32_t nitems, uint32_t lds,
                                      int32_t *planes, uint32_t *table, uint32_t epoch, int *item_status, unsigned long long *rows_loaded);
+// Regions of indexed streams of ANY shapes straight into views (felics_decompress_region_views_device_indexed and its 16-bit form,
+// felics.h "Restart index: regions into views and mixed shapes"): one wave per work item = (region, plane, needed segment),
+// k_decode8_region_views / k_decode16_region_views -- the region walk (it stops behind the region's last pixel) with a sink that writes
+// a gray sample of the window through the region's view, one aligned store at view_sample_offset(.., col - x, y - y0, 0), and an RGB one
+// to plane c of the region's crop-sized planes at planes + plane_off (converted through the view by the strided conversion:
+// launch_seg_views_finish with a DecodeRow of W = w, H = h per region).  The tables: a RegionViewStream per stream of the call that
+// passed the host's checks (what the host read out of its headers; the walk checks both again), a RegionRow per region (stream: the
+// stream's number, which names its RegionViewStream and its offsets / lens; item0 / nitems for k_seg_status; out_off unused) with its
+// ViewRow beside it, RegionItem as in the same-shape region calls (no REGION_HEADER_ONLY items: the header checks are final on the
+// host, an empty region has no item).
+struct RegionViewStream {
+    uint32_t W, H, color;
+    uint32_t segment_pixels, K;
+    uint32_t pad;
+    uint64_t index_off;  // byte offset of its index in `index` (index + index_off a multiple of 16; 16-bit: of 64)
+};
+// One launch: `nitems` < 2^31 consecutive items of the work list whose streams' rows all fit `lds` bytes of dynamic LDS; item_status: a
+// word per item of the launch.  The 16-bit form: wave b on table b of `table`, one fresh epoch per launch, the index's length from
+// idx_lens[stream], *rows_loaded += the state rows copied (as launch_decode16_seg_views).
+hipError_t launch_decode8_region_views(hipStream_t s, const uint8_t *streams, const uint64_t *offsets, const uint64_t *lens, const uint8_t *index,
+                                       const RegionViewStream *srows, const RegionRow *regions, const ViewRow *views, const RegionItem *items,
+                                       uint32_t nitems, uint32_t lds, int16_t *planes, int *item_status);
+hipError_t launch_decode16_region_views(hipStream_t s, const uint8_t *streams, const uint64_t *offsets, const uint64_t *lens, const uint8_t *index,
+                                        const uint64_t *idx_lens, const RegionViewStream *srows, const RegionRow *regions, const ViewRow *views,
+                                        const RegionItem *items, uint32_t nitems, uint32_t lds, int32_t *planes, uint32_t *table, uint32_t epoch,
+                                        int *item_status, unsigned long long *rows_loaded);
 // The same for 16-bit streams, gray or RGB (k_decode16_lanes): 64 streams per wave, lane = stream; needs W >= 8 and a table of
 // decode16_lanes_table_bytes(n, W, H, color) bytes = n * planes * dec16l_rows(W * H, planes) * 64 (felics_lanetable.h: sized by the
 // pixel count, 512 KB per plane of a 64 x 64 stream, the wave form's 8.4 MB from 32 771 pixels on), zero-initialised ONCE: rows carry

@@ -12,6 +12,10 @@
 //     admissible view (a pitch, pixel stride 1 or 2, a flipped row or channel axis, interleaved or planar) whose target buffer is
 //     EXACTLY the size of the view's hull, so a store outside it is the sanitizer's to report: on a good pair every sample must be
 //     felics_decompress's and every other byte of the hull untouched; on a mutated or foreign pair any code, no crash.
+//   * felics_decompress_region_indexed_view (and, in the 16-bit mode, felics_decompress_region_indexed16_view), the host models of
+//     the region views calls, on all of these pairs as well: random regions into random admissible views of the window's size whose
+//     hull lies between guard bytes (region_view_leg below).  On a good pair the samples must equal the dense region call's, every
+//     other byte of the hull and both guards must be untouched; on a mutated or foreign pair any code, guards intact, no crash.
 // In both modes every stream with a valid header also has the device region calls' plan made for its shape (felics_index.h:
 // region_plan) and checked against felics_region_segments: plan_leg below.
 // `index_fuzz --index16 DIR` runs the 16-bit index's host functions instead (felics_index16.cpp): felics_index16_build at the same
@@ -112,6 +116,53 @@ static size_t plan_leg(const felics_header &h, uint32_t seg, uint32_t sample_byt
     return regs.size();
 }
 
+// The host models of the region views calls (S = 1: felics_decompress_region_indexed_view, S = 2: felics_decompress_region_indexed16_view)
+// on one pair: window r of the image of header h into a random admissible view of r's size (a pitch, every sample or every other, a
+// flipped row or channel axis, interleaved or planar) whose hull lies between GUARD bytes of 0xA5 on either side.  Whatever the pair:
+// both guards intact.  `good`: the model and the dense region call (its code rc_dense, its crop `crop`) must both have succeeded, every
+// sample must be the dense crop's and every other byte of the hull untouched.  False where any of that does not hold.
+template <int S, typename Next>
+static bool region_view_leg(const std::vector<uint8_t> &stream, const uint8_t *index, size_t index_len, const felics_header &h, const felics_region &r,
+                            const uint8_t *crop, int rc_dense, bool good, Next next) {
+    constexpr size_t GUARD = 64;
+    static std::vector<uint8_t> target, expect;
+    const int64_t W = r.w, H = r.h, C = h.color_type ? 3 : 1;
+    if ((uint64_t)W * H * C * S * 4 > (32u << 20)) return true;  // (targets are this driver's to allocate)
+    felics_view v = {nullptr, r.w, r.h, h.color_type, S == 2 ? FELICS_DEPTH_16 : FELICS_DEPTH_8, 0, 0, 0};
+    const int64_t ps = S * (1 + (int64_t)(next() % 2)), pad = S * (int64_t)(next() % 8);
+    const bool planar = C == 3 && next() % 2, flip_rows = next() % 2, flip_ch = C == 3 && next() % 2;
+    if (C == 1 || planar) {
+        v.pixel_stride = ps;
+        v.row_stride = W * ps + pad;
+        v.channel_stride = C == 3 ? H * v.row_stride + pad : 0;
+    } else {
+        v.channel_stride = S;
+        v.pixel_stride = (3 + (int64_t)(next() % 2)) * ps;  // RGB or RGBA pixels, every one or every other
+        v.row_stride = W * v.pixel_stride + pad;
+    }
+    if (flip_rows) v.row_stride = -v.row_stride;
+    if (flip_ch) v.channel_stride = -v.channel_stride;
+    int64_t lo = 0, hi = W && H ? S : 0;
+    const int64_t spans[3] = {(H - 1) * v.row_stride, (W - 1) * v.pixel_stride, (C - 1) * v.channel_stride};
+    for (int d = 0; d < 3 && W && H; d++) (spans[d] < 0 ? lo : hi) += spans[d];
+    target.assign(GUARD + (size_t)(hi - lo) + GUARD, 0xA5);
+    uint8_t *hull = target.data() + GUARD;
+    if (W && H) v.data = hull - lo;
+    felics_header hv;
+    const int rc = S == 2 ? felics_decompress_region_indexed16_view(stream.data(), stream.size(), index, index_len, &r, &v, &hv)
+                          : felics_decompress_region_indexed_view(stream.data(), stream.size(), index, index_len, &r, &v, &hv);
+    for (size_t i = 0; i < GUARD; i++)
+        if (target[i] != 0xA5 || target[target.size() - 1 - i] != 0xA5) return false;
+    if (!good) return true;
+    if (rc != FELICS_OK || rc_dense != FELICS_OK) return false;
+    expect.assign(target.size(), 0xA5);
+    for (int64_t y = 0; y < H; y++)
+        for (int64_t x = 0; x < W; x++)
+            for (int64_t c = 0; c < C; c++)
+                memcpy(&expect[GUARD + (size_t)(y * v.row_stride + x * v.pixel_stride + c * v.channel_stride - lo)], &crop[(size_t)((y * W + x) * C + c) * S], S);
+    return target == expect;
+}
+
 // the --index16 mode
 static int fuzz16(const char *dir) {
     {  // argument checks
@@ -122,6 +173,11 @@ static int fuzz16(const char *dir) {
         bad += felics_index16_build(b, sizeof b, 4096, b, sizeof b, nullptr) != FELICS_E_INVALID_ARGUMENT;
         bad += felics_decompress_indexed16(nullptr, 5, b, sizeof b, b, sizeof b, nullptr) != FELICS_E_INVALID_ARGUMENT;
         bad += felics_decompress_indexed16(b, sizeof b, nullptr, 5, b, sizeof b, nullptr) != FELICS_E_INVALID_ARGUMENT;
+        const felics_region one{0, 0, 0, 1, 1};
+        const felics_view px1{b, 1, 1, FELICS_COLOR_GRAY, FELICS_DEPTH_16, 2, 2, 0};
+        bad += felics_decompress_region_indexed16_view(b, sizeof b, b, sizeof b, nullptr, &px1, nullptr) != FELICS_E_INVALID_ARGUMENT;
+        bad += felics_decompress_region_indexed16_view(b, sizeof b, b, sizeof b, &one, nullptr, nullptr) != FELICS_E_INVALID_ARGUMENT;
+        bad += felics_decompress_region_indexed16_view(nullptr, 5, b, sizeof b, &one, &px1, nullptr) != FELICS_E_INVALID_ARGUMENT;
         bad += felics_index16_size_max(1, 1, 0, 4095) != 0 || felics_index16_size_max(1, 1, 2, 4096) != 0 || felics_index16_size_max(1, 1, 0, 4096) != 192;  // (header, one entry, one window)
         bad += felics_index16_size_max(0xFFFFFFFFu, 0xFFFFFFFFu, 1, 4096) != 0 || felics_index16_size_max(0, 5, 1, 4096) != 64;
         if (bad) {
@@ -167,6 +223,8 @@ static int fuzz16(const char *dir) {
             crop.assign(bytes, 0xA5);
             felics_header hr;
             const int rc = felics_decompress_region_indexed16(buf.data(), buf.size(), index_bytes, index_len, &r, crop.data(), bytes, &hr);
+            // the same window into a view (a mutated pair: the seeded window only -- every call clears a 7.9 MB table)
+            if ((good || k == 1) && !region_view_leg<2>(buf, index_bytes, index_len, h, r, crop.data(), rc, good, next)) return false;
             if (!good) continue;
             if (rc != FELICS_OK) return false;
             if (k == 0 && memcmp(crop.data(), px.data(), bytes) != 0) return false;  // (px: felics_decompress_indexed16's frame)
@@ -263,7 +321,7 @@ static int fuzz16(const char *dir) {
                 return 1;
             }
             if (!regions16_on(index.data(), ilen, h, true)) {
-                fprintf(stderr, "%s: a region of a good pair failed or differs from felics_decompress_indexed16's window\n", n.c_str());
+                fprintf(stderr, "%s: a region of a good pair failed or differs from felics_decompress_indexed16's window, or its view differs from the crop\n", n.c_str());
                 return 1;
             }
             if (!view16_on(index.data(), ilen, h, true) || !view16_on(index.data(), ilen, h, true)) {
@@ -287,7 +345,10 @@ static int fuzz16(const char *dir) {
                 }
                 mutations++;
                 if (felics_decompress_indexed16(buf.data(), buf.size(), bad.data(), bad.size(), px.data(), px.size(), &h2) == FELICS_OK) mut_accepted++;
-                regions16_on(bad.data(), bad.size(), h, false);
+                if (!regions16_on(bad.data(), bad.size(), h, false)) {
+                    fprintf(stderr, "%s: a region view of a mutated index wrote into its guard bytes\n", n.c_str());
+                    return 1;
+                }
                 if (m % 2 == 0) view16_on(bad.data(), bad.size(), h, false);  // (every call clears a 7.9 MB table: every other mutation)
                 if (m % 5 == 0) {  // and cut short
                     const size_t cut = (size_t)(next() % ilen);
@@ -335,6 +396,11 @@ int main(int argc, char **argv) {
         bad += felics_decompress_indexed_view(b, sizeof b, b, sizeof b, nullptr, nullptr) != FELICS_E_INVALID_ARGUMENT;
         bad += felics_decompress_indexed_view(nullptr, 5, b, sizeof b, &ok, nullptr) != FELICS_E_INVALID_ARGUMENT;
         bad += felics_decompress_indexed_view(b, sizeof b, b, sizeof b, &alias, nullptr) != FELICS_E_INVALID_ARGUMENT;  // rows that share bytes
+        const felics_view win{b, 2, 2, FELICS_COLOR_GRAY, FELICS_DEPTH_8, 8, 1, 0};
+        bad += felics_decompress_region_indexed_view(b, sizeof b, b, sizeof b, nullptr, &win, nullptr) != FELICS_E_INVALID_ARGUMENT;
+        bad += felics_decompress_region_indexed_view(b, sizeof b, b, sizeof b, &in, nullptr, nullptr) != FELICS_E_INVALID_ARGUMENT;
+        bad += felics_decompress_region_indexed_view(nullptr, 5, b, sizeof b, &in, &win, nullptr) != FELICS_E_INVALID_ARGUMENT;
+        bad += felics_decompress_region_indexed_view(b, sizeof b, b, sizeof b, &in, &ok, nullptr) != FELICS_E_INVALID_ARGUMENT;  // an 8 x 8 view of a 2 x 2 window
         if (bad) {
             fprintf(stderr, "argument checks: %d unexpected results\n", bad);
             return 1;
@@ -381,6 +447,7 @@ int main(int argc, char **argv) {
             const int rc = felics_decompress_region_indexed(buf.data(), buf.size(), index_bytes.data(), index_len, &r, crop.data(), crop.size() - 1, &hr);
             regions++;
             if (crop.back() != 0xA5) return false;
+            if (!region_view_leg<1>(buf, index_bytes.data(), index_len, h, r, crop.data(), rc, good, next)) return false;  // the same window into a view
             if (!good) continue;
             if (rc != FELICS_OK) return false;
             for (uint32_t yy = 0; yy < r.h; yy++)

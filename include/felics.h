@@ -601,8 +601,9 @@ int felics_get_decode_view_stats(const felics_ctx *ctx, felics_decode_view_stats
  *                 a stream, an index or a view is touched in this call, the two header kernels included.
  * The stream headers and the first 64 bytes of every index are read by two kernels and come back in one synchronise; no header is
  * fetched with a blocking copy.  The call is blocking: the views are complete when it returns.  It creates no HIP stream.
- * NOT HERE: a lane-per-segment form, regions into views, a queued form, streams without an index in the same call; 16-bit streams
+ * NOT HERE: a lane-per-segment form, a queued form, streams without an index in the same call; 16-bit streams
  * (they have a call of their own: "Restart index: 16-bit streams into views and mixed shapes", below).
+ * (Regions into views: "Restart index: regions into views and mixed shapes", below.)
  * (The encode side of this call is felics_compress_views_device_indexed, below.) */
 int felics_decompress_views_device_indexed(felics_ctx *ctx, size_t n, const void *d_streams, const uint64_t *offsets, const uint64_t *lens,
                                            const void *d_index, const uint64_t *idx_offsets, const uint64_t *idx_lens,
@@ -832,7 +833,8 @@ static inline int felics_get_index16_stats(const felics_ctx *ctx, felics_index16
  * NAMES: exported as felics_decompress_region_indexed_wide, felics_decompress_regions_device_indexed_wide and
  * felics_get_region_wide_stats; the aliases felics_decompress_region_indexed16, felics_decompress_regions_device_indexed16 and
  * felics_get_region16_stats follow the declarations.
- * NOT HERE: regions into views, mixed shapes, a lane form, a queued form; dfelics --region for 16-bit files. */
+ * NOT HERE: a lane form, a queued form; dfelics --region for 16-bit files.  (Regions into views and regions of mixed shapes:
+ * "Restart index: regions into views and mixed shapes", below.) */
 
 /* Host only: the w x h window *r of a 16-bit stream through its version-2 index, as dense uint16 samples (w * h * C of them;
  * pixels_cap in bytes).  The host model of k_decode16_region: every needed segment, in (plane, segment) order, from its checkpoint
@@ -928,7 +930,8 @@ static inline int felics_get_region16_stats(const felics_ctx *ctx, felics_region
  * NAMES: exported as felics_decompress_views_device_indexed_wide, felics_decompress_indexed_view_wide and
  * felics_get_index_view_wide_stats; the aliases felics_decompress_views_device_indexed16, felics_decompress_indexed16_view and
  * felics_get_index16_view_stats follow the declarations.
- * NOT HERE: regions into views, a lane form, a queued form, 8-bit and 16-bit streams in one call, cfelics / dfelics flags. */
+ * NOT HERE: a lane form, a queued form, 8-bit and 16-bit streams in one call, cfelics / dfelics flags.  (Regions into views:
+ * "Restart index: regions into views and mixed shapes", below.) */
 int felics_decompress_views_device_indexed_wide(felics_ctx *ctx, size_t n, const void *d_streams, const uint64_t *offsets, const uint64_t *lens,
                                                 const void *d_index, const uint64_t *idx_offsets, const uint64_t *idx_lens,
                                                 const felics_view *views, void *ready_event, felics_header *hdrs /* optional */, int *status);
@@ -970,6 +973,124 @@ static inline int felics_decompress_indexed16_view(const uint8_t *in, size_t len
 }
 static inline int felics_get_index16_view_stats(const felics_ctx *ctx, felics_index16_view_stats *out, size_t out_size) {
     return felics_get_index_view_wide_stats(ctx, out, out_size);
+}
+
+/* ---- Restart index: regions into views and mixed shapes ----
+ * The region calls and the views calls in one: a window of every stream, the streams of any shapes, decoded straight into views.
+ * Stream s (at d_streams + offsets[s], lens[s] bytes) is any 8-bit stream (_wide: any 16-bit stream) with its own shape, colour,
+ * segment_pixels and K; its index is addressed as in felics_decompress_views_device_indexed (_wide: _indexed16): d_index +
+ * idx_offsets[s], idx_lens[s] bytes, the address a multiple of 16 (_wide: of 64).  Region r is the window regions[r].{x, y, w, h} of
+ * stream regions[r].stream; several regions may name one stream, a stream may go unnamed.  The window is decoded straight into
+ * views[r]: window sample (i, j, c), that is image pixel (x + i, y + j), lands at data + j * row_stride + i * pixel_stride +
+ * c * channel_stride.  Every sample is the one felics_decompress yields at its place.
+ * One wave per (region, plane, needed segment): k_decode8_region_views / k_decode16_region_views, the walk of the region kernels with
+ * a sink that writes through the view.  The needed segments are those felics_region_segments names for the stream's own W, H and
+ * segment_pixels; each is walked up to `stop` as "Restart index: regions" defines it.
+ * WHAT THE CHECKS COVER is exactly what "Restart index: regions" says: the checks of "Restart index" (_wide: of "Restart index: 16-bit
+ * streams") for the NEEDED segments only, with no end check where a walk stops early.  A segment no region needs is not looked at: a
+ * forged entry there goes unnoticed, as in the region calls.
+ * offsets / lens / idx_offsets / idx_lens / regions / views / hdrs / status are HOST arrays; status has n_regions words, hdrs
+ * (optional) n_streams headers.  status[] is filled on every return and the first non-zero status in region order is returned.
+ *   Checked before anything is launched (the first error in region order is returned and put in every status[r]): NULL pointers;
+ *   n_regions > 2^31 - 1, or n_streams == 0 with regions (FELICS_E_INVALID_ARGUMENT); regions[r].stream >= n_streams
+ *   (FELICS_E_INVALID_ARGUMENT); views[r] refused by felics_view_writable (its code); views[r].width != regions[r].w or
+ *   views[r].height != regions[r].h (FELICS_E_INVALID_ARGUMENT); then the index alignment rule for every stream
+ *   (FELICS_E_INVALID_ARGUMENT).  Refused while a ticket is outstanding (FELICS_E_INVALID_ARGUMENT); FELICS_E_HIP on a failed
+ *   context; n_regions == 0 returns FELICS_OK.
+ *   Per stream, after the headers are read (the stream headers and the first 64 bytes of every index come back from the two header
+ *   kernels of the views calls in one synchronise): the per-stream codes of felics_decompress_views_device_indexed (_wide: of
+ *   _indexed16) in that call's order, except that a header is compared with a view per region (below).  hdrs[s] is filled as there.
+ *   Per region, in this order: its stream's code; FELICS_E_INVALID_ARGUMENT for a window outside that stream's image (x + w and y + h
+ *   as 64-bit sums); FELICS_E_INVALID_DIMENSIONS if views[r]'s colour or depth differs from the stream's; the code of its first
+ *   failing item in (plane, segment) order; FELICS_E_INVALID_VALUE from the RGB conversion.
+ *   A region that gets a code before the launch writes nothing.  A region that fails while decoding may leave any of its own view's
+ *   samples written or unwritten, and nothing else; an RGB region with a failing item is not converted.  One bad stream or region
+ *   does not fail the others.  An empty region (w = 0 or h = 0, with a zero-sized view) gets its stream's header and index-header
+ *   code, then the two per-region checks above like any other region (an empty window must still lie inside the image, its view
+ *   must still have the stream's colour and depth), and launches no walk.  FELICS_E_UNSUPPORTED in every status for 2^31 work items or more, once the headers are known.
+ *   The write guarantee is the views calls', word for word: SAMPLE BYTES ONLY.  Gray is one aligned store of one sample through all
+ *   strides, so NO gray view is staged, whatever its layout.  RGB goes through CROP-SIZED Y / Co / Cg planes in the context's plane
+ *   scratch (6 bytes per crop pixel; _wide: 12) and the strided conversion of the unindexed call writes the view.
+ *   ready_event: as in the views calls.  Nothing of a stream, an index or a view is touched before it, the header kernels included.
+ *   The call is blocking and creates no HIP stream.  The views of one call share no sample with each other or with the streams: the
+ *   caller's contract.
+ *   Passes: consecutive regions whose RGB planes fit a quarter of the free device memory make a pass, a single larger region is a
+ *   pass of its own; FELICS_TEST_INDEX_VIEWS_PASS=<bytes> caps it.  Within a pass the items run in the LDS classes of the views
+ *   calls, a launch per class.  _wide: a launch holds at most as many items as there are estimator tables, with a fresh epoch per
+ *   launch (FELICS_TEST_INDEX16_PASS=k caps it); a table cut may fall inside a region or a plane.
+ * NAMES: the 16-bit forms are exported as felics_decompress_region_views_device_indexed_wide,
+ * felics_decompress_region_indexed_view_wide and felics_get_region_view_wide_stats; the aliases
+ * felics_decompress_region_views_device_indexed16, felics_decompress_region_indexed16_view and felics_get_region16_view_stats follow
+ * the declarations.
+ * NOT HERE: a lane form, a queued form, regions of streams without an index, 8-bit and 16-bit streams in one call, dfelics flags. */
+int felics_decompress_region_views_device_indexed(felics_ctx *ctx, size_t n_streams, const void *d_streams, const uint64_t *offsets,
+                                                  const uint64_t *lens, const void *d_index, const uint64_t *idx_offsets,
+                                                  const uint64_t *idx_lens, size_t n_regions, const felics_region *regions,
+                                                  const felics_view *views, void *ready_event, felics_header *hdrs /* optional, n_streams */,
+                                                  int *status /* n_regions */);
+int felics_decompress_region_views_device_indexed_wide(felics_ctx *ctx, size_t n_streams, const void *d_streams, const uint64_t *offsets,
+                                                       const uint64_t *lens, const void *d_index, const uint64_t *idx_offsets,
+                                                       const uint64_t *idx_lens, size_t n_regions, const felics_region *regions,
+                                                       const felics_view *views, void *ready_event,
+                                                       felics_header *hdrs /* optional, n_streams */, int *status /* n_regions */);
+
+/* Host only, the models of k_decode8_region_views and k_decode16_region_views: the checks of the device call for one stream and one
+ * region in its order -- the view writable (its code), the view w x h (FELICS_E_INVALID_ARGUMENT), the per-stream codes, the window
+ * inside the image (FELICS_E_INVALID_ARGUMENT), the view's colour and depth the stream's (FELICS_E_INVALID_DIMENSIONS), all before a
+ * byte is written --, then the needed segments from their checkpoints alone (the walk of felics_decompress_region_indexed /
+ * _indexed16), written through the view's strides into HOST memory by the offset function the kernel's sink compiles (sample bytes
+ * only).  A failing RGB region leaves the view untouched; a failing gray one may have written samples of its own window.
+ * r->stream is ignored.  hdr (optional) gets the stream's header where felics_read_header accepts it. */
+int felics_decompress_region_indexed_view(const uint8_t *in, size_t len, const uint8_t *index, size_t index_len, const felics_region *r,
+                                          const felics_view *view, felics_header *hdr);
+int felics_decompress_region_indexed_view_wide(const uint8_t *in, size_t len, const uint8_t *index, size_t index_len, const felics_region *r,
+                                               const felics_view *view, felics_header *hdr);
+
+/* What a context's felics_decompress_region_views_device_indexed calls did so far (cumulative; calls that passed the checks made
+ * before a launch).  The other region and view counters do not count these calls. */
+typedef struct felics_region_view_stats {
+    uint64_t regions;           /* regions handed in */
+    uint64_t undecoded;         /* ... that got a code before a wave was launched for them */
+    uint64_t segments_walked;   /* waves launched: C per needed segment of a decoded region */
+    uint64_t segments_skipped;  /* C * K per decoded region minus the walked */
+    uint64_t pixels_walked;     /* pixels those walks cover */
+    uint64_t launches;          /* k_decode8_region_views launches (one per LDS class of a pass) */
+    uint64_t passes;            /* passes (consecutive regions whose RGB planes share the scratch) */
+    uint64_t plane_bytes;       /* NOT cumulative: the RGB scratch of the last call's largest pass */
+} felics_region_view_stats;
+/* Writes min(out_size, sizeof(felics_region_view_stats)) bytes, never more. */
+int felics_get_region_view_stats(const felics_ctx *ctx, felics_region_view_stats *out, size_t out_size);
+
+/* The same for felics_decompress_region_views_device_indexed16 (launches: per pass and LDS class, cut by the tables). */
+typedef struct felics_region16_view_stats {
+    uint64_t regions;
+    uint64_t undecoded;
+    uint64_t segments_walked;
+    uint64_t segments_skipped;
+    uint64_t pixels_walked;
+    uint64_t launches;
+    uint64_t passes;
+    uint64_t plane_bytes;  /* NOT cumulative */
+    uint64_t rows_loaded;  /* state rows copied into tables */
+    uint64_t table_bytes;  /* NOT cumulative: the estimator tables of the last call */
+} felics_region16_view_stats;
+/* Writes min(out_size, sizeof(felics_region16_view_stats)) bytes, never more. */
+int felics_get_region_view_wide_stats(const felics_ctx *ctx, felics_region16_view_stats *out, size_t out_size);
+
+static inline int felics_decompress_region_views_device_indexed16(felics_ctx *ctx, size_t n_streams, const void *d_streams,
+                                                                  const uint64_t *offsets, const uint64_t *lens, const void *d_index,
+                                                                  const uint64_t *idx_offsets, const uint64_t *idx_lens, size_t n_regions,
+                                                                  const felics_region *regions, const felics_view *views, void *ready_event,
+                                                                  felics_header *hdrs, int *status) {
+    return felics_decompress_region_views_device_indexed_wide(ctx, n_streams, d_streams, offsets, lens, d_index, idx_offsets, idx_lens, n_regions,
+                                                              regions, views, ready_event, hdrs, status);
+}
+static inline int felics_decompress_region_indexed16_view(const uint8_t *in, size_t len, const uint8_t *index, size_t index_len,
+                                                          const felics_region *r, const felics_view *view, felics_header *hdr) {
+    return felics_decompress_region_indexed_view_wide(in, len, index, index_len, r, view, hdr);
+}
+static inline int felics_get_region16_view_stats(const felics_ctx *ctx, felics_region16_view_stats *out, size_t out_size) {
+    return felics_get_region_view_wide_stats(ctx, out, out_size);
 }
 
 /* ---- Restart index: 16-bit streams, written while encoding views and mixed shapes ----
