@@ -27,6 +27,7 @@
 #include "felics_kernels.h"
 #include "felics_codes.h"
 #include "felics_pairs.h"
+#include "felics_frontout.h"
 
 namespace felics {
 
@@ -256,13 +257,20 @@ __device__ __forceinline__ uint32_t field_of(int v, int16_t) { return ((uint32_t
 //      counters end as the wave's event count per context;
 //   3. thread c turns the four waves' counts of context c into the tile's layout -- contexts in ascending order, within a
 //      context wave 0's events, then wave 1's ..., every context's run starting on a multiple of REC slots -- and writes the
-//      run table entry {first record, events} of (tile, c), the slots in use and the padding slots (pix = 0xFFFF);
-//   4. every wave moves its events to their places in the tile's sorted order in LDS (start of its context + rank);
-//   5. the workgroup writes the sorted tile out, 256 consecutive events per trip, to the tile's own place: slot
-//      (plane * ntiles + tile) * cap + s (felics_kernels.h: tile-local layout) -- no histogram pass, no offsets from other
-//      tiles.  Each event is compared with its successor: (context, pixel offset) must ascend strictly.  That is exactly
-//      "stable partition": the set of events of a context is fixed by the counts, and ascending pixel offsets are the one
-//      raster order of that set.  A violation raises TL_FLAG_ORDER; the host then redoes the batch with ranks from ballots.
+//      run table entry {first record, events} of (tile, c) and the slots in use; every (wave, context) cursor becomes the SLOT
+//      where that wave's events of the context begin (felics_frontout.h);
+//   4. every wave moves its events to their slots in LDS (cursor + rank); srt was all ones before, so a slot nothing is placed
+//      at is a padding slot and the sorted tile in LDS is the output image, padding included;
+//   5. the workgroup copies it out, four consecutive slots per thread and pass (one 16-byte LDS read, one store of four values,
+//      one of four pix; an all-ones entry gives pix = 0xFFFF), to the tile's own place: slot (plane * ntiles + tile) * cap + s
+//      (felics_kernels.h: tile-local layout) -- no histogram pass, no offsets from other tiles.  Each entry is compared with
+//      the entry in the next slot: within a run (context, pixel offset) must ascend strictly.  That is exactly "stable
+//      partition": the set of events of a context and the run's place are fixed by the counts, and ascending pixel offsets are
+//      the one raster order of that set.  A violation raises TL_FLAG_ORDER; the host then redoes the batch with ranks from ballots.
+//      A tile of more than SORT_TILE slots (noise) does not fit srt: it keeps the events' own order there (cursors in events, a
+//      sentinel behind the last), steps 3 and 5 write its padding slots and its events apart, 256 events per pass with narrow
+//      stores, through a per-context table of where the run lies among the slots (gdst) -- the form every tile took before
+//      FELICS_FORMS bit 256;
 //   BALLOT (the launcher's mode & FRONT_SAFE_RANK picks the instantiation): ranks from ballots instead of the returning add (a
 //   context's fallback once the order check has failed: no assumption about the LDS); mode & FRONT_TEST_VIOLATION, read once
 //   behind the loops: report a violation whatever the order (tests).
@@ -280,8 +288,10 @@ __device__ __forceinline__ uint32_t field_of(int v, int16_t) { return ((uint32_t
 //   32 group_codes_k by pairs (k_pack_t's k path)           64 group_codes_w by pairs (its word path)
 // and of profiles/latency_forms.txt (memory round trips taken off a tile's path):
 //   128 k_front: every trip of a wave's quarter in flight (8-bit samples)
+// and of profiles/front_out.txt (felics_frontout.h: the sorted tile in LDS in slot order, padding included):
+//   256 k_front: step 4 places an event at its slot, step 5 copies four slots per store
 #ifndef FELICS_FORMS
-#define FELICS_FORMS 255
+#define FELICS_FORMS 511
 #endif
 #ifndef FELICS_FRONT_WAVES
 #define FELICS_FRONT_WAVES 6  // (gray planes; what the LDS allows.  A/B builds: profiles/tools/variant.sh)
@@ -358,11 +368,16 @@ __attribute__((amdgpu_waves_per_eu(sizeof(T) == 1 ? FELICS_FRONT_WAVES : 5))) __
     constexpr uint32_t QUARTER = SORT_TILE / 4, TRIPS = QUARTER / 256;
     constexpr uint32_t PER = NC / 256;  // contexts per thread in step 3
     constexpr uint32_t KEY = 0xFFC00FFFu;  // context and pixel offset of a record
+    static_assert(KEY == felics::FRONTOUT_KEY && REC == felics::FRONTOUT_REC, "felics_frontout.h speaks of the same record");
     static_assert(SORT_TILE % 1024 == 0 && SORT_TILE <= (1u << 12), "four whole trips per wave; 12 bits of pixel offset");
     static_assert(NC % 256 == 0 && NC <= 512, "a thread takes NC / 256 contexts; 9 bits of context");
-    __shared__ uint32_t srt[SORT_TILE + 1 + 256];  // the tile's events, contexts ascending, raster order inside, a sentinel behind the last; [.. + 1 + thread]: where slots without an event are "placed"
+    constexpr bool SLOT_ORDER = (FELICS_FORMS & 256) != 0;  // srt holds the tile's slots, not its events: steps 3 to 5 below
+    // the tile's events, contexts ascending, raster order inside, a sentinel behind the last; [.. + 1 + thread]: where slots without an
+    // event are "placed".  SLOT_ORDER, a tile of at most SORT_TILE slots: the tile's slots, padding slots all ones; [SORT_TILE]: all
+    // ones, the successor of the last slot
+    __shared__ alignas(16) uint32_t srt[SORT_TILE + 1 + 256];
     __shared__ uint32_t cnt[4][NC + 64];      // per wave and context: count, then cursor into srt; [NC + lane]: what slots without an event count on
-    __shared__ uint32_t gdst[NC];             // a context's run: its place among the tile's slots minus its place in srt
+    __shared__ uint32_t gdst[NC];             // (srt in the events' order) a context's run: its place among the tile's slots minus its place in srt
     __shared__ uint32_t wsum[4];
 #ifdef FELICS_FRONT_STAMPS
     unsigned long long f_acc[15] = {}, f_last = __builtin_amdgcn_s_memtime();
@@ -582,6 +597,13 @@ __attribute__((amdgpu_waves_per_eu(sizeof(T) == 1 ? FELICS_FRONT_WAVES : 5))) __
             }
         }
     }
+    // (SLOT_ORDER: the window all ones before anything is placed -- a slot no event is placed at is a padding slot.  Here, behind the
+    // classification and in front of the barriers of step 3)
+    if constexpr (SLOT_ORDER) {
+#pragma unroll
+        for (uint32_t k = 0; k < SORT_TILE / 1024; k++) reinterpret_cast<uint4 *>(srt)[k * 256 + tid] = make_uint4(~0u, ~0u, ~0u, ~0u);
+        if (tid == 0) srt[SORT_TILE] = 0xFFFFFFFFu;
+    }
     FSTAMP(8);
     __syncthreads();
     FSTAMP(9);
@@ -589,6 +611,11 @@ __attribute__((amdgpu_waves_per_eu(sizeof(T) == 1 ? FELICS_FRONT_WAVES : 5))) __
     // half: the context's place in srt) and the slots in front (high half: every run rounded up to whole records)
     const uint64_t pt = (uint64_t)plane * ntiles + tile;
     uint32_t padpos[PER], nev_c[PER];
+    // SLOT_ORDER: whether this tile's srt holds its slots -- a tile of at most SORT_TILE slots, nearly every one.  A larger tile (noise;
+    // the worst-case caps are 7936 and 11776 slots) keeps the events' order in srt and the out stage that goes with it: to go
+    // through srt a window of slots at a time, the records and ranks would have to stay in registers across the windows, and
+    // the u8 kernels have none to spare at their cap (profiles/front_out.txt)
+    bool in_slots = false;
     {
         uint32_t n[4][PER], tot = 0;
 #pragma unroll
@@ -599,31 +626,42 @@ __attribute__((amdgpu_waves_per_eu(sizeof(T) == 1 ? FELICS_FRONT_WAVES : 5))) __
                 n[w][u] = cnt[w][tid * PER + u];
                 nev_c[u] += n[w][u];
             }
-            tot += nev_c[u] | (((nev_c[u] + REC - 1u) & ~(REC - 1u)) << 16);
+            tot += felics::frontout_layout_term(nev_c[u]);
         }
         const uint32_t incl = wave_incl_scan(tot);  // (no carry between the halves: at most 4096 events)
         if (lane == 63) wsum[wave] = incl;
         __syncthreads();
         uint32_t at = incl - tot;
         for (uint32_t w = 0; w < wave; w++) at += wsum[w];
+        if constexpr (SLOT_ORDER) in_slots = felics::frontout_one_window((wsum[0] + wsum[1] + wsum[2] + wsum[3]) >> 16, SORT_TILE);
 #pragma unroll
         for (uint32_t u = 0; u < PER; u++) {
             const uint32_t c = tid * PER + u;
             uint32_t cs = at & 0xFFFFu;
             const uint32_t ps = at >> 16;
             padpos[u] = ps;
-            gdst[c] = ps - cs;
+            if (SLOT_ORDER && in_slots) {
+                // the cursors are slots: the context's first slot + the events of the waves in front (felics_frontout.h)
+                const uint32_t nw[4] = {n[0][u], n[1][u], n[2][u], n[3][u]};
+                uint32_t cursor[4];
+                felics::frontout_slot_bases(at, nw, cursor);
 #pragma unroll
-            for (uint32_t w = 0; w < 4; w++) {
-                cnt[w][c] = cs;
-                cs += n[w][u];
+                for (uint32_t w = 0; w < 4; w++) cnt[w][c] = cursor[w];
+            } else {
+                gdst[c] = ps - cs;
+#pragma unroll
+                for (uint32_t w = 0; w < 4; w++) {
+                    cnt[w][c] = cs;
+                    cs += n[w][u];
+                }
             }
-            at += nev_c[u] | (((nev_c[u] + REC - 1u) & ~(REC - 1u)) << 16);
+            at += felics::frontout_layout_term(nev_c[u]);
         }
     }
     const uint32_t both = wsum[0] + wsum[1] + wsum[2] + wsum[3];
     const uint32_t total = both & 0xFFFFu, slots = both >> 16;
-    if (tid == 0) srt[total] = 0xFFFFFFFFu;  // larger than any record's key: the last event has a successor to be compared with
+    if (!in_slots)
+        if (tid == 0) srt[total] = 0xFFFFFFFFu;  // larger than any record's key: the last event has a successor to be compared with
     const bool fits = slots <= cap;  // (if not: nothing of the tile is written, the host redoes the batch with the worst-case cap)
     if (fits) {
         // the run table, context-major (a chain reads its row of tiles; the tiles of a plane run in order on one XCD, so the
@@ -631,10 +669,12 @@ __attribute__((amdgpu_waves_per_eu(sizeof(T) == 1 ? FELICS_FRONT_WAVES : 5))) __
         uint32_t *rt = runtab + ((uint64_t)plane * NC + tid * PER) * ntiles + tile;
 #pragma unroll
         for (uint32_t u = 0; u < PER; u++) rt[(uint64_t)u * ntiles] = (padpos[u] / REC) | (nev_c[u] << 16);
-        uint16_t *px = pix + pt * cap;
+        if (!in_slots) {  // (in_slots: step 5 writes the padding slots with the events around them)
+            uint16_t *px = pix + pt * cap;
 #pragma unroll
-        for (uint32_t u = 0; u < PER; u++)
-            for (uint32_t i = nev_c[u]; i < ((nev_c[u] + REC - 1u) & ~(REC - 1u)); i++) px[padpos[u] + i] = 0xFFFFu;
+            for (uint32_t u = 0; u < PER; u++)
+                for (uint32_t i = nev_c[u]; i < ((nev_c[u] + REC - 1u) & ~(REC - 1u)); i++) px[padpos[u] + i] = 0xFFFFu;
+        }
         if (tid == 0) tile_slots[pt] = slots;
     } else {  // (an empty run table: the chain stage finds nothing of this tile)
         uint32_t *rt = runtab + ((uint64_t)plane * NC + tid * PER) * ntiles + tile;
@@ -648,7 +688,7 @@ __attribute__((amdgpu_waves_per_eu(sizeof(T) == 1 ? FELICS_FRONT_WAVES : 5))) __
     __syncthreads();
     FSTAMP(12);
     // ---- 4. place: where the context's events of this wave start + the event's rank among them (a slot without an event: a
-    // place of this thread's own behind the tile)
+    // place of this thread's own behind the tile).  in_slots: that place is the event's slot
 #pragma unroll
     for (uint32_t q0 = 0; q0 < SLOTS; q0 += 8) {
         uint32_t at[8];
@@ -664,7 +704,34 @@ __attribute__((amdgpu_waves_per_eu(sizeof(T) == 1 ? FELICS_FRONT_WAVES : 5))) __
     FSTAMP(13);
     // ---- 5. out, checked: (context, pixel offset) must ascend strictly -- exactly "stable partition by context"
     uint32_t bad = mode & FRONT_TEST_VIOLATION;
-    if (fits) {
+    if (SLOT_ORDER && in_slots) {
+        // srt is the output image, padding included.  A thread takes four consecutive slots a pass: one 16-byte LDS read and the
+        // entry behind them, one store of four values, one of four pixel offsets (cap and slots are multiples of REC: the stores
+        // are aligned and no four are partial).  Each entry is compared with the entry in the next slot: within a run (context,
+        // pixel offset) must ascend strictly -- the ranks' raster order, all that is not fixed by the counts (felics_frontout.h)
+        if (fits) {
+            char *evo = reinterpret_cast<char *>(ev + pt * cap);
+            char *pxo = reinterpret_cast<char *>(pix + pt * cap);
+            bool unordered = false;  // (wave-wide in a scalar register pair until the loop is over)
+            for (uint32_t g = tid; 4u * g < slots; g += 256u) {
+                uint32_t g_ = g;
+                asm volatile("" : "+v"(g_));  // (named here: a 32-bit offset from the tile's scalar bases, no 64-bit address per store)
+                const uint32_t j = 4u * g_;
+                uint4 e = *reinterpret_cast<const uint4 *>(&srt[j]);
+                const uint32_t nxt = srt[j + 4u];  // (srt[SORT_TILE]: all ones)
+                asm volatile("" : "+v"(e.x), "+v"(e.y), "+v"(e.z), "+v"(e.w));  // (read once)
+                if constexpr (sizeof(ET) == 1)
+                    *reinterpret_cast<uint32_t *>(evo + j) = felics::frontout_ev_u8(e.x, e.y, e.z, e.w);
+                else
+                    *reinterpret_cast<uint2 *>(evo + 2u * j) = make_uint2(felics::frontout_ev_u16(e.x, e.y), felics::frontout_ev_u16(e.z, e.w));
+                *reinterpret_cast<uint2 *>(pxo + 2u * j) = make_uint2(felics::frontout_pix_pair(e.x, e.y), felics::frontout_pix_pair(e.z, e.w));
+                const bool b0 = felics::frontout_pair_bad(e.x, e.y), b1 = felics::frontout_pair_bad(e.y, e.z);
+                const bool b2 = felics::frontout_pair_bad(e.z, e.w), b3 = felics::frontout_pair_bad(e.w, nxt);
+                unordered |= b0 | b1 | b2 | b3;
+            }
+            bad |= unordered ? 1u : 0u;
+        }
+    } else if (fits) {
         ET *evo = ev + pt * cap;
         uint16_t *pxo = pix + pt * cap;
         for (uint32_t j = tid; j < total; j += 256) {
